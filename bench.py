@@ -6,8 +6,14 @@ reference, src/Main.cpp:838-848) over a synthetic compacted de Bruijn graph whos
 CSR adjacency and k-mer count table are already resident in HBM; graph generation, GFA/KMC
 parsing, upload and Unitig_Id writing are outside the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--unitigs U]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--unitigs U] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (`value`, `ms_per_step`, ...).  --full adds what
+the headline does not need, outside the timed region: the same steps without the join, the per-kernel table with every launch
+timed and the rooflines built on it, the K-COV probe, the twelve files against the committed reference digests, the sharded
+files against a pass of rank 0 alone, and the CPU baseline (--no-cpu-baseline leaves that out).  --dump-outputs DIR writes
+what the last timed step computed as DIR/<name>.npy (dump_outputs).
 
 N > 1: one process per GPU, ONE graph (BASELINE.json configs[2]: "5 M-unitig ... 1->8 MI355X scaling"), replicated in every
 GPU's HBM (ploidyfrost_amd/dist.py).  PloidyEstimation -- two thirds of a pass -- is cut over the ranks: each rank aligns, formats
@@ -329,7 +335,11 @@ def main():
                          "(a 250 k sample with chromosome-long traversals takes 75 s, the 5 M graph 700 s)")
     ap.add_argument("--cpu-runs", type=int, default=3)
     ap.add_argument("--host-threads", type=int, default=0, help="host threads per rank (0 = min(32, cpus/ranks))")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baseline out")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check what the headline does not need (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64; a fixed, seeded sample of a large file)")
     ap.add_argument("--gen-in-process", action="store_true",
                     help="make the inputs in this process instead of a child (for runs under rocprofv3, which must not have children)")
     ap.add_argument("--keep", action="store_true")
@@ -348,6 +358,8 @@ def main():
                          "k=31, -z 16, insertions up to 50 bp (K-BUBBLE's traceback is the phase), 10 M unitigs (--unitigs 1000000: the "
                          "setting whose reference digests are committed)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     wl = WORKLOADS[args.workload]
     if not args.unitigs:
         args.unitigs = wl["unitigs"]
@@ -566,6 +578,10 @@ def main():
             dist.barrier()
         elapsed = time.perf_counter() - t0
         tt = run.times()
+        # what the last timed step left, before any further pass of --full: the files of one graph over several ranks are
+        # complete after the barrier above
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, os.path.join(workdir, "PloidyFrost_output"), "b", tt)
         def kernel_times():   # kernel times from HIP events recorded by the library on the launches' own streams
             kt, ku = {}, {}
             for i, name in enumerate(hipapi.KERNELS):
@@ -586,7 +602,7 @@ def main():
         L.pf_timing_select(ctx, 0)   # the second region is timed as a whole only
         # the same K steps without the join (the pass over the joined coverage array alone), timed the same way
         elapsed_excl, step_s_excl = None, []
-        if join_in_step[0]:
+        if join_in_step[0] and args.full:
             join_in_step[0] = False
             if world > 1:
                 dist.barrier()
@@ -605,29 +621,31 @@ def main():
         # the kernel table and the device-busy time (the union of the launches' intervals: the pipeline runs kernels side by side, so
         # the per-kernel sums overlap): further passes, every launch timed, outside the timed region
         TABLE_PASSES = max(1, min(5, args.steps))
-        L.pf_timing_select(ctx, (1 << 64) - 1)
-        L.pf_reset_timing(ctx)
-        torch.cuda.synchronize()
-        t_tab = time.perf_counter()
-        for _ in range(TABLE_PASSES):
-            step()
-        torch.cuda.synchronize()
-        table_elapsed = time.perf_counter() - t_tab
-        if world > 1:
-            dist.barrier()
-        busy_ms, span_ms = C.c_double(), C.c_double()
-        L.pf_device_busy(ctx, C.byref(busy_ms), C.byref(span_ms))
-        # ... and without the copies of the result text to the host (the runtime moves them with a kernel of its own on the device:
-        # rocprofv3 lists it as __amd_rocclr_copyBuffer; the library times them as "copy_text_to_host")
-        busy_own = C.c_double()
-        copy_bit = 1 << hipapi.KERNELS.index("copy_text_to_host")
-        L.pf_kernel_busy(ctx, ((1 << len(hipapi.KERNELS)) - 1) & ~copy_bit, C.byref(busy_own))
-        ktimes, kunits = kernel_times()
+        ktimes, kunits, table_elapsed, busy_ms, busy_own = {}, {}, None, None, None
+        if args.full:
+            L.pf_timing_select(ctx, (1 << 64) - 1)
+            L.pf_reset_timing(ctx)
+            torch.cuda.synchronize()
+            t_tab = time.perf_counter()
+            for _ in range(TABLE_PASSES):
+                step()
+            torch.cuda.synchronize()
+            table_elapsed = time.perf_counter() - t_tab
+            if world > 1:
+                dist.barrier()
+            busy_ms, span_ms = C.c_double(), C.c_double()
+            L.pf_device_busy(ctx, C.byref(busy_ms), C.byref(span_ms))
+            # ... and without the copies of the result text to the host (the runtime moves them with a kernel of its own on the device:
+            # rocprofv3 lists it as __amd_rocclr_copyBuffer; the library times them as "copy_text_to_host")
+            busy_own = C.c_double()
+            copy_bit = 1 << hipapi.KERNELS.index("copy_text_to_host")
+            L.pf_kernel_busy(ctx, ((1 << len(hipapi.KERNELS)) - 1) & ~copy_bit, C.byref(busy_own))
+            ktimes, kunits = kernel_times()
 
         # outside the timed region: C1 computed the other way (every k-mer probed in the hash table, what K-COV-JOIN does once
         # at load) -- its duration, and that both routes agree on this graph
         probe = None
-        if rank == 0 and not colored:
+        if rank == 0 and not colored and args.full:
             import numpy as np
             res = [(np.zeros(n_unitigs, np.uint64), np.zeros(n_unitigs, np.uint32), np.zeros(n_unitigs, np.uint8)) for _ in range(2)]
             L.pf_reset_timing(ctx)
@@ -647,13 +665,13 @@ def main():
         output_check = None
         if world > 1:
             dist.barrier()
-        if rank == 0:
+        if rank == 0 and args.full:
             output_check = check_outputs(os.path.join(workdir, "PloidyFrost_output"), "b", n_unitigs, seed, args.workload)
             log("output check: %s" % output_check)
 
         # one graph over several ranks: hold the shared files against a pass of rank 0 alone, once, outside the timed region
         sharded_identical = None
-        if strong and not args.no_verify:
+        if strong and not args.no_verify and args.full:
             if rank == 0:
                 import hashlib
                 shared = os.path.join(workdir, "PloidyFrost_output")
@@ -783,7 +801,7 @@ def main():
             except (OSError, IndexError):
                 output_fs = "?"
             cpu = None
-            if not args.no_cpu_baseline and not colored:
+            if args.full and not args.no_cpu_baseline and not colored:
                 cpu = cpu_baseline(workdir, args.cpu_sample_unitigs, dev, args.cpu_runs, args.workload, n_unitigs)
             out = {
                 "metric": "unitigs/s through superbubble+SeqAlign (k=%d, z=%d)" % (wl["k"], Z),
@@ -838,16 +856,18 @@ def main():
                 "roofline": dom_roof, "roofline_k_bubble": roof if dom_roof is not roof else None,
                 "roofline_issue": issue_roofline(dom, kernels[dom]["avg_ms"], n_unitigs, kernels[dom]) if dom else None,
                 "roofline_k_cov": roof_cov, "roofline_k_cov_join": roof_join, "cpu_baseline": cpu,
-                "gpu_kernel_ms_per_step": round(sum(e["ms_per_step"] for n_, e in kernels.items() if n_ != "copy_text_to_host"), 3),
+                "gpu_kernel_ms_per_step": round(sum(e["ms_per_step"] for n_, e in kernels.items() if n_ != "copy_text_to_host"), 3) if args.full else None,
                 # union of the launches' [start, end] intervals (HIP events on their streams) over the timed passes / passes;
                 # tools/summarize_prof.py gives the same figure from the rocprofv3 kernel trace (profiles/*_device_busy.json)
                 # (of the table passes, where every launch carries events; their own wall time is the denominator)
-                "device_busy_ms_per_step": round(busy_ms.value / TABLE_PASSES, 3),
-                "device_busy_frac": round(busy_ms.value / (table_elapsed * 1e3), 4),
-                "device_busy_frac_own_kernels_only": round(busy_own.value / (table_elapsed * 1e3), 4),
+                "device_busy_ms_per_step": round(busy_ms.value / TABLE_PASSES, 3) if args.full else None,
+                "device_busy_frac": round(busy_ms.value / (table_elapsed * 1e3), 4) if args.full else None,
+                "device_busy_frac_own_kernels_only": round(busy_own.value / (table_elapsed * 1e3), 4) if args.full else None,
                 "kernel_table": {"passes": TABLE_PASSES, "ms_per_pass_with_every_launch_timed": round(table_elapsed / TABLE_PASSES * 1e3, 2),
                                  "note": "inside the timed region only the roofline kernels' launches carry HIP events (" + ", ".join(sorted(ktimes_live)) +
-                                         "); the other rows of `kernels`, gpu_kernel_ms_per_step and device_busy_* are from these further passes"},
+                                         "); the other rows of `kernels`, gpu_kernel_ms_per_step and device_busy_* are from these further passes"}
+                                if args.full else None,
+                "full": bool(args.full),
                 "first_pass": first_pass, "load_s": round(load_s, 3), "load_breakdown": load_breakdown,
                 "output_check": output_check, "sharded_output_check": sharded_identical,
                 "kernels": kernels, "k_cov_probe": probe,
@@ -948,6 +968,68 @@ def check_outputs(outdir: str, prefix: str, n_unitigs: int, seed: int, workload:
     return {"files": len(ent["files"]), "identical_to_reference": not differing, "differing": differing,
             "digest_source": "profiles/reference_digests.json: md5 of what oracle/_ref/PloidyFrost -t 1 wrote for this graph (%d unitigs, seed %d; "
                              "run on %s, %s, by tools/reference_digests.py)" % (n_unitigs, seed, ent.get("host", "?"), ent.get("date", "?"))}
+
+
+# --dump-outputs: the files a step writes (the load writes <prefix>_Unitig_Id.txt, outside the step), and how much of each is kept
+DUMP_FILES = ["super_bubble", "alignseq", "allele_frequency", "bicov", "bifre", "tricov", "trifre", "tetracov", "tetrafre",
+              "pentacov", "pentafre"]
+DUMP_ROWS = 1 << 16          # lines of a longer file: a sample drawn with DUMP_SEED
+DUMP_BYTES = 4 << 20         # values of one file at most (and DUMP_ROWS line numbers): 11 files stay well under 64 MB
+DUMP_SEED = 20261016
+COUNTERS = ["unitigs", "candidates", "superbubbles", "tasks", "align_jobs", "site_strings", "output_bytes"]
+NUMBER = re.compile(rb"[-+]?(?:\d+\.?\d*|\.\d+)(?:[eE][-+]?\d+)?")
+
+
+def _field(f: bytes) -> float:
+    """one tab-separated field as a number: as written where it is a decimal number, else the CRC-32 of its bytes (strand,
+    sequence, header, nan)"""
+    if NUMBER.fullmatch(f):
+        return float(f)
+    import zlib
+    return float(zlib.crc32(f))
+
+
+def dump_outputs(dest: str, outdir: str, prefix: str, tt: dict) -> None:
+    """What a caller of the timed path receives from a step -- the files findSuperBubble and PloidyEstimation wrote and the run's
+    counters -- as float64 arrays, so that two builds can be held against each other output for output:
+      <name>.npy       one row per line of <prefix>_<name>.txt, one column per tab-separated field (_field; a short row is padded
+                       with NaN); a file of more than DUMP_ROWS lines, or of more than DUMP_BYTES of values, is represented by a
+                       sample of its lines drawn with a fixed seed
+      <name>_rows.npy  the 0-based numbers of those lines
+      counters.npy     COUNTERS, the sites with 2..5 alleles, then the line count of every file of DUMP_FILES
+    A file the step left empty (no site with five alleles, say) has no arrays: its line count, 0, is in counters.npy."""
+    os.makedirs(dest, exist_ok=True)
+    line_counts = []
+    written = 1
+    for name in DUMP_FILES:
+        with open(os.path.join(outdir, "%s_%s.txt" % (prefix, name)), "rb") as fh:
+            raw = fh.read()
+        buf = np.frombuffer(raw, dtype=np.uint8)
+        ends = np.flatnonzero(buf == ord("\n"))
+        if len(buf) and buf[-1] != ord("\n"):
+            ends = np.append(ends, len(buf))
+        starts = np.concatenate(([0], ends[:-1] + 1)) if len(ends) else ends
+        n = len(ends)
+        line_counts.append(n)
+        if not n:
+            for stale in (name + ".npy", name + "_rows.npy"):   # (of an earlier dump into the same folder)
+                if os.path.exists(os.path.join(dest, stale)):
+                    os.remove(os.path.join(dest, stale))
+            continue
+        pick = np.random.default_rng(DUMP_SEED).permutation(n)[:DUMP_ROWS]
+        rows = {int(i): raw[starts[i]:ends[i]].rstrip(b"\t").split(b"\t") for i in pick}
+        width = max((len(r) for r in rows.values()), default=0)
+        keep = np.sort(pick[:max(1, DUMP_BYTES // (8 * max(width, 1)))])
+        vals = np.full((len(keep), width), np.nan, dtype=np.float64)
+        for j, i in enumerate(keep):
+            r = rows[int(i)]
+            vals[j, :len(r)] = [_field(f) for f in r]
+        np.save(os.path.join(dest, name + ".npy"), vals)
+        np.save(os.path.join(dest, name + "_rows.npy"), keep.astype(np.float64))
+        written += 2
+    counters = [tt[c] for c in COUNTERS] + list(tt["allele"]) + line_counts
+    np.save(os.path.join(dest, "counters.npy"), np.asarray(counters, dtype=np.float64))
+    log("outputs of the last timed step: %d files in %s" % (written, dest))
 
 
 def issue_roofline(kernel: str, avg_ms: float, n_unitigs: int, entry: dict | None = None):

@@ -341,3 +341,33 @@ def test_bench_cov_roofline_picks_the_streaming_kernel_of_the_workload():
     assert b["kernel"] == "k_cov_colored" and b["frac"] == 0.3 and b["traffic"] is None
     assert bench.cov_roofline({"k_bfs": {"avg_ms": 1.0}}, False, 123) is None
     assert bench.algorithmic_bytes("k_cov", {"kmers": 64, "unitigs": 2}) == 64 * (4 + 1 / 8 + 1 / 16) + 32
+
+
+def test_bench_dump_outputs_is_a_fixed_sample_of_the_result_files(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float64 rows of the result files as written, the same lines on every call, counters last."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_ROWS", 50)
+    src = os.path.join(ROOT, "tests", "golden", "tet60k", "expected")
+    tt = {c: i + 1 for i, c in enumerate(bench.COUNTERS)}
+    tt["allele"] = [365, 7, 2, 0]
+    (tmp_path / "b").mkdir()
+    (tmp_path / "b" / "pentacov.npy").write_bytes(b"stale")
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), src, "g", tt)
+    for name in bench.DUMP_FILES:
+        lines = open(os.path.join(src, "g_%s.txt" % name), "rb").read().splitlines()
+        if not lines:   # g_pentacov.txt, g_pentafre.txt: no array of an empty file, and none left of an earlier dump
+            assert not any(os.path.exists(str(tmp_path / d / (name + x))) for d in ("a", "b") for x in (".npy", "_rows.npy"))
+            continue
+        vals, rows = np.load(str(tmp_path / "a" / (name + ".npy"))), np.load(str(tmp_path / "a" / (name + "_rows.npy")))
+        assert vals.dtype == np.float64 and len(vals) == len(rows) == min(len(lines), 50)
+        assert np.array_equal(vals, np.load(str(tmp_path / "b" / (name + ".npy"))), equal_nan=True)
+        for v, i in zip(vals, rows.astype(int)):
+            f = lines[i].rstrip(b"\t").split(b"\t")
+            assert [bench._field(x) for x in f] == list(v[:len(f)])
+    bicov = np.load(str(tmp_path / "a" / "bicov.npy"))
+    assert bicov.shape[1] == 7 and bicov[:, 0].max() > 1.0   # coverages as numbers, not hashes
+    counters = np.load(str(tmp_path / "a" / "counters.npy"))
+    assert list(counters[:len(bench.COUNTERS) + 4]) == list(range(1, len(bench.COUNTERS) + 1)) + [365, 7, 2, 0]
+    assert list(counters[len(bench.COUNTERS) + 4:]) == [len(open(os.path.join(src, "g_%s.txt" % n), "rb").read().splitlines())
+                                                        for n in bench.DUMP_FILES]
