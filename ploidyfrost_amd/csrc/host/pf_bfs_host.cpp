@@ -154,4 +154,17 @@ const std::vector<uint32_t> &HugeWalker::walk(const uint32_t *succ, const uint32
     return list;
 }
 
+void WalkerPool::walk(const uint32_t *succ, const uint32_t *pred, uint32_t N, uint32_t entrance, pf_bfs_record &r, std::vector<uint32_t> &out) {
+    std::unique_ptr<HugeWalker> w;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        if (!walkers_.empty()) { w = std::move(walkers_.back()); walkers_.pop_back(); }
+    }
+    if (!w) w = std::make_unique<HugeWalker>();
+    r.list_off = 0;
+    const std::vector<uint32_t> &list = w->walk(succ, pred, N, entrance, r);
+    out.assign(list.begin(), list.begin() + r.n_list);
+    add(std::move(w));
+}
+
 }  // namespace pfh

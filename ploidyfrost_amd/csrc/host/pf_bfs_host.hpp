@@ -13,6 +13,8 @@
 // per-traversal epoch (the strand of a `seen` entry is that of its first sighting: which oriented vertex the entry stands for).
 #pragma once
 #include <cstdint>
+#include <memory>
+#include <mutex>
 #include <vector>
 
 #include "ploidyfrost_hip.h"
@@ -28,6 +30,20 @@ struct HugeWalker {
     // walks from the oriented vertex s over the CSR rows (4 slots per oriented vertex, PF_NONE = empty); fills every field
     // of `r` except list_off and returns the list the replay needs (seen[] when an exit was found, the cycle set otherwise)
     const std::vector<uint32_t> &walk(const uint32_t *succ, const uint32_t *pred, uint32_t n_unitigs, uint32_t s, pf_bfs_record &r);
+};
+
+// The walkers of one graph, shared by the threads that walk its long traversals.  A walker keeps 4 bytes of state per unitig, so
+// they are kept from walk to walk and from pass to pass; the pool grows to as many as ever walked side by side.
+class WalkerPool {
+public:
+    // One traversal on a walker taken from the pool (a new one when all are out), its list into `out`.  HugeWalker::walk writes
+    // every field of `r` but list_off, which is set to 0 here: a record needs no other preparation, whatever it held before.
+    void walk(const uint32_t *succ, const uint32_t *pred, uint32_t n_unitigs, uint32_t entrance, pf_bfs_record &r, std::vector<uint32_t> &out);
+    void add(std::unique_ptr<HugeWalker> w) { std::lock_guard<std::mutex> lk(mu_); walkers_.push_back(std::move(w)); }
+    size_t size() { std::lock_guard<std::mutex> lk(mu_); return walkers_.size(); }   // walkers at rest in the pool
+private:
+    std::vector<std::unique_ptr<HugeWalker>> walkers_;
+    std::mutex mu_;
 };
 
 }  // namespace pfh

@@ -165,8 +165,7 @@ int CDBG::init_device(int device, pf_ctx *adopt, bool colored) {
                 made[i]->seen.reserve(1u << 18);
                 made[i]->todo.reserve(1u << 12);
             });
-            std::lock_guard<std::mutex> lk(walkers_mu_);
-            for (auto &w : made) walkers_.push_back(std::move(w));
+            for (auto &w : made) walkers_.add(std::move(w));
         });
     }
     if (g_.numbering_deferred) {
@@ -229,7 +228,7 @@ void CDBG::start_prealloc() {
         prealloc_call_ = std::thread([this, est, piece, N, call_buffers] {
             LoadTrace trace;
             uint64_t n_cand = 0;   // findSuperBubble's buffers first: it is the first to run
-            if (commits_on_device(1) && pf_count_candidates(ctx_, 0, N, &n_cand) == PF_OK) {
+            if (commits_on_device() && pf_count_candidates(ctx_, 0, N, &n_cand) == PF_OK) {
                 trace.mark("reserve: candidates counted");
                 (void)pf_find_reserve(ctx_, n_cand);
                 trace.mark("reserve: findSuperBubble's buffers");

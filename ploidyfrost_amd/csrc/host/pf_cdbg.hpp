@@ -84,6 +84,8 @@ private:
     bool ctx_known_ = false;
 };
 
+struct FindTrace;   // pf_cdbg_impl.hpp
+
 class CDBG {
 public:
     CDBG(UnitigSet &graph, const size_t &complexsize, double &m, double &d, double &g, std::string kmc_db = "",
@@ -179,7 +181,8 @@ protected:
 
     struct Task;
     using clk_time = std::chrono::steady_clock::time_point;
-    int finish_find(const std::string &outpre, const size_t &thr, clk_time t_all, bool write_file);
+    // timing_lines: the `Cpu time` / `Real time` pair of findSuperBubble's stdout goes first
+    int finish_find(const std::string &outpre, const FindTrace &tr, bool write_file, bool timing_lines);
     std::vector<pf_bfs_record> shard_rec_;
     std::vector<uint32_t> shard_pool_;
     pf_call_result slice_res_ = {};
@@ -230,14 +233,29 @@ protected:
     bool colours_on_device_ = false;   // colored path: pf_replay_set_colours succeeded
     bool colored_resident_ = false;    // colored path: pf_call_set_colours succeeded -- the calling phase runs on the resident pipeline
     std::vector<uint8_t> big_f2_;
-    bool commits_on_device(size_t thr) const;
-    int find_superbubbles_device(const std::string &outpre, const size_t &thr);
+    bool commits_on_device() const;
     ParallelReplay par_;
     unsigned replay_threads(size_t thr) const;
+    size_t host_threads(size_t thr) const;     // set_threads, else the call's `thr` argument
+    unsigned walk_threads(size_t thr) const;   // ... of which so many may walk long traversals side by side
+    void set_record_stats(const ReplayStats &s);
+    // the steps of findSuperBubble (pf_cdbg_find.cpp): with the commits on the device ...
+    struct EarlyWalks; struct DeviceFind; struct SlicedFind;
+    int find_superbubbles_device(const std::string &outpre, const size_t &thr);
+    int traverse_resident(EarlyWalks &early, DeviceFind &df, const FindTrace &tr);
+    void walk_remaining(EarlyWalks &early, DeviceFind &df, const FindTrace &tr, unsigned threads);
+    void walked_into_candidate_order(DeviceFind &df);
+    int commit_large_on_host(DeviceFind &df, const FindTrace &tr, unsigned threads);
+    int patch_device_state(const std::vector<uint32_t> &sides, const FindTrace &tr, unsigned threads);
+    // ... and with the commits on the host: the device thread's side of the sliced pass
+    void traverse_slices(SlicedFind &sf, const FindTrace &tr);
+    int traverse_slice(SlicedFind &sf, int i, const FindTrace &tr);
+    void walk_long(const FindTrace &tr, bool say_start, uint32_t entrance, pf_bfs_record &r, std::vector<uint32_t> &out);
+    template <class Call> int with_deferred(uint64_t &n_deferred, Call call);
+    template <class ListOf> void replay_sequential(const pf_bfs_record *rec, uint64_t n, ListOf list_of, ReplayStats &stats);
     // third K-BFS tier (traversals beyond 4096 vertices) on host cores, pf_bfs_host.hpp; false = the device's k_bfs_huge
     bool third_tier_on_host_ = true;
-    std::vector<std::unique_ptr<HugeWalker>> walkers_;
-    std::mutex walkers_mu_;
+    WalkerPool walkers_;
     std::vector<uint32_t> deferred_;   // record indices pf_bfs_candidates_split leaves to the host walkers
     std::vector<uint32_t> deferred_ent_;   // their entrances (pf_bfs_candidates_begin)
     // vertex lists of the records walked on the host (pf_bfs_record::pad_ == 1, list_off = index), per K-BFS slice: a slice's

@@ -6,6 +6,9 @@
 #include <charconv>
 #include <chrono>
 #include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <ctime>
 #include <string>
 
 #include "pf_cdbg.hpp"
@@ -36,6 +39,15 @@ inline void put_uint(std::string &s, uint64_t x) {
     s.append(buf, (size_t)(r.ptr - buf));
 }
 }  // namespace
+
+// What one findSuperBubble call measures itself by and traces to stderr: built once per call (the PF_TRACE_* seams are read here,
+// not from the worker threads) and handed to its steps.
+struct FindTrace {
+    const clk::time_point t_all = clk::now();
+    const clock_t cpu0 = clock();
+    const bool find = getenv("PF_TRACE_FIND") != nullptr, bfs = getenv("PF_TRACE_BFS") != nullptr;
+    void step(const char *what) const { if (find) fprintf(stderr, "[find] %-28s %.2f ms\n", what, since(t_all) * 1e3); }
+};
 
 // len bytes of src into the file at file_off, by `threads` threads side by side.  Concurrent write()s to ONE file serialise on
 // the inode lock (tmpfs and ext4 alike), so a 400 MB result file written in pieces by 32 threads moves at the speed of one;

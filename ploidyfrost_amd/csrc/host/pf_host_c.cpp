@@ -403,15 +403,16 @@ uint32_t pfh_gfa_numbering_replays(const char *gfa_path) {
         return ~0u;
     }
 }
+// (the walkers of the two test hooks below: the pool the product's paths walk through, pf_bfs_host.hpp)
+static pfh::WalkerPool g_walkers;
 int pfh_host_walk(const uint32_t *succ, const uint32_t *pred, uint32_t n_unitigs, uint32_t entrance, pf_bfs_record *record, uint32_t *list,
                   uint64_t list_cap) {
     if (!succ || !pred || !record || n_unitigs == 0 || (entrance >> 1) >= n_unitigs) return 1;
     try {
-        static thread_local pfh::HugeWalker walker;
-        const std::vector<uint32_t> &l = walker.walk(succ, pred, n_unitigs, entrance, *record);
-        record->list_off = 0;
+        static thread_local std::vector<uint32_t> l;
+        g_walkers.walk(succ, pred, n_unitigs, entrance, *record, l);
         if (record->n_list > list_cap) return 2;
-        if (list) std::copy(l.begin(), l.begin() + record->n_list, list);
+        if (list) std::copy(l.begin(), l.end(), list);
         return 0;
     } catch (const std::exception &e) {
         g_open_err = std::string("ploidyfrost host layer: ") + e.what();
@@ -422,7 +423,7 @@ uint64_t pfh_host_walk_range(const uint32_t *succ, const uint32_t *pred, uint32_
                              pf_bfs_record *records, uint64_t rec_cap, uint32_t *pool, uint64_t pool_cap, uint64_t *pool_used) {
     if (!succ || !pred || u0 > u1 || u1 > n_unitigs) return ~0ull;
     try {
-        pfh::HugeWalker walker;
+        std::vector<uint32_t> l;
         uint64_t n = 0, used = 0;
         bool fits = true;
         for (uint32_t ov = 2 * u0; ov < 2 * u1; ++ov) {
@@ -430,12 +431,11 @@ uint64_t pfh_host_walk_range(const uint32_t *succ, const uint32_t *pred, uint32_
             for (int b = 0; b < 4; ++b) deg += succ[(size_t)ov * 4 + b] != 0xFFFFFFFFu;
             if (deg < 2) continue;
             pf_bfs_record r;
-            memset(&r, 0, sizeof(r));
-            const std::vector<uint32_t> &l = walker.walk(succ, pred, n_unitigs, ov, r);
+            g_walkers.walk(succ, pred, n_unitigs, ov, r, l);
             r.list_off = used;
             if (n < rec_cap && used + r.n_list <= pool_cap && records && pool) {
                 records[n] = r;
-                std::copy(l.begin(), l.begin() + r.n_list, pool + used);
+                std::copy(l.begin(), l.end(), pool + used);
             } else {
                 fits = false;
             }

@@ -65,14 +65,44 @@ private:
     const ColourGate *gate_ = nullptr;
 };
 
+// What a replay reports of the traversals beyond 4096 unitigs (PhaseTimes::bfs_large ... bfs_large_used_max), one pass's worth.
 struct ReplayStats {
     uint64_t large = 0, large_seen = 0, max_seen = 0, large_used = 0, large_used_max = 0;
+    // one record on its way through a replay; takes_effect = the gate let it through to its commit
+    void note(const pf_bfs_record &r, bool takes_effect) {
+        if (r.n_seen > max_seen) max_seen = r.n_seen;
+        if (r.n_seen > 4096) { large++; large_seen += r.n_seen; }
+        if (r.n_seen > 4096 && takes_effect) { large_used++; large_used_max = std::max<uint64_t>(large_used_max, r.n_seen); }
+    }
     void merge(const ReplayStats &o) {
         large += o.large; large_seen += o.large_seen; large_used += o.large_used;
         max_seen = std::max(max_seen, o.max_seen);
         large_used_max = std::max(large_used_max, o.large_used_max);
     }
 };
+
+// The commits chase per-unitig state at random: what the records 12 and 6 places ahead of j in a replay of n records will touch is
+// pulled into cache.  rec_at(j) = the j-th record in the replay's order; flags[w * flag_stride] = unitig w's (first) flag byte.
+template <class RecAt, class ListOf>
+inline void prefetch_commit_state(size_t j, size_t n, RecAt rec_at, ListOf list_of, const uint8_t *flags, size_t flag_stride, const uint32_t *plus, const uint32_t *minus) {
+    if (j + 12 < n) {
+        const pf_bfs_record &nx = rec_at(j + 12);
+        __builtin_prefetch(list_of(nx));
+        __builtin_prefetch(&plus[nx.entrance >> 1]);
+        __builtin_prefetch(&minus[nx.entrance >> 1]);
+    }
+    if (j + 6 < n) {
+        const pf_bfs_record &nx = rec_at(j + 6);
+        const uint32_t *l = list_of(nx);
+        const uint32_t nl = nx.n_list < 6 ? nx.n_list : 6;
+        for (uint32_t q = 0; q < nl; ++q) {
+            const uint32_t w = l[q] >> 1;
+            __builtin_prefetch(&flags[flag_stride * w]);
+            __builtin_prefetch(&plus[w]);
+            __builtin_prefetch(&minus[w]);
+        }
+    }
+}
 
 class ParallelReplay {
 public:
@@ -97,31 +127,12 @@ public:
             const uint32_t *o = order + class_off[c];
             const size_t n = class_off[c + 1] - class_off[c];
             for (size_t j = 0; j < n; ++j) {
-                // the commits chase per-unitig state at random: pull the state of a record a few iterations ahead into cache
                 if (j + 32 < n) __builtin_prefetch(&rec[o[j + 32]]);
-                if (j + 12 < n) {
-                    const pf_bfs_record &nx = rec[o[j + 12]];
-                    __builtin_prefetch(list_of(nx));
-                    __builtin_prefetch(&plus_[nx.entrance >> 1]);
-                    __builtin_prefetch(&minus_[nx.entrance >> 1]);
-                }
-                if (j + 6 < n) {
-                    const pf_bfs_record &nx = rec[o[j + 6]];
-                    const uint32_t *l = list_of(nx);
-                    const uint32_t nl = nx.n_list < 6 ? nx.n_list : 6;
-                    for (uint32_t q = 0; q < nl; ++q) {
-                        const uint32_t w = l[q] >> 1;
-                        __builtin_prefetch(&f2_[2 * (size_t)w]);
-                        __builtin_prefetch(&plus_[w]);
-                        __builtin_prefetch(&minus_[w]);
-                    }
-                }
+                prefetch_commit_state(j, n, [&](size_t x) -> const pf_bfs_record & { return rec[o[x]]; }, list_of, f2_.data(), 2, plus_, minus_);
                 const pf_bfs_record &r = rec[o[j]];
-                if (r.n_seen > 4096) { st.large++; st.large_seen += r.n_seen; }
-                if (r.n_seen > st.max_seen) st.max_seen = r.n_seen;
-                if (!cm.gate_open(r.entrance)) continue;
-                if (r.n_seen > 4096) { st.large_used++; st.large_used_max = std::max<uint64_t>(st.large_used_max, r.n_seen); }
-                cm.replay(r, list_of(r));
+                const bool open = cm.gate_open(r.entrance);
+                st.note(r, open);
+                if (open) cm.replay(r, list_of(r));
             }
             std::lock_guard<std::mutex> lk(mu);
             stats.merge(st);

@@ -1765,31 +1765,23 @@ static int bfs_candidates_impl(pf_ctx *ctx, uint32_t u0, uint32_t u1, pf_bfs_rec
     uint32_t *d_wlist = (uint32_t *)ctx_ws(ctx, WS_BFS_WLIST, (n + 8) * 4);
     if (!d_wlist) return PF_ERR_HIP;
     unsigned int *d_nwlist = reinterpret_cast<unsigned int *>(small + 48);
-    constexpr bool thread_tier = true;
     // (PF_BFS_WAVE_CAP, read per call: measurements of where the wavefront tier should give up)
     const uint32_t wave_cap = [] { const char *e = getenv("PF_BFS_WAVE_CAP"); return e ? (uint32_t)std::max(16, std::min((int)BFS_LDS_CAP, atoi(e))) : BFS_LDS_CAP; }();
-    if (thread_tier) {
-        ctx_begin(ctx, PF_K_BFS_THREAD);
-        k_bfs_thread<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(ctx->d_succ, ctx->d_pred, ctx->d_cand, c0, c1, o, d_wlist, d_nwlist);
-        ctx_end(ctx);
-        const int grid = ctx_grid(ctx, (n / 4 + 64) * 64, 256, 8);
-        ctx_begin(ctx, PF_K_BFS);
-        k_bfs<<<grid, 256, 0, ctx->stream>>>(ctx->d_succ, ctx->d_pred, ctx->d_cand, c0, c1, o, d_wlist, d_nwlist, wave_cap);
-        ctx_end(ctx);
-    } else {
-        const int grid = ctx_grid(ctx, n * 64, 256, 8);
-        ctx_begin(ctx, PF_K_BFS);
-        k_bfs<<<grid, 256, 0, ctx->stream>>>(ctx->d_succ, ctx->d_pred, ctx->d_cand, c0, c1, o, nullptr, nullptr, wave_cap);
-        ctx_end(ctx);
-    }
+    ctx_begin(ctx, PF_K_BFS_THREAD);
+    k_bfs_thread<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(ctx->d_succ, ctx->d_pred, ctx->d_cand, c0, c1, o, d_wlist, d_nwlist);
+    ctx_end(ctx);
+    const int grid = ctx_grid(ctx, (n / 4 + 64) * 64, 256, 8);
+    ctx_begin(ctx, PF_K_BFS);
+    k_bfs<<<grid, 256, 0, ctx->stream>>>(ctx->d_succ, ctx->d_pred, ctx->d_cand, c0, c1, o, d_wlist, d_nwlist, wave_cap);
+    ctx_end(ctx);
     unsigned int n_def = 0, n_wl = 0, n_live = 0;
     PF_HIP(hipMemcpyAsync(&n_def, d_ndef, 4, hipMemcpyDeviceToHost, ctx->stream));
     if (o.live) PF_HIP(hipMemcpyAsync(&n_live, d_nlive, 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (ctx->timing && thread_tier) PF_HIP(hipMemcpyAsync(&n_wl, d_nwlist, 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (ctx->timing) PF_HIP(hipMemcpyAsync(&n_wl, d_nwlist, 4, hipMemcpyDeviceToHost, ctx->stream));
     PF_HIP(hipStreamSynchronize(ctx->stream));
     ctx->bfs_live_n = n_live;
-    ctx_units(ctx, PF_K_BFS, thread_tier ? n_wl : n);
-    if (thread_tier) ctx_units(ctx, PF_K_BFS_THREAD, n);
+    ctx_units(ctx, PF_K_BFS, n_wl);
+    ctx_units(ctx, PF_K_BFS_THREAD, n);
     int status = PF_OK;
     if (n_def && deferred) {
         // the caller walks everything that outgrew the LDS tier itself (a host core needs ~20 ns per vertex; the 4096-entry

@@ -302,6 +302,21 @@ def test_work_pool(tmp_path):
     assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout
 
 
+def test_walker_pool(tmp_path):
+    """The pool findSuperBubble's host paths (and pfh_host_walk*) walk the long traversals through, on its own (no GPU, no library
+    beyond pf_bfs_host.cpp): tests/cpp/test_walker_pool.cpp."""
+    import shutil
+    import subprocess
+    if not shutil.which("g++"):
+        pytest.skip("no g++")
+    exe = str(tmp_path / "test_walker_pool")
+    host = os.path.join(ROOT, "ploidyfrost_amd", "csrc", "host")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-pthread", "-I", host, "-I", os.path.join(ROOT, "include"),
+                    os.path.join(ROOT, "tests", "cpp", "test_walker_pool.cpp"), os.path.join(host, "pf_bfs_host.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], stdout=subprocess.PIPE, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout
+
+
 def test_packed_alignseq_round_trip(tmp_path):
     """alignseq.txt leaves the device packed (csrc/pf_alnpack.hpp) and becomes text in the host's writer: the host half on its own,
     tests/cpp/test_alnpack.cpp (the device half is held to the reference's files by every end-to-end test, both ways: PF_ALIGNSEQ_ASCII)."""
