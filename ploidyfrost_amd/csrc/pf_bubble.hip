@@ -843,8 +843,8 @@ int bubble_launch(pf_ctx *ctx, const BubbleLaunch &L, unsigned long long heads[4
     if (L.keep_heads) PF_HIP(hipMemsetAsync(small + 32, 0, 96, st));
     else PF_HIP(hipMemsetAsync(small, 0, 128, st));
     BubOut o;
-    o.res = L.res; o.text = L.otext; o.sites = L.osites; o.groups = L.ogroups; o.ilen = L.oilen;
-    o.text_cap = L.text_cap; o.site_cap = L.site_cap; o.group_cap = L.group_cap; o.ilen_cap = L.ilen_cap;
+    o.res = L.out.res; o.text = L.out.otext; o.sites = L.out.osites; o.groups = L.out.ogroups; o.ilen = L.out.oilen;
+    o.text_cap = L.out.text_cap; o.site_cap = L.out.site_cap; o.group_cap = L.out.group_cap; o.ilen_cap = L.out.ilen_cap;
     o.heads = reinterpret_cast<unsigned long long *>(small);
     o.n_retry = reinterpret_cast<unsigned int *>(small + 40);
     unsigned int *queue_heads = reinterpret_cast<unsigned int *>(small + 64);
@@ -1073,7 +1073,7 @@ int bubble_launch(pf_ctx *ctx, const BubbleLaunch &L, unsigned long long heads[4
             std::vector<pf_bubble_path> pp(std::min<uint32_t>(tk.n_paths, 12));
             if (!pp.empty()) PF_HIP(hipMemcpy(pp.data(), L.paths + tk.path_first, pp.size() * sizeof(pf_bubble_path), hipMemcpyDeviceToHost));
             pf_bubble_result rr;
-            PF_HIP(hipMemcpy(&rr, L.res + t, sizeof(rr), hipMemcpyDeviceToHost));
+            PF_HIP(hipMemcpy(&rr, L.out.res + t, sizeof(rr), hipMemcpyDeviceToHost));
             fprintf(stderr, "   slowest: task %u ticks %llu paths %u -> rows %u cols %u sites %u; lens", t, clk[t], tk.n_paths, rr.n_rows, rr.n_cols, rr.n_sites);
             for (auto &x : pp) fprintf(stderr, " %u", x.len);
             fprintf(stderr, "\n");
@@ -1081,7 +1081,7 @@ int bubble_launch(pf_ctx *ctx, const BubbleLaunch &L, unsigned long long heads[4
         }
     }
     PF_HIP(hipMemcpy(heads, o.heads, 32, hipMemcpyDeviceToHost));
-    if (status == PF_OK && (heads[0] > L.text_cap || heads[1] > L.site_cap || heads[2] > L.group_cap || heads[3] > L.ilen_cap)) {
+    if (status == PF_OK && (heads[0] > L.out.text_cap || heads[1] > L.out.site_cap || heads[2] > L.out.group_cap || heads[3] > L.out.ilen_cap)) {
         pf::CtxErr{ctx} = "pf_align_bubbles: output pools too small";
         status = PF_ERR_OVERFLOW;
     }
@@ -1175,16 +1175,16 @@ extern "C" int pf_align_bubbles(pf_ctx *ctx, const char *text, uint64_t text_len
     const bool dev_out = is_dev(results);
     BubbleLaunch L;
     if (dev_out) {
-        L.res = results; L.otext = out_text; L.osites = out_sites; L.ogroups = out_groups; L.oilen = out_ilen;
+        L.out.res = results; L.out.otext = out_text; L.out.osites = out_sites; L.out.ogroups = out_groups; L.out.oilen = out_ilen;
     } else {
-        L.res = (pf_bubble_result *)ctx_ws(ctx, WS_BUB_RES, (size_t)n_tasks * sizeof(pf_bubble_result));
-        L.otext = (char *)ctx_ws(ctx, WS_BUB_OTEXT, std::max<uint64_t>(text_cap, 1));
-        L.osites = (pf_bubble_site *)ctx_ws(ctx, WS_BUB_OSITES, std::max<uint64_t>(site_cap, 1) * sizeof(pf_bubble_site));
-        L.ogroups = (uint8_t *)ctx_ws(ctx, WS_BUB_OGROUPS, std::max<uint64_t>(group_cap, 1));
-        L.oilen = (uint32_t *)ctx_ws(ctx, WS_BUB_OILEN, std::max<uint64_t>(ilen_cap, 1) * 4);
-        if (!L.res || !L.otext || !L.osites || !L.ogroups || !L.oilen) return PF_ERR_HIP;
+        L.out.res = (pf_bubble_result *)ctx_ws(ctx, WS_BUB_RES, (size_t)n_tasks * sizeof(pf_bubble_result));
+        L.out.otext = (char *)ctx_ws(ctx, WS_BUB_OTEXT, std::max<uint64_t>(text_cap, 1));
+        L.out.osites = (pf_bubble_site *)ctx_ws(ctx, WS_BUB_OSITES, std::max<uint64_t>(site_cap, 1) * sizeof(pf_bubble_site));
+        L.out.ogroups = (uint8_t *)ctx_ws(ctx, WS_BUB_OGROUPS, std::max<uint64_t>(group_cap, 1));
+        L.out.oilen = (uint32_t *)ctx_ws(ctx, WS_BUB_OILEN, std::max<uint64_t>(ilen_cap, 1) * 4);
+        if (!L.out.res || !L.out.otext || !L.out.osites || !L.out.ogroups || !L.out.oilen) return PF_ERR_HIP;
     }
-    L.text_cap = text_cap; L.site_cap = site_cap; L.group_cap = group_cap; L.ilen_cap = ilen_cap;
+    L.out.text_cap = text_cap; L.out.site_cap = site_cap; L.out.group_cap = group_cap; L.out.ilen_cap = ilen_cap;
     L.text = d_text; L.paths = d_paths; L.tasks = d_tasks; L.n_tasks = n_tasks;
     L.match = match; L.mismatch = mismatch; L.gap = gap;
     uint32_t idx_off = 0;
@@ -1201,11 +1201,11 @@ extern "C" int pf_align_bubbles(pf_ctx *ctx, const char *text, uint64_t text_len
     int status = bubble_launch(ctx, L, heads);
     for (int x = 0; x < 4; ++x) used[x] = heads[x];
     if (!dev_out && status == PF_OK) {
-        PF_HIP(hipMemcpyAsync(results, L.res, (size_t)n_tasks * sizeof(pf_bubble_result), hipMemcpyDeviceToHost, st));
-        PF_HIP(hipMemcpyAsync(out_text, L.otext, (size_t)heads[0], hipMemcpyDeviceToHost, st));
-        PF_HIP(hipMemcpyAsync(out_sites, L.osites, (size_t)heads[1] * sizeof(pf_bubble_site), hipMemcpyDeviceToHost, st));
-        PF_HIP(hipMemcpyAsync(out_groups, L.ogroups, (size_t)heads[2], hipMemcpyDeviceToHost, st));
-        PF_HIP(hipMemcpyAsync(out_ilen, L.oilen, (size_t)heads[3] * 4, hipMemcpyDeviceToHost, st));
+        PF_HIP(hipMemcpyAsync(results, L.out.res, (size_t)n_tasks * sizeof(pf_bubble_result), hipMemcpyDeviceToHost, st));
+        PF_HIP(hipMemcpyAsync(out_text, L.out.otext, (size_t)heads[0], hipMemcpyDeviceToHost, st));
+        PF_HIP(hipMemcpyAsync(out_sites, L.out.osites, (size_t)heads[1] * sizeof(pf_bubble_site), hipMemcpyDeviceToHost, st));
+        PF_HIP(hipMemcpyAsync(out_groups, L.out.ogroups, (size_t)heads[2], hipMemcpyDeviceToHost, st));
+        PF_HIP(hipMemcpyAsync(out_ilen, L.out.oilen, (size_t)heads[3] * 4, hipMemcpyDeviceToHost, st));
         PF_HIP(hipStreamSynchronize(st));
     }
     return status;

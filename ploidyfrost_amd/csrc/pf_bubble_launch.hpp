@@ -39,6 +39,21 @@ __host__ __device__ inline int bubble_class(uint32_t l0, uint32_t lmax) {
     return kBubLdsClasses;
 }
 
+// Where finished bubbles are published, device memory: the result record of every task and four pools handed out by atomic heads
+// (bubble_pool_heads).  K-BUBBLE and the kernels of the resident pipeline that finish bubbles themselves share one block of it.
+struct RowPools {
+    pf_bubble_result *res = nullptr;
+    char *otext = nullptr;
+    uint64_t text_cap = 0;
+    pf_bubble_site *osites = nullptr;
+    uint64_t site_cap = 0;
+    uint8_t *ogroups = nullptr;
+    uint64_t group_cap = 0;
+    uint32_t *oilen = nullptr;
+    uint64_t ilen_cap = 0;
+    unsigned long long *heads = nullptr;   // [0] text, [1] sites, [2] groups, [3] ilen (bubble_launch takes its lane's own)
+};
+
 struct BubbleLaunch {
     // inputs, device memory
     const char *text = nullptr;
@@ -50,13 +65,7 @@ struct BubbleLaunch {
     uint64_t max_need = 0;            // largest bubble_need in the global-memory class
     uint64_t retry_need = 0;          // working storage bound for the retry tier
     double match = 2, mismatch = -1, gap = -3;
-    // outputs, device memory
-    pf_bubble_result *res = nullptr;
-    char *otext = nullptr;
-    pf_bubble_site *osites = nullptr;
-    uint8_t *ogroups = nullptr;
-    uint32_t *oilen = nullptr;
-    uint64_t text_cap = 0, site_cap = 0, group_cap = 0, ilen_cap = 0;
+    RowPools out;                     // outputs
     // the pool heads (bubble_pool_heads) already hold what an earlier kernel of the caller took from the pools: do not reset them
     bool keep_heads = false;
     // which set of K-BUBBLE's workspaces, class streams and events (the lane of the resident pipeline's pf_call_align_lane: calls on

@@ -20,31 +20,8 @@
 //                            as `ostream << double` does (pf_format_dev.hpp); bubble numbering (var_count) by a scan
 //
 // All integer / byte work with data-dependent control flow; HBM traffic is the text itself.  No MFMA.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <cmath>
-#include <cstddef>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "pf_bubble_launch.hpp"
-#include "pf_alnpack.hpp"
-#include "pf_call_dev.hpp"
-#include "pf_colored_dev.hpp"
-#include "pf_cov_stream.hpp"
-#include "pf_ctx.hpp"
-#include "pf_device_common.hpp"
-#include "pf_format_dev.hpp"
-#include "pf_pair_dev.hpp"
+#include "pf_call_kernels.hpp"
 #include "pf_scan.hpp"
-#include "pf_stack_dev.hpp"
-#include "ploidyfrost_hip.h"
 
 using namespace pf;
 
@@ -57,11 +34,17 @@ using namespace pf;
         }                                                                                    \
     } while (0)
 
-#define NEED_TEXT(buf, bytes) do { if (!(buf).ensure(bytes)) { pf::CtxErr{ctx} = "pf_call_text: out of device memory"; return PF_ERR_HIP; } } while (0)
-
-#include "pf_call_kernels.hpp"
+#define PF_TRY(call) do { const int s_ = (call); if (s_ != PF_OK) return s_; } while (0)
 
 using namespace pf_call;
+
+// every buffer of the list at least as large as asked, or "<who>: out of device memory"
+struct Need { DevBuf *buf; size_t bytes; };
+static int need(pf_ctx *ctx, const char *who, std::initializer_list<Need> list) {
+    for (const Need &n : list)
+        if (!n.buf->ensure(n.bytes)) { pf::CtxErr{ctx} = std::string(who) + ": out of device memory"; return PF_ERR_HIP; }
+    return PF_OK;
+}
 
 namespace pf {
 
@@ -430,7 +413,454 @@ int pf_call_select(pf_ctx *ctx, const uint32_t *side_index, uint64_t n_tasks) {
     return PF_OK;
 }
 
-// one batch, first half: bubbles [t0, t1) of the selection up to the site coverages; out->n_called tells how far var_count advances
+}  // extern "C"
+
+// =====================================================================================================================
+// One batch, first half (pf_call_align_lane): bubbles [t0, t1) of the selection up to the site coverages.  Every size comes from
+// pf_call_plan.hpp; pf_call_reserve_lanes takes the same buffers ahead of a first call through the same three functions.
+namespace {
+
+// everything sized by the number of bubbles alone: counters, tasks, work lists, result records, bubble numbering
+int ensure_batch_buffers(pf_ctx *ctx, const char *who, CallState::AlignWork &W, CallState::AlignOut &O, uint32_t nb) {
+    const size_t list = (size_t)nb * 4;
+    return need(ctx, who, {{&W.counters, sizeof(CallCounters)}, {&W.btask, (size_t)nb * sizeof(pf_bubble_task)}, {&W.queues, (size_t)NQ * list},
+                           {&W.blist, list}, {&W.slist, list}, {&W.plist, list}, {&W.plist2, list}, {&W.klist, list}, {&W.klist_b, list}, {&W.has, list},
+                           {&O.res, (size_t)nb * sizeof(pf_bubble_result)}, {&O.sv_off, (size_t)nb * 8}, {&O.vc, list}});
+}
+
+// per-wavefront scratch of the kernels whose grids loop over a list (K-PAIR's second tier and K-SITES size theirs when they run)
+int ensure_wave_scratch(pf_ctx *ctx, const char *who, CallState::AlignWork &W, const CallGrids &g, uint32_t depth, bool stack_tier, bool pair_tier) {
+    PF_TRY(need(ctx, who, {{&W.paths_scr, paths_per_wave(depth) * g.paths}}));
+    if (stack_tier) PF_TRY(need(ctx, who, {{&W.stack_scr, stack_scratch_bytes() * g.stack}}));
+    if (pair_tier) PF_TRY(need(ctx, who, {{&W.pair_scr, PairGeom<PAIR_MAX>::scratch_bytes * g.pair}}));
+    return PF_OK;
+}
+
+// the pools of an attempt: every one grows until the batch fits (first batches of a run only)
+int ensure_pools(pf_ctx *ctx, const char *who, CallState::AlignWork &W, CallState::AlignOut &O, uint32_t nb, const BatchPools &p) {
+    PF_TRY(need(ctx, who, {{&W.bpath, p.path_entries(nb) * sizeof(pf_bubble_path)}, {&W.ptext, p.path_text}, {&O.otext, p.row_text},
+                           {&O.osites, p.sites * sizeof(pf_bubble_site)}, {&O.ogroups, p.groups}, {&O.oilen, p.ilen * 4}}));
+    if (p.walk) PF_TRY(need(ctx, who, {{&W.walk_pool, p.walk * 4}, {&W.walk_off, (size_t)nb * 8}}));
+    return PF_OK;
+}
+
+// a lane's stream (lane 0 runs on the context's) and the side stream K-PATHS runs on beside K-SNP and K-PAIR, with its two events
+int ensure_lane_streams(pf_ctx *ctx, CallState::AlignWork &W, int lane) {
+    if (lane != 0 && !W.stream) { PF_HIP(lane_stream_create(&W.stream, lane)); W.own_stream = true; }
+    if (!W.side_stream) {
+        PF_HIP(lane_stream_create(&W.side_stream, lane));
+        PF_HIP(hipEventCreateWithFlags(&W.ev_prep, hipEventDisableTiming));
+        PF_HIP(hipEventCreateWithFlags(&W.ev_paths, hipEventDisableTiming));
+    }
+    return PF_OK;
+}
+
+// PF_PAIR_STATS / PF_SITES_STATS (diagnostics): a zeroed table of `words` counters for a launch to fill, and its read-back
+int stats_begin(pf_ctx *ctx, DevTmp<unsigned long long> &prof, size_t words, hipStream_t st, unsigned long long **arg) {
+    PF_HIP(prof.alloc(words * 8));
+    PF_HIP(hipMemsetAsync(prof.p, 0, words * 8, st));
+    *arg = prof.p;
+    return PF_OK;
+}
+int print_pair_stats(pf_ctx *ctx, const DevTmp<unsigned long long> &prof) {
+    unsigned long long h[8];
+    PF_HIP(hipMemcpy(h, prof.p, 64, hipMemcpyDeviceToHost));
+    fprintf(stderr, "[k_call_pair] %llu wavefront rounds; lane-0 ticks (10 ns): decode %llu fill %llu traceback %llu classify %llu publish %llu\n", h[5],
+            h[0], h[1], h[2], h[3], h[4]);
+    return PF_OK;
+}
+int print_sites_stats(pf_ctx *ctx, const DevTmp<unsigned long long> &prof, int grid, hipStream_t st) {
+    PF_HIP(hipStreamSynchronize(st));
+    std::vector<unsigned long long> h((size_t)grid * 6);
+    PF_HIP(hipMemcpy(h.data(), prof.p, h.size() * 8, hipMemcpyDeviceToHost));
+    unsigned long long sum[6] = {0, 0, 0, 0, 0, 0}, mx = 0;
+    for (int w = 0; w < grid; ++w) {
+        for (int x = 0; x < 6; ++x) sum[x] += h[(size_t)w * 6 + x];
+        mx = std::max(mx, h[(size_t)w * 6]);
+    }
+    fprintf(stderr, "[k_call_sites] %d wavefronts, %llu bubbles; ticks (10 ns) per wavefront: total %.0f (max %llu) = pop + load %.0f, strings %.0f, ranks + probes %.0f, groups %.0f\n",
+            grid, sum[5], (double)sum[0] / grid, mx, (double)sum[1] / grid, (double)sum[2] / grid, (double)sum[3] / grid, (double)sum[4] / grid);
+    return PF_OK;
+}
+
+int env_int(const char *name, int otherwise) { const char *e = getenv(name); return e ? atoi(e) : otherwise; }
+
+// What one pf_call_align_lane call traces to stderr: PF_TRACE_ALIGN is read once per call and serves every line of it.
+struct AlignTrace {
+    const bool on = getenv("PF_TRACE_ALIGN") != nullptr;
+    const std::chrono::steady_clock::time_point t_enter = std::chrono::steady_clock::now();
+    void stage(const char *what) const {   // where a call's time goes (a first call above all)
+        if (on) fprintf(stderr, "[pf_call_align]   %-34s %.2f ms\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_enter).count() * 1e3);
+    }
+};
+
+// One pf_call_align_lane call: what its stages share.  A stage returns a status; one that may find a pool too small sets *retry
+// after growing it, and the attempt starts over.
+struct AlignCall {
+    static constexpr const char *who = "pf_call_run";
+    pf_ctx *const ctx; CallState *const S;
+    CallState::AlignWork &W; CallState::AlignOut &O;
+    const int lane; const uint64_t t0; const uint32_t nb;
+    const double match, mismatch, gap;
+    const AlignTrace trace;
+    // which tiers the scores allow.  K-PAIR: scores of sane magnitude only (the fill adds them in ints)
+    const bool snp_ok = snp_shortcut_scores(match, mismatch, gap);
+    const bool pair_tier = std::fabs(match) < 1e5 && std::fabs(mismatch) < 1e5 && std::fabs(gap) < 1e5;
+    const bool pair_integral = match == std::floor(match) && mismatch == std::floor(mismatch) && gap == std::floor(gap);
+    const bool stack_tier = stack_scores(match, mismatch, gap);
+    // what K-STACK is given (read per call: tools/ab_pass.py): 1 = bubbles of three and more paths of one length, 2 = also those whose
+    // later paths are shorter than the first (one gap run each), 3 = also the two-path bubbles ahead of K-PAIR
+    const int stack_ok = stack_tier ? std::max(1, std::min(3, env_int("PF_STACK_LEVEL", 1))) : 0;
+    const int paths_force_scratch = env_int("PF_PATHS_SCRATCH", 0) ? 1 : 0;   // (read per call: tests)
+    const CallGrids grids = call_grids(ctx->n_cu);
+    const uint32_t depth;
+    hipStream_t st = nullptr;
+    CallCounters *d_cnt = nullptr;
+    // the blocks the kernels' arguments are assembled from: the first three per call, the pools per attempt
+    BatchRef batch = {};
+    GraphSeq graph = {};
+    CallLists lists = {};
+    RowPools pools;
+    BatchPools cap = {};
+    PathArgs ph = {};   // K-PATHS' launch: the launch for bubbles of more than 255 walks derives its own from it
+    PairArgs pr = {};   // K-PAIR's launch: the second tier derives its own from it
+    int attempt = 0;
+    CallCounters hc = {};
+    unsigned long long heads[4] = {0, 0, 0, 0};
+    uint64_t n_jobs = 0;
+    uint32_t n_called = 0;
+    size_t tl_at = (size_t)-1;   // launch timing by place: calls on other lanes time their launches at the same time
+
+    AlignCall(pf_ctx *c, int lane_, uint64_t t0_, uint32_t nb_, uint32_t complex_size, double m, double d, double g)
+        : ctx(c), S(c->call), W(c->call->work[lane_]), O(c->call->lane[lane_]), lane(lane_), t0(t0_), nb(nb_), match(m), mismatch(d), gap(g), depth(depth_cap(complex_size)) {}
+
+    void tbegin(int kernel, hipStream_t s) { (void)ctx_begin_at(ctx, kernel, s, &tl_at); }
+    void tend(hipStream_t s) { ctx_end_at(ctx, tl_at, s); }
+
+    int prepare() {
+        PF_TRY(ensure_lane_streams(ctx, W, lane));
+        st = lane == 0 ? ctx->stream : W.stream;   // (lane 0: the context's stream, whatever pf_set_stream made it since)
+        // the write pass of K-TEXT over what this lane held may still be running (pf_call_text_range_lane does not wait for it)
+        for (hipEvent_t e : O.read_ev) if (e) PF_HIP(hipStreamWaitEvent(st, e, 0));
+        // (another lane's stream needs no event to wait for: the scan and the selection on the context's stream ended in host waits --
+        // pf_call_resolve / pf_call_select hand the host the number of bubbles this call's range is cut from)
+        PF_TRY(ensure_batch_buffers(ctx, who, W, O, nb));
+        PF_TRY(ensure_wave_scratch(ctx, who, W, grids, depth, stack_tier, pair_tier));
+        // bubbles of more than 255 walks in one range: the list grows to what an attempt asked for (advisor, round 3: an overflow used
+        // to be reported as "more than 65535 paths", a refusal of a run no bubble of which had that many)
+        if (W.mlist_cap < MANY_LIST_MIN) W.mlist_cap = MANY_LIST_MIN;
+        PF_TRY(need(ctx, who, {{&W.mlist, (size_t)W.mlist_cap * 4}}));
+        d_cnt = W.counters.as<CallCounters>();
+        batch = BatchRef{S->ctask.as<CallTask>(), S->kept.as<uint32_t>(), t0, nb};
+        graph = GraphSeq{ctx->d_seq, ctx->d_off, ctx->d_len};
+        lists = CallLists{W.queues.as<uint32_t>(), W.blist.as<uint32_t>(), W.slist.as<uint32_t>(), W.plist.as<uint32_t>(), W.plist2.as<uint32_t>(), W.klist.as<uint32_t>(), W.klist_b.as<uint32_t>(), nb};
+        trace.stage("lists and scratch");
+        return PF_OK;
+    }
+
+    // the pools of this attempt, from the plan and what earlier batches learnt; counters and pool heads zeroed
+    int size_pools() {
+        LearntPools l;
+        l.path_pool = S->path_pool; l.path_text = S->text_pool; l.row_text = S->otext_cap; l.sites = S->osites_cap; l.groups = S->ogroups_cap; l.ilen = S->oilen_cap;
+        l.walk = W.walk_cap;
+        cap = batch_pools(nb, grids, l, S->n_colors != 0);
+        PF_TRY(ensure_pools(ctx, who, W, O, nb, cap));
+        unsigned long long *d_heads = bubble_pool_heads(ctx, lane);
+        if (!d_heads) return PF_ERR_HIP;
+        pools = RowPools{O.res.as<pf_bubble_result>(), O.otext.as<char>(), cap.row_text, O.osites.as<pf_bubble_site>(), cap.sites, O.ogroups.as<uint8_t>(), cap.groups,
+                         O.oilen.as<uint32_t>(), cap.ilen, d_heads};
+        PF_HIP(hipMemsetAsync(d_cnt, 0, sizeof(CallCounters), st));
+        PF_HIP(hipMemsetAsync(d_heads, 0, 32, st));
+        return PF_OK;
+    }
+
+    // K-PREP; K-PATHS on the side stream; K-SNP, K-STACK (strict list), K-PAIR; join; K-STACK (branching list)
+    int launch_tiers() {
+        PrepArgs pa;
+        pa.batch = batch; pa.len = graph.len; pa.btask = W.btask.as<pf_bubble_task>(); pa.bpath = W.bpath.as<pf_bubble_path>(); pa.res = pools.res;
+        pa.lists = lists; pa.snp_ok = snp_ok ? 1 : 0; pa.pair_ok = pair_tier ? 1 : 0; pa.stack_ok = stack_ok; pa.cnt = d_cnt;
+        tbegin(PF_K_CALL_PREP, st);
+        k_call_prep<<<(nb + 255) / 256, 256, 0, st>>>(pa);
+        tend(st);
+        // K-PATHS (branching bubbles) beside K-SNP and K-PAIR (two-path bubbles): latency-bound walks next to an issue-bound fill
+        hipStream_t pst = W.side_stream;
+        PF_HIP(hipEventRecord(W.ev_prep, st));
+        PF_HIP(hipStreamWaitEvent(pst, W.ev_prep, 0));
+        ph = PathArgs{};
+        ph.batch = batch; ph.blist = lists.blist; ph.succ = ctx->d_succ; ph.graph = graph; ph.k = ctx->k; ph.depth_cap = depth;
+        ph.scratch = W.paths_scr.as<uint8_t>(); ph.scratch_per_wave = paths_per_wave(depth); ph.force_scratch = paths_force_scratch;
+        ph.max_paths = MAX_PATHS; ph.n_list = &d_cnt->n_branching; ph.mlist = W.mlist.as<uint32_t>(); ph.mlist_cap = W.mlist_cap;
+        ph.walk_pool = S->n_colors ? W.walk_pool.as<uint32_t>() : nullptr; ph.walk_off = W.walk_off.as<uint64_t>(); ph.walk_cap = cap.walk;
+        ph.btask = pa.btask; ph.bpath = pa.bpath; ph.path_cap = cap.path_pool; ph.text = W.ptext.as<char>(); ph.text_cap = cap.path_text;
+        ph.queues = lists.queues; ph.klist = lists.klist_b; ph.stack_ok = stack_ok; ph.cnt = d_cnt;
+        tbegin(PF_K_CALL_PATHS, pst);
+        k_call_paths<false><<<grids.paths, 64, 0, pst>>>(ph);
+        tend(pst);
+        PF_HIP(hipEventRecord(W.ev_paths, pst));
+        if (snp_ok) {
+            SnpArgs sn;
+            sn.batch = batch; sn.slist = lists.slist; sn.graph = graph; sn.out = pools; sn.lists = lists; sn.pair_ok = pa.pair_ok; sn.stack_ok = stack_ok; sn.cnt = d_cnt;
+            tbegin(PF_K_CALL_SNP, st);
+            k_call_snp<<<(nb + 255) / 256, 256, 0, st>>>(sn);   // (the list length is on the device: surplus threads leave at once)
+            tend(st);
+        }
+        StackArgs sk;
+        if (stack_tier) {
+            // K-STACK, first launch: the strict bubbles K-PREP and K-SNP listed (two paths that are not a single mismatch, three and
+            // four paths); what it cannot certify is K-PAIR's (launched behind it) or K-BUBBLE's
+            sk.list = lists.klist; sk.n_list = &d_cnt->n_stack; sk.scratch = W.stack_scr.as<uint8_t>(); sk.pair_ok = pa.pair_ok;
+            sk.btask = pa.btask; sk.bpath = pa.bpath; sk.ptext = W.ptext.as<char>(); sk.graph = graph;
+            sk.M = (int)match; sk.D = (int)mismatch; sk.G = (int)gap;
+            sk.out = pools; sk.lists = lists; sk.cnt = d_cnt;
+            tbegin(PF_K_CALL_STACK, st);
+            k_call_stack<<<grids.stack, 64, 0, st>>>(sk);
+            tend(st);
+        }
+        if (pair_tier) {
+            // K-PAIR: the grid loops over its list
+            pr = PairArgs{};
+            pr.batch = batch; pr.graph = graph; pr.M = match; pr.D = mismatch; pr.G = gap; pr.Mi = (int)match; pr.Di = (int)mismatch; pr.Gi = (int)gap;
+            pr.list = lists.plist; pr.n_list = &d_cnt->n_pair; pr.n_done = &d_cnt->n_pair_done;
+            pr.scratch = W.pair_scr.as<uint8_t>(); pr.out = pools; pr.lists = lists; pr.cnt = d_cnt;
+            static const bool pair_stats = getenv("PF_PAIR_STATS") != nullptr;
+            DevTmp<unsigned long long> prof;
+            if (pair_stats) PF_TRY(stats_begin(ctx, prof, 8, st, &pr.prof));
+            tbegin(PF_K_CALL_PAIR, st);
+            if (pair_integral) k_call_pair<PAIR_MAX, true><<<grids.pair, 64, 0, st>>>(pr);
+            else k_call_pair<PAIR_MAX, false><<<grids.pair, 64, 0, st>>>(pr);
+            tend(st);
+            if (pair_stats) PF_TRY(print_pair_stats(ctx, prof));
+            pr.prof = nullptr;
+        }
+        PF_HIP(hipStreamWaitEvent(st, W.ev_paths, 0));
+        if (stack_tier) {
+            // K-STACK, second launch: the branching bubbles K-PATHS listed (their two-path rejects cannot go to K-PAIR, which reads
+            // the inner unitigs of a strict bubble: K-BUBBLE's)
+            sk.list = lists.klist_b; sk.n_list = &d_cnt->n_stack_b; sk.pair_ok = 0;
+            tbegin(PF_K_CALL_STACK, st);
+            k_call_stack<<<grids.stack, 64, 0, st>>>(sk);
+            tend(st);
+        }
+        return PF_OK;
+    }
+
+    // what the kernels launched so far counted: the one place the host waits for them
+    int read_counters() {
+        PF_HIP(hipGetLastError());
+        PF_HIP(hipMemcpyAsync(&hc, d_cnt, sizeof(hc), hipMemcpyDeviceToHost, st));
+        PF_HIP(hipStreamSynchronize(st));
+        return PF_OK;
+    }
+
+    // K-PAIR's second tier (paths of 65 .. 128 bases, or a longer indel than the first tier's band follows): few on most graphs, so
+    // its scratch and its launch wait until the host knows there are any; its rejects join K-BUBBLE's queues.  The counters are read
+    // once more behind it.
+    int launch_pair_tier2() {
+        if (!pair_tier || !hc.n_pair2) return PF_OK;
+        PairArgs p2 = pr;
+        p2.list = lists.plist2; p2.n_list = &d_cnt->n_pair2; p2.n_done = &d_cnt->n_pair2_done;
+        const uint32_t tier2_min = (uint32_t)env_int("PF_PAIR2_MIN", 0);   // (read per call: tests run the tier on a few bubbles)
+        if (hc.n_pair2 < (tier2_min ? tier2_min : pair2_min(ctx->n_cu))) {
+            k_call_pair2_reroute<<<(hc.n_pair2 + 255) / 256, 256, 0, st>>>(p2);
+        } else {
+            const int g2 = call_pair2_grid(hc.n_pair2, grids);
+            PF_TRY(need(ctx, who, {{&W.pair_scr2, PairGeom<PAIR_MAX2>::scratch_bytes * g2}}));
+            p2.scratch = W.pair_scr2.as<uint8_t>();
+            tbegin(PF_K_CALL_PAIR, st);
+            if (pair_integral) k_call_pair<PAIR_MAX2, true><<<g2, 64, 0, st>>>(p2);
+            else k_call_pair<PAIR_MAX2, false><<<g2, 64, 0, st>>>(p2);
+            tend(st);
+        }
+        return read_counters();
+    }
+
+    void note_units() const {
+        ctx_units(ctx, PF_K_CALL_PREP, nb);
+        if (snp_ok) ctx_units(ctx, PF_K_CALL_SNP, hc.n_snp);
+        if (pair_tier) ctx_units(ctx, PF_K_CALL_PAIR, hc.n_pair + hc.n_pair2);
+        if (stack_tier) ctx_units(ctx, PF_K_CALL_STACK, hc.n_stack + hc.n_stack_b);
+        ctx_units(ctx, PF_K_CALL_PATHS, hc.n_branching);
+        if (trace.on) fprintf(stderr, "[pf_call_align] bubbles of more than 255 walks: %u, err %u\n", hc.n_many, hc.err);
+    }
+
+    // bubbles of more than 255 walks: walked again by a few wavefronts with room for PATHS_BIG walks each, the counters read once more
+    // behind them -- once their list held them all
+    int launch_paths_big(bool *retry) {
+        if (!hc.n_many || (hc.err & ERR_WALK)) return PF_OK;
+        if (hc.n_many > W.mlist_cap) {
+            W.mlist_cap = grown_many(hc.n_many);
+            *retry = true;
+            return need(ctx, who, {{&W.mlist, (size_t)W.mlist_cap * 4}});
+        }
+        const int big_grid = paths_big_grid(hc.n_many);
+        const uint64_t big_per_wave = paths_big_per_wave(depth, PATHS_BIG);
+        PF_TRY(need(ctx, who, {{&W.paths_big_scr, big_per_wave * big_grid}}));
+        PathArgs pb = ph;
+        pb.blist = W.mlist.as<uint32_t>(); pb.n_list = &d_cnt->n_many; pb.max_paths = PATHS_BIG; pb.mlist = nullptr; pb.mlist_cap = 0;
+        pb.scratch = W.paths_big_scr.as<uint8_t>(); pb.scratch_per_wave = big_per_wave;
+        tbegin(PF_K_CALL_PATHS, st);
+        k_call_paths<true><<<big_grid, 64, 0, st>>>(pb);
+        tend(st);
+        return read_counters();
+    }
+
+    // every walk is in: a bubble K-PATHS gave up on ends the call; pools that were too small grow and the attempt is repeated
+    int accept_walks(bool *retry) {
+        if (hc.err & ERR_WALK) {
+            char where[96];
+            snprintf(where, sizeof where, " (superbubble from unitig %u%c to unitig %u%c)", (hc.err_entrance >> 1) + 1, (hc.err_entrance & 1) ? '-' : '+',
+                     (hc.err_exit >> 1) + 1, (hc.err_exit & 1) ? '-' : '+');
+            pf::CtxErr{ctx} = std::string(hc.err & ERR_MANY_PATHS ? "pf_call_run: a bubble has more than 65535 paths" : "pf_call_run: a bubble is deeper than the complex size allows") + where;
+            return PF_ERR_ARG;
+        }
+        amax(S->otext_cap, cap.row_text); amax(S->osites_cap, cap.sites);
+        amax(S->ogroups_cap, cap.groups); amax(S->oilen_cap, cap.ilen);
+        amax(S->path_pool, cap.path_pool);
+        amax(S->text_pool, cap.path_text);
+        // (the path text is handed out in per-wavefront chunks: its size varies by a few per mille from pass to pass, hence the margin)
+        const uint64_t rows_need = row_text_need(hc.text_head, hc.n_branching, nb);
+        if (trace.on)
+            fprintf(stderr, "[pf_call_align] attempt %d: %u bubbles, path pool %llu of %llu, path text %llu of %llu, rows text cap %llu (needs %llu)\n", attempt, nb,
+                    (unsigned long long)hc.path_head, (unsigned long long)cap.path_pool, (unsigned long long)hc.text_head, (unsigned long long)cap.path_text,
+                    (unsigned long long)cap.row_text, (unsigned long long)rows_need);
+        if (hc.path_head > cap.path_pool || hc.text_head > cap.path_text || hc.walk_head > cap.walk) {
+            amax(S->path_pool, grown(hc.path_head, 1024));
+            amax(S->text_pool, grown(hc.text_head, 4096));
+            if (S->n_colors) W.walk_cap = std::max<uint64_t>(W.walk_cap, grown(hc.walk_head, 1024));
+            *retry = true;
+            return PF_OK;
+        }
+        if (S->n_colors) W.walk_cap = std::max(W.walk_cap, cap.walk);
+        if (cap.row_text < rows_need) {   // make room before K-BUBBLE runs
+            amax(S->otext_cap, rows_need + rows_need / 16 + 4096);
+            *retry = true;
+        }
+        return PF_OK;
+    }
+
+    // K-BUBBLE over what the other kernels left in its queues
+    int run_bubble(bool *retry) {
+        n_jobs = 0;
+        for (int x = 0; x < NQ; ++x) n_jobs += hc.q_n[x];
+        // the queues are heavy-then-light per class; compact them into one index array
+        PF_TRY(need(ctx, who, {{&W.scan_tmp2, std::max<size_t>((size_t)n_jobs, 1) * 4}}));
+        uint32_t *d_idx = W.scan_tmp2.as<uint32_t>();
+        size_t at = 0;
+        for (int x = 0; x < NQ; ++x) {
+            if (!hc.q_n[x]) continue;
+            PF_HIP(hipMemcpyAsync(d_idx + at, W.queues.as<uint32_t>() + (size_t)x * nb, (size_t)hc.q_n[x] * 4, hipMemcpyDeviceToDevice, st));
+            at += hc.q_n[x];
+        }
+        BubbleLaunch BL;
+        BL.text = W.ptext.as<char>(); BL.paths = W.bpath.as<pf_bubble_path>(); BL.tasks = W.btask.as<pf_bubble_task>();
+        BL.n_tasks = nb; BL.idx = d_idx;
+        for (int c = 0; c <= kBubLdsClasses; ++c) BL.n_cls[c] = hc.q_n[2 * c] + hc.q_n[2 * c + 1];
+        BL.max_need = hc.max_need; BL.retry_need = hc.retry_need;
+        BL.match = match; BL.mismatch = mismatch; BL.gap = gap;
+        BL.out = pools;
+        BL.keep_heads = true;
+        BL.lane = lane; BL.stream = st;
+        trace.stage("K-BUBBLE launching");
+        const int bst = bubble_launch(ctx, BL, heads);
+        trace.stage("K-BUBBLE done");
+        if (trace.on)
+            fprintf(stderr, "[pf_call_align] attempt %d: K-BUBBLE status %d, pools text %llu of %llu, sites %llu of %llu, groups %llu of %llu, indel lengths %llu of %llu\n", attempt, bst,
+                    heads[0], (unsigned long long)cap.row_text, heads[1], (unsigned long long)cap.sites, heads[2], (unsigned long long)cap.groups, heads[3], (unsigned long long)cap.ilen);
+        if (bst == PF_ERR_OVERFLOW && (heads[0] > cap.row_text || heads[1] > cap.sites || heads[2] > cap.groups || heads[3] > cap.ilen)) {
+            amax(S->otext_cap, heads[0] + heads[0] / 8);
+            amax(S->osites_cap, heads[1] + heads[1] / 8);
+            amax(S->ogroups_cap, heads[2] + heads[2] / 8);
+            amax(S->oilen_cap, heads[3] + heads[3] / 8);
+            *retry = true;
+            return PF_OK;
+        }
+        return bst;
+    }
+
+    // bubble numbering inside the batch (launched ahead of K-SITES, read with its counters: one wait for both)
+    int number_called() {
+        k_call_has<<<(nb + 255) / 256, 256, 0, st>>>(O.res.as<pf_bubble_result>(), nb, W.has.as<uint32_t>());
+        PF_TRY(need(ctx, who, {{&W.scan_tmp, scan_scratch_bytes(nb)}}));
+        PF_HIP(scan_inclusive_u32(W.has.as<uint32_t>(), O.vc.as<uint32_t>(), nb, W.scan_tmp.p, st));
+        PF_HIP(hipMemcpyAsync(&n_called, O.vc.as<uint32_t>() + (nb - 1), 4, hipMemcpyDeviceToHost, st));
+        return PF_OK;
+    }
+
+    SiteArgs site_args(uint32_t ks, uint64_t rows_cap, uint64_t per_wave, uint64_t sv_cap) const {
+        SiteArgs sa;
+        sa.batch = batch; sa.blist = lists.blist; sa.res = pools.res; sa.otext = pools.otext; sa.osites = pools.osites; sa.ogroups = pools.ogroups;
+        sa.k = ctx->k; sa.tab = ctx->d_tab; sa.mask = ctx->tab_cap - 1; sa.one_strand = ctx->tab_one_strand; sa.tab_exact = ctx->tab_exact;
+        sa.low = S->low; sa.up = S->up; sa.ks = ks; sa.rows_cap = (uint32_t)rows_cap;
+        sa.scratch = W.sites_scr.as<uint8_t>(); sa.scratch_per_wave = per_wave; sa.sv_off = O.sv_off.as<uint64_t>();
+        sa.sv = O.sv.as<double>(); sa.sv_cap = sv_cap; sa.cnt = d_cnt; sa.prof = nullptr;
+        sa.n_colors = S->n_colors;
+        sa.ctab = CTab{ctx->d_ctab, ctx->ctab_cap - 1, ctx->ctab_line_bytes}; sa.c_one_strand = ctx->ctab_one_strand; sa.unread = ctx->d_unread;
+        sa.clow = S->col_low.as<uint32_t>(); sa.cup = S->col_up.as<uint32_t>(); sa.full = S->col_full.as<uint64_t>(); sa.cwords = S->col_words;
+        sa.part_first = S->part_first.as<uint32_t>(); sa.part_colour = S->part_colour.as<uint32_t>(); sa.part_word = S->part_word.as<uint64_t>();
+        sa.part_bits = S->part_bits.as<uint64_t>(); sa.walk_pool = W.walk_pool.as<uint32_t>(); sa.walk_off = W.walk_off.as<uint64_t>();
+        sa.graph = graph;
+        return sa;
+    }
+
+    // one K-SITES launch over the branching bubbles, and its counters (with n_called)
+    int launch_sites(SiteArgs &sa, int grid) {
+        static const bool sites_stats = getenv("PF_SITES_STATS") != nullptr;   // measurements: where a wavefront's time goes
+        DevTmp<unsigned long long> prof;
+        if (sites_stats) PF_TRY(stats_begin(ctx, prof, (size_t)grid * 6, st, &sa.prof));
+        PF_HIP(hipMemsetAsync(&d_cnt->sites_next, 0, 4, st));
+        PF_HIP(hipMemsetAsync(&d_cnt->sv_head, 0, 8, st));
+        PF_HIP(hipMemsetAsync(&d_cnt->site_strings, 0, 8, st));
+        tbegin(PF_K_CALL_SITES, st);
+        if (sa.n_colors) k_call_sites<true><<<grid, 64, 0, st>>>(sa);
+        else k_call_sites<false><<<grid, 64, 0, st>>>(sa);
+        tend(st);
+        ctx_units(ctx, PF_K_CALL_SITES, hc.n_branching);
+        if (sites_stats) { PF_HIP(hipGetLastError()); PF_TRY(print_sites_stats(ctx, prof, grid, st)); }
+        return read_counters();
+    }
+
+    // K-SITES
+    // (a site string is k characters long unless it takes the raw columns up to its row's end -- substr with a negative count,
+    // src/CDBG.cpp:1499 -- or more than k characters agree behind an indel: a launch that meets one longer than its room says how
+    // long, ks_need, and is repeated with that much)
+    int run_sites() {
+        uint32_t KS = std::max<uint32_t>(first_site_string(ctx->k), S->sites_ks.load());
+        const uint32_t C = S->n_colors;
+        const uint64_t rows_cap = sites_rows_cap(hc.max_rows);
+        for (int sv_attempt = 0, ks_attempt = 0;;) {
+            const uint64_t per_wave = sites_per_wave(rows_cap, KS, C, S->col_words);
+            const int grid = call_sites_grid(hc.n_branching, grids, per_wave);
+            const uint64_t sv_cap = site_values_cap(C, hc.n_branching, grid, S->sv_pool);
+            PF_TRY(need(ctx, who, {{&W.sites_scr, per_wave * grid}, {&O.sv, sv_cap * 8}}));
+            SiteArgs sa = site_args(KS, rows_cap, per_wave, sv_cap);
+            PF_TRY(launch_sites(sa, grid));
+            if (hc.err & ERR_SITE_LONG) {
+                if (++ks_attempt > 3 || hc.ks_need <= KS) { pf::CtxErr{ctx} = "pf_call_run: the room for a site string does not converge"; return PF_ERR_OVERFLOW; }
+                KS = grown_site_string(hc.ks_need);
+                amax(S->sites_ks, KS);
+                hc.err = 0; hc.ks_need = 0;   // (the other bits are looked at when every string had room: a string cut short has no verdict)
+                PF_HIP(hipMemsetAsync(&d_cnt->err, 0, 4, st));
+                PF_HIP(hipMemsetAsync(&d_cnt->ks_need, 0, 4, st));
+                continue;
+            }
+            if (hc.err & ERR_MISSING_KMER) { pf::CtxErr{ctx} = "CDBG::readCov(): a kmer of a site string can not found ."; return PF_ERR_MISSING_KMER; }
+            if (hc.err & ERR_SITE_ROW) { pf::CtxErr{ctx} = "CDBG::PloidyEstimation(): a site string runs past the end of an aligned row (the reference terminates here: std::out_of_range from substr, src/CDBG.cpp:1478-1590)"; return PF_ERR_ARG; }
+            if (hc.err & ERR_SITE_UNITIG) { pf::CtxErr{ctx} = "CCDBG::PloidyEstimation(): a site string does not start on a unitig of its bubble"; return PF_ERR_ARG; }
+            if (hc.sv_head > sv_cap) {
+                if (sv_attempt++ >= 2) { pf::CtxErr{ctx} = "pf_call_run: site value pool does not converge"; return PF_ERR_OVERFLOW; }
+                amax(S->sv_pool, grown(hc.sv_head, 1024));
+                continue;
+            }
+            amax(S->sv_pool, sv_cap);
+            return PF_OK;
+        }
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
 int pf_call_align_lane(pf_ctx *ctx, int lane, uint64_t t0, uint64_t t1, uint32_t complex_size, double match, double mismatch, double gap,
                        pf_call_result *out) {
     if (!ctx || !out || lane < 0 || lane >= PF_CALL_LANES) return PF_ERR_ARG;
@@ -444,432 +874,42 @@ int pf_call_align_lane(pf_ctx *ctx, int lane, uint64_t t0, uint64_t t1, uint32_t
     if (t1 == t0) return PF_OK;
     if (t1 - t0 > (1u << 24)) { pf::CtxErr{ctx} = "pf_call_align: at most 2^24 bubbles per batch"; return PF_ERR_ARG; }
     PF_HIP(hipSetDevice(ctx->device));
-    CallState::AlignWork &W = S->work[lane];
-    if (lane != 0 && !W.stream) { PF_HIP(lane_stream_create(&W.stream, lane)); W.own_stream = true; }
-    hipStream_t st = lane == 0 ? ctx->stream : W.stream;   // (lane 0: the context's stream, whatever pf_set_stream made it since)
-    // the write pass of K-TEXT over what this lane held may still be running (pf_call_text_range_lane does not wait for it)
-    for (hipEvent_t e : O.read_ev) if (e) PF_HIP(hipStreamWaitEvent(st, e, 0));
-    // (another lane's stream needs no event to wait for: the scan and the selection on the context's stream ended in host waits --
-    // pf_call_resolve / pf_call_select hand the host the number of bubbles this call's range is cut from)
-    // launch timing by place: calls on other lanes time their launches at the same time
-    size_t tl_at = (size_t)-1;
-    auto tbegin = [&](int kernel, hipStream_t s) { (void)ctx_begin_at(ctx, kernel, s, &tl_at); };
-    auto tend = [&](hipStream_t s) { ctx_end_at(ctx, tl_at, s); };
-    const uint32_t nb = (uint32_t)(t1 - t0);
-    const int k = ctx->k;
-    const bool trace_stages = getenv("PF_TRACE_ALIGN") != nullptr;   // where a call's time goes (a first call above all)
-    const auto t_enter = std::chrono::steady_clock::now();
-    auto ta = [&](const char *what) {
-        if (trace_stages) fprintf(stderr, "[pf_call_align]   %-34s %.2f ms\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_enter).count() * 1e3);
-    };
-    const char *oom = "pf_call_run: out of device memory";
-#define NEED(buf, bytes) do { if (!(buf).ensure(bytes)) { pf::CtxErr{ctx} = oom; return PF_ERR_HIP; } } while (0)
-    NEED(W.counters, sizeof(CallCounters));
-    NEED(W.btask, (size_t)nb * sizeof(pf_bubble_task));
-    NEED(W.queues, (size_t)NQ * nb * 4);
-    NEED(W.blist, (size_t)nb * 4);
-    NEED(O.res, (size_t)nb * sizeof(pf_bubble_result));
-    NEED(O.sv_off, (size_t)nb * 8);
-    NEED(W.has, (size_t)nb * 4);
-    NEED(O.vc, (size_t)nb * 4);
-    CallCounters *d_cnt = W.counters.as<CallCounters>();
-    CallCounters hc;
-    // K-PATHS scratch: stacks sized by the complex size (a non-complex bubble has at most that many vertices)
-    const uint32_t depth_cap = std::max<uint32_t>(complex_size + 4, 16);
-    const uint64_t paths_per_wave = ((256 * 8 + 256 * 4 + (10ull * depth_cap + 4) * 4) + 255) & ~255ull;
-    constexpr int paths_per_cu = 16;
-    const int paths_grid = ctx->n_cu * paths_per_cu;
-    NEED(W.paths_scr, paths_per_wave * paths_grid);
-    // bubbles of more than 255 walks in one range: the list grows to what an attempt asked for (advisor, round 3: an overflow used
-    // to be reported as "more than 65535 paths", a refusal of a run no bubble of which had that many)
-    if (W.mlist_cap < 4096) W.mlist_cap = 4096;
-    NEED(W.mlist, (size_t)W.mlist_cap * 4);
-    PathArgs ph_keep = {};
-    const int paths_force_scratch = [] { const char *e = getenv("PF_PATHS_SCRATCH"); return e && atoi(e) ? 1 : 0; }();   // (read per call: tests)
-
-    // ---- K-PREP, K-SNP, K-PATHS, K-BUBBLE; every pool grows until the batch fits (first batches of a run only) ----
-    NEED(W.slist, (size_t)nb * 4);
-    NEED(W.plist, (size_t)nb * 4);
-    NEED(W.plist2, (size_t)nb * 4);
-    NEED(W.klist, (size_t)nb * 4);
-    NEED(W.klist_b, (size_t)nb * 4);
-    const int snp_ok = snp_shortcut_scores(match, mismatch, gap) ? 1 : 0;
-    // K-PAIR: register-bound (the score row of the fill is 65 / 129 registers): 3 / 2 wavefronts per SIMD, the grid loops over its list
-    // (scores of sane magnitude only: the fill adds them in ints)
-    const bool pair_tier = std::fabs(match) < 1e5 && std::fabs(mismatch) < 1e5 && std::fabs(gap) < 1e5;
-    const bool stack_tier = stack_scores(match, mismatch, gap);
-    // what K-STACK is given (read per call: tools/ab_pass.py): 1 = bubbles of three and more paths of one length, 2 = also those whose
-    // later paths are shorter than the first (one gap run each), 3 = also the two-path bubbles ahead of K-PAIR
-    const int stack_level = [] { const char *e = getenv("PF_STACK_LEVEL"); return e ? std::max(1, std::min(3, atoi(e))) : 1; }();
-    const int stack_grid = ctx->n_cu * 8;
-    if (stack_tier) NEED(W.stack_scr, stack_scratch_bytes() * stack_grid);
-    const bool pair_integral = match == std::floor(match) && mismatch == std::floor(mismatch) && gap == std::floor(gap);
-    const int pair_grid = ctx->n_cu * 12, pair_grid2 = ctx->n_cu * 4;
-    if (pair_tier) NEED(W.pair_scr, PairGeom<PAIR_MAX>::scratch_bytes * pair_grid);
-    unsigned long long heads[4] = {0, 0, 0, 0};
-    uint64_t n_jobs = 0;
-    ta("lists and scratch");
-    for (int attempt = 0;; ++attempt) {
-        if (attempt > 5) { pf::CtxErr{ctx} = "pf_call_align: pools do not converge"; return PF_ERR_OVERFLOW; }
-        const uint64_t path_cap = std::max<uint64_t>(S->path_pool, (uint64_t)nb / 2 + 128ull * paths_grid + 1024);   // (a started piece per wavefront)
-        // (first-pass sizes, learnt afterwards; a pool that turns out too small costs a repeated attempt -- at configs[4]'s parameters,
-        // k = 31 and insertions to 50 bp, a whole K-BUBBLE run thrown away: 334 B of rows, 2.4 sites, 8 group bytes, 1.1 indel lengths
-        // and 55 B of path text per bubble there; 216 B / 1.2 / 2.7 / 0.03 / 17 B at configs[2]'s)
-        const uint64_t text_cap = std::max<uint64_t>(S->text_pool, (uint64_t)nb * FIRST_PATH_TEXT + (1u << 16));
-        const uint64_t cap_text = std::max<uint64_t>(S->otext_cap, (uint64_t)FIRST_ROW_TEXT * nb + (1u << 16));
-        const uint64_t cap_sites = std::max<uint64_t>(S->osites_cap, (uint64_t)FIRST_SITES * nb + 64);
-        const uint64_t cap_groups = std::max<uint64_t>(S->ogroups_cap, (uint64_t)FIRST_GROUPS * nb + 64);
-        const uint64_t cap_ilen = std::max<uint64_t>(S->oilen_cap, (uint64_t)FIRST_ILEN * nb + 64);
-        NEED(W.bpath, ((size_t)4 * nb + path_cap) * sizeof(pf_bubble_path));
-        NEED(W.ptext, text_cap);
-        const uint64_t walk_cap = S->n_colors ? std::max<uint64_t>(W.walk_cap, (uint64_t)nb * 2 + 256ull * paths_grid + 1024) : 0;
-        if (S->n_colors) {
-            NEED(W.walk_pool, walk_cap * 4);
-            NEED(W.walk_off, (size_t)nb * 8);
-        }
-        NEED(O.otext, cap_text);
-        NEED(O.osites, cap_sites * sizeof(pf_bubble_site));
-        NEED(O.ogroups, cap_groups);
-        NEED(O.oilen, cap_ilen * 4);
-        unsigned long long *d_heads = bubble_pool_heads(ctx, lane);
-        if (!d_heads) return PF_ERR_HIP;
-        PF_HIP(hipMemsetAsync(d_cnt, 0, sizeof(CallCounters), st));
-        PF_HIP(hipMemsetAsync(d_heads, 0, 32, st));
-        PrepArgs pa;
-        pa.ct = S->ctask.as<CallTask>(); pa.kept = S->kept.as<uint32_t>(); pa.t0 = t0; pa.nb = nb; pa.len = ctx->d_len;
-        pa.btask = W.btask.as<pf_bubble_task>(); pa.bpath = W.bpath.as<pf_bubble_path>(); pa.res = O.res.as<pf_bubble_result>();
-        pa.lists = CallLists{W.queues.as<uint32_t>(), W.blist.as<uint32_t>(), W.slist.as<uint32_t>(), W.plist.as<uint32_t>(), W.plist2.as<uint32_t>(), W.klist.as<uint32_t>(), W.klist_b.as<uint32_t>(), nb};
-        pa.snp_ok = snp_ok;
-        pa.pair_ok = pair_tier ? 1 : 0;
-        pa.stack_ok = stack_tier ? stack_level : 0;
-        pa.cnt = d_cnt;
-        tbegin(PF_K_CALL_PREP, st);
-        k_call_prep<<<(nb + 255) / 256, 256, 0, st>>>(pa);
-        tend(st);
-        // K-PATHS (branching bubbles) beside K-SNP and K-PAIR (two-path bubbles): latency-bound walks next to an issue-bound fill
-        constexpr bool fork_paths = true;
-        hipStream_t pst = st;
-        if (fork_paths) {
-            if (!W.side_stream) {
-                PF_HIP(lane_stream_create(&W.side_stream, lane));
-                PF_HIP(hipEventCreateWithFlags(&W.ev_prep, hipEventDisableTiming));
-                PF_HIP(hipEventCreateWithFlags(&W.ev_paths, hipEventDisableTiming));
-            }
-            pst = W.side_stream;
-            PF_HIP(hipEventRecord(W.ev_prep, st));
-            PF_HIP(hipStreamWaitEvent(pst, W.ev_prep, 0));
-        }
-        {
-            PathArgs ph;
-            ph.ct = pa.ct; ph.kept = pa.kept; ph.t0 = t0; ph.nb = nb; ph.blist = pa.lists.blist; ph.succ = ctx->d_succ; ph.seq = ctx->d_seq;
-            ph.off = ctx->d_off; ph.len = ctx->d_len; ph.k = k; ph.depth_cap = depth_cap; ph.scratch = W.paths_scr.as<uint8_t>();
-            ph.scratch_per_wave = paths_per_wave; ph.force_scratch = paths_force_scratch; ph.btask = pa.btask; ph.bpath = pa.bpath; ph.path_cap = path_cap;
-            ph.text = W.ptext.as<char>(); ph.text_cap = text_cap; ph.queues = pa.lists.queues; ph.cnt = d_cnt;
-            ph.klist = pa.lists.klist_b; ph.stack_ok = pa.stack_ok;
-           
-            ph.walk_pool = S->n_colors ? W.walk_pool.as<uint32_t>() : nullptr; ph.walk_off = W.walk_off.as<uint64_t>(); ph.walk_cap = walk_cap;
-            ph.max_paths = MAX_PATHS; ph.n_list = &d_cnt->n_branching; ph.mlist = W.mlist.as<uint32_t>(); ph.mlist_cap = W.mlist_cap;
-            ph_keep = ph;
-            tbegin(PF_K_CALL_PATHS, pst);
-            k_call_paths<false><<<paths_grid, 64, 0, pst>>>(ph);
-            tend(pst);
-            if (fork_paths) PF_HIP(hipEventRecord(W.ev_paths, pst));
-        }
-        if (snp_ok) {
-            SnpArgs sn;
-            sn.ct = pa.ct; sn.kept = pa.kept; sn.t0 = t0; sn.nb = nb; sn.slist = pa.lists.slist; sn.seq = ctx->d_seq; sn.off = ctx->d_off;
-            sn.len = ctx->d_len; sn.res = pa.res; sn.otext = O.otext.as<char>(); sn.text_cap = cap_text;
-            sn.osites = O.osites.as<pf_bubble_site>(); sn.site_cap = cap_sites; sn.ogroups = O.ogroups.as<uint8_t>(); sn.group_cap = cap_groups;
-            sn.heads = d_heads; sn.lists = pa.lists; sn.pair_ok = pa.pair_ok; sn.stack_ok = pa.stack_ok; sn.cnt = d_cnt;
-            tbegin(PF_K_CALL_SNP, st);
-            k_call_snp<<<(nb + 255) / 256, 256, 0, st>>>(sn);   // (the list length is on the device: surplus threads leave at once)
-            tend(st);
-        }
-        StackArgs sk;
-        if (stack_tier) {
-            // K-STACK, first launch: the strict bubbles K-PREP and K-SNP listed (two paths that are not a single mismatch, three and
-            // four paths); what it cannot certify is K-PAIR's (launched behind it) or K-BUBBLE's
-            sk.list = pa.lists.klist; sk.n_list = &d_cnt->n_stack; sk.scratch = W.stack_scr.as<uint8_t>();
-            sk.btask = pa.btask; sk.bpath = pa.bpath; sk.ptext = W.ptext.as<char>();
-            sk.seq = ctx->d_seq; sk.off = ctx->d_off; sk.len = ctx->d_len;
-            sk.M = (int)match; sk.D = (int)mismatch; sk.G = (int)gap;
-            sk.res = pa.res; sk.otext = O.otext.as<char>(); sk.text_cap = cap_text; sk.osites = O.osites.as<pf_bubble_site>(); sk.site_cap = cap_sites;
-            sk.ogroups = O.ogroups.as<uint8_t>(); sk.group_cap = cap_groups; sk.oilen = O.oilen.as<uint32_t>(); sk.ilen_cap = cap_ilen;
-            sk.heads = d_heads; sk.lists = pa.lists; sk.cnt = d_cnt;
-            sk.pair_ok = pa.pair_ok;
-            tbegin(PF_K_CALL_STACK, st);
-            k_call_stack<<<stack_grid, 64, 0, st>>>(sk);
-            tend(st);
-        }
-        PairArgs pr;
-        static const bool pair_stats = getenv("PF_PAIR_STATS") != nullptr;
-        DevTmp<unsigned long long> prof_;
-        if (pair_tier) {
-            pr.ct = pa.ct; pr.kept = pa.kept; pr.t0 = t0; pr.seq = ctx->d_seq; pr.off = ctx->d_off; pr.len = ctx->d_len;
-            pr.M = match; pr.D = mismatch; pr.G = gap;
-            pr.Mi = (int)match; pr.Di = (int)mismatch; pr.Gi = (int)gap;
-            pr.list = pa.lists.plist; pr.n_list = &d_cnt->n_pair; pr.n_done = &d_cnt->n_pair_done;
-            pr.scratch = W.pair_scr.as<uint8_t>(); pr.res = pa.res; pr.otext = O.otext.as<char>(); pr.text_cap = cap_text;
-            pr.osites = O.osites.as<pf_bubble_site>(); pr.site_cap = cap_sites; pr.ogroups = O.ogroups.as<uint8_t>(); pr.group_cap = cap_groups;
-            pr.oilen = O.oilen.as<uint32_t>(); pr.ilen_cap = cap_ilen; pr.heads = d_heads; pr.lists = pa.lists; pr.cnt = d_cnt;
-            pr.prof = nullptr;
-            if (pair_stats) {
-                PF_HIP(prof_.alloc(64));
-                PF_HIP(hipMemsetAsync(prof_.p, 0, 64, st));
-                pr.prof = prof_.p;
-            }
-            tbegin(PF_K_CALL_PAIR, st);
-            if (pair_integral) k_call_pair<PAIR_MAX, true><<<pair_grid, 64, 0, st>>>(pr);
-            else k_call_pair<PAIR_MAX, false><<<pair_grid, 64, 0, st>>>(pr);
-            tend(st);
-            if (pair_stats) {
-                unsigned long long h[8];
-                PF_HIP(hipMemcpy(h, prof_.p, 64, hipMemcpyDeviceToHost));
-                fprintf(stderr, "[k_call_pair] %llu wavefront rounds; lane-0 ticks (10 ns): decode %llu fill %llu traceback %llu classify %llu publish %llu\n", h[5],
-                        h[0], h[1], h[2], h[3], h[4]);
-            }
-        }
-        if (fork_paths) PF_HIP(hipStreamWaitEvent(st, W.ev_paths, 0));
-        if (stack_tier) {
-            // K-STACK, second launch: the branching bubbles K-PATHS listed (their two-path rejects cannot go to K-PAIR, which reads
-            // the inner unitigs of a strict bubble: K-BUBBLE's)
-            sk.list = pa.lists.klist_b; sk.n_list = &d_cnt->n_stack_b; sk.pair_ok = 0;
-            tbegin(PF_K_CALL_STACK, st);
-            k_call_stack<<<stack_grid, 64, 0, st>>>(sk);
-            tend(st);
-        }
-        PF_HIP(hipGetLastError());
-        PF_HIP(hipMemcpyAsync(&hc, d_cnt, sizeof(hc), hipMemcpyDeviceToHost, st));
-        PF_HIP(hipStreamSynchronize(st));
-        ta("K-PREP .. K-STACK done");
-        bool again = false;   // kernels launched once the host knows their lists' lengths: the counters are read once more behind them
-        if (pair_tier && hc.n_pair2) {
-            // second tier (paths of 65 .. 128 bases, or a longer indel than the first tier's band follows): few on most graphs, so
-            // its scratch and its launch wait until the host knows there are any; its rejects join K-BUBBLE's queues
-            const int g2 = (int)std::min<uint32_t>((hc.n_pair2 + 63) / 64, (uint32_t)pair_grid2);
-            pr.list = pa.lists.plist2; pr.n_list = &d_cnt->n_pair2; pr.n_done = &d_cnt->n_pair2_done;
-            pr.prof = nullptr;
-            const uint32_t tier2_min = [] { const char *e = getenv("PF_PAIR2_MIN"); return e ? (uint32_t)atoi(e) : 0u; }();   // (read per call: tests run the tier on a few bubbles)
-            if (hc.n_pair2 < (tier2_min ? tier2_min : (uint32_t)ctx->n_cu * 32u)) {
-                k_call_pair2_reroute<<<(hc.n_pair2 + 255) / 256, 256, 0, st>>>(pr);
-            } else {
-                NEED(W.pair_scr2, PairGeom<PAIR_MAX2>::scratch_bytes * g2);
-                pr.scratch = W.pair_scr2.as<uint8_t>();
-                tbegin(PF_K_CALL_PAIR, st);
-                if (pair_integral) k_call_pair<PAIR_MAX2, true><<<g2, 64, 0, st>>>(pr);
-                else k_call_pair<PAIR_MAX2, false><<<g2, 64, 0, st>>>(pr);
-                tend(st);
-            }
-            again = true;
-        }
-        if (again) {
-            PF_HIP(hipGetLastError());
-            PF_HIP(hipMemcpyAsync(&hc, d_cnt, sizeof(hc), hipMemcpyDeviceToHost, st));
-            PF_HIP(hipStreamSynchronize(st));
-        }
-        ctx_units(ctx, PF_K_CALL_PREP, nb);
-        if (snp_ok) ctx_units(ctx, PF_K_CALL_SNP, hc.n_snp);
-        if (pair_tier) ctx_units(ctx, PF_K_CALL_PAIR, hc.n_pair + hc.n_pair2);
-        if (stack_tier) ctx_units(ctx, PF_K_CALL_STACK, hc.n_stack + hc.n_stack_b);
-        ctx_units(ctx, PF_K_CALL_PATHS, hc.n_branching);
-        if (getenv("PF_TRACE_ALIGN")) fprintf(stderr, "[pf_call_align] bubbles of more than 255 walks: %u, err %u\n", hc.n_many, hc.err);
-        if (hc.n_many > W.mlist_cap && !(hc.err & 33u)) {
-            W.mlist_cap = hc.n_many + hc.n_many / 8 + 64;
-            NEED(W.mlist, (size_t)W.mlist_cap * 4);
-            continue;
-        }
-        if (hc.n_many && !(hc.err & 33u)) {
-            // bubbles of more than 255 walks: walked again by a few wavefronts with room for PATHS_BIG walks each
-            const uint32_t n_many = hc.n_many;
-            const int big_grid = (int)std::min<uint32_t>(n_many, 32);
-            const uint64_t big_per_wave = (((((uint64_t)10 * depth_cap + 4) * 4 + 7) & ~7ull) + ((uint64_t)PATHS_BIG + 1) * 12 + 255) & ~255ull;
-            NEED(W.paths_big_scr, big_per_wave * big_grid);
-            PathArgs pb = ph_keep;
-            pb.blist = W.mlist.as<uint32_t>(); pb.n_list = &d_cnt->n_many; pb.max_paths = PATHS_BIG; pb.mlist = nullptr; pb.mlist_cap = 0;
-            pb.scratch = W.paths_big_scr.as<uint8_t>(); pb.scratch_per_wave = big_per_wave;
-            tbegin(PF_K_CALL_PATHS, st);
-            k_call_paths<true><<<big_grid, 64, 0, st>>>(pb);
-            tend(st);
-            PF_HIP(hipGetLastError());
-            PF_HIP(hipMemcpyAsync(&hc, d_cnt, sizeof(hc), hipMemcpyDeviceToHost, st));
-            PF_HIP(hipStreamSynchronize(st));
-        }
-        if (hc.err & 33u) {
-            char where[96];
-            snprintf(where, sizeof where, " (superbubble from unitig %u%c to unitig %u%c)", (hc.err_entrance >> 1) + 1, (hc.err_entrance & 1) ? '-' : '+',
-                     (hc.err_exit >> 1) + 1, (hc.err_exit & 1) ? '-' : '+');
-            pf::CtxErr{ctx} = std::string(hc.err & 1u ? "pf_call_run: a bubble has more than 65535 paths" : "pf_call_run: a bubble is deeper than the complex size allows") + where;
-            return PF_ERR_ARG;
-        }
-        amax(S->otext_cap, cap_text); amax(S->osites_cap, cap_sites);
-        amax(S->ogroups_cap, cap_groups); amax(S->oilen_cap, cap_ilen);
-        amax(S->path_pool, path_cap);
-        amax(S->text_pool, text_cap);
-        static const bool trace_retry = getenv("PF_TRACE_ALIGN") != nullptr;
-        if (trace_retry)
-            fprintf(stderr, "[pf_call_align] attempt %d: %u bubbles, path pool %llu of %llu, path text %llu of %llu, rows text cap %llu (needs %llu)\n", attempt, nb,
-                    (unsigned long long)hc.path_head, (unsigned long long)path_cap, (unsigned long long)hc.text_head, (unsigned long long)text_cap,
-                    (unsigned long long)cap_text, (unsigned long long)(3 * hc.text_head + 128ull * hc.n_branching + 160ull * nb));
-        if (hc.path_head > path_cap || hc.text_head > text_cap || hc.walk_head > walk_cap) {
-            amax(S->path_pool, hc.path_head + hc.path_head / 8 + 1024);
-            amax(S->text_pool, hc.text_head + hc.text_head / 8 + 4096);
-            if (S->n_colors) W.walk_cap = std::max<uint64_t>(W.walk_cap, hc.walk_head + hc.walk_head / 8 + 1024);
-            continue;
-        }
-        if (S->n_colors) W.walk_cap = std::max(W.walk_cap, walk_cap);
-        // the aligned rows of the branching bubbles come on top of what K-SNP took: make room before K-BUBBLE runs
-        // (the path text is handed out in per-wavefront chunks: its size varies by a few per mille from pass to pass, hence the margin)
-        if (cap_text < 3 * hc.text_head + 128ull * hc.n_branching + 160ull * nb) {
-            const uint64_t need = 3 * hc.text_head + 128ull * hc.n_branching + 160ull * nb;
-            amax(S->otext_cap, need + need / 16 + 4096);
-            continue;
-        }
-        n_jobs = 0;
-        for (int x = 0; x < NQ; ++x) n_jobs += hc.q_n[x];
-        // K-BUBBLE: the queues are heavy-then-light per class; compact them into one index array
-        NEED(W.scan_tmp2, std::max<size_t>((size_t)n_jobs, 1) * 4);
-        {
-            uint32_t *d_idx = W.scan_tmp2.as<uint32_t>();
-            size_t at = 0;
-            for (int x = 0; x < NQ; ++x) {
-                if (!hc.q_n[x]) continue;
-                PF_HIP(hipMemcpyAsync(d_idx + at, W.queues.as<uint32_t>() + (size_t)x * nb, (size_t)hc.q_n[x] * 4, hipMemcpyDeviceToDevice, st));
-                at += hc.q_n[x];
-            }
-        }
-        BubbleLaunch BL;
-        BL.text = W.ptext.as<char>(); BL.paths = W.bpath.as<pf_bubble_path>(); BL.tasks = W.btask.as<pf_bubble_task>();
-        BL.n_tasks = nb; BL.idx = W.scan_tmp2.as<uint32_t>();
-        for (int c = 0; c <= kBubLdsClasses; ++c) BL.n_cls[c] = hc.q_n[2 * c] + hc.q_n[2 * c + 1];
-        BL.max_need = hc.max_need; BL.retry_need = hc.retry_need;
-        BL.match = match; BL.mismatch = mismatch; BL.gap = gap;
-        BL.res = O.res.as<pf_bubble_result>(); BL.otext = O.otext.as<char>(); BL.osites = O.osites.as<pf_bubble_site>();
-        BL.ogroups = O.ogroups.as<uint8_t>(); BL.oilen = O.oilen.as<uint32_t>();
-        BL.text_cap = cap_text; BL.site_cap = cap_sites; BL.group_cap = cap_groups; BL.ilen_cap = cap_ilen;
-        BL.keep_heads = true;
-        BL.lane = lane; BL.stream = st;
-        ta("K-BUBBLE launching");
-        const int bst = bubble_launch(ctx, BL, heads);
-        ta("K-BUBBLE done");
-        if (trace_retry)
-            fprintf(stderr, "[pf_call_align] attempt %d: K-BUBBLE status %d, pools text %llu of %llu, sites %llu of %llu, groups %llu of %llu, indel lengths %llu of %llu\n", attempt, bst,
-                    heads[0], (unsigned long long)cap_text, heads[1], (unsigned long long)cap_sites, heads[2], (unsigned long long)cap_groups, heads[3], (unsigned long long)cap_ilen);
-        if (bst == PF_ERR_OVERFLOW && (heads[0] > cap_text || heads[1] > cap_sites || heads[2] > cap_groups || heads[3] > cap_ilen)) {
-            amax(S->otext_cap, heads[0] + heads[0] / 8);
-            amax(S->osites_cap, heads[1] + heads[1] / 8);
-            amax(S->ogroups_cap, heads[2] + heads[2] / 8);
-            amax(S->oilen_cap, heads[3] + heads[3] / 8);
-            continue;
-        }
-        if (bst != PF_OK) return bst;
-        break;
+    AlignCall A(ctx, lane, t0, (uint32_t)(t1 - t0), complex_size, match, mismatch, gap);
+    PF_TRY(A.prepare());
+    // K-PREP .. K-BUBBLE; every pool grows until the batch fits (first batches of a run only)
+    for (A.attempt = 0;; ++A.attempt) {
+        if (A.attempt > 5) { pf::CtxErr{ctx} = "pf_call_align: pools do not converge"; return PF_ERR_OVERFLOW; }
+        bool retry = false;
+        PF_TRY(A.size_pools());
+        PF_TRY(A.launch_tiers());
+        PF_TRY(A.read_counters());
+        A.trace.stage("K-PREP .. K-STACK done");
+        // kernels launched once the host knows their lists' lengths
+        PF_TRY(A.launch_pair_tier2());
+        A.note_units();
+        PF_TRY(A.launch_paths_big(&retry));
+        if (!retry) PF_TRY(A.accept_walks(&retry));
+        if (!retry) PF_TRY(A.run_bubble(&retry));
+        if (!retry) break;
     }
+    const CallCounters &hc = A.hc;
     out->n_branching = hc.n_branching;
-    out->align_jobs = n_jobs + hc.n_snp_done + hc.n_pair_done + hc.n_pair2_done + hc.n_stack_done;
-    out->snp_jobs = hc.n_snp_done; out->pair_jobs = hc.n_pair_done + hc.n_pair2_done; out->wave_jobs = n_jobs; out->stack_jobs = hc.n_stack_done;
-
-    // ---- bubble numbering inside the batch (launched ahead of K-SITES, read with its counters: one wait for both) ----
-    k_call_has<<<(nb + 255) / 256, 256, 0, st>>>(O.res.as<pf_bubble_result>(), nb, W.has.as<uint32_t>());
-    NEED(W.scan_tmp, scan_scratch_bytes(nb));
-    PF_HIP(scan_inclusive_u32(W.has.as<uint32_t>(), O.vc.as<uint32_t>(), nb, W.scan_tmp.p, st));
-    uint32_t n_called = 0;
-    PF_HIP(hipMemcpyAsync(&n_called, O.vc.as<uint32_t>() + (nb - 1), 4, hipMemcpyDeviceToHost, st));
-
-    // ---- K-SITES ----
-    // (a site string is k characters long unless it takes the raw columns up to its row's end -- substr with a negative count,
-    // src/CDBG.cpp:1499 -- or more than k characters agree behind an indel: a launch that meets one longer than its room says how
-    // long, ks_need, and is repeated with that much)
-    uint32_t KS = std::max<uint32_t>((uint32_t)(2 * k + 64), S->sites_ks.load());
+    out->align_jobs = A.n_jobs + hc.n_snp_done + hc.n_pair_done + hc.n_pair2_done + hc.n_stack_done;
+    out->snp_jobs = hc.n_snp_done; out->pair_jobs = hc.n_pair_done + hc.n_pair2_done; out->wave_jobs = A.n_jobs; out->stack_jobs = hc.n_stack_done;
+    PF_TRY(A.number_called());
     if (hc.n_branching) {
-        const uint32_t C = S->n_colors;
-        const uint64_t rows_cap = std::max<uint64_t>(256, ((uint64_t)hc.max_rows + 63) & ~63ull);
-        constexpr int sites_per_cu = 16;
-        for (int attempt = 0, ks_attempt = 0;; ++attempt) {
-            const uint64_t sites_per_wave = ((2 * rows_cap * KS + rows_cap * (4 + 4 + 4 + 1 + 1 + 8) + (C ? rows_cap * (16ull * S->col_words + 8ull * C + 1) : 0)) + 255) & ~255ull;
-            // (tables for thousands of rows: fewer wavefronts, at most 2 GB of them)
-            const int sites_grid = (int)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint32_t>(hc.n_branching, (uint32_t)(ctx->n_cu * sites_per_cu)), (2ull << 30) / sites_per_wave));
-            NEED(W.sites_scr, sites_per_wave * sites_grid);
-            const uint64_t sv_cap = std::max<uint64_t>(S->sv_pool, 8ull * std::max<uint32_t>(C, 1) * hc.n_branching + 1024ull * sites_grid + 1024);   // (a started chunk per wavefront)
-            NEED(O.sv, sv_cap * 8);
-            SiteArgs sa;
-            sa.ct = S->ctask.as<CallTask>(); sa.kept = S->kept.as<uint32_t>(); sa.t0 = t0; sa.blist = W.blist.as<uint32_t>();
-            sa.res = O.res.as<pf_bubble_result>(); sa.otext = O.otext.as<char>(); sa.osites = O.osites.as<pf_bubble_site>();
-            sa.ogroups = O.ogroups.as<uint8_t>(); sa.k = k; sa.tab = ctx->d_tab; sa.mask = ctx->tab_cap - 1;
-            sa.one_strand = ctx->tab_one_strand; sa.tab_exact = ctx->tab_exact; sa.low = S->low; sa.up = S->up; sa.ks = KS; sa.rows_cap = (uint32_t)rows_cap;
-            sa.scratch = W.sites_scr.as<uint8_t>(); sa.scratch_per_wave = sites_per_wave; sa.sv_off = O.sv_off.as<uint64_t>();
-            sa.sv = O.sv.as<double>(); sa.sv_cap = sv_cap; sa.cnt = d_cnt;
-            sa.n_colors = C;
-            sa.ctab = CTab{ctx->d_ctab, ctx->ctab_cap - 1, ctx->ctab_line_bytes}; sa.c_one_strand = ctx->ctab_one_strand; sa.unread = ctx->d_unread;
-            sa.clow = S->col_low.as<uint32_t>(); sa.cup = S->col_up.as<uint32_t>(); sa.full = S->col_full.as<uint64_t>(); sa.cwords = S->col_words;
-            sa.part_first = S->part_first.as<uint32_t>(); sa.part_colour = S->part_colour.as<uint32_t>(); sa.part_word = S->part_word.as<uint64_t>();
-            sa.part_bits = S->part_bits.as<uint64_t>(); sa.walk_pool = W.walk_pool.as<uint32_t>(); sa.walk_off = W.walk_off.as<uint64_t>();
-            sa.seq = ctx->d_seq; sa.off = ctx->d_off; sa.len = ctx->d_len;
-            static const bool sites_stats = getenv("PF_SITES_STATS") != nullptr;   // measurements: where a wavefront's time goes
-            DevTmp<unsigned long long> sprof_;
-            sa.prof = nullptr;
-            if (sites_stats) {
-                PF_HIP(sprof_.alloc((size_t)sites_grid * 48));
-                PF_HIP(hipMemsetAsync(sprof_.p, 0, (size_t)sites_grid * 48, st));
-                sa.prof = sprof_.p;
-            }
-            PF_HIP(hipMemsetAsync(&d_cnt->sites_next, 0, 4, st));
-            PF_HIP(hipMemsetAsync(&d_cnt->sv_head, 0, 8, st));
-            PF_HIP(hipMemsetAsync(&d_cnt->site_strings, 0, 8, st));
-            tbegin(PF_K_CALL_SITES, st);
-            if (C) k_call_sites<true><<<sites_grid, 64, 0, st>>>(sa);
-            else k_call_sites<false><<<sites_grid, 64, 0, st>>>(sa);
-            tend(st);
-            ctx_units(ctx, PF_K_CALL_SITES, hc.n_branching);
-            PF_HIP(hipGetLastError());
-            if (sa.prof) {
-                PF_HIP(hipStreamSynchronize(st));
-                std::vector<unsigned long long> h((size_t)sites_grid * 6);
-                PF_HIP(hipMemcpy(h.data(), sprof_.p, h.size() * 8, hipMemcpyDeviceToHost));
-                unsigned long long sum[6] = {0, 0, 0, 0, 0, 0}, mx = 0;
-                for (int w = 0; w < sites_grid; ++w) {
-                    for (int x = 0; x < 6; ++x) sum[x] += h[(size_t)w * 6 + x];
-                    mx = std::max(mx, h[(size_t)w * 6]);
-                }
-                fprintf(stderr, "[k_call_sites] %d wavefronts, %llu bubbles; ticks (10 ns) per wavefront: total %.0f (max %llu) = pop + load %.0f, strings %.0f, ranks + probes %.0f, groups %.0f\n",
-                        sites_grid, sum[5], (double)sum[0] / sites_grid, mx, (double)sum[1] / sites_grid, (double)sum[2] / sites_grid, (double)sum[3] / sites_grid,
-                        (double)sum[4] / sites_grid);
-            }
-            PF_HIP(hipMemcpyAsync(&hc, d_cnt, sizeof(hc), hipMemcpyDeviceToHost, st));
-            PF_HIP(hipStreamSynchronize(st));
-            if (hc.err & 16u) {
-                if (++ks_attempt > 3 || hc.ks_need <= KS) { pf::CtxErr{ctx} = "pf_call_run: the room for a site string does not converge"; return PF_ERR_OVERFLOW; }
-                KS = (hc.ks_need + 63u) & ~63u;
-                amax(S->sites_ks, KS);
-                hc.err = 0; hc.ks_need = 0;   // (the other bits are looked at when every string had room: a string cut short has no verdict)
-                PF_HIP(hipMemsetAsync(&d_cnt->err, 0, 4, st));
-                PF_HIP(hipMemsetAsync(&d_cnt->ks_need, 0, 4, st));
-                --attempt;
-                continue;
-            }
-            if (hc.err & 2u) { pf::CtxErr{ctx} = "CDBG::readCov(): a kmer of a site string can not found ."; return PF_ERR_MISSING_KMER; }
-            if (hc.err & 4u) { pf::CtxErr{ctx} = "CDBG::PloidyEstimation(): a site string runs past the end of an aligned row (the reference terminates here: std::out_of_range from substr, src/CDBG.cpp:1478-1590)"; return PF_ERR_ARG; }
-            if (hc.err & 64u) { pf::CtxErr{ctx} = "CCDBG::PloidyEstimation(): a site string does not start on a unitig of its bubble"; return PF_ERR_ARG; }
-            if (hc.sv_head > sv_cap) {
-                if (attempt >= 2) { pf::CtxErr{ctx} = "pf_call_run: site value pool does not converge"; return PF_ERR_OVERFLOW; }
-                amax(S->sv_pool, hc.sv_head + hc.sv_head / 8 + 1024);
-                continue;
-            }
-            amax(S->sv_pool, sv_cap);
-            break;
-        }
+        PF_TRY(A.run_sites());
     } else {
-        NEED(O.sv, 16);
-        PF_HIP(hipStreamSynchronize(st));   // (n_called)
+        PF_TRY(need(ctx, A.who, {{&O.sv, 16}}));
+        PF_HIP(hipStreamSynchronize(A.st));   // (n_called)
     }
     out->site_strings = hc.site_strings;
-    ta("K-SITES done");
-
-    out->n_called = n_called;
-    O.nb = nb;
+    A.trace.stage("K-SITES done");
+    out->n_called = A.n_called;
+    O.nb = A.nb;
     O.cur = *out;
-    for (int x = 0; x < 4; ++x) O.used[x] = heads[x];
+    for (int x = 0; x < 4; ++x) O.used[x] = A.heads[x];
     O.used[4] = hc.n_branching ? hc.sv_head : 0;
-#undef NEED
     return PF_OK;
 }
 
@@ -912,57 +952,32 @@ int pf_call_peek(pf_ctx *ctx, int lane, pf_call_bubble *bubbles, pf_bubble_resul
 }
 
 // The buffers pf_call_align_lane asks for on its first call for ranges of up to nb bubbles, taken NOW (a caller does this beside the
-// load): a first pass then starts with its pools in place instead of two dozen hipMallocs, 20 ms at 5 M unitigs.  Sizes are the
-// first-call formulas of pf_call_align_lane; whatever turns out too small there grows as before.
+// load): a first pass then starts with its pools in place instead of two dozen hipMallocs, 20 ms at 5 M unitigs.  The sizes are a
+// first call's, from the same plan; whatever turns out too small there grows as before.
 int pf_call_reserve_lanes(pf_ctx *ctx, uint64_t nb64, uint32_t complex_size, int n_lanes) {
     if (!ctx || nb64 == 0 || n_lanes < 1 || n_lanes > PF_CALL_LANES) return PF_ERR_ARG;
     CallState *S = state_of(ctx);
     PF_HIP(hipSetDevice(ctx->device));
     const uint32_t nb = (uint32_t)std::min<uint64_t>(nb64, 1u << 24);
-    const char *oom = "pf_call_reserve: out of device memory";
-#define NEED(buf, bytes) do { if (!(buf).ensure(bytes)) { pf::CtxErr{ctx} = oom; return PF_ERR_HIP; } } while (0)
+    const char *who = "pf_call_reserve";
+    const CallGrids grids = call_grids(ctx->n_cu);
     DevLoadTrace trace;
     for (int lane = 0; lane < n_lanes; ++lane) {
         CallState::AlignWork &W = S->work[lane];
-        NEED(W.counters, sizeof(CallCounters));
-        NEED(W.btask, (size_t)nb * sizeof(pf_bubble_task));
-        NEED(W.queues, (size_t)NQ * nb * 4);
-        for (DevBuf *b : {&W.blist, &W.slist, &W.plist, &W.plist2, &W.klist, &W.klist_b, &W.has}) NEED(*b, (size_t)nb * 4);
-        NEED(W.stack_scr, stack_scratch_bytes() * (uint64_t)(ctx->n_cu * 8));
-        const uint32_t depth_cap = std::max<uint32_t>(complex_size + 4, 16);
-        const uint64_t paths_per_wave = ((256 * 8 + 256 * 4 + (10ull * depth_cap + 4) * 4) + 255) & ~255ull;
-        NEED(W.paths_scr, paths_per_wave * (uint64_t)(ctx->n_cu * 16));
-        NEED(W.pair_scr, PairGeom<PAIR_MAX>::scratch_bytes * (uint64_t)(ctx->n_cu * 12));
-        NEED(W.bpath, ((size_t)4 * nb + (uint64_t)nb / 2 + 128ull * (ctx->n_cu * 16) + 1024) * sizeof(pf_bubble_path));
-        NEED(W.ptext, (uint64_t)nb * FIRST_PATH_TEXT + (1u << 16));
-        NEED(W.scan_tmp2, (size_t)nb / 4 * 4 + 4096);
-        {   // K-SITES' tables for bubbles of up to 256 walks (single-sample; for the longest k: the graph may still be on its way)
-            const uint64_t KS = (uint64_t)(2 * 31 + 64), rows_cap = 256;
-            const uint64_t sites_per_wave = ((2 * rows_cap * KS + rows_cap * (4 + 4 + 4 + 1 + 1 + 8)) + 255) & ~255ull;
-            NEED(W.sites_scr, sites_per_wave * (uint64_t)(ctx->n_cu * 16));
-        }
         CallState::AlignOut &O = S->lane[lane];
-        NEED(O.res, (size_t)nb * sizeof(pf_bubble_result));
-        NEED(O.sv_off, (size_t)nb * 8);
-        NEED(O.vc, (size_t)nb * 4);
-        NEED(O.otext, (uint64_t)FIRST_ROW_TEXT * nb + (1u << 16));
-        NEED(O.osites, ((uint64_t)FIRST_SITES * nb + 64) * sizeof(pf_bubble_site));
-        NEED(O.ogroups, (uint64_t)FIRST_GROUPS * nb + 64);
-        NEED(O.oilen, ((uint64_t)FIRST_ILEN * nb + 64) * 4);
-        NEED(O.sv, ((uint64_t)nb / 4 + 1024ull * ctx->n_cu * 16 + 1024) * 8);
+        PF_TRY(ensure_batch_buffers(ctx, who, W, O, nb));
+        PF_TRY(ensure_wave_scratch(ctx, who, W, grids, depth_cap(complex_size), true, true));
+        PF_TRY(ensure_pools(ctx, who, W, O, nb, batch_pools(nb, grids, LearntPools{}, false)));
+        // what a first call sizes by counts of its batch is guessed: K-BUBBLE's job index and the site values (pf_call_plan.hpp), and
+        // K-SITES' tables for bubbles of up to 256 walks, single-sample, for the longest k (the graph may still be on its way)
+        PF_TRY(need(ctx, who, {{&W.scan_tmp2, reserve_job_index_bytes(nb)}, {&W.sites_scr, sites_per_wave(256, first_site_string(31), 0, 1) * grids.sites},
+                               {&O.sv, reserve_site_values(nb, grids) * 8}}));
         trace.mark("reserve: a lane's buffers");
-        if (lane != 0 && !W.stream) { PF_HIP(lane_stream_create(&W.stream, lane)); W.own_stream = true; }
-        if (!W.side_stream) {
-            PF_HIP(lane_stream_create(&W.side_stream, lane));
-            PF_HIP(hipEventCreateWithFlags(&W.ev_prep, hipEventDisableTiming));
-            PF_HIP(hipEventCreateWithFlags(&W.ev_paths, hipEventDisableTiming));
-        }
+        PF_TRY(ensure_lane_streams(ctx, W, lane));
         trace.mark("reserve: a lane's streams and events");
-        const int st = bubble_reserve(ctx, nb, lane);
-        if (st != PF_OK) return st;
+        PF_TRY(bubble_reserve(ctx, nb, lane));
         trace.mark("reserve: K-BUBBLE's workspaces and first launches");
     }
-#undef NEED
     return PF_OK;
 }
 
@@ -985,12 +1000,8 @@ static int text_work_of(pf_ctx *ctx, pf::CallState *S, int which, uint32_t nb) {
         PF_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
         PF_HIP(hipStreamCreateWithPriority(&T.stream, hipStreamNonBlocking, greatest));
     }
-    NEED_TEXT(T.sizes, (size_t)N_INT * (nb + 1) * 4);
-    NEED_TEXT(T.offs, ((size_t)N_INT * (nb + 1) + 1) * 8);
-    NEED_TEXT(T.totals, 16 * 8);
-    NEED_TEXT(T.tcounters, sizeof(CallCounters));
-    NEED_TEXT(T.tscan, scan_scratch_bytes((uint64_t)N_INT * (nb + 1)));
-    return PF_OK;
+    return need(ctx, "pf_call_text", {{&T.sizes, (size_t)N_INT * (nb + 1) * 4}, {&T.offs, ((size_t)N_INT * (nb + 1) + 1) * 8}, {&T.totals, 16 * 8},
+                                      {&T.tcounters, sizeof(CallCounters)}, {&T.tscan, scan_scratch_bytes((uint64_t)N_INT * (nb + 1))}});
 }
 
 // what the first pf_call_text_range of a run would take (see pf_call_reserve): the text streams, the size tables of a piece of
@@ -1001,7 +1012,7 @@ int pf_call_reserve_text(pf_ctx *ctx, uint64_t piece_bubbles) {
     PF_HIP(hipSetDevice(ctx->device));
     const uint32_t nb = (uint32_t)std::min<uint64_t>(piece_bubbles, 1u << 24);
     for (int which = 0; which < 2; ++which) { const int ts = text_work_of(ctx, S, which, nb); if (ts != PF_OK) return ts; }
-    for (int slab = 0; slab < PF_CALL_SLABS; ++slab) NEED_TEXT(S->out[slab], (11ull * 31 + 40) * nb);   // (the longest k: the graph may still be on its way)
+    for (int slab = 0; slab < PF_CALL_SLABS; ++slab) PF_TRY(need(ctx, "pf_call_text", {{&S->out[slab], (11ull * 31 + 40) * nb}}));   // (the longest k: the graph may still be on its way)
     // K-TEXT's two passes once over no bubbles on each of its streams: what the first launch of a kernel this size pays on a stream
     // (scratch for its spills: 2.3 ms of a first piece's count pass) is paid here, beside the load
     for (int which = 0; which < 2; ++which) {
@@ -1045,8 +1056,6 @@ static int call_text_impl(pf_ctx *ctx, int lane, int slab, uint64_t first, uint6
     uint32_t vc_edge[2] = {0, 0};
     PF_HIP(hipMemcpyAsync(&vc_edge[1], O.vc.as<uint32_t>() + (first + count - 1), 4, hipMemcpyDeviceToHost, st));
     if (first) PF_HIP(hipMemcpyAsync(&vc_edge[0], O.vc.as<uint32_t>() + (first - 1), 4, hipMemcpyDeviceToHost, st));
-    const char *oom = "pf_call_text: out of device memory";
-#define NEED(buf, bytes) do { if (!(buf).ensure(bytes)) { pf::CtxErr{ctx} = oom; return PF_ERR_HIP; } } while (0)
     CallCounters *d_cnt = T.tcounters.as<CallCounters>();
     CallCounters hc;
     const size_t n_sizes = (size_t)N_INT * (nb + 1);
@@ -1087,7 +1096,7 @@ static int call_text_impl(pf_ctx *ctx, int lane, int slab, uint64_t first, uint6
         return PF_OK;
     }
     ta("sizes counted");
-    NEED(S->out[slab], std::max<uint64_t>(all, 16));
+    PF_TRY(need(ctx, "pf_call_text", {{&S->out[slab], std::max<uint64_t>(all, 16)}}));
     ta("slab taken");
     all = 0;
     for (int s = 0; s < N_STREAMS; ++s) {
@@ -1118,7 +1127,7 @@ static int call_text_impl(pf_ctx *ctx, int lane, int slab, uint64_t first, uint6
             foff[s] = fall;
             fall += flen[s];
         }
-        NEED(S->outp[slab], fall + 16);
+        PF_TRY(need(ctx, "pf_call_text", {{&S->outp[slab], fall + 16}}));
         char *pb = S->outp[slab].as<char>();
         PF_HIP(hipMemsetAsync(pb + fall, 0, 16, st));
         if (slab_len(PF_OUT_ALIGNSEQ))
@@ -1155,7 +1164,6 @@ static int call_text_impl(pf_ctx *ctx, int lane, int slab, uint64_t first, uint6
     for (int x = 0; x < 4; ++x) out->allele[x] = hc.allele[x];
     out->core_cov = hc.core_cov;
     out->core_num = hc.core_num;
-#undef NEED
     return PF_OK;
 }
 

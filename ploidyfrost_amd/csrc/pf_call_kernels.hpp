@@ -21,6 +21,7 @@
 #include "pf_bubble_launch.hpp"
 #include "pf_alnpack.hpp"
 #include "pf_call_dev.hpp"
+#include "pf_call_plan.hpp"
 #include "pf_colored_dev.hpp"
 #include "pf_cov_stream.hpp"
 #include "pf_ctx.hpp"
@@ -38,9 +39,6 @@ constexpr uint8_t B_PLUS = 0x01, B_MINUS = 0x02, B_STRICT_M = 0x08, B_STRICT_P =
 constexpr int N_STREAMS = PF_CALL_STREAMS;
 constexpr int N_INT = N_STREAMS + 1;   // size / offset tables: the ten streams + the packed form of alignseq (pf_alnpack.hpp)
 constexpr int S_PACK = N_STREAMS;
-// first-pass pool sizes per bubble of a range (pf_call_align_lane, pf_call_reserve_lanes): bytes of aligned rows, sites, group bytes,
-// indel lengths, bytes of path text
-constexpr uint32_t FIRST_ROW_TEXT = 384, FIRST_SITES = 4, FIRST_GROUPS = 12, FIRST_ILEN = 2, FIRST_PATH_TEXT = 64;
 // work lists of a batch: K-BUBBLE's queues (heavy and light per size class), then the three lists of the other kernels
 constexpr int NQ = 2 * (kBubLdsClasses + 1);
 constexpr int KEY_BRANCHING = NQ, KEY_SNP = NQ + 1, KEY_PAIR = NQ + 2, KEY_PAIR2 = NQ + 3, KEY_STACK = NQ + 4, KEY_NONE = NQ + 5;
@@ -75,6 +73,18 @@ inline void amax(std::atomic<T> &a, V v) {
     while (cur < (T)v && !a.compare_exchange_weak(cur, (T)v, std::memory_order_relaxed)) {}
 }
 
+// the bits of CallCounters::err
+enum CallErr : unsigned int {
+    ERR_MANY_PATHS = 1u,     // a bubble has more than 65535 paths
+    ERR_MISSING_KMER = 2u,   // a k-mer of a site string is not in the count table
+    ERR_SITE_ROW = 4u,       // a site string runs past the end of its row
+    ERR_PATH_POOL = 8u,      // a path pool overflowed (path_head, text_head, walk_head tell how much is needed)
+    ERR_SITE_LONG = 16u,     // a site string is longer than its room (ks_need tells how long)
+    ERR_TOO_DEEP = 32u,      // a bubble is deeper than the complex size allows
+    ERR_SITE_UNITIG = 64u,   // colored: a site string does not start on a unitig of its bubble
+    ERR_WALK = ERR_MANY_PATHS | ERR_TOO_DEEP,   // K-PATHS gave up on a bubble: the batch cannot be called
+};
+
 // counters of one batch, device side (zeroed per batch)
 struct CallCounters {
     unsigned int q_n[NQ];           // work queues: class c heavy = q_n[2c], light = q_n[2c + 1]
@@ -85,10 +95,9 @@ struct CallCounters {
     unsigned int n_stack, n_stack_b, n_stack_done;   // K-STACK's lists (strict bubbles; branching ones, filled by K-PATHS) / the bubbles whose alignment it certified
     unsigned int paths_next, sites_next;   // queue heads of K-PATHS / K-SITES
     unsigned int n_many, max_rows;         // bubbles of more than 255 walks (K-PATHS' second launch takes them) / the most walks of any bubble
-    unsigned int ks_need;                  // K-SITES: the longest site string a wavefront had no room for (err bit 4: the launch is repeated with room)
-    unsigned int err;               // bit 0: > 65535 paths, 1: missing k-mer in a site string, 2: site string outside its row,
-                                    // 3: a path pool overflowed (sizes below tell how much is needed), 4: site string too long
-    unsigned int err_entrance, err_exit;   // the bubble bits 0 / 5 speak of (oriented vertices; whichever wavefront wrote last)
+    unsigned int ks_need;                  // K-SITES: the longest site string a wavefront had no room for (ERR_SITE_LONG: the launch is repeated with room)
+    unsigned int err;                      // CallErr bits
+    unsigned int err_entrance, err_exit;   // the bubble ERR_MANY_PATHS / ERR_TOO_DEEP speak of (oriented vertices; whichever wavefront wrote last)
     unsigned long long path_head, text_head, sv_head, walk_head;
     unsigned long long max_need, retry_need;
     unsigned long long allele[4], core_cov, core_num, n_called, site_strings;
@@ -353,11 +362,15 @@ __device__ inline void block_append(int key, uint32_t val, const CallLists &L, C
     __syncthreads();   // (the tables may be used again by the caller's next call)
 }
 
+// What several argument blocks share, filled once per attempt of a batch and assigned whole.
+// the batch: bubble j is task ct[kept[t0 + j]], j < nb
+struct BatchRef { const CallTask *ct; const uint32_t *kept; uint64_t t0; uint32_t nb; };
+// the 2-bit graph
+struct GraphSeq { const uint64_t *seq, *off; const uint32_t *len; };
+// (RowPools, where a kernel that finishes bubbles publishes them: pf_bubble_launch.hpp)
+
 struct PrepArgs {
-    const CallTask *ct;
-    const uint32_t *kept;
-    uint64_t t0;
-    uint32_t nb;
+    BatchRef batch;
     const uint32_t *len;
     pf_bubble_task *btask;
     pf_bubble_path *bpath;
@@ -370,32 +383,18 @@ struct PrepArgs {
 };
 
 struct SnpArgs {
-    const CallTask *ct;
-    const uint32_t *kept;
-    uint64_t t0;
-    uint32_t nb;
+    BatchRef batch;
     const uint32_t *slist;
-    const uint64_t *seq, *off;
-    const uint32_t *len;
-    pf_bubble_result *res;
-    char *otext;
-    uint64_t text_cap;
-    pf_bubble_site *osites;
-    uint64_t site_cap;
-    uint8_t *ogroups;
-    uint64_t group_cap;
-    unsigned long long *heads;  // K-BUBBLE's pool heads: [0] text, [1] sites, [2] groups
+    GraphSeq graph;
+    RowPools out;   // (no indel lengths: a single mismatch)
     CallLists lists;
     int pair_ok, stack_ok;
     CallCounters *cnt;
 };
 
 struct PairArgs {
-    const CallTask *ct;
-    const uint32_t *kept;
-    uint64_t t0;
-    const uint64_t *seq, *off;
-    const uint32_t *len;
+    BatchRef batch;
+    GraphSeq graph;
     double M, D, G;
     int Mi, Di, Gi;               // the same as ints (integral scores)
     const uint32_t *list;         // this tier's bubbles (batch-local indices) ...
@@ -403,16 +402,7 @@ struct PairArgs {
     unsigned int *n_done;
     unsigned long long *prof;   // diagnostic (PF_PAIR_STATS): ticks of lane 0 in decode, fill, traceback, classify, publish; or nullptr
     uint8_t *scratch;           // PairGeom<NMAX>::scratch_bytes per wavefront of the grid
-    pf_bubble_result *res;
-    char *otext;
-    uint64_t text_cap;
-    pf_bubble_site *osites;
-    uint64_t site_cap;
-    uint8_t *ogroups;
-    uint64_t group_cap;
-    uint32_t *oilen;
-    uint64_t ilen_cap;
-    unsigned long long *heads;  // [0] text, [1] sites, [2] groups, [3] ilen
+    RowPools out;
     CallLists lists;
     CallCounters *cnt;
 };
@@ -424,36 +414,22 @@ struct StackArgs {
     const uint32_t *list;
     const unsigned int *n_list;   // how many (on the device)
     uint8_t *scratch;             // stack_scratch_bytes() per wavefront of the grid
-    uint32_t *oilen;
-    uint64_t ilen_cap;
     int pair_ok;                  // two-path bubbles of the strict list that are not certified go to K-PAIR when they fit it (it runs behind this launch)
     const pf_bubble_task *btask;
     const pf_bubble_path *bpath;
     const char *ptext;          // path text of the branching bubbles (K-PATHS)
-    const uint64_t *seq, *off;
-    const uint32_t *len;
+    GraphSeq graph;
     int M, D, G;
-    pf_bubble_result *res;
-    char *otext;
-    uint64_t text_cap;
-    pf_bubble_site *osites;
-    uint64_t site_cap;
-    uint8_t *ogroups;
-    uint64_t group_cap;
-    unsigned long long *heads;  // [0] text, [1] sites, [2] groups, [3] ilen
+    RowPools out;
     CallLists lists;
     CallCounters *cnt;
 };
 
 struct PathArgs {
-    const CallTask *ct;
-    const uint32_t *kept;
-    uint64_t t0;
-    uint32_t nb;
+    BatchRef batch;
     const uint32_t *blist;
     const uint32_t *succ;
-    const uint64_t *seq, *off;
-    const uint32_t *len;
+    GraphSeq graph;
     int k;
     uint32_t depth_cap;     // entries of the major stack (complex size + slack); minor holds 4x
     uint8_t *scratch;       // per wave, for the bubbles whose stacks outgrow the registers: major[depth_cap], minor[4 depth_cap], seg_start
@@ -485,9 +461,7 @@ constexpr uint32_t MAX_PATHS = 255;        // walks of one bubble whose tables f
 constexpr uint32_t PATHS_BIG = 65535;      // ... in the second launch's global tables
 
 struct SiteArgs {
-    const CallTask *ct;
-    const uint32_t *kept;
-    uint64_t t0;
+    BatchRef batch;
     const uint32_t *blist;
     const pf_bubble_result *res;
     const char *otext;
@@ -521,8 +495,7 @@ struct SiteArgs {
     const uint64_t *part_word, *part_bits;
     const uint32_t *walk_pool;
     const uint64_t *walk_off;
-    const uint64_t *seq, *off;
-    const uint32_t *len;
+    GraphSeq graph;
 };
 
 struct FmtArgs {

@@ -49,7 +49,7 @@ __device__ inline char path_char(const PathArgs &a, const uint32_t *major, const
     uint32_t x = 0;
     while (x + 1 < n_seg && seg_start[x + 1] <= pos) ++x;
     const uint32_t idx = pos - seg_start[x] + (x == 0 ? first_idx : 0);
-    return pf::base_char((uint32_t)(oriented_base(a.seq, a.off, a.len, major[x], idx)));
+    return pf::base_char((uint32_t)(oriented_base(a.graph.seq, a.graph.off, a.graph.len, major[x], idx)));
 }
 
 // Two-stack enumeration of every s -> t walk (src/CDBG.cpp:1364-1412) with both stacks in REGISTERS: entry x of the major stack
@@ -63,7 +63,7 @@ __device__ inline bool walk_in_registers(const PathArgs &a, const CallTask &t, T
                                          WalkOut &o, const int lane) {
     const uint32_t eu = t.exit_ov >> 1;
     const uint32_t K = (uint32_t)a.k;
-    const uint32_t first_idx = a.len[t.u] - K;   // s gives the first character of its last k-mer
+    const uint32_t first_idx = a.graph.len[t.u] - K;   // s gives the first character of its last k-mer
     uint32_t mj = 0, ml = 0, s0 = NONE, s1 = NONE, s2 = NONE, s3 = NONE;
     unsigned long long mo = 0;
     uint32_t mn0 = 0, mn1 = 0, mn2 = 0, mn3 = 0;
@@ -93,7 +93,7 @@ __device__ inline bool walk_in_registers(const PathArgs &a, const CallTask &t, T
             const uint32_t *r = a.succ + (size_t)w * 4;
             r0 = r[0]; r1 = r[1]; r2 = r[2]; r3 = r[3];
         }
-        if ((uint32_t)lane == n_major) { mj = w; ml = a.len[u]; mo = a.off[u]; s0 = r0; s1 = r1; s2 = r2; s3 = r3; }
+        if ((uint32_t)lane == n_major) { mj = w; ml = a.graph.len[u]; mo = a.graph.off[u]; s0 = r0; s1 = r1; s2 = r2; s3 = r3; }
         ++n_major;
         if (at_exit) {
             if (o.n_paths >= a.max_paths) { o.too_many = true; return true; }
@@ -116,7 +116,7 @@ __device__ inline bool walk_in_registers(const PathArgs &a, const CallTask &t, T
                         const uint32_t idx = p - ss + (mine == 0 ? first_idx : 0u);
                         const bool rev = (sw & 1) != 0;
                         const uint32_t j = rev ? sl - 1 - idx : idx;
-                        const uint64_t word = a.seq[(((uint64_t)so_hi << 32) | so_lo) + (j >> 5)];
+                        const uint64_t word = a.graph.seq[(((uint64_t)so_hi << 32) | so_lo) + (j >> 5)];
                         uint32_t b = (uint32_t)(word >> (62 - 2 * (j & 31))) & 3u;
                         b = rev ? 3 - b : b;
                         a.text[at + p] = (char)((0x54474341u >> (8 * b)) & 0xFFu);   // "ACGT"[b]
@@ -158,7 +158,7 @@ __device__ inline bool walk_in_registers(const PathArgs &a, const CallTask &t, T
 __device__ __noinline__ void walk_in_scratch(const PathArgs a, const CallTask &t, TextChunk &tx, unsigned long long *poff, uint32_t *plen,
                                              WalkOut &o, uint32_t *major, uint32_t *minor, uint32_t *seg_start, uint32_t *seen, const int lane) {
     const uint32_t eu = t.exit_ov >> 1;
-    const uint32_t ulen = a.len[t.u] - (uint32_t)a.k + 1;
+    const uint32_t ulen = a.graph.len[t.u] - (uint32_t)a.k + 1;
     uint32_t n_major = 0, n_minor = 0;
     o.n_seen = 0;
     if (lane == 0) minor[0] = t.entrance_ov;
@@ -187,7 +187,7 @@ __device__ __noinline__ void walk_in_scratch(const PathArgs a, const CallTask &t
             uint32_t total = 0;
             for (uint32_t x = 0; x < n_major; ++x) {
                 if (lane == 0) seg_start[x] = total;
-                const uint32_t wl = a.len[major[x] >> 1] - (uint32_t)a.k + 1;
+                const uint32_t wl = a.graph.len[major[x] >> 1] - (uint32_t)a.k + 1;
                 total += x == 0 ? 1u : (x + 1 == n_major ? (uint32_t)a.k : wl);
             }
             if (n_major == 1) total = 0;
@@ -236,7 +236,7 @@ __device__ inline void paths_flush(const PathArgs &a, uint32_t pend_key, uint32_
         c_off = key < (uint32_t)NQ ? (uint32_t)offsetof(CallCounters, q_n) + 4u * key : c_off;
         unsigned int *counter = reinterpret_cast<unsigned int *>(reinterpret_cast<char *>(a.cnt) + c_off);
         uint64_t l_at = (uint64_t)(uintptr_t)a.klist;
-        l_at = key < (uint32_t)NQ ? (uint64_t)(uintptr_t)(a.queues + (size_t)key * a.nb) : l_at;
+        l_at = key < (uint32_t)NQ ? (uint64_t)(uintptr_t)(a.queues + (size_t)key * a.batch.nb) : l_at;
         uint32_t *list = reinterpret_cast<uint32_t *>((uintptr_t)l_at);
         uint32_t base = 0;
         if (lane == 0) base = atomicAdd(counter, (unsigned int)__popcll(m));
@@ -267,7 +267,7 @@ __global__ __launch_bounds__(64, 4) void k_call_paths(PathArgs a) {
     unsigned long long need_retry = 0, need_max = 0;
     for (uint32_t q = blockIdx.x; q < n_branching; q += gridDim.x) {   // (bubbles cost about the same: no queue head to fight over)
         const uint32_t j = a.blist[q];
-        const CallTask &t = a.ct[a.kept[a.t0 + j]];
+        const CallTask &t = a.batch.ct[a.batch.kept[a.batch.t0 + j]];
         WalkOut wo;
         walk_reset(wo);
         __builtin_amdgcn_wave_barrier();   // (the loop before may still be reading poff / plen)
@@ -286,7 +286,7 @@ __global__ __launch_bounds__(64, 4) void k_call_paths(PathArgs a) {
                     const uint32_t at = atomicAdd(&a.cnt->n_many, 1u);
                     if (at < a.mlist_cap) a.mlist[at] = j;   // (beyond: the host sees n_many > mlist_cap, grows the list and repeats the attempt)
                 } else {
-                    atomicOr(&a.cnt->err, wo.too_many ? 1u : 32u);
+                    atomicOr(&a.cnt->err, wo.too_many ? ERR_MANY_PATHS : ERR_TOO_DEEP);
                     a.cnt->err_entrance = t.entrance_ov;
                     a.cnt->err_exit = t.exit_ov;
                 }
@@ -354,7 +354,7 @@ __global__ __launch_bounds__(64, 4) void k_call_paths(PathArgs a) {
                     if ((uint32_t)lane == (o_first ? i : o)) ++rank;
                 }
             }
-            if ((uint32_t)lane < n_paths) a.bpath[(size_t)4 * a.nb + first + rank] = pf_bubble_path{poff[lane], plen[lane], PF_NONE};
+            if ((uint32_t)lane < n_paths) a.bpath[(size_t)4 * a.batch.nb + first + rank] = pf_bubble_path{poff[lane], plen[lane], PF_NONE};
         } else if (fits && text_ok) {
             for (uint32_t i = lane; i < n_paths; i += WAVE) {
                 const char *si = a.text + poff[i];
@@ -373,12 +373,12 @@ __global__ __launch_bounds__(64, 4) void k_call_paths(PathArgs a) {
                     }
                     rank += before;
                 }
-                a.bpath[(size_t)4 * a.nb + first + rank] = pf_bubble_path{poff[i], li, PF_NONE};
+                a.bpath[(size_t)4 * a.batch.nb + first + rank] = pf_bubble_path{poff[i], li, PF_NONE};
             }
         } else if (lane == 0) {
-            atomicOr(&a.cnt->err, 8u);
+            atomicOr(&a.cnt->err, ERR_PATH_POOL);
         }
-        if (lane == 0) a.btask[j] = pf_bubble_task{(uint64_t)4 * a.nb + first, n_paths, 0};
+        if (lane == 0) a.btask[j] = pf_bubble_task{(uint64_t)4 * a.batch.nb + first, n_paths, 0};
         if (BIG && lane == 0) atomicMax(&a.cnt->max_rows, n_paths);
         // where the bubble goes next (all of this is wave-uniform): the list entry waits in the wave's registers, the two sizes in
         // its running maxima -- one atomic per list and 64 bubbles instead of three per bubble on one cache line, which is what

@@ -40,8 +40,8 @@ __device__ inline bool colours_of_string(const SiteArgs &a, const char *sp, uint
     const uint64_t rhead = rc_kmer(head, k);
     for (uint32_t q = 0; q < n_walk; ++q) {
         const uint32_t u = walk[q] >> 1;
-        const uint32_t Lu = a.len[u];
-        const uint64_t *w = a.seq + a.off[u];
+        const uint32_t Lu = a.graph.len[u];
+        const uint64_t *w = a.graph.seq + a.graph.off[u];
         auto base_at = [&](uint32_t x) -> int { return (int)((w[x >> 5] >> (62 - 2 * (x & 31))) & 3u); };
         uint64_t y = 0, word = 0;
         int hit = 0;   // 1 forward, 2 reverse complement
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(64, 4) void k_call_sites(SiteArgs a) {
                     }
                     if (lane == 0 && room) a.sv[vcur + gi] = tc;
                 }
-                if (fatal) { err = 2; break; }
+                if (fatal) { err = ERR_MISSING_KMER; break; }
                 if (lane == 0 && room) a.sv[vcur + maxnum] = total;
                 if (lane == 0) a.osites[r.site_off + si].pad_ = ok ? 1 : 0;
                 vcur += maxnum + 1;
@@ -278,11 +278,11 @@ __global__ __launch_bounds__(64, 4) void k_call_sites(SiteArgs a) {
                         if (__ballot(e)) bad = 1;
                     }
                     if (napp >= KS) {   // (still growing: ask for the most a string can reach -- a row's characters and its raw columns)
-                        bad = 16;
+                        bad = ERR_SITE_LONG;
                         if (lane == 0) atomicMax(&a.cnt->ks_need, 2 * L + (uint32_t)k + 2);
                     }
                     sync();
-                    if (bad) { err = bad == 16 ? 16 : 4; break; }
+                    if (bad) { err = bad == ERR_SITE_LONG ? ERR_SITE_LONG : ERR_SITE_ROW; break; }
                     const char first = app[napp];
                     bool differ = false;
                     for (uint32_t base = 0; base < R; base += WAVE) {
@@ -345,7 +345,7 @@ __global__ __launch_bounds__(64, 4) void k_call_sites(SiteArgs a) {
                             for (uint32_t x = 0; x <= site && x < L; ++x)
                                 if (row[x] != '-') push(row[x]);
                             for (uint32_t x = site + 1; n < (uint32_t)k; ++x) {
-                                if (x >= L) { e = 4; break; }
+                                if (x >= L) { e = ERR_SITE_ROW; break; }
                                 if (row[x] != '-') push(row[x]);
                             }
                         } else {
@@ -358,23 +358,23 @@ __global__ __launch_bounds__(64, 4) void k_call_sites(SiteArgs a) {
                         }
                     } else {
                         const long from = (long)site - k + 1;
-                        if (from < 0 || (uint64_t)from > L) e = 4;
+                        if (from < 0 || (uint64_t)from > L) e = ERR_SITE_ROW;
                         else {
                             const uint32_t take = (uint32_t)std::min<uint64_t>((uint64_t)k, L - (uint64_t)from);
                             for (uint32_t x = 0; x < take; ++x) push(row[from + x]);
                         }
                     }
-                    if (n > KS) { e = 16; atomicMax(&a.cnt->ks_need, n); }
+                    if (n > KS) { e = ERR_SITE_LONG; atomicMax(&a.cnt->ks_need, n); }
                     flen[p] = n;
                 }
-                if (__ballot(e == 4)) row_err |= 4;
-                if (__ballot(e == 16)) row_err |= 16;
+                if (__ballot(e == ERR_SITE_ROW)) row_err |= ERR_SITE_ROW;
+                if (__ballot(e == ERR_SITE_LONG)) row_err |= ERR_SITE_LONG;
             }
             if (sr.is_indel) ++indel;
             sync();
             const unsigned long long pc = a.prof ? wall_clock64() : 0;
             pk[2] += pc - pb;
-            if (row_err) { err = (row_err & 4) ? 4 : 16; break; }
+            if (row_err) { err = (row_err & ERR_SITE_ROW) ? ERR_SITE_ROW : ERR_SITE_LONG; break; }
             // distinct strings per allele group in std::set order, their coverage (readCov(string), src/CDBG.cpp:29-60)
             for (uint32_t base = 0; base < R; base += WAVE) {
                 const uint32_t p = base + lane;
@@ -493,7 +493,7 @@ __global__ __launch_bounds__(64, 4) void k_call_sites(SiteArgs a) {
                     }
                     all_seen = all_seen && seen == (C - 64 * w >= 64 ? ~0ull : ((1ull << (C - 64 * w)) - 1));
                 }
-                if (fatal) { err = 64; break; }
+                if (fatal) { err = ERR_SITE_UNITIG; break; }
                 const bool valid = ok && all_seen;
                 if (lane == 0 && room) a.sv[vcur + (uint64_t)C * maxnum] = valid ? 1.0 : 0.0;
                 if (lane == 0) a.osites[r.site_off + si].pad_ = valid ? 1 : 0;
@@ -530,7 +530,7 @@ __global__ __launch_bounds__(64, 4) void k_call_sites(SiteArgs a) {
                 }
                 if (lane == 0 && room) a.sv[vcur + gi] = tc;
             }
-            if (fatal) { err = 2; break; }
+            if (fatal) { err = ERR_MISSING_KMER; break; }
             if (lane == 0 && room) a.sv[vcur + maxnum] = total;
             if (lane == 0) a.osites[r.site_off + si].pad_ = ok ? 1 : 0;
             vcur += maxnum + 1;

@@ -10,8 +10,8 @@ __global__ __launch_bounds__(256) void k_call_prep(PrepArgs a) {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     int key = KEY_NONE;
     unsigned long long need3 = 0, retry = 0;
-    if (j < a.nb) {
-        const CallTask &t = a.ct[a.kept[a.t0 + j]];
+    if (j < a.batch.nb) {
+        const CallTask &t = a.batch.ct[a.batch.kept[a.batch.t0 + j]];
         pf_bubble_result z;
         z.rows_off = z.site_off = z.group_off = z.ilen_off = 0;
         z.n_rows = z.n_cols = z.n_sites = z.n_indel_len = 0;
@@ -82,12 +82,12 @@ __global__ __launch_bounds__(256) void k_call_snp(SnpArgs a) {
     const uint64_t *w0 = nullptr, *w1 = nullptr;
     if (active) {
         j = a.slist[i];
-        const CallTask &t = a.ct[a.kept[a.t0 + j]];
+        const CallTask &t = a.batch.ct[a.batch.kept[a.batch.t0 + j]];
         ov0 = t.inner[0];
         ov1 = t.inner[1];
-        m = a.len[ov0 >> 1];
-        w0 = a.seq + a.off[ov0 >> 1];
-        w1 = a.seq + a.off[ov1 >> 1];
+        m = a.graph.len[ov0 >> 1];
+        w0 = a.graph.seq + a.graph.off[ov0 >> 1];
+        w1 = a.graph.seq + a.graph.off[ov1 >> 1];
         // 32 bases per step from two packed words (the paths are equally long: K-PREP's condition for this list)
         for (uint32_t c = 0; 32 * c < m; ++c) {
             const uint64_t x = oriented_chunk(w0, m, (ov0 & 1) != 0, c) ^ oriented_chunk(w1, m, (ov1 & 1) != 0, c);
@@ -126,9 +126,9 @@ __global__ __launch_bounds__(256) void k_call_snp(SnpArgs a) {
         const uint32_t total = s_wtot[0] + s_wtot[1] + s_wtot[2] + s_wtot[3], cnt = s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
         unsigned long long tb = 0, sb = 0;
         if (cnt) {
-            tb = atomicAdd(&a.heads[0], (unsigned long long)total);
-            sb = atomicAdd(&a.heads[1], (unsigned long long)cnt);
-            atomicAdd(&a.heads[2], 2ull * cnt);   // groups: two bytes per site, at 2 * (site index)
+            tb = atomicAdd(&a.out.heads[0], (unsigned long long)total);
+            sb = atomicAdd(&a.out.heads[1], (unsigned long long)cnt);
+            atomicAdd(&a.out.heads[2], 2ull * cnt);   // groups: two bytes per site, at 2 * (site index)
             atomicAdd(&a.cnt->n_snp_done, cnt);
         }
         s_tb = tb;
@@ -158,8 +158,8 @@ __global__ __launch_bounds__(256) void k_call_snp(SnpArgs a) {
         r.n_cols = m;
         r.n_sites = 1;
         r.n_indel_len = 0;
-        a.res[j] = r;
-        if (t_off + 2ull * m <= a.text_cap && s_off + 1 <= a.site_cap && 2 * s_off + 2 <= a.group_cap) {
+        a.out.res[j] = r;
+        if (t_off + 2ull * m <= a.out.text_cap && s_off + 1 <= a.out.site_cap && 2 * s_off + 2 <= a.out.group_cap) {
             // (two loops, so that the staged one stores through an LDS pointer: one pointer for both would be a generic one, flat stores)
             if (staged) {
                 char *o = stage + my_excl;
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) void k_call_snp(SnpArgs a) {
                     }
                 }
             } else {
-                char *o = a.otext + t_off;
+                char *o = a.out.otext + t_off;
                 for (uint32_t c = 0; 32 * c < m; ++c) {
                     const uint64_t x0 = oriented_chunk(w0, m, (ov0 & 1) != 0, c), x1 = oriented_chunk(w1, m, (ov1 & 1) != 0, c);
                     const uint32_t e = m - 32 * c < 32 ? m - 32 * c : 32;
@@ -182,22 +182,22 @@ __global__ __launch_bounds__(256) void k_call_snp(SnpArgs a) {
                     }
                 }
             }
-            a.ogroups[2 * s_off] = 1;
-            a.ogroups[2 * s_off + 1] = 2;
+            a.out.ogroups[2 * s_off] = 1;
+            a.out.ogroups[2 * s_off + 1] = 2;
             pf_bubble_site sr;
             sr.col = col;
             sr.is_indel = 0;
             sr.maxnum = 2;
             sr.pad_ = 0;
-            a.osites[s_off] = sr;
+            a.out.osites[s_off] = sr;
         }
     }
-    if (tm && staged && wb + wave_total <= a.text_cap) {
+    if (tm && staged && wb + wave_total <= a.out.text_cap) {
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         __builtin_amdgcn_wave_barrier();
         // (in words: the stage is word-aligned, global memory takes the unaligned word; the last one to three bytes singly)
         const uint32_t n_words = wave_total >> 2;
-        char *dst = a.otext + wb;
+        char *dst = a.out.otext + wb;
         for (uint32_t x = lane; x < n_words; x += WAVE) {
             const uint32_t w = reinterpret_cast<const uint32_t *>(stage)[x];
             __builtin_memcpy(dst + 4 * (size_t)x, &w, 4);
@@ -239,8 +239,8 @@ __global__ __launch_bounds__(256) void k_call_pair2_reroute(PairArgs a) {
     uint32_t j = 0;
     if (i < *a.n_list) {
         j = a.list[i];
-        const CallTask &t = a.ct[a.kept[a.t0 + j]];
-        const uint32_t m = a.len[t.inner[0] >> 1], n = a.len[t.inner[1] >> 1];
+        const CallTask &t = a.batch.ct[a.batch.kept[a.batch.t0 + j]];
+        const uint32_t m = a.graph.len[t.inner[0] >> 1], n = a.graph.len[t.inner[1] >> 1];
         key = 2 * bubble_class(m, m > n ? m : n) + (m > 64 || n > 64 ? 0 : 1);
     }
     wave_append(key, j, a.lists, a.cnt);
@@ -266,9 +266,9 @@ __global__ __launch_bounds__(64, NMAX == 64 ? 3 : 2) void k_call_pair(PairArgs a
         bool defer = false;
         if (active) {
             j = a.list[i];
-            const CallTask &t = a.ct[a.kept[a.t0 + j]];
+            const CallTask &t = a.batch.ct[a.batch.kept[a.batch.t0 + j]];
             const uint32_t ov0 = t.inner[0], ov1 = t.inner[1];
-            const uint32_t m = a.len[ov0 >> 1], n = a.len[ov1 >> 1];
+            const uint32_t m = a.graph.len[ov0 >> 1], n = a.graph.len[ov1 >> 1];
             unsigned long long tq = a.prof ? wall_clock64() : 0;
             auto mark = [&](int slot) {
                 if (!a.prof) return;
@@ -278,7 +278,7 @@ __global__ __launch_bounds__(64, NMAX == 64 ? 3 : 2) void k_call_pair(PairArgs a
             };
             uint64_t Aw[Gm::NA], Bw[Gm::NA];
             uint32_t b0[Gm::NA], b1[Gm::NA];
-            const uint64_t *w0 = a.seq + a.off[ov0 >> 1], *w1 = a.seq + a.off[ov1 >> 1];
+            const uint64_t *w0 = a.graph.seq + a.graph.off[ov0 >> 1], *w1 = a.graph.seq + a.graph.off[ov1 >> 1];
 #pragma unroll
             for (int c = 0; c < Gm::NA; ++c) {
                 Aw[c] = 32u * c < m ? oriented_chunk(w0, m, (ov0 & 1) != 0, (uint32_t)c) : 0;
@@ -305,10 +305,10 @@ __global__ __launch_bounds__(64, NMAX == 64 ? 3 : 2) void k_call_pair(PairArgs a
         const bool take = active && !defer;
         // pool space for the whole wavefront: one atomic per pool
         uint32_t e_text, e_sites, e_groups, e_ilen;
-        const unsigned long long b_text = wave_take(&a.heads[0], take ? 2 * L : 0, e_text);
-        const unsigned long long b_sites = wave_take(&a.heads[1], take ? n_sites : 0, e_sites);
-        const unsigned long long b_groups = wave_take(&a.heads[2], take ? 2 * n_sites : 0, e_groups);
-        const unsigned long long b_ilen = wave_take(&a.heads[3], take ? n_ilen : 0, e_ilen);
+        const unsigned long long b_text = wave_take(&a.out.heads[0], take ? 2 * L : 0, e_text);
+        const unsigned long long b_sites = wave_take(&a.out.heads[1], take ? n_sites : 0, e_sites);
+        const unsigned long long b_groups = wave_take(&a.out.heads[2], take ? 2 * n_sites : 0, e_groups);
+        const unsigned long long b_ilen = wave_take(&a.out.heads[3], take ? n_ilen : 0, e_ilen);
         if (take) {
             const unsigned long long t_off = b_text + e_text, s_off = b_sites + e_sites, g_off = b_groups + e_groups, l_off = b_ilen + e_ilen;
             pf_bubble_result r;
@@ -320,12 +320,12 @@ __global__ __launch_bounds__(64, NMAX == 64 ? 3 : 2) void k_call_pair(PairArgs a
             r.n_cols = L;
             r.n_sites = n_sites;
             r.n_indel_len = n_ilen;
-            a.res[j] = r;
-            if (t_off + 2ull * L <= a.text_cap && s_off + n_sites <= a.site_cap && g_off + 2ull * n_sites <= a.group_cap && l_off + n_ilen <= a.ilen_cap) {
-                char *o = a.otext + t_off;
+            a.out.res[j] = r;
+            if (t_off + 2ull * L <= a.out.text_cap && s_off + n_sites <= a.out.site_cap && g_off + 2ull * n_sites <= a.out.group_cap && l_off + n_ilen <= a.out.ilen_cap) {
+                char *o = a.out.otext + t_off;
                 for (uint32_t c = 0; c < L; ++c) { o[c] = PF_AT(mem.fa, c); o[L + c] = PF_AT(mem.fb, c); }
-                (void)pair_classify<true>(mem.fa, mem.fb, L, a.osites + s_off, a.oilen + l_off);
-                for (uint32_t q = 0; q < n_sites; ++q) { a.ogroups[g_off + 2 * q] = 1; a.ogroups[g_off + 2 * q + 1] = 2; }
+                (void)pair_classify<true>(mem.fa, mem.fb, L, a.out.osites + s_off, a.out.oilen + l_off);
+                for (uint32_t q = 0; q < n_sites; ++q) { a.out.ogroups[g_off + 2 * q] = 1; a.out.ogroups[g_off + 2 * q + 1] = 2; }
             }
         }
         const unsigned long long done_m = __ballot(take);
@@ -401,7 +401,7 @@ __device__ inline void stack_load(const StackArgs &a, const pf_bubble_path &pp, 
 #pragma unroll
     for (int w = 0; w < 4; ++w) P.lo[w] = P.hi[w] = 0;
     if (pp.ov != NONE) {
-        const uint64_t *w = a.seq + a.off[pp.ov >> 1];
+        const uint64_t *w = a.graph.seq + a.graph.off[pp.ov >> 1];
 #pragma unroll
         for (int c = 0; c < 4; ++c)
             if (32u * c < pp.len) pair_planes(oriented_chunk(w, pp.len, (pp.ov & 1) != 0, (uint32_t)c), P.lo[c], P.hi[c]);
@@ -509,10 +509,10 @@ __global__ __launch_bounds__(64) void k_call_stack(StackArgs a) {
         }
         const bool take = active && ok;
         uint32_t e_text, e_sites, e_groups, e_ilen;
-        const unsigned long long b_text = wave_take(&a.heads[0], take ? n * L : 0, e_text);
-        const unsigned long long b_sites = wave_take(&a.heads[1], take ? n_sites : 0, e_sites);
-        const unsigned long long b_groups = wave_take(&a.heads[2], take ? n * n_sites : 0, e_groups);
-        const unsigned long long b_ilen = wave_take(&a.heads[3], take ? n_ilen : 0, e_ilen);
+        const unsigned long long b_text = wave_take(&a.out.heads[0], take ? n * L : 0, e_text);
+        const unsigned long long b_sites = wave_take(&a.out.heads[1], take ? n_sites : 0, e_sites);
+        const unsigned long long b_groups = wave_take(&a.out.heads[2], take ? n * n_sites : 0, e_groups);
+        const unsigned long long b_ilen = wave_take(&a.out.heads[3], take ? n_ilen : 0, e_ilen);
         if (take) {
             const unsigned long long t_off = b_text + e_text, s_off = b_sites + e_sites, g_off = b_groups + e_groups, l_off = b_ilen + e_ilen;
             pf_bubble_result r;
@@ -524,21 +524,21 @@ __global__ __launch_bounds__(64) void k_call_stack(StackArgs a) {
             r.n_cols = L;
             r.n_sites = n_sites;
             r.n_indel_len = n_ilen;
-            a.res[j] = r;
-            const bool room = t_off + (uint64_t)n * L <= a.text_cap && s_off + n_sites <= a.site_cap && g_off + (uint64_t)n * n_sites <= a.group_cap &&
-                              l_off + n_ilen <= a.ilen_cap;
+            a.out.res[j] = r;
+            const bool room = t_off + (uint64_t)n * L <= a.out.text_cap && s_off + n_sites <= a.out.site_cap && g_off + (uint64_t)n * n_sites <= a.out.group_cap &&
+                              l_off + n_ilen <= a.out.ilen_cap;
             if (room && gapped) {
-                char *o = a.otext + t_off;
+                char *o = a.out.otext + t_off;
                 for (uint32_t p = 0; p < n; ++p)
                     for (uint32_t c = 0; c < L; ++c) o[(size_t)p * L + c] = grows[(size_t)p * RS + (size_t)c * CS];
-                (void)classify_columns<true>(grows, RS, CS, n, L, a.osites + s_off, a.ogroups + g_off, a.oilen + l_off);
+                (void)classify_columns<true>(grows, RS, CS, n, L, a.out.osites + s_off, a.out.ogroups + g_off, a.out.oilen + l_off);
             } else if (room) {
                 // the rows, and per variant column the bases of all rows
                 for (uint32_t p = 0; p < n; ++p) {
                     const pf_bubble_path pp = a.bpath[first + p];
                     StackPlanes Y;
                     stack_load(a, pp, Y);
-                    char *o = a.otext + t_off + (uint64_t)p * L;
+                    char *o = a.out.otext + t_off + (uint64_t)p * L;
                     for (uint32_t c = 0; c < L; ++c) o[c] = pf::base_char((uint32_t)(stack_code(Y, c)));
                     // this row's base in every variant column, kept in the group bytes for now
                     uint32_t q = 0;
@@ -548,7 +548,7 @@ __global__ __launch_bounds__(64) void k_call_stack(StackArgs a) {
                         while (m) {
                             const uint32_t c = 32u * w + (uint32_t)__ffs((int)m) - 1;
                             m &= m - 1;
-                            a.ogroups[g_off + (uint64_t)q * n + p] = (uint8_t)stack_code(Y, c);
+                            a.out.ogroups[g_off + (uint64_t)q * n + p] = (uint8_t)stack_code(Y, c);
                             ++q;
                         }
                     }
@@ -562,7 +562,7 @@ __global__ __launch_bounds__(64) void k_call_stack(StackArgs a) {
                         const uint32_t c = 32u * w + (uint32_t)__ffs((int)m) - 1;
                         m &= m - 1;
                         uint32_t tab = 0, maxnum = 0;   // group of base b in byte b
-                        uint8_t *gp = a.ogroups + g_off + (uint64_t)q * n;
+                        uint8_t *gp = a.out.ogroups + g_off + (uint64_t)q * n;
                         for (uint32_t p = 0; p < n; ++p) {
                             const uint32_t b = gp[p];
                             uint32_t gr = (tab >> (8 * b)) & 0xFFu;
@@ -574,7 +574,7 @@ __global__ __launch_bounds__(64) void k_call_stack(StackArgs a) {
                         sr.is_indel = 0;
                         sr.maxnum = (uint8_t)maxnum;
                         sr.pad_ = 0;
-                        a.osites[s_off + q] = sr;
+                        a.out.osites[s_off + q] = sr;
                         ++q;
                     }
                 }

@@ -346,6 +346,20 @@ def test_packed_numeric_streams_round_trip(tmp_path):
     assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout
 
 
+def test_call_plan_sizes(tmp_path):
+    """The sizing plan pf_call_align_lane and pf_call_reserve_lanes share (csrc/pf_call_plan.hpp: grids, per-wavefront scratch,
+    first-call pool capacities) against numbers worked out by hand: tests/cpp/test_call_plan.cpp.  Plain g++, no HIP header."""
+    import shutil
+    import subprocess
+    if not shutil.which("g++"):
+        pytest.skip("no g++")
+    exe = str(tmp_path / "test_call_plan")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "ploidyfrost_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "cpp", "test_call_plan.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr
+
+
 def test_bench_cov_roofline_picks_the_streaming_kernel_of_the_workload():
     """bench.py `roofline_k_cov`: K-COV for the single-sample workload (with the committed PMC traffic), K-COV-C for the colored."""
     import bench
