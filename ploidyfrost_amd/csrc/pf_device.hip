@@ -480,9 +480,16 @@ __global__ __launch_bounds__(256) void k_cov_join_rest(const CountLine *__restri
         const JoinRest x = mine[e];
         uint32_t c;
         bool found;
-        if (one_strand) {   // one form to look for, and its first line is known to be full of other keys
+        if (one_strand) {
+            // The table holds at most one form of a k-mer, and K-COV-JOIN has looked for the smaller one in the first line of the
+            // sequence: that look-up goes on from the second line.  Every k-mer it did not find there is handed on, whether the line
+            // was full or not, and `one_strand` does not say that the keys are canonical (check_table_strands: a database may store
+            // a k-mer as its larger form only): what is not found as the smaller form is looked up as the larger one, from the
+            // first line on (src/CDBG.cpp:78-82).  A canonical database pays for that only with k-mers it does not hold.
             const uint64_t rc = rc_kmer(x.fwd, k);
-            found = count_find(t, mask, rc < x.fwd ? rc : x.fwd, kmer_lines(x.fwd, rc, k, mask), c, 1);
+            const LineSeq sq = kmer_lines(x.fwd, rc, k, mask);
+            const uint64_t lo = rc < x.fwd ? rc : x.fwd, hi = rc < x.fwd ? x.fwd : rc;
+            found = count_find(t, mask, lo, sq, c, 1) || (hi != lo && count_find(t, mask, hi, sq, c));
         } else {
             found = canonical_count(t, mask, x.fwd, k, c, false);
         }

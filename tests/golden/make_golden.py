@@ -130,6 +130,9 @@ CASES = {
     "crowd25": (lambda: synth.make_haplotypes(synth.HapSpec(24000, 4, seed=4, gap_lo=8, gap_hi=150, p_multi=0.05),
                                               lambda b: synth.plant_crowded_minimizer(np.random.default_rng(41), b, 17, 100)), 25,
                 ["-l", "5", "-u", "1000"], "kmc1", "haps", "abundant"),
+    # a random half of the database's keys stored as their larger form, the header's both-strands bit set: no k-mer is stored
+    # twice, and a look-up finds the form as read or its reverse complement (src/CDBG.cpp:78-82)
+    "strandmix": (lambda: synth.make_haplotypes(synth.HapSpec(20000, 2, seed=71)), 25, ["-l", "5", "-u", "1000"], "kmc1_strandmix"),
 }
 
 
@@ -247,6 +250,11 @@ def make_case(name: str) -> None:
         if layout == "kmc1_stranded":
             skm, scnt = synth.stranded_counts(km, mult, k)
             synth.write_kmc1(os.path.join(out, "db"), skm, scnt, k, both_strands=False)
+        elif layout == "kmc1_strandmix":
+            flip = np.random.default_rng(7100).random(len(km)) < 0.5
+            mixed = np.where(flip, synth.revcomp_u64(km, k), km)
+            order = np.argsort(mixed)
+            synth.write_kmc1(os.path.join(out, "db"), mixed[order], cnt[order], k, both_strands=True)
         elif layout == "kmc2":
             synth.write_kmc2(os.path.join(out, "db"), km, cnt, k, sig_len=7, n_bins=11)
         else:
