@@ -61,6 +61,7 @@ enum pf_kernel {
     PF_K_CALL_SCAN, PF_K_CALL_PREP, PF_K_CALL_PATHS, PF_K_CALL_SITES, PF_K_CALL_FORMAT, PF_K_CALL_SNP, PF_K_BFS_THREAD, PF_K_CALL_PAIR, PF_K_CALL_STACK,
     PF_K_COV_JOIN_REST, /* second kernel of K-COV-JOIN: the look-ups whose first line was full */
     PF_K_COPY_TEXT, /* not a kernel of this library: the copies of result text to the host (the runtime moves them with a kernel of its own) */
+    PF_K_CALL_MODEL, /* the kernels of one pf_call_model_take (rows of a piece's text -> the model's values), timed as one launch */
     PF_K_COUNT_
 };
 int pf_enable_timing(pf_ctx *, int on);
@@ -602,6 +603,33 @@ int pf_gmm_upload(pf_ctx *, const double *values, uint64_t n);
 uint64_t pf_gmm_count(const pf_ctx *);
 int pf_gmm_fit(pf_ctx *, uint32_t gauss, double m_thre, double n_thre, int32_t max_iter, double max_delta, double *weights,
                double *means, double *vars, double *loglik, uint32_t *iterations);
+/* The values pf_gmm_fit reads, copied to the host: the first min(cap, pf_gmm_count) of them. */
+int pf_gmm_values(pf_ctx *, double *dst, uint64_t cap);
+
+/* ---- the model fed from the resident call streams (csrc/pf_call_model.hip) ----
+ * The values `PloidyFrost model` reads back from <outpre>_bicov / _tricov / _tetracov.txt (-f) or <outpre>_allele_frequency.txt (-g)
+ * are defined by the TEXT of those files; K-TEXT leaves that text in HBM piece by piece.  These three calls turn it into the array
+ * pf_gmm_fit reads without a file, a host loop or a second context, element for element what GmmModel::readCovFile / readFreFile
+ * (csrc/host/pf_gmm_model.cpp, reference src/GmmModel.cpp:21-257) make of the files -- quirks included: atoi on "%g" fields, the
+ * integer frequency test, the neighbour-pair "min", pentacov never read, the last frequency token counted twice.  The per-row rule
+ * is csrc/pf_model_rows.hpp, shared with the host (pfh_model_rows).  Single-sample path only.
+ *   pf_call_model_begin   source PF_MODEL_COV | PF_MODEL_FRE, minimum frequency q (`model -q`); drops the context's GMM array.
+ *   pf_call_model_take    the piece in `slab`: after the pf_call_text / pf_call_text_range(_lane) call that made it, before the next
+ *                         call that writes that slab (which then waits on the device until these kernels have read it).  Pieces
+ *                         are taken in file order, from one thread.  Reads the text as K-TEXT wrote it, so
+ *                         pf_call_set_numeric_packed / pf_call_set_alignseq_packed change nothing.  No wait, no copy to the host.
+ *   pf_call_model_finish  waits; bi | tri | tetra (or the frequencies) end to end where pf_gmm_fit reads them, *n_values =
+ *                         pf_gmm_count.  PF_ERR_ARG with pf_last_error naming stream and row (from 1, over the whole run) when a
+ *                         coverage row sums to 0 (the reference divides by it) or a frequency row is not one number operator>>
+ *                         reads ("nan", "inf") -- the errors the `model` sub-command gives -- or is a number the device cannot
+ *                         convert exactly with one fp64 operation (more than 15 digits, decimal exponent beyond 22; "%g" never
+ *                         prints such a frequency). */
+enum pf_model_source { PF_MODEL_COV = 0, PF_MODEL_FRE = 1 };
+int pf_call_model_begin(pf_ctx *, int source, double q);
+int pf_call_model_take(pf_ctx *, int slab);
+int pf_call_model_finish(pf_ctx *, uint64_t *n_values);
+/* Bytes of the ten result streams the pf_call_fetch* calls of this context have copied to the host so far. */
+uint64_t pf_call_fetched_bytes(const pf_ctx *);
 
 /* ---- pinned host memory for the exchange buffers (optional: pageable memory works, slower) ---- */
 int pf_host_alloc(pf_ctx *, size_t bytes, void **out);

@@ -145,6 +145,30 @@ int pfh_gmm_run(pfh_gmm *, int min_gauss, int max_gauss, double m_thre, double n
 /* enable = 1 / 0 switches the HIP-event timing of the K-GMM launches on / off; enable < 0 reads the totals */
 int pfh_gmm_kernel_time(pfh_gmm *, int enable, double *total_ms, uint64_t *launches);
 
+/* ---- the ploidy estimate in the same run (single-sample path; pf_call_model_* in ploidyfrost_hip.h) ----
+ * pfh_set_model before pfh_ploidy_estimation: that call then feeds the model from the text pieces while they are resident on the
+ * device, fits gauss = lo .. hi on the run's own context and writes <outpre>_model_result.txt -- the bytes
+ * `model -f <outpre>` (source 0, cov) / `model -g <outpre>_allele_frequency.txt` (source 1, fre) write from the files.
+ * source < 0 switches it off again.  only != 0: none of the ten calling files is written and none of their text is copied to the
+ * host.  Options as `PloidyFrost model` checks them (q < 0.5, 1 <= lo <= hi <= PF_GMM_MAX_GAUSS, the rest >= 0); refused for a
+ * colored run.  0 = ok, else pfh_last_error().
+ * After the pass: pfh_model_values copies min(cap, n) values of the device array and returns n; pfh_model_fit returns the record of
+ * `gauss` Gaussians (arrays of gauss doubles; 0 = ok, 1 = no such fit); pfh_model_ploidy the value of the result file's last line
+ * (0 when nothing was fitted); pfh_text_bytes_fetched how many bytes of the ten calling streams that pass copied from the device. */
+int pfh_set_model(pfh_run *, int source, double min_frequency, int lo, int hi, double m_thre, double n_thre, int32_t max_iter,
+                  double max_delta, int only);
+uint64_t pfh_model_values(pfh_run *, double *out, uint64_t cap);
+int pfh_model_fit(const pfh_run *, uint32_t gauss, double *weights, double *means, double *vars, double *loglik, double *aic,
+                  uint32_t *iterations);
+double pfh_model_ploidy(const pfh_run *);
+uint64_t pfh_text_bytes_fetched(const pfh_run *);
+/* The row rule of that path on text in host memory (csrc/pf_model_rows.hpp, the code the device kernels run), no device involved:
+ * source 0: text[0..2] = the bytes of _bicov / _tricov / _tetracov.txt, source 1: text[0] = those of _allele_frequency.txt; the
+ * values in file order to out (at most cap; *n = how many there are).  0 = ok, 1 = an error of the readers (a coverage row that
+ * sums to 0, a token that is no number) or a number the rule does not convert exactly, worded in err. */
+int pfh_model_rows(int source, double min_frequency, const char *const *text, const uint64_t *len, double *out, uint64_t cap,
+                   uint64_t *n, char *err, uint64_t err_cap);
+
 /* The host tier of K-BFS on its own (host/pf_bfs_host.hpp; no device involved): extractSuperBubble_ptr's traversal
  * (src/CDBG.cpp:253-372) from one oriented vertex over CSR rows laid out as pf_build_adjacency returns them.  Fills *record
  * (list_off = 0) and copies its list -- seen[] when an exit was found, the cycle set otherwise -- to `list`.

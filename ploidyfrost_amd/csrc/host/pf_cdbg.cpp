@@ -466,6 +466,20 @@ int CDBG::set_reference_threads(size_t n) {
     return st == PF_OK ? 0 : fail(st, pf_last_error(ctx_));
 }
 
+// (refused without touching the run's status: the caller may set other options and go on)
+int CDBG::set_model(const ModelOptions &o) {
+    auto refuse = [&](const std::string &m) { err_ = m; return (int)PF_ERR_ARG; };
+    if (o.on) {
+        if (col_) return refuse("CCDBG:: the model in the same run is built for the single-sample path only (the colored coverage tables have other columns)");
+        if (o.source != PF_MODEL_COV && o.source != PF_MODEL_FRE) return refuse("CDBG::set_model(): source is cov or fre");
+        if (o.lo < 1 || o.hi < o.lo || o.hi > PF_GMM_MAX_GAUSS) return refuse("CDBG::set_model(): Gaussians lo:hi with 1 <= lo <= hi <= " + std::to_string(PF_GMM_MAX_GAUSS));
+        if (o.q >= 0.5 || o.max_iter < 0 || o.max_delta < 0 || o.m_thre < 0 || o.n_thre < 0) return refuse("CDBG::set_model(): q < 0.5, iterations, delta and thresholds >= 0 (as `model` checks them)");
+    }
+    model_ = o;
+    if (!o.on) model_.only = false;
+    return 0;
+}
+
 int CDBG::join_pending_ids() {
     if (pending_ids_.joinable()) {
         pending_ids_.join();

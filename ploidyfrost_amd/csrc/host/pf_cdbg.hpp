@@ -30,6 +30,7 @@
 #include <utility>
 #include <vector>
 
+#include "pf_gmm_model.hpp"
 #include "pf_host_colors.hpp"
 #include "pf_host_graph.hpp"
 #include "pf_pinned.hpp"
@@ -123,6 +124,27 @@ public:
     // rows of a bubble grouped by arity (src/CDBG.cpp:1829, 2056, 2158-2162, 2550) and its stdout wording; the order of rows
     // stays the deterministic `-t 1` one (the reference's own depends on thread timing).
     int set_reference_threads(size_t n);
+    // The ploidy estimate in the same run (single-sample path, resident pipeline): PloidyEstimation hands every text piece to
+    // pf_call_model_take while it is resident, then fits on the same device context (run_model over a GmmModel that borrows it) and
+    // writes <outpre>_model_result.txt -- what `model -f <outpre>` (source cov) / `model -g <outpre>_allele_frequency.txt` (fre)
+    // writes from the files.  only: none of the ten calling files is written and their text never leaves the device.
+    struct ModelOptions {
+        bool on = false, only = false;
+        int source = 0;          // pf_model_source
+        double q = 0;            // `model -q`
+        int lo = 1, hi = 9;      // Gaussians, i.e. ploidy 2 .. 10 (`model -l / -u`)
+        double m_thre = 5.0, n_thre = 2.0, max_delta = 0.01;
+        int max_iter = 1000;
+    };
+    int set_model(const ModelOptions &o);
+    // of the last PloidyEstimation with a model: one record per number of Gaussians, the value of the result file's last line and
+    // that line; how many values the device array holds
+    const std::vector<GmmModel::Fit> &model_fits() const { return model_fits_; }
+    double model_ploidy() const { return model_ploidy_; }
+    const std::string &model_last_line() const { return model_last_line_; }
+    uint64_t model_count() const { return model_n_; }
+    // bytes of the ten calling streams the last PloidyEstimation copied from the device (0 with ModelOptions::only)
+    uint64_t text_bytes_fetched() const { return text_fetched_; }
     // ---- one graph over several GPUs (reference owner rule src/CDBG.cpp:1190, 1352, 1656-1679) -------------
     // findSuperBubble: every rank traverses the entrances of its unitig range (find_shard), the ranks exchange the records,
     // every rank replays all of them (find_replay; rank 0 writes the file).  PloidyEstimation: the scan and the sequential pass
@@ -185,6 +207,11 @@ protected:
     int finish_find(const std::string &outpre, const FindTrace &tr, bool write_file, bool timing_lines);
     std::vector<pf_bfs_record> shard_rec_;
     std::vector<uint32_t> shard_pool_;
+    ModelOptions model_;
+    std::vector<GmmModel::Fit> model_fits_;
+    double model_ploidy_ = 0;
+    std::string model_last_line_;
+    uint64_t model_n_ = 0, text_fetched_ = 0;
     pf_call_result slice_res_ = {};
     uint64_t slice_nb_ = 0, slice_var_base_ = 0;   // ploidy_align's range and ploidy_text's numbering base, for ploidy_write's pieces
     int fail(int st, const std::string &msg);

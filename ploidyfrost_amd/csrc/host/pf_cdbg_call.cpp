@@ -18,6 +18,7 @@
 #include <deque>
 #include <memory>
 #include <mutex>
+#include <sstream>
 #include <thread>
 
 #include "../pf_alnpack.hpp"
@@ -237,6 +238,14 @@ int CDBG::ploidy_estimation_resident(const std::string &outpre, const std::vecto
     clock_t c0 = clock();
     if (!quiet_) printf("%s::PloidyEstimation():  Analyzing superbubbles to generate sites' information\n", tag_);
     if (write_files_ && ensure_dir()) return status_;
+    if (model_.on && (col_ || !write_files_)) return fail(PF_ERR_ARG, std::string(tag_) + "::PloidyEstimation(): the model in the same run needs the single-sample path and an output directory");
+    // with ModelOptions::only the ten calling files are neither opened nor written, and their text stays on the device
+    const bool write_ten = write_files_ && !model_.only;
+    model_fits_.clear();
+    model_last_line_.clear();
+    model_ploidy_ = 0;
+    model_n_ = 0;
+    const uint64_t fetched_before = pf_call_fetched_bytes(ctx_);
     const unsigned T = threads_ ? threads_ : (unsigned)std::max<size_t>(thr, 1);
     times_.cov_device_s = times_.tasks_s = times_.align_s = times_.sites_s = times_.format_s = times_.write_s = 0;
     times_.tasks = times_.align_jobs = times_.site_strings = 0;
@@ -260,7 +269,7 @@ int CDBG::ploidy_estimation_resident(const std::string &outpre, const std::vecto
     MappedOut *maps = out_maps_.get();
     int open_failed = -1;
     std::thread opener;
-    if (write_files_)
+    if (write_ten)
         opener = std::thread([&] {
             for (size_t i = 0; i < files.size(); ++i)
                 if (maps[i].open_for(outdir_ + "/" + files[i].name)) { open_failed = (int)i; return; }
@@ -289,7 +298,7 @@ int CDBG::ploidy_estimation_resident(const std::string &outpre, const std::vecto
         std::atomic<bool> &stop;
         ~Prefault0Guard() { stop.store(true); if (t.joinable()) t.join(); }
     } prefault0_guard{prefault0, prefault0_stop};
-    if (write_files_ && n_tasks) {
+    if (write_ten && n_tasks) {
         const double nbub = 1.1 * (double)n_tasks;
         // (order: pf_call_stream.  Measured at k = 25, tetraploid: 18.4, 157, 18.0, 0.34, 0.07, 0, 30.2, 0.45, 0.08, 0 bytes per bubble;
         // what is reserved beyond the final size is touched here and cut off again at the end -- 8 ms for 60 MB too many)
@@ -327,6 +336,7 @@ int CDBG::ploidy_estimation_resident(const std::string &outpre, const std::vecto
     // The copy to the host is what a pass ends with: 17.7 MB a piece at 55 GB/s, 0.33 ms each, twelve pieces behind the alignment.
     const bool num_packed = !getenv("PF_NUMERIC_ASCII");
     if (pf_call_set_numeric_packed(ctx_, num_packed ? 1 : 0) != PF_OK) return fail(PF_ERR_HIP, std::string(tag_) + "::PloidyEstimation(): " + pf_last_error(ctx_));
+    if (model_.on && pf_call_model_begin(ctx_, model_.source, model_.q) != PF_OK) return fail(PF_ERR_ARG, std::string(tag_) + "::PloidyEstimation(): " + pf_last_error(ctx_));
     struct PackGuard {   // the sliced calls (ploidy_text, one graph over several ranks) read the text as the device writes it
         pf_ctx *c;
         ~PackGuard() { (void)pf_call_set_alignseq_packed(c, 0); (void)pf_call_set_numeric_packed(c, 0); }
@@ -433,7 +443,7 @@ int CDBG::ploidy_estimation_resident(const std::string &outpre, const std::vecto
             for (int s = 0; s < PF_CALL_STREAMS; ++s) { off[s] = total; total += slab_len(d.res, s); }
             PinnedBuf<char> &hb = cx_.slab[d.hslab];
             // append: every stream at its running offset through a shared mapping, copied by all threads side by side
-            if (write_files_) {
+            if (write_ten) {
                 CopySpan spans[PF_CALL_STREAMS];
                 bool nib_span[PF_CALL_STREAMS] = {};   // the span's source is nibbles: expanded instead of copied
                 size_t n_spans = 0;
@@ -606,22 +616,24 @@ int CDBG::ploidy_estimation_resident(const std::string &outpre, const std::vecto
             const uint64_t rn = r.a1 - r.a0;
             for (uint64_t p0 = 0; p0 < rn; p0 += CHUNK, ++b) {
                 const uint64_t count = std::min<uint64_t>(CHUNK, rn - p0);
-                {   // its device slab was last used by piece b - PF_CALL_SLABS
+                {   // its device slab was last used by piece b - PF_CALL_SLABS (nothing is fetched with ModelOptions::only: the write
+                    // pass then waits on the device for the model's kernels over that piece)
                     std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return stop || b < fetched + PF_CALL_SLABS; });
+                    cv.wait(lk, [&] { return stop || model_.only || b < fetched + PF_CALL_SLABS; });
                     if (stop) return;
                 }
                 Done d;
                 d.slab = (int)(b % PF_CALL_SLABS);
                 d.hslab = (int)(b & 1);
-                const int st = pf_call_text_range_lane(ctx_, r.lane, d.slab, p0, count, var_base, &d.res);
+                int st = pf_call_text_range_lane(ctx_, r.lane, d.slab, p0, count, var_base, &d.res);
+                if (st == PF_OK && model_.on) st = pf_call_model_take(ctx_, d.slab);   // the piece's rows -> the model's values, while it is resident
                 if (st != PF_OK) {
                     { std::lock_guard<std::mutex> lk(mu); if (rc == PF_OK) { rc = st; rc_err = pf_last_error(ctx_); } stop = true; }
                     cv.notify_all();
                     return;
                 }
                 if (trace) fprintf(stderr, "[ploidy]   piece %zu formatted on the device %.2f ms\n", b, since(t_all) * 1e3);
-                if (b == 0 && write_files_) {
+                if (b == 0 && write_ten) {
                     // first piece of a pass: fresh result files get their final size (extrapolated from this piece, cut to the true
                     // one at the end) and their pages now, on helper threads, instead of fault by fault under the writer
                     const double scale = 1.05 * (double)n_tasks / (double)std::max<uint64_t>(1, count);
@@ -650,8 +662,10 @@ int CDBG::ploidy_estimation_resident(const std::string &outpre, const std::vecto
                 for (int a = 0; a < 4; ++a) allele_[a] += d.res.allele[a];
                 core_cov_ += d.res.core_cov;
                 core_num_ += d.res.core_num;
-                { std::lock_guard<std::mutex> lk(mu); ready.push_back(d); }
-                cv.notify_all();
+                if (!model_.only) {
+                    { std::lock_guard<std::mutex> lk(mu); ready.push_back(d); }
+                    cv.notify_all();
+                }
             }
             var_base += r.n_called;
             { std::lock_guard<std::mutex> lk(mu); ++ranges_formatted; }
@@ -733,14 +747,38 @@ int CDBG::ploidy_estimation_resident(const std::string &outpre, const std::vecto
         OutFile &of = files[i];
         out_bytes_ += of.bytes;
         const auto tfin = clk::now();
-        if (write_files_ && maps[i].finish(of.bytes)) of.rc = 1;
+        if (write_ten && maps[i].finish(of.bytes)) of.rc = 1;
         if (trace) fprintf(stderr, "[ploidy]   %s finished at %llu bytes in %.3f ms\n", of.name.c_str(), (unsigned long long)of.bytes, since(tfin) * 1e3);
         if (of.rc) return fail(PF_ERR_ARG, "CDBG:: write error on " + of.name);
     }
-    if (write_files_) { last_allfre_file_ = outdir_ + "/" + files[0].name; last_allfre_bytes_ = files[0].bytes; }
+    if (write_ten) { last_allfre_file_ = outdir_ + "/" + files[0].name; last_allfre_bytes_ = files[0].bytes; }
     write_s += since(t0);
     times_.write_s = write_s;
     tp("files closed");
+    text_fetched_ = pf_call_fetched_bytes(ctx_) - fetched_before;
+    if (model_.on) {
+        // the values lie where K-GMM reads them: the fits of `PloidyFrost model`, on this run's own context
+        // (an error of the model -- the ones `PloidyFrost model` gives on the same files -- ends this call, not the run: the
+        // calling files are complete and the next pass may go ahead)
+        auto model_fail = [&](int st, const std::string &m) { err_ = m; return st ? st : (int)PF_ERR_ARG; };
+        uint64_t n_values = 0;
+        const int ms = pf_call_model_finish(ctx_, &n_values);
+        if (ms != PF_OK) return model_fail(ms, pf_last_error(ctx_));
+        model_n_ = n_values;
+        GmmModel gm;
+        gm.borrow(ctx_, (size_t)n_values);
+        gm.setMThreshold(model_.m_thre);
+        gm.setNThreshold(model_.n_thre);
+        gm.setMaxIterNum(model_.max_iter);
+        gm.setMaxDeltaNum(model_.max_delta);
+        std::string merr;
+        if (run_model(gm, model_.lo, model_.hi, outdir_ + "/" + outpre, merr, &model_ploidy_)) return model_fail(PF_ERR_ARG, merr);
+        model_fits_ = gm.fits();
+        std::ostringstream line;
+        line << "estimated ploidy level is : " << model_ploidy_;
+        model_last_line_ = line.str();
+        tp("model fitted");
+    }
     times_.ploidy_total_s = since(t_all);
     if (!quiet_) {
         printf(mt_format_ ? "%s::PloidyEstimation(): Cpu time : %gs\n" : "%s::PloidyEstimation():  Cpu time : %gs\n", tag_,

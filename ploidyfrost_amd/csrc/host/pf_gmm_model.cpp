@@ -10,7 +10,16 @@
 namespace pfh {
 
 GmmModel::~GmmModel() {
-    if (ctx_) pf_destroy(ctx_);
+    if (ctx_ && !borrowed_) pf_destroy(ctx_);
+}
+
+void GmmModel::borrow(pf_ctx *ctx, size_t n) {
+    if (ctx_ && !borrowed_) pf_destroy(ctx_);
+    ctx_ = ctx;
+    borrowed_ = true;
+    borrowed_n_ = n;
+    uploaded_ = true;   // emIterate() uploads nothing: the values are where pf_gmm_fit reads them
+    allele_fre.clear();
 }
 
 // src/GmmModel.cpp:8-20
@@ -41,6 +50,7 @@ int GmmModel::emIterate() {
         return fail(std::string("GmmModel: ") + pf_last_error(ctx_));
     iterations_ = it;
     computeAIC();
+    fits_.push_back(Fit{gauss, weights, means, vars, logLikelihood, aic, iterations_});
     return 0;
 }
 
@@ -111,7 +121,7 @@ int GmmModel::readCovFile(const std::string &name, const double &frequency) {
 // src/GmmModel.cpp:350-369
 void GmmModel::output(std::ostream &os) const {
     os << "ploidy : " << gauss + 1 << "\tgauss : " << gauss << std::endl;
-    os << "avg loglikelihood : " << getLogLikelihood() / allele_fre.size() << std::endl;
+    os << "avg loglikelihood : " << getLogLikelihood() / size() << std::endl;
     os << "AIC : " << getAIC() << std::endl;
     os << "means :\t" << std::endl << "\t";
     for (size_t i = 0; i < gauss; i++) os << means[i] << "\t";
@@ -128,7 +138,7 @@ void GmmModel::output(std::ostream &os) const {
 void GmmModel::print() const {
     std::ostream &os = std::cout;
     os << "ploidy:\t" << gauss + 1 << "\tgauss:\t" << gauss << std::endl;
-    os << "avg loglikelihood:\t" << getLogLikelihood() / allele_fre.size() << std::endl;
+    os << "avg loglikelihood:\t" << getLogLikelihood() / size() << std::endl;
     os << "AIC:\t" << getAIC() << std::endl;
     os << "means:\t" << std::endl << "\t";
     for (size_t i = 0; i < gauss; i++) os << means[i] << "\t";
@@ -142,7 +152,7 @@ void GmmModel::print() const {
 }
 
 // src/Main.cpp:659-690
-int run_model(GmmModel &model, int lo, int hi, const std::string &outprefix, std::string &err) {
+int run_model(GmmModel &model, int lo, int hi, const std::string &outprefix, std::string &err, double *ploidy) {
     std::ofstream outfile(outprefix + "_model_result.txt", std::ios::out | std::ios::trunc);
     if (!outfile.is_open()) { err = "ERROR: open output file " + outprefix + "_model_result.txt error!"; return 1; }
     double maxll = DBL_MIN, minaic = DBL_MAX, ll_p = 0, aic_p = 0;
@@ -156,6 +166,7 @@ int run_model(GmmModel &model, int lo, int hi, const std::string &outprefix, std
     outfile << "max loglikelihood : " << maxll << "\tploidy : " << ll_p << std::endl;
     outfile << "min AIC : " << minaic << "\tploidy : " << aic_p << std::endl;
     outfile << "estimated ploidy level is : " << aic_p << std::endl;
+    if (ploidy) *ploidy = aic_p;
     return 0;
 }
 

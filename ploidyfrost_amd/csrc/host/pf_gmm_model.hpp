@@ -2,6 +2,8 @@
 // (pf_gmm_upload / pf_gmm_fit, ../pf_gmm.hip).  Same method names and argument meaning; errors come back as a status plus
 // error() instead of exit().  The readers run on the host -- they are the reference's text parsing, quirks included -- and
 // need no device; emIterate() creates the device context on first use and fails without a gfx950 device (no CPU fit).
+// borrow(): a model over values that are already resident in somebody else's context (pf_call_model_finish: the calling pipeline's
+// own run) -- no second context, no upload, no host copy of the values.
 #pragma once
 #include <cstddef>
 #include <ostream>
@@ -27,11 +29,23 @@ public:
     int emIterate();   // 0 = ok
     double getLogLikelihood() const { return logLikelihood; }
     double computeAIC() {
-        aic = (2 * ((double)gauss * 2 - 1) - 2 * logLikelihood) / (double)allele_fre.size();
+        aic = (2 * ((double)gauss * 2 - 1) - 2 * logLikelihood) / (double)size();
         return aic;
     }
     double getAIC() const { return aic; }
     void readData(const std::vector<double> &v) { allele_fre = v; uploaded_ = false; }
+    // the n values pf_gmm_fit finds resident in ctx (not owned, not destroyed); values() stays empty
+    void borrow(pf_ctx *ctx, size_t n);
+    size_t size() const { return borrowed_ ? borrowed_n_ : allele_fre.size(); }   // values the fit runs over
+    // one record per emIterate() since the last clear_fits(): what output() prints, as numbers
+    struct Fit {
+        size_t gauss;
+        std::vector<double> weights, means, vars;
+        double loglik, aic;
+        unsigned iterations;
+    };
+    const std::vector<Fit> &fits() const { return fits_; }
+    void clear_fits() { fits_.clear(); }
     int readFreFile(const std::string &filename, const double &freq);
     int readCovFile(const std::string &prefix, const double &freq);
     void output(std::ostream &os) const;
@@ -58,10 +72,14 @@ private:
     int device_;
     pf_ctx *ctx_ = nullptr;
     bool uploaded_ = false;
+    bool borrowed_ = false;
+    size_t borrowed_n_ = 0;
+    std::vector<Fit> fits_;
     std::string err_;
 };
 
 // `PloidyFrost model` after option parsing (src/Main.cpp:644-692): fits gauss = lo .. hi, writes <outprefix>_model_result.txt
-int run_model(GmmModel &model, int lo, int hi, const std::string &outprefix, std::string &err);
+// *ploidy (optional): the value of the file's last line
+int run_model(GmmModel &model, int lo, int hi, const std::string &outprefix, std::string &err, double *ploidy = nullptr);
 
 }  // namespace pfh

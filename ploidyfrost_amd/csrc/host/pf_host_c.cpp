@@ -8,6 +8,7 @@
 #include "pf_bfs_host.hpp"
 #include "pf_cdbg.hpp"
 #include "pf_trace.hpp"
+#include "../pf_model_rows.hpp"
 #include "pf_filter.hpp"
 #include "pf_gmm_model.hpp"
 #include "pf_host_colors.hpp"
@@ -570,6 +571,86 @@ int pfh_gmm_kernel_time(pfh_gmm *m, int enable, double *total_ms, uint64_t *laun
     if (!ctx) return 1;
     if (enable >= 0) return pf_enable_timing(ctx, enable);
     return pf_kernel_time(ctx, PF_K_GMM, total_ms, launches);
+}
+
+// ---- the model in the same run ---------------------------------------------------------------------------------------
+int pfh_set_model(pfh_run *r, int source, double min_frequency, int lo, int hi, double m_thre, double n_thre, int32_t max_iter,
+                  double max_delta, int only) {
+    return guarded(r, [&] {
+        pfh::CDBG::ModelOptions o;
+        o.on = source >= 0;
+        o.only = only != 0;
+        o.source = source;
+        o.q = min_frequency;
+        o.lo = lo; o.hi = hi;
+        o.m_thre = m_thre; o.n_thre = n_thre; o.max_iter = max_iter; o.max_delta = max_delta;
+        return r->cdbg->set_model(o);
+    });
+}
+uint64_t pfh_model_values(pfh_run *r, double *out, uint64_t cap) {
+    const uint64_t n = r->cdbg->model_count();
+    if (out && cap && n && pf_gmm_values(r->cdbg->device(), out, cap) != PF_OK) return 0;
+    return n;
+}
+int pfh_model_fit(const pfh_run *r, uint32_t gauss, double *weights, double *means, double *vars, double *loglik, double *aic,
+                  uint32_t *iterations) {
+    for (const pfh::GmmModel::Fit &f : r->cdbg->model_fits()) {
+        if (f.gauss != gauss) continue;
+        for (uint32_t i = 0; i < gauss; ++i) {
+            if (weights) weights[i] = f.weights[i];
+            if (means) means[i] = f.means[i];
+            if (vars) vars[i] = f.vars[i];
+        }
+        if (loglik) *loglik = f.loglik;
+        if (aic) *aic = f.aic;
+        if (iterations) *iterations = f.iterations;
+        return 0;
+    }
+    return 1;
+}
+double pfh_model_ploidy(const pfh_run *r) { return r->cdbg->model_ploidy(); }
+uint64_t pfh_text_bytes_fetched(const pfh_run *r) { return r->cdbg->text_bytes_fetched(); }
+
+// the device kernels' steps over one stream, in order, on the host: rows end at line feeds (a last row without one ends with the
+// text), the row rule, and for the frequencies readFreFile's last turn
+int pfh_model_rows(int source, double min_frequency, const char *const *text, const uint64_t *len, double *out, uint64_t cap,
+                   uint64_t *n, char *err, uint64_t err_cap) {
+    if ((source != pf::MODEL_COV && source != pf::MODEL_FRE) || !text || !len || !n) return 1;
+    static const char *name[2][3] = {{"_bicov", "_tricov", "_tetracov"}, {"_allele_frequency", "", ""}};
+    uint64_t count = 0;
+    auto put = [&](double v) { if (out && count < cap) out[count] = v; ++count; };
+    auto say = [&](int code, int ord, uint64_t row) {
+        const std::string where = "row " + std::to_string(row + 1) + " of stream " + name[source][ord];
+        const std::string m = code == pf::MODEL_ROW_COV_ZERO ? "Model::readCovFile() : " + where + " sums to 0 (the reference divides by it)"
+                            : code == pf::MODEL_ROW_BAD_TOKEN ? "ERROR: " + where + " holds something that is not a number"
+                                                              : "ERROR: " + where + " holds a number outside what the device converts exactly (more than 15 digits or a decimal exponent beyond 22)";
+        if (err && err_cap) { strncpy(err, m.c_str(), err_cap - 1); err[err_cap - 1] = 0; }
+        return 1;
+    };
+    const int n_ord = source == pf::MODEL_COV ? 3 : 1;
+    for (int ord = 0; ord < n_ord; ++ord) {
+        const char *s = text[ord];
+        const uint64_t L = len[ord];
+        if (L >= 0xFFFFFFF0ull) return 1;
+        double last = 0;
+        bool have_last = false;
+        uint64_t row = 0;
+        for (uint64_t start = 0; start < L; ++row) {
+            uint64_t end = start;
+            while (end < L && s[end] != '\n') ++end;
+            double v[4];
+            int code = pf::MODEL_ROW_OK;
+            const int k = source == pf::MODEL_COV ? pf::model_cov_row(s + start, (uint32_t)(end - start), ord + 2, min_frequency, v, &code)
+                                                  : pf::model_fre_row(s + start, (uint32_t)(end - start), min_frequency, v, &code);
+            if (code != pf::MODEL_ROW_OK) return say(code, ord, row);
+            for (int i = 0; i < k; ++i) put(v[i]);
+            if (source == pf::MODEL_FRE) { last = v[0]; have_last = true; }
+            start = end + 1;
+        }
+        if (source == pf::MODEL_FRE && have_last && L && s[L - 1] == '\n' && pf::model_fre_keep(last, min_frequency)) put(last);
+    }
+    *n = count;
+    return 0;
 }
 
 uint64_t pfh_bifrost_kmer_hash(uint64_t left_aligned_kmer, uint64_t seed) { return pfh::bifrost_kmer_hash(left_aligned_kmer, seed); }

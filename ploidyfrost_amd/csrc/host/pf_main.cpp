@@ -59,7 +59,14 @@ void PrintUsage() {
          << "  --ref-threads N N > 1: text format of the reference's `-t N` run (ids from 0, allele_frequency grouped by arity)" << endl
          << "  --gpus N        one graph over N GPUs of this node (single-sample path): one process per GPU, the bubble list cut into N slices," << endl
          << "                  two small all-gathers over RCCL, every rank writes its slabs into the shared result files" << endl
-         << "  --detach-teardown  return as soon as the result files are complete; a child process gives the device memory back" << endl << endl
+         << "  --detach-teardown  return as soon as the result files are complete; a child process gives the device memory back" << endl
+         << "  --model cov|fre    the ploidy estimate in the same run (single-sample path, one GPU): <prefix>_model_result.txt as" << endl
+         << "                  `model -f <prefix>` (cov) / `model -g <prefix>_allele_frequency.txt` (fre) writes it, fitted from the" << endl
+         << "                  result text while it is on the device; its last line is printed as well" << endl
+         << "  --model-ploidy LO:HI  Gaussians to fit, ploidy - 1 (default 1:9; `model -l / -u`)" << endl
+         << "  --model-q Q     minimum allele frequency (default 0; `model -q`)" << endl
+         << "  --model-m M, --model-n N, --model-iter K, --model-delta A   `model -m / -n / -k / -a` (defaults 5, 2, 1000, 0.01)" << endl
+         << "  --model-only    write <prefix>_model_result.txt but none of the ten calling files; their text never leaves the device" << endl << endl
          << "Usage: PloidyFrost cutoffL kmer_histogram_file" << endl
          << "Usage: PloidyFrost cutoffU kmer_histogram_file (quantile[<1 ,default:0.998])" << endl << endl
          << "Usage: PloidyFrost model ...          (GMM ploidy inference from the coverage / frequency files; `PloidyFrost model` prints its options)" << endl
@@ -111,6 +118,11 @@ struct Options {
     int coverage_lower = 10, coverage_upper = 1000, k = 25;
     vector<pair<int, int>> coverage_vec;
     double match = 2, mismatch = -1, gap = -3, frequency = 0.998;
+    // --model ...: the estimate in the same run
+    string model_source, model_ploidy = "1:9";
+    bool model_only = false, model_option_seen = false;
+    double model_q = 0, model_m = 5.0, model_n = 2.0, model_delta = 0.01;
+    int model_iter = 1000;
 };
 
 bool file_exists(const string &p) {
@@ -227,10 +239,25 @@ int main(int argc, char **argv) {
             for (int j = i; j + 2 <= argc; ++j) argv[j] = j + 2 < argc ? argv[j + 2] : nullptr;
             argc -= 2;
             --i;
-        } else if (strcmp(argv[i], "--detach-teardown") == 0) {
-            opt.detach_teardown = true;
+        } else if (strcmp(argv[i], "--detach-teardown") == 0 || strcmp(argv[i], "--model-only") == 0) {
+            if (argv[i][2] == 'd') opt.detach_teardown = true;
+            else opt.model_only = opt.model_option_seen = true;
             for (int j = i; j + 1 <= argc; ++j) argv[j] = j + 1 < argc ? argv[j + 1] : nullptr;
             argc -= 1;
+            --i;
+        } else if (strncmp(argv[i], "--model", 7) == 0 && i + 1 < argc) {
+            const string name = argv[i], val = argv[i + 1];
+            if (name == "--model") opt.model_source = val;
+            else if (name == "--model-ploidy") opt.model_ploidy = val;
+            else if (name == "--model-q") opt.model_q = atof(val.c_str());
+            else if (name == "--model-m") opt.model_m = atof(val.c_str());
+            else if (name == "--model-n") opt.model_n = atof(val.c_str());
+            else if (name == "--model-iter") opt.model_iter = atoi(val.c_str());
+            else if (name == "--model-delta") opt.model_delta = atof(val.c_str());
+            else { cerr << "Error: unknown option " << name << endl; return 1; }
+            opt.model_option_seen = true;
+            for (int j = i; j + 2 <= argc; ++j) argv[j] = j + 2 < argc ? argv[j + 2] : nullptr;
+            argc -= 2;
             --i;
         }
     }
@@ -260,6 +287,30 @@ int main(int argc, char **argv) {
                 PrintUsage();
                 exit(EXIT_FAILURE);
         }
+    }
+    // --model: refused here, before anything is read or written
+    pfh::CDBG::ModelOptions model;
+    if (opt.model_option_seen) {
+        if (opt.model_source.empty()) { cerr << "Error: the --model-... options need --model cov|fre" << endl; return 1; }
+        if (opt.model_source != "cov" && opt.model_source != "fre") { cerr << "Error: --model " << opt.model_source << ": the source is cov or fre" << endl; return 1; }
+        if (!opt.colorfile.empty()) { cerr << "Error: --model reads the single-sample result streams; with -f the coverage tables have other columns" << endl; return 1; }
+        if (opt.gpus > 1) { cerr << "Error: --model and --gpus " << opt.gpus << " do not go together (each rank holds a slice of the values)" << endl; return 1; }
+        int lo = 0, hi = 0;
+        char tail = 0;
+        if (sscanf(opt.model_ploidy.c_str(), "%d:%d%c", &lo, &hi, &tail) != 2 || lo < 1 || hi < lo || hi > PF_GMM_MAX_GAUSS) {
+            cerr << "Error: --model-ploidy " << opt.model_ploidy << ": LO:HI Gaussians with 1 <= LO <= HI <= " << PF_GMM_MAX_GAUSS << endl;
+            return 1;
+        }
+        if (opt.model_q >= 0.5) { cerr << "Error: --model-q: frequency cutoff value should < 0.5" << endl; return 1; }
+        if (opt.model_iter < 0) { cerr << "Error: --model-iter: iterate count should > 0" << endl; return 1; }
+        if (opt.model_delta < 0) { cerr << "Error: --model-delta: iterate delta should > 0" << endl; return 1; }
+        if (opt.model_m < 0 || opt.model_n < 0) { cerr << "Error: --model-m / --model-n: minimum threshold should > 0" << endl; return 1; }
+        model.on = true;
+        model.only = opt.model_only;
+        model.source = opt.model_source == "cov" ? PF_MODEL_COV : PF_MODEL_FRE;
+        model.q = opt.model_q;
+        model.lo = lo; model.hi = hi;
+        model.m_thre = opt.model_m; model.n_thre = opt.model_n; model.max_iter = opt.model_iter; model.max_delta = opt.model_delta;
     }
     // check_ProgramOptions (:278-541), single-sample subset
     bool ok = true;
@@ -562,6 +613,7 @@ int main(int argc, char **argv) {
         if (rc) { cerr << "a rank ended with status " << rc << endl; _exit(rc); }
         _exit(0);
     }
+    if (model.on && g.set_model(model)) die();
     if (g.setUnitigId(opt.outprefix, opt.graphfile, opt.nb_threads)) die();
     if (opt.info && g.printInfo(opt.verbose, opt.outprefix)) die();
     mark("setUnitigId");
@@ -571,6 +623,7 @@ int main(int argc, char **argv) {
     cout << "CDBG:: Maximum Coverage:" << opt.coverage_upper << endl;
     if (g.ploidyEstimation_multithread_ptr(opt.outprefix, opt.coverage_lower, opt.coverage_upper, opt.nb_threads)) die();
     mark("PloidyEstimation");
+    if (model.on) cout << g.model_last_line() << endl;
     if (opt.verbose) {
         const pfh::PhaseTimes &t = g.times();
         printf("[device] candidates %llu (big tier %llu)  bfs %.3fs replay %.3fs | cov %.3fs tasks %.3fs (%llu) align %.3fs (%llu jobs) "

@@ -1107,6 +1107,8 @@ static int call_text_impl(pf_ctx *ctx, int lane, int slab, uint64_t first, uint6
         all += slab_len(s);
     }
     if (fa.packed) { fa.out[S_PACK] = fa.out[PF_OUT_ALIGNSEQ]; fa.out[PF_OUT_ALIGNSEQ] = nullptr; }
+    // (a piece pf_call_model_take is still reading out of this slab: the write pass waits for it)
+    if (S->model.read_ev[slab]) PF_HIP(hipStreamWaitEvent(st, S->model.read_ev[slab], 0));
     ctx_begin_at(ctx, PF_K_CALL_FORMAT, st, &at);
     if (S->n_colors) k_call_format<true, true><<<(nb + FMT_BLOCK - 1) / FMT_BLOCK, FMT_BLOCK, 0, st>>>(fa);
     else k_call_format<true, false><<<(nb + FMT_BLOCK - 1) / FMT_BLOCK, FMT_BLOCK, 0, st>>>(fa);
@@ -1186,6 +1188,7 @@ int pf_call_fetch_text(pf_ctx *ctx, int slab, int stream, char *dst, uint64_t le
     if (S->text_ev[slab] && hipStreamWaitEvent(S->copy_stream, S->text_ev[slab], 0) != hipSuccess) return PF_ERR_HIP;
     if (hipMemcpyAsync(dst, S->out[slab].as<char>() + S->txt_off[slab][stream], (size_t)len, hipMemcpyDeviceToHost, S->copy_stream) != hipSuccess) return PF_ERR_HIP;
     if (hipStreamSynchronize(S->copy_stream) != hipSuccess) return PF_ERR_HIP;
+    S->fetched_bytes.fetch_add(len, std::memory_order_relaxed);
     return PF_OK;
 }
 
@@ -1234,6 +1237,7 @@ int pf_call_fetch(pf_ctx *ctx, int slab, int stream, char *dst, uint64_t len) {
     if (S->text_ev[slab] && hipStreamWaitEvent(S->copy_stream, S->text_ev[slab], 0) != hipSuccess) return PF_ERR_HIP;
     if (hipMemcpyAsync(dst, S->fetch_base[slab] + S->out_off[slab][stream], (size_t)len, hipMemcpyDeviceToHost, S->copy_stream) != hipSuccess) return PF_ERR_HIP;
     if (hipStreamSynchronize(S->copy_stream) != hipSuccess) return PF_ERR_HIP;
+    S->fetched_bytes.fetch_add(len, std::memory_order_relaxed);
     return PF_OK;
 }
 
@@ -1267,6 +1271,7 @@ int pf_call_fetch_slab(pf_ctx *ctx, int slab, char *dst, const uint64_t *len) {
     }
     ctx_end_at(ctx, tl_at, S->copy_stream);
     if (hipStreamSynchronize(S->copy_stream) != hipSuccess) return PF_ERR_HIP;
+    S->fetched_bytes.fetch_add(at, std::memory_order_relaxed);
     return PF_OK;
 }
 
@@ -1287,6 +1292,7 @@ int pf_call_fetch_range(pf_ctx *ctx, int slab, uint64_t first_byte, char *dst, u
     if (len && hipMemcpyAsync(dst, S->fetch_base[slab] + first_byte, (size_t)len, hipMemcpyDeviceToHost, S->copy_stream) != hipSuccess) return PF_ERR_HIP;
     ctx_end_at(ctx, tl_at, S->copy_stream);
     if (hipEventRecord(S->fetch_ev[slot], S->copy_stream) != hipSuccess) return PF_ERR_HIP;
+    S->fetched_bytes.fetch_add(len, std::memory_order_relaxed);
     return PF_OK;
 }
 

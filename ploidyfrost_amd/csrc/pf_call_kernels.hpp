@@ -186,7 +186,24 @@ struct CallState {
     hipEvent_t fetch_ev[2] = {nullptr, nullptr};   // pf_call_fetch_range / pf_call_fetch_wait
     hipEvent_t text_ev[PF_CALL_SLABS] = {};        // the write pass of the piece in a slab has finished (the fetches wait for it on their stream)
     bool mt_format = false;   // pf_call_set_format
+    std::atomic<uint64_t> fetched_bytes{0};   // pf_call_fetched_bytes
+    // pf_call_model_* (pf_call_model.hip): the model's values made of the slabs' text, on a stream of its own
+    struct ModelWork {
+        bool active = false;
+        int source = 0;
+        double q = 0;
+        hipStream_t stream = nullptr;
+        DevBuf state, flags, ends, nvals, voff, n_rows, scan;   // the collection's record; per piece: line-feed flags, row ends, values per row, their offsets
+        DevBuf vals[3];                                         // the values of each stream of the source, in file order
+        uint64_t bound[3] = {};                                 // values the text taken so far can hold at most
+        hipEvent_t read_ev[PF_CALL_SLABS] = {};                 // the kernels over a slab's piece have read it
+    } model;
     void release_all() {
+        for (DevBuf *b : {&model.state, &model.flags, &model.ends, &model.nvals, &model.voff, &model.n_rows, &model.scan, &model.vals[0], &model.vals[1], &model.vals[2]}) b->release();
+        if (model.stream) { (void)hipStreamDestroy(model.stream); model.stream = nullptr; }
+        for (hipEvent_t &e : model.read_ev)
+            if (e) { (void)hipEventDestroy(e); e = nullptr; }
+        model.active = false;
         DevBuf *all[] = {&col_low, &col_up, &col_full, &col_size, &part_first, &part_colour, &part_word, &part_bits, &ccov_sum, &ccov_min, &ccov_max, &ccov_miss,
                          &flags, &plus, &minus, &cov_sum, &cov_min, &cov_miss, &side_cnt, &side_base, &sides, &ctask, &scan_tmp, &target, &pending, &killed, &rstate, &rflag, &rsmall, &kept, &sb_cnt, &sb_base, &sb_sizes, &sb_offs, &sb_out,
                          };

@@ -12,6 +12,7 @@
 // rounding (tests state the tolerance), the summation order is fixed so that runs are reproducible bit for bit.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <string>
@@ -190,6 +191,18 @@ int pf_gmm_upload(pf_ctx *ctx, const double *x, uint64_t n) {
 }
 
 uint64_t pf_gmm_count(const pf_ctx *ctx) { return ctx && ctx->gmm_loaded ? ctx->gmm_n : 0; }
+
+int pf_gmm_values(pf_ctx *ctx, double *dst, uint64_t cap) {
+    if (!ctx || !ctx->gmm_loaded || (cap && !dst)) return PF_ERR_ARG;
+    const uint64_t n = std::min<uint64_t>(cap, ctx->gmm_n);
+    if (n == 0) return PF_OK;
+    PF_HIP(hipSetDevice(ctx->device));
+    const double *dx = (const double *)ctx_ws(ctx, WS_GMM_X, (size_t)ctx->gmm_n * 8);
+    if (!dx) return PF_ERR_HIP;
+    PF_HIP(hipMemcpyAsync(dst, dx, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PF_HIP(hipStreamSynchronize(ctx->stream));
+    return PF_OK;
+}
 
 int pf_gmm_fit(pf_ctx *ctx, uint32_t gauss, double m_thre, double n_thre, int32_t max_iter, double max_delta, double *weights,
                double *means, double *vars, double *loglik, uint32_t *iterations) {

@@ -32,7 +32,8 @@ DECLARED_SYMBOLS = ["pfh_open", "pfh_close", "pfh_last_error", "pfh_set_output_d
                     "pfh_colors_unitig", "pfh_bifrost_kmer_hash", "pfh_gfa_abundant_kmers", "pfh_gfa_write_unitig_ids", "pfh_gfa_write_unitig_ids_given_inputs", "pfh_gfa_numbering_replays", "pfh_gfa_minimizer_counts", "pfh_host_walk", "pfh_host_walk_range", "pfh_replay_open", "pfh_replay_close", "pfh_replay_apply", "pfh_replay_state", "pfh_replay_apply_parallel", "pfh_side_components", "pfh_replay_check_footprints", "pfh_colors_check_footprints",
                     "pfh_find_shard", "pfh_shard_records", "pfh_shard_pool", "pfh_find_replay", "pfh_set_replay_threads", "pfh_set_write_super_bubble", "pfh_ploidy_select", "pfh_ploidy_select_colored", "pfh_ploidy_align", "pfh_ploidy_text", "pfh_ploidy_write",
                     "pfh_gmm_open", "pfh_gmm_close", "pfh_gmm_last_error", "pfh_gmm_read_fre", "pfh_gmm_read_cov", "pfh_gmm_set_values",
-                    "pfh_gmm_size", "pfh_gmm_values", "pfh_gmm_fit", "pfh_gmm_run", "pfh_gmm_kernel_time"]
+                    "pfh_gmm_size", "pfh_gmm_values", "pfh_gmm_fit", "pfh_gmm_run", "pfh_gmm_kernel_time",
+                    "pfh_set_model", "pfh_model_values", "pfh_model_fit", "pfh_model_ploidy", "pfh_text_bytes_fetched", "pfh_model_rows"]
 
 
 def load_library() -> C.CDLL:
@@ -129,6 +130,16 @@ def load_library() -> C.CDLL:
     L.pfh_replay_state.argtypes = [vp, vp, vp, vp]
     L.pfh_bifrost_kmer_hash.restype = C.c_uint64
     L.pfh_bifrost_kmer_hash.argtypes = [C.c_uint64, C.c_uint64]
+    d = C.c_double
+    L.pfh_set_model.argtypes = [vp, C.c_int, d, C.c_int, C.c_int, d, d, C.c_int32, d, C.c_int]
+    L.pfh_model_values.restype = u64
+    L.pfh_model_values.argtypes = [vp, vp, u64]
+    L.pfh_model_fit.argtypes = [vp, u32, vp, vp, vp, C.POINTER(d), C.POINTER(d), C.POINTER(u32)]
+    L.pfh_model_ploidy.restype = d
+    L.pfh_model_ploidy.argtypes = [vp]
+    L.pfh_text_bytes_fetched.restype = u64
+    L.pfh_text_bytes_fetched.argtypes = [vp]
+    L.pfh_model_rows.argtypes = [C.c_int, d, C.POINTER(C.c_char_p), C.POINTER(u64), vp, u64, C.POINTER(u64), C.c_char_p, u64]
     _lib = L
     return L
 
@@ -248,6 +259,31 @@ class Colors:
         return out, sz, nf.value
 
 
+MODEL_SOURCES = {"cov": 0, "fre": 1}
+
+
+def model_rows(source: str, texts, q: float = 0.0) -> np.ndarray:
+    """The model's values as the shared row rule (csrc/pf_model_rows.hpp, what the device kernels run) reads them from text in
+    host memory: source "cov" with the bytes of (_bicov, _tricov, _tetracov), source "fre" with those of _allele_frequency.
+    No device.  RuntimeError with the readers' wording for a coverage row that sums to 0 or a token that is no number."""
+    L = load_library()
+    if isinstance(texts, (bytes, bytearray)):
+        texts = [texts]
+    texts = [bytes(t) for t in texts]
+    want = 3 if source == "cov" else 1
+    if len(texts) != want:
+        raise ValueError("source %s takes %d texts" % (source, want))
+    ptrs = (C.c_char_p * 3)(*(texts + [None] * (3 - len(texts))))
+    lens = (C.c_uint64 * 3)(*([len(t) for t in texts] + [0] * (3 - len(texts))))
+    n = C.c_uint64()
+    err = C.create_string_buffer(512)
+    cap = sum(len(t) for t in texts) + 2
+    out = np.zeros(cap, dtype=np.float64)
+    if L.pfh_model_rows(MODEL_SOURCES[source], q, ptrs, lens, out.ctypes.data, cap, C.byref(n), err, len(err)) != 0:
+        raise RuntimeError(err.value.decode() or "pfh_model_rows failed")
+    return out[: n.value].copy()
+
+
 def load_trace(reset: bool = True) -> list:
     """[(step, seconds)] of the loads of this process since the last reset (pfh_load_trace)"""
     L = load_library()
@@ -319,6 +355,37 @@ class Run:
 
     def ploidy_estimation(self, outpre: str, lower: int = 10, upper: int = 1000):
         self._check(self.L.pfh_ploidy_estimation(self.h, outpre.encode(), lower, upper))
+
+    def set_model(self, source, q: float = 0.0, lo: int = 1, hi: int = 9, m_thre: float = 5.0, n_thre: float = 2.0,
+                  max_iter: int = 1000, max_delta: float = 0.01, only: bool = False):
+        """The ploidy estimate in the same run: the next ploidy_estimation feeds K-GMM from the result text while it is on the
+        device and writes <outpre>_model_result.txt (source "cov": as `model -f <outpre>`, "fre": as `model -g
+        <outpre>_allele_frequency.txt`; lo .. hi Gaussians = ploidy lo + 1 .. hi + 1).  only: none of the ten calling files.
+        source None switches it off."""
+        src = -1 if source is None else MODEL_SOURCES[source]
+        self._check(self.L.pfh_set_model(self.h, src, q, lo, hi, m_thre, n_thre, max_iter, max_delta, int(only)))
+
+    def model_values(self) -> np.ndarray:
+        """the array K-GMM fitted in the last ploidy_estimation, copied from the device"""
+        n = self.L.pfh_model_values(self.h, None, 0)
+        out = np.zeros(n, dtype=np.float64)
+        if n and self.L.pfh_model_values(self.h, out.ctypes.data, n) != n:
+            raise hipapi.DeviceError(hipapi.PF_ERR_HIP, "pfh_model_values: copy from the device failed")
+        return out
+
+    def model_result(self) -> dict:
+        """{"fits": {gauss: {weights, means, vars, loglik, aic, iterations}}, "ploidy": last line of the result file, "values": n}"""
+        fits = {}
+        for g in range(1, 17):
+            w, mean, var = (np.zeros(g) for _ in range(3))
+            ll, aic, it = C.c_double(), C.c_double(), C.c_uint32()
+            if self.L.pfh_model_fit(self.h, g, w.ctypes.data, mean.ctypes.data, var.ctypes.data, C.byref(ll), C.byref(aic), C.byref(it)) == 0:
+                fits[g] = {"weights": w, "means": mean, "vars": var, "loglik": ll.value, "aic": aic.value, "iterations": it.value}
+        return {"fits": fits, "ploidy": self.L.pfh_model_ploidy(self.h), "values": int(self.L.pfh_model_values(self.h, None, 0))}
+
+    def text_bytes_fetched(self) -> int:
+        """bytes of the ten calling streams the last ploidy_estimation copied from the device"""
+        return int(self.L.pfh_text_bytes_fetched(self.h))
 
     def times(self) -> dict:
         t = Times()
