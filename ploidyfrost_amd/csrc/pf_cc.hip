@@ -352,13 +352,6 @@ bool grow(T *&p, uint64_t &cap, uint64_t want) {
 struct CcState;
 pfh::ColourGate gate_of(const pf_ctx *ctx, const CcState *S);
 
-bool is_device(const void *p) {
-    hipPointerAttribute_t at;
-    const bool dev = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice;
-    (void)hipGetLastError();
-    return dev;
-}
-
 pfh::ColourGate gate_of(const pf_ctx *ctx, const CcState *S) {
     pfh::ColourGate g;
     if (!S->n_colors) return g;   // (n_colors == 0: no gate)
@@ -488,7 +481,7 @@ int pf_side_components(pf_ctx *ctx, int reset, const pf_bfs_record *records, uin
         d_rec = ctx->bfs_last_rec;
         d_pool = ctx->bfs_last_pool;
         pool_len = ctx->bfs_last_pool_len;
-    } else if (is_device(records)) {
+    } else if (is_device_ptr(records)) {
         d_rec = records;
         d_pool = pool;
     } else {

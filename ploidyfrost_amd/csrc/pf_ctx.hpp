@@ -28,6 +28,14 @@ struct TimedLaunch {
     bool closed;   // b has been recorded
 };
 struct CallState;  // pf_call.hip: buffers of the resident calling pipeline
+
+// does `p` point into device memory?  (The probe of a plain host pointer fails and leaves HIP's sticky error set: cleared here.)
+inline bool is_device_ptr(const void *p) {
+    hipPointerAttribute_t at;
+    const bool dev = p && hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice;
+    (void)hipGetLastError();
+    return dev;
+}
 }  // namespace pf
 
 struct pf_ctx {
@@ -111,7 +119,7 @@ struct pf_ctx {
     hipEvent_t bub_events[PF_CALL_LANES][13] = {};
 
     // K-CC (pf_cc.hip): union-find over unitig sides for the parallel commit replay; the records and vertex pool of the last
-    // K-BFS call as they lie in the workspace
+    // K-BFS call (pf_bfs.hip) as they lie in the workspace
     void *cc = nullptr;
     void *gfa = nullptr;   // K-GFA (pf_gfa.hip): segment table of the last pf_gfa_ingest until pf_gfa_segments fetches it
     void *comm = nullptr;  // pf_gather.hip: this rank's RCCL communicator and its two small device buffers
@@ -131,7 +139,6 @@ struct pf_ctx {
         std::vector<uint32_t> deferred;
     } bfs_pending;
 
-    unsigned int bfs_deferred = 0;  // candidates of the last pf_bfs_candidates that needed the big tier
     unsigned int bfs_live_n = 0;    // entries the last pf_bfs_candidates call put into the live list (pf_bfs_live_count)
     unsigned long long *h_live = nullptr;   // pf_bfs_live_deferred: pinned, coherent host memory the wave tier reports its give-ups into
     uint64_t live_cap = 0;

@@ -2,9 +2,8 @@
 //   K-TABLE  count-table build           (CKMCFile::OpenForRA data -> device hash table)
 //   K-ADJ    end-k-mer join -> CSR       (Bifrost neighbour discovery, NeighborIterator.tcc:25-47)
 //   K-COV    per-unitig coverage         (CDBG::readCov(UnitigMap), src/CDBG.cpp:66-120)
-//   K-BFS    superbubble traversal       (CDBG::extractSuperBubble_ptr, src/CDBG.cpp:253-372)
 //   K-STRCOV site-string coverage        (CDBG::readCov(string), src/CDBG.cpp:29-60)
-// K-ALN lives in pf_align.hip.  Integer / index-bound work: no MFMA anywhere.
+// K-BFS lives in pf_bfs.hip, K-ALN in pf_align.hip.  Integer / index-bound work: no MFMA anywhere.
 #include <hip/hip_runtime.h>
 #include <sys/mman.h>
 
@@ -15,8 +14,6 @@
 #include <type_traits>
 #include <vector>
 
-#include "pf_bfs.hpp"
-#include "pf_bfs_huge.hpp"
 #include "pf_cov_stream.hpp"
 #include "pf_ctx.hpp"
 #include "pf_device_common.hpp"
@@ -525,244 +522,6 @@ __global__ void k_strcov(const CountLine *__restrict__ t, uint64_t mask, int k, 
     }
 }
 
-// K-BFS, LDS tier: 4 waves per block, each with its own LDS slice of CAP entries.
-constexpr uint32_t BFS_LDS_CAP = 128;
-constexpr uint32_t BFS_BIG_CAP = 1u << 12;  // linear-scan tables: beyond this the direct-indexed tier takes over
-
-struct BfsOut {
-    pf_bfs_record *rec;
-    uint32_t *pool;
-    uint64_t pool_cap;
-    unsigned long long *pool_head;  // running total (may exceed pool_cap: tells the size needed)
-    uint32_t *deferred;             // candidate indices for the big tier
-    unsigned int *n_deferred;
-    uint32_t *deferred2;            // ... and for the direct-indexed tier
-    unsigned int *n_deferred2;
-    // pf_bfs_live_deferred: the same hand-over, at once, in host memory the caller polls while the kernel runs: entry d =
-    // entrance << 32 | (candidate index + 1)
-    unsigned long long *live;
-    uint32_t live_cap;
-    unsigned int *n_live;   // entries of the live list (notices of traversals still running on the device included)
-    uint32_t hint_at;       // a traversal is entered when it reaches this many vertices
-};
-
-// Per-wave bump allocation in the vertex pool: a wave reserves BFS_POOL_CHUNK entries with one
-// atomic and hands them out locally, so the single pool head is touched once per ~50 candidates instead
-// of once per candidate (one hot word saturates at ~90 atomics/us chip-wide).
-constexpr uint32_t BFS_POOL_CHUNK = 256;
-struct BfsAlloc {
-    unsigned long long cur = 0, end = 0;
-};
-
-__device__ inline void bfs_emit(const BfsOut &o, BfsAlloc &al, uint64_t ci, uint32_t s, const BfsResult &r, const BfsStore &st) {
-    const int lane = lane_id();
-    // what the host replay needs: seen[] when an exit was found, the cycle set otherwise
-    const bool want_seen = r.outcome != PF_BFS_NONE;
-    const uint32_t n_list = want_seen ? r.n_seen : (r.flag_cycle ? r.n_cyc : 0);
-    const uint32_t *src = want_seen ? st.ent : st.cyc;
-    unsigned long long off = 0;
-    if (n_list) {
-        if (n_list > al.end - al.cur) {
-            const uint32_t want = n_list > BFS_POOL_CHUNK ? n_list : BFS_POOL_CHUNK;
-            unsigned long long got = 0;
-            if (lane == 0) got = atomicAdd(o.pool_head, (unsigned long long)want);
-            got = ((unsigned long long)__shfl((uint32_t)(got >> 32), 0, WAVE) << 32) | __shfl((uint32_t)got, 0, WAVE);
-            al.cur = got;
-            al.end = got + want;
-        }
-        off = al.cur;
-        al.cur += n_list;
-    }
-    if (off + n_list <= o.pool_cap)
-        for (uint32_t i = lane; i < n_list; i += WAVE) o.pool[off + i] = src[i];
-    if (lane == 0) {
-        pf_bfs_record rec;
-        rec.entrance = s;
-        rec.exit = r.exit_ov;
-        rec.n_seen = r.n_seen;
-        rec.n_list = n_list;
-        rec.list_off = off;
-        rec.outcome = r.outcome;
-        rec.flag_cycle = r.flag_cycle;
-        rec.flag_tip = r.flag_tip;
-        rec.strict = r.strict;
-        rec.pad_ = 0;
-        o.rec[ci] = rec;
-    }
-}
-
-// thread tier (pf_bfs.hpp): one thread per candidate; what outgrows its 8-entry tables is listed for the wavefront tier
-__global__ __launch_bounds__(256) void k_bfs_thread(const uint32_t *__restrict__ succ, const uint32_t *__restrict__ pred,
-                                                    const uint32_t *__restrict__ cand, uint64_t c0, uint64_t c1, BfsOut o, uint32_t *wave_list,
-                                                    unsigned int *n_wave_list) {
-    __shared__ uint32_t s_ent[BFS_THREAD_CAP * 256];
-    __shared__ uint32_t s_todo[BFS_THREAD_CAP * 256];
-    __shared__ uint32_t s_cyc[BFS_THREAD_CAP * 256];
-    __shared__ uint8_t s_meta[BFS_THREAD_CAP * 256];
-    const uint32_t tid = threadIdx.x;
-    const BfsThreadStore st{s_ent + tid, s_todo + tid, s_cyc + tid, s_meta + tid, 256};
-    const uint64_t c = c0 + (uint64_t)blockIdx.x * 256 + tid;
-    const int lane = lane_id();
-    const bool active = c < c1;
-    BfsResult r;
-    r.overflow = false;
-    r.outcome = PF_BFS_NONE;
-    r.n_seen = r.n_cyc = 0;
-    r.flag_cycle = 0;
-    uint32_t s = 0;
-    if (active) {
-        s = cand[c];
-        r = bfs_traverse_thread(succ, pred, st, s);
-    }
-    const bool done = active && !r.overflow;
-    // vertex lists: one atomic per wavefront for the space of all its lists
-    const bool want_seen = r.outcome != PF_BFS_NONE;
-    const uint32_t n_list = done ? (want_seen ? r.n_seen : (r.flag_cycle ? r.n_cyc : 0)) : 0;
-    uint32_t incl = n_list;
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const uint32_t x = __shfl_up(incl, d, WAVE);
-        if (lane >= d) incl += x;
-    }
-    const uint32_t total = __shfl(incl, WAVE - 1, WAVE);
-    unsigned long long base = 0;
-    if (total) {
-        if (lane == 0) base = atomicAdd(o.pool_head, (unsigned long long)total);
-        base = ((unsigned long long)__shfl((uint32_t)(base >> 32), 0, WAVE) << 32) | __shfl((uint32_t)base, 0, WAVE);
-    }
-    const unsigned long long off = base + (incl - n_list);
-    if (done) {
-        if (off + n_list <= o.pool_cap)
-            for (uint32_t i = 0; i < n_list; ++i) o.pool[off + i] = want_seen ? st.E(i) : st.C(i);
-        pf_bfs_record rec;
-        rec.entrance = s;
-        rec.exit = r.exit_ov;
-        rec.n_seen = r.n_seen;
-        rec.n_list = n_list;
-        rec.list_off = n_list ? off : 0;
-        rec.outcome = r.outcome;
-        rec.flag_cycle = r.flag_cycle;
-        rec.flag_tip = r.flag_tip;
-        rec.strict = r.strict;
-        rec.pad_ = 0;
-        o.rec[c - c0] = rec;
-    }
-    // the rest goes to the wavefront tier, in candidate order within the wavefront
-    const bool over = active && r.overflow;
-    const unsigned long long m = __ballot(over);
-    if (m) {
-        unsigned int b = 0;
-        if (lane == 0) b = atomicAdd(n_wave_list, (unsigned int)__popcll(m));
-        b = __shfl(b, 0, WAVE);
-        if (over) wave_list[b + (unsigned int)__popcll(m & ((1ull << lane) - 1))] = (uint32_t)(c - c0);
-    }
-}
-
-// wavefront tier: candidates c0 + [0, c1 - c0), or, with a list, the candidates c0 + list[0 .. *n_list)
-__global__ __launch_bounds__(256) void k_bfs(const uint32_t *__restrict__ succ, const uint32_t *__restrict__ pred,
-                                             const uint32_t *__restrict__ cand, uint64_t c0, uint64_t c1, BfsOut o,
-                                             const uint32_t *__restrict__ list, const unsigned int *__restrict__ n_list, uint32_t cap) {
-    __shared__ uint32_t s_ent[4][BFS_LDS_CAP];
-    __shared__ uint32_t s_todo[4][BFS_LDS_CAP];
-    __shared__ uint32_t s_cyc[4][BFS_LDS_CAP];
-    __shared__ uint8_t s_meta[4][BFS_LDS_CAP];
-    const int wv = threadIdx.x >> 6;
-    BfsStore st{s_ent[wv], s_meta[wv], s_todo[wv], s_cyc[wv], cap};   // cap <= BFS_LDS_CAP: where this tier gives a traversal up
-    st.live = o.live; st.n_live = o.n_live; st.live_cap = o.live_cap; st.hint_at = o.hint_at;
-    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-    BfsAlloc al;
-    const uint64_t n_items = list ? (uint64_t)*n_list : c1 - c0;
-    for (uint64_t it = wave; it < n_items; it += n_waves) {
-        const uint64_t c = c0 + (list ? (uint64_t)list[it] : it);
-        const uint32_t s = cand[c];
-        st.hint_tag = (uint32_t)(c - c0 + 1);
-        BfsResult r = bfs_traverse(succ, pred, st, s);
-        if (r.overflow) {
-            if (lane_id() == 0) {
-                pf_bfs_record rec;
-                memset(&rec, 0, sizeof(rec));
-                rec.entrance = s;
-                rec.exit = NONE;
-                rec.outcome = BFS_DEFERRED;
-                o.rec[c - c0] = rec;
-                const unsigned int d = atomicAdd(o.n_deferred, 1u);
-                o.deferred[d] = (uint32_t)(c - c0);
-                if (o.live && !r.hinted) {   // (a table other than the seen list ran over before the notice went out)
-                    const unsigned int l = atomicAdd(o.n_live, 1u);
-                    if (l < o.live_cap)
-                        __hip_atomic_store(&o.live[l], ((unsigned long long)s << 32) | (unsigned long long)(c - c0 + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-                }
-            }
-        } else {
-            bfs_emit(o, al, c - c0, s, r, st);
-        }
-        wave_sync();
-    }
-}
-
-// K-BFS, big tier: same traversal over per-wave global scratch (BFS_BIG_CAP entries per table).
-__global__ __launch_bounds__(64) void k_bfs_big(const uint32_t *__restrict__ succ, const uint32_t *__restrict__ pred,
-                                                const uint32_t *__restrict__ cand, uint64_t c0, unsigned int n_deferred,
-                                                uint32_t *scratch32, uint8_t *scratch8, BfsOut o) {
-    const uint32_t wave = blockIdx.x;
-    uint32_t *base = scratch32 + (size_t)wave * 3 * BFS_BIG_CAP;
-    BfsStore st{base, scratch8 + (size_t)wave * BFS_BIG_CAP, base + BFS_BIG_CAP, base + 2 * BFS_BIG_CAP, BFS_BIG_CAP};
-    BfsAlloc al;
-    for (unsigned int d = wave; d < n_deferred; d += gridDim.x) {
-        const uint32_t ci = o.deferred[d];
-        const uint32_t s = cand[c0 + ci];
-        BfsResult r = bfs_traverse(succ, pred, st, s);
-        if (r.overflow) {
-            if (lane_id() == 0) {
-                const unsigned int d2 = atomicAdd(o.n_deferred2, 1u);
-                o.deferred2[d2] = ci;
-            }
-        } else {
-            bfs_emit(o, al, ci, s, r, st);
-        }
-        wave_sync();
-    }
-}
-
-// K-BFS, last tier: direct-indexed state (pf_bfs_huge.hpp), one candidate per wave.
-// two-hop rows for the huge tier: the predecessor rows of the four successors of every oriented vertex
-__global__ void k_pred16(const uint32_t *__restrict__ succ, const uint32_t *__restrict__ pred, uint32_t n_ov,
-                         uint32_t *__restrict__ pred16) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (; i < (uint64_t)n_ov * 4; i += stride) {
-        const uint32_t sv = succ[i];
-        uint4 row;
-        row.x = row.y = row.z = row.w = NONE;
-        if (sv != NONE) row = *reinterpret_cast<const uint4 *>(pred + (size_t)sv * 4);
-        *reinterpret_cast<uint4 *>(pred16 + i * 4) = row;
-    }
-}
-
-__global__ __launch_bounds__(64) void k_bfs_huge(const uint32_t *__restrict__ succ, const uint32_t *__restrict__ pred,
-                                                 const uint32_t *__restrict__ cand, uint64_t c0, unsigned int n_deferred2,
-                                                 uint32_t *scratch, uint32_t n_unitigs, BfsOut o) {
-    const uint32_t wave = blockIdx.x;
-    const size_t N = n_unitigs;
-    uint32_t *b = scratch + (size_t)wave * (9 * N + 16);
-    HugeStore st{b, b + N, b + 2 * N, b + 4 * N, b + 5 * N + 4, b + 7 * N + 12, n_unitigs};
-    BfsStore view{st.seen, nullptr, st.todo, st.cyc, n_unitigs};
-    BfsAlloc al;
-    uint32_t epoch = 0;
-    for (unsigned int d = wave; d < n_deferred2; d += gridDim.x) {
-        const uint32_t ci = o.deferred2[d];
-        const uint32_t s = cand[c0 + ci];
-        ++epoch;
-        BfsResult r = bfs_traverse_huge(succ, pred, st, epoch, s);
-        if (r.overflow) {
-            if (lane_id() == 0) o.rec[ci].outcome = BFS_TOO_LARGE;
-        } else {
-            bfs_emit(o, al, ci, s, r, view);
-        }
-        wave_sync();
-    }
-}
-
 // ------------------------------------------------------------------------------------------
 // host side of the C ABI
 // ------------------------------------------------------------------------------------------
@@ -975,14 +734,12 @@ int join_graph_counts(pf_ctx *ctx) {
 // helper: device staging of an input that may live on the host
 template <typename T>
 static int stage_in(pf_ctx *ctx, const T *src, size_t n, T **dev, bool *owned) {
-    hipPointerAttribute_t at;
     *owned = false;
     if (n == 0) { *dev = nullptr; return PF_OK; }
-    if (hipPointerGetAttributes(&at, src) == hipSuccess && at.type == hipMemoryTypeDevice) {
+    if (is_device_ptr(src)) {
         *dev = const_cast<T *>(src);
         return PF_OK;
     }
-    (void)hipGetLastError();
     PF_HIP(hipMalloc(dev, n * sizeof(T)));
     *owned = true;
     PF_HIP(hipMemcpyAsync(*dev, src, n * sizeof(T), hipMemcpyDefault, ctx->stream));
@@ -1497,9 +1254,7 @@ int pf_upload_counts(pf_ctx *ctx, const uint64_t *kmers, const uint32_t *counts,
     ctx->tab_k = (int)k;
     PF_HIP(hipMemsetAsync(ctx->d_tab, 0xFF, cap * sizeof(CountLine), ctx->stream));   // every key free
     // stage the records on the device if the caller passed host memory
-    hipPointerAttribute_t at;
-    const bool on_dev = n && hipPointerGetAttributes(&at, kmers) == hipSuccess && at.type == hipMemoryTypeDevice;
-    (void)hipGetLastError();
+    const bool on_dev = n && is_device_ptr(kmers);
     DevTmp<uint64_t> dk_;
     DevTmp<uint32_t> dc_;
     const uint64_t *pk = kmers;
@@ -1588,9 +1343,7 @@ static int unitig_cov_impl(pf_ctx *ctx, uint32_t u0, uint32_t u1, int exact, uin
     PF_HIP(hipSetDevice(ctx->device));
     const uint32_t n = u1 - u0;
     // outputs: write straight into device memory when the caller gave device pointers
-    hipPointerAttribute_t at;
-    const bool dev_out = hipPointerGetAttributes(&at, sum) == hipSuccess && at.type == hipMemoryTypeDevice;
-    (void)hipGetLastError();
+    const bool dev_out = is_device_ptr(sum);
     uint64_t *ds = sum;
     uint32_t *dm = mn;
     uint8_t *dx = miss;
@@ -1672,9 +1425,7 @@ int pf_string_cov(pf_ctx *ctx, const char *text, const uint64_t *str_off, uint32
     PF_HIP(hipSetDevice(ctx->device));
     if (ctx->tab_exact) {
         // readCov(string) looks nothing up in a database without canonical counting and returns (0, true) (src/CDBG.cpp:34, 59)
-        hipPointerAttribute_t at;
-        const bool dev_out = hipPointerGetAttributes(&at, sum) == hipSuccess && at.type == hipMemoryTypeDevice;
-        (void)hipGetLastError();
+        const bool dev_out = is_device_ptr(sum);
         if (dev_out) {
             PF_HIP(hipMemsetAsync(sum, 0, (size_t)n_str * 8, ctx->stream));
             PF_HIP(hipMemsetAsync(ok, 1, n_str, ctx->stream));
@@ -1706,277 +1457,4 @@ int pf_string_cov(pf_ctx *ctx, const char *text, const uint64_t *str_off, uint32
     PF_HIP(hipStreamSynchronize(ctx->stream));
     return PF_OK;
 }
-
-static void cand_range(const pf_ctx *ctx, uint32_t u0, uint32_t u1, uint64_t *c0, uint64_t *c1) {
-    const auto &v = ctx->h_cand;
-    *c0 = std::lower_bound(v.begin(), v.end(), u0 * 2) - v.begin();
-    *c1 = std::lower_bound(v.begin(), v.end(), u1 * 2) - v.begin();
-}
-
-int pf_count_candidates(pf_ctx *ctx, uint32_t u0, uint32_t u1, uint64_t *n) {
-    if (!ctx || !ctx->has_adj || u0 > u1 || u1 > ctx->N || !n) return PF_ERR_ARG;
-    uint64_t c0, c1;
-    cand_range(ctx, u0, u1, &c0, &c1);
-    *n = c1 - c0;
-    return PF_OK;
-}
-
-// deferred != nullptr: the third tier is left to the caller (pf_bfs_candidates_split)
-// async_copy (pf_bfs_candidates_begin): the records and the pool are sent to the host on the copy stream and the call returns;
-// pf_bfs_candidates_end waits for them and marks the deferred records.
-static int bfs_candidates_impl(pf_ctx *ctx, uint32_t u0, uint32_t u1, pf_bfs_record *records, uint64_t rec_cap, uint32_t *pool,
-                               uint64_t pool_cap, uint64_t *n_records, uint64_t *pool_used, uint32_t *deferred, uint64_t deferred_cap,
-                               uint64_t *n_deferred, bool async_copy = false, uint32_t *deferred_entrance = nullptr) {
-    if (!ctx || !ctx->has_adj || u0 > u1 || u1 > ctx->N || !records || !pool || !n_records || !pool_used) return PF_ERR_ARG;
-    if (ctx->bfs_pending.active) { pf::CtxErr{ctx} = "pf_bfs_candidates_end first"; return PF_ERR_ARG; }
-    if (n_deferred) *n_deferred = 0;
-    PF_HIP(hipSetDevice(ctx->device));
-    uint64_t c0, c1;
-    cand_range(ctx, u0, u1, &c0, &c1);
-    const uint64_t n = c1 - c0;
-    *n_records = n;
-    *pool_used = 0;
-    if (n > rec_cap) { pf::CtxErr{ctx} = "record buffer too small"; return PF_ERR_OVERFLOW; }
-    if (n == 0) return PF_OK;
-    hipPointerAttribute_t at;
-    const bool dev_out = hipPointerGetAttributes(&at, records) == hipSuccess && at.type == hipMemoryTypeDevice;
-    (void)hipGetLastError();
-    pf_bfs_record *d_rec = records;
-    uint32_t *d_pool = pool;
-    if (!dev_out) {
-        d_rec = (pf_bfs_record *)ctx_ws(ctx, WS_BFS_REC, n * sizeof(pf_bfs_record));
-        d_pool = (uint32_t *)ctx_ws(ctx, WS_BFS_POOL, (pool_cap ? pool_cap : 1) * 4);
-        if (!d_rec || !d_pool) return PF_ERR_HIP;
-    }
-    uint8_t *small = (uint8_t *)ctx_ws(ctx, WS_BFS_SMALL, 64);
-    uint32_t *d_def = (uint32_t *)ctx_ws(ctx, WS_BFS_DEF, (n * 2 + 8) * 4);
-    if (!small || !d_def) return PF_ERR_HIP;
-    unsigned long long *d_head = reinterpret_cast<unsigned long long *>(small);
-    unsigned int *d_ndef = reinterpret_cast<unsigned int *>(small + 16);
-    unsigned int *d_ndef2 = reinterpret_cast<unsigned int *>(small + 32);
-    PF_HIP(hipMemsetAsync(small, 0, 64, ctx->stream));
-    unsigned int *d_nlive = reinterpret_cast<unsigned int *>(small + 56);
-    BfsOut o{d_rec, d_pool, pool_cap, d_head, d_def, d_ndef, d_def + n + 4, d_ndef2, nullptr, 0, d_nlive, 0};
-    if (ctx->h_live && deferred) {   // (armed by pf_bfs_live_deferred: the caller polls the list while the kernels below run)
-        // The list is zeroed by pf_bfs_live_deferred -- once per arming, BEFORE the caller starts the threads that poll it.  Zeroing it
-        // here raced with them (they saw the pass before's entries first; advisor, round 3) and a retry after a pool overflow wiped
-        // what they were reading.  A retry writes the list again from slot 0: an entry a poller took before and the one that replaces
-        // it are both real candidates of this graph, walks are keyed by (candidate, entrance), what no poller saw is walked afterwards.
-        o.live = reinterpret_cast<unsigned long long *>(ctx->h_live);
-        o.live_cap = (uint32_t)ctx->live_cap;
-        // (PF_BFS_HINT_AT, read per call: measurements; beyond the tier's tables = notice only when it gives up)
-        o.hint_at = [] { const char *e = getenv("PF_BFS_HINT_AT"); return e ? (uint32_t)std::max(9, atoi(e)) : 48u; }();
-    }
-    ctx->bfs_live_n = 0;
-    // thread tier first (one thread per candidate, 8-entry tables), then the wavefront tier for what outgrew it
-    uint32_t *d_wlist = (uint32_t *)ctx_ws(ctx, WS_BFS_WLIST, (n + 8) * 4);
-    if (!d_wlist) return PF_ERR_HIP;
-    unsigned int *d_nwlist = reinterpret_cast<unsigned int *>(small + 48);
-    // (PF_BFS_WAVE_CAP, read per call: measurements of where the wavefront tier should give up)
-    const uint32_t wave_cap = [] { const char *e = getenv("PF_BFS_WAVE_CAP"); return e ? (uint32_t)std::max(16, std::min((int)BFS_LDS_CAP, atoi(e))) : BFS_LDS_CAP; }();
-    ctx_begin(ctx, PF_K_BFS_THREAD);
-    k_bfs_thread<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(ctx->d_succ, ctx->d_pred, ctx->d_cand, c0, c1, o, d_wlist, d_nwlist);
-    ctx_end(ctx);
-    const int grid = ctx_grid(ctx, (n / 4 + 64) * 64, 256, 8);
-    ctx_begin(ctx, PF_K_BFS);
-    k_bfs<<<grid, 256, 0, ctx->stream>>>(ctx->d_succ, ctx->d_pred, ctx->d_cand, c0, c1, o, d_wlist, d_nwlist, wave_cap);
-    ctx_end(ctx);
-    unsigned int n_def = 0, n_wl = 0, n_live = 0;
-    PF_HIP(hipMemcpyAsync(&n_def, d_ndef, 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (o.live) PF_HIP(hipMemcpyAsync(&n_live, d_nlive, 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (ctx->timing) PF_HIP(hipMemcpyAsync(&n_wl, d_nwlist, 4, hipMemcpyDeviceToHost, ctx->stream));
-    PF_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->bfs_live_n = n_live;
-    ctx_units(ctx, PF_K_BFS, n_wl);
-    ctx_units(ctx, PF_K_BFS_THREAD, n);
-    int status = PF_OK;
-    if (n_def && deferred) {
-        // the caller walks everything that outgrew the LDS tier itself (a host core needs ~20 ns per vertex; the 4096-entry
-        // tier below searches its tables linearly and is quadratic in the traversal's size)
-        if (n_deferred) *n_deferred = n_def;
-        if (n_def > deferred_cap) { pf::CtxErr{ctx} = "deferred-candidate buffer too small"; status = PF_ERR_OVERFLOW; }
-        else PF_HIP(hipMemcpy(deferred, d_def, (size_t)n_def * 4, hipMemcpyDeviceToHost));
-    } else if (n_def) {
-        const unsigned int waves = std::min<unsigned int>(n_def, 256);
-        DevTmp<uint32_t> sc32_;
-        DevTmp<uint8_t> sc8_;
-        PF_HIP(sc32_.alloc((size_t)waves * 3 * BFS_BIG_CAP * 4));
-        PF_HIP(sc8_.alloc((size_t)waves * BFS_BIG_CAP));
-        uint32_t *sc32 = sc32_.p;
-        uint8_t *sc8 = sc8_.p;
-        ctx_begin(ctx, PF_K_BFS_BIG);
-        k_bfs_big<<<waves, 64, 0, ctx->stream>>>(ctx->d_succ, ctx->d_pred, ctx->d_cand, c0, n_def, sc32, sc8, o);
-        ctx_end(ctx);
-        unsigned int n_def2 = 0;
-        PF_HIP(hipMemcpyAsync(&n_def2, d_ndef2, 4, hipMemcpyDeviceToHost, ctx->stream));
-        PF_HIP(hipStreamSynchronize(ctx->stream));
-        if (n_def2) {
-            // traversals beyond the linear tables: direct-indexed state sized by the graph, a few waves
-            // one wave per traversal, as many side by side as ~16 GiB of state allow
-            const unsigned int hw = (unsigned int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(n_def2, 64), (16ull << 30) / (36 * (size_t)ctx->N + 64)));
-            const size_t per = 9 * (size_t)ctx->N + 16;
-            DevTmp<uint32_t> hs_;
-            PF_HIP(hs_.alloc(per * hw * 4));
-            uint32_t *hs = hs_.p;
-            PF_HIP(hipMemsetAsync(hs, 0, per * hw * 4, ctx->stream));
-            ctx_begin(ctx, PF_K_BFS_BIG);
-            if (!ctx->d_pred16) {
-                PF_HIP(hipMalloc(&ctx->d_pred16, (size_t)ctx->N * 2 * 16 * 4));
-                k_pred16<<<ctx_grid(ctx, (uint64_t)ctx->N * 8, 256, 8), 256, 0, ctx->stream>>>(ctx->d_succ, ctx->d_pred, ctx->N * 2, ctx->d_pred16);
-            }
-            k_bfs_huge<<<hw, 64, 0, ctx->stream>>>(ctx->d_succ, ctx->d_pred16, ctx->d_cand, c0, n_def2, hs, ctx->N, o);
-            ctx_end(ctx);
-            PF_HIP(hipStreamSynchronize(ctx->stream));
-        }
-    }
-    ctx->bfs_deferred = n_def;
-    ctx->bfs_last_rec = d_rec; ctx->bfs_last_pool = d_pool; ctx->bfs_last_n = n; ctx->bfs_last_pool_len = pool_cap;
-    ctx->bfs_call_id++;
-    unsigned long long head = 0;
-    PF_HIP(hipMemcpy(&head, d_head, 8, hipMemcpyDeviceToHost));
-    *pool_used = head;
-    if (head > pool_cap) {
-        pf::CtxErr{ctx} = "vertex pool too small";
-        status = PF_ERR_OVERFLOW;
-    }
-    if (!dev_out && status == PF_OK && async_copy) {
-        if (!ctx->copy_stream) PF_HIP(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-        PF_HIP(hipMemcpyAsync(records, d_rec, n * sizeof(pf_bfs_record), hipMemcpyDeviceToHost, ctx->copy_stream));
-        PF_HIP(hipMemcpyAsync(pool, d_pool, (size_t)head * 4, hipMemcpyDeviceToHost, ctx->copy_stream));
-        ctx->bfs_pending.active = true;
-        ctx->bfs_pending.records = records;
-        ctx->bfs_pending.c0 = c0;
-        ctx->bfs_pending.deferred.assign(deferred, deferred + (n_deferred ? *n_deferred : 0));
-        if (deferred_entrance && n_deferred)
-            for (uint64_t d = 0; d < *n_deferred; ++d) deferred_entrance[d] = ctx->h_cand[c0 + deferred[d]];
-        return PF_OK;
-    }
-    if (!dev_out) {
-        if (status == PF_OK) {
-            PF_HIP(hipMemcpy(records, d_rec, n * sizeof(pf_bfs_record), hipMemcpyDeviceToHost));
-            PF_HIP(hipMemcpy(pool, d_pool, (size_t)head * 4, hipMemcpyDeviceToHost));
-            if (deferred && n_deferred)
-                for (uint64_t d = 0; d < *n_deferred; ++d) {  // records the caller fills: entrance set, everything else empty
-                    pf_bfs_record &r = records[deferred[d]];
-                    memset(&r, 0, sizeof r);
-                    r.entrance = ctx->h_cand[c0 + deferred[d]];
-                    r.exit = NONE;
-                }
-            for (uint64_t i = 0; i < n; ++i)
-                if (records[i].outcome == BFS_TOO_LARGE) {
-                    pf::CtxErr{ctx} = "a traversal exceeded the direct-indexed tier (internal limit)";
-                    status = PF_ERR_OVERFLOW;
-                    break;
-                }
-        }
-    }
-    return status;
-}
-
-int pf_bfs_candidates(pf_ctx *ctx, uint32_t u0, uint32_t u1, pf_bfs_record *records, uint64_t rec_cap, uint32_t *pool,
-                      uint64_t pool_cap, uint64_t *n_records, uint64_t *pool_used) {
-    return bfs_candidates_impl(ctx, u0, u1, records, rec_cap, pool, pool_cap, n_records, pool_used, nullptr, 0, nullptr);
-}
-
-int pf_bfs_candidates_split(pf_ctx *ctx, uint32_t u0, uint32_t u1, pf_bfs_record *records, uint64_t rec_cap, uint32_t *pool,
-                            uint64_t pool_cap, uint64_t *n_records, uint64_t *pool_used, uint32_t *deferred, uint64_t deferred_cap,
-                            uint64_t *n_deferred) {
-    if (!deferred || !n_deferred) return PF_ERR_ARG;
-    if (ctx) {
-        hipPointerAttribute_t at;
-        if (records && hipPointerGetAttributes(&at, records) == hipSuccess && at.type == hipMemoryTypeDevice) {
-            pf::CtxErr{ctx} = "pf_bfs_candidates_split fills host records";
-            return PF_ERR_ARG;
-        }
-        (void)hipGetLastError();
-    }
-    return bfs_candidates_impl(ctx, u0, u1, records, rec_cap, pool, pool_cap, n_records, pool_used, deferred, deferred_cap, n_deferred);
-}
-
-int pf_bfs_candidates_begin(pf_ctx *ctx, uint32_t u0, uint32_t u1, pf_bfs_record *records, uint64_t rec_cap, uint32_t *pool,
-                            uint64_t pool_cap, uint64_t *n_records, uint64_t *pool_used, uint32_t *deferred, uint32_t *deferred_entrance,
-                            uint64_t deferred_cap, uint64_t *n_deferred) {
-    if (!deferred || !deferred_entrance || !n_deferred) return PF_ERR_ARG;
-    if (ctx) {
-        hipPointerAttribute_t at;
-        if (records && hipPointerGetAttributes(&at, records) == hipSuccess && at.type == hipMemoryTypeDevice) {
-            pf::CtxErr{ctx} = "pf_bfs_candidates_begin fills host records";
-            return PF_ERR_ARG;
-        }
-        (void)hipGetLastError();
-    }
-    return bfs_candidates_impl(ctx, u0, u1, records, rec_cap, pool, pool_cap, n_records, pool_used, deferred, deferred_cap, n_deferred, true,
-                               deferred_entrance);
-}
-
-// K-BFS with records and vertex pool left in the context's own device buffers (for K-CC and the device-side commits): nothing
-// travels to the host but the deferred candidates' indices and entrances.
-int pf_bfs_candidates_resident(pf_ctx *ctx, uint32_t u0, uint32_t u1, uint64_t *n_records, uint64_t *pool_used, uint32_t *deferred,
-                               uint32_t *deferred_entrance, uint64_t deferred_cap, uint64_t *n_deferred) {
-    if (!ctx || !n_records || !pool_used || !deferred || !deferred_entrance || !n_deferred) return PF_ERR_ARG;
-    if (!ctx->has_adj || u0 > u1 || u1 > ctx->N) return PF_ERR_ARG;
-    uint64_t c0, c1;
-    cand_range(ctx, u0, u1, &c0, &c1);
-    const uint64_t n = c1 - c0;
-    uint64_t cap = std::max<uint64_t>(ctx->bfs_res_pool_cap, n * 6 + (1u << 20));
-    for (int attempt = 0; attempt < 4; ++attempt) {
-        pf_bfs_record *d_rec = (pf_bfs_record *)ctx_ws(ctx, WS_BFS_RES_REC, (n + 1) * sizeof(pf_bfs_record));
-        uint32_t *d_pool = (uint32_t *)ctx_ws(ctx, WS_BFS_RES_POOL, (cap + 1) * 4);
-        if (!d_rec || !d_pool) return PF_ERR_HIP;
-        const int st = bfs_candidates_impl(ctx, u0, u1, d_rec, n + 1, d_pool, cap, n_records, pool_used, deferred, deferred_cap, n_deferred);
-        if (st == PF_ERR_OVERFLOW && *pool_used > cap) { cap = *pool_used + *pool_used / 8 + 1024; continue; }
-        if (st == PF_OK) {
-            ctx->bfs_res_pool_cap = cap;
-            for (uint64_t d = 0; d < *n_deferred; ++d) deferred_entrance[d] = ctx->h_cand[c0 + deferred[d]];
-        }
-        return st;
-    }
-    pf::CtxErr{ctx} = "pf_bfs_candidates_resident: the vertex pool does not converge";
-    return PF_ERR_OVERFLOW;
-}
-
-int pf_bfs_live_count(pf_ctx *ctx, uint64_t *n) {
-    if (!ctx || !n) return PF_ERR_ARG;
-    *n = ctx->bfs_live_n;
-    return PF_OK;
-}
-
-int pf_bfs_live_deferred(pf_ctx *ctx, uint64_t cap, volatile uint64_t **list) {
-    if (!ctx || !list) return PF_ERR_ARG;
-    *list = nullptr;
-    PF_HIP(hipSetDevice(ctx->device));
-    if (cap == 0) {   // off
-        if (ctx->h_live) (void)hipHostFree(ctx->h_live);
-        ctx->h_live = nullptr;
-        ctx->live_cap = 0;
-        return PF_OK;
-    }
-    if (ctx->h_live && ctx->live_cap != cap) { (void)hipHostFree(ctx->h_live); ctx->h_live = nullptr; ctx->live_cap = 0; }
-    if (!ctx->h_live) {
-        void *p = nullptr;
-        if (hipHostMalloc(&p, cap * 8, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) { (void)hipGetLastError(); pf::CtxErr{ctx} = "pf_bfs_live_deferred: no pinned host memory"; return PF_ERR_HIP; }
-        ctx->h_live = static_cast<unsigned long long *>(p);
-        ctx->live_cap = cap;
-    }
-    for (uint64_t x = 0; x < cap; ++x) __atomic_store_n(&ctx->h_live[x], 0ull, __ATOMIC_RELAXED);   // (per arming: see bfs_candidates_impl)
-    __atomic_thread_fence(__ATOMIC_SEQ_CST);
-    *list = reinterpret_cast<volatile uint64_t *>(ctx->h_live);
-    return PF_OK;
-}
-
-int pf_bfs_candidates_end(pf_ctx *ctx) {
-    if (!ctx) return PF_ERR_ARG;
-    if (!ctx->bfs_pending.active) return PF_OK;
-    ctx->bfs_pending.active = false;
-    PF_HIP(hipSetDevice(ctx->device));
-    PF_HIP(hipStreamSynchronize(ctx->copy_stream));
-    for (uint32_t idx : ctx->bfs_pending.deferred) {  // records the caller fills: entrance set, everything else empty
-        pf_bfs_record &r = ctx->bfs_pending.records[idx];
-        memset(&r, 0, sizeof r);
-        r.entrance = ctx->h_cand[ctx->bfs_pending.c0 + idx];
-        r.exit = NONE;
-    }
-    return PF_OK;
-}
-
 }  // extern "C"

@@ -84,6 +84,7 @@ def load_library() -> C.CDLL:
         "pf_side_components": (i, [vp, i, vp, u64, vp, u64, vp, u64, vp, u64]),
         "pf_bfs_candidates_begin": (i, [vp, C.c_uint32, C.c_uint32, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), vp, vp, u64, C.POINTER(u64)]),
         "pf_bfs_candidates_end": (i, [vp]),
+        "pf_bfs_candidates_split": (i, [vp, C.c_uint32, C.c_uint32, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), vp, u64, C.POINTER(u64)]),
         "pf_fetch": (i, [vp, vp, vp, u64]),
         "pf_bfs_candidates_resident": (i, [vp, C.c_uint32, C.c_uint32, C.POINTER(u64), C.POINTER(u64), vp, vp, u64, C.POINTER(u64)]),
         "pf_replay_device": (i, [vp, C.c_uint32, C.c_uint32, C.POINTER(u64), C.POINTER(u64)]),
@@ -508,6 +509,50 @@ class Device:
                 continue
             self._check(st)
             return rec[: nr.value], pool[: used.value]
+
+    def _bfs_handing_over(self, entry, u0, u1, pool_cap, entrances):
+        """pf_bfs_candidates_split / _begin: (records, pool, deferred[, deferred_entrance]) with a pool that is large enough"""
+        u1 = self.n if u1 is None else u1
+        n = self.count_candidates(u0, u1)
+        rec = np.zeros(max(n, 1), dtype=BFS_RECORD)
+        deferred = np.zeros(max(n, 1), dtype=np.uint32)
+        entrance = (np.zeros(max(n, 1), dtype=np.uint32),) if entrances else ()
+        pool_cap = pool_cap or max(1024, n * 8)
+        while True:
+            pool = np.zeros(pool_cap, dtype=np.uint32)
+            nr, used, nd = C.c_uint64(), C.c_uint64(), C.c_uint64()
+            st = entry(self.h, u0, u1, rec.ctypes.data, len(rec), pool.ctypes.data, pool_cap, C.byref(nr), C.byref(used),
+                       deferred.ctypes.data, *[e.ctypes.data for e in entrance], len(deferred), C.byref(nd))
+            if st == PF_ERR_OVERFLOW and used.value > pool_cap:
+                pool_cap = int(used.value)
+                continue
+            self._check(st)
+            if entrances:
+                self._bfs_pending = (rec, pool)   # written to until bfs_end()
+            return (rec[: nr.value], pool[: used.value], deferred[: nd.value]) + tuple(e[: nd.value] for e in entrance)
+
+    def bfs_split(self, u0=0, u1=None, pool_cap=None):
+        """(records, pool, deferred): what the wavefront tier gave up is left to the caller -- records[deferred] hold an entrance only"""
+        return self._bfs_handing_over(self.L.pf_bfs_candidates_split, u0, u1, pool_cap, entrances=False)
+
+    def bfs_begin(self, u0=0, u1=None, pool_cap=None):
+        """(records, pool, deferred, deferred_entrance) like bfs_split; records and pool are still on their way until bfs_end()"""
+        return self._bfs_handing_over(self.L.pf_bfs_candidates_begin, u0, u1, pool_cap, entrances=True)
+
+    def bfs_end(self):
+        self._check(self.L.pf_bfs_candidates_end(self.h))
+        self._bfs_pending = None
+
+    def bfs_resident(self, u0=0, u1=None):
+        """(n_records, pool_used, deferred, deferred_entrance): records and pool stay on the device, for side_components(n_records=...)"""
+        u1 = self.n if u1 is None else u1
+        n = self.count_candidates(u0, u1)
+        deferred = np.zeros(max(n, 1), dtype=np.uint32)
+        entrance = np.zeros(max(n, 1), dtype=np.uint32)
+        nr, used, nd = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.L.pf_bfs_candidates_resident(self.h, u0, u1, C.byref(nr), C.byref(used), deferred.ctypes.data, entrance.ctypes.data,
+                                                      len(deferred), C.byref(nd)))
+        return nr.value, used.value, deferred[: nd.value], entrance[: nd.value]
 
     def side_components(self, records=None, pool=None, n_records=None, reset=True, extra=None, extra_pool=None):
         """K-CC: the records (default: the ones the last bfs() call left on the device) join the union-find over unitig sides"""

@@ -6,6 +6,7 @@ import sys
 import numpy as np
 import pytest
 
+from bfs_cases import lattice_gfa
 from conftest import ROOT, golden_cases, load_case
 
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -380,41 +381,6 @@ def test_count_table_with_a_minimizer_shared_by_thousands_of_kmers():
         # a graph of another k is refused, and so is a table of another k beside a graph
         with pytest.raises(RuntimeError):
             d.upload_graph(*hipapi.pack_unitigs([b"ACGT" * 20]), k + 2 if k < 30 else k - 2)
-
-
-def lattice_gfa(path, k=25, depth=7, seed=3):
-    """A superbubble wider than the LDS tables of K-BFS: a binary tree of `depth` levels fanning out
-    from one entrance and its mirror image collapsing into one exit (2^depth unitigs in the middle)."""
-    rng = np.random.default_rng(seed)
-
-    def rnd(n):
-        return bytes(rng.choice(list(b"ACGT"), size=n).tolist())
-
-    segs = [rnd(60)]
-    level = [0]  # indices into segs
-    # expanding half: node -> two children that start with the node's last k-1 bases + a distinct base
-    for _ in range(depth):
-        nxt = []
-        for i in level:
-            for b in (b"A", b"C"):
-                segs.append(segs[i][-(k - 1):] + b + rnd(30))
-                nxt.append(len(segs) - 1)
-        level = nxt
-    # collapsing half: two parents are extended so that both end with the same k-1 bases after distinct bases
-    while len(level) > 1:
-        nxt = []
-        for i in range(0, len(level), 2):
-            join = rnd(k - 1)
-            segs[level[i]] += b"G" + join
-            segs[level[i + 1]] += b"T" + join
-            segs.append(join + rnd(30))
-            nxt.append(len(segs) - 1)
-        level = nxt
-    with open(path, "wb") as f:
-        f.write(b"H\tVN:Z:1.0\tKL:Z:%d\tML:Z:17\n" % k)
-        for i, s in enumerate(segs):
-            f.write(b"S\t%d\t%s\n" % (i + 1, s))
-    return len(segs)
 
 
 @pytest.mark.parametrize("depth,limit", [(7, 128), (12, 4096)])
