@@ -628,6 +628,27 @@ enum pf_model_source { PF_MODEL_COV = 0, PF_MODEL_FRE = 1 };
 int pf_call_model_begin(pf_ctx *, int source, double q);
 int pf_call_model_take(pf_ctx *, int slab);
 int pf_call_model_finish(pf_ctx *, uint64_t *n_values);
+/* ---- a row filter in front of the model (csrc/pf_filter_rows.hpp) ----
+ * The options of `ploidyfrost filter` (script/Filter.R; csrc/host/pf_filter.hpp FilterOptions) without the prefixes.  With a filter
+ * the collection reads the four coverage streams (_bicov, _tricov, _tetracov, _pentacov) for either source and gives the array
+ * that `filter` followed by `model -f` (cov) / `model -g <filtered>_allele_frequency.txt` (fre) would read, without writing a
+ * filtered table: for fre the kept rows' frequencies column by column (all A-frequencies of the bi rows, all B-frequencies, ...,
+ * 14 columns), each in (frequency, 1 - frequency), rounded to 7 places as R rounds and prints them, the last one counted twice.
+ *   pf_call_model_filter     between pf_call_model_begin and the first take; NULL = no filter (the state after begin).
+ *   pf_call_model_take_text  a piece of the text of stream `stream_ord` of the collection (without a filter: cov 0..2 = bi, tri,
+ *                            tetra, fre 0; with one: 0..3 = bi, tri, tetra, penta) from host memory through the same kernels:
+ *                            upload, then the collection's launches.  Pieces of a stream in file order, cut behind line feeds.
+ * pf_call_model_finish then also refuses, naming stream and row: a row without its A + 5 fields or with a cell that is no finite
+ * decimal number (what the host filter refuses), a kept coverage R would print in scientific notation (source cov; the
+ * three-command chain handles those), and -- R's own error, the calling files being complete -- four tables that keep no row. */
+typedef struct pf_filter_opts {
+    int simple, indel, snp;          /* -S, -I, -P */
+    long long low, up;               /* -l, -u   every coverage in (low, up) */
+    long long num, distance, size;   /* -n VarNum < num, -d VarDis > distance, -s VarType < size */
+    double frequency;                /* -q       frequencies in (q, 1 - q) */
+} pf_filter_opts;
+int pf_call_model_filter(pf_ctx *, const pf_filter_opts *);
+int pf_call_model_take_text(pf_ctx *, int stream_ord, const char *host_text, uint64_t len);
 /* Bytes of the ten result streams the pf_call_fetch* calls of this context have copied to the host so far. */
 uint64_t pf_call_fetched_bytes(const pf_ctx *);
 

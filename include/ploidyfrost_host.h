@@ -169,6 +169,19 @@ uint64_t pfh_text_bytes_fetched(const pfh_run *);
 int pfh_model_rows(int source, double min_frequency, const char *const *text, const uint64_t *len, double *out, uint64_t cap,
                    uint64_t *n, char *err, uint64_t err_cap);
 
+/* ---- `ploidyfrost filter`'s row predicates in front of that model (pf_filter_opts and pf_call_model_filter in ploidyfrost_hip.h) ----
+ * pfh_set_filter after pfh_set_model: the next pfh_ploidy_estimation fits what `filter -i <outpre> ...` followed by `model -f` /
+ * `model -g <filtered>_allele_frequency.txt` would read, from the coverage text while it is on the device; no filtered table is
+ * written.  NULL: no filter again.  Refused (pfh_last_error) unless a model is set and for frequency > 0.5; pfh_set_model with
+ * source < 0 drops the filter as well.  When no table keeps a row the pass fails with R's error after the calling files are
+ * complete, and the run stays usable.
+ * pfh_filter_rows: the same rule (csrc/pf_filter_rows.hpp) on host text, no device: text[0..3] = the bytes of _bicov / _tricov /
+ * _tetracov / _pentacov.txt, out = the model's array for `source` (at most cap; *n = how many there are).  0 = ok, 1 = refused,
+ * worded in err as the device path words it. */
+int pfh_set_filter(pfh_run *, const pf_filter_opts *);
+int pfh_filter_rows(int source, double min_frequency, const pf_filter_opts *opts, const char *const *text, const uint64_t *len,
+                    double *out, uint64_t cap, uint64_t *n, char *err, uint64_t err_cap);
+
 /* The host tier of K-BFS on its own (host/pf_bfs_host.hpp; no device involved): extractSuperBubble_ptr's traversal
  * (src/CDBG.cpp:253-372) from one oriented vertex over CSR rows laid out as pf_build_adjacency returns them.  Fills *record
  * (list_off = 0) and copies its list -- seen[] when an exit was found, the cycle set otherwise -- to `list`.

@@ -476,7 +476,16 @@ int CDBG::set_model(const ModelOptions &o) {
         if (o.q >= 0.5 || o.max_iter < 0 || o.max_delta < 0 || o.m_thre < 0 || o.n_thre < 0) return refuse("CDBG::set_model(): q < 0.5, iterations, delta and thresholds >= 0 (as `model` checks them)");
     }
     model_ = o;
-    if (!o.on) model_.only = false;
+    if (!o.on) model_.only = filter_on_ = false;
+    return 0;
+}
+
+int CDBG::set_filter(const pf_filter_opts *o) {
+    auto refuse = [&](const std::string &m) { err_ = m; return (int)PF_ERR_ARG; };
+    if (o && !model_.on) return refuse("CDBG::set_filter(): the row filter stands in front of the model of the same run; set a model first");
+    if (o && !(o->frequency <= 0.5)) return refuse("CDBG::set_filter(): frequency should < 0.5");
+    filter_on_ = o != nullptr;
+    if (o) filter_ = *o;
     return 0;
 }
 

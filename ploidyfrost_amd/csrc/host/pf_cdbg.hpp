@@ -137,6 +137,10 @@ public:
         int max_iter = 1000;
     };
     int set_model(const ModelOptions &o);
+    // `ploidyfrost filter`'s row predicates in front of that model (pf_call_model_filter; the rule is csrc/pf_filter_rows.hpp): the
+    // estimate of `filter` + `model` on this run's files, no filtered table written.  Null: no filter.  Refused unless a model is set;
+    // switching the model off drops it.
+    int set_filter(const pf_filter_opts *o);
     // of the last PloidyEstimation with a model: one record per number of Gaussians, the value of the result file's last line and
     // that line; how many values the device array holds
     const std::vector<GmmModel::Fit> &model_fits() const { return model_fits_; }
@@ -208,6 +212,8 @@ protected:
     std::vector<pf_bfs_record> shard_rec_;
     std::vector<uint32_t> shard_pool_;
     ModelOptions model_;
+    bool filter_on_ = false;
+    pf_filter_opts filter_ = {};
     std::vector<GmmModel::Fit> model_fits_;
     double model_ploidy_ = 0;
     std::string model_last_line_;

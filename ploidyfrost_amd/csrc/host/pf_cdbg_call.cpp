@@ -336,7 +336,8 @@ int CDBG::ploidy_estimation_resident(const std::string &outpre, const std::vecto
     // The copy to the host is what a pass ends with: 17.7 MB a piece at 55 GB/s, 0.33 ms each, twelve pieces behind the alignment.
     const bool num_packed = !getenv("PF_NUMERIC_ASCII");
     if (pf_call_set_numeric_packed(ctx_, num_packed ? 1 : 0) != PF_OK) return fail(PF_ERR_HIP, std::string(tag_) + "::PloidyEstimation(): " + pf_last_error(ctx_));
-    if (model_.on && pf_call_model_begin(ctx_, model_.source, model_.q) != PF_OK) return fail(PF_ERR_ARG, std::string(tag_) + "::PloidyEstimation(): " + pf_last_error(ctx_));
+    if (model_.on && (pf_call_model_begin(ctx_, model_.source, model_.q) != PF_OK || (filter_on_ && pf_call_model_filter(ctx_, &filter_) != PF_OK)))
+        return fail(PF_ERR_ARG, std::string(tag_) + "::PloidyEstimation(): " + pf_last_error(ctx_));
     struct PackGuard {   // the sliced calls (ploidy_text, one graph over several ranks) read the text as the device writes it
         pf_ctx *c;
         ~PackGuard() { (void)pf_call_set_alignseq_packed(c, 0); (void)pf_call_set_numeric_packed(c, 0); }

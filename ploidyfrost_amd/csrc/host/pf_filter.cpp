@@ -9,6 +9,7 @@
 #include <fstream>
 #include <iostream>
 #include <sstream>
+#include <algorithm>
 
 namespace pfh {
 
@@ -259,15 +260,14 @@ void filter_usage(bool multi) {
 }
 }  // namespace
 
-int filter_main(int argc, char **argv, bool multi) {
-    FilterOptions o;
-    o.multi = multi;
+// the option table of the two scripts over args: 0 = ok, 1 = an error (worded in err), 2 = -h
+int parse_filter_options(const std::vector<std::string> &args, bool multi, FilterOptions &o, std::string &err, std::string *seen) {
     struct Opt { char s; const char *l; bool flag; };
     static const Opt table[] = {{'S', "simple", true}, {'o', "outprefix", false}, {'i', "inprefix", false}, {'l', "low", false}, {'u', "up", false},
                                 {'I', "indel", true}, {'P', "snp", true}, {'n', "num", false}, {'d', "distance", false}, {'s', "size", false},
                                 {'q', "frequency", false}, {'c', "color", false}, {'v', "cramer", false}, {'h', "help", true}};
-    for (int i = 2; i < argc; ++i) {
-        std::string a = argv[i], val;
+    for (size_t i = 0; i < args.size(); ++i) {
+        std::string a = args[i], val;
         const Opt *hit = nullptr;
         bool have_val = false;
         if (a.rfind("--", 0) == 0) {
@@ -281,12 +281,13 @@ int filter_main(int argc, char **argv, bool multi) {
                 if (a[1] == t.s) hit = &t;
             if (a.size() > 2) { val = a.substr(2); have_val = true; }
         }
-        if (!hit || (!multi && (hit->s == 'c' || hit->s == 'v'))) { std::cerr << "Error: unknown option " << a << std::endl; filter_usage(multi); return 1; }
-        if (hit->s == 'h') { filter_usage(multi); return 0; }
+        if (!hit || (!multi && (hit->s == 'c' || hit->s == 'v'))) { err = "Error: unknown option " + a; return 1; }
+        if (hit->s == 'h') return 2;
         if (!hit->flag && !have_val) {
-            if (i + 1 >= argc) { std::cerr << "Error: option " << a << " needs a value" << std::endl; return 1; }
-            val = argv[++i];
+            if (i + 1 >= args.size()) { err = "Error: option " + a + " needs a value"; return 3; }
+            val = args[++i];
         }
+        if (seen) *seen += hit->s;
         switch (hit->s) {
             case 'S': o.simple = true; break;
             case 'I': o.indel = true; break;
@@ -302,6 +303,20 @@ int filter_main(int argc, char **argv, bool multi) {
             case 'q': o.frequency = atof(val.c_str()); break;
             case 'v': o.cramer = atof(val.c_str()); break;
         }
+    }
+    return 0;
+}
+
+int filter_main(int argc, char **argv, bool multi) {
+    FilterOptions o;
+    o.multi = multi;
+    std::string perr;
+    const int ps = parse_filter_options(std::vector<std::string>(argv + std::min(argc, 2), argv + argc), multi, o, perr, nullptr);
+    if (ps == 2) { filter_usage(multi); return 0; }
+    if (ps) {
+        std::cerr << perr << std::endl;
+        if (ps == 1) filter_usage(multi);
+        return 1;
     }
     std::string messages, err;
     const int rc = run_filter(o, messages, err);

@@ -40,5 +40,8 @@ std::string r_format_double(double x);
 double r_round7(double x);
 
 int filter_main(int argc, char **argv, bool multi);
+// The option table filter_main reads, over a list of words: 0 = ok, 2 = -h, else an error worded in err.  seen (may be null)
+// collects the short letter of every option met, in order.
+int parse_filter_options(const std::vector<std::string> &args, bool multi, FilterOptions &o, std::string &err, std::string *seen);
 
 }  // namespace pfh

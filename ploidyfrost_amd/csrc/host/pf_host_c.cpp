@@ -9,6 +9,7 @@
 #include "pf_cdbg.hpp"
 #include "pf_trace.hpp"
 #include "../pf_model_rows.hpp"
+#include "../pf_filter_rows.hpp"
 #include "pf_filter.hpp"
 #include "pf_gmm_model.hpp"
 #include "pf_host_colors.hpp"
@@ -648,6 +649,76 @@ int pfh_model_rows(int source, double min_frequency, const char *const *text, co
             start = end + 1;
         }
         if (source == pf::MODEL_FRE && have_last && L && s[L - 1] == '\n' && pf::model_fre_keep(last, min_frequency)) put(last);
+    }
+    *n = count;
+    return 0;
+}
+
+int pfh_set_filter(pfh_run *r, const pf_filter_opts *opts) {
+    return guarded(r, [&] { return r->cdbg->set_filter(opts); });
+}
+
+// the filtered collection's steps on the host, in its order: every row of the four tables read (what the filter refuses while it
+// reads comes first), R's error when no table keeps a row, then what the model says of the kept rows, then the array
+int pfh_filter_rows(int source, double min_frequency, const pf_filter_opts *o, const char *const *text, const uint64_t *len, double *out,
+                    uint64_t cap, uint64_t *n, char *err, uint64_t err_cap) {
+    if ((source != pf::MODEL_COV && source != pf::MODEL_FRE) || !o || !text || !len || !n) return 1;
+    auto say = [&](const std::string &m) {
+        if (err && err_cap) { strncpy(err, m.c_str(), err_cap - 1); err[err_cap - 1] = 0; }
+        return 1;
+    };
+    if (!(o->frequency <= 0.5)) return say("frequency should < 0.5 ");
+    pf::FilterRule f;
+    f.simple = o->simple != 0; f.indel = o->indel != 0; f.snp = o->snp != 0;
+    f.low = (double)o->low; f.up = (double)o->up; f.num = (double)o->num; f.distance = (double)o->distance; f.size = (double)o->size;
+    f.fq = o->frequency;
+    std::vector<double> col[pf::FILTER_COLUMNS];
+    bool kept_any = false;
+    std::string late;
+    for (int t = 0; t < pf::FILTER_TABLES; ++t) {
+        const char *s = text[t];
+        const uint64_t L = len[t];
+        if (L >= 0xFFFFFFF0ull) return 1;
+        const int A = t + 2, base = pf::filter_column_base(t);
+        uint64_t row = 0;
+        for (uint64_t start = 0; start < L; ++row) {
+            uint64_t end = start;
+            while (end < L && s[end] != '\n') ++end;
+            double v[5];
+            int code = pf::MODEL_ROW_OK;
+            bool kept = false;
+            if (source == pf::MODEL_COV) {
+                const int k = pf::filter_cov_row(s + start, (uint32_t)(end - start), A, f, min_frequency, v, &kept, &code);
+                for (int i = 0; i < k; ++i) col[t].push_back(v[i]);
+            } else {
+                const uint32_t mask = pf::filter_fre_row(s + start, (uint32_t)(end - start), A, f, v, &kept, &code);
+                for (int c = 0; c < A; ++c)
+                    if ((mask >> c) & 1u) col[base + c].push_back(v[c]);
+            }
+            kept_any = kept_any || kept;
+            if (code != pf::MODEL_ROW_OK) {
+                if (!pf::filter_err_is_late(code)) return say(pf::filter_error_text(code, t, row + 1));
+                if (late.empty()) late = pf::filter_error_text(code, t, row + 1);
+            }
+            start = end + 1;
+        }
+    }
+    if (!kept_any) return say(pf::filter_none_kept_text());
+    if (!late.empty()) return say(late);
+    uint64_t count = 0;
+    auto put = [&](double v) { if (out && count < cap) out[count] = v; ++count; };
+    if (source == pf::MODEL_COV) {
+        for (int t = 0; t < 3; ++t)
+            for (double v : col[t]) put(v);
+    } else {
+        double last = 0;
+        bool have = false;
+        for (const std::vector<double> &c : col)
+            for (double v : c) {
+                if (pf::model_fre_keep(v, min_frequency)) put(v);
+                last = v; have = true;
+            }
+        if (have && pf::model_fre_keep(last, min_frequency)) put(last);   // the file ends in a line feed: its last token counts twice
     }
     *n = count;
     return 0;

@@ -22,6 +22,9 @@
 #include <cmath>
 #include <cstring>
 #include <iostream>
+#include <iterator>
+#include <sstream>
+#include <algorithm>
 #include <string>
 #include <fstream>
 #include <thread>
@@ -120,7 +123,8 @@ struct Options {
     double match = 2, mismatch = -1, gap = -3, frequency = 0.998;
     // --model ...: the estimate in the same run
     string model_source, model_ploidy = "1:9";
-    bool model_only = false, model_option_seen = false;
+    bool model_only = false, model_option_seen = false, filter_seen = false;
+    string filter_words;   // --filter "<options of `ploidyfrost filter`>"
     double model_q = 0, model_m = 5.0, model_n = 2.0, model_delta = 0.01;
     int model_iter = 1000;
 };
@@ -128,6 +132,36 @@ struct Options {
 bool file_exists(const string &p) {
     struct stat sb;
     return stat(p.c_str(), &sb) == 0;
+}
+
+// --filter "<opts>": the words through the option table of `ploidyfrost filter`; what has no meaning in front of the model of the
+// same run is refused by name.  false: refused, one line on stderr.
+bool parse_filter_words(const string &words, pf_filter_opts &out) {
+    std::istringstream in(words);
+    vector<string> args;
+    for (string w; in >> w;) args.push_back(w);
+    pfh::FilterOptions o;
+    string err, seen;
+    const int ps = pfh::parse_filter_options(args, false, o, err, &seen);
+    if (ps == 2) { cerr << "Error: --filter takes the options of `ploidyfrost filter` (-S -l -u -I -P -n -d -s -q), not -h" << endl; return false; }
+    if (ps) {
+        if (err.rfind("Error: unknown option -c", 0) == 0 || err.rfind("Error: unknown option -v", 0) == 0 || err.rfind("Error: unknown option --color", 0) == 0 ||
+            err.rfind("Error: unknown option --cramer", 0) == 0)
+            err += " in --filter (filter-multi's option: the colored path has no model in the same run)";
+        else err += " in --filter";
+        cerr << err << endl;
+        return false;
+    }
+    for (char c : seen)
+        if (c == 'i' || c == 'o') {
+            cerr << "Error: --filter: -" << c << " has no meaning here (the filter reads this run's own streams and writes no table)" << endl;
+            return false;
+        }
+    if (o.frequency > 0.5) { cerr << "Error: --filter: -q " << o.frequency << ": frequency should < 0.5" << endl; return false; }
+    out.simple = o.simple; out.indel = o.indel; out.snp = o.snp;
+    out.low = o.low; out.up = o.up; out.num = o.num; out.distance = o.distance; out.size = o.size;
+    out.frequency = o.frequency;
+    return true;
 }
 
 void PrintModelUsage() {  // src/Main.cpp:694-718
@@ -143,6 +177,8 @@ void PrintModelUsage() {  // src/Main.cpp:694-718
          << "  -k,             Maximum iterations" << endl
          << "  -a,             Maximum delta" << endl
          << "  -o,             Output prefix" << endl
+         << "  --filter \"OPTS\" with -f: the rows of the (unfiltered) coverage files through `ploidyfrost filter OPTS` first, on the device;" << endl
+         << "                  add --source fre for the filtered frequencies (as `model -g <filtered>_allele_frequency.txt`)" << endl
          << endl;
 }
 
@@ -151,6 +187,22 @@ int model_main(int argc, char **argv) {
     string graphfile, colorfile, outprefix = "output";
     int lower = 1, upper = 9, iters = 1000;
     double frequency = 0, delta = 0.01, mthreshold = 5.0, nthreshold = 2.0;
+    // --filter "<opts>" [--source cov|fre] (this build's own switches, taken out of argv before getopt sees them)
+    bool filtered = false;
+    string filter_words, filter_source = "cov";
+    for (int i = 2; i < argc; ++i) {
+        const bool is_filter = strcmp(argv[i], "--filter") == 0;
+        if ((is_filter || strcmp(argv[i], "--source") == 0) && i + 1 < argc) {
+            if (is_filter) { filtered = true; filter_words = argv[i + 1]; }
+            else filter_source = argv[i + 1];
+            for (int j = i; j + 2 <= argc; ++j) argv[j] = j + 2 < argc ? argv[j + 2] : nullptr;
+            argc -= 2;
+            --i;
+        }
+    }
+    pf_filter_opts fopts = {};
+    if (filtered && !parse_filter_words(filter_words, fopts)) return 1;
+    if (filtered && filter_source != "cov" && filter_source != "fre") { cerr << "Error: --source " << filter_source << ": cov or fre" << endl; return 1; }
     int oc;
     while ((oc = getopt(argc, argv, "M:D:G:z:a:l:q:u:e:C:R:o:t:g:f:k:d:m:n:h:ibvpNSc")) != -1) {
         switch (oc) {
@@ -177,6 +229,8 @@ int model_main(int argc, char **argv) {
     if (nthreshold < 0) { cerr << "Error: minimum threshold should > 0 " << endl; ok = false; }
     if (colorfile.empty() && graphfile.empty()) { cout << "ERROR: input a frequency or coverage file " << endl; ok = false; }
     if (!graphfile.empty() && !file_exists(graphfile)) { cout << "ERROR: open frequency file " << graphfile << " error!" << endl; ok = false; }
+    if (filtered && colorfile.empty()) { cerr << "Error: model --filter reads the coverage files of a prefix: give it with -f" << endl; return 1; }
+    if (filtered && !file_exists(colorfile + "_pentacov.txt")) { cout << "ERROR: open coverage file " << colorfile + "_pentacov.txt" << " error!" << endl; ok = false; }
     if (!colorfile.empty())
         for (const char *suf : {"_bicov.txt", "_tricov.txt", "_tetracov.txt"})
             if (!file_exists(colorfile + suf)) { cout << "ERROR: open coverage file " << colorfile + suf << " error!" << endl; ok = false; }
@@ -187,6 +241,36 @@ int model_main(int argc, char **argv) {
     model.setNThreshold(nthreshold);
     model.setMaxIterNum(iters);
     model.setMaxDeltaNum(delta);
+    if (filtered) {
+        // the filter and the fit in one command from files: the four tables through the kernels of the one-command run
+        // (pf_call_model_take_text), pieces of at most 1 MB cut behind line feeds
+        pf_ctx *ctx = nullptr;
+        auto leave = [&](const string &m) {
+            cout << m << endl;
+            exit(EXIT_FAILURE);
+        };
+        if (pf_create(0, &ctx) != PF_OK) leave(string("GmmModel: no device context (") + (pf_last_error(nullptr) ? pf_last_error(nullptr) : "?") + "); the fit runs on the GPU only");
+        if (pf_call_model_begin(ctx, filter_source == "cov" ? PF_MODEL_COV : PF_MODEL_FRE, frequency) != PF_OK || pf_call_model_filter(ctx, &fopts) != PF_OK) leave(pf_last_error(ctx));
+        int ord = 0;
+        for (const char *suf : {"_bicov.txt", "_tricov.txt", "_tetracov.txt", "_pentacov.txt"}) {
+            ifstream in(colorfile + suf, std::ios::binary);
+            const string text((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+            for (size_t at = 0; at < text.size();) {
+                size_t end = std::min(text.size(), at + ((size_t)1 << 20));
+                if (end < text.size()) {
+                    const size_t nl = text.rfind('\n', end - 1);
+                    if (nl != string::npos && nl >= at) end = nl + 1;
+                    else { const size_t next = text.find('\n', end); end = next == string::npos ? text.size() : next + 1; }
+                }
+                if (pf_call_model_take_text(ctx, ord, text.data() + at, end - at) != PF_OK) leave(pf_last_error(ctx));
+                at = end;
+            }
+            ++ord;
+        }
+        uint64_t n_values = 0;
+        if (pf_call_model_finish(ctx, &n_values) != PF_OK) leave(pf_last_error(ctx));
+        model.borrow(ctx, (size_t)n_values);
+    } else
     if (!colorfile.empty() ? model.readCovFile(colorfile, frequency) : model.readFreFile(graphfile, frequency)) {
         cout << model.error() << endl;
         exit(EXIT_FAILURE);
@@ -245,6 +329,12 @@ int main(int argc, char **argv) {
             for (int j = i; j + 1 <= argc; ++j) argv[j] = j + 1 < argc ? argv[j + 1] : nullptr;
             argc -= 1;
             --i;
+        } else if (strcmp(argv[i], "--filter") == 0 && i + 1 < argc) {
+            opt.filter_seen = true;
+            opt.filter_words = argv[i + 1];
+            for (int j = i; j + 2 <= argc; ++j) argv[j] = j + 2 < argc ? argv[j + 2] : nullptr;
+            argc -= 2;
+            --i;
         } else if (strncmp(argv[i], "--model", 7) == 0 && i + 1 < argc) {
             const string name = argv[i], val = argv[i + 1];
             if (name == "--model") opt.model_source = val;
@@ -290,6 +380,13 @@ int main(int argc, char **argv) {
     }
     // --model: refused here, before anything is read or written
     pfh::CDBG::ModelOptions model;
+    pf_filter_opts filter = {};
+    if (opt.filter_seen) {
+        if (opt.model_source.empty()) { cerr << "Error: --filter stands in front of the model of the same run: it needs --model cov|fre (the filtered tables themselves: `ploidyfrost filter`)" << endl; return 1; }
+        if (!opt.colorfile.empty()) { cerr << "Error: --filter reads the single-sample result streams; with -f the coverage tables have other columns (filter-multi)" << endl; return 1; }
+        if (opt.gpus > 1) { cerr << "Error: --filter and --gpus " << opt.gpus << " do not go together (each rank holds a slice of the rows)" << endl; return 1; }
+        if (!parse_filter_words(opt.filter_words, filter)) return 1;
+    }
     if (opt.model_option_seen) {
         if (opt.model_source.empty()) { cerr << "Error: the --model-... options need --model cov|fre" << endl; return 1; }
         if (opt.model_source != "cov" && opt.model_source != "fre") { cerr << "Error: --model " << opt.model_source << ": the source is cov or fre" << endl; return 1; }
@@ -614,6 +711,7 @@ int main(int argc, char **argv) {
         _exit(0);
     }
     if (model.on && g.set_model(model)) die();
+    if (opt.filter_seen && g.set_filter(&filter)) die();
     if (g.setUnitigId(opt.outprefix, opt.graphfile, opt.nb_threads)) die();
     if (opt.info && g.printInfo(opt.verbose, opt.outprefix)) die();
     mark("setUnitigId");

@@ -26,6 +26,7 @@
 #include "pf_cov_stream.hpp"
 #include "pf_ctx.hpp"
 #include "pf_device_common.hpp"
+#include "pf_filter_rows.hpp"
 #include "pf_format_dev.hpp"
 #include "pf_pair_dev.hpp"
 #include "pf_stack_dev.hpp"
@@ -194,12 +195,16 @@ struct CallState {
         double q = 0;
         hipStream_t stream = nullptr;
         DevBuf state, flags, ends, nvals, voff, n_rows, scan;   // the collection's record; per piece: line-feed flags, row ends, values per row, their offsets
-        DevBuf vals[3];                                         // the values of each stream of the source, in file order
-        uint64_t bound[3] = {};                                 // values the text taken so far can hold at most
+        DevBuf vals[14];                                        // the values of each stream of the source, in file order (with a filter, fre: of each column)
+        uint64_t bound[14] = {};                                // values the text taken so far can hold at most
+        bool filter = false, taken = false;                     // pf_call_model_filter; a piece was taken since begin
+        pf::FilterRule rule = {};
+        DevBuf cflag, coff, upload, tokens;                     // with a filter, fre: a piece's column flags and their scan; take_text's piece; finish
         hipEvent_t read_ev[PF_CALL_SLABS] = {};                 // the kernels over a slab's piece have read it
     } model;
     void release_all() {
-        for (DevBuf *b : {&model.state, &model.flags, &model.ends, &model.nvals, &model.voff, &model.n_rows, &model.scan, &model.vals[0], &model.vals[1], &model.vals[2]}) b->release();
+        for (DevBuf *b : {&model.state, &model.flags, &model.ends, &model.nvals, &model.voff, &model.n_rows, &model.scan, &model.cflag, &model.coff, &model.upload, &model.tokens}) b->release();
+        for (DevBuf &b : model.vals) b.release();
         if (model.stream) { (void)hipStreamDestroy(model.stream); model.stream = nullptr; }
         for (hipEvent_t &e : model.read_ev)
             if (e) { (void)hipEventDestroy(e); e = nullptr; }

@@ -19,7 +19,10 @@ enum ModelRowErr : int {
     MODEL_ROW_COV_ZERO = 1,    // the coverages of a row sum to 0 (the reference divides by it)
     MODEL_ROW_BAD_TOKEN = 2,   // a frequency row is not one number operator>>(double) reads ("nan", "inf", two tokens, none)
     MODEL_ROW_RANGE = 3,       // a number outside what one fp64 operation converts exactly (more than 15 digits, |exponent| > 22)
-    MODEL_ROW_NO_ROOM = 4      // device only: the value array was sized for fewer values than the rows give
+    MODEL_ROW_NO_ROOM = 4,     // device only: the value array was sized for fewer values than the rows give
+    // with a row filter in front (pf_filter_rows.hpp)
+    MODEL_ROW_FIELDS = 5,      // a coverage row that does not have its A + 5 fields
+    MODEL_ROW_R_SCI = 6        // a kept coverage R's write.table renders in scientific notation (`model -f` then reads its leading digit)
 };
 
 PF_MODEL_HD inline bool model_isspace(char c) { return c == ' ' || (c >= '\t' && c <= '\r'); }
@@ -42,20 +45,8 @@ PF_MODEL_HD inline int model_atoi(const char *s, uint32_t len, uint32_t from) {
     return (int)(uint32_t)(neg ? 0 - v : v);
 }
 
-// One row of <prefix>_bicov / _tricov / _tetracov.txt (n = 2 / 3 / 4): the values it adds to the model's array, 0 or n of them.
-// The first n tab-terminated fields through atoi; fewer than n tabs: skipped; sum >= 10000: skipped; sum == 0: the error; the
-// frequency test divides INTEGERS; "min" of three or more alleles only compares neighbours.
-PF_MODEL_HD inline int model_cov_row(const char *s, uint32_t len, int n, double q, double *out, int *err) {
-    *err = MODEL_ROW_OK;
-    int cov[4];
-    uint32_t from = 0;
-    for (int i = 0; i < n; ++i) {
-        uint32_t t = from;
-        while (t < len && s[t] != '\t') ++t;
-        if (t >= len) return 0;
-        cov[i] = model_atoi(s, len, from);
-        from = t + 1;
-    }
+// The part of a coverage row behind atoi: its n integers -> its values (model_cov_row below; the filtered rows of pf_filter_rows.hpp)
+PF_MODEL_HD inline int model_cov_ints(const int *cov, int n, double q, double *out, int *err) {
     uint32_t usum = 0;
     for (int i = 0; i < n; ++i) usum += (uint32_t)cov[i];
     const int cov_sum = (int)usum;
@@ -70,16 +61,30 @@ PF_MODEL_HD inline int model_cov_row(const char *s, uint32_t len, int n, double 
     return n;
 }
 
+// One row of <prefix>_bicov / _tricov / _tetracov.txt (n = 2 / 3 / 4): the values it adds to the model's array, 0 or n of them.
+// The first n tab-terminated fields through atoi; fewer than n tabs: skipped; sum >= 10000: skipped; sum == 0: the error; the
+// frequency test divides INTEGERS; "min" of three or more alleles only compares neighbours.
+PF_MODEL_HD inline int model_cov_row(const char *s, uint32_t len, int n, double q, double *out, int *err) {
+    *err = MODEL_ROW_OK;
+    int cov[4];
+    uint32_t from = 0;
+    for (int i = 0; i < n; ++i) {
+        uint32_t t = from;
+        while (t < len && s[t] != '\t') ++t;
+        if (t >= len) return 0;
+        cov[i] = model_atoi(s, len, from);
+        from = t + 1;
+    }
+    return model_cov_ints(cov, n, q, out, err);
+}
+
 // One token of <prefix>_allele_frequency.txt as operator>>(double) / strtod converts it, for the forms "%g" prints: an
 // optional '-', digits with at most one '.', an optional exponent.  The value is m / 10^e or m * 10^e with m < 10^15 < 2^53 and
 // e <= 22: m and 10^e are exact in fp64, so the one division or multiplication is correctly rounded -- the same double strtod
 // gives.  Anything else is named, never approximated.
-PF_MODEL_HD inline int model_fre_token(const char *s, uint32_t len, double *val) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
-    const double p10[23] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11,
-                            1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
+// ... in two steps: the token's decimal parts (value = +-m * 10^e10, m < 10^15; m_digits = digits of m counted from its first
+// non-zero one), then the one operation
+PF_MODEL_HD inline int model_token_parts(const char *s, uint32_t len, bool *negative, uint64_t *mant, int *m_digits, int *exp10) {
     uint32_t i = 0;
     bool neg = false;
     if (i < len && s[i] == '-') { neg = true; ++i; }
@@ -108,7 +113,20 @@ PF_MODEL_HD inline int model_fre_token(const char *s, uint32_t len, double *val)
         if (eneg) e = -e;
     }
     if (i != len) return MODEL_ROW_BAD_TOKEN;
-    const int e10 = e - frac;
+    *negative = neg; *mant = m; *m_digits = sig; *exp10 = e - frac;
+    return MODEL_ROW_OK;
+}
+PF_MODEL_HD inline int model_fre_token(const char *s, uint32_t len, double *val) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const double p10[23] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11,
+                            1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
+    bool neg;
+    uint64_t m;
+    int sig, e10;
+    const int st = model_token_parts(s, len, &neg, &m, &sig, &e10);
+    if (st != MODEL_ROW_OK) return st;
     double v;
     if (m == 0) v = 0.0;
     else if (e10 < -22 || e10 > 22) return MODEL_ROW_RANGE;

@@ -33,7 +33,13 @@ DECLARED_SYMBOLS = ["pfh_open", "pfh_close", "pfh_last_error", "pfh_set_output_d
                     "pfh_find_shard", "pfh_shard_records", "pfh_shard_pool", "pfh_find_replay", "pfh_set_replay_threads", "pfh_set_write_super_bubble", "pfh_ploidy_select", "pfh_ploidy_select_colored", "pfh_ploidy_align", "pfh_ploidy_text", "pfh_ploidy_write",
                     "pfh_gmm_open", "pfh_gmm_close", "pfh_gmm_last_error", "pfh_gmm_read_fre", "pfh_gmm_read_cov", "pfh_gmm_set_values",
                     "pfh_gmm_size", "pfh_gmm_values", "pfh_gmm_fit", "pfh_gmm_run", "pfh_gmm_kernel_time",
-                    "pfh_set_model", "pfh_model_values", "pfh_model_fit", "pfh_model_ploidy", "pfh_text_bytes_fetched", "pfh_model_rows"]
+                    "pfh_set_model", "pfh_model_values", "pfh_model_fit", "pfh_model_ploidy", "pfh_text_bytes_fetched", "pfh_model_rows",
+                    "pfh_set_filter", "pfh_filter_rows"]
+
+
+class FilterOpts(C.Structure):   # pf_filter_opts (include/ploidyfrost_hip.h)
+    _fields_ = [("simple", C.c_int), ("indel", C.c_int), ("snp", C.c_int), ("low", C.c_longlong), ("up", C.c_longlong),
+                ("num", C.c_longlong), ("distance", C.c_longlong), ("size", C.c_longlong), ("frequency", C.c_double)]
 
 
 def load_library() -> C.CDLL:
@@ -140,6 +146,10 @@ def load_library() -> C.CDLL:
     L.pfh_text_bytes_fetched.restype = u64
     L.pfh_text_bytes_fetched.argtypes = [vp]
     L.pfh_model_rows.argtypes = [C.c_int, d, C.POINTER(C.c_char_p), C.POINTER(u64), vp, u64, C.POINTER(u64), C.c_char_p, u64]
+    L.pfh_set_filter.restype = C.c_int
+    L.pfh_set_filter.argtypes = [vp, C.POINTER(FilterOpts)]
+    L.pfh_filter_rows.restype = C.c_int
+    L.pfh_filter_rows.argtypes = [C.c_int, d, C.POINTER(FilterOpts), C.POINTER(C.c_char_p), C.POINTER(u64), vp, u64, C.POINTER(u64), C.c_char_p, u64]
     _lib = L
     return L
 
@@ -284,6 +294,32 @@ def model_rows(source: str, texts, q: float = 0.0) -> np.ndarray:
     return out[: n.value].copy()
 
 
+def filter_opts(simple=False, low=0, up=10000, indel=False, snp=False, num=10000, distance=-1, size=10000, frequency=0.05) -> FilterOpts:
+    """the options of `ploidyfrost filter` (-S -l -u -I -P -n -d -s -q) with the script's defaults"""
+    return FilterOpts(int(simple), int(indel), int(snp), int(low), int(up), int(num), int(distance), int(size), float(frequency))
+
+
+def filter_rows(source: str, texts, q: float = 0.0, **opts) -> np.ndarray:
+    """The model's values behind a row filter, as the shared rule (csrc/pf_filter_rows.hpp, what the device kernels run) reads
+    them from the bytes of (_bicov, _tricov, _tetracov, _pentacov): what `filter` with **opts (see filter_opts) followed by
+    `model -f` (source "cov") / `model -g <filtered>_allele_frequency.txt` ("fre") with -q q reads.  No device.  RuntimeError
+    with the wording of the one-command run for what it refuses."""
+    L = load_library()
+    texts = [bytes(t) for t in texts]
+    if len(texts) != 4:
+        raise ValueError("four texts: bi, tri, tetra, penta")
+    ptrs = (C.c_char_p * 4)(*texts)
+    lens = (C.c_uint64 * 4)(*[len(t) for t in texts])
+    o = filter_opts(**opts)
+    n = C.c_uint64()
+    err = C.create_string_buffer(1024)
+    cap = sum(len(t) for t in texts) + 2
+    out = np.zeros(cap, dtype=np.float64)
+    if L.pfh_filter_rows(MODEL_SOURCES[source], q, C.byref(o), ptrs, lens, out.ctypes.data, cap, C.byref(n), err, len(err)) != 0:
+        raise RuntimeError(err.value.decode() or "pfh_filter_rows failed")
+    return out[: n.value].copy()
+
+
 def load_trace(reset: bool = True) -> list:
     """[(step, seconds)] of the loads of this process since the last reset (pfh_load_trace)"""
     L = load_library()
@@ -364,6 +400,16 @@ class Run:
         source None switches it off."""
         src = -1 if source is None else MODEL_SOURCES[source]
         self._check(self.L.pfh_set_model(self.h, src, q, lo, hi, m_thre, n_thre, max_iter, max_delta, int(only)))
+
+    def set_filter(self, simple=False, low=0, up=10000, indel=False, snp=False, num=10000, distance=-1, size=10000, frequency=0.05):
+        """`ploidyfrost filter`'s row predicates in front of the model of the same run (after set_model): the next
+        ploidy_estimation fits what `filter` with these options followed by `model` would read from this run's files, and writes
+        no filtered table.  set_filter(None) takes the filter away again, as set_model(None) does."""
+        if simple is None:
+            self._check(self.L.pfh_set_filter(self.h, None))
+            return
+        o = filter_opts(simple, low, up, indel, snp, num, distance, size, frequency)
+        self._check(self.L.pfh_set_filter(self.h, C.byref(o)))
 
     def model_values(self) -> np.ndarray:
         """the array K-GMM fitted in the last ploidy_estimation, copied from the device"""
