@@ -612,7 +612,8 @@ int pf_gmm_values(pf_ctx *, double *dst, uint64_t cap);
  * pf_gmm_fit reads without a file, a host loop or a second context, element for element what GmmModel::readCovFile / readFreFile
  * (csrc/host/pf_gmm_model.cpp, reference src/GmmModel.cpp:21-257) make of the files -- quirks included: atoi on "%g" fields, the
  * integer frequency test, the neighbour-pair "min", pentacov never read, the last frequency token counted twice.  The per-row rule
- * is csrc/pf_model_rows.hpp, shared with the host (pfh_model_rows).  Single-sample path only.
+ * is csrc/pf_model_rows.hpp, shared with the host (pfh_model_rows).  Single-sample path; the colored one behind
+ * pf_call_model_filter_multi (below).
  *   pf_call_model_begin   source PF_MODEL_COV | PF_MODEL_FRE, minimum frequency q (`model -q`); drops the context's GMM array.
  *   pf_call_model_take    the piece in `slab`: after the pf_call_text / pf_call_text_range(_lane) call that made it, before the next
  *                         call that writes that slab (which then waits on the device until these kernels have read it).  Pieces
@@ -649,6 +650,41 @@ typedef struct pf_filter_opts {
 } pf_filter_opts;
 int pf_call_model_filter(pf_ctx *, const pf_filter_opts *);
 int pf_call_model_take_text(pf_ctx *, int stream_ord, const char *host_text, uint64_t len);
+/* ---- the multi form: the colored tables behind `ploidyfrost filter-multi`'s predicates ----
+ * The colored path writes rows of A + 7 fields (A coverages, colour, isStrict, VarType, VarId, VarNum, Cramer's V, VarDis); the rule
+ * is the opt.multi branch of run_filter (csrc/host/pf_filter.cpp) in csrc/pf_filter_rows.hpp: the predicates of the single-sample
+ * filter without the clause on the sum of the first four coverages, Cramer's V > cramer (strictly), colour == color when color >= 0.
+ * Behind it nothing changes: the array is what `filter-multi` followed by `model -f` / `model -g` reads.
+ *   pf_call_model_filter_multi  between pf_call_model_begin and the first take, instead of pf_call_model_filter.  each_color = 0:
+ *                               one collection, of colour `color` or pooled (color < 0).  each_color != 0 (with color < 0 only): the
+ *                               pooled collection, each value with its row's colour beside it; pf_call_model_finish then gives the
+ *                               pooled array and count and keeps the tokens for pf_call_model_color_select.  NULL: no filter.
+ *   pf_call_model_color_count   after such a finish: one more than the largest colour that kept a row (0: none, or no such finish).
+ *   pf_call_model_color_select  makes the array of colour `color` -- what the chain run with -c color reads, element for element --
+ *                               the context's GMM array (pf_gmm_fit, pf_gmm_values), *n_values its length; a colour that kept no
+ *                               row: PF_OK, *n_values = PF_MODEL_NO_ROW and the array as it was.  *n_values = 0: rows kept that
+ *                               hold no value (cov: penta rows alone; fre: all outside the model's test) -- nothing to fit.
+ *                               Any number of times, any order.
+ * Refusals (PF_ERR_ARG, pf_last_error): pf_call_model_filter_multi outside begin .. first take, with frequency > 0.5, with
+ * each_color and color >= 0 or without options; pf_call_model_take on a colored context without the multi filter (the tables have
+ * other columns) and with it on a single-sample one; pf_call_model_filter on a colored context; pf_call_model_color_select
+ * without a finished each_color collection or with a colour outside 0 .. PF_MAX_COLORS - 1.  pf_call_model_finish refuses as with
+ * pf_call_model_filter (a row without its A + 7 fields is R's "did not have <table + 9> elements"; a Cramer's V of 0 / 0, printed
+ * "-nan", is a cell that is no finite decimal number) and, split by colour, a kept row whose colour cell is no integer in
+ * 0 .. PF_MAX_COLORS - 1; a refusal the model gives for a kept row (a sum of 0, scientific notation) then refuses every colour,
+ * as it refuses the pooled collection. */
+typedef struct pf_filter_multi_opts {
+    int simple, indel, snp;
+    long long low, up;
+    long long num, distance, size;
+    double frequency;
+    long long color;                 /* -c       rows of this colour; < 0: every colour */
+    double cramer;                   /* -v       Cramer's V > cramer */
+} pf_filter_multi_opts;
+#define PF_MODEL_NO_ROW 0xFFFFFFFFFFFFFFFFull
+int pf_call_model_filter_multi(pf_ctx *, const pf_filter_multi_opts *, int each_color);
+uint32_t pf_call_model_color_count(const pf_ctx *);
+int pf_call_model_color_select(pf_ctx *, int color, uint64_t *n_values);
 /* Bytes of the ten result streams the pf_call_fetch* calls of this context have copied to the host so far. */
 uint64_t pf_call_fetched_bytes(const pf_ctx *);
 

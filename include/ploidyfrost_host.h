@@ -182,6 +182,29 @@ int pfh_set_filter(pfh_run *, const pf_filter_opts *);
 int pfh_filter_rows(int source, double min_frequency, const pf_filter_opts *opts, const char *const *text, const uint64_t *len,
                     double *out, uint64_t cap, uint64_t *n, char *err, uint64_t err_cap);
 
+/* ---- the colored path: `ploidyfrost filter-multi`'s predicates in front of the model (pf_filter_multi_opts in ploidyfrost_hip.h) ----
+ * A colored run accepts pfh_set_model behind a multi filter only (its unfiltered tables pool every sample): pfh_set_model, then
+ * pfh_set_filter_multi, then pfh_ploidy_estimation_colored, which fits what `filter-multi -i <outpre> ...` followed by `model`
+ * would read and writes no filtered table.  each_color != 0 (with opts->color < 0): one fit for every colour that keeps a row, in
+ * colour order, written to <outpre>_color<c>_model_result.txt -- the chain run with -c c -- and no pooled result file;
+ * pfh_model_values then gives the pooled array (of the last pass, whatever is set afterwards); a colour whose kept rows hold no
+ * value for the model is not fitted and gets no file, and the colours above it are fitted all the same.  NULL: off again, as pfh_set_model with source < 0 does.  Refused on a
+ * single-sample run, without a model, for frequency > 0.5 and for each_color with one colour; pfh_set_filter is refused on a
+ * colored run; a colored pass with a model and no multi filter is refused when it starts.
+ * After a pass split by colour: pfh_model_color_count = the colours fitted, pfh_model_color_at(i) the i-th of them (ascending);
+ * pfh_model_color_values / _fit / _ploidy as pfh_model_values / _fit / _ploidy for one colour (values: ~0 for a colour without a
+ * fit; fit: 1).
+ * pfh_filter_rows_multi: the multi rule on host text as pfh_filter_rows has the single-sample one (rows of A + 7 fields). */
+int pfh_set_filter_multi(pfh_run *, const pf_filter_multi_opts *, int each_color);
+int pfh_filter_rows_multi(int source, double min_frequency, const pf_filter_multi_opts *opts, const char *const *text, const uint64_t *len,
+                          double *out, uint64_t cap, uint64_t *n, char *err, uint64_t err_cap);
+uint32_t pfh_model_color_count(const pfh_run *);
+int pfh_model_color_at(const pfh_run *, uint32_t i);
+uint64_t pfh_model_color_values(const pfh_run *, int color, double *out, uint64_t cap);
+int pfh_model_color_fit(const pfh_run *, int color, uint32_t gauss, double *weights, double *means, double *vars, double *loglik, double *aic,
+                        uint32_t *iterations);
+double pfh_model_color_ploidy(const pfh_run *, int color);
+
 /* The host tier of K-BFS on its own (host/pf_bfs_host.hpp; no device involved): extractSuperBubble_ptr's traversal
  * (src/CDBG.cpp:253-372) from one oriented vertex over CSR rows laid out as pf_build_adjacency returns them.  Fills *record
  * (list_off = 0) and copies its list -- seen[] when an exit was found, the cycle set otherwise -- to `list`.

@@ -470,18 +470,31 @@ int CDBG::set_reference_threads(size_t n) {
 int CDBG::set_model(const ModelOptions &o) {
     auto refuse = [&](const std::string &m) { err_ = m; return (int)PF_ERR_ARG; };
     if (o.on) {
-        if (col_) return refuse("CCDBG:: the model in the same run is built for the single-sample path only (the colored coverage tables have other columns)");
         if (o.source != PF_MODEL_COV && o.source != PF_MODEL_FRE) return refuse("CDBG::set_model(): source is cov or fre");
         if (o.lo < 1 || o.hi < o.lo || o.hi > PF_GMM_MAX_GAUSS) return refuse("CDBG::set_model(): Gaussians lo:hi with 1 <= lo <= hi <= " + std::to_string(PF_GMM_MAX_GAUSS));
         if (o.q >= 0.5 || o.max_iter < 0 || o.max_delta < 0 || o.m_thre < 0 || o.n_thre < 0) return refuse("CDBG::set_model(): q < 0.5, iterations, delta and thresholds >= 0 (as `model` checks them)");
     }
     model_ = o;
-    if (!o.on) model_.only = filter_on_ = false;
+    if (!o.on) model_.only = filter_on_ = multi_on_ = multi_each_ = false;
+    return 0;
+}
+
+int CDBG::set_filter_multi(const pf_filter_multi_opts *o, bool each_color) {
+    auto refuse = [&](const std::string &m) { err_ = m; return (int)PF_ERR_ARG; };
+    if (o && !col_) return refuse("CDBG::set_filter_multi(): filter-multi reads the colored coverage tables; the single-sample path has set_filter");
+    if (o && !model_.on) return refuse("CCDBG::set_filter_multi(): the row filter stands in front of the model of the same run; set a model first");
+    if (o && !(o->frequency <= 0.5)) return refuse("CCDBG::set_filter_multi(): frequency should < 0.5");
+    if (o && each_color && o->color >= 0) return refuse("CCDBG::set_filter_multi(): every colour at once does not go with one colour (color >= 0)");
+    if (!o && each_color) return refuse("CCDBG::set_filter_multi(): every colour at once needs the filter's options");
+    multi_on_ = o != nullptr;
+    multi_each_ = o && each_color;
+    if (o) multi_ = *o;
     return 0;
 }
 
 int CDBG::set_filter(const pf_filter_opts *o) {
     auto refuse = [&](const std::string &m) { err_ = m; return (int)PF_ERR_ARG; };
+    if (o && col_) return refuse("CCDBG::set_filter(): the colored coverage tables have other columns (single-sample path only; the colored one has set_filter_multi)");
     if (o && !model_.on) return refuse("CDBG::set_filter(): the row filter stands in front of the model of the same run; set a model first");
     if (o && !(o->frequency <= 0.5)) return refuse("CDBG::set_filter(): frequency should < 0.5");
     filter_on_ = o != nullptr;

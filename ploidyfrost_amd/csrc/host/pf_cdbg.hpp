@@ -141,6 +141,24 @@ public:
     // estimate of `filter` + `model` on this run's files, no filtered table written.  Null: no filter.  Refused unless a model is set;
     // switching the model off drops it.
     int set_filter(const pf_filter_opts *o);
+    // the colored path: `ploidyfrost filter-multi`'s predicates (pf_call_model_filter_multi) in front of the model, which the colored
+    // run accepts behind them only (its unfiltered tables pool every sample): set_model, then this, then PloidyEstimation.
+    // each_color: one fit per colour that keeps a row, <outpre>_color<c>_model_result.txt each (needs color < 0).  Null: off.
+    int set_filter_multi(const pf_filter_multi_opts *o, bool each_color);
+    // of the last PloidyEstimation split by colour, in colour order: the fits as model_fits() has them, the values copied from the
+    // device, the colours below model_color_count() that kept no row, and those that kept rows which hold no value for the model
+    // (cov: penta rows alone; fre: every frequency outside the model's test) -- neither kind is fitted or gets a file
+    struct ColorFit {
+        int color = 0;
+        std::vector<GmmModel::Fit> fits;
+        double ploidy = 0;
+        std::vector<double> values;
+    };
+    const std::vector<ColorFit> &model_color_fits() const { return color_fits_; }
+    const std::vector<int> &model_colors_without_rows() const { return color_none_; }
+    const std::vector<int> &model_colors_without_values() const { return color_empty_; }
+    const std::vector<double> &model_pooled_values() const { return pooled_values_; }
+    bool model_was_each_color() const { return last_each_; }   // of the last pass, not of the settings
     // of the last PloidyEstimation with a model: one record per number of Gaussians, the value of the result file's last line and
     // that line; how many values the device array holds
     const std::vector<GmmModel::Fit> &model_fits() const { return model_fits_; }
@@ -214,6 +232,12 @@ protected:
     ModelOptions model_;
     bool filter_on_ = false;
     pf_filter_opts filter_ = {};
+    bool multi_on_ = false, multi_each_ = false;
+    pf_filter_multi_opts multi_ = {};
+    std::vector<ColorFit> color_fits_;
+    std::vector<int> color_none_, color_empty_;
+    std::vector<double> pooled_values_;
+    bool last_each_ = false;   // the last PloidyEstimation's model was split by colour (whatever the settings are by now)
     std::vector<GmmModel::Fit> model_fits_;
     double model_ploidy_ = 0;
     std::string model_last_line_;

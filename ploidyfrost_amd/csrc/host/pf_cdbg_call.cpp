@@ -238,13 +238,19 @@ int CDBG::ploidy_estimation_resident(const std::string &outpre, const std::vecto
     clock_t c0 = clock();
     if (!quiet_) printf("%s::PloidyEstimation():  Analyzing superbubbles to generate sites' information\n", tag_);
     if (write_files_ && ensure_dir()) return status_;
-    if (model_.on && (col_ || !write_files_)) return fail(PF_ERR_ARG, std::string(tag_) + "::PloidyEstimation(): the model in the same run needs the single-sample path and an output directory");
+    if (model_.on && ((col_ && !multi_on_) || !write_files_))
+        return fail(PF_ERR_ARG, std::string(tag_) + "::PloidyEstimation(): the model in the same run needs the single-sample path (the colored one: a multi filter in front of it, set_filter_multi) and an output directory");
     // with ModelOptions::only the ten calling files are neither opened nor written, and their text stays on the device
     const bool write_ten = write_files_ && !model_.only;
     model_fits_.clear();
     model_last_line_.clear();
     model_ploidy_ = 0;
     model_n_ = 0;
+    color_fits_.clear();
+    color_none_.clear();
+    color_empty_.clear();
+    pooled_values_.clear();
+    last_each_ = false;
     const uint64_t fetched_before = pf_call_fetched_bytes(ctx_);
     const unsigned T = threads_ ? threads_ : (unsigned)std::max<size_t>(thr, 1);
     times_.cov_device_s = times_.tasks_s = times_.align_s = times_.sites_s = times_.format_s = times_.write_s = 0;
@@ -336,7 +342,8 @@ int CDBG::ploidy_estimation_resident(const std::string &outpre, const std::vecto
     // The copy to the host is what a pass ends with: 17.7 MB a piece at 55 GB/s, 0.33 ms each, twelve pieces behind the alignment.
     const bool num_packed = !getenv("PF_NUMERIC_ASCII");
     if (pf_call_set_numeric_packed(ctx_, num_packed ? 1 : 0) != PF_OK) return fail(PF_ERR_HIP, std::string(tag_) + "::PloidyEstimation(): " + pf_last_error(ctx_));
-    if (model_.on && (pf_call_model_begin(ctx_, model_.source, model_.q) != PF_OK || (filter_on_ && pf_call_model_filter(ctx_, &filter_) != PF_OK)))
+    if (model_.on && (pf_call_model_begin(ctx_, model_.source, model_.q) != PF_OK || (filter_on_ && pf_call_model_filter(ctx_, &filter_) != PF_OK) ||
+                      (multi_on_ && pf_call_model_filter_multi(ctx_, &multi_, multi_each_ ? 1 : 0) != PF_OK)))
         return fail(PF_ERR_ARG, std::string(tag_) + "::PloidyEstimation(): " + pf_last_error(ctx_));
     struct PackGuard {   // the sliced calls (ploidy_text, one graph over several ranks) read the text as the device writes it
         pf_ctx *c;
@@ -766,19 +773,48 @@ int CDBG::ploidy_estimation_resident(const std::string &outpre, const std::vecto
         const int ms = pf_call_model_finish(ctx_, &n_values);
         if (ms != PF_OK) return model_fail(ms, pf_last_error(ctx_));
         model_n_ = n_values;
-        GmmModel gm;
-        gm.borrow(ctx_, (size_t)n_values);
-        gm.setMThreshold(model_.m_thre);
-        gm.setNThreshold(model_.n_thre);
-        gm.setMaxIterNum(model_.max_iter);
-        gm.setMaxDeltaNum(model_.max_delta);
+        auto fit = [&](uint64_t n, const std::string &prefix, std::vector<GmmModel::Fit> &fits, double &ploidy, std::string &merr) {
+            GmmModel gm;
+            gm.borrow(ctx_, (size_t)n);
+            gm.setMThreshold(model_.m_thre);
+            gm.setNThreshold(model_.n_thre);
+            gm.setMaxIterNum(model_.max_iter);
+            gm.setMaxDeltaNum(model_.max_delta);
+            if (run_model(gm, model_.lo, model_.hi, prefix, merr, &ploidy)) return 1;
+            fits = gm.fits();
+            return 0;
+        };
         std::string merr;
-        if (run_model(gm, model_.lo, model_.hi, outdir_ + "/" + outpre, merr, &model_ploidy_)) return model_fail(PF_ERR_ARG, merr);
-        model_fits_ = gm.fits();
-        std::ostringstream line;
-        line << "estimated ploidy level is : " << model_ploidy_;
-        model_last_line_ = line.str();
-        tp("model fitted");
+        if (multi_on_ && multi_each_) {
+            // one fit per colour that kept a row, in colour order, each over its own selection of the pooled tokens
+            last_each_ = true;
+            pooled_values_.resize((size_t)n_values);
+            if (n_values && pf_gmm_values(ctx_, pooled_values_.data(), n_values) != PF_OK) return model_fail(PF_ERR_HIP, pf_last_error(ctx_));
+            const uint32_t nc = std::max<uint32_t>(pf_call_model_color_count(ctx_), col_ ? (uint32_t)col_->n_colors : 0u);
+            for (uint32_t c = 0; c < nc; ++c) {
+                uint64_t n_c = 0;
+                const int cs = pf_call_model_color_select(ctx_, (int)c, &n_c);
+                if (cs != PF_OK) return model_fail(cs, pf_last_error(ctx_));
+                if (n_c == PF_MODEL_NO_ROW) { color_none_.push_back((int)c); continue; }
+                // rows kept and no value behind them (cov: penta rows alone; fre: every frequency outside the model's test): nothing
+                // to fit, and no reason to keep the colours above it from their fits
+                if (n_c == 0) { color_empty_.push_back((int)c); continue; }
+                ColorFit cf;
+                cf.color = (int)c;
+                cf.values.resize((size_t)n_c);
+                if (n_c && pf_gmm_values(ctx_, cf.values.data(), n_c) != PF_OK) return model_fail(PF_ERR_HIP, pf_last_error(ctx_));
+                if (fit(n_c, outdir_ + "/" + outpre + "_color" + std::to_string(c), cf.fits, cf.ploidy, merr)) return model_fail(PF_ERR_ARG, merr);
+                color_fits_.push_back(std::move(cf));
+            }
+            if (color_fits_.empty()) return model_fail(PF_ERR_ARG, std::string(tag_) + "::PloidyEstimation(): no colour holds a value for the model");
+            tp("models fitted, colour by colour");
+        } else {
+            if (fit(n_values, outdir_ + "/" + outpre, model_fits_, model_ploidy_, merr)) return model_fail(PF_ERR_ARG, merr);
+            std::ostringstream line;
+            line << "estimated ploidy level is : " << model_ploidy_;
+            model_last_line_ = line.str();
+            tp("model fitted");
+        }
     }
     times_.ploidy_total_s = since(t_all);
     if (!quiet_) {

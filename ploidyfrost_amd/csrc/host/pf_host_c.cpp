@@ -590,6 +590,11 @@ int pfh_set_model(pfh_run *r, int source, double min_frequency, int lo, int hi, 
 }
 uint64_t pfh_model_values(pfh_run *r, double *out, uint64_t cap) {
     const uint64_t n = r->cdbg->model_count();
+    if (r->cdbg->model_was_each_color()) {   // the last pass was split by colour: the device array is the last colour's by now; the pooled one was copied
+        const std::vector<double> &v = r->cdbg->model_pooled_values();
+        if (out) std::copy(v.begin(), v.begin() + (size_t)std::min<uint64_t>(cap, v.size()), out);
+        return v.size();
+    }
     if (out && cap && n && pf_gmm_values(r->cdbg->device(), out, cap) != PF_OK) return 0;
     return n;
 }
@@ -660,18 +665,25 @@ int pfh_set_filter(pfh_run *r, const pf_filter_opts *opts) {
 
 // the filtered collection's steps on the host, in its order: every row of the four tables read (what the filter refuses while it
 // reads comes first), R's error when no table keeps a row, then what the model says of the kept rows, then the array
-int pfh_filter_rows(int source, double min_frequency, const pf_filter_opts *o, const char *const *text, const uint64_t *len, double *out,
-                    uint64_t cap, uint64_t *n, char *err, uint64_t err_cap) {
-    if ((source != pf::MODEL_COV && source != pf::MODEL_FRE) || !o || !text || !len || !n) return 1;
+}  // extern "C"
+
+template <typename Opts>
+static pf::FilterRule filter_rule_of(const Opts *o) {
+    pf::FilterRule f = {};
+    f.simple = o->simple != 0; f.indel = o->indel != 0; f.snp = o->snp != 0;
+    f.low = (double)o->low; f.up = (double)o->up; f.num = (double)o->num; f.distance = (double)o->distance; f.size = (double)o->size;
+    f.fq = o->frequency;
+    return f;
+}
+
+static int filter_rows_by_rule(int source, double min_frequency, const pf::FilterRule &f, const char *const *text, const uint64_t *len, double *out,
+                               uint64_t cap, uint64_t *n, char *err, uint64_t err_cap) {
+    if ((source != pf::MODEL_COV && source != pf::MODEL_FRE) || !text || !len || !n) return 1;
     auto say = [&](const std::string &m) {
         if (err && err_cap) { strncpy(err, m.c_str(), err_cap - 1); err[err_cap - 1] = 0; }
         return 1;
     };
-    if (!(o->frequency <= 0.5)) return say("frequency should < 0.5 ");
-    pf::FilterRule f;
-    f.simple = o->simple != 0; f.indel = o->indel != 0; f.snp = o->snp != 0;
-    f.low = (double)o->low; f.up = (double)o->up; f.num = (double)o->num; f.distance = (double)o->distance; f.size = (double)o->size;
-    f.fq = o->frequency;
+    if (!(f.fq <= 0.5)) return say("frequency should < 0.5 ");
     std::vector<double> col[pf::FILTER_COLUMNS];
     bool kept_any = false;
     std::string late;
@@ -697,8 +709,8 @@ int pfh_filter_rows(int source, double min_frequency, const pf_filter_opts *o, c
             }
             kept_any = kept_any || kept;
             if (code != pf::MODEL_ROW_OK) {
-                if (!pf::filter_err_is_late(code)) return say(pf::filter_error_text(code, t, row + 1));
-                if (late.empty()) late = pf::filter_error_text(code, t, row + 1);
+                if (!pf::filter_err_is_late(code)) return say(pf::filter_error_text(code, t, row + 1, f.multi != 0));
+                if (late.empty()) late = pf::filter_error_text(code, t, row + 1, f.multi != 0);
             }
             start = end + 1;
         }
@@ -722,6 +734,68 @@ int pfh_filter_rows(int source, double min_frequency, const pf_filter_opts *o, c
     }
     *n = count;
     return 0;
+}
+
+extern "C" {
+
+int pfh_filter_rows(int source, double min_frequency, const pf_filter_opts *o, const char *const *text, const uint64_t *len, double *out,
+                    uint64_t cap, uint64_t *n, char *err, uint64_t err_cap) {
+    if (!o) return 1;
+    return filter_rows_by_rule(source, min_frequency, filter_rule_of(o), text, len, out, cap, n, err, err_cap);
+}
+
+// ---- the multi form: the colored tables behind filter-multi's predicates ----
+int pfh_filter_rows_multi(int source, double min_frequency, const pf_filter_multi_opts *o, const char *const *text, const uint64_t *len,
+                          double *out, uint64_t cap, uint64_t *n, char *err, uint64_t err_cap) {
+    if (!o) return 1;
+    pf::FilterRule f = filter_rule_of(o);
+    f.multi = 1;
+    f.cramer = o->cramer;
+    f.color = o->color >= 0 ? (double)o->color : -1.0;
+    return filter_rows_by_rule(source, min_frequency, f, text, len, out, cap, n, err, err_cap);
+}
+
+int pfh_set_filter_multi(pfh_run *r, const pf_filter_multi_opts *opts, int each_color) {
+    return guarded(r, [&] { return r->cdbg->set_filter_multi(opts, each_color != 0); });
+}
+
+static const pfh::CDBG::ColorFit *color_fit_of(const pfh_run *r, int color) {
+    for (const pfh::CDBG::ColorFit &cf : r->cdbg->model_color_fits())
+        if (cf.color == color) return &cf;
+    return nullptr;
+}
+uint32_t pfh_model_color_count(const pfh_run *r) { return (uint32_t)r->cdbg->model_color_fits().size(); }
+int pfh_model_color_at(const pfh_run *r, uint32_t i) {
+    const auto &v = r->cdbg->model_color_fits();
+    return i < v.size() ? v[i].color : -1;
+}
+uint64_t pfh_model_color_values(const pfh_run *r, int color, double *out, uint64_t cap) {
+    const pfh::CDBG::ColorFit *cf = color_fit_of(r, color);
+    if (!cf) return ~0ull;
+    if (out) std::copy(cf->values.begin(), cf->values.begin() + (size_t)std::min<uint64_t>(cap, cf->values.size()), out);
+    return cf->values.size();
+}
+int pfh_model_color_fit(const pfh_run *r, int color, uint32_t gauss, double *weights, double *means, double *vars, double *loglik, double *aic,
+                        uint32_t *iterations) {
+    const pfh::CDBG::ColorFit *cf = color_fit_of(r, color);
+    if (!cf) return 1;
+    for (const pfh::GmmModel::Fit &f : cf->fits) {
+        if (f.gauss != gauss) continue;
+        for (uint32_t i = 0; i < gauss; ++i) {
+            if (weights) weights[i] = f.weights[i];
+            if (means) means[i] = f.means[i];
+            if (vars) vars[i] = f.vars[i];
+        }
+        if (loglik) *loglik = f.loglik;
+        if (aic) *aic = f.aic;
+        if (iterations) *iterations = f.iterations;
+        return 0;
+    }
+    return 1;
+}
+double pfh_model_color_ploidy(const pfh_run *r, int color) {
+    const pfh::CDBG::ColorFit *cf = color_fit_of(r, color);
+    return cf ? cf->ploidy : 0;
 }
 
 uint64_t pfh_bifrost_kmer_hash(uint64_t left_aligned_kmer, uint64_t seed) { return pfh::bifrost_kmer_hash(left_aligned_kmer, seed); }

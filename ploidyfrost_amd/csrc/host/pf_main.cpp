@@ -69,7 +69,12 @@ void PrintUsage() {
          << "  --model-ploidy LO:HI  Gaussians to fit, ploidy - 1 (default 1:9; `model -l / -u`)" << endl
          << "  --model-q Q     minimum allele frequency (default 0; `model -q`)" << endl
          << "  --model-m M, --model-n N, --model-iter K, --model-delta A   `model -m / -n / -k / -a` (defaults 5, 2, 1000, 0.01)" << endl
-         << "  --model-only    write <prefix>_model_result.txt but none of the ten calling files; their text never leaves the device" << endl << endl
+         << "  --model-only    write <prefix>_model_result.txt but none of the ten calling files; their text never leaves the device" << endl
+         << "  --filter \"OPTS\"  with --model: the rows through `ploidyfrost filter OPTS` (-S -l -u -I -P -n -d -s -q) first, on the device" << endl
+         << "  --filter-multi \"OPTS\"  with -f and --model: the colored rows through `ploidyfrost filter-multi OPTS` (-S -l -u -I -P -n -d -s -q" << endl
+         << "                  -c -v) first, on the device; the estimate of that filter and `model` in one command, no filtered table written" << endl
+         << "  --model-each-color  with --filter-multi (without -c): one estimate per colour, <prefix>_color<c>_model_result.txt each, as" << endl
+         << "                  --filter-multi \"OPTS -c c\" gives them one run at a time" << endl << endl
          << "Usage: PloidyFrost cutoffL kmer_histogram_file" << endl
          << "Usage: PloidyFrost cutoffU kmer_histogram_file (quantile[<1 ,default:0.998])" << endl << endl
          << "Usage: PloidyFrost model ...          (GMM ploidy inference from the coverage / frequency files; `PloidyFrost model` prints its options)" << endl
@@ -123,8 +128,9 @@ struct Options {
     double match = 2, mismatch = -1, gap = -3, frequency = 0.998;
     // --model ...: the estimate in the same run
     string model_source, model_ploidy = "1:9";
-    bool model_only = false, model_option_seen = false, filter_seen = false;
+    bool model_only = false, model_option_seen = false, filter_seen = false, multi_seen = false, each_color = false;
     string filter_words;   // --filter "<options of `ploidyfrost filter`>"
+    string multi_words;    // --filter-multi "<options of `ploidyfrost filter-multi`>"
     double model_q = 0, model_m = 5.0, model_n = 2.0, model_delta = 0.01;
     int model_iter = 1000;
 };
@@ -164,6 +170,36 @@ bool parse_filter_words(const string &words, pf_filter_opts &out) {
     return true;
 }
 
+// --filter-multi "<opts>": the same through the option table of `ploidyfrost filter-multi`
+bool parse_filter_multi_words(const string &words, pf_filter_multi_opts &out) {
+    std::istringstream in(words);
+    vector<string> args;
+    for (string w; in >> w;) args.push_back(w);
+    pfh::FilterOptions o;
+    o.multi = true;
+    string err, seen;
+    const int ps = pfh::parse_filter_options(args, true, o, err, &seen);
+    if (ps == 2) { cerr << "Error: --filter-multi takes the options of `ploidyfrost filter-multi` (-S -l -u -I -P -n -d -s -q -c -v), not -h" << endl; return false; }
+    if (ps) { cerr << err << " in --filter-multi" << endl; return false; }
+    for (char c : seen)
+        if (c == 'i' || c == 'o') {
+            cerr << "Error: --filter-multi: -" << c << " has no meaning here (the filter reads this run's own streams and writes no table)" << endl;
+            return false;
+        }
+    if (o.frequency > 0.5) { cerr << "Error: --filter-multi: -q " << o.frequency << ": frequency should < 0.5" << endl; return false; }
+    out.simple = o.simple; out.indel = o.indel; out.snp = o.snp;
+    out.low = o.low; out.up = o.up; out.num = o.num; out.distance = o.distance; out.size = o.size;
+    out.frequency = o.frequency;
+    out.color = o.color;
+    out.cramer = o.cramer;
+    return true;
+}
+bool refuse_each_color_with_one(const pf_filter_multi_opts &m) {
+    if (m.color < 0) return false;
+    cerr << "Error: --model-each-color fits every colour: --filter-multi holds -c " << m.color << " (one colour: leave --model-each-color out)" << endl;
+    return true;
+}
+
 void PrintModelUsage() {  // src/Main.cpp:694-718
     cout << "Usage: PloidyFrost model" << endl
          << "GMM model" << endl
@@ -179,6 +215,8 @@ void PrintModelUsage() {  // src/Main.cpp:694-718
          << "  -o,             Output prefix" << endl
          << "  --filter \"OPTS\" with -f: the rows of the (unfiltered) coverage files through `ploidyfrost filter OPTS` first, on the device;" << endl
          << "                  add --source fre for the filtered frequencies (as `model -g <filtered>_allele_frequency.txt`)" << endl
+         << "  --filter-multi \"OPTS\" with -f: the same for the coverage files of a colored run through `ploidyfrost filter-multi OPTS`;" << endl
+         << "                  --model-each-color: one result per colour, <out>_color<c>_model_result.txt" << endl
          << endl;
 }
 
@@ -188,12 +226,21 @@ int model_main(int argc, char **argv) {
     int lower = 1, upper = 9, iters = 1000;
     double frequency = 0, delta = 0.01, mthreshold = 5.0, nthreshold = 2.0;
     // --filter "<opts>" [--source cov|fre] (this build's own switches, taken out of argv before getopt sees them)
-    bool filtered = false;
+    bool filtered = false, multi = false, each_color = false;
     string filter_words, filter_source = "cov";
     for (int i = 2; i < argc; ++i) {
-        const bool is_filter = strcmp(argv[i], "--filter") == 0;
-        if ((is_filter || strcmp(argv[i], "--source") == 0) && i + 1 < argc) {
-            if (is_filter) { filtered = true; filter_words = argv[i + 1]; }
+        const bool is_filter = strcmp(argv[i], "--filter") == 0, is_multi = strcmp(argv[i], "--filter-multi") == 0;
+        if (strcmp(argv[i], "--model-each-color") == 0) {
+            each_color = true;
+            for (int j = i; j + 1 <= argc; ++j) argv[j] = j + 1 < argc ? argv[j + 1] : nullptr;
+            argc -= 1;
+            --i;
+        } else
+        if ((is_filter || is_multi || strcmp(argv[i], "--source") == 0) && i + 1 < argc) {
+            if (is_filter || is_multi) {
+                if (filtered) { cerr << "Error: --filter and --filter-multi do not go together (one table layout a run)" << endl; return 1; }
+                filtered = true; multi = is_multi; filter_words = argv[i + 1];
+            }
             else filter_source = argv[i + 1];
             for (int j = i; j + 2 <= argc; ++j) argv[j] = j + 2 < argc ? argv[j + 2] : nullptr;
             argc -= 2;
@@ -201,7 +248,10 @@ int model_main(int argc, char **argv) {
         }
     }
     pf_filter_opts fopts = {};
-    if (filtered && !parse_filter_words(filter_words, fopts)) return 1;
+    pf_filter_multi_opts mopts = {};
+    if (each_color && !multi) { cerr << "Error: --model-each-color needs --filter-multi \"OPTS\" (the colour is a column of the colored tables)" << endl; return 1; }
+    if (filtered && !(multi ? parse_filter_multi_words(filter_words, mopts) : parse_filter_words(filter_words, fopts))) return 1;
+    if (each_color && refuse_each_color_with_one(mopts)) return 1;
     if (filtered && filter_source != "cov" && filter_source != "fre") { cerr << "Error: --source " << filter_source << ": cov or fre" << endl; return 1; }
     int oc;
     while ((oc = getopt(argc, argv, "M:D:G:z:a:l:q:u:e:C:R:o:t:g:f:k:d:m:n:h:ibvpNSc")) != -1) {
@@ -250,7 +300,7 @@ int model_main(int argc, char **argv) {
             exit(EXIT_FAILURE);
         };
         if (pf_create(0, &ctx) != PF_OK) leave(string("GmmModel: no device context (") + (pf_last_error(nullptr) ? pf_last_error(nullptr) : "?") + "); the fit runs on the GPU only");
-        if (pf_call_model_begin(ctx, filter_source == "cov" ? PF_MODEL_COV : PF_MODEL_FRE, frequency) != PF_OK || pf_call_model_filter(ctx, &fopts) != PF_OK) leave(pf_last_error(ctx));
+        if (pf_call_model_begin(ctx, filter_source == "cov" ? PF_MODEL_COV : PF_MODEL_FRE, frequency) != PF_OK || (multi ? pf_call_model_filter_multi(ctx, &mopts, each_color ? 1 : 0) : pf_call_model_filter(ctx, &fopts)) != PF_OK) leave(pf_last_error(ctx));
         int ord = 0;
         for (const char *suf : {"_bicov.txt", "_tricov.txt", "_tetracov.txt", "_pentacov.txt"}) {
             ifstream in(colorfile + suf, std::ios::binary);
@@ -269,6 +319,32 @@ int model_main(int argc, char **argv) {
         }
         uint64_t n_values = 0;
         if (pf_call_model_finish(ctx, &n_values) != PF_OK) leave(pf_last_error(ctx));
+        if (each_color) {   // one result per colour that kept a row, in colour order
+            // (colours above the largest one that kept a row are not known here -- the tables do not say how many there are -- so
+            // they get no line; the run with -f <colors file> names every colour of the graph)
+            const uint32_t nc = pf_call_model_color_count(ctx);
+            uint32_t fitted = 0;
+            for (uint32_t c = 0; c < nc; ++c) {
+                uint64_t n_c = 0;
+                if (pf_call_model_color_select(ctx, (int)c, &n_c) != PF_OK) leave(pf_last_error(ctx));
+                if (n_c == PF_MODEL_NO_ROW) { cerr << "color " << c << ": no row kept, no estimate" << endl; continue; }
+                if (n_c == 0) { cerr << "color " << c << ": the rows kept hold no value for the model, no estimate" << endl; continue; }
+                pfh::GmmModel cm;
+                cm.setMThreshold(mthreshold);
+                cm.setNThreshold(nthreshold);
+                cm.setMaxIterNum(iters);
+                cm.setMaxDeltaNum(delta);
+                cm.borrow(ctx, (size_t)n_c);
+                string cerr_;
+                double ploidy = 0;
+                if (pfh::run_model(cm, lower, upper, outprefix + "_color" + to_string(c), cerr_, &ploidy)) leave(cerr_);
+                cout << "color " << c << ": estimated ploidy level is : " << ploidy << endl;
+                ++fitted;
+            }
+            pf_destroy(ctx);
+            if (!fitted) { cout << "model --model-each-color: no colour holds a value for the model" << endl; return EXIT_FAILURE; }
+            return 0;
+        }
         model.borrow(ctx, (size_t)n_values);
     } else
     if (!colorfile.empty() ? model.readCovFile(colorfile, frequency) : model.readFreFile(graphfile, frequency)) {
@@ -329,6 +405,17 @@ int main(int argc, char **argv) {
             for (int j = i; j + 1 <= argc; ++j) argv[j] = j + 1 < argc ? argv[j + 1] : nullptr;
             argc -= 1;
             --i;
+        } else if (strcmp(argv[i], "--model-each-color") == 0) {
+            opt.each_color = true;
+            for (int j = i; j + 1 <= argc; ++j) argv[j] = j + 1 < argc ? argv[j + 1] : nullptr;
+            argc -= 1;
+            --i;
+        } else if (strcmp(argv[i], "--filter-multi") == 0 && i + 1 < argc) {
+            opt.multi_seen = true;
+            opt.multi_words = argv[i + 1];
+            for (int j = i; j + 2 <= argc; ++j) argv[j] = j + 2 < argc ? argv[j + 2] : nullptr;
+            argc -= 2;
+            --i;
         } else if (strcmp(argv[i], "--filter") == 0 && i + 1 < argc) {
             opt.filter_seen = true;
             opt.filter_words = argv[i + 1];
@@ -383,14 +470,27 @@ int main(int argc, char **argv) {
     pf_filter_opts filter = {};
     if (opt.filter_seen) {
         if (opt.model_source.empty()) { cerr << "Error: --filter stands in front of the model of the same run: it needs --model cov|fre (the filtered tables themselves: `ploidyfrost filter`)" << endl; return 1; }
-        if (!opt.colorfile.empty()) { cerr << "Error: --filter reads the single-sample result streams; with -f the coverage tables have other columns (filter-multi)" << endl; return 1; }
+        if (!opt.colorfile.empty()) { cerr << "Error: --filter reads the single-sample result streams; with -f the coverage tables have other columns (the colored path has --filter-multi)" << endl; return 1; }
         if (opt.gpus > 1) { cerr << "Error: --filter and --gpus " << opt.gpus << " do not go together (each rank holds a slice of the rows)" << endl; return 1; }
         if (!parse_filter_words(opt.filter_words, filter)) return 1;
+    }
+    pf_filter_multi_opts multi = {};
+    if (opt.each_color && !opt.multi_seen) { cerr << "Error: --model-each-color needs --filter-multi \"OPTS\" (the colour is a column of the colored tables)" << endl; return 1; }
+    if (opt.multi_seen) {
+        if (opt.filter_seen) { cerr << "Error: --filter-multi and --filter do not go together (one table layout a run)" << endl; return 1; }
+        if (opt.model_source.empty()) { cerr << "Error: --filter-multi stands in front of the model of the same run: it needs --model cov|fre (the filtered tables themselves: `ploidyfrost filter-multi`)" << endl; return 1; }
+        if (opt.gpus > 1) { cerr << "Error: --filter-multi and --gpus " << opt.gpus << " do not go together (the colored path runs on one GPU)" << endl; return 1; }
+        if (opt.colorfile.empty()) { cerr << "Error: --filter-multi reads the colored result streams: it needs -f (the single-sample path has --filter)" << endl; return 1; }
+        if (!parse_filter_multi_words(opt.multi_words, multi)) return 1;
+        if (opt.each_color && refuse_each_color_with_one(multi)) return 1;
     }
     if (opt.model_option_seen) {
         if (opt.model_source.empty()) { cerr << "Error: the --model-... options need --model cov|fre" << endl; return 1; }
         if (opt.model_source != "cov" && opt.model_source != "fre") { cerr << "Error: --model " << opt.model_source << ": the source is cov or fre" << endl; return 1; }
-        if (!opt.colorfile.empty()) { cerr << "Error: --model reads the single-sample result streams; with -f the coverage tables have other columns" << endl; return 1; }
+        if (!opt.colorfile.empty() && !opt.multi_seen) {
+            cerr << "Error: --model reads the single-sample result streams; with -f the coverage tables have other columns and pool every sample: put --filter-multi \"OPTS\" in front of it" << endl;
+            return 1;
+        }
         if (opt.gpus > 1) { cerr << "Error: --model and --gpus " << opt.gpus << " do not go together (each rank holds a slice of the values)" << endl; return 1; }
         int lo = 0, hi = 0;
         char tail = 0;
@@ -512,6 +612,8 @@ int main(int argc, char **argv) {
         if (!g.good()) die();
         g.set_threads((unsigned)opt.nb_threads);
         g.set_overlap_output(true);
+        if (model.on && g.set_model(model)) die();
+        if (opt.multi_seen && g.set_filter_multi(&multi, opt.each_color)) die();
         if (g.setUnitigId(opt.outprefix, opt.graphfile, opt.nb_threads)) die();
         if (opt.info && g.printInfo(opt.verbose, opt.outprefix)) die();
         if (g.findSuperBubble_multithread_ptr(opt.outprefix, opt.nb_threads)) die();
@@ -520,6 +622,11 @@ int main(int argc, char **argv) {
             cout << "CCDBG:: Maximum Coverage:" << opt.coverage_vec[i].second << endl;
         }
         if (g.ploidyEstimation_multithread_ptr(opt.outprefix, opt.coverage_vec, opt.nb_threads)) die();
+        if (model.on && opt.each_color) {
+            for (int c : g.model_colors_without_rows()) cerr << "color " << c << ": no row kept, no estimate" << endl;
+            for (int c : g.model_colors_without_values()) cerr << "color " << c << ": the rows kept hold no value for the model, no estimate" << endl;
+            for (const pfh::CDBG::ColorFit &cf : g.model_color_fits()) cout << "color " << cf.color << ": estimated ploidy level is : " << cf.ploidy << endl;
+        } else if (model.on) cout << g.model_last_line() << endl;
         if (opt.verbose) {
             const pfh::PhaseTimes &t = g.times();
             printf("[device] candidates %llu  bfs %.3fs replay %.3fs | cov %.3fs tasks %.3fs (%llu) align %.3fs (%llu jobs) "

@@ -200,11 +200,20 @@ struct CallState {
         bool filter = false, taken = false;                     // pf_call_model_filter; a piece was taken since begin
         pf::FilterRule rule = {};
         DevBuf cflag, coff, upload, tokens;                     // with a filter, fre: a piece's column flags and their scan; take_text's piece; finish
+        // split by colour (pf_call_model_filter_multi with each_color): a colour key beside every value, the keys of the pooled
+        // tokens at finish, one colour's tokens; what finish left for pf_call_model_color_select
+        bool each = false, each_done = false;
+        DevBuf keys[14], tkeys, ctok;
+        uint64_t pooled_n = 0;
+        uint32_t color_count = 0;
+        uint8_t color_kept[1024] = {};
         hipEvent_t read_ev[PF_CALL_SLABS] = {};                 // the kernels over a slab's piece have read it
     } model;
     void release_all() {
-        for (DevBuf *b : {&model.state, &model.flags, &model.ends, &model.nvals, &model.voff, &model.n_rows, &model.scan, &model.cflag, &model.coff, &model.upload, &model.tokens}) b->release();
+        for (DevBuf *b : {&model.state, &model.flags, &model.ends, &model.nvals, &model.voff, &model.n_rows, &model.scan, &model.cflag, &model.coff, &model.upload, &model.tokens, &model.tkeys, &model.ctok}) b->release();
         for (DevBuf &b : model.vals) b.release();
+        for (DevBuf &b : model.keys) b.release();
+        model.each_done = false;
         if (model.stream) { (void)hipStreamDestroy(model.stream); model.stream = nullptr; }
         for (hipEvent_t &e : model.read_ev)
             if (e) { (void)hipEventDestroy(e); e = nullptr; }

@@ -24,6 +24,12 @@
 //           k_filter_advance  the A column counts and the stream's row counter
 //         and at finish: the columns end to end (device-to-device copies), the last token once more (the file ends in a line
 //         feed), then the model's own test over all of them: k_model_keep_flags, select, k_model_gather.
+// With the multi rule (pf_call_model_filter_multi: the colored tables, `filter-multi`'s predicates) the same launches run with
+// FilterRule::multi set, for one colour or pooled.  Split by colour (each_color) the collection is the pooled one, and the write
+// passes store each value's colour (uint16_t) in a key buffer beside its value buffer -- no launch more per piece, no buffer that
+// grows with the number of colours.  finish lays the keys end to end as it lays the tokens; pf_call_model_color_select then takes
+// one colour's tokens out in order (k_color_flags, select, k_model_gather: fre_all of the chain run with -c c, element for
+// element), counts its last token twice, and runs the model's own test (k_model_keep_flags, select, k_model_gather).
 // Bytes per character of a piece (counts, not measurements): without a filter 1 + 1 flags, 4 ends, 4 + 8 counts and offsets;
 // fre with a filter adds 12 A for the column flags and their scan (A = 2 .. 5).
 #include "pf_call_kernels.hpp"
@@ -51,6 +57,7 @@ struct ModelDev {
     uint32_t kept_any;                      // with a filter: some row of some table was kept (every writer stores 1)
     double last;                            // fre: value of the last token read (kept or not)
     uint32_t have_last, ends_nl;            // ... there is one; the text so far ends in a line feed
+    uint8_t color_kept[FILTER_MAX_COLORS];  // split by colour: some row of this colour was kept (every writer stores 1)
 };
 
 constexpr int MODEL_BLOCK = 256;
@@ -83,6 +90,8 @@ struct ModelRowsArgs {
     const uint64_t *voff;       // [cap + 1], write pass
     double *dst;
     uint64_t dst_cap;           // values dst has room for
+    uint16_t *key;              // split by colour: [dst_cap] the colour of each value; else null
+    int each;                   // split by colour
     ModelDev *st;
 };
 
@@ -99,18 +108,28 @@ __global__ __launch_bounds__(MODEL_BLOCK) void k_model_rows(ModelRowsArgs a) {
         double v[4];
         int err = MODEL_ROW_OK;
         bool kept = false;
-        const int n = a.filter ? filter_cov_row(a.text + start, end - start, a.arity, a.rule, a.q, v, &kept, &err)
+        double colour = -1;
+        const int n = a.filter ? filter_cov_row(a.text + start, end - start, a.arity, a.rule, a.q, v, &kept, &err, &colour)
                     : a.arity  ? model_cov_row(a.text + start, end - start, a.arity, a.q, v, &err)
                                : model_fre_row(a.text + start, end - start, a.q, v, &err);
         if (!EMIT) {
             a.nvals[r] = (uint32_t)n;
             if (kept) a.st->kept_any = 1u;
+            if (kept && a.each) {
+                const int ck = filter_color_key(colour);
+                if (ck >= 0) a.st->color_kept[ck] = 1;
+                else if (err == MODEL_ROW_OK) err = MODEL_ROW_COLOR;
+            }
             if (err != MODEL_ROW_OK) atomicMin(&a.st->err_key, model_err_key(a.filter != 0, a.ord, a.st->rows[a.ord] + r, err));
             else if (!a.arity && r + 1 == n_rows) { a.st->last = v[0]; a.st->have_last = 1; }
         } else if (n) {
             const uint64_t at = a.st->count[a.ord] + a.voff[r];
             if (at + (uint64_t)n <= a.dst_cap) {
                 for (int i = 0; i < n; ++i) a.dst[at + i] = v[i];
+                if (a.key) {
+                    const int ck = filter_color_key(colour);
+                    for (int i = 0; i < n; ++i) a.key[at + i] = (uint16_t)(ck < 0 ? 0 : ck);   // (ck < 0: refused in the count pass)
+                }
             } else {   // (never with K-TEXT's rows: the host sizes dst from the bytes of the text)
                 atomicMin(&a.st->err_key, model_err_key(a.filter != 0, a.ord, a.st->rows[a.ord] + r, MODEL_ROW_NO_ROOM));
             }
@@ -137,6 +156,8 @@ struct FilterFreArgs {
     const uint64_t *coff;       // the same array scanned, write pass
     double *dst[5];
     uint64_t dst_cap[5];
+    uint16_t *key[5];           // split by colour: the colour of each value, beside dst[c]; else null
+    int each;
     ModelDev *st;
 };
 
@@ -147,14 +168,21 @@ __global__ __launch_bounds__(MODEL_BLOCK) void k_filter_fre(FilterFreArgs a) {
     const int base = filter_column_base(a.ord);
     for (uint64_t r = (uint64_t)blockIdx.x * MODEL_BLOCK + threadIdx.x; r <= a.cap; r += stride) {
         uint32_t mask = 0;
+        int ckey = 0;
         double v[5];
         if (r < n_rows) {
             const uint32_t start = r ? a.ends[r - 1] + 1 : 0, end = a.ends[r];
             int err = MODEL_ROW_OK;
             bool kept = false;
-            mask = filter_fre_row(a.text + start, end - start, a.arity, a.rule, v, &kept, &err);
+            double colour = -1;
+            mask = filter_fre_row(a.text + start, end - start, a.arity, a.rule, v, &kept, &err, &colour);
+            ckey = a.each && kept ? filter_color_key(colour) : 0;
             if (!EMIT) {
                 if (kept) a.st->kept_any = 1u;
+                if (kept && a.each) {
+                    if (ckey >= 0) a.st->color_kept[ckey] = 1;
+                    else if (err == MODEL_ROW_OK) err = MODEL_ROW_COLOR;
+                }
                 if (err != MODEL_ROW_OK) atomicMin(&a.st->err_key, model_err_key(true, a.ord, a.st->rows[a.ord] + r, err));
             }
         }
@@ -165,8 +193,10 @@ __global__ __launch_bounds__(MODEL_BLOCK) void k_filter_fre(FilterFreArgs a) {
             for (int c = 0; c < a.arity; ++c) {
                 if (!((mask >> c) & 1u)) continue;
                 const uint64_t at = a.st->count[base + c] + (a.coff[(uint64_t)c * cap1 + r] - a.coff[(uint64_t)c * cap1]);
-                if (at < a.dst_cap[c]) a.dst[c][at] = v[c];
-                else atomicMin(&a.st->err_key, model_err_key(true, a.ord, a.st->rows[a.ord] + r, MODEL_ROW_NO_ROOM));
+                if (at < a.dst_cap[c]) {
+                    a.dst[c][at] = v[c];
+                    if (a.key[c]) a.key[c][at] = (uint16_t)(ckey < 0 ? 0 : ckey);
+                } else atomicMin(&a.st->err_key, model_err_key(true, a.ord, a.st->rows[a.ord] + r, MODEL_ROW_NO_ROOM));
             }
         }
     }
@@ -189,6 +219,12 @@ __global__ __launch_bounds__(MODEL_BLOCK) void k_model_gather(const double *__re
     if (i < n) dst[i] = tok[ids[i]];
 }
 
+// split by colour: which of the pooled tokens are of one colour
+__global__ __launch_bounds__(MODEL_BLOCK) void k_color_flags(const uint16_t *__restrict__ key, uint64_t n, uint16_t colour, uint8_t *__restrict__ flags) {
+    const uint64_t i = (uint64_t)blockIdx.x * MODEL_BLOCK + threadIdx.x;
+    if (i < n) flags[i] = key[i] == colour ? 1 : 0;
+}
+
 // readFreFile's last turn: the read that runs into the end of a file ending in white space leaves `a` as it was
 __global__ void k_model_fre_last(ModelDev *st, double q, double *dst, uint64_t dst_cap) {
     if (blockIdx.x == 0 && threadIdx.x == 0 && st->have_last && st->ends_nl && model_fre_keep(st->last, q) && st->count[0] < dst_cap) dst[st->count[0]++] = st->last;
@@ -201,17 +237,31 @@ static const int kFilterStream[FILTER_TABLES] = {PF_OUT_BICOV, PF_OUT_TRICOV, PF
 // room for `want` values in vals[ord], keeping what is there (the copy runs on the collection's stream, behind the kernels that wrote it)
 static int model_grow(pf_ctx *ctx, CallState::ModelWork &M, int ord, uint64_t want) {
     DevBuf &b = M.vals[ord];
-    if (want * 8 <= b.cap && b.p) return PF_OK;
-    const size_t bytes = (size_t)std::max<uint64_t>(want * 8 + want * 2, 1u << 16);
-    void *np = nullptr;
-    PF_HIP(hipMalloc(&np, bytes));
-    if (b.p) {
-        PF_HIP(hipMemcpyAsync(np, b.p, b.cap, hipMemcpyDeviceToDevice, M.stream));
-        PF_HIP(hipStreamSynchronize(M.stream));
-        (void)hipFree(b.p);
+    if (want * 8 > b.cap || !b.p) {
+        const size_t bytes = (size_t)std::max<uint64_t>(want * 8 + want * 2, 1u << 16);
+        void *np = nullptr;
+        PF_HIP(hipMalloc(&np, bytes));
+        if (b.p) {
+            PF_HIP(hipMemcpyAsync(np, b.p, b.cap, hipMemcpyDeviceToDevice, M.stream));
+            PF_HIP(hipStreamSynchronize(M.stream));
+            (void)hipFree(b.p);
+        }
+        b.p = np;
+        b.cap = bytes;
     }
-    b.p = np;
-    b.cap = bytes;
+    // split by colour: a key of two bytes for every value the buffer has room for
+    DevBuf &k = M.keys[ord];
+    if (M.each && (k.cap < b.cap / 4 || !k.p)) {
+        void *nk = nullptr;
+        PF_HIP(hipMalloc(&nk, b.cap / 4));
+        if (k.p) {
+            PF_HIP(hipMemcpyAsync(nk, k.p, k.cap, hipMemcpyDeviceToDevice, M.stream));
+            PF_HIP(hipStreamSynchronize(M.stream));
+            (void)hipFree(k.p);
+        }
+        k.p = nk;
+        k.cap = b.cap / 4;
+    }
     return PF_OK;
 }
 
@@ -257,7 +307,9 @@ static int model_take_stream(pf_ctx *ctx, CallState::ModelWork &M, int ord, cons
         for (int c = 0; c < 5; ++c) {
             DevBuf &b = M.vals[filter_column_base(ord) + (c < arity ? c : 0)];
             f.dst[c] = b.as<double>(); f.dst_cap[c] = b.cap / 8;
+            f.key[c] = M.each ? M.keys[filter_column_base(ord) + (c < arity ? c : 0)].as<uint16_t>() : nullptr;
         }
+        f.each = M.each ? 1 : 0;
         k_filter_fre<false><<<grid, MODEL_BLOCK, 0, st>>>(f);
         PF_HIP(scan_exclusive_u32_u64(f.cflag, M.coff.as<uint64_t>(), (uint64_t)col_entries, M.scan.p, st));
         k_filter_fre<true><<<grid, MODEL_BLOCK, 0, st>>>(f);
@@ -270,6 +322,7 @@ static int model_take_stream(pf_ctx *ctx, CallState::ModelWork &M, int ord, cons
     a.arity = arity; a.ord = ord; a.filter = M.filter ? 1 : 0; a.rule = M.rule; a.q = M.q;
     a.nvals = M.nvals.as<uint32_t>(); a.voff = M.voff.as<uint64_t>();
     a.dst = arity <= 4 ? M.vals[ord].as<double>() : nullptr; a.dst_cap = arity <= 4 ? M.vals[ord].cap / 8 : 0; a.st = dst;
+    a.key = M.each && arity <= 4 ? M.keys[ord].as<uint16_t>() : nullptr; a.each = M.each ? 1 : 0;
     k_model_rows<false><<<grid, MODEL_BLOCK, 0, st>>>(a);
     PF_HIP(scan_exclusive_u32_u64(a.nvals, M.voff.as<uint64_t>(), (uint64_t)cap + 1, M.scan.p, st));
     if (arity <= 4) k_model_rows<true><<<grid, MODEL_BLOCK, 0, st>>>(a);   // (the penta rows of a filtered cov collection add no value)
@@ -283,7 +336,7 @@ static int model_finish_filtered(pf_ctx *ctx, CallState::ModelWork &M, const Mod
     hipStream_t st = M.stream;
     const bool late = h.err_key != ~0ull && ((h.err_key >> 60) & 1);
     if ((h.err_key != ~0ull && !late) || (late && h.kept_any)) {
-        pf::CtxErr{ctx} = filter_error_text((int)(h.err_key & 15), (int)(h.err_key >> 58) & 3, ((h.err_key >> 4) & ((1ull << 54) - 1)) + 1);
+        pf::CtxErr{ctx} = filter_error_text((int)(h.err_key & 15), (int)(h.err_key >> 58) & 3, ((h.err_key >> 4) & ((1ull << 54) - 1)) + 1, M.rule.multi != 0);
         return PF_ERR_ARG;
     }
     if (!h.kept_any) { pf::CtxErr{ctx} = filter_none_kept_text(); return PF_ERR_ARG; }
@@ -335,10 +388,91 @@ static int model_finish_filtered(pf_ctx *ctx, CallState::ModelWork &M, const Mod
         PF_HIP(hipStreamSynchronize(st));
         n = n_keep;
     }
+    if (M.each) {
+        // what pf_call_model_color_select reads: the pooled tokens (fre: before the model's test) and their keys, end to end
+        uint64_t nt = 0;
+        for (int c = 0; c < n_col; ++c) nt += h.count[c];
+        if (nt >= 0xFFFFFFF0ull) { pf::CtxErr{ctx} = "pf_call_model_finish: 2^32 values or more"; return PF_ERR_ARG; }
+        if (!M.tokens.ensure((size_t)(nt + 1) * 8) || !M.tkeys.ensure((size_t)(nt + 1) * 2)) { pf::CtxErr{ctx} = "pf_call_model_finish: out of device memory"; return PF_ERR_HIP; }
+        uint64_t at = 0;
+        for (int c = 0; c < n_col; ++c) {
+            if (h.count[c]) {
+                PF_HIP(hipMemcpyAsync(M.tokens.as<double>() + at, M.vals[c].p, (size_t)h.count[c] * 8, hipMemcpyDeviceToDevice, st));
+                PF_HIP(hipMemcpyAsync(M.tkeys.as<uint16_t>() + at, M.keys[c].p, (size_t)h.count[c] * 2, hipMemcpyDeviceToDevice, st));
+            }
+            at += h.count[c];
+        }
+        PF_HIP(hipStreamSynchronize(st));
+        M.pooled_n = nt;
+        M.color_count = 0;
+        for (int c = 0; c < FILTER_MAX_COLORS; ++c) {
+            M.color_kept[c] = h.color_kept[c];
+            if (h.color_kept[c]) M.color_count = (uint32_t)c + 1;
+        }
+        M.each_done = true;
+    }
     ctx->gmm_n = n;
     ctx->gmm_loaded = true;
     if (n_values) *n_values = n;
     return PF_OK;
+}
+
+// one colour's array out of the pooled tokens of a finished collection: a stable selection by key, then what finish does behind it
+static int model_color_select_steps(pf_ctx *ctx, CallState::ModelWork &M, int color, uint64_t *n_values) {
+    hipStream_t st = M.stream;
+    const uint64_t nt = M.pooled_n;
+    uint32_t n_c = 0, n_keep = 0;
+    const double *tok = M.tokens.as<double>();
+    if (nt) {
+        k_color_flags<<<(unsigned)((nt + MODEL_BLOCK - 1) / MODEL_BLOCK), MODEL_BLOCK, 0, st>>>(M.tkeys.as<uint16_t>(), nt, (uint16_t)color, M.flags.as<uint8_t>());
+        PF_HIP(select_flagged_u8(M.flags.as<uint8_t>(), M.ends.as<uint32_t>(), M.n_rows.as<uint32_t>(), nullptr, nt, M.scan.p, st));
+        PF_HIP(hipMemcpyAsync(&n_c, M.n_rows.p, 4, hipMemcpyDeviceToHost, st));
+        PF_HIP(hipStreamSynchronize(st));
+    }
+    if (n_c > nt) { pf::CtxErr{ctx} = "pf_call_model_color_select: more values of a colour than there are values"; return PF_ERR_ARG; }
+    uint64_t n = 0;
+    if (M.source == PF_MODEL_COV || n_c == 0) {
+        double *x = (double *)ctx_ws(ctx, WS_GMM_X, (size_t)n_c * 8);
+        if (!x) { pf::CtxErr{ctx} = "pf_call_model_color_select: out of device memory"; return PF_ERR_HIP; }
+        if (n_c) k_model_gather<<<(n_c + MODEL_BLOCK - 1) / MODEL_BLOCK, MODEL_BLOCK, 0, st>>>(tok, M.ends.as<uint32_t>(), n_c, x);
+        n = n_c;
+    } else {
+        // the colour's frequency file: its tokens, the last one twice, the model's own test
+        double *ct = M.ctok.as<double>();
+        const uint64_t nc1 = (uint64_t)n_c + 1;
+        k_model_gather<<<(n_c + MODEL_BLOCK - 1) / MODEL_BLOCK, MODEL_BLOCK, 0, st>>>(tok, M.ends.as<uint32_t>(), n_c, ct);
+        PF_HIP(hipMemcpyAsync(ct + n_c, ct + n_c - 1, 8, hipMemcpyDeviceToDevice, st));
+        k_model_keep_flags<<<(unsigned)((nc1 + MODEL_BLOCK - 1) / MODEL_BLOCK), MODEL_BLOCK, 0, st>>>(ct, nc1, M.q, M.flags.as<uint8_t>());
+        PF_HIP(select_flagged_u8(M.flags.as<uint8_t>(), M.ends.as<uint32_t>(), M.n_rows.as<uint32_t>(), nullptr, nc1, M.scan.p, st));
+        PF_HIP(hipMemcpyAsync(&n_keep, M.n_rows.p, 4, hipMemcpyDeviceToHost, st));
+        PF_HIP(hipStreamSynchronize(st));
+        if (n_keep > nc1) { pf::CtxErr{ctx} = "pf_call_model_color_select: more values kept than there are tokens"; return PF_ERR_ARG; }
+        double *x = (double *)ctx_ws(ctx, WS_GMM_X, (size_t)n_keep * 8);
+        if (!x) { pf::CtxErr{ctx} = "pf_call_model_color_select: out of device memory"; return PF_ERR_HIP; }
+        if (n_keep) k_model_gather<<<(n_keep + MODEL_BLOCK - 1) / MODEL_BLOCK, MODEL_BLOCK, 0, st>>>(ct, M.ends.as<uint32_t>(), n_keep, x);
+        n = n_keep;
+    }
+    PF_HIP(hipGetLastError());
+    PF_HIP(hipStreamSynchronize(st));
+    ctx->gmm_n = n;
+    ctx->gmm_loaded = true;
+    if (n_values) *n_values = n;
+    return PF_OK;
+}
+
+// the steps inside one timing record, which is closed however they end
+static int model_color_select(pf_ctx *ctx, CallState::ModelWork &M, int color, uint64_t *n_values) {
+    const uint64_t nt = M.pooled_n;
+    if (!M.flags.ensure((size_t)nt + 1) || !M.ends.ensure(((size_t)nt + 1) * 4) || !M.n_rows.ensure(16) || !M.scan.ensure(scan_scratch_bytes(nt + 1)) ||
+        !M.ctok.ensure(((size_t)nt + 1) * 8)) {
+        pf::CtxErr{ctx} = "pf_call_model_color_select: out of device memory";
+        return PF_ERR_HIP;
+    }
+    size_t tat = 0;
+    ctx_begin_at(ctx, PF_K_CALL_MODEL, M.stream, &tat);
+    const int rc = model_color_select_steps(ctx, M, color, n_values);
+    ctx_end_at(ctx, tat, M.stream);
+    return rc;
 }
 
 }  // namespace pf_call
@@ -349,7 +483,6 @@ int pf_call_model_begin(pf_ctx *ctx, int source, double q) {
     if (!ctx || (source != PF_MODEL_COV && source != PF_MODEL_FRE)) return PF_ERR_ARG;
     CallState *S = state_of(ctx);
     if (!S) return PF_ERR_HIP;
-    if (S->n_colors) { pf::CtxErr{ctx} = "pf_call_model_begin: the colored coverage tables have other columns (single-sample path only)"; return PF_ERR_ARG; }
     PF_HIP(hipSetDevice(ctx->device));
     CallState::ModelWork &M = S->model;
     if (!M.stream) PF_HIP(hipStreamCreateWithFlags(&M.stream, hipStreamNonBlocking));
@@ -363,6 +496,8 @@ int pf_call_model_begin(pf_ctx *ctx, int source, double q) {
     M.q = q;
     for (uint64_t &b : M.bound) b = 2;   // (the doubled last token)
     M.filter = M.taken = false;
+    M.each = M.each_done = false;
+    M.rule = {};
     M.active = true;
     ctx->gmm_loaded = false;
     ctx->gmm_n = 0;
@@ -374,12 +509,55 @@ int pf_call_model_filter(pf_ctx *ctx, const pf_filter_opts *o) {
     CallState::ModelWork &M = ctx->call->model;
     if (!M.active || M.taken) { pf::CtxErr{ctx} = "pf_call_model_filter: between pf_call_model_begin and the first piece"; return PF_ERR_ARG; }
     M.filter = o != nullptr;
+    M.each = false;
+    M.rule = {};
     if (!o) return PF_OK;
+    if (ctx->call->n_colors) { M.filter = false; pf::CtxErr{ctx} = "pf_call_model_filter: the colored coverage tables have other columns (single-sample path only; pf_call_model_filter_multi)"; return PF_ERR_ARG; }
     if (!(o->frequency <= 0.5)) { M.filter = false; pf::CtxErr{ctx} = "pf_call_model_filter: frequency should < 0.5"; return PF_ERR_ARG; }
     M.rule.simple = o->simple != 0; M.rule.indel = o->indel != 0; M.rule.snp = o->snp != 0;
     M.rule.low = (double)o->low; M.rule.up = (double)o->up; M.rule.num = (double)o->num; M.rule.distance = (double)o->distance; M.rule.size = (double)o->size;
     M.rule.fq = o->frequency;
     return PF_OK;
+}
+
+int pf_call_model_filter_multi(pf_ctx *ctx, const pf_filter_multi_opts *o, int each_color) {
+    if (!ctx || !ctx->call) return PF_ERR_ARG;
+    CallState::ModelWork &M = ctx->call->model;
+    if (!M.active || M.taken) { pf::CtxErr{ctx} = "pf_call_model_filter_multi: between pf_call_model_begin and the first piece"; return PF_ERR_ARG; }
+    M.filter = M.each = false;
+    M.rule = {};
+    if (!o) {
+        if (each_color) { pf::CtxErr{ctx} = "pf_call_model_filter_multi: the values are split by colour behind a filter only"; return PF_ERR_ARG; }
+        return PF_OK;
+    }
+    if (!(o->frequency <= 0.5)) { pf::CtxErr{ctx} = "pf_call_model_filter_multi: frequency should < 0.5"; return PF_ERR_ARG; }
+    if (each_color && o->color >= 0) { pf::CtxErr{ctx} = "pf_call_model_filter_multi: every colour at once goes with color = -1, not with one colour"; return PF_ERR_ARG; }
+    M.rule.simple = o->simple != 0; M.rule.indel = o->indel != 0; M.rule.snp = o->snp != 0;
+    M.rule.low = (double)o->low; M.rule.up = (double)o->up; M.rule.num = (double)o->num; M.rule.distance = (double)o->distance; M.rule.size = (double)o->size;
+    M.rule.fq = o->frequency;
+    M.rule.multi = 1;
+    M.rule.cramer = o->cramer;
+    M.rule.color = o->color >= 0 ? (double)o->color : -1.0;
+    M.filter = true;
+    M.each = each_color != 0;
+    return PF_OK;
+}
+
+uint32_t pf_call_model_color_count(const pf_ctx *ctx) {
+    return ctx && ctx->call && ctx->call->model.each_done ? ctx->call->model.color_count : 0;
+}
+
+int pf_call_model_color_select(pf_ctx *ctx, int color, uint64_t *n_values) {
+    if (!ctx || !ctx->call) return PF_ERR_ARG;
+    CallState::ModelWork &M = ctx->call->model;
+    if (!M.each_done || M.active) { pf::CtxErr{ctx} = "pf_call_model_color_select: behind the pf_call_model_finish of a collection split by colour"; return PF_ERR_ARG; }
+    if (color < 0 || color >= FILTER_MAX_COLORS) { pf::CtxErr{ctx} = "pf_call_model_color_select: colours are 0 .. PF_MAX_COLORS - 1"; return PF_ERR_ARG; }
+    if (!M.color_kept[color]) {
+        if (n_values) *n_values = PF_MODEL_NO_ROW;
+        return PF_OK;
+    }
+    PF_HIP(hipSetDevice(ctx->device));
+    return model_color_select(ctx, M, color, n_values);
 }
 
 int pf_call_model_take_text(pf_ctx *ctx, int stream_ord, const char *host_text, uint64_t len) {
@@ -409,6 +587,11 @@ int pf_call_model_take(pf_ctx *ctx, int slab) {
     CallState *S = ctx->call;
     CallState::ModelWork &M = S->model;
     if (!M.active) { pf::CtxErr{ctx} = "pf_call_model_take: no collection was begun (pf_call_model_begin)"; return PF_ERR_ARG; }
+    if ((S->n_colors != 0) != (M.filter && M.rule.multi)) {
+        pf::CtxErr{ctx} = S->n_colors ? "pf_call_model_take: the colored coverage tables have other columns: the collection needs pf_call_model_filter_multi"
+                                      : "pf_call_model_take: the multi filter reads the colored tables (single-sample path: pf_call_model_filter)";
+        return PF_ERR_ARG;
+    }
     PF_HIP(hipSetDevice(ctx->device));
     hipStream_t st = M.stream;
     if (S->text_ev[slab]) PF_HIP(hipStreamWaitEvent(st, S->text_ev[slab], 0));

@@ -3,6 +3,8 @@
 // _pentacov text.  One definition for both sides, in the manner of pf_model_rows.hpp: the kernels of pf_call_model.hip call them
 // with a lane per row, the host layer exports them (pfh_filter_rows) so that a CPU test holds the same code to the three-command
 // chain.  The host filter is the definition; its parity with R is unpinned and stays so.
+// The multi form (FilterRule::multi: `ploidyfrost filter-multi`, the opt.multi branch of run_filter) reads the rows of the colored
+// tables -- A coverages, colour, isStrict, VarType, VarId, VarNum, Cramer's V, VarDis -- with the same functions.
 #pragma once
 #include "pf_model_rows.hpp"
 #include <string>
@@ -14,7 +16,11 @@ struct FilterRule {
     int simple, indel, snp;
     double low, up, num, distance, size;
     double fq;   // -q: frequencies kept in (fq, 1 - fq)
+    // filter-multi: rows of A + 7 fields, Cramer's V > cramer (strictly), colour == color when color >= 0, no sum clause
+    int multi;
+    double cramer, color;
 };
+constexpr int FILTER_MAX_COLORS = 1024;   // colours a collection splits by (PF_MAX_COLORS)
 
 constexpr int FILTER_TABLES = 4;    // bi, tri, tetra, penta
 constexpr int FILTER_COLUMNS = 14;  // 2 + 3 + 4 + 5 frequency columns, table by table
@@ -82,10 +88,13 @@ PF_MODEL_HD inline uint64_t filter_scaled_round7(double x) {
 // One row of a *cov stream of A = 2 .. 5 alleles: read as read_table reads it (every cell, kept or not), then run_filter's
 // predicates (pf_filter.cpp:192-212) in fp64.  cov[A] = the coverages, sci = bit c set where R would print coverage c in
 // scientific notation.  Returns whether the row is kept; *err = MODEL_ROW_FIELDS / _BAD_TOKEN / _RANGE names what read_table refuses.
-PF_MODEL_HD inline bool filter_row(const char *s, uint32_t len, int A, const FilterRule &f, double *cov, uint32_t *sci, int *err) {
+// The multi form has the colour behind the coverages and Cramer's V in front of VarDis (A + 7 fields; Filter-multi.R:114-120 has no
+// clause on the sum of the first four coverages); *colour = the row's colour cell (single-sample rows: -1).
+PF_MODEL_HD inline bool filter_row(const char *s, uint32_t len, int A, const FilterRule &f, double *cov, uint32_t *sci, int *err, double *colour = nullptr) {
     *err = MODEL_ROW_OK;
     *sci = 0;
-    const int want = A + 5;
+    if (colour) *colour = -1;
+    const int want = A + (f.multi ? 7 : 5);
     int fields = 0;
     for (uint32_t i = 0; i < len;) {   // fields as `in >> token` cuts them: runs of anything but white space
         while (i < len && model_isspace(s[i])) ++i;
@@ -94,7 +103,7 @@ PF_MODEL_HD inline bool filter_row(const char *s, uint32_t len, int A, const Fil
         ++fields;
     }
     if (fields != want) { *err = MODEL_ROW_FIELDS; return false; }
-    double tail[5];   // isStrict VarType VarId VarNum VarDis
+    double tail[7];   // isStrict VarType VarId VarNum VarDis; multi: colour isStrict VarType VarId VarNum Cramer VarDis
     uint32_t i = 0;
     for (int c = 0; c < want; ++c) {
         while (i < len && model_isspace(s[i])) ++i;
@@ -113,7 +122,9 @@ PF_MODEL_HD inline bool filter_row(const char *s, uint32_t len, int A, const Fil
         } else tail[c - A] = v;
         i = t;
     }
-    const double strict = tail[0], type = tail[1], num = tail[3], dis = tail[4];
+    const int t0 = f.multi ? 1 : 0;
+    const double strict = tail[t0], type = tail[t0 + 1], num = tail[t0 + 3], dis = tail[f.multi ? 6 : 4];
+    if (f.multi && colour) *colour = tail[0];
     bool k = true;
     if (f.simple) k = k && strict == 1;
     if (f.indel) k = k && type == 0;
@@ -123,18 +134,22 @@ PF_MODEL_HD inline bool filter_row(const char *s, uint32_t len, int A, const Fil
         k = k && cov[c] > f.low && cov[c] < f.up;
         if (c < 4) first4 += cov[c];
     }
-    if (A >= 4) k = k && first4 < f.up;   // the penta row's fifth coverage is not in the sum
+    if (!f.multi && A >= 4) k = k && first4 < f.up;   // the penta row's fifth coverage is not in the sum
     k = k && num < f.num && dis > f.distance && type < f.size;
+    if (f.multi) {
+        k = k && tail[5] > f.cramer;
+        if (f.color >= 0) k = k && tail[0] == f.color;
+    }
     return k;
 }
 
 // source cov: what `model -f` makes of the row the filter wrote -- R's rendering of each coverage through atoi, then the rest of
 // model_cov_row.  The penta table is written and never read.  A kept coverage R prints in scientific notation is refused
 // (MODEL_ROW_R_SCI): atoi would read its leading digit, and which rendering a tri / tetra column gets depends on the whole column.
-PF_MODEL_HD inline int filter_cov_row(const char *s, uint32_t len, int A, const FilterRule &f, double q, double *out, bool *kept, int *err) {
+PF_MODEL_HD inline int filter_cov_row(const char *s, uint32_t len, int A, const FilterRule &f, double q, double *out, bool *kept, int *err, double *colour = nullptr) {
     double cov[5];
     uint32_t sci;
-    *kept = filter_row(s, len, A, f, cov, &sci, err);
+    *kept = filter_row(s, len, A, f, cov, &sci, err, colour);
     if (!*kept || A > 4) return 0;
     if (sci) { *err = MODEL_ROW_R_SCI; return 0; }
     int ci[4];
@@ -145,13 +160,13 @@ PF_MODEL_HD inline int filter_cov_row(const char *s, uint32_t len, int A, const 
 // source fre: the tokens the row adds to the filter's <out>_allele_frequency.txt, as the model reads them back.  x_c = cov_c / sum
 // (sum left to right), written iff fq < x_c < 1 - fq on the unrounded value; out[c] = the written token's value.  Returns the mask
 // of written columns.  (The model's own test, model_fre_keep, comes behind: the file's last token counts twice whether kept or not.)
-PF_MODEL_HD inline uint32_t filter_fre_row(const char *s, uint32_t len, int A, const FilterRule &f, double *out, bool *kept, int *err) {
+PF_MODEL_HD inline uint32_t filter_fre_row(const char *s, uint32_t len, int A, const FilterRule &f, double *out, bool *kept, int *err, double *colour = nullptr) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
     double cov[5];
     uint32_t sci;
-    *kept = filter_row(s, len, A, f, cov, &sci, err);
+    *kept = filter_row(s, len, A, f, cov, &sci, err, colour);
     if (!*kept) return 0;
     double sum = 0;
     for (int c = 0; c < A; ++c) sum += cov[c];
@@ -164,6 +179,14 @@ PF_MODEL_HD inline uint32_t filter_fre_row(const char *s, uint32_t len, int A, c
         }
     }
     return mask;
+}
+
+// A collection that splits its values by colour keys each value with its row's colour: an integer 0 .. FILTER_MAX_COLORS - 1, or -1
+// for a cell that is none (a kept row with such a cell is refused: MODEL_ROW_COLOR)
+PF_MODEL_HD inline int filter_color_key(double colour) {
+    if (!(colour >= 0 && colour < (double)FILTER_MAX_COLORS)) return -1;
+    const int k = (int)colour;
+    return (double)k == colour ? k : -1;
 }
 
 // ---- the words for what a filtered collection refuses, one wording for the device path and pfh_filter_rows ----
@@ -179,11 +202,11 @@ inline const char *filter_stream_name(int table) {
 inline const char *filter_none_kept_text() {
     return "Error in round(fre_all[fre_all > opt$frequency & fre_all < (1 - opt$frequency)],  : \n  non-numeric argument to mathematical function";
 }
-inline std::string filter_error_text(int code, int table, unsigned long long row /* from 1 */) {
+inline std::string filter_error_text(int code, int table, unsigned long long row /* from 1 */, bool multi = false) {
     const std::string stream = std::string("stream ") + filter_stream_name(table), r = std::to_string(row);
     switch (code) {
         case MODEL_ROW_FIELDS:
-            return "Error in scan(file = file, what = what, sep = sep, quote = quote, dec = dec,  : \n  line " + r + " did not have " + std::to_string(table + 7) +
+            return "Error in scan(file = file, what = what, sep = sep, quote = quote, dec = dec,  : \n  line " + r + " did not have " + std::to_string(table + (multi ? 9 : 7)) +
                    " elements (" + stream + ")";
         case MODEL_ROW_BAD_TOKEN:
             return "pf_filter: a cell in line " + r + " of " + stream +
@@ -195,6 +218,9 @@ inline std::string filter_error_text(int code, int table, unsigned long long row
         case MODEL_ROW_R_SCI:
             return "ERROR: row " + r + " of " + stream + " is kept with a coverage that R's write.table prints in scientific notation (1e+05, 1e-04); `model -f` reads such a cell "
                    "by its leading digit -- not reproduced here: the three-command chain (ploidyfrost, filter, model -f) handles this input";
+        case MODEL_ROW_COLOR:
+            return "ERROR: row " + r + " of " + stream + " is kept with a colour that is no integer in 0 .. " + std::to_string(FILTER_MAX_COLORS - 1) +
+                   " (the values of a run are split by the colour column)";
         default:
             return "pf_call_model_finish: row " + r + " of " + stream + " has more values than its text allows";
     }

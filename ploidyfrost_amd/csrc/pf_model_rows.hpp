@@ -21,8 +21,9 @@ enum ModelRowErr : int {
     MODEL_ROW_RANGE = 3,       // a number outside what one fp64 operation converts exactly (more than 15 digits, |exponent| > 22)
     MODEL_ROW_NO_ROOM = 4,     // device only: the value array was sized for fewer values than the rows give
     // with a row filter in front (pf_filter_rows.hpp)
-    MODEL_ROW_FIELDS = 5,      // a coverage row that does not have its A + 5 fields
-    MODEL_ROW_R_SCI = 6        // a kept coverage R's write.table renders in scientific notation (`model -f` then reads its leading digit)
+    MODEL_ROW_FIELDS = 5,      // a coverage row that does not have its A + 5 fields (colored tables: A + 7)
+    MODEL_ROW_R_SCI = 6,       // a kept coverage R's write.table renders in scientific notation (`model -f` then reads its leading digit)
+    MODEL_ROW_COLOR = 7        // split by colour: a kept row whose colour cell is no integer 0 .. 1023
 };
 
 PF_MODEL_HD inline bool model_isspace(char c) { return c == ' ' || (c >= '\t' && c <= '\r'); }

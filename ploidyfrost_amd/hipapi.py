@@ -183,6 +183,9 @@ def load_library() -> C.CDLL:
         "pf_call_fetched_bytes": (u64, [vp]),
         "pf_call_model_filter": (i, [vp, vp]),
         "pf_call_model_take_text": (i, [vp, i, C.c_char_p, u64]),
+        "pf_call_model_filter_multi": (i, [vp, vp, i]),
+        "pf_call_model_color_count": (C.c_uint32, [vp]),
+        "pf_call_model_color_select": (i, [vp, i, C.POINTER(u64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError = header / library mismatch
@@ -202,7 +205,8 @@ DECLARED_SYMBOLS = ["pf_create", "pf_warmup", "pf_destroy", "pf_last_error", "pf
                     "pf_call_set_state", "pf_call_set_format", "pf_superbubble_rows", "pf_superbubble_fetch", "pf_call_coverage", "pf_call_scan", "pf_call_sides", "pf_call_resolve", "pf_call_select", "pf_call_run", "pf_call_align",
                     "pf_call_text", "pf_call_set_alignseq_packed", "pf_comm_unique_id", "pf_comm_init", "pf_gather", "pf_comm_destroy", "pf_call_reserve", "pf_call_reserve_lanes", "pf_timing_select", "pf_kernel_busy", "pf_call_reserve_text", "pf_selftest_scan", "pf_call_set_numeric_packed", "pf_call_fetch_text", "pf_find_reserve", "pf_call_set_colours", "pf_call_set_cutoffs", "pf_call_peek", "pf_call_text_range", "pf_call_align_lane", "pf_call_text_range_lane", "pf_call_text_sizes", "pf_call_fetch", "pf_call_fetch_slab", "pf_call_fetch_range", "pf_call_fetch_wait", "pf_format_doubles",
                     "pf_gmm_values", "pf_call_model_begin", "pf_call_model_take", "pf_call_model_finish", "pf_call_fetched_bytes",
-                    "pf_call_model_filter", "pf_call_model_take_text"]
+                    "pf_call_model_filter", "pf_call_model_take_text",
+                    "pf_call_model_filter_multi", "pf_call_model_color_count", "pf_call_model_color_select"]
 
 
 def call_peek(ctx_handle, lane: int = 0):

@@ -34,12 +34,18 @@ DECLARED_SYMBOLS = ["pfh_open", "pfh_close", "pfh_last_error", "pfh_set_output_d
                     "pfh_gmm_open", "pfh_gmm_close", "pfh_gmm_last_error", "pfh_gmm_read_fre", "pfh_gmm_read_cov", "pfh_gmm_set_values",
                     "pfh_gmm_size", "pfh_gmm_values", "pfh_gmm_fit", "pfh_gmm_run", "pfh_gmm_kernel_time",
                     "pfh_set_model", "pfh_model_values", "pfh_model_fit", "pfh_model_ploidy", "pfh_text_bytes_fetched", "pfh_model_rows",
-                    "pfh_set_filter", "pfh_filter_rows"]
+                    "pfh_set_filter", "pfh_filter_rows",
+                    "pfh_set_filter_multi", "pfh_filter_rows_multi", "pfh_model_color_count", "pfh_model_color_at", "pfh_model_color_values",
+                    "pfh_model_color_fit", "pfh_model_color_ploidy"]
 
 
 class FilterOpts(C.Structure):   # pf_filter_opts (include/ploidyfrost_hip.h)
     _fields_ = [("simple", C.c_int), ("indel", C.c_int), ("snp", C.c_int), ("low", C.c_longlong), ("up", C.c_longlong),
                 ("num", C.c_longlong), ("distance", C.c_longlong), ("size", C.c_longlong), ("frequency", C.c_double)]
+
+
+class FilterMultiOpts(C.Structure):   # pf_filter_multi_opts
+    _fields_ = FilterOpts._fields_ + [("color", C.c_longlong), ("cramer", C.c_double)]
 
 
 def load_library() -> C.CDLL:
@@ -150,6 +156,19 @@ def load_library() -> C.CDLL:
     L.pfh_set_filter.argtypes = [vp, C.POINTER(FilterOpts)]
     L.pfh_filter_rows.restype = C.c_int
     L.pfh_filter_rows.argtypes = [C.c_int, d, C.POINTER(FilterOpts), C.POINTER(C.c_char_p), C.POINTER(u64), vp, u64, C.POINTER(u64), C.c_char_p, u64]
+    L.pfh_set_filter_multi.restype = C.c_int
+    L.pfh_set_filter_multi.argtypes = [vp, C.POINTER(FilterMultiOpts), C.c_int]
+    L.pfh_filter_rows_multi.restype = C.c_int
+    L.pfh_filter_rows_multi.argtypes = [C.c_int, d, C.POINTER(FilterMultiOpts), C.POINTER(C.c_char_p), C.POINTER(u64), vp, u64, C.POINTER(u64), C.c_char_p, u64]
+    L.pfh_model_color_count.restype = u32
+    L.pfh_model_color_count.argtypes = [vp]
+    L.pfh_model_color_at.restype = C.c_int
+    L.pfh_model_color_at.argtypes = [vp, u32]
+    L.pfh_model_color_values.restype = u64
+    L.pfh_model_color_values.argtypes = [vp, C.c_int, vp, u64]
+    L.pfh_model_color_fit.argtypes = [vp, C.c_int, u32, vp, vp, vp, C.POINTER(d), C.POINTER(d), C.POINTER(u32)]
+    L.pfh_model_color_ploidy.restype = d
+    L.pfh_model_color_ploidy.argtypes = [vp, C.c_int]
     _lib = L
     return L
 
@@ -299,23 +318,31 @@ def filter_opts(simple=False, low=0, up=10000, indel=False, snp=False, num=10000
     return FilterOpts(int(simple), int(indel), int(snp), int(low), int(up), int(num), int(distance), int(size), float(frequency))
 
 
-def filter_rows(source: str, texts, q: float = 0.0, **opts) -> np.ndarray:
+def filter_multi_opts(color=-1, cramer=0.0, **opts) -> FilterMultiOpts:
+    """the options of `ploidyfrost filter-multi`: those of filter_opts plus -c colour (-1: all) and -v Cramer's V"""
+    o = filter_opts(**opts)
+    return FilterMultiOpts(*[getattr(o, n) for n, _ in FilterOpts._fields_], int(color), float(cramer))
+
+
+def filter_rows(source: str, texts, q: float = 0.0, multi: bool = False, **opts) -> np.ndarray:
     """The model's values behind a row filter, as the shared rule (csrc/pf_filter_rows.hpp, what the device kernels run) reads
     them from the bytes of (_bicov, _tricov, _tetracov, _pentacov): what `filter` with **opts (see filter_opts) followed by
     `model -f` (source "cov") / `model -g <filtered>_allele_frequency.txt` ("fre") with -q q reads.  No device.  RuntimeError
-    with the wording of the one-command run for what it refuses."""
+    with the wording of the one-command run for what it refuses.  multi=True: the tables of a colored run and `filter-multi`,
+    with color= (-1: all) and cramer= among the options."""
     L = load_library()
     texts = [bytes(t) for t in texts]
     if len(texts) != 4:
         raise ValueError("four texts: bi, tri, tetra, penta")
     ptrs = (C.c_char_p * 4)(*texts)
     lens = (C.c_uint64 * 4)(*[len(t) for t in texts])
-    o = filter_opts(**opts)
+    o = filter_multi_opts(**opts) if multi else filter_opts(**opts)
     n = C.c_uint64()
     err = C.create_string_buffer(1024)
     cap = sum(len(t) for t in texts) + 2
     out = np.zeros(cap, dtype=np.float64)
-    if L.pfh_filter_rows(MODEL_SOURCES[source], q, C.byref(o), ptrs, lens, out.ctypes.data, cap, C.byref(n), err, len(err)) != 0:
+    fn = L.pfh_filter_rows_multi if multi else L.pfh_filter_rows
+    if fn(MODEL_SOURCES[source], q, C.byref(o), ptrs, lens, out.ctypes.data, cap, C.byref(n), err, len(err)) != 0:
         raise RuntimeError(err.value.decode() or "pfh_filter_rows failed")
     return out[: n.value].copy()
 
@@ -542,6 +569,48 @@ class ColoredRun(Run):
         lo = (C.c_int * self.n_colors)(*[int(c[0]) for c in cutoffs])
         up = (C.c_int * self.n_colors)(*[int(c[1]) for c in cutoffs])
         self._check(self.L.pfh_ploidy_estimation_colored(self.h, outpre.encode(), lo, up, len(cutoffs)))
+
+    def set_filter_multi(self, color=-1, cramer=0.0, each_color=False, **opts):
+        """`ploidyfrost filter-multi`'s row predicates in front of the model of the same run (after set_model, which a colored run
+        accepts behind this filter only): the next ploidy_estimation fits what `filter-multi` with these options (those of
+        Run.set_filter plus color and cramer) followed by `model` would read from this run's files, and writes no filtered table.
+        each_color (with color=-1): one fit per colour that keeps a row, <outpre>_color<c>_model_result.txt each; model_values() is
+        then the pooled array.  set_filter_multi(None) takes the filter away again, as set_model(None) does."""
+        if color is None:
+            self._check(self.L.pfh_set_filter_multi(self.h, None, 0))
+            return
+        o = filter_multi_opts(color, cramer, **opts)
+        self._check(self.L.pfh_set_filter_multi(self.h, C.byref(o), int(each_color)))
+
+    def model_colors(self) -> list:
+        """the colours the last ploidy_estimation split by colour has a fit for, ascending"""
+        return [int(self.L.pfh_model_color_at(self.h, i)) for i in range(self.L.pfh_model_color_count(self.h))]
+
+    def model_values(self, color=None) -> np.ndarray:
+        """the array K-GMM fitted in the last ploidy_estimation (split by colour: the pooled one); color=c: that colour's"""
+        if color is None:
+            return Run.model_values(self)
+        n = self.L.pfh_model_color_values(self.h, int(color), None, 0)
+        if n == 0xFFFFFFFFFFFFFFFF:
+            raise KeyError("colour %d has no fit" % color)
+        out = np.zeros(n, dtype=np.float64)
+        if n:
+            self.L.pfh_model_color_values(self.h, int(color), out.ctypes.data, n)
+        return out
+
+    def model_result(self, color=None) -> dict:
+        """Run.model_result; color=c: the fits of that colour after a ploidy_estimation split by colour"""
+        if color is None:
+            return Run.model_result(self)
+        if int(color) not in self.model_colors():
+            raise KeyError("colour %d has no fit" % color)
+        fits = {}
+        for g in range(1, 17):
+            w, mean, var = (np.zeros(g) for _ in range(3))
+            ll, aic, it = C.c_double(), C.c_double(), C.c_uint32()
+            if self.L.pfh_model_color_fit(self.h, int(color), g, w.ctypes.data, mean.ctypes.data, var.ctypes.data, C.byref(ll), C.byref(aic), C.byref(it)) == 0:
+                fits[g] = {"weights": w, "means": mean, "vars": var, "loglik": ll.value, "aic": aic.value, "iterations": it.value}
+        return {"fits": fits, "ploidy": self.L.pfh_model_color_ploidy(self.h, int(color)), "values": len(self.model_values(color))}
 
     def ploidy_select(self, cutoffs) -> int:
         """scan + sequential pass with one (lower, upper) per colour; then ploidy_align / ploidy_text / ploidy_write as for Run"""
