@@ -62,6 +62,7 @@ enum pf_kernel {
     PF_K_COV_JOIN_REST, /* second kernel of K-COV-JOIN: the look-ups whose first line was full */
     PF_K_COPY_TEXT, /* not a kernel of this library: the copies of result text to the host (the runtime moves them with a kernel of its own) */
     PF_K_CALL_MODEL, /* the kernels of one pf_call_model_take (rows of a piece's text -> the model's values), timed as one launch */
+    PF_K_DENSITY, /* the kernels of one pf_gmm_density, timed as one launch; unit: values x grid points */
     PF_K_COUNT_
 };
 int pf_enable_timing(pf_ctx *, int on);
@@ -605,6 +606,24 @@ int pf_gmm_fit(pf_ctx *, uint32_t gauss, double m_thre, double n_thre, int32_t m
                double *means, double *vars, double *loglik, uint32_t *iterations);
 /* The values pf_gmm_fit reads, copied to the host: the first min(cap, pf_gmm_count) of them. */
 int pf_gmm_values(pf_ctx *, double *dst, uint64_t cap);
+/* The Gaussian kernel density of the values pf_gmm_fit reads (csrc/pf_density.hip): the curve script/Drawfreq.R draws, by ggplot2's
+ * geom_density defaults.  bandwidth = adjust * bw.nrd0: 0.9 * min(sd, IQR / 1.34) * n^(-1/5) with the two-pass sample standard
+ * deviation (divisor n - 1) and type-7 quartiles; when that minimum is 0 the first non-zero of sd, |values[0]|, 1 takes its place.
+ * Grid: `points` (PF_DENSITY_MIN_POINTS .. PF_DENSITY_MAX_POINTS) abscissae x[j] = min + j * (max - min) / (points - 1), the last
+ * one max itself.  density[j] = 1 / (n * bw) * sum_i phi((x[j] - v[i]) / bw): the exact sum -- R's density() bins the values onto
+ * 1024 cells and convolves by FFT, so its numbers differ by its binning error; parity with R is unpinned.  fp64; every sum has a
+ * shape that depends on n and points only (no floating-point atomics), so two calls give the same bits.  The array is left as it
+ * was: pf_gmm_fit and pf_call_model_color_select may precede or follow.  x and density: `points` doubles each; info: the record.
+ * PF_ERR_ARG (pf_last_error): fewer than two values ("need at least 2 data points"), a value that is not finite (named with the
+ * index of the first one), points or adjust out of range. */
+#define PF_DENSITY_MIN_POINTS 2
+#define PF_DENSITY_MAX_POINTS 4096
+typedef struct pf_density_info {
+    uint64_t n;
+    double min, max, sd, q1, q3, bw;
+    double order[4]; /* x(lo), x(lo+1) of Q(0.25), then of Q(0.75) */
+} pf_density_info;
+int pf_gmm_density(pf_ctx *, uint32_t points, double adjust, double *x, double *density, pf_density_info *info);
 
 /* ---- the model fed from the resident call streams (csrc/pf_call_model.hip) ----
  * The values `PloidyFrost model` reads back from <outpre>_bicov / _tricov / _tetracov.txt (-f) or <outpre>_allele_frequency.txt (-g)

@@ -144,6 +144,19 @@ int pfh_gmm_run(pfh_gmm *, int min_gauss, int max_gauss, double m_thre, double n
                 const char *outprefix);
 /* enable = 1 / 0 switches the HIP-event timing of the K-GMM launches on / off; enable < 0 reads the totals */
 int pfh_gmm_kernel_time(pfh_gmm *, int enable, double *total_ms, uint64_t *launches);
+/* ---- the curve script/Drawfreq.R draws, as numbers (pf_gmm_density in ploidyfrost_hip.h) ----
+ * pfh_gmm_read_column: a plain column of numbers, what Drawfreq's read.table makes of its -f file (blank lines and lines that begin
+ * with '#' skipped; every other line one finite number that strtod consumes whole, else refused with the line number; no frequency
+ * test, no doubled last value).  pfh_gmm_density: the Gaussian kernel density of the model's values on the GPU by ggplot2's
+ * geom_density defaults (x, density: `points` doubles each); the exact sum, where R's density() bins onto 1024 cells and convolves by
+ * FFT -- parity with R is unpinned.  Fewer than two values: "need at least 2 data points".  pfh_gmm_write_density writes
+ * <outprefix>_allele_frequency_density.txt: the line "# values N bandwidth BW points P", then P rows x<TAB>density, every number
+ * %.17g (the doubles exactly).  pfh_gmm_density_time: the HIP-event time of the density launches since timing was switched on
+ * (pfh_gmm_kernel_time with enable = 1). */
+int pfh_gmm_read_column(pfh_gmm *, const char *column_file);
+int pfh_gmm_density(pfh_gmm *, uint32_t points, double adjust, double *x, double *density, pf_density_info *info);
+int pfh_gmm_write_density(pfh_gmm *, const char *outprefix, const pf_density_info *info, uint32_t points, const double *x, const double *density);
+int pfh_gmm_density_time(pfh_gmm *, double *total_ms, uint64_t *launches);
 
 /* ---- the ploidy estimate in the same run (single-sample path; pf_call_model_* in ploidyfrost_hip.h) ----
  * pfh_set_model before pfh_ploidy_estimation: that call then feeds the model from the text pieces while they are resident on the
@@ -161,6 +174,16 @@ uint64_t pfh_model_values(pfh_run *, double *out, uint64_t cap);
 int pfh_model_fit(const pfh_run *, uint32_t gauss, double *weights, double *means, double *vars, double *loglik, double *aic,
                   uint32_t *iterations);
 double pfh_model_ploidy(const pfh_run *);
+/* pfh_set_density after pfh_set_model: the pass then takes the kernel density (pf_gmm_density) of the array each fit reads, right
+ * after that fit -- the pooled array, and split by colour every colour's -- and writes <outpre>_allele_frequency_density.txt /
+ * <outpre>_color<c>_allele_frequency_density.txt beside the model results.  points == 0 switches it off, as switching the model off
+ * does; refused without a model, for points outside PF_DENSITY_MIN_POINTS .. PF_DENSITY_MAX_POINTS and for an adjust that is not a
+ * finite positive number.  After the pass: pfh_model_density_points(color < 0: pooled) = the grid's length (0: no curve),
+ * pfh_model_density / pfh_model_color_density copy grid, curve and record (each may be NULL; 0 = ok, 1 = no curve). */
+int pfh_set_density(pfh_run *, uint32_t points, double adjust);
+uint32_t pfh_model_density_points(const pfh_run *, int color);
+int pfh_model_density(const pfh_run *, double *x, double *density, pf_density_info *info);
+int pfh_model_color_density(const pfh_run *, int color, double *x, double *density, pf_density_info *info);
 uint64_t pfh_text_bytes_fetched(const pfh_run *);
 /* The row rule of that path on text in host memory (csrc/pf_model_rows.hpp, the code the device kernels run), no device involved:
  * source 0: text[0..2] = the bytes of _bicov / _tricov / _tetracov.txt, source 1: text[0] = those of _allele_frequency.txt; the

@@ -475,7 +475,19 @@ int CDBG::set_model(const ModelOptions &o) {
         if (o.q >= 0.5 || o.max_iter < 0 || o.max_delta < 0 || o.m_thre < 0 || o.n_thre < 0) return refuse("CDBG::set_model(): q < 0.5, iterations, delta and thresholds >= 0 (as `model` checks them)");
     }
     model_ = o;
-    if (!o.on) model_.only = filter_on_ = multi_on_ = multi_each_ = false;
+    if (!o.on) { model_.only = filter_on_ = multi_on_ = multi_each_ = false; density_points_ = 0; }
+    return 0;
+}
+
+int CDBG::set_density(unsigned points, double adjust) {
+    auto refuse = [&](const std::string &m) { err_ = m; return (int)PF_ERR_ARG; };
+    if (points == 0) { density_points_ = 0; return 0; }
+    if (!model_.on) return refuse(std::string(tag_) + "::set_density(): the density is taken of the array the model of the same run reads; set a model first");
+    if (points < PF_DENSITY_MIN_POINTS || points > PF_DENSITY_MAX_POINTS)
+        return refuse(std::string(tag_) + "::set_density(): " + std::to_string(points) + " points: the grid holds " + std::to_string(PF_DENSITY_MIN_POINTS) + " to " + std::to_string(PF_DENSITY_MAX_POINTS));
+    if (!(adjust > 0) || !std::isfinite(adjust)) return refuse(std::string(tag_) + "::set_density(): adjust is a finite positive number");
+    density_points_ = points;
+    density_adjust_ = adjust;
     return 0;
 }
 

@@ -137,6 +137,15 @@ public:
         int max_iter = 1000;
     };
     int set_model(const ModelOptions &o);
+    // The kernel density of the array every fit of that model reads (pf_gmm_density), taken right after the fit: the pooled array,
+    // and with each_color every colour's after its selection; written to <outpre>_allele_frequency_density.txt /
+    // <outpre>_color<c>_allele_frequency_density.txt beside the model results.  After set_model; points == 0: off (as switching the
+    // model off does).  An array of fewer than two values: the pass ends with "need at least 2 data points" once everything else is
+    // complete; split by colour such a colour is listed (model_colors_without_density), gets no file, and the pass fails only when
+    // no colour has a curve.
+    int set_density(unsigned points, double adjust);
+    const Density *model_density() const { return density_done_ ? &density_ : nullptr; }
+    const std::vector<int> &model_colors_without_density() const { return color_no_density_; }
     // `ploidyfrost filter`'s row predicates in front of that model (pf_call_model_filter; the rule is csrc/pf_filter_rows.hpp): the
     // estimate of `filter` + `model` on this run's files, no filtered table written.  Null: no filter.  Refused unless a model is set;
     // switching the model off drops it.
@@ -153,6 +162,8 @@ public:
         std::vector<GmmModel::Fit> fits;
         double ploidy = 0;
         std::vector<double> values;
+        bool has_density = false;
+        Density density;
     };
     const std::vector<ColorFit> &model_color_fits() const { return color_fits_; }
     const std::vector<int> &model_colors_without_rows() const { return color_none_; }
@@ -230,6 +241,11 @@ protected:
     std::vector<pf_bfs_record> shard_rec_;
     std::vector<uint32_t> shard_pool_;
     ModelOptions model_;
+    unsigned density_points_ = 0;   // 0: no density
+    double density_adjust_ = 1.0;
+    Density density_;
+    bool density_done_ = false;
+    std::vector<int> color_no_density_;
     bool filter_on_ = false;
     pf_filter_opts filter_ = {};
     bool multi_on_ = false, multi_each_ = false;

@@ -249,6 +249,8 @@ int CDBG::ploidy_estimation_resident(const std::string &outpre, const std::vecto
     color_fits_.clear();
     color_none_.clear();
     color_empty_.clear();
+    color_no_density_.clear();
+    density_done_ = false;
     pooled_values_.clear();
     last_each_ = false;
     const uint64_t fetched_before = pf_call_fetched_bytes(ctx_);
@@ -784,6 +786,14 @@ int CDBG::ploidy_estimation_resident(const std::string &outpre, const std::vecto
             fits = gm.fits();
             return 0;
         };
+        // the density of the array the fit has just read (the array is as the fit found it); 2 = fewer than two values
+        auto density = [&](uint64_t n, const std::string &prefix, Density &d, std::string &derr) {
+            if (n < 2) { derr = "need at least 2 data points"; return 2; }
+            GmmModel gm;
+            gm.borrow(ctx_, (size_t)n);
+            if (gm.density(density_points_, density_adjust_, d)) { derr = gm.error(); return 1; }
+            return write_density(prefix, d, derr);
+        };
         std::string merr;
         if (multi_on_ && multi_each_) {
             // one fit per colour that kept a row, in colour order, each over its own selection of the pooled tokens
@@ -804,9 +814,16 @@ int CDBG::ploidy_estimation_resident(const std::string &outpre, const std::vecto
                 cf.values.resize((size_t)n_c);
                 if (n_c && pf_gmm_values(ctx_, cf.values.data(), n_c) != PF_OK) return model_fail(PF_ERR_HIP, pf_last_error(ctx_));
                 if (fit(n_c, outdir_ + "/" + outpre + "_color" + std::to_string(c), cf.fits, cf.ploidy, merr)) return model_fail(PF_ERR_ARG, merr);
+                if (density_points_) {
+                    const int ds = density(n_c, outdir_ + "/" + outpre + "_color" + std::to_string(c), cf.density, merr);
+                    if (ds == 1) return model_fail(PF_ERR_ARG, merr);
+                    cf.has_density = ds == 0;
+                    if (ds == 2) color_no_density_.push_back((int)c);
+                }
                 color_fits_.push_back(std::move(cf));
             }
             if (color_fits_.empty()) return model_fail(PF_ERR_ARG, std::string(tag_) + "::PloidyEstimation(): no colour holds a value for the model");
+            if (density_points_ && color_no_density_.size() == color_fits_.size()) return model_fail(PF_ERR_ARG, "need at least 2 data points");
             tp("models fitted, colour by colour");
         } else {
             if (fit(n_values, outdir_ + "/" + outpre, model_fits_, model_ploidy_, merr)) return model_fail(PF_ERR_ARG, merr);
@@ -814,6 +831,11 @@ int CDBG::ploidy_estimation_resident(const std::string &outpre, const std::vecto
             line << "estimated ploidy level is : " << model_ploidy_;
             model_last_line_ = line.str();
             tp("model fitted");
+            if (density_points_) {
+                if (density(n_values, outdir_ + "/" + outpre, density_, merr)) return model_fail(PF_ERR_ARG, merr);
+                density_done_ = true;
+                tp("density taken");
+            }
         }
     }
     times_.ploidy_total_s = since(t_all);

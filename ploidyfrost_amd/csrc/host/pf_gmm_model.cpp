@@ -1,6 +1,8 @@
 #include "pf_gmm_model.hpp"
 
 #include <cfloat>
+#include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
@@ -31,9 +33,7 @@ void GmmModel::resize(size_t g) {
     for (size_t i = 1; i <= g; ++i) means[i - 1] = (double)i / (double)(g + 1);
 }
 
-// src/GmmModel.cpp:371-385, the loop itself runs on the device
-int GmmModel::emIterate() {
-    if (gauss < 1 || gauss > PF_GMM_MAX_GAUSS) return fail("GmmModel: the device fit takes 1.." + std::to_string(PF_GMM_MAX_GAUSS) + " Gaussians");
+int GmmModel::to_device() {
     if (!ctx_) {
         if (pf_create(device_, &ctx_) != PF_OK) {
             const char *e = pf_last_error(nullptr);
@@ -45,6 +45,48 @@ int GmmModel::emIterate() {
         if (pf_gmm_upload(ctx_, allele_fre.data(), allele_fre.size()) != PF_OK) return fail(std::string("GmmModel: ") + pf_last_error(ctx_));
         uploaded_ = true;
     }
+    return 0;
+}
+
+int GmmModel::density(unsigned points, double adjust, Density &out) {
+    // (what needs no device is refused without one)
+    if (points < PF_DENSITY_MIN_POINTS || points > PF_DENSITY_MAX_POINTS)
+        return fail("density: " + std::to_string(points) + " points: the grid holds " + std::to_string(PF_DENSITY_MIN_POINTS) + " to " + std::to_string(PF_DENSITY_MAX_POINTS));
+    if (!(adjust > 0) || !std::isfinite(adjust)) return fail("density: adjust is a finite positive number");
+    if (size() < 2) return fail("need at least 2 data points");
+    if (to_device()) return 1;
+    out.x.assign(points, 0.0);
+    out.density.assign(points, 0.0);
+    if (pf_gmm_density(ctx_, points, adjust, out.x.data(), out.density.data(), &out.info) != PF_OK) return fail(pf_last_error(ctx_));
+    return 0;
+}
+
+int GmmModel::readColumn(const std::string &filename) {
+    std::ifstream in(filename, std::ios::in);
+    if (!in.is_open()) return fail("ERROR: open column file " + filename + " error!");
+    allele_fre.clear();
+    uploaded_ = false;
+    std::string s;
+    for (size_t line = 1; std::getline(in, s, '\n'); ++line) {
+        if (!s.empty() && s.back() == '\r') s.pop_back();
+        const size_t from = s.find_first_not_of(" \t"), to = s.find_last_not_of(" \t");
+        if (from == std::string::npos || s[from] == '#') continue;
+        const std::string tok = s.substr(from, to - from + 1);
+        char *end = nullptr;
+        const double v = strtod(tok.c_str(), &end);
+        if (end == tok.c_str() || *end != 0 || !std::isfinite(v)) {
+            allele_fre.clear();
+            return fail("ERROR: line " + std::to_string(line) + " of " + filename + " is not one finite number");
+        }
+        allele_fre.push_back(v);
+    }
+    return 0;
+}
+
+// src/GmmModel.cpp:371-385, the loop itself runs on the device
+int GmmModel::emIterate() {
+    if (gauss < 1 || gauss > PF_GMM_MAX_GAUSS) return fail("GmmModel: the device fit takes 1.." + std::to_string(PF_GMM_MAX_GAUSS) + " Gaussians");
+    if (to_device()) return 1;
     uint32_t it = 0;
     if (pf_gmm_fit(ctx_, (uint32_t)gauss, m_thre, n_thre, emMaxIter, emMaxDelta, weights.data(), means.data(), vars.data(), &logLikelihood, &it) != PF_OK)
         return fail(std::string("GmmModel: ") + pf_last_error(ctx_));
@@ -167,6 +209,17 @@ int run_model(GmmModel &model, int lo, int hi, const std::string &outprefix, std
     outfile << "min AIC : " << minaic << "\tploidy : " << aic_p << std::endl;
     outfile << "estimated ploidy level is : " << aic_p << std::endl;
     if (ploidy) *ploidy = aic_p;
+    return 0;
+}
+
+int write_density(const std::string &outprefix, const Density &d, std::string &err) {
+    const std::string name = density_file(outprefix);
+    FILE *f = fopen(name.c_str(), "w");
+    if (!f) { err = "ERROR: open output file " + name + " error!"; return 1; }
+    fprintf(f, "# values %llu bandwidth %.17g points %zu\n", (unsigned long long)d.info.n, d.info.bw, d.x.size());
+    for (size_t j = 0; j < d.x.size(); ++j) fprintf(f, "%.17g\t%.17g\n", d.x[j], d.density[j]);
+    const bool bad = ferror(f) != 0;
+    if (fclose(f) != 0 || bad) { err = "ERROR: write error on " + name; return 1; }
     return 0;
 }
 

@@ -10,9 +10,15 @@
 #include <string>
 #include <vector>
 
-struct pf_ctx;
+#include "ploidyfrost_hip.h"
 
 namespace pfh {
+
+// one kernel density estimate (pf_gmm_density): the grid, the curve over it and the record of how it was made
+struct Density {
+    std::vector<double> x, density;
+    pf_density_info info = {};
+};
 
 class GmmModel {
 public:
@@ -48,6 +54,12 @@ public:
     void clear_fits() { fits_.clear(); }
     int readFreFile(const std::string &filename, const double &freq);
     int readCovFile(const std::string &prefix, const double &freq);
+    // a plain column of numbers, what script/Drawfreq.R's read.table makes of its -f file: blank lines and lines that begin
+    // with '#' are skipped, every other line is one finite number (strtod takes the whole token) or is refused with its number;
+    // no frequency test and no doubled last value
+    int readColumn(const std::string &filename);
+    // the Gaussian kernel density of the values on the device (pf_gmm_density): 0 = ok
+    int density(unsigned points, double adjust, Density &out);
     void output(std::ostream &os) const;
     void print() const;
 
@@ -61,6 +73,7 @@ public:
 
 private:
     int fail(const std::string &m) { err_ = m; return 1; }
+    int to_device();   // the context on first use, the values where the kernels read them
     std::vector<double> allele_fre;
     size_t gauss = 0;
     std::vector<double> weights, means, vars;
@@ -81,5 +94,9 @@ private:
 // `PloidyFrost model` after option parsing (src/Main.cpp:644-692): fits gauss = lo .. hi, writes <outprefix>_model_result.txt
 // *ploidy (optional): the value of the file's last line
 int run_model(GmmModel &model, int lo, int hi, const std::string &outprefix, std::string &err, double *ploidy = nullptr);
+// <outprefix>_allele_frequency_density.txt: "# values N bandwidth BW points P", then P rows x<TAB>density, every number %.17g
+// (the doubles exactly; read.table and gnuplot skip the comment).  0 = ok
+int write_density(const std::string &outprefix, const Density &d, std::string &err);
+inline std::string density_file(const std::string &outprefix) { return outprefix + "_allele_frequency_density.txt"; }
 
 }  // namespace pfh

@@ -566,12 +566,42 @@ int pfh_gmm_run(pfh_gmm *m, int min_gauss, int max_gauss, double m_thre, double 
         return pfh::run_model(m->model, min_gauss, max_gauss, outprefix, m->err);
     });
 }
+int pfh_gmm_read_column(pfh_gmm *m, const char *file) {
+    return gmm_guard(m, [&] { return m->model.readColumn(file); });
+}
+int pfh_gmm_density(pfh_gmm *m, uint32_t points, double adjust, double *x, double *density, pf_density_info *info) {
+    return gmm_guard(m, [&] {
+        if (!x || !density || !info) { m->err = "pfh_gmm_density: x, density and info are needed"; return 1; }
+        pfh::Density d;
+        if (m->model.density(points, adjust, d)) return 1;
+        std::copy(d.x.begin(), d.x.end(), x);
+        std::copy(d.density.begin(), d.density.end(), density);
+        *info = d.info;
+        return 0;
+    });
+}
+int pfh_gmm_write_density(pfh_gmm *m, const char *outprefix, const pf_density_info *info, uint32_t points, const double *x, const double *density) {
+    return gmm_guard(m, [&] {
+        if (!outprefix || !info || !x || !density) { m->err = "pfh_gmm_write_density: prefix, info, x and density are needed"; return 1; }
+        pfh::Density d;
+        d.x.assign(x, x + points);
+        d.density.assign(density, density + points);
+        d.info = *info;
+        return pfh::write_density(outprefix, d, m->err);
+    });
+}
 int pfh_gmm_kernel_time(pfh_gmm *m, int enable, double *total_ms, uint64_t *launches) {
     if (!m) return 1;
     pf_ctx *ctx = m->model.device_context();
     if (!ctx) return 1;
     if (enable >= 0) return pf_enable_timing(ctx, enable);
     return pf_kernel_time(ctx, PF_K_GMM, total_ms, launches);
+}
+int pfh_gmm_density_time(pfh_gmm *m, double *total_ms, uint64_t *launches) {
+    if (!m) return 1;
+    pf_ctx *ctx = m->model.device_context();
+    if (!ctx) return 1;
+    return pf_kernel_time(ctx, PF_K_DENSITY, total_ms, launches);
 }
 
 // ---- the model in the same run ---------------------------------------------------------------------------------------
@@ -587,6 +617,30 @@ int pfh_set_model(pfh_run *r, int source, double min_frequency, int lo, int hi, 
         o.m_thre = m_thre; o.n_thre = n_thre; o.max_iter = max_iter; o.max_delta = max_delta;
         return r->cdbg->set_model(o);
     });
+}
+int pfh_set_density(pfh_run *r, uint32_t points, double adjust) {
+    return guarded(r, [&] { return r->cdbg->set_density(points, adjust); });
+}
+static int density_out(const pfh::Density *d, double *x, double *density, pf_density_info *info) {
+    if (!d) return 1;
+    if (x) std::copy(d->x.begin(), d->x.end(), x);
+    if (density) std::copy(d->density.begin(), d->density.end(), density);
+    if (info) *info = d->info;
+    return 0;
+}
+uint32_t pfh_model_density_points(const pfh_run *r, int color) {
+    if (color < 0) return r->cdbg->model_density() ? (uint32_t)r->cdbg->model_density()->x.size() : 0;
+    for (const pfh::CDBG::ColorFit &cf : r->cdbg->model_color_fits())
+        if (cf.color == color) return cf.has_density ? (uint32_t)cf.density.x.size() : 0;
+    return 0;
+}
+int pfh_model_density(const pfh_run *r, double *x, double *density, pf_density_info *info) {
+    return density_out(r->cdbg->model_density(), x, density, info);
+}
+int pfh_model_color_density(const pfh_run *r, int color, double *x, double *density, pf_density_info *info) {
+    for (const pfh::CDBG::ColorFit &cf : r->cdbg->model_color_fits())
+        if (cf.color == color) return density_out(cf.has_density ? &cf.density : nullptr, x, density, info);
+    return 1;
 }
 uint64_t pfh_model_values(pfh_run *r, double *out, uint64_t cap) {
     const uint64_t n = r->cdbg->model_count();

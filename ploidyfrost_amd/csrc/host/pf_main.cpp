@@ -74,10 +74,14 @@ void PrintUsage() {
          << "  --filter-multi \"OPTS\"  with -f and --model: the colored rows through `ploidyfrost filter-multi OPTS` (-S -l -u -I -P -n -d -s -q" << endl
          << "                  -c -v) first, on the device; the estimate of that filter and `model` in one command, no filtered table written" << endl
          << "  --model-each-color  with --filter-multi (without -c): one estimate per colour, <prefix>_color<c>_model_result.txt each, as" << endl
-         << "                  --filter-multi \"OPTS -c c\" gives them one run at a time" << endl << endl
+         << "                  --filter-multi \"OPTS -c c\" gives them one run at a time" << endl
+         << "  --density       with --model: the Gaussian kernel density of the values the model read (the curve of script/Drawfreq.R, as" << endl
+         << "                  numbers), <prefix>_allele_frequency_density.txt; with --model-each-color one file per fitted colour" << endl
+         << "  --density-points N, --density-adjust A   grid points (default 512, 2 to 4096) and bandwidth factor (default 1)" << endl << endl
          << "Usage: PloidyFrost cutoffL kmer_histogram_file" << endl
          << "Usage: PloidyFrost cutoffU kmer_histogram_file (quantile[<1 ,default:0.998])" << endl << endl
          << "Usage: PloidyFrost model ...          (GMM ploidy inference from the coverage / frequency files; `PloidyFrost model` prints its options)" << endl
+         << "Usage: PloidyFrost density -f <column file> -o <outfile_prefix> [-n points] [-a adjust]   (kernel density of a column of numbers)" << endl
          << "Usage: PloidyFrost filter ...         (the row predicates of script/Filter.R over <prefix>_*cov.txt; -h prints its options)" << endl
          << "Usage: PloidyFrost filter-multi ...   (script/Filter-multi.R: the colored tables, with -c colour and -v Cramer's V)" << endl;
 }
@@ -200,6 +204,91 @@ bool refuse_each_color_with_one(const pf_filter_multi_opts &m) {
     return true;
 }
 
+// --density [--density-points N] [--density-adjust A]: the words as given, checked before anything is read or written
+struct DensityCli {
+    bool on = false, points_seen = false, adjust_seen = false;
+    string points_word, adjust_word;
+    unsigned points = 512;
+    double adjust = 1.0;
+    // takes argv[i] (and its value) when it is one of the three switches: 0 = not one of them, else the number of words taken
+    int take(int argc, char **argv, int i) {
+        if (strcmp(argv[i], "--density") == 0) { on = true; return 1; }
+        const bool p = strcmp(argv[i], "--density-points") == 0, a = strcmp(argv[i], "--density-adjust") == 0;
+        if ((p || a) && i + 1 < argc) {
+            (p ? points_seen : adjust_seen) = true;
+            (p ? points_word : adjust_word) = argv[i + 1];
+            return 2;
+        }
+        return 0;
+    }
+    // false: refused, one line on stderr
+    bool check(const char *points_name = "--density-points", const char *adjust_name = "--density-adjust") {
+        if ((points_seen || adjust_seen) && !on) { cerr << "Error: --density-points / --density-adjust need --density" << endl; return false; }
+        if (points_seen) {
+            char *end = nullptr;
+            const long v = strtol(points_word.c_str(), &end, 10);
+            if (end == points_word.c_str() || *end != 0 || v < PF_DENSITY_MIN_POINTS || v > PF_DENSITY_MAX_POINTS) {
+                cerr << "Error: " << points_name << " " << points_word << ": grid points from " << PF_DENSITY_MIN_POINTS << " to " << PF_DENSITY_MAX_POINTS << endl;
+                return false;
+            }
+            points = (unsigned)v;
+        }
+        if (adjust_seen) {
+            char *end = nullptr;
+            const double v = strtod(adjust_word.c_str(), &end);
+            if (end == adjust_word.c_str() || *end != 0 || !std::isfinite(v) || !(v > 0)) {
+                cerr << "Error: " << adjust_name << " " << adjust_word << ": the bandwidth factor is a finite positive number" << endl;
+                return false;
+            }
+            adjust = v;
+        }
+        return true;
+    }
+};
+
+// the density of the values `model` has on the device, written beside its result: 0 = ok, 2 = fewer than two values
+int density_of(pfh::GmmModel &model, const DensityCli &dc, const string &outprefix, string &err) {
+    if (model.size() < 2) { err = "need at least 2 data points"; return 2; }
+    pfh::Density d;
+    if (model.density(dc.points, dc.adjust, d)) { err = model.error(); return 1; }
+    return pfh::write_density(outprefix, d, err);
+}
+
+void PrintDensityUsage() {
+    cout << "Usage: PloidyFrost density" << endl
+         << "Gaussian kernel density of a column of numbers (the curve script/Drawfreq.R draws; the exact sum, on the device)" << endl
+         << "  -f,             Column file: one number a line, blank lines and lines beginning with # skipped" << endl
+         << "  -o,             Output prefix: <prefix>_allele_frequency_density.txt (default : 'output')" << endl
+         << "  -n,             Grid points (default : 512, 2 to 4096)" << endl
+         << "  -a,             Bandwidth factor, ggplot2's adjust (default : 1)" << endl
+         << endl;
+}
+
+// `ploidyfrost density`: Drawfreq.R's numbers (its -t and -p draw and are not taken)
+int density_main(int argc, char **argv) {
+    string file, outprefix = "output";
+    DensityCli dc;
+    dc.on = true;
+    int oc;
+    while ((oc = getopt(argc, argv, "f:o:n:a:")) != -1) {
+        switch (oc) {
+            case 'f': file = optarg; break;
+            case 'o': outprefix = optarg; break;
+            case 'n': dc.points_seen = true; dc.points_word = optarg; break;
+            case 'a': dc.adjust_seen = true; dc.adjust_word = optarg; break;
+            default: PrintDensityUsage(); return 1;
+        }
+    }
+    if (file.empty()) { PrintDensityUsage(); return argc > 2 ? 1 : 0; }
+    if (!dc.check("-n", "-a")) return 1;
+    if (!file_exists(file)) { cerr << "ERROR: open column file " << file << " error!" << endl; return 1; }
+    pfh::GmmModel model;
+    string err;
+    if (model.readColumn(file)) { cerr << model.error() << endl; return 1; }
+    if (density_of(model, dc, outprefix, err)) { cerr << err << endl; return 1; }
+    return 0;
+}
+
 void PrintModelUsage() {  // src/Main.cpp:694-718
     cout << "Usage: PloidyFrost model" << endl
          << "GMM model" << endl
@@ -217,6 +306,8 @@ void PrintModelUsage() {  // src/Main.cpp:694-718
          << "                  add --source fre for the filtered frequencies (as `model -g <filtered>_allele_frequency.txt`)" << endl
          << "  --filter-multi \"OPTS\" with -f: the same for the coverage files of a colored run through `ploidyfrost filter-multi OPTS`;" << endl
          << "                  --model-each-color: one result per colour, <out>_color<c>_model_result.txt" << endl
+         << "  --density       the Gaussian kernel density of the values the model read, <out>_allele_frequency_density.txt (per colour:" << endl
+         << "                  <out>_color<c>_allele_frequency_density.txt); --density-points N (default 512), --density-adjust A (default 1)" << endl
          << endl;
 }
 
@@ -228,7 +319,14 @@ int model_main(int argc, char **argv) {
     // --filter "<opts>" [--source cov|fre] (this build's own switches, taken out of argv before getopt sees them)
     bool filtered = false, multi = false, each_color = false;
     string filter_words, filter_source = "cov";
+    DensityCli dc;
     for (int i = 2; i < argc; ++i) {
+        if (const int took = dc.take(argc, argv, i)) {
+            for (int j = i; j + took <= argc; ++j) argv[j] = j + took < argc ? argv[j + took] : nullptr;
+            argc -= took;
+            --i;
+            continue;
+        }
         const bool is_filter = strcmp(argv[i], "--filter") == 0, is_multi = strcmp(argv[i], "--filter-multi") == 0;
         if (strcmp(argv[i], "--model-each-color") == 0) {
             each_color = true;
@@ -253,6 +351,7 @@ int model_main(int argc, char **argv) {
     if (filtered && !(multi ? parse_filter_multi_words(filter_words, mopts) : parse_filter_words(filter_words, fopts))) return 1;
     if (each_color && refuse_each_color_with_one(mopts)) return 1;
     if (filtered && filter_source != "cov" && filter_source != "fre") { cerr << "Error: --source " << filter_source << ": cov or fre" << endl; return 1; }
+    if (!dc.check()) return 1;
     int oc;
     while ((oc = getopt(argc, argv, "M:D:G:z:a:l:q:u:e:C:R:o:t:g:f:k:d:m:n:h:ibvpNSc")) != -1) {
         switch (oc) {
@@ -323,7 +422,7 @@ int model_main(int argc, char **argv) {
             // (colours above the largest one that kept a row are not known here -- the tables do not say how many there are -- so
             // they get no line; the run with -f <colors file> names every colour of the graph)
             const uint32_t nc = pf_call_model_color_count(ctx);
-            uint32_t fitted = 0;
+            uint32_t fitted = 0, curves = 0;
             for (uint32_t c = 0; c < nc; ++c) {
                 uint64_t n_c = 0;
                 if (pf_call_model_color_select(ctx, (int)c, &n_c) != PF_OK) leave(pf_last_error(ctx));
@@ -340,9 +439,16 @@ int model_main(int argc, char **argv) {
                 if (pfh::run_model(cm, lower, upper, outprefix + "_color" + to_string(c), cerr_, &ploidy)) leave(cerr_);
                 cout << "color " << c << ": estimated ploidy level is : " << ploidy << endl;
                 ++fitted;
+                if (dc.on) {
+                    const int ds = density_of(cm, dc, outprefix + "_color" + to_string(c), cerr_);
+                    if (ds == 1) leave(cerr_);
+                    if (ds == 2) cerr << "color " << c << ": " << cerr_ << ", no density" << endl;
+                    else ++curves;
+                }
             }
             pf_destroy(ctx);
             if (!fitted) { cout << "model --model-each-color: no colour holds a value for the model" << endl; return EXIT_FAILURE; }
+            if (dc.on && !curves) { cout << "need at least 2 data points" << endl; return EXIT_FAILURE; }
             return 0;
         }
         model.borrow(ctx, (size_t)n_values);
@@ -356,6 +462,10 @@ int model_main(int argc, char **argv) {
         cout << err << endl;
         exit(EXIT_FAILURE);
     }
+    if (dc.on && density_of(model, dc, outprefix, err)) {
+        cout << err << endl;
+        exit(EXIT_FAILURE);
+    }
     return 0;
 }
 }  // namespace
@@ -363,6 +473,7 @@ int model_main(int argc, char **argv) {
 int main(int argc, char **argv) {
     if (argc < 2) { PrintUsage(); return 0; }
     if (!strcmp(argv[1], "model")) return model_main(argc, argv);
+    if (!strcmp(argv[1], "density")) return density_main(argc - 1, argv + 1);
     if (!strcmp(argv[1], "filter")) return pfh::filter_main(argc, argv, false);         // script/Filter.R
     if (!strcmp(argv[1], "filter-multi")) return pfh::filter_main(argc, argv, true);    // script/Filter-multi.R
     if (!strcmp(argv[1], "cutoffL")) {  // src/Main.cpp:721-730
@@ -386,9 +497,15 @@ int main(int argc, char **argv) {
         return 0;
     }
     Options opt;
+    DensityCli dc;
     // --ref-threads N (this build's own switch, taken out of argv before getopt sees it): write the text format of the reference's
     // `-t N` functions -- with N > 1: ids and var_count from 0, allele_frequency rows grouped by arity per bubble -- whatever -t says
     for (int i = 1; i < argc; ++i) {
+        if (const int took = dc.take(argc, argv, i)) {
+            for (int j = i; j + took <= argc; ++j) argv[j] = j + took < argc ? argv[j + took] : nullptr;
+            argc -= took;
+            --i;
+        } else
         if (strcmp(argv[i], "--ref-threads") == 0 && i + 1 < argc) {
             opt.ref_threads = (size_t)atoi(argv[i + 1]);
             for (int j = i; j + 2 <= argc; ++j) argv[j] = j + 2 < argc ? argv[j + 2] : nullptr;
@@ -509,6 +626,8 @@ int main(int argc, char **argv) {
         model.lo = lo; model.hi = hi;
         model.m_thre = opt.model_m; model.n_thre = opt.model_n; model.max_iter = opt.model_iter; model.max_delta = opt.model_delta;
     }
+    if (!dc.check()) return 1;
+    if (dc.on && !model.on) { cerr << "Error: --density takes the density of the values the model of the same run reads: it needs --model cov|fre (a column of numbers: `ploidyfrost density`)" << endl; return 1; }
     // check_ProgramOptions (:278-541), single-sample subset
     bool ok = true;
     const size_t max_threads = std::thread::hardware_concurrency();
@@ -614,6 +733,7 @@ int main(int argc, char **argv) {
         g.set_overlap_output(true);
         if (model.on && g.set_model(model)) die();
         if (opt.multi_seen && g.set_filter_multi(&multi, opt.each_color)) die();
+        if (dc.on && g.set_density(dc.points, dc.adjust)) die();
         if (g.setUnitigId(opt.outprefix, opt.graphfile, opt.nb_threads)) die();
         if (opt.info && g.printInfo(opt.verbose, opt.outprefix)) die();
         if (g.findSuperBubble_multithread_ptr(opt.outprefix, opt.nb_threads)) die();
@@ -626,6 +746,7 @@ int main(int argc, char **argv) {
             for (int c : g.model_colors_without_rows()) cerr << "color " << c << ": no row kept, no estimate" << endl;
             for (int c : g.model_colors_without_values()) cerr << "color " << c << ": the rows kept hold no value for the model, no estimate" << endl;
             for (const pfh::CDBG::ColorFit &cf : g.model_color_fits()) cout << "color " << cf.color << ": estimated ploidy level is : " << cf.ploidy << endl;
+            for (int c : g.model_colors_without_density()) cerr << "color " << c << ": need at least 2 data points, no density" << endl;
         } else if (model.on) cout << g.model_last_line() << endl;
         if (opt.verbose) {
             const pfh::PhaseTimes &t = g.times();
@@ -819,6 +940,7 @@ int main(int argc, char **argv) {
     }
     if (model.on && g.set_model(model)) die();
     if (opt.filter_seen && g.set_filter(&filter)) die();
+    if (dc.on && g.set_density(dc.points, dc.adjust)) die();
     if (g.setUnitigId(opt.outprefix, opt.graphfile, opt.nb_threads)) die();
     if (opt.info && g.printInfo(opt.verbose, opt.outprefix)) die();
     mark("setUnitigId");

@@ -217,6 +217,7 @@ enum WsSlot {
     WS_BUB_TEXT, WS_BUB_PATHS, WS_BUB_TASKS, WS_BUB_SMALL, WS_BUB_RETRY, WS_BUB_IDX, WS_BUB_RES, WS_BUB_OTEXT, WS_BUB_OSITES,
     WS_BUB_OGROUPS, WS_BUB_OILEN, WS_BUB_SCRATCH, WS_BUB_WORK, WS_BUB_IDX2, WS_CCOV_SUM, WS_CCOV_MIN, WS_CCOV_MAX, WS_CCOV_MISS, WS_GMM_X, WS_GMM_STATE, WS_GMM_PART,
     WS_JOIN_REST, WS_JOIN_REST_N,   // K-COV-JOIN: the look-ups its pipeline hands on (pf_device.hip)
+    WS_DENSITY,     // K-DENSITY: state, histograms, partial sums and the curve of one pf_gmm_density (pf_density.hip)
     WS_BUB_LANES,   // K-BUBBLE's five launch workspaces (small, retry, scratch, work, idx2) of lanes 1 .. PF_CALL_LANES - 1 (bub_ws)
     WS_COUNT_ = WS_BUB_LANES + 5 * (PF_CALL_LANES - 1)
 };

@@ -23,6 +23,12 @@ KERNELS = ["k_table_build", "k_adj_insert", "k_adj_probe", "k_cov", "k_bfs", "k_
            "k_strcov", "k_bubble", "k_bubble_big", "k_cov_colored", "k_strcov_colored", "k_gmm", "k_kmc_decode", "k_minz_count", "k_cov_join",
            "k_call_sides", "k_call_prep", "k_call_paths", "k_call_sites", "k_call_format", "k_call_snp", "k_bfs_thread", "k_call_pair", "k_call_stack", "k_cov_join_rest", "copy_text_to_host", "k_call_model"]
 
+K_DENSITY = len(KERNELS)   # PF_K_DENSITY ("k_density"): the kernels of one pf_gmm_density, timed as one launch
+DENSITY_INFO = np.dtype([("n", "<u8"), ("min", "<f8"), ("max", "<f8"), ("sd", "<f8"), ("q1", "<f8"), ("q3", "<f8"), ("bw", "<f8"),
+                         ("order", "<f8", (4,))])   # pf_density_info
+assert DENSITY_INFO.itemsize == 88
+DENSITY_MIN_POINTS, DENSITY_MAX_POINTS = 2, 4096
+
 BFS_RECORD = np.dtype([("entrance", "<u4"), ("exit", "<u4"), ("n_seen", "<u4"), ("n_list", "<u4"), ("list_off", "<u8"),
                        ("outcome", "u1"), ("flag_cycle", "u1"), ("flag_tip", "u1"), ("strict", "u1"), ("pad", "<u4")])
 ALIGN_JOB = np.dtype([("a_off", "<u8"), ("b_off", "<u8"), ("a_len", "<u4"), ("b_len", "<u4")])
@@ -186,6 +192,7 @@ def load_library() -> C.CDLL:
         "pf_call_model_filter_multi": (i, [vp, vp, i]),
         "pf_call_model_color_count": (C.c_uint32, [vp]),
         "pf_call_model_color_select": (i, [vp, i, C.POINTER(u64)]),
+        "pf_gmm_density": (i, [vp, u32, C.c_double, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError = header / library mismatch
@@ -206,7 +213,15 @@ DECLARED_SYMBOLS = ["pf_create", "pf_warmup", "pf_destroy", "pf_last_error", "pf
                     "pf_call_text", "pf_call_set_alignseq_packed", "pf_comm_unique_id", "pf_comm_init", "pf_gather", "pf_comm_destroy", "pf_call_reserve", "pf_call_reserve_lanes", "pf_timing_select", "pf_kernel_busy", "pf_call_reserve_text", "pf_selftest_scan", "pf_call_set_numeric_packed", "pf_call_fetch_text", "pf_find_reserve", "pf_call_set_colours", "pf_call_set_cutoffs", "pf_call_peek", "pf_call_text_range", "pf_call_align_lane", "pf_call_text_range_lane", "pf_call_text_sizes", "pf_call_fetch", "pf_call_fetch_slab", "pf_call_fetch_range", "pf_call_fetch_wait", "pf_format_doubles",
                     "pf_gmm_values", "pf_call_model_begin", "pf_call_model_take", "pf_call_model_finish", "pf_call_fetched_bytes",
                     "pf_call_model_filter", "pf_call_model_take_text",
-                    "pf_call_model_filter_multi", "pf_call_model_color_count", "pf_call_model_color_select"]
+                    "pf_call_model_filter_multi", "pf_call_model_color_count", "pf_call_model_color_select",
+                    "pf_gmm_density"]
+
+
+def density_dict(x: np.ndarray, density: np.ndarray, info: np.ndarray) -> dict:
+    """grid, curve and pf_density_info record as the dict the Python layers return"""
+    r = info[0]
+    return {"x": x, "density": density, "bw": float(r["bw"]), "n": int(r["n"]), "min": float(r["min"]), "max": float(r["max"]),
+            "sd": float(r["sd"]), "q1": float(r["q1"]), "q3": float(r["q3"]), "order": np.array(r["order"], dtype=np.float64)}
 
 
 def call_peek(ctx_handle, lane: int = 0):

@@ -36,7 +36,9 @@ DECLARED_SYMBOLS = ["pfh_open", "pfh_close", "pfh_last_error", "pfh_set_output_d
                     "pfh_set_model", "pfh_model_values", "pfh_model_fit", "pfh_model_ploidy", "pfh_text_bytes_fetched", "pfh_model_rows",
                     "pfh_set_filter", "pfh_filter_rows",
                     "pfh_set_filter_multi", "pfh_filter_rows_multi", "pfh_model_color_count", "pfh_model_color_at", "pfh_model_color_values",
-                    "pfh_model_color_fit", "pfh_model_color_ploidy"]
+                    "pfh_model_color_fit", "pfh_model_color_ploidy",
+                    "pfh_gmm_read_column", "pfh_gmm_density", "pfh_gmm_write_density", "pfh_gmm_density_time",
+                    "pfh_set_density", "pfh_model_density_points", "pfh_model_density", "pfh_model_color_density"]
 
 
 class FilterOpts(C.Structure):   # pf_filter_opts (include/ploidyfrost_hip.h)
@@ -169,6 +171,11 @@ def load_library() -> C.CDLL:
     L.pfh_model_color_fit.argtypes = [vp, C.c_int, u32, vp, vp, vp, C.POINTER(d), C.POINTER(d), C.POINTER(u32)]
     L.pfh_model_color_ploidy.restype = d
     L.pfh_model_color_ploidy.argtypes = [vp, C.c_int]
+    L.pfh_set_density.argtypes = [vp, u32, d]
+    L.pfh_model_density_points.restype = u32
+    L.pfh_model_density_points.argtypes = [vp, C.c_int]
+    L.pfh_model_density.argtypes = [vp, vp, vp, vp]
+    L.pfh_model_color_density.argtypes = [vp, C.c_int, vp, vp, vp]
     _lib = L
     return L
 
@@ -438,6 +445,30 @@ class Run:
         o = filter_opts(simple, low, up, indel, snp, num, distance, size, frequency)
         self._check(self.L.pfh_set_filter(self.h, C.byref(o)))
 
+    def set_density(self, points: int = 512, adjust: float = 1.0):
+        """After set_model: the next ploidy_estimation also takes the Gaussian kernel density (ggplot2's geom_density defaults: bw.nrd0,
+        `points` abscissae over [min, max]; the exact sum, on the device) of the array every fit reads, right after that fit, and
+        writes <outpre>_allele_frequency_density.txt (split by colour: <outpre>_color<c>_allele_frequency_density.txt) beside the
+        model result.  points=0 (or None) switches it off, as set_model(None) does."""
+        self._check(self.L.pfh_set_density(self.h, int(points or 0), float(adjust)))
+
+    def _density(self, color: int) -> dict:
+        n = int(self.L.pfh_model_density_points(self.h, color))
+        if n == 0:
+            raise KeyError("the last ploidy_estimation took no density" + (" of colour %d" % color if color >= 0 else ""))
+        x, den, info = np.zeros(n), np.zeros(n), np.zeros(1, dtype=hipapi.DENSITY_INFO)
+        if color < 0:
+            rc = self.L.pfh_model_density(self.h, x.ctypes.data, den.ctypes.data, info.ctypes.data)
+        else:
+            rc = self.L.pfh_model_color_density(self.h, color, x.ctypes.data, den.ctypes.data, info.ctypes.data)
+        if rc != 0:
+            raise KeyError("the last ploidy_estimation took no density")
+        return hipapi.density_dict(x, den, info)
+
+    def model_density(self) -> dict:
+        """the density the last ploidy_estimation took (set_density): what Gmm.density returns"""
+        return self._density(-1)
+
     def model_values(self) -> np.ndarray:
         """the array K-GMM fitted in the last ploidy_estimation, copied from the device"""
         n = self.L.pfh_model_values(self.h, None, 0)
@@ -598,6 +629,10 @@ class ColoredRun(Run):
             self.L.pfh_model_color_values(self.h, int(color), out.ctypes.data, n)
         return out
 
+    def model_density(self, color=None) -> dict:
+        """Run.model_density; color=c: the density of that colour's array after a ploidy_estimation split by colour"""
+        return self._density(-1 if color is None else int(color))
+
     def model_result(self, color=None) -> dict:
         """Run.model_result; color=c: the fits of that colour after a ploidy_estimation split by colour"""
         if color is None:
@@ -641,6 +676,10 @@ class Gmm:
         L.pfh_gmm_fit.argtypes = [vp, C.c_uint32, d, d, C.c_int32, d, vp, vp, vp, C.POINTER(d), C.POINTER(d), C.POINTER(C.c_uint32)]
         L.pfh_gmm_run.argtypes = [vp, C.c_int, C.c_int, d, d, C.c_int32, d, C.c_char_p]
         L.pfh_gmm_kernel_time.argtypes = [vp, C.c_int, C.POINTER(d), C.POINTER(C.c_uint64)]
+        L.pfh_gmm_read_column.argtypes = [vp, C.c_char_p]
+        L.pfh_gmm_density.argtypes = [vp, C.c_uint32, d, vp, vp, vp]
+        L.pfh_gmm_write_density.argtypes = [vp, C.c_char_p, vp, C.c_uint32, vp, vp]
+        L.pfh_gmm_density_time.argtypes = [vp, C.POINTER(d), C.POINTER(C.c_uint64)]
         self.h = L.pfh_gmm_open(device)
         if not self.h:
             raise RuntimeError(L.pfh_gmm_last_error(None).decode())
@@ -661,6 +700,41 @@ class Gmm:
 
     def read_cov(self, prefix, min_frequency=0.0):
         self._check(self.L.pfh_gmm_read_cov(self.h, prefix.encode(), min_frequency))
+
+    def read_column(self, path):
+        """a plain column of numbers (what script/Drawfreq.R reads): blank lines and lines beginning with '#' are skipped, every
+        other line is one finite number or is refused with its line number"""
+        self._check(self.L.pfh_gmm_read_column(self.h, str(path).encode()))
+
+    def density(self, points=512, adjust=1.0) -> dict:
+        """The Gaussian kernel density of the values, on the GPU: ggplot2's geom_density defaults (bandwidth adjust * bw.nrd0,
+        `points` abscissae from min to max), the exact sum in fp64 (R bins onto 1024 cells and convolves by FFT: its numbers differ
+        by that binning error).  {"x", "density", "bw", "n", "min", "max", "sd", "q1", "q3", "order"}; order = x(lo), x(lo+1) of
+        Q(0.25), then of Q(0.75).  RuntimeError: fewer than two values, a value that is not finite, points or adjust out of range."""
+        if not 0 <= int(points) < 2 ** 32:
+            raise RuntimeError("density: %d points: the grid holds %d to %d" % (points, hipapi.DENSITY_MIN_POINTS, hipapi.DENSITY_MAX_POINTS))
+        n = min(max(int(points), 1), hipapi.DENSITY_MAX_POINTS)
+        x, den, info = np.zeros(n), np.zeros(n), np.zeros(1, dtype=hipapi.DENSITY_INFO)
+        self._check(self.L.pfh_gmm_density(self.h, int(points), float(adjust), x.ctypes.data, den.ctypes.data, info.ctypes.data))
+        return hipapi.density_dict(x, den, info)
+
+    def write_density(self, outprefix, dens: dict) -> str:
+        """<outprefix>_allele_frequency_density.txt from what density() returned: "# values N bandwidth BW points P", then P rows
+        x<TAB>density, every number %.17g; returns the file's name"""
+        x = np.ascontiguousarray(dens["x"], dtype=np.float64)
+        den = np.ascontiguousarray(dens["density"], dtype=np.float64)
+        if x.shape != den.shape or x.ndim != 1:
+            raise ValueError("x and density are two columns of one length")
+        info = np.zeros(1, dtype=hipapi.DENSITY_INFO)
+        info[0]["n"], info[0]["bw"] = int(dens["n"]), float(dens["bw"])
+        self._check(self.L.pfh_gmm_write_density(self.h, str(outprefix).encode(), info.ctypes.data, len(x), x.ctypes.data, den.ctypes.data))
+        return str(outprefix) + "_allele_frequency_density.txt"
+
+    def density_time(self):
+        """(milliseconds, launches) of the density calls since enable_timing()"""
+        ms, n = C.c_double(), C.c_uint64()
+        self._check(self.L.pfh_gmm_density_time(self.h, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
 
     def set_values(self, v):
         import numpy as np
