@@ -63,6 +63,7 @@ enum pf_kernel {
     PF_K_COPY_TEXT, /* not a kernel of this library: the copies of result text to the host (the runtime moves them with a kernel of its own) */
     PF_K_CALL_MODEL, /* the kernels of one pf_call_model_take (rows of a piece's text -> the model's values), timed as one launch */
     PF_K_DENSITY, /* the kernels of one pf_gmm_density, timed as one launch; unit: values x grid points */
+    PF_K_HIST, /* K-HIST (pf_count_histogram); unit: counters */
     PF_K_COUNT_
 };
 int pf_enable_timing(pf_ctx *, int on);
@@ -144,6 +145,13 @@ int pf_minimizer_replay_inputs(pf_ctx *, int g, uint32_t limit, uint8_t *counter
 int pf_kmc_decode(pf_ctx *, const uint8_t *records, uint64_t n_records, uint32_t suffix_bytes, uint32_t counter_bytes,
                   const uint64_t *lut, uint64_t n_lut, uint32_t lut_prefix_len, uint32_t k, uint64_t **kmers_dev, uint32_t **counts_dev);
 void pf_device_free(pf_ctx *, void *device_pointer);
+/* K-HIST: the k-mer histogram of a database from the counters pf_kmc_decode left on the device -- the file the reference's
+ * cutoffL / cutoffU / -h read (src/Main.cpp:200-277) and step 1 of its workflow makes with a second tool and a second pass over the
+ * database (`kmc_tools transform <db> histogram <file>`).  For every counts[i] with lo <= counts[i] <= hi:
+ * hist[min(counts[i], n_bins - 1)] += 1; every other bin is 0 (n = 0 or lo > hi: all of them).  Integers only: the same bits on
+ * every call.  n_bins from 1 to PF_HIST_MAX_BINS, else PF_ERR_ARG.  counts, hist: [host|dev] */
+#define PF_HIST_MAX_BINS (1u << 20)
+int pf_count_histogram(pf_ctx *, const uint32_t *counts, uint64_t n, uint64_t lo, uint64_t hi, uint32_t n_bins, uint64_t *hist);
 int pf_copy_to_host(pf_ctx *, void *dst, const void *src_dev, size_t bytes);
 
 /* K1/K2: builds the device hash table from the database records (exact k-mers as stored, any

@@ -61,6 +61,24 @@ void pfh_set_align_pieces(pfh_run *, uint64_t n);   /* bubbles per batch of the 
 int pfh_set_unitig_id(pfh_run *, const char *outpre);
 int pfh_find_superbubbles(pfh_run *, const char *outpre);
 int pfh_ploidy_estimation(pfh_run *, const char *outpre, int lower, int upper);
+/* ---- the coverage thresholds from the database itself (K-HIST, pf_count_histogram in ploidyfrost_hip.h) ----
+ * pfh_kmc_histogram: the rows of the database's k-mer histogram, counted on the device from the decoded counters: row r = the number
+ * of records whose count is *min_count + r, from the header's min_count through min(max_count, 2^(8 counter_size) - 1,
+ * PF_HIST_MAX_BINS - 1), zero rows included; records outside [min_count, max_count] left out, counts above the cap in the last row.
+ * (What `kmc_tools transform <db> histogram` writes as far as can be read without the tool: PARITY UNPINNED.)  At most cap rows are
+ * copied, *n_rows = how many there are.  0 = ok, else pfh_last_error(NULL).
+ * pfh_cutoffs_from_rows: cutoffL / cutoffH of src/Main.cpp:200-277 on the second column of a histogram, in file order: *lower = the
+ * value before the callers' max(10, .), *upper = cutoffH at `quantile`.  0 = ok, 1 = fewer than two rows (the reference's "Histogram
+ * File is badly Formatted."; *lower is set, *upper is not), 2 = a missing argument.  No device involved.
+ * pfh_set_auto_cutoffs: the run derives its thresholds from its own database(s) -- a colored run one pair per colour -- on its
+ * device context: max(10, lower), upper at `quantile`, with the checks of -h (lower <= upper); pfh_ploidy_estimation /
+ * pfh_ploidy_estimation_colored then use them instead of their arguments.  quantile < 0: off again.
+ * pfh_cutoffs: the pairs the last estimation used (before one: those pfh_set_auto_cutoffs derived); returns how many there are and
+ * copies at most cap of them. */
+int pfh_kmc_histogram(const char *kmc_prefix, uint64_t *rows_out, uint64_t cap, uint64_t *n_rows, uint64_t *min_count);
+int pfh_cutoffs_from_rows(const uint64_t *rows, uint64_t n, double quantile, int *lower, int *upper);
+int pfh_set_auto_cutoffs(pfh_run *, double quantile);
+uint32_t pfh_cutoffs(const pfh_run *, int *lower, int *upper, uint32_t cap);
 void pfh_get_times(const pfh_run *, pfh_times *out);
 /* Where the loads of this process spent their time (GFA map / parse / upload, count database, join, adjacency, numbering, ...):
  * "step\tseconds\n" per step since the last reset, in the order the steps ended (steps of helper threads overlap those of the

@@ -16,6 +16,7 @@
 #include <thread>
 
 #include "pf_cdbg_impl.hpp"
+#include "pf_cutoffs.hpp"
 #include "pf_parallel.hpp"
 
 namespace pfh {
@@ -35,7 +36,7 @@ bool ColoredUnitigSet::read(const std::string &graphfile, const std::string &col
 bool ColoredUnitigSet::reload_colors() { return colors.load(colorfile_, graph, color_threads_, err); }
 
 CCDBG::CCDBG(ColoredUnitigSet &graph, const size_t &complexsize, double &m, double &d, double &g, std::string kmc_db_list,
-             const size_t &thread, int device, bool quiet)
+             const size_t &thread, int device, bool quiet, std::vector<std::vector<uint64_t>> *rows_out)
     : CDBG(graph.graph, complexsize, m, d, g, device, quiet, NoCounts{}), cg_(graph) {
     if (status_) return;
     if (cg_.graph.n_abundant && !cg_.reload_colors()) { fail(PF_ERR_ARG, "CCDBG::CCDBG():Error: " + cg_.err); return; }
@@ -81,9 +82,11 @@ CCDBG::CCDBG(ColoredUnitigSet &graph, const size_t &complexsize, double &m, doub
         std::vector<uint64_t> n(C), mn(C), mx(C);
         std::vector<int> both(C);
         int st = PF_OK;
+        if (rows_out) rows_out->assign(C, {});
         for (uint32_t c = 0; c < C && st == PF_OK; ++c) {
             st = pf_kmc_decode(ctx_, dbs[c].records, dbs[c].total, dbs[c].suffix_bytes, dbs[c].counter_size, dbs[c].lut.data(), dbs[c].n_lut(),
                                dbs[c].lut_prefix_len, dbs[c].k, &pk[c], &pc[c]);
+            if (st == PF_OK && rows_out) st = kmc_rows_of_counts(ctx_, dbs[c], pc[c], (*rows_out)[c]);
             n[c] = dbs[c].total;
             mn[c] = dbs[c].min_count;
             mx[c] = dbs[c].max_count;

@@ -19,6 +19,7 @@
 #include <thread>
 
 #include "pf_cdbg_impl.hpp"
+#include "pf_cutoffs.hpp"
 #include "pf_parallel.hpp"
 #include "pf_trace.hpp"
 
@@ -92,6 +93,10 @@ void CountsLoader::start(int device, const std::string &kmc_prefix) {
         uint64_t *dk = nullptr;
         uint32_t *dc = nullptr;
         status = pf_kmc_decode(ctx, db.records, db.total, db.suffix_bytes, db.counter_size, db.lut.data(), db.n_lut(), db.lut_prefix_len, db.k, &dk, &dc);
+        if (status == PF_OK && want_rows) {
+            rows_min_count = db.min_count;
+            status = kmc_rows_of_counts(ctx, db, dc, rows);
+        }
         if (status == PF_OK) status = pf_upload_counts(ctx, dk, dc, db.total, db.k, db.min_count, db.max_count, db.both_strands);
         pf_device_free(ctx, dk);
         pf_device_free(ctx, dc);

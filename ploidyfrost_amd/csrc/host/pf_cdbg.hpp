@@ -68,6 +68,11 @@ struct CountsLoader {
     std::string error;
     bool both_strands = true;
     int k = 0;
+    // set before start(): the rows of the database's k-mer histogram (pf_cutoffs.hpp) are counted from the decoded counters before
+    // they are freed (K-HIST); off: nothing more is launched or allocated
+    bool want_rows = false;
+    std::vector<uint64_t> rows;
+    uint64_t rows_min_count = 0;
     void wait() { if (th_.joinable()) th_.join(); }
     pf_ctx *release() { pf_ctx *c = ctx; ctx = nullptr; return c; }
     // the context as soon as it exists (the count table is still on its way): nullptr when its creation failed.  Only calls
@@ -422,8 +427,10 @@ private:
 // HBM table (include/ploidyfrost_hip.h, pf_upload_counts_colored).
 class CCDBG : public CDBG {
 public:
+    // rows_out: the rows of every database's k-mer histogram (pf_cutoffs.hpp), one vector per colour, counted from the decoded
+    // counters of each (K-HIST); null: nothing more is launched or allocated
     CCDBG(ColoredUnitigSet &graph, const size_t &complexsize, double &m, double &d, double &g, std::string kmc_db_list = "",
-          const size_t &thread = 1, int device = 0, bool quiet = false);
+          const size_t &thread = 1, int device = 0, bool quiet = false, std::vector<std::vector<uint64_t>> *rows_out = nullptr);
     int ploidyEstimation_multithread_ptr(const std::string &outpre, const std::vector<std::pair<int, int>> &cutoff, const size_t &thr);
 
 private:

@@ -7,6 +7,7 @@
 
 #include "pf_bfs_host.hpp"
 #include "pf_cdbg.hpp"
+#include "pf_cutoffs.hpp"
 #include "pf_trace.hpp"
 #include "../pf_model_rows.hpp"
 #include "../pf_filter_rows.hpp"
@@ -26,6 +27,11 @@ struct pfh_run {
     size_t z = 8;
     double load_s = 0, upload_s = 0;
     std::string err;
+    // pfh_set_auto_cutoffs: the database prefix (colored runs: the list file), the thresholds derived from it, and those the last
+    // estimation used
+    std::string kmc;
+    bool auto_cutoffs = false;
+    std::vector<std::pair<int, int>> auto_cut, used_cut;
 };
 
 static std::string g_open_err;
@@ -81,6 +87,7 @@ pfh_run *pfh_open(const char *gfa_path, const char *kmc_prefix, uint32_t complex
     r->cdbg = std::make_unique<pfh::CDBG>(r->graph, r->z, r->z_M, r->z_D, r->z_G, kmc_prefix ? kmc_prefix : "", device, true);
     r->upload_s = std::chrono::duration<double>(clk::now() - t0).count();
     if (!r->cdbg->good()) { g_open_err = r->cdbg->error(); return nullptr; }
+    r->kmc = kmc_prefix ? kmc_prefix : "";
     return r.release();
     } catch (const std::exception &e) {
         g_open_err = std::string("ploidyfrost host layer: ") + e.what();
@@ -106,6 +113,7 @@ pfh_run *pfh_open_colored(const char *gfa_path, const char *colors_path, const c
         if (!cc->good()) { g_open_err = cc->error(); return nullptr; }
         r->ccdbg = cc.get();
         r->cdbg = std::move(cc);
+        r->kmc = kmc_list_file ? kmc_list_file : "";
         return r.release();
     } catch (const std::exception &e) {
         g_open_err = std::string("ploidyfrost host layer: ") + e.what();
@@ -119,7 +127,9 @@ int pfh_ploidy_estimation_colored(pfh_run *r, const char *outpre, const int *low
     if (!r->ccdbg) { r->err = "pfh_ploidy_estimation_colored: the run was not opened with pfh_open_colored"; return PF_ERR_ARG; }
     return guarded(r, [&] {
         std::vector<std::pair<int, int>> cut(n_colors);
-        for (uint32_t c = 0; c < n_colors; ++c) cut[c] = {lower[c], upper[c]};
+        if (r->auto_cutoffs) cut = r->auto_cut;
+        else for (uint32_t c = 0; c < n_colors; ++c) cut[c] = {lower[c], upper[c]};
+        r->used_cut = cut;
         return r->ccdbg->ploidyEstimation_multithread_ptr(outpre, cut, 1);
     });
 }
@@ -146,7 +156,84 @@ int pfh_find_superbubbles(pfh_run *r, const char *outpre) {
     return guarded(r, [&] { return r->cdbg->findSuperBubble_multithread_ptr(outpre, 1); });
 }
 int pfh_ploidy_estimation(pfh_run *r, const char *outpre, int lower, int upper) {
-    return guarded(r, [&] { return r->cdbg->ploidyEstimation_multithread_ptr(outpre, lower, upper, 1); });
+    return guarded(r, [&] {
+        if (r->auto_cutoffs && !r->auto_cut.empty()) { lower = r->auto_cut[0].first; upper = r->auto_cut[0].second; }
+        r->used_cut.assign(1, {lower, upper});
+        return r->cdbg->ploidyEstimation_multithread_ptr(outpre, lower, upper, 1);
+    });
+}
+
+// ---- thresholds from the database itself (K-HIST) ---------------------------------------------------
+int pfh_kmc_histogram(const char *kmc_prefix, uint64_t *rows_out, uint64_t cap, uint64_t *n_rows, uint64_t *min_count) {
+    if (!kmc_prefix || !n_rows) { g_open_err = "pfh_kmc_histogram: prefix and n_rows are needed"; return 1; }
+    try {
+        std::vector<uint64_t> rows;
+        uint64_t mn = 0;
+        if (pfh::kmc_histogram(kmc_prefix, 0, rows, mn, g_open_err)) return 1;
+        *n_rows = rows.size();
+        if (min_count) *min_count = mn;
+        if (rows_out) std::copy(rows.begin(), rows.begin() + (size_t)std::min<uint64_t>(cap, rows.size()), rows_out);
+        return 0;
+    } catch (const std::exception &e) {
+        g_open_err = std::string("ploidyfrost host layer: ") + e.what();
+        return 1;
+    }
+}
+int pfh_cutoffs_from_rows(const uint64_t *rows, uint64_t n, double quantile, int *lower, int *upper) {
+    if ((n && !rows) || !lower || !upper) return 2;
+    int lo = 0, up = 0;
+    const int rc = pfh::cutoffs_from_rows(std::vector<uint64_t>(rows, rows + n), quantile, lo, up);
+    *lower = lo;
+    if (!rc) *upper = up;
+    return rc;
+}
+int pfh_set_auto_cutoffs(pfh_run *r, double quantile) {
+    return guarded(r, [&] {
+        r->auto_cutoffs = false;
+        r->auto_cut.clear();
+        r->used_cut.clear();
+        if (quantile < 0) return (int)PF_OK;
+        if (quantile > 1) { r->err = "Error: frequency cutoff value should be between 0 and 1 "; return (int)PF_ERR_ARG; }
+        std::vector<std::string> names;
+        if (r->ccdbg) {   // one database name per line, one line per colour (src/CCDBG.cpp:13-43)
+            FILE *f = fopen(r->kmc.c_str(), "r");
+            if (!f) { r->err = "pfh_set_auto_cutoffs: cannot read the database list " + r->kmc; return (int)PF_ERR_ARG; }
+            std::string cur;
+            int ch;
+            while ((ch = fgetc(f)) != EOF) {
+                if (ch == '\n') { names.push_back(cur); cur.clear(); }
+                else cur.push_back((char)ch);
+            }
+            if (!cur.empty()) names.push_back(cur);
+            fclose(f);
+            names.resize(r->cgraph->getNbColors());
+        } else {
+            if (r->kmc.empty()) { r->err = "pfh_set_auto_cutoffs: the run was opened without a database"; return (int)PF_ERR_ARG; }
+            names.push_back(r->kmc);
+        }
+        std::vector<std::pair<int, int>> cut;
+        for (const std::string &name : names) {
+            std::vector<uint64_t> rows;
+            uint64_t mn = 0;
+            if (pfh::kmc_rows(r->cdbg->device(), name, rows, mn, r->err)) return (int)PF_ERR_ARG;
+            int lo = 0, up = 0;
+            if (pfh::cutoffs_from_rows(rows, quantile, lo, up)) { r->err = "Error: Histogram File is badly Formatted."; return (int)PF_ERR_ARG; }
+            lo = std::max(10, lo);
+            if (lo > up) { r->err = "Error: lower cutoff need be smaller than upper cutoff "; return (int)PF_ERR_ARG; }
+            cut.push_back({lo, up});
+        }
+        r->auto_cut = cut;
+        r->auto_cutoffs = true;
+        return (int)PF_OK;
+    });
+}
+uint32_t pfh_cutoffs(const pfh_run *r, int *lower, int *upper, uint32_t cap) {
+    const std::vector<std::pair<int, int>> &v = !r->used_cut.empty() ? r->used_cut : r->auto_cut;
+    for (uint32_t c = 0; c < cap && c < v.size(); ++c) {
+        if (lower) lower[c] = v[c].first;
+        if (upper) upper[c] = v[c].second;
+    }
+    return (uint32_t)v.size();
 }
 void *pfh_device_ctx(pfh_run *r) { return r->cdbg->device(); }
 

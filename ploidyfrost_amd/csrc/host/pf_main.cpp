@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "pf_cdbg.hpp"
+#include "pf_cutoffs.hpp"
 #include "pf_filter.hpp"
 #include "pf_multi.hpp"
 #include "pf_gmm_model.hpp"
@@ -59,6 +60,8 @@ void PrintUsage() {
          << "  -i,             Output Information about Bifrost graph" << endl << endl
          << "  -h,             k-mer histogram file (with -f: a list of them): thresholds = cutoffL / cutoffU of it" << endl
          << "  -q,             quantile for the upper threshold derived from -h (default : 0.998 )" << endl
+         << "  --auto-cutoffs  thresholds = cutoffL / cutoffU (quantile -q) of the k-mer histogram of the database itself (with -f: of every" << endl
+         << "                  colour's), counted on the device while it is loaded; instead of -h, -C, -l, -u" << endl
          << "  --ref-threads N N > 1: text format of the reference's `-t N` run (ids from 0, allele_frequency grouped by arity)" << endl
          << "  --gpus N        one graph over N GPUs of this node (single-sample path): one process per GPU, the bubble list cut into N slices," << endl
          << "                  two small all-gathers over RCCL, every rank writes its slabs into the shared result files" << endl
@@ -79,48 +82,54 @@ void PrintUsage() {
          << "                  numbers), <prefix>_allele_frequency_density.txt; with --model-each-color one file per fitted colour" << endl
          << "  --density-points N, --density-adjust A   grid points (default 512, 2 to 4096) and bandwidth factor (default 1)" << endl << endl
          << "Usage: PloidyFrost cutoffL kmer_histogram_file" << endl
-         << "Usage: PloidyFrost cutoffU kmer_histogram_file (quantile[<1 ,default:0.998])" << endl << endl
+         << "Usage: PloidyFrost cutoffU kmer_histogram_file (quantile[<1 ,default:0.998])" << endl
+         << "Usage: PloidyFrost cutoffL -d <KMCDatabase>" << endl
+         << "Usage: PloidyFrost cutoffU -d <KMCDatabase> (quantile[<1 ,default:0.998])" << endl
+         << "Usage: PloidyFrost histogram -d <KMCDatabase> [-o <file>]   (the k-mer histogram file of the database, count<TAB>number per row)" << endl << endl
          << "Usage: PloidyFrost model ...          (GMM ploidy inference from the coverage / frequency files; `PloidyFrost model` prints its options)" << endl
          << "Usage: PloidyFrost density -f <column file> -o <outfile_prefix> [-n points] [-a adjust]   (kernel density of a column of numbers)" << endl
          << "Usage: PloidyFrost filter ...         (the row predicates of script/Filter.R over <prefix>_*cov.txt; -h prints its options)" << endl
          << "Usage: PloidyFrost filter-multi ...   (script/Filter-multi.R: the colored tables, with -c colour and -v Cramer's V)" << endl;
 }
 
-// lower threshold: 1.25 x the position of the first local minimum of the histogram (src/Main.cpp:200-235)
-int cutoffL(const string &file) {
+// the second column of a histogram file, in file order (the parsing of src/Main.cpp:202-225, 238-261)
+vector<uint64_t> histogram_rows(const string &file) {
     ifstream f(file);
     if (!f.is_open()) { cout << "ERROR:Open Histogram File " << file << " error!" << endl; exit(EXIT_FAILURE); }
-    vector<size_t> v;
+    vector<uint64_t> v;
     string s;
     while (getline(f, s, '\n')) {
         const size_t pos1 = s.find("\t");
         if (pos1 == string::npos) { cerr << "Error: Histogram File is badly Formatted." << endl; exit(EXIT_FAILURE); }
-        v.emplace_back((size_t)atoll(s.substr(pos1 + 1).c_str()));
+        v.emplace_back((uint64_t)(size_t)atoll(s.substr(pos1 + 1).c_str()));
     }
-    size_t peak;
-    for (peak = 1; peak < v.size(); peak++)
-        if (v[peak - 1] < v[peak]) break;
-    return int(round(1.25 * ((double)peak - 1)));
+    return v;
 }
 
+// lower threshold: 1.25 x the position of the first local minimum of the histogram (src/Main.cpp:200-235)
+int cutoffL(const vector<uint64_t> &rows) {
+    int lower = 0, upper = 0;
+    (void)pfh::cutoffs_from_rows(rows, 0.998, lower, upper);
+    return lower;
+}
+int cutoffL(const string &file) { return cutoffL(histogram_rows(file)); }
+
 // upper threshold: the multiplicity below which `frequency` of the k-mers beyond the first bin lie (src/Main.cpp:236-277)
-int cutoffH(const string &file, double frequency = 0.998) {
-    ifstream f(file);
-    if (!f.is_open()) { cout << "ERROR:Open Histogram File " << file << " error!" << endl; exit(EXIT_FAILURE); }
-    vector<size_t> v;
-    v.emplace_back(0);
-    string s;
-    while (getline(f, s, '\n')) {
-        const size_t pos1 = s.find("\t");
-        if (pos1 == string::npos) { cerr << "Error: Histogram File is badly Formatted." << endl; exit(EXIT_FAILURE); }
-        v.emplace_back((size_t)atoll(s.substr(pos1 + 1).c_str()) + v.back());
-    }
-    if (v.size() <= 2) { cerr << "Error: Histogram File is badly Formatted." << endl; exit(EXIT_FAILURE); }
-    const size_t cf = (size_t)(frequency * (double)(v.back() - v[1]) + (double)v[1]);
-    size_t peak;
-    for (peak = 2; peak < v.size(); peak++)
-        if (v[peak] > cf) break;
-    return (int)peak;
+int cutoffH(const vector<uint64_t> &rows, double frequency = 0.998) {
+    int lower = 0, upper = 0;
+    if (pfh::cutoffs_from_rows(rows, frequency, lower, upper)) { cerr << "Error: Histogram File is badly Formatted." << endl; exit(EXIT_FAILURE); }
+    return upper;
+}
+int cutoffH(const string &file, double frequency = 0.998) { return cutoffH(histogram_rows(file), frequency); }
+
+// the rows of a database's k-mer histogram, counted on the device (K-HIST); leaves with the reason when that fails
+vector<uint64_t> database_rows(const string &db, uint64_t *min_count = nullptr) {
+    vector<uint64_t> rows;
+    uint64_t mn = 0;
+    string err;
+    if (pfh::kmc_histogram(db, 0, rows, mn, err)) { cout << "ERROR: " << err << endl; exit(EXIT_FAILURE); }
+    if (min_count) *min_count = mn;
+    return rows;
 }
 
 struct Options {
@@ -133,6 +142,7 @@ struct Options {
     // --model ...: the estimate in the same run
     string model_source, model_ploidy = "1:9";
     bool model_only = false, model_option_seen = false, filter_seen = false, multi_seen = false, each_color = false;
+    bool auto_cutoffs = false, l_seen = false, u_seen = false, cfile_seen = false;   // --auto-cutoffs and what it does not go with
     string filter_words;   // --filter "<options of `ploidyfrost filter`>"
     string multi_words;    // --filter-multi "<options of `ploidyfrost filter-multi`>"
     double model_q = 0, model_m = 5.0, model_n = 2.0, model_delta = 0.01;
@@ -476,6 +486,38 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[1], "density")) return density_main(argc - 1, argv + 1);
     if (!strcmp(argv[1], "filter")) return pfh::filter_main(argc, argv, false);         // script/Filter.R
     if (!strcmp(argv[1], "filter-multi")) return pfh::filter_main(argc, argv, true);    // script/Filter-multi.R
+    if (!strcmp(argv[1], "histogram")) {   // the file `kmc_tools transform <db> histogram <file>` writes, from the database on the device
+        string db, out;
+        for (int i = 2; i < argc; ++i) {
+            if (!strcmp(argv[i], "-d") && i + 1 < argc) db = argv[++i];
+            else if (!strcmp(argv[i], "-o") && i + 1 < argc) out = argv[++i];
+            else { db.clear(); break; }
+        }
+        if (db.empty()) { cout << "Usage:PloidyFrost histogram -d kmc_database [-o kmer_histogram_file]" << endl; exit(EXIT_FAILURE); }
+        uint64_t min_count = 0;
+        const vector<uint64_t> rows = database_rows(db, &min_count);
+        const string text = pfh::histogram_text(min_count, rows);
+        if (out.empty()) { cout << text; return 0; }
+        ofstream f(out, std::ios::binary);
+        if (!f.is_open() || !(f << text) || !f.flush()) { cout << "ERROR:Write Histogram File " << out << " error!" << endl; exit(EXIT_FAILURE); }
+        return 0;
+    }
+    if (!strcmp(argv[1], "cutoffL") && argc == 4 && !strcmp(argv[2], "-d")) {   // the same from the database itself
+        cout << max(10, cutoffL(database_rows(argv[3]))) << endl;
+        return 0;
+    }
+    if (!strcmp(argv[1], "cutoffU") && (argc == 4 || argc == 5) && !strcmp(argv[2], "-d")) {
+        const char *usage = "Usage:PloidyFrost cutoffU -d kmc_database (quantile[<1 ,default:0.998]) ";
+        if (argc == 4) {
+            cout << cutoffH(database_rows(argv[3])) << endl;
+        } else {
+            double y;
+            try { y = stod(argv[4]); } catch (const exception &) { cout << usage << endl; exit(EXIT_FAILURE); }
+            if (y >= 1) { cout << usage << endl; exit(EXIT_FAILURE); }
+            cout << cutoffH(database_rows(argv[3]), y);
+        }
+        return 0;
+    }
     if (!strcmp(argv[1], "cutoffL")) {  // src/Main.cpp:721-730
         if (argc != 3) { cout << "Usage:PloidyFrost cutoffL kmer_histogram_file" << endl; exit(EXIT_FAILURE); }
         cout << max(10, cutoffL(argv[2])) << endl;
@@ -522,8 +564,9 @@ int main(int argc, char **argv) {
             for (int j = i; j + 1 <= argc; ++j) argv[j] = j + 1 < argc ? argv[j + 1] : nullptr;
             argc -= 1;
             --i;
-        } else if (strcmp(argv[i], "--model-each-color") == 0) {
-            opt.each_color = true;
+        } else if (strcmp(argv[i], "--model-each-color") == 0 || strcmp(argv[i], "--auto-cutoffs") == 0) {
+            if (argv[i][2] == 'a') opt.auto_cutoffs = true;
+            else opt.each_color = true;
             for (int j = i; j + 1 <= argc; ++j) argv[j] = j + 1 < argc ? argv[j + 1] : nullptr;
             argc -= 1;
             --i;
@@ -562,13 +605,13 @@ int main(int argc, char **argv) {
             case 'M': opt.match = atof(optarg); break;
             case 'D': opt.mismatch = atof(optarg); break;
             case 'G': opt.gap = atof(optarg); break;
-            case 'u': opt.coverage_upper = atoi(optarg);  // falls through, as in the reference (:149-153)
-            case 'C': opt.coveragefile = optarg; break;
+            case 'u': opt.coverage_upper = atoi(optarg); opt.u_seen = true;  // falls through, as in the reference (:149-153)
+            case 'C': opt.coveragefile = optarg; if (oc == 'C') opt.cfile_seen = true; break;
             case 'h': opt.hist = optarg; break;
             case 'g': opt.graphfile = optarg; break;
             case 'f': opt.colorfile = optarg; break;
             case 'o': opt.outprefix = optarg; break;
-            case 'l': opt.coverage_lower = atoi(optarg); break;
+            case 'l': opt.coverage_lower = atoi(optarg); opt.l_seen = true; break;
             case 't': opt.nb_threads = (size_t)atoi(optarg); break;
             case 'k': opt.k = atoi(optarg); break;
             case 'v': opt.verbose = true; break;
@@ -581,6 +624,17 @@ int main(int argc, char **argv) {
                 PrintUsage();
                 exit(EXIT_FAILURE);
         }
+    }
+    // --auto-cutoffs: the thresholds come from the database itself; every other source of them is refused by name, before anything
+    // is read or written
+    if (opt.auto_cutoffs) {
+        const char *with = !opt.hist.empty() ? "-h (one source of thresholds a run: the histogram file or the database)"
+                         : opt.cfile_seen ? "-C (one source of thresholds a run: the coverage file or the databases)"
+                         : opt.l_seen ? "-l (the lower threshold is derived: leave it out)"
+                         : opt.u_seen ? "-u (the upper threshold is derived: leave it out)" : nullptr;
+        if (with) { cerr << "Error: --auto-cutoffs does not go with " << with << endl; return 1; }
+        if (opt.gpus > 1) { cerr << "Error: --auto-cutoffs and --gpus " << opt.gpus << " do not go together (every rank would count the whole database)" << endl; return 1; }
+        opt.coveragefile.clear();
     }
     // --model: refused here, before anything is read or written
     pfh::CDBG::ModelOptions model;
@@ -721,7 +775,8 @@ int main(int argc, char **argv) {
             cerr << "CCDBG::CCDBG():Error: " << kmc_db_num << " kmc databases listed for " << cdbg.getNbColors() << " colors" << endl;
             exit(EXIT_FAILURE);
         }
-        pfh::CCDBG g(cdbg, opt.complex_size, opt.match, opt.mismatch, opt.gap, opt.db, opt.nb_threads);
+        vector<vector<uint64_t>> color_rows;
+        pfh::CCDBG g(cdbg, opt.complex_size, opt.match, opt.mismatch, opt.gap, opt.db, opt.nb_threads, 0, false, opt.auto_cutoffs ? &color_rows : nullptr);
         if (opt.verbose && cdbg.graph.n_abundant)
             cout << "ColoredCDBG::read(): " << cdbg.graph.n_abundant << " k-length unitigs are abundant k-mers (numbered last, in Bifrost's hash table order)" << endl;
         auto die = [&]() {
@@ -729,6 +784,12 @@ int main(int argc, char **argv) {
             exit(EXIT_FAILURE);
         };
         if (!g.good()) die();
+        if (opt.auto_cutoffs) {   // one (lower, upper) per colour from its own database, as -h derives them from one file per colour (:359-396)
+            for (size_t c = 0; c < color_rows.size() && c < opt.coverage_vec.size(); c++) {
+                opt.coverage_vec[c] = {max(10, cutoffL(color_rows[c])), cutoffH(color_rows[c], opt.frequency)};
+                if (opt.coverage_vec[c].first > opt.coverage_vec[c].second) { cerr << "Error: lower cutoff need be smaller than upper cutoff " << endl; exit(EXIT_FAILURE); }
+            }
+        }
         g.set_threads((unsigned)opt.nb_threads);
         g.set_overlap_output(true);
         if (model.on && g.set_model(model)) die();
@@ -804,6 +865,7 @@ int main(int argc, char **argv) {
     }
     // the device context and the count table are built on a helper thread while the graph file is read
     pfh::CountsLoader counts;
+    counts.want_rows = opt.auto_cutoffs;
     counts.start(ranks.device(), opt.db);
     pfh::UnitigSet graph;
     std::string err;
@@ -850,6 +912,12 @@ int main(int argc, char **argv) {
             if (ranks.rank == 0) (void)ranks.finish();
             _exit(EXIT_FAILURE);
         }
+    }
+    if (opt.auto_cutoffs) {   // as -h sets them from a histogram file (:354-358), with its checks
+        opt.coverage_lower = max(10, cutoffL(counts.rows));
+        opt.coverage_upper = cutoffH(counts.rows, opt.frequency);
+        if (opt.coverage_lower < 0 || opt.coverage_upper < 0) { cerr << "Error: Filter coverage need a positive number." << endl; exit(EXIT_FAILURE); }
+        if (opt.coverage_lower > opt.coverage_upper) { cerr << "Error: lower cutoff need be smaller than upper cutoff " << endl; exit(EXIT_FAILURE); }
     }
     if (!host_gfa) {
         cout << "CompactedDBG::read(): Graph loading successful" << endl;

@@ -24,6 +24,8 @@ KERNELS = ["k_table_build", "k_adj_insert", "k_adj_probe", "k_cov", "k_bfs", "k_
            "k_call_sides", "k_call_prep", "k_call_paths", "k_call_sites", "k_call_format", "k_call_snp", "k_bfs_thread", "k_call_pair", "k_call_stack", "k_cov_join_rest", "copy_text_to_host", "k_call_model"]
 
 K_DENSITY = len(KERNELS)   # PF_K_DENSITY ("k_density"): the kernels of one pf_gmm_density, timed as one launch
+K_HIST = K_DENSITY + 1     # PF_K_HIST ("k_hist"): K-HIST, the histogram of decoded counters (pf_count_histogram)
+HIST_MAX_BINS = 1 << 20
 DENSITY_INFO = np.dtype([("n", "<u8"), ("min", "<f8"), ("max", "<f8"), ("sd", "<f8"), ("q1", "<f8"), ("q3", "<f8"), ("bw", "<f8"),
                          ("order", "<f8", (4,))])   # pf_density_info
 assert DENSITY_INFO.itemsize == 88
@@ -193,6 +195,7 @@ def load_library() -> C.CDLL:
         "pf_call_model_color_count": (C.c_uint32, [vp]),
         "pf_call_model_color_select": (i, [vp, i, C.POINTER(u64)]),
         "pf_gmm_density": (i, [vp, u32, C.c_double, vp, vp, vp]),
+        "pf_count_histogram": (i, [vp, vp, u64, u64, u64, u32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError = header / library mismatch
@@ -214,7 +217,7 @@ DECLARED_SYMBOLS = ["pf_create", "pf_warmup", "pf_destroy", "pf_last_error", "pf
                     "pf_gmm_values", "pf_call_model_begin", "pf_call_model_take", "pf_call_model_finish", "pf_call_fetched_bytes",
                     "pf_call_model_filter", "pf_call_model_take_text",
                     "pf_call_model_filter_multi", "pf_call_model_color_count", "pf_call_model_color_select",
-                    "pf_gmm_density"]
+                    "pf_gmm_density", "pf_count_histogram"]
 
 
 def density_dict(x: np.ndarray, density: np.ndarray, info: np.ndarray) -> dict:
@@ -429,6 +432,23 @@ class Device:
             self.L.pf_device_free(self.h, dk)
             self.L.pf_device_free(self.h, dc)
         return km, ct
+
+    def count_histogram(self, counts, lo: int, hi: int, n_bins: int, out=None):
+        """K-HIST (pf_count_histogram): hist[min(c, n_bins - 1)] += 1 for every counter c with lo <= c <= hi.  counts: u32, a numpy
+        array or a device tensor; out: a device tensor of n_bins int64 to fill instead of a new numpy array."""
+        if isinstance(counts, np.ndarray):
+            counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        n = int(counts.shape[0])
+        hist = np.zeros(max(int(n_bins), 0), dtype=np.uint64) if out is None else out
+        buf = hist if len(hist) else np.zeros(1, dtype=np.uint64)
+        self._check(self.L.pf_count_histogram(self.h, _ptr(counts) if n else None, n, lo, hi, n_bins, _ptr(buf)))
+        return hist
+
+    def kernel_time(self, kernel: int):
+        """(ms, launches) of one kernel of the enum by number (K_DENSITY, K_HIST: not in KERNELS)"""
+        ms, n = C.c_double(), C.c_uint64()
+        self._check(self.L.pf_kernel_time(self.h, kernel, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
 
     def lookup(self, kmers: np.ndarray):
         n = len(kmers)

@@ -38,7 +38,8 @@ DECLARED_SYMBOLS = ["pfh_open", "pfh_close", "pfh_last_error", "pfh_set_output_d
                     "pfh_set_filter_multi", "pfh_filter_rows_multi", "pfh_model_color_count", "pfh_model_color_at", "pfh_model_color_values",
                     "pfh_model_color_fit", "pfh_model_color_ploidy",
                     "pfh_gmm_read_column", "pfh_gmm_density", "pfh_gmm_write_density", "pfh_gmm_density_time",
-                    "pfh_set_density", "pfh_model_density_points", "pfh_model_density", "pfh_model_color_density"]
+                    "pfh_set_density", "pfh_model_density_points", "pfh_model_density", "pfh_model_color_density",
+                    "pfh_kmc_histogram", "pfh_cutoffs_from_rows", "pfh_set_auto_cutoffs", "pfh_cutoffs"]
 
 
 class FilterOpts(C.Structure):   # pf_filter_opts (include/ploidyfrost_hip.h)
@@ -176,6 +177,11 @@ def load_library() -> C.CDLL:
     L.pfh_model_density_points.argtypes = [vp, C.c_int]
     L.pfh_model_density.argtypes = [vp, vp, vp, vp]
     L.pfh_model_color_density.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.pfh_kmc_histogram.argtypes = [C.c_char_p, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.pfh_cutoffs_from_rows.argtypes = [vp, u64, d, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.pfh_set_auto_cutoffs.argtypes = [vp, d]
+    L.pfh_cutoffs.restype = u32
+    L.pfh_cutoffs.argtypes = [vp, vp, vp, u32]
     _lib = L
     return L
 
@@ -354,6 +360,31 @@ def filter_rows(source: str, texts, q: float = 0.0, multi: bool = False, **opts)
     return out[: n.value].copy()
 
 
+def kmc_histogram(prefix: str):
+    """(min_count, rows): the k-mer histogram of a KMC database, counted on the device from the decoded counters (K-HIST).
+    rows[r] = records whose count is min_count + r, up to min(max_count, the counter's range, 2^20 - 1), zero rows included."""
+    L = load_library()
+    n, mn = C.c_uint64(), C.c_uint64()
+    if L.pfh_kmc_histogram(prefix.encode(), None, 0, C.byref(n), C.byref(mn)):
+        raise RuntimeError(L.pfh_last_error(None).decode())
+    rows = np.zeros(n.value, dtype=np.uint64)
+    if L.pfh_kmc_histogram(prefix.encode(), rows.ctypes.data, n.value, C.byref(n), C.byref(mn)):
+        raise RuntimeError(L.pfh_last_error(None).decode())
+    return int(mn.value), rows
+
+
+def cutoffs_from_rows(rows, q: float = 0.998):
+    """(lower, upper) of the reference's cutoffL / cutoffU (src/Main.cpp:200-277) on the second column of a histogram, in file
+    order; lower is the value before the callers' max(10, lower).  Fewer than two rows: ValueError with the reference's words."""
+    L = load_library()
+    r = np.ascontiguousarray(rows, dtype=np.uint64)
+    lo, up = C.c_int(), C.c_int()
+    rc = L.pfh_cutoffs_from_rows(r.ctypes.data, len(r), q, C.byref(lo), C.byref(up))
+    if rc:
+        raise ValueError("Error: Histogram File is badly Formatted.")
+    return lo.value, up.value
+
+
 def load_trace(reset: bool = True) -> list:
     """[(step, seconds)] of the loads of this process since the last reset (pfh_load_trace)"""
     L = load_library()
@@ -425,6 +456,20 @@ class Run:
 
     def ploidy_estimation(self, outpre: str, lower: int = 10, upper: int = 1000):
         self._check(self.L.pfh_ploidy_estimation(self.h, outpre.encode(), lower, upper))
+
+    def set_auto_cutoffs(self, q: float | None = 0.998):
+        """The thresholds from the run's own database (K-HIST): max(10, cutoffL), cutoffU at quantile q of its k-mer histogram; the
+        next ploidy_estimation uses them instead of its arguments.  None: off again."""
+        self._check(self.L.pfh_set_auto_cutoffs(self.h, -1.0 if q is None else q))
+
+    def cutoffs(self):
+        """(lower, upper) the last ploidy_estimation used (before one: what set_auto_cutoffs derived); a colored run: one pair per
+        colour"""
+        n = self.L.pfh_cutoffs(self.h, None, None, 0)
+        lo, up = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
+        self.L.pfh_cutoffs(self.h, lo, up, n)
+        pairs = [(lo[c], up[c]) for c in range(n)]
+        return pairs if isinstance(self, ColoredRun) else (pairs[0] if pairs else None)
 
     def set_model(self, source, q: float = 0.0, lo: int = 1, hi: int = 9, m_thre: float = 5.0, n_thre: float = 2.0,
                   max_iter: int = 1000, max_delta: float = 0.01, only: bool = False):
@@ -595,8 +640,10 @@ class ColoredRun(Run):
             raise RuntimeError("ploidyfrost host layer: " + self.L.pfh_last_error(None).decode())
         self.n_colors = self.L.pfh_num_colors(self.h)
 
-    def ploidy_estimation(self, outpre: str, cutoffs):
-        """cutoffs: one (lower, upper) per colour, the reference's -C file"""
+    def ploidy_estimation(self, outpre: str, cutoffs=None):
+        """cutoffs: one (lower, upper) per colour, the reference's -C file (None after set_auto_cutoffs: the derived ones)"""
+        if cutoffs is None:
+            cutoffs = self.cutoffs()
         lo = (C.c_int * self.n_colors)(*[int(c[0]) for c in cutoffs])
         up = (C.c_int * self.n_colors)(*[int(c[1]) for c in cutoffs])
         self._check(self.L.pfh_ploidy_estimation_colored(self.h, outpre.encode(), lo, up, len(cutoffs)))
