@@ -64,6 +64,7 @@ enum pf_kernel {
     PF_K_CALL_MODEL, /* the kernels of one pf_call_model_take (rows of a piece's text -> the model's values), timed as one launch */
     PF_K_DENSITY, /* the kernels of one pf_gmm_density, timed as one launch; unit: values x grid points */
     PF_K_HIST, /* K-HIST (pf_count_histogram); unit: counters */
+    PF_K_MASK, /* K-MASK: everything one pf_mask_reads / pf_mask_fastq launches (index, classes, flag, paint), timed as one launch; unit: windows */
     PF_K_COUNT_
 };
 int pf_enable_timing(pf_ctx *, int on);
@@ -152,6 +153,36 @@ void pf_device_free(pf_ctx *, void *device_pointer);
  * every call.  n_bins from 1 to PF_HIST_MAX_BINS, else PF_ERR_ARG.  counts, hist: [host|dev] */
 #define PF_HIST_MAX_BINS (1u << 20)
 int pf_count_histogram(pf_ctx *, const uint32_t *counts, uint64_t n, uint64_t lo, uint64_t hi, uint32_t n_bins, uint64_t *hist);
+/* K-MASK: low-coverage k-mers of reads masked against the count table (pf_upload_counts comes first) -- what step 2 of the
+ * reference's workflow does with `kmc_tools filter -hm <db> <reads> -ci<L>`, whose inner loop is CKMCFile::GetCountersForRead
+ * (KMC/kmc_api/kmc_file.cpp:904-1090).  The rule (csrc/pf_mask_rule.hpp): a read s[0..n) has one window per i in 0 .. n - k, k the
+ * table's k-mer length; its counter is 0 when the window holds a byte outside ACGTacgt, else the count the table holds for it (lower
+ * case read as upper case; a both_strands table is asked for the canonical form, any other for the window as it reads; absent, or
+ * outside the header's [min_count, max_count]: 0).  A window is bad when its counter is below low or above up (up = 0xFFFFFFFF: no
+ * upper bound).  A byte of a read becomes 'N' when a bad window covers it; every other byte of the text is copied.  PARITY with
+ * kmc_tools UNPINNED (the tool is not part of the build): the other reading would mask only bases that no good window covers.
+ * Integer sums: the same bytes and statistics on every call.  Without a table: PF_ERR_ARG, by name. */
+typedef struct pf_mask_stats {
+    uint64_t reads;          /* records seen */
+    uint64_t reads_changed;  /* records in which at least one byte changed */
+    uint64_t bases;          /* sequence bytes */
+    uint64_t bases_masked;   /* bytes that changed to N (an input N under a bad window does not count) */
+    uint64_t kmers;          /* windows */
+    uint64_t kmers_bad;      /* bad windows */
+} pf_mask_stats;
+/* reads given explicitly: read i = text[read_off[i] .. read_off[i] + read_len[i]), ascending and without overlaps (else PF_ERR_ARG
+ * with the first offender); out = text with the rule applied.  text, read_off, read_len, out: [host|dev]; out may not alias text.
+ * n_reads = 0 or n_bytes = 0 is not an error. */
+int pf_mask_reads(pf_ctx *, const char *text, uint64_t n_bytes, const uint64_t *read_off, const uint32_t *read_len,
+                  uint64_t n_reads, uint32_t low, uint32_t up, char *out, pf_mask_stats *stats);
+/* one chunk (fewer than 2^32 bytes) of a FASTQ file with four lines per record: index, check, mask.  Lines end in '\n'; a '\r'
+ * directly before it belongs to the line end; roles come from the line's index.  final = 0: the chunk may end inside a record;
+ * *bytes_used is the end of the last whole record, out is written up to there, and the caller carries the rest into the next chunk.
+ * final = 1: the last line may lack its '\n'.  On a format error (first line without '@', third without '+', quality and sequence of
+ * different lengths, with final a line count that is no multiple of four): PF_ERR_ARG, *bad_record is the 0-based record within the
+ * chunk (the smallest offender), pf_last_error names the clause, and nothing has been written to out.  text, out: [host|dev] */
+int pf_mask_fastq(pf_ctx *, const char *text, uint64_t n_bytes, int final, uint32_t low, uint32_t up, char *out,
+                  uint64_t *bytes_used, pf_mask_stats *stats, uint64_t *bad_record);
 int pf_copy_to_host(pf_ctx *, void *dst, const void *src_dev, size_t bytes);
 
 /* K1/K2: builds the device hash table from the database records (exact k-mers as stored, any

@@ -79,6 +79,27 @@ int pfh_kmc_histogram(const char *kmc_prefix, uint64_t *rows_out, uint64_t cap, 
 int pfh_cutoffs_from_rows(const uint64_t *rows, uint64_t n, double quantile, int *lower, int *upper);
 int pfh_set_auto_cutoffs(pfh_run *, double quantile);
 uint32_t pfh_cutoffs(const pfh_run *, int *lower, int *upper, uint32_t cap);
+/* ---- low-coverage k-mers masked in reads (K-MASK, pf_mask_reads / pf_mask_fastq in ploidyfrost_hip.h) ----
+ * Step 2 of the reference's workflow (README; script/pipeline/3.filter: `kmc_tools filter -hm <db> <reads.fq> -ci<L> <out.fq>`) in one
+ * call: the database is mapped and decoded once (K-KMC), with auto_lower its histogram gives the lower threshold max(10, cutoffL)
+ * (K-HIST, as `cutoffL -d` prints it), the count table is built, and the inputs are streamed through pf_mask_fastq in chunks of
+ * chunk_bytes (0: 256 MB; a record that straddles a chunk edge is carried, a chunk without a whole record grows by the next one) into
+ * out_path, one input after the other, written under a temporary name and renamed at the end.  The rule: csrc/pf_mask_rule.hpp.
+ * Refused by name, with the input's path and the 1-based record number, nothing left under out_path or the temporary name: a record
+ * whose first line does not start with '@' or whose third does not start with '+', a quality line of another length than its
+ * sequence line, a line count that is no multiple of four, FASTA (first byte '>'), gzip (1f 8b), out_path equal to an input.
+ * up = 0xFFFFFFFF: no upper bound.  *lower_used = the lower threshold that was applied.  0 = ok, else pfh_last_error(NULL).
+ * pfh_mask_read: the rule on one read with the counters given by the caller (counters[i] for window i of 0 .. n - k, what
+ * CKMCFile::GetCountersForRead fills); out[0..n) = the masked read; returns the bytes that changed.  No device involved.
+ * pfh_mask_index_fastq: the FASTQ index of a chunk on the host (lines, roles, format clauses of the same header): returns the clause
+ * of the smallest offending record (0 = none; pfh_mask_clause_text names it), *bad_record its 0-based number, *bytes_used and
+ * *n_records as pf_mask_fastq gives them; read_off / read_len (may be NULL, cap entries) receive the sequence lines. */
+int pfh_mask_fastq(const char *db_prefix, const char *const *inputs, uint32_t n_inputs, const char *out_path, uint32_t low, uint32_t up,
+                   int auto_lower, uint64_t chunk_bytes, int device, pf_mask_stats *stats, uint32_t *lower_used);
+uint64_t pfh_mask_read(const char *seq, uint64_t n, uint32_t k, const uint32_t *counters, uint32_t low, uint32_t up, char *out);
+int pfh_mask_index_fastq(const char *text, uint64_t n, int final, uint64_t *bytes_used, uint64_t *n_records, uint64_t *bad_record,
+                         uint64_t *read_off, uint32_t *read_len, uint64_t cap);
+const char *pfh_mask_clause_text(int clause);
 void pfh_get_times(const pfh_run *, pfh_times *out);
 /* Where the loads of this process spent their time (GFA map / parse / upload, count database, join, adjacency, numbering, ...):
  * "step\tseconds\n" per step since the last reset, in the order the steps ended (steps of helper threads overlap those of the

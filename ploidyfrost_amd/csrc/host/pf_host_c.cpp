@@ -8,6 +8,8 @@
 #include "pf_bfs_host.hpp"
 #include "pf_cdbg.hpp"
 #include "pf_cutoffs.hpp"
+#include "pf_mask_host.hpp"
+#include "../pf_mask_rule.hpp"
 #include "pf_trace.hpp"
 #include "../pf_model_rows.hpp"
 #include "../pf_filter_rows.hpp"
@@ -236,6 +238,44 @@ uint32_t pfh_cutoffs(const pfh_run *r, int *lower, int *upper, uint32_t cap) {
     return (uint32_t)v.size();
 }
 void *pfh_device_ctx(pfh_run *r) { return r->cdbg->device(); }
+
+// ---- reads masked against the database (K-MASK) ----------------------------------------------------
+int pfh_mask_fastq(const char *db_prefix, const char *const *inputs, uint32_t n_inputs, const char *out_path, uint32_t low, uint32_t up,
+                   int auto_lower, uint64_t chunk_bytes, int device, pf_mask_stats *stats, uint32_t *lower_used) {
+    if (!db_prefix || !out_path || (n_inputs && !inputs)) { g_open_err = "pfh_mask_fastq: database, inputs and output are needed"; return 1; }
+    try {
+        std::vector<std::string> in;
+        for (uint32_t i = 0; i < n_inputs; ++i) in.push_back(inputs[i] ? inputs[i] : "");
+        pf_mask_stats st = {};
+        uint32_t lower = low;
+        const int rc = pfh::mask_fastq(db_prefix, in, out_path, low, up, auto_lower != 0, chunk_bytes, device, st, lower, nullptr, g_open_err);
+        if (stats) *stats = st;
+        if (lower_used) *lower_used = lower;
+        return rc;
+    } catch (const std::exception &e) {
+        g_open_err = std::string("ploidyfrost host layer: ") + e.what();
+        return 1;
+    }
+}
+uint64_t pfh_mask_read(const char *seq, uint64_t n, uint32_t k, const uint32_t *counters, uint32_t low, uint32_t up, char *out) {
+    return pf_mask::mask_read(seq, n, k, counters, low, up, out);
+}
+int pfh_mask_index_fastq(const char *text, uint64_t n, int final, uint64_t *bytes_used, uint64_t *n_records, uint64_t *bad_record,
+                         uint64_t *read_off, uint32_t *read_len, uint64_t cap) {
+    uint64_t used = 0, recs = 0, bad = 0;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> len;
+    const int clause = pf_mask::index_fastq(text, n, final != 0, used, recs, bad, &off, &len);
+    if (bytes_used) *bytes_used = used;
+    if (n_records) *n_records = recs;
+    if (bad_record) *bad_record = bad;
+    for (uint64_t i = 0; i < cap && i < off.size(); ++i) {
+        if (read_off) read_off[i] = off[i];
+        if (read_len) read_len[i] = len[i];
+    }
+    return clause;
+}
+const char *pfh_mask_clause_text(int clause) { return pf_mask::clause_text(clause); }
 
 // ---- one graph over several GPUs -------------------------------------------------------------------
 int pfh_find_shard(pfh_run *r, uint32_t u0, uint32_t u1) {

@@ -32,6 +32,7 @@
 
 #include "pf_cdbg.hpp"
 #include "pf_cutoffs.hpp"
+#include "pf_mask_host.hpp"
 #include "pf_filter.hpp"
 #include "pf_multi.hpp"
 #include "pf_gmm_model.hpp"
@@ -86,6 +87,9 @@ void PrintUsage() {
          << "Usage: PloidyFrost cutoffL -d <KMCDatabase>" << endl
          << "Usage: PloidyFrost cutoffU -d <KMCDatabase> (quantile[<1 ,default:0.998])" << endl
          << "Usage: PloidyFrost histogram -d <KMCDatabase> [-o <file>]   (the k-mer histogram file of the database, count<TAB>number per row)" << endl << endl
+         << "Usage: PloidyFrost mask -d <KMCDatabase> -i <reads.fq> [-i <more.fq> ...] -o <out.fq> (-l L | --auto-cutoffs) [-u U] [--chunk-bytes N] [-v]" << endl
+         << "                  (`kmc_tools filter -hm <db> <reads.fq> -ci<L> [-cx<U>] <out.fq>` on the device: every base of every k-mer whose count" << endl
+         << "                  lies outside [L, U] becomes N; --auto-cutoffs: L = what `cutoffL -d` prints, printed on stdout)" << endl << endl
          << "Usage: PloidyFrost model ...          (GMM ploidy inference from the coverage / frequency files; `PloidyFrost model` prints its options)" << endl
          << "Usage: PloidyFrost density -f <column file> -o <outfile_prefix> [-n points] [-a adjust]   (kernel density of a column of numbers)" << endl
          << "Usage: PloidyFrost filter ...         (the row predicates of script/Filter.R over <prefix>_*cov.txt; -h prints its options)" << endl
@@ -480,12 +484,66 @@ int model_main(int argc, char **argv) {
 }
 }  // namespace
 
+// `mask`: step 2 of the reference's workflow (`kmc_tools filter -hm <db> <reads.fq> -ci<L> <out.fq>`) against the database on the device
+int mask_main(int argc, char **argv) {
+    const char *usage = "Usage:PloidyFrost mask -d kmc_database -i reads.fq [-i more.fq ...] -o out.fq (-l L | --auto-cutoffs) [-u U] [--chunk-bytes N] [-v]";
+    string db, out;
+    vector<string> inputs;
+    bool l_seen = false, auto_cutoffs = false, verbose = false;
+    long long low = 0, up = 0xFFFFFFFFll, chunk = 0;
+    auto refuse = [&](const string &why) { cerr << "Error: mask: " << why << endl << usage << endl; return 1; };
+    auto number = [&](const char *opt, const char *text, long long &v) {
+        char *end = nullptr;
+        errno = 0;
+        v = strtoll(text, &end, 10);
+        if (!errno && end != text && !*end && v >= 0 && v <= 0xFFFFFFFFll) return true;
+        refuse(string(opt) + " takes a number from 0 to 4294967295, not '" + text + "'");
+        return false;
+    };
+    for (int i = 2; i < argc; ++i) {
+        const string a = argv[i];
+        const bool has_value = i + 1 < argc;
+        if (a == "--auto-cutoffs") auto_cutoffs = true;
+        else if (a == "-v") verbose = true;
+        else if (!has_value) return refuse(a == "-d" || a == "-i" || a == "-o" || a == "-l" || a == "-u" || a == "--chunk-bytes" ? a + " needs a value" : "unknown option " + a);
+        else if (a == "-d") db = argv[++i];
+        else if (a == "-i") inputs.push_back(argv[++i]);
+        else if (a == "-o") out = argv[++i];
+        else if (a == "-l") { if (!number("-l", argv[++i], low)) return 1; l_seen = true; }
+        else if (a == "-u") { if (!number("-u", argv[++i], up)) return 1; }
+        else if (a == "--chunk-bytes") { if (!number("--chunk-bytes", argv[++i], chunk)) return 1; if (!chunk) return refuse("--chunk-bytes takes a positive number"); }
+        else return refuse("unknown option " + a);
+    }
+    // refused by name, before anything is read or written
+    if (db.empty()) return refuse("-d <KMCDatabase> is missing");
+    if (inputs.empty()) return refuse("-i <reads.fq> is missing");
+    if (out.empty()) return refuse("-o <out.fq> is missing");
+    if (l_seen && auto_cutoffs) return refuse("-l does not go with --auto-cutoffs (the lower threshold is derived: leave it out)");
+    if (!l_seen && !auto_cutoffs) return refuse("the lower threshold is missing: -l L, or --auto-cutoffs to derive it from the database");
+    if (l_seen && low > up) return refuse("-l " + to_string(low) + " is above -u " + to_string(up) + " (L > U)");
+    pf_mask_stats st = {};
+    uint32_t lower = (uint32_t)low;
+    pfh::MaskTimes tm;
+    string err;
+    if (pfh::mask_fastq(db, inputs, out, (uint32_t)low, (uint32_t)up, auto_cutoffs, (uint64_t)chunk, 0, st, lower, &tm, err)) {
+        cerr << "Error: " << err << endl;
+        return 1;
+    }
+    if (auto_cutoffs) cout << lower << endl;   // exactly as `cutoffL -d` prints it
+    cerr << "mask: reads " << st.reads << " changed " << st.reads_changed << " bases " << st.bases << " masked " << st.bases_masked << " kmers " << st.kmers
+         << " bad " << st.kmers_bad << endl;
+    if (verbose)
+        cerr << "mask: load " << tm.load_s << "s stream " << tm.stream_s << "s (device " << tm.device_s << "s, read " << tm.read_s << "s, write " << tm.write_s << "s)" << endl;
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) { PrintUsage(); return 0; }
     if (!strcmp(argv[1], "model")) return model_main(argc, argv);
     if (!strcmp(argv[1], "density")) return density_main(argc - 1, argv + 1);
     if (!strcmp(argv[1], "filter")) return pfh::filter_main(argc, argv, false);         // script/Filter.R
     if (!strcmp(argv[1], "filter-multi")) return pfh::filter_main(argc, argv, true);    // script/Filter-multi.R
+    if (!strcmp(argv[1], "mask")) return mask_main(argc, argv);
     if (!strcmp(argv[1], "histogram")) {   // the file `kmc_tools transform <db> histogram <file>` writes, from the database on the device
         string db, out;
         for (int i = 2; i < argc; ++i) {

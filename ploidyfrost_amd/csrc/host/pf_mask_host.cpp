@@ -1,0 +1,279 @@
+#include "pf_mask_host.hpp"
+
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <cerrno>
+#include <chrono>
+#include <condition_variable>
+#include <cstring>
+#include <deque>
+#include <memory>
+#include <mutex>
+#include <thread>
+
+#include "../pf_mask_rule.hpp"
+#include "pf_cutoffs.hpp"
+#include "pf_host_graph.hpp"
+
+namespace pfh {
+
+namespace {
+
+using clk = std::chrono::steady_clock;
+double since(clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); }
+
+// a bounded hand-over between two threads; close() wakes everybody, pop() then drains what is left and fails
+template <typename T>
+struct Chan {
+    std::mutex mu;
+    std::condition_variable cv;
+    std::deque<T> q;
+    bool closed = false;
+    void push(T v) {
+        { std::lock_guard<std::mutex> lk(mu); q.push_back(std::move(v)); }
+        cv.notify_all();
+    }
+    bool pop(T &v) {
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return !q.empty() || closed; });
+        if (q.empty()) return false;
+        v = std::move(q.front());
+        q.pop_front();
+        return true;
+    }
+    void close() {
+        { std::lock_guard<std::mutex> lk(mu); closed = true; }
+        cv.notify_all();
+    }
+};
+
+struct Block {     // reader -> device: bytes [HEAD, HEAD + len) of input buffer `buf`
+    int buf = -1;
+    uint64_t len = 0;
+    size_t input = 0;
+    bool eof = false;
+};
+struct Piece {     // device -> writer: `len` bytes at `p`; buf >= 0: an output buffer to hand back, else `own` keeps them alive
+    int buf = -1;
+    const char *p = nullptr;
+    uint64_t len = 0;
+    std::shared_ptr<std::vector<char>> own;
+};
+
+constexpr uint64_t MASK_HEAD = 1u << 16;   // room in front of a block for the record carried over from the last one
+
+struct PinnedBuf {
+    pf_ctx *ctx = nullptr;
+    char *p = nullptr;
+    bool pinned = false;
+    bool alloc(pf_ctx *c, size_t bytes) {
+        ctx = c;
+        void *v = nullptr;
+        if (pf_host_alloc(c, bytes, &v) == PF_OK && v) { p = static_cast<char *>(v); pinned = true; return true; }
+        p = static_cast<char *>(malloc(bytes));   // pageable memory works, slower
+        return p != nullptr;
+    }
+    ~PinnedBuf() {
+        if (p && pinned) pf_host_free(ctx, p);
+        else free(p);
+    }
+};
+
+bool same_file(const std::string &a, const std::string &b) {
+    if (a == b) return true;
+    struct stat sa, sb;
+    return stat(a.c_str(), &sa) == 0 && stat(b.c_str(), &sb) == 0 && sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino;
+}
+
+}  // namespace
+
+int mask_fastq(const std::string &db_prefix, const std::vector<std::string> &inputs, const std::string &out_path, uint32_t low, uint32_t up,
+               bool auto_lower, uint64_t chunk_bytes, int device, pf_mask_stats &stats, uint32_t &lower_used, MaskTimes *times, std::string &err) {
+    stats = pf_mask_stats{};
+    lower_used = low;
+    MaskTimes tm;
+    // ---- refusals that need no device: every input is looked at before anything is written ----
+    if (inputs.empty()) { err = "mask: no input"; return 1; }
+    if (out_path.empty()) { err = "mask: no output path"; return 1; }
+    uint64_t largest = 0;
+    for (const std::string &in : inputs) {
+        if (same_file(in, out_path)) { err = "mask: " + in + ": " + pf_mask::clause_text(pf_mask::CLAUSE_SAME_PATH); return 1; }
+        const int fd = open(in.c_str(), O_RDONLY);
+        if (fd < 0) { err = "mask: cannot read " + in + " (" + strerror(errno) + ")"; return 1; }
+        unsigned char first[2];
+        const ssize_t got = read(fd, first, 2);
+        struct stat st;
+        if (fstat(fd, &st) == 0) largest = std::max<uint64_t>(largest, (uint64_t)st.st_size);
+        close(fd);
+        const int clause = pf_mask::file_clause(first, got > 0 ? (uint64_t)got : 0);
+        if (clause) { err = "mask: " + in + ": record 1: " + pf_mask::clause_text(clause); return 1; }
+    }
+    if (!auto_lower && low > up) { err = "mask: the lower threshold " + std::to_string(low) + " is above the upper threshold " + std::to_string(up); return 1; }
+
+    // ---- load: the database once -- decode (K-KMC), with auto_lower its histogram (K-HIST), the table ----
+    const auto t_load = clk::now();
+    pf_ctx *ctx = nullptr;
+    if (pf_create(device, &ctx) != PF_OK) {
+        err = std::string("mask: no device context (") + (pf_last_error(nullptr) ? pf_last_error(nullptr) : "?") + "); reads are masked on the GPU only";
+        return 1;
+    }
+    struct CtxGuard { pf_ctx *c; ~CtxGuard() { pf_destroy(c); } } ctx_guard{ctx};
+    {
+        KmcRecords db;
+        std::string e;
+        if (!db.load(db_prefix, e)) { err = "Open kmc database " + db_prefix + " error (" + e + ")"; return 1; }
+        uint64_t *dk = nullptr;
+        uint32_t *dc = nullptr;
+        int st = pf_kmc_decode(ctx, db.records, db.total, db.suffix_bytes, db.counter_size, db.lut.data(), db.n_lut(), db.lut_prefix_len, db.k, &dk, &dc);
+        std::vector<uint64_t> rows;
+        if (st == PF_OK && auto_lower) st = kmc_rows_of_counts(ctx, db, dc, rows);
+        if (st == PF_OK) st = pf_upload_counts(ctx, dk, dc, db.total, db.k, db.min_count, db.max_count, db.both_strands);
+        pf_device_free(ctx, dk);
+        pf_device_free(ctx, dc);
+        if (st != PF_OK) { err = "mask: count table of " + db_prefix + ": " + pf_last_error(ctx); return 1; }
+        if (auto_lower) {
+            int lo = 0, hi = 0;
+            (void)cutoffs_from_rows(rows, 0.998, lo, hi);
+            lower_used = low = (uint32_t)std::max(10, lo);
+            if (low > up) { err = "mask: the derived lower threshold " + std::to_string(low) + " is above the upper threshold " + std::to_string(up); return 1; }
+        }
+    }
+    tm.load_s = since(t_load);
+
+    // ---- stream ----
+    const auto t_stream = clk::now();
+    uint64_t chunk = chunk_bytes ? chunk_bytes : MASK_DEFAULT_CHUNK;
+    chunk = std::max<uint64_t>(1, std::min<uint64_t>(chunk, std::max<uint64_t>(largest, 1)));   // (no gigabyte of pinned memory for a small file)
+    chunk = std::min<uint64_t>(chunk, 1ull << 31);                                               // a chunk and its carry stay below pf_mask_fastq's 2^32
+    PinnedBuf in_buf[2], out_buf[2];
+    for (int i = 0; i < 2; ++i)
+        if (!in_buf[i].alloc(ctx, MASK_HEAD + chunk) || !out_buf[i].alloc(ctx, MASK_HEAD + chunk)) { err = "mask: no memory for the chunk buffers"; return 1; }
+    const std::string tmp_path = out_path + ".tmp." + std::to_string((long)getpid());
+    const int out_fd = open(tmp_path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (out_fd < 0) { err = "mask: cannot write " + tmp_path + " (" + strerror(errno) + ")"; return 1; }
+
+    Chan<int> free_in, free_out;
+    Chan<Block> blocks;
+    Chan<Piece> pieces;
+    for (int i = 0; i < 2; ++i) { free_in.push(i); free_out.push(i); }
+    std::string read_err, write_err;
+    double read_s = 0, write_s = 0;
+    // reader: the next block of the next input is read while the device works on this one
+    std::thread reader([&] {
+        for (size_t f = 0; f < inputs.size(); ++f) {
+            const int fd = open(inputs[f].c_str(), O_RDONLY);
+            if (fd < 0) { read_err = "mask: cannot read " + inputs[f] + " (" + strerror(errno) + ")"; break; }
+            for (bool eof = false; !eof;) {
+                Block b;
+                if (!free_in.pop(b.buf)) { close(fd); return; }
+                b.input = f;
+                const auto t0 = clk::now();
+                while (b.len < chunk) {
+                    const ssize_t got = read(fd, in_buf[b.buf].p + MASK_HEAD + b.len, (size_t)(chunk - b.len));
+                    if (got < 0 && errno == EINTR) continue;
+                    if (got < 0) { read_err = "mask: reading " + inputs[f] + " (" + strerror(errno) + ")"; break; }
+                    if (got == 0) { eof = true; break; }
+                    b.len += (uint64_t)got;
+                }
+                read_s += since(t0);
+                if (!read_err.empty()) { close(fd); blocks.close(); return; }
+                b.eof = eof;
+                blocks.push(b);
+            }
+            close(fd);
+        }
+        blocks.close();
+    });
+    // writer: the last piece is written while the device works on this one
+    std::thread writer([&] {
+        Piece p;
+        while (pieces.pop(p)) {
+            const auto t0 = clk::now();
+            for (uint64_t done = 0; done < p.len && write_err.empty();) {
+                const ssize_t put = write(out_fd, p.p + done, (size_t)(p.len - done));
+                if (put < 0 && errno == EINTR) continue;
+                if (put < 0) { write_err = "mask: writing " + tmp_path + " (" + strerror(errno) + ")"; break; }
+                done += (uint64_t)put;
+            }
+            write_s += since(t0);
+            if (p.buf >= 0) free_out.push(p.buf);
+        }
+    });
+
+    // device: carry + block -> pf_mask_fastq -> piece
+    std::vector<char> carry;
+    uint64_t records_before = 0;   // whole records of the current input in front of the current chunk
+    size_t cur_input = 0;
+    Block b;
+    while (err.empty() && blocks.pop(b)) {
+        if (b.input != cur_input) { cur_input = b.input; records_before = 0; }
+        const uint64_t n = carry.size() + b.len;
+        const char *text;
+        char *out;
+        Piece piece;
+        std::shared_ptr<std::vector<char>> big_in;
+        if (carry.size() <= MASK_HEAD) {   // the carried record in front of the block, in place
+            char *p = in_buf[b.buf].p + MASK_HEAD - carry.size();
+            memcpy(p, carry.data(), carry.size());
+            text = p;
+            if (!free_out.pop(piece.buf)) break;
+            out = out_buf[piece.buf].p;
+        } else {   // a record longer than the room in front: this chunk holds what has gathered so far
+            big_in = std::make_shared<std::vector<char>>(n);
+            memcpy(big_in->data(), carry.data(), carry.size());
+            memcpy(big_in->data() + carry.size(), in_buf[b.buf].p + MASK_HEAD, b.len);
+            text = big_in->data();
+            piece.own = std::make_shared<std::vector<char>>(n);
+            out = piece.own->data();
+        }
+        uint64_t used = 0, bad = 0;
+        pf_mask_stats st = {};
+        const auto t0 = clk::now();
+        const int rc = n ? pf_mask_fastq(ctx, text, n, b.eof ? 1 : 0, low, up, out, &used, &st, &bad) : (int)PF_OK;
+        tm.device_s += since(t0);
+        if (rc != PF_OK) {
+            const std::string why = pf_last_error(ctx);
+            const size_t at = why.find("of the chunk: ");
+            err = at != std::string::npos
+                      ? "mask: " + inputs[b.input] + ": record " + std::to_string(records_before + bad + 1) + ": " + why.substr(at + 14)
+                      : "mask: " + inputs[b.input] + ": " + why;
+            if (piece.buf >= 0) free_out.push(piece.buf);
+            break;
+        }
+        // a chunk that holds no whole record gives used = 0: everything is carried and the next chunk is this one plus the next block
+        carry.assign(text + used, text + n);
+        free_in.push(b.buf);
+        records_before += st.reads;
+        stats.reads += st.reads;
+        stats.reads_changed += st.reads_changed;
+        stats.bases += st.bases;
+        stats.bases_masked += st.bases_masked;
+        stats.kmers += st.kmers;
+        stats.kmers_bad += st.kmers_bad;
+        piece.p = out;
+        piece.len = used;
+        pieces.push(std::move(piece));
+    }
+    // wind down: on an error the threads are let go first
+    free_in.close();
+    blocks.close();
+    reader.join();
+    pieces.close();
+    writer.join();
+    free_out.close();
+    if (err.empty()) err = !read_err.empty() ? read_err : write_err;
+    if (err.empty() && close(out_fd) != 0) err = "mask: closing " + tmp_path + " (" + strerror(errno) + ")";
+    else if (!err.empty()) close(out_fd);
+    if (err.empty() && rename(tmp_path.c_str(), out_path.c_str()) != 0) err = "mask: renaming " + tmp_path + " to " + out_path + " (" + strerror(errno) + ")";
+    if (!err.empty()) { unlink(tmp_path.c_str()); return 1; }
+    tm.stream_s = since(t_stream);
+    tm.read_s = read_s;
+    tm.write_s = write_s;
+    if (times) *times = tm;
+    return 0;
+}
+
+}  // namespace pfh

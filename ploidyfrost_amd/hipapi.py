@@ -26,6 +26,9 @@ KERNELS = ["k_table_build", "k_adj_insert", "k_adj_probe", "k_cov", "k_bfs", "k_
 K_DENSITY = len(KERNELS)   # PF_K_DENSITY ("k_density"): the kernels of one pf_gmm_density, timed as one launch
 K_HIST = K_DENSITY + 1     # PF_K_HIST ("k_hist"): K-HIST, the histogram of decoded counters (pf_count_histogram)
 HIST_MAX_BINS = 1 << 20
+K_MASK = K_HIST + 1        # PF_K_MASK ("k_mask"): everything one pf_mask_reads / pf_mask_fastq launches; unit: windows
+MASK_STATS = np.dtype([(f, "<u8") for f in ("reads", "reads_changed", "bases", "bases_masked", "kmers", "kmers_bad")])   # pf_mask_stats
+MASK_NO_UPPER = 0xFFFFFFFF
 DENSITY_INFO = np.dtype([("n", "<u8"), ("min", "<f8"), ("max", "<f8"), ("sd", "<f8"), ("q1", "<f8"), ("q3", "<f8"), ("bw", "<f8"),
                          ("order", "<f8", (4,))])   # pf_density_info
 assert DENSITY_INFO.itemsize == 88
@@ -196,6 +199,8 @@ def load_library() -> C.CDLL:
         "pf_call_model_color_select": (i, [vp, i, C.POINTER(u64)]),
         "pf_gmm_density": (i, [vp, u32, C.c_double, vp, vp, vp]),
         "pf_count_histogram": (i, [vp, vp, u64, u64, u64, u32, vp]),
+        "pf_mask_reads": (i, [vp, vp, u64, vp, vp, u64, u32, u32, vp, vp]),
+        "pf_mask_fastq": (i, [vp, vp, u64, i, u32, u32, vp, C.POINTER(u64), vp, C.POINTER(u64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError = header / library mismatch
@@ -217,7 +222,7 @@ DECLARED_SYMBOLS = ["pf_create", "pf_warmup", "pf_destroy", "pf_last_error", "pf
                     "pf_gmm_values", "pf_call_model_begin", "pf_call_model_take", "pf_call_model_finish", "pf_call_fetched_bytes",
                     "pf_call_model_filter", "pf_call_model_take_text",
                     "pf_call_model_filter_multi", "pf_call_model_color_count", "pf_call_model_color_select",
-                    "pf_gmm_density", "pf_count_histogram"]
+                    "pf_gmm_density", "pf_count_histogram", "pf_mask_reads", "pf_mask_fastq"]
 
 
 def density_dict(x: np.ndarray, density: np.ndarray, info: np.ndarray) -> dict:
@@ -445,10 +450,52 @@ class Device:
         return hist
 
     def kernel_time(self, kernel: int):
-        """(ms, launches) of one kernel of the enum by number (K_DENSITY, K_HIST: not in KERNELS)"""
+        """(ms, launches) of one kernel of the enum by number (K_DENSITY, K_HIST, K_MASK: not in KERNELS)"""
         ms, n = C.c_double(), C.c_uint64()
         self._check(self.L.pf_kernel_time(self.h, kernel, C.byref(ms), C.byref(n)))
         return ms.value, n.value
+
+    def kernel_units(self, kernel: int) -> int:
+        """work items handed to the timed launches of one kernel of the enum by number (pf_kernel_units)"""
+        n = C.c_uint64()
+        self._check(self.L.pf_kernel_units(self.h, kernel, C.byref(n)))
+        return n.value
+
+    def mask_reads(self, text, read_off, read_len, low: int, up: int = MASK_NO_UPPER, out=None):
+        """K-MASK (pf_mask_reads): text with every base of every k-mer whose count lies outside [low, up] replaced by N, for the reads
+        text[read_off[i] : read_off[i] + read_len[i]].  text: bytes, a uint8 numpy array or a device tensor; read_off / read_len: numpy
+        arrays or device tensors (u64 / u32); out: a device tensor to fill instead of a new numpy array.  Returns (out, stats dict)."""
+        if isinstance(text, (bytes, bytearray)):
+            text = np.frombuffer(bytes(text), dtype=np.uint8)
+        if isinstance(read_off, (list, tuple, np.ndarray)):
+            read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
+        if isinstance(read_len, (list, tuple, np.ndarray)):
+            read_len = np.ascontiguousarray(read_len, dtype=np.uint32)
+        n, n_reads = int(text.shape[0]), int(read_off.shape[0])
+        if out is None:
+            out = np.zeros(n, dtype=np.uint8)
+        stats = np.zeros(1, dtype=MASK_STATS)
+        self._check(self.L.pf_mask_reads(self.h, _ptr(text) if n else None, n, _ptr(read_off) if n_reads else None,
+                                         _ptr(read_len) if n_reads else None, n_reads, low, up, _ptr(out) if n else None, stats.ctypes.data))
+        return out, {f: int(stats[0][f]) for f in MASK_STATS.names}
+
+    def mask_fastq(self, text, low: int, up: int = MASK_NO_UPPER, final: bool = True, out=None):
+        """K-MASK on one chunk of a FASTQ file (pf_mask_fastq): (out[:bytes_used], bytes_used, stats dict).  A format error raises
+        DeviceError with .bad_record = the 0-based record within the chunk."""
+        if isinstance(text, (bytes, bytearray)):
+            text = np.frombuffer(bytes(text), dtype=np.uint8)
+        n = int(text.shape[0])
+        if out is None:
+            out = np.zeros(n, dtype=np.uint8)
+        stats = np.zeros(1, dtype=MASK_STATS)
+        used, bad = C.c_uint64(), C.c_uint64()
+        st = self.L.pf_mask_fastq(self.h, _ptr(text) if n else None, n, int(final), low, up, _ptr(out) if n else None, C.byref(used),
+                                  stats.ctypes.data, C.byref(bad))
+        if st != PF_OK:
+            e = DeviceError(st, self.L.pf_last_error(self.h).decode())
+            e.bad_record = bad.value
+            raise e
+        return out[: used.value], used.value, {f: int(stats[0][f]) for f in MASK_STATS.names}
 
     def lookup(self, kmers: np.ndarray):
         n = len(kmers)

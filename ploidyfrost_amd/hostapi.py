@@ -39,7 +39,8 @@ DECLARED_SYMBOLS = ["pfh_open", "pfh_close", "pfh_last_error", "pfh_set_output_d
                     "pfh_model_color_fit", "pfh_model_color_ploidy",
                     "pfh_gmm_read_column", "pfh_gmm_density", "pfh_gmm_write_density", "pfh_gmm_density_time",
                     "pfh_set_density", "pfh_model_density_points", "pfh_model_density", "pfh_model_color_density",
-                    "pfh_kmc_histogram", "pfh_cutoffs_from_rows", "pfh_set_auto_cutoffs", "pfh_cutoffs"]
+                    "pfh_kmc_histogram", "pfh_cutoffs_from_rows", "pfh_set_auto_cutoffs", "pfh_cutoffs",
+                    "pfh_mask_fastq", "pfh_mask_read", "pfh_mask_index_fastq", "pfh_mask_clause_text"]
 
 
 class FilterOpts(C.Structure):   # pf_filter_opts (include/ploidyfrost_hip.h)
@@ -182,6 +183,12 @@ def load_library() -> C.CDLL:
     L.pfh_set_auto_cutoffs.argtypes = [vp, d]
     L.pfh_cutoffs.restype = u32
     L.pfh_cutoffs.argtypes = [vp, vp, vp, u32]
+    L.pfh_mask_fastq.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), u32, C.c_char_p, u32, u32, C.c_int, u64, C.c_int, vp, C.POINTER(u32)]
+    L.pfh_mask_read.restype = u64
+    L.pfh_mask_read.argtypes = [vp, u64, u32, vp, u32, u32, vp]
+    L.pfh_mask_index_fastq.argtypes = [vp, u64, C.c_int, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp, vp, u64]
+    L.pfh_mask_clause_text.restype = C.c_char_p
+    L.pfh_mask_clause_text.argtypes = [C.c_int]
     _lib = L
     return L
 
@@ -383,6 +390,58 @@ def cutoffs_from_rows(rows, q: float = 0.998):
     if rc:
         raise ValueError("Error: Histogram File is badly Formatted.")
     return lo.value, up.value
+
+
+MASK_STATS_FIELDS = ("reads", "reads_changed", "bases", "bases_masked", "kmers", "kmers_bad")   # pf_mask_stats
+MASK_CLAUSES = ("none", "header", "plus", "quality", "line_count", "fasta", "gzip", "same_path")      # pf_mask::Clause, in its order
+
+
+def mask_fastq(db: str, inputs, out: str, lower=None, upper=None, auto: bool = False, chunk_bytes: int = 0) -> dict:
+    """`ploidyfrost mask` (pfh_mask_fastq): the reads of the FASTQ file(s) `inputs`, one after the other, with every base of every
+    k-mer whose count in the KMC database `db` lies outside [lower, upper] replaced by N, written to `out`.  auto: lower =
+    max(10, cutoffL) of the database's own histogram.  Returns the statistics plus "lower" (the threshold applied).  A refusal
+    raises RuntimeError with the input's path and the 1-based record number; nothing is left under `out`."""
+    L = load_library()
+    if isinstance(inputs, (str, bytes, os.PathLike)):
+        inputs = [inputs]
+    if auto == (lower is not None):
+        raise ValueError("mask_fastq: either lower=L or auto=True")
+    paths = (C.c_char_p * max(len(inputs), 1))(*[os.fsencode(p) for p in inputs])
+    stats = np.zeros(len(MASK_STATS_FIELDS), dtype=np.uint64)
+    used = C.c_uint32()
+    rc = L.pfh_mask_fastq(os.fsencode(db), paths, len(inputs), os.fsencode(out), 0 if lower is None else int(lower),
+                          0xFFFFFFFF if upper is None else int(upper), int(auto), int(chunk_bytes), 0, stats.ctypes.data, C.byref(used))
+    if rc:
+        raise RuntimeError(L.pfh_last_error(None).decode())
+    d = {f: int(v) for f, v in zip(MASK_STATS_FIELDS, stats)}
+    d["lower"] = used.value
+    return d
+
+
+def mask_read(seq: bytes, k: int, counters, lower: int, upper: int = 0xFFFFFFFF):
+    """(masked read, bytes changed): the rule of `mask` on one read with the counters given (pfh_mask_read; no device)"""
+    L = load_library()
+    n = len(seq)
+    c = np.ascontiguousarray(counters, dtype=np.uint32)
+    assert len(c) >= max(n - k + 1, 0)
+    src = np.frombuffer(bytes(seq), dtype=np.uint8)
+    out = np.zeros(n, dtype=np.uint8)
+    changed = L.pfh_mask_read(src.ctypes.data if n else None, n, k, c.ctypes.data if len(c) else None, lower, upper, out.ctypes.data if n else None)
+    return out.tobytes(), int(changed)
+
+
+def mask_index_fastq(text: bytes, final: bool = True):
+    """The FASTQ index of a chunk by the shared rule header, on the host (pfh_mask_index_fastq): dict with clause (a name of
+    MASK_CLAUSES), message, bad_record, bytes_used, n_records, read_off, read_len"""
+    L = load_library()
+    src = np.frombuffer(bytes(text), dtype=np.uint8)
+    n = len(src)
+    cap = text.count(b"\n") // 4 + 2
+    off, ln = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint32)
+    used, recs, bad = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    clause = L.pfh_mask_index_fastq(src.ctypes.data if n else None, n, int(final), C.byref(used), C.byref(recs), C.byref(bad), off.ctypes.data, ln.ctypes.data, cap)
+    return dict(clause=MASK_CLAUSES[clause], message=L.pfh_mask_clause_text(clause).decode(), bad_record=bad.value, bytes_used=used.value,
+                n_records=recs.value, read_off=off[: recs.value].copy(), read_len=ln[: recs.value].copy())
 
 
 def load_trace(reset: bool = True) -> list:
