@@ -65,6 +65,7 @@ enum pf_kernel {
     PF_K_DENSITY, /* the kernels of one pf_gmm_density, timed as one launch; unit: values x grid points */
     PF_K_HIST, /* K-HIST (pf_count_histogram); unit: counters */
     PF_K_MASK, /* K-MASK: everything one pf_mask_reads / pf_mask_fastq launches (index, classes, flag, paint), timed as one launch; unit: windows */
+    PF_K_COUNT, /* K-COUNT: everything one pf_count_reads / pf_count_fastq launches (index, classes, insert, growth), timed as one launch; unit: windows */
     PF_K_COUNT_
 };
 int pf_enable_timing(pf_ctx *, int on);
@@ -183,6 +184,45 @@ int pf_mask_reads(pf_ctx *, const char *text, uint64_t n_bytes, const uint64_t *
  * chunk (the smallest offender), pf_last_error names the clause, and nothing has been written to out.  text, out: [host|dev] */
 int pf_mask_fastq(pf_ctx *, const char *text, uint64_t n_bytes, int final, uint32_t low, uint32_t up, char *out,
                   uint64_t *bytes_used, pf_mask_stats *stats, uint64_t *bad_record);
+/* K-COUNT: k-mers counted from reads on the device -- what step `2.kmc_db` of the reference's workflow does with
+ * `kmc -k<k> -ci<ci> -cs<cs> -cx<cx> [-b]`.  The rule (csrc/pf_count_rule.hpp): the windows are K-MASK's (one per i in 0 .. n - k of a
+ * read, counted when all k bytes are in ACGTacgt, lower case read as upper case); the key is the canonical form min(fw, rc), or with
+ * both_strands = 0 the window as it reads; a counter is the exact number of counted windows of its key over all calls, a uint32 that
+ * never wraps (PF_ERR_OVERFLOW, "a k-mer occurs more than 4294967295 times").  A k-mer is given out when ci <= c <= cx, with the value
+ * min(c, cs).  The table lies in HBM and grows by itself; when it cannot (free memory), PF_ERR_OVERFLOW by name with the number of
+ * distinct k-mers reached.  PARITY with kmc UNPINNED (the tool is not part of the build).  Integer sums: the same arrays on every run,
+ * whatever the chunking. */
+typedef struct pf_count_stats {
+    uint64_t reads;      /* records seen */
+    uint64_t bases;      /* sequence bytes */
+    uint64_t kmers;      /* windows */
+    uint64_t kmers_bad;  /* windows holding a byte outside ACGTacgt: not counted */
+    uint64_t unique;     /* pf_count_finish only: distinct k-mers counted */
+    uint64_t below_min;  /* ... of them with c < ci */
+    uint64_t above_max;  /* ... with c > cx */
+    uint64_t written;    /* ... given out */
+} pf_count_stats;
+/* opens a count: 3 <= k <= 31.  initial_slots = 0: twice the first call's bytes; else rounded up to a power of two of at least 64.
+ * A second begin without pf_count_finish / pf_count_abort: PF_ERR_ARG by name. */
+int pf_count_begin(pf_ctx *, uint32_t k, int both_strands, uint64_t initial_slots);
+/* reads given explicitly, as pf_mask_reads takes them (ascending, no overlaps, else PF_ERR_ARG with the first offender); stats: this
+ * call's reads, bases, kmers, kmers_bad.  text, read_off, read_len: [host|dev] */
+int pf_count_reads(pf_ctx *, const char *text, uint64_t n_bytes, const uint64_t *read_off, const uint32_t *read_len, uint64_t n_reads,
+                   pf_count_stats *stats);
+/* one chunk of a FASTQ file: the chunk contract and the format clauses of pf_mask_fastq; nothing is counted from a refused chunk.
+ * text: [host|dev] */
+int pf_count_fastq(pf_ctx *, const char *text, uint64_t n_bytes, int final, uint64_t *bytes_used, pf_count_stats *stats, uint64_t *bad_record);
+/* closes the count: the k-mers with ci <= c <= cx, sorted, and min(c, cs), as two device arrays like pf_kmc_decode's (for
+ * pf_count_histogram, pf_upload_counts, pf_kmc_encode; released with pf_device_free); stats: the totals of all calls and the four
+ * finish fields.  ci < 1, ci > cx, cs < 1 or a value above 2^32 - 1: PF_ERR_ARG by name, and the count stays open. */
+int pf_count_finish(pf_ctx *, uint64_t ci, uint64_t cx, uint64_t cs, uint64_t **kmers_dev, uint32_t **counts_dev, uint64_t *n, pf_count_stats *stats);
+int pf_count_abort(pf_ctx *);
+/* the inverse of K-KMC: sorted distinct k-mers and their counts as the record area of a KMC1 <db>.kmc_suf (n records of
+ * (k - lut_prefix_len) / 4 suffix bytes, most significant first, + counter_bytes counter bytes, least significant first) and the
+ * prefix table of its <db>.kmc_pre (4^lut_prefix_len entries plus lut[4^lut_prefix_len] = n).  Either output may be NULL (a block of
+ * records needs no table).  kmers, counts, records_out, lut_out: [host|dev] */
+int pf_kmc_encode(pf_ctx *, const uint64_t *kmers, const uint32_t *counts, uint64_t n, uint32_t k, uint32_t lut_prefix_len, uint32_t counter_bytes,
+                  uint8_t *records_out, uint64_t *lut_out);
 int pf_copy_to_host(pf_ctx *, void *dst, const void *src_dev, size_t bytes);
 
 /* K1/K2: builds the device hash table from the database records (exact k-mers as stored, any

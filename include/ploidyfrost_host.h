@@ -100,6 +100,35 @@ uint64_t pfh_mask_read(const char *seq, uint64_t n, uint32_t k, const uint32_t *
 int pfh_mask_index_fastq(const char *text, uint64_t n, int final, uint64_t *bytes_used, uint64_t *n_records, uint64_t *bad_record,
                          uint64_t *read_off, uint32_t *read_len, uint64_t cap);
 const char *pfh_mask_clause_text(int clause);
+/* ---- k-mers counted from reads (K-COUNT, pf_count_* and pf_kmc_encode in ploidyfrost_hip.h) ----
+ * Step `2.kmc_db` of the reference's workflow (`kmc -ci1 -cs10000 -k25 @FILES kmc_sample tmp`) in one call: the FASTQ inputs are
+ * streamed through pf_count_fastq in chunks of chunk_bytes (0: 256 MB; the chunk contract and the format refusals of pfh_mask_fastq),
+ * the counters with ci <= c <= cx are given out as min(c, cs) (kmc's letters; defaults 2, 1000000000, 255), and <out_prefix>.kmc_pre /
+ * .kmc_suf are written in the KMC1 layout under temporary names and renamed at the end.  hist (may be NULL): the histogram file of the
+ * finished counters, byte for byte what `histogram -d <out_prefix>` writes.  initial_slots: 0 = twice the first chunk's bytes.  The
+ * rule: csrc/pf_count_rule.hpp.  Refused by name before a device context exists: no input, no output, k outside 3 .. 31, ci < 1,
+ * ci > cx, cs < 1, a cut-off above 2^32 - 1, FASTA, gzip, an output that is an input.  0 = ok, else pfh_last_error(NULL).
+ * pfh_mask_fastq_counted: `mask -k`: pfh_mask_fastq without a database -- the inputs are counted first with these options, the finished
+ * counters give the histogram (auto_lower) and the table, the inputs are streamed a second time through K-MASK; db_out (may be NULL):
+ * the database is written as well.
+ * The host's plain restatement of the rule, no device involved:
+ * pfh_count_reads_host: counts the reads text[off[i] .. off[i] + len[i]) and applies the cut-offs; at most cap sorted (k-mer, count)
+ * pairs are written, *n is their number; returns the refusal of the options (0 = none; pfh_count_cut_text names it), -1 when a counter
+ * passed 2^32 - 1.
+ * pfh_count_encode_kmc1: the bytes of the two files for sorted distinct k-mers, with lut_prefix_len and counter_bytes by the rule;
+ * at most *_cap bytes are written, *pre_n / *suf_n are the sizes. */
+int pfh_count_fastq(const char *const *inputs, uint32_t n_inputs, const char *out_prefix, uint32_t k, uint64_t ci, uint64_t cx, uint64_t cs,
+                    int both_strands, const char *hist, uint64_t chunk_bytes, uint64_t initial_slots, int device, pf_count_stats *stats);
+int pfh_mask_fastq_counted(const char *const *inputs, uint32_t n_inputs, const char *out_path, uint32_t k, uint64_t ci, uint64_t cx, uint64_t cs,
+                           int both_strands, const char *db_out, uint32_t low, uint32_t up, int auto_lower, uint64_t chunk_bytes, int device,
+                           pf_mask_stats *stats, uint32_t *lower_used);
+int pfh_count_reads_host(const char *text, const uint64_t *off, const uint32_t *len, uint64_t n_reads, uint32_t k, int both_strands, uint64_t ci,
+                         uint64_t cx, uint64_t cs, uint64_t *kmers_out, uint32_t *counts_out, uint64_t cap, uint64_t *n, pf_count_stats *stats);
+int pfh_count_encode_kmc1(const uint64_t *kmers, const uint32_t *counts, uint64_t n, uint32_t k, uint64_t ci, uint64_t cx, uint64_t cs,
+                          int both_strands, uint8_t *pre_out, uint64_t pre_cap, uint64_t *pre_n, uint8_t *suf_out, uint64_t suf_cap, uint64_t *suf_n);
+uint32_t pfh_count_counter_bytes(uint64_t cx, uint64_t cs);
+uint32_t pfh_count_lut_prefix_len(uint32_t k);
+const char *pfh_count_cut_text(int clause);
 void pfh_get_times(const pfh_run *, pfh_times *out);
 /* Where the loads of this process spent their time (GFA map / parse / upload, count database, join, adjacency, numbering, ...):
  * "step\tseconds\n" per step since the last reset, in the order the steps ended (steps of helper threads overlap those of the

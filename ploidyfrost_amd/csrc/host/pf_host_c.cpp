@@ -9,6 +9,7 @@
 #include "pf_cdbg.hpp"
 #include "pf_cutoffs.hpp"
 #include "pf_mask_host.hpp"
+#include "pf_count_host.hpp"
 #include "../pf_mask_rule.hpp"
 #include "pf_trace.hpp"
 #include "../pf_model_rows.hpp"
@@ -276,6 +277,96 @@ int pfh_mask_index_fastq(const char *text, uint64_t n, int final, uint64_t *byte
     return clause;
 }
 const char *pfh_mask_clause_text(int clause) { return pf_mask::clause_text(clause); }
+
+// ---- k-mers counted from reads (K-COUNT) -----------------------------------------------------------
+static pfh::CountOptions count_options(uint32_t k, uint64_t ci, uint64_t cx, uint64_t cs, int both_strands) {
+    pfh::CountOptions opt;
+    opt.k = k;
+    opt.ci = ci;
+    opt.cx = cx;
+    opt.cs = cs;
+    opt.both_strands = both_strands != 0;
+    return opt;
+}
+int pfh_count_fastq(const char *const *inputs, uint32_t n_inputs, const char *out_prefix, uint32_t k, uint64_t ci, uint64_t cx, uint64_t cs,
+                    int both_strands, const char *hist, uint64_t chunk_bytes, uint64_t initial_slots, int device, pf_count_stats *stats) {
+    if (!out_prefix || (n_inputs && !inputs)) { g_open_err = "pfh_count_fastq: inputs and output prefix are needed"; return 1; }
+    try {
+        std::vector<std::string> in;
+        for (uint32_t i = 0; i < n_inputs; ++i) in.push_back(inputs[i] ? inputs[i] : "");
+        pfh::CountOptions opt = count_options(k, ci, cx, cs, both_strands);
+        opt.chunk_bytes = chunk_bytes;
+        opt.initial_slots = initial_slots;
+        if (hist) opt.hist = hist;
+        pf_count_stats st = {};
+        const int rc = pfh::count_fastq(in, out_prefix, opt, device, st, nullptr, g_open_err);
+        if (stats) *stats = st;
+        return rc;
+    } catch (const std::exception &e) {
+        g_open_err = std::string("ploidyfrost host layer: ") + e.what();
+        return 1;
+    }
+}
+int pfh_mask_fastq_counted(const char *const *inputs, uint32_t n_inputs, const char *out_path, uint32_t k, uint64_t ci, uint64_t cx, uint64_t cs,
+                           int both_strands, const char *db_out, uint32_t low, uint32_t up, int auto_lower, uint64_t chunk_bytes, int device,
+                           pf_mask_stats *stats, uint32_t *lower_used) {
+    if (!out_path || (n_inputs && !inputs)) { g_open_err = "pfh_mask_fastq_counted: inputs and output are needed"; return 1; }
+    try {
+        std::vector<std::string> in;
+        for (uint32_t i = 0; i < n_inputs; ++i) in.push_back(inputs[i] ? inputs[i] : "");
+        pf_mask_stats st = {};
+        uint32_t lower = low;
+        const int rc = pfh::mask_fastq_counted(count_options(k, ci, cx, cs, both_strands), db_out ? db_out : "", in, out_path, low, up, auto_lower != 0,
+                                               chunk_bytes, device, st, lower, nullptr, g_open_err);
+        if (stats) *stats = st;
+        if (lower_used) *lower_used = lower;
+        return rc;
+    } catch (const std::exception &e) {
+        g_open_err = std::string("ploidyfrost host layer: ") + e.what();
+        return 1;
+    }
+}
+static void count_stats_c(const pf_count::Stats &s, pf_count_stats *out) {
+    if (!out) return;
+    *out = pf_count_stats{s.reads, s.bases, s.kmers, s.kmers_bad, s.unique, s.below_min, s.above_max, s.written};
+}
+int pfh_count_reads_host(const char *text, const uint64_t *off, const uint32_t *len, uint64_t n_reads, uint32_t k, int both_strands, uint64_t ci,
+                         uint64_t cx, uint64_t cs, uint64_t *kmers_out, uint32_t *counts_out, uint64_t cap, uint64_t *n, pf_count_stats *stats) {
+    if (n) *n = 0;
+    if (!pf_count::k_ok(k)) return pf_count::CUT_K;
+    const int clause = pf_count::cut_clause(ci, cx, cs);
+    if (clause) return clause;
+    pf_count::Table table;
+    pf_count::Stats st;
+    pf_count::count_reads_host(text, off, len, n_reads, (int)k, both_strands != 0, table, st);
+    std::vector<uint64_t> kmers;
+    std::vector<uint32_t> counts;
+    if (!pf_count::finish_host(table, (uint32_t)ci, (uint32_t)cx, (uint32_t)cs, kmers, counts, st)) return -1;
+    for (uint64_t i = 0; i < cap && i < kmers.size(); ++i) {
+        if (kmers_out) kmers_out[i] = kmers[i];
+        if (counts_out) counts_out[i] = counts[i];
+    }
+    if (n) *n = kmers.size();
+    count_stats_c(st, stats);
+    return 0;
+}
+int pfh_count_encode_kmc1(const uint64_t *kmers, const uint32_t *counts, uint64_t n, uint32_t k, uint64_t ci, uint64_t cx, uint64_t cs,
+                          int both_strands, uint8_t *pre_out, uint64_t pre_cap, uint64_t *pre_n, uint8_t *suf_out, uint64_t suf_cap, uint64_t *suf_n) {
+    if (!pf_count::k_ok(k)) return pf_count::CUT_K;
+    if (!pf_count::lut_prefix_len((int)k)) return pf_count::CUT_K_LAYOUT;
+    const int clause = pf_count::cut_clause(ci, cx, cs);
+    if (clause) return clause;
+    std::vector<uint8_t> pre, suf;
+    pf_count::encode_kmc1_host(kmers, counts, n, (int)k, pf_count::lut_prefix_len((int)k), pf_count::counter_bytes(cx, cs), ci, cx, both_strands != 0, pre, suf);
+    if (pre_out) memcpy(pre_out, pre.data(), (size_t)std::min<uint64_t>(pre_cap, pre.size()));
+    if (suf_out) memcpy(suf_out, suf.data(), (size_t)std::min<uint64_t>(suf_cap, suf.size()));
+    if (pre_n) *pre_n = pre.size();
+    if (suf_n) *suf_n = suf.size();
+    return 0;
+}
+uint32_t pfh_count_counter_bytes(uint64_t cx, uint64_t cs) { return pf_count::counter_bytes(cx, cs); }
+uint32_t pfh_count_lut_prefix_len(uint32_t k) { return (uint32_t)pf_count::lut_prefix_len((int)k); }
+const char *pfh_count_cut_text(int clause) { return pf_count::cut_text(clause); }
 
 // ---- one graph over several GPUs -------------------------------------------------------------------
 int pfh_find_shard(pfh_run *r, uint32_t u0, uint32_t u1) {

@@ -32,6 +32,7 @@
 
 #include "pf_cdbg.hpp"
 #include "pf_cutoffs.hpp"
+#include "pf_count_host.hpp"
 #include "pf_mask_host.hpp"
 #include "pf_filter.hpp"
 #include "pf_multi.hpp"
@@ -87,7 +88,9 @@ void PrintUsage() {
          << "Usage: PloidyFrost cutoffL -d <KMCDatabase>" << endl
          << "Usage: PloidyFrost cutoffU -d <KMCDatabase> (quantile[<1 ,default:0.998])" << endl
          << "Usage: PloidyFrost histogram -d <KMCDatabase> [-o <file>]   (the k-mer histogram file of the database, count<TAB>number per row)" << endl << endl
+         << "Usage: PloidyFrost count -k 25 -ci 1 -cs 10000 [-cx N] [-b] -i <reads.fq> [-i <more.fq> ...] -o <KMCDatabase> [--hist <file>] [--chunk-bytes N] [--initial-slots N] [-v]" << endl
          << "Usage: PloidyFrost mask -d <KMCDatabase> -i <reads.fq> [-i <more.fq> ...] -o <out.fq> (-l L | --auto-cutoffs) [-u U] [--chunk-bytes N] [-v]" << endl
+         << "Usage: PloidyFrost mask -k 25 [-ci N -cs N -cx N -b] -i <reads.fq> ... -o <out.fq> (-l L | --auto-cutoffs) [-u U] [--db-out <KMCDatabase>] [--chunk-bytes N]" << endl
          << "                  (`kmc_tools filter -hm <db> <reads.fq> -ci<L> [-cx<U>] <out.fq>` on the device: every base of every k-mer whose count" << endl
          << "                  lies outside [L, U] becomes N; --auto-cutoffs: L = what `cutoffL -d` prints, printed on stdout)" << endl << endl
          << "Usage: PloidyFrost model ...          (GMM ploidy inference from the coverage / frequency files; `PloidyFrost model` prints its options)" << endl
@@ -484,10 +487,90 @@ int model_main(int argc, char **argv) {
 }
 }  // namespace
 
+// kmc's letters of `count` and `mask -k`, with a detached or an attached value (-k 25, -k25, -ci1, -cs10000), and -b
+struct CountArgs {
+    pfh::CountOptions opt;
+    string seen;   // the first of -ci -cx -cs -b that was given ("" = none)
+    bool k_seen = false;
+};
+// 0 = argv[i] is none of them, 1 = taken (i stands on its last word), -1 = refused with `why`
+int take_count_option(int argc, char **argv, int &i, CountArgs &c, string &why) {
+    const string a = argv[i];
+    if (a == "-b") { c.opt.both_strands = false; if (c.seen.empty()) c.seen = "-b"; return 1; }
+    string name;
+    for (const char *o : {"-ci", "-cx", "-cs", "-k"})
+        if (a.compare(0, strlen(o), o) == 0 && (a.size() == strlen(o) || isdigit((unsigned char)a[strlen(o)]))) { name = o; break; }
+    if (name.empty()) return 0;
+    string text = a.substr(name.size());
+    if (text.empty()) {
+        if (i + 1 >= argc) { why = name + " needs a value"; return -1; }
+        text = argv[++i];
+    }
+    char *end = nullptr;
+    errno = 0;
+    unsigned long long v = strtoull(text.c_str(), &end, 10);
+    if (!isdigit((unsigned char)text[0]) || *end) { why = name + " takes a number, not '" + text + "'"; return -1; }
+    if (errno == ERANGE) v = pf_count::COUNTER_MAX + 1;   // (refused with the cut-offs, by name)
+    if (name == "-k") { c.opt.k = (uint32_t)std::min<unsigned long long>(v, 0xFFFFFFFFull); c.k_seen = true; return 1; }
+    (name == "-ci" ? c.opt.ci : name == "-cx" ? c.opt.cx : c.opt.cs) = v;
+    if (c.seen.empty()) c.seen = name;
+    return 1;
+}
+
+// `count`: step `2.kmc_db` of the reference's workflow (`kmc -ci1 -cs10000 -k25 @FILES kmc_sample tmp`) on the device
+int count_main(int argc, char **argv) {
+    const char *usage = "Usage:PloidyFrost count -k 25 -ci 1 -cs 10000 [-cx N] [-b] -i reads.fq [-i more.fq ...] -o kmc_database [--hist file] [--chunk-bytes N] [--initial-slots N] [-v]";
+    CountArgs c;
+    string out;
+    vector<string> inputs;
+    bool verbose = false;
+    auto refuse = [&](const string &why) { cerr << "Error: count: " << why << endl << usage << endl; return 1; };
+    auto number = [&](const string &opt, const char *text, uint64_t &v) {
+        char *end = nullptr;
+        errno = 0;
+        v = strtoull(text, &end, 10);
+        if (!errno && isdigit((unsigned char)text[0]) && !*end && v > 0) return true;
+        refuse(opt + " takes a positive number, not '" + text + "'");
+        return false;
+    };
+    for (int i = 2; i < argc; ++i) {
+        const string a = argv[i];
+        string why;
+        const int taken = take_count_option(argc, argv, i, c, why);
+        if (taken < 0) return refuse(why);
+        if (taken) continue;
+        const bool has_value = i + 1 < argc;
+        if (a == "-v") verbose = true;
+        else if (!has_value) return refuse(a == "-i" || a == "-o" || a == "--hist" || a == "--chunk-bytes" || a == "--initial-slots" ? a + " needs a value" : "unknown option " + a);
+        else if (a == "-i") inputs.push_back(argv[++i]);
+        else if (a == "-o") out = argv[++i];
+        else if (a == "--hist") c.opt.hist = argv[++i];
+        else if (a == "--chunk-bytes") { if (!number(a, argv[++i], c.opt.chunk_bytes)) return 1; }
+        else if (a == "--initial-slots") { if (!number(a, argv[++i], c.opt.initial_slots)) return 1; }
+        else return refuse("unknown option " + a);
+    }
+    // refused by name, before anything is read or written
+    if (inputs.empty()) return refuse("-i <reads.fq> is missing");
+    if (out.empty()) return refuse("-o <KMCDatabase> is missing");
+    { const int clause = pfh::count_options_clause(c.opt, true); if (clause) return refuse(pf_count::cut_text(clause)); }
+    pf_count_stats st = {};
+    pfh::CountTimes tm;
+    string err;
+    if (pfh::count_fastq(inputs, out, c.opt, 0, st, &tm, err)) {
+        cerr << "Error: " << err << endl;
+        return 1;
+    }
+    cerr << "count: reads " << st.reads << " bases " << st.bases << " kmers " << st.kmers << " bad " << st.kmers_bad << " unique " << st.unique << " below "
+         << st.below_min << " above " << st.above_max << " written " << st.written << endl;
+    if (verbose) cerr << "count: stream " << tm.stream_s << "s finish " << tm.finish_s << "s write " << tm.write_s << "s" << endl;
+    return 0;
+}
+
 // `mask`: step 2 of the reference's workflow (`kmc_tools filter -hm <db> <reads.fq> -ci<L> <out.fq>`) against the database on the device
 int mask_main(int argc, char **argv) {
     const char *usage = "Usage:PloidyFrost mask -d kmc_database -i reads.fq [-i more.fq ...] -o out.fq (-l L | --auto-cutoffs) [-u U] [--chunk-bytes N] [-v]";
-    string db, out;
+    string db, out, db_out;
+    CountArgs c;   // -k: the inputs are counted instead of a database read
     vector<string> inputs;
     bool l_seen = false, auto_cutoffs = false, verbose = false;
     long long low = 0, up = 0xFFFFFFFFll, chunk = 0;
@@ -502,11 +585,18 @@ int mask_main(int argc, char **argv) {
     };
     for (int i = 2; i < argc; ++i) {
         const string a = argv[i];
+        {
+            string why;
+            const int taken = take_count_option(argc, argv, i, c, why);
+            if (taken < 0) return refuse(why);
+            if (taken) continue;
+        }
         const bool has_value = i + 1 < argc;
         if (a == "--auto-cutoffs") auto_cutoffs = true;
         else if (a == "-v") verbose = true;
-        else if (!has_value) return refuse(a == "-d" || a == "-i" || a == "-o" || a == "-l" || a == "-u" || a == "--chunk-bytes" ? a + " needs a value" : "unknown option " + a);
+        else if (!has_value) return refuse(a == "-d" || a == "-i" || a == "-o" || a == "-l" || a == "-u" || a == "--chunk-bytes" || a == "--db-out" ? a + " needs a value" : "unknown option " + a);
         else if (a == "-d") db = argv[++i];
+        else if (a == "--db-out") db_out = argv[++i];
         else if (a == "-i") inputs.push_back(argv[++i]);
         else if (a == "-o") out = argv[++i];
         else if (a == "-l") { if (!number("-l", argv[++i], low)) return 1; l_seen = true; }
@@ -515,17 +605,23 @@ int mask_main(int argc, char **argv) {
         else return refuse("unknown option " + a);
     }
     // refused by name, before anything is read or written
-    if (db.empty()) return refuse("-d <KMCDatabase> is missing");
+    if (!db.empty() && c.k_seen) return refuse("-d does not go with -k (the database is either read, or counted from the inputs)");
+    if (!c.k_seen && !c.seen.empty()) return refuse(c.seen + " needs -k (it belongs to the count of the inputs)");
+    if (!c.k_seen && !db_out.empty()) return refuse("--db-out needs -k (it belongs to the count of the inputs)");
+    if (db.empty() && !c.k_seen) return refuse("-d <KMCDatabase> is missing");
     if (inputs.empty()) return refuse("-i <reads.fq> is missing");
     if (out.empty()) return refuse("-o <out.fq> is missing");
     if (l_seen && auto_cutoffs) return refuse("-l does not go with --auto-cutoffs (the lower threshold is derived: leave it out)");
     if (!l_seen && !auto_cutoffs) return refuse("the lower threshold is missing: -l L, or --auto-cutoffs to derive it from the database");
     if (l_seen && low > up) return refuse("-l " + to_string(low) + " is above -u " + to_string(up) + " (L > U)");
+    if (c.k_seen) { const int clause = pfh::count_options_clause(c.opt, !db_out.empty()); if (clause) return refuse(pf_count::cut_text(clause)); }
     pf_mask_stats st = {};
     uint32_t lower = (uint32_t)low;
     pfh::MaskTimes tm;
     string err;
-    if (pfh::mask_fastq(db, inputs, out, (uint32_t)low, (uint32_t)up, auto_cutoffs, (uint64_t)chunk, 0, st, lower, &tm, err)) {
+    const int rc = c.k_seen ? pfh::mask_fastq_counted(c.opt, db_out, inputs, out, (uint32_t)low, (uint32_t)up, auto_cutoffs, (uint64_t)chunk, 0, st, lower, &tm, err)
+                            : pfh::mask_fastq(db, inputs, out, (uint32_t)low, (uint32_t)up, auto_cutoffs, (uint64_t)chunk, 0, st, lower, &tm, err);
+    if (rc) {
         cerr << "Error: " << err << endl;
         return 1;
     }
@@ -544,6 +640,7 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[1], "filter")) return pfh::filter_main(argc, argv, false);         // script/Filter.R
     if (!strcmp(argv[1], "filter-multi")) return pfh::filter_main(argc, argv, true);    // script/Filter-multi.R
     if (!strcmp(argv[1], "mask")) return mask_main(argc, argv);
+    if (!strcmp(argv[1], "count")) return count_main(argc, argv);
     if (!strcmp(argv[1], "histogram")) {   // the file `kmc_tools transform <db> histogram <file>` writes, from the database on the device
         string db, out;
         for (int i = 2; i < argc; ++i) {

@@ -5,6 +5,7 @@
 #pragma once
 #include <stdint.h>
 
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -12,8 +13,10 @@
 
 namespace pfh {
 
+struct CountOptions;   // pf_count_host.hpp
+
 struct MaskTimes {
-    double load_s = 0;     // database: map, decode, histogram, table
+    double load_s = 0;     // database: map, decode, histogram, table (with -k: the count of the inputs instead)
     double stream_s = 0;   // first byte read to last byte written (wall)
     double device_s = 0;   // of it: inside pf_mask_fastq (upload, kernels, download)
     double read_s = 0;     // of it, beside the device: read() of the inputs
@@ -27,5 +30,39 @@ constexpr uint64_t MASK_DEFAULT_CHUNK = 256ull << 20;
 // it.  chunk_bytes = 0: MASK_DEFAULT_CHUNK.  0 = ok, else worded in err (format refusals name the input and the 1-based record).
 int mask_fastq(const std::string &db_prefix, const std::vector<std::string> &inputs, const std::string &out_path, uint32_t low, uint32_t up,
                bool auto_lower, uint64_t chunk_bytes, int device, pf_mask_stats &stats, uint32_t &lower_used, MaskTimes *times, std::string &err);
+// The same without a database (`mask -k`): the inputs are counted first (K-COUNT, pf_count_host.hpp), the finished counters give the
+// histogram and the table, and the inputs are streamed a second time through K-MASK -- what `count ... -o db` followed by
+// `mask -d db ...` gives.  db_out (may be empty): the database is written as well.
+int mask_fastq_counted(const CountOptions &count, const std::string &db_out, const std::vector<std::string> &inputs, const std::string &out_path,
+                       uint32_t low, uint32_t up, bool auto_lower, uint64_t chunk_bytes, int device, pf_mask_stats &stats, uint32_t &lower_used,
+                       MaskTimes *times, std::string &err);
+
+// ---- what `mask` and `count` share: FASTQ files streamed through a device call in chunks ----
+// pinned host memory of a context (pageable when that fails: it works, slower)
+struct ChunkBuf {
+    pf_ctx *ctx = nullptr;
+    char *p = nullptr;
+    bool pinned = false;
+    bool alloc(pf_ctx *c, size_t bytes);
+    ChunkBuf() = default;
+    ChunkBuf(const ChunkBuf &) = delete;
+    ChunkBuf &operator=(const ChunkBuf &) = delete;
+    ~ChunkBuf();
+};
+bool same_file(const std::string &a, const std::string &b);
+// The refusals that need no device, every input looked at before anything is written: no input, an input that cannot be read, FASTA,
+// gzip, an input that is one of `outputs`.  `what`: the last word of the FASTA / gzip texts ("masked", "counted").  largest: the size
+// of the largest input.
+int fastq_preflight(const char *who, const char *what, const std::vector<std::string> &inputs, const std::vector<std::string> &outputs,
+                    uint64_t &largest, std::string &err);
+// One chunk on the device: text[0, n), final = the input ends with it; out = where output bytes go (null without an output).  Fills
+// used (bytes of whole records), reads (records), bad (0-based offender within the chunk); PF_OK or the call's status (pf_last_error).
+typedef std::function<int(const char *text, uint64_t n, bool final, char *out, uint64_t &used, uint64_t &reads, uint64_t &bad)> ChunkStep;
+struct StreamTimes { double device_s = 0, read_s = 0, write_s = 0; };
+// Reader thread, device loop and (out_fd >= 0) writer thread over two pinned buffers each way, with the carry of a record across a
+// chunk edge; the used bytes of `out` of every chunk go to out_fd in order.  0 = ok, else worded in err (format refusals name the
+// input and the 1-based record from the start of that input).
+int stream_fastq(pf_ctx *ctx, const char *who, const std::vector<std::string> &inputs, uint64_t chunk_bytes, uint64_t largest, int out_fd,
+                 const std::string &out_name, const ChunkStep &step, StreamTimes &tm, std::string &err);
 
 }  // namespace pfh

@@ -29,6 +29,8 @@ HIST_MAX_BINS = 1 << 20
 K_MASK = K_HIST + 1        # PF_K_MASK ("k_mask"): everything one pf_mask_reads / pf_mask_fastq launches; unit: windows
 MASK_STATS = np.dtype([(f, "<u8") for f in ("reads", "reads_changed", "bases", "bases_masked", "kmers", "kmers_bad")])   # pf_mask_stats
 MASK_NO_UPPER = 0xFFFFFFFF
+K_COUNT = K_MASK + 1       # PF_K_COUNT ("k_count"): everything one pf_count_reads / pf_count_fastq launches; unit: windows
+COUNT_STATS = np.dtype([(f, "<u8") for f in ("reads", "bases", "kmers", "kmers_bad", "unique", "below_min", "above_max", "written")])   # pf_count_stats
 DENSITY_INFO = np.dtype([("n", "<u8"), ("min", "<f8"), ("max", "<f8"), ("sd", "<f8"), ("q1", "<f8"), ("q3", "<f8"), ("bw", "<f8"),
                          ("order", "<f8", (4,))])   # pf_density_info
 assert DENSITY_INFO.itemsize == 88
@@ -201,6 +203,12 @@ def load_library() -> C.CDLL:
         "pf_count_histogram": (i, [vp, vp, u64, u64, u64, u32, vp]),
         "pf_mask_reads": (i, [vp, vp, u64, vp, vp, u64, u32, u32, vp, vp]),
         "pf_mask_fastq": (i, [vp, vp, u64, i, u32, u32, vp, C.POINTER(u64), vp, C.POINTER(u64)]),
+        "pf_count_begin": (i, [vp, u32, i, u64]),
+        "pf_count_reads": (i, [vp, vp, u64, vp, vp, u64, vp]),
+        "pf_count_fastq": (i, [vp, vp, u64, i, C.POINTER(u64), vp, C.POINTER(u64)]),
+        "pf_count_finish": (i, [vp, u64, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), vp]),
+        "pf_count_abort": (i, [vp]),
+        "pf_kmc_encode": (i, [vp, vp, vp, u64, u32, u32, u32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError = header / library mismatch
@@ -222,7 +230,8 @@ DECLARED_SYMBOLS = ["pf_create", "pf_warmup", "pf_destroy", "pf_last_error", "pf
                     "pf_gmm_values", "pf_call_model_begin", "pf_call_model_take", "pf_call_model_finish", "pf_call_fetched_bytes",
                     "pf_call_model_filter", "pf_call_model_take_text",
                     "pf_call_model_filter_multi", "pf_call_model_color_count", "pf_call_model_color_select",
-                    "pf_gmm_density", "pf_count_histogram", "pf_mask_reads", "pf_mask_fastq"]
+                    "pf_gmm_density", "pf_count_histogram", "pf_mask_reads", "pf_mask_fastq",
+                    "pf_count_begin", "pf_count_reads", "pf_count_fastq", "pf_count_finish", "pf_count_abort", "pf_kmc_encode"]
 
 
 def density_dict(x: np.ndarray, density: np.ndarray, info: np.ndarray) -> dict:
@@ -496,6 +505,72 @@ class Device:
             e.bad_record = bad.value
             raise e
         return out[: used.value], used.value, {f: int(stats[0][f]) for f in MASK_STATS.names}
+
+    def count_begin(self, k: int, both_strands: bool = True, initial_slots: int = 0):
+        """K-COUNT (pf_count_begin): opens a count of k-mers of length k (3 .. 31); both_strands: canonical keys.  initial_slots = 0:
+        twice the first call's bytes."""
+        self._check(self.L.pf_count_begin(self.h, k, int(both_strands), initial_slots))
+
+    def count_reads(self, text, read_off, read_len):
+        """pf_count_reads: counts the reads text[read_off[i] : read_off[i] + read_len[i]] (arguments as mask_reads takes them); returns
+        this call's statistics."""
+        if isinstance(text, (bytes, bytearray)):
+            text = np.frombuffer(bytes(text), dtype=np.uint8)
+        if isinstance(read_off, (list, tuple, np.ndarray)):
+            read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
+        if isinstance(read_len, (list, tuple, np.ndarray)):
+            read_len = np.ascontiguousarray(read_len, dtype=np.uint32)
+        n, n_reads = int(text.shape[0]), int(read_off.shape[0])
+        stats = np.zeros(1, dtype=COUNT_STATS)
+        self._check(self.L.pf_count_reads(self.h, _ptr(text) if n else None, n, _ptr(read_off) if n_reads else None,
+                                          _ptr(read_len) if n_reads else None, n_reads, stats.ctypes.data))
+        return {f: int(stats[0][f]) for f in COUNT_STATS.names}
+
+    def count_fastq(self, text, final: bool = True):
+        """pf_count_fastq on one chunk of a FASTQ file: (bytes_used, this call's statistics).  A format error raises DeviceError with
+        .bad_record = the 0-based record within the chunk."""
+        if isinstance(text, (bytes, bytearray)):
+            text = np.frombuffer(bytes(text), dtype=np.uint8)
+        n = int(text.shape[0])
+        stats = np.zeros(1, dtype=COUNT_STATS)
+        used, bad = C.c_uint64(), C.c_uint64()
+        st = self.L.pf_count_fastq(self.h, _ptr(text) if n else None, n, int(final), C.byref(used), stats.ctypes.data, C.byref(bad))
+        if st != PF_OK:
+            e = DeviceError(st, self.L.pf_last_error(self.h).decode())
+            e.bad_record = bad.value
+            raise e
+        return used.value, {f: int(stats[0][f]) for f in COUNT_STATS.names}
+
+    def count_finish(self, ci: int = 2, cx: int = 10 ** 9, cs: int = 255):
+        """pf_count_finish: (kmers u64 sorted, counts u32 = min(c, cs), statistics of the whole count) copied back to the host."""
+        dk, dc, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        stats = np.zeros(1, dtype=COUNT_STATS)
+        self._check(self.L.pf_count_finish(self.h, ci, cx, cs, C.byref(dk), C.byref(dc), C.byref(n), stats.ctypes.data))
+        km, ct = np.zeros(n.value, dtype=np.uint64), np.zeros(n.value, dtype=np.uint32)
+        try:
+            if n.value:
+                self._check(self.L.pf_copy_to_host(self.h, _ptr(km), dk, n.value * 8))
+                self._check(self.L.pf_copy_to_host(self.h, _ptr(ct), dc, n.value * 4))
+        finally:
+            self.L.pf_device_free(self.h, dk)
+            self.L.pf_device_free(self.h, dc)
+        return km, ct, {f: int(stats[0][f]) for f in COUNT_STATS.names}
+
+    def count_abort(self):
+        self._check(self.L.pf_count_abort(self.h))
+
+    def kmc_encode(self, kmers, counts, k: int, p: int, counter_bytes: int):
+        """pf_kmc_encode, the inverse of kmc_decode: (records u8, lut u64 of 4^p + 1 entries) of sorted distinct k-mers.  kmers / counts:
+        numpy arrays or device tensors."""
+        if isinstance(kmers, np.ndarray):
+            kmers = np.ascontiguousarray(kmers, dtype=np.uint64)
+        if isinstance(counts, np.ndarray):
+            counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        n = int(kmers.shape[0])
+        rec = np.zeros(max(n * ((k - p) // 4 + counter_bytes), 1), dtype=np.uint8)
+        lut = np.zeros(4 ** p + 1, dtype=np.uint64)
+        self._check(self.L.pf_kmc_encode(self.h, _ptr(kmers) if n else None, _ptr(counts) if n else None, n, k, p, counter_bytes, _ptr(rec), _ptr(lut)))
+        return rec[: n * ((k - p) // 4 + counter_bytes)], lut
 
     def lookup(self, kmers: np.ndarray):
         n = len(kmers)

@@ -40,7 +40,9 @@ DECLARED_SYMBOLS = ["pfh_open", "pfh_close", "pfh_last_error", "pfh_set_output_d
                     "pfh_gmm_read_column", "pfh_gmm_density", "pfh_gmm_write_density", "pfh_gmm_density_time",
                     "pfh_set_density", "pfh_model_density_points", "pfh_model_density", "pfh_model_color_density",
                     "pfh_kmc_histogram", "pfh_cutoffs_from_rows", "pfh_set_auto_cutoffs", "pfh_cutoffs",
-                    "pfh_mask_fastq", "pfh_mask_read", "pfh_mask_index_fastq", "pfh_mask_clause_text"]
+                    "pfh_mask_fastq", "pfh_mask_read", "pfh_mask_index_fastq", "pfh_mask_clause_text",
+                    "pfh_count_fastq", "pfh_mask_fastq_counted", "pfh_count_reads_host", "pfh_count_encode_kmc1", "pfh_count_counter_bytes",
+                    "pfh_count_lut_prefix_len", "pfh_count_cut_text"]
 
 
 class FilterOpts(C.Structure):   # pf_filter_opts (include/ploidyfrost_hip.h)
@@ -189,6 +191,17 @@ def load_library() -> C.CDLL:
     L.pfh_mask_index_fastq.argtypes = [vp, u64, C.c_int, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp, vp, u64]
     L.pfh_mask_clause_text.restype = C.c_char_p
     L.pfh_mask_clause_text.argtypes = [C.c_int]
+    L.pfh_count_fastq.argtypes = [C.POINTER(C.c_char_p), u32, C.c_char_p, u32, u64, u64, u64, C.c_int, C.c_char_p, u64, u64, C.c_int, vp]
+    L.pfh_mask_fastq_counted.argtypes = [C.POINTER(C.c_char_p), u32, C.c_char_p, u32, u64, u64, u64, C.c_int, C.c_char_p, u32, u32, C.c_int, u64, C.c_int,
+                                         vp, C.POINTER(u32)]
+    L.pfh_count_reads_host.argtypes = [vp, vp, vp, u64, u32, C.c_int, u64, u64, u64, vp, vp, u64, C.POINTER(u64), vp]
+    L.pfh_count_encode_kmc1.argtypes = [vp, vp, u64, u32, u64, u64, u64, C.c_int, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64)]
+    L.pfh_count_counter_bytes.restype = u32
+    L.pfh_count_counter_bytes.argtypes = [u64, u64]
+    L.pfh_count_lut_prefix_len.restype = u32
+    L.pfh_count_lut_prefix_len.argtypes = [u32]
+    L.pfh_count_cut_text.restype = C.c_char_p
+    L.pfh_count_cut_text.argtypes = [C.c_int]
     _lib = L
     return L
 
@@ -442,6 +455,95 @@ def mask_index_fastq(text: bytes, final: bool = True):
     clause = L.pfh_mask_index_fastq(src.ctypes.data if n else None, n, int(final), C.byref(used), C.byref(recs), C.byref(bad), off.ctypes.data, ln.ctypes.data, cap)
     return dict(clause=MASK_CLAUSES[clause], message=L.pfh_mask_clause_text(clause).decode(), bad_record=bad.value, bytes_used=used.value,
                 n_records=recs.value, read_off=off[: recs.value].copy(), read_len=ln[: recs.value].copy())
+
+
+COUNT_STATS_FIELDS = ("reads", "bases", "kmers", "kmers_bad", "unique", "below_min", "above_max", "written")   # pf_count_stats
+COUNT_CUT_CLAUSES = ("none", "ci_zero", "ci_above_cx", "cs_zero", "too_large", "k", "k_layout")                               # pf_count::CutClause, in its order
+
+
+def _paths(inputs):
+    if isinstance(inputs, (str, bytes, os.PathLike)):
+        inputs = [inputs]
+    return (C.c_char_p * max(len(inputs), 1))(*[os.fsencode(p) for p in inputs]), len(inputs)
+
+
+def count_fastq(inputs, out_prefix: str, k: int = 25, ci: int = 2, cx: int = 10 ** 9, cs: int = 255, both_strands: bool = True, hist=None,
+                chunk_bytes: int = 0, initial_slots: int = 0) -> dict:
+    """`ploidyfrost count` (pfh_count_fastq): the k-mers of the FASTQ file(s) `inputs` counted on the device (K-COUNT), those with
+    ci <= c <= cx written as min(c, cs) to <out_prefix>.kmc_pre / .kmc_suf in the KMC1 layout; hist: the histogram file of the finished
+    counters.  Returns the statistics.  A refusal raises RuntimeError by name (format refusals with the input's path and the 1-based
+    record number); nothing is left under the output names."""
+    L = load_library()
+    paths, n = _paths(inputs)
+    stats = np.zeros(len(COUNT_STATS_FIELDS), dtype=np.uint64)
+    rc = L.pfh_count_fastq(paths, n, os.fsencode(out_prefix), int(k), int(ci), int(cx), int(cs), int(both_strands),
+                           None if hist is None else os.fsencode(hist), int(chunk_bytes), int(initial_slots), 0, stats.ctypes.data)
+    if rc:
+        raise RuntimeError(L.pfh_last_error(None).decode())
+    return {f: int(v) for f, v in zip(COUNT_STATS_FIELDS, stats)}
+
+
+def mask_fastq_counted(inputs, out: str, k: int = 25, ci: int = 2, cx: int = 10 ** 9, cs: int = 255, both_strands: bool = True, db_out=None,
+                       lower=None, upper=None, auto: bool = False, chunk_bytes: int = 0) -> dict:
+    """`ploidyfrost mask -k` (pfh_mask_fastq_counted): mask_fastq without a database -- the inputs are counted first, then masked
+    against their own counters; db_out: the database is written as well."""
+    L = load_library()
+    if auto == (lower is not None):
+        raise ValueError("mask_fastq_counted: either lower=L or auto=True")
+    paths, n = _paths(inputs)
+    stats = np.zeros(len(MASK_STATS_FIELDS), dtype=np.uint64)
+    used = C.c_uint32()
+    rc = L.pfh_mask_fastq_counted(paths, n, os.fsencode(out), int(k), int(ci), int(cx), int(cs), int(both_strands),
+                                  None if db_out is None else os.fsencode(db_out), 0 if lower is None else int(lower),
+                                  0xFFFFFFFF if upper is None else int(upper), int(auto), int(chunk_bytes), 0, stats.ctypes.data, C.byref(used))
+    if rc:
+        raise RuntimeError(L.pfh_last_error(None).decode())
+    d = {f: int(v) for f, v in zip(MASK_STATS_FIELDS, stats)}
+    d["lower"] = used.value
+    return d
+
+
+def count_reads_host(text: bytes, read_off, read_len, k: int, both_strands: bool = True, ci: int = 2, cx: int = 10 ** 9, cs: int = 255):
+    """(kmers u64 sorted, counts u32, stats dict): the rule of `count` on the host (pfh_count_reads_host; no device).  A refusal of the
+    options raises ValueError with its name of COUNT_CUT_CLAUSES and its text."""
+    L = load_library()
+    src = np.frombuffer(bytes(text), dtype=np.uint8)
+    off = np.ascontiguousarray(read_off, dtype=np.uint64)
+    ln = np.ascontiguousarray(read_len, dtype=np.uint32)
+    cap = max(int(ln.astype(np.int64).sum()), 1)
+    kmers, counts = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint32)
+    n = C.c_uint64()
+    stats = np.zeros(len(COUNT_STATS_FIELDS), dtype=np.uint64)
+    rc = L.pfh_count_reads_host(src.ctypes.data if len(src) else None, off.ctypes.data, ln.ctypes.data, len(off), int(k), int(both_strands), int(ci),
+                                int(cx), int(cs), kmers.ctypes.data, counts.ctypes.data, cap, C.byref(n), stats.ctypes.data)
+    if rc > 0:
+        raise ValueError("%s: %s" % (COUNT_CUT_CLAUSES[rc], L.pfh_count_cut_text(rc).decode()))
+    if rc < 0:
+        raise OverflowError("a k-mer occurs more than 4294967295 times")
+    return kmers[: n.value].copy(), counts[: n.value].copy(), {f: int(v) for f, v in zip(COUNT_STATS_FIELDS, stats)}
+
+
+def count_encode_kmc1(kmers, counts, k: int, ci: int = 2, cx: int = 10 ** 9, cs: int = 255, both_strands: bool = True):
+    """(bytes of .kmc_pre, bytes of .kmc_suf) for sorted distinct k-mers, by the host's restatement (pfh_count_encode_kmc1)"""
+    L = load_library()
+    km = np.ascontiguousarray(kmers, dtype=np.uint64)
+    ct = np.ascontiguousarray(counts, dtype=np.uint32)
+    pn, sn = C.c_uint64(), C.c_uint64()
+    args = (km.ctypes.data, ct.ctypes.data, len(km), int(k), int(ci), int(cx), int(cs), int(both_strands))
+    rc = L.pfh_count_encode_kmc1(*args, None, 0, C.byref(pn), None, 0, C.byref(sn))
+    if rc:
+        raise ValueError("%s: %s" % (COUNT_CUT_CLAUSES[rc], L.pfh_count_cut_text(rc).decode()))
+    pre, suf = np.zeros(pn.value, dtype=np.uint8), np.zeros(sn.value, dtype=np.uint8)
+    L.pfh_count_encode_kmc1(*args, pre.ctypes.data, len(pre), C.byref(pn), suf.ctypes.data, len(suf), C.byref(sn))
+    return pre.tobytes(), suf.tobytes()
+
+
+def count_counter_bytes(cx: int, cs: int) -> int:
+    return int(load_library().pfh_count_counter_bytes(int(cx), int(cs)))
+
+
+def count_lut_prefix_len(k: int) -> int:
+    return int(load_library().pfh_count_lut_prefix_len(int(k)))
 
 
 def load_trace(reset: bool = True) -> list:
