@@ -66,6 +66,7 @@ enum pf_kernel {
     PF_K_HIST, /* K-HIST (pf_count_histogram); unit: counters */
     PF_K_MASK, /* K-MASK: everything one pf_mask_reads / pf_mask_fastq launches (index, classes, flag, paint), timed as one launch; unit: windows */
     PF_K_COUNT, /* K-COUNT: everything one pf_count_reads / pf_count_fastq launches (index, classes, insert, growth), timed as one launch; unit: windows */
+    PF_K_TRIM, /* K-TRIM: everything one pf_trim_fastq / pf_trim_fastq_pair launches (index, intervals, sizes, scan, copy), timed as one launch; unit: records */
     PF_K_COUNT_
 };
 int pf_enable_timing(pf_ctx *, int on);
@@ -223,6 +224,49 @@ int pf_count_abort(pf_ctx *);
  * records needs no table).  kmers, counts, records_out, lut_out: [host|dev] */
 int pf_kmc_encode(pf_ctx *, const uint64_t *kmers, const uint32_t *counts, uint64_t n, uint32_t k, uint32_t lut_prefix_len, uint32_t counter_bytes,
                   uint8_t *records_out, uint64_t *lut_out);
+/* K-TRIM: reads quality-trimmed on the device -- what step `1.trim` of the reference's workflow does with
+ * `trimmomatic PE -phred33 ... LEADING:10 TRAILING:10 SLIDINGWINDOW:3:20 MINLEN:50`.  The rule (csrc/pf_trim_rule.hpp): the quality of
+ * position i of a read of n bases is q[i] = (int)byte - phred (phred 33 or 64; signed); the state is an interval [b, e) of the read,
+ * [0, n) at first, or dropped; up to PF_TRIM_MAX_STEPS steps apply in the order given.  LEADING:t  b = the first i of [b, e) with
+ * q[i] >= t, none: dropped.  TRAILING:t  e = 1 + the last such i, none: dropped.  SLIDINGWINDOW:w:t  e - b < w: dropped; window j is
+ * bad when q[b+j] + .. + q[b+j+w-1] < w * t; window 0 bad: dropped; else with j the first bad window e = b + j - 1 + w (the end of the
+ * last good window).  MINLEN:l  e - b < l: dropped.  e == b after the last step: dropped.  0 <= t <= 93, 1 <= w <= 64.  A kept record is
+ * written as header content, seq[b:e], plus-line content, qual[b:e], each followed by one '\n' (CRLF input comes out with '\n', a
+ * last line without a newline gets one); a dropped record writes nothing.  PARITY with Trimmomatic UNPINNED (the tool is not part of
+ * the build): whether bases below t at the end of the last good window go too is the one open point (pf_trim::sliding_end).
+ * Integers only: the same bytes and statistics on every call.  Bad steps or a bad phred: PF_ERR_ARG by name. */
+enum { PF_TRIM_LEADING = 1, PF_TRIM_TRAILING = 2, PF_TRIM_SLIDINGWINDOW = 3, PF_TRIM_MINLEN = 4 };
+#define PF_TRIM_MAX_STEPS 8
+typedef struct pf_trim_step {
+    uint32_t kind;   /* PF_TRIM_LEADING .. PF_TRIM_MINLEN */
+    uint32_t a;      /* t of LEADING / TRAILING, w of SLIDINGWINDOW, l of MINLEN */
+    uint32_t b;      /* t of SLIDINGWINDOW, else 0 */
+} pf_trim_step;
+typedef struct pf_trim_stats {
+    uint64_t reads;       /* per file: records seen */
+    uint64_t kept;        /* ... written */
+    uint64_t dropped;     /* ... not written */
+    uint64_t bases;       /* ... quality bytes of the records seen */
+    uint64_t bases_kept;  /* ... of them written */
+    uint64_t both;        /* pair calls (else 0): pairs with both records kept */
+    uint64_t only1;       /* ... with the record of file 1 alone */
+    uint64_t only2;       /* ... with the record of file 2 alone */
+    uint64_t neither;     /* ... with none */
+} pf_trim_stats;
+/* one chunk (fewer than 2^32 bytes) of a FASTQ file: the chunk contract and the format clauses of pf_mask_fastq; a refused chunk has
+ * written nothing.  out holds n_bytes + 1 bytes, *out_bytes of them are written.  rec_begin / rec_len (may be NULL, one entry per
+ * whole record of the chunk -- at most n_bytes / 4; len 0 = dropped).  text, out, rec_begin, rec_len: [host|dev] */
+int pf_trim_fastq(pf_ctx *, const char *text, uint64_t n_bytes, int final, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred,
+                  char *out, uint64_t *out_bytes, uint64_t *bytes_used, uint32_t *rec_begin, uint32_t *rec_len, uint64_t *n_records,
+                  pf_trim_stats *stats, uint64_t *bad_record);
+/* one chunk of each file of a pair: record r of file 1 pairs with record r of file 2 (header names are not compared).  Both chunks are
+ * indexed and n = the smaller of their whole-record counts is taken from each: bytes_used[f] = the end of record n - 1 of file f; final
+ * chunks with different counts are refused by name.  Both kept: out[0] (o1) and out[2] (o2); file 1 alone: out[1] (u1); file 2 alone:
+ * out[3] (u2); out[0], out[1] hold n1 + 1 bytes, out[2], out[3] n2 + 1.  *bad_record = 2 * record + file (0, 1).  stats[f]: file f;
+ * the pair fields are the same in both.  The pointers inside out / rec_begin / rec_len: [host|dev] */
+int pf_trim_fastq_pair(pf_ctx *, const char *text1, uint64_t n1, const char *text2, uint64_t n2, int final, const pf_trim_step *steps,
+                       uint32_t n_steps, uint32_t phred, char *out[4], uint64_t out_bytes[4], uint64_t bytes_used[2], uint32_t *rec_begin[2],
+                       uint32_t *rec_len[2], uint64_t *n_records, pf_trim_stats stats[2], uint64_t *bad_record);
 int pf_copy_to_host(pf_ctx *, void *dst, const void *src_dev, size_t bytes);
 
 /* K1/K2: builds the device hash table from the database records (exact k-mers as stored, any

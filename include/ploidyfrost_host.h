@@ -129,6 +129,34 @@ int pfh_count_encode_kmc1(const uint64_t *kmers, const uint32_t *counts, uint64_
 uint32_t pfh_count_counter_bytes(uint64_t cx, uint64_t cs);
 uint32_t pfh_count_lut_prefix_len(uint32_t k);
 const char *pfh_count_cut_text(int clause);
+/* ---- reads quality-trimmed (K-TRIM, pf_trim_fastq / pf_trim_fastq_pair in ploidyfrost_hip.h) ----
+ * Step `1.trim` of the reference's workflow (`trimmomatic PE -phred33 r1 r2 trim1 u1 trim2 u2 LEADING:10 TRAILING:10 SLIDINGWINDOW:3:20
+ * MINLEN:50`) in one call.  The rule: csrc/pf_trim_rule.hpp (parity with Trimmomatic unpinned: the tool is not part of the build).
+ * pfh_trim_fastq: single-ended -- the inputs, one after the other, streamed through pf_trim_fastq in chunks of chunk_bytes (0: 256 MB;
+ * the chunk contract and the format refusals of pfh_mask_fastq) into out_path.  pfh_trim_fastq_pair: record r of in1 pairs with record
+ * r of in2; out_paths = o1 u1 o2 u2 (both kept -> o1 / o2, file 1 alone -> u1, file 2 alone -> u2); each file keeps its own carry, and
+ * a file that ends while the other still holds a whole record is refused by name with the record counts; stats[f]: file f.
+ * trimlog (may be NULL): one line per record in input order (pairs: record r of file 1, then of file 2),
+ * `<header without '@'> <kept length> <b> <e> <n - e>`, a dropped record `0 0 0 0`.  Every output is written under a temporary name
+ * and renamed at the end; nothing is left under any name after a refusal.  Refused by name before a device context exists: the steps
+ * (unknown kind, value out of range, more than 8, none), phred other than 33 or 64, no or unreadable input, FASTA, gzip, an output
+ * that is an input, two outputs with the same path.  0 = ok, else pfh_last_error(NULL).
+ * The host's plain restatement of the rule, no device involved:
+ * pfh_trim_parse_step: one of Trimmomatic's words ("LEADING:10") into a step; returns the refusal (0 = none; pfh_trim_refusal_text
+ * names it).  pfh_trim_read: the rule on one quality line: 1 = kept with [*begin, *end), 0 = dropped, -1 = the steps or phred are
+ * refused (pfh_last_error(NULL)).  pfh_trim_fastq_chunk: what pf_trim_fastq gives for one chunk: returns the format clause of the
+ * smallest offending record (0 = none; pfh_mask_clause_text names it), -1 = the steps are refused; out holds n + 1 bytes; rec_begin /
+ * rec_len (may be NULL): cap entries. */
+int pfh_trim_fastq(const char *const *inputs, uint32_t n_inputs, const char *out_path, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred,
+                   const char *trimlog, uint64_t chunk_bytes, int device, pf_trim_stats *stats);
+int pfh_trim_fastq_pair(const char *in1, const char *in2, const char *const *out_paths, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred,
+                        const char *trimlog, uint64_t chunk_bytes, int device, pf_trim_stats *stats);
+int pfh_trim_parse_step(const char *word, pf_trim_step *step);
+const char *pfh_trim_refusal_text(int refusal);
+int pfh_trim_read(const char *qual, uint64_t n, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, uint32_t *begin, uint32_t *end);
+int pfh_trim_fastq_chunk(const char *text, uint64_t n, int final, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, char *out,
+                         uint64_t *out_bytes, uint64_t *bytes_used, uint32_t *rec_begin, uint32_t *rec_len, uint64_t cap, uint64_t *n_records,
+                         pf_trim_stats *stats, uint64_t *bad_record);
 void pfh_get_times(const pfh_run *, pfh_times *out);
 /* Where the loads of this process spent their time (GFA map / parse / upload, count database, join, adjacency, numbering, ...):
  * "step\tseconds\n" per step since the last reset, in the order the steps ended (steps of helper threads overlap those of the

@@ -11,6 +11,8 @@
 #include "pf_mask_host.hpp"
 #include "pf_count_host.hpp"
 #include "../pf_mask_rule.hpp"
+#include "../pf_trim_rule.hpp"
+#include "pf_trim_host.hpp"
 #include "pf_trace.hpp"
 #include "../pf_model_rows.hpp"
 #include "../pf_filter_rows.hpp"
@@ -277,6 +279,85 @@ int pfh_mask_index_fastq(const char *text, uint64_t n, int final, uint64_t *byte
     return clause;
 }
 const char *pfh_mask_clause_text(int clause) { return pf_mask::clause_text(clause); }
+
+// ---- reads quality-trimmed (K-TRIM) ------------------------------------------------------------------
+static pfh::TrimOptions trim_options(const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, const char *trimlog, uint64_t chunk_bytes) {
+    pfh::TrimOptions opt;
+    if (steps) opt.steps.assign(steps, steps + n_steps);
+    opt.phred = phred;
+    opt.trimlog = trimlog ? trimlog : "";
+    opt.chunk_bytes = chunk_bytes;
+    return opt;
+}
+int pfh_trim_fastq(const char *const *inputs, uint32_t n_inputs, const char *out_path, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred,
+                   const char *trimlog, uint64_t chunk_bytes, int device, pf_trim_stats *stats) {
+    if (!out_path || (n_inputs && !inputs)) { g_open_err = "pfh_trim_fastq: inputs and output are needed"; return 1; }
+    try {
+        std::vector<std::string> in;
+        for (uint32_t i = 0; i < n_inputs; ++i) in.push_back(inputs[i] ? inputs[i] : "");
+        pf_trim_stats st = {};
+        const int rc = pfh::trim_fastq(in, out_path, trim_options(steps, n_steps, phred, trimlog, chunk_bytes), device, st, nullptr, g_open_err);
+        if (stats) *stats = st;
+        return rc;
+    } catch (const std::exception &e) {
+        g_open_err = std::string("ploidyfrost host layer: ") + e.what();
+        return 1;
+    }
+}
+int pfh_trim_fastq_pair(const char *in1, const char *in2, const char *const *out_paths, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred,
+                        const char *trimlog, uint64_t chunk_bytes, int device, pf_trim_stats *stats) {
+    if (!in1 || !in2 || !out_paths || !out_paths[0] || !out_paths[1] || !out_paths[2] || !out_paths[3]) {
+        g_open_err = "pfh_trim_fastq_pair: two inputs and four outputs are needed";
+        return 1;
+    }
+    try {
+        const std::string out[4] = {out_paths[0], out_paths[1], out_paths[2], out_paths[3]};
+        pf_trim_stats st[2] = {};
+        const int rc = pfh::trim_fastq_pair(in1, in2, out, trim_options(steps, n_steps, phred, trimlog, chunk_bytes), device, st, nullptr, g_open_err);
+        if (stats) { stats[0] = st[0]; stats[1] = st[1]; }
+        return rc;
+    } catch (const std::exception &e) {
+        g_open_err = std::string("ploidyfrost host layer: ") + e.what();
+        return 1;
+    }
+}
+int pfh_trim_parse_step(const char *word, pf_trim_step *step) {
+    pf_trim::Step s;
+    const int c = pf_trim::parse_step(word ? word : "", s);
+    if (step) *step = pf_trim_step{s.kind, s.a, s.b};
+    return c;
+}
+const char *pfh_trim_refusal_text(int refusal) { return pf_trim::refusal_text(refusal); }
+int pfh_trim_read(const char *qual, uint64_t n, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, uint32_t *begin, uint32_t *end) {
+    if (pfh::trim_options_clause(trim_options(steps, n_steps, phred, nullptr, 0), g_open_err)) return -1;
+    if (n > 0xFFFFFFFFull) { g_open_err = "pfh_trim_read: a read holds fewer than 2^32 bases"; return -1; }
+    uint32_t b = 0, e = 0;
+    const bool kept = pf_trim::trim_read(qual, (uint32_t)n, reinterpret_cast<const pf_trim::Step *>(steps), n_steps, phred, b, e);
+    if (begin) *begin = b;
+    if (end) *end = e;
+    return kept ? 1 : 0;
+}
+int pfh_trim_fastq_chunk(const char *text, uint64_t n, int final, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, char *out,
+                         uint64_t *out_bytes, uint64_t *bytes_used, uint32_t *rec_begin, uint32_t *rec_len, uint64_t cap, uint64_t *n_records,
+                         pf_trim_stats *stats, uint64_t *bad_record) {
+    if (pfh::trim_options_clause(trim_options(steps, n_steps, phred, nullptr, 0), g_open_err)) return -1;
+    std::string o;
+    std::vector<uint32_t> rb, rl;
+    uint64_t used = 0, recs = 0, bad = 0;
+    pf_trim::Stats st = {};
+    const int clause = pf_trim::trim_fastq(text, n, final != 0, reinterpret_cast<const pf_trim::Step *>(steps), n_steps, phred, o, used, recs, bad, &rb, &rl, &st);
+    if (out_bytes) *out_bytes = o.size();
+    if (out && !o.empty()) memcpy(out, o.data(), o.size());
+    if (bytes_used) *bytes_used = used;
+    if (n_records) *n_records = recs;
+    if (bad_record) *bad_record = bad;
+    if (stats) memcpy(stats, &st, sizeof st);
+    for (uint64_t i = 0; i < cap && i < rb.size(); ++i) {
+        if (rec_begin) rec_begin[i] = rb[i];
+        if (rec_len) rec_len[i] = rl[i];
+    }
+    return clause;
+}
 
 // ---- k-mers counted from reads (K-COUNT) -----------------------------------------------------------
 static pfh::CountOptions count_options(uint32_t k, uint64_t ci, uint64_t cx, uint64_t cs, int both_strands) {

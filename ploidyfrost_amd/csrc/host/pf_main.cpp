@@ -34,6 +34,8 @@
 #include "pf_cutoffs.hpp"
 #include "pf_count_host.hpp"
 #include "pf_mask_host.hpp"
+#include "pf_trim_host.hpp"
+#include "../pf_trim_rule.hpp"
 #include "pf_filter.hpp"
 #include "pf_multi.hpp"
 #include "pf_gmm_model.hpp"
@@ -93,6 +95,9 @@ void PrintUsage() {
          << "Usage: PloidyFrost mask -k 25 [-ci N -cs N -cx N -b] -i <reads.fq> ... -o <out.fq> (-l L | --auto-cutoffs) [-u U] [--db-out <KMCDatabase>] [--chunk-bytes N]" << endl
          << "                  (`kmc_tools filter -hm <db> <reads.fq> -ci<L> [-cx<U>] <out.fq>` on the device: every base of every k-mer whose count" << endl
          << "                  lies outside [L, U] becomes N; --auto-cutoffs: L = what `cutoffL -d` prints, printed on stdout)" << endl << endl
+         << "Usage: PloidyFrost trim -i <reads.fq> [-i <more.fq> ...] -o <trimmed.fq> STEP... [--phred 33|64] [--trimlog <file>] [--chunk-bytes N] [-v]" << endl
+         << "Usage: PloidyFrost trim -1 <r1.fq> -2 <r2.fq> -o1 <p1.fq> -u1 <u1.fq> -o2 <p2.fq> -u2 <u2.fq> STEP... [the same options]" << endl
+         << "                  (`trimmomatic SE|PE` on the device; STEP: LEADING:t TRAILING:t SLIDINGWINDOW:w:t MINLEN:l, applied in the order given)" << endl << endl
          << "Usage: PloidyFrost model ...          (GMM ploidy inference from the coverage / frequency files; `PloidyFrost model` prints its options)" << endl
          << "Usage: PloidyFrost density -f <column file> -o <outfile_prefix> [-n points] [-a adjust]   (kernel density of a column of numbers)" << endl
          << "Usage: PloidyFrost filter ...         (the row predicates of script/Filter.R over <prefix>_*cov.txt; -h prints its options)" << endl
@@ -633,6 +638,81 @@ int mask_main(int argc, char **argv) {
     return 0;
 }
 
+// `trim`: step 1 of the reference's workflow (`trimmomatic PE -phred33 r1 r2 trim1 u1 trim2 u2 LEADING:10 TRAILING:10 SLIDINGWINDOW:3:20
+// MINLEN:50`) on the device; the steps are Trimmomatic's words as positional arguments
+int trim_main(int argc, char **argv) {
+    const char *usage = "Usage:PloidyFrost trim -i reads.fq [-i more.fq ...] -o trimmed.fq STEP... [--phred 33|64] [--trimlog file] [--chunk-bytes N] [-v]\n"
+                        "      PloidyFrost trim -1 r1.fq -2 r2.fq -o1 p1.fq -u1 u1.fq -o2 p2.fq -u2 u2.fq STEP... [the same options]\n"
+                        "      STEP: LEADING:t TRAILING:t SLIDINGWINDOW:w:t MINLEN:l";
+    vector<string> inputs, words;
+    string out, in_pair[2], out_pair[4];
+    pfh::TrimOptions opt;
+    bool verbose = false;
+    auto refuse = [&](const string &why) { cerr << "Error: trim: " << why << endl << usage << endl; return 1; };
+    const char *pair_opts[6] = {"-1", "-2", "-o1", "-u1", "-o2", "-u2"};
+    for (int i = 2; i < argc; ++i) {
+        const string a = argv[i];
+        if (a.empty() || a[0] != '-') { words.push_back(a); continue; }
+        if (a == "-v") { verbose = true; continue; }
+        const bool known = a == "-i" || a == "-o" || a == "--phred" || a == "--trimlog" || a == "--chunk-bytes" ||
+                           std::find_if(pair_opts, pair_opts + 6, [&](const char *o) { return a == o; }) != pair_opts + 6;
+        if (!known) return refuse("unknown option " + a);
+        if (i + 1 >= argc) return refuse(a + " needs a value");
+        const string v = argv[++i];
+        if (a == "-i") inputs.push_back(v);
+        else if (a == "-o") out = v;
+        else if (a == "--trimlog") opt.trimlog = v;
+        else if (a == "--phred") {
+            if (v != "33" && v != "64") return refuse("--phred takes 33 or 64, not '" + v + "'");
+            opt.phred = (uint32_t)stoi(v);
+        } else if (a == "--chunk-bytes") {
+            char *end = nullptr;
+            errno = 0;
+            opt.chunk_bytes = strtoull(v.c_str(), &end, 10);
+            if (errno || !isdigit((unsigned char)v[0]) || *end || !opt.chunk_bytes) return refuse("--chunk-bytes takes a positive number, not '" + v + "'");
+        } else {
+            for (int j = 0; j < 6; ++j)
+                if (a == pair_opts[j]) (j < 2 ? in_pair[j] : out_pair[j - 2]) = v;
+        }
+    }
+    // refused by name, before anything is read or written
+    {
+        vector<const char *> w;
+        for (const string &x : words) w.push_back(x.c_str());
+        vector<pf_trim::Step> steps;
+        size_t bad = 0;
+        const int c = pf_trim::parse_steps(w.data(), w.size(), steps, &bad);
+        if (c == pf_trim::REFUSE_NO_STEP) return refuse(pf_trim::refusal_text(c));
+        if (c) return refuse(words[bad] + ": " + pf_trim::refusal_text(c));
+        for (const pf_trim::Step &st : steps) opt.steps.push_back(pf_trim_step{st.kind, st.a, st.b});
+    }
+    const bool pair_in = !in_pair[0].empty() || !in_pair[1].empty();
+    const bool pair_out = !out_pair[0].empty() || !out_pair[1].empty() || !out_pair[2].empty() || !out_pair[3].empty();
+    if (!inputs.empty() && pair_in) return refuse("-i does not go with -1 / -2 (the inputs are either single-ended or one pair)");
+    if (pair_in && !out.empty()) return refuse("-o does not go with -1 / -2 (a pair is written to -o1 -u1 -o2 -u2)");
+    if (!pair_in && pair_out) return refuse(inputs.empty() ? "-1 <r1.fq> and -2 <r2.fq> are missing" : "-o1 -u1 -o2 -u2 do not go with -i (single-ended reads are written to -o)");
+    pf_trim_stats st[2] = {};
+    pfh::TrimTimes tm;
+    string err;
+    if (pair_in) {
+        for (int j = 0; j < 2; ++j)
+            if (in_pair[j].empty()) return refuse(string(pair_opts[j]) + " <r" + to_string(j + 1) + ".fq> is missing");
+        for (int j = 0; j < 4; ++j)
+            if (out_pair[j].empty()) return refuse(string(pair_opts[2 + j]) + " <out.fq> is missing");
+        if (pfh::trim_fastq_pair(in_pair[0], in_pair[1], out_pair, opt, 0, st, &tm, err)) { cerr << "Error: " << err << endl; return 1; }
+        cerr << "trim: pairs " << st[0].reads << " both " << st[0].both << " forward_only " << st[0].only1 << " reverse_only " << st[0].only2 << " dropped "
+             << st[0].neither << " bases " << st[0].bases + st[1].bases << " bases_kept " << st[0].bases_kept + st[1].bases_kept << endl;
+    } else {
+        if (inputs.empty()) return refuse("-i <reads.fq> is missing (or -1 <r1.fq> -2 <r2.fq> for a pair)");
+        if (out.empty()) return refuse("-o <trimmed.fq> is missing");
+        if (pfh::trim_fastq(inputs, out, opt, 0, st[0], &tm, err)) { cerr << "Error: " << err << endl; return 1; }
+        cerr << "trim: reads " << st[0].reads << " kept " << st[0].kept << " dropped " << st[0].dropped << " bases " << st[0].bases << " bases_kept "
+             << st[0].bases_kept << endl;
+    }
+    if (verbose) cerr << "trim: stream " << tm.stream_s << "s (device " << tm.device_s << "s, read " << tm.read_s << "s, write " << tm.write_s << "s)" << endl;
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) { PrintUsage(); return 0; }
     if (!strcmp(argv[1], "model")) return model_main(argc, argv);
@@ -641,6 +721,7 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[1], "filter-multi")) return pfh::filter_main(argc, argv, true);    // script/Filter-multi.R
     if (!strcmp(argv[1], "mask")) return mask_main(argc, argv);
     if (!strcmp(argv[1], "count")) return count_main(argc, argv);
+    if (!strcmp(argv[1], "trim")) return trim_main(argc, argv);
     if (!strcmp(argv[1], "histogram")) {   // the file `kmc_tools transform <db> histogram <file>` writes, from the database on the device
         string db, out;
         for (int i = 2; i < argc; ++i) {

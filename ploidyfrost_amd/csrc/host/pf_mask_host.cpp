@@ -26,31 +26,6 @@ namespace {
 using clk = std::chrono::steady_clock;
 double since(clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); }
 
-// a bounded hand-over between two threads; close() wakes everybody, pop() then drains what is left and fails
-template <typename T>
-struct Chan {
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<T> q;
-    bool closed = false;
-    void push(T v) {
-        { std::lock_guard<std::mutex> lk(mu); q.push_back(std::move(v)); }
-        cv.notify_all();
-    }
-    bool pop(T &v) {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return !q.empty() || closed; });
-        if (q.empty()) return false;
-        v = std::move(q.front());
-        q.pop_front();
-        return true;
-    }
-    void close() {
-        { std::lock_guard<std::mutex> lk(mu); closed = true; }
-        cv.notify_all();
-    }
-};
-
 struct Block {     // reader -> device: bytes [HEAD, HEAD + len) of input buffer `buf`
     int buf = -1;
     uint64_t len = 0;
@@ -112,16 +87,28 @@ int fastq_preflight(const char *who, const char *what, const std::vector<std::st
     return 0;
 }
 
-int stream_fastq(pf_ctx *ctx, const char *who_c, const std::vector<std::string> &inputs, uint64_t chunk_bytes, uint64_t largest, int out_fd,
+int stream_fastq(pf_ctx *ctx, const char *who, const std::vector<std::string> &inputs, uint64_t chunk_bytes, uint64_t largest, int out_fd,
                  const std::string &out_name, const ChunkStep &step, StreamTimes &tm, std::string &err) {
+    return stream_fastq_sized(ctx, who, inputs, chunk_bytes, largest, out_fd, out_name,
+                              [&](const char *text, uint64_t n, bool final, char *out, uint64_t &used, uint64_t &reads, uint64_t &bad, uint64_t &out_len) {
+                                  const int rc = step(text, n, final, out, used, reads, bad);
+                                  out_len = used;
+                                  return rc;
+                              },
+                              tm, err);
+}
+
+int stream_fastq_sized(pf_ctx *ctx, const char *who_c, const std::vector<std::string> &inputs, uint64_t chunk_bytes, uint64_t largest, int out_fd,
+                       const std::string &out_name, const SizedChunkStep &step, StreamTimes &tm, std::string &err) {
     const std::string who = who_c;
+    err.clear();   // (a caller's `err` may still hold the text of an earlier call: the loop below runs while it is empty)
     const bool writes = out_fd >= 0;
     uint64_t chunk = chunk_bytes ? chunk_bytes : MASK_DEFAULT_CHUNK;
     chunk = std::max<uint64_t>(1, std::min<uint64_t>(chunk, std::max<uint64_t>(largest, 1)));   // (no gigabyte of pinned memory for a small file)
     chunk = std::min<uint64_t>(chunk, 1ull << 31);                                               // a chunk and its carry stay below the 2^32 of the device calls
     ChunkBuf in_buf[2], out_buf[2];
     for (int i = 0; i < 2; ++i)
-        if (!in_buf[i].alloc(ctx, MASK_HEAD + chunk) || (writes && !out_buf[i].alloc(ctx, MASK_HEAD + chunk))) { err = who + ": no memory for the chunk buffers"; return 1; }
+        if (!in_buf[i].alloc(ctx, MASK_HEAD + chunk) || (writes && !out_buf[i].alloc(ctx, MASK_HEAD + chunk + 16))) { err = who + ": no memory for the chunk buffers"; return 1; }
 
     Chan<int> free_in, free_out;
     Chan<Block> blocks;
@@ -198,13 +185,13 @@ int stream_fastq(pf_ctx *ctx, const char *who_c, const std::vector<std::string> 
             memcpy(big_in->data() + carry.size(), in_buf[b.buf].p + MASK_HEAD, b.len);
             text = big_in->data();
             if (writes) {
-                piece.own = std::make_shared<std::vector<char>>(n);
+                piece.own = std::make_shared<std::vector<char>>(n + 1);
                 out = piece.own->data();
             }
         }
-        uint64_t used = 0, bad = 0, reads = 0;
+        uint64_t used = 0, bad = 0, reads = 0, out_len = 0;
         const auto t0 = clk::now();
-        const int rc = n ? step(text, n, b.eof, out, used, reads, bad) : (int)PF_OK;
+        const int rc = n ? step(text, n, b.eof, out, used, reads, bad, out_len) : (int)PF_OK;
         tm.device_s += since(t0);
         if (rc != PF_OK) {
             const std::string why = pf_last_error(ctx);
@@ -220,7 +207,7 @@ int stream_fastq(pf_ctx *ctx, const char *who_c, const std::vector<std::string> 
         free_in.push(b.buf);
         records_before += reads;
         piece.p = out;
-        piece.len = used;
+        piece.len = out_len;
         if (writes) pieces.push(std::move(piece));
     }
     // wind down: on an error the threads are let go first

@@ -5,7 +5,10 @@
 #pragma once
 #include <stdint.h>
 
+#include <condition_variable>
+#include <deque>
 #include <functional>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -37,7 +40,32 @@ int mask_fastq_counted(const CountOptions &count, const std::string &db_out, con
                        uint32_t low, uint32_t up, bool auto_lower, uint64_t chunk_bytes, int device, pf_mask_stats &stats, uint32_t &lower_used,
                        MaskTimes *times, std::string &err);
 
-// ---- what `mask` and `count` share: FASTQ files streamed through a device call in chunks ----
+// ---- what `mask`, `count` and `trim` share: FASTQ files streamed through a device call in chunks ----
+// a hand-over between two threads; close() wakes everybody, pop() then drains what is left and fails
+template <typename T>
+struct Chan {
+    std::mutex mu;
+    std::condition_variable cv;
+    std::deque<T> q;
+    bool closed = false;
+    void push(T v) {
+        { std::lock_guard<std::mutex> lk(mu); q.push_back(std::move(v)); }
+        cv.notify_all();
+    }
+    bool pop(T &v) {
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return !q.empty() || closed; });
+        if (q.empty()) return false;
+        v = std::move(q.front());
+        q.pop_front();
+        return true;
+    }
+    void close() {
+        { std::lock_guard<std::mutex> lk(mu); closed = true; }
+        cv.notify_all();
+    }
+};
+
 // pinned host memory of a context (pageable when that fails: it works, slower)
 struct ChunkBuf {
     pf_ctx *ctx = nullptr;
@@ -64,5 +92,11 @@ struct StreamTimes { double device_s = 0, read_s = 0, write_s = 0; };
 // input and the 1-based record from the start of that input).
 int stream_fastq(pf_ctx *ctx, const char *who, const std::vector<std::string> &inputs, uint64_t chunk_bytes, uint64_t largest, int out_fd,
                  const std::string &out_name, const ChunkStep &step, StreamTimes &tm, std::string &err);
+
+// The same for a step whose output is not as long as its input (`trim`: records are shortened or dropped): out holds n + 1 bytes, and
+// the step says in out_len how many of them the writer gets.  stream_fastq is this with out_len = used.
+typedef std::function<int(const char *text, uint64_t n, bool final, char *out, uint64_t &used, uint64_t &reads, uint64_t &bad, uint64_t &out_len)> SizedChunkStep;
+int stream_fastq_sized(pf_ctx *ctx, const char *who, const std::vector<std::string> &inputs, uint64_t chunk_bytes, uint64_t largest, int out_fd,
+                       const std::string &out_name, const SizedChunkStep &step, StreamTimes &tm, std::string &err);
 
 }  // namespace pfh

@@ -88,7 +88,7 @@ __device__ inline uint64_t tile_kmer(const uint32_t *s_code, int p, int k) {
 }
 
 // ---- the table: ascending, inside the text, no overlaps (explicit tables only: the FASTQ index makes its own) ----
-static __global__ void k_mask_check_table(const uint64_t *__restrict__ off, const uint32_t *__restrict__ len, uint64_t n_reads, uint64_t n_bytes,
+[[maybe_unused]] static __global__ void k_mask_check_table(const uint64_t *__restrict__ off, const uint32_t *__restrict__ len, uint64_t n_reads, uint64_t n_bytes,
                                           MaskCounts *c) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_reads) return;
@@ -98,7 +98,7 @@ static __global__ void k_mask_check_table(const uint64_t *__restrict__ off, cons
 }
 
 // ---- classes ----
-static __global__ __launch_bounds__(MASK_BLOCK) void k_mask_classes(const uint64_t *__restrict__ off, const uint32_t *__restrict__ len,
+[[maybe_unused]] static __global__ __launch_bounds__(MASK_BLOCK) void k_mask_classes(const uint64_t *__restrict__ off, const uint32_t *__restrict__ len,
                                                                     uint64_t n_reads, uint64_t n_words, uint32_t k, uint64_t *__restrict__ seq,
                                                                     uint64_t *__restrict__ start, MaskCounts *c) {
     // grid-stride, sums kept per lane: one atomic a wavefront when the kernel ends (one a word's wavefront was 146 000 adds to two
@@ -169,7 +169,7 @@ static __global__ __launch_bounds__(MASK_BLOCK) void k_fq_line_starts(const uint
 // n_lines: lines of the text (n_newlines, plus one for a last line without '\n')
 static __global__ __launch_bounds__(MASK_BLOCK) void k_fq_records(const char *__restrict__ text, uint64_t n, const uint32_t *__restrict__ line_start,
                                                                   uint64_t n_newlines, uint64_t n_rec, uint64_t *__restrict__ off, uint32_t *__restrict__ len,
-                                                                  MaskCounts *c) {
+                                                                  MaskCounts *c, uint32_t *__restrict__ lines = nullptr) {
     const uint64_t r = (uint64_t)blockIdx.x * MASK_BLOCK + threadIdx.x;
     if (r >= n_rec) return;
     uint64_t b[4], e[4];
@@ -182,6 +182,10 @@ static __global__ __launch_bounds__(MASK_BLOCK) void k_fq_records(const char *__
     }
     off[r] = b[pf_mask::LINE_SEQUENCE];
     len[r] = (uint32_t)(e[pf_mask::LINE_SEQUENCE] - b[pf_mask::LINE_SEQUENCE]);
+    if (lines) {   // K-TRIM: content begin and end of all four lines, 32 bytes a record
+        reinterpret_cast<uint4 *>(lines)[2 * r] = make_uint4((uint32_t)b[0], (uint32_t)e[0], (uint32_t)b[1], (uint32_t)e[1]);
+        reinterpret_cast<uint4 *>(lines)[2 * r + 1] = make_uint4((uint32_t)b[2], (uint32_t)e[2], (uint32_t)b[3], (uint32_t)e[3]);
+    }
     const int clause = pf_mask::record_clause(text, b[pf_mask::LINE_HEADER], e[pf_mask::LINE_HEADER], e[pf_mask::LINE_SEQUENCE] - b[pf_mask::LINE_SEQUENCE],
                                               b[pf_mask::LINE_PLUS], e[pf_mask::LINE_PLUS], e[pf_mask::LINE_QUALITY] - b[pf_mask::LINE_QUALITY]);
     if (clause) atomicMin(&c->bad_entry, (unsigned long long)((r << 3) | (uint64_t)clause));
@@ -215,6 +219,12 @@ struct FastqIndex {
     const uint64_t *off = nullptr;   // device, n_rec entries (null when n_rec = 0)
     const uint32_t *len = nullptr;
     MaskCounts *counts = nullptr;    // device: all 0, no offender
+    // K-TRIM asks for more (set before the call; K-MASK and K-COUNT leave them as they are):
+    bool want_lines = false;                                     // fill `lines`
+    int ws_index = WS_MASK_INDEX, ws_table = WS_MASK_TABLE;      // the workspaces (a pair's second file has its own)
+    const uint32_t *lines = nullptr;        // device, 8 per record: content begin and end of header, sequence, plus and quality line
+    const uint32_t *line_start = nullptr;   // device: first byte of every line (n_newlines + 1 entries; null when n_rec = 0)
+    uint64_t n_newlines = 0;
 };
 static inline int fastq_index(pf_ctx *ctx, const char *who, const char *dt, uint64_t n_bytes, int final, FastqIndex &ix, uint64_t *bad_record) {
     auto refuse = [&](const std::string &m) { pf::CtxErr{ctx} = m; return (int)PF_ERR_ARG; };
@@ -222,7 +232,7 @@ static inline int fastq_index(pf_ctx *ctx, const char *who, const char *dt, uint
     // newlines: bitmap, count per word, prefix
     const uint64_t n_words = (n_bytes + 63) / 64;
     const size_t nl_bytes = up256((size_t)n_words * 8), cnt_bytes = up256((size_t)n_words * 4), scr_bytes = up256(scan_scratch_bytes(n_words));
-    char *iw = static_cast<char *>(ctx_ws(ctx, WS_MASK_INDEX, nl_bytes + 2 * cnt_bytes + scr_bytes + 256));
+    char *iw = static_cast<char *>(ctx_ws(ctx, ix.ws_index, nl_bytes + 2 * cnt_bytes + scr_bytes + 256));
     if (!iw) return PF_ERR_HIP;
     uint64_t *nl = reinterpret_cast<uint64_t *>(iw);
     uint32_t *cnt = reinterpret_cast<uint32_t *>(iw + nl_bytes), *pre = reinterpret_cast<uint32_t *>(iw + nl_bytes + cnt_bytes);
@@ -245,18 +255,23 @@ static inline int fastq_index(pf_ctx *ctx, const char *who, const char *dt, uint
     const uint64_t n_lines = n_newlines + ((final && !ends_in_newline) ? 1 : 0);
     const uint64_t n_rec = n_lines / 4;
     ix.n_rec = n_rec;
+    ix.n_newlines = n_newlines;
     ix.used = final ? n_bytes : 0;
     if (n_rec) {
         const size_t ls_bytes = up256((size_t)(n_newlines + 2) * 4), off_bytes = up256((size_t)n_rec * 8), len_bytes = up256((size_t)n_rec * 4);
-        char *tw = static_cast<char *>(ctx_ws(ctx, WS_MASK_TABLE, ls_bytes + off_bytes + len_bytes));
+        const size_t lines_bytes = ix.want_lines ? up256((size_t)n_rec * 32) : 0;
+        char *tw = static_cast<char *>(ctx_ws(ctx, ix.ws_table, ls_bytes + off_bytes + len_bytes + lines_bytes));
         if (!tw) return PF_ERR_HIP;
+        uint32_t *dlines = ix.want_lines ? reinterpret_cast<uint32_t *>(tw + ls_bytes + off_bytes + len_bytes) : nullptr;
+        ix.lines = dlines;
+        ix.line_start = reinterpret_cast<uint32_t *>(tw);
         uint32_t *line_start = reinterpret_cast<uint32_t *>(tw);
         uint64_t *doff = reinterpret_cast<uint64_t *>(tw + ls_bytes);
         uint32_t *dlen = reinterpret_cast<uint32_t *>(tw + ls_bytes + off_bytes);
         ix.off = doff;
         ix.len = dlen;
         k_fq_line_starts<<<word_grid, MASK_BLOCK, 0, ctx->stream>>>(nl, pre, n_words, line_start);
-        k_fq_records<<<(unsigned)((n_rec + MASK_BLOCK - 1) / MASK_BLOCK), MASK_BLOCK, 0, ctx->stream>>>(dt, n_bytes, line_start, n_newlines, n_rec, doff, dlen, dc);
+        k_fq_records<<<(unsigned)((n_rec + MASK_BLOCK - 1) / MASK_BLOCK), MASK_BLOCK, 0, ctx->stream>>>(dt, n_bytes, line_start, n_newlines, n_rec, doff, dlen, dc, dlines);
         uint32_t end32 = 0;
         if (!final) PF_HIP(hipMemcpyAsync(&end32, line_start + 4 * n_rec, 4, hipMemcpyDeviceToHost, ctx->stream));
         PF_HIP(hipMemcpyAsync(&h, dc, sizeof h, hipMemcpyDeviceToHost, ctx->stream));

@@ -1,0 +1,468 @@
+// K-TRIM: `trimmomatic SE|PE -phred33 ... LEADING:t TRAILING:t SLIDINGWINDOW:w:t MINLEN:l` (step `1.trim` of the reference's workflow)
+// on one chunk of a FASTQ file, or one chunk of each file of a pair.  The rule is pf_trim_rule.hpp; this file is its device form.
+//
+//   index      fastq_index of pf_reads_dev.hpp (K-MASK's and K-COUNT's), asked for the extents of all four lines of a record.
+//   intervals  k_trim_intervals: a ROW of 16 lanes per read, four reads a wavefront.  A row stages 256 bytes of the quality line (and
+//              64 bytes of halo behind them) into its 320 bytes of LDS with one aligned 16-byte load a lane -- the 64 lanes of a
+//              wavefront read four contiguous stretches instead of 64 byte streams -- and a lane owns 16 positions.  Per step a lane
+//              builds a 16-bit mask of its positions inside [b, e) ("q >= t" for LEADING / TRAILING, nothing for SLIDINGWINDOW, whose
+//              lanes slide a byte sum over their positions and stop at their first bad window: w - 1 bytes of halo come from the LDS of
+//              the row), and the row reduces "first" / "last" with four xor-shuffles.  The masks depend on the bytes only, never on b.
+//              A read of up to 256 - 15 bytes is staged once for all steps; a longer one loops, each step over the row steps that
+//              its [b, e) touches, forwards or backwards, and stops at the first hit.  Output: (begin, len) per record, len 0 = dropped.
+//   sizes      k_trim_sizes, one thread a record: output bytes per destination (1 single-ended, 4 for a pair: o1 u1 o2 u2), the pair
+//              statistics.
+//   offsets    scan_exclusive_u32_u64 over the destinations laid end to end.
+//   copy       k_trim_copy: a row of 16 lanes per kept record of a file; each of its four pieces goes to its offset with aligned
+//              16-byte stores (the source read as two aligned 16-byte units and shifted when it is not congruent), bytes at the
+//              ragged ends, one '\n' behind each piece.  Plain vector stores.
+// Statistics are kept per lane over a grid-stride loop and summed per wavefront when a kernel ends: one integer atomic per
+// wavefront (k_mask_classes gives the reason).  Everything of one call is timed as one launch of PF_K_TRIM; unit: records.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+
+#include "../../include/ploidyfrost_hip.h"
+#include "pf_ctx.hpp"
+#include "pf_reads_dev.hpp"
+#include "pf_scan.hpp"
+#include "pf_trim_rule.hpp"
+
+static_assert(sizeof(pf_trim_step) == sizeof(pf_trim::Step) && sizeof(pf_trim_stats) == sizeof(pf_trim::Stats), "the rule header restates the ABI's records");
+static_assert((int)PF_TRIM_LEADING == (int)pf_trim::KIND_LEADING && (int)PF_TRIM_TRAILING == (int)pf_trim::KIND_TRAILING &&
+              (int)PF_TRIM_SLIDINGWINDOW == (int)pf_trim::KIND_SLIDINGWINDOW && (int)PF_TRIM_MINLEN == (int)pf_trim::KIND_MINLEN &&
+              PF_TRIM_MAX_STEPS == pf_trim::MAX_STEPS, "the rule header restates the ABI's constants");
+
+namespace pf {
+
+constexpr int TRIM_BLOCK = 256;
+constexpr int TRIM_ROW = 16;                                   // lanes of a row: one read
+constexpr int TRIM_ROWS = TRIM_BLOCK / TRIM_ROW;               // rows of a block
+constexpr int TRIM_STEP_BYTES = TRIM_ROW * 16;                 // bytes of a row step
+constexpr int TRIM_HALO_UNITS = 4;                             // 64 bytes behind them: the rest of the last window, w - 1 <= 63
+constexpr int TRIM_UNITS = TRIM_ROW + TRIM_HALO_UNITS;
+constexpr uint32_t TRIM_NONE = 0xFFFFFFFFu;
+static_assert(pf_trim::MAX_W - 1 <= 16 * TRIM_HALO_UNITS, "the halo holds the rest of a row step's last window");
+
+struct TrimSteps {   // by value
+    uint32_t n, phred;
+    pf_trim::Step s[pf_trim::MAX_STEPS];
+};
+struct TrimCounts {   // device side of pf_trim_stats: [0], [1] per file; the pair fields in [0]
+    unsigned long long kept, bases, bases_kept, both, only1, only2;
+};
+
+__device__ inline uint32_t row_min_u32(uint32_t v) {
+#pragma unroll
+    for (int o = TRIM_ROW / 2; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o, TRIM_ROW));
+    return v;
+}
+__device__ inline uint32_t row_max_u32(uint32_t v) {
+#pragma unroll
+    for (int o = TRIM_ROW / 2; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, TRIM_ROW));
+    return v;
+}
+// the lanes of a row run together: its LDS is written, then read by other lanes of the same row
+__device__ inline void row_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// ---- intervals ----
+__global__ __launch_bounds__(TRIM_BLOCK) void k_trim_intervals(const char *__restrict__ text, uint64_t n_bytes, const uint32_t *__restrict__ lines,
+                                                               uint64_t n_rec, const TrimSteps ts, uint32_t *__restrict__ rec_begin,
+                                                               uint32_t *__restrict__ rec_len, TrimCounts *c) {
+    __shared__ uint4 s_q[TRIM_ROWS][TRIM_UNITS];
+    const int rl = (int)threadIdx.x & (TRIM_ROW - 1), row = (int)threadIdx.x / TRIM_ROW;
+    uint4 *sq = s_q[row];
+    const uint8_t *sb = reinterpret_cast<const uint8_t *>(sq);
+    const int x0 = 16 * rl;   // this lane's first byte of the row step
+    uint64_t kept = 0, bases = 0, bases_kept = 0;
+    for (uint64_t r = (uint64_t)blockIdx.x * TRIM_ROWS + row; r < n_rec; r += (uint64_t)gridDim.x * TRIM_ROWS) {
+        const uint32_t qb = lines[8 * r + 6], n = lines[8 * r + 7] - qb;
+        const uint64_t unit0 = qb >> 4;          // the aligned unit that holds the line's first byte
+        const uint32_t mis = qb & 15u;           // position p of the read is byte mis + p from there
+        uint32_t b = 0, e = n;
+        bool alive = n > 0;                      // (every step keeps e > b while the read lives)
+        int64_t staged = -1;
+        // row step `chunk` of the line into the row's LDS; position of byte x of it: chunk * 256 + x - mis
+        auto stage = [&](int64_t chunk) {
+            if (staged == chunk) return;
+            row_sync();   // the last row step has been read
+            const uint64_t u = unit0 + (uint64_t)chunk * TRIM_ROW + (uint64_t)rl;
+            sq[rl] = mask_load_unit(text, n_bytes, u);
+            if (rl < TRIM_HALO_UNITS) sq[TRIM_ROW + rl] = mask_load_unit(text, n_bytes, u + TRIM_ROW);
+            row_sync();
+            staged = chunk;
+        };
+        // bits of this lane's 16 positions that lie in [lo, hi)
+        auto inside = [&](int64_t base, uint32_t lo, uint32_t hi) {
+            int64_t a = (int64_t)lo - base, z = (int64_t)hi - base;
+            a = a < 0 ? 0 : a > 16 ? 16 : a;
+            z = z < 0 ? 0 : z > 16 ? 16 : z;
+            return z > a ? ((1u << z) - 1u) & ~((1u << a) - 1u) : 0u;
+        };
+        auto good_bits = [&](uint32_t thr) {   // byte >= t + phred, i.e. q >= t
+            const uint4 v = sq[rl];
+            uint32_t m = 0;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) m |= (uint32_t)(unit_byte(v, k) >= thr) << k;
+            return m;
+        };
+        for (uint32_t s = 0; s < ts.n && alive; ++s) {
+            const pf_trim::Step st = ts.s[s];
+            if (st.kind == pf_trim::KIND_LEADING) {
+                uint32_t first = TRIM_NONE;
+                const int64_t c1 = ((int64_t)mis + e - 1) >> 8;
+                for (int64_t ch = ((int64_t)mis + b) >> 8; ch <= c1 && first == TRIM_NONE; ++ch) {
+                    stage(ch);
+                    const int64_t base = ch * TRIM_STEP_BYTES + x0 - (int64_t)mis;
+                    const uint32_t m = good_bits(st.a + ts.phred) & inside(base, b, e);
+                    first = row_min_u32(m ? (uint32_t)(base + (__ffs((int)m) - 1)) : TRIM_NONE);
+                }
+                if (first == TRIM_NONE) alive = false; else b = first;
+            } else if (st.kind == pf_trim::KIND_TRAILING) {
+                uint32_t end = 0;   // 1 + the last good position, 0 = none
+                const int64_t c0 = ((int64_t)mis + b) >> 8;
+                for (int64_t ch = ((int64_t)mis + e - 1) >> 8; ch >= c0 && end == 0; --ch) {
+                    stage(ch);
+                    const int64_t base = ch * TRIM_STEP_BYTES + x0 - (int64_t)mis;
+                    const uint32_t m = good_bits(st.a + ts.phred) & inside(base, b, e);
+                    end = row_max_u32(m ? (uint32_t)(base + (31 - __clz((int)m)) + 1) : 0u);
+                }
+                if (end == 0) alive = false; else e = end;
+            } else if (st.kind == pf_trim::KIND_SLIDINGWINDOW) {
+                const uint32_t w = st.a;
+                if (e - b < w) { alive = false; continue; }
+                const uint32_t last_start = e - w;   // windows start in [b, last_start]
+                uint32_t bad = TRIM_NONE;
+                const int64_t c1 = ((int64_t)mis + last_start) >> 8;
+                for (int64_t ch = ((int64_t)mis + b) >> 8; ch <= c1 && bad == TRIM_NONE; ++ch) {
+                    stage(ch);
+                    const int64_t base = ch * TRIM_STEP_BYTES + x0 - (int64_t)mis;
+                    const uint32_t in = inside(base, b, last_start + 1);
+                    uint32_t mine = TRIM_NONE;
+                    if (in) {
+                        const int k0 = __ffs((int)in) - 1, k1 = 31 - __clz((int)in);
+                        uint32_t sum = 0;
+                        for (uint32_t i = 0; i < w; ++i) sum += sb[x0 + k0 + (int)i];
+                        for (int k = k0;; ++k) {
+                            if (pf_trim::window_bad_bytes(sum, w, st.b, ts.phred)) { mine = (uint32_t)(base + k); break; }
+                            if (k == k1) break;
+                            sum += (uint32_t)sb[x0 + k + (int)w] - (uint32_t)sb[x0 + k];
+                        }
+                    }
+                    bad = row_min_u32(mine);
+                }
+                if (bad == b) alive = false;
+                else if (bad != TRIM_NONE) e = pf_trim::sliding_end(b, bad - b, w);
+            } else {   // KIND_MINLEN
+                if (pf_trim::too_short(b, e, st.a)) alive = false;
+            }
+        }
+        if (rl == 0) {
+            rec_begin[r] = alive ? b : 0u;
+            rec_len[r] = alive ? e - b : 0u;
+            kept += alive;
+            bases += n;
+            bases_kept += alive ? e - b : 0u;
+        }
+    }
+    kept = wave_sum_u64(kept);
+    bases = wave_sum_u64(bases);
+    bases_kept = wave_sum_u64(bases_kept);
+    if (lane_id() == 0) {
+        if (kept) atomicAdd(&c->kept, (unsigned long long)kept);
+        if (bases) atomicAdd(&c->bases, (unsigned long long)bases);
+        if (bases_kept) atomicAdd(&c->bases_kept, (unsigned long long)bases_kept);
+    }
+}
+
+// ---- sizes ----
+// destination of the record of file f of a pair whose records are kept (k1, k2): o1 u1 o2 u2 = 0 1 2 3
+__device__ inline int trim_dest(int f, bool k1, bool k2) { return f == 0 ? (k2 ? 0 : 1) : (k1 ? 2 : 3); }
+__device__ inline uint32_t trim_record_bytes(const uint32_t *__restrict__ lines, uint64_t r, uint32_t len) {
+    return (lines[8 * r + 1] - lines[8 * r]) + (lines[8 * r + 5] - lines[8 * r + 4]) + 2 * len + 4;
+}
+// size[d * n_rec + r] = bytes record r writes to destination d; size[n_dest * n_rec] = 0 (the scan's last entry is the total)
+__global__ __launch_bounds__(TRIM_BLOCK) void k_trim_sizes(const uint32_t *__restrict__ lines1, const uint32_t *__restrict__ len1,
+                                                           const uint32_t *__restrict__ lines2, const uint32_t *__restrict__ len2, uint64_t n_rec,
+                                                           uint32_t *__restrict__ size, TrimCounts *c) {
+    uint64_t both = 0, only1 = 0, only2 = 0;
+    const bool pair = lines2 != nullptr;
+    if (blockIdx.x == 0 && threadIdx.x == 0) size[(pair ? 4 : 1) * n_rec] = 0;
+    for (uint64_t r = (uint64_t)blockIdx.x * TRIM_BLOCK + threadIdx.x; r < n_rec; r += (uint64_t)gridDim.x * TRIM_BLOCK) {
+        const uint32_t l1 = len1[r];
+        if (!pair) {
+            size[r] = l1 ? trim_record_bytes(lines1, r, l1) : 0u;
+            continue;
+        }
+        const uint32_t l2 = len2[r];
+        const bool k1 = l1 != 0, k2 = l2 != 0;
+        uint32_t sz[4] = {0, 0, 0, 0};
+        if (k1) sz[trim_dest(0, k1, k2)] = trim_record_bytes(lines1, r, l1);
+        if (k2) sz[trim_dest(1, k1, k2)] = trim_record_bytes(lines2, r, l2);
+#pragma unroll
+        for (int d = 0; d < 4; ++d) size[(uint64_t)d * n_rec + r] = sz[d];
+        both += k1 && k2;
+        only1 += k1 && !k2;
+        only2 += !k1 && k2;
+    }
+    both = wave_sum_u64(both);
+    only1 = wave_sum_u64(only1);
+    only2 = wave_sum_u64(only2);
+    if (lane_id() == 0) {
+        if (both) atomicAdd(&c->both, (unsigned long long)both);
+        if (only1) atomicAdd(&c->only1, (unsigned long long)only1);
+        if (only2) atomicAdd(&c->only2, (unsigned long long)only2);
+    }
+}
+
+// ---- copy ----
+struct TrimCopyArgs {
+    const char *text[2];
+    uint64_t n_text[2];
+    const uint32_t *lines[2], *begin[2], *len[2];
+    const uint64_t *offs;   // the scan of `size`
+    char *out[4];           // 16-byte aligned
+    uint64_t n_rec;
+    int n_files;
+};
+// the 16 bytes of the text from byte s: one aligned unit, or two and a shift
+__device__ inline uint4 trim_load_shifted(const char *__restrict__ text, uint64_t n, uint64_t s) {
+    const uint4 lo = mask_load_unit(text, n, s >> 4);
+    const uint32_t sh = (uint32_t)(s & 15);
+    if (sh == 0) return lo;
+    const uint4 hi = mask_load_unit(text, n, (s >> 4) + 1);
+    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    const uint32_t d = sh >> 2, bits = (sh & 3) * 8;
+    uint32_t t[5], o[4];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) t[i] = d == 0 ? w[i] : d == 1 ? w[i + 1] : d == 2 ? w[i + 2] : w[i + 3];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = (uint32_t)(((((uint64_t)t[i + 1]) << 32) | t[i]) >> bits);
+    return make_uint4(o[0], o[1], o[2], o[3]);
+}
+// one piece by a row: text[src, src + len) to out[dst ..), then '\n'
+__device__ inline void trim_row_copy(const char *__restrict__ text, uint64_t n_text, uint64_t src, uint32_t len, char *__restrict__ out, uint64_t dst,
+                                     int rl) {
+    const uint64_t end = dst + len;
+    uint64_t a0 = (dst + 15) & ~15ull;                       // head bytes [dst, a0)
+    if (a0 > end) a0 = end;
+    const uint64_t a1 = a0 + ((end - a0) & ~15ull);          // whole units [a0, a1), tail bytes [a1, end)
+    if (dst + (uint64_t)rl < a0) out[dst + rl] = text[src + rl];
+    for (uint64_t u = a0 + 16ull * rl; u < a1; u += 16ull * TRIM_ROW)
+        *reinterpret_cast<uint4 *>(out + u) = trim_load_shifted(text, n_text, src + (u - dst));
+    if (a1 + (uint64_t)rl < end) out[a1 + rl] = text[src + (a1 + rl - dst)];
+    if (rl == TRIM_ROW - 1) out[end] = '\n';
+}
+__global__ __launch_bounds__(TRIM_BLOCK) void k_trim_copy(const TrimCopyArgs a) {
+    const int rl = (int)threadIdx.x & (TRIM_ROW - 1), row = (int)threadIdx.x / TRIM_ROW;
+    const uint64_t n_items = a.n_rec * (uint64_t)a.n_files;
+    for (uint64_t it = (uint64_t)blockIdx.x * TRIM_ROWS + row; it < n_items; it += (uint64_t)gridDim.x * TRIM_ROWS) {
+        const uint64_t r = a.n_files == 2 ? it >> 1 : it;
+        const int f = a.n_files == 2 ? (int)(it & 1) : 0;
+        const uint32_t len = a.len[f][r];
+        if (!len) continue;
+        int d = 0;
+        if (a.n_files == 2) d = trim_dest(f, a.len[0][r] != 0, a.len[1][r] != 0);
+        const uint64_t at = a.offs[(uint64_t)d * a.n_rec + r] - a.offs[(uint64_t)d * a.n_rec];
+        const uint32_t *ln = a.lines[f] + 8 * r;
+        const uint32_t b = a.begin[f][r], hl = ln[1] - ln[0], pl = ln[5] - ln[4];
+        const char *text = a.text[f];
+        char *out = a.out[d];
+        trim_row_copy(text, a.n_text[f], ln[0], hl, out, at, rl);
+        trim_row_copy(text, a.n_text[f], (uint64_t)ln[2] + b, len, out, at + hl + 1, rl);
+        trim_row_copy(text, a.n_text[f], ln[4], pl, out, at + hl + 1 + len + 1, rl);
+        trim_row_copy(text, a.n_text[f], (uint64_t)ln[6] + b, len, out, at + hl + 1 + len + 1 + pl + 1, rl);
+    }
+}
+
+// ---- host side ----
+struct TrimTimed {   // brackets everything one call launches as one timed launch of PF_K_TRIM
+    pf_ctx *ctx;
+    explicit TrimTimed(pf_ctx *c) : ctx(c) { ctx_begin(ctx, PF_K_TRIM); }
+    ~TrimTimed() { ctx_end(ctx); }
+};
+
+// the text of file f on the device, 16-byte aligned (mask_stage_text for a slot of the caller's choice)
+static int trim_stage_text(pf_ctx *ctx, int slot, const char *text, uint64_t n, const char **dev) {
+    if (is_device_ptr(text) && ((uintptr_t)text & 15) == 0) { *dev = text; return PF_OK; }
+    char *p = static_cast<char *>(ctx_ws(ctx, slot, (size_t)n + 16));
+    if (!p) return PF_ERR_HIP;
+    PF_HIP(hipMemcpyAsync(p, text, (size_t)n, hipMemcpyDefault, ctx->stream));
+    *dev = p;
+    return PF_OK;
+}
+
+// one chunk of a file (n_files = 1) or of each file of a pair (2); the arguments are arrays of n_files (out, out_bytes: 1 or 4)
+static int trim_core(pf_ctx *ctx, const char *who_c, int n_files, const char *const *text, const uint64_t *n_bytes, int final,
+                     const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, char *const *out, uint64_t *out_bytes, uint64_t *bytes_used,
+                     uint32_t *const *rec_begin, uint32_t *const *rec_len, uint64_t *n_records, pf_trim_stats *stats, uint64_t *bad_record) {
+    const std::string who = who_c;
+    auto refuse = [&](const std::string &m) { pf::CtxErr{ctx} = who + ": " + m; return (int)PF_ERR_ARG; };
+    const int n_dest = n_files == 2 ? 4 : 1;
+    if (!out_bytes || !bytes_used || !n_records) return refuse("out_bytes, bytes_used and n_records are needed");
+    for (int d = 0; d < n_dest; ++d) out_bytes[d] = 0;
+    for (int f = 0; f < n_files; ++f) bytes_used[f] = 0;
+    *n_records = 0;
+    if (bad_record) *bad_record = 0;
+    if (stats) for (int f = 0; f < n_files; ++f) stats[f] = pf_trim_stats{};
+    {
+        uint32_t bad_step = 0;
+        const int c = pf_trim::steps_clause(reinterpret_cast<const pf_trim::Step *>(steps), n_steps, phred, &bad_step);
+        if (c == pf_trim::REFUSE_PHRED) return refuse(std::string(pf_trim::refusal_text(c)) + ", not " + std::to_string(phred));
+        if (c == pf_trim::REFUSE_NO_STEP || c == pf_trim::REFUSE_TOO_MANY) return refuse(pf_trim::refusal_text(c));
+        if (c) return refuse("step " + std::to_string(bad_step) + ": " + pf_trim::refusal_text(c));
+    }
+    for (int f = 0; f < n_files; ++f) {
+        if (n_bytes[f] && !text[f]) return refuse("text is needed");
+        if (n_bytes[f] > 0xFFFFFF00ull) return refuse("a chunk holds fewer than 2^32 bytes (line starts are 32 bits)");
+        for (int d = 2 * f; d < (n_files == 2 ? 2 * f + 2 : 1); ++d) {
+            if (n_bytes[f] && !out[d]) return refuse("out is needed");
+            if (n_bytes[f] && out[d] == text[f]) return refuse("out may not alias text");
+        }
+    }
+    if (n_bytes[0] == 0 && (n_files == 1 || n_bytes[1] == 0)) return PF_OK;
+    PF_HIP(hipSetDevice(ctx->device));
+    TrimTimed timed(ctx);
+
+    // ---- index ----
+    const char *dt[2] = {nullptr, nullptr};
+    FastqIndex ix[2];
+    for (int f = 0; f < n_files; ++f) {
+        if (!n_bytes[f]) continue;   // (no record: a pair's other file decides what that means)
+        { const int rc = trim_stage_text(ctx, f == 0 ? (int)WS_MASK_TEXT : (int)WS_TRIM_TEXT2, text[f], n_bytes[f], &dt[f]); if (rc) return rc; }
+        ix[f].want_lines = true;
+        if (f == 1) { ix[f].ws_index = WS_TRIM_INDEX2; ix[f].ws_table = WS_TRIM_TABLE2; }
+        const std::string w = n_files == 2 ? who + ": file " + std::to_string(f + 1) : who;
+        uint64_t bad = 0;
+        const int rc = fastq_index(ctx, w.c_str(), dt[f], n_bytes[f], final, ix[f], &bad);   // refused before anything is trimmed
+        if (rc) { if (bad_record) *bad_record = n_files == 2 ? 2 * bad + (uint64_t)f : bad; return rc; }
+    }
+    uint64_t n = ix[0].n_rec;
+    if (n_files == 2) {
+        n = std::min(ix[0].n_rec, ix[1].n_rec);
+        if (final && ix[0].n_rec != ix[1].n_rec) {
+            if (bad_record) *bad_record = 2 * n + (ix[0].n_rec < ix[1].n_rec ? 0 : 1);
+            return refuse("the final chunks hold different numbers of records (file 1: " + std::to_string(ix[0].n_rec) + ", file 2: " +
+                          std::to_string(ix[1].n_rec) + ")");
+        }
+    }
+    if (n == 0) return PF_OK;   // no whole record (of both files): everything is carried
+    uint32_t end32[2] = {0, 0};
+    for (int f = 0; f < n_files; ++f)   // the end of record n - 1
+        if (n < ix[f].n_rec) PF_HIP(hipMemcpyAsync(&end32[f], ix[f].line_start + 4 * n, 4, hipMemcpyDeviceToHost, ctx->stream));
+
+    // ---- intervals, sizes, offsets ----
+    const uint64_t n_size = (uint64_t)n_dest * n + 1;
+    const size_t rec_bytes = up256((size_t)n * 4), size_bytes = up256((size_t)n_size * 4), offs_bytes = up256((size_t)n_size * 8),
+                 scr_bytes = up256(scan_scratch_bytes(n_size));
+    char *ww = static_cast<char *>(ctx_ws(ctx, WS_TRIM_WORK, 4 * rec_bytes + size_bytes + offs_bytes + scr_bytes + 256));
+    if (!ww) return PF_ERR_HIP;
+    uint32_t *d_begin[2] = {reinterpret_cast<uint32_t *>(ww), reinterpret_cast<uint32_t *>(ww + rec_bytes)};
+    uint32_t *d_len[2] = {reinterpret_cast<uint32_t *>(ww + 2 * rec_bytes), reinterpret_cast<uint32_t *>(ww + 3 * rec_bytes)};
+    uint32_t *d_size = reinterpret_cast<uint32_t *>(ww + 4 * rec_bytes);
+    uint64_t *d_offs = reinterpret_cast<uint64_t *>(ww + 4 * rec_bytes + size_bytes);
+    void *scratch = ww + 4 * rec_bytes + size_bytes + offs_bytes;
+    TrimCounts *dc = reinterpret_cast<TrimCounts *>(ww + 4 * rec_bytes + size_bytes + offs_bytes + scr_bytes);
+    PF_HIP(hipMemsetAsync(dc, 0, 2 * sizeof(TrimCounts), ctx->stream));
+    TrimSteps ts = {};
+    ts.n = n_steps;
+    ts.phred = phred;
+    for (uint32_t s = 0; s < n_steps; ++s) ts.s[s] = pf_trim::Step{steps[s].kind, steps[s].a, steps[s].b};
+    for (int f = 0; f < n_files; ++f)
+        k_trim_intervals<<<ctx_grid(ctx, n * TRIM_ROW, TRIM_BLOCK, 8), TRIM_BLOCK, 0, ctx->stream>>>(dt[f], n_bytes[f], ix[f].lines, n, ts, d_begin[f],
+                                                                                                     d_len[f], dc + f);
+    k_trim_sizes<<<ctx_grid(ctx, n, TRIM_BLOCK, 8), TRIM_BLOCK, 0, ctx->stream>>>(ix[0].lines, d_len[0], n_files == 2 ? ix[1].lines : nullptr,
+                                                                                  n_files == 2 ? d_len[1] : nullptr, n, d_size, dc);
+    PF_HIP(scan_exclusive_u32_u64(d_size, d_offs, n_size, scratch, ctx->stream));
+
+    // ---- copy ----
+    size_t cap[4], stage_at[4], stage_bytes = 0;
+    bool direct[4];
+    for (int d = 0; d < n_dest; ++d) {
+        cap[d] = (size_t)n_bytes[n_files == 2 ? d / 2 : 0] + 1;
+        direct[d] = is_device_ptr(out[d]) && ((uintptr_t)out[d] & 15) == 0;
+        stage_at[d] = stage_bytes;
+        if (!direct[d]) stage_bytes += up256(cap[d] + 16);
+    }
+    char *stage = nullptr;
+    if (stage_bytes) {
+        stage = static_cast<char *>(ctx_ws(ctx, WS_TRIM_OUT, stage_bytes));
+        if (!stage) return PF_ERR_HIP;
+    }
+    TrimCopyArgs ca = {};
+    for (int f = 0; f < n_files; ++f) {
+        ca.text[f] = dt[f];
+        ca.n_text[f] = n_bytes[f];
+        ca.lines[f] = ix[f].lines;
+        ca.begin[f] = d_begin[f];
+        ca.len[f] = d_len[f];
+    }
+    ca.offs = d_offs;
+    for (int d = 0; d < n_dest; ++d) ca.out[d] = direct[d] ? out[d] : stage + stage_at[d];
+    ca.n_rec = n;
+    ca.n_files = n_files;
+    k_trim_copy<<<ctx_grid(ctx, n * (uint64_t)n_files * TRIM_ROW, TRIM_BLOCK, 8), TRIM_BLOCK, 0, ctx->stream>>>(ca);
+    {
+        const hipError_t le = hipGetLastError();
+        if (le != hipSuccess) { pf::CtxErr{ctx} = std::string("K-TRIM launch: ") + hipGetErrorString(le); return PF_ERR_HIP; }
+    }
+    uint64_t base[5] = {0, 0, 0, 0, 0};
+    for (int d = 0; d <= n_dest; ++d) PF_HIP(hipMemcpyAsync(&base[d], d_offs + (uint64_t)d * n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    TrimCounts h[2] = {};
+    PF_HIP(hipMemcpyAsync(h, dc, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    PF_HIP(hipStreamSynchronize(ctx->stream));
+    for (int d = 0; d < n_dest; ++d) {
+        out_bytes[d] = base[d + 1] - base[d];
+        if (!direct[d] && out_bytes[d]) PF_HIP(hipMemcpyAsync(out[d], ca.out[d], (size_t)out_bytes[d], hipMemcpyDefault, ctx->stream));
+    }
+    for (int f = 0; f < n_files; ++f) {
+        if (rec_begin && rec_begin[f]) PF_HIP(hipMemcpyAsync(rec_begin[f], d_begin[f], (size_t)n * 4, hipMemcpyDefault, ctx->stream));
+        if (rec_len && rec_len[f]) PF_HIP(hipMemcpyAsync(rec_len[f], d_len[f], (size_t)n * 4, hipMemcpyDefault, ctx->stream));
+    }
+    PF_HIP(hipStreamSynchronize(ctx->stream));
+    for (int f = 0; f < n_files; ++f) {
+        bytes_used[f] = n < ix[f].n_rec ? (uint64_t)end32[f] : ix[f].used;
+        if (!stats) continue;
+        stats[f].reads = n;
+        stats[f].kept = h[f].kept;
+        stats[f].dropped = n - h[f].kept;
+        stats[f].bases = h[f].bases;
+        stats[f].bases_kept = h[f].bases_kept;
+        if (n_files == 2) {
+            stats[f].both = h[0].both;
+            stats[f].only1 = h[0].only1;
+            stats[f].only2 = h[0].only2;
+            stats[f].neither = n - h[0].both - h[0].only1 - h[0].only2;
+        }
+    }
+    *n_records = n;
+    ctx_units(ctx, PF_K_TRIM, n * (uint64_t)n_files);
+    return PF_OK;
+}
+
+}  // namespace pf
+
+using namespace pf;
+
+extern "C" int pf_trim_fastq(pf_ctx *ctx, const char *text, uint64_t n_bytes, int final, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred,
+                             char *out, uint64_t *out_bytes, uint64_t *bytes_used, uint32_t *rec_begin, uint32_t *rec_len, uint64_t *n_records,
+                             pf_trim_stats *stats, uint64_t *bad_record) {
+    if (!ctx) return PF_ERR_ARG;
+    return trim_core(ctx, "pf_trim_fastq", 1, &text, &n_bytes, final, steps, n_steps, phred, &out, out_bytes, bytes_used, &rec_begin, &rec_len, n_records,
+                     stats, bad_record);
+}
+
+extern "C" int pf_trim_fastq_pair(pf_ctx *ctx, const char *text1, uint64_t n1, const char *text2, uint64_t n2, int final, const pf_trim_step *steps,
+                                  uint32_t n_steps, uint32_t phred, char *out[4], uint64_t out_bytes[4], uint64_t bytes_used[2], uint32_t *rec_begin[2],
+                                  uint32_t *rec_len[2], uint64_t *n_records, pf_trim_stats stats[2], uint64_t *bad_record) {
+    if (!ctx) return PF_ERR_ARG;
+    if (!out) { pf::CtxErr{ctx} = "pf_trim_fastq_pair: out is needed"; return PF_ERR_ARG; }
+    const char *text[2] = {text1, text2};
+    const uint64_t n[2] = {n1, n2};
+    return trim_core(ctx, "pf_trim_fastq_pair", 2, text, n, final, steps, n_steps, phred, out, out_bytes, bytes_used, rec_begin, rec_len, n_records, stats,
+                     bad_record);
+}

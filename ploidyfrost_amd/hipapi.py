@@ -31,6 +31,10 @@ MASK_STATS = np.dtype([(f, "<u8") for f in ("reads", "reads_changed", "bases", "
 MASK_NO_UPPER = 0xFFFFFFFF
 K_COUNT = K_MASK + 1       # PF_K_COUNT ("k_count"): everything one pf_count_reads / pf_count_fastq launches; unit: windows
 COUNT_STATS = np.dtype([(f, "<u8") for f in ("reads", "bases", "kmers", "kmers_bad", "unique", "below_min", "above_max", "written")])   # pf_count_stats
+K_TRIM = K_COUNT + 1       # PF_K_TRIM ("k_trim"): everything one pf_trim_fastq / pf_trim_fastq_pair launches; unit: records
+TRIM_STEP = np.dtype([("kind", "<u4"), ("a", "<u4"), ("b", "<u4")])   # pf_trim_step
+TRIM_STATS = np.dtype([(f, "<u8") for f in ("reads", "kept", "dropped", "bases", "bases_kept", "both", "only1", "only2", "neither")])   # pf_trim_stats
+TRIM_KINDS = {"LEADING": 1, "TRAILING": 2, "SLIDINGWINDOW": 3, "MINLEN": 4}   # PF_TRIM_LEADING ..
 DENSITY_INFO = np.dtype([("n", "<u8"), ("min", "<f8"), ("max", "<f8"), ("sd", "<f8"), ("q1", "<f8"), ("q3", "<f8"), ("bw", "<f8"),
                          ("order", "<f8", (4,))])   # pf_density_info
 assert DENSITY_INFO.itemsize == 88
@@ -209,6 +213,9 @@ def load_library() -> C.CDLL:
         "pf_count_finish": (i, [vp, u64, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), vp]),
         "pf_count_abort": (i, [vp]),
         "pf_kmc_encode": (i, [vp, vp, vp, u64, u32, u32, u32, vp, vp]),
+        "pf_trim_fastq": (i, [vp, vp, u64, i, vp, u32, u32, vp, C.POINTER(u64), C.POINTER(u64), vp, vp, C.POINTER(u64), vp, C.POINTER(u64)]),
+        "pf_trim_fastq_pair": (i, [vp, vp, u64, vp, u64, i, vp, u32, u32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(vp), C.POINTER(vp),
+                                   C.POINTER(u64), vp, C.POINTER(u64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError = header / library mismatch
@@ -231,7 +238,24 @@ DECLARED_SYMBOLS = ["pf_create", "pf_warmup", "pf_destroy", "pf_last_error", "pf
                     "pf_call_model_filter", "pf_call_model_take_text",
                     "pf_call_model_filter_multi", "pf_call_model_color_count", "pf_call_model_color_select",
                     "pf_gmm_density", "pf_count_histogram", "pf_mask_reads", "pf_mask_fastq",
-                    "pf_count_begin", "pf_count_reads", "pf_count_fastq", "pf_count_finish", "pf_count_abort", "pf_kmc_encode"]
+                    "pf_count_begin", "pf_count_reads", "pf_count_fastq", "pf_count_finish", "pf_count_abort", "pf_kmc_encode",
+                    "pf_trim_fastq", "pf_trim_fastq_pair"]
+
+
+def trim_steps(steps) -> np.ndarray:
+    """a TRIM_STEP array from Trimmomatic's words ("LEADING:10", "SLIDINGWINDOW:3:20", ...), tuples (kind, a[, b]) or such an array.
+    Nothing is checked here: the library refuses bad steps by name."""
+    if isinstance(steps, np.ndarray) and steps.dtype == TRIM_STEP:
+        return np.ascontiguousarray(steps)
+    if isinstance(steps, str):
+        steps = steps.split()
+    out = np.zeros(len(steps), dtype=TRIM_STEP)
+    for j, s in enumerate(steps):
+        if isinstance(s, str):
+            name, *fields = s.split(":")
+            s = (TRIM_KINDS[name],) + tuple(int(x) for x in fields)
+        out[j] = tuple(s) + (0,) * (3 - len(s))
+    return out
 
 
 def density_dict(x: np.ndarray, density: np.ndarray, info: np.ndarray) -> dict:
@@ -505,6 +529,59 @@ class Device:
             e.bad_record = bad.value
             raise e
         return out[: used.value], used.value, {f: int(stats[0][f]) for f in MASK_STATS.names}
+
+    def trim_fastq(self, text, steps, phred: int = 33, final: bool = True, out=None):
+        """K-TRIM on one chunk of a FASTQ file (pf_trim_fastq): dict with out (the kept records, trimmed), bytes_used, n_records, begin /
+        len (u32 per record, len 0 = dropped) and stats.  steps: trim_steps() of Trimmomatic's words, or a TRIM_STEP array.  text: bytes,
+        a uint8 numpy array or a device tensor; out: a device tensor of len(text) + 1 bytes to fill instead of a new numpy array.  A format
+        error raises DeviceError with .bad_record = the 0-based record within the chunk."""
+        if isinstance(text, (bytes, bytearray)):
+            text = np.frombuffer(bytes(text), dtype=np.uint8)
+        steps = trim_steps(steps)
+        n = int(text.shape[0])
+        if out is None:
+            out = np.zeros(n + 1, dtype=np.uint8)
+        cap = n // 4 + 1
+        begin, ln = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32)
+        stats = np.zeros(1, dtype=TRIM_STATS)
+        out_n, used, recs, bad = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        st = self.L.pf_trim_fastq(self.h, _ptr(text) if n else None, n, int(final), steps.ctypes.data if len(steps) else None, len(steps), phred,
+                                  _ptr(out), C.byref(out_n), C.byref(used), begin.ctypes.data, ln.ctypes.data, C.byref(recs), stats.ctypes.data,
+                                  C.byref(bad))
+        if st != PF_OK:
+            e = DeviceError(st, self.L.pf_last_error(self.h).decode())
+            e.bad_record = bad.value
+            raise e
+        return dict(out=out[: out_n.value], bytes_used=used.value, n_records=recs.value, begin=begin[: recs.value], len=ln[: recs.value],
+                    stats={f: int(stats[0][f]) for f in TRIM_STATS.names})
+
+    def trim_fastq_pair(self, text1, text2, steps, phred: int = 33, final: bool = True, outs=None):
+        """K-TRIM on one chunk of each file of a pair (pf_trim_fastq_pair): dict with out = [o1, u1, o2, u2], bytes_used = [file 1,
+        file 2], n_records, begin / len = [file 1, file 2], stats = [file 1, file 2].  outs: four arrays or device tensors to fill (o1,
+        u1: len(text1) + 1 bytes; o2, u2: len(text2) + 1).  bad_record of a DeviceError: 2 * record + file."""
+        texts = [np.frombuffer(bytes(t), dtype=np.uint8) if isinstance(t, (bytes, bytearray)) else t for t in (text1, text2)]
+        steps = trim_steps(steps)
+        n = [int(t.shape[0]) for t in texts]
+        if outs is None:
+            outs = [np.zeros(n[d // 2] + 1, dtype=np.uint8) for d in range(4)]
+        cap = min(n) // 4 + 1
+        begin = [np.zeros(cap, dtype=np.uint32) for _ in range(2)]
+        ln = [np.zeros(cap, dtype=np.uint32) for _ in range(2)]
+        stats = np.zeros(2, dtype=TRIM_STATS)
+        out_p = (C.c_void_p * 4)(*[_ptr(o) for o in outs])
+        begin_p = (C.c_void_p * 2)(*[b.ctypes.data for b in begin])
+        len_p = (C.c_void_p * 2)(*[x.ctypes.data for x in ln])
+        out_n, used, recs, bad = (C.c_uint64 * 4)(), (C.c_uint64 * 2)(), C.c_uint64(), C.c_uint64()
+        st = self.L.pf_trim_fastq_pair(self.h, _ptr(texts[0]) if n[0] else None, n[0], _ptr(texts[1]) if n[1] else None, n[1], int(final),
+                                       steps.ctypes.data if len(steps) else None, len(steps), phred, out_p, out_n, used, begin_p, len_p,
+                                       C.byref(recs), stats.ctypes.data, C.byref(bad))
+        if st != PF_OK:
+            e = DeviceError(st, self.L.pf_last_error(self.h).decode())
+            e.bad_record = bad.value
+            raise e
+        r = recs.value
+        return dict(out=[outs[d][: out_n[d]] for d in range(4)], bytes_used=[used[0], used[1]], n_records=r, begin=[b[:r] for b in begin],
+                    len=[x[:r] for x in ln], stats=[{f: int(stats[j][f]) for f in TRIM_STATS.names} for j in range(2)])
 
     def count_begin(self, k: int, both_strands: bool = True, initial_slots: int = 0):
         """K-COUNT (pf_count_begin): opens a count of k-mers of length k (3 .. 31); both_strands: canonical keys.  initial_slots = 0:

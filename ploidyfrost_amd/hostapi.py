@@ -42,7 +42,8 @@ DECLARED_SYMBOLS = ["pfh_open", "pfh_close", "pfh_last_error", "pfh_set_output_d
                     "pfh_kmc_histogram", "pfh_cutoffs_from_rows", "pfh_set_auto_cutoffs", "pfh_cutoffs",
                     "pfh_mask_fastq", "pfh_mask_read", "pfh_mask_index_fastq", "pfh_mask_clause_text",
                     "pfh_count_fastq", "pfh_mask_fastq_counted", "pfh_count_reads_host", "pfh_count_encode_kmc1", "pfh_count_counter_bytes",
-                    "pfh_count_lut_prefix_len", "pfh_count_cut_text"]
+                    "pfh_count_lut_prefix_len", "pfh_count_cut_text",
+                    "pfh_trim_fastq", "pfh_trim_fastq_pair", "pfh_trim_parse_step", "pfh_trim_refusal_text", "pfh_trim_read", "pfh_trim_fastq_chunk"]
 
 
 class FilterOpts(C.Structure):   # pf_filter_opts (include/ploidyfrost_hip.h)
@@ -202,6 +203,13 @@ def load_library() -> C.CDLL:
     L.pfh_count_lut_prefix_len.argtypes = [u32]
     L.pfh_count_cut_text.restype = C.c_char_p
     L.pfh_count_cut_text.argtypes = [C.c_int]
+    L.pfh_trim_fastq.argtypes = [C.POINTER(C.c_char_p), u32, C.c_char_p, vp, u32, u32, C.c_char_p, u64, C.c_int, vp]
+    L.pfh_trim_fastq_pair.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), vp, u32, u32, C.c_char_p, u64, C.c_int, vp]
+    L.pfh_trim_parse_step.argtypes = [C.c_char_p, vp]
+    L.pfh_trim_refusal_text.restype = C.c_char_p
+    L.pfh_trim_refusal_text.argtypes = [C.c_int]
+    L.pfh_trim_read.argtypes = [vp, u64, vp, u32, u32, C.POINTER(u32), C.POINTER(u32)]
+    L.pfh_trim_fastq_chunk.argtypes = [vp, u64, C.c_int, vp, u32, u32, vp, C.POINTER(u64), C.POINTER(u64), vp, vp, u64, C.POINTER(u64), vp, C.POINTER(u64)]
     _lib = L
     return L
 
@@ -455,6 +463,95 @@ def mask_index_fastq(text: bytes, final: bool = True):
     clause = L.pfh_mask_index_fastq(src.ctypes.data if n else None, n, int(final), C.byref(used), C.byref(recs), C.byref(bad), off.ctypes.data, ln.ctypes.data, cap)
     return dict(clause=MASK_CLAUSES[clause], message=L.pfh_mask_clause_text(clause).decode(), bad_record=bad.value, bytes_used=used.value,
                 n_records=recs.value, read_off=off[: recs.value].copy(), read_len=ln[: recs.value].copy())
+
+
+TRIM_STATS_FIELDS = ("reads", "kept", "dropped", "bases", "bases_kept", "both", "only1", "only2", "neither")   # pf_trim_stats
+TRIM_STEP = np.dtype([("kind", "<u4"), ("a", "<u4"), ("b", "<u4")])                                               # pf_trim_step
+TRIM_REFUSALS = ("none", "unknown", "field", "range", "too_many", "no_step", "phred")                             # pf_trim::Refusal, in its order
+
+
+def trim_parse_steps(steps) -> np.ndarray:
+    """Trimmomatic's words ("LEADING:10", "SLIDINGWINDOW:3:20", ...; a list or one string) as a TRIM_STEP array, by the parser of
+    the rule header (pfh_trim_parse_step).  A word that is refused raises ValueError with the refusal's text; .refusal names it."""
+    L = load_library()
+    if isinstance(steps, np.ndarray) and steps.dtype == TRIM_STEP:
+        return np.ascontiguousarray(steps)
+    if isinstance(steps, str):
+        steps = steps.split()
+    out = np.zeros(len(steps), dtype=TRIM_STEP)
+    for j, word in enumerate(steps):
+        c = L.pfh_trim_parse_step(os.fsencode(word), out[j:].ctypes.data)
+        if c:
+            e = ValueError("trim: %s: %s" % (word, L.pfh_trim_refusal_text(c).decode()))
+            e.refusal = TRIM_REFUSALS[c]
+            raise e
+    return out
+
+
+def trim_read(qual: bytes, steps, phred: int = 33):
+    """The rule of `trim` on one quality line (pfh_trim_read; no device): (b, e) of the kept interval, or None for a dropped read.
+    Steps or a phred that are refused raise ValueError."""
+    L = load_library()
+    st = trim_parse_steps(steps)
+    src = np.frombuffer(bytes(qual), dtype=np.uint8)
+    b, e = C.c_uint32(), C.c_uint32()
+    rc = L.pfh_trim_read(src.ctypes.data if len(src) else None, len(src), st.ctypes.data if len(st) else None, len(st), phred, C.byref(b), C.byref(e))
+    if rc < 0:
+        raise ValueError(L.pfh_last_error(None).decode())
+    return (b.value, e.value) if rc else None
+
+
+def trim_fastq_chunk(text: bytes, steps, phred: int = 33, final: bool = True):
+    """What pf_trim_fastq gives for one chunk, by the host's plain restatement (pfh_trim_fastq_chunk; no device): dict with clause (a
+    name of MASK_CLAUSES), bad_record, out, bytes_used, n_records, begin, len, stats."""
+    L = load_library()
+    st = trim_parse_steps(steps)
+    src = np.frombuffer(bytes(text), dtype=np.uint8)
+    n = len(src)
+    out = np.zeros(n + 1, dtype=np.uint8)
+    cap = n // 4 + 1
+    begin, ln = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32)
+    stats = np.zeros(len(TRIM_STATS_FIELDS), dtype=np.uint64)
+    out_n, used, recs, bad = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    clause = L.pfh_trim_fastq_chunk(src.ctypes.data if n else None, n, int(final), st.ctypes.data if len(st) else None, len(st), phred, out.ctypes.data,
+                                    C.byref(out_n), C.byref(used), begin.ctypes.data, ln.ctypes.data, cap, C.byref(recs), stats.ctypes.data, C.byref(bad))
+    if clause < 0:
+        raise ValueError(L.pfh_last_error(None).decode())
+    return dict(clause=MASK_CLAUSES[clause], bad_record=bad.value, out=out[: out_n.value].tobytes(), bytes_used=used.value, n_records=recs.value,
+                begin=begin[: recs.value].tolist(), len=ln[: recs.value].tolist(), stats={f: int(v) for f, v in zip(TRIM_STATS_FIELDS, stats)})
+
+
+def trim_fastq(inputs, out: str, steps, phred: int = 33, trimlog=None, chunk_bytes: int = 0) -> dict:
+    """`ploidyfrost trim -i ... -o out STEP...` (pfh_trim_fastq): the reads of the FASTQ file(s) `inputs`, one after the other,
+    quality-trimmed by `steps` (Trimmomatic's words) into `out`; trimlog: a file with one line per record.  Returns the statistics.  A
+    refusal raises RuntimeError (format refusals with the input's path and the 1-based record number); nothing is left under any
+    output name."""
+    L = load_library()
+    if isinstance(inputs, (str, bytes, os.PathLike)):
+        inputs = [inputs]
+    st = trim_parse_steps(steps)
+    paths = (C.c_char_p * max(len(inputs), 1))(*[os.fsencode(p) for p in inputs])
+    stats = np.zeros(len(TRIM_STATS_FIELDS), dtype=np.uint64)
+    rc = L.pfh_trim_fastq(paths, len(inputs), os.fsencode(out), st.ctypes.data if len(st) else None, len(st), phred,
+                          os.fsencode(trimlog) if trimlog else None, int(chunk_bytes), 0, stats.ctypes.data)
+    if rc:
+        raise RuntimeError(L.pfh_last_error(None).decode())
+    return {f: int(v) for f, v in zip(TRIM_STATS_FIELDS, stats)}
+
+
+def trim_fastq_pair(in1: str, in2: str, outs, steps, phred: int = 33, trimlog=None, chunk_bytes: int = 0):
+    """`ploidyfrost trim -1 in1 -2 in2 -o1 .. -u1 .. -o2 .. -u2 .. STEP...` (pfh_trim_fastq_pair): outs = (o1, u1, o2, u2).  Returns the
+    statistics of file 1 and of file 2 (the pair fields are the same in both)."""
+    L = load_library()
+    st = trim_parse_steps(steps)
+    assert len(outs) == 4
+    paths = (C.c_char_p * 4)(*[os.fsencode(p) for p in outs])
+    stats = np.zeros((2, len(TRIM_STATS_FIELDS)), dtype=np.uint64)
+    rc = L.pfh_trim_fastq_pair(os.fsencode(in1), os.fsencode(in2), paths, st.ctypes.data if len(st) else None, len(st), phred,
+                               os.fsencode(trimlog) if trimlog else None, int(chunk_bytes), 0, stats.ctypes.data)
+    if rc:
+        raise RuntimeError(L.pfh_last_error(None).decode())
+    return [{f: int(v) for f, v in zip(TRIM_STATS_FIELDS, row)} for row in stats]
 
 
 COUNT_STATS_FIELDS = ("reads", "bases", "kmers", "kmers_bad", "unique", "below_min", "above_max", "written")   # pf_count_stats
