@@ -220,6 +220,12 @@ int pfh_gfa_write_unitig_ids(const char *gfa_path, const char *out_path);
 /* [tests] the same file through the numbering replay with its inputs handed in (as pf_minimizer_replay_inputs hands them over): the host's
  * own counters + bump (saturating upper bounds), every unitig flagged */
 int pfh_gfa_write_unitig_ids_given_inputs(const char *gfa_path, const char *out_path, int bump);
+/* [tests] the same with the two arrays of pf_minimizer_replay_inputs themselves: n_slots saturating counters and one flag per unitig
+ * in the loader's order before the move (segments longer than k in file order, then the k-length ones).  Non-zero, with a message
+ * under pfh_last_error(NULL), when n_slots is not the table size of this graph or n_flags not its number of unitigs: the arrays
+ * are used as handed in or not at all */
+int pfh_gfa_write_unitig_ids_given_arrays(const char *gfa_path, const char *out_path, const uint8_t *counters8, uint64_t n_slots,
+                                          const uint8_t *flags, uint64_t n_flags);
 /* ---- `PloidyFrost model`: class GmmModel (src/GmmModel.hpp:5-49) and the driver of src/Main.cpp:636-692 ------------------
  * pfh_gmm_open needs no device; the readers are the reference's text parsers (readFreFile src/GmmModel.cpp:240-257,
  * readCovFile :21-239); pfh_gmm_fit = setMThreshold/setNThreshold/setMaxIterNum/setMaxDeltaNum + resize(gauss) +

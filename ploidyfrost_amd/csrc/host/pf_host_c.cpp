@@ -19,6 +19,7 @@
 #include "pf_filter.hpp"
 #include "pf_gmm_model.hpp"
 #include "pf_host_colors.hpp"
+#include "pf_host_minz.hpp"
 #include "pf_replay_par.hpp"
 #include "ploidyfrost_host.h"
 
@@ -796,6 +797,40 @@ int pfh_gfa_write_unitig_ids_given_inputs(const char *gfa_path, const char *out_
         if (!g.load_gfa(gfa_path, g_open_err, true)) return 1;
         const std::vector<uint8_t> flags(g.n(), 1);
         g.finish_numbering(nullptr, c.empty() ? nullptr : c.data(), c.empty() ? nullptr : flags.data(), c.size());
+        FILE *f = fopen(out_path, "w");
+        if (!f) { g_open_err = std::string("cannot write ") + out_path; return 1; }
+        for (uint32_t u = 0; u < g.n(); ++u) {
+            const std::string_view s = g.seq(u);
+            fprintf(f, "%u\t%.*s\n", u + 1, (int)s.size(), s.data());
+        }
+        fclose(f);
+        return 0;
+    } catch (const std::exception &e) {
+        g_open_err = std::string("ploidyfrost host layer: ") + e.what();
+        return 1;
+    }
+}
+// The numbering with the two arrays of pf_minimizer_replay_inputs themselves handed in: the counter table and one flag per unitig in
+// the loader's order before the move (long unitigs in file order, then the k-length ones).  Arrays of another geometry are refused,
+// never ignored: the replay must run from exactly what it was given.  [tests]
+int pfh_gfa_write_unitig_ids_given_arrays(const char *gfa_path, const char *out_path, const uint8_t *counters8, uint64_t n_slots,
+                                          const uint8_t *flags, uint64_t n_flags) {
+    try {
+        if (!counters8 || !flags) { g_open_err = "pfh_gfa_write_unitig_ids_given_arrays: counters8 and flags are both needed"; return 1; }
+        pfh::UnitigSet g;
+        if (!g.load_gfa(gfa_path, g_open_err, true)) return 1;
+        uint64_t n_kmers = 0;
+        for (uint32_t u = 0; u < g.n(); ++u) n_kmers += g.len_km(u);
+        const uint64_t slots = pfh::minimizer_table_slots(n_kmers);
+        if (n_slots != slots) {
+            g_open_err = "pfh_gfa_write_unitig_ids_given_arrays: " + std::to_string(n_slots) + " counters handed in, the table of this graph has " + std::to_string(slots);
+            return 2;
+        }
+        if (n_flags != g.n()) {
+            g_open_err = "pfh_gfa_write_unitig_ids_given_arrays: " + std::to_string(n_flags) + " flags handed in, the graph has " + std::to_string(g.n()) + " unitigs";
+            return 2;
+        }
+        g.finish_numbering(nullptr, counters8, flags, n_slots);
         FILE *f = fopen(out_path, "w");
         if (!f) { g_open_err = std::string("cannot write ") + out_path; return 1; }
         for (uint32_t u = 0; u < g.n(); ++u) {

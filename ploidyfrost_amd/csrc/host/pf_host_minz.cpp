@@ -283,6 +283,12 @@ struct Replay {
 
 }  // namespace
 
+uint64_t minimizer_table_slots(uint64_t n_kmers) {
+    uint64_t cap = 1ull << 16;
+    while (cap < n_kmers / 2 && cap < (1ull << 30)) cap <<= 1;
+    return cap;
+}
+
 void bifrost_numbering(int k, int g, const std::vector<SegRef> &segs, unsigned threads, UnitigNumbering &out, std::vector<uint8_t> *counters,
                        const uint8_t *counters_in, const uint8_t *touches_in, uint64_t counters_in_len) {
     const bool trace = getenv("PF_TRACE_LOAD") != nullptr;
@@ -298,8 +304,7 @@ void bifrost_numbering(int k, int g, const std::vector<SegRef> &segs, unsigned t
     if (S == 0 || g < 1 || g > k - 2 || g > 31) return;
     uint64_t n_kmers = 0;
     for (const SegRef &sg : segs) n_kmers += sg.len - (uint32_t)k + 1;
-    uint64_t cap = 1ull << 16;
-    while (cap < n_kmers / 2 && cap < (1ull << 30)) cap <<= 1;
+    const uint64_t cap = minimizer_table_slots(n_kmers);
     std::unique_ptr<std::atomic<uint8_t>[]> cnt(new std::atomic<uint8_t>[cap]);
     const size_t kChunk = 4096;
     const bool from_device = counters_in != nullptr && touches_in != nullptr && counters_in_len == cap;   // (same table geometry, or not used)

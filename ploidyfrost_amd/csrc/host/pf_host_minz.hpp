@@ -30,6 +30,9 @@ struct UnitigNumbering {
     uint64_t replayed_unitigs = 0;
 };
 
+// slots of the counter table of step 1 for a graph of n_kmers k-mers (pf_minimizer_table_slots of the device layer: the same geometry)
+uint64_t minimizer_table_slots(uint64_t n_kmers);
+
 // segs in file order; g <= k - 2 (bifrost/src/CompactedDBG.tcc:8383).  counters (optional): the saturating occurrence
 // counters of step 1, slot = mix(canonical minimizer) & (size - 1) -- the table the device pass (K-MINZ) bounds from above.
 // counters_in / touches_in (optional, both or neither): what the device pass already knows (pf_minimizer_replay_inputs) -- the counter

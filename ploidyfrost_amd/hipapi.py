@@ -454,6 +454,14 @@ class Device:
         self._check(self.L.pf_minimizer_crowding(self.h, g, limit, C.byref(mx), C.byref(crowded), _ptr(table) if want_table else None))
         return (mx.value, crowded.value, table) if want_table else (mx.value, crowded.value)
 
+    def minimizer_replay_inputs(self, g: int, limit: int = 15):
+        """K-MINZ's hand-off to the host replay (pf_minimizer_replay_inputs): (the census as saturating u8 counters, one u8 flag
+        per unitig in upload order: 1 when a counted position of it lies in a slot that reached `limit`)."""
+        counters8 = np.zeros(self.L.pf_minimizer_table_slots(self.L.pf_num_kmers(self.h)), dtype=np.uint8)
+        flags = np.zeros(max(1, self.n), dtype=np.uint8)
+        self._check(self.L.pf_minimizer_replay_inputs(self.h, g, limit, _ptr(counters8), _ptr(flags)))
+        return counters8, flags[: self.n]
+
     def kmc_decode(self, records: np.ndarray, n: int, suffix_bytes: int, counter_bytes: int, lut: np.ndarray, p: int, k: int):
         """K-KMC on raw .kmc_suf records (pf_kmc_decode): returns (kmers u64, counts u32) copied back to the host."""
         records = np.ascontiguousarray(records, dtype=np.uint8)
