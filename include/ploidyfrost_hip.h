@@ -67,6 +67,7 @@ enum pf_kernel {
     PF_K_MASK, /* K-MASK: everything one pf_mask_reads / pf_mask_fastq launches (index, classes, flag, paint), timed as one launch; unit: windows */
     PF_K_COUNT, /* K-COUNT: everything one pf_count_reads / pf_count_fastq launches (index, classes, insert, growth), timed as one launch; unit: windows */
     PF_K_TRIM, /* K-TRIM: everything one pf_trim_fastq / pf_trim_fastq_pair launches (index, intervals, sizes, scan, copy), timed as one launch; unit: records */
+    PF_K_UNITIG, /* K-UNITIG: everything one pf_unitig_build launches (index, adjacency, link, simplify, rank, cycles, emit), timed as one launch; unit: k-mers */
     PF_K_COUNT_
 };
 int pf_enable_timing(pf_ctx *, int on);
@@ -224,6 +225,36 @@ int pf_count_abort(pf_ctx *);
  * records needs no table).  kmers, counts, records_out, lut_out: [host|dev] */
 int pf_kmc_encode(pf_ctx *, const uint64_t *kmers, const uint32_t *counts, uint64_t n, uint32_t k, uint32_t lut_prefix_len, uint32_t counter_bytes,
                   uint8_t *records_out, uint64_t *lut_out);
+/* K-UNITIG: the compacted de Bruijn graph of reads built on the device -- what step `4.bifrost` of the reference's workflow does with
+ * `Bifrost build [-i] [-d] -k <k> -r reads.fq -o sample`.  The rule (csrc/pf_unitig_rule.hpp): the vertices are the sorted distinct
+ * canonical k-mers pf_count_finish gives (ci = 1); an oriented k-mer x links to y when succ(x) == [y], pred(y) == [x] and they are
+ * different k-mers, a unitig is a maximal chain of links; with clip_tips (-i) and / or del_isolated (-d) the unitigs of fewer than k
+ * k-mers that CompactedDBG::removeUnitigs removes go, and what is left is compacted once more.  The text of <sample>.gfa stays on the
+ * device until pf_unitig_release: the H line (KL = k, ML = g), then one `S <id> <sequence>` line per unitig, each in the reading
+ * whose first k-mer is the smaller one (a closed cycle from its smallest canonical k-mer), ascending by that k-mer, ids from 1, no L
+ * lines.  The same bytes on every call.  Single-sample graphs only. */
+#define PF_UNITIG_STAGES 6 /* index, adjacency + link, simplify, rank, cycles, emit */
+typedef struct pf_unitig_stats {
+    uint64_t distinct;     /* k-mers given */
+    uint64_t unitigs;      /* unitigs before simplifying */
+    uint64_t removed;      /* of them removed by clip_tips / del_isolated */
+    uint64_t unitigs_out;  /* S lines */
+    uint64_t longest;      /* bases of the longest sequence */
+    uint64_t bytes;        /* of the text, header line included */
+    uint64_t cycles;       /* closed cycles among the S lines */
+    uint64_t rounds;       /* pointer-jumping rounds of the rank stage (at most ceil(log2(2 n)) + 1) */
+    uint64_t cycle_rounds; /* the same of the cycle stage (0 without a closed cycle) */
+    double stage_ms[PF_UNITIG_STAGES]; /* device time of each stage, from events on the launch stream */
+} pf_unitig_stats;
+/* kmers: n sorted distinct canonical k-mers of length k, [host|dev] (anything else: PF_ERR_ARG by name); 3 <= k <= 31, 1 <= g <= k - 2 or
+ * g = PF_UNITIG_G_DEFAULT (Bifrost's default for k: k - 8 from k = 15, k - 4 from k = 7, else k - 2),
+ * n < 2^31, else PF_ERR_ARG.  Buffers that do not fit the free device memory: PF_ERR_OVERFLOW by name with n.  A second build without
+ * pf_unitig_release: PF_ERR_ARG by name. */
+#define PF_UNITIG_G_DEFAULT 0xFFFFFFFFu
+int pf_unitig_build(pf_ctx *, const uint64_t *kmers, uint64_t n, uint32_t k, uint32_t g, int clip_tips, int del_isolated, pf_unitig_stats *stats);
+/* bytes [first_byte, first_byte + len) of the text to the host; outside the text, or without a build: PF_ERR_ARG */
+int pf_unitig_fetch(pf_ctx *, uint64_t first_byte, uint64_t len, char *host);
+int pf_unitig_release(pf_ctx *);
 /* K-TRIM: reads quality-trimmed on the device -- what step `1.trim` of the reference's workflow does with
  * `trimmomatic PE -phred33 ... LEADING:10 TRAILING:10 SLIDINGWINDOW:3:20 MINLEN:50`.  The rule (csrc/pf_trim_rule.hpp): the quality of
  * position i of a read of n bases is q[i] = (int)byte - phred (phred 33 or 64; signed); the state is an interval [b, e) of the read,

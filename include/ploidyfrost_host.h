@@ -129,6 +129,22 @@ int pfh_count_encode_kmc1(const uint64_t *kmers, const uint32_t *counts, uint64_
 uint32_t pfh_count_counter_bytes(uint64_t cx, uint64_t cs);
 uint32_t pfh_count_lut_prefix_len(uint32_t k);
 const char *pfh_count_cut_text(int clause);
+/* ---- the compacted de Bruijn graph built from reads (K-UNITIG, pf_unitig_* in ploidyfrost_hip.h) ----
+ * Step `4.bifrost` of the reference's workflow (`Bifrost build -i -d -k 25 -r sample_filtered.fq -o sample`) in one call: the FASTQ
+ * inputs are counted as pfh_count_fastq counts them (every k-mer kept, both strands; the chunk contract and the format refusals of
+ * pfh_mask_fastq), the sorted k-mers are compacted into unitigs on the device and <out_prefix>.gfa is written (under a temporary name,
+ * renamed at the end).  g: the ML tag of the header, PFH_UNITIG_G_DEFAULT = Bifrost's default for k (0 is refused like any other g outside 1 .. k - 2).  The rule: csrc/pf_unitig_rule.hpp.  Refused by name
+ * before a device context exists: no input, no output, k outside 3 .. 31, g outside 1 .. k - 2, FASTA, gzip, an output that is an
+ * input.  counted / stats (may be NULL): what the count and the graph report.
+ * [tests] pfh_unitig_build_host: the host's plain restatement on k-mers in any order (no device): at most cap bytes of the text are
+ * written, *text_bytes is its size, stats_out = {distinct, unitigs, removed, unitigs_out, longest, bytes}; 1: bad k or no k-mers
+ * array, 2: bad g.  pfh_unitig_no_room_text: the wording of the refusal of buffers that do not fit the free device memory. */
+#define PFH_UNITIG_G_DEFAULT (-2147483647 - 1)
+int pfh_build_fastq(const char *const *inputs, uint32_t n_inputs, const char *out_prefix, uint32_t k, int32_t g, int clip_tips, int del_isolated,
+                    uint64_t chunk_bytes, uint64_t initial_slots, int device, pf_count_stats *counted, pf_unitig_stats *stats);
+int pfh_unitig_build_host(const uint64_t *kmers, uint64_t n, uint32_t k, int32_t g, int clip_tips, int del_isolated, char *text_out, uint64_t cap,
+                          uint64_t *text_bytes, uint64_t stats_out[6]);
+const char *pfh_unitig_no_room_text(uint64_t need, uint64_t free_bytes, uint64_t n_kmers);
 /* ---- reads quality-trimmed (K-TRIM, pf_trim_fastq / pf_trim_fastq_pair in ploidyfrost_hip.h) ----
  * Step `1.trim` of the reference's workflow (`trimmomatic PE -phred33 r1 r2 trim1 u1 trim2 u2 LEADING:10 TRAILING:10 SLIDINGWINDOW:3:20
  * MINLEN:50`) in one call.  The rule: csrc/pf_trim_rule.hpp (parity with Trimmomatic unpinned: the tool is not part of the build).

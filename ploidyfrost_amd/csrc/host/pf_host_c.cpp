@@ -10,6 +10,7 @@
 #include "pf_cutoffs.hpp"
 #include "pf_mask_host.hpp"
 #include "pf_count_host.hpp"
+#include "pf_build_host.hpp"
 #include "../pf_mask_rule.hpp"
 #include "../pf_trim_rule.hpp"
 #include "pf_trim_host.hpp"
@@ -449,6 +450,53 @@ int pfh_count_encode_kmc1(const uint64_t *kmers, const uint32_t *counts, uint64_
 uint32_t pfh_count_counter_bytes(uint64_t cx, uint64_t cs) { return pf_count::counter_bytes(cx, cs); }
 uint32_t pfh_count_lut_prefix_len(uint32_t k) { return (uint32_t)pf_count::lut_prefix_len((int)k); }
 const char *pfh_count_cut_text(int clause) { return pf_count::cut_text(clause); }
+
+// ---- `build` (K-UNITIG) ----
+static_assert(pfh::BuildOptions::G_DEFAULT == PFH_UNITIG_G_DEFAULT, "one sentinel for the default minimizer length");
+int pfh_build_fastq(const char *const *inputs, uint32_t n_inputs, const char *out_prefix, uint32_t k, int32_t g, int clip_tips, int del_isolated,
+                    uint64_t chunk_bytes, uint64_t initial_slots, int device, pf_count_stats *counted, pf_unitig_stats *stats) {
+    if (!out_prefix || (n_inputs && !inputs)) { g_open_err = "pfh_build_fastq: inputs and output prefix are needed"; return 1; }
+    try {
+        std::vector<std::string> in;
+        for (uint32_t i = 0; i < n_inputs; ++i) in.push_back(inputs[i] ? inputs[i] : "");
+        pfh::BuildOptions opt;
+        opt.k = k;
+        opt.g = g;
+        opt.clip_tips = clip_tips != 0;
+        opt.del_isolated = del_isolated != 0;
+        opt.chunk_bytes = chunk_bytes;
+        opt.initial_slots = initial_slots;
+        pf_count_stats cst = {};
+        pf_unitig_stats st = {};
+        const int rc = pfh::build_fastq(in, out_prefix, opt, device, cst, st, nullptr, g_open_err);
+        if (counted) *counted = cst;
+        if (stats) *stats = st;
+        return rc;
+    } catch (const std::exception &e) {
+        g_open_err = std::string("ploidyfrost host layer: ") + e.what();
+        return 1;
+    }
+}
+int pfh_unitig_build_host(const uint64_t *kmers, uint64_t n, uint32_t k, int32_t g, int clip_tips, int del_isolated, char *text_out, uint64_t cap,
+                          uint64_t *text_bytes, uint64_t stats_out[6]) {
+    if (!pf_count::k_ok(k) || (n && !kmers)) return 1;
+    const int gg = g == PFH_UNITIG_G_DEFAULT ? pf_unitig::default_g((int)k) : g;
+    if (!pf_unitig::g_ok(gg, (int)k)) return 2;
+    pf_unitig::Stats st;
+    const std::string text = pf_unitig::build_host(std::vector<uint64_t>(kmers, kmers + n), (int)k, clip_tips != 0, del_isolated != 0, gg, &st);
+    if (text_out) memcpy(text_out, text.data(), (size_t)std::min<uint64_t>(cap, text.size()));
+    if (text_bytes) *text_bytes = text.size();
+    if (stats_out) {
+        const uint64_t v[6] = {st.distinct, st.unitigs, st.removed, st.unitigs_out, st.longest, st.bytes};
+        memcpy(stats_out, v, sizeof v);
+    }
+    return 0;
+}
+const char *pfh_unitig_no_room_text(uint64_t need, uint64_t free_bytes, uint64_t n_kmers) {
+    static thread_local std::string text;
+    text = pf_unitig::no_room_text(need, free_bytes, n_kmers);
+    return text.c_str();
+}
 
 // ---- one graph over several GPUs -------------------------------------------------------------------
 int pfh_find_shard(pfh_run *r, uint32_t u0, uint32_t u1) {

@@ -33,6 +33,7 @@
 #include "pf_cdbg.hpp"
 #include "pf_cutoffs.hpp"
 #include "pf_count_host.hpp"
+#include "pf_build_host.hpp"
 #include "pf_mask_host.hpp"
 #include "pf_trim_host.hpp"
 #include "../pf_trim_rule.hpp"
@@ -98,6 +99,9 @@ void PrintUsage() {
          << "Usage: PloidyFrost trim -i <reads.fq> [-i <more.fq> ...] -o <trimmed.fq> STEP... [--phred 33|64] [--trimlog <file>] [--chunk-bytes N] [-v]" << endl
          << "Usage: PloidyFrost trim -1 <r1.fq> -2 <r2.fq> -o1 <p1.fq> -u1 <u1.fq> -o2 <p2.fq> -u2 <u2.fq> STEP... [the same options]" << endl
          << "                  (`trimmomatic SE|PE` on the device; STEP: LEADING:t TRAILING:t SLIDINGWINDOW:w:t MINLEN:l, applied in the order given)" << endl << endl
+         << "Usage: PloidyFrost build -k 25 [-i] [-d] -r <reads.fq> [-r <more.fq> ...] -o <sample> [-g G] [-t N] [--chunk-bytes N] [--initial-slots N] [-v]" << endl
+         << "                  (`Bifrost build -r` on the device: <sample>.gfa, the compacted de Bruijn graph of the reads; -i clips tips, -d deletes" << endl
+         << "                  isolated unitigs, both of fewer than k k-mers; single-sample graphs from FASTQ only)" << endl << endl
          << "Usage: PloidyFrost model ...          (GMM ploidy inference from the coverage / frequency files; `PloidyFrost model` prints its options)" << endl
          << "Usage: PloidyFrost density -f <column file> -o <outfile_prefix> [-n points] [-a adjust]   (kernel density of a column of numbers)" << endl
          << "Usage: PloidyFrost filter ...         (the row predicates of script/Filter.R over <prefix>_*cov.txt; -h prints its options)" << endl
@@ -571,6 +575,69 @@ int count_main(int argc, char **argv) {
     return 0;
 }
 
+// `build`: step `4.bifrost` of the reference's workflow (`Bifrost build -i -d -k 25 -r sample_filtered.fq -o sample`) on the device.  The
+// letters are Bifrost's: -i clips tips here, the reads come with -r.
+int build_main(int argc, char **argv) {
+    const char *usage = "Usage:PloidyFrost build -k 25 [-i] [-d] -r reads.fq [-r more.fq ...] -o sample [-g G] [-t N] [--chunk-bytes N] [--initial-slots N] [-v]";
+    pfh::BuildOptions opt;
+    string out;
+    vector<string> inputs;
+    bool verbose = false;
+    auto refuse = [&](const string &why) { cerr << "Error: build: " << why << endl << usage << endl; return 1; };
+    auto number = [&](const string &o, const char *text, uint64_t &v) {
+        char *end = nullptr;
+        errno = 0;
+        v = strtoull(text, &end, 10);
+        if (!errno && isdigit((unsigned char)text[0]) && !*end && v > 0) return true;
+        refuse(o + " takes a positive number, not '" + text + "'");
+        return false;
+    };
+    static const char *const not_built[] = {"-s", "-c", "-y", "-f", "-a", "-m", "-n", "-b", "-B", "-l", "-w", "-e"};
+    for (int i = 2; i < argc; ++i) {
+        const string a = argv[i];
+        for (const char *nb : not_built)
+            if (a == nb) return refuse(a + " is not built (a single-sample graph of the reads given with -r, written as GFA, is all there is)");
+        if (a == "--gpus") return refuse("--gpus is not built: the graph is made on one GPU");
+        if (a == "-i") { opt.clip_tips = true; continue; }
+        if (a == "-d") { opt.del_isolated = true; continue; }
+        if (a == "-v") { verbose = true; continue; }
+        const bool takes_value = a == "-k" || a == "-g" || a == "-t" || a == "-r" || a == "-o" || a == "--chunk-bytes" || a == "--initial-slots";
+        if (!takes_value) return refuse("unknown option " + a);
+        if (i + 1 >= argc) return refuse(a + " needs a value");
+        const char *val = argv[++i];
+        uint64_t v = 0;
+        if (a == "-r") inputs.push_back(val);
+        else if (a == "-o") out = val;
+        else if (!number(a, val, v)) return 1;
+        else if (a == "-k") opt.k = (uint32_t)std::min<uint64_t>(v, 0xFFFFFFFFull);
+        else if (a == "-g") opt.g = (int)std::min<uint64_t>(v, 0x7FFFFFFFull);
+        else if (a == "--chunk-bytes") opt.chunk_bytes = v;
+        else if (a == "--initial-slots") opt.initial_slots = v;
+        // (-t: accepted and ignored)
+    }
+    // refused by name, before anything is read or written
+    if (inputs.empty()) return refuse("-r <reads.fq> is missing");
+    if (out.empty()) return refuse("-o <sample> is missing");
+    { const string why = pfh::build_options_refusal(opt); if (!why.empty()) return refuse(why); }
+    pf_count_stats cst = {};
+    pf_unitig_stats st = {};
+    pfh::BuildTimes tm;
+    string err;
+    if (pfh::build_fastq(inputs, out, opt, 0, cst, st, &tm, err)) {
+        cerr << "Error: " << err << endl;
+        return 1;
+    }
+    cerr << "build: reads " << cst.reads << " bases " << cst.bases << " kmers " << cst.kmers << " bad " << cst.kmers_bad << " distinct " << st.distinct
+         << " unitigs " << st.unitigs << " removed " << st.removed << " unitigs_out " << st.unitigs_out << " longest " << st.longest << " bytes " << st.bytes
+         << (st.distinct == 0 ? " (no k-mer in the input: the header line alone is written)" : "") << endl;
+    if (verbose) {
+        cerr << "build: stream " << tm.stream_s << "s finish " << tm.finish_s << "s graph " << tm.graph_s << "s write " << tm.write_s << "s; device ms: index "
+             << st.stage_ms[0] << " adjacency " << st.stage_ms[1] << " simplify " << st.stage_ms[2] << " rank " << st.stage_ms[3] << " (" << st.rounds
+             << " rounds) cycles " << st.stage_ms[4] << " (" << st.cycles << " closed, " << st.cycle_rounds << " rounds) emit " << st.stage_ms[5] << endl;
+    }
+    return 0;
+}
+
 // `mask`: step 2 of the reference's workflow (`kmc_tools filter -hm <db> <reads.fq> -ci<L> <out.fq>`) against the database on the device
 int mask_main(int argc, char **argv) {
     const char *usage = "Usage:PloidyFrost mask -d kmc_database -i reads.fq [-i more.fq ...] -o out.fq (-l L | --auto-cutoffs) [-u U] [--chunk-bytes N] [-v]";
@@ -721,6 +788,7 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[1], "filter-multi")) return pfh::filter_main(argc, argv, true);    // script/Filter-multi.R
     if (!strcmp(argv[1], "mask")) return mask_main(argc, argv);
     if (!strcmp(argv[1], "count")) return count_main(argc, argv);
+    if (!strcmp(argv[1], "build")) return build_main(argc, argv);
     if (!strcmp(argv[1], "trim")) return trim_main(argc, argv);
     if (!strcmp(argv[1], "histogram")) {   // the file `kmc_tools transform <db> histogram <file>` writes, from the database on the device
         string db, out;

@@ -34,6 +34,11 @@ COUNT_STATS = np.dtype([(f, "<u8") for f in ("reads", "bases", "kmers", "kmers_b
 K_TRIM = K_COUNT + 1       # PF_K_TRIM ("k_trim"): everything one pf_trim_fastq / pf_trim_fastq_pair launches; unit: records
 TRIM_STEP = np.dtype([("kind", "<u4"), ("a", "<u4"), ("b", "<u4")])   # pf_trim_step
 TRIM_STATS = np.dtype([(f, "<u8") for f in ("reads", "kept", "dropped", "bases", "bases_kept", "both", "only1", "only2", "neither")])   # pf_trim_stats
+K_UNITIG = K_TRIM + 1      # PF_K_UNITIG ("k_unitig"): everything one pf_unitig_build launches; unit: k-mers
+UNITIG_G_DEFAULT = 0xFFFFFFFF   # PF_UNITIG_G_DEFAULT: Bifrost's default for k
+UNITIG_STAGES = ("index", "adjacency", "simplify", "rank", "cycles", "emit")
+UNITIG_STATS = np.dtype([(f, "<u8") for f in ("distinct", "unitigs", "removed", "unitigs_out", "longest", "bytes", "cycles", "rounds", "cycle_rounds")] +
+                        [("stage_ms", "<f8", (len(UNITIG_STAGES),))])   # pf_unitig_stats
 TRIM_KINDS = {"LEADING": 1, "TRAILING": 2, "SLIDINGWINDOW": 3, "MINLEN": 4}   # PF_TRIM_LEADING ..
 DENSITY_INFO = np.dtype([("n", "<u8"), ("min", "<f8"), ("max", "<f8"), ("sd", "<f8"), ("q1", "<f8"), ("q3", "<f8"), ("bw", "<f8"),
                          ("order", "<f8", (4,))])   # pf_density_info
@@ -213,6 +218,9 @@ def load_library() -> C.CDLL:
         "pf_count_finish": (i, [vp, u64, u64, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), vp]),
         "pf_count_abort": (i, [vp]),
         "pf_kmc_encode": (i, [vp, vp, vp, u64, u32, u32, u32, vp, vp]),
+        "pf_unitig_build": (i, [vp, vp, u64, u32, u32, i, i, vp]),
+        "pf_unitig_fetch": (i, [vp, u64, u64, vp]),
+        "pf_unitig_release": (i, [vp]),
         "pf_trim_fastq": (i, [vp, vp, u64, i, vp, u32, u32, vp, C.POINTER(u64), C.POINTER(u64), vp, vp, C.POINTER(u64), vp, C.POINTER(u64)]),
         "pf_trim_fastq_pair": (i, [vp, vp, u64, vp, u64, i, vp, u32, u32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(vp), C.POINTER(vp),
                                    C.POINTER(u64), vp, C.POINTER(u64)]),
@@ -239,7 +247,7 @@ DECLARED_SYMBOLS = ["pf_create", "pf_warmup", "pf_destroy", "pf_last_error", "pf
                     "pf_call_model_filter_multi", "pf_call_model_color_count", "pf_call_model_color_select",
                     "pf_gmm_density", "pf_count_histogram", "pf_mask_reads", "pf_mask_fastq",
                     "pf_count_begin", "pf_count_reads", "pf_count_fastq", "pf_count_finish", "pf_count_abort", "pf_kmc_encode",
-                    "pf_trim_fastq", "pf_trim_fastq_pair"]
+                    "pf_trim_fastq", "pf_trim_fastq_pair", "pf_unitig_build", "pf_unitig_fetch", "pf_unitig_release"]
 
 
 def trim_steps(steps) -> np.ndarray:
@@ -643,6 +651,25 @@ class Device:
 
     def count_abort(self):
         self._check(self.L.pf_count_abort(self.h))
+
+    def unitig_build(self, kmers, k: int, clip_tips: bool = False, del_isolated: bool = False, g=None):
+        """K-UNITIG (pf_unitig_build, pf_unitig_fetch, pf_unitig_release): (the text of the GFA file as bytes, statistics) of the
+        compacted de Bruijn graph of `kmers` -- sorted distinct canonical k-mers as count_finish gives them, a numpy array or a device
+        tensor.  g: the ML tag of the header, None = Bifrost's default for k."""
+        if isinstance(kmers, (list, tuple, np.ndarray)):
+            kmers = np.ascontiguousarray(kmers, dtype=np.uint64)
+        n = int(kmers.shape[0])
+        g = UNITIG_G_DEFAULT if g is None else min(max(int(g), 0), UNITIG_G_DEFAULT - 1)   # (0 is refused by name like any other g outside 1 .. k - 2)
+        stats = np.zeros(1, dtype=UNITIG_STATS)
+        self._check(self.L.pf_unitig_build(self.h, _ptr(kmers) if n else None, n, k, g, int(clip_tips), int(del_isolated), stats.ctypes.data))
+        try:
+            text = np.zeros(max(int(stats[0]["bytes"]), 1), dtype=np.uint8)
+            self._check(self.L.pf_unitig_fetch(self.h, 0, int(stats[0]["bytes"]), _ptr(text)))
+        finally:
+            self.L.pf_unitig_release(self.h)
+        out = {f: int(stats[0][f]) for f in UNITIG_STATS.names if f != "stage_ms"}
+        out["stage_ms"] = dict(zip(UNITIG_STAGES, (float(x) for x in stats[0]["stage_ms"])))
+        return text[: int(stats[0]["bytes"])].tobytes(), out
 
     def kmc_encode(self, kmers, counts, k: int, p: int, counter_bytes: int):
         """pf_kmc_encode, the inverse of kmc_decode: (records u8, lut u64 of 4^p + 1 entries) of sorted distinct k-mers.  kmers / counts:

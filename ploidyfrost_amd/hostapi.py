@@ -42,7 +42,7 @@ DECLARED_SYMBOLS = ["pfh_open", "pfh_close", "pfh_last_error", "pfh_set_output_d
                     "pfh_kmc_histogram", "pfh_cutoffs_from_rows", "pfh_set_auto_cutoffs", "pfh_cutoffs",
                     "pfh_mask_fastq", "pfh_mask_read", "pfh_mask_index_fastq", "pfh_mask_clause_text",
                     "pfh_count_fastq", "pfh_mask_fastq_counted", "pfh_count_reads_host", "pfh_count_encode_kmc1", "pfh_count_counter_bytes",
-                    "pfh_count_lut_prefix_len", "pfh_count_cut_text",
+                    "pfh_count_lut_prefix_len", "pfh_count_cut_text", "pfh_build_fastq", "pfh_unitig_build_host", "pfh_unitig_no_room_text",
                     "pfh_trim_fastq", "pfh_trim_fastq_pair", "pfh_trim_parse_step", "pfh_trim_refusal_text", "pfh_trim_read", "pfh_trim_fastq_chunk"]
 
 
@@ -203,6 +203,10 @@ def load_library() -> C.CDLL:
     L.pfh_count_counter_bytes.argtypes = [u64, u64]
     L.pfh_count_lut_prefix_len.restype = u32
     L.pfh_count_lut_prefix_len.argtypes = [u32]
+    L.pfh_build_fastq.argtypes = [C.POINTER(C.c_char_p), u32, C.c_char_p, u32, C.c_int32, C.c_int, C.c_int, u64, u64, C.c_int, vp, vp]
+    L.pfh_unitig_build_host.argtypes = [vp, u64, u32, C.c_int32, C.c_int, C.c_int, vp, u64, C.POINTER(u64), vp]
+    L.pfh_unitig_no_room_text.restype = C.c_char_p
+    L.pfh_unitig_no_room_text.argtypes = [u64, u64, u64]
     L.pfh_count_cut_text.restype = C.c_char_p
     L.pfh_count_cut_text.argtypes = [C.c_int]
     L.pfh_trim_fastq.argtypes = [C.POINTER(C.c_char_p), u32, C.c_char_p, vp, u32, u32, C.c_char_p, u64, C.c_int, vp]
@@ -635,6 +639,56 @@ def count_encode_kmc1(kmers, counts, k: int, ci: int = 2, cx: int = 10 ** 9, cs:
     pre, suf = np.zeros(pn.value, dtype=np.uint8), np.zeros(sn.value, dtype=np.uint8)
     L.pfh_count_encode_kmc1(*args, pre.ctypes.data, len(pre), C.byref(pn), suf.ctypes.data, len(suf), C.byref(sn))
     return pre.tobytes(), suf.tobytes()
+
+
+UNITIG_G_DEFAULT = -2 ** 31   # PFH_UNITIG_G_DEFAULT: Bifrost's minimizer length for k (pf_unitig::default_g decides)
+
+
+def _unitig_g(g) -> int:
+    """the g argument of the pfh_ calls: None = the default, any number as it is (0 and below are refused there by name)"""
+    return UNITIG_G_DEFAULT if g is None else max(min(int(g), 2 ** 31 - 1), UNITIG_G_DEFAULT + 1)
+
+
+UNITIG_STATS_FIELDS = ("distinct", "unitigs", "removed", "unitigs_out", "longest", "bytes")   # the first six of pf_unitig_stats
+UNITIG_STATS = np.dtype([(f, "<u8") for f in UNITIG_STATS_FIELDS + ("cycles", "rounds", "cycle_rounds")] + [("stage_ms", "<f8", (6,))])   # pf_unitig_stats
+
+
+def build_graph(inputs, out_prefix: str, k: int = 25, clip_tips: bool = False, del_isolated: bool = False, g=None, chunk_bytes: int = 0,
+                initial_slots: int = 0) -> dict:
+    """`ploidyfrost build` (pfh_build_fastq): the compacted de Bruijn graph of the FASTQ file(s) `inputs`, counted and compacted on the
+    device (K-COUNT, K-UNITIG), written to <out_prefix>.gfa -- `Bifrost build [-i] [-d] -k <k> -r <inputs> -o <out_prefix>`.  Returns
+    the statistics of the count and of the graph.  A refusal raises RuntimeError by name; nothing is left under the output name."""
+    L = load_library()
+    paths, n = _paths(inputs)
+    counted = np.zeros(len(COUNT_STATS_FIELDS), dtype=np.uint64)
+    stats = np.zeros(1, dtype=UNITIG_STATS)
+    rc = L.pfh_build_fastq(paths, n, os.fsencode(out_prefix), int(k), _unitig_g(g), int(clip_tips), int(del_isolated), int(chunk_bytes),
+                           int(initial_slots), 0, counted.ctypes.data, stats.ctypes.data)
+    if rc:
+        raise RuntimeError(L.pfh_last_error(None).decode())
+    d = {f: int(v) for f, v in zip(COUNT_STATS_FIELDS[:4], counted)}
+    d.update({f: int(stats[0][f]) for f in UNITIG_STATS.names if f != "stage_ms"})
+    d["stage_ms"] = [float(x) for x in stats[0]["stage_ms"]]
+    return d
+
+
+def unitig_build_host(kmers, k: int, clip_tips: bool = False, del_isolated: bool = False, g=None):
+    """(text of the GFA file as bytes, statistics): the rule of `build` on the host (pfh_unitig_build_host; no device) from canonical
+    k-mers in any order"""
+    L = load_library()
+    km = np.ascontiguousarray(kmers, dtype=np.uint64)
+    size, stats = C.c_uint64(), np.zeros(6, dtype=np.uint64)
+    text = np.zeros(64 + len(km) * (int(k) + 16), dtype=np.uint8)   # the header, and at most one line (S, tabs, id, k bases, newline) and one base a k-mer
+    rc = L.pfh_unitig_build_host(km.ctypes.data if len(km) else None, len(km), int(k), _unitig_g(g), int(clip_tips),
+                                 int(del_isolated), text.ctypes.data, len(text), C.byref(size), stats.ctypes.data)
+    if rc:
+        raise ValueError("unitig_build_host: %s" % ("k goes from 3 to 31" if rc == 1 else "g goes from 1 to k - 2"))
+    assert size.value <= len(text)
+    return text[: size.value].tobytes(), {f: int(v) for f, v in zip(UNITIG_STATS_FIELDS, stats)}
+
+
+def unitig_no_room_text(need: int, free_bytes: int, n_kmers: int) -> str:
+    return load_library().pfh_unitig_no_room_text(int(need), int(free_bytes), int(n_kmers)).decode()
 
 
 def count_counter_bytes(cx: int, cs: int) -> int:
