@@ -255,6 +255,38 @@ int pf_unitig_build(pf_ctx *, const uint64_t *kmers, uint64_t n, uint32_t k, uin
 /* bytes [first_byte, first_byte + len) of the text to the host; outside the text, or without a build: PF_ERR_ARG */
 int pf_unitig_fetch(pf_ctx *, uint64_t first_byte, uint64_t len, char *host);
 int pf_unitig_release(pf_ctx *);
+/* K-COLOR: the coloured graph of several files of reads -- what `Bifrost build -c -r s0.fq -r s1.fq ...` writes beside the graph.  The
+ * rule: csrc/pf_color_rule.hpp.  pf_unitig_build_colored is pf_unitig_build on the k-mers of all files together (same graph, same line
+ * order and ids) that also places every line's colour set (n_seeds rounds, 1 .. 255; *overflow = lines left over), ends every S line in
+ * `\tDA:Z:<round>` (0: overflow table) and keeps every live k-mer's place in graph order in the context.  pf_color_begin(n_colors, 1 ..
+ * 1024) builds the look-up table over those k-mers and clears one bit plane per colour (what does not fit: PF_ERR_OVERFLOW by name with
+ * the counts; a unitig with n_colors * k-mers >= 2^32: PF_ERR_ARG by name).  pf_color_reads / pf_color_fastq stream the reads of colour
+ * `colour` as pf_count_reads / pf_count_fastq take them (stats: that call's).  pf_color_finish turns the planes into runs of ids
+ * colour * m + position per line (stats: the whole colouring's); pf_color_fetch copies per line the head k-mer as written, the k-mer
+ * count and the slot, run_off (lines + 1 entries) and the runs (two words each: first id, last id) to the host; any may be NULL.
+ * pf_unitig_fetch gives the text, pf_unitig_release ends it all.  kmers: as pf_unitig_build; a device array stays the caller's and is
+ * read until pf_color_begin has returned. */
+typedef struct pf_color_stats {
+    uint64_t colors;
+    uint64_t reads;             /* records streamed */
+    uint64_t windows_colored;   /* windows whose k-mer lies in the graph */
+    uint64_t windows_unplaced;  /* windows of k bases whose k-mer -i / -d removed */
+    uint64_t windows_bad;       /* windows that hold a byte outside ACGTacgt */
+    uint64_t runs;
+    uint64_t overflow;          /* lines placed by no round */
+    uint64_t lines;
+    uint64_t table_slots, plane_words;
+    double table_ms, mark_ms, runs_ms; /* device time of the stages, from events on the launch stream */
+} pf_color_stats;
+int pf_unitig_build_colored(pf_ctx *, const uint64_t *kmers, uint64_t n, uint32_t k, uint32_t g, int clip_tips, int del_isolated, uint32_t n_seeds,
+                            pf_unitig_stats *stats, uint64_t *overflow);
+int pf_color_begin(pf_ctx *, uint32_t n_colors);
+int pf_color_reads(pf_ctx *, uint32_t colour, const char *text, uint64_t n_bytes, const uint64_t *read_off, const uint32_t *read_len, uint64_t n_reads,
+                   pf_color_stats *stats);
+int pf_color_fastq(pf_ctx *, uint32_t colour, const char *text, uint64_t n_bytes, int final, uint64_t *bytes_used, pf_color_stats *stats,
+                   uint64_t *bad_record);
+int pf_color_finish(pf_ctx *, pf_color_stats *stats);
+int pf_color_fetch(pf_ctx *, uint64_t *heads, uint32_t *m, uint32_t *slot, uint64_t *run_off, uint32_t *runs);
 /* K-TRIM: reads quality-trimmed on the device -- what step `1.trim` of the reference's workflow does with
  * `trimmomatic PE -phred33 ... LEADING:10 TRAILING:10 SLIDINGWINDOW:3:20 MINLEN:50`.  The rule (csrc/pf_trim_rule.hpp): the quality of
  * position i of a read of n bases is q[i] = (int)byte - phred (phred 33 or 64; signed); the state is an interval [b, e) of the read,

@@ -145,6 +145,25 @@ int pfh_build_fastq(const char *const *inputs, uint32_t n_inputs, const char *ou
 int pfh_unitig_build_host(const uint64_t *kmers, uint64_t n, uint32_t k, int32_t g, int clip_tips, int del_isolated, char *text_out, uint64_t cap,
                           uint64_t *text_bytes, uint64_t stats_out[6]);
 const char *pfh_unitig_no_room_text(uint64_t need, uint64_t free_bytes, uint64_t n_kmers);
+/* ---- the coloured graph built from several files of reads (K-COLOR, pf_color_* in ploidyfrost_hip.h) ----
+ * `Bifrost build -c -k 25 [-i] [-d] -r s0.fq -r s1.fq ... -o sample` in one call: pfh_build_fastq's graph of all inputs together with a
+ * DA tag on every S line, and <out_prefix>.bfg_colors (format version 2; csrc/host/pf_bfg_write.hpp), every input one colour in the
+ * order given, named by its path as given.  Both files are written under temporary names and renamed at the end: both or neither.
+ * Refused by name: what pfh_build_fastq refuses, more than 1024 inputs, the same path twice, n_seeds outside 1 .. 255 (0: 31).
+ * [tests] pfh_build_colored_host: the host's plain restatement (no device) from the reads of every colour -- reads[i], n_reads of them,
+ * belongs to colour colour_of[i] (ascending); the two files' bytes (at most the caps are written, the sizes always),
+ * graph_stats = pfh_unitig_build_host's six, color_stats = {colors, windows_colored, windows_unplaced, windows_bad, runs, overflow};
+ * 1: bad k or arguments, 2: bad g, 3: bad n_seeds, 4: too many colours or a unitig too long for them.
+ * pfh_bfg_colors_bytes: the bytes of the colour file from what pf_color_fetch gives.  pfh_color_no_room_text: the refusal's wording. */
+int pfh_build_colored_fastq(const char *const *inputs, uint32_t n_inputs, const char *out_prefix, uint32_t k, int32_t g, int clip_tips, int del_isolated,
+                            uint32_t n_seeds, uint64_t chunk_bytes, uint64_t initial_slots, int device, pf_count_stats *counted, pf_unitig_stats *stats,
+                            pf_color_stats *colored, uint64_t *color_bytes, double times_out[6]);
+int pfh_build_colored_host(const char *const *reads, const uint32_t *colour_of, uint64_t n_reads, uint32_t n_colors, const char *const *names, uint32_t k,
+                           int32_t g, int clip_tips, int del_isolated, uint32_t n_seeds, char *gfa_out, uint64_t gfa_cap, uint64_t *gfa_bytes,
+                           uint8_t *colors_out, uint64_t colors_cap, uint64_t *colors_bytes, uint64_t graph_stats[6], uint64_t color_stats[6]);
+int pfh_bfg_colors_bytes(const uint64_t *heads, const uint32_t *m, const uint32_t *slot, const uint64_t *run_off, const uint32_t *runs, uint64_t n_lines,
+                         uint32_t k, uint32_t n_seeds, const char *const *names, uint32_t n_colors, uint8_t *out, uint64_t cap, uint64_t *bytes);
+const char *pfh_color_no_room_text(uint64_t need, uint64_t free_bytes, uint64_t n_colors, uint64_t n_kmers);
 /* ---- reads quality-trimmed (K-TRIM, pf_trim_fastq / pf_trim_fastq_pair in ploidyfrost_hip.h) ----
  * Step `1.trim` of the reference's workflow (`trimmomatic PE -phred33 r1 r2 trim1 u1 trim2 u2 LEADING:10 TRAILING:10 SLIDINGWINDOW:3:20
  * MINLEN:50`) in one call.  The rule: csrc/pf_trim_rule.hpp (parity with Trimmomatic unpinned: the tool is not part of the build).

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "../pf_color_rule.hpp"
 #include "../pf_unitig_rule.hpp"
 #include "pf_count_host.hpp"
 #include "ploidyfrost_hip.h"
@@ -37,5 +38,20 @@ std::string build_options_refusal(const BuildOptions &opt);
 // worded in err (format refusals name the input and the 1-based record).
 int build_fastq(const std::vector<std::string> &inputs, const std::string &out_prefix, const BuildOptions &opt, int device, pf_count_stats &counted,
                 pf_unitig_stats &stats, BuildTimes *times, std::string &err);
+
+// ---- `ploidyfrost build-multi`: the host side of K-COLOR (pf_color_* in ploidyfrost_hip.h, the rule in ../pf_color_rule.hpp) ----
+struct ColoredTimes {
+    BuildTimes build;
+    double color_s = 0;       // every input streamed a second time (wall); its stages on the device: pf_color_stats
+    double serialise_s = 0;   // runs and slots into the bytes of the colour file (host)
+};
+// the refusals of the inputs that need no file ("" = none): more than 1024, the same path twice
+std::string colored_inputs_refusal(const std::vector<std::string> &inputs);
+// The whole of `ploidyfrost build-multi`: <out_prefix>.gfa and <out_prefix>.bfg_colors, every input one colour in the order given,
+// named by its path as given.  Both are written under temporary names and renamed at the end; nothing is left under any of the four
+// names after a refusal.  n_seeds = 0: pf_color::DEFAULT_SEEDS.  0 = ok, else worded in err.
+int build_colored_fastq(const std::vector<std::string> &inputs, const std::string &out_prefix, const BuildOptions &opt, uint32_t n_seeds, int device,
+                        pf_count_stats &counted, pf_unitig_stats &stats, pf_color_stats &colored, uint64_t &color_bytes, ColoredTimes *times,
+                        std::string &err);
 
 }  // namespace pfh

@@ -11,6 +11,7 @@
 #include "pf_mask_host.hpp"
 #include "pf_count_host.hpp"
 #include "pf_build_host.hpp"
+#include "pf_bfg_write.hpp"
 #include "../pf_mask_rule.hpp"
 #include "../pf_trim_rule.hpp"
 #include "pf_trim_host.hpp"
@@ -495,6 +496,105 @@ int pfh_unitig_build_host(const uint64_t *kmers, uint64_t n, uint32_t k, int32_t
 const char *pfh_unitig_no_room_text(uint64_t need, uint64_t free_bytes, uint64_t n_kmers) {
     static thread_local std::string text;
     text = pf_unitig::no_room_text(need, free_bytes, n_kmers);
+    return text.c_str();
+}
+int pfh_build_colored_fastq(const char *const *inputs, uint32_t n_inputs, const char *out_prefix, uint32_t k, int32_t g, int clip_tips, int del_isolated,
+                            uint32_t n_seeds, uint64_t chunk_bytes, uint64_t initial_slots, int device, pf_count_stats *counted, pf_unitig_stats *stats,
+                            pf_color_stats *colored, uint64_t *color_bytes, double times_out[6]) {
+    if (!out_prefix || (n_inputs && !inputs)) { g_open_err = "pfh_build_colored_fastq: inputs and output prefix are needed"; return 1; }
+    try {
+        std::vector<std::string> in;
+        for (uint32_t i = 0; i < n_inputs; ++i) in.push_back(inputs[i] ? inputs[i] : "");
+        pfh::BuildOptions opt;
+        opt.k = k;
+        opt.g = g;
+        opt.clip_tips = clip_tips != 0;
+        opt.del_isolated = del_isolated != 0;
+        opt.chunk_bytes = chunk_bytes;
+        opt.initial_slots = initial_slots;
+        pf_count_stats cst = {};
+        pf_unitig_stats st = {};
+        pf_color_stats col = {};
+        uint64_t nb = 0;
+        pfh::ColoredTimes tm;
+        const int rc = pfh::build_colored_fastq(in, out_prefix, opt, n_seeds, device, cst, st, col, nb, &tm, g_open_err);
+        if (counted) *counted = cst;
+        if (stats) *stats = st;
+        if (colored) *colored = col;
+        if (color_bytes) *color_bytes = nb;
+        if (times_out) {
+            const double v[6] = {tm.build.stream_s, tm.build.finish_s, tm.build.graph_s, tm.color_s, tm.serialise_s, tm.build.write_s};
+            memcpy(times_out, v, sizeof v);
+        }
+        return rc;
+    } catch (const std::exception &e) {
+        g_open_err = std::string("ploidyfrost host layer: ") + e.what();
+        return 1;
+    }
+}
+int pfh_build_colored_host(const char *const *reads, const uint32_t *colour_of, uint64_t n_reads, uint32_t n_colors, const char *const *names, uint32_t k,
+                           int32_t g, int clip_tips, int del_isolated, uint32_t n_seeds, char *gfa_out, uint64_t gfa_cap, uint64_t *gfa_bytes,
+                           uint8_t *colors_out, uint64_t colors_cap, uint64_t *colors_bytes, uint64_t graph_stats[6], uint64_t color_stats[6]) {
+    if (!pf_count::k_ok(k) || (n_reads && (!reads || !colour_of)) || !names || n_colors == 0) return 1;
+    const int gg = g == PFH_UNITIG_G_DEFAULT ? pf_unitig::default_g((int)k) : g;
+    if (!pf_unitig::g_ok(gg, (int)k)) return 2;
+    if (n_seeds == 0) n_seeds = pf_color::DEFAULT_SEEDS;
+    if (!pf_color::seeds_ok(n_seeds)) return 3;
+    if (n_colors > pf_color::MAX_COLORS) return 4;
+    std::vector<std::vector<std::string>> per(n_colors);
+    for (uint64_t i = 0; i < n_reads; ++i) {
+        if (colour_of[i] >= n_colors) return 1;
+        per[colour_of[i]].push_back(reads[i] ? reads[i] : "");
+    }
+    std::vector<std::string> nm;
+    for (uint32_t c = 0; c < n_colors; ++c) nm.push_back(names[c] ? names[c] : "");
+    pf_color::Colored cg;
+    pf_unitig::Stats gst;
+    pf_color::Stats cst;
+    const std::string text = pf_color::build_colored_host(per, (int)k, clip_tips != 0, del_isolated != 0, gg, n_seeds, cg, &gst, &cst);
+    if (gst.longest && (uint64_t)n_colors * (gst.longest - k + 1) >= (1ull << 32)) return 4;
+    std::vector<uint8_t> bytes;
+    if (!pf_bfg::write(cg, (int)k, n_seeds, nm, bytes).empty()) return 1;
+    if (gfa_out) memcpy(gfa_out, text.data(), (size_t)std::min<uint64_t>(gfa_cap, text.size()));
+    if (gfa_bytes) *gfa_bytes = text.size();
+    if (colors_out) memcpy(colors_out, bytes.data(), (size_t)std::min<uint64_t>(colors_cap, bytes.size()));
+    if (colors_bytes) *colors_bytes = bytes.size();
+    if (graph_stats) {
+        const uint64_t v[6] = {gst.distinct, gst.unitigs, gst.removed, gst.unitigs_out, gst.longest, gst.bytes};
+        memcpy(graph_stats, v, sizeof v);
+    }
+    if (color_stats) {
+        const uint64_t v[6] = {cst.colors, cst.windows_colored, cst.windows_unplaced, cst.windows_bad, cst.runs, cst.overflow};
+        memcpy(color_stats, v, sizeof v);
+    }
+    return 0;
+}
+int pfh_bfg_colors_bytes(const uint64_t *heads, const uint32_t *m, const uint32_t *slot, const uint64_t *run_off, const uint32_t *runs, uint64_t n_lines,
+                         uint32_t k, uint32_t n_seeds, const char *const *names, uint32_t n_colors, uint8_t *out, uint64_t cap, uint64_t *bytes) {
+    if (!run_off || !names || (n_lines && (!heads || !m || !slot)) || !pf_count::k_ok(k) || !pf_color::seeds_ok(n_seeds)) { g_open_err = "pfh_bfg_colors_bytes: arrays, k or n_seeds"; return 1; }
+    pf_color::Colored cg;
+    cg.lines.resize((size_t)n_lines);
+    for (uint64_t j = 0; j < n_lines; ++j) {
+        cg.lines[j].head = heads[j];
+        cg.lines[j].m = m[j];
+        cg.lines[j].slot = slot[j];
+        if (slot[j] >= n_lines) cg.overflow += 1;
+    }
+    cg.run_off.assign(run_off, run_off + n_lines + 1);
+    if (cg.run_off.back() && !runs) { g_open_err = "pfh_bfg_colors_bytes: runs is needed"; return 1; }
+    for (uint64_t i = 0; i < cg.run_off.back(); ++i) cg.runs.emplace_back(runs[2 * i], runs[2 * i + 1]);
+    std::vector<std::string> nm;
+    for (uint32_t c = 0; c < n_colors; ++c) nm.push_back(names[c] ? names[c] : "");
+    std::vector<uint8_t> b;
+    const std::string why = pf_bfg::write(cg, (int)k, n_seeds, nm, b);
+    if (!why.empty()) { g_open_err = "pfh_bfg_colors_bytes: " + why; return 1; }
+    if (out) memcpy(out, b.data(), (size_t)std::min<uint64_t>(cap, b.size()));
+    if (bytes) *bytes = b.size();
+    return 0;
+}
+const char *pfh_color_no_room_text(uint64_t need, uint64_t free_bytes, uint64_t n_colors, uint64_t n_kmers) {
+    static thread_local std::string text;
+    text = pf_color::no_room_text(need, free_bytes, n_colors, n_kmers);
     return text.c_str();
 }
 

@@ -6,26 +6,13 @@
 #include <cstring>
 #include <mutex>
 
+#include "../pf_color_rule.hpp"
 #include "pf_parallel.hpp"
 
 namespace pfh {
 
-// ---- wyhash final version 3 (public domain, github.com/wangyi-fudan/wyhash) for an 8-byte key ----------
-namespace {
-inline uint64_t wymix(uint64_t a, uint64_t b) {
-    __uint128_t r = (__uint128_t)a * b;
-    return (uint64_t)r ^ (uint64_t)(r >> 64);
-}
-const uint64_t kWyp0 = 0xa0761d6478bd642full, kWyp1 = 0xe7037ed1a0b428dbull;
-}  // namespace
-
-uint64_t bifrost_kmer_hash(uint64_t x, uint64_t seed) {
-    // len = 8: a = (first 4 bytes << 32) | last 4 bytes, b = (last 4 bytes << 32) | first 4 bytes, little endian
-    const uint64_t lo = x & 0xFFFFFFFFull, hi = x >> 32;
-    const uint64_t a = (lo << 32) | hi, b = (hi << 32) | lo;
-    seed ^= kWyp0;
-    return wymix(kWyp1 ^ 8, wymix(a ^ kWyp1, b ^ seed));
-}
+// the hash itself lies in ../pf_color_rule.hpp, where the device that writes colour files finds it too
+uint64_t bifrost_kmer_hash(uint64_t x, uint64_t seed) { return pf_color::bifrost_kmer_hash(x, seed); }
 
 namespace {
 

@@ -101,7 +101,10 @@ void PrintUsage() {
          << "                  (`trimmomatic SE|PE` on the device; STEP: LEADING:t TRAILING:t SLIDINGWINDOW:w:t MINLEN:l, applied in the order given)" << endl << endl
          << "Usage: PloidyFrost build -k 25 [-i] [-d] -r <reads.fq> [-r <more.fq> ...] -o <sample> [-g G] [-t N] [--chunk-bytes N] [--initial-slots N] [-v]" << endl
          << "                  (`Bifrost build -r` on the device: <sample>.gfa, the compacted de Bruijn graph of the reads; -i clips tips, -d deletes" << endl
-         << "                  isolated unitigs, both of fewer than k k-mers; single-sample graphs from FASTQ only)" << endl << endl
+         << "                  isolated unitigs, both of fewer than k k-mers; single-sample graphs from FASTQ only)" << endl
+         << "Usage: PloidyFrost build-multi -k 25 [-i] [-d] -r <s0.fq> -r <s1.fq> [-r ...] -o <sample> [-g G] [-t N] [--chunk-bytes N] [--initial-slots N] [-v]" << endl
+         << "                  (`Bifrost build -c -r ... -r ...` on the device: <sample>.gfa of all files together, every S line with its DA tag, and" << endl
+         << "                  <sample>.bfg_colors, one colour per -r in the order given; what the calling run takes with -g and -f)" << endl << endl
          << "Usage: PloidyFrost model ...          (GMM ploidy inference from the coverage / frequency files; `PloidyFrost model` prints its options)" << endl
          << "Usage: PloidyFrost density -f <column file> -o <outfile_prefix> [-n points] [-a adjust]   (kernel density of a column of numbers)" << endl
          << "Usage: PloidyFrost filter ...         (the row predicates of script/Filter.R over <prefix>_*cov.txt; -h prints its options)" << endl
@@ -596,7 +599,8 @@ int build_main(int argc, char **argv) {
     for (int i = 2; i < argc; ++i) {
         const string a = argv[i];
         for (const char *nb : not_built)
-            if (a == nb) return refuse(a + " is not built (a single-sample graph of the reads given with -r, written as GFA, is all there is)");
+            if (a == nb) return refuse(a + " is not built (a single-sample graph of the reads given with -r, written as GFA, is all there is)" +
+                                       (a == "-c" ? "; the coloured graph of several samples: `build-multi`" : ""));
         if (a == "--gpus") return refuse("--gpus is not built: the graph is made on one GPU");
         if (a == "-i") { opt.clip_tips = true; continue; }
         if (a == "-d") { opt.del_isolated = true; continue; }
@@ -634,6 +638,75 @@ int build_main(int argc, char **argv) {
         cerr << "build: stream " << tm.stream_s << "s finish " << tm.finish_s << "s graph " << tm.graph_s << "s write " << tm.write_s << "s; device ms: index "
              << st.stage_ms[0] << " adjacency " << st.stage_ms[1] << " simplify " << st.stage_ms[2] << " rank " << st.stage_ms[3] << " (" << st.rounds
              << " rounds) cycles " << st.stage_ms[4] << " (" << st.cycles << " closed, " << st.cycle_rounds << " rounds) emit " << st.stage_ms[5] << endl;
+    }
+    return 0;
+}
+
+// `build-multi`: the last step of the reference's multi-sample workflow (`Bifrost build -i -d -k 25 -r s0.fq -r s1.fq ... -c -o sample`)
+// on the device: the graph of `build` from all files together, and the colour file with one colour per -r in the order given.
+int build_multi_main(int argc, char **argv) {
+    const char *usage = "Usage:PloidyFrost build-multi -k 25 [-i] [-d] -r s0.fq -r s1.fq [-r ...] -o sample [-g G] [-t N] [--chunk-bytes N] [--initial-slots N] [-v]";
+    pfh::BuildOptions opt;
+    string out;
+    vector<string> inputs;
+    bool verbose = false;
+    auto refuse = [&](const string &why) { cerr << "Error: build-multi: " << why << endl << usage << endl; return 1; };
+    auto number = [&](const string &o, const char *text, uint64_t &v) {
+        char *end = nullptr;
+        errno = 0;
+        v = strtoull(text, &end, 10);
+        if (!errno && isdigit((unsigned char)text[0]) && !*end && v > 0) return true;
+        refuse(o + " takes a positive number, not '" + text + "'");
+        return false;
+    };
+    static const char *const not_built[] = {"-s", "-y", "-f", "-a", "-m", "-n", "-b", "-B", "-l", "-w", "-e"};
+    for (int i = 2; i < argc; ++i) {
+        const string a = argv[i];
+        for (const char *nb : not_built)
+            if (a == nb) return refuse(a + " is not built (the coloured graph of the reads given with -r, one colour a file, is all there is)");
+        if (a == "--gpus") return refuse("--gpus is not built: the graph is made on one GPU");
+        if (a == "-i") { opt.clip_tips = true; continue; }
+        if (a == "-d") { opt.del_isolated = true; continue; }
+        if (a == "-v") { verbose = true; continue; }
+        if (a == "-c") continue;   // (Bifrost's letter for what this sub-command always does)
+        const bool takes_value = a == "-k" || a == "-g" || a == "-t" || a == "-r" || a == "-o" || a == "--chunk-bytes" || a == "--initial-slots";
+        if (!takes_value) return refuse("unknown option " + a);
+        if (i + 1 >= argc) return refuse(a + " needs a value");
+        const char *val = argv[++i];
+        uint64_t v = 0;
+        if (a == "-r") inputs.push_back(val);
+        else if (a == "-o") out = val;
+        else if (!number(a, val, v)) return 1;
+        else if (a == "-k") opt.k = (uint32_t)std::min<uint64_t>(v, 0xFFFFFFFFull);
+        else if (a == "-g") opt.g = (int)std::min<uint64_t>(v, 0x7FFFFFFFull);
+        else if (a == "--chunk-bytes") opt.chunk_bytes = v;
+        else if (a == "--initial-slots") opt.initial_slots = v;
+        // (-t: accepted and ignored)
+    }
+    // refused by name, before anything is read or written
+    if (inputs.empty()) return refuse("-r <reads.fq> is missing");
+    if (out.empty()) return refuse("-o <sample> is missing");
+    { const string why = pfh::build_options_refusal(opt); if (!why.empty()) return refuse(why); }
+    { const string why = pfh::colored_inputs_refusal(inputs); if (!why.empty()) return refuse(why); }
+    pf_count_stats cst = {};
+    pf_unitig_stats st = {};
+    pf_color_stats col = {};
+    uint64_t color_bytes = 0;
+    pfh::ColoredTimes tm;
+    string err;
+    if (pfh::build_colored_fastq(inputs, out, opt, 0, 0, cst, st, col, color_bytes, &tm, err)) {
+        cerr << "Error: " << err << endl;
+        return 1;
+    }
+    cerr << "build-multi: colors " << col.colors << " reads " << cst.reads << " bases " << cst.bases << " kmers " << cst.kmers << " bad " << cst.kmers_bad
+         << " distinct " << st.distinct << " unitigs " << st.unitigs << " removed " << st.removed << " unitigs_out " << st.unitigs_out << " longest "
+         << st.longest << " bytes " << st.bytes << " windows_colored " << col.windows_colored << " windows_unplaced " << col.windows_unplaced << " runs "
+         << col.runs << " overflow " << col.overflow << " color_bytes " << color_bytes << endl;
+    if (verbose) {
+        cerr << "build-multi: stream " << tm.build.stream_s << "s finish " << tm.build.finish_s << "s graph " << tm.build.graph_s << "s color " << tm.color_s
+             << "s serialise " << tm.serialise_s << "s write " << tm.build.write_s << "s; device ms: index " << st.stage_ms[0] << " adjacency " << st.stage_ms[1]
+             << " simplify " << st.stage_ms[2] << " rank " << st.stage_ms[3] << " cycles " << st.stage_ms[4] << " emit " << st.stage_ms[5] << " table "
+             << col.table_ms << " mark " << col.mark_ms << " runs " << col.runs_ms << endl;
     }
     return 0;
 }
@@ -789,6 +862,7 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[1], "mask")) return mask_main(argc, argv);
     if (!strcmp(argv[1], "count")) return count_main(argc, argv);
     if (!strcmp(argv[1], "build")) return build_main(argc, argv);
+    if (!strcmp(argv[1], "build-multi")) return build_multi_main(argc, argv);
     if (!strcmp(argv[1], "trim")) return trim_main(argc, argv);
     if (!strcmp(argv[1], "histogram")) {   // the file `kmc_tools transform <db> histogram <file>` writes, from the database on the device
         string db, out;

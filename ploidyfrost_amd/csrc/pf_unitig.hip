@@ -28,6 +28,11 @@
 //                  k-mer with rocprim::radix_sort_pairs over bits [0, 2k), line lengths scanned exclusively; every live node of a
 //                  chosen reading writes its last base at line + prefix + k - 1 + distance, the start the prefix, its first k - 1
 //                  bases and the '\n'                                                           3 gathers per node (root, line, offset)
+//   placement  pf_unitig_build_colored only (pf_color_rule.hpp; `build-multi`): between the sort and the sizing of the text, n_seeds
+//                  rounds of an ask kernel (atomicMin of the line into the claim of a free slot) and a grant kernel (the claim's line
+//                  takes the slot; DA = the round), the lines left over numbered behind the slots by a scan, the tag's bytes added to
+//                  the line lengths; emit writes the tag, and the flat position km_off[line] + distance of every live k-mer, which
+//                  K-COLOR (pf_color.hip) reads with the lines' heads, k-mer counts and slots (pf_unitig_state.hpp)   1 hash a round and line
 // Every loop is bounded (by k, the slot count or 2 n) and sets an error flag at its bound; nothing spins.  The kernels are gathers
 // bound by latency: 256 threads a block, no LDS, no scratch, and no second argument of __launch_bounds__ that would make the compiler
 // trade registers for it -- all of them compile to 24 VGPRs or fewer (eight wavefronts a SIMD) but k_uni_adj, which keeps its eight
@@ -44,10 +49,12 @@
 #include <string>
 
 #include "../../include/ploidyfrost_hip.h"
+#include "pf_color_rule.hpp"
 #include "pf_ctx.hpp"
 #include "pf_reads_dev.hpp"
 #include "pf_scan.hpp"
 #include "pf_unitig_rule.hpp"
+#include "pf_unitig_state.hpp"
 
 namespace pf {
 
@@ -63,11 +70,6 @@ struct UniDev {   // device counters of one build
     unsigned long long starts, removed, cycle_nodes, cycles, old_cycles, longest;
     uint32_t stuck, bad_input;
     uint32_t changed[2 * UNI_MAX_ROUNDS];   // one word a round: rank, then cycles
-};
-
-struct UnitigState {   // the text of the last build until pf_unitig_release
-    char *text = nullptr;
-    uint64_t bytes = 0;
 };
 
 __device__ inline uint64_t node_read(const uint64_t *__restrict__ kmers, uint32_t v, int k) {
@@ -314,13 +316,14 @@ __global__ __launch_bounds__(256) void k_uni_keys(const uint32_t *__restrict__ i
     for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < n_lines; j += (uint64_t)gridDim.x * 256) keys[j] = node_read(kmers, ids[j], k);
 }
 __global__ __launch_bounds__(256) void k_uni_lines(const uint32_t *__restrict__ sorted, uint64_t n_lines, int k, const uint2 *__restrict__ rank,
-                                                   uint32_t *__restrict__ line_of, uint32_t *__restrict__ len, UniDev *d) {
+                                                   uint32_t *__restrict__ line_of, uint32_t *__restrict__ len, uint32_t *__restrict__ m_of, UniDev *d) {
     uint64_t longest = 0;
     for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < n_lines; j += (uint64_t)gridDim.x * 256) {
         const uint32_t r = sorted[j];
         const uint64_t m = (uint64_t)rank[r ^ 1u].y + 1;   // the mirror of the start is the mirror chain's last node
         line_of[r] = (uint32_t)j;
         len[j] = (uint32_t)pf_unitig::line_bytes(j + 1, m, k);
+        if (m_of) m_of[j] = (uint32_t)m;   // (a coloured build: the lines' k-mer counts are scanned into graph order)
         longest = m + (uint64_t)k - 1 > longest ? m + (uint64_t)k - 1 : longest;
     }
     longest = wave_max_u64(longest);
@@ -328,7 +331,8 @@ __global__ __launch_bounds__(256) void k_uni_lines(const uint32_t *__restrict__ 
 }
 __global__ __launch_bounds__(256) void k_uni_emit(uint64_t n_nodes, const uint64_t *__restrict__ kmers, int k, const uint2 *__restrict__ rank,
                                                   const uint8_t *__restrict__ dead, const uint32_t *__restrict__ line_of, const uint64_t *__restrict__ off,
-                                                  const uint32_t *__restrict__ len, uint64_t header_bytes, char *__restrict__ text) {
+                                                  const uint32_t *__restrict__ len, uint64_t header_bytes, char *__restrict__ text,
+                                                  const uint8_t *__restrict__ da, const uint64_t *__restrict__ km_off, uint32_t *__restrict__ flat_of) {
     for (uint64_t v64 = (uint64_t)blockIdx.x * 256 + threadIdx.x; v64 < n_nodes; v64 += (uint64_t)gridDim.x * 256) {
         const uint32_t v = (uint32_t)v64;
         if (dead && dead[v >> 1]) continue;
@@ -340,6 +344,7 @@ __global__ __launch_bounds__(256) void k_uni_emit(uint64_t n_nodes, const uint64
         const uint32_t digits = pf_unitig::id_digits((uint64_t)j + 1);
         char *seq = line + 2 + digits + 1;
         seq[(uint64_t)(k - 1) + p.y] = pf_unitig::base_char(x);
+        if (flat_of) flat_of[v >> 1] = (uint32_t)(km_off[j] + p.y);   // a coloured build: the k-mer's place in graph order
         if (p.x != v) continue;
         line[0] = 'S';
         line[1] = '\t';
@@ -348,6 +353,47 @@ __global__ __launch_bounds__(256) void k_uni_emit(uint64_t n_nodes, const uint64
         line[2 + digits] = '\t';
         for (int b = 0; b < k - 1; ++b) seq[b] = pf_unitig::base_char(x >> (2 * (k - 1 - b)));
         line[len[j] - 1] = '\n';
+        if (da) {   // a coloured build: "\tDA:Z:<round>" before the end of the line
+            uint32_t tag = da[j];
+            char *end = line + len[j] - 1;
+            for (uint32_t c = pf_unitig::id_digits(tag); c-- > 0; tag /= 10) *--end = (char)('0' + tag % 10);
+            end -= pf_color::DA_PREFIX_BYTES;
+            for (uint32_t c = 0; c < pf_color::DA_PREFIX_BYTES; ++c) end[c] = pf_color::DA_PREFIX[c];
+        }
+    }
+}
+
+// ---- placement of the lines' colour sets (pf_color_rule.hpp): one ask and one grant kernel a round ----
+// owner[s] = the line that holds slot s, written by grants only; claim[s] = the smallest line that asked for the free slot s this
+// round.  A claimed slot is granted in the same round, so a free slot's claim is NONE when a round begins.
+__global__ __launch_bounds__(256) void k_uni_place_ask(const uint64_t *__restrict__ heads, uint64_t n_lines, int k, uint32_t round,
+                                                       const uint32_t *__restrict__ slot, const uint32_t *__restrict__ owner, uint32_t *claim) {
+    for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < n_lines; j += (uint64_t)gridDim.x * 256) {
+        if (slot[j] != UNI_NONE) continue;
+        const uint32_t at = pf_color::asked_slot(heads[j], k, round, n_lines);
+        if (owner[at] == UNI_NONE) atomicMin(&claim[at], (uint32_t)j);
+    }
+}
+__global__ __launch_bounds__(256) void k_uni_place_grant(const uint64_t *__restrict__ heads, uint64_t n_lines, int k, uint32_t round, uint32_t *slot,
+                                                         uint32_t *owner, const uint32_t *__restrict__ claim, uint8_t *__restrict__ da) {
+    for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < n_lines; j += (uint64_t)gridDim.x * 256) {
+        if (slot[j] != UNI_NONE) continue;
+        const uint32_t at = pf_color::asked_slot(heads[j], k, round, n_lines);
+        if (claim[at] != (uint32_t)j) continue;   // (a slot taken in an earlier round keeps the claim of its placed line)
+        owner[at] = (uint32_t)j;
+        slot[j] = at;
+        da[j] = (uint8_t)round;
+    }
+}
+__global__ __launch_bounds__(256) void k_uni_place_left(const uint32_t *__restrict__ slot, uint64_t n_lines, uint32_t *__restrict__ left) {
+    for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < n_lines; j += (uint64_t)gridDim.x * 256) left[j] = slot[j] == UNI_NONE ? 1u : 0u;
+}
+// the lines left over take the overflow slots in their order; every line's length grows by its tag
+__global__ __launch_bounds__(256) void k_uni_place_end(uint64_t n_lines, const uint32_t *__restrict__ left, const uint32_t *__restrict__ rank, uint32_t *slot,
+                                                       const uint8_t *__restrict__ da, uint32_t *len) {
+    for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < n_lines; j += (uint64_t)gridDim.x * 256) {
+        if (left[j]) slot[j] = (uint32_t)(n_lines + rank[j]);
+        len[j] += pf_color::da_bytes(da[j]);
     }
 }
 
@@ -357,7 +403,14 @@ static UnitigState *unitig_state(pf_ctx *ctx) { return static_cast<UnitigState *
 void unitig_destroy(pf_ctx *ctx) {
     UnitigState *S = unitig_state(ctx);
     if (!S) return;
+    color_destroy(S);
     (void)hipFree(S->text);
+    (void)hipFree(S->kmers_own);
+    (void)hipFree(S->flat_of);
+    (void)hipFree(S->heads);
+    (void)hipFree(S->m_of);
+    (void)hipFree(S->km_off);
+    (void)hipFree(S->slot);
     delete S;
     ctx->unitig = nullptr;
 }
@@ -407,9 +460,12 @@ static int uni_fits(pf_ctx *ctx, uint64_t need, uint64_t n) {
 
 using namespace pf;
 
-extern "C" int pf_unitig_build(pf_ctx *ctx, const uint64_t *kmers, uint64_t n, uint32_t k, uint32_t g, int clip_tips, int del_isolated,
-                               pf_unitig_stats *stats) {
+// n_seeds = 0: the plain build.  Otherwise the coloured one: the lines' colour sets are placed before the text is sized, every S line
+// ends in its DA tag, and what K-COLOR needs stays in the context beside the text.
+static int unitig_build_impl(pf_ctx *ctx, const uint64_t *kmers, uint64_t n, uint32_t k, uint32_t g, int clip_tips, int del_isolated, uint32_t n_seeds,
+                             pf_unitig_stats *stats, uint64_t *overflow_out) {
     if (!ctx) return PF_ERR_ARG;
+    const bool colored = n_seeds != 0;
     auto refuse = [&](const std::string &m) { pf::CtxErr{ctx} = m; return (int)PF_ERR_ARG; };
     if (ctx->unitig) return refuse("pf_unitig_build: a built graph is held already (pf_unitig_release comes first)");
     if (!pf_count::k_ok(k)) return refuse("pf_unitig_build: k = " + std::to_string(k) + ": " + pf_count::cut_text(pf_count::CUT_K));
@@ -430,10 +486,11 @@ extern "C" int pf_unitig_build(pf_ctx *ctx, const uint64_t *kmers, uint64_t n, u
     pf_unitig_stats st = {};
     st.distinct = n;
     UniDev h = {};
-    DevTmp<uint64_t> staged, keys0, keys1, off;
+    DevTmp<uint64_t> staged, keys0, keys1, off, km_off;
     DevTmp<UniSlot> tab;
-    DevTmp<uint8_t> adj0, adj1, dead, flag, scratch, sort_tmp;
-    DevTmp<uint32_t> link, line_of, ids, sorted, len;
+    DevTmp<uint8_t> adj0, adj1, dead, flag, scratch, sort_tmp, da;
+    DevTmp<uint32_t> link, line_of, ids, sorted, len, m_of, slot, owner, claim, left, left_rank, flat_of;
+    uint64_t overflow = 0, n_live = 0;
     DevTmp<uint2> ra, rb, rc;
     DevTmp<UniDev> dev;
     UNI_ALLOC(dev, sizeof(UniDev));
@@ -572,7 +629,44 @@ extern "C" int pf_unitig_build(pf_ctx *ctx, const uint64_t *kmers, uint64_t n, u
         UNI_ALLOC(sort_tmp, need);
         PF_HIP(rocprim::radix_sort_pairs(sort_tmp.p, need, keys0.p, keys1.p, ids.p, sorted.p, (size_t)n_lines, 0, 2 * k, ctx->stream));
         PF_HIP(hipMemsetAsync(line_at, 0xFF, n_nodes * 4, ctx->stream));
-        k_uni_lines<<<g_l, 256, 0, ctx->stream>>>(sorted.p, n_lines, K, rank, line_at, len.p, dev.p);
+        if (colored) {
+            { const int rc_ = uni_fits(ctx, n_lines * (4 * 6 + 1 + 8) + n * 4, n); if (rc_) return rc_; }
+            UNI_ALLOC(m_of, n_lines * 4);
+        }
+        k_uni_lines<<<g_l, 256, 0, ctx->stream>>>(sorted.p, n_lines, K, rank, line_at, len.p, m_of.p, dev.p);
+        if (colored) {   // the DA digits are part of a line's length: place before the text is sized (keys1: the lines' heads, sorted)
+            UNI_ALLOC(slot, n_lines * 4);
+            UNI_ALLOC(owner, n_lines * 4);
+            UNI_ALLOC(claim, n_lines * 4);
+            UNI_ALLOC(left, n_lines * 4);
+            UNI_ALLOC(left_rank, n_lines * 4);
+            UNI_ALLOC(da, n_lines);
+            UNI_ALLOC(km_off, n_lines * 8);
+            UNI_ALLOC(flat_of, n * 4);
+            PF_HIP(hipMemsetAsync(slot.p, 0xFF, n_lines * 4, ctx->stream));
+            PF_HIP(hipMemsetAsync(owner.p, 0xFF, n_lines * 4, ctx->stream));
+            PF_HIP(hipMemsetAsync(claim.p, 0xFF, n_lines * 4, ctx->stream));
+            PF_HIP(hipMemsetAsync(da.p, 0, n_lines, ctx->stream));
+            PF_HIP(hipMemsetAsync(flat_of.p, 0xFF, n * 4, ctx->stream));
+            for (uint32_t round = 1; round <= n_seeds; ++round) {
+                k_uni_place_ask<<<g_l, 256, 0, ctx->stream>>>(keys1.p, n_lines, K, round, slot.p, owner.p, claim.p);
+                k_uni_place_grant<<<g_l, 256, 0, ctx->stream>>>(keys1.p, n_lines, K, round, slot.p, owner.p, claim.p, da.p);
+            }
+            k_uni_place_left<<<g_l, 256, 0, ctx->stream>>>(slot.p, n_lines, left.p);
+            PF_HIP(scan_exclusive_u32(left.p, left_rank.p, n_lines, scratch.p, ctx->stream));
+            uint32_t last_left = 0, last_rank = 0;
+            PF_HIP(hipMemcpyAsync(&last_left, left.p + (n_lines - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
+            PF_HIP(hipMemcpyAsync(&last_rank, left_rank.p + (n_lines - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
+            k_uni_place_end<<<g_l, 256, 0, ctx->stream>>>(n_lines, left.p, left_rank.p, slot.p, da.p, len.p);
+            PF_HIP(scan_exclusive_u32_u64(m_of.p, km_off.p, n_lines, scratch.p, ctx->stream));
+            uint64_t last_km = 0;
+            uint32_t last_m = 0;
+            PF_HIP(hipMemcpyAsync(&last_km, km_off.p + (n_lines - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
+            PF_HIP(hipMemcpyAsync(&last_m, m_of.p + (n_lines - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
+            PF_HIP(hipStreamSynchronize(ctx->stream));
+            overflow = (uint64_t)last_left + last_rank;
+            n_live = last_km + last_m;
+        }
         PF_HIP(scan_exclusive_u32_u64(len.p, off.p, n_lines, scratch.p, ctx->stream));
         uint64_t last_off = 0;
         uint32_t last_len = 0;
@@ -589,7 +683,7 @@ extern "C" int pf_unitig_build(pf_ctx *ctx, const uint64_t *kmers, uint64_t n, u
         text.p = nullptr;   // held by the context from here
         S->bytes = header.size() + body;
         ctx->unitig = S;
-        k_uni_emit<<<g_n, 256, 0, ctx->stream>>>(n_nodes, kmers, K, rank, d_dead, line_at, off.p, len.p, header.size(), S->text);
+        k_uni_emit<<<g_n, 256, 0, ctx->stream>>>(n_nodes, kmers, K, rank, d_dead, line_at, off.p, len.p, header.size(), S->text, da.p, km_off.p, flat_of.p);
     } else {
         DevTmp<char> text;
         UNI_ALLOC(text, header.size());
@@ -614,8 +708,44 @@ extern "C" int pf_unitig_build(pf_ctx *ctx, const uint64_t *kmers, uint64_t n, u
         if (hipEventElapsedTime(&ms, ev.e[s], ev.e[s + 1]) == hipSuccess) st.stage_ms[s] = ms;
     }
     ctx_units(ctx, PF_K_UNITIG, n);
+    if (colored) {   // what K-COLOR reads stays with the text
+        UnitigState *S = unitig_state(ctx);
+        S->colored = true;
+        S->k = K;
+        S->kmers = kmers;
+        S->kmers_own = staged.p;
+        S->n = n;
+        S->n_live = n_live;
+        S->n_lines = n_lines;
+        S->longest_m = st.longest ? st.longest - k + 1 : 0;
+        S->overflow = overflow;
+        S->flat_of = flat_of.p;
+        S->heads = keys1.p;
+        S->m_of = m_of.p;
+        S->km_off = km_off.p;
+        S->slot = slot.p;
+        staged.p = nullptr;
+        flat_of.p = nullptr;
+        keys1.p = nullptr;
+        m_of.p = nullptr;
+        km_off.p = nullptr;
+        slot.p = nullptr;
+    }
     if (stats) *stats = st;
+    if (overflow_out) *overflow_out = overflow;
     return PF_OK;
+}
+
+extern "C" int pf_unitig_build(pf_ctx *ctx, const uint64_t *kmers, uint64_t n, uint32_t k, uint32_t g, int clip_tips, int del_isolated,
+                               pf_unitig_stats *stats) {
+    return unitig_build_impl(ctx, kmers, n, k, g, clip_tips, del_isolated, 0, stats, nullptr);
+}
+
+extern "C" int pf_unitig_build_colored(pf_ctx *ctx, const uint64_t *kmers, uint64_t n, uint32_t k, uint32_t g, int clip_tips, int del_isolated,
+                                       uint32_t n_seeds, pf_unitig_stats *stats, uint64_t *overflow) {
+    if (!ctx) return PF_ERR_ARG;
+    if (!pf_color::seeds_ok(n_seeds)) { pf::CtxErr{ctx} = "pf_unitig_build_colored: n_seeds = " + std::to_string(n_seeds) + ": " + pf_color::seeds_text(); return PF_ERR_ARG; }
+    return unitig_build_impl(ctx, kmers, n, k, g, clip_tips, del_isolated, n_seeds, stats, overflow);
 }
 
 extern "C" int pf_unitig_fetch(pf_ctx *ctx, uint64_t first_byte, uint64_t len, char *host) {

@@ -36,6 +36,9 @@ TRIM_STEP = np.dtype([("kind", "<u4"), ("a", "<u4"), ("b", "<u4")])   # pf_trim_
 TRIM_STATS = np.dtype([(f, "<u8") for f in ("reads", "kept", "dropped", "bases", "bases_kept", "both", "only1", "only2", "neither")])   # pf_trim_stats
 K_UNITIG = K_TRIM + 1      # PF_K_UNITIG ("k_unitig"): everything one pf_unitig_build launches; unit: k-mers
 UNITIG_G_DEFAULT = 0xFFFFFFFF   # PF_UNITIG_G_DEFAULT: Bifrost's default for k
+COLOR_SEEDS = 31                # pf_color::DEFAULT_SEEDS: placement rounds of a colour file
+COLOR_STATS = np.dtype([(f, "<u8") for f in ("colors", "reads", "windows_colored", "windows_unplaced", "windows_bad", "runs", "overflow", "lines",
+                                             "table_slots", "plane_words")] + [(f, "<f8") for f in ("table_ms", "mark_ms", "runs_ms")])   # pf_color_stats
 UNITIG_STAGES = ("index", "adjacency", "simplify", "rank", "cycles", "emit")
 UNITIG_STATS = np.dtype([(f, "<u8") for f in ("distinct", "unitigs", "removed", "unitigs_out", "longest", "bytes", "cycles", "rounds", "cycle_rounds")] +
                         [("stage_ms", "<f8", (len(UNITIG_STAGES),))])   # pf_unitig_stats
@@ -221,6 +224,12 @@ def load_library() -> C.CDLL:
         "pf_unitig_build": (i, [vp, vp, u64, u32, u32, i, i, vp]),
         "pf_unitig_fetch": (i, [vp, u64, u64, vp]),
         "pf_unitig_release": (i, [vp]),
+        "pf_unitig_build_colored": (i, [vp, vp, u64, u32, u32, i, i, u32, vp, C.POINTER(u64)]),
+        "pf_color_begin": (i, [vp, u32]),
+        "pf_color_reads": (i, [vp, u32, vp, u64, vp, vp, u64, vp]),
+        "pf_color_fastq": (i, [vp, u32, vp, u64, i, C.POINTER(u64), vp, C.POINTER(u64)]),
+        "pf_color_finish": (i, [vp, vp]),
+        "pf_color_fetch": (i, [vp, vp, vp, vp, vp, vp]),
         "pf_trim_fastq": (i, [vp, vp, u64, i, vp, u32, u32, vp, C.POINTER(u64), C.POINTER(u64), vp, vp, C.POINTER(u64), vp, C.POINTER(u64)]),
         "pf_trim_fastq_pair": (i, [vp, vp, u64, vp, u64, i, vp, u32, u32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(vp), C.POINTER(vp),
                                    C.POINTER(u64), vp, C.POINTER(u64)]),
@@ -247,7 +256,8 @@ DECLARED_SYMBOLS = ["pf_create", "pf_warmup", "pf_destroy", "pf_last_error", "pf
                     "pf_call_model_filter_multi", "pf_call_model_color_count", "pf_call_model_color_select",
                     "pf_gmm_density", "pf_count_histogram", "pf_mask_reads", "pf_mask_fastq",
                     "pf_count_begin", "pf_count_reads", "pf_count_fastq", "pf_count_finish", "pf_count_abort", "pf_kmc_encode",
-                    "pf_trim_fastq", "pf_trim_fastq_pair", "pf_unitig_build", "pf_unitig_fetch", "pf_unitig_release"]
+                    "pf_trim_fastq", "pf_trim_fastq_pair", "pf_unitig_build", "pf_unitig_fetch", "pf_unitig_release",
+                    "pf_unitig_build_colored", "pf_color_begin", "pf_color_reads", "pf_color_fastq", "pf_color_finish", "pf_color_fetch"]
 
 
 def trim_steps(steps) -> np.ndarray:
@@ -670,6 +680,78 @@ class Device:
         out = {f: int(stats[0][f]) for f in UNITIG_STATS.names if f != "stage_ms"}
         out["stage_ms"] = dict(zip(UNITIG_STAGES, (float(x) for x in stats[0]["stage_ms"])))
         return text[: int(stats[0]["bytes"])].tobytes(), out
+
+    def unitig_build_colored(self, kmers, k: int, clip_tips: bool = False, del_isolated: bool = False, g=None, n_seeds: int = COLOR_SEEDS):
+        """pf_unitig_build_colored: unitig_build on the k-mers of all colours' reads together, every S line with its DA tag; returns (the
+        text of the GFA file, statistics with "overflow").  The graph stays held for color_begin, color_reads / color_fastq and
+        color_finish until unitig_release."""
+        if isinstance(kmers, (list, tuple, np.ndarray)):
+            kmers = np.ascontiguousarray(kmers, dtype=np.uint64)
+        n = int(kmers.shape[0])
+        g = UNITIG_G_DEFAULT if g is None else min(max(int(g), 0), UNITIG_G_DEFAULT - 1)
+        stats = np.zeros(1, dtype=UNITIG_STATS)
+        over = C.c_uint64()
+        self._check(self.L.pf_unitig_build_colored(self.h, _ptr(kmers) if n else None, n, k, g, int(clip_tips), int(del_isolated), int(n_seeds),
+                                                   stats.ctypes.data, C.byref(over)))
+        try:
+            text = np.zeros(max(int(stats[0]["bytes"]), 1), dtype=np.uint8)
+            self._check(self.L.pf_unitig_fetch(self.h, 0, int(stats[0]["bytes"]), _ptr(text)))
+        except Exception:
+            self.L.pf_unitig_release(self.h)
+            raise
+        out = {f: int(stats[0][f]) for f in UNITIG_STATS.names if f != "stage_ms"}
+        out["stage_ms"] = dict(zip(UNITIG_STAGES, (float(x) for x in stats[0]["stage_ms"])))
+        out["overflow"] = over.value
+        return text[: int(stats[0]["bytes"])].tobytes(), out
+
+    def unitig_release(self):
+        self._check(self.L.pf_unitig_release(self.h))
+
+    def color_begin(self, n_colors: int):
+        """K-COLOR (pf_color_begin): the look-up table over the k-mers of the held coloured graph and one cleared bit plane a colour"""
+        self._check(self.L.pf_color_begin(self.h, int(n_colors)))
+
+    def color_reads(self, colour: int, text, read_off, read_len):
+        """pf_color_reads: colours the k-mers of the reads text[read_off[i] : read_off[i] + read_len[i]] (arguments as count_reads takes
+        them) with `colour`; returns this call's statistics."""
+        if isinstance(text, (bytes, bytearray)):
+            text = np.frombuffer(bytes(text), dtype=np.uint8)
+        if isinstance(read_off, (list, tuple, np.ndarray)):
+            read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
+        if isinstance(read_len, (list, tuple, np.ndarray)):
+            read_len = np.ascontiguousarray(read_len, dtype=np.uint32)
+        n, n_reads = int(text.shape[0]), int(read_off.shape[0])
+        stats = np.zeros(1, dtype=COLOR_STATS)
+        self._check(self.L.pf_color_reads(self.h, int(colour), _ptr(text) if n else None, n, _ptr(read_off) if n_reads else None,
+                                          _ptr(read_len) if n_reads else None, n_reads, stats.ctypes.data))
+        return {f: stats[0][f].item() for f in COLOR_STATS.names}
+
+    def color_fastq(self, colour: int, text, final: bool = True):
+        """pf_color_fastq on one chunk of a FASTQ file of `colour`: (bytes_used, this call's statistics).  A format error raises
+        DeviceError with .bad_record = the 0-based record within the chunk."""
+        if isinstance(text, (bytes, bytearray)):
+            text = np.frombuffer(bytes(text), dtype=np.uint8)
+        n = int(text.shape[0])
+        stats = np.zeros(1, dtype=COLOR_STATS)
+        used, bad = C.c_uint64(), C.c_uint64()
+        st = self.L.pf_color_fastq(self.h, int(colour), _ptr(text) if n else None, n, int(final), C.byref(used), stats.ctypes.data, C.byref(bad))
+        if st != PF_OK:
+            e = DeviceError(st, self.L.pf_last_error(self.h).decode())
+            e.bad_record = bad.value
+            raise e
+        return used.value, {f: stats[0][f].item() for f in COLOR_STATS.names}
+
+    def color_finish(self):
+        """pf_color_finish and pf_color_fetch: (statistics of the whole colouring, what leaves the device: per line `heads` u64, `m` u32,
+        `slot` u32, `run_off` u64 of lines + 1 entries, and `runs` u32 [n, 2] = first id, last id)"""
+        stats = np.zeros(1, dtype=COLOR_STATS)
+        self._check(self.L.pf_color_finish(self.h, stats.ctypes.data))
+        nl, nr = int(stats[0]["lines"]), int(stats[0]["runs"])
+        got = dict(heads=np.zeros(nl, dtype=np.uint64), m=np.zeros(nl, dtype=np.uint32), slot=np.zeros(nl, dtype=np.uint32),
+                   run_off=np.zeros(nl + 1, dtype=np.uint64), runs=np.zeros((nr, 2), dtype=np.uint32))
+        self._check(self.L.pf_color_fetch(self.h, _ptr(got["heads"]) if nl else None, _ptr(got["m"]) if nl else None, _ptr(got["slot"]) if nl else None,
+                                          _ptr(got["run_off"]), _ptr(got["runs"]) if nr else None))
+        return {f: stats[0][f].item() for f in COLOR_STATS.names}, got
 
     def kmc_encode(self, kmers, counts, k: int, p: int, counter_bytes: int):
         """pf_kmc_encode, the inverse of kmc_decode: (records u8, lut u64 of 4^p + 1 entries) of sorted distinct k-mers.  kmers / counts:

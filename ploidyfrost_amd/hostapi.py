@@ -43,6 +43,7 @@ DECLARED_SYMBOLS = ["pfh_open", "pfh_close", "pfh_last_error", "pfh_set_output_d
                     "pfh_mask_fastq", "pfh_mask_read", "pfh_mask_index_fastq", "pfh_mask_clause_text",
                     "pfh_count_fastq", "pfh_mask_fastq_counted", "pfh_count_reads_host", "pfh_count_encode_kmc1", "pfh_count_counter_bytes",
                     "pfh_count_lut_prefix_len", "pfh_count_cut_text", "pfh_build_fastq", "pfh_unitig_build_host", "pfh_unitig_no_room_text",
+                    "pfh_build_colored_fastq", "pfh_build_colored_host", "pfh_bfg_colors_bytes", "pfh_color_no_room_text",
                     "pfh_trim_fastq", "pfh_trim_fastq_pair", "pfh_trim_parse_step", "pfh_trim_refusal_text", "pfh_trim_read", "pfh_trim_fastq_chunk"]
 
 
@@ -207,6 +208,13 @@ def load_library() -> C.CDLL:
     L.pfh_unitig_build_host.argtypes = [vp, u64, u32, C.c_int32, C.c_int, C.c_int, vp, u64, C.POINTER(u64), vp]
     L.pfh_unitig_no_room_text.restype = C.c_char_p
     L.pfh_unitig_no_room_text.argtypes = [u64, u64, u64]
+    L.pfh_build_colored_fastq.argtypes = [C.POINTER(C.c_char_p), u32, C.c_char_p, u32, C.c_int32, C.c_int, C.c_int, u32, u64, u64, C.c_int, vp, vp, vp,
+                                          C.POINTER(u64), vp]
+    L.pfh_build_colored_host.argtypes = [C.POINTER(C.c_char_p), vp, u64, u32, C.POINTER(C.c_char_p), u32, C.c_int32, C.c_int, C.c_int, u32, vp, u64,
+                                         C.POINTER(u64), vp, u64, C.POINTER(u64), vp, vp]
+    L.pfh_bfg_colors_bytes.argtypes = [vp, vp, vp, vp, vp, u64, u32, u32, C.POINTER(C.c_char_p), u32, vp, u64, C.POINTER(u64)]
+    L.pfh_color_no_room_text.restype = C.c_char_p
+    L.pfh_color_no_room_text.argtypes = [u64, u64, u64, u64]
     L.pfh_count_cut_text.restype = C.c_char_p
     L.pfh_count_cut_text.argtypes = [C.c_int]
     L.pfh_trim_fastq.argtypes = [C.POINTER(C.c_char_p), u32, C.c_char_p, vp, u32, u32, C.c_char_p, u64, C.c_int, vp]
@@ -689,6 +697,89 @@ def unitig_build_host(kmers, k: int, clip_tips: bool = False, del_isolated: bool
 
 def unitig_no_room_text(need: int, free_bytes: int, n_kmers: int) -> str:
     return load_library().pfh_unitig_no_room_text(int(need), int(free_bytes), int(n_kmers)).decode()
+
+
+COLOR_SEEDS = 31   # pf_color::DEFAULT_SEEDS
+COLOR_STATS = np.dtype([(f, "<u8") for f in ("colors", "reads", "windows_colored", "windows_unplaced", "windows_bad", "runs", "overflow", "lines",
+                                             "table_slots", "plane_words")] + [(f, "<f8") for f in ("table_ms", "mark_ms", "runs_ms")])   # pf_color_stats
+COLOR_STATS_FIELDS = ("colors", "windows_colored", "windows_unplaced", "windows_bad", "runs", "overflow")   # what the host's restatement reports
+COLOR_TIMES = ("stream_s", "finish_s", "graph_s", "color_s", "serialise_s", "write_s")
+
+
+def _names(names):
+    arr = (C.c_char_p * max(len(names), 1))(*[os.fsencode(n) for n in names])
+    return arr
+
+
+def build_colored_graph(inputs, out_prefix: str, k: int = 25, clip_tips: bool = False, del_isolated: bool = False, g=None, n_seeds: int = 0,
+                        chunk_bytes: int = 0, initial_slots: int = 0) -> dict:
+    """`ploidyfrost build-multi` (pfh_build_colored_fastq): the coloured graph of the FASTQ files `inputs`, one colour a file in the
+    order given -- `Bifrost build -c [-i] [-d] -k <k> -r ... -o <out_prefix>` on the device (K-COUNT, K-UNITIG, K-COLOR): <out_prefix>.gfa
+    and <out_prefix>.bfg_colors.  Returns the statistics of the count, the graph and the colouring, "color_bytes" and "times".  A refusal
+    raises RuntimeError by name; nothing is left under either output name."""
+    L = load_library()
+    paths, n = _paths(inputs)
+    counted = np.zeros(len(COUNT_STATS_FIELDS), dtype=np.uint64)
+    stats = np.zeros(1, dtype=UNITIG_STATS)
+    col = np.zeros(1, dtype=COLOR_STATS)
+    nb = C.c_uint64()
+    times = np.zeros(6, dtype=np.float64)
+    rc = L.pfh_build_colored_fastq(paths, n, os.fsencode(out_prefix), int(k), _unitig_g(g), int(clip_tips), int(del_isolated), int(n_seeds),
+                                   int(chunk_bytes), int(initial_slots), 0, counted.ctypes.data, stats.ctypes.data, col.ctypes.data, C.byref(nb),
+                                   times.ctypes.data)
+    if rc:
+        raise RuntimeError(L.pfh_last_error(None).decode())
+    d = {f: int(v) for f, v in zip(COUNT_STATS_FIELDS[:4], counted)}
+    d.update({f: int(stats[0][f]) for f in UNITIG_STATS.names if f != "stage_ms"})
+    d["stage_ms"] = [float(x) for x in stats[0]["stage_ms"]]
+    d.update({f: col[0][f].item() for f in COLOR_STATS.names if f != "reads"})
+    d["color_bytes"] = nb.value
+    d["times"] = dict(zip(COLOR_TIMES, (float(x) for x in times)))
+    return d
+
+
+def build_colored_host(reads_per_colour, k: int, clip_tips: bool = False, del_isolated: bool = False, g=None, n_seeds: int = COLOR_SEEDS, names=None):
+    """(gfa bytes, bfg_colors bytes, statistics): the rule of `build-multi` on the host (pfh_build_colored_host; no device) from the reads
+    of every colour; names: the colours' names (default "c0", "c1", ...)"""
+    L = load_library()
+    flat = [(r if isinstance(r, bytes) else r.encode()) for reads in reads_per_colour for r in reads]
+    colour_of = np.array([c for c, reads in enumerate(reads_per_colour) for _ in reads], dtype=np.uint32)
+    n_colors = len(reads_per_colour)
+    names = ["c%d" % c for c in range(n_colors)] if names is None else list(names)
+    assert len(names) == n_colors
+    arr = (C.c_char_p * max(len(flat), 1))(*flat)
+    gs, cs, gst, cst = C.c_uint64(), C.c_uint64(), np.zeros(6, dtype=np.uint64), np.zeros(6, dtype=np.uint64)
+    args = (arr, colour_of.ctypes.data if len(flat) else None, len(flat), n_colors, _names(names), int(k), _unitig_g(g), int(clip_tips), int(del_isolated),
+            int(n_seeds))
+    rc = L.pfh_build_colored_host(*args, None, 0, C.byref(gs), None, 0, C.byref(cs), None, None)
+    if rc:
+        raise ValueError("build_colored_host: %s" % {1: "k goes from 3 to 31", 2: "g goes from 1 to k - 2", 3: "n_seeds goes from 1 to 255"}.get(
+            rc, "more than 1024 colours, or colours times k-mers of a unitig reach 2^32"))
+    gfa, col = np.zeros(max(gs.value, 1), dtype=np.uint8), np.zeros(max(cs.value, 1), dtype=np.uint8)
+    L.pfh_build_colored_host(*args, gfa.ctypes.data, len(gfa), C.byref(gs), col.ctypes.data, len(col), C.byref(cs), gst.ctypes.data, cst.ctypes.data)
+    st = {f: int(v) for f, v in zip(UNITIG_STATS_FIELDS, gst)}
+    st.update({f: int(v) for f, v in zip(COLOR_STATS_FIELDS, cst)})
+    return gfa[: gs.value].tobytes(), col[: cs.value].tobytes(), st
+
+
+def bfg_colors_bytes(fetched: dict, k: int, names, n_seeds: int = COLOR_SEEDS) -> bytes:
+    """the bytes of the colour file (pfh_bfg_colors_bytes, csrc/host/pf_bfg_write.hpp) from what hipapi.Device.color_finish fetched"""
+    L = load_library()
+    heads, m, slot = (np.ascontiguousarray(fetched[f], dtype=t) for f, t in (("heads", np.uint64), ("m", np.uint32), ("slot", np.uint32)))
+    run_off, runs = np.ascontiguousarray(fetched["run_off"], dtype=np.uint64), np.ascontiguousarray(fetched["runs"], dtype=np.uint32)
+    n = len(heads)
+    size = C.c_uint64()
+    args = (heads.ctypes.data if n else None, m.ctypes.data if n else None, slot.ctypes.data if n else None, run_off.ctypes.data,
+            runs.ctypes.data if len(runs) else None, n, int(k), int(n_seeds), _names(list(names)), len(names))
+    if L.pfh_bfg_colors_bytes(*args, None, 0, C.byref(size)):
+        raise RuntimeError(L.pfh_last_error(None).decode())
+    out = np.zeros(max(size.value, 1), dtype=np.uint8)
+    L.pfh_bfg_colors_bytes(*args, out.ctypes.data, len(out), C.byref(size))
+    return out[: size.value].tobytes()
+
+
+def color_no_room_text(need: int, free_bytes: int, n_colors: int, n_kmers: int) -> str:
+    return load_library().pfh_color_no_room_text(int(need), int(free_bytes), int(n_colors), int(n_kmers)).decode()
 
 
 def count_counter_bytes(cx: int, cs: int) -> int:
