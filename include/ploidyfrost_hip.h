@@ -68,6 +68,7 @@ enum pf_kernel {
     PF_K_COUNT, /* K-COUNT: everything one pf_count_reads / pf_count_fastq launches (index, classes, insert, growth), timed as one launch; unit: windows */
     PF_K_TRIM, /* K-TRIM: everything one pf_trim_fastq / pf_trim_fastq_pair launches (index, intervals, sizes, scan, copy), timed as one launch; unit: records */
     PF_K_UNITIG, /* K-UNITIG: everything one pf_unitig_build launches (index, adjacency, link, simplify, rank, cycles, emit), timed as one launch; unit: k-mers */
+    PF_K_MASKCOUNT, /* K-MASKCOUNT: everything one pf_maskcount_reads / pf_maskcount_fastq launches (index, classes, flag, insert, growth), timed as one launch; unit: windows */
     PF_K_COUNT_
 };
 int pf_enable_timing(pf_ctx *, int on);
@@ -219,6 +220,29 @@ int pf_count_fastq(pf_ctx *, const char *text, uint64_t n_bytes, int final, uint
  * finish fields.  ci < 1, ci > cx, cs < 1 or a value above 2^32 - 1: PF_ERR_ARG by name, and the count stays open. */
 int pf_count_finish(pf_ctx *, uint64_t ci, uint64_t cx, uint64_t cs, uint64_t **kmers_dev, uint32_t **counts_dev, uint64_t *n, pf_count_stats *stats);
 int pf_count_abort(pf_ctx *);
+/* K-MASKCOUNT: `mask` followed by the count of `build` in one pass and without the masked text -- every window of the reads that
+ * would still hold k bytes of ACGTacgt after K-MASK had painted its Ns is counted into the open count.  The rule
+ * (csrc/pf_run_rule.hpp): with bad(q) as K-MASK defines it against the resident table (window q's counter outside [low, up]) and
+ * valid(p) as K-COUNT does (all k bytes are bases), window p counts when valid(p) and no q in [p - k + 1, p + k - 1] is bad; the key
+ * is the canonical form.  Both calls need a resident count table (pf_upload_counts) and an open count (pf_count_begin, both strands)
+ * whose k equals the table's: each missing piece is PF_ERR_ARG by name.  They add to the open count as pf_count_reads /
+ * pf_count_fastq do -- the same growth and the same refusals -- and pf_count_finish closes it: the same arrays whatever the chunking,
+ * equal to those of pf_mask_* followed by pf_count_* on the masked text. */
+typedef struct pf_maskcount_stats {
+    uint64_t reads;          /* records seen */
+    uint64_t bases;          /* sequence bytes */
+    uint64_t kmers;          /* windows */
+    uint64_t kmers_invalid;  /* windows holding a byte outside ACGTacgt */
+    uint64_t kmers_bad;      /* bad windows (pf_mask_stats::kmers_bad) */
+    uint64_t kmers_kept;     /* windows counted */
+} pf_maskcount_stats;
+/* reads given explicitly, as pf_mask_reads takes them.  text, read_off, read_len: [host|dev] */
+int pf_maskcount_reads(pf_ctx *, const char *text, uint64_t n_bytes, const uint64_t *read_off, const uint32_t *read_len, uint64_t n_reads,
+                       uint32_t low, uint32_t up, pf_maskcount_stats *stats);
+/* one chunk of a FASTQ file: the chunk contract and the format clauses of pf_mask_fastq; nothing is counted from a refused chunk.
+ * text: [host|dev] */
+int pf_maskcount_fastq(pf_ctx *, const char *text, uint64_t n_bytes, int final, uint32_t low, uint32_t up, uint64_t *bytes_used,
+                       pf_maskcount_stats *stats, uint64_t *bad_record);
 /* the inverse of K-KMC: sorted distinct k-mers and their counts as the record area of a KMC1 <db>.kmc_suf (n records of
  * (k - lut_prefix_len) / 4 suffix bytes, most significant first, + counter_bytes counter bytes, least significant first) and the
  * prefix table of its <db>.kmc_pre (4^lut_prefix_len entries plus lut[4^lut_prefix_len] = n).  Either output may be NULL (a block of
@@ -254,6 +278,9 @@ typedef struct pf_unitig_stats {
 int pf_unitig_build(pf_ctx *, const uint64_t *kmers, uint64_t n, uint32_t k, uint32_t g, int clip_tips, int del_isolated, pf_unitig_stats *stats);
 /* bytes [first_byte, first_byte + len) of the text to the host; outside the text, or without a build: PF_ERR_ARG */
 int pf_unitig_fetch(pf_ctx *, uint64_t first_byte, uint64_t len, char *host);
+/* the resident text itself, for a reader on the same device (pf_gfa_parse takes the bytes behind the header line as its body):
+ * *text_dev [dev], *n_bytes as pf_unitig_stats::bytes; valid until pf_unitig_release.  Without a build: PF_ERR_ARG by name. */
+int pf_unitig_text(pf_ctx *, const char **text_dev, uint64_t *n_bytes);
 int pf_unitig_release(pf_ctx *);
 /* K-COLOR: the coloured graph of several files of reads -- what `Bifrost build -c -r s0.fq -r s1.fq ...` writes beside the graph.  The
  * rule: csrc/pf_color_rule.hpp.  pf_unitig_build_colored is pf_unitig_build on the k-mers of all files together (same graph, same line

@@ -145,6 +145,42 @@ int pfh_build_fastq(const char *const *inputs, uint32_t n_inputs, const char *ou
 int pfh_unitig_build_host(const uint64_t *kmers, uint64_t n, uint32_t k, int32_t g, int clip_tips, int del_isolated, char *text_out, uint64_t cap,
                           uint64_t *text_bytes, uint64_t stats_out[6]);
 const char *pfh_unitig_no_room_text(uint64_t need, uint64_t free_bytes, uint64_t n_kmers);
+/* ---- reads to ploidy estimate in one process (`ploidyfrost run`; K-MASKCOUNT, pf_maskcount_* in ploidyfrost_hip.h) ----
+ * Steps 2 to 5 of the reference's workflow for one sample on one device context: the inputs counted (pfh_count_fastq's count with
+ * k / ci / cx / cs), L = max(10, cutoffL) and U = cutoffU(quantile) of the counted k-mers, the count table, the inputs streamed a
+ * second time through pf_maskcount_fastq (low = L, up = mask_up), the k-mers of the masked reads compacted into unitigs
+ * (pfh_build_fastq's graph), and the single-sample calling run over that graph and that table with L and U; the twelve
+ * PloidyFrost_output/<out_prefix>_*.txt files, with model_source the model's result as well.  No masked reads, no database and no
+ * graph file lie in between; db_out / gfa_out (may be NULL) write the database of `mask --db-out` and the file of `build`.  L is
+ * printed on stdout.  The rule of the second pass: csrc/pf_run_rule.hpp.  Refused by name before a device context exists: no
+ * input, no output, k outside 5 .. 31, g outside 1 .. k - 2, ci < 1, ci > cx, cs < 1, FASTA, gzip, an output that is an input.
+ * 0 = ok, else pfh_last_error(NULL).
+ * pfh_count_masked_host: the host's plain restatement of the second pass, no device involved -- counters[p] is the counter of the
+ * window that starts at byte p of the text (read at window starts only); every window that survives the masking with [low, up] is
+ * counted in canonical form; at most cap sorted (k-mer, count) pairs are written, *n is their number; stats_out = {reads, bases,
+ * kmers, kmers_invalid, kmers_bad, kmers_kept}.  1: bad k. */
+typedef struct pfh_run_options {
+    uint32_t k;                      /* 25 */
+    uint64_t ci, cx, cs;             /* 1, 1000000000, 10000 */
+    int32_t g;                       /* PFH_UNITIG_G_DEFAULT */
+    int clip_tips, del_isolated;     /* 1, 1 */
+    uint64_t chunk_bytes, initial_slots;
+    double quantile;                 /* 0.998 */
+    uint32_t mask_up;                /* 0xFFFFFFFF: no upper bound on the masking */
+    uint32_t complex_size;           /* 8 */
+    double match, mismatch, gap;     /* 2, -1, -3 */
+    uint32_t threads;                /* 1 */
+    int model_source;                /* -1: no model; PF_MODEL_COV / PF_MODEL_FRE */
+    int model_only;
+    const char *db_out, *gfa_out;    /* may be NULL */
+} pfh_run_options;
+typedef struct pfh_run_stats {
+    uint64_t reads, bases, kmers, bad, distinct, lower, upper, windows_bad, windows_kept, distinct_kept, unitigs, removed, unitigs_out, longest;
+} pfh_run_stats;
+void pfh_run_defaults(pfh_run_options *opt);
+int pfh_run_fastq(const char *const *inputs, uint32_t n_inputs, const char *out_prefix, const pfh_run_options *opt, int device, pfh_run_stats *stats);
+int pfh_count_masked_host(const char *text, const uint64_t *off, const uint32_t *len, uint64_t n_reads, uint32_t k, const uint32_t *counters,
+                          uint32_t low, uint32_t up, uint64_t *kmers_out, uint32_t *counts_out, uint64_t cap, uint64_t *n, uint64_t stats_out[6]);
 /* ---- the coloured graph built from several files of reads (K-COLOR, pf_color_* in ploidyfrost_hip.h) ----
  * `Bifrost build -c -k 25 [-i] [-d] -r s0.fq -r s1.fq ... -o sample` in one call: pfh_build_fastq's graph of all inputs together with a
  * DA tag on every S line, and <out_prefix>.bfg_colors (format version 2; csrc/host/pf_bfg_write.hpp), every input one colour in the

@@ -105,6 +105,21 @@ void CountsLoader::start(int device, const std::string &kmc_prefix) {
     });
 }
 
+void CountsLoader::adopt(pf_ctx *c, int k_, bool both_strands_, std::vector<uint64_t> rows_, uint64_t rows_min_count_) {
+    ctx = c;
+    status = PF_OK;
+    k = k_;
+    both_strands = both_strands_;
+    want_rows = !rows_.empty();
+    rows = std::move(rows_);
+    rows_min_count = rows_min_count_;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        ctx_known_ = true;
+    }
+    cv_.notify_all();
+}
+
 int CDBG::init_device(int device, pf_ctx *adopt, bool colored) {
     LoadTrace trace;
     int st = PF_OK;

@@ -62,6 +62,10 @@ struct PhaseTimes {
 struct CountsLoader {
     ~CountsLoader();
     void start(int device, const std::string &kmc_prefix);
+    // Instead of start(): a context that holds the count table already (`ploidyfrost run`: pf_upload_counts of the counters it has
+    // just counted), with the histogram rows of those counters (pfh::counted_rows) for the thresholds.  No thread, no file; the
+    // loader owns the context from here, as after start().
+    void adopt(pf_ctx *c, int k_, bool both_strands_, std::vector<uint64_t> rows_, uint64_t rows_min_count_);
     // valid after wait()
     pf_ctx *ctx = nullptr;
     int status = 0;

@@ -11,6 +11,8 @@
 #include "pf_mask_host.hpp"
 #include "pf_count_host.hpp"
 #include "pf_build_host.hpp"
+#include "pf_run_host.hpp"
+#include "../pf_run_rule.hpp"
 #include "pf_bfg_write.hpp"
 #include "../pf_mask_rule.hpp"
 #include "../pf_trim_rule.hpp"
@@ -477,6 +479,79 @@ int pfh_build_fastq(const char *const *inputs, uint32_t n_inputs, const char *ou
         g_open_err = std::string("ploidyfrost host layer: ") + e.what();
         return 1;
     }
+}
+// ---- `run` (K-MASKCOUNT) ----
+void pfh_run_defaults(pfh_run_options *o) {
+    if (!o) return;
+    const pfh::RunOptions d;
+    *o = pfh_run_options{};
+    o->k = d.k;
+    o->ci = d.ci; o->cx = d.cx; o->cs = d.cs;
+    o->g = d.g;
+    o->clip_tips = d.clip_tips; o->del_isolated = d.del_isolated;
+    o->quantile = d.quantile;
+    o->mask_up = d.mask_up;
+    o->complex_size = (uint32_t)d.complex_size;
+    o->match = d.match; o->mismatch = d.mismatch; o->gap = d.gap;
+    o->threads = 1;
+    o->model_source = -1;
+}
+int pfh_run_fastq(const char *const *inputs, uint32_t n_inputs, const char *out_prefix, const pfh_run_options *o, int device, pfh_run_stats *stats) {
+    if (!out_prefix || !o || (n_inputs && !inputs)) { g_open_err = "pfh_run_fastq: inputs, output prefix and options are needed"; return 1; }
+    try {
+        std::vector<std::string> in;
+        for (uint32_t i = 0; i < n_inputs; ++i) in.push_back(inputs[i] ? inputs[i] : "");
+        pfh::RunOptions opt;
+        opt.k = o->k;
+        opt.ci = o->ci; opt.cx = o->cx; opt.cs = o->cs;
+        opt.g = o->g;
+        opt.clip_tips = o->clip_tips != 0; opt.del_isolated = o->del_isolated != 0;
+        opt.chunk_bytes = o->chunk_bytes; opt.initial_slots = o->initial_slots;
+        opt.quantile = o->quantile;
+        opt.mask_up = o->mask_up;
+        opt.complex_size = o->complex_size;
+        opt.match = o->match; opt.mismatch = o->mismatch; opt.gap = o->gap;
+        opt.call.threads = o->threads ? o->threads : 1;
+        if (o->model_source >= 0) {
+            opt.call.model.on = true;
+            opt.call.model.only = o->model_only != 0;
+            opt.call.model.source = o->model_source;
+        }
+        if (o->db_out) opt.db_out = o->db_out;
+        if (o->gfa_out) opt.gfa_out = o->gfa_out;
+        pfh::RunStats st;
+        const int rc = pfh::run_fastq(in, out_prefix, opt, device, st, nullptr, g_open_err);
+        if (stats)
+            *stats = pfh_run_stats{st.counted.reads, st.counted.bases, st.counted.kmers, st.counted.kmers_bad, st.counted.unique, st.lower, st.upper,
+                                   st.masked.kmers_bad, st.masked.kmers_kept, st.distinct_kept, st.graph.unitigs, st.graph.removed, st.graph.unitigs_out,
+                                   st.graph.longest};
+        return rc;
+    } catch (const std::exception &e) {
+        g_open_err = std::string("ploidyfrost host layer: ") + e.what();
+        return 1;
+    }
+}
+int pfh_count_masked_host(const char *text, const uint64_t *off, const uint32_t *len, uint64_t n_reads, uint32_t k, const uint32_t *counters,
+                          uint32_t low, uint32_t up, uint64_t *kmers_out, uint32_t *counts_out, uint64_t cap, uint64_t *n, uint64_t stats_out[6]) {
+    if (n) *n = 0;
+    if (!pf_count::k_ok(k)) return 1;
+    pf_count::Table table;
+    pf_run::Stats st;
+    pf_run::count_masked_host(text, off, len, n_reads, (int)k, counters, low, up, table, st);
+    uint64_t i = 0;
+    for (const auto &kv : table) {
+        if (i < cap) {
+            if (kmers_out) kmers_out[i] = kv.first;
+            if (counts_out) counts_out[i] = (uint32_t)std::min<uint64_t>(kv.second, pf_count::COUNTER_MAX);
+        }
+        ++i;
+    }
+    if (n) *n = i;
+    if (stats_out) {
+        const uint64_t s[6] = {st.reads, st.bases, st.kmers, st.kmers_invalid, st.kmers_bad, st.kmers_kept};
+        memcpy(stats_out, s, sizeof s);
+    }
+    return 0;
 }
 int pfh_unitig_build_host(const uint64_t *kmers, uint64_t n, uint32_t k, int32_t g, int clip_tips, int del_isolated, char *text_out, uint64_t cap,
                           uint64_t *text_bytes, uint64_t stats_out[6]) {

@@ -230,7 +230,8 @@ bool UnitigSet::load_gfa(const std::string &path, std::string &err, bool defer_n
 // ---- device ingest ----------------------------------------------------------------------------------------------------
 struct GfaSource {
     Mapped file;
-    const char *body = nullptr;
+    const char *body = nullptr;       // host: behind the header line (the mapped file, or the caller's copy of a text in memory)
+    const char *dev_body = nullptr;   // open_gfa_memory: the same bytes where they lie on the device already
     uint64_t body_n = 0;
     int version = 1;
     std::vector<uint64_t> file_off;   // per unitig: its sequence field inside body
@@ -268,6 +269,19 @@ bool UnitigSet::open_gfa(const std::string &path, std::string &err) {
     return true;
 }
 
+bool UnitigSet::open_gfa_memory(const char *host_text, uint64_t n, const char *device_text, std::string &err) {
+    auto s = std::make_shared<GfaSource>();
+    const char *body = nullptr;
+    if (!host_text || !device_text) { err = "no GFA text"; return false; }
+    if (!parse_gfa_header(host_text, host_text + n, s->version, k, g, body, err)) return false;
+    s->body = body;
+    s->dev_body = device_text + (body - host_text);
+    s->body_n = (uint64_t)(host_text + n - body);
+    src_ = s;
+    ingested_ = false;
+    return true;
+}
+
 uint64_t UnitigSet::estimated_unitigs() const {
     if (parsed_on_ && parse_status_ == 0) return parsed_n_;   // (the device has parsed the file already: the count itself)
     return src_ ? src_->body_n / 75 + 1024 : n();
@@ -276,7 +290,7 @@ uint64_t UnitigSet::estimated_unitigs() const {
 int UnitigSet::parse_on_device(pf_ctx *ctx) {
     LoadTrace trace;
     parsed_on_ = ctx;
-    parse_status_ = pf_gfa_parse(ctx, src_->body, src_->body_n, src_->version, k, &parsed_n_, &parsed_short_);
+    parse_status_ = pf_gfa_parse(ctx, src_->dev_body ? src_->dev_body : src_->body, src_->body_n, src_->version, k, &parsed_n_, &parsed_short_);
     trace.mark("gfa: parse + 2-bit pack on the device");
     return parse_status_;
 }
@@ -288,6 +302,10 @@ int UnitigSet::ingest_on_device(pf_ctx *ctx, std::string &err) {
     uint32_t N = parsed_n_, ns = parsed_short_;
     int st = pf_gfa_upload(ctx);
     if (st != PF_OK) { err = pf_last_error(ctx); return st; }
+    if (src_->dev_body) {   // the text of pf_unitig_build has been packed: its device copy is dead (the host copy serves ensure_text)
+        (void)pf_unitig_release(ctx);
+        src_->dev_body = nullptr;
+    }
     trace.mark("gfa: packed graph adopted by the context");
     n_short = ns;
     len_bp.resize(N);

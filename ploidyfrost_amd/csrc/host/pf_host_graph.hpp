@@ -63,6 +63,12 @@ struct UnitigSet {
     // seq(), append_mapped(), words) is made from the mapped file only when somebody asks: ensure_text().  Same unitig order,
     // same error messages as load_gfa(defer_numbering = true).
     bool open_gfa(const std::string &path, std::string &err);
+    // The same for a GFA text that lies in memory and not in a file (`ploidyfrost run`: the text pf_unitig_build left on the device):
+    // host_text[0, n) is the whole text with its header line, device_text the same bytes on the device (pf_unitig_text).  The header
+    // line is read from the host copy; parse_on_device hands pf_gfa_parse the device body; ensure_text and copy_seq read the host
+    // copy, which stays the caller's and outlives the set.  ingest_on_device calls pf_unitig_release once pf_gfa_upload has adopted
+    // the packed graph.  Everything behind this seam is open_gfa's code: same unitig order, numbering and error messages.
+    bool open_gfa_memory(const char *host_text, uint64_t n, const char *device_text, std::string &err);
     bool ingest_pending() const { return src_ != nullptr && !ingested_; }
     uint64_t estimated_unitigs() const;   // before the ingest: from the size of the file
     // parse_on_device: the parse + pack half alone (pf_gfa_parse: may run while another thread feeds the count table to the same

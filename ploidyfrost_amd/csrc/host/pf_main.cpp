@@ -35,6 +35,7 @@
 #include "pf_count_host.hpp"
 #include "pf_build_host.hpp"
 #include "pf_mask_host.hpp"
+#include "pf_run_host.hpp"
 #include "pf_trim_host.hpp"
 #include "../pf_trim_rule.hpp"
 #include "pf_filter.hpp"
@@ -105,6 +106,11 @@ void PrintUsage() {
          << "Usage: PloidyFrost build-multi -k 25 [-i] [-d] -r <s0.fq> -r <s1.fq> [-r ...] -o <sample> [-g G] [-t N] [--chunk-bytes N] [--initial-slots N] [-v]" << endl
          << "                  (`Bifrost build -c -r ... -r ...` on the device: <sample>.gfa of all files together, every S line with its DA tag, and" << endl
          << "                  <sample>.bfg_colors, one colour per -r in the order given; what the calling run takes with -g and -f)" << endl << endl
+         << "Usage: PloidyFrost run [-k 25 -ci 1 -cs 10000 -cx N] -i <trimmed.fq> [-i <more.fq> ...] -o <sample> [-q Q] [-u U] [--keep-tips] [--keep-isolated] [-g G]" << endl
+         << "                  [-z -M -D -G -t --ref-threads] [--model cov|fre ... --model-only --filter \"OPTS\" --density ...] [--db-out <KMCDatabase>] [--gfa-out <sample>]" << endl
+         << "                  [--chunk-bytes N] [--initial-slots N] [-v]" << endl
+         << "                  (reads to ploidy estimate in one process: `mask -k ... --auto-cutoffs`, `build -i -d` and the calling run with --auto-cutoffs on" << endl
+         << "                  one device context, no masked reads, database or graph file in between; L is printed on stdout)" << endl << endl
          << "Usage: PloidyFrost model ...          (GMM ploidy inference from the coverage / frequency files; `PloidyFrost model` prints its options)" << endl
          << "Usage: PloidyFrost density -f <column file> -o <outfile_prefix> [-n points] [-a adjust]   (kernel density of a column of numbers)" << endl
          << "Usage: PloidyFrost filter ...         (the row predicates of script/Filter.R over <prefix>_*cov.txt; -h prints its options)" << endl
@@ -154,7 +160,7 @@ vector<uint64_t> database_rows(const string &db, uint64_t *min_count = nullptr) 
 struct Options {
     string graphfile, colorfile, outprefix = "output", db, coveragefile, hist;
     size_t nb_threads = 1, complex_size = 8, ref_threads = 1, gpus = 1;
-    bool verbose = false, info = false, detach_teardown = false;
+    bool verbose = false, info = false, detach_teardown = false, gpus_seen = false;
     int coverage_lower = 10, coverage_upper = 1000, k = 25;
     vector<pair<int, int>> coverage_vec;
     double match = 2, mismatch = -1, gap = -3, frequency = 0.998;
@@ -853,8 +859,138 @@ int trim_main(int argc, char **argv) {
     return 0;
 }
 
+bool take_long_options(int &argc, char **argv, int first, Options &opt, DensityCli &dc);
+bool model_setup(const Options &opt, DensityCli &dc, pfh::CDBG::ModelOptions &model, pf_filter_opts &filter, pf_filter_multi_opts &multi);
+int calling_main(Options &opt, DensityCli &dc);
+
+// `run`: steps 2 to 5 of the reference's workflow for one sample (`kmc`, `kmc_tools filter`, `Bifrost build`, `PloidyFrost`) in one
+// process and on one device context; the letters are those of `count` / `mask` (-k -ci -cs -cx -i -u), of `build` (-g) and of the
+// calling run (-z -M -D -G -t -q --model ...)
+int run_main(int argc, char **argv) {
+    const char *usage = "Usage:PloidyFrost run [-k 25] [-ci 1] [-cs 10000] [-cx N] -i trimmed.fq [-i more.fq ...] -o sample [-q Q] [-u U] [--keep-tips] [--keep-isolated] [-g G]\n"
+                        "                 [-z Z -M m -D d -G g -t T --ref-threads N] [--model cov|fre ... --model-only --filter \"OPTS\" --density ...]\n"
+                        "                 [--db-out <KMCDatabase>] [--gfa-out <sample>] [--chunk-bytes N] [--initial-slots N] [-v]";
+    auto refuse = [&](const string &why) { cerr << "Error: run: " << why << endl << usage << endl; return 1; };
+    Options lopt;   // the long options of the calling run
+    DensityCli dc;
+    if (!take_long_options(argc, argv, 2, lopt, dc)) return 1;
+    pfh::RunOptions opt;
+    CountArgs c;
+    c.opt.ci = opt.ci;
+    c.opt.cx = opt.cx;
+    c.opt.cs = opt.cs;
+    string out;
+    vector<string> inputs;
+    bool verbose = false;
+    auto number = [&](const string &o, const char *text, uint64_t &v, bool positive) {
+        char *end = nullptr;
+        errno = 0;
+        v = strtoull(text, &end, 10);
+        if (!errno && isdigit((unsigned char)text[0]) && !*end && (v > 0 || !positive)) return true;
+        refuse(o + " takes a " + (positive ? "positive " : "") + "number, not '" + text + "'");
+        return false;
+    };
+    auto real = [&](const string &o, const char *text, double &v) {
+        char *end = nullptr;
+        v = strtod(text, &end);
+        if (end != text && !*end && std::isfinite(v)) return true;
+        refuse(o + " takes a number, not '" + text + "'");
+        return false;
+    };
+    static const struct { const char *name, *why; } not_here[] = {
+        {"-f", "-f is not built into run: the coloured workflow goes in steps (`build-multi`, then the calling run with -f)"},
+        {"-C", "-C does not go with run: the thresholds come from the counted k-mers (one sample, no coverage file)"},
+        {"-d", "-d does not go with run: the database is counted from the reads (--db-out writes it; isolated unitigs are removed unless --keep-isolated)"},
+        {"-h", "-h does not go with run: the thresholds come from the counted k-mers, not from a histogram file"},
+        {"-l", "-l does not go with run: the lower threshold is derived from the counted k-mers (as --auto-cutoffs derives it)"},
+        {"-b", "-b does not go with run: the graph is built from both strands"},
+        {"--filtered-out", "--filtered-out is not built: the masked reads are never made (`mask` writes them)"},
+        {"--detach-teardown", "--detach-teardown is not built into run"},
+    };
+    if (lopt.gpus_seen) return refuse("--gpus is not built into run: one sample, one GPU");
+    if (lopt.each_color || lopt.multi_seen) return refuse("--filter-multi / --model-each-color belong to the coloured path: run has --filter");
+    if (lopt.detach_teardown) return refuse(not_here[7].why);
+    for (int i = 2; i < argc; ++i) {
+        const string a = argv[i];
+        for (const auto &nh : not_here)
+            if (a == nh.name) return refuse(nh.why);
+        {
+            string why;
+            const int taken = take_count_option(argc, argv, i, c, why);
+            if (taken < 0) return refuse(why);
+            if (taken) continue;
+        }
+        if (a == "-v") { verbose = true; continue; }
+        if (a == "--keep-tips") { opt.clip_tips = false; continue; }
+        if (a == "--keep-isolated") { opt.del_isolated = false; continue; }
+        const bool takes_value = a == "-i" || a == "-o" || a == "-q" || a == "-u" || a == "-g" || a == "-z" || a == "-M" || a == "-D" || a == "-G" || a == "-t" ||
+                                 a == "--db-out" || a == "--gfa-out" || a == "--chunk-bytes" || a == "--initial-slots";
+        if (!takes_value) return refuse("unknown option " + a);
+        if (i + 1 >= argc) return refuse(a + " needs a value");
+        const char *val = argv[++i];
+        uint64_t v = 0;
+        if (a == "-i") inputs.push_back(val);
+        else if (a == "-o") out = val;
+        else if (a == "--db-out") opt.db_out = val;
+        else if (a == "--gfa-out") opt.gfa_out = val;
+        else if (a == "-q") { if (!real(a, val, opt.quantile)) return 1; }
+        else if (a == "-M") { if (!real(a, val, opt.match)) return 1; }
+        else if (a == "-D") { if (!real(a, val, opt.mismatch)) return 1; }
+        else if (a == "-G") { if (!real(a, val, opt.gap)) return 1; }
+        else if (a == "-u") { if (!number(a, val, v, false)) return 1; if (v > 0xFFFFFFFFull) return refuse("-u takes a number from 0 to 4294967295, not '" + string(val) + "'"); opt.mask_up = (uint32_t)v; }
+        else if (!number(a, val, v, true)) return 1;
+        else if (a == "-g") opt.g = (int)std::min<uint64_t>(v, 0x7FFFFFFFull);
+        else if (a == "-z") opt.complex_size = (size_t)v;
+        else if (a == "-t") opt.call.threads = (size_t)v;
+        else if (a == "--chunk-bytes") opt.chunk_bytes = v;
+        else if (a == "--initial-slots") opt.initial_slots = v;
+    }
+    // refused by name, before anything is read or written and before a device context exists
+    if (inputs.empty()) return refuse("-i <reads.fq> is missing");
+    if (out.empty()) return refuse("-o <sample> is missing");
+    opt.k = c.opt.k;
+    opt.ci = c.opt.ci;
+    opt.cx = c.opt.cx;
+    opt.cs = c.opt.cs;
+    { const string why = pfh::run_options_refusal(opt); if (!why.empty()) return refuse(why); }
+    if (opt.quantile < 0 || opt.quantile > 1) return refuse("-q: frequency cutoff value should be between 0 and 1");
+    if (opt.complex_size < 4) return refuse("-z: Maximum number of unitigs in superbubble is at least 4 !");
+    if (opt.mismatch > opt.match) return refuse("-D: Mismatch penalty should be smaller than match score !");
+    if (opt.gap > opt.match) return refuse("-G: Gap penalty should be smaller than match score !");
+    if (opt.call.threads > std::thread::hardware_concurrency()) return refuse("-t: Number of threads cannot be greater than " + to_string(std::thread::hardware_concurrency()));
+    pf_filter_opts filter = {};
+    pf_filter_multi_opts multi = {};
+    if (!model_setup(lopt, dc, opt.call.model, filter, multi)) return 1;
+    opt.call.ref_threads = lopt.ref_threads;
+    opt.call.verbose = verbose;
+    opt.call.filter = lopt.filter_seen ? &filter : nullptr;
+    opt.call.density_points = dc.on ? dc.points : 0;
+    opt.call.density_adjust = dc.adjust;
+    pfh::RunStats st;
+    pfh::RunTimes tm;
+    string err;
+    if (pfh::run_fastq(inputs, out, opt, 0, st, &tm, err)) {
+        cout.flush();
+        fflush(nullptr);
+        // (what the chain's last command says on stdout is said there; its own refusals carry their "Error:" already)
+        if (err.rfind("CompactedDBG::read()", 0) == 0) cout << err << endl;
+        else if (err.rfind("run: ", 0) == 0) cerr << "Error: " << err << endl;
+        else cerr << err << endl;
+        return EXIT_FAILURE;
+    }
+    cerr << "run: reads " << st.counted.reads << " bases " << st.counted.bases << " kmers " << st.counted.kmers << " bad " << st.counted.kmers_bad << " distinct "
+         << st.counted.unique << " lower " << st.lower << " upper " << st.upper << " windows_bad " << st.masked.kmers_bad << " windows_kept " << st.masked.kmers_kept
+         << " distinct_kept " << st.distinct_kept << " unitigs " << st.graph.unitigs << " removed " << st.graph.removed << " unitigs_out " << st.graph.unitigs_out
+         << " longest " << st.graph.longest << endl;
+    if (verbose)
+        cerr << "run: count " << tm.count_s << "s finish " << tm.finish_s << "s table " << tm.table_s << "s db-out " << tm.db_out_s << "s recount " << tm.recount_s
+             << "s refinish " << tm.refinish_s << "s graph " << tm.graph_s << "s gfa-out " << tm.gfa_out_s << "s load " << tm.load_s << "s call " << tm.call_s << "s" << endl;
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) { PrintUsage(); return 0; }
+    if (!strcmp(argv[1], "run")) return run_main(argc, argv);
     if (!strcmp(argv[1], "model")) return model_main(argc, argv);
     if (!strcmp(argv[1], "density")) return density_main(argc - 1, argv + 1);
     if (!strcmp(argv[1], "filter")) return pfh::filter_main(argc, argv, false);         // script/Filter.R
@@ -918,9 +1054,42 @@ int main(int argc, char **argv) {
     }
     Options opt;
     DensityCli dc;
-    // --ref-threads N (this build's own switch, taken out of argv before getopt sees it): write the text format of the reference's
-    // `-t N` functions -- with N > 1: ids and var_count from 0, allele_frequency rows grouped by arity per bubble -- whatever -t says
-    for (int i = 1; i < argc; ++i) {
+    if (!take_long_options(argc, argv, 1, opt, dc)) return 1;
+    int oc;
+    while ((oc = getopt(argc, argv, "M:D:G:z:a:l:q:u:e:C:R:o:t:g:f:k:d:m:n:h:ibvpNSc")) != -1) {
+        switch (oc) {
+            case 'z': opt.complex_size = (size_t)atoi(optarg); break;
+            case 'M': opt.match = atof(optarg); break;
+            case 'D': opt.mismatch = atof(optarg); break;
+            case 'G': opt.gap = atof(optarg); break;
+            case 'u': opt.coverage_upper = atoi(optarg); opt.u_seen = true;  // falls through, as in the reference (:149-153)
+            case 'C': opt.coveragefile = optarg; if (oc == 'C') opt.cfile_seen = true; break;
+            case 'h': opt.hist = optarg; break;
+            case 'g': opt.graphfile = optarg; break;
+            case 'f': opt.colorfile = optarg; break;
+            case 'o': opt.outprefix = optarg; break;
+            case 'l': opt.coverage_lower = atoi(optarg); opt.l_seen = true; break;
+            case 't': opt.nb_threads = (size_t)atoi(optarg); break;
+            case 'k': opt.k = atoi(optarg); break;
+            case 'v': opt.verbose = true; break;
+            case 'd': opt.db = optarg; break;
+            case 'i': opt.info = true; break;
+            case 'q': opt.frequency = atof(optarg); break;
+            case 'm': case 'n': case 'a': case 'b': case 'p': break;  // accepted, no effect on this path
+            default:
+                cout << "Invalid option" << endl;
+                PrintUsage();
+                exit(EXIT_FAILURE);
+        }
+    }
+    return calling_main(opt, dc);
+}
+
+// The long options of the calling run, this build's own switches, taken out of argv[first ..] before getopt (or `run`'s own loop) sees
+// what is left.  --ref-threads N: write the text format of the reference's `-t N` functions -- with N > 1: ids and var_count from 0,
+// allele_frequency rows grouped by arity per bubble -- whatever -t says.  false: refused, one line on stderr.
+bool take_long_options(int &argc, char **argv, int first, Options &opt, DensityCli &dc) {
+    for (int i = first; i < argc; ++i) {
         if (const int took = dc.take(argc, argv, i)) {
             for (int j = i; j + took <= argc; ++j) argv[j] = j + took < argc ? argv[j + took] : nullptr;
             argc -= took;
@@ -933,6 +1102,7 @@ int main(int argc, char **argv) {
             --i;
         } else if (strcmp(argv[i], "--gpus") == 0 && i + 1 < argc) {
             opt.gpus = (size_t)std::max(1, atoi(argv[i + 1]));
+            opt.gpus_seen = true;
             for (int j = i; j + 2 <= argc; ++j) argv[j] = j + 2 < argc ? argv[j + 2] : nullptr;
             argc -= 2;
             --i;
@@ -969,40 +1139,65 @@ int main(int argc, char **argv) {
             else if (name == "--model-n") opt.model_n = atof(val.c_str());
             else if (name == "--model-iter") opt.model_iter = atoi(val.c_str());
             else if (name == "--model-delta") opt.model_delta = atof(val.c_str());
-            else { cerr << "Error: unknown option " << name << endl; return 1; }
+            else { cerr << "Error: unknown option " << name << endl; return false; }
             opt.model_option_seen = true;
             for (int j = i; j + 2 <= argc; ++j) argv[j] = j + 2 < argc ? argv[j + 2] : nullptr;
             argc -= 2;
             --i;
         }
     }
-    int oc;
-    while ((oc = getopt(argc, argv, "M:D:G:z:a:l:q:u:e:C:R:o:t:g:f:k:d:m:n:h:ibvpNSc")) != -1) {
-        switch (oc) {
-            case 'z': opt.complex_size = (size_t)atoi(optarg); break;
-            case 'M': opt.match = atof(optarg); break;
-            case 'D': opt.mismatch = atof(optarg); break;
-            case 'G': opt.gap = atof(optarg); break;
-            case 'u': opt.coverage_upper = atoi(optarg); opt.u_seen = true;  // falls through, as in the reference (:149-153)
-            case 'C': opt.coveragefile = optarg; if (oc == 'C') opt.cfile_seen = true; break;
-            case 'h': opt.hist = optarg; break;
-            case 'g': opt.graphfile = optarg; break;
-            case 'f': opt.colorfile = optarg; break;
-            case 'o': opt.outprefix = optarg; break;
-            case 'l': opt.coverage_lower = atoi(optarg); opt.l_seen = true; break;
-            case 't': opt.nb_threads = (size_t)atoi(optarg); break;
-            case 'k': opt.k = atoi(optarg); break;
-            case 'v': opt.verbose = true; break;
-            case 'd': opt.db = optarg; break;
-            case 'i': opt.info = true; break;
-            case 'q': opt.frequency = atof(optarg); break;
-            case 'm': case 'n': case 'a': case 'b': case 'p': break;  // accepted, no effect on this path
-            default:
-                cout << "Invalid option" << endl;
-                PrintUsage();
-                exit(EXIT_FAILURE);
-        }
+    return true;
+}
+
+// --model / --filter / --filter-multi / --density: refused here, before anything is read or written; the settings of the run
+bool model_setup(const Options &opt, DensityCli &dc, pfh::CDBG::ModelOptions &model, pf_filter_opts &filter, pf_filter_multi_opts &multi) {
+    if (opt.filter_seen) {
+        if (opt.model_source.empty()) { cerr << "Error: --filter stands in front of the model of the same run: it needs --model cov|fre (the filtered tables themselves: `ploidyfrost filter`)" << endl; return false; }
+        if (!opt.colorfile.empty()) { cerr << "Error: --filter reads the single-sample result streams; with -f the coverage tables have other columns (the colored path has --filter-multi)" << endl; return false; }
+        if (opt.gpus > 1) { cerr << "Error: --filter and --gpus " << opt.gpus << " do not go together (each rank holds a slice of the rows)" << endl; return false; }
+        if (!parse_filter_words(opt.filter_words, filter)) return false;
     }
+    if (opt.each_color && !opt.multi_seen) { cerr << "Error: --model-each-color needs --filter-multi \"OPTS\" (the colour is a column of the colored tables)" << endl; return false; }
+    if (opt.multi_seen) {
+        if (opt.filter_seen) { cerr << "Error: --filter-multi and --filter do not go together (one table layout a run)" << endl; return false; }
+        if (opt.model_source.empty()) { cerr << "Error: --filter-multi stands in front of the model of the same run: it needs --model cov|fre (the filtered tables themselves: `ploidyfrost filter-multi`)" << endl; return false; }
+        if (opt.gpus > 1) { cerr << "Error: --filter-multi and --gpus " << opt.gpus << " do not go together (the colored path runs on one GPU)" << endl; return false; }
+        if (opt.colorfile.empty()) { cerr << "Error: --filter-multi reads the colored result streams: it needs -f (the single-sample path has --filter)" << endl; return false; }
+        if (!parse_filter_multi_words(opt.multi_words, multi)) return false;
+        if (opt.each_color && refuse_each_color_with_one(multi)) return false;
+    }
+    if (opt.model_option_seen) {
+        if (opt.model_source.empty()) { cerr << "Error: the --model-... options need --model cov|fre" << endl; return false; }
+        if (opt.model_source != "cov" && opt.model_source != "fre") { cerr << "Error: --model " << opt.model_source << ": the source is cov or fre" << endl; return false; }
+        if (!opt.colorfile.empty() && !opt.multi_seen) {
+            cerr << "Error: --model reads the single-sample result streams; with -f the coverage tables have other columns and pool every sample: put --filter-multi \"OPTS\" in front of it" << endl;
+            return false;
+        }
+        if (opt.gpus > 1) { cerr << "Error: --model and --gpus " << opt.gpus << " do not go together (each rank holds a slice of the values)" << endl; return false; }
+        int lo = 0, hi = 0;
+        char tail = 0;
+        if (sscanf(opt.model_ploidy.c_str(), "%d:%d%c", &lo, &hi, &tail) != 2 || lo < 1 || hi < lo || hi > PF_GMM_MAX_GAUSS) {
+            cerr << "Error: --model-ploidy " << opt.model_ploidy << ": LO:HI Gaussians with 1 <= LO <= HI <= " << PF_GMM_MAX_GAUSS << endl;
+            return false;
+        }
+        if (opt.model_q >= 0.5) { cerr << "Error: --model-q: frequency cutoff value should < 0.5" << endl; return false; }
+        if (opt.model_iter < 0) { cerr << "Error: --model-iter: iterate count should > 0" << endl; return false; }
+        if (opt.model_delta < 0) { cerr << "Error: --model-delta: iterate delta should > 0" << endl; return false; }
+        if (opt.model_m < 0 || opt.model_n < 0) { cerr << "Error: --model-m / --model-n: minimum threshold should > 0" << endl; return false; }
+        model.on = true;
+        model.only = opt.model_only;
+        model.source = opt.model_source == "cov" ? PF_MODEL_COV : PF_MODEL_FRE;
+        model.q = opt.model_q;
+        model.lo = lo; model.hi = hi;
+        model.m_thre = opt.model_m; model.n_thre = opt.model_n; model.max_iter = opt.model_iter; model.max_delta = opt.model_delta;
+    }
+    if (!dc.check()) return false;
+    if (dc.on && !model.on) { cerr << "Error: --density takes the density of the values the model of the same run reads: it needs --model cov|fre (a column of numbers: `ploidyfrost density`)" << endl; return false; }
+    return true;
+}
+
+// the calling run: `ploidyfrost -g <graph> -d <database> ...`, single-sample or colored
+int calling_main(Options &opt, DensityCli &dc) {
     // --auto-cutoffs: the thresholds come from the database itself; every other source of them is refused by name, before anything
     // is read or written
     if (opt.auto_cutoffs) {
@@ -1017,49 +1212,8 @@ int main(int argc, char **argv) {
     // --model: refused here, before anything is read or written
     pfh::CDBG::ModelOptions model;
     pf_filter_opts filter = {};
-    if (opt.filter_seen) {
-        if (opt.model_source.empty()) { cerr << "Error: --filter stands in front of the model of the same run: it needs --model cov|fre (the filtered tables themselves: `ploidyfrost filter`)" << endl; return 1; }
-        if (!opt.colorfile.empty()) { cerr << "Error: --filter reads the single-sample result streams; with -f the coverage tables have other columns (the colored path has --filter-multi)" << endl; return 1; }
-        if (opt.gpus > 1) { cerr << "Error: --filter and --gpus " << opt.gpus << " do not go together (each rank holds a slice of the rows)" << endl; return 1; }
-        if (!parse_filter_words(opt.filter_words, filter)) return 1;
-    }
     pf_filter_multi_opts multi = {};
-    if (opt.each_color && !opt.multi_seen) { cerr << "Error: --model-each-color needs --filter-multi \"OPTS\" (the colour is a column of the colored tables)" << endl; return 1; }
-    if (opt.multi_seen) {
-        if (opt.filter_seen) { cerr << "Error: --filter-multi and --filter do not go together (one table layout a run)" << endl; return 1; }
-        if (opt.model_source.empty()) { cerr << "Error: --filter-multi stands in front of the model of the same run: it needs --model cov|fre (the filtered tables themselves: `ploidyfrost filter-multi`)" << endl; return 1; }
-        if (opt.gpus > 1) { cerr << "Error: --filter-multi and --gpus " << opt.gpus << " do not go together (the colored path runs on one GPU)" << endl; return 1; }
-        if (opt.colorfile.empty()) { cerr << "Error: --filter-multi reads the colored result streams: it needs -f (the single-sample path has --filter)" << endl; return 1; }
-        if (!parse_filter_multi_words(opt.multi_words, multi)) return 1;
-        if (opt.each_color && refuse_each_color_with_one(multi)) return 1;
-    }
-    if (opt.model_option_seen) {
-        if (opt.model_source.empty()) { cerr << "Error: the --model-... options need --model cov|fre" << endl; return 1; }
-        if (opt.model_source != "cov" && opt.model_source != "fre") { cerr << "Error: --model " << opt.model_source << ": the source is cov or fre" << endl; return 1; }
-        if (!opt.colorfile.empty() && !opt.multi_seen) {
-            cerr << "Error: --model reads the single-sample result streams; with -f the coverage tables have other columns and pool every sample: put --filter-multi \"OPTS\" in front of it" << endl;
-            return 1;
-        }
-        if (opt.gpus > 1) { cerr << "Error: --model and --gpus " << opt.gpus << " do not go together (each rank holds a slice of the values)" << endl; return 1; }
-        int lo = 0, hi = 0;
-        char tail = 0;
-        if (sscanf(opt.model_ploidy.c_str(), "%d:%d%c", &lo, &hi, &tail) != 2 || lo < 1 || hi < lo || hi > PF_GMM_MAX_GAUSS) {
-            cerr << "Error: --model-ploidy " << opt.model_ploidy << ": LO:HI Gaussians with 1 <= LO <= HI <= " << PF_GMM_MAX_GAUSS << endl;
-            return 1;
-        }
-        if (opt.model_q >= 0.5) { cerr << "Error: --model-q: frequency cutoff value should < 0.5" << endl; return 1; }
-        if (opt.model_iter < 0) { cerr << "Error: --model-iter: iterate count should > 0" << endl; return 1; }
-        if (opt.model_delta < 0) { cerr << "Error: --model-delta: iterate delta should > 0" << endl; return 1; }
-        if (opt.model_m < 0 || opt.model_n < 0) { cerr << "Error: --model-m / --model-n: minimum threshold should > 0" << endl; return 1; }
-        model.on = true;
-        model.only = opt.model_only;
-        model.source = opt.model_source == "cov" ? PF_MODEL_COV : PF_MODEL_FRE;
-        model.q = opt.model_q;
-        model.lo = lo; model.hi = hi;
-        model.m_thre = opt.model_m; model.n_thre = opt.model_n; model.max_iter = opt.model_iter; model.max_delta = opt.model_delta;
-    }
-    if (!dc.check()) return 1;
-    if (dc.on && !model.on) { cerr << "Error: --density takes the density of the values the model of the same run reads: it needs --model cov|fre (a column of numbers: `ploidyfrost density`)" << endl; return 1; }
+    if (!model_setup(opt, dc, model, filter, multi)) return 1;
     // check_ProgramOptions (:278-541), single-sample subset
     bool ok = true;
     const size_t max_threads = std::thread::hardware_concurrency();
@@ -1303,10 +1457,20 @@ int main(int argc, char **argv) {
     }
     if (opt.verbose && graph.n_abundant)
         cout << "CompactedDBG::read(): " << graph.n_abundant << " k-length unitigs are abundant k-mers (numbered last, in Bifrost's hash table order)" << endl;
-    g.set_threads((unsigned)opt.nb_threads);
-    g.set_overlap_output(true);
-    if (opt.ref_threads > 1 && g.set_reference_threads(opt.ref_threads)) die();
-    if (getenv("PF_BFS_HUGE_ON_DEVICE")) g.set_third_tier_on_host(false);   // experiments: giant traversals on one wavefront each
+    // the single-sample path's settings and steps: shared with `ploidyfrost run` (pf_run_host.hpp)
+    pfh::CallSetup call;
+    call.outprefix = opt.outprefix;
+    call.threads = opt.nb_threads;
+    call.ref_threads = opt.ref_threads;
+    call.lower = opt.coverage_lower;
+    call.upper = opt.coverage_upper;
+    call.info = opt.info;
+    call.verbose = opt.verbose;
+    call.model = model;
+    call.filter = opt.filter_seen ? &filter : nullptr;
+    call.density_points = dc.on ? dc.points : 0;
+    call.density_adjust = dc.adjust;
+    if (pfh::call_configure(g, call)) die();
     if (ranks.world > 1) {
         // ---- one graph over the GPUs of the node (the protocol of ploidyfrost_amd/dist.py from the C++ side) ----
         // every step that ends in a collective: the rank's own outcome first, then whether everybody is still there (pf_multi.hpp,
@@ -1384,32 +1548,7 @@ int main(int argc, char **argv) {
         if (rc) { cerr << "a rank ended with status " << rc << endl; _exit(rc); }
         _exit(0);
     }
-    if (model.on && g.set_model(model)) die();
-    if (opt.filter_seen && g.set_filter(&filter)) die();
-    if (dc.on && g.set_density(dc.points, dc.adjust)) die();
-    if (g.setUnitigId(opt.outprefix, opt.graphfile, opt.nb_threads)) die();
-    if (opt.info && g.printInfo(opt.verbose, opt.outprefix)) die();
-    mark("setUnitigId");
-    if (g.findSuperBubble_multithread_ptr(opt.outprefix, opt.nb_threads)) die();
-    mark("findSuperBubble");
-    cout << "CDBG:: Minimum Coverage:" << opt.coverage_lower << endl;
-    cout << "CDBG:: Maximum Coverage:" << opt.coverage_upper << endl;
-    if (g.ploidyEstimation_multithread_ptr(opt.outprefix, opt.coverage_lower, opt.coverage_upper, opt.nb_threads)) die();
-    mark("PloidyEstimation");
-    if (model.on) cout << g.model_last_line() << endl;
-    if (opt.verbose) {
-        const pfh::PhaseTimes &t = g.times();
-        printf("[device] candidates %llu (big tier %llu)  bfs %.3fs replay %.3fs | cov %.3fs tasks %.3fs (%llu) align %.3fs (%llu jobs) "
-               "sites %.3fs (%llu strings) format %.3fs write %.3fs\n",
-               (unsigned long long)t.candidates, (unsigned long long)t.bfs_deferred, t.bfs_device_s, t.replay_s, t.cov_device_s,
-               t.tasks_s, (unsigned long long)t.tasks, t.align_s, (unsigned long long)t.align_jobs, t.sites_s,
-               (unsigned long long)t.site_strings, t.format_s, t.write_s);
-        printf("[bfs]    traversals > 4096 unitigs: %llu (sum of seen %llu, largest %llu); committed by the replay: %llu (largest %llu)\n",
-               (unsigned long long)t.bfs_large, (unsigned long long)t.bfs_large_seen, (unsigned long long)t.bfs_max_seen,
-               (unsigned long long)t.bfs_large_used, (unsigned long long)t.bfs_large_used_max);
-        printf("[host]   scan %.3fs | align: build %.3fs device-call %.3fs post %.3fs choose %.3fs\n", t.scan_s, t.align_build_s,
-               t.align_device_s, t.align_post_s, t.align_choose_s);
-    }
+    if (pfh::call_run(g, call, mark)) die();
     // every result file is complete (PloidyEstimation joined the background writers): leave without walking the destructors
     cout.flush();
     cerr.flush();

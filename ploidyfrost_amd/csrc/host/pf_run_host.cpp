@@ -1,0 +1,261 @@
+#include "pf_run_host.hpp"
+
+#include <fcntl.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <cerrno>
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+#include <iostream>
+
+#include "pf_cutoffs.hpp"
+#include "pf_host_graph.hpp"
+#include "pf_mask_host.hpp"
+
+namespace pfh {
+
+namespace {
+
+using clk = std::chrono::steady_clock;
+double since(clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); }
+
+bool write_all(int fd, const void *p, uint64_t n) {
+    const char *c = static_cast<const char *>(p);
+    for (uint64_t done = 0; done < n;) {
+        const ssize_t put = write(fd, c + done, (size_t)(n - done));
+        if (put < 0 && errno == EINTR) continue;
+        if (put < 0) return false;
+        done += (uint64_t)put;
+    }
+    return true;
+}
+
+CountOptions count_options_of(const RunOptions &opt) {
+    CountOptions c;
+    c.k = opt.k;
+    c.ci = opt.ci;
+    c.cx = opt.cx;
+    c.cs = opt.cs;
+    c.both_strands = true;
+    c.chunk_bytes = opt.chunk_bytes;
+    c.initial_slots = opt.initial_slots;
+    return c;
+}
+
+}  // namespace
+
+// ---- the calling run behind a loaded CDBG ----
+int call_configure(CDBG &g, const CallSetup &s) {
+    g.set_threads((unsigned)s.threads);
+    g.set_overlap_output(true);
+    if (s.ref_threads > 1 && g.set_reference_threads(s.ref_threads)) return 1;
+    if (getenv("PF_BFS_HUGE_ON_DEVICE")) g.set_third_tier_on_host(false);   // experiments: giant traversals on one wavefront each
+    return 0;
+}
+
+int call_run(CDBG &g, const CallSetup &s, const std::function<void(const char *)> &mark) {
+    auto done = [&](const char *what) { if (mark) mark(what); };
+    if (s.model.on && g.set_model(s.model)) return 1;
+    if (s.filter && g.set_filter(s.filter)) return 1;
+    if (s.density_points && g.set_density(s.density_points, s.density_adjust)) return 1;
+    if (g.setUnitigId(s.outprefix, "", s.threads)) return 1;
+    if (s.info && g.printInfo(s.verbose, s.outprefix)) return 1;
+    done("setUnitigId");
+    if (g.findSuperBubble_multithread_ptr(s.outprefix, s.threads)) return 1;
+    done("findSuperBubble");
+    std::cout << "CDBG:: Minimum Coverage:" << s.lower << std::endl;
+    std::cout << "CDBG:: Maximum Coverage:" << s.upper << std::endl;
+    if (g.ploidyEstimation_multithread_ptr(s.outprefix, s.lower, s.upper, s.threads)) return 1;
+    done("PloidyEstimation");
+    if (s.model.on) std::cout << g.model_last_line() << std::endl;
+    if (s.verbose) {
+        const PhaseTimes &t = g.times();
+        printf("[device] candidates %llu (big tier %llu)  bfs %.3fs replay %.3fs | cov %.3fs tasks %.3fs (%llu) align %.3fs (%llu jobs) "
+               "sites %.3fs (%llu strings) format %.3fs write %.3fs\n",
+               (unsigned long long)t.candidates, (unsigned long long)t.bfs_deferred, t.bfs_device_s, t.replay_s, t.cov_device_s,
+               t.tasks_s, (unsigned long long)t.tasks, t.align_s, (unsigned long long)t.align_jobs, t.sites_s,
+               (unsigned long long)t.site_strings, t.format_s, t.write_s);
+        printf("[bfs]    traversals > 4096 unitigs: %llu (sum of seen %llu, largest %llu); committed by the replay: %llu (largest %llu)\n",
+               (unsigned long long)t.bfs_large, (unsigned long long)t.bfs_large_seen, (unsigned long long)t.bfs_max_seen,
+               (unsigned long long)t.bfs_large_used, (unsigned long long)t.bfs_large_used_max);
+        printf("[host]   scan %.3fs | align: build %.3fs device-call %.3fs post %.3fs choose %.3fs\n", t.scan_s, t.align_build_s,
+               t.align_device_s, t.align_post_s, t.align_choose_s);
+    }
+    return 0;
+}
+
+// ---- run ----
+std::string run_options_refusal(const RunOptions &opt) {
+    { const int c = count_options_clause(count_options_of(opt), true); if (c) return pf_count::cut_text(c); }
+    BuildOptions b;
+    b.k = opt.k;
+    b.g = opt.g;
+    return build_options_refusal(b);
+}
+
+int run_fastq(const std::vector<std::string> &inputs, const std::string &out_prefix, const RunOptions &opt, int device, RunStats &stats, RunTimes *times,
+              std::string &err) {
+    stats = RunStats{};
+    RunTimes tm;
+    // ---- refusals that need no device ----
+    if (inputs.empty()) { err = "run: no input"; return 1; }
+    if (out_prefix.empty()) { err = "run: no output prefix"; return 1; }
+    { const std::string why = run_options_refusal(opt); if (!why.empty()) { err = "run: " + why; return 1; } }
+    const CountOptions copt = count_options_of(opt);
+    const std::string tail = ".tmp." + std::to_string((long)getpid());
+    const std::string gfa_path = opt.gfa_out.empty() ? "" : opt.gfa_out + ".gfa", gfa_tmp = gfa_path + tail;
+    std::vector<std::string> outputs;
+    if (!opt.db_out.empty()) { outputs.push_back(opt.db_out + ".kmc_pre"); outputs.push_back(opt.db_out + ".kmc_suf"); }
+    if (!gfa_path.empty()) outputs.push_back(gfa_path);
+    uint64_t largest = 0;
+    if (fastq_preflight("run", "read", inputs, outputs, largest, err)) return 1;
+
+    pf_ctx *ctx = nullptr;
+    if (pf_create(device, &ctx) != PF_OK) {
+        err = std::string("run: no device context (") + (pf_last_error(nullptr) ? pf_last_error(nullptr) : "?") + "); reads are counted and called on the GPU only";
+        return 1;
+    }
+    // (the context goes to the loader of the calling run in the end: destroyed here only on the way out before that)
+    struct CtxGuard { pf_ctx *c; ~CtxGuard() { if (c) pf_destroy(c); } } ctx_guard{ctx};
+    bool db_written = false, gfa_tmp_written = false;
+    auto fail = [&](const std::string &m) {   // nothing is left under any output name after a refusal
+        err = m;
+        if (db_written) { unlink((opt.db_out + ".kmc_pre").c_str()); unlink((opt.db_out + ".kmc_suf").c_str()); }
+        if (gfa_tmp_written) unlink(gfa_tmp.c_str());
+        return 1;
+    };
+    auto dev_fail = [&]() { return fail(std::string("run: ") + pf_last_error(ctx)); };
+
+    // ---- count: every k-mer of the reads, both strands, the user's cut-offs ----
+    std::vector<uint64_t> rows;
+    int lo = 0, hi = 0;   // L, U
+    {
+        Counted db;
+        CountTimes ctm;
+        if (count_stream(ctx, "run", inputs, copt, largest, db, stats.counted, ctm, err)) return 1;
+        struct Free { pf_ctx *c; Counted &d; ~Free() { pf_device_free(c, d.kmers); pf_device_free(c, d.counts); } } free_db{ctx, db};
+        tm.count_s = ctm.stream_s;
+        tm.finish_s = ctm.finish_s;
+        // ---- cut-offs and the table: the histogram rows of the finished counters, then the counters into the table ----
+        const auto t_table = clk::now();
+        if (counted_rows(ctx, db, copt, rows) != PF_OK) return fail(std::string("run: histogram of the counters: ") + pf_last_error(ctx));
+        if (cutoffs_from_rows(rows, opt.quantile, lo, hi)) return fail("Error: Histogram File is badly Formatted.");
+        lo = std::max(10, lo);   // (what the calling run refuses about the pair it refuses below, where the chain's last command does)
+        stats.lower = (uint32_t)lo;
+        stats.upper = (uint32_t)std::max(hi, 0);
+        if (stats.lower > opt.mask_up)
+            return fail("run: the derived lower threshold " + std::to_string(stats.lower) + " is above the upper threshold " + std::to_string(opt.mask_up));
+        printf("%u\n", stats.lower);   // exactly as `mask --auto-cutoffs` prints it
+        fflush(stdout);
+        if (pf_upload_counts(ctx, db.kmers, db.counts, db.n, opt.k, opt.ci, opt.cx, 1) != PF_OK)
+            return fail(std::string("run: count table of the inputs: ") + pf_last_error(ctx));
+        tm.table_s = since(t_table);
+        if (!opt.db_out.empty()) {
+            const auto t_db = clk::now();
+            if (write_counted(ctx, "run", opt.db_out, db, copt, err)) return 1;
+            db_written = true;
+            tm.db_out_s = since(t_db);
+        }
+    }   // (the first count's arrays are freed here: the table holds what the rest of the run asks for)
+
+    // ---- recount: the k-mers of the masked reads, without the masked reads ----
+    Counted kept;
+    struct FreeKept { pf_ctx *&c; Counted &d; ~FreeKept() { if (c) { pf_device_free(c, d.kmers); pf_device_free(c, d.counts); } } } free_kept{ctx_guard.c, kept};
+    {
+        const auto t_stream = clk::now();
+        if (pf_count_begin(ctx, opt.k, 1, opt.initial_slots) != PF_OK) return dev_fail();
+        StreamTimes stm;
+        if (stream_fastq(ctx, "run", inputs, opt.chunk_bytes, largest, -1, "",
+                         [&](const char *text, uint64_t n, bool final, char *, uint64_t &used, uint64_t &reads, uint64_t &bad) {
+                             pf_maskcount_stats st = {};
+                             const int rc = pf_maskcount_fastq(ctx, text, n, final ? 1 : 0, stats.lower, opt.mask_up, &used, &st, &bad);
+                             if (rc != PF_OK) return rc;
+                             reads = st.reads;
+                             stats.masked.reads += st.reads;
+                             stats.masked.bases += st.bases;
+                             stats.masked.kmers += st.kmers;
+                             stats.masked.kmers_invalid += st.kmers_invalid;
+                             stats.masked.kmers_bad += st.kmers_bad;
+                             stats.masked.kmers_kept += st.kmers_kept;
+                             return (int)PF_OK;
+                         },
+                         stm, err)) {
+            pf_count_abort(ctx);
+            return fail(err);
+        }
+        tm.recount_s = since(t_stream);
+        const auto t_finish = clk::now();
+        pf_count_stats st2 = {};
+        if (pf_count_finish(ctx, 1, pf_count::COUNTER_MAX, pf_count::COUNTER_MAX, &kept.kmers, &kept.counts, &kept.n, &st2) != PF_OK) {
+            const int rc = dev_fail();
+            pf_count_abort(ctx);
+            return rc;
+        }
+        tm.refinish_s = since(t_finish);
+        pf_device_free(ctx, kept.counts);   // the graph asks for the k-mers alone
+        kept.counts = nullptr;
+        stats.distinct_kept = kept.n;
+    }
+    if (kept.n >= pf_unitig::MAX_KMERS) return fail(std::string("run: ") + pf_unitig::TOO_MANY_TEXT + " (" + std::to_string(kept.n) + ")");
+
+    // ---- graph ----
+    const auto t_graph = clk::now();
+    const uint32_t g = opt.g == BuildOptions::G_DEFAULT ? PF_UNITIG_G_DEFAULT : (uint32_t)opt.g;
+    if (pf_unitig_build(ctx, kept.kmers, kept.n, opt.k, g, opt.clip_tips ? 1 : 0, opt.del_isolated ? 1 : 0, &stats.graph) != PF_OK) return dev_fail();
+    pf_device_free(ctx, kept.kmers);   // the second count's arrays are dead: the text is the graph
+    kept.kmers = nullptr;
+    tm.graph_s = since(t_graph);
+
+    // ---- hand-off: the text stays where it is; the host gets its one copy (the size of the graph, not of the reads) ----
+    const auto t_load = clk::now();
+    const char *dev_text = nullptr;
+    uint64_t n_text = 0;
+    if (pf_unitig_text(ctx, &dev_text, &n_text) != PF_OK) return dev_fail();
+    std::vector<char> host_text((size_t)n_text);
+    if (pf_unitig_fetch(ctx, 0, n_text, host_text.data()) != PF_OK) return dev_fail();
+    if (!gfa_path.empty()) {
+        const auto t_gfa = clk::now();
+        const int fd = open(gfa_tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (fd < 0) return fail("run: cannot write " + gfa_tmp + " (" + strerror(errno) + ")");
+        gfa_tmp_written = true;
+        if (!write_all(fd, host_text.data(), n_text)) { const int e = errno; close(fd); return fail("run: writing " + gfa_tmp + " (" + strerror(e) + ")"); }
+        if (close(fd) != 0) return fail("run: closing " + gfa_tmp + " (" + strerror(errno) + ")");
+        tm.gfa_out_s = since(t_gfa);
+    }
+    UnitigSet graph;
+    {
+        std::string e;
+        if (!graph.open_gfa_memory(host_text.data(), n_text, dev_text, e)) return fail("CompactedDBG::read(): Graph could not be loaded! Exit. (" + e + ")");
+    }
+    graph.parse_on_device(ctx);   // a refusal is reported by the constructor
+    CountsLoader counts;
+    counts.adopt(ctx, (int)opt.k, true, rows, opt.ci);
+    ctx_guard.c = nullptr;   // the loader's from here, then the CDBG's
+    double match = opt.match, mismatch = opt.mismatch, gap = opt.gap;
+    const size_t complex_size = opt.complex_size;
+    CDBG cdbg(graph, complex_size, match, mismatch, gap, "", device, false, &counts);
+    if (!cdbg.good()) return fail(cdbg.error());
+    // as --auto-cutoffs checks the pair once graph and table are loaded
+    if (lo < 0 || hi < 0) return fail("Error: Filter coverage need a positive number.");
+    if (lo > hi) return fail("Error: lower cutoff need be smaller than upper cutoff ");
+    tm.load_s = since(t_load) - tm.gfa_out_s;
+
+    // ---- calling: the single-sample path as the command line sets it up ----
+    const auto t_call = clk::now();
+    CallSetup call = opt.call;
+    call.outprefix = out_prefix;
+    call.lower = (int)stats.lower;
+    call.upper = (int)stats.upper;
+    if (call_configure(cdbg, call) || call_run(cdbg, call)) return fail(cdbg.error());
+    stats.model_last_line = cdbg.model_last_line();
+    tm.call_s = since(t_call);
+    if (!gfa_path.empty() && rename(gfa_tmp.c_str(), gfa_path.c_str()) != 0)
+        return fail("run: renaming " + gfa_tmp + " to " + gfa_path + " (" + strerror(errno) + ")");
+    fflush(stdout);
+    if (times) *times = tm;
+    return 0;
+}
+
+}  // namespace pfh

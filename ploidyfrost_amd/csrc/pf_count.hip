@@ -30,6 +30,7 @@
 #include <string>
 
 #include "../../include/ploidyfrost_hip.h"
+#include "pf_count_dev.hpp"
 #include "pf_count_rule.hpp"
 #include "pf_ctx.hpp"
 #include "pf_reads_dev.hpp"
@@ -37,52 +38,10 @@
 
 namespace pf {
 
-struct CountSlot {
-    unsigned long long key;
-    uint32_t count, pad;
-};
-static_assert(sizeof(CountSlot) == 16, "one slot, one 16-byte vector access");
-constexpr uint64_t COUNT_MIN_SLOTS = 64;   // one word of the kept bitmap
-
-struct CountDev {   // device counters of one run
-    unsigned long long occupied;                  // claimed slots, exact
-    unsigned long long unique, below, above;      // k_count_flag
-    uint32_t overflow, stuck;                     // a counter wrapped; a probe went round the table
-};
-
-struct CountState {
-    CountSlot *tab = nullptr;
-    uint64_t slots = 0, occupied = 0, initial_slots = 0;
-    int k = 0;
-    bool both_strands = true;
-    CountDev *dev = nullptr;
-    pf_count_stats total = {};
-};
-
-__device__ inline uint64_t slot_key(const CountSlot *s) {
-    return __hip_atomic_load(&s->key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // ---- table ----
 __global__ __launch_bounds__(256) void k_count_clear(CountSlot *tab, uint64_t slots) {
     for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s < slots; s += (uint64_t)gridDim.x * 256)
         *reinterpret_cast<uint4 *>(tab + s) = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u);
-}
-
-// the slot of `key`: its own, or an empty one claimed for it.  0 = found, 1 = claimed, 2 = the probe went round the table
-__device__ inline int count_claim(CountSlot *tab, uint64_t mask, uint64_t key, uint64_t &slot) {
-    uint64_t s = mix64(key) & mask;
-    for (uint64_t step = 0; step <= mask; ++step) {
-        unsigned long long cur = slot_key(tab + s);
-        int claimed = 0;
-        if (cur == pf_count::EMPTY_KEY) {
-            cur = atomicCAS(&tab[s].key, (unsigned long long)pf_count::EMPTY_KEY, (unsigned long long)key);
-            if (cur == pf_count::EMPTY_KEY) { cur = key; claimed = 1; }
-        }
-        if (cur == key) { slot = s; return claimed; }
-        s = (s + 1) & mask;
-    }
-    return 2;
 }
 
 // ---- insert ----
@@ -224,8 +183,6 @@ struct CountTimed {   // brackets everything one call launches as one timed laun
     ~CountTimed() { ctx_end(ctx); }
 };
 
-static CountState *count_state(pf_ctx *ctx) { return static_cast<CountState *>(ctx->count); }
-
 void count_destroy(pf_ctx *ctx) {
     CountState *S = count_state(ctx);
     if (!S) return;
@@ -258,7 +215,7 @@ static int count_alloc_table(pf_ctx *ctx, const CountState *S, uint64_t slots, C
 }
 
 // the invariant: occupied + add <= 3/4 slots before a launch that can claim `add` slots
-static int count_reserve(pf_ctx *ctx, CountState *S, uint64_t add) {
+int count_reserve(pf_ctx *ctx, CountState *S, uint64_t add) {
     uint64_t want = S->tab ? S->slots : (S->initial_slots ? S->initial_slots : pow2_at_least(2 * add));
     while (S->occupied + add > want / 4 * 3) want <<= 1;
     if (S->tab && want == S->slots) return PF_OK;
@@ -299,12 +256,16 @@ static int count_core(pf_ctx *ctx, CountState *S, const char *text, uint64_t n, 
     k_count_insert<<<ctx_grid(ctx, n_tiles * MASK_BLOCK, MASK_BLOCK, 8), MASK_BLOCK, 0, ctx->stream>>>(a);
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess) { pf::CtxErr{ctx} = std::string("K-COUNT launch: ") + hipGetErrorString(le); return PF_ERR_HIP; }
+    return count_after_insert(ctx, S, "K-COUNT", counts, h);
+}
+
+int count_after_insert(pf_ctx *ctx, CountState *S, const char *who, MaskCounts *counts, MaskCounts &h) {
     CountDev d = {};
     PF_HIP(hipMemcpyAsync(&h, counts, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
     PF_HIP(hipMemcpyAsync(&d, S->dev, sizeof d, hipMemcpyDeviceToHost, ctx->stream));
     PF_HIP(hipStreamSynchronize(ctx->stream));
     S->occupied = d.occupied;
-    if (d.stuck) { pf::CtxErr{ctx} = "K-COUNT: a probe went round the whole table (the load bound was broken)"; return PF_ERR_HIP; }
+    if (d.stuck) { pf::CtxErr{ctx} = std::string(who) + ": a probe went round the whole table (the load bound was broken)"; return PF_ERR_HIP; }
     return PF_OK;
 }
 

@@ -165,17 +165,9 @@ struct MaskTimed {
     ~MaskTimed() { ctx_end(ctx); }
 };
 
-// classes, flag, paint, changed over text[0, n) on the device with the table on the device; counts zeroed by the caller, n > 0
-static int mask_core(pf_ctx *ctx, const char *text, uint64_t n, const uint64_t *off, const uint32_t *len, uint64_t n_reads, uint32_t low,
-                     uint32_t up, char *out, MaskCounts *counts) {
-    const uint64_t n_tiles = (n + MASK_TILE - 1) / MASK_TILE;
-    const uint64_t n_words = n_tiles * (MASK_TILE / 64);   // whole tiles: the flag phase writes every word of a tile
-    const uint64_t n_units = (n + 15) / 16;
-    uint64_t *bits = static_cast<uint64_t *>(ctx_ws(ctx, WS_MASK_BITS, (size_t)n_words * 8 * 4));
-    if (!bits) return PF_ERR_HIP;
-    uint64_t *seq = bits, *start = bits + n_words, *bad = bits + 2 * n_words, *changed = bits + 3 * n_words;
-    k_mask_classes<<<ctx_grid(ctx, n_words, MASK_BLOCK, 8), MASK_BLOCK, 0, ctx->stream>>>(off, len, n_reads, n_words, (uint32_t)ctx->tab_k, seq,
-                                                                                                      start, counts);
+// the flag phase alone over the resident table (K-MASKCOUNT launches it as well: pf_reads_dev.hpp)
+void mask_flag_launch(pf_ctx *ctx, const char *text, uint64_t n, uint64_t n_tiles, const uint64_t *start, uint64_t *bad, uint32_t low, uint32_t up,
+                      MaskCounts *counts) {
     MaskFlagArgs a;
     a.tab = ctx->d_tab;
     a.mask = ctx->tab_cap - 1;
@@ -190,6 +182,20 @@ static int mask_core(pf_ctx *ctx, const char *text, uint64_t n, const uint64_t *
     a.up = up;
     a.c = counts;
     k_mask_flag<<<ctx_grid(ctx, n_tiles * MASK_BLOCK, MASK_BLOCK, 8), MASK_BLOCK, 0, ctx->stream>>>(a);
+}
+
+// classes, flag, paint, changed over text[0, n) on the device with the table on the device; counts zeroed by the caller, n > 0
+static int mask_core(pf_ctx *ctx, const char *text, uint64_t n, const uint64_t *off, const uint32_t *len, uint64_t n_reads, uint32_t low,
+                     uint32_t up, char *out, MaskCounts *counts) {
+    const uint64_t n_tiles = (n + MASK_TILE - 1) / MASK_TILE;
+    const uint64_t n_words = n_tiles * (MASK_TILE / 64);   // whole tiles: the flag phase writes every word of a tile
+    const uint64_t n_units = (n + 15) / 16;
+    uint64_t *bits = static_cast<uint64_t *>(ctx_ws(ctx, WS_MASK_BITS, (size_t)n_words * 8 * 4));
+    if (!bits) return PF_ERR_HIP;
+    uint64_t *seq = bits, *start = bits + n_words, *bad = bits + 2 * n_words, *changed = bits + 3 * n_words;
+    k_mask_classes<<<ctx_grid(ctx, n_words, MASK_BLOCK, 8), MASK_BLOCK, 0, ctx->stream>>>(off, len, n_reads, n_words, (uint32_t)ctx->tab_k, seq,
+                                                                                                      start, counts);
+    mask_flag_launch(ctx, text, n, n_tiles, start, bad, low, up, counts);
     // (the last word of `changed` a read may touch lies inside the tiles; units beyond n_units are never read as changed bits:
     // zeroed so that the words are whole)
     PF_HIP(hipMemsetAsync(changed, 0, (size_t)n_words * 8, ctx->stream));

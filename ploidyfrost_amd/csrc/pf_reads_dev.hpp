@@ -36,7 +36,9 @@ static_assert(pf_mask::MAX_K - 1 <= 16 * MASK_HALO_UNITS, "the halo holds the re
 struct MaskCounts {   // device side of pf_mask_stats (reads is known to the host)
     unsigned long long reads_changed, bases, bases_masked, kmers, kmers_bad;
     unsigned long long bad_entry;   // k_mask_check_table / k_fq_records: the smallest offender, MASK_NO_RECORD = none
+    unsigned long long kmers_invalid, kmers_kept;   // K-MASKCOUNT only: windows holding a non-base, windows counted
 };
+static_assert(sizeof(MaskCounts) <= 256, "the counters lie in the 256 bytes behind a call's table or index");
 
 // 16 bytes of the text from unit `u`: one vector load inside the text, byte by byte (0 beyond the end) at its end
 __device__ inline uint4 mask_load_unit(const char *__restrict__ text, uint64_t n, uint64_t u) {
@@ -192,6 +194,11 @@ static __global__ __launch_bounds__(MASK_BLOCK) void k_fq_records(const char *__
 }
 
 // ---- host side ----
+// pf_mask.hip: k_mask_flag over text[0, n) against the context's resident count table, on the context's stream -- bad[w] for every
+// word of every tile from the window-start bitmap, kmers_bad added to counts.  The caller has checked that a table is resident.
+void mask_flag_launch(pf_ctx *ctx, const char *text, uint64_t n, uint64_t n_tiles, const uint64_t *start, uint64_t *bad, uint32_t low, uint32_t up,
+                      MaskCounts *counts);
+
 static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 constexpr uint64_t MASK_MAX_BYTES = 1ull << 40;   // every grid of a call stays far below 2^31 blocks
 

@@ -762,6 +762,19 @@ extern "C" int pf_unitig_fetch(pf_ctx *ctx, uint64_t first_byte, uint64_t len, c
     return PF_OK;
 }
 
+extern "C" int pf_unitig_text(pf_ctx *ctx, const char **text_dev, uint64_t *n_bytes) {
+    if (!ctx) return PF_ERR_ARG;
+    auto refuse = [&](const std::string &m) { pf::CtxErr{ctx} = m; return (int)PF_ERR_ARG; };
+    if (!text_dev || !n_bytes) return refuse("pf_unitig_text: text_dev and n_bytes are needed");
+    *text_dev = nullptr;
+    *n_bytes = 0;
+    UnitigState *S = unitig_state(ctx);
+    if (!S) return refuse("pf_unitig_text: no built graph is held (pf_unitig_build comes first)");
+    *text_dev = S->text;
+    *n_bytes = S->bytes;
+    return PF_OK;
+}
+
 extern "C" int pf_unitig_release(pf_ctx *ctx) {
     if (!ctx) return PF_ERR_ARG;
     (void)hipSetDevice(ctx->device);

@@ -35,6 +35,8 @@ K_TRIM = K_COUNT + 1       # PF_K_TRIM ("k_trim"): everything one pf_trim_fastq 
 TRIM_STEP = np.dtype([("kind", "<u4"), ("a", "<u4"), ("b", "<u4")])   # pf_trim_step
 TRIM_STATS = np.dtype([(f, "<u8") for f in ("reads", "kept", "dropped", "bases", "bases_kept", "both", "only1", "only2", "neither")])   # pf_trim_stats
 K_UNITIG = K_TRIM + 1      # PF_K_UNITIG ("k_unitig"): everything one pf_unitig_build launches; unit: k-mers
+K_MASKCOUNT = K_UNITIG + 1   # PF_K_MASKCOUNT ("k_maskcount"): everything one pf_maskcount_reads / pf_maskcount_fastq launches; unit: windows
+MASKCOUNT_STATS = np.dtype([(f, "<u8") for f in ("reads", "bases", "kmers", "kmers_invalid", "kmers_bad", "kmers_kept")])   # pf_maskcount_stats
 UNITIG_G_DEFAULT = 0xFFFFFFFF   # PF_UNITIG_G_DEFAULT: Bifrost's default for k
 COLOR_SEEDS = 31                # pf_color::DEFAULT_SEEDS: placement rounds of a colour file
 COLOR_STATS = np.dtype([(f, "<u8") for f in ("colors", "reads", "windows_colored", "windows_unplaced", "windows_bad", "runs", "overflow", "lines",
@@ -224,6 +226,9 @@ def load_library() -> C.CDLL:
         "pf_unitig_build": (i, [vp, vp, u64, u32, u32, i, i, vp]),
         "pf_unitig_fetch": (i, [vp, u64, u64, vp]),
         "pf_unitig_release": (i, [vp]),
+        "pf_unitig_text": (i, [vp, C.POINTER(vp), C.POINTER(u64)]),
+        "pf_maskcount_reads": (i, [vp, vp, u64, vp, vp, u64, u32, u32, vp]),
+        "pf_maskcount_fastq": (i, [vp, vp, u64, i, u32, u32, C.POINTER(u64), vp, C.POINTER(u64)]),
         "pf_unitig_build_colored": (i, [vp, vp, u64, u32, u32, i, i, u32, vp, C.POINTER(u64)]),
         "pf_color_begin": (i, [vp, u32]),
         "pf_color_reads": (i, [vp, u32, vp, u64, vp, vp, u64, vp]),
@@ -257,7 +262,8 @@ DECLARED_SYMBOLS = ["pf_create", "pf_warmup", "pf_destroy", "pf_last_error", "pf
                     "pf_gmm_density", "pf_count_histogram", "pf_mask_reads", "pf_mask_fastq",
                     "pf_count_begin", "pf_count_reads", "pf_count_fastq", "pf_count_finish", "pf_count_abort", "pf_kmc_encode",
                     "pf_trim_fastq", "pf_trim_fastq_pair", "pf_unitig_build", "pf_unitig_fetch", "pf_unitig_release",
-                    "pf_unitig_build_colored", "pf_color_begin", "pf_color_reads", "pf_color_fastq", "pf_color_finish", "pf_color_fetch"]
+                    "pf_unitig_build_colored", "pf_color_begin", "pf_color_reads", "pf_color_fastq", "pf_color_finish", "pf_color_fetch",
+                    "pf_maskcount_reads", "pf_maskcount_fastq", "pf_unitig_text"]
 
 
 def trim_steps(steps) -> np.ndarray:
@@ -661,6 +667,43 @@ class Device:
 
     def count_abort(self):
         self._check(self.L.pf_count_abort(self.h))
+
+    def maskcount_reads(self, text, read_off, read_len, low: int, up: int = MASK_NO_UPPER):
+        """K-MASKCOUNT (pf_maskcount_reads): counts into the open count every window of the reads that survives the masking with
+        [low, up] against the resident table -- mask_reads followed by count_reads on its output, without that output.  Arguments as
+        count_reads takes them; returns this call's statistics."""
+        if isinstance(text, (bytes, bytearray)):
+            text = np.frombuffer(bytes(text), dtype=np.uint8)
+        if isinstance(read_off, (list, tuple, np.ndarray)):
+            read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
+        if isinstance(read_len, (list, tuple, np.ndarray)):
+            read_len = np.ascontiguousarray(read_len, dtype=np.uint32)
+        n, n_reads = int(text.shape[0]), int(read_off.shape[0])
+        stats = np.zeros(1, dtype=MASKCOUNT_STATS)
+        self._check(self.L.pf_maskcount_reads(self.h, _ptr(text) if n else None, n, _ptr(read_off) if n_reads else None,
+                                              _ptr(read_len) if n_reads else None, n_reads, low, up, stats.ctypes.data))
+        return {f: int(stats[0][f]) for f in MASKCOUNT_STATS.names}
+
+    def maskcount_fastq(self, text, low: int, up: int = MASK_NO_UPPER, final: bool = True):
+        """pf_maskcount_fastq on one chunk of a FASTQ file: (bytes_used, this call's statistics).  A format error raises DeviceError
+        with .bad_record = the 0-based record within the chunk."""
+        if isinstance(text, (bytes, bytearray)):
+            text = np.frombuffer(bytes(text), dtype=np.uint8)
+        n = int(text.shape[0])
+        stats = np.zeros(1, dtype=MASKCOUNT_STATS)
+        used, bad = C.c_uint64(), C.c_uint64()
+        st = self.L.pf_maskcount_fastq(self.h, _ptr(text) if n else None, n, int(final), low, up, C.byref(used), stats.ctypes.data, C.byref(bad))
+        if st != PF_OK:
+            e = DeviceError(st, self.L.pf_last_error(self.h).decode())
+            e.bad_record = bad.value
+            raise e
+        return used.value, {f: int(stats[0][f]) for f in MASKCOUNT_STATS.names}
+
+    def unitig_text(self):
+        """pf_unitig_text: (device address, bytes) of the text a held graph keeps on the device until unitig_release"""
+        p, n = C.c_void_p(), C.c_uint64()
+        self._check(self.L.pf_unitig_text(self.h, C.byref(p), C.byref(n)))
+        return p.value, n.value
 
     def unitig_build(self, kmers, k: int, clip_tips: bool = False, del_isolated: bool = False, g=None):
         """K-UNITIG (pf_unitig_build, pf_unitig_fetch, pf_unitig_release): (the text of the GFA file as bytes, statistics) of the

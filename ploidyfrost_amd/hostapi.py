@@ -44,7 +44,20 @@ DECLARED_SYMBOLS = ["pfh_open", "pfh_close", "pfh_last_error", "pfh_set_output_d
                     "pfh_count_fastq", "pfh_mask_fastq_counted", "pfh_count_reads_host", "pfh_count_encode_kmc1", "pfh_count_counter_bytes",
                     "pfh_count_lut_prefix_len", "pfh_count_cut_text", "pfh_build_fastq", "pfh_unitig_build_host", "pfh_unitig_no_room_text",
                     "pfh_build_colored_fastq", "pfh_build_colored_host", "pfh_bfg_colors_bytes", "pfh_color_no_room_text",
+                    "pfh_run_defaults", "pfh_run_fastq", "pfh_count_masked_host",
                     "pfh_trim_fastq", "pfh_trim_fastq_pair", "pfh_trim_parse_step", "pfh_trim_refusal_text", "pfh_trim_read", "pfh_trim_fastq_chunk"]
+
+
+class RunOptions(C.Structure):   # pfh_run_options (include/ploidyfrost_host.h)
+    _fields_ = [("k", C.c_uint32), ("ci", C.c_uint64), ("cx", C.c_uint64), ("cs", C.c_uint64), ("g", C.c_int32), ("clip_tips", C.c_int),
+                ("del_isolated", C.c_int), ("chunk_bytes", C.c_uint64), ("initial_slots", C.c_uint64), ("quantile", C.c_double),
+                ("mask_up", C.c_uint32), ("complex_size", C.c_uint32), ("match", C.c_double), ("mismatch", C.c_double), ("gap", C.c_double),
+                ("threads", C.c_uint32), ("model_source", C.c_int), ("model_only", C.c_int), ("db_out", C.c_char_p), ("gfa_out", C.c_char_p)]
+
+
+RUN_STATS_FIELDS = ("reads", "bases", "kmers", "bad", "distinct", "lower", "upper", "windows_bad", "windows_kept", "distinct_kept", "unitigs",
+                    "removed", "unitigs_out", "longest")   # pfh_run_stats: the fields of `run`'s stderr line, in its order
+MASKCOUNT_STATS_FIELDS = ("reads", "bases", "kmers", "kmers_invalid", "kmers_bad", "kmers_kept")   # pf_maskcount_stats
 
 
 class FilterOpts(C.Structure):   # pf_filter_opts (include/ploidyfrost_hip.h)
@@ -206,6 +219,10 @@ def load_library() -> C.CDLL:
     L.pfh_count_lut_prefix_len.argtypes = [u32]
     L.pfh_build_fastq.argtypes = [C.POINTER(C.c_char_p), u32, C.c_char_p, u32, C.c_int32, C.c_int, C.c_int, u64, u64, C.c_int, vp, vp]
     L.pfh_unitig_build_host.argtypes = [vp, u64, u32, C.c_int32, C.c_int, C.c_int, vp, u64, C.POINTER(u64), vp]
+    L.pfh_run_defaults.restype = None
+    L.pfh_run_defaults.argtypes = [C.POINTER(RunOptions)]
+    L.pfh_run_fastq.argtypes = [C.POINTER(C.c_char_p), u32, C.c_char_p, C.POINTER(RunOptions), C.c_int, vp]
+    L.pfh_count_masked_host.argtypes = [vp, vp, vp, u64, u32, vp, u32, u32, vp, vp, u64, C.POINTER(u64), vp]
     L.pfh_unitig_no_room_text.restype = C.c_char_p
     L.pfh_unitig_no_room_text.argtypes = [u64, u64, u64]
     L.pfh_build_colored_fastq.argtypes = [C.POINTER(C.c_char_p), u32, C.c_char_p, u32, C.c_int32, C.c_int, C.c_int, u32, u64, u64, C.c_int, vp, vp, vp,
@@ -678,6 +695,62 @@ def build_graph(inputs, out_prefix: str, k: int = 25, clip_tips: bool = False, d
     d.update({f: int(stats[0][f]) for f in UNITIG_STATS.names if f != "stage_ms"})
     d["stage_ms"] = [float(x) for x in stats[0]["stage_ms"]]
     return d
+
+
+def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 ** 9, cs: int = 10000, q: float = 0.998, mask_upper=None,
+              keep_tips: bool = False, keep_isolated: bool = False, g=None, z: int = 8, M: float = 2.0, D: float = -1.0, G: float = -3.0,
+              threads: int = 1, model=None, model_only: bool = False, db_out=None, gfa_out=None, chunk_bytes: int = 0,
+              initial_slots: int = 0) -> dict:
+    """`ploidyfrost run` (pfh_run_fastq): reads to ploidy estimate in one process -- the FASTQ file(s) `inputs` counted, the thresholds
+    derived, the k-mers of the masked reads counted (K-MASKCOUNT), the graph built and the single-sample calling run made on one device
+    context; PloidyFrost_output/<out_prefix>_*.txt in the working directory.  model: None, "cov" or "fre".  Returns the fields of the
+    command's stderr line ("lower" and "upper" among them).  A refusal raises RuntimeError by name."""
+    L = load_library()
+    paths, n = _paths(inputs)
+    o = RunOptions()
+    L.pfh_run_defaults(C.byref(o))
+    o.k, o.ci, o.cx, o.cs = int(k), int(ci), int(cx), int(cs)
+    o.g = _unitig_g(g)
+    o.clip_tips, o.del_isolated = int(not keep_tips), int(not keep_isolated)
+    o.chunk_bytes, o.initial_slots = int(chunk_bytes), int(initial_slots)
+    o.quantile = float(q)
+    o.mask_up = 0xFFFFFFFF if mask_upper is None else int(mask_upper)
+    o.complex_size, o.match, o.mismatch, o.gap, o.threads = int(z), float(M), float(D), float(G), int(threads)
+    if model is not None:
+        if model not in ("cov", "fre"):
+            raise ValueError("run_reads: model is None, 'cov' or 'fre'")
+        o.model_source = 0 if model == "cov" else 1   # PF_MODEL_COV, PF_MODEL_FRE
+        o.model_only = int(model_only)
+    o.db_out = None if db_out is None else os.fsencode(db_out)
+    o.gfa_out = None if gfa_out is None else os.fsencode(gfa_out)
+    stats = np.zeros(len(RUN_STATS_FIELDS), dtype=np.uint64)
+    rc = L.pfh_run_fastq(paths, n, os.fsencode(out_prefix), C.byref(o), 0, stats.ctypes.data)
+    if rc:
+        raise RuntimeError(L.pfh_last_error(None).decode())
+    return {f: int(v) for f, v in zip(RUN_STATS_FIELDS, stats)}
+
+
+def count_masked_host(text: bytes, read_off, read_len, k: int, counters, low: int, up: int = 0xFFFFFFFF):
+    """(kmers u64 sorted, counts u32, stats dict): the rule of `run`'s second pass on the host (pfh_count_masked_host,
+    csrc/pf_run_rule.hpp; no device) -- every window of the reads that survives the masking with [low, up], counted in canonical form.
+    counters: one u32 per byte of the text, the counter of the window that starts there (read at window starts only)."""
+    L = load_library()
+    src = np.frombuffer(bytes(text), dtype=np.uint8)
+    off = np.ascontiguousarray(read_off, dtype=np.uint64)
+    ln = np.ascontiguousarray(read_len, dtype=np.uint32)
+    cnt = np.ascontiguousarray(counters, dtype=np.uint32)
+    if len(cnt) < len(src):
+        raise ValueError("count_masked_host: one counter per byte of the text")
+    cap = max(int(ln.astype(np.int64).sum()), 1)
+    kmers, counts = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint32)
+    n = C.c_uint64()
+    stats = np.zeros(len(MASKCOUNT_STATS_FIELDS), dtype=np.uint64)
+    rc = L.pfh_count_masked_host(src.ctypes.data if len(src) else None, off.ctypes.data, ln.ctypes.data, len(off), int(k),
+                                 cnt.ctypes.data if len(cnt) else None, int(low), int(up), kmers.ctypes.data, counts.ctypes.data, cap, C.byref(n),
+                                 stats.ctypes.data)
+    if rc:
+        raise ValueError("count_masked_host: k = %d: k goes from 3 to 31" % k)
+    return kmers[: n.value].copy(), counts[: n.value].copy(), {f: int(v) for f, v in zip(MASKCOUNT_STATS_FIELDS, stats)}
 
 
 def unitig_build_host(kmers, k: int, clip_tips: bool = False, del_isolated: bool = False, g=None):
