@@ -69,6 +69,8 @@ enum pf_kernel {
     PF_K_TRIM, /* K-TRIM: everything one pf_trim_fastq / pf_trim_fastq_pair launches (index, intervals, sizes, scan, copy), timed as one launch; unit: records */
     PF_K_UNITIG, /* K-UNITIG: everything one pf_unitig_build launches (index, adjacency, link, simplify, rank, cycles, emit), timed as one launch; unit: k-mers */
     PF_K_MASKCOUNT, /* K-MASKCOUNT: everything one pf_maskcount_reads / pf_maskcount_fastq launches (index, classes, flag, insert, growth), timed as one launch; unit: windows */
+    PF_K_UNION, /* K-UNION: everything one pf_kmer_union launches (check, the count and write kernels of every merge, their scans), timed as one launch; unit: keys given */
+    PF_K_COLORSET, /* K-COLORSET: the kernel of one pf_color_kmers; unit: keys */
     PF_K_COUNT_
 };
 int pf_enable_timing(pf_ctx *, int on);
@@ -312,8 +314,24 @@ int pf_color_reads(pf_ctx *, uint32_t colour, const char *text, uint64_t n_bytes
                    pf_color_stats *stats);
 int pf_color_fastq(pf_ctx *, uint32_t colour, const char *text, uint64_t n_bytes, int final, uint64_t *bytes_used, pf_color_stats *stats,
                    uint64_t *bad_record);
+/* K-COLORSET: colour `colour` from the sorted or unsorted distinct canonical k-mers of its reads instead of from the reads (the rule:
+ * csrc/pf_runmulti_rule.hpp) -- one look-up per key in the table pf_color_begin built, the same planes pf_color_reads sets from the
+ * windows.  Between pf_color_begin and pf_color_finish; may be mixed with pf_color_reads / pf_color_fastq.  kmers_dev: [dev].  Refused by
+ * name (PF_ERR_ARG): no colouring open, a colour of n_colors or more, an array that is not on the device. */
+typedef struct pf_color_kmers_stats {
+    uint64_t kmers;           /* keys given */
+    uint64_t kmers_colored;   /* keys that lie in the graph */
+    uint64_t kmers_unplaced;  /* keys the graph does not hold (-i / -d removed them, or they never were vertices) */
+} pf_color_kmers_stats;
+int pf_color_kmers(pf_ctx *, uint32_t colour, const uint64_t *kmers_dev, uint64_t n, pf_color_kmers_stats *stats);
 int pf_color_finish(pf_ctx *, pf_color_stats *stats);
 int pf_color_fetch(pf_ctx *, uint64_t *heads, uint32_t *m, uint32_t *slot, uint64_t *run_off, uint32_t *runs);
+/* K-UNION: the sorted distinct union of n_sets (1 .. 1024) sorted distinct arrays of 64-bit keys on the device (csrc/pf_union.hip; the
+ * rule: csrc/pf_runmulti_rule.hpp) -- the vertices of the coloured graph from the k-mers of every sample's masked reads.  sets_dev[c]:
+ * [dev], n[c] keys (an empty set may be NULL); the inputs stay the caller's.  *out_dev: a fresh device array of *n_out keys, released with
+ * pf_device_free; the same array on every call.  A set that is not on the device, not ascending or holds a key twice: PF_ERR_ARG by
+ * name, before anything is merged.  What does not fit the free device memory: PF_ERR_OVERFLOW by name with the counts. */
+int pf_kmer_union(pf_ctx *, uint32_t n_sets, const uint64_t *const *sets_dev, const uint64_t *n, uint64_t **out_dev, uint64_t *n_out);
 /* K-TRIM: reads quality-trimmed on the device -- what step `1.trim` of the reference's workflow does with
  * `trimmomatic PE -phred33 ... LEADING:10 TRAILING:10 SLIDINGWINDOW:3:20 MINLEN:50`.  The rule (csrc/pf_trim_rule.hpp): the quality of
  * position i of a read of n bases is q[i] = (int)byte - phred (phred 33 or 64; signed); the state is an interval [b, e) of the read,
@@ -368,6 +386,9 @@ int pf_copy_to_host(pf_ctx *, void *dst, const void *src_dev, size_t bytes);
  * (csrc/pf_device_common.hpp, "minimizer-local addressing").  [host|dev] */
 int pf_upload_counts(pf_ctx *, const uint64_t *kmers, const uint32_t *counts, uint64_t n, uint32_t k, uint64_t min_count,
                      uint64_t max_count, int both_strands);
+/* Gives the single-sample count table (and the coverage array joined from it) back: the context is as before the first
+ * pf_upload_counts.  `ploidyfrost run-multi` calls it behind the last sample's second pass, before the coloured graph goes in. */
+int pf_release_counts(pf_ctx *);
 /* K-COV-JOIN again (it runs by itself when graph and table are both resident): every look-up CDBG::readCov(UnitigMap) makes in one
  * run of the reference -- one CheckKmer per graph k-mer (src/CDBG.cpp:66-120 inside :1187-1220) -- as one kernel launch.  For
  * callers that account for those look-ups per pass (bench.py's value_incl_join).  PF_ERR_ARG without a graph and a canonical table. */

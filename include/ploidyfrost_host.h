@@ -181,6 +181,26 @@ void pfh_run_defaults(pfh_run_options *opt);
 int pfh_run_fastq(const char *const *inputs, uint32_t n_inputs, const char *out_prefix, const pfh_run_options *opt, int device, pfh_run_stats *stats);
 int pfh_count_masked_host(const char *text, const uint64_t *off, const uint32_t *len, uint64_t n_reads, uint32_t k, const uint32_t *counters,
                           uint32_t low, uint32_t up, uint64_t *kmers_out, uint32_t *counts_out, uint64_t cap, uint64_t *n, uint64_t stats_out[6]);
+/* ---- reads of several samples to per-sample ploidy in one process (`ploidyfrost run-multi`, K-UNION and K-COLORSET) ----
+ * pfh_run_multi_fastq: for n_samples samples (a sample is a colour, named names[c], in the order given) what n_samples times
+ * `mask -k ... --auto-cutoffs --db-out`, one `build-multi -i -d` and the coloured calling run with --auto-cutoffs do with files between
+ * them, on one device context (csrc/host/pf_runmulti_host.hpp; the rule: csrc/pf_runmulti_rule.hpp).  inputs: the files of sample 0,
+ * then of sample 1, ...; n_inputs_of[c] of them belong to sample c.  opt: pfh_run_options (db_out: <db_out><c>.kmc_pre / .kmc_suf per
+ * sample; gfa_out: <gfa_out>.gfa and <gfa_out>.bfg_colors); a model needs multi (the options of `filter-multi`; may be NULL without
+ * one), each_color: one estimate per colour.  per_color (may be NULL): four numbers per sample -- lower, upper, distinct k-mers
+ * counted, distinct k-mers of the masked reads.  Every L is printed on stdout.  Refused by name before a device context exists: what
+ * pfh_run_fastq refuses, no sample, more than 1024, a sample without input, a name twice, a file in two samples.  0 = ok, else
+ * pfh_last_error(NULL).
+ * pfh_union_host: the host's plain restatement of K-UNION (pairwise rounds, an odd set carried), no device involved: out holds the sum
+ * of n[] keys at least, *n_out the size of the union.  1: a set that is not ascending or holds a key twice (pfh_last_error(NULL)). */
+typedef struct pfh_run_multi_stats {
+    uint64_t colors, reads, bases, kmers, bad, distinct, windows_bad, windows_kept, distinct_kept, unitigs, removed, unitigs_out, longest, kmers_colored,
+        kmers_unplaced, runs, overflow, color_bytes;
+} pfh_run_multi_stats;
+int pfh_run_multi_fastq(const char *const *names, const uint32_t *n_inputs_of, uint32_t n_samples, const char *const *inputs, const char *out_prefix,
+                        const pfh_run_options *opt, const pf_filter_multi_opts *multi, int each_color, int device, pfh_run_multi_stats *stats,
+                        uint64_t *per_color);
+int pfh_union_host(const uint64_t *const *sets, const uint64_t *n, uint32_t n_sets, uint64_t *out, uint64_t *n_out);
 /* ---- the coloured graph built from several files of reads (K-COLOR, pf_color_* in ploidyfrost_hip.h) ----
  * `Bifrost build -c -k 25 [-i] [-d] -r s0.fq -r s1.fq ... -o sample` in one call: pfh_build_fastq's graph of all inputs together with a
  * DA tag on every S line, and <out_prefix>.bfg_colors (format version 2; csrc/host/pf_bfg_write.hpp), every input one colour in the

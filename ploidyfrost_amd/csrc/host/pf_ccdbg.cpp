@@ -33,24 +33,30 @@ bool ColoredUnitigSet::read(const std::string &graphfile, const std::string &col
     return colors.load(colorfile, graph, color_threads_, err);
 }
 
-bool ColoredUnitigSet::reload_colors() { return colors.load(colorfile_, graph, color_threads_, err); }
+bool ColoredUnitigSet::open_memory(const char *host_text, uint64_t n, const char *device_text, const uint8_t *color_bytes, uint64_t n_color_bytes,
+                                   size_t nb_threads) {
+    if (!graph.open_gfa_memory(host_text, n, device_text, err)) return false;
+    color_bytes_ = color_bytes;
+    n_color_bytes_ = n_color_bytes;
+    colors_pending_ = true;
+    color_threads_ = (unsigned)std::max<size_t>(nb_threads, 1);
+    return true;
+}
+
+bool ColoredUnitigSet::reload_colors() {
+    if (!color_bytes_) return colors.load(colorfile_, graph, color_threads_, err);
+    // behind the device ingest the host holds the segment table alone: the reader asks for the packed head k-mers as load_gfa leaves them
+    graph.ensure_text();
+    if (graph.words.empty()) graph.pack();
+    colors_pending_ = false;
+    return colors.load_bytes(color_bytes_, (size_t)n_color_bytes_, graph, color_threads_, err);
+}
 
 CCDBG::CCDBG(ColoredUnitigSet &graph, const size_t &complexsize, double &m, double &d, double &g, std::string kmc_db_list,
              const size_t &thread, int device, bool quiet, std::vector<std::vector<uint64_t>> *rows_out)
     : CDBG(graph.graph, complexsize, m, d, g, device, quiet, NoCounts{}), cg_(graph) {
-    if (status_) return;
-    if (cg_.graph.n_abundant && !cg_.reload_colors()) { fail(PF_ERR_ARG, "CCDBG::CCDBG():Error: " + cg_.err); return; }
-    col_ = &cg_.colors;
-    st_.col = col_;
+    if (status_ || !init_colors()) return;
     const uint32_t C = cg_.colors.n_colors;
-    if (C > PF_MAX_COLORS_TABLE) { fail(PF_ERR_ARG, "CCDBG::CCDBG():Error: more colours than the device table holds"); return; }
-    // the colour gate of the accept commit goes to the device with the graph: the commits run there (pf_replay_device).  Colour sets
-    // are (C + 63) / 64 words per unitig, on the host and on the device alike: the reference has no limit on the number of colours
-    // (src/CCDBG.cpp:2759-2853 loops over getNbColors()), the joined table's PF_MAX_COLORS_TABLE is the only one here.
-    {
-        const int st = pf_replay_set_colours(ctx_, C, cg_.colors.full_mask.data(), cg_.colors.size_total.data(), cg_.colors.n_full_enc.data());
-        colours_on_device_ = st == PF_OK;
-    }
     if (!kmc_db_list.empty()) {
         // src/CCDBG.cpp:13-43: one database name per line, one line per colour
         FILE *f = fopen(kmc_db_list.c_str(), "r");
@@ -95,31 +101,68 @@ CCDBG::CCDBG(ColoredUnitigSet &graph, const size_t &complexsize, double &m, doub
         if (st == PF_OK) st = pf_upload_counts_colored(ctx_, C, pk.data(), pc.data(), n.data(), mn.data(), mx.data(), both.data());
         for (uint32_t c = 0; c < C; ++c) { pf_device_free(ctx_, pk[c]); pf_device_free(ctx_, pc[c]); }
         if (st != PF_OK) { fail(st, std::string("CCDBG::CCDBG():Error: ") + pf_last_error(ctx_)); return; }
-        // the colour sets the calling phase asks about go to the device as well (pf_call_set_colours): the mask of colours on every
-        // k-mer, UnitigColors::size(), and one bit per k-mer for a colour on part of a unitig
-        if (const char *e = getenv("PF_CALL")) resident_ = strcmp(e, "host") != 0;
-        if (resident_) {
-            const ColorSets &cs = cg_.colors;
-            const uint32_t N = g_.n();
-            std::vector<uint32_t> us;
-            us.reserve(cs.partial.size());
-            for (const auto &kv : cs.partial) us.push_back(kv.first);
-            std::sort(us.begin(), us.end());
-            std::vector<uint32_t> part_first((size_t)N + 1, 0), part_colour;
-            std::vector<uint64_t> part_word, bits;
-            for (uint32_t u : us) part_first[(size_t)u + 1] = (uint32_t)cs.partial.at(u).size();
-            for (uint32_t u = 0; u < N; ++u) part_first[(size_t)u + 1] += part_first[u];
-            for (uint32_t u : us)
-                for (const ColorSets::Partial &pt : cs.partial.at(u)) {
-                    part_colour.push_back(pt.colour);
-                    part_word.push_back(bits.size());
-                    bits.insert(bits.end(), pt.bits.begin(), pt.bits.end());
-                }
-            st = pf_call_set_colours(ctx_, C, cs.full_mask.data(), cs.size_total.data(), part_first.data(), part_colour.data(), part_word.data(), bits.data(),
-                                     part_colour.size(), bits.size());
-            colored_resident_ = st == PF_OK;
-        }
+        colours_to_device();
     }
+    if (!quiet_) printf("CCDBG::CCDBG():CCDBG initialized!\n");
+}
+
+bool CCDBG::init_colors() {
+    if ((cg_.colors_pending() || cg_.graph.n_abundant) && !cg_.reload_colors()) { fail(PF_ERR_ARG, "CCDBG::CCDBG():Error: " + cg_.err); return false; }
+    col_ = &cg_.colors;
+    st_.col = col_;
+    const uint32_t C = cg_.colors.n_colors;
+    if (C > PF_MAX_COLORS_TABLE) { fail(PF_ERR_ARG, "CCDBG::CCDBG():Error: more colours than the device table holds"); return false; }
+    // the colour gate of the accept commit goes to the device with the graph: the commits run there (pf_replay_device).  Colour sets
+    // are (C + 63) / 64 words per unitig, on the host and on the device alike: the reference has no limit on the number of colours
+    // (src/CCDBG.cpp:2759-2853 loops over getNbColors()), the joined table's PF_MAX_COLORS_TABLE is the only one here.
+    const int st = pf_replay_set_colours(ctx_, C, cg_.colors.full_mask.data(), cg_.colors.size_total.data(), cg_.colors.n_full_enc.data());
+    colours_on_device_ = st == PF_OK;
+    return true;
+}
+
+void CCDBG::colours_to_device() {
+    const uint32_t C = cg_.colors.n_colors;
+    int st = PF_OK;
+    // the colour sets the calling phase asks about go to the device as well (pf_call_set_colours): the mask of colours on every
+    // k-mer, UnitigColors::size(), and one bit per k-mer for a colour on part of a unitig
+    if (const char *e = getenv("PF_CALL")) resident_ = strcmp(e, "host") != 0;
+    if (resident_) {
+        const ColorSets &cs = cg_.colors;
+        const uint32_t N = g_.n();
+        std::vector<uint32_t> us;
+        us.reserve(cs.partial.size());
+        for (const auto &kv : cs.partial) us.push_back(kv.first);
+        std::sort(us.begin(), us.end());
+        std::vector<uint32_t> part_first((size_t)N + 1, 0), part_colour;
+        std::vector<uint64_t> part_word, bits;
+        for (uint32_t u : us) part_first[(size_t)u + 1] = (uint32_t)cs.partial.at(u).size();
+        for (uint32_t u = 0; u < N; ++u) part_first[(size_t)u + 1] += part_first[u];
+        for (uint32_t u : us)
+            for (const ColorSets::Partial &pt : cs.partial.at(u)) {
+                part_colour.push_back(pt.colour);
+                part_word.push_back(bits.size());
+                bits.insert(bits.end(), pt.bits.begin(), pt.bits.end());
+            }
+        st = pf_call_set_colours(ctx_, C, cs.full_mask.data(), cs.size_total.data(), part_first.data(), part_colour.data(), part_word.data(), bits.data(),
+                                 part_colour.size(), bits.size());
+        colored_resident_ = st == PF_OK;
+    }
+}
+
+CCDBG::CCDBG(ColoredUnitigSet &graph, const size_t &complexsize, double &m, double &d, double &g, const ColorCounts &counts, int device, bool quiet)
+    : CDBG(graph.graph, complexsize, m, d, g, device, quiet, NoCounts{}, counts.ctx), cg_(graph) {
+    if (status_ || !init_colors()) return;
+    const uint32_t C = cg_.colors.n_colors;
+    if (counts.kmers.size() != C || counts.counts.size() != C || counts.n.size() != C) {
+        fail(PF_ERR_ARG, "CCDBG::CCDBG():Error: " + std::to_string(counts.n.size()) + " count arrays for " + std::to_string(C) + " colors");
+        return;
+    }
+    if (counts.k != g_.k) { fail(PF_ERR_ARG, "CCDBG::CCDBG():Error: k of the counted k-mers differs from the graph's"); return; }
+    const std::vector<uint64_t> mn(C, counts.min_count), mx(C, counts.max_count);
+    const std::vector<int> both(C, 1);
+    const int st = pf_upload_counts_colored(ctx_, C, counts.kmers.data(), counts.counts.data(), counts.n.data(), mn.data(), mx.data(), both.data());
+    if (st != PF_OK) { fail(st, std::string("CCDBG::CCDBG():Error: ") + pf_last_error(ctx_)); return; }
+    colours_to_device();
     if (!quiet_) printf("CCDBG::CCDBG():CCDBG initialized!\n");
 }
 

@@ -307,13 +307,13 @@ CDBG::CDBG(UnitigSet &graph, const size_t &complexsize, double &m, double &d, do
     if (!quiet_) printf("CDBG::CDBG():CDBG initialized!\n");
 }
 
-CDBG::CDBG(UnitigSet &graph, const size_t &complexsize, double &m, double &d, double &g, int device, bool quiet, NoCounts)
+CDBG::CDBG(UnitigSet &graph, const size_t &complexsize, double &m, double &d, double &g, int device, bool quiet, NoCounts, pf_ctx *adopt)
     : g_(graph), complex_size_(complexsize), quiet_(quiet) {
     sc_.match = m;
     sc_.mismatch = d;
     sc_.gap = g;
     tag_ = "CCDBG";
-    init_device(device, nullptr, true);
+    init_device(device, adopt, true);
 }
 
 int write_span_parallel(int fd, uint64_t file_off, const char *src, uint64_t len, unsigned threads) {

@@ -230,7 +230,8 @@ public:
 protected:
     // graph + adjacency on the device, no count database yet (the colored subclass brings its own)
     struct NoCounts {};
-    CDBG(UnitigSet &graph, const size_t &complexsize, double &m, double &d, double &g, int device, bool quiet, NoCounts);
+    // adopt: a context that exists already (`ploidyfrost run-multi`); the CDBG owns it from here
+    CDBG(UnitigSet &graph, const size_t &complexsize, double &m, double &d, double &g, int device, bool quiet, NoCounts, pf_ctx *adopt = nullptr);
     int init_device(int device, pf_ctx *adopt = nullptr, bool colored = false);
     void start_prealloc();  // the first launches' device buffers, on a helper thread (single-sample, resident pipeline)
     // the path proper; cutoff holds one (lower, upper) pair (single sample) or one per colour
@@ -413,11 +414,32 @@ struct ColoredUnitigSet {
     size_t getNbColors() const { return colors.n_colors; }
     int getK() const { return graph.k; }
     size_t size() const { return graph.n(); }
-    bool reload_colors();   // after the unitig order changed (abundant k-mers found by the device census)
+    // The same for a graph and a colour file that lie in memory (`ploidyfrost run-multi`): the GFA text as UnitigSet::open_gfa_memory
+    // takes it (K-GFA reads the DA tags with the segments), the bytes of the colour file as pf_bfg::write laid them out.  Both stay the
+    // caller's and outlive the set.  The colour sets are read by the CCDBG constructor once the device has parsed the segments
+    // (colors_pending): the reader asks for every unitig's length, head k-mer and DA tag.
+    bool open_memory(const char *host_text, uint64_t n, const char *device_text, const uint8_t *color_bytes, uint64_t n_color_bytes, size_t nb_threads = 1);
+    bool colors_pending() const { return colors_pending_; }
+    bool reload_colors();   // after the unitig order changed (abundant k-mers found by the device census), or the first time behind open_memory
 
 private:
     std::string colorfile_;
+    const uint8_t *color_bytes_ = nullptr;
+    uint64_t n_color_bytes_ = 0;
+    bool colors_pending_ = false;
     unsigned color_threads_ = 1;
+};
+
+// The count databases of a coloured run where they lie on the device already (`ploidyfrost run-multi`: every sample's finished
+// counters), instead of a list of database names: per colour the k-mers, the counters and how many, with the filters every database
+// would carry in its header.  The arrays stay the caller's; the context is adopted (CountsLoader::adopt's coloured twin).
+struct ColorCounts {
+    pf_ctx *ctx = nullptr;
+    std::vector<const uint64_t *> kmers;
+    std::vector<const uint32_t *> counts;
+    std::vector<uint64_t> n;
+    uint64_t min_count = 1, max_count = 0xFFFFFFFFull;
+    int k = 0;
 };
 
 // pfh::CCDBG -- mirror of the reference class CCDBG (src/CCDBG.hpp:18-40, driven from src/Main.cpp:775-810):
@@ -435,9 +457,15 @@ public:
     // counters of each (K-HIST); null: nothing more is launched or allocated
     CCDBG(ColoredUnitigSet &graph, const size_t &complexsize, double &m, double &d, double &g, std::string kmc_db_list = "",
           const size_t &thread = 1, int device = 0, bool quiet = false, std::vector<std::vector<uint64_t>> *rows_out = nullptr);
+    // the adopting route: graph and colours through ColoredUnitigSet::open_memory, the joined table from device arrays
+    CCDBG(ColoredUnitigSet &graph, const size_t &complexsize, double &m, double &d, double &g, const ColorCounts &counts, int device = 0,
+          bool quiet = false);
     int ploidyEstimation_multithread_ptr(const std::string &outpre, const std::vector<std::pair<int, int>> &cutoff, const size_t &thr);
 
 private:
+    // the steps of the constructors: the colour sets and the commit gate; the colour sets the calling phase asks about
+    bool init_colors();
+    void colours_to_device();
     ColoredUnitigSet &cg_;
 };
 

@@ -12,6 +12,8 @@
 #include "pf_count_host.hpp"
 #include "pf_build_host.hpp"
 #include "pf_run_host.hpp"
+#include "pf_runmulti_host.hpp"
+#include "../pf_runmulti_rule.hpp"
 #include "../pf_run_rule.hpp"
 #include "pf_bfg_write.hpp"
 #include "../pf_mask_rule.hpp"
@@ -530,6 +532,74 @@ int pfh_run_fastq(const char *const *inputs, uint32_t n_inputs, const char *out_
         g_open_err = std::string("ploidyfrost host layer: ") + e.what();
         return 1;
     }
+}
+// ---- `run-multi` (K-UNION, K-COLORSET) ----
+int pfh_run_multi_fastq(const char *const *names, const uint32_t *n_inputs_of, uint32_t n_samples, const char *const *inputs, const char *out_prefix,
+                        const pfh_run_options *o, const pf_filter_multi_opts *multi, int each_color, int device, pfh_run_multi_stats *stats,
+                        uint64_t *per_color) {
+    if (!out_prefix || !o || (n_samples && (!names || !n_inputs_of))) { g_open_err = "pfh_run_multi_fastq: samples, output prefix and options are needed"; return 1; }
+    try {
+        std::vector<pfh::MultiSample> samples(n_samples);
+        uint64_t at = 0;
+        for (uint32_t c = 0; c < n_samples; ++c) {
+            samples[c].name = names[c] ? names[c] : "";
+            for (uint32_t i = 0; i < n_inputs_of[c]; ++i, ++at) samples[c].inputs.push_back(inputs && inputs[at] ? inputs[at] : "");
+        }
+        pfh::RunMultiOptions mopt;
+        pfh::RunOptions &opt = mopt.run;
+        opt.k = o->k;
+        opt.ci = o->ci; opt.cx = o->cx; opt.cs = o->cs;
+        opt.g = o->g;
+        opt.clip_tips = o->clip_tips != 0; opt.del_isolated = o->del_isolated != 0;
+        opt.chunk_bytes = o->chunk_bytes; opt.initial_slots = o->initial_slots;
+        opt.quantile = o->quantile;
+        opt.mask_up = o->mask_up;
+        opt.complex_size = o->complex_size;
+        opt.match = o->match; opt.mismatch = o->mismatch; opt.gap = o->gap;
+        mopt.call.threads = o->threads ? o->threads : 1;
+        if (o->model_source >= 0) {
+            if (!multi) { g_open_err = "run-multi: a model reads the coloured result streams behind the options of filter-multi: multi is needed"; return 1; }
+            mopt.call.model.on = true;
+            mopt.call.model.only = o->model_only != 0;
+            mopt.call.model.source = o->model_source;
+            mopt.call.filter_multi = multi;
+            mopt.call.each_color = each_color != 0;
+        }
+        if (o->db_out) opt.db_out = o->db_out;
+        if (o->gfa_out) opt.gfa_out = o->gfa_out;
+        pfh::RunMultiStats st;
+        const int rc = pfh::run_multi_fastq(samples, out_prefix, mopt, device, st, nullptr, g_open_err);
+        if (stats)
+            *stats = pfh_run_multi_stats{st.colors, st.reads, st.bases, st.kmers, st.bad, st.distinct, st.windows_bad, st.windows_kept, st.distinct_kept,
+                                         st.graph.unitigs, st.graph.removed, st.graph.unitigs_out, st.graph.longest, st.kmers_colored, st.kmers_unplaced,
+                                         st.runs, st.overflow, st.color_bytes};
+        if (per_color)
+            for (size_t c = 0; c < st.color.size() && c < n_samples; ++c) {
+                per_color[4 * c] = st.color[c].lower;
+                per_color[4 * c + 1] = st.color[c].upper;
+                per_color[4 * c + 2] = st.color[c].distinct;
+                per_color[4 * c + 3] = st.color[c].kept;
+            }
+        return rc;
+    } catch (const std::exception &e) {
+        g_open_err = std::string("ploidyfrost host layer: ") + e.what();
+        return 1;
+    }
+}
+int pfh_union_host(const uint64_t *const *sets, const uint64_t *n, uint32_t n_sets, uint64_t *out, uint64_t *n_out) {
+    if (n_out) *n_out = 0;
+    if (!n_out || (n_sets && (!sets || !n))) { g_open_err = "pfh_union_host: sets, n and n_out are needed"; return 1; }
+    std::vector<std::vector<uint64_t>> v(n_sets);
+    for (uint32_t c = 0; c < n_sets; ++c) {
+        const std::string why = pf_runmulti::set_refusal(sets[c], n[c], c);
+        if (!why.empty()) { g_open_err = "pfh_union_host: " + why; return 1; }
+        v[c].assign(sets[c], sets[c] + n[c]);
+    }
+    const std::vector<uint64_t> u = pf_runmulti::union_host(std::move(v));
+    if (!u.empty() && !out) { g_open_err = "pfh_union_host: out is needed"; return 1; }
+    std::copy(u.begin(), u.end(), out);
+    *n_out = u.size();
+    return 0;
 }
 int pfh_count_masked_host(const char *text, const uint64_t *off, const uint32_t *len, uint64_t n_reads, uint32_t k, const uint32_t *counters,
                           uint32_t low, uint32_t up, uint64_t *kmers_out, uint32_t *counts_out, uint64_t cap, uint64_t *n, uint64_t stats_out[6]) {

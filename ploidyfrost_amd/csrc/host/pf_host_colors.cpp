@@ -222,6 +222,16 @@ bool ColorSets::contains(uint32_t u, uint32_t colour, uint32_t dist, uint32_t le
 bool ColorSets::load(const std::string &path, const UnitigSet &g, unsigned threads, std::string &err) {
     std::vector<uint8_t> buf;
     if (!read_file(path, buf)) { err = "DataStorage::read(): Could not open file " + path + " for reading color sets"; return false; }
+    return load_bytes(buf.data(), buf.size(), g, threads, err);
+}
+
+bool ColorSets::load_bytes(const uint8_t *bytes, size_t n_bytes, const UnitigSet &g, unsigned threads, std::string &err) {
+    struct Span {   // the bytes of the file, wherever they lie
+        const uint8_t *p;
+        size_t n;
+        const uint8_t *data() const { return p; }
+        size_t size() const { return n; }
+    } buf{bytes, n_bytes};
     Reader r{buf.data(), buf.data() + buf.size()};
     // header, DataStorage.tcc:831-862
     const uint64_t format_version = r.get<uint64_t>(), nb_seeds = r.get<uint64_t>(), nb_colors = r.get<uint64_t>(),

@@ -39,6 +39,8 @@ struct ColorSets {
 
     // threads: worker threads for decoding (the result does not depend on it)
     bool load(const std::string &path, const UnitigSet &g, unsigned threads, std::string &err);
+    // the same reader over the bytes of a colour file that lie in memory (`ploidyfrost run-multi`: what pf_bfg::write laid out)
+    bool load_bytes(const uint8_t *bytes, size_t n_bytes, const UnitigSet &g, unsigned threads, std::string &err);
 
     // UnitigColors::contains(um, colour): colour on every k-mer of [dist, dist + len)
     bool contains(uint32_t u, uint32_t colour, uint32_t dist, uint32_t len) const;

@@ -36,6 +36,7 @@
 #include "pf_build_host.hpp"
 #include "pf_mask_host.hpp"
 #include "pf_run_host.hpp"
+#include "pf_runmulti_host.hpp"
 #include "pf_trim_host.hpp"
 #include "../pf_trim_rule.hpp"
 #include "pf_filter.hpp"
@@ -111,6 +112,11 @@ void PrintUsage() {
          << "                  [--chunk-bytes N] [--initial-slots N] [-v]" << endl
          << "                  (reads to ploidy estimate in one process: `mask -k ... --auto-cutoffs`, `build -i -d` and the calling run with --auto-cutoffs on" << endl
          << "                  one device context, no masked reads, database or graph file in between; L is printed on stdout)" << endl << endl
+         << "Usage: PloidyFrost run-multi [-k 25 -ci 1 -cs 10000 -cx N] --sample <NAME> -i <a.fq> [-i <b.fq> ...] --sample <NAME2> -i <c.fq> [...] -o <out> [-q Q] [-u U]" << endl
+         << "                  [--keep-tips] [--keep-isolated] [-g G] [-z -M -D -G -t --ref-threads] [--model cov|fre --filter-multi \"OPTS\" [--model-each-color] [--density ...] [--model-only]]" << endl
+         << "                  [--db-out <KMCDatabase>] [--gfa-out <graph>] [--chunk-bytes N] [--initial-slots N] [-v]" << endl
+         << "                  (reads of several samples to one estimate per sample in one process: `mask -k ... --auto-cutoffs` per sample, `build-multi -i -d`" << endl
+         << "                  and the coloured calling run with --auto-cutoffs on one device context; a sample is a colour, in the order given; every L on stdout)" << endl << endl
          << "Usage: PloidyFrost model ...          (GMM ploidy inference from the coverage / frequency files; `PloidyFrost model` prints its options)" << endl
          << "Usage: PloidyFrost density -f <column file> -o <outfile_prefix> [-n points] [-a adjust]   (kernel density of a column of numbers)" << endl
          << "Usage: PloidyFrost filter ...         (the row predicates of script/Filter.R over <prefix>_*cov.txt; -h prints its options)" << endl
@@ -988,8 +994,146 @@ int run_main(int argc, char **argv) {
     return 0;
 }
 
+// `run-multi`: the multi-sample workflow (script/pipeline/run-multisample.sh) behind the trimmed reads in one process and on one device
+// context; `run`'s letters, with --sample NAME in front of every sample's -i and the coloured run's --filter-multi / --model-each-color
+int run_multi_main(int argc, char **argv) {
+    const char *usage = "Usage:PloidyFrost run-multi [-k 25] [-ci 1] [-cs 10000] [-cx N] --sample NAME -i a.fq [-i b.fq ...] --sample NAME2 -i c.fq [...] -o out\n"
+                        "                 [-q Q] [-u U] [--keep-tips] [--keep-isolated] [-g G] [-z Z -M m -D d -G g -t T --ref-threads N]\n"
+                        "                 [--model cov|fre --filter-multi \"OPTS\" [--model-each-color] [--density ...] [--model-only]]\n"
+                        "                 [--db-out <KMCDatabase>] [--gfa-out <graph>] [--chunk-bytes N] [--initial-slots N] [-v]";
+    auto refuse = [&](const string &why) { cerr << "Error: run-multi: " << why << endl << usage << endl; return 1; };
+    Options lopt;   // the long options of the calling run
+    DensityCli dc;
+    if (!take_long_options(argc, argv, 2, lopt, dc)) return 1;
+    pfh::RunMultiOptions mopt;
+    pfh::RunOptions &opt = mopt.run;
+    CountArgs c;
+    c.opt.ci = opt.ci;
+    c.opt.cx = opt.cx;
+    c.opt.cs = opt.cs;
+    string out;
+    vector<pfh::MultiSample> samples;
+    bool verbose = false;
+    size_t threads = 1;
+    auto number = [&](const string &o, const char *text, uint64_t &v, bool positive) {
+        char *end = nullptr;
+        errno = 0;
+        v = strtoull(text, &end, 10);
+        if (!errno && isdigit((unsigned char)text[0]) && !*end && (v > 0 || !positive)) return true;
+        refuse(o + " takes a " + (positive ? "positive " : "") + "number, not '" + text + "'");
+        return false;
+    };
+    auto real = [&](const string &o, const char *text, double &v) {
+        char *end = nullptr;
+        v = strtod(text, &end);
+        if (end != text && !*end && std::isfinite(v)) return true;
+        refuse(o + " takes a number, not '" + text + "'");
+        return false;
+    };
+    static const struct { const char *name, *why; } not_here[] = {
+        {"-f", "-f does not go with run-multi: the colour file is made from the samples (--gfa-out writes it)"},
+        {"-C", "-C does not go with run-multi: the thresholds come from every sample's counted k-mers (no coverage file)"},
+        {"-d", "-d does not go with run-multi: the databases are counted from the reads (--db-out writes them; isolated unitigs are removed unless --keep-isolated)"},
+        {"-h", "-h does not go with run-multi: the thresholds come from every sample's counted k-mers, not from histogram files"},
+        {"-l", "-l does not go with run-multi: the lower thresholds are derived from the counted k-mers (as --auto-cutoffs derives them)"},
+        {"-b", "-b does not go with run-multi: the graph is built from both strands"},
+        {"--filtered-out", "--filtered-out is not built: the masked reads are never made (`mask` writes them)"},
+        {"--detach-teardown", "--detach-teardown is not built into run-multi"},
+    };
+    if (lopt.gpus_seen) return refuse("--gpus is not built into run-multi: the coloured path runs on one GPU");
+    if (lopt.filter_seen) return refuse("--filter reads the single-sample result streams: run-multi has --filter-multi");
+    if (lopt.detach_teardown) return refuse(not_here[7].why);
+    for (int i = 2; i < argc; ++i) {
+        const string a = argv[i];
+        for (const auto &nh : not_here)
+            if (a == nh.name) return refuse(nh.why);
+        {
+            string why;
+            const int taken = take_count_option(argc, argv, i, c, why);
+            if (taken < 0) return refuse(why);
+            if (taken) continue;
+        }
+        if (a == "-v") { verbose = true; continue; }
+        if (a == "--keep-tips") { opt.clip_tips = false; continue; }
+        if (a == "--keep-isolated") { opt.del_isolated = false; continue; }
+        const bool takes_value = a == "--sample" || a == "-i" || a == "-o" || a == "-q" || a == "-u" || a == "-g" || a == "-z" || a == "-M" || a == "-D" || a == "-G" ||
+                                 a == "-t" || a == "--db-out" || a == "--gfa-out" || a == "--chunk-bytes" || a == "--initial-slots";
+        if (!takes_value) return refuse("unknown option " + a);
+        if (i + 1 >= argc) return refuse(a + " needs a value");
+        const char *val = argv[++i];
+        uint64_t v = 0;
+        if (a == "--sample") { samples.emplace_back(); samples.back().name = val; }
+        else if (a == "-i") {
+            if (samples.empty()) return refuse(string("-i ") + val + " stands before any --sample NAME: every input belongs to a sample");
+            samples.back().inputs.push_back(val);
+        }
+        else if (a == "-o") out = val;
+        else if (a == "--db-out") opt.db_out = val;
+        else if (a == "--gfa-out") opt.gfa_out = val;
+        else if (a == "-q") { if (!real(a, val, opt.quantile)) return 1; }
+        else if (a == "-M") { if (!real(a, val, opt.match)) return 1; }
+        else if (a == "-D") { if (!real(a, val, opt.mismatch)) return 1; }
+        else if (a == "-G") { if (!real(a, val, opt.gap)) return 1; }
+        else if (a == "-u") { if (!number(a, val, v, false)) return 1; if (v > 0xFFFFFFFFull) return refuse("-u takes a number from 0 to 4294967295, not '" + string(val) + "'"); opt.mask_up = (uint32_t)v; }
+        else if (!number(a, val, v, true)) return 1;
+        else if (a == "-g") opt.g = (int)std::min<uint64_t>(v, 0x7FFFFFFFull);
+        else if (a == "-z") opt.complex_size = (size_t)v;
+        else if (a == "-t") threads = (size_t)v;
+        else if (a == "--chunk-bytes") opt.chunk_bytes = v;
+        else if (a == "--initial-slots") opt.initial_slots = v;
+    }
+    // refused by name, before anything is read or written and before a device context exists
+    { const string why = pfh::run_multi_samples_refusal(samples); if (!why.empty()) return refuse(why); }
+    if (out.empty()) return refuse("-o <out> is missing");
+    opt.k = c.opt.k;
+    opt.ci = c.opt.ci;
+    opt.cx = c.opt.cx;
+    opt.cs = c.opt.cs;
+    { const string why = pfh::run_options_refusal(opt); if (!why.empty()) return refuse(why); }
+    if (opt.quantile < 0 || opt.quantile > 1) return refuse("-q: frequency cutoff value should be between 0 and 1");
+    if (opt.complex_size < 4) return refuse("-z: Maximum number of unitigs in superbubble is at least 4 !");
+    if (opt.mismatch > opt.match) return refuse("-D: Mismatch penalty should be smaller than match score !");
+    if (opt.gap > opt.match) return refuse("-G: Gap penalty should be smaller than match score !");
+    if (threads > std::thread::hardware_concurrency()) return refuse("-t: Number of threads cannot be greater than " + to_string(std::thread::hardware_concurrency()));
+    pf_filter_opts filter = {};
+    pf_filter_multi_opts multi = {};
+    lopt.colorfile = "run-multi";   // (the coloured run's rules for --model / --filter-multi: the colour file is made here)
+    if (!model_setup(lopt, dc, mopt.call.model, filter, multi)) return 1;
+    // (--ref-threads is taken and changes nothing, as in the coloured calling run: it writes the `-t 1` text format alone)
+    mopt.call.threads = threads;
+    mopt.call.verbose = verbose;
+    mopt.call.filter_multi = lopt.multi_seen ? &multi : nullptr;
+    mopt.call.each_color = lopt.each_color;
+    mopt.call.density_points = dc.on ? dc.points : 0;
+    mopt.call.density_adjust = dc.adjust;
+    pfh::RunMultiStats st;
+    pfh::RunMultiTimes tm;
+    string err;
+    if (pfh::run_multi_fastq(samples, out, mopt, 0, st, &tm, err)) {
+        cout.flush();
+        fflush(nullptr);
+        // (what the chain's last command says on stdout is said there; its own refusals carry their "Error:" already)
+        if (err.rfind("ColoredCDBG::read()", 0) == 0) cout << err << endl;
+        else if (err.rfind("run-multi: ", 0) == 0) cerr << "Error: " << err << endl;
+        else cerr << err << endl;
+        return EXIT_FAILURE;
+    }
+    cerr << "run-multi: colors " << st.colors << " reads " << st.reads << " bases " << st.bases << " kmers " << st.kmers << " bad " << st.bad << " distinct "
+         << st.distinct << " windows_bad " << st.windows_bad << " windows_kept " << st.windows_kept << " distinct_kept " << st.distinct_kept << " unitigs "
+         << st.graph.unitigs << " removed " << st.graph.removed << " unitigs_out " << st.graph.unitigs_out << " longest " << st.graph.longest << " kmers_colored "
+         << st.kmers_colored << " kmers_unplaced " << st.kmers_unplaced << " runs " << st.runs << " overflow " << st.overflow << " color_bytes " << st.color_bytes << endl;
+    for (size_t i = 0; i < st.color.size(); ++i)
+        cerr << "run-multi: color " << i << " lower " << st.color[i].lower << " upper " << st.color[i].upper << " distinct " << st.color[i].distinct << " kept "
+             << st.color[i].kept << endl;
+    if (verbose)
+        cerr << "run-multi: count " << tm.count_s << "s db-out " << tm.db_out_s << "s recount " << tm.recount_s << "s union " << tm.union_s << "s graph " << tm.graph_s
+             << "s color " << tm.color_s << "s serialise " << tm.serialise_s << "s gfa-out " << tm.gfa_out_s << "s load " << tm.load_s << "s call " << tm.call_s << "s" << endl;
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) { PrintUsage(); return 0; }
+    if (!strcmp(argv[1], "run-multi")) return run_multi_main(argc, argv);
     if (!strcmp(argv[1], "run")) return run_main(argc, argv);
     if (!strcmp(argv[1], "model")) return model_main(argc, argv);
     if (!strcmp(argv[1], "density")) return density_main(argc - 1, argv + 1);
@@ -1316,37 +1460,24 @@ int calling_main(Options &opt, DensityCli &dc) {
             exit(EXIT_FAILURE);
         };
         if (!g.good()) die();
-        if (opt.auto_cutoffs) {   // one (lower, upper) per colour from its own database, as -h derives them from one file per colour (:359-396)
-            for (size_t c = 0; c < color_rows.size() && c < opt.coverage_vec.size(); c++) {
-                opt.coverage_vec[c] = {max(10, cutoffL(color_rows[c])), cutoffH(color_rows[c], opt.frequency)};
-                if (opt.coverage_vec[c].first > opt.coverage_vec[c].second) { cerr << "Error: lower cutoff need be smaller than upper cutoff " << endl; exit(EXIT_FAILURE); }
-            }
-        }
-        g.set_threads((unsigned)opt.nb_threads);
-        g.set_overlap_output(true);
-        if (model.on && g.set_model(model)) die();
-        if (opt.multi_seen && g.set_filter_multi(&multi, opt.each_color)) die();
-        if (dc.on && g.set_density(dc.points, dc.adjust)) die();
-        if (g.setUnitigId(opt.outprefix, opt.graphfile, opt.nb_threads)) die();
-        if (opt.info && g.printInfo(opt.verbose, opt.outprefix)) die();
-        if (g.findSuperBubble_multithread_ptr(opt.outprefix, opt.nb_threads)) die();
-        for (size_t i = 0; i < opt.coverage_vec.size(); i++) {
-            cout << "CCDBG:: Database " << i << " Minimum Coverage:" << opt.coverage_vec[i].first << endl;
-            cout << "CCDBG:: Maximum Coverage:" << opt.coverage_vec[i].second << endl;
-        }
-        if (g.ploidyEstimation_multithread_ptr(opt.outprefix, opt.coverage_vec, opt.nb_threads)) die();
-        if (model.on && opt.each_color) {
-            for (int c : g.model_colors_without_rows()) cerr << "color " << c << ": no row kept, no estimate" << endl;
-            for (int c : g.model_colors_without_values()) cerr << "color " << c << ": the rows kept hold no value for the model, no estimate" << endl;
-            for (const pfh::CDBG::ColorFit &cf : g.model_color_fits()) cout << "color " << cf.color << ": estimated ploidy level is : " << cf.ploidy << endl;
-            for (int c : g.model_colors_without_density()) cerr << "color " << c << ": need at least 2 data points, no density" << endl;
-        } else if (model.on) cout << g.model_last_line() << endl;
-        if (opt.verbose) {
-            const pfh::PhaseTimes &t = g.times();
-            printf("[device] candidates %llu  bfs %.3fs replay %.3fs | cov %.3fs tasks %.3fs (%llu) align %.3fs (%llu jobs) "
-                   "sites %.3fs (%llu strings) format %.3fs write %.3fs\n",
-                   (unsigned long long)t.candidates, t.bfs_device_s, t.replay_s, t.cov_device_s, t.tasks_s, (unsigned long long)t.tasks,
-                   t.align_s, (unsigned long long)t.align_jobs, t.sites_s, (unsigned long long)t.site_strings, t.format_s, t.write_s);
+        pfh::ColoredCallSetup call;
+        call.outprefix = opt.outprefix;
+        call.graphfile = opt.graphfile;
+        call.threads = opt.nb_threads;
+        call.info = opt.info;
+        call.verbose = opt.verbose;
+        call.model = model;
+        call.filter_multi = opt.multi_seen ? &multi : nullptr;
+        call.each_color = opt.each_color;
+        call.density_points = dc.on ? dc.points : 0;
+        call.density_adjust = dc.adjust;
+        call.cutoffs = opt.coverage_vec;
+        call.color_rows = opt.auto_cutoffs ? &color_rows : nullptr;
+        call.quantile = opt.frequency;
+        string call_err;
+        if (pfh::colored_call_run(g, call, call_err)) {
+            cerr << call_err << endl;
+            exit(EXIT_FAILURE);
         }
         return 0;
     }

@@ -86,6 +86,49 @@ int call_run(CDBG &g, const CallSetup &s, const std::function<void(const char *)
     return 0;
 }
 
+// ---- the coloured calling run behind a loaded CCDBG ----
+int colored_call_run(CCDBG &g, ColoredCallSetup &s, std::string &err) {
+    using std::cerr;
+    using std::cout;
+    using std::endl;
+    if (s.color_rows) {   // one (lower, upper) per colour from its own database, as -h derives them from one file per colour (src/Main.cpp:359-396)
+        for (size_t c = 0; c < s.color_rows->size() && c < s.cutoffs.size(); c++) {
+            int lo = 0, hi = 0;
+            if (cutoffs_from_rows((*s.color_rows)[c], s.quantile, lo, hi)) { err = "Error: Histogram File is badly Formatted."; return 1; }
+            s.cutoffs[c] = {std::max(10, lo), hi};
+            if (s.cutoffs[c].first > s.cutoffs[c].second) { err = "Error: lower cutoff need be smaller than upper cutoff "; return 1; }
+        }
+    }
+    auto bad = [&]() { err = g.error(); return 1; };
+    g.set_threads((unsigned)s.threads);
+    g.set_overlap_output(true);
+    if (s.model.on && g.set_model(s.model)) return bad();
+    if (s.filter_multi && g.set_filter_multi(s.filter_multi, s.each_color)) return bad();
+    if (s.density_points && g.set_density(s.density_points, s.density_adjust)) return bad();
+    if (g.setUnitigId(s.outprefix, s.graphfile, s.threads)) return bad();
+    if (s.info && g.printInfo(s.verbose, s.outprefix)) return bad();
+    if (g.findSuperBubble_multithread_ptr(s.outprefix, s.threads)) return bad();
+    for (size_t i = 0; i < s.cutoffs.size(); i++) {
+        cout << "CCDBG:: Database " << i << " Minimum Coverage:" << s.cutoffs[i].first << endl;
+        cout << "CCDBG:: Maximum Coverage:" << s.cutoffs[i].second << endl;
+    }
+    if (g.ploidyEstimation_multithread_ptr(s.outprefix, s.cutoffs, s.threads)) return bad();
+    if (s.model.on && s.each_color) {
+        for (int c : g.model_colors_without_rows()) cerr << "color " << c << ": no row kept, no estimate" << endl;
+        for (int c : g.model_colors_without_values()) cerr << "color " << c << ": the rows kept hold no value for the model, no estimate" << endl;
+        for (const CDBG::ColorFit &cf : g.model_color_fits()) cout << "color " << cf.color << ": estimated ploidy level is : " << cf.ploidy << endl;
+        for (int c : g.model_colors_without_density()) cerr << "color " << c << ": need at least 2 data points, no density" << endl;
+    } else if (s.model.on) cout << g.model_last_line() << endl;
+    if (s.verbose) {
+        const PhaseTimes &t = g.times();
+        printf("[device] candidates %llu  bfs %.3fs replay %.3fs | cov %.3fs tasks %.3fs (%llu) align %.3fs (%llu jobs) "
+               "sites %.3fs (%llu strings) format %.3fs write %.3fs\n",
+               (unsigned long long)t.candidates, t.bfs_device_s, t.replay_s, t.cov_device_s, t.tasks_s, (unsigned long long)t.tasks,
+               t.align_s, (unsigned long long)t.align_jobs, t.sites_s, (unsigned long long)t.site_strings, t.format_s, t.write_s);
+    }
+    return 0;
+}
+
 // ---- run ----
 std::string run_options_refusal(const RunOptions &opt) {
     { const int c = count_options_clause(count_options_of(opt), true); if (c) return pf_count::cut_text(c); }

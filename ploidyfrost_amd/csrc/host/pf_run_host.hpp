@@ -43,6 +43,27 @@ int call_configure(CDBG &g, const CallSetup &s);
 // name of every finished phase.  0 = ok, else g.error()
 int call_run(CDBG &g, const CallSetup &s, const std::function<void(const char *)> &mark = nullptr);
 
+// ---- the coloured calling run behind a loaded CCDBG, as the command line sets it up (`ploidyfrost -g -f -d` and `run-multi`) ----
+struct ColoredCallSetup {
+    std::string outprefix = "output", graphfile;
+    size_t threads = 1;
+    bool info = false, verbose = false;
+    CDBG::ModelOptions model;                            // --model ...
+    const pf_filter_multi_opts *filter_multi = nullptr;  // --filter-multi "...": null = none
+    bool each_color = false;                             // --model-each-color
+    unsigned density_points = 0;                         // --density: 0 = off
+    double density_adjust = 1.0;
+    std::vector<std::pair<int, int>> cutoffs;            // one (lower, upper) per colour
+    // --auto-cutoffs: the histogram rows of every colour's counters; the pairs are derived from them (max(10, cutoffL), cutoffU(q))
+    const std::vector<std::vector<uint64_t>> *color_rows = nullptr;
+    double quantile = 0.998;
+};
+// Thresholds per colour, host threads and overlapped output, model, filter-multi and density settings, setUnitigId, printInfo,
+// findSuperBubble, the "Database i Minimum Coverage" lines, PloidyEstimation, the model's last line or the per-colour lines, with
+// `verbose` the phase times -- on stdout / stderr, as `ploidyfrost -g -f -d` prints them.  s.cutoffs holds the pairs used afterwards.
+// 0 = ok, else err holds the line for stderr.
+int colored_call_run(CCDBG &g, ColoredCallSetup &s, std::string &err);
+
 // ---- run ----
 struct RunOptions {
     // the count (the workflow's defaults, not kmc's) and the graph (tips clipped, isolated unitigs removed)

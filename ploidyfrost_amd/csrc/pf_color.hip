@@ -14,6 +14,8 @@
 //           read costs one redundant atomic and nothing else (or is idempotent).  The colour is a kernel argument: it changes with the
 //           file, not with the chunk.  Hits, misses and bad windows are summed per lane and per wavefront before one atomic each when the
 //           kernel ends.  The probe loop is bounded by the slot count and flags at its bound.                 1 probe, <= 1 atomic
+//   keys    k_col_keys (K-COLORSET, pf_color_kmers): the same marking from the distinct canonical k-mers of a colour's reads instead of
+//           from the reads (pf_runmulti_rule.hpp) -- one key a lane, no text, no tile, no bitmaps.                  1 probe, <= 1 atomic a key
 //   runs    k_col_runs, twice (count, scan, write).  One 16-lane row per unitig; its id space c * m + p is walked 512 ids a step, 32 ids a
 //           lane, gathered from the planes of the colours the 32 ids span, so ids of adjacent colours merge by themselves.  A run begins
 //           at a set id behind a clear one and ends at a set id before a clear one; begins and ends are numbered by a prefix sum over
@@ -161,6 +163,33 @@ __global__ __launch_bounds__(MASK_BLOCK) void k_col_mark(const ColMarkArgs a) {
         if (n_bad) atomicAdd(&a.c->kmers_bad, (unsigned long long)n_bad);
     }
     if (stuck) a.d->stuck = 1u;
+}
+
+// ---- mark from keys (K-COLORSET) ----
+// The distinct canonical k-mers of a colour's reads instead of the reads (pf_runmulti_rule.hpp): one key a lane, consecutive lanes
+// consecutive keys (coalesced 8-byte loads), one probe of the table, the plane word loaded and the atomicOr issued only where the bit
+// is clear, as k_col_mark does.  Hits and misses are summed per lane and per wavefront before one atomic each.
+__global__ __launch_bounds__(256) void k_col_keys(const ColSlot *__restrict__ tab, uint64_t mask, uint32_t *plane, const uint64_t *__restrict__ keys,
+                                                  uint64_t n, ColDev *d) {
+    uint64_t hits = 0, misses = 0;
+    bool stuck = false;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+        const uint32_t flat = col_find(tab, mask, keys[i], stuck);
+        if (flat == COL_NONE) misses += 1;
+        else {
+            hits += 1;
+            uint32_t *w = plane + (flat >> 5);
+            const uint32_t bit = 1u << (flat & 31u);
+            if (!(__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit)) atomicOr(w, bit);
+        }
+    }
+    hits = wave_sum_u64(hits);
+    misses = wave_sum_u64(misses);
+    if ((threadIdx.x & 63) == 0) {
+        if (hits) atomicAdd(&d->hits, (unsigned long long)hits);
+        if (misses) atomicAdd(&d->misses, (unsigned long long)misses);
+    }
+    if (stuck) d->stuck = 1u;
 }
 
 // ---- runs ----
@@ -457,6 +486,39 @@ extern "C" int pf_color_fastq(pf_ctx *ctx, uint32_t colour, const char *text, ui
     }
     *bytes_used = ix.used;
     color_stats_out(stats, C, ix.n_rec, h, d);
+    return PF_OK;
+}
+
+extern "C" int pf_color_kmers(pf_ctx *ctx, uint32_t colour, const uint64_t *kmers_dev, uint64_t n, pf_color_kmers_stats *stats) {
+    if (!ctx) return PF_ERR_ARG;
+    auto refuse = [&](const std::string &m) { pf::CtxErr{ctx} = m; return (int)PF_ERR_ARG; };
+    { const int rc = col_needs_begin(ctx, "pf_color_kmers", true); if (rc) return rc; }
+    ColorState *C = col_state(ctx);
+    if (colour >= C->n_colors) return refuse("pf_color_kmers: colour " + std::to_string(colour) + " of " + std::to_string(C->n_colors));
+    if (n && !kmers_dev) return refuse("pf_color_kmers: kmers_dev is needed");
+    if (n && (!is_device_ptr(kmers_dev) || ((uintptr_t)kmers_dev & 7))) return refuse("pf_color_kmers: kmers_dev is not an aligned array on the device");
+    if (n >= (1ull << 40)) return refuse("pf_color_kmers: more than 2^40 keys");
+    pf_color_kmers_stats st = {};
+    st.kmers = n;
+    if (n) {
+        PF_HIP(hipSetDevice(ctx->device));
+        ColDev d = {};
+        ctx_begin(ctx, PF_K_COLORSET);
+        ColEvents ev(ctx->stream);
+        PF_HIP(hipMemsetAsync(C->dev, 0, sizeof(ColDev), ctx->stream));
+        k_col_keys<<<ctx_grid(ctx, n, 256, 8), 256, 0, ctx->stream>>>(C->tab, C->slots - 1, C->planes + (uint64_t)colour * C->words, kmers_dev, n, C->dev);
+        const hipError_t le = hipGetLastError();
+        ctx_end(ctx);
+        if (le != hipSuccess) { pf::CtxErr{ctx} = std::string("K-COLORSET launch: ") + hipGetErrorString(le); return PF_ERR_HIP; }
+        PF_HIP(hipMemcpyAsync(&d, C->dev, sizeof d, hipMemcpyDeviceToHost, ctx->stream));
+        PF_HIP(hipStreamSynchronize(ctx->stream));
+        C->total.mark_ms += ev.ms();
+        ctx_units(ctx, PF_K_COLORSET, n);
+        if (d.stuck) { pf::CtxErr{ctx} = "K-COLORSET: a probe went round the whole table"; return PF_ERR_HIP; }
+        st.kmers_colored = d.hits;
+        st.kmers_unplaced = d.misses;
+    }
+    if (stats) *stats = st;
     return PF_OK;
 }
 

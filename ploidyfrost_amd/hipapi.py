@@ -37,6 +37,11 @@ TRIM_STATS = np.dtype([(f, "<u8") for f in ("reads", "kept", "dropped", "bases",
 K_UNITIG = K_TRIM + 1      # PF_K_UNITIG ("k_unitig"): everything one pf_unitig_build launches; unit: k-mers
 K_MASKCOUNT = K_UNITIG + 1   # PF_K_MASKCOUNT ("k_maskcount"): everything one pf_maskcount_reads / pf_maskcount_fastq launches; unit: windows
 MASKCOUNT_STATS = np.dtype([(f, "<u8") for f in ("reads", "bases", "kmers", "kmers_invalid", "kmers_bad", "kmers_kept")])   # pf_maskcount_stats
+K_UNION = K_MASKCOUNT + 1    # PF_K_UNION ("k_union"): everything one pf_kmer_union launches; unit: keys given
+K_COLORSET = K_UNION + 1     # PF_K_COLORSET ("k_colorset"): the kernel of one pf_color_kmers; unit: keys
+UNION_TILE = 1024            # pf_runmulti::UNION_TILE: merged positions a block of K-UNION takes
+UNION_ITEMS = 4              # pf_runmulti::UNION_ITEMS: ... and a lane
+COLOR_KMERS_STATS = np.dtype([(f, "<u8") for f in ("kmers", "kmers_colored", "kmers_unplaced")])   # pf_color_kmers_stats
 UNITIG_G_DEFAULT = 0xFFFFFFFF   # PF_UNITIG_G_DEFAULT: Bifrost's default for k
 COLOR_SEEDS = 31                # pf_color::DEFAULT_SEEDS: placement rounds of a colour file
 COLOR_STATS = np.dtype([(f, "<u8") for f in ("colors", "reads", "windows_colored", "windows_unplaced", "windows_bad", "runs", "overflow", "lines",
@@ -234,6 +239,9 @@ def load_library() -> C.CDLL:
         "pf_color_reads": (i, [vp, u32, vp, u64, vp, vp, u64, vp]),
         "pf_color_fastq": (i, [vp, u32, vp, u64, i, C.POINTER(u64), vp, C.POINTER(u64)]),
         "pf_color_finish": (i, [vp, vp]),
+        "pf_color_kmers": (i, [vp, u32, vp, u64, vp]),
+        "pf_release_counts": (i, [vp]),
+        "pf_kmer_union": (i, [vp, u32, vp, vp, C.POINTER(vp), C.POINTER(u64)]),
         "pf_color_fetch": (i, [vp, vp, vp, vp, vp, vp]),
         "pf_trim_fastq": (i, [vp, vp, u64, i, vp, u32, u32, vp, C.POINTER(u64), C.POINTER(u64), vp, vp, C.POINTER(u64), vp, C.POINTER(u64)]),
         "pf_trim_fastq_pair": (i, [vp, vp, u64, vp, u64, i, vp, u32, u32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(vp), C.POINTER(vp),
@@ -263,7 +271,8 @@ DECLARED_SYMBOLS = ["pf_create", "pf_warmup", "pf_destroy", "pf_last_error", "pf
                     "pf_count_begin", "pf_count_reads", "pf_count_fastq", "pf_count_finish", "pf_count_abort", "pf_kmc_encode",
                     "pf_trim_fastq", "pf_trim_fastq_pair", "pf_unitig_build", "pf_unitig_fetch", "pf_unitig_release",
                     "pf_unitig_build_colored", "pf_color_begin", "pf_color_reads", "pf_color_fastq", "pf_color_finish", "pf_color_fetch",
-                    "pf_maskcount_reads", "pf_maskcount_fastq", "pf_unitig_text"]
+                    "pf_maskcount_reads", "pf_maskcount_fastq", "pf_unitig_text",
+                    "pf_kmer_union", "pf_color_kmers", "pf_release_counts"]
 
 
 def trim_steps(steps) -> np.ndarray:
@@ -783,6 +792,39 @@ class Device:
             e.bad_record = bad.value
             raise e
         return used.value, {f: stats[0][f].item() for f in COLOR_STATS.names}
+
+    def _keys_on_device(self, a):
+        """a numpy array of 64-bit keys as a device tensor (a device tensor stays what it is)"""
+        if not isinstance(a, (list, tuple, np.ndarray)):
+            return a
+        import torch
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        return torch.from_numpy(a.view(np.int64).copy()).to("cuda")
+
+    def kmer_union(self, arrays):
+        """K-UNION (pf_kmer_union): the sorted distinct union (numpy u64) of sorted distinct arrays of 64-bit keys -- numpy arrays, which
+        are copied to the device first, or device tensors.  An array that is not ascending or holds a key twice raises DeviceError."""
+        dev = [self._keys_on_device(a) for a in arrays]
+        ns = np.array([int(d.shape[0]) for d in dev], dtype=np.uint64)
+        ptrs = np.array([_ptr(d) if int(d.shape[0]) else 0 for d in dev], dtype=np.uint64)
+        out, n = C.c_void_p(), C.c_uint64()
+        self._check(self.L.pf_kmer_union(self.h, len(dev), _ptr(ptrs) if len(dev) else None, _ptr(ns) if len(dev) else None, C.byref(out), C.byref(n)))
+        res = np.zeros(n.value, dtype=np.uint64)
+        try:
+            if n.value:
+                self._check(self.L.pf_copy_to_host(self.h, _ptr(res), out, n.value * 8))
+        finally:
+            self.L.pf_device_free(self.h, out)
+        return res
+
+    def color_kmers(self, colour: int, kmers):
+        """K-COLORSET (pf_color_kmers): colours with `colour` the graph k-mers among `kmers`, the distinct canonical k-mers of that
+        colour's reads (a numpy array, copied to the device first, or a device tensor); returns this call's statistics."""
+        dev = self._keys_on_device(kmers)
+        n = int(dev.shape[0])
+        stats = np.zeros(1, dtype=COLOR_KMERS_STATS)
+        self._check(self.L.pf_color_kmers(self.h, int(colour), _ptr(dev) if n else None, n, stats.ctypes.data))
+        return {f: int(stats[0][f]) for f in COLOR_KMERS_STATS.names}
 
     def color_finish(self):
         """pf_color_finish and pf_color_fetch: (statistics of the whole colouring, what leaves the device: per line `heads` u64, `m` u32,

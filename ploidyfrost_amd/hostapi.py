@@ -44,7 +44,7 @@ DECLARED_SYMBOLS = ["pfh_open", "pfh_close", "pfh_last_error", "pfh_set_output_d
                     "pfh_count_fastq", "pfh_mask_fastq_counted", "pfh_count_reads_host", "pfh_count_encode_kmc1", "pfh_count_counter_bytes",
                     "pfh_count_lut_prefix_len", "pfh_count_cut_text", "pfh_build_fastq", "pfh_unitig_build_host", "pfh_unitig_no_room_text",
                     "pfh_build_colored_fastq", "pfh_build_colored_host", "pfh_bfg_colors_bytes", "pfh_color_no_room_text",
-                    "pfh_run_defaults", "pfh_run_fastq", "pfh_count_masked_host",
+                    "pfh_run_defaults", "pfh_run_fastq", "pfh_count_masked_host", "pfh_run_multi_fastq", "pfh_union_host",
                     "pfh_trim_fastq", "pfh_trim_fastq_pair", "pfh_trim_parse_step", "pfh_trim_refusal_text", "pfh_trim_read", "pfh_trim_fastq_chunk"]
 
 
@@ -57,6 +57,9 @@ class RunOptions(C.Structure):   # pfh_run_options (include/ploidyfrost_host.h)
 
 RUN_STATS_FIELDS = ("reads", "bases", "kmers", "bad", "distinct", "lower", "upper", "windows_bad", "windows_kept", "distinct_kept", "unitigs",
                     "removed", "unitigs_out", "longest")   # pfh_run_stats: the fields of `run`'s stderr line, in its order
+RUN_MULTI_STATS_FIELDS = ("colors", "reads", "bases", "kmers", "bad", "distinct", "windows_bad", "windows_kept", "distinct_kept", "unitigs", "removed",
+                          "unitigs_out", "longest", "kmers_colored", "kmers_unplaced", "runs", "overflow", "color_bytes")   # pfh_run_multi_stats: `run-multi`'s stderr line
+RUN_MULTI_COLOR_FIELDS = ("lower", "upper", "distinct", "kept")   # of its `run-multi: color c ...` lines
 MASKCOUNT_STATS_FIELDS = ("reads", "bases", "kmers", "kmers_invalid", "kmers_bad", "kmers_kept")   # pf_maskcount_stats
 
 
@@ -222,6 +225,9 @@ def load_library() -> C.CDLL:
     L.pfh_run_defaults.restype = None
     L.pfh_run_defaults.argtypes = [C.POINTER(RunOptions)]
     L.pfh_run_fastq.argtypes = [C.POINTER(C.c_char_p), u32, C.c_char_p, C.POINTER(RunOptions), C.c_int, vp]
+    L.pfh_run_multi_fastq.argtypes = [C.POINTER(C.c_char_p), vp, u32, C.POINTER(C.c_char_p), C.c_char_p, C.POINTER(RunOptions), C.POINTER(FilterMultiOpts),
+                                      C.c_int, C.c_int, vp, vp]
+    L.pfh_union_host.argtypes = [vp, vp, u32, vp, C.POINTER(C.c_uint64)]
     L.pfh_count_masked_host.argtypes = [vp, vp, vp, u64, u32, vp, u32, u32, vp, vp, u64, C.POINTER(u64), vp]
     L.pfh_unitig_no_room_text.restype = C.c_char_p
     L.pfh_unitig_no_room_text.argtypes = [u64, u64, u64]
@@ -728,6 +734,74 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
     if rc:
         raise RuntimeError(L.pfh_last_error(None).decode())
     return {f: int(v) for f, v in zip(RUN_STATS_FIELDS, stats)}
+
+
+def run_multi_reads(samples, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 ** 9, cs: int = 10000, q: float = 0.998, mask_upper=None,
+                    keep_tips: bool = False, keep_isolated: bool = False, g=None, z: int = 8, M: float = 2.0, D: float = -1.0, G: float = -3.0,
+                    threads: int = 1, model=None, model_only: bool = False, filter_multi=None, each_color: bool = False, db_out=None, gfa_out=None,
+                    chunk_bytes: int = 0, initial_slots: int = 0) -> dict:
+    """`ploidyfrost run-multi` (pfh_run_multi_fastq): reads of several samples to one estimate per sample in one process.  samples: a
+    list of (name, file or list of files), a sample a colour in the order given.  Every sample is counted and its thresholds derived,
+    the k-mers of its masked reads counted (K-MASKCOUNT), their union taken (K-UNION), the coloured graph built and coloured per
+    distinct k-mer (K-COLORSET) and the coloured calling run made on one device context; PloidyFrost_output/<out_prefix>_*.txt in the
+    working directory.  model: None, "cov" or "fre", behind filter_multi = the options of filter_multi_opts as a dict.  Returns the
+    fields of the command's stderr line (RUN_MULTI_STATS_FIELDS) and under "color" one dict of RUN_MULTI_COLOR_FIELDS per sample.  A
+    refusal raises RuntimeError by name."""
+    L = load_library()
+    names, counts, flat = [], [], []
+    for name, files in samples:
+        if isinstance(files, (str, bytes, os.PathLike)):
+            files = [files]
+        names.append(os.fsencode(name))
+        counts.append(len(files))
+        flat.extend(files)
+    c_names = (C.c_char_p * max(len(names), 1))(*names)
+    n_of = np.ascontiguousarray(counts, dtype=np.uint32)
+    paths, _ = _paths(flat)
+    o = RunOptions()
+    L.pfh_run_defaults(C.byref(o))
+    o.k, o.ci, o.cx, o.cs = int(k), int(ci), int(cx), int(cs)
+    o.g = _unitig_g(g)
+    o.clip_tips, o.del_isolated = int(not keep_tips), int(not keep_isolated)
+    o.chunk_bytes, o.initial_slots = int(chunk_bytes), int(initial_slots)
+    o.quantile = float(q)
+    o.mask_up = 0xFFFFFFFF if mask_upper is None else int(mask_upper)
+    o.complex_size, o.match, o.mismatch, o.gap, o.threads = int(z), float(M), float(D), float(G), int(threads)
+    multi = None
+    if model is not None:
+        if model not in ("cov", "fre"):
+            raise ValueError("run_multi_reads: model is None, 'cov' or 'fre'")
+        if filter_multi is None:
+            raise ValueError("run_multi_reads: a model stands behind filter_multi (the options of `filter-multi`)")
+        o.model_source = 0 if model == "cov" else 1   # PF_MODEL_COV, PF_MODEL_FRE
+        o.model_only = int(model_only)
+        multi = filter_multi_opts(**filter_multi)
+    o.db_out = None if db_out is None else os.fsencode(db_out)
+    o.gfa_out = None if gfa_out is None else os.fsencode(gfa_out)
+    stats = np.zeros(len(RUN_MULTI_STATS_FIELDS), dtype=np.uint64)
+    per = np.zeros((max(len(names), 1), len(RUN_MULTI_COLOR_FIELDS)), dtype=np.uint64)
+    rc = L.pfh_run_multi_fastq(c_names, n_of.ctypes.data if len(names) else None, len(names), paths, os.fsencode(out_prefix), C.byref(o),
+                               C.byref(multi) if multi is not None else None, int(each_color), 0, stats.ctypes.data, per.ctypes.data)
+    if rc:
+        raise RuntimeError(L.pfh_last_error(None).decode())
+    out = {f: int(v) for f, v in zip(RUN_MULTI_STATS_FIELDS, stats)}
+    out["color"] = [{f: int(v) for f, v in zip(RUN_MULTI_COLOR_FIELDS, per[c])} for c in range(len(names))]
+    return out
+
+
+def union_host(arrays) -> np.ndarray:
+    """The sorted distinct union of sorted distinct arrays of 64-bit keys as K-UNION defines it (pfh_union_host, csrc/pf_runmulti_rule.hpp;
+    no device): rounds of pairwise merges, an odd set carried.  An array that is not ascending or holds a key twice raises RuntimeError
+    by name."""
+    L = load_library()
+    arrs = [np.ascontiguousarray(a, dtype=np.uint64) for a in arrays]
+    ns = np.array([len(a) for a in arrs], dtype=np.uint64)
+    ptrs = np.array([a.ctypes.data for a in arrs], dtype=np.uint64)
+    out = np.zeros(max(int(ns.sum()), 1), dtype=np.uint64)
+    n = C.c_uint64()
+    if L.pfh_union_host(ptrs.ctypes.data if len(arrs) else None, ns.ctypes.data if len(arrs) else None, len(arrs), out.ctypes.data, C.byref(n)):
+        raise RuntimeError(L.pfh_last_error(None).decode())
+    return out[: n.value].copy()
 
 
 def count_masked_host(text: bytes, read_off, read_len, k: int, counters, low: int, up: int = 0xFFFFFFFF):
