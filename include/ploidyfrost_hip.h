@@ -71,6 +71,7 @@ enum pf_kernel {
     PF_K_MASKCOUNT, /* K-MASKCOUNT: everything one pf_maskcount_reads / pf_maskcount_fastq launches (index, classes, flag, insert, growth), timed as one launch; unit: windows */
     PF_K_UNION, /* K-UNION: everything one pf_kmer_union launches (check, the count and write kernels of every merge, their scans), timed as one launch; unit: keys given */
     PF_K_COLORSET, /* K-COLORSET: the kernel of one pf_color_kmers; unit: keys */
+    PF_K_TRIMCOUNT, /* K-TRIMCOUNT: everything one pf_trim_table_fastq* / pf_count_fastq*_trimmed / pf_maskcount_fastq*_trimmed launches (index, intervals, table, then K-COUNT's or K-MASKCOUNT's core), timed as one launch; unit: records */
     PF_K_COUNT_
 };
 int pf_enable_timing(pf_ctx *, int on);
@@ -375,6 +376,40 @@ int pf_trim_fastq(pf_ctx *, const char *text, uint64_t n_bytes, int final, const
 int pf_trim_fastq_pair(pf_ctx *, const char *text1, uint64_t n1, const char *text2, uint64_t n2, int final, const pf_trim_step *steps,
                        uint32_t n_steps, uint32_t phred, char *out[4], uint64_t out_bytes[4], uint64_t bytes_used[2], uint32_t *rec_begin[2],
                        uint32_t *rec_len[2], uint64_t *n_records, pf_trim_stats stats[2], uint64_t *bad_record);
+/* K-TRIMCOUNT: K-TRIM folded into K-COUNT and K-MASKCOUNT -- one chunk of raw FASTQ (or one chunk of each file of a pair) trimmed and
+ * counted in one call, without the trimmed text (the rule: csrc/pf_trimrun_rule.hpp).  The reads handed on are the sequence bytes
+ * [seq_begin + b, seq_begin + e) of every whole record that K-TRIM keeps; for a pair, record r of a file is handed on only when record
+ * r of BOTH files is kept (the reference counts trim1 / trim2, never the unpaired survivors).  They form a reads table as
+ * pf_count_reads / pf_maskcount_reads take it, per file over that file's own text, and K-COUNT's / K-MASKCOUNT's rule applies to the
+ * table unchanged: a window that reaches into the trimmed-off head or tail of a read is no window -- neither counted nor flagged bad.
+ * The chunk contract, the format clauses and bad_record are pf_trim_fastq's / pf_trim_fastq_pair's (a refused chunk has counted
+ * nothing); the step refusals are K-TRIM's; what the count calls need (an open count, a resident table, the same k, both strands,
+ * low <= up) is what pf_count_fastq / pf_maskcount_fastq need.  All by name, under the entry point's name.  trim_stats: what
+ * pf_trim_fastq[_pair] reports for the chunk.  stats: what pf_count_fastq / pf_maskcount_fastq report on the trimmed text (reads and
+ * bases are of the reads handed on, of both files of a pair).  Timed as one launch of PF_K_TRIMCOUNT per call; unit: whole records
+ * taken (of both files).  text: [host|dev] */
+typedef struct pf_trim_plan {
+    const pf_trim_step *steps;
+    uint32_t n_steps;
+    uint32_t phred;   /* 33 or 64 */
+} pf_trim_plan;
+/* the table by itself: read_off / read_len ([host|dev], room for one entry per whole record of the chunk -- at most n_bytes / 4)
+ * receive *n_reads entries; *n_records = whole records taken.  A pair has one table per file, both of *n_reads entries: entry i of
+ * both are the two records of one pair. */
+int pf_trim_table_fastq(pf_ctx *, const char *text, uint64_t n_bytes, int final, const pf_trim_plan *plan, uint64_t *read_off, uint32_t *read_len,
+                        uint64_t *n_reads, uint64_t *bytes_used, uint64_t *n_records, pf_trim_stats *stats, uint64_t *bad_record);
+int pf_trim_table_fastq_pair(pf_ctx *, const char *text1, uint64_t n1, const char *text2, uint64_t n2, int final, const pf_trim_plan *plan,
+                             uint64_t *read_off[2], uint32_t *read_len[2], uint64_t *n_reads, uint64_t bytes_used[2], uint64_t *n_records,
+                             pf_trim_stats stats[2], uint64_t *bad_record);
+int pf_count_fastq_trimmed(pf_ctx *, const char *text, uint64_t n_bytes, int final, const pf_trim_plan *plan, uint64_t *bytes_used,
+                           pf_trim_stats *trim_stats, pf_count_stats *stats, uint64_t *bad_record);
+int pf_count_fastq_pair_trimmed(pf_ctx *, const char *text1, uint64_t n1, const char *text2, uint64_t n2, int final, const pf_trim_plan *plan,
+                                uint64_t bytes_used[2], pf_trim_stats trim_stats[2], pf_count_stats *stats, uint64_t *bad_record);
+int pf_maskcount_fastq_trimmed(pf_ctx *, const char *text, uint64_t n_bytes, int final, const pf_trim_plan *plan, uint32_t low, uint32_t up,
+                               uint64_t *bytes_used, pf_trim_stats *trim_stats, pf_maskcount_stats *stats, uint64_t *bad_record);
+int pf_maskcount_fastq_pair_trimmed(pf_ctx *, const char *text1, uint64_t n1, const char *text2, uint64_t n2, int final, const pf_trim_plan *plan,
+                                    uint32_t low, uint32_t up, uint64_t bytes_used[2], pf_trim_stats trim_stats[2], pf_maskcount_stats *stats,
+                                    uint64_t *bad_record);
 int pf_copy_to_host(pf_ctx *, void *dst, const void *src_dev, size_t bytes);
 
 /* K1/K2: builds the device hash table from the database records (exact k-mers as stored, any

@@ -248,6 +248,36 @@ int pfh_trim_read(const char *qual, uint64_t n, const pf_trim_step *steps, uint3
 int pfh_trim_fastq_chunk(const char *text, uint64_t n, int final, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, char *out,
                          uint64_t *out_bytes, uint64_t *bytes_used, uint32_t *rec_begin, uint32_t *rec_len, uint64_t cap, uint64_t *n_records,
                          pf_trim_stats *stats, uint64_t *bad_record);
+/* ---- raw reads to ploidy estimate in one process: step `1.trim` inside `run` / `run-multi` (K-TRIMCOUNT, pf_*_trimmed in ploidyfrost_hip.h) ----
+ * The rule: csrc/pf_trimrun_rule.hpp.  pfh_run_fastq_trimmed: pfh_run_fastq on the raw reads -- both passes stream them and trim them on
+ * the device on the way in, no trimmed file is written.  paired = 0: what `trim -i inputs... -o t.fq STEP...` followed by
+ * `run -i t.fq` writes; paired != 0: the inputs alternate file 1, file 2, and the result is that of one
+ * `trim -1 .. -2 .. -o1 t1 -u1 .. -o2 t2 -u2 ..` per pair followed by `run -i t1 -i t2 [-i t1' -i t2' ...]`: the records of a pair go on
+ * only when both are kept, the unpaired survivors are never counted.  n_steps = 0 with paired = 0 is pfh_run_fastq.  per_unit (may be
+ * NULL): the trimming statistics of the first pass, one entry for all single-ended inputs together, one entry per input file when
+ * paired.  Refused by name before a device context exists, beside what pfh_run_fastq refuses: what K-TRIM refuses about steps and
+ * phred, paired inputs without a step or in odd number, a file given twice (by name or as one file under two names).  After the stream
+ * has started: the files of a pair that hold different numbers of records, with the counts.
+ * pfh_run_multi_fastq_trimmed: pfh_run_multi_fastq likewise; paired_of[c] != 0: the inputs of sample c are pairs; steps and phred
+ * hold for every sample.  per_input (may be NULL): one entry per input file (a single-ended sample's unit stands in its first entry).
+ * The host's plain restatement of the hand-on rule, no device involved: pfh_trim_table_chunk / pfh_trim_table_chunk_pair give what
+ * pf_trim_table_fastq / pf_trim_table_fastq_pair give for one chunk -- the table (at most cap entries per file are written, *n_reads
+ * always), bytes_used, *n_records, the statistics; they return the format clause of the smallest offending record (0 = none;
+ * pfh_trim_table_clause_text names it, the pair's "final chunks hold different numbers of records" among them), -1 = the steps are
+ * refused. */
+int pfh_run_fastq_trimmed(const char *const *inputs, uint32_t n_inputs, int paired, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred,
+                          const char *out_prefix, const pfh_run_options *opt, int device, pfh_run_stats *stats, pf_trim_stats *per_unit);
+int pfh_run_multi_fastq_trimmed(const char *const *names, const uint32_t *n_inputs_of, const int *paired_of, uint32_t n_samples, const char *const *inputs,
+                                const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, const char *out_prefix, const pfh_run_options *opt,
+                                const pf_filter_multi_opts *multi, int each_color, int device, pfh_run_multi_stats *stats, uint64_t *per_color,
+                                pf_trim_stats *per_input);
+int pfh_trim_table_chunk(const char *text, uint64_t n, int final, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, uint64_t *read_off,
+                         uint32_t *read_len, uint64_t cap, uint64_t *n_reads, uint64_t *bytes_used, uint64_t *n_records, pf_trim_stats *stats,
+                         uint64_t *bad_record);
+int pfh_trim_table_chunk_pair(const char *text1, uint64_t n1, const char *text2, uint64_t n2, int final, const pf_trim_step *steps, uint32_t n_steps,
+                              uint32_t phred, uint64_t *const read_off[2], uint32_t *const read_len[2], uint64_t cap, uint64_t *n_reads, uint64_t bytes_used[2],
+                              uint64_t *n_records, pf_trim_stats stats[2], uint64_t *bad_record);
+const char *pfh_trim_table_clause_text(int clause);
 void pfh_get_times(const pfh_run *, pfh_times *out);
 /* Where the loads of this process spent their time (GFA map / parse / upload, count database, join, adjacency, numbering, ...):
  * "step\tseconds\n" per step since the last reset, in the order the steps ended (steps of helper threads overlap those of the

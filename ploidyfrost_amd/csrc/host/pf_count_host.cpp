@@ -42,20 +42,27 @@ int count_options_clause(const CountOptions &opt, bool writes) {
 
 int count_stream(pf_ctx *ctx, const char *who_c, const std::vector<std::string> &inputs, const CountOptions &opt, uint64_t largest, Counted &out,
                  pf_count_stats &stats, CountTimes &tm, std::string &err) {
+    return count_stream_with(ctx, who_c, opt, [&](std::string &e) {
+        StreamTimes stm;
+        return stream_fastq(ctx, who_c, inputs, opt.chunk_bytes, largest, -1, "",
+                            [&](const char *text, uint64_t n, bool final, char *, uint64_t &used, uint64_t &reads, uint64_t &bad) {
+                                pf_count_stats st = {};
+                                const int rc = pf_count_fastq(ctx, text, n, final ? 1 : 0, &used, &st, &bad);
+                                reads = st.reads;
+                                return rc;
+                            },
+                            stm, e);
+    }, out, stats, tm, err);
+}
+
+int count_stream_with(pf_ctx *ctx, const char *who_c, const CountOptions &opt, const std::function<int(std::string &)> &pass, Counted &out,
+                      pf_count_stats &stats, CountTimes &tm, std::string &err) {
     const std::string who = who_c;
     out = Counted{};
     stats = pf_count_stats{};
     const auto t_stream = clk::now();
     if (pf_count_begin(ctx, opt.k, opt.both_strands ? 1 : 0, opt.initial_slots) != PF_OK) { err = who + ": " + pf_last_error(ctx); return 1; }
-    StreamTimes stm;
-    if (stream_fastq(ctx, who_c, inputs, opt.chunk_bytes, largest, -1, "",
-                     [&](const char *text, uint64_t n, bool final, char *, uint64_t &used, uint64_t &reads, uint64_t &bad) {
-                         pf_count_stats st = {};
-                         const int rc = pf_count_fastq(ctx, text, n, final ? 1 : 0, &used, &st, &bad);
-                         reads = st.reads;
-                         return rc;
-                     },
-                     stm, err)) {
+    if (pass(err)) {
         pf_count_abort(ctx);
         return 1;
     }

@@ -6,6 +6,7 @@
 #pragma once
 #include <stdint.h>
 
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -41,6 +42,10 @@ int count_options_clause(const CountOptions &opt, bool writes);
 // pf_device_free), else worded in err; no count is left open.
 int count_stream(pf_ctx *ctx, const char *who, const std::vector<std::string> &inputs, const CountOptions &opt, uint64_t largest, Counted &out,
                  pf_count_stats &stats, CountTimes &tm, std::string &err);
+// the same around any pass that feeds the open count (`run STEP...`: the raw reads through the trimmed entry points): pf_count_begin,
+// pass(err) (0 = ok, else err is worded and the count is aborted), pf_count_finish
+int count_stream_with(pf_ctx *ctx, const char *who, const CountOptions &opt, const std::function<int(std::string &)> &pass, Counted &out,
+                      pf_count_stats &stats, CountTimes &tm, std::string &err);
 // the rows of the histogram of the finished counters, as pfh::kmc_rows gives them for the written database.  PF_OK, else pf_last_error
 int counted_rows(pf_ctx *ctx, const Counted &db, const CountOptions &opt, std::vector<uint64_t> &rows);
 // <prefix>.kmc_pre / <prefix>.kmc_suf from the finished counters: encoded on the device block by block, written under temporary

@@ -18,6 +18,7 @@
 #include "pf_bfg_write.hpp"
 #include "../pf_mask_rule.hpp"
 #include "../pf_trim_rule.hpp"
+#include "../pf_trimrun_rule.hpp"
 #include "pf_trim_host.hpp"
 #include "pf_trace.hpp"
 #include "../pf_model_rows.hpp"
@@ -498,64 +499,77 @@ void pfh_run_defaults(pfh_run_options *o) {
     o->threads = 1;
     o->model_source = -1;
 }
-int pfh_run_fastq(const char *const *inputs, uint32_t n_inputs, const char *out_prefix, const pfh_run_options *o, int device, pfh_run_stats *stats) {
-    if (!out_prefix || !o || (n_inputs && !inputs)) { g_open_err = "pfh_run_fastq: inputs, output prefix and options are needed"; return 1; }
+static void run_options_from(const pfh_run_options *o, pfh::RunOptions &opt) {
+    opt.k = o->k;
+    opt.ci = o->ci; opt.cx = o->cx; opt.cs = o->cs;
+    opt.g = o->g;
+    opt.clip_tips = o->clip_tips != 0; opt.del_isolated = o->del_isolated != 0;
+    opt.chunk_bytes = o->chunk_bytes; opt.initial_slots = o->initial_slots;
+    opt.quantile = o->quantile;
+    opt.mask_up = o->mask_up;
+    opt.complex_size = o->complex_size;
+    opt.match = o->match; opt.mismatch = o->mismatch; opt.gap = o->gap;
+    if (o->db_out) opt.db_out = o->db_out;
+    if (o->gfa_out) opt.gfa_out = o->gfa_out;
+}
+static void trim_inputs_from(const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, pfh::TrimInputs &t) {
+    t.steps.assign(steps, steps + (steps ? n_steps : 0));
+    t.phred = phred;
+}
+static int run_fastq_c(const char *who, const char *const *inputs, uint32_t n_inputs, int paired, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred,
+                       const char *out_prefix, const pfh_run_options *o, int device, pfh_run_stats *stats, pf_trim_stats *per_unit) {
+    if (!out_prefix || !o || (n_inputs && !inputs)) { g_open_err = std::string(who) + ": inputs, output prefix and options are needed"; return 1; }
     try {
         std::vector<std::string> in;
         for (uint32_t i = 0; i < n_inputs; ++i) in.push_back(inputs[i] ? inputs[i] : "");
         pfh::RunOptions opt;
-        opt.k = o->k;
-        opt.ci = o->ci; opt.cx = o->cx; opt.cs = o->cs;
-        opt.g = o->g;
-        opt.clip_tips = o->clip_tips != 0; opt.del_isolated = o->del_isolated != 0;
-        opt.chunk_bytes = o->chunk_bytes; opt.initial_slots = o->initial_slots;
-        opt.quantile = o->quantile;
-        opt.mask_up = o->mask_up;
-        opt.complex_size = o->complex_size;
-        opt.match = o->match; opt.mismatch = o->mismatch; opt.gap = o->gap;
+        run_options_from(o, opt);
         opt.call.threads = o->threads ? o->threads : 1;
         if (o->model_source >= 0) {
             opt.call.model.on = true;
             opt.call.model.only = o->model_only != 0;
             opt.call.model.source = o->model_source;
         }
-        if (o->db_out) opt.db_out = o->db_out;
-        if (o->gfa_out) opt.gfa_out = o->gfa_out;
+        trim_inputs_from(steps, n_steps, phred, opt.trim);
+        opt.paired = paired != 0;
         pfh::RunStats st;
         const int rc = pfh::run_fastq(in, out_prefix, opt, device, st, nullptr, g_open_err);
         if (stats)
             *stats = pfh_run_stats{st.counted.reads, st.counted.bases, st.counted.kmers, st.counted.kmers_bad, st.counted.unique, st.lower, st.upper,
                                    st.masked.kmers_bad, st.masked.kmers_kept, st.distinct_kept, st.graph.unitigs, st.graph.removed, st.graph.unitigs_out,
                                    st.graph.longest};
+        if (per_unit) std::copy(st.trim.begin(), st.trim.end(), per_unit);
         return rc;
     } catch (const std::exception &e) {
         g_open_err = std::string("ploidyfrost host layer: ") + e.what();
         return 1;
     }
 }
+int pfh_run_fastq(const char *const *inputs, uint32_t n_inputs, const char *out_prefix, const pfh_run_options *o, int device, pfh_run_stats *stats) {
+    return run_fastq_c("pfh_run_fastq", inputs, n_inputs, 0, nullptr, 0, 33, out_prefix, o, device, stats, nullptr);
+}
+int pfh_run_fastq_trimmed(const char *const *inputs, uint32_t n_inputs, int paired, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred,
+                          const char *out_prefix, const pfh_run_options *o, int device, pfh_run_stats *stats, pf_trim_stats *per_unit) {
+    return run_fastq_c("pfh_run_fastq_trimmed", inputs, n_inputs, paired, steps, n_steps, phred, out_prefix, o, device, stats, per_unit);
+}
 // ---- `run-multi` (K-UNION, K-COLORSET) ----
-int pfh_run_multi_fastq(const char *const *names, const uint32_t *n_inputs_of, uint32_t n_samples, const char *const *inputs, const char *out_prefix,
-                        const pfh_run_options *o, const pf_filter_multi_opts *multi, int each_color, int device, pfh_run_multi_stats *stats,
-                        uint64_t *per_color) {
-    if (!out_prefix || !o || (n_samples && (!names || !n_inputs_of))) { g_open_err = "pfh_run_multi_fastq: samples, output prefix and options are needed"; return 1; }
+static int run_multi_fastq_c(const char *who, const char *const *names, const uint32_t *n_inputs_of, const int *paired_of, uint32_t n_samples,
+                             const char *const *inputs, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, const char *out_prefix,
+                             const pfh_run_options *o, const pf_filter_multi_opts *multi, int each_color, int device, pfh_run_multi_stats *stats,
+                             uint64_t *per_color, pf_trim_stats *per_input) {
+    if (!out_prefix || !o || (n_samples && (!names || !n_inputs_of))) { g_open_err = std::string(who) + ": samples, output prefix and options are needed"; return 1; }
     try {
         std::vector<pfh::MultiSample> samples(n_samples);
         uint64_t at = 0;
         for (uint32_t c = 0; c < n_samples; ++c) {
             samples[c].name = names[c] ? names[c] : "";
+            samples[c].paired = paired_of && paired_of[c];
             for (uint32_t i = 0; i < n_inputs_of[c]; ++i, ++at) samples[c].inputs.push_back(inputs && inputs[at] ? inputs[at] : "");
         }
         pfh::RunMultiOptions mopt;
         pfh::RunOptions &opt = mopt.run;
-        opt.k = o->k;
-        opt.ci = o->ci; opt.cx = o->cx; opt.cs = o->cs;
-        opt.g = o->g;
-        opt.clip_tips = o->clip_tips != 0; opt.del_isolated = o->del_isolated != 0;
-        opt.chunk_bytes = o->chunk_bytes; opt.initial_slots = o->initial_slots;
-        opt.quantile = o->quantile;
-        opt.mask_up = o->mask_up;
-        opt.complex_size = o->complex_size;
-        opt.match = o->match; opt.mismatch = o->mismatch; opt.gap = o->gap;
+        run_options_from(o, opt);
+        trim_inputs_from(steps, n_steps, phred, opt.trim);
         mopt.call.threads = o->threads ? o->threads : 1;
         if (o->model_source >= 0) {
             if (!multi) { g_open_err = "run-multi: a model reads the coloured result streams behind the options of filter-multi: multi is needed"; return 1; }
@@ -565,8 +579,6 @@ int pfh_run_multi_fastq(const char *const *names, const uint32_t *n_inputs_of, u
             mopt.call.filter_multi = multi;
             mopt.call.each_color = each_color != 0;
         }
-        if (o->db_out) opt.db_out = o->db_out;
-        if (o->gfa_out) opt.gfa_out = o->gfa_out;
         pfh::RunMultiStats st;
         const int rc = pfh::run_multi_fastq(samples, out_prefix, mopt, device, st, nullptr, g_open_err);
         if (stats)
@@ -580,12 +592,76 @@ int pfh_run_multi_fastq(const char *const *names, const uint32_t *n_inputs_of, u
                 per_color[4 * c + 2] = st.color[c].distinct;
                 per_color[4 * c + 3] = st.color[c].kept;
             }
+        if (per_input) {   // one entry per input file; a single-ended sample's unit stands in its first entry
+            uint64_t i = 0;
+            for (uint32_t c = 0; c < n_samples; i += n_inputs_of[c], ++c)
+                for (size_t j = 0; j < n_inputs_of[c]; ++j) per_input[i + j] = c < st.trim.size() && j < st.trim[c].size() ? st.trim[c][j] : pf_trim_stats{};
+        }
         return rc;
     } catch (const std::exception &e) {
         g_open_err = std::string("ploidyfrost host layer: ") + e.what();
         return 1;
     }
 }
+int pfh_run_multi_fastq(const char *const *names, const uint32_t *n_inputs_of, uint32_t n_samples, const char *const *inputs, const char *out_prefix,
+                        const pfh_run_options *o, const pf_filter_multi_opts *multi, int each_color, int device, pfh_run_multi_stats *stats,
+                        uint64_t *per_color) {
+    return run_multi_fastq_c("pfh_run_multi_fastq", names, n_inputs_of, nullptr, n_samples, inputs, nullptr, 0, 33, out_prefix, o, multi, each_color, device, stats,
+                             per_color, nullptr);
+}
+int pfh_run_multi_fastq_trimmed(const char *const *names, const uint32_t *n_inputs_of, const int *paired_of, uint32_t n_samples, const char *const *inputs,
+                                const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, const char *out_prefix, const pfh_run_options *o,
+                                const pf_filter_multi_opts *multi, int each_color, int device, pfh_run_multi_stats *stats, uint64_t *per_color,
+                                pf_trim_stats *per_input) {
+    return run_multi_fastq_c("pfh_run_multi_fastq_trimmed", names, n_inputs_of, paired_of, n_samples, inputs, steps, n_steps, phred, out_prefix, o, multi,
+                             each_color, device, stats, per_color, per_input);
+}
+// ---- `run STEP...`: the table of the reads handed on, on the host (../pf_trimrun_rule.hpp) ----
+int pfh_trim_table_chunk(const char *text, uint64_t n, int final, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, uint64_t *read_off,
+                         uint32_t *read_len, uint64_t cap, uint64_t *n_reads, uint64_t *bytes_used, uint64_t *n_records, pf_trim_stats *stats,
+                         uint64_t *bad_record) {
+    if (pfh::trim_options_clause(trim_options(steps, n_steps, phred, nullptr, 0), g_open_err)) return -1;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> len;
+    uint64_t used = 0, recs = 0, bad = 0;
+    pf_trim::Stats st = {};
+    const int clause = pf_trimrun::reads_table(text, n, final != 0, reinterpret_cast<const pf_trim::Step *>(steps), n_steps, phred, off, len, used, recs, bad, &st);
+    if (n_reads) *n_reads = off.size();
+    if (bytes_used) *bytes_used = used;
+    if (n_records) *n_records = recs;
+    if (bad_record) *bad_record = bad;
+    if (stats) memcpy(stats, &st, sizeof st);
+    for (uint64_t i = 0; i < cap && i < off.size(); ++i) {
+        if (read_off) read_off[i] = off[i];
+        if (read_len) read_len[i] = len[i];
+    }
+    return clause;
+}
+int pfh_trim_table_chunk_pair(const char *text1, uint64_t n1, const char *text2, uint64_t n2, int final, const pf_trim_step *steps, uint32_t n_steps,
+                              uint32_t phred, uint64_t *const read_off[2], uint32_t *const read_len[2], uint64_t cap, uint64_t *n_reads, uint64_t bytes_used[2],
+                              uint64_t *n_records, pf_trim_stats stats[2], uint64_t *bad_record) {
+    if (pfh::trim_options_clause(trim_options(steps, n_steps, phred, nullptr, 0), g_open_err)) return -1;
+    const char *const text[2] = {text1, text2};
+    const uint64_t n[2] = {n1, n2};
+    std::vector<uint64_t> off[2];
+    std::vector<uint32_t> len[2];
+    uint64_t used[2] = {0, 0}, recs = 0, bad = 0;
+    pf_trim::Stats st[2] = {};
+    const int clause = pf_trimrun::reads_table_pair(text, n, final != 0, reinterpret_cast<const pf_trim::Step *>(steps), n_steps, phred, off, len, used, recs, bad, st);
+    if (n_reads) *n_reads = off[0].size();
+    if (n_records) *n_records = recs;
+    if (bad_record) *bad_record = bad;
+    for (int f = 0; f < 2; ++f) {
+        if (bytes_used) bytes_used[f] = used[f];
+        if (stats) memcpy(&stats[f], &st[f], sizeof st[f]);
+        for (uint64_t i = 0; i < cap && i < off[f].size(); ++i) {
+            if (read_off && read_off[f]) read_off[f][i] = off[f][i];
+            if (read_len && read_len[f]) read_len[f][i] = len[f][i];
+        }
+    }
+    return clause;
+}
+const char *pfh_trim_table_clause_text(int clause) { return pf_trimrun::clause_text(clause); }
 int pfh_union_host(const uint64_t *const *sets, const uint64_t *n, uint32_t n_sets, uint64_t *out, uint64_t *n_out) {
     if (n_out) *n_out = 0;
     if (!n_out || (n_sets && (!sets || !n))) { g_open_err = "pfh_union_host: sets, n and n_out are needed"; return 1; }

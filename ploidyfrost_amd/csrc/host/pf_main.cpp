@@ -111,7 +111,10 @@ void PrintUsage() {
          << "                  [-z -M -D -G -t --ref-threads] [--model cov|fre ... --model-only --filter \"OPTS\" --density ...] [--db-out <KMCDatabase>] [--gfa-out <sample>]" << endl
          << "                  [--chunk-bytes N] [--initial-slots N] [-v]" << endl
          << "                  (reads to ploidy estimate in one process: `mask -k ... --auto-cutoffs`, `build -i -d` and the calling run with --auto-cutoffs on" << endl
-         << "                  one device context, no masked reads, database or graph file in between; L is printed on stdout)" << endl << endl
+         << "                  one device context, no masked reads, database or graph file in between; L is printed on stdout)" << endl
+         << "Usage: PloidyFrost run [the same options] (-i <raw.fq> [-i <more.fq> ...] | -1 <r1.fq> -2 <r2.fq> [-1 <r3.fq> -2 <r4.fq> ...]) -o <sample> STEP... [--phred 33|64]" << endl
+         << "                  (raw reads to ploidy estimate: the reads are trimmed on the device on the way in, as `trim STEP...` trims them; of a pair the" << endl
+         << "                  records go on when both are kept; `run-multi` takes STEP... and -1 / -2 inside a --sample likewise)" << endl << endl
          << "Usage: PloidyFrost run-multi [-k 25 -ci 1 -cs 10000 -cx N] --sample <NAME> -i <a.fq> [-i <b.fq> ...] --sample <NAME2> -i <c.fq> [...] -o <out> [-q Q] [-u U]" << endl
          << "                  [--keep-tips] [--keep-isolated] [-g G] [-z -M -D -G -t --ref-threads] [--model cov|fre --filter-multi \"OPTS\" [--model-each-color] [--density ...] [--model-only]]" << endl
          << "                  [--db-out <KMCDatabase>] [--gfa-out <graph>] [--chunk-bytes N] [--initial-slots N] [-v]" << endl
@@ -865,6 +868,57 @@ int trim_main(int argc, char **argv) {
     return 0;
 }
 
+// `run STEP...` / `run-multi STEP...`: the words and options of step 1 as `trim` takes them -- the same parser, refusals and texts
+struct TrimCli {
+    vector<string> words;   // the positional words: the steps
+    bool phred_seen = false, pair_seen = false;
+    uint32_t phred = 33;
+    string pending1;        // a -1 whose -2 has not come yet
+    // 1 = the option was taken (i moved past its value), 0 = not one of these, -1 = refused with `why`
+    int take(int argc, char **argv, int &i, const char *sub, vector<string> &files, string &why) {
+        const string a = argv[i];
+        if (a.empty() || a[0] != '-') { words.push_back(a); return 1; }
+        for (const char *o : {"--trimlog", "-o1", "-u1", "-o2", "-u2"})
+            if (a == o) { why = a + " is not built into " + sub + ": `trim` writes the trimmed reads, the unpaired ones and the log"; return -1; }
+        if (a != "--phred" && a != "-1" && a != "-2") return 0;
+        if (i + 1 >= argc) { why = a + " needs a value"; return -1; }
+        const string v = argv[++i];
+        if (a == "--phred") {
+            if (v != "33" && v != "64") { why = "--phred takes 33 or 64, not '" + v + "'"; return -1; }
+            phred = (uint32_t)stoi(v);
+            phred_seen = true;
+        } else if (a == "-1") {
+            if (!pending1.empty()) { why = no_second(); return -1; }
+            pending1 = v;
+            pair_seen = true;
+        } else {
+            if (pending1.empty()) { why = "-2 " + v + " has no -1 in front of it (the files of a pair come as -1 <r1.fq> -2 <r2.fq>)"; return -1; }
+            files.push_back(pending1);
+            files.push_back(v);
+            pending1.clear();
+        }
+        return 1;
+    }
+    string no_second() const { return "-1 " + pending1 + " has no -2 behind it (the files of a pair come as -1 <r1.fq> -2 <r2.fq>)"; }
+    // after the last argument: "" = accepted, with the steps parsed
+    string finish(const char *sub, vector<pf_trim_step> &steps) const {
+        if (!pending1.empty()) return no_second();
+        if (words.empty()) {
+            if (pair_seen) return string("-1 / -2 need a step: the files of a pair are trimmed together (two files without trimming go with -i: ") + sub + " -i r1.fq -i r2.fq)";
+            if (phred_seen) return "--phred needs a step: the quality offset is read by the trimming alone";
+            return "";
+        }
+        vector<const char *> w;
+        for (const string &x : words) w.push_back(x.c_str());
+        vector<pf_trim::Step> parsed;
+        size_t bad = 0;
+        const int c = pf_trim::parse_steps(w.data(), w.size(), parsed, &bad);
+        if (c) return words[bad] + ": " + pf_trim::refusal_text(c);
+        for (const pf_trim::Step &st : parsed) steps.push_back(pf_trim_step{st.kind, st.a, st.b});
+        return "";
+    }
+};
+
 bool take_long_options(int &argc, char **argv, int first, Options &opt, DensityCli &dc);
 bool model_setup(const Options &opt, DensityCli &dc, pfh::CDBG::ModelOptions &model, pf_filter_opts &filter, pf_filter_multi_opts &multi);
 int calling_main(Options &opt, DensityCli &dc);
@@ -875,7 +929,10 @@ int calling_main(Options &opt, DensityCli &dc);
 int run_main(int argc, char **argv) {
     const char *usage = "Usage:PloidyFrost run [-k 25] [-ci 1] [-cs 10000] [-cx N] -i trimmed.fq [-i more.fq ...] -o sample [-q Q] [-u U] [--keep-tips] [--keep-isolated] [-g G]\n"
                         "                 [-z Z -M m -D d -G g -t T --ref-threads N] [--model cov|fre ... --model-only --filter \"OPTS\" --density ...]\n"
-                        "                 [--db-out <KMCDatabase>] [--gfa-out <sample>] [--chunk-bytes N] [--initial-slots N] [-v]";
+                        "                 [--db-out <KMCDatabase>] [--gfa-out <sample>] [--chunk-bytes N] [--initial-slots N] [-v]\n"
+                        "      PloidyFrost run [the same options] -i raw.fq [-i more.fq ...] -o sample STEP... [--phred 33|64]\n"
+                        "      PloidyFrost run [the same options] -1 r1.fq -2 r2.fq [-1 r3.fq -2 r4.fq ...] -o sample STEP... [--phred 33|64]\n"
+                        "      STEP: LEADING:t TRAILING:t SLIDINGWINDOW:w:t MINLEN:l (the raw reads are trimmed on the way in, as `trim` trims them)";
     auto refuse = [&](const string &why) { cerr << "Error: run: " << why << endl << usage << endl; return 1; };
     Options lopt;   // the long options of the calling run
     DensityCli dc;
@@ -886,7 +943,8 @@ int run_main(int argc, char **argv) {
     c.opt.cx = opt.cx;
     c.opt.cs = opt.cs;
     string out;
-    vector<string> inputs;
+    vector<string> inputs, pair_files;
+    TrimCli tc;
     bool verbose = false;
     auto number = [&](const string &o, const char *text, uint64_t &v, bool positive) {
         char *end = nullptr;
@@ -926,6 +984,12 @@ int run_main(int argc, char **argv) {
             if (taken < 0) return refuse(why);
             if (taken) continue;
         }
+        {
+            string why;
+            const int taken = tc.take(argc, argv, i, "run", pair_files, why);
+            if (taken < 0) return refuse(why);
+            if (taken) continue;
+        }
         if (a == "-v") { verbose = true; continue; }
         if (a == "--keep-tips") { opt.clip_tips = false; continue; }
         if (a == "--keep-isolated") { opt.del_isolated = false; continue; }
@@ -952,6 +1016,10 @@ int run_main(int argc, char **argv) {
         else if (a == "--initial-slots") opt.initial_slots = v;
     }
     // refused by name, before anything is read or written and before a device context exists
+    { const string why = tc.finish("run", opt.trim.steps); if (!why.empty()) return refuse(why); }
+    opt.trim.phred = tc.phred;
+    if (tc.pair_seen && !inputs.empty()) return refuse("-i does not go with -1 / -2 (the inputs are either single-ended or pairs)");
+    if (tc.pair_seen) { inputs = pair_files; opt.paired = true; }
     if (inputs.empty()) return refuse("-i <reads.fq> is missing");
     if (out.empty()) return refuse("-o <sample> is missing");
     opt.k = c.opt.k;
@@ -984,6 +1052,8 @@ int run_main(int argc, char **argv) {
         else cerr << err << endl;
         return EXIT_FAILURE;
     }
+    for (size_t u = 0; u < pfh::trim_unit_count(inputs.size(), opt.paired) && opt.trim.on(); ++u)   // one line per `trim` of the equivalent chain
+        cerr << pfh::trim_unit_line(&st.trim[opt.paired ? 2 * u : 0], opt.paired) << endl;
     cerr << "run: reads " << st.counted.reads << " bases " << st.counted.bases << " kmers " << st.counted.kmers << " bad " << st.counted.kmers_bad << " distinct "
          << st.counted.unique << " lower " << st.lower << " upper " << st.upper << " windows_bad " << st.masked.kmers_bad << " windows_kept " << st.masked.kmers_kept
          << " distinct_kept " << st.distinct_kept << " unitigs " << st.graph.unitigs << " removed " << st.graph.removed << " unitigs_out " << st.graph.unitigs_out
@@ -1000,7 +1070,9 @@ int run_multi_main(int argc, char **argv) {
     const char *usage = "Usage:PloidyFrost run-multi [-k 25] [-ci 1] [-cs 10000] [-cx N] --sample NAME -i a.fq [-i b.fq ...] --sample NAME2 -i c.fq [...] -o out\n"
                         "                 [-q Q] [-u U] [--keep-tips] [--keep-isolated] [-g G] [-z Z -M m -D d -G g -t T --ref-threads N]\n"
                         "                 [--model cov|fre --filter-multi \"OPTS\" [--model-each-color] [--density ...] [--model-only]]\n"
-                        "                 [--db-out <KMCDatabase>] [--gfa-out <graph>] [--chunk-bytes N] [--initial-slots N] [-v]";
+                        "                 [--db-out <KMCDatabase>] [--gfa-out <graph>] [--chunk-bytes N] [--initial-slots N] [-v]\n"
+                        "      PloidyFrost run-multi [the same options] --sample NAME (-i raw.fq ... | -1 r1.fq -2 r2.fq ...) --sample NAME2 ... -o out STEP... [--phred 33|64]\n"
+                        "      STEP: LEADING:t TRAILING:t SLIDINGWINDOW:w:t MINLEN:l (the raw reads are trimmed on the way in, as `trim` trims them)";
     auto refuse = [&](const string &why) { cerr << "Error: run-multi: " << why << endl << usage << endl; return 1; };
     Options lopt;   // the long options of the calling run
     DensityCli dc;
@@ -1013,6 +1085,7 @@ int run_multi_main(int argc, char **argv) {
     c.opt.cs = opt.cs;
     string out;
     vector<pfh::MultiSample> samples;
+    TrimCli tc;
     bool verbose = false;
     size_t threads = 1;
     auto number = [&](const string &o, const char *text, uint64_t &v, bool positive) {
@@ -1053,6 +1126,18 @@ int run_multi_main(int argc, char **argv) {
             if (taken < 0) return refuse(why);
             if (taken) continue;
         }
+        {
+            if ((a == "-1" || a == "-2") && samples.empty()) return refuse(a + " stands before any --sample NAME: every input belongs to a sample");
+            if ((a == "-1" || a == "-2") && !samples.back().paired && !samples.back().inputs.empty())
+                return refuse("sample " + samples.back().name + ": -i does not go with -1 / -2 (the inputs of a sample are either single-ended or pairs)");
+            if (a == "--sample" && !tc.pending1.empty()) return refuse(tc.no_second());
+            static vector<string> no_files;
+            string why;
+            const int taken = tc.take(argc, argv, i, "run-multi", samples.empty() ? no_files : samples.back().inputs, why);
+            if (taken < 0) return refuse(why);
+            if (taken && (a == "-1" || a == "-2")) samples.back().paired = true;
+            if (taken) continue;
+        }
         if (a == "-v") { verbose = true; continue; }
         if (a == "--keep-tips") { opt.clip_tips = false; continue; }
         if (a == "--keep-isolated") { opt.del_isolated = false; continue; }
@@ -1065,6 +1150,7 @@ int run_multi_main(int argc, char **argv) {
         if (a == "--sample") { samples.emplace_back(); samples.back().name = val; }
         else if (a == "-i") {
             if (samples.empty()) return refuse(string("-i ") + val + " stands before any --sample NAME: every input belongs to a sample");
+            if (samples.back().paired) return refuse("sample " + samples.back().name + ": -i does not go with -1 / -2 (the inputs of a sample are either single-ended or pairs)");
             samples.back().inputs.push_back(val);
         }
         else if (a == "-o") out = val;
@@ -1083,6 +1169,8 @@ int run_multi_main(int argc, char **argv) {
         else if (a == "--initial-slots") opt.initial_slots = v;
     }
     // refused by name, before anything is read or written and before a device context exists
+    { const string why = tc.finish("run-multi", opt.trim.steps); if (!why.empty()) return refuse(why); }
+    opt.trim.phred = tc.phred;
     { const string why = pfh::run_multi_samples_refusal(samples); if (!why.empty()) return refuse(why); }
     if (out.empty()) return refuse("-o <out> is missing");
     opt.k = c.opt.k;
@@ -1118,6 +1206,9 @@ int run_multi_main(int argc, char **argv) {
         else cerr << err << endl;
         return EXIT_FAILURE;
     }
+    for (size_t c = 0; c < st.trim.size(); ++c)   // one line per `trim` of the equivalent chain, in the order given
+        for (size_t u = 0; u < pfh::trim_unit_count(samples[c].inputs.size(), samples[c].paired); ++u)
+            cerr << pfh::trim_unit_line(&st.trim[c][samples[c].paired ? 2 * u : 0], samples[c].paired) << endl;
     cerr << "run-multi: colors " << st.colors << " reads " << st.reads << " bases " << st.bases << " kmers " << st.kmers << " bad " << st.bad << " distinct "
          << st.distinct << " windows_bad " << st.windows_bad << " windows_kept " << st.windows_kept << " distinct_kept " << st.distinct_kept << " unitigs "
          << st.graph.unitigs << " removed " << st.graph.removed << " unitigs_out " << st.graph.unitigs_out << " longest " << st.graph.longest << " kmers_colored "

@@ -12,7 +12,9 @@
 
 #include "pf_cutoffs.hpp"
 #include "pf_host_graph.hpp"
+#include "../pf_trim_rule.hpp"
 #include "pf_mask_host.hpp"
+#include "pf_trim_host.hpp"
 
 namespace pfh {
 
@@ -129,6 +131,85 @@ int colored_call_run(CCDBG &g, ColoredCallSetup &s, std::string &err) {
     return 0;
 }
 
+// ---- trimmed inputs ----
+std::string trim_inputs_refusal(const std::vector<std::string> &inputs, bool paired, const TrimInputs &trim) {
+    if (paired && !trim.on()) return "the files of a pair are trimmed together: -1 / -2 need a step (two files without trimming go with -i)";
+    if (!trim.on()) return "";
+    {
+        TrimOptions o;
+        o.steps = trim.steps;
+        o.phred = trim.phred;
+        std::string e;
+        if (trim_options_clause(o, e)) return e.substr(6);   // (worded "trim: ...": the caller puts its own name in front)
+    }
+    if (paired && inputs.size() % 2) return inputs.back() + ": the first file of a pair without its second (-1 <r1.fq> -2 <r2.fq>)";
+    for (size_t i = 0; i < inputs.size(); ++i)
+        for (size_t j = 0; j < i; ++j)
+            if (same_file(inputs[i], inputs[j]))
+                return inputs[i] + (inputs[i] == inputs[j] ? " is given twice" : " and " + inputs[j] + " are one file") + ": every read is counted once";
+    return "";
+}
+
+std::string trim_unit_line(const pf_trim_stats *st, bool paired) {
+    auto n = [](uint64_t v) { return std::to_string(v); };
+    if (paired)
+        return "trim: pairs " + n(st[0].reads) + " both " + n(st[0].both) + " forward_only " + n(st[0].only1) + " reverse_only " + n(st[0].only2) + " dropped " +
+               n(st[0].neither) + " bases " + n(st[0].bases + st[1].bases) + " bases_kept " + n(st[0].bases_kept + st[1].bases_kept);
+    return "trim: reads " + n(st[0].reads) + " kept " + n(st[0].kept) + " dropped " + n(st[0].dropped) + " bases " + n(st[0].bases) + " bases_kept " +
+           n(st[0].bases_kept);
+}
+
+namespace {
+void add_trim_stats(pf_trim_stats &a, const pf_trim_stats &b) {
+    a.reads += b.reads; a.kept += b.kept; a.dropped += b.dropped; a.bases += b.bases; a.bases_kept += b.bases_kept;
+    a.both += b.both; a.only1 += b.only1; a.only2 += b.only2; a.neither += b.neither;
+}
+void add_masked_stats(pf_maskcount_stats &a, const pf_maskcount_stats &b) {
+    a.reads += b.reads; a.bases += b.bases; a.kmers += b.kmers; a.kmers_invalid += b.kmers_invalid; a.kmers_bad += b.kmers_bad; a.kmers_kept += b.kmers_kept;
+}
+}  // namespace
+
+int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<std::string> &inputs, bool paired, const TrimInputs &trim, uint64_t chunk_bytes,
+                   uint64_t largest, bool masked, uint32_t low, uint32_t up, pf_trim_stats *unit_stats, pf_maskcount_stats *masked_stats, std::string &err) {
+    const pf_trim_plan plan = {trim.steps.data(), (uint32_t)trim.steps.size(), trim.phred};
+    if (!paired) {
+        StreamTimes stm;
+        return stream_fastq(ctx, who, inputs, chunk_bytes, largest, -1, "",
+                            [&](const char *text, uint64_t n, bool final, char *, uint64_t &used, uint64_t &reads, uint64_t &bad) {
+                                pf_trim_stats ts = {};
+                                pf_count_stats cs = {};
+                                pf_maskcount_stats ms = {};
+                                const int rc = masked ? pf_maskcount_fastq_trimmed(ctx, text, n, final ? 1 : 0, &plan, low, up, &used, &ts, &ms, &bad)
+                                                      : pf_count_fastq_trimmed(ctx, text, n, final ? 1 : 0, &plan, &used, &ts, &cs, &bad);
+                                if (rc != PF_OK) return rc;
+                                reads = ts.reads;   // the records taken, kept or not: the next chunk's records are numbered behind them
+                                if (unit_stats) add_trim_stats(unit_stats[0], ts);
+                                if (masked_stats) add_masked_stats(*masked_stats, ms);
+                                return (int)PF_OK;
+                            },
+                            stm, err);
+    }
+    for (size_t u = 0; u + 1 < inputs.size(); u += 2) {
+        PairStreamTimes ptm;
+        if (stream_fastq_pair(ctx, who, inputs[u], inputs[u + 1], chunk_bytes, largest,
+                              [&](const char *t1, uint64_t n1, const char *t2, uint64_t n2, bool final, uint64_t used[2], uint64_t &recs, uint64_t &bad) {
+                                  pf_trim_stats ts[2] = {};
+                                  pf_count_stats cs = {};
+                                  pf_maskcount_stats ms = {};
+                                  const int rc = masked ? pf_maskcount_fastq_pair_trimmed(ctx, t1, n1, t2, n2, final ? 1 : 0, &plan, low, up, used, ts, &ms, &bad)
+                                                        : pf_count_fastq_pair_trimmed(ctx, t1, n1, t2, n2, final ? 1 : 0, &plan, used, ts, &cs, &bad);
+                                  if (rc != PF_OK) return rc;
+                                  recs = ts[0].reads;
+                                  if (unit_stats) { add_trim_stats(unit_stats[u], ts[0]); add_trim_stats(unit_stats[u + 1], ts[1]); }
+                                  if (masked_stats) add_masked_stats(*masked_stats, ms);
+                                  return (int)PF_OK;
+                              },
+                              ptm, err))
+            return 1;
+    }
+    return 0;
+}
+
 // ---- run ----
 std::string run_options_refusal(const RunOptions &opt) {
     { const int c = count_options_clause(count_options_of(opt), true); if (c) return pf_count::cut_text(c); }
@@ -146,6 +227,9 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
     if (inputs.empty()) { err = "run: no input"; return 1; }
     if (out_prefix.empty()) { err = "run: no output prefix"; return 1; }
     { const std::string why = run_options_refusal(opt); if (!why.empty()) { err = "run: " + why; return 1; } }
+    { const std::string why = trim_inputs_refusal(inputs, opt.paired, opt.trim); if (!why.empty()) { err = "run: " + why; return 1; } }
+    const bool trimming = opt.trim.on();
+    if (trimming) stats.trim.assign(opt.paired ? inputs.size() : 1, pf_trim_stats{});
     const CountOptions copt = count_options_of(opt);
     const std::string tail = ".tmp." + std::to_string((long)getpid());
     const std::string gfa_path = opt.gfa_out.empty() ? "" : opt.gfa_out + ".gfa", gfa_tmp = gfa_path + tail;
@@ -177,7 +261,11 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
     {
         Counted db;
         CountTimes ctm;
-        if (count_stream(ctx, "run", inputs, copt, largest, db, stats.counted, ctm, err)) return 1;
+        if (trimming ? count_stream_with(ctx, "run", copt, [&](std::string &e) {
+                           return stream_trimmed(ctx, "run", inputs, opt.paired, opt.trim, opt.chunk_bytes, largest, false, 0, 0, stats.trim.data(), nullptr, e);
+                       }, db, stats.counted, ctm, err)
+                     : count_stream(ctx, "run", inputs, copt, largest, db, stats.counted, ctm, err))
+            return 1;
         struct Free { pf_ctx *c; Counted &d; ~Free() { pf_device_free(c, d.kmers); pf_device_free(c, d.counts); } } free_db{ctx, db};
         tm.count_s = ctm.stream_s;
         tm.finish_s = ctm.finish_s;
@@ -210,7 +298,8 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
         const auto t_stream = clk::now();
         if (pf_count_begin(ctx, opt.k, 1, opt.initial_slots) != PF_OK) return dev_fail();
         StreamTimes stm;
-        if (stream_fastq(ctx, "run", inputs, opt.chunk_bytes, largest, -1, "",
+        if (trimming ? stream_trimmed(ctx, "run", inputs, opt.paired, opt.trim, opt.chunk_bytes, largest, true, stats.lower, opt.mask_up, nullptr, &stats.masked, err)
+                     : stream_fastq(ctx, "run", inputs, opt.chunk_bytes, largest, -1, "",
                          [&](const char *text, uint64_t n, bool final, char *, uint64_t &used, uint64_t &reads, uint64_t &bad) {
                              pf_maskcount_stats st = {};
                              const int rc = pf_maskcount_fastq(ctx, text, n, final ? 1 : 0, stats.lower, opt.mask_up, &used, &st, &bad);

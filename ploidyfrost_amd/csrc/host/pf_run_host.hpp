@@ -64,6 +64,28 @@ struct ColoredCallSetup {
 // 0 = ok, else err holds the line for stderr.
 int colored_call_run(CCDBG &g, ColoredCallSetup &s, std::string &err);
 
+// ---- `run STEP...` / `run-multi STEP...`: step 1 of the workflow folded in (K-TRIMCOUNT, the rule in ../pf_trimrun_rule.hpp) ----
+// The inputs are the raw reads; both passes stream them and trim again through pf_count_fastq[_pair]_trimmed and
+// pf_maskcount_fastq[_pair]_trimmed.  Nothing per record is kept between the passes, so the result does not depend on the chunking.
+struct TrimInputs {
+    std::vector<pf_trim_step> steps;   // none: no trimming, the inputs are read as they are
+    uint32_t phred = 33;
+    bool on() const { return !steps.empty(); }
+};
+// A unit is what one `trim` command of the equivalent chain takes: all single-ended files together, or one pair.
+inline size_t trim_unit_count(size_t n_inputs, bool paired) { return paired ? n_inputs / 2 : 1; }
+// what is refused about the inputs of a trimmed run before a device context exists ("" = none), without the sub-command's name:
+// a pair without its second file, steps or phred K-TRIM refuses, a file given twice (by name or as one file under two names)
+std::string trim_inputs_refusal(const std::vector<std::string> &inputs, bool paired, const TrimInputs &trim);
+// One pass over the raw reads into the open count: masked = false through pf_count_fastq[_pair]_trimmed, true through
+// pf_maskcount_fastq[_pair]_trimmed with [low, up].  paired: the inputs alternate file 1, file 2, and every pair goes through the
+// lock-step stream of pf_trim_host.hpp; else they go through stream_fastq one after the other.  unit_stats (may be null; paired: one
+// entry per input file, else one entry) and masked_stats (may be null) are added to.  0 = ok, else worded in err by `who`.
+int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<std::string> &inputs, bool paired, const TrimInputs &trim, uint64_t chunk_bytes,
+                   uint64_t largest, bool masked, uint32_t low, uint32_t up, pf_trim_stats *unit_stats, pf_maskcount_stats *masked_stats, std::string &err);
+// the `trim:` line of a unit on stderr, in `trim`'s own format: st = the unit's statistics (paired: of file 1 and of file 2)
+std::string trim_unit_line(const pf_trim_stats *st, bool paired);
+
 // ---- run ----
 struct RunOptions {
     // the count (the workflow's defaults, not kmc's) and the graph (tips clipped, isolated unitigs removed)
@@ -81,6 +103,9 @@ struct RunOptions {
     CallSetup call;   // (outprefix, lower and upper are filled in by run_fastq)
     // optional outputs, written through the writers of `mask --db-out` and `build`
     std::string db_out, gfa_out;
+    // STEP...: the inputs are raw reads (paired: -1 / -2, alternating file 1, file 2)
+    TrimInputs trim;
+    bool paired = false;
 };
 struct RunStats {
     pf_count_stats counted = {};       // the first pass, finished with ci / cx / cs
@@ -89,6 +114,7 @@ struct RunStats {
     uint64_t distinct_kept = 0;        // distinct k-mers of the masked reads
     pf_unitig_stats graph = {};
     std::string model_last_line;       // with a model: what the calling run prints last
+    std::vector<pf_trim_stats> trim;   // STEP...: the trimming of the first pass (paired: one entry per input file, else one entry)
 };
 struct RunTimes {
     double count_s = 0, finish_s = 0, table_s = 0, db_out_s = 0, recount_s = 0, refinish_s = 0, graph_s = 0, gfa_out_s = 0, load_s = 0, call_s = 0;
@@ -98,7 +124,9 @@ struct RunTimes {
 std::string run_options_refusal(const RunOptions &opt);
 // The whole of `ploidyfrost run`.  FASTA, gzip and an output that is an input are refused before a device context exists; L is
 // printed on stdout as `mask --auto-cutoffs` prints it; --db-out and --gfa-out are written under temporary names and renamed at the
-// end.  0 = ok, else worded in err (what the calling run itself refuses is worded as `ploidyfrost -g -d` words it).
+// end.  With opt.trim.steps the inputs are the raw reads and every file `run` writes is what `trim` followed by `run` on the trimmed
+// reads of the pairs kept whole (o1 / o2; single-ended: -o) writes.  0 = ok, else worded in err (what the calling run itself refuses
+// is worded as `ploidyfrost -g -d` words it).
 int run_fastq(const std::vector<std::string> &inputs, const std::string &out_prefix, const RunOptions &opt, int device, RunStats &stats, RunTimes *times,
               std::string &err);
 

@@ -94,6 +94,11 @@ int run_multi_fastq(const std::vector<MultiSample> &samples, const std::string &
     if (out_prefix.empty()) { err = "run-multi: no output prefix"; return 1; }
     { const std::string why = run_options_refusal(opt); if (!why.empty()) { err = "run-multi: " + why; return 1; } }
     if (!pf_color::seeds_ok(n_seeds)) { err = "run-multi: " + pf_color::seeds_text(); return 1; }
+    const bool trimming = opt.trim.on();
+    for (const MultiSample &s : samples) {   // (the steps and the offset are global: they are refused with the first sample)
+        const std::string why = trim_inputs_refusal(s.inputs, s.paired, opt.trim);
+        if (!why.empty()) { err = "run-multi: sample " + s.name + ": " + why; return 1; }
+    }
     const uint32_t C = (uint32_t)samples.size();
     const CountOptions copt = count_options_of(opt);
     const std::string tail = ".tmp." + std::to_string((long)getpid());
@@ -141,6 +146,10 @@ int run_multi_fastq(const std::vector<MultiSample> &samples, const std::string &
     // ---- first pass, per sample: count, thresholds; the counters stay resident ----
     stats.colors = C;
     stats.color.assign(C, RunMultiColor{});
+    if (trimming) {
+        stats.trim.resize(C);
+        for (uint32_t c = 0; c < C; ++c) stats.trim[c].assign(samples[c].paired ? samples[c].inputs.size() : 1, pf_trim_stats{});
+    }
     std::vector<Counted> db(C), kept(C);
     std::vector<std::vector<uint64_t>> rows(C);
     for (uint32_t c = 0; c < C; ++c) {
@@ -148,7 +157,12 @@ int run_multi_fastq(const std::vector<MultiSample> &samples, const std::string &
         pf_count_stats counted = {};
         CountTimes ctm;
         std::string e;
-        if (count_stream(ctx, "run-multi", samples[c].inputs, copt, largest, db[c], counted, ctm, e)) return fail(e);
+        if (trimming ? count_stream_with(ctx, "run-multi", copt, [&](std::string &pe) {
+                           return stream_trimmed(ctx, "run-multi", samples[c].inputs, samples[c].paired, opt.trim, opt.chunk_bytes, largest, false, 0, 0,
+                                                 stats.trim[c].data(), nullptr, pe);
+                       }, db[c], counted, ctm, e)
+                     : count_stream(ctx, "run-multi", samples[c].inputs, copt, largest, db[c], counted, ctm, e))
+            return fail(e);
         held.p.push_back(db[c].kmers);
         held.p.push_back(db[c].counts);
         stats.reads += counted.reads;
@@ -186,7 +200,10 @@ int run_multi_fastq(const std::vector<MultiSample> &samples, const std::string &
         if (pf_count_begin(ctx, opt.k, 1, opt.initial_slots) != PF_OK) return dev_fail();
         StreamTimes stm;
         std::string e;
-        if (stream_fastq(ctx, "run-multi", samples[c].inputs, opt.chunk_bytes, largest, -1, "",
+        pf_maskcount_stats masked = {};
+        if (trimming ? stream_trimmed(ctx, "run-multi", samples[c].inputs, samples[c].paired, opt.trim, opt.chunk_bytes, largest, true, stats.color[c].lower,
+                                      opt.mask_up, nullptr, &masked, e)
+                     : stream_fastq(ctx, "run-multi", samples[c].inputs, opt.chunk_bytes, largest, -1, "",
                          [&](const char *text, uint64_t n, bool final, char *, uint64_t &used, uint64_t &reads, uint64_t &bad) {
                              pf_maskcount_stats st = {};
                              const int rc = pf_maskcount_fastq(ctx, text, n, final ? 1 : 0, stats.color[c].lower, opt.mask_up, &used, &st, &bad);
@@ -200,6 +217,8 @@ int run_multi_fastq(const std::vector<MultiSample> &samples, const std::string &
             pf_count_abort(ctx);
             return fail(e);
         }
+        stats.windows_bad += masked.kmers_bad;
+        stats.windows_kept += masked.kmers_kept;
         pf_count_stats st2 = {};
         if (pf_count_finish(ctx, 1, pf_count::COUNTER_MAX, pf_count::COUNTER_MAX, &kept[c].kmers, &kept[c].counts, &kept[c].n, &st2) != PF_OK) {
             const int rc = dev_fail();

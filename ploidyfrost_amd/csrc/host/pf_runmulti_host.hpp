@@ -29,6 +29,7 @@ namespace pfh {
 struct MultiSample {
     std::string name;                  // the colour's name in the colour file
     std::vector<std::string> inputs;   // its FASTQ files
+    bool paired = false;               // STEP... only: the inputs alternate file 1, file 2 (-1 / -2)
 };
 struct RunMultiOptions {
     RunOptions run;          // count, thresholds, graph, scoring, --db-out / --gfa-out prefixes (run.call is not used)
@@ -48,6 +49,7 @@ struct RunMultiStats {
     uint64_t kmers_colored = 0, kmers_unplaced = 0, runs = 0, overflow = 0, color_bytes = 0;
     std::vector<RunMultiColor> color;
     std::string model_last_line;
+    std::vector<std::vector<pf_trim_stats>> trim;   // STEP...: per sample the trimming of its first pass (paired: per input file, else one entry)
 };
 struct RunMultiTimes {
     double count_s = 0, db_out_s = 0, recount_s = 0, union_s = 0, graph_s = 0, color_s = 0, serialise_s = 0, gfa_out_s = 0, load_s = 0, call_s = 0;

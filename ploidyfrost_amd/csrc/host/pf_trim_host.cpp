@@ -104,10 +104,10 @@ int trim_create(int device, pf_ctx **ctx, std::string &err) {
 }
 
 // "who: [file f: ]record R of the chunk: clause" of the device call as the sub-command words it
-std::string reword(pf_ctx *ctx, const std::string &path, uint64_t record_1based) {
+std::string reword(pf_ctx *ctx, const std::string &who, const std::string &path, uint64_t record_1based) {
     const std::string why = pf_last_error(ctx);
     const size_t at = why.find("of the chunk: ");
-    return at != std::string::npos ? "trim: " + path + ": record " + std::to_string(record_1based) + ": " + why.substr(at + 14) : "trim: " + path + ": " + why;
+    return at != std::string::npos ? who + ": " + path + ": record " + std::to_string(record_1based) + ": " + why.substr(at + 14) : who + ": " + path + ": " + why;
 }
 
 // ---- the pair loop's threads ----
@@ -122,12 +122,12 @@ struct PairReader {   // reads one file in blocks of `chunk` bytes, at most two 
     std::string err;
     double read_s = 0;
     std::thread th;
-    void start(const std::string &path, uint64_t chunk) {
+    void start(const std::string &who, const std::string &path, uint64_t chunk) {
         tokens.push(0);
         tokens.push(0);
-        th = std::thread([this, path, chunk] {
+        th = std::thread([this, who, path, chunk] {
             const int fd = open(path.c_str(), O_RDONLY);
-            if (fd < 0) { err = "trim: cannot read " + path + " (" + strerror(errno) + ")"; blocks.close(); return; }
+            if (fd < 0) { err = who + ": cannot read " + path + " (" + strerror(errno) + ")"; blocks.close(); return; }
             for (bool eof = false; !eof;) {
                 int token;
                 if (!tokens.pop(token)) break;
@@ -137,7 +137,7 @@ struct PairReader {   // reads one file in blocks of `chunk` bytes, at most two 
                 while (b.len < chunk) {
                     const ssize_t got = read(fd, b.p.get() + b.len, (size_t)(chunk - b.len));
                     if (got < 0 && errno == EINTR) continue;
-                    if (got < 0) { err = "trim: reading " + path + " (" + strerror(errno) + ")"; break; }
+                    if (got < 0) { err = who + ": reading " + path + " (" + strerror(errno) + ")"; break; }
                     if (got == 0) { eof = true; break; }
                     b.len += (uint64_t)got;
                 }
@@ -249,6 +249,77 @@ int trim_fastq(const std::vector<std::string> &inputs, const std::string &out_pa
     return 0;
 }
 
+int stream_fastq_pair(pf_ctx *ctx, const char *who_c, const std::string &in1, const std::string &in2, uint64_t chunk_bytes, uint64_t largest,
+                      const PairChunkStep &step, PairStreamTimes &tm, std::string &err) {
+    const std::string who = who_c;
+    const std::string inputs[2] = {in1, in2};
+    err.clear();
+    // a call holds what is pending of each file, up to two blocks of it: both stay below the 2^32 bytes of the device call
+    uint64_t chunk = chunk_bytes ? chunk_bytes : MASK_DEFAULT_CHUNK;
+    chunk = std::max<uint64_t>(1, std::min<uint64_t>(chunk, std::max<uint64_t>(largest, 1)));
+    chunk = std::min<uint64_t>(chunk, 1ull << 30);
+    PairReader rd[2];
+    rd[0].start(who, in1, chunk);
+    rd[1].start(who, in2, chunk);
+
+    std::vector<char> pend[2];             // the carry of each file, then the blocks read behind it
+    bool eof[2] = {false, false}, more[2] = {true, true};
+    uint64_t records_before = 0;           // pairs in front of the current call
+    // whole records of what is pending of file f (on the host: only when the other file has ended)
+    auto whole_records = [&](int f) {
+        uint64_t used = 0, recs = 0, bad = 0;
+        (void)pf_mask::index_fastq(pend[f].data(), pend[f].size(), eof[f], used, recs, bad);
+        return recs;
+    };
+    while (err.empty()) {
+        // ---- each file grows by a block while it holds less than a chunk, or held no whole record the last time ----
+        for (int f = 0; f < 2 && err.empty(); ++f)
+            while (!eof[f] && (pend[f].size() < chunk || more[f])) {
+                ReadBlock b;
+                if (!rd[f].blocks.pop(b)) { err = !rd[f].err.empty() ? rd[f].err : who + ": reading " + inputs[f] + " ended early"; break; }
+                pend[f].insert(pend[f].end(), b.p.get(), b.p.get() + b.len);
+                eof[f] = b.eof;
+                more[f] = false;
+                b.p.reset();
+                rd[f].tokens.push(0);
+            }
+        if (!err.empty()) break;
+        const bool final = eof[0] && eof[1];
+        if (final && pend[0].empty() && pend[1].empty()) break;
+        // ---- one file has ended and is used up while the other still holds a whole record ----
+        for (int f = 0; f < 2 && !final; ++f)
+            if (eof[f] && pend[f].empty() && whole_records(1 - f)) {
+                err = who + ": " + inputs[f] + " ends after " + std::to_string(records_before) + " records while " + inputs[1 - f] + " holds more (at least " +
+                      std::to_string(records_before + whole_records(1 - f)) + "): the files of a pair hold the same number of records";
+            }
+        if (!err.empty()) break;
+        // ---- the device stage ----
+        uint64_t used[2] = {0, 0}, recs = 0, bad = 0;
+        const auto t0 = clk::now();
+        const int rc = step(pend[0].data(), pend[0].size(), pend[1].data(), pend[1].size(), final, used, recs, bad);
+        tm.device_s += since(t0);
+        if (rc != PF_OK) {
+            if (!err.empty()) break;   // (the step has worded it)
+            const std::string why = pf_last_error(ctx);
+            if (why.find("different numbers of records") != std::string::npos)
+                err = who + ": " + in1 + " holds " + std::to_string(records_before + whole_records(0)) + " records, " + in2 + " holds " +
+                      std::to_string(records_before + whole_records(1)) + ": the files of a pair hold the same number of records";
+            else
+                err = reword(ctx, who, inputs[bad & 1], records_before + (bad >> 1) + 1);
+            break;
+        }
+        for (int f = 0; f < 2; ++f) pend[f].erase(pend[f].begin(), pend[f].begin() + (ptrdiff_t)used[f]);
+        records_before += recs;
+        if (final) break;
+        if (recs == 0) more[0] = more[1] = true;   // no whole pair: a file that can grows by the next block
+    }
+    // wind down: on an error the threads are let go first
+    for (int f = 0; f < 2; ++f) rd[f].stop();
+    for (int f = 0; f < 2 && err.empty(); ++f) err = rd[f].err;
+    tm.read_s = std::max(rd[0].read_s, rd[1].read_s);
+    return err.empty() ? 0 : 1;
+}
+
 int trim_fastq_pair(const std::string &in1, const std::string &in2, const std::string out_paths[4], const TrimOptions &opt, int device,
                     pf_trim_stats stats[2], TrimTimes *times, std::string &err) {
     stats[0] = stats[1] = pf_trim_stats{};
@@ -267,108 +338,56 @@ int trim_fastq_pair(const std::string &in1, const std::string &in2, const std::s
     OutFiles outs;
     if (outs.open_all(paths, err)) return 1;
 
-    // a call holds what is pending of each file, up to two blocks of it: both stay below the 2^32 bytes of the device call
-    uint64_t chunk = opt.chunk_bytes ? opt.chunk_bytes : MASK_DEFAULT_CHUNK;
-    chunk = std::max<uint64_t>(1, std::min<uint64_t>(chunk, std::max<uint64_t>(largest, 1)));
-    chunk = std::min<uint64_t>(chunk, 1ull << 30);
-    PairReader rd[2];
     PairWriter wr[4];
-    rd[0].start(in1, chunk);
-    rd[1].start(in2, chunk);
     for (int d = 0; d < 4; ++d) wr[d].start(outs.f[d].fd, outs.f[d].tmp);
-
-    std::vector<char> pend[2];             // the carry of each file, then the blocks read behind it
-    bool eof[2] = {false, false}, more[2] = {true, true};
-    uint64_t records_before = 0;           // pairs in front of the current call
-    double device_s = 0;
     std::vector<uint32_t> rb[2], rl[2];
     std::vector<uint64_t> lb[2], le[2];
     std::string log;
-    // whole records of what is pending of file f (on the host: only when the other file has ended)
-    auto whole_records = [&](int f) {
-        uint64_t used = 0, recs = 0, bad = 0;
-        (void)pf_mask::index_fastq(pend[f].data(), pend[f].size(), eof[f], used, recs, bad);
-        return recs;
-    };
-    while (err.empty()) {
-        // ---- each file grows by a block while it holds less than a chunk, or held no whole record the last time ----
-        for (int f = 0; f < 2 && err.empty(); ++f)
-            while (!eof[f] && (pend[f].size() < chunk || more[f])) {
-                ReadBlock b;
-                if (!rd[f].blocks.pop(b)) { err = !rd[f].err.empty() ? rd[f].err : "trim: reading " + inputs[f] + " ended early"; break; }
-                pend[f].insert(pend[f].end(), b.p.get(), b.p.get() + b.len);
-                eof[f] = b.eof;
-                more[f] = false;
-                b.p.reset();
-                rd[f].tokens.push(0);
-            }
-        if (!err.empty()) break;
-        const bool final = eof[0] && eof[1];
-        if (final && pend[0].empty() && pend[1].empty()) break;
-        // ---- one file has ended and is used up while the other still holds a whole record ----
-        for (int f = 0; f < 2 && !final; ++f)
-            if (eof[f] && pend[f].empty() && whole_records(1 - f)) {
-                err = "trim: " + inputs[f] + " ends after " + std::to_string(records_before) + " records while " + inputs[1 - f] + " holds more (at least " +
-                      std::to_string(records_before + whole_records(1 - f)) + "): the files of a pair hold the same number of records";
-            }
-        if (!err.empty()) break;
-        // ---- the device stage ----
-        const uint64_t n[2] = {pend[0].size(), pend[1].size()};
-        std::shared_ptr<char> out[4];
-        char *out_p[4];
-        for (int d = 0; d < 4; ++d) {
-            out[d] = std::shared_ptr<char>(new char[n[d / 2] + 1], std::default_delete<char[]>());
-            out_p[d] = out[d].get();
-        }
-        uint32_t *rb_p[2] = {nullptr, nullptr}, *rl_p[2] = {nullptr, nullptr};
-        if (logs)
-            for (int f = 0; f < 2; ++f) {
-                rb[f].resize(n[f] / 4 + 1);
-                rl[f].resize(n[f] / 4 + 1);
-                rb_p[f] = rb[f].data();
-                rl_p[f] = rl[f].data();
-            }
-        uint64_t out_bytes[4] = {0, 0, 0, 0}, used[2] = {0, 0}, recs = 0, bad = 0;
-        pf_trim_stats st[2] = {};
-        const auto t0 = clk::now();
-        const int rc = pf_trim_fastq_pair(ctx, pend[0].data(), n[0], pend[1].data(), n[1], final ? 1 : 0, opt.steps.data(), (uint32_t)opt.steps.size(),
-                                          opt.phred, out_p, out_bytes, used, rb_p, rl_p, &recs, st, &bad);
-        device_s += since(t0);
-        if (rc != PF_OK) {
-            const std::string why = pf_last_error(ctx);
-            if (why.find("different numbers of records") != std::string::npos)
-                err = "trim: " + in1 + " holds " + std::to_string(records_before + whole_records(0)) + " records, " + in2 + " holds " +
-                      std::to_string(records_before + whole_records(1)) + ": the files of a pair hold the same number of records";
-            else
-                err = reword(ctx, inputs[bad & 1], records_before + (bad >> 1) + 1);
-            break;
-        }
-        add_stats(stats[0], st[0]);
-        add_stats(stats[1], st[1]);
-        if (logs) {
-            log.clear();
-            for (int f = 0; f < 2; ++f) pf_trim::record_lines(pend[f].data(), used[f], recs, lb[f], le[f]);
-            for (uint64_t r = 0; r < recs; ++r)
-                for (int f = 0; f < 2; ++f) trimlog_line(log, pend[f].data(), &lb[f][4 * r], &le[f][4 * r], rb[f][r], rl[f][r]);
-            if (!write_all(outs.f[4].fd, log.data(), log.size(), outs.f[4].tmp, err)) break;
-        }
-        for (int d = 0; d < 4; ++d)
-            if (out_bytes[d]) wr[d].put(WritePiece{out[d], out_bytes[d]});
-        for (int f = 0; f < 2; ++f) pend[f].erase(pend[f].begin(), pend[f].begin() + (ptrdiff_t)used[f]);
-        records_before += recs;
-        if (final) break;
-        if (recs == 0) more[0] = more[1] = true;   // no whole pair: a file that can grows by the next block
-    }
-    // wind down: on an error the threads are let go first
-    for (int f = 0; f < 2; ++f) rd[f].stop();
+    PairStreamTimes ptm;
+    stream_fastq_pair(ctx, "trim", in1, in2, opt.chunk_bytes, largest,
+                      [&](const char *t1, uint64_t n1, const char *t2, uint64_t n2, bool final, uint64_t used[2], uint64_t &recs, uint64_t &bad) {
+                          const char *text[2] = {t1, t2};
+                          const uint64_t n[2] = {n1, n2};
+                          std::shared_ptr<char> out[4];
+                          char *out_p[4];
+                          for (int d = 0; d < 4; ++d) {
+                              out[d] = std::shared_ptr<char>(new char[n[d / 2] + 1], std::default_delete<char[]>());
+                              out_p[d] = out[d].get();
+                          }
+                          uint32_t *rb_p[2] = {nullptr, nullptr}, *rl_p[2] = {nullptr, nullptr};
+                          if (logs)
+                              for (int f = 0; f < 2; ++f) {
+                                  rb[f].resize(n[f] / 4 + 1);
+                                  rl[f].resize(n[f] / 4 + 1);
+                                  rb_p[f] = rb[f].data();
+                                  rl_p[f] = rl[f].data();
+                              }
+                          uint64_t out_bytes[4] = {0, 0, 0, 0};
+                          pf_trim_stats st[2] = {};
+                          const int rc = pf_trim_fastq_pair(ctx, t1, n1, t2, n2, final ? 1 : 0, opt.steps.data(), (uint32_t)opt.steps.size(), opt.phred, out_p,
+                                                            out_bytes, used, rb_p, rl_p, &recs, st, &bad);
+                          if (rc != PF_OK) return rc;
+                          add_stats(stats[0], st[0]);
+                          add_stats(stats[1], st[1]);
+                          if (logs) {
+                              log.clear();
+                              for (int f = 0; f < 2; ++f) pf_trim::record_lines(text[f], used[f], recs, lb[f], le[f]);
+                              for (uint64_t r = 0; r < recs; ++r)
+                                  for (int f = 0; f < 2; ++f) trimlog_line(log, text[f], &lb[f][4 * r], &le[f][4 * r], rb[f][r], rl[f][r]);
+                              if (!write_all(outs.f[4].fd, log.data(), log.size(), outs.f[4].tmp, err)) return (int)PF_ERR_ARG;   // (err is worded)
+                          }
+                          for (int d = 0; d < 4; ++d)
+                              if (out_bytes[d]) wr[d].put(WritePiece{out[d], out_bytes[d]});
+                          return (int)PF_OK;
+                      },
+                      ptm, err);
     for (int d = 0; d < 4; ++d) wr[d].stop();
-    for (int f = 0; f < 2 && err.empty(); ++f) err = rd[f].err;
     for (int d = 0; d < 4 && err.empty(); ++d) err = wr[d].err;
     if (!err.empty() || outs.commit(err)) return 1;
     if (times) {
         times->stream_s = since(t_stream);
-        times->device_s = device_s;
-        times->read_s = std::max(rd[0].read_s, rd[1].read_s);
+        times->device_s = ptm.device_s;
+        times->read_s = ptm.read_s;
         times->write_s = wr[0].write_s + wr[1].write_s + wr[2].write_s + wr[3].write_s;
     }
     return 0;

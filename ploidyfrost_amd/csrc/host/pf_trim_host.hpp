@@ -5,6 +5,7 @@
 #pragma once
 #include <stdint.h>
 
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -39,5 +40,19 @@ int trim_fastq(const std::vector<std::string> &inputs, const std::string &out_pa
 // holds a whole record is refused by name.  The trimlog has record r of file 1, then record r of file 2.
 int trim_fastq_pair(const std::string &in1, const std::string &in2, const std::string out_paths[4], const TrimOptions &opt, int device,
                     pf_trim_stats stats[2], TrimTimes *times, std::string &err);
+
+// The lock-step stream of the two files of a pair, for `trim` and for `run STEP...` / `run-multi STEP...` alike: two reader threads, a
+// carry per file, one device stage.  step(text 1, n1, text 2, n2, final, used[2], records, bad) is one device call on what is pending of
+// both files: it reports the bytes it used of each, the pairs it took and, with a status other than PF_OK, bad = 2 * record + file of a
+// format refusal.  A refusal is worded by `who` with the input's path and the 1-based record (files that end at different record
+// counts: with the counts); a step that has worded err itself keeps its words.
+using PairChunkStep = std::function<int(const char *text1, uint64_t n1, const char *text2, uint64_t n2, bool final, uint64_t used[2], uint64_t &records,
+                                        uint64_t &bad)>;
+struct PairStreamTimes {
+    double device_s = 0;   // inside the step
+    double read_s = 0;     // read() of the inputs, the slower of the two
+};
+int stream_fastq_pair(pf_ctx *ctx, const char *who, const std::string &in1, const std::string &in2, uint64_t chunk_bytes, uint64_t largest,
+                      const PairChunkStep &step, PairStreamTimes &tm, std::string &err);
 
 }  // namespace pfh

@@ -233,7 +233,7 @@ int count_reserve(pf_ctx *ctx, CountState *S, uint64_t add) {
 }
 
 // classes and insert over text[0, n) on the device with the table of reads on the device; counts reset by the caller, n > 0
-static int count_core(pf_ctx *ctx, CountState *S, const char *text, uint64_t n, const uint64_t *off, const uint32_t *len, uint64_t n_reads,
+int count_core(pf_ctx *ctx, CountState *S, const char *text, uint64_t n, const uint64_t *off, const uint32_t *len, uint64_t n_reads,
                       MaskCounts *counts, MaskCounts &h) {
     { const int rc = count_reserve(ctx, S, n); if (rc) return rc; }
     const uint64_t n_tiles = (n + MASK_TILE - 1) / MASK_TILE;
@@ -269,7 +269,7 @@ int count_after_insert(pf_ctx *ctx, CountState *S, const char *who, MaskCounts *
     return PF_OK;
 }
 
-static void count_stats_out(pf_count_stats *stats, CountState *S, uint64_t n_reads, const MaskCounts &h) {
+void count_stats_out(pf_count_stats *stats, CountState *S, uint64_t n_reads, const MaskCounts &h) {
     pf_count_stats st = {};
     st.reads = n_reads;
     st.bases = h.bases;
@@ -284,7 +284,7 @@ static void count_stats_out(pf_count_stats *stats, CountState *S, uint64_t n_rea
     if (stats) *stats = st;
 }
 
-static int count_needs_begin(pf_ctx *ctx, const char *who) {
+int count_needs_begin(pf_ctx *ctx, const char *who) {
     if (ctx->count) return PF_OK;
     pf::CtxErr{ctx} = std::string(who) + ": no count is open (pf_count_begin comes first)";
     return PF_ERR_ARG;

@@ -63,4 +63,19 @@ int count_reserve(pf_ctx *ctx, CountState *S, uint64_t add);
 // the table refused by name
 int count_after_insert(pf_ctx *ctx, CountState *S, const char *who, MaskCounts *counts, MaskCounts &h);
 
+// ---- what K-TRIMCOUNT (pf_trimcount.hip) runs over the table it made ----
+// pf_count.hip: an open count, by `who`; classes and insert over text[0, n) on the device with the table of reads on the device
+// (counts reset by the caller, n > 0; `counts` accumulates over calls, h is their state after this one); this call's statistics and
+// its share of the totals pf_count_finish reports
+int count_needs_begin(pf_ctx *ctx, const char *who);
+int count_core(pf_ctx *ctx, CountState *S, const char *text, uint64_t n, const uint64_t *off, const uint32_t *len, uint64_t n_reads, MaskCounts *counts,
+               MaskCounts &h);
+void count_stats_out(pf_count_stats *stats, CountState *S, uint64_t n_reads, const MaskCounts &h);
+// pf_maskcount.hip: a resident table, an open count on both strands, the same k, each missing piece by `who`; classes, flag and
+// insert; the statistics
+int maskcount_needs(pf_ctx *ctx, const char *who);
+int maskcount_core(pf_ctx *ctx, CountState *S, const char *text, uint64_t n, const uint64_t *off, const uint32_t *len, uint64_t n_reads, uint32_t low,
+                   uint32_t up, MaskCounts *counts, MaskCounts &h);
+void maskcount_stats_out(pf_maskcount_stats *stats, CountState *S, uint64_t n_reads, const MaskCounts &h);
+
 }  // namespace pf

@@ -108,7 +108,7 @@ struct MaskCountTimed {   // brackets everything one call launches as one timed 
 };
 
 // a resident table, an open count on both strands, the same k: each missing piece by name
-static int maskcount_needs(pf_ctx *ctx, const char *who) {
+int maskcount_needs(pf_ctx *ctx, const char *who) {
     auto refuse = [&](const std::string &m) { pf::CtxErr{ctx} = std::string(who) + ": " + m; return (int)PF_ERR_ARG; };
     if (!(ctx->d_tab && ctx->tab_cap && ctx->tab_k >= 3 && ctx->tab_k <= pf_mask::MAX_K)) return refuse("no count table is resident (pf_upload_counts comes first)");
     const CountState *S = count_state(ctx);
@@ -120,7 +120,7 @@ static int maskcount_needs(pf_ctx *ctx, const char *who) {
 }
 
 // classes, flag and insert over text[0, n) on the device with the table of reads on the device; counts reset by the caller, n > 0
-static int maskcount_core(pf_ctx *ctx, CountState *S, const char *text, uint64_t n, const uint64_t *off, const uint32_t *len, uint64_t n_reads,
+int maskcount_core(pf_ctx *ctx, CountState *S, const char *text, uint64_t n, const uint64_t *off, const uint32_t *len, uint64_t n_reads,
                           uint32_t low, uint32_t up, MaskCounts *counts, MaskCounts &h) {
     { const int rc = count_reserve(ctx, S, n); if (rc) return rc; }
     const uint64_t n_tiles = (n + MASK_TILE - 1) / MASK_TILE;
@@ -148,7 +148,7 @@ static int maskcount_core(pf_ctx *ctx, CountState *S, const char *text, uint64_t
 }
 
 // this call's statistics, and its share of the totals pf_count_finish reports
-static void maskcount_stats_out(pf_maskcount_stats *stats, CountState *S, uint64_t n_reads, const MaskCounts &h) {
+void maskcount_stats_out(pf_maskcount_stats *stats, CountState *S, uint64_t n_reads, const MaskCounts &h) {
     pf_maskcount_stats st = {};
     st.reads = n_reads;
     st.bases = h.bases;

@@ -39,6 +39,7 @@ K_MASKCOUNT = K_UNITIG + 1   # PF_K_MASKCOUNT ("k_maskcount"): everything one pf
 MASKCOUNT_STATS = np.dtype([(f, "<u8") for f in ("reads", "bases", "kmers", "kmers_invalid", "kmers_bad", "kmers_kept")])   # pf_maskcount_stats
 K_UNION = K_MASKCOUNT + 1    # PF_K_UNION ("k_union"): everything one pf_kmer_union launches; unit: keys given
 K_COLORSET = K_UNION + 1     # PF_K_COLORSET ("k_colorset"): the kernel of one pf_color_kmers; unit: keys
+K_TRIMCOUNT = K_COLORSET + 1   # PF_K_TRIMCOUNT ("k_trimcount"): everything one pf_*_trimmed / pf_trim_table_* call launches; unit: records
 UNION_TILE = 1024            # pf_runmulti::UNION_TILE: merged positions a block of K-UNION takes
 UNION_ITEMS = 4              # pf_runmulti::UNION_ITEMS: ... and a lane
 COLOR_KMERS_STATS = np.dtype([(f, "<u8") for f in ("kmers", "kmers_colored", "kmers_unplaced")])   # pf_color_kmers_stats
@@ -246,6 +247,13 @@ def load_library() -> C.CDLL:
         "pf_trim_fastq": (i, [vp, vp, u64, i, vp, u32, u32, vp, C.POINTER(u64), C.POINTER(u64), vp, vp, C.POINTER(u64), vp, C.POINTER(u64)]),
         "pf_trim_fastq_pair": (i, [vp, vp, u64, vp, u64, i, vp, u32, u32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(vp), C.POINTER(vp),
                                    C.POINTER(u64), vp, C.POINTER(u64)]),
+        "pf_trim_table_fastq": (i, [vp, vp, u64, i, vp, vp, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp, C.POINTER(u64)]),
+        "pf_trim_table_fastq_pair": (i, [vp, vp, u64, vp, u64, i, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp,
+                                         C.POINTER(u64)]),
+        "pf_count_fastq_trimmed": (i, [vp, vp, u64, i, vp, C.POINTER(u64), vp, vp, C.POINTER(u64)]),
+        "pf_count_fastq_pair_trimmed": (i, [vp, vp, u64, vp, u64, i, vp, C.POINTER(u64), vp, vp, C.POINTER(u64)]),
+        "pf_maskcount_fastq_trimmed": (i, [vp, vp, u64, i, vp, u32, u32, C.POINTER(u64), vp, vp, C.POINTER(u64)]),
+        "pf_maskcount_fastq_pair_trimmed": (i, [vp, vp, u64, vp, u64, i, vp, u32, u32, C.POINTER(u64), vp, vp, C.POINTER(u64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError = header / library mismatch
@@ -272,7 +280,13 @@ DECLARED_SYMBOLS = ["pf_create", "pf_warmup", "pf_destroy", "pf_last_error", "pf
                     "pf_trim_fastq", "pf_trim_fastq_pair", "pf_unitig_build", "pf_unitig_fetch", "pf_unitig_release",
                     "pf_unitig_build_colored", "pf_color_begin", "pf_color_reads", "pf_color_fastq", "pf_color_finish", "pf_color_fetch",
                     "pf_maskcount_reads", "pf_maskcount_fastq", "pf_unitig_text",
-                    "pf_kmer_union", "pf_color_kmers", "pf_release_counts"]
+                    "pf_kmer_union", "pf_color_kmers", "pf_release_counts",
+                    "pf_trim_table_fastq", "pf_trim_table_fastq_pair", "pf_count_fastq_trimmed", "pf_count_fastq_pair_trimmed",
+                    "pf_maskcount_fastq_trimmed", "pf_maskcount_fastq_pair_trimmed"]
+
+
+class TrimPlan(C.Structure):   # pf_trim_plan
+    _fields_ = [("steps", C.c_void_p), ("n_steps", C.c_uint32), ("phred", C.c_uint32)]
 
 
 def trim_steps(steps) -> np.ndarray:
@@ -707,6 +721,96 @@ class Device:
             e.bad_record = bad.value
             raise e
         return used.value, {f: int(stats[0][f]) for f in MASKCOUNT_STATS.names}
+
+    # ---- K-TRIMCOUNT: K-TRIM folded into K-COUNT / K-MASKCOUNT (pf_trimrun_rule.hpp) ----
+    @staticmethod
+    def _trim_plan(steps, phred):
+        steps = trim_steps(steps)
+        return steps, TrimPlan(steps.ctypes.data if len(steps) else None, len(steps), phred)   # (the array is kept alive by the caller)
+
+    def _raise_bad(self, st, bad):
+        e = DeviceError(st, self.L.pf_last_error(self.h).decode())
+        e.bad_record = bad.value
+        raise e
+
+    def trim_table_fastq(self, text, steps, phred: int = 33, final: bool = True, read_off=None, read_len=None):
+        """pf_trim_table_fastq on one chunk of raw FASTQ: dict with read_off (u64) / read_len (u32) = the table of the reads handed on
+        (sequence bytes [seq_begin + b, seq_begin + e) of every kept record), n_reads, bytes_used, n_records, stats (pf_trim_stats).
+        read_off / read_len: device tensors to fill instead of new numpy arrays (one entry per record of the chunk)."""
+        if isinstance(text, (bytes, bytearray)):
+            text = np.frombuffer(bytes(text), dtype=np.uint8)
+        steps, plan = self._trim_plan(steps, phred)
+        n = int(text.shape[0])
+        cap = n // 4 + 1
+        off = np.zeros(cap, dtype=np.uint64) if read_off is None else read_off
+        ln = np.zeros(cap, dtype=np.uint32) if read_len is None else read_len
+        stats = np.zeros(1, dtype=TRIM_STATS)
+        n_reads, used, recs, bad = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        st = self.L.pf_trim_table_fastq(self.h, _ptr(text) if n else None, n, int(final), C.addressof(plan), _ptr(off), _ptr(ln), C.byref(n_reads),
+                                        C.byref(used), C.byref(recs), stats.ctypes.data, C.byref(bad))
+        if st != PF_OK:
+            self._raise_bad(st, bad)
+        return dict(read_off=off[: n_reads.value], read_len=ln[: n_reads.value], n_reads=n_reads.value, bytes_used=used.value, n_records=recs.value,
+                    stats={f: int(stats[0][f]) for f in TRIM_STATS.names})
+
+    def trim_table_fastq_pair(self, text1, text2, steps, phred: int = 33, final: bool = True, read_off=None, read_len=None):
+        """pf_trim_table_fastq_pair on one chunk of each file of a pair: read_off / read_len = [file 1, file 2] (a record is handed on only
+        when the records of both files are kept: both tables have n_reads entries), bytes_used = [file 1, file 2], n_records,
+        stats = [file 1, file 2].  bad_record of a DeviceError: 2 * record + file."""
+        texts = [np.frombuffer(bytes(t), dtype=np.uint8) if isinstance(t, (bytes, bytearray)) else t for t in (text1, text2)]
+        steps, plan = self._trim_plan(steps, phred)
+        n = [int(t.shape[0]) for t in texts]
+        cap = min(n) // 4 + 1
+        off = [np.zeros(cap, dtype=np.uint64) for _ in range(2)] if read_off is None else read_off
+        ln = [np.zeros(cap, dtype=np.uint32) for _ in range(2)] if read_len is None else read_len
+        off_p = (C.c_void_p * 2)(*[_ptr(x) for x in off])
+        len_p = (C.c_void_p * 2)(*[_ptr(x) for x in ln])
+        stats = np.zeros(2, dtype=TRIM_STATS)
+        n_reads, used, recs, bad = C.c_uint64(), (C.c_uint64 * 2)(), C.c_uint64(), C.c_uint64()
+        st = self.L.pf_trim_table_fastq_pair(self.h, _ptr(texts[0]) if n[0] else None, n[0], _ptr(texts[1]) if n[1] else None, n[1], int(final),
+                                             C.addressof(plan), off_p, len_p, C.byref(n_reads), used, C.byref(recs), stats.ctypes.data, C.byref(bad))
+        if st != PF_OK:
+            self._raise_bad(st, bad)
+        m = n_reads.value
+        return dict(read_off=[x[:m] for x in off], read_len=[x[:m] for x in ln], n_reads=m, bytes_used=[used[0], used[1]], n_records=recs.value,
+                    stats=[{f: int(stats[j][f]) for f in TRIM_STATS.names} for j in range(2)])
+
+    def _counted_trimmed(self, masked, texts, steps, phred, final, low, up):
+        texts = [np.frombuffer(bytes(t), dtype=np.uint8) if isinstance(t, (bytes, bytearray)) else t for t in texts]
+        steps, plan = self._trim_plan(steps, phred)
+        n = [int(t.shape[0]) for t in texts]
+        pair = len(texts) == 2
+        dt = MASKCOUNT_STATS if masked else COUNT_STATS
+        tstats, stats = np.zeros(2, dtype=TRIM_STATS), np.zeros(1, dtype=dt)
+        used, bad = (C.c_uint64 * 2)(), C.c_uint64()
+        args = [self.h]
+        for t, m in zip(texts, n):
+            args += [_ptr(t) if m else None, m]
+        args += [int(final), C.addressof(plan)] + ([low, up] if masked else []) + [used, tstats.ctypes.data, stats.ctypes.data, C.byref(bad)]
+        fn = getattr(self.L, "pf_%s_fastq%s_trimmed" % ("maskcount" if masked else "count", "_pair" if pair else ""))
+        st = fn(*args)
+        if st != PF_OK:
+            self._raise_bad(st, bad)
+        ts = [{f: int(tstats[j][f]) for f in TRIM_STATS.names} for j in range(2 if pair else 1)]
+        return ([used[0], used[1]] if pair else used[0]), (ts if pair else ts[0]), {f: int(stats[0][f]) for f in dt.names}
+
+    def count_fastq_trimmed(self, text, steps, phred: int = 33, final: bool = True):
+        """pf_count_fastq_trimmed on one chunk of raw FASTQ: (bytes_used, trimming statistics, this call's counting statistics) -- trim_fastq
+        followed by count_fastq on its output, without that output."""
+        return self._counted_trimmed(False, [text], steps, phred, final, 0, 0)
+
+    def count_fastq_pair_trimmed(self, text1, text2, steps, phred: int = 33, final: bool = True):
+        """pf_count_fastq_pair_trimmed: ([bytes_used 1, 2], [trimming statistics 1, 2], counting statistics): the both-kept records of
+        both files are counted (o1 and o2 of trim_fastq_pair)."""
+        return self._counted_trimmed(False, [text1, text2], steps, phred, final, 0, 0)
+
+    def maskcount_fastq_trimmed(self, text, steps, low: int, up: int = MASK_NO_UPPER, phred: int = 33, final: bool = True):
+        """pf_maskcount_fastq_trimmed: (bytes_used, trimming statistics, K-MASKCOUNT's statistics) on the trimmed reads of the chunk"""
+        return self._counted_trimmed(True, [text], steps, phred, final, low, up)
+
+    def maskcount_fastq_pair_trimmed(self, text1, text2, steps, low: int, up: int = MASK_NO_UPPER, phred: int = 33, final: bool = True):
+        """pf_maskcount_fastq_pair_trimmed: the pair form of maskcount_fastq_trimmed"""
+        return self._counted_trimmed(True, [text1, text2], steps, phred, final, low, up)
 
     def unitig_text(self):
         """pf_unitig_text: (device address, bytes) of the text a held graph keeps on the device until unitig_release"""

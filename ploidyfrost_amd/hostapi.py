@@ -45,7 +45,8 @@ DECLARED_SYMBOLS = ["pfh_open", "pfh_close", "pfh_last_error", "pfh_set_output_d
                     "pfh_count_lut_prefix_len", "pfh_count_cut_text", "pfh_build_fastq", "pfh_unitig_build_host", "pfh_unitig_no_room_text",
                     "pfh_build_colored_fastq", "pfh_build_colored_host", "pfh_bfg_colors_bytes", "pfh_color_no_room_text",
                     "pfh_run_defaults", "pfh_run_fastq", "pfh_count_masked_host", "pfh_run_multi_fastq", "pfh_union_host",
-                    "pfh_trim_fastq", "pfh_trim_fastq_pair", "pfh_trim_parse_step", "pfh_trim_refusal_text", "pfh_trim_read", "pfh_trim_fastq_chunk"]
+                    "pfh_trim_fastq", "pfh_trim_fastq_pair", "pfh_trim_parse_step", "pfh_trim_refusal_text", "pfh_trim_read", "pfh_trim_fastq_chunk",
+                    "pfh_run_fastq_trimmed", "pfh_run_multi_fastq_trimmed", "pfh_trim_table_chunk", "pfh_trim_table_chunk_pair", "pfh_trim_table_clause_text"]
 
 
 class RunOptions(C.Structure):   # pfh_run_options (include/ploidyfrost_host.h)
@@ -247,6 +248,14 @@ def load_library() -> C.CDLL:
     L.pfh_trim_refusal_text.argtypes = [C.c_int]
     L.pfh_trim_read.argtypes = [vp, u64, vp, u32, u32, C.POINTER(u32), C.POINTER(u32)]
     L.pfh_trim_fastq_chunk.argtypes = [vp, u64, C.c_int, vp, u32, u32, vp, C.POINTER(u64), C.POINTER(u64), vp, vp, u64, C.POINTER(u64), vp, C.POINTER(u64)]
+    L.pfh_run_fastq_trimmed.argtypes = [C.POINTER(C.c_char_p), u32, C.c_int, vp, u32, u32, C.c_char_p, C.POINTER(RunOptions), C.c_int, vp, vp]
+    L.pfh_run_multi_fastq_trimmed.argtypes = [C.POINTER(C.c_char_p), vp, vp, u32, C.POINTER(C.c_char_p), vp, u32, u32, C.c_char_p, C.POINTER(RunOptions),
+                                              C.POINTER(FilterMultiOpts), C.c_int, C.c_int, vp, vp, vp]
+    L.pfh_trim_table_chunk.argtypes = [vp, u64, C.c_int, vp, u32, u32, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp, C.POINTER(u64)]
+    L.pfh_trim_table_chunk_pair.argtypes = [vp, u64, vp, u64, C.c_int, vp, u32, u32, C.POINTER(vp), C.POINTER(vp), u64, C.POINTER(u64), C.POINTER(u64),
+                                            C.POINTER(u64), vp, C.POINTER(u64)]
+    L.pfh_trim_table_clause_text.restype = C.c_char_p
+    L.pfh_trim_table_clause_text.argtypes = [C.c_int]
     _lib = L
     return L
 
@@ -558,6 +567,44 @@ def trim_fastq_chunk(text: bytes, steps, phred: int = 33, final: bool = True):
                 begin=begin[: recs.value].tolist(), len=ln[: recs.value].tolist(), stats={f: int(v) for f, v in zip(TRIM_STATS_FIELDS, stats)})
 
 
+TRIM_TABLE_CLAUSES = MASK_CLAUSES + ("pair_count",)   # pf_mask::Clause, then pf_trimrun::CLAUSE_PAIR_COUNT
+
+
+def trim_table_chunk(text, steps, phred: int = 33, final: bool = True, text2=None):
+    """What `run STEP...` hands on from one chunk of raw FASTQ, by the host's plain restatement (pfh_trim_table_chunk; no device;
+    csrc/pf_trimrun_rule.hpp): dict with clause (a name of TRIM_TABLE_CLAUSES), message, bad_record, read_off / read_len (the table of the
+    reads handed on: the kept interval of the sequence line of every kept record), n_reads, bytes_used, n_records, stats.  text2: the
+    chunk of the second file of a pair (pfh_trim_table_chunk_pair) -- read_off / read_len / bytes_used / stats are then [file 1,
+    file 2], a record goes on only when it is kept in both files, and bad_record = 2 * record + file."""
+    L = load_library()
+    st = trim_parse_steps(steps)
+    texts = [np.frombuffer(bytes(x), dtype=np.uint8) for x in ((text,) if text2 is None else (text, text2))]
+    n = [len(x) for x in texts]
+    cap = min(n) // 4 + 1
+    off = [np.zeros(cap, dtype=np.uint64) for _ in texts]
+    ln = [np.zeros(cap, dtype=np.uint32) for _ in texts]
+    stats = np.zeros((len(texts), len(TRIM_STATS_FIELDS)), dtype=np.uint64)
+    n_reads, recs, bad, used = C.c_uint64(), C.c_uint64(), C.c_uint64(), (C.c_uint64 * 2)()
+    sp, sn = (st.ctypes.data if len(st) else None), len(st)
+    if text2 is None:
+        clause = L.pfh_trim_table_chunk(texts[0].ctypes.data if n[0] else None, n[0], int(final), sp, sn, phred, off[0].ctypes.data, ln[0].ctypes.data, cap,
+                                        C.byref(n_reads), used, C.byref(recs), stats.ctypes.data, C.byref(bad))
+    else:
+        off_p = (C.c_void_p * 2)(*[x.ctypes.data for x in off])
+        len_p = (C.c_void_p * 2)(*[x.ctypes.data for x in ln])
+        clause = L.pfh_trim_table_chunk_pair(texts[0].ctypes.data if n[0] else None, n[0], texts[1].ctypes.data if n[1] else None, n[1], int(final), sp, sn,
+                                             phred, off_p, len_p, cap, C.byref(n_reads), used, C.byref(recs), stats.ctypes.data, C.byref(bad))
+    if clause < 0:
+        raise ValueError(L.pfh_last_error(None).decode())
+    m = n_reads.value
+    per = [dict(read_off=off[f][:m].tolist(), read_len=ln[f][:m].tolist(), bytes_used=used[f],
+                stats={k: int(v) for k, v in zip(TRIM_STATS_FIELDS, stats[f])}) for f in range(len(texts))]
+    out = dict(clause=TRIM_TABLE_CLAUSES[clause], message=L.pfh_trim_table_clause_text(clause).decode(), bad_record=bad.value, n_reads=m, n_records=recs.value)
+    for key in ("read_off", "read_len", "bytes_used", "stats"):
+        out[key] = per[0][key] if text2 is None else [x[key] for x in per]
+    return out
+
+
 def trim_fastq(inputs, out: str, steps, phred: int = 33, trimlog=None, chunk_bytes: int = 0) -> dict:
     """`ploidyfrost trim -i ... -o out STEP...` (pfh_trim_fastq): the reads of the FASTQ file(s) `inputs`, one after the other,
     quality-trimmed by `steps` (Trimmomatic's words) into `out`; trimlog: a file with one line per record.  Returns the statistics.  A
@@ -706,12 +753,21 @@ def build_graph(inputs, out_prefix: str, k: int = 25, clip_tips: bool = False, d
 def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 ** 9, cs: int = 10000, q: float = 0.998, mask_upper=None,
               keep_tips: bool = False, keep_isolated: bool = False, g=None, z: int = 8, M: float = 2.0, D: float = -1.0, G: float = -3.0,
               threads: int = 1, model=None, model_only: bool = False, db_out=None, gfa_out=None, chunk_bytes: int = 0,
-              initial_slots: int = 0) -> dict:
+              initial_slots: int = 0, steps=None, phred: int = 33, pairs=None) -> dict:
     """`ploidyfrost run` (pfh_run_fastq): reads to ploidy estimate in one process -- the FASTQ file(s) `inputs` counted, the thresholds
     derived, the k-mers of the masked reads counted (K-MASKCOUNT), the graph built and the single-sample calling run made on one device
     context; PloidyFrost_output/<out_prefix>_*.txt in the working directory.  model: None, "cov" or "fre".  Returns the fields of the
-    command's stderr line ("lower" and "upper" among them).  A refusal raises RuntimeError by name."""
+    command's stderr line ("lower" and "upper" among them).  A refusal raises RuntimeError by name.
+    steps (Trimmomatic's words, as trim_fastq takes them): `run STEP...` (pfh_run_fastq_trimmed) -- the inputs are raw reads, trimmed on
+    the device on the way into both passes; pairs = [(r1.fq, r2.fq), ...] instead of inputs (None then): the records of a pair go on
+    only when both are kept.  The result then has "trim" as well: the statistics of every unit (one dict for all single-ended inputs;
+    per pair a list of two, file 1 and file 2), as the command's `trim:` lines give them."""
     L = load_library()
+    if pairs is not None:
+        if inputs is not None:
+            raise ValueError("run_reads: either inputs or pairs")
+        inputs = [f for p in pairs for f in p]
+    st = trim_parse_steps(steps) if steps is not None else np.zeros(0, dtype=TRIM_STEP)
     paths, n = _paths(inputs)
     o = RunOptions()
     L.pfh_run_defaults(C.byref(o))
@@ -730,31 +786,46 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
     o.db_out = None if db_out is None else os.fsencode(db_out)
     o.gfa_out = None if gfa_out is None else os.fsencode(gfa_out)
     stats = np.zeros(len(RUN_STATS_FIELDS), dtype=np.uint64)
-    rc = L.pfh_run_fastq(paths, n, os.fsencode(out_prefix), C.byref(o), 0, stats.ctypes.data)
+    if steps is None and pairs is None:
+        rc = L.pfh_run_fastq(paths, n, os.fsencode(out_prefix), C.byref(o), 0, stats.ctypes.data)
+        if rc:
+            raise RuntimeError(L.pfh_last_error(None).decode())
+        return {f: int(v) for f, v in zip(RUN_STATS_FIELDS, stats)}
+    per = np.zeros((max(n, 1), len(TRIM_STATS_FIELDS)), dtype=np.uint64)
+    rc = L.pfh_run_fastq_trimmed(paths, n, int(pairs is not None), st.ctypes.data if len(st) else None, len(st), int(phred), os.fsencode(out_prefix),
+                                 C.byref(o), 0, stats.ctypes.data, per.ctypes.data)
     if rc:
         raise RuntimeError(L.pfh_last_error(None).decode())
-    return {f: int(v) for f, v in zip(RUN_STATS_FIELDS, stats)}
+    out = {f: int(v) for f, v in zip(RUN_STATS_FIELDS, stats)}
+    rows = [{f: int(v) for f, v in zip(TRIM_STATS_FIELDS, row)} for row in per]
+    out["trim"] = [rows[0]] if pairs is None else [[rows[2 * u], rows[2 * u + 1]] for u in range(len(pairs))]
+    return out
 
 
 def run_multi_reads(samples, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 ** 9, cs: int = 10000, q: float = 0.998, mask_upper=None,
                     keep_tips: bool = False, keep_isolated: bool = False, g=None, z: int = 8, M: float = 2.0, D: float = -1.0, G: float = -3.0,
                     threads: int = 1, model=None, model_only: bool = False, filter_multi=None, each_color: bool = False, db_out=None, gfa_out=None,
-                    chunk_bytes: int = 0, initial_slots: int = 0) -> dict:
+                    chunk_bytes: int = 0, initial_slots: int = 0, steps=None, phred: int = 33, pairs=None) -> dict:
     """`ploidyfrost run-multi` (pfh_run_multi_fastq): reads of several samples to one estimate per sample in one process.  samples: a
     list of (name, file or list of files), a sample a colour in the order given.  Every sample is counted and its thresholds derived,
     the k-mers of its masked reads counted (K-MASKCOUNT), their union taken (K-UNION), the coloured graph built and coloured per
     distinct k-mer (K-COLORSET) and the coloured calling run made on one device context; PloidyFrost_output/<out_prefix>_*.txt in the
     working directory.  model: None, "cov" or "fre", behind filter_multi = the options of filter_multi_opts as a dict.  Returns the
     fields of the command's stderr line (RUN_MULTI_STATS_FIELDS) and under "color" one dict of RUN_MULTI_COLOR_FIELDS per sample.  A
-    refusal raises RuntimeError by name."""
+    refusal raises RuntimeError by name.
+    steps: `run-multi STEP...` (pfh_run_multi_fastq_trimmed) -- the files are raw reads, trimmed on the way into both passes; pairs: the
+    names of the samples whose files are pairs (file 1, file 2, file 1, ...).  The result then has "trim": per sample the statistics of
+    its units, as run_reads gives them."""
     L = load_library()
-    names, counts, flat = [], [], []
+    names, counts, flat, paired = [], [], [], []
     for name, files in samples:
         if isinstance(files, (str, bytes, os.PathLike)):
             files = [files]
         names.append(os.fsencode(name))
         counts.append(len(files))
         flat.extend(files)
+        paired.append(int(pairs is not None and name in pairs))
+    st = trim_parse_steps(steps) if steps is not None else np.zeros(0, dtype=TRIM_STEP)
     c_names = (C.c_char_p * max(len(names), 1))(*names)
     n_of = np.ascontiguousarray(counts, dtype=np.uint32)
     paths, _ = _paths(flat)
@@ -780,12 +851,27 @@ def run_multi_reads(samples, out_prefix: str, k: int = 25, ci: int = 1, cx: int 
     o.gfa_out = None if gfa_out is None else os.fsencode(gfa_out)
     stats = np.zeros(len(RUN_MULTI_STATS_FIELDS), dtype=np.uint64)
     per = np.zeros((max(len(names), 1), len(RUN_MULTI_COLOR_FIELDS)), dtype=np.uint64)
-    rc = L.pfh_run_multi_fastq(c_names, n_of.ctypes.data if len(names) else None, len(names), paths, os.fsencode(out_prefix), C.byref(o),
-                               C.byref(multi) if multi is not None else None, int(each_color), 0, stats.ctypes.data, per.ctypes.data)
+    trimmed = steps is not None or pairs is not None
+    per_in = np.zeros((max(len(flat), 1), len(TRIM_STATS_FIELDS)), dtype=np.uint64)
+    if trimmed:
+        pair_of = np.ascontiguousarray(paired, dtype=np.int32)
+        rc = L.pfh_run_multi_fastq_trimmed(c_names, n_of.ctypes.data if len(names) else None, pair_of.ctypes.data if len(names) else None, len(names), paths,
+                                           st.ctypes.data if len(st) else None, len(st), int(phred), os.fsencode(out_prefix), C.byref(o),
+                                           C.byref(multi) if multi is not None else None, int(each_color), 0, stats.ctypes.data, per.ctypes.data,
+                                           per_in.ctypes.data)
+    else:
+        rc = L.pfh_run_multi_fastq(c_names, n_of.ctypes.data if len(names) else None, len(names), paths, os.fsencode(out_prefix), C.byref(o),
+                                   C.byref(multi) if multi is not None else None, int(each_color), 0, stats.ctypes.data, per.ctypes.data)
     if rc:
         raise RuntimeError(L.pfh_last_error(None).decode())
     out = {f: int(v) for f, v in zip(RUN_MULTI_STATS_FIELDS, stats)}
     out["color"] = [{f: int(v) for f, v in zip(RUN_MULTI_COLOR_FIELDS, per[c])} for c in range(len(names))]
+    if trimmed:
+        rows = [{f: int(v) for f, v in zip(TRIM_STATS_FIELDS, row)} for row in per_in]
+        out["trim"], at = [], 0
+        for c in range(len(names)):
+            out["trim"].append([[rows[at + 2 * u], rows[at + 2 * u + 1]] for u in range(counts[c] // 2)] if paired[c] else [rows[at]])
+            at += counts[c]
     return out
 
 
