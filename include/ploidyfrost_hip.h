@@ -72,6 +72,7 @@ enum pf_kernel {
     PF_K_UNION, /* K-UNION: everything one pf_kmer_union launches (check, the count and write kernels of every merge, their scans), timed as one launch; unit: keys given */
     PF_K_COLORSET, /* K-COLORSET: the kernel of one pf_color_kmers; unit: keys */
     PF_K_TRIMCOUNT, /* K-TRIMCOUNT: everything one pf_trim_table_fastq* / pf_count_fastq*_trimmed / pf_maskcount_fastq*_trimmed launches (index, intervals, table, then K-COUNT's or K-MASKCOUNT's core), timed as one launch; unit: records */
+    PF_K_INFLATE, /* K-INFLATE: everything one pf_inflate_bgzf launches (headers, scan, inflate with the CRC), timed as one launch; unit: inflated bytes */
     PF_K_COUNT_
 };
 int pf_enable_timing(pf_ctx *, int on);
@@ -410,7 +411,26 @@ int pf_maskcount_fastq_trimmed(pf_ctx *, const char *text, uint64_t n_bytes, int
 int pf_maskcount_fastq_pair_trimmed(pf_ctx *, const char *text1, uint64_t n1, const char *text2, uint64_t n2, int final, const pf_trim_plan *plan,
                                     uint32_t low, uint32_t up, uint64_t bytes_used[2], pf_trim_stats trim_stats[2], pf_maskcount_stats *stats,
                                     uint64_t *bad_record);
+/* K-INFLATE: blocked gzip (BGZF: what bgzip, bcl2fastq2 and BCL Convert write) inflated on the device, where pf_*_fastq read their text.
+ * The rule -- the member header, RFC 1951, the refusals by name -- is csrc/pf_inflate_rule.hpp; the decoder one lane runs is
+ * csrc/pf_inflate_core.hpp, shared with the host.  One wavefront per member; the CRC-32 of every member's text is checked against
+ * its trailer.  Timed as one launch of PF_K_INFLATE per call; unit: inflated bytes. */
+typedef struct pf_inflate_stats {
+    uint64_t members, bytes_in, bytes_out, blocks_stored, blocks_fixed, blocks_dynamic;
+} pf_inflate_stats;
+/* comp[0, n_bytes): whole BGZF members, member m = comp[member_off[m], member_off[m+1]); member_off has n_members + 1 entries.
+ * out receives the members' texts one behind the other; *out_bytes = their sum.  out_cap too small: PF_ERR_OVERFLOW, *out_bytes = needed.
+ * A refused member: PF_ERR_ARG, *bad_member = the smallest offender, pf_last_error names the clause ("pf_inflate_bgzf: member M of the
+ * call: <clause>"); out is then unspecified.
+ * comp, member_off, out: [host|dev] */
+int pf_inflate_bgzf(pf_ctx *, const uint8_t *comp, uint64_t n_bytes, const uint64_t *member_off, uint64_t n_members,
+                    char *out, uint64_t out_cap, uint64_t *out_bytes, pf_inflate_stats *stats, uint64_t *bad_member);
+
 int pf_copy_to_host(pf_ctx *, void *dst, const void *src_dev, size_t bytes);
+/* Device memory of the caller's own (freed with pf_device_free), and a copy between any two places (host or device) on the launch
+ * stream, waited for: what the host layer keeps the inflated text of `--gz` in between two calls. */
+int pf_device_alloc(pf_ctx *, size_t bytes, void **out);
+int pf_copy(pf_ctx *, void *dst, const void *src, size_t bytes);
 
 /* K1/K2: builds the device hash table from the database records (exact k-mers as stored, any
  * order).  Records with count outside [min_count, max_count] are not retrievable, as in

@@ -521,6 +521,28 @@ struct pfh_colors;
 uint64_t pfh_colors_check_footprints(const struct pfh_colors *, const uint32_t *succ, const pf_bfs_record *records, uint64_t n_records,
                                      const uint32_t *pool, uint32_t complex_size, uint64_t slice, uint64_t *first_bad);
 
+/* ---- blocked gzip (K-INFLATE, `--gz`): the rule without a device (csrc/pf_inflate_rule.hpp) ----
+ * Every call returns a clause of pf_inflate::Clause (0 = none), worded by pfh_inflate_clause_text.
+ * pfh_inflate_parse_member: one BGZF member header at bytes[0, n), n = bytes up to the end of the file;
+ *   fields = { payload offset 12 + XLEN, member length BSIZE + 1, CRC32, ISIZE }.
+ * pfh_inflate_member: one member's deflate stream payload[0, n_in) -> out[0, isize); nothing outside either range is touched whatever
+ *   the bytes say.  *produced = bytes written, blocks = { stored, fixed, dynamic }.  The CRC is not looked at.
+ * pfh_inflate_bgzf_member: a whole member: header, stream, length and CRC-32; out holds 65536 bytes.
+ * pfh_inflate_crc32 / _sliced: the CRC-32 of n bytes, plainly and from `n_lanes` slices as the kernel's lanes compute it.
+ * pfh_inflate_file_clause: what the first bytes of a file say with `--gz`: 0 plain, 1 blocked gzip, 2 refused with *clause. */
+/* `--gz` for the calls that take the sequencer's files: after pfh_reads_gz(1) the next pfh_count_fastq, pfh_trim_fastq[_pair],
+ * pfh_run_fastq[_trimmed] or pfh_run_multi_fastq[_trimmed] of this thread reads inputs with the gzip magic as blocked gzip and inflates
+ * them on the device; the call takes the switch back.  (pfh_trim_read and pfh_trim_fastq_chunk, which build the same options, take it
+ * back as well and ignore it.) */
+void pfh_reads_gz(int on);
+int pfh_inflate_parse_member(const uint8_t *bytes, uint64_t n, uint32_t fields[4]);
+int pfh_inflate_member(const uint8_t *payload, uint32_t n_in, uint8_t *out, uint32_t isize, uint32_t *produced, uint32_t blocks[3]);
+int pfh_inflate_bgzf_member(const uint8_t *bytes, uint64_t n, uint8_t *out, uint32_t *out_len, uint32_t blocks[3]);
+uint32_t pfh_inflate_crc32(const uint8_t *bytes, uint64_t n);
+uint32_t pfh_inflate_crc32_sliced(const uint8_t *bytes, uint32_t n, uint32_t n_lanes);
+int pfh_inflate_file_clause(const uint8_t *first, uint64_t n_first, uint64_t file_size, int *clause);
+const char *pfh_inflate_clause_text(int clause);
+
 /* Kmer::hash(seed) of the reference's Bifrost build (wyhash over the 8-byte left-aligned k-mer) */
 uint64_t pfh_bifrost_kmer_hash(uint64_t left_aligned_kmer, uint64_t seed);
 

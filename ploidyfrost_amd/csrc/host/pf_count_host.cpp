@@ -51,7 +51,7 @@ int count_stream(pf_ctx *ctx, const char *who_c, const std::vector<std::string> 
                                 reads = st.reads;
                                 return rc;
                             },
-                            stm, e);
+                            stm, e, opt.gz);
     }, out, stats, tm, err);
 }
 
@@ -150,7 +150,7 @@ int count_fastq(const std::vector<std::string> &inputs, const std::string &out_p
     std::vector<std::string> outputs = {out_prefix + ".kmc_pre", out_prefix + ".kmc_suf"};
     if (!opt.hist.empty()) outputs.push_back(opt.hist);
     uint64_t largest = 0;
-    if (fastq_preflight("count", "counted", inputs, outputs, largest, err)) return 1;
+    if (fastq_preflight("count", "counted", inputs, outputs, largest, err, opt.gz)) return 1;
 
     pf_ctx *ctx = nullptr;
     if (pf_create(device, &ctx) != PF_OK) {

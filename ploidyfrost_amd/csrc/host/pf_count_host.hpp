@@ -23,6 +23,7 @@ struct CountOptions {   // kmc's letters and defaults
     uint64_t chunk_bytes = 0;     // 0: MASK_DEFAULT_CHUNK
     uint64_t initial_slots = 0;   // 0: twice the first chunk's bytes
     std::string hist;             // --hist: the histogram file of the finished counters
+    bool gz = false;              // --gz: inputs with the gzip magic are blocked gzip, inflated on the device (pf_gz_host.hpp)
 };
 struct CountTimes {
     double stream_s = 0;   // first byte read to the last chunk counted (wall)
@@ -51,7 +52,7 @@ int counted_rows(pf_ctx *ctx, const Counted &db, const CountOptions &opt, std::v
 // <prefix>.kmc_pre / <prefix>.kmc_suf from the finished counters: encoded on the device block by block, written under temporary
 // names and renamed at the end; nothing is left under any of the four names after a refusal
 int write_counted(pf_ctx *ctx, const char *who, const std::string &prefix, const Counted &db, const CountOptions &opt, std::string &err);
-// the whole of `ploidyfrost count`.  FASTA, gzip and an output that is an input are refused before a device context exists
+// the whole of `ploidyfrost count`.  FASTA, gzip (with opt.gz: gzip that is not blocked gzip) and an output that is an input are refused before a device context exists
 int count_fastq(const std::vector<std::string> &inputs, const std::string &out_prefix, const CountOptions &opt, int device, pf_count_stats &stats,
                 CountTimes *times, std::string &err);
 

@@ -19,6 +19,7 @@
 #include "../pf_mask_rule.hpp"
 #include "../pf_trim_rule.hpp"
 #include "../pf_trimrun_rule.hpp"
+#include "../pf_inflate_rule.hpp"
 #include "pf_trim_host.hpp"
 #include "pf_trace.hpp"
 #include "../pf_model_rows.hpp"
@@ -250,6 +251,11 @@ uint32_t pfh_cutoffs(const pfh_run *r, int *lower, int *upper, uint32_t cap) {
 }
 void *pfh_device_ctx(pfh_run *r) { return r->cdbg->device(); }
 
+// ---- blocked-gzip inputs: the next reads call of this thread takes them (`--gz`) ----
+static thread_local bool g_reads_gz = false;
+void pfh_reads_gz(int on) { g_reads_gz = on != 0; }
+static bool take_reads_gz() { const bool gz = g_reads_gz; g_reads_gz = false; return gz; }
+
 // ---- reads masked against the database (K-MASK) ----------------------------------------------------
 int pfh_mask_fastq(const char *db_prefix, const char *const *inputs, uint32_t n_inputs, const char *out_path, uint32_t low, uint32_t up,
                    int auto_lower, uint64_t chunk_bytes, int device, pf_mask_stats *stats, uint32_t *lower_used) {
@@ -295,6 +301,7 @@ static pfh::TrimOptions trim_options(const pf_trim_step *steps, uint32_t n_steps
     opt.phred = phred;
     opt.trimlog = trimlog ? trimlog : "";
     opt.chunk_bytes = chunk_bytes;
+    opt.gz = take_reads_gz();
     return opt;
 }
 int pfh_trim_fastq(const char *const *inputs, uint32_t n_inputs, const char *out_path, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred,
@@ -386,6 +393,7 @@ int pfh_count_fastq(const char *const *inputs, uint32_t n_inputs, const char *ou
         pfh::CountOptions opt = count_options(k, ci, cx, cs, both_strands);
         opt.chunk_bytes = chunk_bytes;
         opt.initial_slots = initial_slots;
+        opt.gz = take_reads_gz();
         if (hist) opt.hist = hist;
         pf_count_stats st = {};
         const int rc = pfh::count_fastq(in, out_prefix, opt, device, st, nullptr, g_open_err);
@@ -524,6 +532,7 @@ static int run_fastq_c(const char *who, const char *const *inputs, uint32_t n_in
         for (uint32_t i = 0; i < n_inputs; ++i) in.push_back(inputs[i] ? inputs[i] : "");
         pfh::RunOptions opt;
         run_options_from(o, opt);
+        opt.gz = take_reads_gz();
         opt.call.threads = o->threads ? o->threads : 1;
         if (o->model_source >= 0) {
             opt.call.model.on = true;
@@ -568,6 +577,7 @@ static int run_multi_fastq_c(const char *who, const char *const *names, const ui
         }
         pfh::RunMultiOptions mopt;
         pfh::RunOptions &opt = mopt.run;
+        opt.gz = take_reads_gz();
         run_options_from(o, opt);
         trim_inputs_from(steps, n_steps, phred, opt.trim);
         mopt.call.threads = o->threads ? o->threads : 1;
@@ -1554,6 +1564,35 @@ double pfh_model_color_ploidy(const pfh_run *r, int color) {
     const pfh::CDBG::ColorFit *cf = color_fit_of(r, color);
     return cf ? cf->ploidy : 0;
 }
+
+// ---- blocked gzip: the rule without a device ----------------------------------------------------------
+int pfh_inflate_parse_member(const uint8_t *bytes, uint64_t n, uint32_t fields[4]) {
+    pf_inflate::Header h;
+    const int c = pf_inflate::parse_member(bytes, n, &h);
+    if (fields) { fields[0] = h.payload_off; fields[1] = h.member_len; fields[2] = h.crc; fields[3] = h.isize; }
+    return c;
+}
+int pfh_inflate_member(const uint8_t *payload, uint32_t n_in, uint8_t *out, uint32_t isize, uint32_t *produced, uint32_t blocks[3]) {
+    int c = 0;
+    pf_inflate::Blocks b;
+    uint32_t made = 0;
+    pf_inflate::inflate_member(payload, n_in, out, isize, &c, &b, &made);
+    if (produced) *produced = made;
+    if (blocks) { blocks[0] = b.stored; blocks[1] = b.fixed; blocks[2] = b.dynamic; }
+    return c;
+}
+int pfh_inflate_bgzf_member(const uint8_t *bytes, uint64_t n, uint8_t *out, uint32_t *out_len, uint32_t blocks[3]) {
+    pf_inflate::Blocks b{0, 0, 0};
+    const int c = pf_inflate::inflate_bgzf_member(bytes, n, out, out_len, &b);
+    if (blocks) { blocks[0] = b.stored; blocks[1] = b.fixed; blocks[2] = b.dynamic; }
+    return c;
+}
+uint32_t pfh_inflate_crc32(const uint8_t *bytes, uint64_t n) { return pf_inflate::crc32(bytes, n); }
+uint32_t pfh_inflate_crc32_sliced(const uint8_t *bytes, uint32_t n, uint32_t n_lanes) { return pf_inflate::crc32_sliced(bytes, n, n_lanes ? n_lanes : 1); }
+int pfh_inflate_file_clause(const uint8_t *first, uint64_t n_first, uint64_t file_size, int *clause) {
+    return pf_inflate::file_clause_gz(first, n_first, file_size, clause);
+}
+const char *pfh_inflate_clause_text(int clause) { return pf_inflate::clause_text(clause); }
 
 uint64_t pfh_bifrost_kmer_hash(uint64_t left_aligned_kmer, uint64_t seed) { return pfh::bifrost_kmer_hash(left_aligned_kmer, seed); }
 

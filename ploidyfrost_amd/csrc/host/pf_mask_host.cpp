@@ -17,6 +17,8 @@
 #include "../pf_mask_rule.hpp"
 #include "pf_count_host.hpp"
 #include "pf_cutoffs.hpp"
+#include "pf_gz_host.hpp"
+#include "../pf_inflate_rule.hpp"
 #include "pf_host_graph.hpp"
 
 namespace pfh {
@@ -31,6 +33,8 @@ struct Block {     // reader -> device: bytes [HEAD, HEAD + len) of input buffer
     uint64_t len = 0;
     size_t input = 0;
     bool eof = false;
+    bool gz = false;   // blocked gzip: `len` bytes of whole members, described by g
+    GzBlock g;
 };
 struct Piece {     // device -> writer: `len` bytes at `p`; buf >= 0: an output buffer to hand back, else `own` keeps them alive
     int buf = -1;
@@ -62,7 +66,7 @@ bool same_file(const std::string &a, const std::string &b) {
 }
 
 int fastq_preflight(const char *who, const char *what, const std::vector<std::string> &inputs, const std::vector<std::string> &outputs,
-                    uint64_t &largest, std::string &err) {
+                    uint64_t &largest, std::string &err, bool gz) {
     const std::string w = who;
     auto text = [&](int clause) {   // (the FASTA and gzip texts end in what is done with FASTQ: "masked")
         std::string t = pf_mask::clause_text(clause);
@@ -71,15 +75,33 @@ int fastq_preflight(const char *who, const char *what, const std::vector<std::st
     };
     largest = 0;
     if (inputs.empty()) { err = w + ": no input"; return 1; }
+    std::vector<unsigned char> head(gz ? 65536 : 2);
     for (const std::string &in : inputs) {
         for (const std::string &out : outputs)
             if (same_file(in, out)) { err = w + ": " + in + ": " + text(pf_mask::CLAUSE_SAME_PATH); return 1; }
         const int fd = open(in.c_str(), O_RDONLY);
         if (fd < 0) { err = w + ": cannot read " + in + " (" + strerror(errno) + ")"; return 1; }
-        unsigned char first[2];
-        const ssize_t got = read(fd, first, 2);
+        unsigned char *first = head.data();
+        ssize_t got = read(fd, first, 2);
         struct stat st;
-        if (fstat(fd, &st) == 0) largest = std::max<uint64_t>(largest, (uint64_t)st.st_size);
+        uint64_t size = 0;
+        if (fstat(fd, &st) == 0) size = (uint64_t)st.st_size;
+        largest = std::max<uint64_t>(largest, size);
+        if (gz && got == 2 && first[0] == 0x1f && first[1] == 0x8b) {   // with --gz: blocked gzip, or refused by name
+            while ((size_t)got < head.size()) {
+                const ssize_t more = read(fd, first + got, head.size() - (size_t)got);
+                if (more < 0 && errno == EINTR) continue;
+                if (more <= 0) break;
+                got += more;
+            }
+            close(fd);
+            int clause = 0;
+            if (pf_inflate::file_clause_gz(first, (uint64_t)got, std::max<uint64_t>(size, (uint64_t)got), &clause) == pf_inflate::FILE_REFUSED) {
+                err = w + ": " + in + ": member 1, byte 0: " + pf_inflate::clause_text(clause);
+                return 1;
+            }
+            continue;
+        }
         close(fd);
         const int clause = pf_mask::file_clause(first, got > 0 ? (uint64_t)got : 0);
         if (clause) { err = w + ": " + in + ": record 1: " + text(clause); return 1; }
@@ -88,27 +110,32 @@ int fastq_preflight(const char *who, const char *what, const std::vector<std::st
 }
 
 int stream_fastq(pf_ctx *ctx, const char *who, const std::vector<std::string> &inputs, uint64_t chunk_bytes, uint64_t largest, int out_fd,
-                 const std::string &out_name, const ChunkStep &step, StreamTimes &tm, std::string &err) {
+                 const std::string &out_name, const ChunkStep &step, StreamTimes &tm, std::string &err, bool gz) {
     return stream_fastq_sized(ctx, who, inputs, chunk_bytes, largest, out_fd, out_name,
                               [&](const char *text, uint64_t n, bool final, char *out, uint64_t &used, uint64_t &reads, uint64_t &bad, uint64_t &out_len) {
                                   const int rc = step(text, n, final, out, used, reads, bad);
                                   out_len = used;
                                   return rc;
                               },
-                              tm, err);
+                              tm, err, gz);
 }
 
 int stream_fastq_sized(pf_ctx *ctx, const char *who_c, const std::vector<std::string> &inputs, uint64_t chunk_bytes, uint64_t largest, int out_fd,
-                       const std::string &out_name, const SizedChunkStep &step, StreamTimes &tm, std::string &err) {
+                       const std::string &out_name, const SizedChunkStep &step, StreamTimes &tm, std::string &err, bool gz) {
     const std::string who = who_c;
     err.clear();   // (a caller's `err` may still hold the text of an earlier call: the loop below runs while it is empty)
     const bool writes = out_fd >= 0;
     uint64_t chunk = chunk_bytes ? chunk_bytes : MASK_DEFAULT_CHUNK;
-    chunk = std::max<uint64_t>(1, std::min<uint64_t>(chunk, std::max<uint64_t>(largest, 1)));   // (no gigabyte of pinned memory for a small file)
+    std::vector<char> is_gz(inputs.size(), 0);   // with --gz: the inputs that start with the gzip magic are blocked gzip (the preflight has looked)
+    bool any_gz = false;
+    for (size_t f = 0; gz && f < inputs.size(); ++f) any_gz |= (is_gz[f] = gz_magic(inputs[f])) != 0;
+    // (no gigabyte of pinned memory for a small file; a blocked-gzip file inflates to a multiple of its size)
+    chunk = std::max<uint64_t>(1, std::min<uint64_t>(chunk, std::max<uint64_t>(any_gz ? std::max<uint64_t>(largest * 8, GZ_MEMBER_MAX) : largest, 1)));
     chunk = std::min<uint64_t>(chunk, 1ull << 31);                                               // a chunk and its carry stay below the 2^32 of the device calls
+    const uint64_t in_bytes = any_gz ? std::max(chunk, gz_buffer_bytes(chunk)) : chunk;          // (--chunk-bytes counts inflated bytes)
     ChunkBuf in_buf[2], out_buf[2];
     for (int i = 0; i < 2; ++i)
-        if (!in_buf[i].alloc(ctx, MASK_HEAD + chunk) || (writes && !out_buf[i].alloc(ctx, MASK_HEAD + chunk + 16))) { err = who + ": no memory for the chunk buffers"; return 1; }
+        if (!in_buf[i].alloc(ctx, MASK_HEAD + in_bytes) || (writes && !out_buf[i].alloc(ctx, MASK_HEAD + chunk + 16))) { err = who + ": no memory for the chunk buffers"; return 1; }
 
     Chan<int> free_in, free_out;
     Chan<Block> blocks;
@@ -119,6 +146,24 @@ int stream_fastq_sized(pf_ctx *ctx, const char *who_c, const std::vector<std::st
     // reader: the next block of the next input is read while the device works on this one
     std::thread reader([&] {
         for (size_t f = 0; f < inputs.size(); ++f) {
+            if (is_gz[f]) {   // whole members, hopped by BSIZE; nothing is decoded here
+                GzReader gr;
+                if (!gr.open_file(who, inputs[f], read_err)) break;
+                for (bool eof = false; !eof;) {
+                    Block b;
+                    if (!free_in.pop(b.buf)) return;
+                    b.input = f;
+                    b.gz = true;
+                    const auto t0 = clk::now();
+                    const bool ok = gr.next(in_buf[b.buf].p + MASK_HEAD, in_bytes, chunk, b.g, read_err);
+                    read_s += since(t0);
+                    if (!ok) { blocks.close(); return; }
+                    b.len = b.g.len;
+                    eof = b.eof = b.g.eof;
+                    blocks.push(std::move(b));
+                }
+                continue;
+            }
             const int fd = open(inputs[f].c_str(), O_RDONLY);
             if (fd < 0) { read_err = who + ": cannot read " + inputs[f] + " (" + strerror(errno) + ")"; break; }
             for (bool eof = false; !eof;) {
@@ -161,17 +206,33 @@ int stream_fastq_sized(pf_ctx *ctx, const char *who_c, const std::vector<std::st
 
     // device: carry + block -> step -> piece
     std::vector<char> carry;
+    std::unique_ptr<GzText> gzt;   // blocked gzip: the text and its carry stay on the device
     uint64_t records_before = 0;   // whole records of the current input in front of the current chunk
     size_t cur_input = 0;
     Block b;
     while (err.empty() && blocks.pop(b)) {
         if (b.input != cur_input) { cur_input = b.input; records_before = 0; }
-        const uint64_t n = carry.size() + b.len;
+        uint64_t n = carry.size() + b.len;
         const char *text;
         char *out = nullptr;
         Piece piece;
         std::shared_ptr<std::vector<char>> big_in;
-        if (carry.size() <= MASK_HEAD) {   // the carried record in front of the block, in place
+        if (b.gz) {
+            if (!gzt) gzt.reset(new GzText(ctx));
+            const auto t0 = clk::now();
+            const bool ok = gzt->append(who, inputs[b.input], in_buf[b.buf].p + MASK_HEAD, b.g, err);
+            tm.device_s += since(t0);
+            if (!ok) break;
+            text = gzt->text();
+            n = gzt->size();
+            if (writes && n + 1 <= MASK_HEAD + chunk + 16) {
+                if (!free_out.pop(piece.buf)) break;
+                out = out_buf[piece.buf].p;
+            } else if (writes) {
+                piece.own = std::make_shared<std::vector<char>>(n + 1);
+                out = piece.own->data();
+            }
+        } else if (carry.size() <= MASK_HEAD) {   // the carried record in front of the block, in place
             char *p = in_buf[b.buf].p + MASK_HEAD - carry.size();
             memcpy(p, carry.data(), carry.size());
             text = p;
@@ -189,6 +250,7 @@ int stream_fastq_sized(pf_ctx *ctx, const char *who_c, const std::vector<std::st
                 out = piece.own->data();
             }
         }
+        tm.text_on_device = b.gz;
         uint64_t used = 0, bad = 0, reads = 0, out_len = 0;
         const auto t0 = clk::now();
         const int rc = n ? step(text, n, b.eof, out, used, reads, bad, out_len) : (int)PF_OK;
@@ -203,7 +265,8 @@ int stream_fastq_sized(pf_ctx *ctx, const char *who_c, const std::vector<std::st
             break;
         }
         // a chunk that holds no whole record gives used = 0: everything is carried and the next chunk is this one plus the next block
-        carry.assign(text + used, text + n);
+        if (b.gz) gzt->use(used);
+        else carry.assign(text + used, text + n);
         free_in.push(b.buf);
         records_before += reads;
         piece.p = out;

@@ -43,6 +43,7 @@ CountOptions count_options_of(const RunOptions &opt) {
     c.both_strands = true;
     c.chunk_bytes = opt.chunk_bytes;
     c.initial_slots = opt.initial_slots;
+    c.gz = opt.gz;
     return c;
 }
 
@@ -170,7 +171,8 @@ void add_masked_stats(pf_maskcount_stats &a, const pf_maskcount_stats &b) {
 }  // namespace
 
 int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<std::string> &inputs, bool paired, const TrimInputs &trim, uint64_t chunk_bytes,
-                   uint64_t largest, bool masked, uint32_t low, uint32_t up, pf_trim_stats *unit_stats, pf_maskcount_stats *masked_stats, std::string &err) {
+                   uint64_t largest, bool masked, uint32_t low, uint32_t up, pf_trim_stats *unit_stats, pf_maskcount_stats *masked_stats, std::string &err,
+                   bool gz) {
     const pf_trim_plan plan = {trim.steps.data(), (uint32_t)trim.steps.size(), trim.phred};
     if (!paired) {
         StreamTimes stm;
@@ -187,7 +189,7 @@ int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<std::string> 
                                 if (masked_stats) add_masked_stats(*masked_stats, ms);
                                 return (int)PF_OK;
                             },
-                            stm, err);
+                            stm, err, gz);
     }
     for (size_t u = 0; u + 1 < inputs.size(); u += 2) {
         PairStreamTimes ptm;
@@ -204,7 +206,7 @@ int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<std::string> 
                                   if (masked_stats) add_masked_stats(*masked_stats, ms);
                                   return (int)PF_OK;
                               },
-                              ptm, err))
+                              ptm, err, gz))
             return 1;
     }
     return 0;
@@ -237,7 +239,7 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
     if (!opt.db_out.empty()) { outputs.push_back(opt.db_out + ".kmc_pre"); outputs.push_back(opt.db_out + ".kmc_suf"); }
     if (!gfa_path.empty()) outputs.push_back(gfa_path);
     uint64_t largest = 0;
-    if (fastq_preflight("run", "read", inputs, outputs, largest, err)) return 1;
+    if (fastq_preflight("run", "read", inputs, outputs, largest, err, opt.gz)) return 1;
 
     pf_ctx *ctx = nullptr;
     if (pf_create(device, &ctx) != PF_OK) {
@@ -262,7 +264,7 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
         Counted db;
         CountTimes ctm;
         if (trimming ? count_stream_with(ctx, "run", copt, [&](std::string &e) {
-                           return stream_trimmed(ctx, "run", inputs, opt.paired, opt.trim, opt.chunk_bytes, largest, false, 0, 0, stats.trim.data(), nullptr, e);
+                           return stream_trimmed(ctx, "run", inputs, opt.paired, opt.trim, opt.chunk_bytes, largest, false, 0, 0, stats.trim.data(), nullptr, e, opt.gz);
                        }, db, stats.counted, ctm, err)
                      : count_stream(ctx, "run", inputs, copt, largest, db, stats.counted, ctm, err))
             return 1;
@@ -298,7 +300,7 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
         const auto t_stream = clk::now();
         if (pf_count_begin(ctx, opt.k, 1, opt.initial_slots) != PF_OK) return dev_fail();
         StreamTimes stm;
-        if (trimming ? stream_trimmed(ctx, "run", inputs, opt.paired, opt.trim, opt.chunk_bytes, largest, true, stats.lower, opt.mask_up, nullptr, &stats.masked, err)
+        if (trimming ? stream_trimmed(ctx, "run", inputs, opt.paired, opt.trim, opt.chunk_bytes, largest, true, stats.lower, opt.mask_up, nullptr, &stats.masked, err, opt.gz)
                      : stream_fastq(ctx, "run", inputs, opt.chunk_bytes, largest, -1, "",
                          [&](const char *text, uint64_t n, bool final, char *, uint64_t &used, uint64_t &reads, uint64_t &bad) {
                              pf_maskcount_stats st = {};
@@ -313,7 +315,7 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
                              stats.masked.kmers_kept += st.kmers_kept;
                              return (int)PF_OK;
                          },
-                         stm, err)) {
+                         stm, err, opt.gz)) {
             pf_count_abort(ctx);
             return fail(err);
         }

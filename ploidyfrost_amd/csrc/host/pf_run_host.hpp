@@ -82,7 +82,8 @@ std::string trim_inputs_refusal(const std::vector<std::string> &inputs, bool pai
 // lock-step stream of pf_trim_host.hpp; else they go through stream_fastq one after the other.  unit_stats (may be null; paired: one
 // entry per input file, else one entry) and masked_stats (may be null) are added to.  0 = ok, else worded in err by `who`.
 int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<std::string> &inputs, bool paired, const TrimInputs &trim, uint64_t chunk_bytes,
-                   uint64_t largest, bool masked, uint32_t low, uint32_t up, pf_trim_stats *unit_stats, pf_maskcount_stats *masked_stats, std::string &err);
+                   uint64_t largest, bool masked, uint32_t low, uint32_t up, pf_trim_stats *unit_stats, pf_maskcount_stats *masked_stats, std::string &err,
+                   bool gz = false);
 // the `trim:` line of a unit on stderr, in `trim`'s own format: st = the unit's statistics (paired: of file 1 and of file 2)
 std::string trim_unit_line(const pf_trim_stats *st, bool paired);
 
@@ -106,6 +107,7 @@ struct RunOptions {
     // STEP...: the inputs are raw reads (paired: -1 / -2, alternating file 1, file 2)
     TrimInputs trim;
     bool paired = false;
+    bool gz = false;   // --gz: inputs with the gzip magic are blocked gzip, inflated on the device in both passes (pf_gz_host.hpp)
 };
 struct RunStats {
     pf_count_stats counted = {};       // the first pass, finished with ci / cx / cs
@@ -122,7 +124,7 @@ struct RunTimes {
 
 // the refusal of the options that needs no file ("" = none): k outside 5 .. 31 (a database is implied), g, ci / cx / cs
 std::string run_options_refusal(const RunOptions &opt);
-// The whole of `ploidyfrost run`.  FASTA, gzip and an output that is an input are refused before a device context exists; L is
+// The whole of `ploidyfrost run`.  FASTA, gzip (with opt.gz: gzip that is not blocked gzip) and an output that is an input are refused before a device context exists; L is
 // printed on stdout as `mask --auto-cutoffs` prints it; --db-out and --gfa-out are written under temporary names and renamed at the
 // end.  With opt.trim.steps the inputs are the raw reads and every file `run` writes is what `trim` followed by `run` on the trimmed
 // reads of the pairs kept whole (o1 / o2; single-ended: -o) writes.  0 = ok, else worded in err (what the calling run itself refuses

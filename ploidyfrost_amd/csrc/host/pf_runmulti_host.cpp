@@ -46,6 +46,7 @@ CountOptions count_options_of(const RunOptions &opt) {
     c.both_strands = true;
     c.chunk_bytes = opt.chunk_bytes;
     c.initial_slots = opt.initial_slots;
+    c.gz = opt.gz;
     return c;
 }
 
@@ -115,7 +116,7 @@ int run_multi_fastq(const std::vector<MultiSample> &samples, const std::string &
     }
     if (!gfa_path.empty()) { outputs.push_back(gfa_path); outputs.push_back(col_path); }
     uint64_t largest = 0;
-    if (fastq_preflight("run-multi", "read", all_inputs, outputs, largest, err)) return 1;
+    if (fastq_preflight("run-multi", "read", all_inputs, outputs, largest, err, opt.gz)) return 1;
     for (uint32_t c = 0; c < C; ++c)   // one file under two names
         for (uint32_t d = 0; d < c; ++d)
             for (const std::string &a : samples[c].inputs)
@@ -159,7 +160,7 @@ int run_multi_fastq(const std::vector<MultiSample> &samples, const std::string &
         std::string e;
         if (trimming ? count_stream_with(ctx, "run-multi", copt, [&](std::string &pe) {
                            return stream_trimmed(ctx, "run-multi", samples[c].inputs, samples[c].paired, opt.trim, opt.chunk_bytes, largest, false, 0, 0,
-                                                 stats.trim[c].data(), nullptr, pe);
+                                                 stats.trim[c].data(), nullptr, pe, opt.gz);
                        }, db[c], counted, ctm, e)
                      : count_stream(ctx, "run-multi", samples[c].inputs, copt, largest, db[c], counted, ctm, e))
             return fail(e);
@@ -202,7 +203,7 @@ int run_multi_fastq(const std::vector<MultiSample> &samples, const std::string &
         std::string e;
         pf_maskcount_stats masked = {};
         if (trimming ? stream_trimmed(ctx, "run-multi", samples[c].inputs, samples[c].paired, opt.trim, opt.chunk_bytes, largest, true, stats.color[c].lower,
-                                      opt.mask_up, nullptr, &masked, e)
+                                      opt.mask_up, nullptr, &masked, e, opt.gz)
                      : stream_fastq(ctx, "run-multi", samples[c].inputs, opt.chunk_bytes, largest, -1, "",
                          [&](const char *text, uint64_t n, bool final, char *, uint64_t &used, uint64_t &reads, uint64_t &bad) {
                              pf_maskcount_stats st = {};
@@ -213,7 +214,7 @@ int run_multi_fastq(const std::vector<MultiSample> &samples, const std::string &
                              stats.windows_kept += st.kmers_kept;
                              return (int)PF_OK;
                          },
-                         stm, e)) {
+                         stm, e, opt.gz)) {
             pf_count_abort(ctx);
             return fail(e);
         }

@@ -58,7 +58,7 @@ struct RunMultiTimes {
 // the refusals that need neither a file nor a device ("" = none): no sample, more than 1024, a sample without input, a name twice, a
 // file in two samples by name
 std::string run_multi_samples_refusal(const std::vector<MultiSample> &samples);
-// The whole of `ploidyfrost run-multi`.  Everything above, FASTA, gzip, a file given twice under two names and an output that is an
+// The whole of `ploidyfrost run-multi`.  Everything above, FASTA, gzip (with opt.run.gz: gzip that is not blocked gzip), a file given twice under two names and an output that is an
 // input are refused before a device context exists; every L_c is printed on its own line on stdout, in colour order; --db-out
 // (<prefix><c>.kmc_pre / .kmc_suf) and --gfa-out (<prefix>.gfa, <prefix>.bfg_colors) are written under temporary names and renamed at
 // the end.  0 = ok, else worded in err (what the calling run itself refuses is worded as `ploidyfrost -g -f -d` words it).

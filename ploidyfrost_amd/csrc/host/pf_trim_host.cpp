@@ -12,6 +12,7 @@
 #include <thread>
 
 #include "../pf_trim_rule.hpp"
+#include "pf_gz_host.hpp"
 #include "pf_mask_host.hpp"
 
 static_assert(sizeof(pf_trim_step) == sizeof(pf_trim::Step) && sizeof(pf_trim_stats) == sizeof(pf_trim::Stats), "the rule header restates the ABI's records");
@@ -94,7 +95,7 @@ int trim_preflight(const std::vector<std::string> &inputs, const std::vector<std
         for (size_t j = 0; j < i; ++j)
             if (same_file(outputs[i], outputs[j])) { err = "trim: two outputs have the same path (" + outputs[i] + ")"; return 1; }
     }
-    return fastq_preflight("trim", "trimmed", inputs, outputs, largest, err);
+    return fastq_preflight("trim", "trimmed", inputs, outputs, largest, err, opt.gz);
 }
 
 int trim_create(int device, pf_ctx **ctx, std::string &err) {
@@ -115,6 +116,7 @@ struct ReadBlock {
     std::unique_ptr<char[]> p;
     uint64_t len = 0;
     bool eof = false;
+    GzBlock g;   // of a blocked-gzip file: `len` bytes of whole members
 };
 struct PairReader {   // reads one file in blocks of `chunk` bytes, at most two ahead of the device stage
     Chan<int> tokens;
@@ -122,9 +124,31 @@ struct PairReader {   // reads one file in blocks of `chunk` bytes, at most two 
     std::string err;
     double read_s = 0;
     std::thread th;
-    void start(const std::string &who, const std::string &path, uint64_t chunk) {
+    void start(const std::string &who, const std::string &path, uint64_t chunk, bool gz) {
         tokens.push(0);
         tokens.push(0);
+        if (gz) {   // whole members, hopped by BSIZE; nothing is decoded here
+            th = std::thread([this, who, path, chunk] {
+                GzReader gr;
+                if (!gr.open_file(who, path, err)) { blocks.close(); return; }
+                const uint64_t cap = gz_buffer_bytes(chunk);
+                for (bool eof = false; !eof;) {
+                    int token;
+                    if (!tokens.pop(token)) break;
+                    ReadBlock b;
+                    b.p.reset(new char[cap]);
+                    const auto t0 = clk::now();
+                    const bool ok = gr.next(b.p.get(), cap, chunk, b.g, err);
+                    read_s += since(t0);
+                    if (!ok) break;
+                    b.len = b.g.len;
+                    eof = b.eof = b.g.eof;
+                    blocks.push(std::move(b));
+                }
+                blocks.close();
+            });
+            return;
+        }
         th = std::thread([this, who, path, chunk] {
             const int fd = open(path.c_str(), O_RDONLY);
             if (fd < 0) { err = who + ": cannot read " + path + " (" + strerror(errno) + ")"; blocks.close(); return; }
@@ -220,6 +244,7 @@ int trim_fastq(const std::vector<std::string> &inputs, const std::string &out_pa
     std::vector<uint32_t> rb, rl;
     std::vector<uint64_t> lb, le;
     std::string log, log_err;
+    std::vector<char> fetched;
     StreamTimes st_tm;
     stream_fastq_sized(ctx, "trim", inputs, opt.chunk_bytes, largest, outs.f[0].fd, outs.f[0].tmp,
                        [&](const char *text, uint64_t n, bool final, char *out, uint64_t &used, uint64_t &reads, uint64_t &bad, uint64_t &out_len) {
@@ -230,6 +255,11 @@ int trim_fastq(const std::vector<std::string> &inputs, const std::string &out_pa
                            if (rc != PF_OK) return rc;
                            add_stats(stats, st);
                            if (logs && log_err.empty()) {   // on the host, from the (begin, len) arrays
+                               if (st_tm.text_on_device) {   // (inflated on the device: the log alone takes the text across)
+                                   fetched.resize(used);
+                                   if (used && pf_copy(ctx, fetched.data(), text, (size_t)used) != PF_OK) return (int)PF_ERR_HIP;
+                                   text = fetched.data();
+                               }
                                pf_trim::record_lines(text, used, reads, lb, le);
                                log.clear();
                                for (uint64_t r = 0; r < reads; ++r) trimlog_line(log, text, &lb[4 * r], &le[4 * r], rb[r], rl[r]);
@@ -237,7 +267,7 @@ int trim_fastq(const std::vector<std::string> &inputs, const std::string &out_pa
                            }
                            return (int)PF_OK;
                        },
-                       st_tm, err);
+                       st_tm, err, opt.gz);
     if (err.empty()) err = log_err;
     if (!err.empty() || outs.commit(err)) return 1;
     if (times) {
@@ -250,34 +280,52 @@ int trim_fastq(const std::vector<std::string> &inputs, const std::string &out_pa
 }
 
 int stream_fastq_pair(pf_ctx *ctx, const char *who_c, const std::string &in1, const std::string &in2, uint64_t chunk_bytes, uint64_t largest,
-                      const PairChunkStep &step, PairStreamTimes &tm, std::string &err) {
+                      const PairChunkStep &step, PairStreamTimes &tm, std::string &err, bool gz) {
     const std::string who = who_c;
     const std::string inputs[2] = {in1, in2};
     err.clear();
+    const bool is_gz[2] = {gz && gz_magic(in1), gz && gz_magic(in2)};   // (each file of the pair by its own first bytes)
     // a call holds what is pending of each file, up to two blocks of it: both stay below the 2^32 bytes of the device call
     uint64_t chunk = chunk_bytes ? chunk_bytes : MASK_DEFAULT_CHUNK;
-    chunk = std::max<uint64_t>(1, std::min<uint64_t>(chunk, std::max<uint64_t>(largest, 1)));
+    const uint64_t bound = (is_gz[0] || is_gz[1]) ? std::max<uint64_t>(largest * 8, GZ_MEMBER_MAX) : largest;   // (blocked gzip inflates to a multiple of the file)
+    chunk = std::max<uint64_t>(1, std::min<uint64_t>(chunk, std::max<uint64_t>(bound, 1)));
     chunk = std::min<uint64_t>(chunk, 1ull << 30);
     PairReader rd[2];
-    rd[0].start(who, in1, chunk);
-    rd[1].start(who, in2, chunk);
+    rd[0].start(who, in1, chunk, is_gz[0]);
+    rd[1].start(who, in2, chunk, is_gz[1]);
 
     std::vector<char> pend[2];             // the carry of each file, then the blocks read behind it
+    std::unique_ptr<GzText> gzt[2];        // the same of a blocked-gzip file: on the device
+    for (int f = 0; f < 2; ++f)
+        if (is_gz[f]) gzt[f].reset(new GzText(ctx));
+    auto size_of = [&](int f) { return is_gz[f] ? gzt[f]->size() : (uint64_t)pend[f].size(); };
+    auto text_of = [&](int f) { return is_gz[f] ? gzt[f]->text() : pend[f].data(); };
     bool eof[2] = {false, false}, more[2] = {true, true};
     uint64_t records_before = 0;           // pairs in front of the current call
     // whole records of what is pending of file f (on the host: only when the other file has ended)
     auto whole_records = [&](int f) {
         uint64_t used = 0, recs = 0, bad = 0;
-        (void)pf_mask::index_fastq(pend[f].data(), pend[f].size(), eof[f], used, recs, bad);
+        std::vector<char> fetched;
+        std::string e;
+        if (is_gz[f]) (void)gzt[f]->fetch(fetched, e);
+        const std::vector<char> &t = is_gz[f] ? fetched : pend[f];
+        (void)pf_mask::index_fastq(t.data(), t.size(), eof[f], used, recs, bad);
         return recs;
     };
     while (err.empty()) {
         // ---- each file grows by a block while it holds less than a chunk, or held no whole record the last time ----
         for (int f = 0; f < 2 && err.empty(); ++f)
-            while (!eof[f] && (pend[f].size() < chunk || more[f])) {
+            while (!eof[f] && (size_of(f) < chunk || more[f])) {
                 ReadBlock b;
                 if (!rd[f].blocks.pop(b)) { err = !rd[f].err.empty() ? rd[f].err : who + ": reading " + inputs[f] + " ended early"; break; }
-                pend[f].insert(pend[f].end(), b.p.get(), b.p.get() + b.len);
+                if (is_gz[f]) {
+                    const auto t0 = clk::now();
+                    const bool ok = gzt[f]->append(who, inputs[f], b.p.get(), b.g, err);
+                    tm.device_s += since(t0);
+                    if (!ok) break;
+                } else {
+                    pend[f].insert(pend[f].end(), b.p.get(), b.p.get() + b.len);
+                }
                 eof[f] = b.eof;
                 more[f] = false;
                 b.p.reset();
@@ -285,18 +333,20 @@ int stream_fastq_pair(pf_ctx *ctx, const char *who_c, const std::string &in1, co
             }
         if (!err.empty()) break;
         const bool final = eof[0] && eof[1];
-        if (final && pend[0].empty() && pend[1].empty()) break;
+        if (final && size_of(0) == 0 && size_of(1) == 0) break;
         // ---- one file has ended and is used up while the other still holds a whole record ----
         for (int f = 0; f < 2 && !final; ++f)
-            if (eof[f] && pend[f].empty() && whole_records(1 - f)) {
+            if (eof[f] && size_of(f) == 0 && whole_records(1 - f)) {
                 err = who + ": " + inputs[f] + " ends after " + std::to_string(records_before) + " records while " + inputs[1 - f] + " holds more (at least " +
                       std::to_string(records_before + whole_records(1 - f)) + "): the files of a pair hold the same number of records";
             }
         if (!err.empty()) break;
         // ---- the device stage ----
         uint64_t used[2] = {0, 0}, recs = 0, bad = 0;
+        tm.text_on_device[0] = is_gz[0];
+        tm.text_on_device[1] = is_gz[1];
         const auto t0 = clk::now();
-        const int rc = step(pend[0].data(), pend[0].size(), pend[1].data(), pend[1].size(), final, used, recs, bad);
+        const int rc = step(text_of(0), size_of(0), text_of(1), size_of(1), final, used, recs, bad);
         tm.device_s += since(t0);
         if (rc != PF_OK) {
             if (!err.empty()) break;   // (the step has worded it)
@@ -308,7 +358,10 @@ int stream_fastq_pair(pf_ctx *ctx, const char *who_c, const std::string &in1, co
                 err = reword(ctx, who, inputs[bad & 1], records_before + (bad >> 1) + 1);
             break;
         }
-        for (int f = 0; f < 2; ++f) pend[f].erase(pend[f].begin(), pend[f].begin() + (ptrdiff_t)used[f]);
+        for (int f = 0; f < 2; ++f) {
+            if (is_gz[f]) gzt[f]->use(used[f]);
+            else pend[f].erase(pend[f].begin(), pend[f].begin() + (ptrdiff_t)used[f]);
+        }
         records_before += recs;
         if (final) break;
         if (recs == 0) more[0] = more[1] = true;   // no whole pair: a file that can grows by the next block
@@ -343,6 +396,7 @@ int trim_fastq_pair(const std::string &in1, const std::string &in2, const std::s
     std::vector<uint32_t> rb[2], rl[2];
     std::vector<uint64_t> lb[2], le[2];
     std::string log;
+    std::vector<char> fetched[2];
     PairStreamTimes ptm;
     stream_fastq_pair(ctx, "trim", in1, in2, opt.chunk_bytes, largest,
                       [&](const char *t1, uint64_t n1, const char *t2, uint64_t n2, bool final, uint64_t used[2], uint64_t &recs, uint64_t &bad) {
@@ -371,6 +425,12 @@ int trim_fastq_pair(const std::string &in1, const std::string &in2, const std::s
                           add_stats(stats[1], st[1]);
                           if (logs) {
                               log.clear();
+                              for (int f = 0; f < 2; ++f)
+                                  if (ptm.text_on_device[f]) {   // (inflated on the device: the log alone takes the text across)
+                                      fetched[f].resize(used[f]);
+                                      if (used[f] && pf_copy(ctx, fetched[f].data(), text[f], (size_t)used[f]) != PF_OK) return (int)PF_ERR_HIP;
+                                      text[f] = fetched[f].data();
+                                  }
                               for (int f = 0; f < 2; ++f) pf_trim::record_lines(text[f], used[f], recs, lb[f], le[f]);
                               for (uint64_t r = 0; r < recs; ++r)
                                   for (int f = 0; f < 2; ++f) trimlog_line(log, text[f], &lb[f][4 * r], &le[f][4 * r], rb[f][r], rl[f][r]);
@@ -380,7 +440,7 @@ int trim_fastq_pair(const std::string &in1, const std::string &in2, const std::s
                               if (out_bytes[d]) wr[d].put(WritePiece{out[d], out_bytes[d]});
                           return (int)PF_OK;
                       },
-                      ptm, err);
+                      ptm, err, opt.gz);
     for (int d = 0; d < 4; ++d) wr[d].stop();
     for (int d = 0; d < 4 && err.empty(); ++d) err = wr[d].err;
     if (!err.empty() || outs.commit(err)) return 1;

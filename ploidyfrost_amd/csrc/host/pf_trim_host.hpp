@@ -18,6 +18,7 @@ struct TrimOptions {
     uint32_t phred = 33;
     std::string trimlog;        // "" = none
     uint64_t chunk_bytes = 0;   // 0 = MASK_DEFAULT_CHUNK
+    bool gz = false;            // --gz: inputs with the gzip magic are blocked gzip, inflated on the device (pf_gz_host.hpp)
 };
 struct TrimTimes {
     double stream_s = 0;   // first byte read to last byte written (wall)
@@ -51,8 +52,9 @@ using PairChunkStep = std::function<int(const char *text1, uint64_t n1, const ch
 struct PairStreamTimes {
     double device_s = 0;   // inside the step
     double read_s = 0;     // read() of the inputs, the slower of the two
+    bool text_on_device[2] = {false, false};   // set before every step: that file's text is device memory (blocked gzip, inflated there)
 };
 int stream_fastq_pair(pf_ctx *ctx, const char *who, const std::string &in1, const std::string &in2, uint64_t chunk_bytes, uint64_t largest,
-                      const PairChunkStep &step, PairStreamTimes &tm, std::string &err);
+                      const PairChunkStep &step, PairStreamTimes &tm, std::string &err, bool gz = false);
 
 }  // namespace pfh

@@ -530,7 +530,7 @@ namespace pf {
 static const char *kKernelNames[PF_K_COUNT_] = {"k_table_build", "k_adj_insert", "k_adj_probe", "k_cov", "k_bfs",
                                                 "k_bfs_big",     "k_align",      "k_align_big", "k_strcov",    "k_bubble",
                                                 "k_bubble_big",  "k_cov_colored", "k_strcov_colored", "k_gmm", "k_kmc_decode", "k_minz_count", "k_cov_join",
-                                                "k_call_sides", "k_call_prep", "k_call_paths", "k_call_sites", "k_call_format", "k_call_snp", "k_bfs_thread", "k_call_pair", "k_call_stack", "k_cov_join_rest", "copy_text_to_host", "k_call_model", "k_density", "k_hist", "k_mask", "k_count", "k_trim", "k_unitig", "k_maskcount", "k_union", "k_colorset", "k_trimcount"};
+                                                "k_call_sides", "k_call_prep", "k_call_paths", "k_call_sites", "k_call_format", "k_call_snp", "k_bfs_thread", "k_call_pair", "k_call_stack", "k_cov_join_rest", "copy_text_to_host", "k_call_model", "k_density", "k_hist", "k_mask", "k_count", "k_trim", "k_unitig", "k_maskcount", "k_union", "k_colorset", "k_trimcount", "k_inflate"};
 
 // (events come from a pool that pf_reset_timing refills: creating two per launch cost more than the launch)
 static size_t launch_push(pf_ctx *ctx, int kernel, hipStream_t stream) {
@@ -1205,6 +1205,23 @@ void pf_device_free(pf_ctx *ctx, void *p) {
     if (!p) return;
     if (ctx) (void)hipSetDevice(ctx->device);
     (void)hipFree(p);
+}
+
+int pf_device_alloc(pf_ctx *ctx, size_t bytes, void **out) {
+    if (!ctx || !out) return PF_ERR_ARG;
+    *out = nullptr;
+    PF_HIP(hipSetDevice(ctx->device));
+    PF_HIP(hipMalloc(out, bytes ? bytes : 1));
+    return PF_OK;
+}
+
+int pf_copy(pf_ctx *ctx, void *dst, const void *src, size_t bytes) {
+    if (!ctx || (bytes && (!dst || !src))) return PF_ERR_ARG;
+    if (!bytes) return PF_OK;
+    PF_HIP(hipSetDevice(ctx->device));
+    PF_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, ctx->stream));
+    PF_HIP(hipStreamSynchronize(ctx->stream));
+    return PF_OK;
 }
 
 int pf_copy_to_host(pf_ctx *ctx, void *dst, const void *src_dev, size_t bytes) {

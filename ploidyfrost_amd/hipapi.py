@@ -40,6 +40,8 @@ MASKCOUNT_STATS = np.dtype([(f, "<u8") for f in ("reads", "bases", "kmers", "kme
 K_UNION = K_MASKCOUNT + 1    # PF_K_UNION ("k_union"): everything one pf_kmer_union launches; unit: keys given
 K_COLORSET = K_UNION + 1     # PF_K_COLORSET ("k_colorset"): the kernel of one pf_color_kmers; unit: keys
 K_TRIMCOUNT = K_COLORSET + 1   # PF_K_TRIMCOUNT ("k_trimcount"): everything one pf_*_trimmed / pf_trim_table_* call launches; unit: records
+K_INFLATE = K_TRIMCOUNT + 1    # PF_K_INFLATE ("k_inflate"): everything one pf_inflate_bgzf launches; unit: inflated bytes
+INFLATE_STATS = np.dtype([(f, "<u8") for f in ("members", "bytes_in", "bytes_out", "blocks_stored", "blocks_fixed", "blocks_dynamic")])   # pf_inflate_stats
 UNION_TILE = 1024            # pf_runmulti::UNION_TILE: merged positions a block of K-UNION takes
 UNION_ITEMS = 4              # pf_runmulti::UNION_ITEMS: ... and a lane
 COLOR_KMERS_STATS = np.dtype([(f, "<u8") for f in ("kmers", "kmers_colored", "kmers_unplaced")])   # pf_color_kmers_stats
@@ -247,6 +249,9 @@ def load_library() -> C.CDLL:
         "pf_trim_fastq": (i, [vp, vp, u64, i, vp, u32, u32, vp, C.POINTER(u64), C.POINTER(u64), vp, vp, C.POINTER(u64), vp, C.POINTER(u64)]),
         "pf_trim_fastq_pair": (i, [vp, vp, u64, vp, u64, i, vp, u32, u32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(vp), C.POINTER(vp),
                                    C.POINTER(u64), vp, C.POINTER(u64)]),
+        "pf_device_alloc": (i, [vp, C.c_size_t, C.POINTER(vp)]),
+        "pf_copy": (i, [vp, vp, vp, C.c_size_t]),
+        "pf_inflate_bgzf": (i, [vp, vp, u64, vp, u64, vp, u64, C.POINTER(u64), vp, C.POINTER(u64)]),
         "pf_trim_table_fastq": (i, [vp, vp, u64, i, vp, vp, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp, C.POINTER(u64)]),
         "pf_trim_table_fastq_pair": (i, [vp, vp, u64, vp, u64, i, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp,
                                          C.POINTER(u64)]),
@@ -282,7 +287,7 @@ DECLARED_SYMBOLS = ["pf_create", "pf_warmup", "pf_destroy", "pf_last_error", "pf
                     "pf_maskcount_reads", "pf_maskcount_fastq", "pf_unitig_text",
                     "pf_kmer_union", "pf_color_kmers", "pf_release_counts",
                     "pf_trim_table_fastq", "pf_trim_table_fastq_pair", "pf_count_fastq_trimmed", "pf_count_fastq_pair_trimmed",
-                    "pf_maskcount_fastq_trimmed", "pf_maskcount_fastq_pair_trimmed"]
+                    "pf_maskcount_fastq_trimmed", "pf_maskcount_fastq_pair_trimmed", "pf_inflate_bgzf", "pf_device_alloc", "pf_copy"]
 
 
 class TrimPlan(C.Structure):   # pf_trim_plan
@@ -609,6 +614,37 @@ class Device:
             raise e
         return dict(out=out[: out_n.value], bytes_used=used.value, n_records=recs.value, begin=begin[: recs.value], len=ln[: recs.value],
                     stats={f: int(stats[0][f]) for f in TRIM_STATS.names})
+
+    def inflate_bgzf(self, comp, member_off, out=None, out_cap=None):
+        """K-INFLATE (pf_inflate_bgzf): the BGZF members comp[member_off[m] : member_off[m + 1]] inflated one behind the other; returns
+        (text, stats).  comp: bytes, a uint8 numpy array or a device tensor; member_off: n_members + 1 offsets (list, u64 array or device
+        tensor); out: an array or device tensor to fill (out_cap bytes of it, default all) instead of a new numpy array of the size
+        needed.  A refused member raises DeviceError with .bad_member = the smallest offender; a buffer too small raises it with
+        status PF_ERR_OVERFLOW and .needed."""
+        if isinstance(comp, (bytes, bytearray)):
+            comp = np.frombuffer(bytes(comp), dtype=np.uint8)
+        if isinstance(member_off, (list, tuple, np.ndarray)):
+            member_off = np.ascontiguousarray(member_off, dtype=np.uint64)
+        n, n_members = int(comp.shape[0]), max(int(member_off.shape[0]) - 1, 0)
+        stats = np.zeros(1, dtype=INFLATE_STATS)
+        out_n, bad = C.c_uint64(), C.c_uint64()
+        call = lambda o, cap: self.L.pf_inflate_bgzf(self.h, _ptr(comp) if n else None, n, _ptr(member_off) if n_members else None, n_members,   # noqa: E731
+                                                     _ptr(o) if o is not None and cap else None, cap, C.byref(out_n), stats.ctypes.data, C.byref(bad))
+        if out is None:   # sized by a first call that writes nothing
+            st = call(None, 0)
+            if st == PF_ERR_OVERFLOW:
+                out = np.zeros(out_n.value, dtype=np.uint8)
+                st = call(out, out_n.value)
+            else:
+                out = np.zeros(0, dtype=np.uint8)
+        else:
+            st = call(out, int(out.shape[0]) if out_cap is None else out_cap)
+        if st != PF_OK:
+            e = DeviceError(st, self.L.pf_last_error(self.h).decode())
+            e.bad_member = bad.value
+            e.needed = out_n.value
+            raise e
+        return out[: out_n.value], {f: int(stats[0][f]) for f in INFLATE_STATS.names}
 
     def trim_fastq_pair(self, text1, text2, steps, phred: int = 33, final: bool = True, outs=None):
         """K-TRIM on one chunk of each file of a pair (pf_trim_fastq_pair): dict with out = [o1, u1, o2, u2], bytes_used = [file 1,

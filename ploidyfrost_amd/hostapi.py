@@ -46,7 +46,9 @@ DECLARED_SYMBOLS = ["pfh_open", "pfh_close", "pfh_last_error", "pfh_set_output_d
                     "pfh_build_colored_fastq", "pfh_build_colored_host", "pfh_bfg_colors_bytes", "pfh_color_no_room_text",
                     "pfh_run_defaults", "pfh_run_fastq", "pfh_count_masked_host", "pfh_run_multi_fastq", "pfh_union_host",
                     "pfh_trim_fastq", "pfh_trim_fastq_pair", "pfh_trim_parse_step", "pfh_trim_refusal_text", "pfh_trim_read", "pfh_trim_fastq_chunk",
-                    "pfh_run_fastq_trimmed", "pfh_run_multi_fastq_trimmed", "pfh_trim_table_chunk", "pfh_trim_table_chunk_pair", "pfh_trim_table_clause_text"]
+                    "pfh_run_fastq_trimmed", "pfh_run_multi_fastq_trimmed", "pfh_trim_table_chunk", "pfh_trim_table_chunk_pair", "pfh_trim_table_clause_text",
+                    "pfh_inflate_parse_member", "pfh_inflate_member", "pfh_inflate_bgzf_member", "pfh_inflate_crc32", "pfh_inflate_crc32_sliced",
+                    "pfh_inflate_file_clause", "pfh_inflate_clause_text", "pfh_reads_gz"]
 
 
 class RunOptions(C.Structure):   # pfh_run_options (include/ploidyfrost_host.h)
@@ -62,6 +64,11 @@ RUN_MULTI_STATS_FIELDS = ("colors", "reads", "bases", "kmers", "bad", "distinct"
                           "unitigs_out", "longest", "kmers_colored", "kmers_unplaced", "runs", "overflow", "color_bytes")   # pfh_run_multi_stats: `run-multi`'s stderr line
 RUN_MULTI_COLOR_FIELDS = ("lower", "upper", "distinct", "kept")   # of its `run-multi: color c ...` lines
 MASKCOUNT_STATS_FIELDS = ("reads", "bases", "kmers", "kmers_invalid", "kmers_bad", "kmers_kept")   # pf_maskcount_stats
+
+
+class ReadsRefused(RuntimeError, ValueError):
+    """what count_fastq, trim_fastq, trim_fastq_pair, run_reads and run_multi_reads raise for a refusal of a call with gz=True, worded as the
+    command words it (without gz= they raise RuntimeError, as before)"""
 
 
 class FilterOpts(C.Structure):   # pf_filter_opts (include/ploidyfrost_hip.h)
@@ -256,6 +263,18 @@ def load_library() -> C.CDLL:
                                             C.POINTER(u64), vp, C.POINTER(u64)]
     L.pfh_trim_table_clause_text.restype = C.c_char_p
     L.pfh_trim_table_clause_text.argtypes = [C.c_int]
+    L.pfh_reads_gz.restype = None
+    L.pfh_reads_gz.argtypes = [C.c_int]
+    L.pfh_inflate_parse_member.argtypes = [vp, u64, vp]
+    L.pfh_inflate_member.argtypes = [vp, u32, vp, u32, C.POINTER(u32), vp]
+    L.pfh_inflate_bgzf_member.argtypes = [vp, u64, vp, C.POINTER(u32), vp]
+    L.pfh_inflate_crc32.restype = u32
+    L.pfh_inflate_crc32.argtypes = [vp, u64]
+    L.pfh_inflate_crc32_sliced.restype = u32
+    L.pfh_inflate_crc32_sliced.argtypes = [vp, u32, u32]
+    L.pfh_inflate_file_clause.argtypes = [vp, u64, u64, C.POINTER(C.c_int)]
+    L.pfh_inflate_clause_text.restype = C.c_char_p
+    L.pfh_inflate_clause_text.argtypes = [C.c_int]
     _lib = L
     return L
 
@@ -605,7 +624,7 @@ def trim_table_chunk(text, steps, phred: int = 33, final: bool = True, text2=Non
     return out
 
 
-def trim_fastq(inputs, out: str, steps, phred: int = 33, trimlog=None, chunk_bytes: int = 0) -> dict:
+def trim_fastq(inputs, out: str, steps, phred: int = 33, trimlog=None, chunk_bytes: int = 0, gz: bool = False) -> dict:
     """`ploidyfrost trim -i ... -o out STEP...` (pfh_trim_fastq): the reads of the FASTQ file(s) `inputs`, one after the other,
     quality-trimmed by `steps` (Trimmomatic's words) into `out`; trimlog: a file with one line per record.  Returns the statistics.  A
     refusal raises RuntimeError (format refusals with the input's path and the 1-based record number); nothing is left under any
@@ -616,14 +635,15 @@ def trim_fastq(inputs, out: str, steps, phred: int = 33, trimlog=None, chunk_byt
     st = trim_parse_steps(steps)
     paths = (C.c_char_p * max(len(inputs), 1))(*[os.fsencode(p) for p in inputs])
     stats = np.zeros(len(TRIM_STATS_FIELDS), dtype=np.uint64)
+    L.pfh_reads_gz(int(gz))
     rc = L.pfh_trim_fastq(paths, len(inputs), os.fsencode(out), st.ctypes.data if len(st) else None, len(st), phred,
                           os.fsencode(trimlog) if trimlog else None, int(chunk_bytes), 0, stats.ctypes.data)
     if rc:
-        raise RuntimeError(L.pfh_last_error(None).decode())
+        raise (ReadsRefused if gz else RuntimeError)(L.pfh_last_error(None).decode())
     return {f: int(v) for f, v in zip(TRIM_STATS_FIELDS, stats)}
 
 
-def trim_fastq_pair(in1: str, in2: str, outs, steps, phred: int = 33, trimlog=None, chunk_bytes: int = 0):
+def trim_fastq_pair(in1: str, in2: str, outs, steps, phred: int = 33, trimlog=None, chunk_bytes: int = 0, gz: bool = False):
     """`ploidyfrost trim -1 in1 -2 in2 -o1 .. -u1 .. -o2 .. -u2 .. STEP...` (pfh_trim_fastq_pair): outs = (o1, u1, o2, u2).  Returns the
     statistics of file 1 and of file 2 (the pair fields are the same in both)."""
     L = load_library()
@@ -631,10 +651,11 @@ def trim_fastq_pair(in1: str, in2: str, outs, steps, phred: int = 33, trimlog=No
     assert len(outs) == 4
     paths = (C.c_char_p * 4)(*[os.fsencode(p) for p in outs])
     stats = np.zeros((2, len(TRIM_STATS_FIELDS)), dtype=np.uint64)
+    L.pfh_reads_gz(int(gz))
     rc = L.pfh_trim_fastq_pair(os.fsencode(in1), os.fsencode(in2), paths, st.ctypes.data if len(st) else None, len(st), phred,
                                os.fsencode(trimlog) if trimlog else None, int(chunk_bytes), 0, stats.ctypes.data)
     if rc:
-        raise RuntimeError(L.pfh_last_error(None).decode())
+        raise (ReadsRefused if gz else RuntimeError)(L.pfh_last_error(None).decode())
     return [{f: int(v) for f, v in zip(TRIM_STATS_FIELDS, row)} for row in stats]
 
 
@@ -649,7 +670,7 @@ def _paths(inputs):
 
 
 def count_fastq(inputs, out_prefix: str, k: int = 25, ci: int = 2, cx: int = 10 ** 9, cs: int = 255, both_strands: bool = True, hist=None,
-                chunk_bytes: int = 0, initial_slots: int = 0) -> dict:
+                chunk_bytes: int = 0, initial_slots: int = 0, gz: bool = False) -> dict:
     """`ploidyfrost count` (pfh_count_fastq): the k-mers of the FASTQ file(s) `inputs` counted on the device (K-COUNT), those with
     ci <= c <= cx written as min(c, cs) to <out_prefix>.kmc_pre / .kmc_suf in the KMC1 layout; hist: the histogram file of the finished
     counters.  Returns the statistics.  A refusal raises RuntimeError by name (format refusals with the input's path and the 1-based
@@ -657,10 +678,11 @@ def count_fastq(inputs, out_prefix: str, k: int = 25, ci: int = 2, cx: int = 10 
     L = load_library()
     paths, n = _paths(inputs)
     stats = np.zeros(len(COUNT_STATS_FIELDS), dtype=np.uint64)
+    L.pfh_reads_gz(int(gz))
     rc = L.pfh_count_fastq(paths, n, os.fsencode(out_prefix), int(k), int(ci), int(cx), int(cs), int(both_strands),
                            None if hist is None else os.fsencode(hist), int(chunk_bytes), int(initial_slots), 0, stats.ctypes.data)
     if rc:
-        raise RuntimeError(L.pfh_last_error(None).decode())
+        raise (ReadsRefused if gz else RuntimeError)(L.pfh_last_error(None).decode())
     return {f: int(v) for f, v in zip(COUNT_STATS_FIELDS, stats)}
 
 
@@ -753,7 +775,7 @@ def build_graph(inputs, out_prefix: str, k: int = 25, clip_tips: bool = False, d
 def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 ** 9, cs: int = 10000, q: float = 0.998, mask_upper=None,
               keep_tips: bool = False, keep_isolated: bool = False, g=None, z: int = 8, M: float = 2.0, D: float = -1.0, G: float = -3.0,
               threads: int = 1, model=None, model_only: bool = False, db_out=None, gfa_out=None, chunk_bytes: int = 0,
-              initial_slots: int = 0, steps=None, phred: int = 33, pairs=None) -> dict:
+              initial_slots: int = 0, steps=None, phred: int = 33, pairs=None, gz: bool = False) -> dict:
     """`ploidyfrost run` (pfh_run_fastq): reads to ploidy estimate in one process -- the FASTQ file(s) `inputs` counted, the thresholds
     derived, the k-mers of the masked reads counted (K-MASKCOUNT), the graph built and the single-sample calling run made on one device
     context; PloidyFrost_output/<out_prefix>_*.txt in the working directory.  model: None, "cov" or "fre".  Returns the fields of the
@@ -787,15 +809,17 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
     o.gfa_out = None if gfa_out is None else os.fsencode(gfa_out)
     stats = np.zeros(len(RUN_STATS_FIELDS), dtype=np.uint64)
     if steps is None and pairs is None:
+        L.pfh_reads_gz(int(gz))
         rc = L.pfh_run_fastq(paths, n, os.fsencode(out_prefix), C.byref(o), 0, stats.ctypes.data)
         if rc:
-            raise RuntimeError(L.pfh_last_error(None).decode())
+            raise (ReadsRefused if gz else RuntimeError)(L.pfh_last_error(None).decode())
         return {f: int(v) for f, v in zip(RUN_STATS_FIELDS, stats)}
     per = np.zeros((max(n, 1), len(TRIM_STATS_FIELDS)), dtype=np.uint64)
+    L.pfh_reads_gz(int(gz))
     rc = L.pfh_run_fastq_trimmed(paths, n, int(pairs is not None), st.ctypes.data if len(st) else None, len(st), int(phred), os.fsencode(out_prefix),
                                  C.byref(o), 0, stats.ctypes.data, per.ctypes.data)
     if rc:
-        raise RuntimeError(L.pfh_last_error(None).decode())
+        raise (ReadsRefused if gz else RuntimeError)(L.pfh_last_error(None).decode())
     out = {f: int(v) for f, v in zip(RUN_STATS_FIELDS, stats)}
     rows = [{f: int(v) for f, v in zip(TRIM_STATS_FIELDS, row)} for row in per]
     out["trim"] = [rows[0]] if pairs is None else [[rows[2 * u], rows[2 * u + 1]] for u in range(len(pairs))]
@@ -805,7 +829,7 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
 def run_multi_reads(samples, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 ** 9, cs: int = 10000, q: float = 0.998, mask_upper=None,
                     keep_tips: bool = False, keep_isolated: bool = False, g=None, z: int = 8, M: float = 2.0, D: float = -1.0, G: float = -3.0,
                     threads: int = 1, model=None, model_only: bool = False, filter_multi=None, each_color: bool = False, db_out=None, gfa_out=None,
-                    chunk_bytes: int = 0, initial_slots: int = 0, steps=None, phred: int = 33, pairs=None) -> dict:
+                    chunk_bytes: int = 0, initial_slots: int = 0, steps=None, phred: int = 33, pairs=None, gz: bool = False) -> dict:
     """`ploidyfrost run-multi` (pfh_run_multi_fastq): reads of several samples to one estimate per sample in one process.  samples: a
     list of (name, file or list of files), a sample a colour in the order given.  Every sample is counted and its thresholds derived,
     the k-mers of its masked reads counted (K-MASKCOUNT), their union taken (K-UNION), the coloured graph built and coloured per
@@ -855,15 +879,17 @@ def run_multi_reads(samples, out_prefix: str, k: int = 25, ci: int = 1, cx: int 
     per_in = np.zeros((max(len(flat), 1), len(TRIM_STATS_FIELDS)), dtype=np.uint64)
     if trimmed:
         pair_of = np.ascontiguousarray(paired, dtype=np.int32)
+        L.pfh_reads_gz(int(gz))
         rc = L.pfh_run_multi_fastq_trimmed(c_names, n_of.ctypes.data if len(names) else None, pair_of.ctypes.data if len(names) else None, len(names), paths,
                                            st.ctypes.data if len(st) else None, len(st), int(phred), os.fsencode(out_prefix), C.byref(o),
                                            C.byref(multi) if multi is not None else None, int(each_color), 0, stats.ctypes.data, per.ctypes.data,
                                            per_in.ctypes.data)
     else:
+        L.pfh_reads_gz(int(gz))
         rc = L.pfh_run_multi_fastq(c_names, n_of.ctypes.data if len(names) else None, len(names), paths, os.fsencode(out_prefix), C.byref(o),
                                    C.byref(multi) if multi is not None else None, int(each_color), 0, stats.ctypes.data, per.ctypes.data)
     if rc:
-        raise RuntimeError(L.pfh_last_error(None).decode())
+        raise (ReadsRefused if gz else RuntimeError)(L.pfh_last_error(None).decode())
     out = {f: int(v) for f, v in zip(RUN_MULTI_STATS_FIELDS, stats)}
     out["color"] = [{f: int(v) for f, v in zip(RUN_MULTI_COLOR_FIELDS, per[c])} for c in range(len(names))]
     if trimmed:
@@ -1450,3 +1476,74 @@ class Gmm:
         ms, n = C.c_double(), C.c_uint64()
         self._check(self.L.pfh_gmm_kernel_time(self.h, -1, C.byref(ms), C.byref(n)))
         return ms.value, n.value
+
+
+# ---- blocked gzip: the rule of K-INFLATE without a device (csrc/pf_inflate_rule.hpp) ----
+def _u8(data):
+    a = np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, dtype=np.uint8)
+    return a, (a.ctypes.data if len(a) else None)
+
+
+def inflate_clause_text(clause: int) -> str:
+    return load_library().pfh_inflate_clause_text(clause).decode()
+
+
+def inflate_parse_member(data, n=None):
+    """pfh_inflate_parse_member: (clause, dict(payload_off, member_len, crc, isize)) of the member header at data[0:]; n: the bytes up to
+    the end of the file (default len(data))."""
+    a, p = _u8(data)
+    f = (C.c_uint32 * 4)()
+    clause = load_library().pfh_inflate_parse_member(p, len(a) if n is None else n, f)
+    return clause, dict(payload_off=f[0], member_len=f[1], crc=f[2], isize=f[3])
+
+
+def inflate_member(payload, isize: int, guard: int = 64):
+    """pfh_inflate_member: one member's deflate stream -> (clause, the bytes produced, [stored, fixed, dynamic] blocks).  The stream is
+    copied to the end of a buffer of its own size and the output gets `guard` bytes behind its isize that must come back untouched."""
+    a, _ = _u8(payload)
+    src = np.empty(len(a), dtype=np.uint8)
+    src[:] = a
+    out = np.full(isize + guard, 0xA5, dtype=np.uint8)
+    made, blocks = C.c_uint32(), (C.c_uint32 * 3)()
+    clause = load_library().pfh_inflate_member(src.ctypes.data if len(src) else None, len(src), out.ctypes.data, isize, C.byref(made), blocks)
+    if made.value > isize or not (out[isize:] == 0xA5).all():
+        raise AssertionError("pfh_inflate_member wrote outside out[0, isize)")
+    return clause, out[: made.value].tobytes(), list(blocks)
+
+
+def inflate_bgzf_member(data, n=None):
+    """pfh_inflate_bgzf_member: a whole member, header to CRC -> (clause, text, [stored, fixed, dynamic])"""
+    a, p = _u8(data)
+    out = np.zeros(65536, dtype=np.uint8)
+    n_out, blocks = C.c_uint32(), (C.c_uint32 * 3)()
+    clause = load_library().pfh_inflate_bgzf_member(p, len(a) if n is None else n, out.ctypes.data, C.byref(n_out), blocks)
+    return clause, out[: n_out.value].tobytes(), list(blocks)
+
+
+def inflate_bgzf(data):
+    """every member of a blocked-gzip file by the host rule: the text (what Device.inflate_bgzf is held to); ValueError names a refusal"""
+    a, _ = _u8(data)
+    out, at, m = [], 0, 0
+    while at < len(a):
+        clause, text, _ = inflate_bgzf_member(a[at:])
+        if clause:
+            raise ValueError("member %d, byte %d: %s" % (m + 1, at, inflate_clause_text(clause)))
+        out.append(text)
+        at += inflate_parse_member(a[at:])[1]["member_len"]
+        m += 1
+    return b"".join(out)
+
+
+def inflate_crc32(data, n_lanes: int = 0) -> int:
+    """pfh_inflate_crc32, or with n_lanes pfh_inflate_crc32_sliced (as the kernel's lanes compute it)"""
+    a, p = _u8(data)
+    L = load_library()
+    return L.pfh_inflate_crc32_sliced(p, len(a), n_lanes) if n_lanes else L.pfh_inflate_crc32(p, len(a))
+
+
+def inflate_file_clause(first, file_size=None):
+    """pfh_inflate_file_clause: (kind, clause): kind 0 plain, 1 blocked gzip, 2 refused by `clause`"""
+    a, p = _u8(first)
+    clause = C.c_int()
+    kind = load_library().pfh_inflate_file_clause(p, len(a), len(a) if file_size is None else file_size, C.byref(clause))
+    return kind, clause.value
