@@ -73,6 +73,7 @@ enum pf_kernel {
     PF_K_COLORSET, /* K-COLORSET: the kernel of one pf_color_kmers; unit: keys */
     PF_K_TRIMCOUNT, /* K-TRIMCOUNT: everything one pf_trim_table_fastq* / pf_count_fastq*_trimmed / pf_maskcount_fastq*_trimmed launches (index, intervals, table, then K-COUNT's or K-MASKCOUNT's core), timed as one launch; unit: records */
     PF_K_INFLATE, /* K-INFLATE: everything one pf_inflate_bgzf launches (headers, scan, inflate with the CRC), timed as one launch; unit: inflated bytes */
+    PF_K_GUNZIP, /* K-GUNZIP: everything one pf_inflate_gzip launches (find, count, chain, decode, window, resolve with the CRC), timed as one launch; unit: inflated bytes */
     PF_K_COUNT_
 };
 int pf_enable_timing(pf_ctx *, int on);
@@ -425,6 +426,33 @@ typedef struct pf_inflate_stats {
  * comp, member_off, out: [host|dev] */
 int pf_inflate_bgzf(pf_ctx *, const uint8_t *comp, uint64_t n_bytes, const uint64_t *member_off, uint64_t n_members,
                     char *out, uint64_t out_cap, uint64_t *out_bytes, pf_inflate_stats *stats, uint64_t *bad_member);
+
+/* K-GUNZIP: a plain gzip member's deflate stream (what gzip and pigz write) inflated on the device.  One stream has no table of its
+ * blocks, so it is cut into pieces at block starts that a search finds, every piece is decoded twice (count, then decode into 16-bit
+ * symbols with markers for what lies in front of the piece) and the markers are resolved afterwards.  The rule -- the container, the
+ * refusals by name, the same stages on the host -- is csrc/pf_gunzip_rule.hpp; what one lane runs is csrc/pf_gunzip_core.hpp.  Timed as
+ * one launch of PF_K_GUNZIP per call; unit: inflated bytes. */
+typedef struct pf_gunzip_result {
+    uint64_t out_bytes;   /* bytes of text written (PF_ERR_OVERFLOW: needed) */
+    uint64_t end_bit;     /* the last complete block boundary: where the next call starts */
+    uint32_t final;       /* the call ended behind a final block: the trailer follows at the next byte boundary */
+    uint32_t n_window;    /* bytes of the new window */
+    uint32_t crc_raw;     /* the raw CRC-32 register (from zero, not inverted) of the call's text: the caller combines the calls' */
+    uint32_t clause;      /* a refusal: the clause (pf_inflate::Clause, pf_gunzip::Clause) and the block boundary in front of it */
+    uint64_t clause_bit;
+} pf_gunzip_result;
+typedef struct pf_gunzip_stats {
+    uint64_t pieces_found, pieces_live, pieces_dead, markers, blocks_stored, blocks_fixed, blocks_dynamic, bytes_in, bytes_out;
+    double stage_ms[5];   /* find, count, decode, window, resolve: filled when timing is on */
+} pf_gunzip_stats;
+/* comp[0, n_bytes) from start_bit on, a block start.  window[0, n_window): the last n_window <= 32768 bytes of the member's text so
+ * far (0 at a member's start); new_window (32768 bytes, may be window) receives the last bytes of the text including this call's.
+ * piece_bytes: the nominal piece stride in compressed bytes (0: 16384; at least 64).  The call stops at a final block or, when the
+ * bytes end inside a block, at the last complete block boundary.  out_cap too small: PF_ERR_OVERFLOW, res->out_bytes = needed,
+ * nothing written.  A refused stream: PF_ERR_ARG with res->clause and res->clause_bit, pf_last_error names the clause.
+ * comp, window, out, new_window: [host|dev] */
+int pf_inflate_gzip(pf_ctx *, const uint8_t *comp, uint64_t n_bytes, uint64_t start_bit, const uint8_t *window, uint32_t n_window,
+                    uint32_t piece_bytes, char *out, uint64_t out_cap, uint8_t *new_window, pf_gunzip_result *res, pf_gunzip_stats *stats);
 
 int pf_copy_to_host(pf_ctx *, void *dst, const void *src_dev, size_t bytes);
 /* Device memory of the caller's own (freed with pf_device_free), and a copy between any two places (host or device) on the launch

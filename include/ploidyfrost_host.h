@@ -543,6 +543,25 @@ uint32_t pfh_inflate_crc32_sliced(const uint8_t *bytes, uint32_t n, uint32_t n_l
 int pfh_inflate_file_clause(const uint8_t *first, uint64_t n_first, uint64_t file_size, int *clause);
 const char *pfh_inflate_clause_text(int clause);
 
+/* ---- plain gzip (K-GUNZIP, `--gz-plain`): the rule without a device (csrc/pf_gunzip_rule.hpp) ----
+ * pfh_reads_gz(2) selects `--gz-plain` for the next reads call: an input with the gzip magic is blocked gzip (K-INFLATE, as with 1) or
+ * any other gzip, inflated by K-GUNZIP.
+ * pfh_gunzip_header: one member header at bytes[0, n): the clause, *len = its bytes.
+ * pfh_gunzip_file_kind: what the first bytes of a file say with `--gz-plain`: 0 plain, 1 blocked gzip, 2 refused with *clause, 3 gzip.
+ * pfh_gunzip_candidate: does a non-final dynamic block header start at `bit` of bytes[0, n)?  (the search of the find stage)
+ * pfh_gunzip_call: one call of pf_inflate_gzip's algorithm on the host, lane 0 of 1: same arguments, same result; out_cap too small
+ *   returns -1 with res->out_bytes = needed.  stats = the nine counters of pf_gunzip_stats.
+ * pfh_gunzip_file: a whole file in memory through the loop the stream seams run (carry, trailer, next header), fed in blocks of
+ *   block_bytes (0: at once): the clause (0: out[0, *out_len) holds the members' texts); *member (0-based) and *byte say where. */
+int pfh_gunzip_header(const uint8_t *bytes, uint64_t n, uint64_t *len);
+int pfh_gunzip_file_kind(const uint8_t *first, uint64_t n_first, uint64_t file_size, int *clause);
+int pfh_gunzip_candidate(const uint8_t *bytes, uint64_t n, uint64_t bit);
+int pfh_gunzip_call(const uint8_t *comp, uint64_t n_bytes, uint64_t start_bit, const uint8_t *window, uint32_t n_window, uint32_t piece_bytes,
+                    uint8_t *out, uint64_t out_cap, uint8_t *new_window, pf_gunzip_result *res, uint64_t stats[9]);
+int pfh_gunzip_file(const uint8_t *bytes, uint64_t n, uint32_t piece_bytes, uint64_t block_bytes, uint64_t carry_max, uint8_t *out, uint64_t out_cap,
+                    uint64_t *out_len, uint64_t *member, uint64_t *byte, uint64_t stats[9]);
+const char *pfh_gunzip_clause_text(int clause);
+
 /* Kmer::hash(seed) of the reference's Bifrost build (wyhash over the 8-byte left-aligned k-mer) */
 uint64_t pfh_bifrost_kmer_hash(uint64_t left_aligned_kmer, uint64_t seed);
 

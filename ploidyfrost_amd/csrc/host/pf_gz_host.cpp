@@ -7,6 +7,7 @@
 #include <cerrno>
 #include <cstring>
 
+#include "../pf_gunzip_rule.hpp"
 #include "../pf_inflate_rule.hpp"
 
 namespace pfh {
@@ -25,6 +26,24 @@ bool gz_magic(const std::string &path) {
     const ssize_t got = read(fd, m, 2);
     close(fd);
     return got == 2 && m[0] == 0x1f && m[1] == 0x8b;
+}
+
+int gz_kind(const std::string &path, int gz) {
+    if (!gz) return GZ_KIND_TEXT;
+    if (gz == 1) return gz_magic(path) ? GZ_KIND_BGZF : GZ_KIND_TEXT;
+    const int fd = open(path.c_str(), O_RDONLY);
+    if (fd < 0) return GZ_KIND_TEXT;
+    std::vector<unsigned char> head(65536);
+    size_t got = 0;
+    while (got < head.size()) {
+        const ssize_t more = read(fd, head.data() + got, head.size() - got);
+        if (more < 0 && errno == EINTR) continue;
+        if (more <= 0) break;
+        got += (size_t)more;
+    }
+    close(fd);
+    const int kind = pf_gunzip::file_kind(head.data(), got, got < head.size() ? got : ~0ull, nullptr);
+    return kind == pf_gunzip::FILE_PLAIN ? GZ_KIND_TEXT : kind == pf_gunzip::FILE_GZIP ? GZ_KIND_GZIP : GZ_KIND_BGZF;
 }
 
 bool GzReader::open_file(const std::string &who_, const std::string &path_, std::string &err) {
@@ -80,7 +99,30 @@ bool GzReader::next(char *buf, uint64_t cap, uint64_t chunk, GzBlock &b, std::st
     return true;
 }
 
+bool GzReader::next_raw(char *buf, uint64_t want, GzBlock &b, std::string &err) {
+    b = GzBlock{};
+    b.plain = true;
+    b.file_off = pos;
+    while (b.len < want) {
+        const ssize_t got = pread(fd, buf + b.len, (size_t)std::min<uint64_t>(want - b.len, GZ_READ_STEP), (off_t)(pos + b.len));
+        if (got < 0 && errno == EINTR) continue;
+        if (got < 0) { err = who + ": reading " + path + " (" + strerror(errno) + ")"; return false; }
+        if (got == 0) { b.eof = true; break; }
+        b.len += (uint64_t)got;
+    }
+    pos += b.len;
+    return true;
+}
+
+struct GzText::Plain {
+    pf_gunzip::Stream stream;
+    char *d_win = nullptr;     // the member's last 32 KiB of text
+    uint32_t n_window = 0;
+};
+
+GzText::GzText(pf_ctx *c) : ctx(c) {}
 GzText::~GzText() {
+    if (plain) pf_device_free(ctx, plain->d_win);
     pf_device_free(ctx, d_comp);
     pf_device_free(ctx, d_off);
     pf_device_free(ctx, d_text[0]);
@@ -117,6 +159,70 @@ bool GzText::append(const std::string &who, const std::string &path, const char 
     cur = other;
     begin = 0;
     end = left + out_bytes;
+    return true;
+}
+
+bool GzText::append_plain(const std::string &who, const std::string &path, const char *raw, uint64_t len, uint64_t file_off, bool eof, std::string &err) {
+    auto dev_err = [&](const char *what) { err = who + ": " + path + ": " + what + ": " + pf_last_error(ctx); return false; };
+    if (!plain || file_off == 0) {
+        if (plain) pf_device_free(ctx, plain->d_win);
+        plain.reset(new Plain);
+    }
+    Plain &pl = *plain;
+    if (!pl.d_win && pf_device_alloc(ctx, pf_gunzip::RING, reinterpret_cast<void **>(&pl.d_win)) != PF_OK) return dev_err("device memory for the window");
+    // what is left moves to the front of the other buffer; every call of this turn writes behind it
+    const uint64_t left = end - begin;
+    const int other = cur ^ 1;
+    auto text_room = [&](int t, uint64_t need, uint64_t keep) {   // d_text[t] holds `need` bytes, its first `keep` kept
+        if (need <= text_cap[t] && d_text[t]) return true;
+        char *grown = nullptr;
+        const uint64_t cap = need + need / 4 + 256;
+        if (pf_device_alloc(ctx, (size_t)cap, reinterpret_cast<void **>(&grown)) != PF_OK) return false;
+        if (keep && pf_copy(ctx, grown, d_text[t], (size_t)keep) != PF_OK) { pf_device_free(ctx, grown); return false; }
+        pf_device_free(ctx, d_text[t]);
+        d_text[t] = grown;
+        text_cap[t] = cap;
+        return true;
+    };
+    if (!text_room(other, left + 5 * (pl.stream.carry.size() + len) + 65536, 0)) return dev_err("device memory for the chunk");
+    if (left && pf_copy(ctx, d_text[other], d_text[cur] + begin, (size_t)left) != PF_OK) return dev_err("carrying the cut record");
+    cur = other;
+    begin = 0;
+    end = left;
+    auto call = [&](const uint8_t *bytes, uint64_t n, uint64_t start_bit, bool fresh, pf_gunzip::Call &r, std::string &e) {
+        if (fresh) pl.n_window = 0;
+        if (n > comp_cap || !d_comp) {
+            pf_device_free(ctx, d_comp);
+            d_comp = nullptr;
+            comp_cap = n + n / 8 + 256;
+            if (pf_device_alloc(ctx, (size_t)comp_cap, reinterpret_cast<void **>(&d_comp)) != PF_OK) { dev_err("device memory for the chunk"); e = err; return false; }
+        }
+        if (n && pf_copy(ctx, d_comp, bytes, (size_t)n) != PF_OK) { dev_err("uploading the compressed chunk"); e = err; return false; }
+        pf_gunzip_result res = {};
+        int rc = PF_OK;
+        for (int turn = 0; turn < 3; ++turn) {   // (a text buffer too small is said before anything is written)
+            rc = pf_inflate_gzip(ctx, reinterpret_cast<const uint8_t *>(d_comp), n, start_bit, reinterpret_cast<const uint8_t *>(pl.d_win), pl.n_window, 0,
+                                 d_text[cur] + end, text_cap[cur] - end, reinterpret_cast<uint8_t *>(pl.d_win), &res, nullptr);
+            if (rc != PF_ERR_OVERFLOW) break;
+            if (!text_room(cur, end + res.out_bytes + 16, end)) { dev_err("device memory for the chunk"); e = err; return false; }
+        }
+        if (rc == PF_ERR_ARG && res.clause) { r.clause = res.clause; r.clause_bit = res.clause_bit; return true; }
+        if (rc != PF_OK) { dev_err("inflating"); e = err; return false; }
+        r.out_bytes = res.out_bytes;
+        r.end_bit = res.end_bit;
+        r.final = res.final;
+        r.n_window = res.n_window;
+        r.crc_raw = res.crc_raw;
+        pl.n_window = res.n_window;
+        end += res.out_bytes;
+        return true;
+    };
+    std::string e;
+    if (!pl.stream.feed(reinterpret_cast<const uint8_t *>(raw), len, eof, call, e)) {
+        if (pl.stream.clause) err = member_refusal(who, path, pl.stream.member, pl.stream.clause_byte, pf_gunzip::clause_text(pl.stream.clause));
+        else if (err.empty()) err = who + ": " + path + ": " + e;
+        return false;
+    }
     return true;
 }
 

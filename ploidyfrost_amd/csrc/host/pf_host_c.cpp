@@ -20,6 +20,7 @@
 #include "../pf_trim_rule.hpp"
 #include "../pf_trimrun_rule.hpp"
 #include "../pf_inflate_rule.hpp"
+#include "../pf_gunzip_rule.hpp"
 #include "pf_trim_host.hpp"
 #include "pf_trace.hpp"
 #include "../pf_model_rows.hpp"
@@ -252,9 +253,9 @@ uint32_t pfh_cutoffs(const pfh_run *r, int *lower, int *upper, uint32_t cap) {
 void *pfh_device_ctx(pfh_run *r) { return r->cdbg->device(); }
 
 // ---- blocked-gzip inputs: the next reads call of this thread takes them (`--gz`) ----
-static thread_local bool g_reads_gz = false;
-void pfh_reads_gz(int on) { g_reads_gz = on != 0; }
-static bool take_reads_gz() { const bool gz = g_reads_gz; g_reads_gz = false; return gz; }
+static thread_local int g_reads_gz = 0;   // 0, 1 `--gz`, 2 `--gz-plain`
+void pfh_reads_gz(int on) { g_reads_gz = on == 2 ? 2 : on != 0; }
+static int take_reads_gz() { const int gz = g_reads_gz; g_reads_gz = 0; return gz; }
 
 // ---- reads masked against the database (K-MASK) ----------------------------------------------------
 int pfh_mask_fastq(const char *db_prefix, const char *const *inputs, uint32_t n_inputs, const char *out_path, uint32_t low, uint32_t up,
@@ -1593,6 +1594,42 @@ int pfh_inflate_file_clause(const uint8_t *first, uint64_t n_first, uint64_t fil
     return pf_inflate::file_clause_gz(first, n_first, file_size, clause);
 }
 const char *pfh_inflate_clause_text(int clause) { return pf_inflate::clause_text(clause); }
+
+// ---- plain gzip: the rule without a device ------------------------------------------------------------
+static void gunzip_stats_out(const pf_gunzip::Stats &st, uint64_t stats[9]) {
+    if (!stats) return;
+    const uint64_t v[9] = {st.pieces_found, st.pieces_live, st.pieces_dead, st.markers, st.blocks_stored, st.blocks_fixed, st.blocks_dynamic, st.bytes_in, st.bytes_out};
+    for (int i = 0; i < 9; ++i) stats[i] = v[i];
+}
+int pfh_gunzip_header(const uint8_t *bytes, uint64_t n, uint64_t *len) { return pf_gunzip::gzip_header(bytes, n, len); }
+int pfh_gunzip_file_kind(const uint8_t *first, uint64_t n_first, uint64_t file_size, int *clause) { return pf_gunzip::file_kind(first, n_first, file_size, clause); }
+int pfh_gunzip_candidate(const uint8_t *bytes, uint64_t n, uint64_t bit) { return pf_gunzip::block_candidate(bytes, n, bit) ? 1 : 0; }
+int pfh_gunzip_call(const uint8_t *comp, uint64_t n_bytes, uint64_t start_bit, const uint8_t *window, uint32_t n_window, uint32_t piece_bytes,
+                    uint8_t *out, uint64_t out_cap, uint8_t *new_window, pf_gunzip_result *res, uint64_t stats[9]) {
+    if (!res || n_bytes > 0x7fffffffull || start_bit > n_bytes * 8 || n_window > pf_gunzip::RING) return -2;
+    std::vector<uint8_t> text, win(pf_gunzip::RING);
+    pf_gunzip::Call r;
+    pf_gunzip::Stats st;
+    pf_gunzip::inflate_call(comp, n_bytes, start_bit, window, n_window, piece_bytes, text, win.data(), r, &st);
+    *res = pf_gunzip_result{r.out_bytes, r.end_bit, r.final, r.clause ? n_window : r.n_window, r.crc_raw, r.clause, r.clause_bit};
+    gunzip_stats_out(st, stats);
+    if (r.clause) return 0;
+    if (text.size() > out_cap) { res->out_bytes = text.size(); return -1; }
+    if (!text.empty()) memcpy(out, text.data(), text.size());
+    if (new_window && r.n_window) memcpy(new_window, win.data(), r.n_window);
+    return 0;
+}
+int pfh_gunzip_file(const uint8_t *bytes, uint64_t n, uint32_t piece_bytes, uint64_t block_bytes, uint64_t carry_max, uint8_t *out, uint64_t out_cap,
+                    uint64_t *out_len, uint64_t *member, uint64_t *byte, uint64_t stats[9]) {
+    std::vector<uint8_t> text;
+    pf_gunzip::Stats st;
+    const int c = pf_gunzip::gunzip_file(bytes, n, piece_bytes, block_bytes, text, member, byte, &st, carry_max ? carry_max : pf_gunzip::CARRY_MAX);
+    gunzip_stats_out(st, stats);
+    if (out_len) *out_len = text.size();
+    if (!c && text.size() <= out_cap && !text.empty()) memcpy(out, text.data(), text.size());
+    return c;
+}
+const char *pfh_gunzip_clause_text(int clause) { return pf_gunzip::clause_text(clause); }
 
 uint64_t pfh_bifrost_kmer_hash(uint64_t left_aligned_kmer, uint64_t seed) { return pfh::bifrost_kmer_hash(left_aligned_kmer, seed); }
 

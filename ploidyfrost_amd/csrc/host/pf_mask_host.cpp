@@ -19,6 +19,7 @@
 #include "pf_cutoffs.hpp"
 #include "pf_gz_host.hpp"
 #include "../pf_inflate_rule.hpp"
+#include "../pf_gunzip_rule.hpp"
 #include "pf_host_graph.hpp"
 
 namespace pfh {
@@ -66,7 +67,7 @@ bool same_file(const std::string &a, const std::string &b) {
 }
 
 int fastq_preflight(const char *who, const char *what, const std::vector<std::string> &inputs, const std::vector<std::string> &outputs,
-                    uint64_t &largest, std::string &err, bool gz) {
+                    uint64_t &largest, std::string &err, int gz) {
     const std::string w = who;
     auto text = [&](int clause) {   // (the FASTA and gzip texts end in what is done with FASTQ: "masked")
         std::string t = pf_mask::clause_text(clause);
@@ -96,6 +97,13 @@ int fastq_preflight(const char *who, const char *what, const std::vector<std::st
             }
             close(fd);
             int clause = 0;
+            if (gz == 2) {   // --gz-plain: blocked gzip as with --gz, any other gzip by its own header
+                if (pf_gunzip::file_kind(first, (uint64_t)got, std::max<uint64_t>(size, (uint64_t)got), &clause) == pf_gunzip::FILE_REFUSED) {
+                    err = w + ": " + in + ": member 1, byte 0: " + pf_gunzip::clause_text(clause);
+                    return 1;
+                }
+                continue;
+            }
             if (pf_inflate::file_clause_gz(first, (uint64_t)got, std::max<uint64_t>(size, (uint64_t)got), &clause) == pf_inflate::FILE_REFUSED) {
                 err = w + ": " + in + ": member 1, byte 0: " + pf_inflate::clause_text(clause);
                 return 1;
@@ -110,7 +118,7 @@ int fastq_preflight(const char *who, const char *what, const std::vector<std::st
 }
 
 int stream_fastq(pf_ctx *ctx, const char *who, const std::vector<std::string> &inputs, uint64_t chunk_bytes, uint64_t largest, int out_fd,
-                 const std::string &out_name, const ChunkStep &step, StreamTimes &tm, std::string &err, bool gz) {
+                 const std::string &out_name, const ChunkStep &step, StreamTimes &tm, std::string &err, int gz) {
     return stream_fastq_sized(ctx, who, inputs, chunk_bytes, largest, out_fd, out_name,
                               [&](const char *text, uint64_t n, bool final, char *out, uint64_t &used, uint64_t &reads, uint64_t &bad, uint64_t &out_len) {
                                   const int rc = step(text, n, final, out, used, reads, bad);
@@ -121,14 +129,14 @@ int stream_fastq(pf_ctx *ctx, const char *who, const std::vector<std::string> &i
 }
 
 int stream_fastq_sized(pf_ctx *ctx, const char *who_c, const std::vector<std::string> &inputs, uint64_t chunk_bytes, uint64_t largest, int out_fd,
-                       const std::string &out_name, const SizedChunkStep &step, StreamTimes &tm, std::string &err, bool gz) {
+                       const std::string &out_name, const SizedChunkStep &step, StreamTimes &tm, std::string &err, int gz) {
     const std::string who = who_c;
     err.clear();   // (a caller's `err` may still hold the text of an earlier call: the loop below runs while it is empty)
     const bool writes = out_fd >= 0;
     uint64_t chunk = chunk_bytes ? chunk_bytes : MASK_DEFAULT_CHUNK;
     std::vector<char> is_gz(inputs.size(), 0);   // with --gz: the inputs that start with the gzip magic are blocked gzip (the preflight has looked)
     bool any_gz = false;
-    for (size_t f = 0; gz && f < inputs.size(); ++f) any_gz |= (is_gz[f] = gz_magic(inputs[f])) != 0;
+    for (size_t f = 0; gz && f < inputs.size(); ++f) any_gz |= (is_gz[f] = (char)gz_kind(inputs[f], gz)) != 0;   // (--gz-plain: GZ_KIND_GZIP beside them)
     // (no gigabyte of pinned memory for a small file; a blocked-gzip file inflates to a multiple of its size)
     chunk = std::max<uint64_t>(1, std::min<uint64_t>(chunk, std::max<uint64_t>(any_gz ? std::max<uint64_t>(largest * 8, GZ_MEMBER_MAX) : largest, 1)));
     chunk = std::min<uint64_t>(chunk, 1ull << 31);                                               // a chunk and its carry stay below the 2^32 of the device calls
@@ -155,7 +163,8 @@ int stream_fastq_sized(pf_ctx *ctx, const char *who_c, const std::vector<std::st
                     b.input = f;
                     b.gz = true;
                     const auto t0 = clk::now();
-                    const bool ok = gr.next(in_buf[b.buf].p + MASK_HEAD, in_bytes, chunk, b.g, read_err);
+                    const bool ok = is_gz[f] == GZ_KIND_GZIP ? gr.next_raw(in_buf[b.buf].p + MASK_HEAD, std::min(in_bytes, gz_plain_block(chunk)), b.g, read_err)
+                                                             : gr.next(in_buf[b.buf].p + MASK_HEAD, in_bytes, chunk, b.g, read_err);
                     read_s += since(t0);
                     if (!ok) { blocks.close(); return; }
                     b.len = b.g.len;
@@ -220,7 +229,8 @@ int stream_fastq_sized(pf_ctx *ctx, const char *who_c, const std::vector<std::st
         if (b.gz) {
             if (!gzt) gzt.reset(new GzText(ctx));
             const auto t0 = clk::now();
-            const bool ok = gzt->append(who, inputs[b.input], in_buf[b.buf].p + MASK_HEAD, b.g, err);
+            const bool ok = b.g.plain ? gzt->append_plain(who, inputs[b.input], in_buf[b.buf].p + MASK_HEAD, b.g.len, b.g.file_off, b.g.eof, err)
+                                      : gzt->append(who, inputs[b.input], in_buf[b.buf].p + MASK_HEAD, b.g, err);
             tm.device_s += since(t0);
             if (!ok) break;
             text = gzt->text();

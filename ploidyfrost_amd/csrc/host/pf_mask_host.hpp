@@ -81,9 +81,10 @@ bool same_file(const std::string &a, const std::string &b);
 // The refusals that need no device, every input looked at before anything is written: no input, an input that cannot be read, FASTA,
 // gzip, an input that is one of `outputs`.  `what`: the last word of the FASTA / gzip texts ("masked", "counted").  largest: the size
 // of the largest input.  gz (`--gz`): an input with the gzip magic is blocked gzip (pf_inflate::file_clause_gz) or refused by the
-// clause of its first member; every other input, and every input without gz, goes the way above, byte for byte.
+// clause of its first member; every other input, and every input without gz, goes the way above, byte for byte.  gz = 2
+// (`--gz-plain`): any other gzip is taken as well (pf_gunzip::file_kind) and refused only for its method, a reserved flag or a cut header.
 int fastq_preflight(const char *who, const char *what, const std::vector<std::string> &inputs, const std::vector<std::string> &outputs,
-                    uint64_t &largest, std::string &err, bool gz = false);
+                    uint64_t &largest, std::string &err, int gz = 0);
 // One chunk on the device: text[0, n), final = the input ends with it; out = where output bytes go (null without an output).  Fills
 // used (bytes of whole records), reads (records), bad (0-based offender within the chunk); PF_OK or the call's status (pf_last_error).
 typedef std::function<int(const char *text, uint64_t n, bool final, char *out, uint64_t &used, uint64_t &reads, uint64_t &bad)> ChunkStep;
@@ -96,13 +97,14 @@ struct StreamTimes {
 // input and the 1-based record from the start of that input).  gz: the inputs that start with the gzip magic are blocked gzip -- the
 // reader packs whole members, K-INFLATE writes their text on the device behind the carried record, and the step gets a device
 // pointer (pf_gz_host.hpp); chunk_bytes then counts inflated bytes, and a refused member is worded `who: path: member N, byte B: clause`.
+// gz = 2: plain-gzip inputs are read in raw blocks and inflated by K-GUNZIP (GzText::append_plain).
 int stream_fastq(pf_ctx *ctx, const char *who, const std::vector<std::string> &inputs, uint64_t chunk_bytes, uint64_t largest, int out_fd,
-                 const std::string &out_name, const ChunkStep &step, StreamTimes &tm, std::string &err, bool gz = false);
+                 const std::string &out_name, const ChunkStep &step, StreamTimes &tm, std::string &err, int gz = 0);
 
 // The same for a step whose output is not as long as its input (`trim`: records are shortened or dropped): out holds n + 1 bytes, and
 // the step says in out_len how many of them the writer gets.  stream_fastq is this with out_len = used.
 typedef std::function<int(const char *text, uint64_t n, bool final, char *out, uint64_t &used, uint64_t &reads, uint64_t &bad, uint64_t &out_len)> SizedChunkStep;
 int stream_fastq_sized(pf_ctx *ctx, const char *who, const std::vector<std::string> &inputs, uint64_t chunk_bytes, uint64_t largest, int out_fd,
-                       const std::string &out_name, const SizedChunkStep &step, StreamTimes &tm, std::string &err, bool gz = false);
+                       const std::string &out_name, const SizedChunkStep &step, StreamTimes &tm, std::string &err, int gz = 0);
 
 }  // namespace pfh

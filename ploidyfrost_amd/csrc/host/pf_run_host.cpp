@@ -172,7 +172,7 @@ void add_masked_stats(pf_maskcount_stats &a, const pf_maskcount_stats &b) {
 
 int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<std::string> &inputs, bool paired, const TrimInputs &trim, uint64_t chunk_bytes,
                    uint64_t largest, bool masked, uint32_t low, uint32_t up, pf_trim_stats *unit_stats, pf_maskcount_stats *masked_stats, std::string &err,
-                   bool gz) {
+                   int gz) {
     const pf_trim_plan plan = {trim.steps.data(), (uint32_t)trim.steps.size(), trim.phred};
     if (!paired) {
         StreamTimes stm;

@@ -83,7 +83,7 @@ std::string trim_inputs_refusal(const std::vector<std::string> &inputs, bool pai
 // entry per input file, else one entry) and masked_stats (may be null) are added to.  0 = ok, else worded in err by `who`.
 int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<std::string> &inputs, bool paired, const TrimInputs &trim, uint64_t chunk_bytes,
                    uint64_t largest, bool masked, uint32_t low, uint32_t up, pf_trim_stats *unit_stats, pf_maskcount_stats *masked_stats, std::string &err,
-                   bool gz = false);
+                   int gz = 0);
 // the `trim:` line of a unit on stderr, in `trim`'s own format: st = the unit's statistics (paired: of file 1 and of file 2)
 std::string trim_unit_line(const pf_trim_stats *st, bool paired);
 
@@ -107,7 +107,7 @@ struct RunOptions {
     // STEP...: the inputs are raw reads (paired: -1 / -2, alternating file 1, file 2)
     TrimInputs trim;
     bool paired = false;
-    bool gz = false;   // --gz: inputs with the gzip magic are blocked gzip, inflated on the device in both passes (pf_gz_host.hpp)
+    int gz = 0;        // --gz (1), --gz-plain (2: any gzip, K-GUNZIP): inputs with the gzip magic are blocked gzip, inflated on the device in both passes (pf_gz_host.hpp)
 };
 struct RunStats {
     pf_count_stats counted = {};       // the first pass, finished with ci / cx / cs

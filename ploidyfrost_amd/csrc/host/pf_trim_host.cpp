@@ -280,19 +280,22 @@ int trim_fastq(const std::vector<std::string> &inputs, const std::string &out_pa
 }
 
 int stream_fastq_pair(pf_ctx *ctx, const char *who_c, const std::string &in1, const std::string &in2, uint64_t chunk_bytes, uint64_t largest,
-                      const PairChunkStep &step, PairStreamTimes &tm, std::string &err, bool gz) {
+                      const PairChunkStep &step, PairStreamTimes &tm, std::string &err, int gz) {
     const std::string who = who_c;
     const std::string inputs[2] = {in1, in2};
     err.clear();
-    const bool is_gz[2] = {gz && gz_magic(in1), gz && gz_magic(in2)};   // (each file of the pair by its own first bytes)
+    const int kind[2] = {gz_kind(in1, gz), gz_kind(in2, gz)};   // (each file of the pair by its own first bytes)
+    const bool is_gz[2] = {kind[0] != GZ_KIND_TEXT, kind[1] != GZ_KIND_TEXT};
     // a call holds what is pending of each file, up to two blocks of it: both stay below the 2^32 bytes of the device call
     uint64_t chunk = chunk_bytes ? chunk_bytes : MASK_DEFAULT_CHUNK;
     const uint64_t bound = (is_gz[0] || is_gz[1]) ? std::max<uint64_t>(largest * 8, GZ_MEMBER_MAX) : largest;   // (blocked gzip inflates to a multiple of the file)
     chunk = std::max<uint64_t>(1, std::min<uint64_t>(chunk, std::max<uint64_t>(bound, 1)));
     chunk = std::min<uint64_t>(chunk, 1ull << 30);
     PairReader rd[2];
-    rd[0].start(who, in1, chunk, is_gz[0]);
-    rd[1].start(who, in2, chunk, is_gz[1]);
+    // (a plain-gzip file is read as it is, in smaller blocks: its text is several times its bytes)
+    rd[0].start(who, in1, kind[0] == GZ_KIND_GZIP ? gz_plain_block(chunk) : chunk, kind[0] == GZ_KIND_BGZF);
+    rd[1].start(who, in2, kind[1] == GZ_KIND_GZIP ? gz_plain_block(chunk) : chunk, kind[1] == GZ_KIND_BGZF);
+    uint64_t raw_off[2] = {0, 0};   // bytes of a plain-gzip file handed over so far
 
     std::vector<char> pend[2];             // the carry of each file, then the blocks read behind it
     std::unique_ptr<GzText> gzt[2];        // the same of a blocked-gzip file: on the device
@@ -320,7 +323,9 @@ int stream_fastq_pair(pf_ctx *ctx, const char *who_c, const std::string &in1, co
                 if (!rd[f].blocks.pop(b)) { err = !rd[f].err.empty() ? rd[f].err : who + ": reading " + inputs[f] + " ended early"; break; }
                 if (is_gz[f]) {
                     const auto t0 = clk::now();
-                    const bool ok = gzt[f]->append(who, inputs[f], b.p.get(), b.g, err);
+                    const bool ok = kind[f] == GZ_KIND_GZIP ? gzt[f]->append_plain(who, inputs[f], b.p.get(), b.len, raw_off[f], b.eof, err)
+                                                            : gzt[f]->append(who, inputs[f], b.p.get(), b.g, err);
+                    raw_off[f] += b.len;
                     tm.device_s += since(t0);
                     if (!ok) break;
                 } else {

@@ -18,7 +18,7 @@ struct TrimOptions {
     uint32_t phred = 33;
     std::string trimlog;        // "" = none
     uint64_t chunk_bytes = 0;   // 0 = MASK_DEFAULT_CHUNK
-    bool gz = false;            // --gz: inputs with the gzip magic are blocked gzip, inflated on the device (pf_gz_host.hpp)
+    int gz = 0;                 // --gz (1), --gz-plain (2: any gzip, K-GUNZIP): inputs with the gzip magic are blocked gzip, inflated on the device (pf_gz_host.hpp)
 };
 struct TrimTimes {
     double stream_s = 0;   // first byte read to last byte written (wall)
@@ -55,6 +55,6 @@ struct PairStreamTimes {
     bool text_on_device[2] = {false, false};   // set before every step: that file's text is device memory (blocked gzip, inflated there)
 };
 int stream_fastq_pair(pf_ctx *ctx, const char *who, const std::string &in1, const std::string &in2, uint64_t chunk_bytes, uint64_t largest,
-                      const PairChunkStep &step, PairStreamTimes &tm, std::string &err, bool gz = false);
+                      const PairChunkStep &step, PairStreamTimes &tm, std::string &err, int gz = 0);
 
 }  // namespace pfh

@@ -41,6 +41,12 @@ K_UNION = K_MASKCOUNT + 1    # PF_K_UNION ("k_union"): everything one pf_kmer_un
 K_COLORSET = K_UNION + 1     # PF_K_COLORSET ("k_colorset"): the kernel of one pf_color_kmers; unit: keys
 K_TRIMCOUNT = K_COLORSET + 1   # PF_K_TRIMCOUNT ("k_trimcount"): everything one pf_*_trimmed / pf_trim_table_* call launches; unit: records
 K_INFLATE = K_TRIMCOUNT + 1    # PF_K_INFLATE ("k_inflate"): everything one pf_inflate_bgzf launches; unit: inflated bytes
+K_GUNZIP = K_INFLATE + 1       # PF_K_GUNZIP ("k_gunzip"): everything one pf_inflate_gzip launches; unit: inflated bytes
+GUNZIP_RESULT = np.dtype([("out_bytes", "<u8"), ("end_bit", "<u8"), ("final", "<u4"), ("n_window", "<u4"), ("crc_raw", "<u4"), ("clause", "<u4"),
+                          ("clause_bit", "<u8")])   # pf_gunzip_result
+GUNZIP_COUNTERS = ("pieces_found", "pieces_live", "pieces_dead", "markers", "blocks_stored", "blocks_fixed", "blocks_dynamic", "bytes_in", "bytes_out")
+GUNZIP_STAGES = ("find", "count", "decode", "window", "resolve")
+GUNZIP_STATS = np.dtype([(f, "<u8") for f in GUNZIP_COUNTERS] + [("stage_ms", "<f8", (5,))])   # pf_gunzip_stats
 INFLATE_STATS = np.dtype([(f, "<u8") for f in ("members", "bytes_in", "bytes_out", "blocks_stored", "blocks_fixed", "blocks_dynamic")])   # pf_inflate_stats
 UNION_TILE = 1024            # pf_runmulti::UNION_TILE: merged positions a block of K-UNION takes
 UNION_ITEMS = 4              # pf_runmulti::UNION_ITEMS: ... and a lane
@@ -252,6 +258,7 @@ def load_library() -> C.CDLL:
         "pf_device_alloc": (i, [vp, C.c_size_t, C.POINTER(vp)]),
         "pf_copy": (i, [vp, vp, vp, C.c_size_t]),
         "pf_inflate_bgzf": (i, [vp, vp, u64, vp, u64, vp, u64, C.POINTER(u64), vp, C.POINTER(u64)]),
+        "pf_inflate_gzip": (i, [vp, vp, u64, u64, vp, u32, u32, vp, u64, vp, vp, vp]),
         "pf_trim_table_fastq": (i, [vp, vp, u64, i, vp, vp, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp, C.POINTER(u64)]),
         "pf_trim_table_fastq_pair": (i, [vp, vp, u64, vp, u64, i, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp,
                                          C.POINTER(u64)]),
@@ -287,7 +294,7 @@ DECLARED_SYMBOLS = ["pf_create", "pf_warmup", "pf_destroy", "pf_last_error", "pf
                     "pf_maskcount_reads", "pf_maskcount_fastq", "pf_unitig_text",
                     "pf_kmer_union", "pf_color_kmers", "pf_release_counts",
                     "pf_trim_table_fastq", "pf_trim_table_fastq_pair", "pf_count_fastq_trimmed", "pf_count_fastq_pair_trimmed",
-                    "pf_maskcount_fastq_trimmed", "pf_maskcount_fastq_pair_trimmed", "pf_inflate_bgzf", "pf_device_alloc", "pf_copy"]
+                    "pf_maskcount_fastq_trimmed", "pf_maskcount_fastq_pair_trimmed", "pf_inflate_bgzf", "pf_inflate_gzip", "pf_device_alloc", "pf_copy"]
 
 
 class TrimPlan(C.Structure):   # pf_trim_plan
@@ -645,6 +652,39 @@ class Device:
             e.needed = out_n.value
             raise e
         return out[: out_n.value], {f: int(stats[0][f]) for f in INFLATE_STATS.names}
+
+    def inflate_gzip(self, comp, start_bit: int = 0, window=None, piece_bytes: int = 0, out=None, out_cap=None, new_window=None):
+        """K-GUNZIP (pf_inflate_gzip): the deflate stream comp[0:] of a plain gzip member from start_bit (a block start) on, up to a final
+        block or the last complete block boundary; returns (text, result, stats, new_window).  comp, window, out, new_window: bytes, uint8
+        numpy arrays or device tensors; window: the last <= 32768 bytes of the member's text so far; result: the fields of
+        pf_gunzip_result (end_bit, final, n_window, crc_raw, ...); stats: the counters and stage_ms by name.  A refused stream raises
+        DeviceError with .clause and .clause_bit; a buffer too small raises it with status PF_ERR_OVERFLOW and .needed."""
+        as_arr = lambda b: np.frombuffer(bytes(b), dtype=np.uint8) if isinstance(b, (bytes, bytearray)) else b   # noqa: E731
+        comp, window = as_arr(comp), as_arr(window) if window is not None else None
+        n, n_window = int(comp.shape[0]), int(window.shape[0]) if window is not None else 0
+        if new_window is None:
+            new_window = np.zeros(32768, dtype=np.uint8)
+        res, stats = np.zeros(1, dtype=GUNZIP_RESULT), np.zeros(1, dtype=GUNZIP_STATS)
+        call = lambda o, cap: self.L.pf_inflate_gzip(self.h, _ptr(comp) if n else None, n, start_bit, _ptr(window) if n_window else None, n_window,   # noqa: E731
+                                                     piece_bytes, _ptr(o) if o is not None and cap else None, cap, _ptr(new_window), res.ctypes.data,
+                                                     stats.ctypes.data)
+        if out is None:   # sized by a first call that writes nothing
+            st = call(None, 0)
+            if st == PF_ERR_OVERFLOW:
+                out = np.zeros(int(res[0]["out_bytes"]), dtype=np.uint8)
+                st = call(out, int(out.shape[0]))
+            else:
+                out = np.zeros(0, dtype=np.uint8)
+        else:
+            st = call(out, int(out.shape[0]) if out_cap is None else out_cap)
+        r = {f: int(res[0][f]) for f in GUNZIP_RESULT.names}
+        if st != PF_OK:
+            e = DeviceError(st, self.L.pf_last_error(self.h).decode())
+            e.clause, e.clause_bit, e.needed = r["clause"], r["clause_bit"], r["out_bytes"]
+            raise e
+        sd = {f: int(stats[0][f]) for f in GUNZIP_COUNTERS}
+        sd["stage_ms"] = dict(zip(GUNZIP_STAGES, (float(x) for x in stats[0]["stage_ms"])))
+        return out[: r["out_bytes"]], r, sd, new_window[: r["n_window"]]
 
     def trim_fastq_pair(self, text1, text2, steps, phred: int = 33, final: bool = True, outs=None):
         """K-TRIM on one chunk of each file of a pair (pf_trim_fastq_pair): dict with out = [o1, u1, o2, u2], bytes_used = [file 1,

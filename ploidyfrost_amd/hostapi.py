@@ -48,7 +48,8 @@ DECLARED_SYMBOLS = ["pfh_open", "pfh_close", "pfh_last_error", "pfh_set_output_d
                     "pfh_trim_fastq", "pfh_trim_fastq_pair", "pfh_trim_parse_step", "pfh_trim_refusal_text", "pfh_trim_read", "pfh_trim_fastq_chunk",
                     "pfh_run_fastq_trimmed", "pfh_run_multi_fastq_trimmed", "pfh_trim_table_chunk", "pfh_trim_table_chunk_pair", "pfh_trim_table_clause_text",
                     "pfh_inflate_parse_member", "pfh_inflate_member", "pfh_inflate_bgzf_member", "pfh_inflate_crc32", "pfh_inflate_crc32_sliced",
-                    "pfh_inflate_file_clause", "pfh_inflate_clause_text", "pfh_reads_gz"]
+                    "pfh_inflate_file_clause", "pfh_inflate_clause_text", "pfh_reads_gz",
+                    "pfh_gunzip_header", "pfh_gunzip_file_kind", "pfh_gunzip_candidate", "pfh_gunzip_call", "pfh_gunzip_file", "pfh_gunzip_clause_text"]
 
 
 class RunOptions(C.Structure):   # pfh_run_options (include/ploidyfrost_host.h)
@@ -275,6 +276,13 @@ def load_library() -> C.CDLL:
     L.pfh_inflate_file_clause.argtypes = [vp, u64, u64, C.POINTER(C.c_int)]
     L.pfh_inflate_clause_text.restype = C.c_char_p
     L.pfh_inflate_clause_text.argtypes = [C.c_int]
+    L.pfh_gunzip_header.argtypes = [vp, u64, C.POINTER(u64)]
+    L.pfh_gunzip_file_kind.argtypes = [vp, u64, u64, C.POINTER(C.c_int)]
+    L.pfh_gunzip_candidate.argtypes = [vp, u64, u64]
+    L.pfh_gunzip_call.argtypes = [vp, u64, u64, vp, u32, u32, vp, u64, vp, vp, vp]
+    L.pfh_gunzip_file.argtypes = [vp, u64, u32, u64, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp]
+    L.pfh_gunzip_clause_text.restype = C.c_char_p
+    L.pfh_gunzip_clause_text.argtypes = [C.c_int]
     _lib = L
     return L
 
@@ -624,6 +632,15 @@ def trim_table_chunk(text, steps, phred: int = 33, final: bool = True, text2=Non
     return out
 
 
+def _gz_mode(gz) -> int:
+    """gz= of the reads calls: False, True (`--gz`: blocked gzip) or "plain" (`--gz-plain`: any gzip) -> what pfh_reads_gz takes"""
+    if isinstance(gz, str):
+        if gz != "plain":
+            raise ValueError('gz is False, True or "plain"')
+        return 2
+    return int(bool(gz))
+
+
 def trim_fastq(inputs, out: str, steps, phred: int = 33, trimlog=None, chunk_bytes: int = 0, gz: bool = False) -> dict:
     """`ploidyfrost trim -i ... -o out STEP...` (pfh_trim_fastq): the reads of the FASTQ file(s) `inputs`, one after the other,
     quality-trimmed by `steps` (Trimmomatic's words) into `out`; trimlog: a file with one line per record.  Returns the statistics.  A
@@ -635,7 +652,7 @@ def trim_fastq(inputs, out: str, steps, phred: int = 33, trimlog=None, chunk_byt
     st = trim_parse_steps(steps)
     paths = (C.c_char_p * max(len(inputs), 1))(*[os.fsencode(p) for p in inputs])
     stats = np.zeros(len(TRIM_STATS_FIELDS), dtype=np.uint64)
-    L.pfh_reads_gz(int(gz))
+    L.pfh_reads_gz(_gz_mode(gz))
     rc = L.pfh_trim_fastq(paths, len(inputs), os.fsencode(out), st.ctypes.data if len(st) else None, len(st), phred,
                           os.fsencode(trimlog) if trimlog else None, int(chunk_bytes), 0, stats.ctypes.data)
     if rc:
@@ -651,7 +668,7 @@ def trim_fastq_pair(in1: str, in2: str, outs, steps, phred: int = 33, trimlog=No
     assert len(outs) == 4
     paths = (C.c_char_p * 4)(*[os.fsencode(p) for p in outs])
     stats = np.zeros((2, len(TRIM_STATS_FIELDS)), dtype=np.uint64)
-    L.pfh_reads_gz(int(gz))
+    L.pfh_reads_gz(_gz_mode(gz))
     rc = L.pfh_trim_fastq_pair(os.fsencode(in1), os.fsencode(in2), paths, st.ctypes.data if len(st) else None, len(st), phred,
                                os.fsencode(trimlog) if trimlog else None, int(chunk_bytes), 0, stats.ctypes.data)
     if rc:
@@ -678,7 +695,7 @@ def count_fastq(inputs, out_prefix: str, k: int = 25, ci: int = 2, cx: int = 10 
     L = load_library()
     paths, n = _paths(inputs)
     stats = np.zeros(len(COUNT_STATS_FIELDS), dtype=np.uint64)
-    L.pfh_reads_gz(int(gz))
+    L.pfh_reads_gz(_gz_mode(gz))
     rc = L.pfh_count_fastq(paths, n, os.fsencode(out_prefix), int(k), int(ci), int(cx), int(cs), int(both_strands),
                            None if hist is None else os.fsencode(hist), int(chunk_bytes), int(initial_slots), 0, stats.ctypes.data)
     if rc:
@@ -809,13 +826,13 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
     o.gfa_out = None if gfa_out is None else os.fsencode(gfa_out)
     stats = np.zeros(len(RUN_STATS_FIELDS), dtype=np.uint64)
     if steps is None and pairs is None:
-        L.pfh_reads_gz(int(gz))
+        L.pfh_reads_gz(_gz_mode(gz))
         rc = L.pfh_run_fastq(paths, n, os.fsencode(out_prefix), C.byref(o), 0, stats.ctypes.data)
         if rc:
             raise (ReadsRefused if gz else RuntimeError)(L.pfh_last_error(None).decode())
         return {f: int(v) for f, v in zip(RUN_STATS_FIELDS, stats)}
     per = np.zeros((max(n, 1), len(TRIM_STATS_FIELDS)), dtype=np.uint64)
-    L.pfh_reads_gz(int(gz))
+    L.pfh_reads_gz(_gz_mode(gz))
     rc = L.pfh_run_fastq_trimmed(paths, n, int(pairs is not None), st.ctypes.data if len(st) else None, len(st), int(phred), os.fsencode(out_prefix),
                                  C.byref(o), 0, stats.ctypes.data, per.ctypes.data)
     if rc:
@@ -879,13 +896,13 @@ def run_multi_reads(samples, out_prefix: str, k: int = 25, ci: int = 1, cx: int 
     per_in = np.zeros((max(len(flat), 1), len(TRIM_STATS_FIELDS)), dtype=np.uint64)
     if trimmed:
         pair_of = np.ascontiguousarray(paired, dtype=np.int32)
-        L.pfh_reads_gz(int(gz))
+        L.pfh_reads_gz(_gz_mode(gz))
         rc = L.pfh_run_multi_fastq_trimmed(c_names, n_of.ctypes.data if len(names) else None, pair_of.ctypes.data if len(names) else None, len(names), paths,
                                            st.ctypes.data if len(st) else None, len(st), int(phred), os.fsencode(out_prefix), C.byref(o),
                                            C.byref(multi) if multi is not None else None, int(each_color), 0, stats.ctypes.data, per.ctypes.data,
                                            per_in.ctypes.data)
     else:
-        L.pfh_reads_gz(int(gz))
+        L.pfh_reads_gz(_gz_mode(gz))
         rc = L.pfh_run_multi_fastq(c_names, n_of.ctypes.data if len(names) else None, len(names), paths, os.fsencode(out_prefix), C.byref(o),
                                    C.byref(multi) if multi is not None else None, int(each_color), 0, stats.ctypes.data, per.ctypes.data)
     if rc:
@@ -1539,6 +1556,83 @@ def inflate_crc32(data, n_lanes: int = 0) -> int:
     a, p = _u8(data)
     L = load_library()
     return L.pfh_inflate_crc32_sliced(p, len(a), n_lanes) if n_lanes else L.pfh_inflate_crc32(p, len(a))
+
+
+# ---- plain gzip: the rule of K-GUNZIP without a device (csrc/pf_gunzip_rule.hpp) ----
+GUNZIP_CLAUSES = ("reserved_flag", "header_past", "cut_block", "cut_trailer", "trailing", "block_too_large", "piece_limit")   # pf_gunzip::Clause, behind INFLATE_CLAUSES
+GUNZIP_COUNTERS = ("pieces_found", "pieces_live", "pieces_dead", "markers", "blocks_stored", "blocks_fixed", "blocks_dynamic", "bytes_in", "bytes_out")
+
+
+def gunzip_clause_text(clause: int) -> str:
+    return load_library().pfh_gunzip_clause_text(clause).decode()
+
+
+def gunzip_header(data, n=None):
+    """pfh_gunzip_header: (clause, header length) of the member header at data[0:n]"""
+    a = np.frombuffer(bytes(data), dtype=np.uint8)
+    ln = C.c_uint64()
+    clause = load_library().pfh_gunzip_header(a.ctypes.data if len(a) else None, len(a) if n is None else n, C.byref(ln))
+    return clause, ln.value
+
+
+def gunzip_file_kind(first, file_size=None):
+    """pfh_gunzip_file_kind: (kind, clause): kind 0 plain, 1 blocked gzip, 2 refused by `clause`, 3 gzip for K-GUNZIP"""
+    a = np.frombuffer(bytes(first), dtype=np.uint8)
+    clause = C.c_int()
+    kind = load_library().pfh_gunzip_file_kind(a.ctypes.data if len(a) else None, len(a), len(a) if file_size is None else file_size, C.byref(clause))
+    return kind, clause.value
+
+
+def gunzip_candidate(data, bit: int) -> bool:
+    a = np.frombuffer(bytes(data), dtype=np.uint8)
+    return bool(load_library().pfh_gunzip_candidate(a.ctypes.data if len(a) else None, len(a), bit))
+
+
+def gunzip_call(comp, start_bit: int = 0, window=b"", piece_bytes: int = 0, out_cap=None):
+    """pfh_gunzip_call: one call of pf_inflate_gzip's algorithm on the host -> (text, result dict, stats dict, new window), as
+    Device.inflate_gzip returns them (a refused stream has result["clause"] set and no text; out_cap too small raises OverflowError)"""
+    from . import hipapi
+    a, w = np.frombuffer(bytes(comp), dtype=np.uint8), np.frombuffer(bytes(window), dtype=np.uint8)
+    res, stats, new_w = np.zeros(1, dtype=hipapi.GUNZIP_RESULT), np.zeros(9, dtype=np.uint64), np.zeros(32768, dtype=np.uint8)
+    L = load_library()
+    call = lambda o, cap: L.pfh_gunzip_call(a.ctypes.data if len(a) else None, len(a), start_bit, w.ctypes.data if len(w) else None, len(w), piece_bytes,   # noqa: E731
+                                            o.ctypes.data, cap, new_w.ctypes.data, res.ctypes.data, stats.ctypes.data)
+    out = np.zeros(1, dtype=np.uint8)
+    rc = call(out, 0 if out_cap is None else out_cap)
+    if rc == -1 and out_cap is None:
+        out = np.zeros(int(res[0]["out_bytes"]), dtype=np.uint8)
+        rc = call(out, len(out))
+    if rc == -1:
+        raise OverflowError(int(res[0]["out_bytes"]))
+    if rc != 0:
+        raise ValueError("pfh_gunzip_call: arguments out of range")
+    r = {f: int(res[0][f]) for f in hipapi.GUNZIP_RESULT.names}
+    n = 0 if r["clause"] else r["out_bytes"]
+    return out[:n].tobytes(), r, dict(zip(GUNZIP_COUNTERS, (int(x) for x in stats))), new_w[: r["n_window"]].tobytes()
+
+
+def gunzip_member(data, piece_bytes: int = 0, block_bytes: int = 0, carry_max: int = 0, stats=None):
+    """The host rule of `--gz-plain` over a whole gzip file in memory (pfh_gunzip_file): every member's text, one behind the other.  The
+    file goes through the loop the stream seams run, in blocks of block_bytes (0: at once), each call cut into pieces of piece_bytes.
+    ValueError names a refusal as the commands do (`member N, byte B: clause`) and carries .clause, .member, .byte.  stats: a dict
+    that receives the summed counters."""
+    a = np.frombuffer(bytes(data), dtype=np.uint8)
+    L = load_library()
+    out_len, member, byte, st = C.c_uint64(), C.c_uint64(), C.c_uint64(), np.zeros(9, dtype=np.uint64)
+    out = np.zeros(1, dtype=np.uint8)
+    for _ in range(2):
+        clause = L.pfh_gunzip_file(a.ctypes.data if len(a) else None, len(a), piece_bytes, block_bytes, carry_max, out.ctypes.data, len(out), C.byref(out_len),
+                                   C.byref(member), C.byref(byte), st.ctypes.data)
+        if clause or out_len.value <= len(out):
+            break
+        out = np.zeros(out_len.value, dtype=np.uint8)
+    if clause:
+        e = ValueError("member %d, byte %d: %s" % (member.value + 1, byte.value, gunzip_clause_text(clause)))
+        e.clause, e.member, e.byte = clause, member.value, byte.value
+        raise e
+    if stats is not None:
+        stats.update(zip(GUNZIP_COUNTERS, (int(x) for x in st)))
+    return out[: out_len.value].tobytes()
 
 
 def inflate_file_clause(first, file_size=None):
