@@ -74,6 +74,7 @@ enum pf_kernel {
     PF_K_TRIMCOUNT, /* K-TRIMCOUNT: everything one pf_trim_table_fastq* / pf_count_fastq*_trimmed / pf_maskcount_fastq*_trimmed launches (index, intervals, table, then K-COUNT's or K-MASKCOUNT's core), timed as one launch; unit: records */
     PF_K_INFLATE, /* K-INFLATE: everything one pf_inflate_bgzf launches (headers, scan, inflate with the CRC), timed as one launch; unit: inflated bytes */
     PF_K_GUNZIP, /* K-GUNZIP: everything one pf_inflate_gzip launches (find, count, chain, decode, window, resolve with the CRC), timed as one launch; unit: inflated bytes */
+    PF_K_FASTA, /* K-FASTA: everything the index of one pf_fasta_index / pf_count_fasta / pf_maskcount_fasta / pf_color_fasta call launches (newlines, lines, words, scans, compact, table), timed as one launch; the core behind it is timed under its own kernel; unit: bytes of the chunk */
     PF_K_COUNT_
 };
 int pf_enable_timing(pf_ctx *, int on);
@@ -316,6 +317,33 @@ int pf_color_begin(pf_ctx *, uint32_t n_colors);
 int pf_color_reads(pf_ctx *, uint32_t colour, const char *text, uint64_t n_bytes, const uint64_t *read_off, const uint32_t *read_len, uint64_t n_reads,
                    pf_color_stats *stats);
 int pf_color_fastq(pf_ctx *, uint32_t colour, const char *text, uint64_t n_bytes, int final, uint64_t *bytes_used, pf_color_stats *stats,
+                   uint64_t *bad_record);
+/* K-FASTA: FASTA reads and assemblies -- one chunk of FASTA text turned on the device into what pf_count_reads, pf_maskcount_reads and
+ * pf_color_reads take: the sequences of its whole records as one compacted text (one directly behind the other, no separator) and the
+ * table (read_off, read_len) into it.  The rule (csrc/pf_fasta_rule.hpp): lines end at '\n', a '\r' directly in front of it is not
+ * content; a line whose first byte is '>' is a header and opens a record; every other line is a sequence line of the record opened
+ * last (an empty line: an empty one; a '>' elsewhere: a sequence byte; no byte is refused); reads = headers, bases = sequence bytes, a
+ * record without a sequence byte is a read of length 0.  The chunk contract is pf_mask_fastq's with FASTA's meaning of "whole": with
+ * final = 0 a record is whole when a later header line starts inside the chunk, and *bytes_used is the first byte of the last such
+ * line (only one: no record, *bytes_used = 0, the caller carries everything); with final = 1 every record is whole.  A chunk starts at
+ * a record start: a first byte other than '>' is PF_ERR_ARG ("record 0 of the chunk: ...").  n_bytes < 2^32 - 256.  No state crosses calls.
+ * What a call makes of F is what its _fastq twin makes of Q(F) -- every record rewritten as "@header", the joined sequence, "+" and one
+ * 'I' per base -- in counts, statistics and refusals of the core.
+ * pf_fasta_index leaves the index on the device: *text_dev (*n_bases bytes, 16-byte aligned), *read_off_dev, *read_len_dev (*n_records
+ * entries) belong to the context and are valid until its next K-FASTA call; pf_fasta_index_fetch copies them to the caller's buffers
+ * (text_cap bytes, table_cap entries; too small: PF_ERR_ARG by name with the sizes needed, which n_records / n_bases then hold).
+ * pf_count_fasta, pf_maskcount_fasta, pf_color_fasta: the contracts of pf_count_fastq, pf_maskcount_fastq, pf_color_fastq; each runs
+ * K-FASTA and then pf_count_reads / pf_maskcount_reads / pf_color_reads over the compacted text on the device.  The index is timed as one
+ * launch of PF_K_FASTA (unit: bytes of the chunk), the core as PF_K_COUNT / PF_K_MASKCOUNT.  text: [host|dev] */
+#define PF_FASTA_TILE 4096 /* bytes of the chunk one block compacts at a time */
+int pf_fasta_index(pf_ctx *, const char *text, uint64_t n_bytes, int final, uint64_t *bytes_used, uint64_t *n_records, uint64_t *n_bases,
+                   const char **text_dev, const uint64_t **read_off_dev, const uint32_t **read_len_dev);
+int pf_fasta_index_fetch(pf_ctx *, const char *text, uint64_t n_bytes, int final, uint64_t *bytes_used, uint64_t *n_records, uint64_t *n_bases,
+                         char *text_out, uint64_t text_cap, uint64_t *read_off, uint32_t *read_len, uint64_t table_cap);
+int pf_count_fasta(pf_ctx *, const char *text, uint64_t n_bytes, int final, uint64_t *bytes_used, pf_count_stats *stats, uint64_t *bad_record);
+int pf_maskcount_fasta(pf_ctx *, const char *text, uint64_t n_bytes, int final, uint32_t low, uint32_t up, uint64_t *bytes_used,
+                       pf_maskcount_stats *stats, uint64_t *bad_record);
+int pf_color_fasta(pf_ctx *, uint32_t colour, const char *text, uint64_t n_bytes, int final, uint64_t *bytes_used, pf_color_stats *stats,
                    uint64_t *bad_record);
 /* K-COLORSET: colour `colour` from the sorted or unsorted distinct canonical k-mers of its reads instead of from the reads (the rule:
  * csrc/pf_runmulti_rule.hpp) -- one look-up per key in the table pf_color_begin built, the same planes pf_color_reads sets from the

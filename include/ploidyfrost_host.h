@@ -543,6 +543,18 @@ uint32_t pfh_inflate_crc32_sliced(const uint8_t *bytes, uint32_t n, uint32_t n_l
 int pfh_inflate_file_clause(const uint8_t *first, uint64_t n_first, uint64_t file_size, int *clause);
 const char *pfh_inflate_clause_text(int clause);
 
+/* ---- FASTA (K-FASTA, `--fasta`): the rule without a device (csrc/pf_fasta_rule.hpp) ----
+ * pfh_reads_fasta(1): the next pfh_count_fastq, pfh_build_fastq, pfh_build_colored_fastq, pfh_run_fastq or pfh_run_multi_fastq of this
+ * thread reads every input (with pfh_reads_gz: every inflated input) whose first byte is '>' as FASTA; the call takes the switch back.
+ * The trimmed forms of run refuse it by name (FASTA has no qualities to trim).
+ * pfh_fasta_index: the host rule on one chunk -- the compacted text (text_out, text_cap bytes) and the table (read_off / read_len,
+ * table_cap entries) of its whole records; *n_records / *n_bases are the sizes needed whatever the capacities.  0, or the clause
+ * (pfh_fasta_clause_text): 1 = the text does not start with '>'. */
+void pfh_reads_fasta(int on);
+int pfh_fasta_index(const char *text, uint64_t n, int final, uint64_t *bytes_used, uint64_t *n_records, uint64_t *n_bases, char *text_out,
+                    uint64_t text_cap, uint64_t *read_off, uint32_t *read_len, uint64_t table_cap);
+const char *pfh_fasta_clause_text(int clause);
+
 /* ---- plain gzip (K-GUNZIP, `--gz-plain`): the rule without a device (csrc/pf_gunzip_rule.hpp) ----
  * pfh_reads_gz(2) selects `--gz-plain` for the next reads call: an input with the gzip magic is blocked gzip (K-INFLATE, as with 1) or
  * any other gzip, inflated by K-GUNZIP.

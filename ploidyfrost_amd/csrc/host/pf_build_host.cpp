@@ -49,7 +49,7 @@ int build_fastq(const std::vector<std::string> &inputs, const std::string &out_p
     { const std::string why = build_options_refusal(opt); if (!why.empty()) { err = "build: " + why; return 1; } }
     const std::string out_path = out_prefix + ".gfa";
     uint64_t largest = 0;
-    if (fastq_preflight("build", "read", inputs, {out_path}, largest, err)) return 1;
+    if (fastq_preflight("build", "read", inputs, {out_path}, largest, err, 0, opt.fasta)) return 1;
 
     pf_ctx *ctx = nullptr;
     if (pf_create(device, &ctx) != PF_OK) {
@@ -66,6 +66,7 @@ int build_fastq(const std::vector<std::string> &inputs, const std::string &out_p
     copt.both_strands = true;
     copt.chunk_bytes = opt.chunk_bytes;
     copt.initial_slots = opt.initial_slots;
+    copt.fasta = opt.fasta;
     Counted db;
     CountTimes ctm;
     if (count_stream(ctx, "build", inputs, copt, largest, db, counted, ctm, err)) return 1;
@@ -135,7 +136,7 @@ int build_colored_fastq(const std::vector<std::string> &inputs, const std::strin
     { const std::string why = colored_inputs_refusal(inputs); if (!why.empty()) { err = "build-multi: " + why; return 1; } }
     const std::string gfa_path = out_prefix + ".gfa", col_path = out_prefix + ".bfg_colors";
     uint64_t largest = 0;
-    if (fastq_preflight("build-multi", "read", inputs, {gfa_path, col_path}, largest, err)) return 1;
+    if (fastq_preflight("build-multi", "read", inputs, {gfa_path, col_path}, largest, err, 0, opt.fasta)) return 1;
 
     pf_ctx *ctx = nullptr;
     if (pf_create(device, &ctx) != PF_OK) {
@@ -153,6 +154,7 @@ int build_colored_fastq(const std::vector<std::string> &inputs, const std::strin
     copt.both_strands = true;
     copt.chunk_bytes = opt.chunk_bytes;
     copt.initial_slots = opt.initial_slots;
+    copt.fasta = opt.fasta;
     Counted db;
     CountTimes ctm;
     if (count_stream(ctx, "build-multi", inputs, copt, largest, db, counted, ctm, err)) return 1;
@@ -179,7 +181,9 @@ int build_colored_fastq(const std::vector<std::string> &inputs, const std::strin
         if (stream_fastq(ctx, "build-multi", {inputs[c]}, opt.chunk_bytes, largest, -1, "",
                          [&](const char *text, uint64_t n, bool final, char *, uint64_t &used, uint64_t &reads, uint64_t &bad) {
                              pf_color_stats st = {};
-                             const int rc = pf_color_fastq(ctx, (uint32_t)c, text, n, final ? 1 : 0, &used, &st, &bad);
+                             const int rc = opt.fasta && chunk_is_fasta(ctx, text, n, stm.text_on_device)
+                                                ? pf_color_fasta(ctx, (uint32_t)c, text, n, final ? 1 : 0, &used, &st, &bad)
+                                                : pf_color_fastq(ctx, (uint32_t)c, text, n, final ? 1 : 0, &used, &st, &bad);
                              reads = st.reads;
                              return rc;
                          },

@@ -23,6 +23,7 @@ struct BuildOptions {   // Bifrost's letters
     bool del_isolated = false;    // -d
     uint64_t chunk_bytes = 0;     // 0: MASK_DEFAULT_CHUNK
     uint64_t initial_slots = 0;   // 0: twice the first chunk's bytes
+    bool fasta = false;           // --fasta: inputs whose first byte is '>' are FASTA (K-FASTA, ../pf_fasta_rule.hpp)
 };
 struct BuildTimes {
     double stream_s = 0;   // first byte read to the last chunk counted (wall)

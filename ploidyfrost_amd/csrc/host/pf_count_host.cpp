@@ -47,7 +47,9 @@ int count_stream(pf_ctx *ctx, const char *who_c, const std::vector<std::string> 
         return stream_fastq(ctx, who_c, inputs, opt.chunk_bytes, largest, -1, "",
                             [&](const char *text, uint64_t n, bool final, char *, uint64_t &used, uint64_t &reads, uint64_t &bad) {
                                 pf_count_stats st = {};
-                                const int rc = pf_count_fastq(ctx, text, n, final ? 1 : 0, &used, &st, &bad);
+                                const int rc = opt.fasta && chunk_is_fasta(ctx, text, n, stm.text_on_device)
+                                                   ? pf_count_fasta(ctx, text, n, final ? 1 : 0, &used, &st, &bad)
+                                                   : pf_count_fastq(ctx, text, n, final ? 1 : 0, &used, &st, &bad);
                                 reads = st.reads;
                                 return rc;
                             },
@@ -150,7 +152,7 @@ int count_fastq(const std::vector<std::string> &inputs, const std::string &out_p
     std::vector<std::string> outputs = {out_prefix + ".kmc_pre", out_prefix + ".kmc_suf"};
     if (!opt.hist.empty()) outputs.push_back(opt.hist);
     uint64_t largest = 0;
-    if (fastq_preflight("count", "counted", inputs, outputs, largest, err, opt.gz)) return 1;
+    if (fastq_preflight("count", "counted", inputs, outputs, largest, err, opt.gz, opt.fasta)) return 1;
 
     pf_ctx *ctx = nullptr;
     if (pf_create(device, &ctx) != PF_OK) {

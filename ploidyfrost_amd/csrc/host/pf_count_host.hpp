@@ -23,6 +23,7 @@ struct CountOptions {   // kmc's letters and defaults
     uint64_t chunk_bytes = 0;     // 0: MASK_DEFAULT_CHUNK
     uint64_t initial_slots = 0;   // 0: twice the first chunk's bytes
     std::string hist;             // --hist: the histogram file of the finished counters
+    bool fasta = false;           // --fasta: a chunk whose first byte is '>' goes through pf_count_fasta (K-FASTA, ../pf_fasta_rule.hpp)
     int gz = 0;                   // --gz (1), --gz-plain (2: any gzip, K-GUNZIP): inputs with the gzip magic are blocked gzip, inflated on the device (pf_gz_host.hpp)
 };
 struct CountTimes {

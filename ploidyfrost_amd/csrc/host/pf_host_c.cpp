@@ -21,6 +21,7 @@
 #include "../pf_trimrun_rule.hpp"
 #include "../pf_inflate_rule.hpp"
 #include "../pf_gunzip_rule.hpp"
+#include "../pf_fasta_rule.hpp"
 #include "pf_trim_host.hpp"
 #include "pf_trace.hpp"
 #include "../pf_model_rows.hpp"
@@ -256,6 +257,27 @@ void *pfh_device_ctx(pfh_run *r) { return r->cdbg->device(); }
 static thread_local int g_reads_gz = 0;   // 0, 1 `--gz`, 2 `--gz-plain`
 void pfh_reads_gz(int on) { g_reads_gz = on == 2 ? 2 : on != 0; }
 static int take_reads_gz() { const int gz = g_reads_gz; g_reads_gz = 0; return gz; }
+// ---- FASTA inputs: the next count, build or run call of this thread takes them (`--fasta`) ----
+static thread_local bool g_reads_fasta = false;
+void pfh_reads_fasta(int on) { g_reads_fasta = on != 0; }
+static bool take_reads_fasta() { const bool f = g_reads_fasta; g_reads_fasta = false; return f; }
+// the host rule of K-FASTA (pf_fasta::index_fasta): the compacted text and the table of one chunk.  0, or the clause; the sizes needed
+// come back in n_records / n_bases whatever the capacities.
+int pfh_fasta_index(const char *text, uint64_t n, int final, uint64_t *bytes_used, uint64_t *n_records, uint64_t *n_bases, char *text_out,
+                    uint64_t text_cap, uint64_t *read_off, uint32_t *read_len, uint64_t table_cap) {
+    pf_fasta::Index ix;
+    const int clause = pf_fasta::index_fasta(text, n, final != 0, ix);
+    if (bytes_used) *bytes_used = ix.bytes_used;
+    if (n_records) *n_records = ix.n_records;
+    if (n_bases) *n_bases = ix.bases;
+    if (text_out && ix.bases <= text_cap && ix.bases) memcpy(text_out, ix.text.data(), (size_t)ix.bases);
+    for (uint64_t i = 0; i < table_cap && i < ix.n_records; ++i) {
+        if (read_off) read_off[i] = ix.read_off[i];
+        if (read_len) read_len[i] = ix.read_len[i];
+    }
+    return clause;
+}
+const char *pfh_fasta_clause_text(int clause) { return pf_fasta::clause_text(clause); }
 
 // ---- reads masked against the database (K-MASK) ----------------------------------------------------
 int pfh_mask_fastq(const char *db_prefix, const char *const *inputs, uint32_t n_inputs, const char *out_path, uint32_t low, uint32_t up,
@@ -395,6 +417,7 @@ int pfh_count_fastq(const char *const *inputs, uint32_t n_inputs, const char *ou
         opt.chunk_bytes = chunk_bytes;
         opt.initial_slots = initial_slots;
         opt.gz = take_reads_gz();
+        opt.fasta = take_reads_fasta();
         if (hist) opt.hist = hist;
         pf_count_stats st = {};
         const int rc = pfh::count_fastq(in, out_prefix, opt, device, st, nullptr, g_open_err);
@@ -475,6 +498,7 @@ int pfh_build_fastq(const char *const *inputs, uint32_t n_inputs, const char *ou
         std::vector<std::string> in;
         for (uint32_t i = 0; i < n_inputs; ++i) in.push_back(inputs[i] ? inputs[i] : "");
         pfh::BuildOptions opt;
+        opt.fasta = take_reads_fasta();
         opt.k = k;
         opt.g = g;
         opt.clip_tips = clip_tips != 0;
@@ -534,6 +558,7 @@ static int run_fastq_c(const char *who, const char *const *inputs, uint32_t n_in
         pfh::RunOptions opt;
         run_options_from(o, opt);
         opt.gz = take_reads_gz();
+        opt.fasta = take_reads_fasta();
         opt.call.threads = o->threads ? o->threads : 1;
         if (o->model_source >= 0) {
             opt.call.model.on = true;
@@ -579,6 +604,7 @@ static int run_multi_fastq_c(const char *who, const char *const *names, const ui
         pfh::RunMultiOptions mopt;
         pfh::RunOptions &opt = mopt.run;
         opt.gz = take_reads_gz();
+        opt.fasta = take_reads_fasta();
         run_options_from(o, opt);
         trim_inputs_from(steps, n_steps, phred, opt.trim);
         mopt.call.threads = o->threads ? o->threads : 1;
@@ -738,6 +764,7 @@ int pfh_build_colored_fastq(const char *const *inputs, uint32_t n_inputs, const 
         std::vector<std::string> in;
         for (uint32_t i = 0; i < n_inputs; ++i) in.push_back(inputs[i] ? inputs[i] : "");
         pfh::BuildOptions opt;
+        opt.fasta = take_reads_fasta();
         opt.k = k;
         opt.g = g;
         opt.clip_tips = clip_tips != 0;

@@ -93,7 +93,7 @@ void PrintUsage() {
          << "Usage: PloidyFrost cutoffL -d <KMCDatabase>" << endl
          << "Usage: PloidyFrost cutoffU -d <KMCDatabase> (quantile[<1 ,default:0.998])" << endl
          << "Usage: PloidyFrost histogram -d <KMCDatabase> [-o <file>]   (the k-mer histogram file of the database, count<TAB>number per row)" << endl << endl
-         << "Usage: PloidyFrost count -k 25 -ci 1 -cs 10000 [-cx N] [-b] -i <reads.fq> [-i <more.fq> ...] -o <KMCDatabase> [--hist <file>] [--chunk-bytes N] [--initial-slots N] [--gz] [--gz-plain] [-v]" << endl
+         << "Usage: PloidyFrost count -k 25 -ci 1 -cs 10000 [-cx N] [-b] -i <reads.fq> [-i <more.fq> ...] -o <KMCDatabase> [--hist <file>] [--chunk-bytes N] [--initial-slots N] [--gz] [--gz-plain] [--fasta] [-v]" << endl
          << "Usage: PloidyFrost mask -d <KMCDatabase> -i <reads.fq> [-i <more.fq> ...] -o <out.fq> (-l L | --auto-cutoffs) [-u U] [--chunk-bytes N] [-v]" << endl
          << "Usage: PloidyFrost mask -k 25 [-ci N -cs N -cx N -b] -i <reads.fq> ... -o <out.fq> (-l L | --auto-cutoffs) [-u U] [--db-out <KMCDatabase>] [--chunk-bytes N]" << endl
          << "                  (`kmc_tools filter -hm <db> <reads.fq> -ci<L> [-cx<U>] <out.fq>` on the device: every base of every k-mer whose count" << endl
@@ -109,7 +109,7 @@ void PrintUsage() {
          << "                  <sample>.bfg_colors, one colour per -r in the order given; what the calling run takes with -g and -f)" << endl << endl
          << "Usage: PloidyFrost run [-k 25 -ci 1 -cs 10000 -cx N] -i <trimmed.fq> [-i <more.fq> ...] -o <sample> [-q Q] [-u U] [--keep-tips] [--keep-isolated] [-g G]" << endl
          << "                  [-z -M -D -G -t --ref-threads] [--model cov|fre ... --model-only --filter \"OPTS\" --density ...] [--db-out <KMCDatabase>] [--gfa-out <sample>]" << endl
-         << "                  [--chunk-bytes N] [--initial-slots N] [--gz] [--gz-plain] [-v]" << endl
+         << "                  [--chunk-bytes N] [--initial-slots N] [--gz] [--gz-plain] [--fasta] [-v]" << endl
          << "                  (reads to ploidy estimate in one process: `mask -k ... --auto-cutoffs`, `build -i -d` and the calling run with --auto-cutoffs on" << endl
          << "                  one device context, no masked reads, database or graph file in between; L is printed on stdout)" << endl
          << "Usage: PloidyFrost run [the same options] (-i <raw.fq> [-i <more.fq> ...] | -1 <r1.fq> -2 <r2.fq> [-1 <r3.fq> -2 <r4.fq> ...]) -o <sample> STEP... [--phred 33|64]" << endl
@@ -117,13 +117,15 @@ void PrintUsage() {
          << "                  records go on when both are kept; `run-multi` takes STEP... and -1 / -2 inside a --sample likewise)" << endl << endl
          << "Usage: PloidyFrost run-multi [-k 25 -ci 1 -cs 10000 -cx N] --sample <NAME> -i <a.fq> [-i <b.fq> ...] --sample <NAME2> -i <c.fq> [...] -o <out> [-q Q] [-u U]" << endl
          << "                  [--keep-tips] [--keep-isolated] [-g G] [-z -M -D -G -t --ref-threads] [--model cov|fre --filter-multi \"OPTS\" [--model-each-color] [--density ...] [--model-only]]" << endl
-         << "                  [--db-out <KMCDatabase>] [--gfa-out <graph>] [--chunk-bytes N] [--initial-slots N] [--gz] [--gz-plain] [-v]" << endl
+         << "                  [--db-out <KMCDatabase>] [--gfa-out <graph>] [--chunk-bytes N] [--initial-slots N] [--gz] [--gz-plain] [--fasta] [-v]" << endl
          << "                  (reads of several samples to one estimate per sample in one process: `mask -k ... --auto-cutoffs` per sample, `build-multi -i -d`" << endl
          << "                  and the coloured calling run with --auto-cutoffs on one device context; a sample is a colour, in the order given; every L on stdout)" << endl << endl
          << "                  (--gz of count, trim, run and run-multi: an input that starts with the gzip magic is blocked gzip -- what bgzip, bcl2fastq2 and" << endl
          << "                  BCL Convert write -- and is inflated on the device; plain gzip is refused: recompress it with bgzip, or decompress it)" << endl
          << "                  (--gz-plain of the same commands implies --gz and takes any other gzip file as well -- what gzip and pigz write, one member or" << endl
-         << "                  several -- its deflate streams cut into pieces at block starts and inflated on the device; every member's CRC-32 is checked)" << endl << endl
+         << "                  several -- its deflate streams cut into pieces at block starts and inflated on the device; every member's CRC-32 is checked)" << endl
+         << "                  (--fasta of count, build, build-multi, run -i and run-multi -i: an input whose first byte -- with --gz / --gz-plain: first inflated" << endl
+         << "                  byte -- is '>' is FASTA, multi-line or not; its records are counted as the same reads in FASTQ would be; FASTA and FASTQ files may be mixed)" << endl << endl
          << "Usage: PloidyFrost model ...          (GMM ploidy inference from the coverage / frequency files; `PloidyFrost model` prints its options)" << endl
          << "Usage: PloidyFrost density -f <column file> -o <outfile_prefix> [-n points] [-a adjust]   (kernel density of a column of numbers)" << endl
          << "Usage: PloidyFrost filter ...         (the row predicates of script/Filter.R over <prefix>_*cov.txt; -h prints its options)" << endl
@@ -550,7 +552,7 @@ int take_count_option(int argc, char **argv, int &i, CountArgs &c, string &why) 
 
 // `count`: step `2.kmc_db` of the reference's workflow (`kmc -ci1 -cs10000 -k25 @FILES kmc_sample tmp`) on the device
 int count_main(int argc, char **argv) {
-    const char *usage = "Usage:PloidyFrost count -k 25 -ci 1 -cs 10000 [-cx N] [-b] -i reads.fq [-i more.fq ...] -o kmc_database [--hist file] [--chunk-bytes N] [--initial-slots N] [--gz] [--gz-plain] [-v]";
+    const char *usage = "Usage:PloidyFrost count -k 25 -ci 1 -cs 10000 [-cx N] [-b] -i reads.fq [-i more.fq ...] -o kmc_database [--hist file] [--chunk-bytes N] [--initial-slots N] [--gz] [--gz-plain] [--fasta] [-v]";
     CountArgs c;
     string out;
     vector<string> inputs;
@@ -574,6 +576,7 @@ int count_main(int argc, char **argv) {
         if (a == "-v") verbose = true;
         else if (a == "--gz") c.opt.gz = std::max(c.opt.gz, 1);
         else if (a == "--gz-plain") c.opt.gz = 2;
+        else if (a == "--fasta") c.opt.fasta = true;
         else if (!has_value) return refuse(a == "-i" || a == "-o" || a == "--hist" || a == "--chunk-bytes" || a == "--initial-slots" ? a + " needs a value" : "unknown option " + a);
         else if (a == "-i") inputs.push_back(argv[++i]);
         else if (a == "-o") out = argv[++i];
@@ -602,7 +605,7 @@ int count_main(int argc, char **argv) {
 // `build`: step `4.bifrost` of the reference's workflow (`Bifrost build -i -d -k 25 -r sample_filtered.fq -o sample`) on the device.  The
 // letters are Bifrost's: -i clips tips here, the reads come with -r.
 int build_main(int argc, char **argv) {
-    const char *usage = "Usage:PloidyFrost build -k 25 [-i] [-d] -r reads.fq [-r more.fq ...] -o sample [-g G] [-t N] [--chunk-bytes N] [--initial-slots N] [-v]";
+    const char *usage = "Usage:PloidyFrost build -k 25 [-i] [-d] -r reads.fq [-r more.fq ...] -o sample [-g G] [-t N] [--chunk-bytes N] [--initial-slots N] [--fasta] [-v]";
     pfh::BuildOptions opt;
     string out;
     vector<string> inputs;
@@ -626,6 +629,7 @@ int build_main(int argc, char **argv) {
         if (a == "-i") { opt.clip_tips = true; continue; }
         if (a == "-d") { opt.del_isolated = true; continue; }
         if (a == "-v") { verbose = true; continue; }
+        if (a == "--fasta") { opt.fasta = true; continue; }
         const bool takes_value = a == "-k" || a == "-g" || a == "-t" || a == "-r" || a == "-o" || a == "--chunk-bytes" || a == "--initial-slots";
         if (!takes_value) return refuse("unknown option " + a);
         if (i + 1 >= argc) return refuse(a + " needs a value");
@@ -666,7 +670,7 @@ int build_main(int argc, char **argv) {
 // `build-multi`: the last step of the reference's multi-sample workflow (`Bifrost build -i -d -k 25 -r s0.fq -r s1.fq ... -c -o sample`)
 // on the device: the graph of `build` from all files together, and the colour file with one colour per -r in the order given.
 int build_multi_main(int argc, char **argv) {
-    const char *usage = "Usage:PloidyFrost build-multi -k 25 [-i] [-d] -r s0.fq -r s1.fq [-r ...] -o sample [-g G] [-t N] [--chunk-bytes N] [--initial-slots N] [-v]";
+    const char *usage = "Usage:PloidyFrost build-multi -k 25 [-i] [-d] -r s0.fq -r s1.fq [-r ...] -o sample [-g G] [-t N] [--chunk-bytes N] [--initial-slots N] [--fasta] [-v]";
     pfh::BuildOptions opt;
     string out;
     vector<string> inputs;
@@ -690,6 +694,7 @@ int build_multi_main(int argc, char **argv) {
         if (a == "-d") { opt.del_isolated = true; continue; }
         if (a == "-v") { verbose = true; continue; }
         if (a == "-c") continue;   // (Bifrost's letter for what this sub-command always does)
+        if (a == "--fasta") { opt.fasta = true; continue; }
         const bool takes_value = a == "-k" || a == "-g" || a == "-t" || a == "-r" || a == "-o" || a == "--chunk-bytes" || a == "--initial-slots";
         if (!takes_value) return refuse("unknown option " + a);
         if (i + 1 >= argc) return refuse(a + " needs a value");
@@ -759,6 +764,7 @@ int mask_main(int argc, char **argv) {
         }
         const bool has_value = i + 1 < argc;
         if (a == "--auto-cutoffs") auto_cutoffs = true;
+        else if (a == "--fasta") return refuse("--fasta is not built into mask: the masked output has the input's layout (count, build, build-multi, run and run-multi take FASTA)");
         else if (a == "-v") verbose = true;
         else if (!has_value) return refuse(a == "-d" || a == "-i" || a == "-o" || a == "-l" || a == "-u" || a == "--chunk-bytes" || a == "--db-out" ? a + " needs a value" : "unknown option " + a);
         else if (a == "-d") db = argv[++i];
@@ -817,6 +823,7 @@ int trim_main(int argc, char **argv) {
         if (a == "-v") { verbose = true; continue; }
         if (a == "--gz") { opt.gz = std::max(opt.gz, 1); continue; }
         if (a == "--gz-plain") { opt.gz = 2; continue; }
+        if (a == "--fasta") return refuse("--fasta does not go with trim: FASTA has no qualities to trim");
         const bool known = a == "-i" || a == "-o" || a == "--phred" || a == "--trimlog" || a == "--chunk-bytes" ||
                            std::find_if(pair_opts, pair_opts + 6, [&](const char *o) { return a == o; }) != pair_opts + 6;
         if (!known) return refuse("unknown option " + a);
@@ -937,7 +944,7 @@ int calling_main(Options &opt, DensityCli &dc);
 int run_main(int argc, char **argv) {
     const char *usage = "Usage:PloidyFrost run [-k 25] [-ci 1] [-cs 10000] [-cx N] -i trimmed.fq [-i more.fq ...] -o sample [-q Q] [-u U] [--keep-tips] [--keep-isolated] [-g G]\n"
                         "                 [-z Z -M m -D d -G g -t T --ref-threads N] [--model cov|fre ... --model-only --filter \"OPTS\" --density ...]\n"
-                        "                 [--db-out <KMCDatabase>] [--gfa-out <sample>] [--chunk-bytes N] [--initial-slots N] [--gz] [--gz-plain] [-v]\n"
+                        "                 [--db-out <KMCDatabase>] [--gfa-out <sample>] [--chunk-bytes N] [--initial-slots N] [--gz] [--gz-plain] [--fasta] [-v]\n"
                         "      PloidyFrost run [the same options] -i raw.fq [-i more.fq ...] -o sample STEP... [--phred 33|64]\n"
                         "      PloidyFrost run [the same options] -1 r1.fq -2 r2.fq [-1 r3.fq -2 r4.fq ...] -o sample STEP... [--phred 33|64]\n"
                         "      STEP: LEADING:t TRAILING:t SLIDINGWINDOW:w:t MINLEN:l (the raw reads are trimmed on the way in, as `trim` trims them)";
@@ -1001,6 +1008,7 @@ int run_main(int argc, char **argv) {
         if (a == "-v") { verbose = true; continue; }
         if (a == "--gz") { opt.gz = std::max(opt.gz, 1); continue; }
         if (a == "--gz-plain") { opt.gz = 2; continue; }
+        if (a == "--fasta") { opt.fasta = true; continue; }
         if (a == "--keep-tips") { opt.clip_tips = false; continue; }
         if (a == "--keep-isolated") { opt.del_isolated = false; continue; }
         const bool takes_value = a == "-i" || a == "-o" || a == "-q" || a == "-u" || a == "-g" || a == "-z" || a == "-M" || a == "-D" || a == "-G" || a == "-t" ||
@@ -1080,7 +1088,7 @@ int run_multi_main(int argc, char **argv) {
     const char *usage = "Usage:PloidyFrost run-multi [-k 25] [-ci 1] [-cs 10000] [-cx N] --sample NAME -i a.fq [-i b.fq ...] --sample NAME2 -i c.fq [...] -o out\n"
                         "                 [-q Q] [-u U] [--keep-tips] [--keep-isolated] [-g G] [-z Z -M m -D d -G g -t T --ref-threads N]\n"
                         "                 [--model cov|fre --filter-multi \"OPTS\" [--model-each-color] [--density ...] [--model-only]]\n"
-                        "                 [--db-out <KMCDatabase>] [--gfa-out <graph>] [--chunk-bytes N] [--initial-slots N] [--gz] [--gz-plain] [-v]\n"
+                        "                 [--db-out <KMCDatabase>] [--gfa-out <graph>] [--chunk-bytes N] [--initial-slots N] [--gz] [--gz-plain] [--fasta] [-v]\n"
                         "      PloidyFrost run-multi [the same options] --sample NAME (-i raw.fq ... | -1 r1.fq -2 r2.fq ...) --sample NAME2 ... -o out STEP... [--phred 33|64]\n"
                         "      STEP: LEADING:t TRAILING:t SLIDINGWINDOW:w:t MINLEN:l (the raw reads are trimmed on the way in, as `trim` trims them)";
     auto refuse = [&](const string &why) { cerr << "Error: run-multi: " << why << endl << usage << endl; return 1; };
@@ -1151,6 +1159,7 @@ int run_multi_main(int argc, char **argv) {
         if (a == "-v") { verbose = true; continue; }
         if (a == "--gz") { opt.gz = std::max(opt.gz, 1); continue; }
         if (a == "--gz-plain") { opt.gz = 2; continue; }
+        if (a == "--fasta") { opt.fasta = true; continue; }
         if (a == "--keep-tips") { opt.clip_tips = false; continue; }
         if (a == "--keep-isolated") { opt.del_isolated = false; continue; }
         const bool takes_value = a == "--sample" || a == "-i" || a == "-o" || a == "-q" || a == "-u" || a == "-g" || a == "-z" || a == "-M" || a == "-D" || a == "-G" ||

@@ -20,6 +20,7 @@
 #include "pf_gz_host.hpp"
 #include "../pf_inflate_rule.hpp"
 #include "../pf_gunzip_rule.hpp"
+#include "../pf_fasta_rule.hpp"
 #include "pf_host_graph.hpp"
 
 namespace pfh {
@@ -67,7 +68,7 @@ bool same_file(const std::string &a, const std::string &b) {
 }
 
 int fastq_preflight(const char *who, const char *what, const std::vector<std::string> &inputs, const std::vector<std::string> &outputs,
-                    uint64_t &largest, std::string &err, int gz) {
+                    uint64_t &largest, std::string &err, int gz, bool fasta) {
     const std::string w = who;
     auto text = [&](int clause) {   // (the FASTA and gzip texts end in what is done with FASTQ: "masked")
         std::string t = pf_mask::clause_text(clause);
@@ -112,9 +113,17 @@ int fastq_preflight(const char *who, const char *what, const std::vector<std::st
         }
         close(fd);
         const int clause = pf_mask::file_clause(first, got > 0 ? (uint64_t)got : 0);
-        if (clause) { err = w + ": " + in + ": record 1: " + text(clause); return 1; }
+        if (clause && !(fasta && clause == pf_mask::CLAUSE_FASTA)) { err = w + ": " + in + ": record 1: " + text(clause); return 1; }
     }
     return 0;
+}
+
+bool chunk_is_fasta(pf_ctx *ctx, const char *text, uint64_t n, bool on_device) {
+    if (!n) return false;
+    char first = 0;
+    if (!on_device) first = text[0];
+    else if (pf_copy_to_host(ctx, &first, text, 1) != PF_OK) return false;   // (the FASTQ call reports what is wrong with the context)
+    return first == pf_fasta::HEADER_BYTE;
 }
 
 int stream_fastq(pf_ctx *ctx, const char *who, const std::vector<std::string> &inputs, uint64_t chunk_bytes, uint64_t largest, int out_fd,

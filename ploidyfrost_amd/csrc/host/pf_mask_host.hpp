@@ -83,8 +83,13 @@ bool same_file(const std::string &a, const std::string &b);
 // of the largest input.  gz (`--gz`): an input with the gzip magic is blocked gzip (pf_inflate::file_clause_gz) or refused by the
 // clause of its first member; every other input, and every input without gz, goes the way above, byte for byte.  gz = 2
 // (`--gz-plain`): any other gzip is taken as well (pf_gunzip::file_kind) and refused only for its method, a reserved flag or a cut header.
+// fasta (`--fasta`): a first byte of '>' is no refusal (an inflated input's kind shows only in the stream: the step decides).
 int fastq_preflight(const char *who, const char *what, const std::vector<std::string> &inputs, const std::vector<std::string> &outputs,
-                    uint64_t &largest, std::string &err, int gz = 0);
+                    uint64_t &largest, std::string &err, int gz = 0, bool fasta = false);
+// `--fasta`: the kind of a chunk is its first byte -- '>' is FASTA (../pf_fasta_rule.hpp), anything else goes the FASTQ way.  That holds
+// for every chunk, not only the first: chunks and carries start at record starts.  on_device (StreamTimes::text_on_device): the text
+// is device memory and the look costs a copy of one byte.
+bool chunk_is_fasta(pf_ctx *ctx, const char *text, uint64_t n, bool on_device);
 // One chunk on the device: text[0, n), final = the input ends with it; out = where output bytes go (null without an output).  Fills
 // used (bytes of whole records), reads (records), bad (0-based offender within the chunk); PF_OK or the call's status (pf_last_error).
 typedef std::function<int(const char *text, uint64_t n, bool final, char *out, uint64_t &used, uint64_t &reads, uint64_t &bad)> ChunkStep;

@@ -44,6 +44,7 @@ CountOptions count_options_of(const RunOptions &opt) {
     c.chunk_bytes = opt.chunk_bytes;
     c.initial_slots = opt.initial_slots;
     c.gz = opt.gz;
+    c.fasta = opt.fasta;
     return c;
 }
 
@@ -214,6 +215,7 @@ int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<std::string> 
 
 // ---- run ----
 std::string run_options_refusal(const RunOptions &opt) {
+    if (opt.fasta && (opt.trim.on() || opt.paired)) return "--fasta does not go with trim steps or -1 / -2 (FASTA has no qualities to trim)";
     { const int c = count_options_clause(count_options_of(opt), true); if (c) return pf_count::cut_text(c); }
     BuildOptions b;
     b.k = opt.k;
@@ -239,7 +241,7 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
     if (!opt.db_out.empty()) { outputs.push_back(opt.db_out + ".kmc_pre"); outputs.push_back(opt.db_out + ".kmc_suf"); }
     if (!gfa_path.empty()) outputs.push_back(gfa_path);
     uint64_t largest = 0;
-    if (fastq_preflight("run", "read", inputs, outputs, largest, err, opt.gz)) return 1;
+    if (fastq_preflight("run", "read", inputs, outputs, largest, err, opt.gz, opt.fasta)) return 1;
 
     pf_ctx *ctx = nullptr;
     if (pf_create(device, &ctx) != PF_OK) {
@@ -304,7 +306,9 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
                      : stream_fastq(ctx, "run", inputs, opt.chunk_bytes, largest, -1, "",
                          [&](const char *text, uint64_t n, bool final, char *, uint64_t &used, uint64_t &reads, uint64_t &bad) {
                              pf_maskcount_stats st = {};
-                             const int rc = pf_maskcount_fastq(ctx, text, n, final ? 1 : 0, stats.lower, opt.mask_up, &used, &st, &bad);
+                             const int rc = opt.fasta && chunk_is_fasta(ctx, text, n, stm.text_on_device)
+                                                ? pf_maskcount_fasta(ctx, text, n, final ? 1 : 0, stats.lower, opt.mask_up, &used, &st, &bad)
+                                                : pf_maskcount_fastq(ctx, text, n, final ? 1 : 0, stats.lower, opt.mask_up, &used, &st, &bad);
                              if (rc != PF_OK) return rc;
                              reads = st.reads;
                              stats.masked.reads += st.reads;

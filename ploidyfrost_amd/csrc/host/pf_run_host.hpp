@@ -108,6 +108,7 @@ struct RunOptions {
     TrimInputs trim;
     bool paired = false;
     int gz = 0;        // --gz (1), --gz-plain (2: any gzip, K-GUNZIP): inputs with the gzip magic are blocked gzip, inflated on the device in both passes (pf_gz_host.hpp)
+    bool fasta = false;   // --fasta: a chunk whose first byte is '>' goes through pf_count_fasta / pf_maskcount_fasta in the two passes (K-FASTA); not with trim steps
 };
 struct RunStats {
     pf_count_stats counted = {};       // the first pass, finished with ci / cx / cs

@@ -47,6 +47,7 @@ CountOptions count_options_of(const RunOptions &opt) {
     c.chunk_bytes = opt.chunk_bytes;
     c.initial_slots = opt.initial_slots;
     c.gz = opt.gz;
+    c.fasta = opt.fasta;
     return c;
 }
 
@@ -116,7 +117,7 @@ int run_multi_fastq(const std::vector<MultiSample> &samples, const std::string &
     }
     if (!gfa_path.empty()) { outputs.push_back(gfa_path); outputs.push_back(col_path); }
     uint64_t largest = 0;
-    if (fastq_preflight("run-multi", "read", all_inputs, outputs, largest, err, opt.gz)) return 1;
+    if (fastq_preflight("run-multi", "read", all_inputs, outputs, largest, err, opt.gz, opt.fasta)) return 1;
     for (uint32_t c = 0; c < C; ++c)   // one file under two names
         for (uint32_t d = 0; d < c; ++d)
             for (const std::string &a : samples[c].inputs)
@@ -207,7 +208,9 @@ int run_multi_fastq(const std::vector<MultiSample> &samples, const std::string &
                      : stream_fastq(ctx, "run-multi", samples[c].inputs, opt.chunk_bytes, largest, -1, "",
                          [&](const char *text, uint64_t n, bool final, char *, uint64_t &used, uint64_t &reads, uint64_t &bad) {
                              pf_maskcount_stats st = {};
-                             const int rc = pf_maskcount_fastq(ctx, text, n, final ? 1 : 0, stats.color[c].lower, opt.mask_up, &used, &st, &bad);
+                             const int rc = opt.fasta && chunk_is_fasta(ctx, text, n, stm.text_on_device)
+                                                ? pf_maskcount_fasta(ctx, text, n, final ? 1 : 0, stats.color[c].lower, opt.mask_up, &used, &st, &bad)
+                                                : pf_maskcount_fastq(ctx, text, n, final ? 1 : 0, stats.color[c].lower, opt.mask_up, &used, &st, &bad);
                              if (rc != PF_OK) return rc;
                              reads = st.reads;
                              stats.windows_bad += st.kmers_bad;

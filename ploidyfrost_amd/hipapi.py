@@ -42,6 +42,8 @@ K_COLORSET = K_UNION + 1     # PF_K_COLORSET ("k_colorset"): the kernel of one p
 K_TRIMCOUNT = K_COLORSET + 1   # PF_K_TRIMCOUNT ("k_trimcount"): everything one pf_*_trimmed / pf_trim_table_* call launches; unit: records
 K_INFLATE = K_TRIMCOUNT + 1    # PF_K_INFLATE ("k_inflate"): everything one pf_inflate_bgzf launches; unit: inflated bytes
 K_GUNZIP = K_INFLATE + 1       # PF_K_GUNZIP ("k_gunzip"): everything one pf_inflate_gzip launches; unit: inflated bytes
+K_FASTA = K_GUNZIP + 1         # PF_K_FASTA ("k_fasta"): everything the index of one pf_fasta_index / pf_*_fasta call launches; unit: bytes of the chunk
+FASTA_TILE = 4096              # PF_FASTA_TILE: bytes of the chunk one block of K-FASTA's compaction kernel takes at a time
 GUNZIP_RESULT = np.dtype([("out_bytes", "<u8"), ("end_bit", "<u8"), ("final", "<u4"), ("n_window", "<u4"), ("crc_raw", "<u4"), ("clause", "<u4"),
                           ("clause_bit", "<u8")])   # pf_gunzip_result
 GUNZIP_COUNTERS = ("pieces_found", "pieces_live", "pieces_dead", "markers", "blocks_stored", "blocks_fixed", "blocks_dynamic", "bytes_in", "bytes_out")
@@ -259,6 +261,11 @@ def load_library() -> C.CDLL:
         "pf_copy": (i, [vp, vp, vp, C.c_size_t]),
         "pf_inflate_bgzf": (i, [vp, vp, u64, vp, u64, vp, u64, C.POINTER(u64), vp, C.POINTER(u64)]),
         "pf_inflate_gzip": (i, [vp, vp, u64, u64, vp, u32, u32, vp, u64, vp, vp, vp]),
+        "pf_fasta_index": (i, [vp, vp, u64, i, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+        "pf_fasta_index_fetch": (i, [vp, vp, u64, i, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp, u64, vp, vp, u64]),
+        "pf_count_fasta": (i, [vp, vp, u64, i, C.POINTER(u64), vp, C.POINTER(u64)]),
+        "pf_maskcount_fasta": (i, [vp, vp, u64, i, u32, u32, C.POINTER(u64), vp, C.POINTER(u64)]),
+        "pf_color_fasta": (i, [vp, u32, vp, u64, i, C.POINTER(u64), vp, C.POINTER(u64)]),
         "pf_trim_table_fastq": (i, [vp, vp, u64, i, vp, vp, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp, C.POINTER(u64)]),
         "pf_trim_table_fastq_pair": (i, [vp, vp, u64, vp, u64, i, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp,
                                          C.POINTER(u64)]),
@@ -294,7 +301,8 @@ DECLARED_SYMBOLS = ["pf_create", "pf_warmup", "pf_destroy", "pf_last_error", "pf
                     "pf_maskcount_reads", "pf_maskcount_fastq", "pf_unitig_text",
                     "pf_kmer_union", "pf_color_kmers", "pf_release_counts",
                     "pf_trim_table_fastq", "pf_trim_table_fastq_pair", "pf_count_fastq_trimmed", "pf_count_fastq_pair_trimmed",
-                    "pf_maskcount_fastq_trimmed", "pf_maskcount_fastq_pair_trimmed", "pf_inflate_bgzf", "pf_inflate_gzip", "pf_device_alloc", "pf_copy"]
+                    "pf_maskcount_fastq_trimmed", "pf_maskcount_fastq_pair_trimmed", "pf_inflate_bgzf", "pf_inflate_gzip", "pf_device_alloc", "pf_copy",
+                    "pf_fasta_index", "pf_fasta_index_fetch", "pf_count_fasta", "pf_maskcount_fasta", "pf_color_fasta"]
 
 
 class TrimPlan(C.Structure):   # pf_trim_plan
@@ -797,6 +805,65 @@ class Device:
             e.bad_record = bad.value
             raise e
         return used.value, {f: int(stats[0][f]) for f in MASKCOUNT_STATS.names}
+
+    # ---- K-FASTA: FASTA chunks to compacted text and table, then the cores (pf_fasta_rule.hpp) ----
+    def _fasta_call(self, fn, text, final, stats, head=(), tail=()):   # head: in front of the text (a colour); tail: behind `final` (low, up)
+        if isinstance(text, (bytes, bytearray)):
+            text = np.frombuffer(bytes(text), dtype=np.uint8)
+        n = int(text.shape[0])
+        used, bad = C.c_uint64(), C.c_uint64()
+        st = fn(self.h, *head, _ptr(text) if n else None, n, int(final), *tail, C.byref(used), stats.ctypes.data, C.byref(bad))
+        if st != PF_OK:
+            e = DeviceError(st, self.L.pf_last_error(self.h).decode())
+            e.bad_record = bad.value
+            raise e
+        return used.value
+
+    def fasta_index(self, text, final: bool = True) -> dict:
+        """K-FASTA alone (pf_fasta_index_fetch) on one chunk of FASTA text: "text" = the compacted text (the sequences of the whole
+        records, one directly behind the other), "read_off" / "read_len" = the table into it, "bytes_used", "records", "bases" -- what
+        hostapi.fasta_index gives for the same chunk.  A chunk that does not start with '>' raises DeviceError."""
+        if isinstance(text, (bytes, bytearray)):
+            text = np.frombuffer(bytes(text), dtype=np.uint8)
+        n = int(text.shape[0])
+        used, n_rec, n_bases = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        off, ln = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint32)   # (a record holds at least its '>')
+        self._check(self.L.pf_fasta_index_fetch(self.h, _ptr(text) if n else None, n, int(final), C.byref(used), C.byref(n_rec), C.byref(n_bases),
+                                                out.ctypes.data, len(out), off.ctypes.data, ln.ctypes.data, len(off)))
+        return {"text": out[: n_bases.value].tobytes(), "read_off": off[: n_rec.value].copy(), "read_len": ln[: n_rec.value].copy(),
+                "bytes_used": used.value, "records": n_rec.value, "bases": n_bases.value}
+
+    def fasta_index_resident(self, text, final: bool = True) -> dict:
+        """K-FASTA alone, the index left on the device (pf_fasta_index): "bytes_used", "records", "bases", and the device addresses
+        "text_dev", "read_off_dev", "read_len_dev" (None where empty), which belong to the context until its next K-FASTA call."""
+        if isinstance(text, (bytes, bytearray)):
+            text = np.frombuffer(bytes(text), dtype=np.uint8)
+        n = int(text.shape[0])
+        used, n_rec, n_bases = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        dt, doff, dlen = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._check(self.L.pf_fasta_index(self.h, _ptr(text) if n else None, n, int(final), C.byref(used), C.byref(n_rec), C.byref(n_bases),
+                                          C.byref(dt), C.byref(doff), C.byref(dlen)))
+        return {"bytes_used": used.value, "records": n_rec.value, "bases": n_bases.value, "text_dev": dt.value, "read_off_dev": doff.value,
+                "read_len_dev": dlen.value}
+
+    def count_fasta(self, text, final: bool = True):
+        """pf_count_fasta on one chunk of a FASTA file: (bytes_used, this call's statistics), as count_fastq gives them for Q(F)."""
+        stats = np.zeros(1, dtype=COUNT_STATS)
+        used = self._fasta_call(self.L.pf_count_fasta, text, final, stats)
+        return used, {f: int(stats[0][f]) for f in COUNT_STATS.names}
+
+    def maskcount_fasta(self, text, low: int, up: int = MASK_NO_UPPER, final: bool = True):
+        """pf_maskcount_fasta on one chunk of a FASTA file: (bytes_used, this call's statistics), as maskcount_fastq gives them for Q(F)."""
+        stats = np.zeros(1, dtype=MASKCOUNT_STATS)
+        used = self._fasta_call(self.L.pf_maskcount_fasta, text, final, stats, tail=(low, up))
+        return used, {f: int(stats[0][f]) for f in MASKCOUNT_STATS.names}
+
+    def color_fasta(self, colour: int, text, final: bool = True):
+        """pf_color_fasta on one chunk of a FASTA file of `colour`: (bytes_used, this call's statistics)."""
+        stats = np.zeros(1, dtype=COLOR_STATS)
+        used = self._fasta_call(self.L.pf_color_fasta, text, final, stats, head=(int(colour),))
+        return used, {f: stats[0][f].item() for f in COLOR_STATS.names}
 
     # ---- K-TRIMCOUNT: K-TRIM folded into K-COUNT / K-MASKCOUNT (pf_trimrun_rule.hpp) ----
     @staticmethod

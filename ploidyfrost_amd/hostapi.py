@@ -48,7 +48,7 @@ DECLARED_SYMBOLS = ["pfh_open", "pfh_close", "pfh_last_error", "pfh_set_output_d
                     "pfh_trim_fastq", "pfh_trim_fastq_pair", "pfh_trim_parse_step", "pfh_trim_refusal_text", "pfh_trim_read", "pfh_trim_fastq_chunk",
                     "pfh_run_fastq_trimmed", "pfh_run_multi_fastq_trimmed", "pfh_trim_table_chunk", "pfh_trim_table_chunk_pair", "pfh_trim_table_clause_text",
                     "pfh_inflate_parse_member", "pfh_inflate_member", "pfh_inflate_bgzf_member", "pfh_inflate_crc32", "pfh_inflate_crc32_sliced",
-                    "pfh_inflate_file_clause", "pfh_inflate_clause_text", "pfh_reads_gz",
+                    "pfh_inflate_file_clause", "pfh_inflate_clause_text", "pfh_reads_gz", "pfh_reads_fasta", "pfh_fasta_index", "pfh_fasta_clause_text",
                     "pfh_gunzip_header", "pfh_gunzip_file_kind", "pfh_gunzip_candidate", "pfh_gunzip_call", "pfh_gunzip_file", "pfh_gunzip_clause_text"]
 
 
@@ -266,6 +266,13 @@ def load_library() -> C.CDLL:
     L.pfh_trim_table_clause_text.argtypes = [C.c_int]
     L.pfh_reads_gz.restype = None
     L.pfh_reads_gz.argtypes = [C.c_int]
+    L.pfh_reads_fasta.restype = None
+    L.pfh_reads_fasta.argtypes = [C.c_int]
+    L.pfh_fasta_index.restype = C.c_int
+    L.pfh_fasta_index.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p,
+                                  C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]
+    L.pfh_fasta_clause_text.restype = C.c_char_p
+    L.pfh_fasta_clause_text.argtypes = [C.c_int]
     L.pfh_inflate_parse_member.argtypes = [vp, u64, vp]
     L.pfh_inflate_member.argtypes = [vp, u32, vp, u32, C.POINTER(u32), vp]
     L.pfh_inflate_bgzf_member.argtypes = [vp, u64, vp, C.POINTER(u32), vp]
@@ -687,15 +694,17 @@ def _paths(inputs):
 
 
 def count_fastq(inputs, out_prefix: str, k: int = 25, ci: int = 2, cx: int = 10 ** 9, cs: int = 255, both_strands: bool = True, hist=None,
-                chunk_bytes: int = 0, initial_slots: int = 0, gz: bool = False) -> dict:
+                chunk_bytes: int = 0, initial_slots: int = 0, gz: bool = False, fasta: bool = False) -> dict:
     """`ploidyfrost count` (pfh_count_fastq): the k-mers of the FASTQ file(s) `inputs` counted on the device (K-COUNT), those with
     ci <= c <= cx written as min(c, cs) to <out_prefix>.kmc_pre / .kmc_suf in the KMC1 layout; hist: the histogram file of the finished
     counters.  Returns the statistics.  A refusal raises RuntimeError by name (format refusals with the input's path and the 1-based
-    record number); nothing is left under the output names."""
+    record number); nothing is left under the output names.  fasta (`--fasta`): an input whose first byte is '>' is read as FASTA
+    (K-FASTA); every other input as before."""
     L = load_library()
     paths, n = _paths(inputs)
     stats = np.zeros(len(COUNT_STATS_FIELDS), dtype=np.uint64)
     L.pfh_reads_gz(_gz_mode(gz))
+    L.pfh_reads_fasta(int(bool(fasta)))
     rc = L.pfh_count_fastq(paths, n, os.fsencode(out_prefix), int(k), int(ci), int(cx), int(cs), int(both_strands),
                            None if hist is None else os.fsencode(hist), int(chunk_bytes), int(initial_slots), 0, stats.ctypes.data)
     if rc:
@@ -721,6 +730,23 @@ def mask_fastq_counted(inputs, out: str, k: int = 25, ci: int = 2, cx: int = 10 
     d = {f: int(v) for f, v in zip(MASK_STATS_FIELDS, stats)}
     d["lower"] = used.value
     return d
+
+
+def fasta_index(text: bytes, final: bool = True) -> dict:
+    """The host rule of K-FASTA on one chunk (pfh_fasta_index, csrc/pf_fasta_rule.hpp; no device): "text" = the compacted text (the
+    sequences of the whole records, one directly behind the other), "read_off" / "read_len" = the table into it, "bytes_used",
+    "records", "bases".  A text that does not start with '>' raises ValueError with the clause's text."""
+    L = load_library()
+    src = np.frombuffer(bytes(text), dtype=np.uint8)
+    used, n_rec, n_bases = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    out = np.zeros(max(len(src), 1), dtype=np.uint8)
+    off, ln = np.zeros(max(len(src), 1), dtype=np.uint64), np.zeros(max(len(src), 1), dtype=np.uint32)   # (a record holds at least its '>')
+    rc = L.pfh_fasta_index(src.ctypes.data if len(src) else None, len(src), int(final), C.byref(used), C.byref(n_rec), C.byref(n_bases),
+                           out.ctypes.data, len(out), off.ctypes.data, ln.ctypes.data, len(off))
+    if rc:
+        raise ValueError(L.pfh_fasta_clause_text(rc).decode())
+    return {"text": out[: n_bases.value].tobytes(), "read_off": off[: n_rec.value].copy(), "read_len": ln[: n_rec.value].copy(),
+            "bytes_used": used.value, "records": n_rec.value, "bases": n_bases.value}
 
 
 def count_reads_host(text: bytes, read_off, read_len, k: int, both_strands: bool = True, ci: int = 2, cx: int = 10 ** 9, cs: int = 255):
@@ -771,14 +797,16 @@ UNITIG_STATS = np.dtype([(f, "<u8") for f in UNITIG_STATS_FIELDS + ("cycles", "r
 
 
 def build_graph(inputs, out_prefix: str, k: int = 25, clip_tips: bool = False, del_isolated: bool = False, g=None, chunk_bytes: int = 0,
-                initial_slots: int = 0) -> dict:
+                initial_slots: int = 0, fasta: bool = False) -> dict:
     """`ploidyfrost build` (pfh_build_fastq): the compacted de Bruijn graph of the FASTQ file(s) `inputs`, counted and compacted on the
     device (K-COUNT, K-UNITIG), written to <out_prefix>.gfa -- `Bifrost build [-i] [-d] -k <k> -r <inputs> -o <out_prefix>`.  Returns
-    the statistics of the count and of the graph.  A refusal raises RuntimeError by name; nothing is left under the output name."""
+    the statistics of the count and of the graph.  A refusal raises RuntimeError by name; nothing is left under the output name.
+    fasta (`--fasta`): an input whose first byte is '>' is read as FASTA (K-FASTA)."""
     L = load_library()
     paths, n = _paths(inputs)
     counted = np.zeros(len(COUNT_STATS_FIELDS), dtype=np.uint64)
     stats = np.zeros(1, dtype=UNITIG_STATS)
+    L.pfh_reads_fasta(int(bool(fasta)))
     rc = L.pfh_build_fastq(paths, n, os.fsencode(out_prefix), int(k), _unitig_g(g), int(clip_tips), int(del_isolated), int(chunk_bytes),
                            int(initial_slots), 0, counted.ctypes.data, stats.ctypes.data)
     if rc:
@@ -792,7 +820,7 @@ def build_graph(inputs, out_prefix: str, k: int = 25, clip_tips: bool = False, d
 def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 ** 9, cs: int = 10000, q: float = 0.998, mask_upper=None,
               keep_tips: bool = False, keep_isolated: bool = False, g=None, z: int = 8, M: float = 2.0, D: float = -1.0, G: float = -3.0,
               threads: int = 1, model=None, model_only: bool = False, db_out=None, gfa_out=None, chunk_bytes: int = 0,
-              initial_slots: int = 0, steps=None, phred: int = 33, pairs=None, gz: bool = False) -> dict:
+              initial_slots: int = 0, steps=None, phred: int = 33, pairs=None, gz: bool = False, fasta: bool = False) -> dict:
     """`ploidyfrost run` (pfh_run_fastq): reads to ploidy estimate in one process -- the FASTQ file(s) `inputs` counted, the thresholds
     derived, the k-mers of the masked reads counted (K-MASKCOUNT), the graph built and the single-sample calling run made on one device
     context; PloidyFrost_output/<out_prefix>_*.txt in the working directory.  model: None, "cov" or "fre".  Returns the fields of the
@@ -800,7 +828,9 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
     steps (Trimmomatic's words, as trim_fastq takes them): `run STEP...` (pfh_run_fastq_trimmed) -- the inputs are raw reads, trimmed on
     the device on the way into both passes; pairs = [(r1.fq, r2.fq), ...] instead of inputs (None then): the records of a pair go on
     only when both are kept.  The result then has "trim" as well: the statistics of every unit (one dict for all single-ended inputs;
-    per pair a list of two, file 1 and file 2), as the command's `trim:` lines give them."""
+    per pair a list of two, file 1 and file 2), as the command's `trim:` lines give them.
+    fasta (`--fasta`): an input whose first byte is '>' (with gz: whose first inflated byte is) is read as FASTA in both passes (K-FASTA);
+    refused by name together with steps or pairs."""
     L = load_library()
     if pairs is not None:
         if inputs is not None:
@@ -827,12 +857,14 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
     stats = np.zeros(len(RUN_STATS_FIELDS), dtype=np.uint64)
     if steps is None and pairs is None:
         L.pfh_reads_gz(_gz_mode(gz))
+        L.pfh_reads_fasta(int(bool(fasta)))
         rc = L.pfh_run_fastq(paths, n, os.fsencode(out_prefix), C.byref(o), 0, stats.ctypes.data)
         if rc:
             raise (ReadsRefused if gz else RuntimeError)(L.pfh_last_error(None).decode())
         return {f: int(v) for f, v in zip(RUN_STATS_FIELDS, stats)}
     per = np.zeros((max(n, 1), len(TRIM_STATS_FIELDS)), dtype=np.uint64)
     L.pfh_reads_gz(_gz_mode(gz))
+    L.pfh_reads_fasta(int(bool(fasta)))
     rc = L.pfh_run_fastq_trimmed(paths, n, int(pairs is not None), st.ctypes.data if len(st) else None, len(st), int(phred), os.fsencode(out_prefix),
                                  C.byref(o), 0, stats.ctypes.data, per.ctypes.data)
     if rc:
@@ -846,7 +878,8 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
 def run_multi_reads(samples, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 ** 9, cs: int = 10000, q: float = 0.998, mask_upper=None,
                     keep_tips: bool = False, keep_isolated: bool = False, g=None, z: int = 8, M: float = 2.0, D: float = -1.0, G: float = -3.0,
                     threads: int = 1, model=None, model_only: bool = False, filter_multi=None, each_color: bool = False, db_out=None, gfa_out=None,
-                    chunk_bytes: int = 0, initial_slots: int = 0, steps=None, phred: int = 33, pairs=None, gz: bool = False) -> dict:
+                    chunk_bytes: int = 0, initial_slots: int = 0, steps=None, phred: int = 33, pairs=None, gz: bool = False,
+                    fasta: bool = False) -> dict:
     """`ploidyfrost run-multi` (pfh_run_multi_fastq): reads of several samples to one estimate per sample in one process.  samples: a
     list of (name, file or list of files), a sample a colour in the order given.  Every sample is counted and its thresholds derived,
     the k-mers of its masked reads counted (K-MASKCOUNT), their union taken (K-UNION), the coloured graph built and coloured per
@@ -856,7 +889,8 @@ def run_multi_reads(samples, out_prefix: str, k: int = 25, ci: int = 1, cx: int 
     refusal raises RuntimeError by name.
     steps: `run-multi STEP...` (pfh_run_multi_fastq_trimmed) -- the files are raw reads, trimmed on the way into both passes; pairs: the
     names of the samples whose files are pairs (file 1, file 2, file 1, ...).  The result then has "trim": per sample the statistics of
-    its units, as run_reads gives them."""
+    its units, as run_reads gives them.
+    fasta (`--fasta`): as run_reads takes it; the files of a sample may mix FASTA and FASTQ."""
     L = load_library()
     names, counts, flat, paired = [], [], [], []
     for name, files in samples:
@@ -897,12 +931,14 @@ def run_multi_reads(samples, out_prefix: str, k: int = 25, ci: int = 1, cx: int 
     if trimmed:
         pair_of = np.ascontiguousarray(paired, dtype=np.int32)
         L.pfh_reads_gz(_gz_mode(gz))
+        L.pfh_reads_fasta(int(bool(fasta)))
         rc = L.pfh_run_multi_fastq_trimmed(c_names, n_of.ctypes.data if len(names) else None, pair_of.ctypes.data if len(names) else None, len(names), paths,
                                            st.ctypes.data if len(st) else None, len(st), int(phred), os.fsencode(out_prefix), C.byref(o),
                                            C.byref(multi) if multi is not None else None, int(each_color), 0, stats.ctypes.data, per.ctypes.data,
                                            per_in.ctypes.data)
     else:
         L.pfh_reads_gz(_gz_mode(gz))
+        L.pfh_reads_fasta(int(bool(fasta)))
         rc = L.pfh_run_multi_fastq(c_names, n_of.ctypes.data if len(names) else None, len(names), paths, os.fsencode(out_prefix), C.byref(o),
                                    C.byref(multi) if multi is not None else None, int(each_color), 0, stats.ctypes.data, per.ctypes.data)
     if rc:
@@ -988,11 +1024,12 @@ def _names(names):
 
 
 def build_colored_graph(inputs, out_prefix: str, k: int = 25, clip_tips: bool = False, del_isolated: bool = False, g=None, n_seeds: int = 0,
-                        chunk_bytes: int = 0, initial_slots: int = 0) -> dict:
+                        chunk_bytes: int = 0, initial_slots: int = 0, fasta: bool = False) -> dict:
     """`ploidyfrost build-multi` (pfh_build_colored_fastq): the coloured graph of the FASTQ files `inputs`, one colour a file in the
     order given -- `Bifrost build -c [-i] [-d] -k <k> -r ... -o <out_prefix>` on the device (K-COUNT, K-UNITIG, K-COLOR): <out_prefix>.gfa
     and <out_prefix>.bfg_colors.  Returns the statistics of the count, the graph and the colouring, "color_bytes" and "times".  A refusal
-    raises RuntimeError by name; nothing is left under either output name."""
+    raises RuntimeError by name; nothing is left under either output name.  fasta (`--fasta`): a file whose first byte is '>' is
+    read as FASTA (K-FASTA); assemblies and read sets may stand side by side."""
     L = load_library()
     paths, n = _paths(inputs)
     counted = np.zeros(len(COUNT_STATS_FIELDS), dtype=np.uint64)
@@ -1000,6 +1037,7 @@ def build_colored_graph(inputs, out_prefix: str, k: int = 25, clip_tips: bool = 
     col = np.zeros(1, dtype=COLOR_STATS)
     nb = C.c_uint64()
     times = np.zeros(6, dtype=np.float64)
+    L.pfh_reads_fasta(int(bool(fasta)))
     rc = L.pfh_build_colored_fastq(paths, n, os.fsencode(out_prefix), int(k), _unitig_g(g), int(clip_tips), int(del_isolated), int(n_seeds),
                                    int(chunk_bytes), int(initial_slots), 0, counted.ctypes.data, stats.ctypes.data, col.ctypes.data, C.byref(nb),
                                    times.ctypes.data)
