@@ -1,6 +1,7 @@
 #include "pf_build_host.hpp"
 
 #include "pf_bfg_write.hpp"
+#include "pf_host_util.hpp"
 
 #include <fcntl.h>
 #include <unistd.h>
@@ -18,17 +19,6 @@ using clk = std::chrono::steady_clock;
 double since(clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); }
 
 constexpr uint64_t FETCH_BLOCK_BYTES = 64ull << 20;   // text a download
-
-bool write_all(int fd, const void *p, uint64_t n) {
-    const char *c = static_cast<const char *>(p);
-    for (uint64_t done = 0; done < n;) {
-        const ssize_t put = write(fd, c + done, (size_t)(n - done));
-        if (put < 0 && errno == EINTR) continue;
-        if (put < 0) return false;
-        done += (uint64_t)put;
-    }
-    return true;
-}
 
 }  // namespace
 
@@ -48,15 +38,15 @@ int build_fastq(const std::vector<std::string> &inputs, const std::string &out_p
     if (out_prefix.empty()) { err = "build: no output prefix"; return 1; }
     { const std::string why = build_options_refusal(opt); if (!why.empty()) { err = "build: " + why; return 1; } }
     const std::string out_path = out_prefix + ".gfa";
-    uint64_t largest = 0;
-    if (fastq_preflight("build", "read", inputs, {out_path}, largest, err, 0, opt.fasta)) return 1;
+    std::vector<ReadsInput> reads;
+    if (fastq_preflight("build", "read", inputs, {out_path}, ReadsOptions{0, opt.fasta}, reads, err)) return 1;
 
     pf_ctx *ctx = nullptr;
     if (pf_create(device, &ctx) != PF_OK) {
         err = std::string("build: no device context (") + (pf_last_error(nullptr) ? pf_last_error(nullptr) : "?") + "); the graph is built on the GPU only";
         return 1;
     }
-    struct CtxGuard { pf_ctx *c; ~CtxGuard() { pf_destroy(c); } } ctx_guard{ctx};
+    CtxGuard ctx_guard{ctx};
     // ---- count: every k-mer of the reads, both strands ----
     CountOptions copt;
     copt.k = opt.k;
@@ -66,10 +56,9 @@ int build_fastq(const std::vector<std::string> &inputs, const std::string &out_p
     copt.both_strands = true;
     copt.chunk_bytes = opt.chunk_bytes;
     copt.initial_slots = opt.initial_slots;
-    copt.fasta = opt.fasta;
     Counted db;
     CountTimes ctm;
-    if (count_stream(ctx, "build", inputs, copt, largest, db, counted, ctm, err)) return 1;
+    if (count_stream(ctx, "build", reads, copt, db, counted, ctm, err)) return 1;
     struct Free { pf_ctx *c; Counted &d; ~Free() { pf_device_free(c, d.kmers); pf_device_free(c, d.counts); } } free_db{ctx, db};
     tm.stream_s = ctm.stream_s;
     tm.finish_s = ctm.finish_s;
@@ -135,15 +124,15 @@ int build_colored_fastq(const std::vector<std::string> &inputs, const std::strin
     if (!pf_color::seeds_ok(n_seeds)) { err = "build-multi: " + pf_color::seeds_text(); return 1; }
     { const std::string why = colored_inputs_refusal(inputs); if (!why.empty()) { err = "build-multi: " + why; return 1; } }
     const std::string gfa_path = out_prefix + ".gfa", col_path = out_prefix + ".bfg_colors";
-    uint64_t largest = 0;
-    if (fastq_preflight("build-multi", "read", inputs, {gfa_path, col_path}, largest, err, 0, opt.fasta)) return 1;
+    std::vector<ReadsInput> reads;
+    if (fastq_preflight("build-multi", "read", inputs, {gfa_path, col_path}, ReadsOptions{0, opt.fasta}, reads, err)) return 1;
 
     pf_ctx *ctx = nullptr;
     if (pf_create(device, &ctx) != PF_OK) {
         err = std::string("build-multi: no device context (") + (pf_last_error(nullptr) ? pf_last_error(nullptr) : "?") + "); the graph is built on the GPU only";
         return 1;
     }
-    struct CtxGuard { pf_ctx *c; ~CtxGuard() { pf_destroy(c); } } ctx_guard{ctx};
+    CtxGuard ctx_guard{ctx};
     auto dev_fail = [&]() { err = std::string("build-multi: ") + pf_last_error(ctx); return 1; };
     // ---- count: every k-mer of all files, both strands ----
     CountOptions copt;
@@ -154,10 +143,9 @@ int build_colored_fastq(const std::vector<std::string> &inputs, const std::strin
     copt.both_strands = true;
     copt.chunk_bytes = opt.chunk_bytes;
     copt.initial_slots = opt.initial_slots;
-    copt.fasta = opt.fasta;
     Counted db;
     CountTimes ctm;
-    if (count_stream(ctx, "build-multi", inputs, copt, largest, db, counted, ctm, err)) return 1;
+    if (count_stream(ctx, "build-multi", reads, copt, db, counted, ctm, err)) return 1;
     struct Free { pf_ctx *c; Counted &d; ~Free() { pf_device_free(c, d.kmers); pf_device_free(c, d.counts); } } free_db{ctx, db};
     tm.build.stream_s = ctm.stream_s;
     tm.build.finish_s = ctm.finish_s;
@@ -178,13 +166,12 @@ int build_colored_fastq(const std::vector<std::string> &inputs, const std::strin
     db.kmers = nullptr;
     for (size_t c = 0; c < inputs.size(); ++c) {
         StreamTimes stm;
-        if (stream_fastq(ctx, "build-multi", {inputs[c]}, opt.chunk_bytes, largest, -1, "",
-                         [&](const char *text, uint64_t n, bool final, char *, uint64_t &used, uint64_t &reads, uint64_t &bad) {
+        if (stream_fastq(ctx, "build-multi", {reads[c]}, opt.chunk_bytes, -1, "",
+                         [&](const Chunk &ch, Taken &t) {
                              pf_color_stats st = {};
-                             const int rc = opt.fasta && chunk_is_fasta(ctx, text, n, stm.text_on_device)
-                                                ? pf_color_fasta(ctx, (uint32_t)c, text, n, final ? 1 : 0, &used, &st, &bad)
-                                                : pf_color_fastq(ctx, (uint32_t)c, text, n, final ? 1 : 0, &used, &st, &bad);
-                             reads = st.reads;
+                             const int rc = ch.fasta ? pf_color_fasta(ctx, (uint32_t)c, ch.text, ch.n, ch.final ? 1 : 0, &t.used, &st, &t.bad)
+                                                     : pf_color_fastq(ctx, (uint32_t)c, ch.text, ch.n, ch.final ? 1 : 0, &t.used, &st, &t.bad);
+                             t.reads = st.reads;
                              return rc;
                          },
                          stm, err))

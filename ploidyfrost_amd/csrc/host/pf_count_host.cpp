@@ -11,6 +11,7 @@
 
 #include "pf_cutoffs.hpp"
 #include "pf_host_graph.hpp"
+#include "pf_host_util.hpp"
 
 namespace pfh {
 
@@ -21,17 +22,6 @@ double since(clk::time_point t) { return std::chrono::duration<double>(clk::now(
 
 constexpr uint64_t WRITE_BLOCK_BYTES = 64ull << 20;   // encoded records a download
 
-bool write_all(int fd, const void *p, uint64_t n) {
-    const char *c = static_cast<const char *>(p);
-    for (uint64_t done = 0; done < n;) {
-        const ssize_t put = write(fd, c + done, (size_t)(n - done));
-        if (put < 0 && errno == EINTR) continue;
-        if (put < 0) return false;
-        done += (uint64_t)put;
-    }
-    return true;
-}
-
 }  // namespace
 
 int count_options_clause(const CountOptions &opt, bool writes) {
@@ -40,20 +30,19 @@ int count_options_clause(const CountOptions &opt, bool writes) {
     return pf_count::cut_clause(opt.ci, opt.cx, opt.cs);
 }
 
-int count_stream(pf_ctx *ctx, const char *who_c, const std::vector<std::string> &inputs, const CountOptions &opt, uint64_t largest, Counted &out,
-                 pf_count_stats &stats, CountTimes &tm, std::string &err) {
+int count_stream(pf_ctx *ctx, const char *who_c, const std::vector<ReadsInput> &inputs, const CountOptions &opt, Counted &out, pf_count_stats &stats,
+                 CountTimes &tm, std::string &err) {
     return count_stream_with(ctx, who_c, opt, [&](std::string &e) {
         StreamTimes stm;
-        return stream_fastq(ctx, who_c, inputs, opt.chunk_bytes, largest, -1, "",
-                            [&](const char *text, uint64_t n, bool final, char *, uint64_t &used, uint64_t &reads, uint64_t &bad) {
+        return stream_fastq(ctx, who_c, inputs, opt.chunk_bytes, -1, "",
+                            [&](const Chunk &c, Taken &t) {
                                 pf_count_stats st = {};
-                                const int rc = opt.fasta && chunk_is_fasta(ctx, text, n, stm.text_on_device)
-                                                   ? pf_count_fasta(ctx, text, n, final ? 1 : 0, &used, &st, &bad)
-                                                   : pf_count_fastq(ctx, text, n, final ? 1 : 0, &used, &st, &bad);
-                                reads = st.reads;
+                                const int rc = c.fasta ? pf_count_fasta(ctx, c.text, c.n, c.final ? 1 : 0, &t.used, &st, &t.bad)
+                                                       : pf_count_fastq(ctx, c.text, c.n, c.final ? 1 : 0, &t.used, &st, &t.bad);
+                                t.reads = st.reads;
                                 return rc;
                             },
-                            stm, e, opt.gz);
+                            stm, e);
     }, out, stats, tm, err);
 }
 
@@ -151,18 +140,18 @@ int count_fastq(const std::vector<std::string> &inputs, const std::string &out_p
     { const int c = count_options_clause(opt, true); if (c) { err = std::string("count: ") + pf_count::cut_text(c); return 1; } }
     std::vector<std::string> outputs = {out_prefix + ".kmc_pre", out_prefix + ".kmc_suf"};
     if (!opt.hist.empty()) outputs.push_back(opt.hist);
-    uint64_t largest = 0;
-    if (fastq_preflight("count", "counted", inputs, outputs, largest, err, opt.gz, opt.fasta)) return 1;
+    std::vector<ReadsInput> reads;
+    if (fastq_preflight("count", "counted", inputs, outputs, ReadsOptions{opt.gz, opt.fasta}, reads, err)) return 1;
 
     pf_ctx *ctx = nullptr;
     if (pf_create(device, &ctx) != PF_OK) {
         err = std::string("count: no device context (") + (pf_last_error(nullptr) ? pf_last_error(nullptr) : "?") + "); k-mers are counted on the GPU only";
         return 1;
     }
-    struct CtxGuard { pf_ctx *c; ~CtxGuard() { pf_destroy(c); } } ctx_guard{ctx};
+    CtxGuard ctx_guard{ctx};
     // ---- stream and finish ----
     Counted db;
-    if (count_stream(ctx, "count", inputs, opt, largest, db, stats, tm, err)) return 1;
+    if (count_stream(ctx, "count", reads, opt, db, stats, tm, err)) return 1;
     struct Free { pf_ctx *c; Counted &d; ~Free() { pf_device_free(c, d.kmers); pf_device_free(c, d.counts); } } free_db{ctx, db};
     const auto t_finish = clk::now();
     if (!opt.hist.empty()) {   // from the finished counters before they leave the device

@@ -1,6 +1,6 @@
 // `ploidyfrost count`: the host side of K-COUNT (pf_count_* and pf_kmc_encode in ploidyfrost_hip.h, the rule in ../pf_count_rule.hpp)
 // -- step `2.kmc_db` of the reference's workflow (`kmc -ci1 -cs10000 -k25 @FILES kmc_sample tmp`): the FASTQ inputs streamed through
-// the count table in HBM over the reader and device threads of `mask` (pf_mask_host.hpp), the kept counters written as a KMC1
+// the count table in HBM over the reader and device threads of the reads stream (pf_reads_stream.hpp), the kept counters written as a KMC1
 // database.  (The host's plain restatement of the rule, pf_count::count_reads_host and pf_count::encode_kmc1_host, lives in the rule
 // header itself.)
 #pragma once
@@ -11,7 +11,7 @@
 #include <vector>
 
 #include "../pf_count_rule.hpp"
-#include "pf_mask_host.hpp"
+#include "pf_reads_stream.hpp"
 #include "ploidyfrost_hip.h"
 
 namespace pfh {
@@ -40,10 +40,10 @@ struct Counted {   // what pf_count_finish gives: device arrays for pf_count_his
 // the refusal of the options (pf_count::CutClause, 0 = none): k, ci < 1, ci > cx, cs < 1, a value above 2^32 - 1; writes: a database
 // is written (k >= 5)
 int count_options_clause(const CountOptions &opt, bool writes);
-// begin, the inputs through pf_count_fastq, finish.  `who` words the refusals ("count", "mask").  0 = ok (the caller frees `out` with
+// begin, the inputs (as the preflight left them) through pf_count_fastq / pf_count_fasta, finish.  `who` words the refusals ("count", "mask").  0 = ok (the caller frees `out` with
 // pf_device_free), else worded in err; no count is left open.
-int count_stream(pf_ctx *ctx, const char *who, const std::vector<std::string> &inputs, const CountOptions &opt, uint64_t largest, Counted &out,
-                 pf_count_stats &stats, CountTimes &tm, std::string &err);
+int count_stream(pf_ctx *ctx, const char *who, const std::vector<ReadsInput> &inputs, const CountOptions &opt, Counted &out, pf_count_stats &stats,
+                 CountTimes &tm, std::string &err);
 // the same around any pass that feeds the open count (`run STEP...`: the raw reads through the trimmed entry points): pf_count_begin,
 // pass(err) (0 = ok, else err is worded and the count is aborted), pf_count_finish
 int count_stream_with(pf_ctx *ctx, const char *who, const CountOptions &opt, const std::function<int(std::string &)> &pass, Counted &out,

@@ -19,50 +19,40 @@ std::string member_refusal(const std::string &who, const std::string &path, uint
 }
 }  // namespace
 
-bool gz_magic(const std::string &path) {
-    const int fd = open(path.c_str(), O_RDONLY);
-    if (fd < 0) return false;
-    unsigned char m[2];
-    const ssize_t got = read(fd, m, 2);
-    close(fd);
-    return got == 2 && m[0] == 0x1f && m[1] == 0x8b;
-}
-
-int gz_kind(const std::string &path, int gz) {
-    if (!gz) return GZ_KIND_TEXT;
-    if (gz == 1) return gz_magic(path) ? GZ_KIND_BGZF : GZ_KIND_TEXT;
-    const int fd = open(path.c_str(), O_RDONLY);
-    if (fd < 0) return GZ_KIND_TEXT;
-    std::vector<unsigned char> head(65536);
-    size_t got = 0;
-    while (got < head.size()) {
-        const ssize_t more = read(fd, head.data() + got, head.size() - got);
-        if (more < 0 && errno == EINTR) continue;
-        if (more <= 0) break;
-        got += (size_t)more;
-    }
-    close(fd);
-    const int kind = pf_gunzip::file_kind(head.data(), got, got < head.size() ? got : ~0ull, nullptr);
-    return kind == pf_gunzip::FILE_PLAIN ? GZ_KIND_TEXT : kind == pf_gunzip::FILE_GZIP ? GZ_KIND_GZIP : GZ_KIND_BGZF;
-}
-
-bool GzReader::open_file(const std::string &who_, const std::string &path_, std::string &err) {
+bool BlockReader::open_file(const std::string &who_, const std::string &path_, GzKind kind_, std::string &err) {
     close_file();
     who = who_;
     path = path_;
+    kind = kind_;
     pos = members = 0;
     ahead.clear();
     fd = open(path.c_str(), O_RDONLY);
     if (fd < 0) { err = who + ": cannot read " + path + " (" + strerror(errno) + ")"; return false; }
     return true;
 }
-void GzReader::close_file() {
+void BlockReader::close_file() {
     if (fd >= 0) close(fd);
     fd = -1;
 }
 
-bool GzReader::next(char *buf, uint64_t cap, uint64_t chunk, GzBlock &b, std::string &err) {
-    b = GzBlock{};
+bool BlockReader::next(char *buf, uint64_t cap, uint64_t chunk, FileBlock &b, std::string &err) {
+    if (kind == GZ_KIND_BGZF) return next_members(buf, cap, chunk, b, err);
+    b = FileBlock{};
+    b.file_off = pos;
+    const uint64_t want = std::min(cap, block_bytes(kind, chunk));
+    while (b.len < want) {
+        const ssize_t got = read(fd, buf + b.len, (size_t)(want - b.len));   // (nothing else moves the descriptor: it stands at pos + len)
+        if (got < 0 && errno == EINTR) continue;
+        if (got < 0) { err = who + ": reading " + path + " (" + strerror(errno) + ")"; return false; }
+        if (got == 0) { b.eof = true; break; }
+        b.len += (uint64_t)got;
+    }
+    pos += b.len;
+    return true;
+}
+
+bool BlockReader::next_members(char *buf, uint64_t cap, uint64_t chunk, FileBlock &b, std::string &err) {
+    b = FileBlock{};
     b.file_off = pos;
     b.first_member = members;
     b.member_off.push_back(0);
@@ -99,21 +89,6 @@ bool GzReader::next(char *buf, uint64_t cap, uint64_t chunk, GzBlock &b, std::st
     return true;
 }
 
-bool GzReader::next_raw(char *buf, uint64_t want, GzBlock &b, std::string &err) {
-    b = GzBlock{};
-    b.plain = true;
-    b.file_off = pos;
-    while (b.len < want) {
-        const ssize_t got = pread(fd, buf + b.len, (size_t)std::min<uint64_t>(want - b.len, GZ_READ_STEP), (off_t)(pos + b.len));
-        if (got < 0 && errno == EINTR) continue;
-        if (got < 0) { err = who + ": reading " + path + " (" + strerror(errno) + ")"; return false; }
-        if (got == 0) { b.eof = true; break; }
-        b.len += (uint64_t)got;
-    }
-    pos += b.len;
-    return true;
-}
-
 struct GzText::Plain {
     pf_gunzip::Stream stream;
     char *d_win = nullptr;     // the member's last 32 KiB of text
@@ -129,7 +104,7 @@ GzText::~GzText() {
     pf_device_free(ctx, d_text[1]);
 }
 
-bool GzText::append(const std::string &who, const std::string &path, const char *comp, const GzBlock &b, std::string &err) {
+bool GzText::append(const std::string &who, const std::string &path, const char *comp, const FileBlock &b, std::string &err) {
     auto dev_err = [&](const char *what) { err = who + ": " + path + ": " + what + ": " + pf_last_error(ctx); return false; };
     auto room = [&](void **p, uint64_t &cap, uint64_t need) {
         if (need <= cap && *p) return true;

@@ -13,7 +13,7 @@
 #include "pf_cutoffs.hpp"
 #include "pf_host_graph.hpp"
 #include "../pf_trim_rule.hpp"
-#include "pf_mask_host.hpp"
+#include "pf_host_util.hpp"
 #include "pf_trim_host.hpp"
 
 namespace pfh {
@@ -22,17 +22,6 @@ namespace {
 
 using clk = std::chrono::steady_clock;
 double since(clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); }
-
-bool write_all(int fd, const void *p, uint64_t n) {
-    const char *c = static_cast<const char *>(p);
-    for (uint64_t done = 0; done < n;) {
-        const ssize_t put = write(fd, c + done, (size_t)(n - done));
-        if (put < 0 && errno == EINTR) continue;
-        if (put < 0) return false;
-        done += (uint64_t)put;
-    }
-    return true;
-}
 
 CountOptions count_options_of(const RunOptions &opt) {
     CountOptions c;
@@ -43,8 +32,6 @@ CountOptions count_options_of(const RunOptions &opt) {
     c.both_strands = true;
     c.chunk_bytes = opt.chunk_bytes;
     c.initial_slots = opt.initial_slots;
-    c.gz = opt.gz;
-    c.fasta = opt.fasta;
     return c;
 }
 
@@ -162,52 +149,49 @@ std::string trim_unit_line(const pf_trim_stats *st, bool paired) {
 }
 
 namespace {
-void add_trim_stats(pf_trim_stats &a, const pf_trim_stats &b) {
-    a.reads += b.reads; a.kept += b.kept; a.dropped += b.dropped; a.bases += b.bases; a.bases_kept += b.bases_kept;
-    a.both += b.both; a.only1 += b.only1; a.only2 += b.only2; a.neither += b.neither;
-}
 void add_masked_stats(pf_maskcount_stats &a, const pf_maskcount_stats &b) {
     a.reads += b.reads; a.bases += b.bases; a.kmers += b.kmers; a.kmers_invalid += b.kmers_invalid; a.kmers_bad += b.kmers_bad; a.kmers_kept += b.kmers_kept;
 }
 }  // namespace
 
-int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<std::string> &inputs, bool paired, const TrimInputs &trim, uint64_t chunk_bytes,
-                   uint64_t largest, bool masked, uint32_t low, uint32_t up, pf_trim_stats *unit_stats, pf_maskcount_stats *masked_stats, std::string &err,
-                   int gz) {
+int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<ReadsInput> &inputs, bool paired, const TrimInputs &trim, uint64_t chunk_bytes,
+                   bool masked, uint32_t low, uint32_t up, pf_trim_stats *unit_stats, pf_maskcount_stats *masked_stats, std::string &err) {
     const pf_trim_plan plan = {trim.steps.data(), (uint32_t)trim.steps.size(), trim.phred};
     if (!paired) {
         StreamTimes stm;
-        return stream_fastq(ctx, who, inputs, chunk_bytes, largest, -1, "",
-                            [&](const char *text, uint64_t n, bool final, char *, uint64_t &used, uint64_t &reads, uint64_t &bad) {
+        return stream_fastq(ctx, who, inputs, chunk_bytes, -1, "",
+                            [&](const Chunk &c, Taken &t) {
                                 pf_trim_stats ts = {};
                                 pf_count_stats cs = {};
                                 pf_maskcount_stats ms = {};
-                                const int rc = masked ? pf_maskcount_fastq_trimmed(ctx, text, n, final ? 1 : 0, &plan, low, up, &used, &ts, &ms, &bad)
-                                                      : pf_count_fastq_trimmed(ctx, text, n, final ? 1 : 0, &plan, &used, &ts, &cs, &bad);
+                                const int rc = masked ? pf_maskcount_fastq_trimmed(ctx, c.text, c.n, c.final ? 1 : 0, &plan, low, up, &t.used, &ts, &ms, &t.bad)
+                                                      : pf_count_fastq_trimmed(ctx, c.text, c.n, c.final ? 1 : 0, &plan, &t.used, &ts, &cs, &t.bad);
                                 if (rc != PF_OK) return rc;
-                                reads = ts.reads;   // the records taken, kept or not: the next chunk's records are numbered behind them
+                                t.reads = ts.reads;   // the records taken, kept or not: the next chunk's records are numbered behind them
                                 if (unit_stats) add_trim_stats(unit_stats[0], ts);
                                 if (masked_stats) add_masked_stats(*masked_stats, ms);
                                 return (int)PF_OK;
                             },
-                            stm, err, gz);
+                            stm, err);
     }
     for (size_t u = 0; u + 1 < inputs.size(); u += 2) {
         PairStreamTimes ptm;
-        if (stream_fastq_pair(ctx, who, inputs[u], inputs[u + 1], chunk_bytes, largest,
-                              [&](const char *t1, uint64_t n1, const char *t2, uint64_t n2, bool final, uint64_t used[2], uint64_t &recs, uint64_t &bad) {
+        if (stream_fastq_pair(ctx, who, inputs[u], inputs[u + 1], chunk_bytes,
+                              [&](const PairChunk &c, PairTaken &t) {
                                   pf_trim_stats ts[2] = {};
                                   pf_count_stats cs = {};
                                   pf_maskcount_stats ms = {};
-                                  const int rc = masked ? pf_maskcount_fastq_pair_trimmed(ctx, t1, n1, t2, n2, final ? 1 : 0, &plan, low, up, used, ts, &ms, &bad)
-                                                        : pf_count_fastq_pair_trimmed(ctx, t1, n1, t2, n2, final ? 1 : 0, &plan, used, ts, &cs, &bad);
+                                  const int rc = masked ? pf_maskcount_fastq_pair_trimmed(ctx, c.text[0], c.n[0], c.text[1], c.n[1], c.final ? 1 : 0, &plan, low, up,
+                                                                                          t.used, ts, &ms, &t.bad)
+                                                        : pf_count_fastq_pair_trimmed(ctx, c.text[0], c.n[0], c.text[1], c.n[1], c.final ? 1 : 0, &plan, t.used, ts, &cs,
+                                                                                      &t.bad);
                                   if (rc != PF_OK) return rc;
-                                  recs = ts[0].reads;
+                                  t.reads = ts[0].reads;
                                   if (unit_stats) { add_trim_stats(unit_stats[u], ts[0]); add_trim_stats(unit_stats[u + 1], ts[1]); }
                                   if (masked_stats) add_masked_stats(*masked_stats, ms);
                                   return (int)PF_OK;
                               },
-                              ptm, err, gz))
+                              ptm, err))
             return 1;
     }
     return 0;
@@ -240,8 +224,8 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
     std::vector<std::string> outputs;
     if (!opt.db_out.empty()) { outputs.push_back(opt.db_out + ".kmc_pre"); outputs.push_back(opt.db_out + ".kmc_suf"); }
     if (!gfa_path.empty()) outputs.push_back(gfa_path);
-    uint64_t largest = 0;
-    if (fastq_preflight("run", "read", inputs, outputs, largest, err, opt.gz, opt.fasta)) return 1;
+    std::vector<ReadsInput> reads;   // what each input is: decided here, once, for both passes
+    if (fastq_preflight("run", "read", inputs, outputs, ReadsOptions{opt.gz, opt.fasta}, reads, err)) return 1;
 
     pf_ctx *ctx = nullptr;
     if (pf_create(device, &ctx) != PF_OK) {
@@ -249,7 +233,7 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
         return 1;
     }
     // (the context goes to the loader of the calling run in the end: destroyed here only on the way out before that)
-    struct CtxGuard { pf_ctx *c; ~CtxGuard() { if (c) pf_destroy(c); } } ctx_guard{ctx};
+    CtxGuard ctx_guard{ctx};
     bool db_written = false, gfa_tmp_written = false;
     auto fail = [&](const std::string &m) {   // nothing is left under any output name after a refusal
         err = m;
@@ -266,9 +250,9 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
         Counted db;
         CountTimes ctm;
         if (trimming ? count_stream_with(ctx, "run", copt, [&](std::string &e) {
-                           return stream_trimmed(ctx, "run", inputs, opt.paired, opt.trim, opt.chunk_bytes, largest, false, 0, 0, stats.trim.data(), nullptr, e, opt.gz);
+                           return stream_trimmed(ctx, "run", reads, opt.paired, opt.trim, opt.chunk_bytes, false, 0, 0, stats.trim.data(), nullptr, e);
                        }, db, stats.counted, ctm, err)
-                     : count_stream(ctx, "run", inputs, copt, largest, db, stats.counted, ctm, err))
+                     : count_stream(ctx, "run", reads, copt, db, stats.counted, ctm, err))
             return 1;
         struct Free { pf_ctx *c; Counted &d; ~Free() { pf_device_free(c, d.kmers); pf_device_free(c, d.counts); } } free_db{ctx, db};
         tm.count_s = ctm.stream_s;
@@ -302,24 +286,18 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
         const auto t_stream = clk::now();
         if (pf_count_begin(ctx, opt.k, 1, opt.initial_slots) != PF_OK) return dev_fail();
         StreamTimes stm;
-        if (trimming ? stream_trimmed(ctx, "run", inputs, opt.paired, opt.trim, opt.chunk_bytes, largest, true, stats.lower, opt.mask_up, nullptr, &stats.masked, err, opt.gz)
-                     : stream_fastq(ctx, "run", inputs, opt.chunk_bytes, largest, -1, "",
-                         [&](const char *text, uint64_t n, bool final, char *, uint64_t &used, uint64_t &reads, uint64_t &bad) {
+        if (trimming ? stream_trimmed(ctx, "run", reads, opt.paired, opt.trim, opt.chunk_bytes, true, stats.lower, opt.mask_up, nullptr, &stats.masked, err)
+                     : stream_fastq(ctx, "run", reads, opt.chunk_bytes, -1, "",
+                         [&](const Chunk &c, Taken &t) {
                              pf_maskcount_stats st = {};
-                             const int rc = opt.fasta && chunk_is_fasta(ctx, text, n, stm.text_on_device)
-                                                ? pf_maskcount_fasta(ctx, text, n, final ? 1 : 0, stats.lower, opt.mask_up, &used, &st, &bad)
-                                                : pf_maskcount_fastq(ctx, text, n, final ? 1 : 0, stats.lower, opt.mask_up, &used, &st, &bad);
+                             const int rc = c.fasta ? pf_maskcount_fasta(ctx, c.text, c.n, c.final ? 1 : 0, stats.lower, opt.mask_up, &t.used, &st, &t.bad)
+                                                    : pf_maskcount_fastq(ctx, c.text, c.n, c.final ? 1 : 0, stats.lower, opt.mask_up, &t.used, &st, &t.bad);
                              if (rc != PF_OK) return rc;
-                             reads = st.reads;
-                             stats.masked.reads += st.reads;
-                             stats.masked.bases += st.bases;
-                             stats.masked.kmers += st.kmers;
-                             stats.masked.kmers_invalid += st.kmers_invalid;
-                             stats.masked.kmers_bad += st.kmers_bad;
-                             stats.masked.kmers_kept += st.kmers_kept;
+                             t.reads = st.reads;
+                             add_masked_stats(stats.masked, st);
                              return (int)PF_OK;
                          },
-                         stm, err, opt.gz)) {
+                         stm, err)) {
             pf_count_abort(ctx);
             return fail(err);
         }

@@ -79,11 +79,11 @@ inline size_t trim_unit_count(size_t n_inputs, bool paired) { return paired ? n_
 std::string trim_inputs_refusal(const std::vector<std::string> &inputs, bool paired, const TrimInputs &trim);
 // One pass over the raw reads into the open count: masked = false through pf_count_fastq[_pair]_trimmed, true through
 // pf_maskcount_fastq[_pair]_trimmed with [low, up].  paired: the inputs alternate file 1, file 2, and every pair goes through the
-// lock-step stream of pf_trim_host.hpp; else they go through stream_fastq one after the other.  unit_stats (may be null; paired: one
-// entry per input file, else one entry) and masked_stats (may be null) are added to.  0 = ok, else worded in err by `who`.
-int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<std::string> &inputs, bool paired, const TrimInputs &trim, uint64_t chunk_bytes,
-                   uint64_t largest, bool masked, uint32_t low, uint32_t up, pf_trim_stats *unit_stats, pf_maskcount_stats *masked_stats, std::string &err,
-                   int gz = 0);
+// lock-step stream of pf_reads_stream.hpp; else they go through stream_fastq one after the other.  The inputs are what the preflight
+// made of them, the same for both passes.  unit_stats (may be null; paired: one entry per input file, else one entry) and masked_stats
+// (may be null) are added to.  0 = ok, else worded in err by `who`.
+int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<ReadsInput> &inputs, bool paired, const TrimInputs &trim, uint64_t chunk_bytes,
+                   bool masked, uint32_t low, uint32_t up, pf_trim_stats *unit_stats, pf_maskcount_stats *masked_stats, std::string &err);
 // the `trim:` line of a unit on stderr, in `trim`'s own format: st = the unit's statistics (paired: of file 1 and of file 2)
 std::string trim_unit_line(const pf_trim_stats *st, bool paired);
 

@@ -14,7 +14,7 @@
 #include "pf_bfg_write.hpp"
 #include "pf_cutoffs.hpp"
 #include "pf_host_graph.hpp"
-#include "pf_mask_host.hpp"
+#include "pf_host_util.hpp"
 
 namespace pfh {
 
@@ -46,8 +46,6 @@ CountOptions count_options_of(const RunOptions &opt) {
     c.both_strands = true;
     c.chunk_bytes = opt.chunk_bytes;
     c.initial_slots = opt.initial_slots;
-    c.gz = opt.gz;
-    c.fasta = opt.fasta;
     return c;
 }
 
@@ -116,8 +114,13 @@ int run_multi_fastq(const std::vector<MultiSample> &samples, const std::string &
         }
     }
     if (!gfa_path.empty()) { outputs.push_back(gfa_path); outputs.push_back(col_path); }
-    uint64_t largest = 0;
-    if (fastq_preflight("run-multi", "read", all_inputs, outputs, largest, err, opt.gz, opt.fasta)) return 1;
+    std::vector<std::vector<ReadsInput>> reads(C);   // what each input is, per sample: decided here, once, for both passes
+    {
+        std::vector<ReadsInput> all;
+        if (fastq_preflight("run-multi", "read", all_inputs, outputs, ReadsOptions{opt.gz, opt.fasta}, all, err)) return 1;
+        auto at = all.begin();
+        for (uint32_t c = 0; c < C; at += (ptrdiff_t)samples[c++].inputs.size()) reads[c].assign(at, at + (ptrdiff_t)samples[c].inputs.size());
+    }
     for (uint32_t c = 0; c < C; ++c)   // one file under two names
         for (uint32_t d = 0; d < c; ++d)
             for (const std::string &a : samples[c].inputs)
@@ -133,7 +136,7 @@ int run_multi_fastq(const std::vector<MultiSample> &samples, const std::string &
         return 1;
     }
     // (the context goes to the CCDBG in the end: destroyed here only on the way out before that)
-    struct CtxGuard { pf_ctx *c; ~CtxGuard() { if (c) pf_destroy(c); } } ctx_guard{ctx};
+    CtxGuard ctx_guard{ctx};
     DeviceArrays held(ctx_guard.c);
     std::vector<std::string> db_tmp;   // prefixes of the databases written so far, under their temporary names
     bool gfa_tmp_written = false;
@@ -160,10 +163,10 @@ int run_multi_fastq(const std::vector<MultiSample> &samples, const std::string &
         CountTimes ctm;
         std::string e;
         if (trimming ? count_stream_with(ctx, "run-multi", copt, [&](std::string &pe) {
-                           return stream_trimmed(ctx, "run-multi", samples[c].inputs, samples[c].paired, opt.trim, opt.chunk_bytes, largest, false, 0, 0,
-                                                 stats.trim[c].data(), nullptr, pe, opt.gz);
+                           return stream_trimmed(ctx, "run-multi", reads[c], samples[c].paired, opt.trim, opt.chunk_bytes, false, 0, 0, stats.trim[c].data(),
+                                                 nullptr, pe);
                        }, db[c], counted, ctm, e)
-                     : count_stream(ctx, "run-multi", samples[c].inputs, copt, largest, db[c], counted, ctm, e))
+                     : count_stream(ctx, "run-multi", reads[c], copt, db[c], counted, ctm, e))
             return fail(e);
         held.p.push_back(db[c].kmers);
         held.p.push_back(db[c].counts);
@@ -203,21 +206,20 @@ int run_multi_fastq(const std::vector<MultiSample> &samples, const std::string &
         StreamTimes stm;
         std::string e;
         pf_maskcount_stats masked = {};
-        if (trimming ? stream_trimmed(ctx, "run-multi", samples[c].inputs, samples[c].paired, opt.trim, opt.chunk_bytes, largest, true, stats.color[c].lower,
-                                      opt.mask_up, nullptr, &masked, e, opt.gz)
-                     : stream_fastq(ctx, "run-multi", samples[c].inputs, opt.chunk_bytes, largest, -1, "",
-                         [&](const char *text, uint64_t n, bool final, char *, uint64_t &used, uint64_t &reads, uint64_t &bad) {
+        if (trimming ? stream_trimmed(ctx, "run-multi", reads[c], samples[c].paired, opt.trim, opt.chunk_bytes, true, stats.color[c].lower, opt.mask_up, nullptr,
+                                      &masked, e)
+                     : stream_fastq(ctx, "run-multi", reads[c], opt.chunk_bytes, -1, "",
+                         [&](const Chunk &ch, Taken &t) {
                              pf_maskcount_stats st = {};
-                             const int rc = opt.fasta && chunk_is_fasta(ctx, text, n, stm.text_on_device)
-                                                ? pf_maskcount_fasta(ctx, text, n, final ? 1 : 0, stats.color[c].lower, opt.mask_up, &used, &st, &bad)
-                                                : pf_maskcount_fastq(ctx, text, n, final ? 1 : 0, stats.color[c].lower, opt.mask_up, &used, &st, &bad);
+                             const int rc = ch.fasta ? pf_maskcount_fasta(ctx, ch.text, ch.n, ch.final ? 1 : 0, stats.color[c].lower, opt.mask_up, &t.used, &st, &t.bad)
+                                                     : pf_maskcount_fastq(ctx, ch.text, ch.n, ch.final ? 1 : 0, stats.color[c].lower, opt.mask_up, &t.used, &st, &t.bad);
                              if (rc != PF_OK) return rc;
-                             reads = st.reads;
+                             t.reads = st.reads;
                              stats.windows_bad += st.kmers_bad;
                              stats.windows_kept += st.kmers_kept;
                              return (int)PF_OK;
                          },
-                         stm, e, opt.gz)) {
+                         stm, e)) {
             pf_count_abort(ctx);
             return fail(e);
         }

@@ -5,7 +5,6 @@
 #pragma once
 #include <stdint.h>
 
-#include <functional>
 #include <string>
 #include <vector>
 
@@ -17,7 +16,7 @@ struct TrimOptions {
     std::vector<pf_trim_step> steps;
     uint32_t phred = 33;
     std::string trimlog;        // "" = none
-    uint64_t chunk_bytes = 0;   // 0 = MASK_DEFAULT_CHUNK
+    uint64_t chunk_bytes = 0;   // 0 = MASK_DEFAULT_CHUNK (pf_reads_stream.hpp)
     int gz = 0;                 // --gz (1), --gz-plain (2: any gzip, K-GUNZIP): inputs with the gzip magic are blocked gzip, inflated on the device (pf_gz_host.hpp)
 };
 struct TrimTimes {
@@ -37,24 +36,9 @@ int trim_options_clause(const TrimOptions &opt, std::string &err);
 int trim_fastq(const std::vector<std::string> &inputs, const std::string &out_path, const TrimOptions &opt, int device, pf_trim_stats &stats,
                TrimTimes *times, std::string &err);
 // Paired: record r of in1 pairs with record r of in2; out_paths = o1 u1 o2 u2 (both kept / file 1 alone / both kept / file 2 alone).
-// Two reader threads, one device stage, a writer per output; each file keeps its own carry.  A file that ends while the other still
+// The lock-step stream of pf_reads_stream.hpp (two reader threads, one device stage, each file its own carry), a writer per output.  A file that ends while the other still
 // holds a whole record is refused by name.  The trimlog has record r of file 1, then record r of file 2.
 int trim_fastq_pair(const std::string &in1, const std::string &in2, const std::string out_paths[4], const TrimOptions &opt, int device,
                     pf_trim_stats stats[2], TrimTimes *times, std::string &err);
-
-// The lock-step stream of the two files of a pair, for `trim` and for `run STEP...` / `run-multi STEP...` alike: two reader threads, a
-// carry per file, one device stage.  step(text 1, n1, text 2, n2, final, used[2], records, bad) is one device call on what is pending of
-// both files: it reports the bytes it used of each, the pairs it took and, with a status other than PF_OK, bad = 2 * record + file of a
-// format refusal.  A refusal is worded by `who` with the input's path and the 1-based record (files that end at different record
-// counts: with the counts); a step that has worded err itself keeps its words.
-using PairChunkStep = std::function<int(const char *text1, uint64_t n1, const char *text2, uint64_t n2, bool final, uint64_t used[2], uint64_t &records,
-                                        uint64_t &bad)>;
-struct PairStreamTimes {
-    double device_s = 0;   // inside the step
-    double read_s = 0;     // read() of the inputs, the slower of the two
-    bool text_on_device[2] = {false, false};   // set before every step: that file's text is device memory (blocked gzip, inflated there)
-};
-int stream_fastq_pair(pf_ctx *ctx, const char *who, const std::string &in1, const std::string &in2, uint64_t chunk_bytes, uint64_t largest,
-                      const PairChunkStep &step, PairStreamTimes &tm, std::string &err, int gz = 0);
 
 }  // namespace pfh

@@ -6,7 +6,7 @@
 // with ISIZE the length mod 2^32.  The container is read on the host (gzip_header, Stream below); the deflate stream is inflated in
 // pieces: inflate_call here runs the algorithm of pf_inflate_gzip (pf_gunzip.hip) as lane 0 of 1 over plain memory -- find, count,
 // chain, decode, window, resolve, with the same core (pf_gunzip_core.hpp) -- so whatever keeps a corrupt stream inside its ranges is
-// checked on the CPU.  Stream is the loop both seams run per gzip file: carry + block -> call -> text, trailer, next header.
+// checked on the CPU.  Stream is the loop both streams (host/pf_reads_stream.hpp) run per gzip file: carry + block -> call -> text, trailer, next header.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -208,7 +208,7 @@ inline void inflate_call(const uint8_t *comp, uint64_t n_bytes, uint64_t start_b
     }
 }
 
-// ---- one gzip file, block by block: what both seams and gunzip_file below run ----
+// ---- one gzip file, block by block: what both streams and gunzip_file below run ----
 // call(bytes, n, start_bit, fresh, res, err) inflates bytes[0, n) from start_bit on and puts the text wherever the caller keeps it; it
 // keeps the member's window itself and empties it when `fresh` (a member's first call).  false: err is worded (a device error).
 struct Stream {

@@ -1,4 +1,4 @@
-// The rule of K-INFLATE (blocked gzip, `--gz`) in one place, for the host layer (host/pf_mask_host.cpp, host/pf_trim_host.cpp), the
+// The rule of K-INFLATE (blocked gzip, `--gz`) in one place, for the host layer (host/pf_reads_stream.cpp, host/pf_gz_host.cpp), the
 // kernel's error texts (pf_inflate.hip) and the stand-alone test (tests/cpp/test_inflate_rule.cpp).
 //
 // Blocked gzip (BGZF, what `bgzip`, bcl2fastq2 and BCL Convert write) is a sequence of gzip members (RFC 1952), each

@@ -1,4 +1,4 @@
-// The rule of `ploidyfrost mask` (K-MASK) in one place, for the kernels (pf_mask.hip), the host restatement (host/pf_mask_host.cpp)
+// The rule of `ploidyfrost mask` (K-MASK) in one place, for the kernels (pf_mask.hip), the host layer (host/pf_mask_host.cpp, host/pf_reads_stream.cpp)
 // and the stand-alone test (tests/cpp/test_mask_rule.cpp): which bytes are bases, which line of a FASTQ record is which, when a
 // window is bad, and which bytes a set of bad windows masks.  It restates what `kmc_tools filter -hm <db> <reads> -ci<L> -cx<U>`
 // is documented to do with the counters of CKMCFile::GetCountersForRead (KMC/kmc_api/kmc_file.cpp:904-1090): one counter per

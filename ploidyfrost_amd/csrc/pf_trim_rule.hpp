@@ -1,4 +1,4 @@
-// The rule of `ploidyfrost trim` (K-TRIM) in one place, for the kernels (pf_trim.hip), the host restatement (host/pf_trim_host.cpp)
+// The rule of `ploidyfrost trim` (K-TRIM) in one place, for the kernels (pf_trim.hip), the host layer (host/pf_trim_host.cpp, host/pf_reads_stream.cpp)
 // and the stand-alone test (tests/cpp/test_trim_rule.cpp): the quality of a base, the four steps LEADING, TRAILING, SLIDINGWINDOW and
 // MINLEN as Trimmomatic words them (step `1.trim` of the reference's workflow: `trimmomatic PE -phred33 ... LEADING:10 TRAILING:10
 // SLIDINGWINDOW:3:20 MINLEN:50`), the parser of those words, and the refusals by name.
