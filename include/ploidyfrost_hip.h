@@ -75,6 +75,7 @@ enum pf_kernel {
     PF_K_INFLATE, /* K-INFLATE: everything one pf_inflate_bgzf launches (headers, scan, inflate with the CRC), timed as one launch; unit: inflated bytes */
     PF_K_GUNZIP, /* K-GUNZIP: everything one pf_inflate_gzip launches (find, count, chain, decode, window, resolve with the CRC), timed as one launch; unit: inflated bytes */
     PF_K_FASTA, /* K-FASTA: everything the index of one pf_fasta_index / pf_count_fasta / pf_maskcount_fasta / pf_color_fasta call launches (newlines, lines, words, scans, compact, table), timed as one launch; the core behind it is timed under its own kernel; unit: bytes of the chunk */
+    PF_K_DEFLATE, /* K-DEFLATE: everything one pf_deflate_bgzf launches (deflate, scan of the members' sizes, pack), timed as one launch; unit: bytes of text */
     PF_K_COUNT_
 };
 int pf_enable_timing(pf_ctx *, int on);
@@ -454,6 +455,17 @@ typedef struct pf_inflate_stats {
  * comp, member_off, out: [host|dev] */
 int pf_inflate_bgzf(pf_ctx *, const uint8_t *comp, uint64_t n_bytes, const uint64_t *member_off, uint64_t n_members,
                     char *out, uint64_t out_cap, uint64_t *out_bytes, pf_inflate_stats *stats, uint64_t *bad_member);
+
+/* K-DEFLATE: text deflated to blocked gzip (BGZF) on the device.  The rule -- the parse, the coding, the block choice and the container,
+ * each a function of the member's text alone -- is csrc/pf_deflate_core.hpp, shared with the host (csrc/pf_deflate_rule.hpp): a call
+ * gives the bytes the host rule gives, member for member.  One block per member; the members go to slots, their sizes are scanned and
+ * a second kernel packs them.  Timed as one launch of PF_K_DEFLATE per call; unit: bytes of text. */
+typedef struct pf_deflate_stats { uint64_t members, bytes_in, bytes_out, blocks_stored, blocks_fixed, blocks_dynamic, literals, matches; } pf_deflate_stats;
+/* text[0, n_bytes) cut into members of member_text bytes (1 .. 65280; the last may be shorter; n_bytes = 0: no member).  out receives
+ * the members one behind the other, *out_bytes their sum; member_off (may be NULL) n_members + 1 offsets into out.
+ * out_cap below n_bytes + 31 * members: PF_ERR_OVERFLOW by name with that bound.  text, out, member_off: [host|dev] */
+int pf_deflate_bgzf(pf_ctx *, const char *text, uint64_t n_bytes, uint32_t member_text, uint8_t *out, uint64_t out_cap,
+                    uint64_t *out_bytes, uint64_t *member_off, pf_deflate_stats *stats);
 
 /* K-GUNZIP: a plain gzip member's deflate stream (what gzip and pigz write) inflated on the device.  One stream has no table of its
  * blocks, so it is cut into pieces at block starts that a search finds, every piece is decoded twice (count, then decode into 16-bit

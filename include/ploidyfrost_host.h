@@ -535,6 +535,9 @@ uint64_t pfh_colors_check_footprints(const struct pfh_colors *, const uint32_t *
  * them on the device; the call takes the switch back.  (pfh_trim_read and pfh_trim_fastq_chunk, which build the same options, take it
  * back as well and ignore it.) */
 void pfh_reads_gz(int on);
+/* `--gz-out`: after pfh_reads_gz_out(1) the next pfh_trim_fastq, pfh_trim_fastq_pair, pfh_mask_fastq or pfh_mask_fastq_counted of this
+ * thread writes every read output as blocked gzip, deflated on the device (K-DEFLATE); the call takes the switch back. */
+void pfh_reads_gz_out(int on);
 int pfh_inflate_parse_member(const uint8_t *bytes, uint64_t n, uint32_t fields[4]);
 int pfh_inflate_member(const uint8_t *payload, uint32_t n_in, uint8_t *out, uint32_t isize, uint32_t *produced, uint32_t blocks[3]);
 int pfh_inflate_bgzf_member(const uint8_t *bytes, uint64_t n, uint8_t *out, uint32_t *out_len, uint32_t blocks[3]);
@@ -542,6 +545,13 @@ uint32_t pfh_inflate_crc32(const uint8_t *bytes, uint64_t n);
 uint32_t pfh_inflate_crc32_sliced(const uint8_t *bytes, uint32_t n, uint32_t n_lanes);
 int pfh_inflate_file_clause(const uint8_t *first, uint64_t n_first, uint64_t file_size, int *clause);
 const char *pfh_inflate_clause_text(int clause);
+
+/* ---- blocked-gzip output (K-DEFLATE): the rule without a device (csrc/pf_deflate_rule.hpp) ----
+ * pfh_deflate_member: text[0, n), n <= 65280 -> one BGZF member at out[0, return value); out_cap >= n + 31.  result = { the block's kind
+ *   (0 stored, 1 fixed, 2 dynamic), literals, matches }.  -1: an argument out of these ranges.
+ * pfh_deflate_bound: the bytes that hold any n_bytes of text cut into members of member_text: n_bytes + 31 a member. */
+int64_t pfh_deflate_member(const uint8_t *text, uint32_t n, uint8_t *out, uint64_t out_cap, uint32_t result[3]);
+uint64_t pfh_deflate_bound(uint64_t n_bytes, uint32_t member_text);
 
 /* ---- FASTA (K-FASTA, `--fasta`): the rule without a device (csrc/pf_fasta_rule.hpp) ----
  * pfh_reads_fasta(1): the next pfh_count_fastq, pfh_build_fastq, pfh_build_colored_fastq, pfh_run_fastq or pfh_run_multi_fastq of this

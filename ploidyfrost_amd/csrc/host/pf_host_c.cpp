@@ -19,6 +19,7 @@
 #include "../pf_mask_rule.hpp"
 #include "../pf_trim_rule.hpp"
 #include "../pf_trimrun_rule.hpp"
+#include "../pf_deflate_rule.hpp"
 #include "../pf_inflate_rule.hpp"
 #include "../pf_gunzip_rule.hpp"
 #include "../pf_fasta_rule.hpp"
@@ -257,6 +258,10 @@ void *pfh_device_ctx(pfh_run *r) { return r->cdbg->device(); }
 static thread_local int g_reads_gz = 0;   // 0, 1 `--gz`, 2 `--gz-plain`
 void pfh_reads_gz(int on) { g_reads_gz = on == 2 ? 2 : on != 0; }
 static int take_reads_gz() { const int gz = g_reads_gz; g_reads_gz = 0; return gz; }
+// ---- blocked-gzip output: the next trim or mask call of this thread writes it (`--gz-out`) ----
+static thread_local bool g_reads_gz_out = false;
+void pfh_reads_gz_out(int on) { g_reads_gz_out = on != 0; }
+static bool take_reads_gz_out() { const bool g = g_reads_gz_out; g_reads_gz_out = false; return g; }
 // ---- FASTA inputs: the next count, build or run call of this thread takes them (`--fasta`) ----
 static thread_local bool g_reads_fasta = false;
 void pfh_reads_fasta(int on) { g_reads_fasta = on != 0; }
@@ -288,7 +293,7 @@ int pfh_mask_fastq(const char *db_prefix, const char *const *inputs, uint32_t n_
         for (uint32_t i = 0; i < n_inputs; ++i) in.push_back(inputs[i] ? inputs[i] : "");
         pf_mask_stats st = {};
         uint32_t lower = low;
-        const int rc = pfh::mask_fastq(db_prefix, in, out_path, low, up, auto_lower != 0, chunk_bytes, device, st, lower, nullptr, g_open_err);
+        const int rc = pfh::mask_fastq(db_prefix, in, out_path, low, up, auto_lower != 0, chunk_bytes, device, st, lower, nullptr, g_open_err, take_reads_gz_out());
         if (stats) *stats = st;
         if (lower_used) *lower_used = lower;
         return rc;
@@ -325,6 +330,7 @@ static pfh::TrimOptions trim_options(const pf_trim_step *steps, uint32_t n_steps
     opt.trimlog = trimlog ? trimlog : "";
     opt.chunk_bytes = chunk_bytes;
     opt.gz = take_reads_gz();
+    opt.gz_out = take_reads_gz_out();
     return opt;
 }
 int pfh_trim_fastq(const char *const *inputs, uint32_t n_inputs, const char *out_path, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred,
@@ -438,7 +444,7 @@ int pfh_mask_fastq_counted(const char *const *inputs, uint32_t n_inputs, const c
         pf_mask_stats st = {};
         uint32_t lower = low;
         const int rc = pfh::mask_fastq_counted(count_options(k, ci, cx, cs, both_strands), db_out ? db_out : "", in, out_path, low, up, auto_lower != 0,
-                                               chunk_bytes, device, st, lower, nullptr, g_open_err);
+                                               chunk_bytes, device, st, lower, nullptr, g_open_err, take_reads_gz_out());
         if (stats) *stats = st;
         if (lower_used) *lower_used = lower;
         return rc;
@@ -1621,6 +1627,17 @@ int pfh_inflate_file_clause(const uint8_t *first, uint64_t n_first, uint64_t fil
     return pf_inflate::file_clause_gz(first, n_first, file_size, clause);
 }
 const char *pfh_inflate_clause_text(int clause) { return pf_inflate::clause_text(clause); }
+
+// ---- blocked-gzip output: the rule without a device ----------------------------------------------------
+int64_t pfh_deflate_member(const uint8_t *text, uint32_t n, uint8_t *out, uint64_t out_cap, uint32_t result[3]) {
+    if (n > pf_deflate::MEMBER_TEXT || out_cap < (uint64_t)n + pf_deflate::MEMBER_EXTRA || !out || (n && !text)) return -1;
+    std::unique_ptr<pf_deflate::HostWork> w(new pf_deflate::HostWork);
+    pf_deflate::Result r;
+    const uint32_t size = pf_deflate::deflate_member(text, n, out, *w, &r);
+    if (result) { result[0] = r.kind; result[1] = r.literals; result[2] = r.matches; }
+    return (int64_t)size;
+}
+uint64_t pfh_deflate_bound(uint64_t n_bytes, uint32_t member_text) { return member_text ? pf_deflate::bound(n_bytes, member_text) : 0; }
 
 // ---- plain gzip: the rule without a device ------------------------------------------------------------
 static void gunzip_stats_out(const pf_gunzip::Stats &st, uint64_t stats[9]) {

@@ -94,11 +94,11 @@ void PrintUsage() {
          << "Usage: PloidyFrost cutoffU -d <KMCDatabase> (quantile[<1 ,default:0.998])" << endl
          << "Usage: PloidyFrost histogram -d <KMCDatabase> [-o <file>]   (the k-mer histogram file of the database, count<TAB>number per row)" << endl << endl
          << "Usage: PloidyFrost count -k 25 -ci 1 -cs 10000 [-cx N] [-b] -i <reads.fq> [-i <more.fq> ...] -o <KMCDatabase> [--hist <file>] [--chunk-bytes N] [--initial-slots N] [--gz] [--gz-plain] [--fasta] [-v]" << endl
-         << "Usage: PloidyFrost mask -d <KMCDatabase> -i <reads.fq> [-i <more.fq> ...] -o <out.fq> (-l L | --auto-cutoffs) [-u U] [--chunk-bytes N] [-v]" << endl
-         << "Usage: PloidyFrost mask -k 25 [-ci N -cs N -cx N -b] -i <reads.fq> ... -o <out.fq> (-l L | --auto-cutoffs) [-u U] [--db-out <KMCDatabase>] [--chunk-bytes N]" << endl
+         << "Usage: PloidyFrost mask -d <KMCDatabase> -i <reads.fq> [-i <more.fq> ...] -o <out.fq> (-l L | --auto-cutoffs) [-u U] [--chunk-bytes N] [--gz-out] [-v]" << endl
+         << "Usage: PloidyFrost mask -k 25 [-ci N -cs N -cx N -b] -i <reads.fq> ... -o <out.fq> (-l L | --auto-cutoffs) [-u U] [--db-out <KMCDatabase>] [--chunk-bytes N] [--gz-out]" << endl
          << "                  (`kmc_tools filter -hm <db> <reads.fq> -ci<L> [-cx<U>] <out.fq>` on the device: every base of every k-mer whose count" << endl
          << "                  lies outside [L, U] becomes N; --auto-cutoffs: L = what `cutoffL -d` prints, printed on stdout)" << endl << endl
-         << "Usage: PloidyFrost trim -i <reads.fq> [-i <more.fq> ...] -o <trimmed.fq> STEP... [--phred 33|64] [--trimlog <file>] [--chunk-bytes N] [--gz] [--gz-plain] [-v]" << endl
+         << "Usage: PloidyFrost trim -i <reads.fq> [-i <more.fq> ...] -o <trimmed.fq> STEP... [--phred 33|64] [--trimlog <file>] [--chunk-bytes N] [--gz] [--gz-plain] [--gz-out] [-v]" << endl
          << "Usage: PloidyFrost trim -1 <r1.fq> -2 <r2.fq> -o1 <p1.fq> -u1 <u1.fq> -o2 <p2.fq> -u2 <u2.fq> STEP... [the same options]" << endl
          << "                  (`trimmomatic SE|PE` on the device; STEP: LEADING:t TRAILING:t SLIDINGWINDOW:w:t MINLEN:l, applied in the order given)" << endl << endl
          << "Usage: PloidyFrost build -k 25 [-i] [-d] -r <reads.fq> [-r <more.fq> ...] -o <sample> [-g G] [-t N] [--chunk-bytes N] [--initial-slots N] [-v]" << endl
@@ -739,11 +739,12 @@ int build_multi_main(int argc, char **argv) {
 
 // `mask`: step 2 of the reference's workflow (`kmc_tools filter -hm <db> <reads.fq> -ci<L> <out.fq>`) against the database on the device
 int mask_main(int argc, char **argv) {
+    // (the short form: `--gz-out`, blocked-gzip output, stands in the overall usage)
     const char *usage = "Usage:PloidyFrost mask -d kmc_database -i reads.fq [-i more.fq ...] -o out.fq (-l L | --auto-cutoffs) [-u U] [--chunk-bytes N] [-v]";
     string db, out, db_out;
     CountArgs c;   // -k: the inputs are counted instead of a database read
     vector<string> inputs;
-    bool l_seen = false, auto_cutoffs = false, verbose = false;
+    bool l_seen = false, auto_cutoffs = false, verbose = false, gz_out = false;
     long long low = 0, up = 0xFFFFFFFFll, chunk = 0;
     auto refuse = [&](const string &why) { cerr << "Error: mask: " << why << endl << usage << endl; return 1; };
     auto number = [&](const char *opt, const char *text, long long &v) {
@@ -764,6 +765,7 @@ int mask_main(int argc, char **argv) {
         }
         const bool has_value = i + 1 < argc;
         if (a == "--auto-cutoffs") auto_cutoffs = true;
+        else if (a == "--gz-out") gz_out = true;
         else if (a == "--fasta") return refuse("--fasta is not built into mask: the masked output has the input's layout (count, build, build-multi, run and run-multi take FASTA)");
         else if (a == "-v") verbose = true;
         else if (!has_value) return refuse(a == "-d" || a == "-i" || a == "-o" || a == "-l" || a == "-u" || a == "--chunk-bytes" || a == "--db-out" ? a + " needs a value" : "unknown option " + a);
@@ -791,8 +793,8 @@ int mask_main(int argc, char **argv) {
     uint32_t lower = (uint32_t)low;
     pfh::MaskTimes tm;
     string err;
-    const int rc = c.k_seen ? pfh::mask_fastq_counted(c.opt, db_out, inputs, out, (uint32_t)low, (uint32_t)up, auto_cutoffs, (uint64_t)chunk, 0, st, lower, &tm, err)
-                            : pfh::mask_fastq(db, inputs, out, (uint32_t)low, (uint32_t)up, auto_cutoffs, (uint64_t)chunk, 0, st, lower, &tm, err);
+    const int rc = c.k_seen ? pfh::mask_fastq_counted(c.opt, db_out, inputs, out, (uint32_t)low, (uint32_t)up, auto_cutoffs, (uint64_t)chunk, 0, st, lower, &tm, err, gz_out)
+                            : pfh::mask_fastq(db, inputs, out, (uint32_t)low, (uint32_t)up, auto_cutoffs, (uint64_t)chunk, 0, st, lower, &tm, err, gz_out);
     if (rc) {
         cerr << "Error: " << err << endl;
         return 1;
@@ -808,7 +810,7 @@ int mask_main(int argc, char **argv) {
 // `trim`: step 1 of the reference's workflow (`trimmomatic PE -phred33 r1 r2 trim1 u1 trim2 u2 LEADING:10 TRAILING:10 SLIDINGWINDOW:3:20
 // MINLEN:50`) on the device; the steps are Trimmomatic's words as positional arguments
 int trim_main(int argc, char **argv) {
-    const char *usage = "Usage:PloidyFrost trim -i reads.fq [-i more.fq ...] -o trimmed.fq STEP... [--phred 33|64] [--trimlog file] [--chunk-bytes N] [--gz] [--gz-plain] [-v]\n"
+    const char *usage = "Usage:PloidyFrost trim -i reads.fq [-i more.fq ...] -o trimmed.fq STEP... [--phred 33|64] [--trimlog file] [--chunk-bytes N] [--gz] [--gz-plain] [--gz-out] [-v]\n"
                         "      PloidyFrost trim -1 r1.fq -2 r2.fq -o1 p1.fq -u1 u1.fq -o2 p2.fq -u2 u2.fq STEP... [the same options]\n"
                         "      STEP: LEADING:t TRAILING:t SLIDINGWINDOW:w:t MINLEN:l";
     vector<string> inputs, words;
@@ -823,6 +825,7 @@ int trim_main(int argc, char **argv) {
         if (a == "-v") { verbose = true; continue; }
         if (a == "--gz") { opt.gz = std::max(opt.gz, 1); continue; }
         if (a == "--gz-plain") { opt.gz = 2; continue; }
+        if (a == "--gz-out") { opt.gz_out = true; continue; }
         if (a == "--fasta") return refuse("--fasta does not go with trim: FASTA has no qualities to trim");
         const bool known = a == "-i" || a == "-o" || a == "--phred" || a == "--trimlog" || a == "--chunk-bytes" ||
                            std::find_if(pair_opts, pair_opts + 6, [&](const char *o) { return a == o; }) != pair_opts + 6;

@@ -4,12 +4,14 @@
 
 #include <algorithm>
 #include <chrono>
+#include <memory>
 
 #include "../pf_mask_rule.hpp"
 #include "pf_count_host.hpp"
 #include "pf_cutoffs.hpp"
 #include "pf_host_graph.hpp"
 #include "pf_host_util.hpp"
+#include "pf_gz_out_host.hpp"
 #include "pf_reads_stream.hpp"
 
 namespace pfh {
@@ -21,16 +23,24 @@ double since(clk::time_point t) { return std::chrono::duration<double>(clk::now(
 
 // the table is resident: the inputs through K-MASK into out_path
 int mask_stream(pf_ctx *ctx, const std::vector<ReadsInput> &inputs, const std::string &out_path, uint32_t low, uint32_t up, uint64_t chunk_bytes,
-                pf_mask_stats &stats, MaskTimes &tm, std::string &err) {
+                bool gz_out, pf_mask_stats &stats, MaskTimes &tm, std::string &err) {
     const auto t_stream = clk::now();
     OutFiles outs("mask");
     if (outs.open_all({out_path}, err)) return 1;
     StreamTimes st_tm;
-    stream_fastq(ctx, "mask", inputs, chunk_bytes, outs.f[0].fd, outs.f[0].tmp,
+    std::unique_ptr<GzOutFile> gzo;   // --gz-out: the output stays on the device until it is deflated, and the stream writes nothing itself
+    if (gz_out) {
+        gzo.reset(new GzOutFile(ctx));
+        gzo->start(outs.f[0].fd, "mask", outs.f[0].tmp);
+    }
+    stream_fastq(ctx, "mask", inputs, chunk_bytes, gzo ? -1 : outs.f[0].fd, outs.f[0].tmp,
                  [&](const Chunk &c, Taken &t) {
                      pf_mask_stats st = {};
-                     const int rc = pf_mask_fastq(ctx, c.text, c.n, c.final ? 1 : 0, low, up, c.out, &t.used, &st, &t.bad);
+                     char *out = c.out;
+                     if (gzo && !(out = gzo->place(c.n + 1, err))) return (int)PF_ERR_HIP;   // (err is worded)
+                     const int rc = pf_mask_fastq(ctx, c.text, c.n, c.final ? 1 : 0, low, up, out, &t.used, &st, &t.bad);
                      if (rc != PF_OK) return rc;
+                     if (gzo && !gzo->take(t.used, false, err)) return (int)PF_ERR_HIP;
                      t.out_len = t.used;
                      t.reads = st.reads;
                      stats.reads += st.reads;
@@ -42,6 +52,12 @@ int mask_stream(pf_ctx *ctx, const std::vector<ReadsInput> &inputs, const std::s
                      return (int)PF_OK;
                  },
                  st_tm, err);
+    if (gzo) {
+        if (err.empty()) gzo->finish(err);
+        gzo->stop();
+        if (err.empty()) err = gzo->wr.err;
+        st_tm.write_s = gzo->wr.write_s;
+    }
     if (!err.empty() || outs.commit(err)) return 1;
     tm.stream_s = since(t_stream);
     tm.device_s = st_tm.device_s;
@@ -68,7 +84,7 @@ int mask_create(int device, pf_ctx **ctx, std::string &err) {
 }  // namespace
 
 int mask_fastq(const std::string &db_prefix, const std::vector<std::string> &inputs, const std::string &out_path, uint32_t low, uint32_t up,
-               bool auto_lower, uint64_t chunk_bytes, int device, pf_mask_stats &stats, uint32_t &lower_used, MaskTimes *times, std::string &err) {
+               bool auto_lower, uint64_t chunk_bytes, int device, pf_mask_stats &stats, uint32_t &lower_used, MaskTimes *times, std::string &err, bool gz_out) {
     stats = pf_mask_stats{};
     lower_used = low;
     MaskTimes tm;
@@ -100,14 +116,14 @@ int mask_fastq(const std::string &db_prefix, const std::vector<std::string> &inp
         if (auto_lower && mask_auto_lower(rows, low, up, lower_used, err)) return 1;
     }
     tm.load_s = since(t_load);
-    if (mask_stream(ctx, reads, out_path, low, up, chunk_bytes, stats, tm, err)) return 1;
+    if (mask_stream(ctx, reads, out_path, low, up, chunk_bytes, gz_out, stats, tm, err)) return 1;
     if (times) *times = tm;
     return 0;
 }
 
 int mask_fastq_counted(const CountOptions &count, const std::string &db_out, const std::vector<std::string> &inputs, const std::string &out_path,
                        uint32_t low, uint32_t up, bool auto_lower, uint64_t chunk_bytes, int device, pf_mask_stats &stats, uint32_t &lower_used,
-                       MaskTimes *times, std::string &err) {
+                       MaskTimes *times, std::string &err, bool gz_out) {
     stats = pf_mask_stats{};
     lower_used = low;
     MaskTimes tm;
@@ -141,7 +157,7 @@ int mask_fastq_counted(const CountOptions &count, const std::string &db_out, con
         if (!db_out.empty() && write_counted(ctx, "mask", db_out, db, opt, err)) return 1;
     }
     tm.load_s = since(t_load);
-    if (mask_stream(ctx, reads, out_path, low, up, chunk_bytes, stats, tm, err)) {
+    if (mask_stream(ctx, reads, out_path, low, up, chunk_bytes, gz_out, stats, tm, err)) {
         if (!db_out.empty()) { unlink((db_out + ".kmc_pre").c_str()); unlink((db_out + ".kmc_suf").c_str()); }   // nothing is left after a refusal
         return 1;
     }

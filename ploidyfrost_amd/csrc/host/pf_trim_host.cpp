@@ -8,6 +8,7 @@
 
 #include "../pf_trim_rule.hpp"
 #include "pf_host_util.hpp"
+#include "pf_gz_out_host.hpp"
 #include "pf_reads_stream.hpp"
 
 static_assert(sizeof(pf_trim_step) == sizeof(pf_trim::Step) && sizeof(pf_trim_stats) == sizeof(pf_trim::Stats), "the rule header restates the ABI's records");
@@ -45,42 +46,6 @@ int trim_create(int device, pf_ctx **ctx, std::string &err) {
     return 1;
 }
 
-// ---- the pair's writers ----
-struct WritePiece {
-    std::shared_ptr<char> p;
-    uint64_t len = 0;
-};
-struct PairWriter {   // writes the pieces of one output in order, at most two behind the device stage
-    Chan<int> tokens;
-    Chan<WritePiece> pieces;
-    std::string err;
-    double write_s = 0;
-    std::thread th;
-    void start(int fd, const std::string &name) {
-        tokens.push(0);
-        tokens.push(0);
-        th = std::thread([this, fd, name] {
-            WritePiece w;
-            while (pieces.pop(w)) {
-                const auto t0 = clk::now();
-                if (err.empty()) write_all(fd, w.p.get(), w.len, "trim", name, err);
-                write_s += since(t0);
-                w.p.reset();
-                tokens.push(0);
-            }
-        });
-    }
-    void put(WritePiece w) {
-        int token;
-        if (tokens.pop(token)) pieces.push(std::move(w));
-    }
-    void stop() {
-        pieces.close();
-        if (th.joinable()) th.join();
-        tokens.close();
-    }
-};
-
 }  // namespace
 
 int trim_options_clause(const TrimOptions &opt, std::string &err) {
@@ -113,13 +78,21 @@ int trim_fastq(const std::vector<std::string> &inputs, const std::string &out_pa
     std::string log, log_err;
     std::vector<char> fetched;
     StreamTimes st_tm;
-    stream_fastq(ctx, "trim", reads, opt.chunk_bytes, outs.f[0].fd, outs.f[0].tmp,
+    std::unique_ptr<GzOutFile> gzo;   // --gz-out: the output stays on the device until it is deflated, and the stream writes nothing itself
+    if (opt.gz_out) {
+        gzo.reset(new GzOutFile(ctx));
+        gzo->start(outs.f[0].fd, "trim", outs.f[0].tmp);
+    }
+    stream_fastq(ctx, "trim", reads, opt.chunk_bytes, gzo ? -1 : outs.f[0].fd, outs.f[0].tmp,
                  [&](const Chunk &c, Taken &t) {
                      if (logs) { rb.resize(c.n / 4 + 1); rl.resize(c.n / 4 + 1); }
                      pf_trim_stats st = {};
-                     const int rc = pf_trim_fastq(ctx, c.text, c.n, c.final ? 1 : 0, opt.steps.data(), (uint32_t)opt.steps.size(), opt.phred, c.out, &t.out_len, &t.used,
+                     char *out = c.out;
+                     if (gzo && !(out = gzo->place(c.n + 1, err))) return (int)PF_ERR_HIP;   // (err is worded)
+                     const int rc = pf_trim_fastq(ctx, c.text, c.n, c.final ? 1 : 0, opt.steps.data(), (uint32_t)opt.steps.size(), opt.phred, out, &t.out_len, &t.used,
                                                   logs ? rb.data() : nullptr, logs ? rl.data() : nullptr, &t.reads, &st, &t.bad);
                      if (rc != PF_OK) return rc;
+                     if (gzo && !gzo->take(t.out_len, false, err)) return (int)PF_ERR_HIP;
                      add_trim_stats(stats, st);
                      if (logs && log_err.empty()) {   // on the host, from the (begin, len) arrays
                          const char *text = c.text;
@@ -136,6 +109,12 @@ int trim_fastq(const std::vector<std::string> &inputs, const std::string &out_pa
                      return (int)PF_OK;
                  },
                  st_tm, err);
+    if (gzo) {
+        if (err.empty()) gzo->finish(err);
+        gzo->stop();
+        if (err.empty()) err = gzo->wr.err;
+        st_tm.write_s = gzo->wr.write_s;
+    }
     if (err.empty()) err = log_err;
     if (!err.empty() || outs.commit(err)) return 1;
     if (times) {
@@ -165,8 +144,16 @@ int trim_fastq_pair(const std::string &in1, const std::string &in2, const std::s
     OutFiles outs("trim");
     if (outs.open_all(paths, err)) return 1;
 
-    PairWriter wr[4];
-    for (int d = 0; d < 4; ++d) wr[d].start(outs.f[d].fd, outs.f[d].tmp);
+    PieceWriter wr[4];
+    std::unique_ptr<GzOutFile> gzo[4];   // --gz-out: the four outputs stay on the device until they are deflated
+    for (int d = 0; d < 4; ++d) {
+        if (opt.gz_out) {
+            gzo[d].reset(new GzOutFile(ctx));
+            gzo[d]->start(outs.f[d].fd, "trim", outs.f[d].tmp);
+        } else {
+            wr[d].start(outs.f[d].fd, "trim", outs.f[d].tmp);
+        }
+    }
     std::vector<uint32_t> rb[2], rl[2];
     std::vector<uint64_t> lb[2], le[2];
     std::string log;
@@ -178,6 +165,10 @@ int trim_fastq_pair(const std::string &in1, const std::string &in2, const std::s
                           std::shared_ptr<char> out[4];
                           char *out_p[4];
                           for (int d = 0; d < 4; ++d) {
+                              if (opt.gz_out) {
+                                  if (!(out_p[d] = gzo[d]->place(c.n[d / 2] + 1, err))) return (int)PF_ERR_HIP;   // (err is worded)
+                                  continue;
+                              }
                               out[d] = std::shared_ptr<char>(new char[c.n[d / 2] + 1], std::default_delete<char[]>());
                               out_p[d] = out[d].get();
                           }
@@ -209,19 +200,26 @@ int trim_fastq_pair(const std::string &in1, const std::string &in2, const std::s
                                   for (int f = 0; f < 2; ++f) trimlog_line(log, text[f], &lb[f][4 * r], &le[f][4 * r], rb[f][r], rl[f][r]);
                               if (!write_all(outs.f[4].fd, log.data(), log.size(), "trim", outs.f[4].tmp, err)) return (int)PF_ERR_ARG;   // (err is worded)
                           }
-                          for (int d = 0; d < 4; ++d)
-                              if (out_bytes[d]) wr[d].put(WritePiece{out[d], out_bytes[d]});
+                          for (int d = 0; d < 4; ++d) {
+                              if (opt.gz_out) { if (!gzo[d]->take(out_bytes[d], false, err)) return (int)PF_ERR_HIP; }
+                              else if (out_bytes[d]) wr[d].put(WritePiece{out[d], out_bytes[d]});
+                          }
                           return (int)PF_OK;
                       },
                       ptm, err);
-    for (int d = 0; d < 4; ++d) wr[d].stop();
-    for (int d = 0; d < 4 && err.empty(); ++d) err = wr[d].err;
+    for (int d = 0; d < 4; ++d) {
+        if (!opt.gz_out) { wr[d].stop(); continue; }
+        if (err.empty()) gzo[d]->finish(err);
+        gzo[d]->stop();
+    }
+    for (int d = 0; d < 4 && err.empty(); ++d) err = opt.gz_out ? gzo[d]->wr.err : wr[d].err;
     if (!err.empty() || outs.commit(err)) return 1;
     if (times) {
         times->stream_s = since(t_stream);
         times->device_s = ptm.device_s;
         times->read_s = ptm.read_s;
-        times->write_s = wr[0].write_s + wr[1].write_s + wr[2].write_s + wr[3].write_s;
+        times->write_s = 0;
+        for (int d = 0; d < 4; ++d) times->write_s += opt.gz_out ? gzo[d]->wr.write_s : wr[d].write_s;
     }
     return 0;
 }

@@ -17,6 +17,7 @@ struct TrimOptions {
     uint32_t phred = 33;
     std::string trimlog;        // "" = none
     uint64_t chunk_bytes = 0;   // 0 = MASK_DEFAULT_CHUNK (pf_reads_stream.hpp)
+    bool gz_out = false;        // --gz-out: every read output is blocked gzip, deflated on the device behind the step (GzOutFile, pf_gz_out_host.hpp)
     int gz = 0;                 // --gz (1), --gz-plain (2: any gzip, K-GUNZIP): inputs with the gzip magic are blocked gzip, inflated on the device (pf_gz_host.hpp)
 };
 struct TrimTimes {

@@ -43,6 +43,7 @@ K_TRIMCOUNT = K_COLORSET + 1   # PF_K_TRIMCOUNT ("k_trimcount"): everything one 
 K_INFLATE = K_TRIMCOUNT + 1    # PF_K_INFLATE ("k_inflate"): everything one pf_inflate_bgzf launches; unit: inflated bytes
 K_GUNZIP = K_INFLATE + 1       # PF_K_GUNZIP ("k_gunzip"): everything one pf_inflate_gzip launches; unit: inflated bytes
 K_FASTA = K_GUNZIP + 1         # PF_K_FASTA ("k_fasta"): everything the index of one pf_fasta_index / pf_*_fasta call launches; unit: bytes of the chunk
+K_DEFLATE = K_FASTA + 1        # PF_K_DEFLATE ("k_deflate"): everything one pf_deflate_bgzf launches; unit: bytes of text
 FASTA_TILE = 4096              # PF_FASTA_TILE: bytes of the chunk one block of K-FASTA's compaction kernel takes at a time
 GUNZIP_RESULT = np.dtype([("out_bytes", "<u8"), ("end_bit", "<u8"), ("final", "<u4"), ("n_window", "<u4"), ("crc_raw", "<u4"), ("clause", "<u4"),
                           ("clause_bit", "<u8")])   # pf_gunzip_result
@@ -50,6 +51,7 @@ GUNZIP_COUNTERS = ("pieces_found", "pieces_live", "pieces_dead", "markers", "blo
 GUNZIP_STAGES = ("find", "count", "decode", "window", "resolve")
 GUNZIP_STATS = np.dtype([(f, "<u8") for f in GUNZIP_COUNTERS] + [("stage_ms", "<f8", (5,))])   # pf_gunzip_stats
 INFLATE_STATS = np.dtype([(f, "<u8") for f in ("members", "bytes_in", "bytes_out", "blocks_stored", "blocks_fixed", "blocks_dynamic")])   # pf_inflate_stats
+DEFLATE_STATS = np.dtype([(f, "<u8") for f in ("members", "bytes_in", "bytes_out", "blocks_stored", "blocks_fixed", "blocks_dynamic", "literals", "matches")])   # pf_deflate_stats
 UNION_TILE = 1024            # pf_runmulti::UNION_TILE: merged positions a block of K-UNION takes
 UNION_ITEMS = 4              # pf_runmulti::UNION_ITEMS: ... and a lane
 COLOR_KMERS_STATS = np.dtype([(f, "<u8") for f in ("kmers", "kmers_colored", "kmers_unplaced")])   # pf_color_kmers_stats
@@ -261,6 +263,7 @@ def load_library() -> C.CDLL:
         "pf_copy": (i, [vp, vp, vp, C.c_size_t]),
         "pf_inflate_bgzf": (i, [vp, vp, u64, vp, u64, vp, u64, C.POINTER(u64), vp, C.POINTER(u64)]),
         "pf_inflate_gzip": (i, [vp, vp, u64, u64, vp, u32, u32, vp, u64, vp, vp, vp]),
+        "pf_deflate_bgzf": (i, [vp, vp, u64, u32, vp, u64, C.POINTER(u64), vp, vp]),
         "pf_fasta_index": (i, [vp, vp, u64, i, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
         "pf_fasta_index_fetch": (i, [vp, vp, u64, i, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp, u64, vp, vp, u64]),
         "pf_count_fasta": (i, [vp, vp, u64, i, C.POINTER(u64), vp, C.POINTER(u64)]),
@@ -302,7 +305,7 @@ DECLARED_SYMBOLS = ["pf_create", "pf_warmup", "pf_destroy", "pf_last_error", "pf
                     "pf_kmer_union", "pf_color_kmers", "pf_release_counts",
                     "pf_trim_table_fastq", "pf_trim_table_fastq_pair", "pf_count_fastq_trimmed", "pf_count_fastq_pair_trimmed",
                     "pf_maskcount_fastq_trimmed", "pf_maskcount_fastq_pair_trimmed", "pf_inflate_bgzf", "pf_inflate_gzip", "pf_device_alloc", "pf_copy",
-                    "pf_fasta_index", "pf_fasta_index_fetch", "pf_count_fasta", "pf_maskcount_fasta", "pf_color_fasta"]
+                    "pf_fasta_index", "pf_fasta_index_fetch", "pf_count_fasta", "pf_maskcount_fasta", "pf_color_fasta", "pf_deflate_bgzf"]
 
 
 class TrimPlan(C.Structure):   # pf_trim_plan
@@ -660,6 +663,28 @@ class Device:
             e.needed = out_n.value
             raise e
         return out[: out_n.value], {f: int(stats[0][f]) for f in INFLATE_STATS.names}
+
+    def deflate_bgzf(self, text, member_text: int = 65280, out=None, out_cap=None, member_off=None):
+        """K-DEFLATE (pf_deflate_bgzf): text cut into BGZF members of member_text bytes; returns (bytes, member_off, stats): the members one
+        behind the other (a uint8 array, or the part of `out` they fill), their n_members + 1 offsets and the counters of
+        pf_deflate_stats.  text: bytes, a uint8 numpy array or a device tensor; out: an array or device tensor to fill (out_cap bytes of
+        it, default all) instead of a new numpy array of the bound's len(text) + 31 a member; member_off: a device tensor for the offsets
+        instead of a new numpy array.  A buffer below the bound raises DeviceError with status PF_ERR_OVERFLOW."""
+        if isinstance(text, (bytes, bytearray)):
+            text = np.frombuffer(bytes(text), dtype=np.uint8)
+        n = int(text.shape[0])
+        n_members = (n + member_text - 1) // member_text if member_text > 0 else 0
+        if out is None:
+            out = np.zeros(n + 31 * n_members, dtype=np.uint8)
+        if member_off is None:
+            member_off = np.zeros(n_members + 1, dtype=np.uint64)
+        stats = np.zeros(1, dtype=DEFLATE_STATS)
+        out_n = C.c_uint64()
+        st = self.L.pf_deflate_bgzf(self.h, _ptr(text) if n else None, n, member_text, _ptr(out) if int(out.shape[0]) else None,
+                                    int(out.shape[0]) if out_cap is None else out_cap, C.byref(out_n), _ptr(member_off), stats.ctypes.data)
+        if st != PF_OK:
+            raise DeviceError(st, self.L.pf_last_error(self.h).decode())
+        return out[: out_n.value], member_off, {f: int(stats[0][f]) for f in DEFLATE_STATS.names}
 
     def inflate_gzip(self, comp, start_bit: int = 0, window=None, piece_bytes: int = 0, out=None, out_cap=None, new_window=None):
         """K-GUNZIP (pf_inflate_gzip): the deflate stream comp[0:] of a plain gzip member from start_bit (a block start) on, up to a final

@@ -49,7 +49,8 @@ DECLARED_SYMBOLS = ["pfh_open", "pfh_close", "pfh_last_error", "pfh_set_output_d
                     "pfh_run_fastq_trimmed", "pfh_run_multi_fastq_trimmed", "pfh_trim_table_chunk", "pfh_trim_table_chunk_pair", "pfh_trim_table_clause_text",
                     "pfh_inflate_parse_member", "pfh_inflate_member", "pfh_inflate_bgzf_member", "pfh_inflate_crc32", "pfh_inflate_crc32_sliced",
                     "pfh_inflate_file_clause", "pfh_inflate_clause_text", "pfh_reads_gz", "pfh_reads_fasta", "pfh_fasta_index", "pfh_fasta_clause_text",
-                    "pfh_gunzip_header", "pfh_gunzip_file_kind", "pfh_gunzip_candidate", "pfh_gunzip_call", "pfh_gunzip_file", "pfh_gunzip_clause_text"]
+                    "pfh_gunzip_header", "pfh_gunzip_file_kind", "pfh_gunzip_candidate", "pfh_gunzip_call", "pfh_gunzip_file", "pfh_gunzip_clause_text",
+                    "pfh_deflate_member", "pfh_deflate_bound", "pfh_reads_gz_out"]
 
 
 class RunOptions(C.Structure):   # pfh_run_options (include/ploidyfrost_host.h)
@@ -266,6 +267,8 @@ def load_library() -> C.CDLL:
     L.pfh_trim_table_clause_text.argtypes = [C.c_int]
     L.pfh_reads_gz.restype = None
     L.pfh_reads_gz.argtypes = [C.c_int]
+    L.pfh_reads_gz_out.restype = None
+    L.pfh_reads_gz_out.argtypes = [C.c_int]
     L.pfh_reads_fasta.restype = None
     L.pfh_reads_fasta.argtypes = [C.c_int]
     L.pfh_fasta_index.restype = C.c_int
@@ -283,6 +286,10 @@ def load_library() -> C.CDLL:
     L.pfh_inflate_file_clause.argtypes = [vp, u64, u64, C.POINTER(C.c_int)]
     L.pfh_inflate_clause_text.restype = C.c_char_p
     L.pfh_inflate_clause_text.argtypes = [C.c_int]
+    L.pfh_deflate_member.restype = C.c_int64
+    L.pfh_deflate_member.argtypes = [vp, u32, vp, u64, vp]
+    L.pfh_deflate_bound.restype = u64
+    L.pfh_deflate_bound.argtypes = [u64, u32]
     L.pfh_gunzip_header.argtypes = [vp, u64, C.POINTER(u64)]
     L.pfh_gunzip_file_kind.argtypes = [vp, u64, u64, C.POINTER(C.c_int)]
     L.pfh_gunzip_candidate.argtypes = [vp, u64, u64]
@@ -497,11 +504,12 @@ MASK_STATS_FIELDS = ("reads", "reads_changed", "bases", "bases_masked", "kmers",
 MASK_CLAUSES = ("none", "header", "plus", "quality", "line_count", "fasta", "gzip", "same_path")      # pf_mask::Clause, in its order
 
 
-def mask_fastq(db: str, inputs, out: str, lower=None, upper=None, auto: bool = False, chunk_bytes: int = 0) -> dict:
+def mask_fastq(db: str, inputs, out: str, lower=None, upper=None, auto: bool = False, chunk_bytes: int = 0, gz_out: bool = False) -> dict:
     """`ploidyfrost mask` (pfh_mask_fastq): the reads of the FASTQ file(s) `inputs`, one after the other, with every base of every
     k-mer whose count in the KMC database `db` lies outside [lower, upper] replaced by N, written to `out`.  auto: lower =
     max(10, cutoffL) of the database's own histogram.  Returns the statistics plus "lower" (the threshold applied).  A refusal
-    raises RuntimeError with the input's path and the 1-based record number; nothing is left under `out`."""
+    raises RuntimeError with the input's path and the 1-based record number; nothing is left under `out`.  gz_out (`--gz-out`): `out` is
+    written as blocked gzip, deflated on the device (K-DEFLATE)."""
     L = load_library()
     if isinstance(inputs, (str, bytes, os.PathLike)):
         inputs = [inputs]
@@ -510,6 +518,7 @@ def mask_fastq(db: str, inputs, out: str, lower=None, upper=None, auto: bool = F
     paths = (C.c_char_p * max(len(inputs), 1))(*[os.fsencode(p) for p in inputs])
     stats = np.zeros(len(MASK_STATS_FIELDS), dtype=np.uint64)
     used = C.c_uint32()
+    L.pfh_reads_gz_out(int(gz_out))
     rc = L.pfh_mask_fastq(os.fsencode(db), paths, len(inputs), os.fsencode(out), 0 if lower is None else int(lower),
                           0xFFFFFFFF if upper is None else int(upper), int(auto), int(chunk_bytes), 0, stats.ctypes.data, C.byref(used))
     if rc:
@@ -648,11 +657,11 @@ def _gz_mode(gz) -> int:
     return int(bool(gz))
 
 
-def trim_fastq(inputs, out: str, steps, phred: int = 33, trimlog=None, chunk_bytes: int = 0, gz: bool = False) -> dict:
+def trim_fastq(inputs, out: str, steps, phred: int = 33, trimlog=None, chunk_bytes: int = 0, gz: bool = False, gz_out: bool = False) -> dict:
     """`ploidyfrost trim -i ... -o out STEP...` (pfh_trim_fastq): the reads of the FASTQ file(s) `inputs`, one after the other,
     quality-trimmed by `steps` (Trimmomatic's words) into `out`; trimlog: a file with one line per record.  Returns the statistics.  A
     refusal raises RuntimeError (format refusals with the input's path and the 1-based record number); nothing is left under any
-    output name."""
+    output name.  gz_out (`--gz-out`): `out` is written as blocked gzip, deflated on the device (K-DEFLATE)."""
     L = load_library()
     if isinstance(inputs, (str, bytes, os.PathLike)):
         inputs = [inputs]
@@ -660,6 +669,7 @@ def trim_fastq(inputs, out: str, steps, phred: int = 33, trimlog=None, chunk_byt
     paths = (C.c_char_p * max(len(inputs), 1))(*[os.fsencode(p) for p in inputs])
     stats = np.zeros(len(TRIM_STATS_FIELDS), dtype=np.uint64)
     L.pfh_reads_gz(_gz_mode(gz))
+    L.pfh_reads_gz_out(int(gz_out))
     rc = L.pfh_trim_fastq(paths, len(inputs), os.fsencode(out), st.ctypes.data if len(st) else None, len(st), phred,
                           os.fsencode(trimlog) if trimlog else None, int(chunk_bytes), 0, stats.ctypes.data)
     if rc:
@@ -667,15 +677,16 @@ def trim_fastq(inputs, out: str, steps, phred: int = 33, trimlog=None, chunk_byt
     return {f: int(v) for f, v in zip(TRIM_STATS_FIELDS, stats)}
 
 
-def trim_fastq_pair(in1: str, in2: str, outs, steps, phred: int = 33, trimlog=None, chunk_bytes: int = 0, gz: bool = False):
+def trim_fastq_pair(in1: str, in2: str, outs, steps, phred: int = 33, trimlog=None, chunk_bytes: int = 0, gz: bool = False, gz_out: bool = False):
     """`ploidyfrost trim -1 in1 -2 in2 -o1 .. -u1 .. -o2 .. -u2 .. STEP...` (pfh_trim_fastq_pair): outs = (o1, u1, o2, u2).  Returns the
-    statistics of file 1 and of file 2 (the pair fields are the same in both)."""
+    statistics of file 1 and of file 2 (the pair fields are the same in both).  gz_out (`--gz-out`): the four outputs are blocked gzip."""
     L = load_library()
     st = trim_parse_steps(steps)
     assert len(outs) == 4
     paths = (C.c_char_p * 4)(*[os.fsencode(p) for p in outs])
     stats = np.zeros((2, len(TRIM_STATS_FIELDS)), dtype=np.uint64)
     L.pfh_reads_gz(_gz_mode(gz))
+    L.pfh_reads_gz_out(int(gz_out))
     rc = L.pfh_trim_fastq_pair(os.fsencode(in1), os.fsencode(in2), paths, st.ctypes.data if len(st) else None, len(st), phred,
                                os.fsencode(trimlog) if trimlog else None, int(chunk_bytes), 0, stats.ctypes.data)
     if rc:
@@ -713,15 +724,16 @@ def count_fastq(inputs, out_prefix: str, k: int = 25, ci: int = 2, cx: int = 10 
 
 
 def mask_fastq_counted(inputs, out: str, k: int = 25, ci: int = 2, cx: int = 10 ** 9, cs: int = 255, both_strands: bool = True, db_out=None,
-                       lower=None, upper=None, auto: bool = False, chunk_bytes: int = 0) -> dict:
+                       lower=None, upper=None, auto: bool = False, chunk_bytes: int = 0, gz_out: bool = False) -> dict:
     """`ploidyfrost mask -k` (pfh_mask_fastq_counted): mask_fastq without a database -- the inputs are counted first, then masked
-    against their own counters; db_out: the database is written as well."""
+    against their own counters; db_out: the database is written as well; gz_out: `out` is blocked gzip."""
     L = load_library()
     if auto == (lower is not None):
         raise ValueError("mask_fastq_counted: either lower=L or auto=True")
     paths, n = _paths(inputs)
     stats = np.zeros(len(MASK_STATS_FIELDS), dtype=np.uint64)
     used = C.c_uint32()
+    L.pfh_reads_gz_out(int(gz_out))
     rc = L.pfh_mask_fastq_counted(paths, n, os.fsencode(out), int(k), int(ci), int(cx), int(cs), int(both_strands),
                                   None if db_out is None else os.fsencode(db_out), 0 if lower is None else int(lower),
                                   0xFFFFFFFF if upper is None else int(upper), int(auto), int(chunk_bytes), 0, stats.ctypes.data, C.byref(used))
@@ -1594,6 +1606,38 @@ def inflate_crc32(data, n_lanes: int = 0) -> int:
     a, p = _u8(data)
     L = load_library()
     return L.pfh_inflate_crc32_sliced(p, len(a), n_lanes) if n_lanes else L.pfh_inflate_crc32(p, len(a))
+
+
+# ---- blocked-gzip output: the rule of K-DEFLATE without a device (csrc/pf_deflate_rule.hpp) ----
+DEFLATE_MEMBER_TEXT = 65280   # pf_deflate::MEMBER_TEXT, bgzip's cut
+DEFLATE_EOF_MARKER = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+def deflate_member(text, guard: int = 64):
+    """pfh_deflate_member: one BGZF member of text (at most 65 280 bytes) -> (member bytes, (stored, fixed, dynamic), literals, matches).
+    The text is copied to a buffer of its own size and the output gets `guard` bytes behind the bound's len(text) + 31 that must come
+    back untouched."""
+    a, _ = _u8(text)
+    if len(a) > DEFLATE_MEMBER_TEXT:
+        raise ValueError("a member holds at most %d bytes of text" % DEFLATE_MEMBER_TEXT)
+    src = np.empty(len(a), dtype=np.uint8)
+    src[:] = a
+    cap = len(a) + 31
+    out = np.full(cap + guard, 0xA5, dtype=np.uint8)
+    res = (C.c_uint32 * 3)()
+    size = load_library().pfh_deflate_member(src.ctypes.data if len(src) else None, len(src), out.ctypes.data, cap, res)
+    if size < 0 or size > cap or not (out[cap:] == 0xA5).all():
+        raise AssertionError("pfh_deflate_member wrote outside out[0, n + 31)")
+    return out[:size].tobytes(), tuple(1 if res[0] == k else 0 for k in range(3)), int(res[1]), int(res[2])
+
+
+def deflate_bgzf(text, member_text: int = DEFLATE_MEMBER_TEXT, eof: bool = True) -> bytes:
+    """text cut into members of member_text bytes by the host rule, then the end-of-file marker: the file `--gz-out` writes for it (what
+    Device.deflate_bgzf is held to)"""
+    if not 1 <= member_text <= DEFLATE_MEMBER_TEXT:
+        raise ValueError("member_text is 1 .. %d" % DEFLATE_MEMBER_TEXT)
+    a, _ = _u8(text)
+    return b"".join(deflate_member(a[at:at + member_text])[0] for at in range(0, len(a), member_text)) + (DEFLATE_EOF_MARKER if eof else b"")
 
 
 # ---- plain gzip: the rule of K-GUNZIP without a device (csrc/pf_gunzip_rule.hpp) ----
