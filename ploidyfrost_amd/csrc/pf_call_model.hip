@@ -36,15 +36,6 @@
 #include "pf_model_rows.hpp"
 #include "pf_scan.hpp"
 
-#define PF_HIP(call)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            pf::CtxErr{ctx} = std::string(#call) + ": " + hipGetErrorString(e_);             \
-            return PF_ERR_HIP;                                                               \
-        }                                                                                    \
-    } while (0)
-
 namespace pf_call {
 
 // device-resident record of one collection

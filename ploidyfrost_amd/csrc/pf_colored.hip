@@ -25,15 +25,6 @@
 
 using namespace pf;
 
-#define PF_HIP(call)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            pf::CtxErr{ctx} = std::string(#call) + ": " + hipGetErrorString(e_);                   \
-            return PF_ERR_HIP;                                                               \
-        }                                                                                    \
-    } while (0)
-
 namespace {
 
 constexpr uint32_t MISSING = pf::CTAB_MISSING;

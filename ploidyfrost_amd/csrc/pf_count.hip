@@ -177,11 +177,6 @@ __global__ __launch_bounds__(256) void k_kmc_lut(const uint64_t *__restrict__ km
 }
 
 // ---- host side ----
-struct CountTimed {   // brackets everything one call launches as one timed launch of PF_K_COUNT
-    pf_ctx *ctx;
-    explicit CountTimed(pf_ctx *c) : ctx(c) { ctx_begin(ctx, PF_K_COUNT); }
-    ~CountTimed() { ctx_end(ctx); }
-};
 
 void count_destroy(pf_ctx *ctx) {
     CountState *S = count_state(ctx);
@@ -337,7 +332,7 @@ extern "C" int pf_count_reads(pf_ctx *ctx, const char *text, uint64_t n_bytes, c
     h.bad_entry = MASK_NO_RECORD;
     if (n_bytes == 0 && n_reads == 0) { count_stats_out(stats, S, 0, h); return PF_OK; }
     PF_HIP(hipSetDevice(ctx->device));
-    CountTimed timed(ctx);
+    Timed timed(ctx, PF_K_COUNT);
     // the table of reads and the counters
     const size_t off_bytes = up256((size_t)n_reads * 8), len_bytes = up256((size_t)n_reads * 4);
     char *tw = static_cast<char *>(ctx_ws(ctx, WS_MASK_TABLE, off_bytes + len_bytes + 256));
@@ -386,7 +381,7 @@ extern "C" int pf_count_fastq(pf_ctx *ctx, const char *text, uint64_t n_bytes, i
     if (n_bytes == 0) { count_stats_out(stats, S, 0, h); return PF_OK; }
     if (stats) *stats = pf_count_stats{};
     PF_HIP(hipSetDevice(ctx->device));
-    CountTimed timed(ctx);
+    Timed timed(ctx, PF_K_COUNT);
     const char *dt = nullptr;
     { const int rc = mask_stage_text(ctx, text, n_bytes, &dt); if (rc) return rc; }
     FastqIndex ix;

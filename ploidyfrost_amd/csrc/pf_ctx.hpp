@@ -168,6 +168,15 @@ struct CtxErr {
         c->err = std::move(s);
     }
 };
+// a HIP call inside an entry point that has `ctx` and returns a PF_ERR_* code: on failure the call's text and HIP's go to pf_ctx::err
+#define PF_HIP(call)                                                                         \
+    do {                                                                                     \
+        hipError_t e_ = (call);                                                              \
+        if (e_ != hipSuccess) {                                                              \
+            pf::CtxErr{ctx} = std::string(#call) + ": " + hipGetErrorString(e_);                   \
+            return PF_ERR_HIP;                                                               \
+        }                                                                                    \
+    } while (0)
 struct Kc4Args;
 int launch_cov_stream(pf_ctx *ctx, Kc4Args a, uint32_t n_colors, bool wide, bool colored);  // pf_device.hip
 int ctx_begin(pf_ctx *ctx, int kernel);
@@ -177,8 +186,15 @@ void ctx_end_on(pf_ctx *ctx, hipStream_t stream);
 // the same for a caller that keeps the place of its launch itself: any thread, any stream
 int ctx_begin_at(pf_ctx *ctx, int kernel, hipStream_t stream, size_t *at);
 void ctx_end_at(pf_ctx *ctx, size_t at, hipStream_t stream);
+// everything an entry point launches from here to the end of the scope, as one timed launch of `kernel`
+struct Timed {
+    pf_ctx *ctx;
+    Timed(pf_ctx *c, int kernel) : ctx(c) { ctx_begin(ctx, kernel); }
+    ~Timed() { ctx_end(ctx); }
+};
 inline void ctx_units(pf_ctx *ctx, int kernel, uint64_t n) { if (ctx->timing) __atomic_fetch_add(&ctx->units[kernel], n, __ATOMIC_RELAXED); }
 int ctx_grid(const pf_ctx *ctx, uint64_t work_items, int block, int per_cu);
+inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }   // the parts of one allocation start at multiples of 256 bytes
 int join_graph_counts(pf_ctx *ctx);
 int join_graph_counts_begin(pf_ctx *ctx);   // pf_device.hip: the kernels on a stream of their own; join_finish() before d_gcov is read
 int join_finish(pf_ctx *ctx);

@@ -30,15 +30,6 @@
 #include "pf_deflate_rule.hpp"
 #include "pf_scan.hpp"
 
-#define PF_HIP(call)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            pf::CtxErr{ctx} = std::string(#call) + ": " + hipGetErrorString(e_);                   \
-            return PF_ERR_HIP;                                                               \
-        }                                                                                    \
-    } while (0)
-
 namespace pf {
 
 namespace dfl = pf_deflate;
@@ -350,14 +341,6 @@ __global__ __launch_bounds__(DEF_BLOCK) void k_deflate_pack(const uint8_t *__res
     for (uint32_t i = head + 4 * n_dw + tid; i < size; i += DEF_BLOCK) dst[i] = src[i];
 }
 
-struct DeflateTimed {   // brackets everything one call launches as one timed launch of PF_K_DEFLATE
-    pf_ctx *ctx;
-    explicit DeflateTimed(pf_ctx *c) : ctx(c) { ctx_begin(ctx, PF_K_DEFLATE); }
-    ~DeflateTimed() { ctx_end(ctx); }
-};
-
-static size_t up256d(size_t n) { return (n + 255) & ~(size_t)255; }
-
 }  // namespace pf
 
 using namespace pf;
@@ -385,7 +368,7 @@ extern "C" int pf_deflate_bgzf(pf_ctx *ctx, const char *text, uint64_t n_bytes, 
         return PF_OK;
     }
     if (!text || !out) return refuse("text and out are needed");
-    DeflateTimed timed(ctx);
+    Timed timed(ctx, PF_K_DEFLATE);
 
     // ---- stage what the caller holds on the host ----
     DevTmp<uint8_t> d_text_, d_out_;
@@ -404,7 +387,7 @@ extern "C" int pf_deflate_bgzf(pf_ctx *ctx, const char *text, uint64_t n_bytes, 
     // ---- slots, sizes, places ----
     const uint32_t stride = (member_text + dfl::MEMBER_EXTRA + 3) & ~3u;
     const uint64_t n1 = n_members + 1;
-    const size_t slot_bytes = up256d((size_t)n_members * stride), size_bytes = up256d((size_t)n1 * 8), scr_bytes = up256d(scan_scratch_bytes(n1));
+    const size_t slot_bytes = up256((size_t)n_members * stride), size_bytes = up256((size_t)n1 * 8), scr_bytes = up256(scan_scratch_bytes(n1));
     DevTmp<char> ww_;
     PF_HIP(ww_.alloc(slot_bytes + 2 * size_bytes + scr_bytes + 256));
     char *ww = ww_.p;

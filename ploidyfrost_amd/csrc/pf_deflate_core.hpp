@@ -47,7 +47,7 @@ constexpr uint32_t MAX_RLE = N_LIT + N_DIST;
 constexpr int LIT_BITS = 15, BL_BITS = 7;
 enum Kind { KIND_STORED = 0, KIND_FIXED = 1, KIND_DYNAMIC = 2 };
 
-struct NoSync { PF_DEF_HD void operator()() const {} };
+using pf_inflate::NoSync;
 
 PF_DEF_HD inline uint32_t hash4(uint32_t w) { return (w * 2654435761u) >> (32 - HASH_BITS); }
 

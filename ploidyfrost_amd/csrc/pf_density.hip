@@ -30,15 +30,6 @@
 // the quantile, the bandwidth and the grid are stated operation by operation: no fused multiply-add takes two of them at once
 #pragma clang fp contract(off)
 
-#define PF_HIP(call)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            pf::CtxErr{ctx} = std::string(#call) + ": " + hipGetErrorString(e_);                   \
-            return PF_ERR_HIP;                                                               \
-        }                                                                                    \
-    } while (0)
-
 namespace pf {
 
 constexpr int DEN_BLOCK = 256;

@@ -24,15 +24,6 @@ using namespace pf;
 
 static std::string g_create_err;
 
-#define PF_HIP(call)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            pf::CtxErr{ctx} = std::string(#call) + ": " + hipGetErrorString(e_);                   \
-            return PF_ERR_HIP;                                                               \
-        }                                                                                    \
-    } while (0)
-
 // ------------------------------------------------------------------------------------------
 // kernels
 // ------------------------------------------------------------------------------------------
@@ -745,7 +736,6 @@ static int stage_in(pf_ctx *ctx, const T *src, size_t n, T **dev, bool *owned) {
     PF_HIP(hipMemcpyAsync(*dev, src, n * sizeof(T), hipMemcpyDefault, ctx->stream));
     return PF_OK;
 }
-
 
 extern "C" {
 

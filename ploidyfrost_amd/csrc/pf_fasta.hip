@@ -150,11 +150,6 @@ __global__ __launch_bounds__(FASTA_BLOCK) void k_fasta_table(const uint64_t *__r
 }
 
 // ---- host side ----
-struct FastaTimed {   // brackets everything the index launches as one timed launch of PF_K_FASTA
-    pf_ctx *ctx;
-    explicit FastaTimed(pf_ctx *c) : ctx(c) { ctx_begin(ctx, PF_K_FASTA); }
-    ~FastaTimed() { ctx_end(ctx); }
-};
 
 struct FastaIndex {   // what K-FASTA leaves on the device
     uint64_t n_rec = 0, used = 0, bases = 0;
@@ -165,7 +160,7 @@ struct FastaIndex {   // what K-FASTA leaves on the device
 
 // the index of one chunk (0 < n_bytes < 2^32 - 256, text staged on the device), by `who`
 static int fasta_index_core(pf_ctx *ctx, const char *who, const char *dt, uint64_t n_bytes, int final, FastaIndex &ix) {
-    FastaTimed timed(ctx);
+    Timed timed(ctx, PF_K_FASTA);
     ix = FastaIndex{};
     ctx_units(ctx, PF_K_FASTA, n_bytes);
     {   // a chunk starts at a record start

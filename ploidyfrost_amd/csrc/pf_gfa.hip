@@ -33,15 +33,6 @@
 
 using namespace pf;
 
-#define PF_HIP(call)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            pf::CtxErr{ctx} = std::string(#call) + ": " + hipGetErrorString(e_);                   \
-            return PF_ERR_HIP;                                                               \
-        }                                                                                    \
-    } while (0)
-
 namespace {
 
 constexpr uint32_t GFA_TILE = 2048;
@@ -254,8 +245,7 @@ extern "C" {
 
 // Errors of pf_gfa_parse are kept in the K-GFA state (pf_gfa_upload reports them): the call may run beside another one on the
 // same context, whose error string it must not touch.
-#undef PF_HIP
-#define PF_HIP(call)                                                                         \
+#define PF_HIP_S(call)                                                                        \
     do {                                                                                     \
         hipError_t e_ = (call);                                                              \
         if (e_ != hipSuccess) {                                                              \
@@ -269,72 +259,72 @@ int pf_gfa_parse(pf_ctx *ctx, const char *body, uint64_t n_bytes, int gfa_versio
     GfaState *S = state_of(ctx);
     S->release();
     S->err.clear();
-    PF_HIP(hipSetDevice(ctx->device));
-    if (!S->stream) PF_HIP(hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking));
+    PF_HIP_S(hipSetDevice(ctx->device));
+    if (!S->stream) PF_HIP_S(hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking));
     hipStream_t st = S->stream;
     S->n_bytes = n_bytes;
-    PF_HIP(hipMalloc(reinterpret_cast<void **>(&S->text), n_bytes + 128));
-    PF_HIP(hipMemsetAsync(S->text + n_bytes, 0, 128, st));
-    if (n_bytes) PF_HIP(hipMemcpyAsync(S->text, body, n_bytes, hipMemcpyDefault, st));
+    PF_HIP_S(hipMalloc(reinterpret_cast<void **>(&S->text), n_bytes + 128));
+    PF_HIP_S(hipMemsetAsync(S->text + n_bytes, 0, 128, st));
+    if (n_bytes) PF_HIP_S(hipMemcpyAsync(S->text, body, n_bytes, hipMemcpyDefault, st));
     const uint64_t n_tiles = (n_bytes + GFA_TILE - 1) / GFA_TILE;
     if (n_tiles >= (1ull << 31)) { S->err = "GFA file larger than 4 TiB"; S->release(); return PF_ERR_ARG; }
     DevTmp<uint32_t> cl_, cs_, bl_, bs_, small_;
-    PF_HIP(cl_.alloc((n_tiles + 1) * 4));
-    PF_HIP(cs_.alloc((n_tiles + 1) * 4));
-    PF_HIP(bl_.alloc((n_tiles + 1) * 4));
-    PF_HIP(bs_.alloc((n_tiles + 1) * 4));
-    PF_HIP(small_.alloc(16));
-    PF_HIP(hipMemsetAsync(small_.p, 0, 16, st));
-    PF_HIP(hipMemsetAsync(cl_.p + n_tiles, 0, 4, st));
-    PF_HIP(hipMemsetAsync(cs_.p + n_tiles, 0, 4, st));
+    PF_HIP_S(cl_.alloc((n_tiles + 1) * 4));
+    PF_HIP_S(cs_.alloc((n_tiles + 1) * 4));
+    PF_HIP_S(bl_.alloc((n_tiles + 1) * 4));
+    PF_HIP_S(bs_.alloc((n_tiles + 1) * 4));
+    PF_HIP_S(small_.alloc(16));
+    PF_HIP_S(hipMemsetAsync(small_.p, 0, 16, st));
+    PF_HIP_S(hipMemsetAsync(cl_.p + n_tiles, 0, 4, st));
+    PF_HIP_S(hipMemsetAsync(cs_.p + n_tiles, 0, 4, st));
     uint32_t *d_err = small_.p, *d_any_da = small_.p + 1;
     const unsigned grid = (unsigned)((n_tiles + 255) / 256);
     if (n_tiles)
         k_gfa_lines<false><<<grid, 256, 0, st>>>(S->text, n_bytes, gfa_version, k, n_tiles, cl_.p, cs_.p, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
                                                  d_err, d_any_da);
-    PF_HIP(hipGetLastError());
+    PF_HIP_S(hipGetLastError());
     DevTmp<uint8_t> tmp_;
-    PF_HIP(tmp_.alloc(scan_scratch_bytes(n_tiles + 1)));
-    PF_HIP(scan_exclusive_u32(cl_.p, bl_.p, n_tiles + 1, tmp_.p, st));
-    PF_HIP(scan_exclusive_u32(cs_.p, bs_.p, n_tiles + 1, tmp_.p, st));
+    PF_HIP_S(tmp_.alloc(scan_scratch_bytes(n_tiles + 1)));
+    PF_HIP_S(scan_exclusive_u32(cl_.p, bl_.p, n_tiles + 1, tmp_.p, st));
+    PF_HIP_S(scan_exclusive_u32(cs_.p, bs_.p, n_tiles + 1, tmp_.p, st));
     uint32_t n_long = 0, n_sh = 0, err = 0;
-    PF_HIP(hipMemcpyAsync(&n_long, bl_.p + n_tiles, 4, hipMemcpyDeviceToHost, st));
-    PF_HIP(hipMemcpyAsync(&n_sh, bs_.p + n_tiles, 4, hipMemcpyDeviceToHost, st));
-    PF_HIP(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, st));
-    PF_HIP(hipStreamSynchronize(st));
+    PF_HIP_S(hipMemcpyAsync(&n_long, bl_.p + n_tiles, 4, hipMemcpyDeviceToHost, st));
+    PF_HIP_S(hipMemcpyAsync(&n_sh, bs_.p + n_tiles, 4, hipMemcpyDeviceToHost, st));
+    PF_HIP_S(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, st));
+    PF_HIP_S(hipStreamSynchronize(st));
     auto refuse = [&](const char *msg) { const std::string m = msg; S->release(); S->err = m; return PF_ERR_ARG; };
     if (err & ERR_FIELDS) return refuse("missing fields in a segment line");
     if (err & ERR_SHORT) return refuse("segment shorter than k");
     const uint64_t N = (uint64_t)n_long + n_sh;
     if (N == 0) return refuse("no segments in the GFA file");
     if (N >= (1u << 30)) return refuse("more than 2^30 unitigs");
-    PF_HIP(hipMalloc(reinterpret_cast<void **>(&S->seg_off), N * 8));
-    PF_HIP(hipMalloc(reinterpret_cast<void **>(&S->seg_len), (N + 1) * 4));
-    PF_HIP(hipMalloc(reinterpret_cast<void **>(&S->rank), N * 4));
-    PF_HIP(hipMalloc(reinterpret_cast<void **>(&S->da), N * 4));
-    PF_HIP(hipMalloc(reinterpret_cast<void **>(&S->stored_rc), N));
+    PF_HIP_S(hipMalloc(reinterpret_cast<void **>(&S->seg_off), N * 8));
+    PF_HIP_S(hipMalloc(reinterpret_cast<void **>(&S->seg_len), (N + 1) * 4));
+    PF_HIP_S(hipMalloc(reinterpret_cast<void **>(&S->rank), N * 4));
+    PF_HIP_S(hipMalloc(reinterpret_cast<void **>(&S->da), N * 4));
+    PF_HIP_S(hipMalloc(reinterpret_cast<void **>(&S->stored_rc), N));
     k_gfa_lines<true><<<grid, 256, 0, st>>>(S->text, n_bytes, gfa_version, k, n_tiles, nullptr, nullptr, bl_.p, bs_.p, n_long, S->seg_off, S->seg_len, S->rank,
                                             S->da, d_err, d_any_da);
-    PF_HIP(hipGetLastError());
+    PF_HIP_S(hipGetLastError());
     // word offsets, then the packed words
     DevTmp<uint64_t> wc_;
-    PF_HIP(wc_.alloc((N + 1) * 8));
-    PF_HIP(hipMalloc(reinterpret_cast<void **>(&S->word_off), (N + 1) * 8));
+    PF_HIP_S(wc_.alloc((N + 1) * 8));
+    PF_HIP_S(hipMalloc(reinterpret_cast<void **>(&S->word_off), (N + 1) * 8));
     k_gfa_words<<<(unsigned)((N + 1 + 255) / 256), 256, 0, st>>>(S->seg_len, (uint32_t)N, wc_.p);
     DevTmp<uint8_t> tmp2_;
-    PF_HIP(tmp2_.alloc(scan_scratch_bytes(N + 1)));
-    PF_HIP(scan_exclusive_u64(wc_.p, S->word_off, N + 1, tmp2_.p, st));
+    PF_HIP_S(tmp2_.alloc(scan_scratch_bytes(N + 1)));
+    PF_HIP_S(scan_exclusive_u64(wc_.p, S->word_off, N + 1, tmp2_.p, st));
     uint64_t n_words = 0;
     uint32_t any_da = 0;
-    PF_HIP(hipMemcpyAsync(&n_words, S->word_off + N, 8, hipMemcpyDeviceToHost, st));
-    PF_HIP(hipMemcpyAsync(&any_da, d_any_da, 4, hipMemcpyDeviceToHost, st));
-    PF_HIP(hipStreamSynchronize(st));
-    PF_HIP(hipMalloc(reinterpret_cast<void **>(&S->words), (n_words + 2) * 8));
-    PF_HIP(hipMemsetAsync(S->words + n_words, 0, 16, st));
+    PF_HIP_S(hipMemcpyAsync(&n_words, S->word_off + N, 8, hipMemcpyDeviceToHost, st));
+    PF_HIP_S(hipMemcpyAsync(&any_da, d_any_da, 4, hipMemcpyDeviceToHost, st));
+    PF_HIP_S(hipStreamSynchronize(st));
+    PF_HIP_S(hipMalloc(reinterpret_cast<void **>(&S->words), (n_words + 2) * 8));
+    PF_HIP_S(hipMemsetAsync(S->words + n_words, 0, 16, st));
     k_gfa_pack<<<(unsigned)((n_words + 255) / 256), 256, 0, st>>>(S->text, S->seg_off, S->seg_len, S->word_off, (uint32_t)N, n_words, k, S->words, S->stored_rc, d_err);
-    PF_HIP(hipGetLastError());
-    PF_HIP(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, st));
-    PF_HIP(hipStreamSynchronize(st));
+    PF_HIP_S(hipGetLastError());
+    PF_HIP_S(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, st));
+    PF_HIP_S(hipStreamSynchronize(st));
     if (err & ERR_BASE) return refuse("non-ACGT base in a segment");
     S->n = (uint32_t)N;
     S->n_short = n_sh;
@@ -348,15 +338,6 @@ int pf_gfa_parse(pf_ctx *ctx, const char *body, uint64_t n_bytes, int gfa_versio
     return PF_OK;
 }
 
-#undef PF_HIP
-#define PF_HIP(call)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            pf::CtxErr{ctx} = std::string(#call) + ": " + hipGetErrorString(e_);                   \
-            return PF_ERR_HIP;                                                               \
-        }                                                                                    \
-    } while (0)
 
 const char *pf_gfa_error(const pf_ctx *ctx) {
     return ctx && ctx->gfa ? static_cast<const GfaState *>(ctx->gfa)->err.c_str() : "";

@@ -27,15 +27,6 @@
 #include "../../include/ploidyfrost_hip.h"
 #include "pf_ctx.hpp"
 
-#define PF_HIP(call)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            pf::CtxErr{ctx} = std::string(#call) + ": " + hipGetErrorString(e_);                   \
-            return PF_ERR_HIP;                                                               \
-        }                                                                                    \
-    } while (0)
-
 namespace pf {
 
 constexpr int GMM_MAXG = PF_GMM_MAX_GAUSS;

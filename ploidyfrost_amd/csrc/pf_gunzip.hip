@@ -7,7 +7,8 @@
 //            start (sixteen wavefronts share a stride, each over its own run of bits: the smallest hit is the first).
 //            k_gunzip_starts puts start_bit (always a true block start) and the candidates in one ascending list.
 //   count    k_gunzip_count, one wavefront per piece: pf_gunzip::decode_piece with a CountSink, up to a final block, a piece start it
-//            lands on, the end of the bits or a clause.
+//            lands on, the end of the bits or a clause.  (decode_piece drives the decoder of pf_inflate_core.hpp, the one K-INFLATE
+//            runs, and reads the compressed bytes through the same window in LDS: GzIn, pf_gz_dev.hpp.)
 //   chain    k_gunzip_chain, one thread: follows the links from piece 0; the pieces on the chain are live and get their places by a
 //            running sum, all others are dead and what they found is ignored.  Correctness rests here: piece 0 starts at a true block
 //            start and a piece stops at block boundaries of its own decode only, so a false candidate costs one wasted wavefront.
@@ -29,23 +30,13 @@
 #include "../../include/ploidyfrost_hip.h"
 #include "pf_ctx.hpp"
 #include "pf_gunzip_rule.hpp"
-
-#define PF_HIP(call)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            pf::CtxErr{ctx} = std::string(#call) + ": " + hipGetErrorString(e_);                   \
-            return PF_ERR_HIP;                                                               \
-        }                                                                                    \
-    } while (0)
+#include "pf_gz_dev.hpp"
 
 namespace pf {
 
 namespace gz = pf_gunzip;
 
-constexpr int GUN_WAVE = 64;
-constexpr uint32_t GUN_WINDOW = 1024;   // bytes of comp held in LDS
-constexpr uint32_t GUN_KEEP = 64;       // of them behind the byte asked for
+constexpr int GUN_WAVE = GZ_WAVE;
 constexpr uint32_t GUN_NO_BAD = 0xffffffffu;
 constexpr uint32_t GUN_FIND_SPLIT = 16;   // wavefronts that search one stride
 constexpr uint32_t GUN_CRC_SLICE = 512; // bytes of text a thread of the CRC takes
@@ -75,11 +66,6 @@ struct GunzipArgs {
     uint32_t crc_threads;
 };
 
-struct GunBytes {
-    const uint8_t *p;
-    __device__ uint32_t operator[](uint64_t i) const { return p[i]; }
-};
-
 // (a stride is searched by GUN_FIND_SPLIT wavefronts, each over its own run of bits; the smallest hit is the first candidate)
 __global__ __launch_bounds__(GUN_WAVE) void k_gunzip_find(const GunzipArgs a) {
     const uint32_t b = blockIdx.x / GUN_FIND_SPLIT, part = blockIdx.x % GUN_FIND_SPLIT;
@@ -91,7 +77,7 @@ __global__ __launch_bounds__(GUN_WAVE) void k_gunzip_find(const GunzipArgs a) {
     uint64_t found = gz::NO_BIT;
     for (uint64_t base = from; base < to; base += GUN_WAVE) {   // (the same turns for every lane)
         const uint64_t bit = base + threadIdx.x;
-        const bool ok = bit < to && gz::block_candidate(GunBytes{a.comp}, (uint64_t)a.n_bytes, bit);
+        const bool ok = bit < to && gz::block_candidate(GzBytes{a.comp}, (uint64_t)a.n_bytes, bit);
         const unsigned long long hit = __ballot(ok);
         if (hit) { found = base + (uint64_t)(__ffsll((long long)hit) - 1); break; }
     }
@@ -107,58 +93,22 @@ __global__ void k_gunzip_starts(const GunzipArgs a) {
     a.small->n_pieces = n;
 }
 
-struct GunSync {
-    __host__ __device__ void operator()() const {
-#if defined(__HIP_DEVICE_COMPILE__)
-        __syncthreads();
-#endif
-    }
-};
-
-// comp[0, n_in) through a window in LDS; every lane of the wavefront asks for the same byte at the same time
-struct GunIn {
-    const uint8_t *p;
-    uint32_t n_in, lane;
-    uint32_t *win;              // GUN_WINDOW / 4 dwords
-    mutable uint32_t base;      // the window holds bytes [base - shift, base - shift + GUN_WINDOW), base a multiple of 4
-    uint32_t shift;             // p's distance from the dword boundary in front of it
-    __device__ void refill(uint32_t j) const {   // j = i + shift
-        __syncthreads();
-        base = (j >= GUN_KEEP ? j - GUN_KEEP : 0u) & ~3u;
-        const uint8_t *q = p - shift;   // a dword boundary; nothing in front of p is read
-        for (uint32_t k = lane; k < GUN_WINDOW / 4; k += GUN_WAVE) {
-            const uint64_t jj = (uint64_t)base + 4 * k;
-            uint32_t v = 0;
-            if (jj >= shift && jj + 4 <= (uint64_t)shift + n_in) {
-                v = *reinterpret_cast<const uint32_t *>(q + jj);
-            } else {
-                for (uint32_t b = 0; b < 4; ++b)
-                    if (jj + b >= shift && jj + b < (uint64_t)shift + n_in) v |= (uint32_t)q[jj + b] << (8 * b);
-            }
-            win[k] = v;
-        }
-        __syncthreads();
-    }
-    __device__ uint8_t byte(uint32_t i) const {   // i < n_in
-        const uint32_t j = i + shift;
-        if (j - base >= GUN_WINDOW) refill(j);
-        return reinterpret_cast<const uint8_t *>(win)[j - base];
-    }
-    __device__ uint8_t raw(uint32_t i) const { return p[i]; }   // i < n_in (a stored block's bytes)
-};
+// comp[0, n_bytes) for a piece that starts at start_bit, the window filled around its first byte
+__device__ inline GzIn gunzip_in(const GunzipArgs &a, uint64_t start_bit, uint32_t lane, uint32_t *window) {
+    return GzIn(a.comp, a.n_bytes, lane, window, (uint32_t)min(start_bit >> 3, (uint64_t)(a.n_bytes ? a.n_bytes - 1 : 0)));
+}
 
 __global__ __launch_bounds__(GUN_WAVE) void k_gunzip_count(const GunzipArgs a) {
-    __shared__ uint32_t window[GUN_WINDOW / 4];
+    __shared__ uint32_t window[GZ_WINDOW / 4];
     __shared__ pf_inflate::Work work;
     const uint32_t p = blockIdx.x, lane = threadIdx.x;
     const uint32_t n_pieces = a.small->n_pieces;
     if (p >= n_pieces) return;
     const uint64_t start = a.starts[p];
-    GunIn in{a.comp, a.n_bytes, lane, window, 0u, (uint32_t)((uintptr_t)a.comp & 3u)};
-    in.refill((uint32_t)min(start >> 3, (uint64_t)(a.n_bytes ? a.n_bytes - 1 : 0)) + in.shift);
+    const GzIn in = gunzip_in(a, start, lane, window);
     gz::CountSink sink;
     gz::Piece r;
-    gz::decode_piece(in, a.n_bytes, start, a.starts, n_pieces, p + 1, gz::NO_BIT, ~0ull, sink, work, lane, (uint32_t)GUN_WAVE, GunSync{}, r);
+    gz::decode_piece(in, a.n_bytes, start, a.starts, n_pieces, p + 1, gz::NO_BIT, ~0ull, sink, work, lane, (uint32_t)GUN_WAVE, GzSync{}, r);
     if (lane == 0) a.pieces[p] = r;
 }
 
@@ -194,29 +144,20 @@ __global__ void k_gunzip_chain(const GunzipArgs a) {
 
 __global__ __launch_bounds__(GUN_WAVE) void k_gunzip_decode(const GunzipArgs a) {
     __shared__ uint16_t ring[gz::RING];
-    __shared__ uint32_t window[GUN_WINDOW / 4];
+    __shared__ uint32_t window[GZ_WINDOW / 4];
     __shared__ pf_inflate::Work work;
     const uint32_t k = blockIdx.x, lane = threadIdx.x;
     const uint32_t p = a.live[k];
     const gz::Piece first = a.pieces[p];
     const uint64_t start = a.starts[p], place = a.place[k];
-    GunIn in{a.comp, a.n_bytes, lane, window, 0u, (uint32_t)((uintptr_t)a.comp & 3u)};
-    in.refill((uint32_t)min(start >> 3, (uint64_t)(a.n_bytes ? a.n_bytes - 1 : 0)) + in.shift);
-    gz::RingSink<GunSync> sink(ring, a.stage + place, place + a.n_window, lane, (uint32_t)GUN_WAVE, GunSync{});
+    const GzIn in = gunzip_in(a, start, lane, window);
+    gz::RingSink<GzSync> sink(ring, a.stage + place, place + a.n_window, lane, (uint32_t)GUN_WAVE, GzSync{});
     gz::Piece r;
-    gz::decode_piece(in, a.n_bytes, start, (const uint64_t *)nullptr, 0u, 0u, first.end_bit, first.symbols, sink, work, lane, (uint32_t)GUN_WAVE, GunSync{}, r);
+    gz::decode_piece(in, a.n_bytes, start, (const uint64_t *)nullptr, 0u, 0u, first.end_bit, first.symbols, sink, work, lane, (uint32_t)GUN_WAVE, GzSync{}, r);
     if (lane == 0) {
         a.again[k] = r;
         if (r.link != gz::LINK_LIMIT || r.symbols != first.symbols) atomicMin(&a.small->bad_live, k);
     }
-}
-
-// the byte a marker v of a piece at `place` stands for
-__device__ inline uint32_t gunzip_behind(const GunzipArgs &a, uint64_t place, uint32_t v) {
-    const long long q = (long long)place - (long long)gz::RING + (long long)(v & 0x7fffu);
-    if (q >= 0) return (uint32_t)a.stage[q] & 0xffu;
-    const long long wq = (long long)a.n_window + q;
-    return wq >= 0 ? (uint32_t)a.window[wq] : 0u;   // (wq < 0 was refused by the decode stage)
 }
 
 __global__ __launch_bounds__(1024) void k_gunzip_window(const GunzipArgs a) {
@@ -225,7 +166,7 @@ __global__ __launch_bounds__(1024) void k_gunzip_window(const GunzipArgs a) {
         const uint64_t place = a.place[k], n = a.place[k + 1] - place;
         for (uint64_t s = (n > gz::RING ? n - gz::RING : 0) + threadIdx.x; s < n; s += blockDim.x) {
             const uint32_t v = a.stage[place + s];
-            if (v & gz::MARKER) a.stage[place + s] = (uint16_t)(gz::RESOLVED | gunzip_behind(a, place, v));   // (reads in front of `place` only)
+            if (v & gz::MARKER) a.stage[place + s] = (uint16_t)(gz::RESOLVED | gz::behind(a.stage, a.window, a.n_window, place, v));   // (reads in front of `place` only)
         }
         __syncthreads();   // the next piece reads what this one wrote
     }
@@ -250,7 +191,7 @@ __global__ __launch_bounds__(256) void k_gunzip_resolve(const GunzipArgs a) {
             while (k + 1 < n_live && i >= a.place[k + 1]) ++k;
             const uint32_t v = a.stage[i];
             if (v & (gz::MARKER | gz::RESOLVED)) ++markers;
-            word |= ((v & gz::MARKER) ? gunzip_behind(a, a.place[k], v) : (v & 0xffu)) << (8 * b);
+            word |= ((v & gz::MARKER) ? gz::behind(a.stage, a.window, a.n_window, a.place[k], v) : (v & 0xffu)) << (8 * b);
         }
         if (n == 4 && (((uintptr_t)(a.out + i0)) & 3u) == 0) {
             *reinterpret_cast<uint32_t *>(a.out + i0) = word;
@@ -269,7 +210,7 @@ __global__ __launch_bounds__(256) void k_gunzip_tail(const GunzipArgs a) {
     if (t < a.crc_threads) {
         const uint32_t begin = pf_inflate::slice_begin(total, a.crc_threads, t), end = pf_inflate::slice_end(total, a.crc_threads, t);
         if (end > begin) {
-            const uint32_t raw = pf_inflate::crc_raw(GunBytes{a.out}, begin, end);
+            const uint32_t raw = pf_inflate::crc_raw(GzBytes{a.out}, begin, end);
             atomicXor(&a.small->crc_raw, pf_inflate::slice_share(raw, total, a.crc_threads, t));
         }
     }
@@ -283,11 +224,6 @@ __global__ __launch_bounds__(256) void k_gunzip_tail(const GunzipArgs a) {
     }
 }
 
-struct GunzipTimed {   // brackets everything one call launches as one timed launch of PF_K_GUNZIP
-    pf_ctx *ctx;
-    explicit GunzipTimed(pf_ctx *c) : ctx(c) { ctx_begin(ctx, PF_K_GUNZIP); }
-    ~GunzipTimed() { ctx_end(ctx); }
-};
 struct GunzipEvents {   // the stages' own times, when the caller asks for stats with timing on
     hipEvent_t e[7] = {};
     bool on = false;
@@ -298,8 +234,6 @@ struct GunzipEvents {   // the stages' own times, when the caller asks for stats
     }
     void mark(int i, hipStream_t s) { if (on) (void)hipEventRecord(e[i], s); }
 };
-
-static size_t gun_up256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 }  // namespace pf
 
@@ -319,7 +253,7 @@ extern "C" int pf_inflate_gzip(pf_ctx *ctx, const uint8_t *comp, uint64_t n_byte
     if (n_window > gz::RING) return refuse("a window holds at most 32768 bytes");
     if ((n_bytes && !comp) || (n_window && !window)) return refuse("comp and window are needed");
     PF_HIP(hipSetDevice(ctx->device));
-    GunzipTimed timed(ctx);
+    Timed timed(ctx, PF_K_GUNZIP);
     GunzipEvents ev;
     ev.start(stats && ctx->timing);
 
@@ -342,8 +276,8 @@ extern "C" int pf_inflate_gzip(pf_ctx *ctx, const uint8_t *comp, uint64_t n_byte
     const uint32_t stride = gz::piece_stride(piece_bytes);
     const uint64_t nb64 = gz::boundary_count(n_bytes, start_bit, stride);
     const uint32_t n_bound = (uint32_t)nb64, n1 = n_bound + 1;
-    const size_t cand_b = gun_up256((size_t)n1 * 8), piece_b = gun_up256((size_t)n1 * sizeof(gz::Piece)), live_b = gun_up256((size_t)n1 * 4),
-                 place_b = gun_up256((size_t)(n1 + 1) * 8);
+    const size_t cand_b = up256((size_t)n1 * 8), piece_b = up256((size_t)n1 * sizeof(gz::Piece)), live_b = up256((size_t)n1 * 4),
+                 place_b = up256((size_t)(n1 + 1) * 8);
     DevTmp<char> ww_;
     PF_HIP(ww_.alloc(2 * cand_b + 2 * piece_b + live_b + place_b + 256));
     char *ww = ww_.p;

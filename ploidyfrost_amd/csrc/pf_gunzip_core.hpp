@@ -6,7 +6,10 @@
 //   CountSink         produces nothing: the first pass, which gives every piece its end, its link and its number of symbols
 //   RingSink          16-bit symbols through a ring of the last 32 Ki symbols: a byte is 0..255, a back-reference that reaches in front
 //                     of the piece is the marker 0x8000 | (32768 + at - dist), an index into the 32 KiB in front of the piece
-// Built on pf_inflate_core.hpp (the bit reader, the code tables, the dynamic header, the CRC pieces), which stays as it is.
+//   behind            the byte a marker stands for, for the window and resolve stages
+// The decoder itself -- the bit reader, the code tables, the symbol loop and the block step -- is pf_inflate_core.hpp's, the one K-INFLATE
+// runs: decode_piece is a loop around pf_inflate::inflate_block, and a piece's sinks say what differs (64-bit places, text in front of
+// place 0, CLAUSE_PIECE_LIMIT for text past the bound).
 //
 // Every loop ends whatever the bytes say: the block loop consumes at least three bits a turn, the symbol loop a bit or a symbol, and a
 // reader past its last bit ends them all.  Nothing is read outside in[0, n_bytes), and a RingSink writes stage[0, max_syms) only.
@@ -150,7 +153,9 @@ PF_INF_HD inline bool block_candidate(const Bytes &p, uint64_t n_bytes, uint64_t
 
 // ---- sinks ----
 struct CountSink {
-    PF_INF_HD uint64_t reach() const { return ~0ull; }
+    typedef uint64_t Pos;
+    static constexpr int BEYOND = CLAUSE_PIECE_LIMIT;
+    PF_INF_HD uint64_t reach() const { return ~0ull; }   // (what lies in front of a piece is known to the second pass only)
     PF_INF_HD void put(uint64_t, uint32_t) {}
     PF_INF_HD void copy(uint64_t, uint32_t, uint32_t) {}
     template <typename In>
@@ -162,6 +167,8 @@ struct CountSink {
 // tested every range: at + len <= max_syms, and dist <= at + before.
 template <typename Sync>
 struct RingSink {
+    typedef uint64_t Pos;
+    static constexpr int BEYOND = CLAUSE_PIECE_LIMIT;
     uint16_t *ring, *stage;
     uint64_t before;        // bytes of text in front of the piece (earlier pieces of the call and the window)
     uint32_t lane, n_lanes;
@@ -202,40 +209,6 @@ struct RingSink {
     PF_INF_HD void finish(uint64_t at) { if (at > flushed) flush(at); }
 };
 
-// the symbols of one fixed or dynamic block (pf_inflate::inflate_codes with a Sink, 64-bit places and the piece's own bounds)
-template <typename In, typename Sink>
-PF_INF_HD inline int piece_codes(BitReader<In> &br, const Work &w, Sink &sink, uint64_t &at, uint64_t max_syms) {
-    const uint16_t lbase[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
-    const uint8_t lext[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
-    const uint16_t dbase[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
-    const uint8_t dext[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
-    for (;;) {   // a turn consumes at least one bit
-        int sym = pf_inflate::decode_symbol(br, w.lit);
-        if (br.over) return pf_inflate::CLAUSE_END;   // (bits that are not there decide nothing)
-        if (sym < 0) return pf_inflate::CLAUSE_BAD_CODE;
-        if (sym < 256) {
-            if (at >= max_syms) return CLAUSE_PIECE_LIMIT;
-            sink.put(at, (uint32_t)sym);
-            ++at;
-            continue;
-        }
-        if (sym == 256) return pf_inflate::CLAUSE_NONE;
-        sym -= 257;
-        if (sym >= 29) return pf_inflate::CLAUSE_LITLEN_SYM;
-        const uint32_t len = (uint32_t)lbase[sym] + br.bits(lext[sym]);
-        const int ds = pf_inflate::decode_symbol(br, w.dist);
-        if (br.over) return pf_inflate::CLAUSE_END;
-        if (ds < 0) return pf_inflate::CLAUSE_BAD_CODE;
-        if (ds >= 30) return pf_inflate::CLAUSE_DIST_SYM;
-        const uint32_t dist = (uint32_t)dbase[ds] + br.bits(dext[ds]);
-        if (br.over) return pf_inflate::CLAUSE_END;
-        if ((uint64_t)dist > at && (uint64_t)dist - at > sink.reach()) return pf_inflate::CLAUSE_DIST_BEFORE;
-        if ((uint64_t)len > max_syms - at) return CLAUSE_PIECE_LIMIT;
-        sink.copy(at, dist, len);
-        at += len;
-    }
-}
-
 template <typename In>
 PF_INF_HD inline uint64_t bit_pos(const BitReader<In> &br) { return (uint64_t)br.pos * 8 - (uint64_t)br.cnt; }
 
@@ -254,37 +227,9 @@ PF_INF_HD inline void decode_piece(const In &in, uint32_t n_bytes, uint64_t star
     uint32_t k = next_stop;
     if (start_bit >= limit_bit) r.link = LINK_LIMIT;   // (a piece without a complete block)
     else for (;;) {   // a turn consumes at least three bits
-        const uint32_t last = br.bits(1), type = br.bits(2);
-        if (br.over) break;
-        int clause = pf_inflate::CLAUSE_NONE;
-        if (type == 0) {
-            const uint32_t p0 = br.align();
-            if (br.over || (uint64_t)p0 + 4 > n_bytes) break;
-            const uint32_t len = br.bits(16), nlen = br.bits(16);
-            if (len != (~nlen & 0xffffu)) clause = pf_inflate::CLAUSE_STORED_LEN;
-            else {
-                const uint32_t src = br.align();
-                if (len > n_bytes - src) break;
-                if ((uint64_t)len > max_syms - at) clause = CLAUSE_PIECE_LIMIT;
-                else {
-                    sink.stored(in, src, at, len);
-                    br.pos = src + len;
-                    at += len;
-                    ++blk.stored;
-                }
-            }
-        } else if (type == 1) {
-            pf_inflate::build_fixed(w, lane, n_lanes, sync);
-            ++blk.fixed;
-            clause = piece_codes(br, w, sink, at, max_syms);
-        } else if (type == 2) {
-            clause = pf_inflate::read_dynamic(br, w, lane, n_lanes, sync);
-            ++blk.dynamic;
-            if (!clause) clause = piece_codes(br, w, sink, at, max_syms);
-        } else {
-            clause = pf_inflate::CLAUSE_BTYPE3;
-        }
-        if (clause == pf_inflate::CLAUSE_END) break;   // the bits ran out inside the block
+        uint32_t last = 0;
+        const int clause = pf_inflate::inflate_block(br, in, n_bytes, sink, at, max_syms, w, lane, n_lanes, sync, blk, last);
+        if (clause == pf_inflate::CLAUSE_END || clause == pf_inflate::CLAUSE_STORED_PAST) break;   // the bits ran out at or inside the block: tail
         if (clause) { r.clause = (uint32_t)clause; r.link = LINK_CLAUSE; break; }
         r.end_bit = bit_pos(br);
         r.symbols = at;
@@ -305,8 +250,15 @@ PF_INF_HD inline void decode_piece(const In &in, uint32_t n_bytes, uint64_t star
 PF_INF_HD inline uint32_t crc_append(uint32_t raw_so_far, uint32_t raw_next, uint64_t len_next) {
     return pf_inflate::crc_mul(pf_inflate::crc_x8n(len_next), raw_so_far) ^ raw_next;
 }
-PF_INF_HD inline uint32_t crc_value(uint32_t raw, uint64_t len) {
-    return raw ^ pf_inflate::crc_mul(pf_inflate::crc_x8n(len), 0xffffffffu) ^ 0xffffffffu;
+// (the CRC-32 itself is pf_inflate::crc_finish of the last register and the member's length)
+
+// ---- the byte a marker v of a piece at `place` stands for: from the staging array in front of the piece, or from the window[0, n_window)
+// in front of the call (a marker that reaches in front of both was refused by the decode stage) ----
+PF_INF_HD inline uint32_t behind(const uint16_t *stage, const uint8_t *window, uint32_t n_window, uint64_t place, uint32_t v) {
+    const int64_t q = (int64_t)place - (int64_t)RING + (int64_t)(v & 0x7fffu);
+    if (q >= 0) return (uint32_t)stage[q] & 0xffu;
+    const int64_t wq = (int64_t)n_window + q;
+    return wq >= 0 ? (uint32_t)window[wq] : 0u;
 }
 
 }  // namespace pf_gunzip

@@ -94,11 +94,7 @@ struct Stats {
     uint64_t pieces_found = 0, pieces_live = 0, pieces_dead = 0, markers = 0, blocks_stored = 0, blocks_fixed = 0, blocks_dynamic = 0, bytes_in = 0, bytes_out = 0;
 };
 
-struct HostIn {
-    const uint8_t *p;
-    uint8_t byte(uint32_t i) const { return p[i]; }
-    uint8_t raw(uint32_t i) const { return p[i]; }
-};
+using pf_inflate::HostIn;
 
 inline uint32_t piece_stride(uint32_t piece_bytes) { return piece_bytes == 0 ? PIECE_DEFAULT : piece_bytes < PIECE_MIN ? PIECE_MIN : piece_bytes; }
 // the first nominal boundary behind start_bit, and how many there are in front of the end of the bytes
@@ -175,17 +171,11 @@ inline void inflate_call(const uint8_t *comp, uint64_t n_bytes, uint64_t start_b
         }
     }
     // window: the markers of every piece's last 32 Ki symbols, the pieces in order
-    auto behind = [&](uint64_t place_k, uint16_t v) -> uint16_t {   // the byte a marker of a piece at place_k stands for
-        const int64_t q = (int64_t)place_k - (int64_t)RING + (int64_t)(v & 0x7fff);
-        if (q >= 0) return (uint16_t)(stage[(size_t)q] & 0xff);
-        const int64_t wq = (int64_t)n_window + q;
-        return wq >= 0 ? window[wq] : 0;
-    };
     for (size_t k = 0; k < live.size(); ++k) {
         const uint64_t n = place[k + 1] - place[k];
         for (uint64_t s = n > RING ? n - RING : 0; s < n; ++s) {
             uint16_t &v = stage[place[k] + s];
-            if (v & MARKER) v = (uint16_t)(RESOLVED | behind(place[k], v));   // (RESOLVED keeps it counted below)
+            if (v & MARKER) v = (uint16_t)(RESOLVED | behind(stage.data(), window, n_window, place[k], v));   // (RESOLVED keeps it counted below)
         }
     }
     // resolve: every remaining marker by the same gather
@@ -195,7 +185,7 @@ inline void inflate_call(const uint8_t *comp, uint64_t n_bytes, uint64_t start_b
         while (i >= place[k + 1]) ++k;
         const uint16_t v = stage[i];
         if (v & (MARKER | RESOLVED)) ++st.markers;
-        out[i] = (uint8_t)((v & MARKER) ? behind(place[k], v) : (v & 0xff));
+        out[i] = (uint8_t)((v & MARKER) ? behind(stage.data(), window, n_window, place[k], v) : (v & 0xff));
     }
     if (stats) { st.bytes_out = total; st.bytes_in = (res.end_bit + 7) / 8 - start_bit / 8; *stats = st; }
     res.out_bytes = total;
@@ -279,7 +269,7 @@ struct Stream {
                 const uint32_t crc = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
                 const uint32_t isize = (uint32_t)t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
                 if ((uint32_t)len != isize) return refuse(pf_inflate::CLAUSE_LENGTH, carry_off + 4);
-                if (crc_value(crc_raw, len) != crc) return refuse(pf_inflate::CLAUSE_CRC, carry_off);
+                if (pf_inflate::crc_finish(crc_raw, len) != crc) return refuse(pf_inflate::CLAUSE_CRC, carry_off);
                 drop(8);
                 ++member;
                 state = HEADER;

@@ -4,9 +4,10 @@
 //             CRC; an exclusive scan of ISIZE (pf_scan.hip) gives every member's place in the output and the total.  One host wait
 //             here: the total (the caller's buffer may be too small) and the smallest member refused so far.
 //   inflate   k_inflate, one wavefront per member.  The decode is serial within a member, so all 64 lanes run pf_inflate::inflate_stream
-//             (pf_inflate_core.hpp, the code the host rule runs) with the same arguments; what is not serial is shared by the lanes:
-//             the look-up tables of a block's codes (build_huff), the match copies (LaneOut::copy, up to 258 bytes, distance < length
-//             as a repeating pattern), stored blocks (LaneOut::stored), the refill of the input window, the CRC and the final write.
+//             (pf_inflate_core.hpp, the decoder the host rule and K-GUNZIP run) with the same arguments; what is not serial is shared by
+//             the lanes: the look-up tables of a block's codes (build_huff), the match copies (LaneOut::copy, up to 258 bytes, distance
+//             < length as a repeating pattern), stored blocks (LaneOut::stored), the refill of the input window (GzIn, pf_gz_dev.hpp,
+//             which K-GUNZIP shares), the CRC and the final write.
 //             The member's text is assembled in LDS (64 KiB) and written once, in whole dwords where the destination allows; with the
 //             tables (4 KiB) and the input window (1 KiB) a block takes 70 KiB, two blocks a CU.  (The form that writes the text to
 //             global memory as it is produced was not built: a copy would wait for the stores of the match before it -- DESIGN.md.)
@@ -22,23 +23,13 @@
 
 #include "../../include/ploidyfrost_hip.h"
 #include "pf_ctx.hpp"
+#include "pf_gz_dev.hpp"
 #include "pf_inflate_rule.hpp"
 #include "pf_scan.hpp"
 
-#define PF_HIP(call)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            pf::CtxErr{ctx} = std::string(#call) + ": " + hipGetErrorString(e_);                   \
-            return PF_ERR_HIP;                                                               \
-        }                                                                                    \
-    } while (0)
-
 namespace pf {
 
-constexpr int INF_WAVE = 64;
-constexpr uint32_t INF_WINDOW = 1024;      // bytes of the payload held in LDS
-constexpr uint32_t INF_KEEP = 64;          // of them behind the byte asked for (the reader steps back by at most two)
+constexpr int INF_WAVE = GZ_WAVE;
 constexpr uint32_t INF_TABLE_LEN = 100, INF_TABLE_ORDER = 101;   // member_off itself is wrong: not clauses of the rule
 constexpr unsigned long long INF_NO_BAD = ~0ull;
 
@@ -58,11 +49,6 @@ struct InflateArgs {
     unsigned long long *blocks;   // stored, fixed, dynamic
 };
 
-struct GlobalBytes {
-    const uint8_t *p;
-    __device__ uint32_t operator[](uint32_t i) const { return p[i]; }
-};
-
 __global__ __launch_bounds__(256) void k_inflate_headers(const InflateArgs a) {
     const uint64_t m = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (m > a.n_members) return;
@@ -74,7 +60,7 @@ __global__ __launch_bounds__(256) void k_inflate_headers(const InflateArgs a) {
         mem.clause = INF_TABLE_ORDER;
     } else {
         pf_inflate::Header h;
-        mem.clause = (uint32_t)pf_inflate::parse_member_bytes(GlobalBytes{a.comp + off}, end - off, h);   // (reads [off, end) only)
+        mem.clause = (uint32_t)pf_inflate::parse_member_bytes(GzBytes{a.comp + off}, end - off, h);   // (reads [off, end) only)
         if (!mem.clause && (uint64_t)h.member_len != end - off) mem.clause = INF_TABLE_LEN;
         if (!mem.clause) {
             mem.payload_off = h.payload_off;
@@ -88,49 +74,13 @@ __global__ __launch_bounds__(256) void k_inflate_headers(const InflateArgs a) {
     if (mem.clause) atomicMin(a.bad, (unsigned long long)m);
 }
 
-struct WaveSync {
-    __host__ __device__ void operator()() const {
-#if defined(__HIP_DEVICE_COMPILE__)
-        __syncthreads();
-#endif
-    }
-};
-
-// the payload p[0, n_in) through a window in LDS; every lane of the wavefront asks for the same byte at the same time
-struct LaneIn {
-    const uint8_t *p;
-    uint32_t n_in, lane;
-    uint32_t *win;              // INF_WINDOW / 4 dwords
-    mutable uint32_t base;      // the window holds payload bytes [base - shift, base - shift + INF_WINDOW), base a multiple of 4
-    uint32_t shift;             // p's distance from the dword boundary in front of it
-    __device__ void refill(uint32_t j) const {   // j = i + shift
-        __syncthreads();
-        base = (j >= INF_KEEP ? j - INF_KEEP : 0u) & ~3u;
-        const uint8_t *q = p - shift;   // a dword boundary; nothing in front of p is read
-        for (uint32_t k = lane; k < INF_WINDOW / 4; k += INF_WAVE) {
-            const uint32_t jj = base + 4 * k;
-            uint32_t v = 0;
-            if (jj >= shift && (uint64_t)jj + 4 <= (uint64_t)shift + n_in) {
-                v = *reinterpret_cast<const uint32_t *>(q + jj);
-            } else {
-                for (uint32_t b = 0; b < 4; ++b)
-                    if (jj + b >= shift && jj + b < shift + n_in) v |= (uint32_t)q[jj + b] << (8 * b);
-            }
-            win[k] = v;
-        }
-        __syncthreads();
-    }
-    __device__ uint8_t byte(uint32_t i) const {   // i < n_in
-        const uint32_t j = i + shift;
-        if (j - base >= INF_WINDOW) refill(j);
-        return reinterpret_cast<const uint8_t *>(win)[j - base];
-    }
-};
-
 // the member's text in LDS; the core has tested every range
 struct LaneOut {
+    typedef uint32_t Pos;
+    static constexpr int BEYOND = pf_inflate::CLAUSE_OUT_BEYOND;
     uint8_t *o;
     uint32_t lane;
+    __device__ uint32_t reach() const { return 0; }   // a member refers to nothing in front of itself
     __device__ void put(uint32_t at, uint8_t b) { if (lane == 0) o[at] = b; }
     __device__ void copy(uint32_t at, uint32_t dist, uint32_t len) {
         __syncthreads();   // the bytes in front of `at` are in place
@@ -141,19 +91,14 @@ struct LaneOut {
             for (uint32_t i = lane; i < len; i += INF_WAVE) o[at + i] = src[i % dist];   // only bytes in front of `at` are read
         }
     }
-    __device__ void stored(const LaneIn &in, uint32_t src, uint32_t at, uint32_t len) {   // src + len <= n_in
-        for (uint32_t i = lane; i < len; i += INF_WAVE) o[at + i] = in.p[src + i];
+    __device__ void stored(const GzIn &in, uint32_t src, uint32_t at, uint32_t len) {   // src + len <= n_in
+        for (uint32_t i = lane; i < len; i += INF_WAVE) o[at + i] = in.raw(src + i);
     }
-};
-
-struct TextBytes {
-    const uint8_t *p;
-    __device__ uint32_t operator[](uint32_t i) const { return p[i]; }
 };
 
 __global__ __launch_bounds__(INF_WAVE) void k_inflate(const InflateArgs a) {
     __shared__ uint32_t text32[pf_inflate::MAX_ISIZE / 4];
-    __shared__ uint32_t window[INF_WINDOW / 4];
+    __shared__ uint32_t window[GZ_WINDOW / 4];
     __shared__ pf_inflate::Work work;
     const uint64_t m = blockIdx.x;
     const uint32_t lane = threadIdx.x;
@@ -162,15 +107,14 @@ __global__ __launch_bounds__(INF_WAVE) void k_inflate(const InflateArgs a) {
     const uint32_t isize = (uint32_t)a.isize[m];
     uint8_t *text = reinterpret_cast<uint8_t *>(text32);
     const uint8_t *payload = a.comp + a.member_off[m] + mem.payload_off;
-    LaneIn in{payload, mem.n_in, lane, window, 0u, (uint32_t)((uintptr_t)payload & 3u)};
-    in.refill(in.shift);
+    const GzIn in(payload, mem.n_in, lane, window, 0u);
     LaneOut out{text, lane};
     pf_inflate::Blocks blocks;
     uint32_t produced = 0;
-    int clause = pf_inflate::inflate_stream(in, mem.n_in, out, isize, work, lane, (uint32_t)INF_WAVE, WaveSync{}, blocks, produced);
+    int clause = pf_inflate::inflate_stream(in, mem.n_in, out, isize, work, lane, (uint32_t)INF_WAVE, GzSync{}, blocks, produced);
     __syncthreads();
     if (!clause) {
-        const uint32_t raw = pf_inflate::crc_raw(TextBytes{text}, pf_inflate::slice_begin(isize, INF_WAVE, lane), pf_inflate::slice_end(isize, INF_WAVE, lane));
+        const uint32_t raw = pf_inflate::crc_raw(GzBytes{text}, pf_inflate::slice_begin(isize, INF_WAVE, lane), pf_inflate::slice_end(isize, INF_WAVE, lane));
         uint32_t sum = pf_inflate::slice_share(raw, isize, INF_WAVE, lane);
         for (int d = 32; d >= 1; d >>= 1) sum ^= (uint32_t)__shfl_xor((int)sum, d, INF_WAVE);
         if (pf_inflate::crc_finish(sum, isize) != mem.crc) clause = pf_inflate::CLAUSE_CRC;
@@ -200,14 +144,6 @@ __global__ __launch_bounds__(INF_WAVE) void k_inflate(const InflateArgs a) {
     }
 }
 
-struct InflateTimed {   // brackets everything one call launches as one timed launch of PF_K_INFLATE
-    pf_ctx *ctx;
-    explicit InflateTimed(pf_ctx *c) : ctx(c) { ctx_begin(ctx, PF_K_INFLATE); }
-    ~InflateTimed() { ctx_end(ctx); }
-};
-
-static size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 }  // namespace pf
 
 using namespace pf;
@@ -224,7 +160,7 @@ extern "C" int pf_inflate_bgzf(pf_ctx *ctx, const uint8_t *comp, uint64_t n_byte
     if (!comp || !member_off) return refuse("comp and member_off are needed");
     if (n_members > 0x7FFFFFFFull) return refuse("a call holds fewer than 2^31 members");
     PF_HIP(hipSetDevice(ctx->device));
-    InflateTimed timed(ctx);
+    Timed timed(ctx, PF_K_INFLATE);
 
     // ---- stage what the caller holds on the host ----
     DevTmp<uint8_t> d_comp_;

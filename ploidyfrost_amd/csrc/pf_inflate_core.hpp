@@ -1,10 +1,12 @@
-// The part of K-INFLATE that one lane executes, for the kernel (pf_inflate.hip) and the host rule (pf_inflate_rule.hpp) alike: the clause
-// enum, the BGZF member header, the bit reader, the code tables from code lengths, the symbol decode, the block loop with every
-// bounds test, and the CRC-32 pieces.  Nothing here allocates, and nothing here touches memory but through the three policies:
-//   In     byte(i): compressed byte i of the payload for i < n_in (the reader never asks for another);
-//   Out    put(at, byte), copy(at, distance, length), stored(in, src, at, length): called only after the bounds tests below have passed
-//          (at + length <= isize, distance <= at, src + length <= n_in);
-//   Work   the tables of one member (LDS on the device, the stack on the host).
+// The deflate decoder that one lane executes, for both gzip readers and for kernel and host rule alike: K-INFLATE (pf_inflate.hip,
+// pf_inflate_rule.hpp) drives it over one BGZF member (inflate_stream below), K-GUNZIP (pf_gunzip.hip, pf_gunzip_rule.hpp) over one piece
+// of a plain gzip stream (pf_gunzip_core.hpp: decode_piece).  Here are the clause enum, the BGZF member header, the bit reader, the
+// code tables from code lengths, the symbol loop (inflate_codes) and the block step (inflate_block) with every bounds test, and the
+// CRC-32 pieces.  Nothing here allocates, and nothing here touches memory but through the three policies:
+//   In     byte(i): compressed byte i of the payload for i < n_in (the reader never asks for another); raw(i): the same byte for a
+//          stored block's copy, which every lane reads at a place of its own;
+//   Sink   where the text goes and what bounds it (described in front of inflate_codes);
+//   Work   the tables of one block (LDS on the device, the stack on the host).
 // lane / n_lanes: the caller's place among those that execute the same call together (host: 0 of 1; kernel: a wavefront's 64 lanes,
 // all with the same arguments).  What is serial is done by every lane alike; the table fill is shared.
 //
@@ -142,7 +144,7 @@ PF_INF_HD inline uint32_t slice_share(uint32_t raw, uint32_t n, uint32_t n_lanes
     return crc_mul(crc_x8n((uint64_t)slice_len(n, n_lanes) * (n_lanes - 1 - j)), raw);
 }
 // the CRC-32 of n bytes from the sum (xor) of the shares: the initial ffffffff moved on by n bytes, and the final inversion
-PF_INF_HD inline uint32_t crc_finish(uint32_t raw_sum, uint32_t n) { return raw_sum ^ crc_mul(crc_x8n(n), 0xffffffffu) ^ 0xffffffffu; }
+PF_INF_HD inline uint32_t crc_finish(uint32_t raw_sum, uint64_t n) { return raw_sum ^ crc_mul(crc_x8n(n), 0xffffffffu) ^ 0xffffffffu; }
 
 // ---- the bit reader: bytes are fetched only when a bit of them is needed, and never beyond n_in ----
 template <typename In>
@@ -309,9 +311,20 @@ PF_INF_HD inline void build_fixed(Work &w, uint32_t lane, uint32_t n_lanes, cons
     (void)build_huff(w.dist, w.lengths + MAX_LIT, 32, lane, n_lanes, sync);
 }
 
-// the symbols of one fixed or dynamic block
-template <typename In, typename Out>
-PF_INF_HD inline int inflate_codes(BitReader<In> &br, const Work &w, Out &out, uint32_t &at, uint32_t isize) {
+// ---- the decoder: one symbol loop and one block step, for every caller, through a sink ----
+// A Sink says where the text goes and what bounds it:
+//   Pos                  the type of a place in the text: uint32_t for a BGZF member (K-INFLATE's arithmetic stays 32-bit), uint64_t for
+//                        a piece of a plain gzip stream
+//   BEYOND               the clause for text past the bound: CLAUSE_OUT_BEYOND for a member, pf_gunzip::CLAUSE_PIECE_LIMIT for a piece
+//   reach()              bytes of text in front of place 0 that a distance may refer to (0 for a member)
+//   put(at, byte), copy(at, distance, length), stored(in, src, at, length)
+//                        called only after the tests below have passed: at + length <= bound, distance <= at + reach(),
+//                        src + length <= n_in (stored reads the payload through in.raw)
+
+// the symbols of one fixed or dynamic block; the four tables of RFC 1951, 3.2.5
+template <typename In, typename Sink>
+PF_INF_HD inline int inflate_codes(BitReader<In> &br, const Work &w, Sink &sink, typename Sink::Pos &at, typename Sink::Pos bound) {
+    typedef typename Sink::Pos Pos;
     const uint16_t lbase[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
     const uint8_t lext[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
     const uint16_t dbase[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
@@ -321,8 +334,8 @@ PF_INF_HD inline int inflate_codes(BitReader<In> &br, const Work &w, Out &out, u
         if (br.over) return CLAUSE_END;   // (bits that are not there decide nothing)
         if (sym < 0) return CLAUSE_BAD_CODE;
         if (sym < 256) {
-            if (at >= isize) return CLAUSE_OUT_BEYOND;
-            out.put(at, (uint8_t)sym);
+            if (at >= bound) return Sink::BEYOND;
+            sink.put(at, (uint8_t)sym);
             ++at;
             continue;
         }
@@ -336,11 +349,48 @@ PF_INF_HD inline int inflate_codes(BitReader<In> &br, const Work &w, Out &out, u
         if (ds >= 30) return CLAUSE_DIST_SYM;
         const uint32_t dist = (uint32_t)dbase[ds] + br.bits(dext[ds]);
         if (br.over) return CLAUSE_END;
-        if (dist > at) return CLAUSE_DIST_BEFORE;
-        if (len > isize - at) return CLAUSE_OUT_BEYOND;
-        out.copy(at, dist, len);
+        if ((Pos)dist > at && (Pos)dist - at > sink.reach()) return CLAUSE_DIST_BEFORE;
+        if ((Pos)len > bound - at) return Sink::BEYOND;
+        sink.copy(at, dist, len);
         at += len;
     }
+}
+
+// One block from its BFINAL bit on: its text through the sink, `at` moved on, its kind counted, *last = BFINAL.  Returns the clause;
+// the two of them that say where the bits ran out are the caller's to judge: CLAUSE_END (at the header or inside the block) and
+// CLAUSE_STORED_PAST (a stored block past the payload).
+template <typename In, typename Sink, typename Sync>
+PF_INF_HD inline int inflate_block(BitReader<In> &br, const In &in, uint32_t n_in, Sink &sink, typename Sink::Pos &at, typename Sink::Pos bound, Work &w,
+                                   uint32_t lane, uint32_t n_lanes, const Sync &sync, Blocks &blocks, uint32_t &last) {
+    typedef typename Sink::Pos Pos;
+    last = br.bits(1);
+    const uint32_t type = br.bits(2);
+    if (br.over) return CLAUSE_END;
+    if (type == 0) {
+        const uint32_t p0 = br.align();
+        if (br.over || (uint64_t)p0 + 4 > n_in) return CLAUSE_STORED_PAST;
+        const uint32_t len = br.bits(16), nlen = br.bits(16);
+        if (len != (~nlen & 0xffffu)) return CLAUSE_STORED_LEN;
+        const uint32_t src = br.align();
+        if (len > n_in - src) return CLAUSE_STORED_PAST;
+        if ((Pos)len > bound - at) return Sink::BEYOND;
+        sink.stored(in, src, at, len);
+        br.pos = src + len;
+        at += len;
+        ++blocks.stored;
+        return CLAUSE_NONE;
+    }
+    if (type == 1) {
+        build_fixed(w, lane, n_lanes, sync);
+        ++blocks.fixed;
+        return inflate_codes(br, w, sink, at, bound);
+    }
+    if (type == 2) {
+        const int clause = read_dynamic(br, w, lane, n_lanes, sync);
+        ++blocks.dynamic;
+        return clause ? clause : inflate_codes(br, w, sink, at, bound);
+    }
+    return CLAUSE_BTYPE3;
 }
 
 // One member's deflate stream: n_in payload bytes -> exactly isize bytes.  *produced = bytes written (<= isize on every path).
@@ -353,31 +403,8 @@ PF_INF_HD inline int inflate_stream(const In &in, uint32_t n_in, Out &out, uint3
     produced = 0;
     int clause = CLAUSE_NONE;
     for (;;) {   // a turn consumes at least three bits
-        const uint32_t last = br.bits(1), type = br.bits(2);
-        if (br.over) { clause = CLAUSE_END; break; }
-        if (type == 0) {
-            const uint32_t p0 = br.align();
-            if (br.over || p0 + 4 > n_in) { clause = CLAUSE_STORED_PAST; break; }
-            const uint32_t len = br.bits(16), nlen = br.bits(16);
-            if (len != (~nlen & 0xffffu)) { clause = CLAUSE_STORED_LEN; break; }
-            const uint32_t src = br.align();
-            if (len > n_in - src) { clause = CLAUSE_STORED_PAST; break; }
-            if (len > isize - at) { clause = CLAUSE_OUT_BEYOND; break; }
-            out.stored(in, src, at, len);
-            br.pos = src + len;
-            at += len;
-            ++blocks.stored;
-        } else if (type == 1) {
-            build_fixed(w, lane, n_lanes, sync);
-            ++blocks.fixed;
-            clause = inflate_codes(br, w, out, at, isize);
-        } else if (type == 2) {
-            clause = read_dynamic(br, w, lane, n_lanes, sync);
-            ++blocks.dynamic;
-            if (!clause) clause = inflate_codes(br, w, out, at, isize);
-        } else {
-            clause = CLAUSE_BTYPE3;
-        }
+        uint32_t last = 0;
+        clause = inflate_block(br, in, n_in, out, at, isize, w, lane, n_lanes, sync, blocks, last);
         if (clause || last) break;
     }
     produced = at;

@@ -71,17 +71,23 @@ inline int file_clause_gz(const uint8_t *first, uint64_t n_first, uint64_t file_
 }
 
 // ---- stream: the core over plain memory ----
-struct HostIn {
+struct HostIn {   // (for pf_gunzip_rule.hpp as well)
     const uint8_t *p;
     uint8_t byte(uint32_t i) const { return p[i]; }
+    uint8_t raw(uint32_t i) const { return p[i]; }
 };
-struct HostOut {
+struct HostOut {   // a member's text: nothing in front of it, places of 32 bits
+    typedef uint32_t Pos;
+    static constexpr int BEYOND = CLAUSE_OUT_BEYOND;
     uint8_t *p;
+    uint32_t reach() const { return 0; }
     void put(uint32_t at, uint8_t b) { p[at] = b; }
     void copy(uint32_t at, uint32_t dist, uint32_t len) {   // dist < len: the pattern repeats
         for (uint32_t i = 0; i < len; ++i) p[at + i] = p[at - dist + (i % dist)];
     }
-    void stored(const HostIn &in, uint32_t src, uint32_t at, uint32_t len) { if (len) memcpy(p + at, in.p + src, len); }
+    void stored(const HostIn &in, uint32_t src, uint32_t at, uint32_t len) {
+        for (uint32_t i = 0; i < len; ++i) p[at + i] = in.raw(src + i);
+    }
 };
 
 inline uint32_t crc32(const uint8_t *bytes, uint64_t n) {

@@ -159,11 +159,6 @@ __global__ __launch_bounds__(MASK_BLOCK) void k_mask_changed(const uint64_t *__r
 
 // ---- host side ----
 // brackets everything one call launches as one timed launch of PF_K_MASK
-struct MaskTimed {
-    pf_ctx *ctx;
-    explicit MaskTimed(pf_ctx *c) : ctx(c) { ctx_begin(ctx, PF_K_MASK); }
-    ~MaskTimed() { ctx_end(ctx); }
-};
 
 // the flag phase alone over the resident table (K-MASKCOUNT launches it as well: pf_reads_dev.hpp)
 void mask_flag_launch(pf_ctx *ctx, const char *text, uint64_t n, uint64_t n_tiles, const uint64_t *start, uint64_t *bad, uint32_t low, uint32_t up,
@@ -243,7 +238,7 @@ extern "C" int pf_mask_reads(pf_ctx *ctx, const char *text, uint64_t n_bytes, co
     if (n_bytes > MASK_MAX_BYTES) return refuse("pf_mask_reads: the text is longer than 2^40 bytes");
     if (n_bytes == 0 && n_reads == 0) { mask_stats_out(stats, 0, h); return PF_OK; }
     PF_HIP(hipSetDevice(ctx->device));
-    MaskTimed timed(ctx);
+    Timed timed(ctx, PF_K_MASK);
     // the table and the counters
     const size_t off_bytes = up256((size_t)n_reads * 8), len_bytes = up256((size_t)n_reads * 4);
     char *tw = static_cast<char *>(ctx_ws(ctx, WS_MASK_TABLE, off_bytes + len_bytes + 256));
@@ -285,7 +280,6 @@ extern "C" int pf_mask_reads(pf_ctx *ctx, const char *text, uint64_t n_bytes, co
     return PF_OK;
 }
 
-
 extern "C" int pf_mask_fastq(pf_ctx *ctx, const char *text, uint64_t n_bytes, int final, uint32_t low, uint32_t up, char *out,
                              uint64_t *bytes_used, pf_mask_stats *stats, uint64_t *bad_record) {
     if (!ctx) return PF_ERR_ARG;
@@ -303,7 +297,7 @@ extern "C" int pf_mask_fastq(pf_ctx *ctx, const char *text, uint64_t n_bytes, in
     mask_stats_out(stats, 0, h);
     if (n_bytes == 0) return PF_OK;
     PF_HIP(hipSetDevice(ctx->device));
-    MaskTimed timed(ctx);
+    Timed timed(ctx, PF_K_MASK);
     const char *dt = nullptr;
     { const int rc = mask_stage_text(ctx, text, n_bytes, &dt); if (rc) return rc; }
     FastqIndex ix;

@@ -101,11 +101,6 @@ __global__ __launch_bounds__(MASK_BLOCK) void k_maskcount_insert(const MaskCount
 }
 
 // ---- host side ----
-struct MaskCountTimed {   // brackets everything one call launches as one timed launch of PF_K_MASKCOUNT
-    pf_ctx *ctx;
-    explicit MaskCountTimed(pf_ctx *c) : ctx(c) { ctx_begin(ctx, PF_K_MASKCOUNT); }
-    ~MaskCountTimed() { ctx_end(ctx); }
-};
 
 // a resident table, an open count on both strands, the same k: each missing piece by name
 int maskcount_needs(pf_ctx *ctx, const char *who) {
@@ -184,7 +179,7 @@ extern "C" int pf_maskcount_reads(pf_ctx *ctx, const char *text, uint64_t n_byte
     h.bad_entry = MASK_NO_RECORD;
     if (n_bytes == 0 && n_reads == 0) { maskcount_stats_out(stats, S, 0, h); return PF_OK; }
     PF_HIP(hipSetDevice(ctx->device));
-    MaskCountTimed timed(ctx);
+    Timed timed(ctx, PF_K_MASKCOUNT);
     // the table of reads and the counters
     const size_t off_bytes = up256((size_t)n_reads * 8), len_bytes = up256((size_t)n_reads * 4);
     char *tw = static_cast<char *>(ctx_ws(ctx, WS_MASK_TABLE, off_bytes + len_bytes + 256));
@@ -234,7 +229,7 @@ extern "C" int pf_maskcount_fastq(pf_ctx *ctx, const char *text, uint64_t n_byte
     if (n_bytes == 0) { maskcount_stats_out(stats, S, 0, h); return PF_OK; }
     if (stats) *stats = pf_maskcount_stats{};
     PF_HIP(hipSetDevice(ctx->device));
-    MaskCountTimed timed(ctx);
+    Timed timed(ctx, PF_K_MASKCOUNT);
     const char *dt = nullptr;
     { const int rc = mask_stage_text(ctx, text, n_bytes, &dt); if (rc) return rc; }
     FastqIndex ix;

@@ -11,17 +11,6 @@
 #include "pf_mask_rule.hpp"
 #include "pf_scan.hpp"
 
-#ifndef PF_HIP
-#define PF_HIP(call)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            pf::CtxErr{ctx} = std::string(#call) + ": " + hipGetErrorString(e_);                   \
-            return PF_ERR_HIP;                                                               \
-        }                                                                                    \
-    } while (0)
-#endif
-
 namespace pf {
 
 constexpr int MASK_BLOCK = 256;
@@ -199,7 +188,6 @@ static __global__ __launch_bounds__(MASK_BLOCK) void k_fq_records(const char *__
 void mask_flag_launch(pf_ctx *ctx, const char *text, uint64_t n, uint64_t n_tiles, const uint64_t *start, uint64_t *bad, uint32_t low, uint32_t up,
                       MaskCounts *counts);
 
-static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 constexpr uint64_t MASK_MAX_BYTES = 1ull << 40;   // every grid of a call stays far below 2^31 blocks
 
 // all counters 0, no offender

@@ -133,11 +133,6 @@ __global__ __launch_bounds__(TRIM_BLOCK) void k_trim_copy(const TrimCopyArgs a) 
 }
 
 // ---- host side ----
-struct TrimTimed {   // brackets everything one call launches as one timed launch of PF_K_TRIM
-    pf_ctx *ctx;
-    explicit TrimTimed(pf_ctx *c) : ctx(c) { ctx_begin(ctx, PF_K_TRIM); }
-    ~TrimTimed() { ctx_end(ctx); }
-};
 
 // one chunk of a file (n_files = 1) or of each file of a pair (2); the arguments are arrays of n_files (out, out_bytes: 1 or 4)
 static int trim_core(pf_ctx *ctx, const char *who_c, int n_files, const char *const *text, const uint64_t *n_bytes, int final,
@@ -163,7 +158,7 @@ static int trim_core(pf_ctx *ctx, const char *who_c, int n_files, const char *co
     }
     if (n_bytes[0] == 0 && (n_files == 1 || n_bytes[1] == 0)) return PF_OK;
     PF_HIP(hipSetDevice(ctx->device));
-    TrimTimed timed(ctx);
+    Timed timed(ctx, PF_K_TRIM);
 
     // ---- index ----
     const char *dt[2] = {nullptr, nullptr};

@@ -82,11 +82,6 @@ __global__ __launch_bounds__(TRIM_BLOCK) void k_trimcount_scatter(const TrimScat
 }
 
 // ---- host side ----
-struct TrimCountTimed {   // brackets everything one call launches as one timed launch of PF_K_TRIMCOUNT
-    pf_ctx *ctx;
-    explicit TrimCountTimed(pf_ctx *c) : ctx(c) { ctx_begin(ctx, PF_K_TRIMCOUNT); }
-    ~TrimCountTimed() { ctx_end(ctx); }
-};
 
 struct TrimTable {   // what the table phase leaves on the device for the core
     int n_files = 1;
@@ -239,7 +234,7 @@ static int trim_table_call(pf_ctx *ctx, const char *who_c, int n_files, const ch
     trim_table_reset(n_files, bytes_used, n_records, stats, bad_record);
     if (trim_chunk_empty(n_files, n_bytes)) return PF_OK;
     PF_HIP(hipSetDevice(ctx->device));
-    TrimCountTimed timed(ctx);
+    Timed timed(ctx, PF_K_TRIMCOUNT);
     TrimTable T;
     { const int rc = trim_table_core(ctx, who, n_files, text, n_bytes, final, plan, T, bytes_used, n_records, stats, bad_record); if (rc) return rc; }
     if (T.n_reads) {
@@ -273,7 +268,7 @@ static int trim_count_call(pf_ctx *ctx, const char *who_c, bool masked, int n_fi
     trim_table_reset(n_files, bytes_used, nullptr, tstats, bad_record);
     if (trim_chunk_empty(n_files, n_bytes)) { stats_out(0); return PF_OK; }
     PF_HIP(hipSetDevice(ctx->device));
-    TrimCountTimed timed(ctx);
+    Timed timed(ctx, PF_K_TRIMCOUNT);
     TrimTable T;
     { const int rc = trim_table_core(ctx, who, n_files, text, n_bytes, final, plan, T, bytes_used, nullptr, tstats, bad_record); if (rc) return rc; }
     if (T.n_reads)   // a chunk that hands on no read launches nothing more and counts nothing

@@ -26,15 +26,6 @@
 #include "pf_runmulti_rule.hpp"
 #include "pf_scan.hpp"
 
-#define PF_HIP(call)                                                                         \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            pf::CtxErr{ctx} = std::string(#call) + ": " + hipGetErrorString(e_);             \
-            return PF_ERR_HIP;                                                               \
-        }                                                                                    \
-    } while (0)
-
 namespace pf {
 
 constexpr int UNION_BLOCK = 256, UNION_ITEMS = pf_runmulti::UNION_ITEMS, UNION_TILE = pf_runmulti::UNION_TILE;

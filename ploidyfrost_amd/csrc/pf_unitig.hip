@@ -415,11 +415,6 @@ void unitig_destroy(pf_ctx *ctx) {
     ctx->unitig = nullptr;
 }
 
-struct UniTimed {   // brackets everything one call launches as one timed launch of PF_K_UNITIG
-    pf_ctx *ctx;
-    explicit UniTimed(pf_ctx *c) : ctx(c) { ctx_begin(ctx, PF_K_UNITIG); }
-    ~UniTimed() { ctx_end(ctx); }
-};
 struct UniEvents {   // the stage times of pf_unitig_stats
     hipEvent_t e[PF_UNITIG_STAGES + 1] = {};
     ~UniEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
@@ -475,7 +470,7 @@ static int unitig_build_impl(pf_ctx *ctx, const uint64_t *kmers, uint64_t n, uin
     if (n && !kmers) return refuse("pf_unitig_build: kmers is needed");
     if ((uintptr_t)kmers & 7) return refuse("pf_unitig_build: kmers is not aligned");
     PF_HIP(hipSetDevice(ctx->device));
-    UniTimed timed(ctx);
+    Timed timed(ctx, PF_K_UNITIG);
     UniEvents ev;
     PF_HIP(ev.make());
     int stage = 0;
