@@ -76,6 +76,7 @@ enum pf_kernel {
     PF_K_GUNZIP, /* K-GUNZIP: everything one pf_inflate_gzip launches (find, count, chain, decode, window, resolve with the CRC), timed as one launch; unit: inflated bytes */
     PF_K_FASTA, /* K-FASTA: everything the index of one pf_fasta_index / pf_count_fasta / pf_maskcount_fasta / pf_color_fasta call launches (newlines, lines, words, scans, compact, table), timed as one launch; the core behind it is timed under its own kernel; unit: bytes of the chunk */
     PF_K_DEFLATE, /* K-DEFLATE: everything one pf_deflate_bgzf launches (deflate, scan of the members' sizes, pack), timed as one launch; unit: bytes of text */
+    PF_K_CLIP, /* K-CLIP: the kernels one pf_trim_fastq* / pf_trim_table_fastq* / pf_*_fastq*_trimmed call launches to clip adapters while a clip is open (one per file), timed as one launch inside the call's own; unit: records */
     PF_K_COUNT_
 };
 int pf_enable_timing(pf_ctx *, int on);
@@ -441,6 +442,36 @@ int pf_maskcount_fastq_trimmed(pf_ctx *, const char *text, uint64_t n_bytes, int
 int pf_maskcount_fastq_pair_trimmed(pf_ctx *, const char *text1, uint64_t n1, const char *text2, uint64_t n2, int final, const pf_trim_plan *plan,
                                     uint32_t low, uint32_t up, uint64_t bytes_used[2], pf_trim_stats trim_stats[2], pf_maskcount_stats *stats,
                                     uint64_t *bad_record);
+/* K-CLIP: adapter read-through clipped on the device in front of the steps of K-TRIM and K-TRIMCOUNT (csrc/pf_clip.hip; the rule:
+ * csrc/pf_clip_rule.hpp).  A clip is state on the context, opened and closed like a count.  While one is open, pf_trim_fastq,
+ * pf_trim_fastq_pair, pf_trim_table_fastq[_pair], pf_count_fastq[_pair]_trimmed and pf_maskcount_fastq[_pair]_trimmed clip first: the
+ * interval of a read starts as [0, clip end) instead of [0, n), clip end 0 = dropped, and they accept n_steps == 0.  With none open
+ * they are bit for bit what they were, the `no step is given` refusal included.  A single-ended call and file 1 of a pair use the
+ * adapters of side 0 and 1, file 2 those of side 0 and 2.
+ * The rule: a read of n bases with q[p] = (int)byte - phred, an adapter of m bases (16 .. 128 of ACGTacgt, at most 64 adapters).
+ * Offset o aligns adapter position j with read position o + j, -(m - 16) <= o <= n - 16; the overlap [max(0, o), min(n, o + m)) holds
+ * at least 16 positions.  Seed: the overlap holds 16 consecutive positions with at most `seed` (0 .. 8) mismatches, a read byte outside
+ * ACGTacgt being one.  Score: per overlap position 0 for a read byte outside ACGTacgt, +60206 for equal bases (case folded), else
+ * -10000 * max(q, 0); the best sum over contiguous sub-ranges, at least 0, must reach 100000 * score (1 .. 1000).  o* = the smallest
+ * passing offset over the side's adapters: none -- untouched; o* <= 0 -- dropped; else clip end o*.  PARITY with Trimmomatic's
+ * ILLUMINACLIP UNPINNED; knowingly different: the smallest offset over all adapters instead of the first found per adapter, no
+ * overlaps below 16, N a full seed mismatch, no palindrome mode.
+ * bases: the adapters one behind the other, adapter a = bases[adapter_off[a], adapter_off[a + 1]); adapter_off has n_adapters + 1
+ * entries; side[a] = 0 (both files), 1 or 2.  All [host]; they are copied.  A second begin, an end or a stats_get without a begin, and
+ * every value out of range: PF_ERR_ARG by name.  The statistics add up over all calls since the begin; a refused call adds nothing. */
+typedef struct pf_clip_stats {   /* [0]: single-ended calls and file 1 of a pair; [1]: file 2 */
+    uint64_t reads_clipped[2];      /* reads cut to o* > 0 bases */
+    uint64_t reads_dropped[2];      /* reads with o* <= 0 */
+    uint64_t bases_clipped[2];      /* n - clip end over both */
+    uint64_t candidates_scored[2];  /* (adapter, offset) pairs whose seed held: the ones scored */
+} pf_clip_stats;
+int pf_clip_begin(pf_ctx *, const char *bases, const uint32_t *adapter_off, const uint8_t *side, uint32_t n_adapters, uint32_t seed, uint32_t score);
+int pf_clip_stats_get(pf_ctx *, pf_clip_stats *stats);
+/* the clip ends of the last pf_trim_fastq* / pf_trim_table_fastq* / pf_*_trimmed call, before another one is made: clip_end [host|dev]
+ * receives n_records entries (at most the records that call took) of file 0 or 1 -- n untouched, 0 dropped.  A call that took no whole
+ * record (or was refused) clipped none: n_records == 0 is PF_OK, more is refused by name.  What `trim --trimlog` counts its last column from. */
+int pf_clip_last_ends(pf_ctx *, int file, uint32_t *clip_end, uint64_t n_records);
+int pf_clip_end(pf_ctx *);
 /* K-INFLATE: blocked gzip (BGZF: what bgzip, bcl2fastq2 and BCL Convert write) inflated on the device, where pf_*_fastq read their text.
  * The rule -- the member header, RFC 1951, the refusals by name -- is csrc/pf_inflate_rule.hpp; the decoder one lane runs is
  * csrc/pf_inflate_core.hpp, shared with the host.  One wavefront per member; the CRC-32 of every member's text is checked against

@@ -248,6 +248,31 @@ int pfh_trim_read(const char *qual, uint64_t n, const pf_trim_step *steps, uint3
 int pfh_trim_fastq_chunk(const char *text, uint64_t n, int final, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, char *out,
                          uint64_t *out_bytes, uint64_t *bytes_used, uint32_t *rec_begin, uint32_t *rec_len, uint64_t cap, uint64_t *n_records,
                          pf_trim_stats *stats, uint64_t *bad_record);
+/* ---- adapters clipped in front of the steps: `--adapters` (K-CLIP, pf_clip_begin .. pf_clip_end in ploidyfrost_hip.h) ----
+ * The rule: csrc/pf_clip_rule.hpp (parity with Trimmomatic's ILLUMINACLIP unpinned; palindrome mode, overlaps below 16 and IUPAC
+ * letters in adapters are not built).  pfh_reads_adapters(path, seed, score): the next pfh_trim_fastq or pfh_trim_fastq_pair of this
+ * thread reads the adapter file (FASTA; names ending in /1 or /2 choose the file of a pair, names starting with Prefix are skipped and
+ * counted), opens a clip on its context and clips every read before the steps; n_steps may then be 0; the call takes the switch back
+ * (path NULL or "": no clipping).  The file and the values are refused by name before a device context exists, with the path and the
+ * 1-based record.  pfh_reads_adapters_report: what that call reported -- usable adapters, skipped entries, the clip's statistics.
+ * The host's plain restatement of the rule, no device involved:
+ * pfh_clip_parse_adapters: the text of an adapter file into bases (upper case, at most bases_cap bytes are written: 64 * 128 always
+ * suffice), adapter_off (room for 65) and side (room for 64); returns the refusal (0 = none; pfh_clip_refusal_text names it) with
+ * *bad_record = the 1-based record (0: the file as a whole).  pfh_clip_read: one read of file file_side (1 or 2): *clip_end = n
+ * untouched, 0 dropped; *scored = the candidates whose seed held; -1 = the adapters or values are refused (pfh_last_error(NULL)).
+ * pfh_trim_fastq_chunk_clip: what pf_trim_fastq gives for one chunk while a clip is open (pfh_trim_fastq_chunk with adapters; clip:
+ * the statistics of this chunk, in place file_side - 1). */
+void pfh_reads_adapters(const char *path, uint32_t seed, uint32_t score);
+void pfh_reads_adapters_report(uint32_t *adapters, uint32_t *skipped, pf_clip_stats *stats);
+int pfh_clip_parse_adapters(const char *text, uint64_t n, char *bases, uint64_t bases_cap, uint32_t *adapter_off, uint8_t *side, uint32_t *n_adapters,
+                            uint32_t *skipped, uint64_t *bad_record);
+const char *pfh_clip_refusal_text(int refusal);
+int pfh_clip_read(const char *seq, const char *qual, uint64_t n, const char *bases, const uint32_t *adapter_off, const uint8_t *side, uint32_t n_adapters,
+                  uint32_t file_side, uint32_t seed, uint32_t score, uint32_t phred, uint32_t *clip_end, uint64_t *scored);
+int pfh_trim_fastq_chunk_clip(const char *text, uint64_t n, int final, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, const char *bases,
+                              const uint32_t *adapter_off, const uint8_t *side, uint32_t n_adapters, uint32_t file_side, uint32_t seed, uint32_t score, char *out,
+                              uint64_t *out_bytes, uint64_t *bytes_used, uint32_t *rec_begin, uint32_t *rec_len, uint64_t cap, uint64_t *n_records,
+                              pf_trim_stats *stats, pf_clip_stats *clip, uint64_t *bad_record);
 /* ---- raw reads to ploidy estimate in one process: step `1.trim` inside `run` / `run-multi` (K-TRIMCOUNT, pf_*_trimmed in ploidyfrost_hip.h) ----
  * The rule: csrc/pf_trimrun_rule.hpp.  pfh_run_fastq_trimmed: pfh_run_fastq on the raw reads -- both passes stream them and trim them on
  * the device on the way in, no trimmed file is written.  paired = 0: what `trim -i inputs... -o t.fq STEP...` followed by

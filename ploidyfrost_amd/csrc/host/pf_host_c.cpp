@@ -322,6 +322,62 @@ int pfh_mask_index_fastq(const char *text, uint64_t n, int final, uint64_t *byte
 }
 const char *pfh_mask_clause_text(int clause) { return pf_mask::clause_text(clause); }
 
+// ---- adapters clipped in front of the steps (K-CLIP) ---------------------------------------------------
+// `--adapters`: the switch of the next trim / run call of this thread, and what that call reported
+static thread_local pfh::ClipOptions g_reads_adapters;
+static thread_local pfh::ClipReport g_clip_report;
+void pfh_reads_adapters(const char *path, uint32_t seed, uint32_t score) {
+    g_reads_adapters = pfh::ClipOptions{};
+    g_reads_adapters.adapters = path ? path : "";
+    g_reads_adapters.seed = seed;
+    g_reads_adapters.score = score;
+}
+static pfh::ClipOptions take_reads_adapters() {
+    const pfh::ClipOptions c = g_reads_adapters;
+    g_reads_adapters = pfh::ClipOptions{};
+    g_clip_report = pfh::ClipReport{};
+    return c;
+}
+void pfh_reads_adapters_report(uint32_t *adapters, uint32_t *skipped, pf_clip_stats *stats) {
+    if (adapters) *adapters = g_clip_report.adapters;
+    if (skipped) *skipped = g_clip_report.skipped;
+    if (stats) *stats = g_clip_report.stats;
+}
+int pfh_clip_parse_adapters(const char *text, uint64_t n, char *bases, uint64_t bases_cap, uint32_t *adapter_off, uint8_t *side, uint32_t *n_adapters,
+                            uint32_t *skipped, uint64_t *bad_record) {
+    pf_clip::Adapters A;
+    uint64_t bad = 0;
+    const int c = pf_clip::parse_adapters(text ? text : "", text ? (size_t)n : 0, A, &bad);
+    if (n_adapters) *n_adapters = A.size();
+    if (skipped) *skipped = A.skipped;
+    if (bad_record) *bad_record = bad;
+    if (c) return c;
+    if (bases) memcpy(bases, A.bases.data(), std::min<uint64_t>(bases_cap, A.bases.size()));
+    if (adapter_off) memcpy(adapter_off, A.off.data(), A.off.size() * 4);
+    if (side && A.size()) memcpy(side, A.side.data(), A.size());
+    return 0;
+}
+const char *pfh_clip_refusal_text(int refusal) { return pf_clip::refusal_text(refusal); }
+static int clip_set_refused(const char *who, const char *bases, const uint32_t *off, const uint8_t *side, uint32_t n_adapters, uint32_t file_side, uint32_t seed,
+                            uint32_t score, uint32_t phred) {
+    uint32_t bad = 0;
+    const int c = pf_clip::set_clause(bases, off, side, n_adapters, seed, score, &bad);
+    if (c) { g_open_err = std::string(who) + ": " + pf_clip::refusal_text(c); return 1; }
+    if (file_side != 1 && file_side != 2) { g_open_err = std::string(who) + ": the side of a file is 1 or 2"; return 1; }
+    if (phred != 33 && phred != 64) { g_open_err = std::string(who) + ": " + pf_trim::refusal_text(pf_trim::REFUSE_PHRED) + ", not " + std::to_string(phred); return 1; }
+    return 0;
+}
+int pfh_clip_read(const char *seq, const char *qual, uint64_t n, const char *bases, const uint32_t *adapter_off, const uint8_t *side, uint32_t n_adapters,
+                  uint32_t file_side, uint32_t seed, uint32_t score, uint32_t phred, uint32_t *clip_end, uint64_t *scored) {
+    if (clip_set_refused("pfh_clip_read", bases, adapter_off, side, n_adapters, file_side, seed, score, phred)) return -1;
+    if (n > 0x7FFFFFFFull) { g_open_err = "pfh_clip_read: a read holds fewer than 2^31 bases"; return -1; }
+    uint64_t sc = 0;
+    const uint32_t e = pf_clip::clip_read(seq, qual, (uint32_t)n, bases, adapter_off, side, n_adapters, file_side, seed, score, phred, &sc);
+    if (clip_end) *clip_end = e;
+    if (scored) *scored = sc;
+    return 0;
+}
+
 // ---- reads quality-trimmed (K-TRIM) ------------------------------------------------------------------
 static pfh::TrimOptions trim_options(const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, const char *trimlog, uint64_t chunk_bytes) {
     pfh::TrimOptions opt;
@@ -333,14 +389,22 @@ static pfh::TrimOptions trim_options(const pf_trim_step *steps, uint32_t n_steps
     opt.gz_out = take_reads_gz_out();
     return opt;
 }
+// (the stream calls alone take the adapters switch: the restatements below take their adapters as arguments)
+static pfh::TrimOptions trim_stream_options(const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, const char *trimlog, uint64_t chunk_bytes,
+                                            const pfh::ClipOptions &clip) {
+    pfh::TrimOptions opt = trim_options(steps, n_steps, phred, trimlog, chunk_bytes);
+    opt.clip = clip;
+    return opt;
+}
 int pfh_trim_fastq(const char *const *inputs, uint32_t n_inputs, const char *out_path, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred,
                    const char *trimlog, uint64_t chunk_bytes, int device, pf_trim_stats *stats) {
+    const pfh::ClipOptions clip = take_reads_adapters();   // taken first: a refusal below does not leave the switch to the next call
     if (!out_path || (n_inputs && !inputs)) { g_open_err = "pfh_trim_fastq: inputs and output are needed"; return 1; }
     try {
         std::vector<std::string> in;
         for (uint32_t i = 0; i < n_inputs; ++i) in.push_back(inputs[i] ? inputs[i] : "");
         pf_trim_stats st = {};
-        const int rc = pfh::trim_fastq(in, out_path, trim_options(steps, n_steps, phred, trimlog, chunk_bytes), device, st, nullptr, g_open_err);
+        const int rc = pfh::trim_fastq(in, out_path, trim_stream_options(steps, n_steps, phred, trimlog, chunk_bytes, clip), device, st, nullptr, g_open_err, &g_clip_report);
         if (stats) *stats = st;
         return rc;
     } catch (const std::exception &e) {
@@ -350,6 +414,7 @@ int pfh_trim_fastq(const char *const *inputs, uint32_t n_inputs, const char *out
 }
 int pfh_trim_fastq_pair(const char *in1, const char *in2, const char *const *out_paths, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred,
                         const char *trimlog, uint64_t chunk_bytes, int device, pf_trim_stats *stats) {
+    const pfh::ClipOptions clip = take_reads_adapters();   // taken first: a refusal below does not leave the switch to the next call
     if (!in1 || !in2 || !out_paths || !out_paths[0] || !out_paths[1] || !out_paths[2] || !out_paths[3]) {
         g_open_err = "pfh_trim_fastq_pair: two inputs and four outputs are needed";
         return 1;
@@ -357,7 +422,7 @@ int pfh_trim_fastq_pair(const char *in1, const char *in2, const char *const *out
     try {
         const std::string out[4] = {out_paths[0], out_paths[1], out_paths[2], out_paths[3]};
         pf_trim_stats st[2] = {};
-        const int rc = pfh::trim_fastq_pair(in1, in2, out, trim_options(steps, n_steps, phred, trimlog, chunk_bytes), device, st, nullptr, g_open_err);
+        const int rc = pfh::trim_fastq_pair(in1, in2, out, trim_stream_options(steps, n_steps, phred, trimlog, chunk_bytes, clip), device, st, nullptr, g_open_err, &g_clip_report);
         if (stats) { stats[0] = st[0]; stats[1] = st[1]; }
         return rc;
     } catch (const std::exception &e) {
@@ -396,6 +461,32 @@ int pfh_trim_fastq_chunk(const char *text, uint64_t n, int final, const pf_trim_
     if (n_records) *n_records = recs;
     if (bad_record) *bad_record = bad;
     if (stats) memcpy(stats, &st, sizeof st);
+    for (uint64_t i = 0; i < cap && i < rb.size(); ++i) {
+        if (rec_begin) rec_begin[i] = rb[i];
+        if (rec_len) rec_len[i] = rl[i];
+    }
+    return clause;
+}
+int pfh_trim_fastq_chunk_clip(const char *text, uint64_t n, int final, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, const char *bases,
+                              const uint32_t *adapter_off, const uint8_t *side, uint32_t n_adapters, uint32_t file_side, uint32_t seed, uint32_t score, char *out,
+                              uint64_t *out_bytes, uint64_t *bytes_used, uint32_t *rec_begin, uint32_t *rec_len, uint64_t cap, uint64_t *n_records,
+                              pf_trim_stats *stats, pf_clip_stats *clip, uint64_t *bad_record) {
+    if (clip_set_refused("pfh_trim_fastq_chunk_clip", bases, adapter_off, side, n_adapters, file_side, seed, score, phred)) return -1;
+    if (n_steps && pfh::trim_options_clause(trim_options(steps, n_steps, phred, nullptr, 0), g_open_err)) return -1;   // (no step beside adapters is a plan)
+    std::string o;
+    std::vector<uint32_t> rb, rl;
+    uint64_t used = 0, recs = 0, bad = 0;
+    pf_trim::Stats st = {};
+    pf_clip::Stats cs = {};
+    const int clause = pf_clip::trim_fastq(text, n, final != 0, reinterpret_cast<const pf_trim::Step *>(steps), n_steps, phred, bases, adapter_off, side, n_adapters,
+                                           file_side, seed, score, o, used, recs, bad, &rb, &rl, &st, &cs);
+    if (out_bytes) *out_bytes = o.size();
+    if (out && !o.empty()) memcpy(out, o.data(), o.size());
+    if (bytes_used) *bytes_used = used;
+    if (n_records) *n_records = recs;
+    if (bad_record) *bad_record = bad;
+    if (stats) memcpy(stats, &st, sizeof st);
+    if (clip) memcpy(clip, &cs, sizeof cs);
     for (uint64_t i = 0; i < cap && i < rb.size(); ++i) {
         if (rec_begin) rec_begin[i] = rb[i];
         if (rec_len) rec_len[i] = rl[i];
@@ -551,12 +642,27 @@ static void run_options_from(const pfh_run_options *o, pfh::RunOptions &opt) {
     if (o->db_out) opt.db_out = o->db_out;
     if (o->gfa_out) opt.gfa_out = o->gfa_out;
 }
-static void trim_inputs_from(const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, pfh::TrimInputs &t) {
+// the clip reports of a run's units as the one report of the call
+static void clip_report_sum(const std::vector<pfh::ClipReport> &units) {
+    for (const pfh::ClipReport &u : units) {
+        g_clip_report.adapters = u.adapters;
+        g_clip_report.skipped = u.skipped;
+        for (int f = 0; f < 2; ++f) {
+            g_clip_report.stats.reads_clipped[f] += u.stats.reads_clipped[f];
+            g_clip_report.stats.reads_dropped[f] += u.stats.reads_dropped[f];
+            g_clip_report.stats.bases_clipped[f] += u.stats.bases_clipped[f];
+            g_clip_report.stats.candidates_scored[f] += u.stats.candidates_scored[f];
+        }
+    }
+}
+static void trim_inputs_from(const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, const pfh::ClipOptions &clip, pfh::TrimInputs &t) {
     t.steps.assign(steps, steps + (steps ? n_steps : 0));
     t.phred = phred;
+    t.clip = clip;
 }
 static int run_fastq_c(const char *who, const char *const *inputs, uint32_t n_inputs, int paired, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred,
                        const char *out_prefix, const pfh_run_options *o, int device, pfh_run_stats *stats, pf_trim_stats *per_unit) {
+    const pfh::ClipOptions clip = take_reads_adapters();   // taken first: a refusal below does not leave the switch to the next call
     if (!out_prefix || !o || (n_inputs && !inputs)) { g_open_err = std::string(who) + ": inputs, output prefix and options are needed"; return 1; }
     try {
         std::vector<std::string> in;
@@ -571,7 +677,7 @@ static int run_fastq_c(const char *who, const char *const *inputs, uint32_t n_in
             opt.call.model.only = o->model_only != 0;
             opt.call.model.source = o->model_source;
         }
-        trim_inputs_from(steps, n_steps, phred, opt.trim);
+        trim_inputs_from(steps, n_steps, phred, clip, opt.trim);
         opt.paired = paired != 0;
         pfh::RunStats st;
         const int rc = pfh::run_fastq(in, out_prefix, opt, device, st, nullptr, g_open_err);
@@ -580,6 +686,7 @@ static int run_fastq_c(const char *who, const char *const *inputs, uint32_t n_in
                                    st.masked.kmers_bad, st.masked.kmers_kept, st.distinct_kept, st.graph.unitigs, st.graph.removed, st.graph.unitigs_out,
                                    st.graph.longest};
         if (per_unit) std::copy(st.trim.begin(), st.trim.end(), per_unit);
+        clip_report_sum(st.clip);
         return rc;
     } catch (const std::exception &e) {
         g_open_err = std::string("ploidyfrost host layer: ") + e.what();
@@ -598,6 +705,7 @@ static int run_multi_fastq_c(const char *who, const char *const *names, const ui
                              const char *const *inputs, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, const char *out_prefix,
                              const pfh_run_options *o, const pf_filter_multi_opts *multi, int each_color, int device, pfh_run_multi_stats *stats,
                              uint64_t *per_color, pf_trim_stats *per_input) {
+    const pfh::ClipOptions clip = take_reads_adapters();   // taken first: a refusal below does not leave the switch to the next call
     if (!out_prefix || !o || (n_samples && (!names || !n_inputs_of))) { g_open_err = std::string(who) + ": samples, output prefix and options are needed"; return 1; }
     try {
         std::vector<pfh::MultiSample> samples(n_samples);
@@ -612,7 +720,7 @@ static int run_multi_fastq_c(const char *who, const char *const *names, const ui
         opt.gz = take_reads_gz();
         opt.fasta = take_reads_fasta();
         run_options_from(o, opt);
-        trim_inputs_from(steps, n_steps, phred, opt.trim);
+        trim_inputs_from(steps, n_steps, phred, clip, opt.trim);
         mopt.call.threads = o->threads ? o->threads : 1;
         if (o->model_source >= 0) {
             if (!multi) { g_open_err = "run-multi: a model reads the coloured result streams behind the options of filter-multi: multi is needed"; return 1; }
@@ -635,6 +743,7 @@ static int run_multi_fastq_c(const char *who, const char *const *names, const ui
                 per_color[4 * c + 2] = st.color[c].distinct;
                 per_color[4 * c + 3] = st.color[c].kept;
             }
+        for (const auto &units : st.clip) clip_report_sum(units);
         if (per_input) {   // one entry per input file; a single-ended sample's unit stands in its first entry
             uint64_t i = 0;
             for (uint32_t c = 0; c < n_samples; i += n_inputs_of[c], ++c)

@@ -100,7 +100,9 @@ void PrintUsage() {
          << "                  lies outside [L, U] becomes N; --auto-cutoffs: L = what `cutoffL -d` prints, printed on stdout)" << endl << endl
          << "Usage: PloidyFrost trim -i <reads.fq> [-i <more.fq> ...] -o <trimmed.fq> STEP... [--phred 33|64] [--trimlog <file>] [--chunk-bytes N] [--gz] [--gz-plain] [--gz-out] [-v]" << endl
          << "Usage: PloidyFrost trim -1 <r1.fq> -2 <r2.fq> -o1 <p1.fq> -u1 <u1.fq> -o2 <p2.fq> -u2 <u2.fq> STEP... [the same options]" << endl
-         << "                  (`trimmomatic SE|PE` on the device; STEP: LEADING:t TRAILING:t SLIDINGWINDOW:w:t MINLEN:l, applied in the order given)" << endl << endl
+         << "                  (`trimmomatic SE|PE` on the device; STEP: LEADING:t TRAILING:t SLIDINGWINDOW:w:t MINLEN:l, applied in the order given)" << endl
+         << "                  [--adapters <adapters.fa> [--adapter-seed 0..8] [--adapter-score 1..1000]] on trim, run STEP... and run-multi STEP...: adapter read-through is" << endl
+         << "                  clipped on the device before the steps (ILLUMINACLIP's simple mode; no STEP is needed beside --adapters, also with -1 / -2)" << endl << endl
          << "Usage: PloidyFrost build -k 25 [-i] [-d] -r <reads.fq> [-r <more.fq> ...] -o <sample> [-g G] [-t N] [--chunk-bytes N] [--initial-slots N] [-v]" << endl
          << "                  (`Bifrost build -r` on the device: <sample>.gfa, the compacted de Bruijn graph of the reads; -i clips tips, -d deletes" << endl
          << "                  isolated unitigs, both of fewer than k k-mers; single-sample graphs from FASTQ only)" << endl
@@ -807,15 +809,53 @@ int mask_main(int argc, char **argv) {
     return 0;
 }
 
+// `--adapters FILE [--adapter-seed S] [--adapter-score T]` of `trim`, `run` and `run-multi`: the one place they are parsed
+struct ClipCli {
+    string adapters, seed, score;
+    bool adapters_seen = false, seed_seen = false, score_seen = false;
+    // 1 = the option was taken (i moved past its value), 0 = not one of these, -1 = refused with `why`
+    int take(int argc, char **argv, int &i, string &why) {
+        const string a = argv[i];
+        if (a != "--adapters" && a != "--adapter-seed" && a != "--adapter-score") return 0;
+        if (i + 1 >= argc) { why = a + " needs a value"; return -1; }
+        const string v = argv[++i];
+        if (a == "--adapters") { adapters = v; adapters_seen = true; }
+        else if (a == "--adapter-seed") { seed = v; seed_seen = true; }
+        else { score = v; score_seen = true; }
+        return 1;
+    }
+    static bool number(const string &v, uint32_t lo, uint32_t hi, uint32_t &out) {
+        if (v.empty() || v.size() > 6) return false;
+        for (char ch : v) if (ch < '0' || ch > '9') return false;
+        out = (uint32_t)stoul(v);
+        return out >= lo && out <= hi;
+    }
+    // after the last argument: "" = accepted
+    string finish(pfh::ClipOptions &opt) const {
+        if (!adapters_seen) {
+            if (seed_seen) return "--adapter-seed needs --adapters: the seed is read by the adapter clipping alone";
+            if (score_seen) return "--adapter-score needs --adapters: the score is read by the adapter clipping alone";
+            return "";
+        }
+        if (adapters.empty()) return "--adapters takes the path of a FASTA file";
+        opt.adapters = adapters;
+        if (seed_seen && !number(seed, 0, pf_clip::MAX_SEED, opt.seed)) return "--adapter-seed takes 0 to 8, not '" + seed + "'";
+        if (score_seen && !number(score, pf_clip::MIN_SCORE, pf_clip::MAX_SCORE, opt.score)) return "--adapter-score takes 1 to 1000, not '" + score + "'";
+        return "";
+    }
+};
+
 // `trim`: step 1 of the reference's workflow (`trimmomatic PE -phred33 r1 r2 trim1 u1 trim2 u2 LEADING:10 TRAILING:10 SLIDINGWINDOW:3:20
 // MINLEN:50`) on the device; the steps are Trimmomatic's words as positional arguments
 int trim_main(int argc, char **argv) {
     const char *usage = "Usage:PloidyFrost trim -i reads.fq [-i more.fq ...] -o trimmed.fq STEP... [--phred 33|64] [--trimlog file] [--chunk-bytes N] [--gz] [--gz-plain] [--gz-out] [-v]\n"
                         "      PloidyFrost trim -1 r1.fq -2 r2.fq -o1 p1.fq -u1 u1.fq -o2 p2.fq -u2 u2.fq STEP... [the same options]\n"
-                        "      STEP: LEADING:t TRAILING:t SLIDINGWINDOW:w:t MINLEN:l";
+                        "      STEP: LEADING:t TRAILING:t SLIDINGWINDOW:w:t MINLEN:l\n"
+                        "      [--adapters adapters.fa [--adapter-seed 0..8] [--adapter-score 1..1000]]: adapters are clipped first; no STEP is needed beside them";
     vector<string> inputs, words;
     string out, in_pair[2], out_pair[4];
     pfh::TrimOptions opt;
+    ClipCli clip_cli;
     bool verbose = false;
     auto refuse = [&](const string &why) { cerr << "Error: trim: " << why << endl << usage << endl; return 1; };
     const char *pair_opts[6] = {"-1", "-2", "-o1", "-u1", "-o2", "-u2"};
@@ -827,6 +867,12 @@ int trim_main(int argc, char **argv) {
         if (a == "--gz-plain") { opt.gz = 2; continue; }
         if (a == "--gz-out") { opt.gz_out = true; continue; }
         if (a == "--fasta") return refuse("--fasta does not go with trim: FASTA has no qualities to trim");
+        {
+            string why;
+            const int taken = clip_cli.take(argc, argv, i, why);
+            if (taken < 0) return refuse(why);
+            if (taken) continue;
+        }
         const bool known = a == "-i" || a == "-o" || a == "--phred" || a == "--trimlog" || a == "--chunk-bytes" ||
                            std::find_if(pair_opts, pair_opts + 6, [&](const char *o) { return a == o; }) != pair_opts + 6;
         if (!known) return refuse("unknown option " + a);
@@ -854,9 +900,10 @@ int trim_main(int argc, char **argv) {
         for (const string &x : words) w.push_back(x.c_str());
         vector<pf_trim::Step> steps;
         size_t bad = 0;
+        { const string why = clip_cli.finish(opt.clip); if (!why.empty()) return refuse(why); }
         const int c = pf_trim::parse_steps(w.data(), w.size(), steps, &bad);
-        if (c == pf_trim::REFUSE_NO_STEP) return refuse(pf_trim::refusal_text(c));
-        if (c) return refuse(words[bad] + ": " + pf_trim::refusal_text(c));
+        if (c == pf_trim::REFUSE_NO_STEP && !opt.clip.on()) return refuse(pf_trim::refusal_text(c));
+        if (c && c != pf_trim::REFUSE_NO_STEP) return refuse(words[bad] + ": " + pf_trim::refusal_text(c));
         for (const pf_trim::Step &st : steps) opt.steps.push_back(pf_trim_step{st.kind, st.a, st.b});
     }
     const bool pair_in = !in_pair[0].empty() || !in_pair[1].empty();
@@ -866,19 +913,22 @@ int trim_main(int argc, char **argv) {
     if (!pair_in && pair_out) return refuse(inputs.empty() ? "-1 <r1.fq> and -2 <r2.fq> are missing" : "-o1 -u1 -o2 -u2 do not go with -i (single-ended reads are written to -o)");
     pf_trim_stats st[2] = {};
     pfh::TrimTimes tm;
+    pfh::ClipReport clip;
     string err;
     if (pair_in) {
         for (int j = 0; j < 2; ++j)
             if (in_pair[j].empty()) return refuse(string(pair_opts[j]) + " <r" + to_string(j + 1) + ".fq> is missing");
         for (int j = 0; j < 4; ++j)
             if (out_pair[j].empty()) return refuse(string(pair_opts[2 + j]) + " <out.fq> is missing");
-        if (pfh::trim_fastq_pair(in_pair[0], in_pair[1], out_pair, opt, 0, st, &tm, err)) { cerr << "Error: " << err << endl; return 1; }
+        if (pfh::trim_fastq_pair(in_pair[0], in_pair[1], out_pair, opt, 0, st, &tm, err, &clip)) { cerr << "Error: " << err << endl; return 1; }
+        if (opt.clip.on()) cerr << pfh::clip_line(clip) << endl;
         cerr << "trim: pairs " << st[0].reads << " both " << st[0].both << " forward_only " << st[0].only1 << " reverse_only " << st[0].only2 << " dropped "
              << st[0].neither << " bases " << st[0].bases + st[1].bases << " bases_kept " << st[0].bases_kept + st[1].bases_kept << endl;
     } else {
         if (inputs.empty()) return refuse("-i <reads.fq> is missing (or -1 <r1.fq> -2 <r2.fq> for a pair)");
         if (out.empty()) return refuse("-o <trimmed.fq> is missing");
-        if (pfh::trim_fastq(inputs, out, opt, 0, st[0], &tm, err)) { cerr << "Error: " << err << endl; return 1; }
+        if (pfh::trim_fastq(inputs, out, opt, 0, st[0], &tm, err, &clip)) { cerr << "Error: " << err << endl; return 1; }
+        if (opt.clip.on()) cerr << pfh::clip_line(clip) << endl;
         cerr << "trim: reads " << st[0].reads << " kept " << st[0].kept << " dropped " << st[0].dropped << " bases " << st[0].bases << " bases_kept "
              << st[0].bases_kept << endl;
     }
@@ -892,12 +942,14 @@ struct TrimCli {
     bool phred_seen = false, pair_seen = false;
     uint32_t phred = 33;
     string pending1;        // a -1 whose -2 has not come yet
+    ClipCli clip;           // --adapters and its two values
     // 1 = the option was taken (i moved past its value), 0 = not one of these, -1 = refused with `why`
     int take(int argc, char **argv, int &i, const char *sub, vector<string> &files, string &why) {
         const string a = argv[i];
         if (a.empty() || a[0] != '-') { words.push_back(a); return 1; }
         for (const char *o : {"--trimlog", "-o1", "-u1", "-o2", "-u2"})
             if (a == o) { why = a + " is not built into " + sub + ": `trim` writes the trimmed reads, the unpaired ones and the log"; return -1; }
+        { const int taken = clip.take(argc, argv, i, why); if (taken) return taken; }
         if (a != "--phred" && a != "-1" && a != "-2") return 0;
         if (i + 1 >= argc) { why = a + " needs a value"; return -1; }
         const string v = argv[++i];
@@ -919,8 +971,10 @@ struct TrimCli {
     }
     string no_second() const { return "-1 " + pending1 + " has no -2 behind it (the files of a pair come as -1 <r1.fq> -2 <r2.fq>)"; }
     // after the last argument: "" = accepted, with the steps parsed
-    string finish(const char *sub, vector<pf_trim_step> &steps) const {
+    string finish(const char *sub, vector<pf_trim_step> &steps, pfh::ClipOptions &clip_opt) const {
         if (!pending1.empty()) return no_second();
+        { const string why = clip.finish(clip_opt); if (!why.empty()) return why; }
+        if (words.empty() && clip_opt.on()) return "";   // --adapters turns trimming on as a step does
         if (words.empty()) {
             if (pair_seen) return string("-1 / -2 need a step: the files of a pair are trimmed together (two files without trimming go with -i: ") + sub + " -i r1.fq -i r2.fq)";
             if (phred_seen) return "--phred needs a step: the quality offset is read by the trimming alone";
@@ -1037,7 +1091,7 @@ int run_main(int argc, char **argv) {
         else if (a == "--initial-slots") opt.initial_slots = v;
     }
     // refused by name, before anything is read or written and before a device context exists
-    { const string why = tc.finish("run", opt.trim.steps); if (!why.empty()) return refuse(why); }
+    { const string why = tc.finish("run", opt.trim.steps, opt.trim.clip); if (!why.empty()) return refuse(why); }
     opt.trim.phred = tc.phred;
     if (tc.pair_seen && !inputs.empty()) return refuse("-i does not go with -1 / -2 (the inputs are either single-ended or pairs)");
     if (tc.pair_seen) { inputs = pair_files; opt.paired = true; }
@@ -1073,8 +1127,10 @@ int run_main(int argc, char **argv) {
         else cerr << err << endl;
         return EXIT_FAILURE;
     }
-    for (size_t u = 0; u < pfh::trim_unit_count(inputs.size(), opt.paired) && opt.trim.on(); ++u)   // one line per `trim` of the equivalent chain
+    for (size_t u = 0; u < pfh::trim_unit_count(inputs.size(), opt.paired) && opt.trim.on(); ++u) {   // one line per `trim` of the equivalent chain
+        if (u < st.clip.size()) cerr << pfh::clip_line(st.clip[u]) << endl;
         cerr << pfh::trim_unit_line(&st.trim[opt.paired ? 2 * u : 0], opt.paired) << endl;
+    }
     cerr << "run: reads " << st.counted.reads << " bases " << st.counted.bases << " kmers " << st.counted.kmers << " bad " << st.counted.kmers_bad << " distinct "
          << st.counted.unique << " lower " << st.lower << " upper " << st.upper << " windows_bad " << st.masked.kmers_bad << " windows_kept " << st.masked.kmers_kept
          << " distinct_kept " << st.distinct_kept << " unitigs " << st.graph.unitigs << " removed " << st.graph.removed << " unitigs_out " << st.graph.unitigs_out
@@ -1193,7 +1249,7 @@ int run_multi_main(int argc, char **argv) {
         else if (a == "--initial-slots") opt.initial_slots = v;
     }
     // refused by name, before anything is read or written and before a device context exists
-    { const string why = tc.finish("run-multi", opt.trim.steps); if (!why.empty()) return refuse(why); }
+    { const string why = tc.finish("run-multi", opt.trim.steps, opt.trim.clip); if (!why.empty()) return refuse(why); }
     opt.trim.phred = tc.phred;
     { const string why = pfh::run_multi_samples_refusal(samples); if (!why.empty()) return refuse(why); }
     if (out.empty()) return refuse("-o <out> is missing");
@@ -1231,8 +1287,10 @@ int run_multi_main(int argc, char **argv) {
         return EXIT_FAILURE;
     }
     for (size_t c = 0; c < st.trim.size(); ++c)   // one line per `trim` of the equivalent chain, in the order given
-        for (size_t u = 0; u < pfh::trim_unit_count(samples[c].inputs.size(), samples[c].paired); ++u)
+        for (size_t u = 0; u < pfh::trim_unit_count(samples[c].inputs.size(), samples[c].paired); ++u) {
+            if (c < st.clip.size() && u < st.clip[c].size()) cerr << pfh::clip_line(st.clip[c][u]) << endl;
             cerr << pfh::trim_unit_line(&st.trim[c][samples[c].paired ? 2 * u : 0], samples[c].paired) << endl;
+        }
     cerr << "run-multi: colors " << st.colors << " reads " << st.reads << " bases " << st.bases << " kmers " << st.kmers << " bad " << st.bad << " distinct "
          << st.distinct << " windows_bad " << st.windows_bad << " windows_kept " << st.windows_kept << " distinct_kept " << st.distinct_kept << " unitigs "
          << st.graph.unitigs << " removed " << st.graph.removed << " unitigs_out " << st.graph.unitigs_out << " longest " << st.graph.longest << " kmers_colored "

@@ -128,6 +128,7 @@ std::string trim_inputs_refusal(const std::vector<std::string> &inputs, bool pai
         TrimOptions o;
         o.steps = trim.steps;
         o.phred = trim.phred;
+        o.clip = trim.clip;
         std::string e;
         if (trim_options_clause(o, e)) return e.substr(6);   // (worded "trim: ...": the caller puts its own name in front)
     }
@@ -155,11 +156,28 @@ void add_masked_stats(pf_maskcount_stats &a, const pf_maskcount_stats &b) {
 }  // namespace
 
 int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<ReadsInput> &inputs, bool paired, const TrimInputs &trim, uint64_t chunk_bytes,
-                   bool masked, uint32_t low, uint32_t up, pf_trim_stats *unit_stats, pf_maskcount_stats *masked_stats, std::string &err) {
+                   bool masked, uint32_t low, uint32_t up, pf_trim_stats *unit_stats, pf_maskcount_stats *masked_stats, std::string &err,
+                   pf_clip_stats *unit_clip) {
     const pf_trim_plan plan = {trim.steps.data(), (uint32_t)trim.steps.size(), trim.phred};
+    // what the clip has counted since the last unit ended, into unit u
+    pf_clip_stats clip_seen = {};
+    auto clip_unit = [&](size_t u, bool store) {
+        if (!unit_clip) return 0;
+        pf_clip_stats now = {};
+        if (pf_clip_stats_get(ctx, &now) != PF_OK) { err = std::string(who) + ": " + pf_last_error(ctx); return 1; }
+        for (int f = 0; f < 2 && store; ++f) {
+            unit_clip[u].reads_clipped[f] = now.reads_clipped[f] - clip_seen.reads_clipped[f];
+            unit_clip[u].reads_dropped[f] = now.reads_dropped[f] - clip_seen.reads_dropped[f];
+            unit_clip[u].bases_clipped[f] = now.bases_clipped[f] - clip_seen.bases_clipped[f];
+            unit_clip[u].candidates_scored[f] = now.candidates_scored[f] - clip_seen.candidates_scored[f];
+        }
+        clip_seen = now;
+        return 0;
+    };
+    if (clip_unit(0, false)) return 1;
     if (!paired) {
         StreamTimes stm;
-        return stream_fastq(ctx, who, inputs, chunk_bytes, -1, "",
+        const int rc0 = stream_fastq(ctx, who, inputs, chunk_bytes, -1, "",
                             [&](const Chunk &c, Taken &t) {
                                 pf_trim_stats ts = {};
                                 pf_count_stats cs = {};
@@ -173,6 +191,7 @@ int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<ReadsInput> &
                                 return (int)PF_OK;
                             },
                             stm, err);
+        return rc0 ? rc0 : clip_unit(0, true);
     }
     for (size_t u = 0; u + 1 < inputs.size(); u += 2) {
         PairStreamTimes ptm;
@@ -193,12 +212,14 @@ int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<ReadsInput> &
                               },
                               ptm, err))
             return 1;
+        if (clip_unit(u / 2, true)) return 1;
     }
     return 0;
 }
 
 // ---- run ----
 std::string run_options_refusal(const RunOptions &opt) {
+    if (opt.fasta && opt.trim.clip.on()) return "--fasta does not go with --adapters (FASTA has no qualities to score an adapter by)";
     if (opt.fasta && (opt.trim.on() || opt.paired)) return "--fasta does not go with trim steps or -1 / -2 (FASTA has no qualities to trim)";
     { const int c = count_options_clause(count_options_of(opt), true); if (c) return pf_count::cut_text(c); }
     BuildOptions b;
@@ -226,6 +247,8 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
     if (!gfa_path.empty()) outputs.push_back(gfa_path);
     std::vector<ReadsInput> reads;   // what each input is: decided here, once, for both passes
     if (fastq_preflight("run", "read", inputs, outputs, ReadsOptions{opt.gz, opt.fasta}, reads, err)) return 1;
+    pf_clip::Adapters adapters;   // --adapters: read and refused here, before a device context exists
+    if (opt.trim.clip.on() && clip_load(opt.trim.clip, adapters, err)) { err = "run: " + err; return 1; }
 
     pf_ctx *ctx = nullptr;
     if (pf_create(device, &ctx) != PF_OK) {
@@ -242,6 +265,11 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
         return 1;
     };
     auto dev_fail = [&]() { return fail(std::string("run: ") + pf_last_error(ctx)); };
+    std::vector<pf_clip_stats> unit_clip;
+    if (opt.trim.clip.on()) {   // the clip stays open over both passes; the first one is reported
+        if (clip_open(ctx, adapters, opt.trim.clip) != PF_OK) return dev_fail();
+        unit_clip.assign(trim_unit_count(inputs.size(), opt.paired), pf_clip_stats{});
+    }
 
     // ---- count: every k-mer of the reads, both strands, the user's cut-offs ----
     std::vector<uint64_t> rows;
@@ -250,7 +278,8 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
         Counted db;
         CountTimes ctm;
         if (trimming ? count_stream_with(ctx, "run", copt, [&](std::string &e) {
-                           return stream_trimmed(ctx, "run", reads, opt.paired, opt.trim, opt.chunk_bytes, false, 0, 0, stats.trim.data(), nullptr, e);
+                           return stream_trimmed(ctx, "run", reads, opt.paired, opt.trim, opt.chunk_bytes, false, 0, 0, stats.trim.data(), nullptr, e,
+                                                 unit_clip.empty() ? nullptr : unit_clip.data());
                        }, db, stats.counted, ctm, err)
                      : count_stream(ctx, "run", reads, copt, db, stats.counted, ctm, err))
             return 1;
@@ -313,6 +342,10 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
         pf_device_free(ctx, kept.counts);   // the graph asks for the k-mers alone
         kept.counts = nullptr;
         stats.distinct_kept = kept.n;
+    }
+    if (opt.trim.clip.on()) {
+        for (const pf_clip_stats &u : unit_clip) stats.clip.push_back(ClipReport{adapters.size(), adapters.skipped, u});
+        if (pf_clip_end(ctx) != PF_OK) return dev_fail();
     }
     if (kept.n >= pf_unitig::MAX_KMERS) return fail(std::string("run: ") + pf_unitig::TOO_MANY_TEXT + " (" + std::to_string(kept.n) + ")");
 

@@ -21,6 +21,7 @@
 #include "pf_build_host.hpp"
 #include "pf_cdbg.hpp"
 #include "pf_count_host.hpp"
+#include "pf_clip_host.hpp"
 #include "ploidyfrost_hip.h"
 
 namespace pfh {
@@ -70,7 +71,8 @@ int colored_call_run(CCDBG &g, ColoredCallSetup &s, std::string &err);
 struct TrimInputs {
     std::vector<pf_trim_step> steps;   // none: no trimming, the inputs are read as they are
     uint32_t phred = 33;
-    bool on() const { return !steps.empty(); }
+    ClipOptions clip;                  // --adapters: K-CLIP in front of the steps; turns trimming on as a step does
+    bool on() const { return !steps.empty() || clip.on(); }
 };
 // A unit is what one `trim` command of the equivalent chain takes: all single-ended files together, or one pair.
 inline size_t trim_unit_count(size_t n_inputs, bool paired) { return paired ? n_inputs / 2 : 1; }
@@ -81,9 +83,11 @@ std::string trim_inputs_refusal(const std::vector<std::string> &inputs, bool pai
 // pf_maskcount_fastq[_pair]_trimmed with [low, up].  paired: the inputs alternate file 1, file 2, and every pair goes through the
 // lock-step stream of pf_reads_stream.hpp; else they go through stream_fastq one after the other.  The inputs are what the preflight
 // made of them, the same for both passes.  unit_stats (may be null; paired: one entry per input file, else one entry) and masked_stats
-// (may be null) are added to.  0 = ok, else worded in err by `who`.
+// (may be null) are added to.  unit_clip (may be null; a clip is open on the context): one entry per unit, what the clip counted
+// while the unit streamed.  0 = ok, else worded in err by `who`.
 int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<ReadsInput> &inputs, bool paired, const TrimInputs &trim, uint64_t chunk_bytes,
-                   bool masked, uint32_t low, uint32_t up, pf_trim_stats *unit_stats, pf_maskcount_stats *masked_stats, std::string &err);
+                   bool masked, uint32_t low, uint32_t up, pf_trim_stats *unit_stats, pf_maskcount_stats *masked_stats, std::string &err,
+                   pf_clip_stats *unit_clip = nullptr);
 // the `trim:` line of a unit on stderr, in `trim`'s own format: st = the unit's statistics (paired: of file 1 and of file 2)
 std::string trim_unit_line(const pf_trim_stats *st, bool paired);
 
@@ -118,6 +122,7 @@ struct RunStats {
     pf_unitig_stats graph = {};
     std::string model_last_line;       // with a model: what the calling run prints last
     std::vector<pf_trim_stats> trim;   // STEP...: the trimming of the first pass (paired: one entry per input file, else one entry)
+    std::vector<ClipReport> clip;      // --adapters: the clipping of the first pass, one entry per unit
 };
 struct RunTimes {
     double count_s = 0, finish_s = 0, table_s = 0, db_out_s = 0, recount_s = 0, refinish_s = 0, graph_s = 0, gfa_out_s = 0, load_s = 0, call_s = 0;

@@ -130,6 +130,9 @@ int run_multi_fastq(const std::vector<MultiSample> &samples, const std::string &
                         return 1;
                     }
 
+    pf_clip::Adapters adapters;   // --adapters: read and refused here, before a device context exists
+    if (opt.trim.clip.on() && clip_load(opt.trim.clip, adapters, err)) { err = "run-multi: " + err; return 1; }
+
     pf_ctx *ctx = nullptr;
     if (pf_create(device, &ctx) != PF_OK) {
         err = std::string("run-multi: no device context (") + (pf_last_error(nullptr) ? pf_last_error(nullptr) : "?") + "); reads are counted and called on the GPU only";
@@ -148,6 +151,11 @@ int run_multi_fastq(const std::vector<MultiSample> &samples, const std::string &
     };
     auto dev_fail = [&]() { return fail(std::string("run-multi: ") + pf_last_error(ctx)); };
 
+    std::vector<std::vector<pf_clip_stats>> unit_clip(C);
+    if (opt.trim.clip.on()) {   // the clip stays open over both passes; the first one is reported
+        if (clip_open(ctx, adapters, opt.trim.clip) != PF_OK) return dev_fail();
+        for (uint32_t c = 0; c < C; ++c) unit_clip[c].assign(trim_unit_count(samples[c].inputs.size(), samples[c].paired), pf_clip_stats{});
+    }
     // ---- first pass, per sample: count, thresholds; the counters stay resident ----
     stats.colors = C;
     stats.color.assign(C, RunMultiColor{});
@@ -164,7 +172,7 @@ int run_multi_fastq(const std::vector<MultiSample> &samples, const std::string &
         std::string e;
         if (trimming ? count_stream_with(ctx, "run-multi", copt, [&](std::string &pe) {
                            return stream_trimmed(ctx, "run-multi", reads[c], samples[c].paired, opt.trim, opt.chunk_bytes, false, 0, 0, stats.trim[c].data(),
-                                                 nullptr, pe);
+                                                 nullptr, pe, unit_clip[c].empty() ? nullptr : unit_clip[c].data());
                        }, db[c], counted, ctm, e)
                      : count_stream(ctx, "run-multi", reads[c], copt, db[c], counted, ctm, e))
             return fail(e);
@@ -236,6 +244,12 @@ int run_multi_fastq(const std::vector<MultiSample> &samples, const std::string &
         held.p.push_back(kept[c].kmers);
         stats.color[c].kept = kept[c].n;
         tm.recount_s += since(t_stream);
+    }
+    if (opt.trim.clip.on()) {
+        stats.clip.resize(C);
+        for (uint32_t c = 0; c < C; ++c)
+            for (const pf_clip_stats &u : unit_clip[c]) stats.clip[c].push_back(ClipReport{adapters.size(), adapters.skipped, u});
+        if (pf_clip_end(ctx) != PF_OK) return dev_fail();
     }
     if (pf_release_counts(ctx) != PF_OK) return dev_fail();   // the last sample's table: the joined one takes its place in the end
 

@@ -49,6 +49,7 @@ struct RunMultiStats {
     uint64_t kmers_colored = 0, kmers_unplaced = 0, runs = 0, overflow = 0, color_bytes = 0;
     std::vector<RunMultiColor> color;
     std::string model_last_line;
+    std::vector<std::vector<ClipReport>> clip;      // --adapters: per sample the clipping of its first pass, one entry per unit
     std::vector<std::vector<pf_trim_stats>> trim;   // STEP...: per sample the trimming of its first pass (paired: per input file, else one entry)
 };
 struct RunMultiTimes {

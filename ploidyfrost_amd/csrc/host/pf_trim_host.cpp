@@ -21,17 +21,19 @@ using clk = std::chrono::steady_clock;
 double since(clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); }
 
 // Trimmomatic's five columns for record r of a chunk whose lines are (lb, le)
-void trimlog_line(std::string &log, const char *text, const uint64_t *lb, const uint64_t *le, uint32_t begin, uint32_t len) {
+// (n: the bases of the read, or with --adapters its clip end -- the log speaks of the read the steps saw)
+void trimlog_line(std::string &log, const char *text, const uint64_t *lb, const uint64_t *le, uint32_t begin, uint32_t len, const uint32_t *clip_end = nullptr) {
     log.append(text + lb[0] + 1, le[0] - lb[0] - 1);   // (the header starts with '@': the index has checked it)
     if (!len) { log += " 0 0 0 0\n"; return; }
-    const uint64_t n = le[3] - lb[3], e = (uint64_t)begin + len;
+    const uint64_t n = clip_end ? (uint64_t)*clip_end : le[3] - lb[3], e = (uint64_t)begin + len;
     log += ' ' + std::to_string(len) + ' ' + std::to_string(begin) + ' ' + std::to_string(e) + ' ' + std::to_string(n - e) + '\n';
 }
 
 // everything that is refused before a device context exists
 int trim_preflight(const std::vector<std::string> &inputs, const std::vector<std::string> &outputs, const TrimOptions &opt, std::vector<ReadsInput> &reads,
-                   std::string &err) {
+                   pf_clip::Adapters &adapters, std::string &err) {
     if (trim_options_clause(opt, err)) return 1;
+    if (opt.clip.on() && clip_load(opt.clip, adapters, err)) { err = "trim: " + err; return 1; }
     for (size_t i = 0; i < outputs.size(); ++i) {
         if (outputs[i].empty()) { err = "trim: an output path is empty"; return 1; }
         for (size_t j = 0; j < i; ++j)
@@ -45,12 +47,28 @@ int trim_create(int device, pf_ctx **ctx, std::string &err) {
     err = std::string("trim: no device context (") + (pf_last_error(nullptr) ? pf_last_error(nullptr) : "?") + "); reads are trimmed on the GPU only";
     return 1;
 }
+// --adapters: the clip of the whole stream, opened on the fresh context (it goes with the context)
+int trim_clip_open(pf_ctx *ctx, const TrimOptions &opt, const pf_clip::Adapters &adapters, std::string &err) {
+    if (!opt.clip.on() || clip_open(ctx, adapters, opt.clip) == PF_OK) return 0;
+    err = std::string("trim: ") + pf_last_error(ctx);
+    return 1;
+}
+int trim_clip_report(pf_ctx *ctx, const TrimOptions &opt, const pf_clip::Adapters &adapters, ClipReport *clip, std::string &err) {
+    if (!opt.clip.on() || !clip || clip_report(ctx, adapters, pf_clip_stats{}, *clip) == PF_OK) return 0;
+    err = std::string("trim: ") + pf_last_error(ctx);
+    return 1;
+}
 
 }  // namespace
 
 int trim_options_clause(const TrimOptions &opt, std::string &err) {
     uint32_t bad = 0;
-    const int c = pf_trim::steps_clause(reinterpret_cast<const pf_trim::Step *>(opt.steps.data()), (uint32_t)opt.steps.size(), opt.phred, &bad);
+    int c = pf_trim::steps_clause(reinterpret_cast<const pf_trim::Step *>(opt.steps.data()), (uint32_t)opt.steps.size(), opt.phred, &bad);
+    if (c == pf_trim::REFUSE_NO_STEP && opt.clip.on() && opt.steps.empty()) c = 0;   // --adapters alone is a plan
+    if (!c && opt.clip.on()) {
+        const int cc = pf_clip::params_clause(opt.clip.seed, opt.clip.score);
+        if (cc) { err = std::string("trim: ") + pf_clip::refusal_text(cc); return cc; }
+    }
     if (!c) return 0;
     err = std::string("trim: ") + pf_trim::refusal_text(c);
     if (c == pf_trim::REFUSE_PHRED) err += ", not " + std::to_string(opt.phred);
@@ -59,21 +77,23 @@ int trim_options_clause(const TrimOptions &opt, std::string &err) {
 }
 
 int trim_fastq(const std::vector<std::string> &inputs, const std::string &out_path, const TrimOptions &opt, int device, pf_trim_stats &stats,
-               TrimTimes *times, std::string &err) {
+               TrimTimes *times, std::string &err, ClipReport *clip) {
     stats = pf_trim_stats{};
     err.clear();
     const bool logs = !opt.trimlog.empty();
     std::vector<std::string> paths = {out_path};
     if (logs) paths.push_back(opt.trimlog);
     std::vector<ReadsInput> reads;
-    if (trim_preflight(inputs, paths, opt, reads, err)) return 1;
+    pf_clip::Adapters adapters;
+    if (trim_preflight(inputs, paths, opt, reads, adapters, err)) return 1;
     pf_ctx *ctx = nullptr;
     if (trim_create(device, &ctx, err)) return 1;
     CtxGuard ctx_guard{ctx};
+    if (trim_clip_open(ctx, opt, adapters, err)) return 1;
     const auto t_stream = clk::now();
     OutFiles outs("trim");
     if (outs.open_all(paths, err)) return 1;
-    std::vector<uint32_t> rb, rl;
+    std::vector<uint32_t> rb, rl, ce;
     std::vector<uint64_t> lb, le;
     std::string log, log_err;
     std::vector<char> fetched;
@@ -102,8 +122,12 @@ int trim_fastq(const std::vector<std::string> &inputs, const std::string &out_pa
                              text = fetched.data();
                          }
                          pf_trim::record_lines(text, t.used, t.reads, lb, le);
+                         if (opt.clip.on()) {
+                             ce.resize(t.reads + 1);
+                             if (pf_clip_last_ends(ctx, 0, ce.data(), t.reads) != PF_OK) return (int)PF_ERR_HIP;
+                         }
                          log.clear();
-                         for (uint64_t r = 0; r < t.reads; ++r) trimlog_line(log, text, &lb[4 * r], &le[4 * r], rb[r], rl[r]);
+                         for (uint64_t r = 0; r < t.reads; ++r) trimlog_line(log, text, &lb[4 * r], &le[4 * r], rb[r], rl[r], opt.clip.on() ? &ce[r] : nullptr);
                          write_all(outs.f[1].fd, log.data(), log.size(), "trim", outs.f[1].tmp, log_err);
                      }
                      return (int)PF_OK;
@@ -116,6 +140,7 @@ int trim_fastq(const std::vector<std::string> &inputs, const std::string &out_pa
         st_tm.write_s = gzo->wr.write_s;
     }
     if (err.empty()) err = log_err;
+    if (err.empty()) trim_clip_report(ctx, opt, adapters, clip, err);
     if (!err.empty() || outs.commit(err)) return 1;
     if (times) {
         times->stream_s = since(t_stream);
@@ -127,7 +152,7 @@ int trim_fastq(const std::vector<std::string> &inputs, const std::string &out_pa
 }
 
 int trim_fastq_pair(const std::string &in1, const std::string &in2, const std::string out_paths[4], const TrimOptions &opt, int device,
-                    pf_trim_stats stats[2], TrimTimes *times, std::string &err) {
+                    pf_trim_stats stats[2], TrimTimes *times, std::string &err, ClipReport *clip) {
     stats[0] = stats[1] = pf_trim_stats{};
     err.clear();
     const bool logs = !opt.trimlog.empty();
@@ -135,11 +160,13 @@ int trim_fastq_pair(const std::string &in1, const std::string &in2, const std::s
     std::vector<std::string> paths(out_paths, out_paths + 4);
     if (logs) paths.push_back(opt.trimlog);
     std::vector<ReadsInput> reads;
-    if (trim_preflight(inputs, paths, opt, reads, err)) return 1;
+    pf_clip::Adapters adapters;
+    if (trim_preflight(inputs, paths, opt, reads, adapters, err)) return 1;
     if (same_file(in1, in2)) { err = "trim: the two inputs of a pair are the same file (" + in1 + ")"; return 1; }
     pf_ctx *ctx = nullptr;
     if (trim_create(device, &ctx, err)) return 1;
     CtxGuard ctx_guard{ctx};
+    if (trim_clip_open(ctx, opt, adapters, err)) return 1;
     const auto t_stream = clk::now();
     OutFiles outs("trim");
     if (outs.open_all(paths, err)) return 1;
@@ -154,7 +181,7 @@ int trim_fastq_pair(const std::string &in1, const std::string &in2, const std::s
             wr[d].start(outs.f[d].fd, "trim", outs.f[d].tmp);
         }
     }
-    std::vector<uint32_t> rb[2], rl[2];
+    std::vector<uint32_t> rb[2], rl[2], ce[2];
     std::vector<uint64_t> lb[2], le[2];
     std::string log;
     std::vector<char> fetched[2];
@@ -196,8 +223,13 @@ int trim_fastq_pair(const std::string &in1, const std::string &in2, const std::s
                                       text[f] = fetched[f].data();
                                   }
                               for (int f = 0; f < 2; ++f) pf_trim::record_lines(text[f], t.used[f], t.reads, lb[f], le[f]);
+                              for (int f = 0; f < 2 && opt.clip.on(); ++f) {
+                                  ce[f].resize(t.reads + 1);
+                                  if (pf_clip_last_ends(ctx, f, ce[f].data(), t.reads) != PF_OK) return (int)PF_ERR_HIP;
+                              }
                               for (uint64_t r = 0; r < t.reads; ++r)
-                                  for (int f = 0; f < 2; ++f) trimlog_line(log, text[f], &lb[f][4 * r], &le[f][4 * r], rb[f][r], rl[f][r]);
+                                  for (int f = 0; f < 2; ++f)
+                                      trimlog_line(log, text[f], &lb[f][4 * r], &le[f][4 * r], rb[f][r], rl[f][r], opt.clip.on() ? &ce[f][r] : nullptr);
                               if (!write_all(outs.f[4].fd, log.data(), log.size(), "trim", outs.f[4].tmp, err)) return (int)PF_ERR_ARG;   // (err is worded)
                           }
                           for (int d = 0; d < 4; ++d) {
@@ -213,6 +245,7 @@ int trim_fastq_pair(const std::string &in1, const std::string &in2, const std::s
         gzo[d]->stop();
     }
     for (int d = 0; d < 4 && err.empty(); ++d) err = opt.gz_out ? gzo[d]->wr.err : wr[d].err;
+    if (err.empty()) trim_clip_report(ctx, opt, adapters, clip, err);
     if (!err.empty() || outs.commit(err)) return 1;
     if (times) {
         times->stream_s = since(t_stream);

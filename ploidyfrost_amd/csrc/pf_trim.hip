@@ -10,6 +10,7 @@
 //              the row), and the row reduces "first" / "last" with four xor-shuffles.  The masks depend on the bytes only, never on b.
 //              A read of up to 256 - 15 bytes is staged once for all steps; a longer one loops, each step over the row steps that
 //              its [b, e) touches, forwards or backwards, and stops at the first hit.  Output: (begin, len) per record, len 0 = dropped.
+//              With a clip open (pf_clip_begin), K-CLIP (pf_clip.hip) runs first and the interval starts as [0, clip end).
 //   sizes      k_trim_sizes, one thread a record: output bytes per destination (1 single-ended, 4 for a pair: o1 u1 o2 u2), the pair
 //              statistics.
 //   offsets    scan_exclusive_u32_u64 over the destinations laid end to end.
@@ -24,6 +25,7 @@
 #include <string>
 
 #include "../../include/ploidyfrost_hip.h"
+#include "pf_clip_dev.hpp"
 #include "pf_ctx.hpp"
 #include "pf_reads_dev.hpp"
 #include "pf_scan.hpp"
@@ -147,7 +149,8 @@ static int trim_core(pf_ctx *ctx, const char *who_c, int n_files, const char *co
     *n_records = 0;
     if (bad_record) *bad_record = 0;
     if (stats) for (int f = 0; f < n_files; ++f) stats[f] = pf_trim_stats{};
-    { const std::string why = trim_steps_refusal(steps, n_steps, phred); if (!why.empty()) return refuse(why); }
+    clip_forget(ctx);
+    { const std::string why = trim_steps_refusal(steps, n_steps, phred, clip_is_open(ctx)); if (!why.empty()) return refuse(why); }
     for (int f = 0; f < n_files; ++f) {
         if (n_bytes[f] && !text[f]) return refuse("text is needed");
         if (n_bytes[f] > 0xFFFFFF00ull) return refuse("a chunk holds fewer than 2^32 bytes (line starts are 32 bits)");
@@ -191,7 +194,8 @@ static int trim_core(pf_ctx *ctx, const char *who_c, int n_files, const char *co
     const uint64_t n_size = (uint64_t)n_dest * n + 1;
     const size_t rec_bytes = up256((size_t)n * 4), size_bytes = up256((size_t)n_size * 4), offs_bytes = up256((size_t)n_size * 8),
                  scr_bytes = up256(scan_scratch_bytes(n_size));
-    char *ww = static_cast<char *>(ctx_ws(ctx, WS_TRIM_WORK, 4 * rec_bytes + size_bytes + offs_bytes + scr_bytes + 256));
+    const bool clip = clip_is_open(ctx);   // K-CLIP: two more arrays behind the counters
+    char *ww = static_cast<char *>(ctx_ws(ctx, WS_TRIM_WORK, 4 * rec_bytes + size_bytes + offs_bytes + scr_bytes + 256 + (clip ? 2 * rec_bytes : 0)));
     if (!ww) return PF_ERR_HIP;
     uint32_t *d_begin[2] = {reinterpret_cast<uint32_t *>(ww), reinterpret_cast<uint32_t *>(ww + rec_bytes)};
     uint32_t *d_len[2] = {reinterpret_cast<uint32_t *>(ww + 2 * rec_bytes), reinterpret_cast<uint32_t *>(ww + 3 * rec_bytes)};
@@ -200,10 +204,17 @@ static int trim_core(pf_ctx *ctx, const char *who_c, int n_files, const char *co
     void *scratch = ww + 4 * rec_bytes + size_bytes + offs_bytes;
     TrimCounts *dc = reinterpret_cast<TrimCounts *>(ww + 4 * rec_bytes + size_bytes + offs_bytes + scr_bytes);
     PF_HIP(hipMemsetAsync(dc, 0, 2 * sizeof(TrimCounts), ctx->stream));
+    uint32_t *d_clip[2] = {nullptr, nullptr};
+    if (clip) {
+        const uint32_t *lines[2] = {ix[0].lines, ix[1].lines};
+        for (int f = 0; f < 2; ++f) d_clip[f] = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(dc) + 256 + f * rec_bytes);
+        const int rc = clip_launch(ctx, n_files, dt, n_bytes, lines, n, phred, d_clip);
+        if (rc) return rc;
+    }
     const TrimSteps ts = trim_steps_by_value(steps, n_steps, phred);
     for (int f = 0; f < n_files; ++f)
         k_trim_intervals<<<ctx_grid(ctx, n * TRIM_ROW, TRIM_BLOCK, 8), TRIM_BLOCK, 0, ctx->stream>>>(dt[f], n_bytes[f], ix[f].lines, n, ts, d_begin[f],
-                                                                                                     d_len[f], dc + f);
+                                                                                                     d_len[f], dc + f, d_clip[f]);
     k_trim_sizes<<<ctx_grid(ctx, n, TRIM_BLOCK, 8), TRIM_BLOCK, 0, ctx->stream>>>(ix[0].lines, d_len[0], n_files == 2 ? ix[1].lines : nullptr,
                                                                                   n_files == 2 ? d_len[1] : nullptr, n, d_size, dc);
     PF_HIP(scan_exclusive_u32_u64(d_size, d_offs, n_size, scratch, ctx->stream));

@@ -1,5 +1,6 @@
 // What K-TRIM (pf_trim.hip) and K-TRIMCOUNT (pf_trimcount.hip) share on the device: the steps of a call by value, the per-file
-// counters, and k_trim_intervals -- the interval [b, e) of every record of a chunk (the rule: pf_trim_rule.hpp).  Kernels are `static`:
+// counters, and k_trim_intervals -- the interval [b, e) of every record of a chunk (the rule: pf_trim_rule.hpp), from [0, n) or, with
+// a clip open (pf_clip_dev.hpp), from [0, clip end).  Kernels are `static`:
 // each of the two files carries its own copy (no device-side calls across files), as with pf_reads_dev.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -54,7 +55,8 @@ __device__ inline void row_sync() {
 // ---- intervals ----
 [[maybe_unused]] static __global__ __launch_bounds__(TRIM_BLOCK) void k_trim_intervals(const char *__restrict__ text, uint64_t n_bytes, const uint32_t *__restrict__ lines,
                                                                uint64_t n_rec, const TrimSteps ts, uint32_t *__restrict__ rec_begin,
-                                                               uint32_t *__restrict__ rec_len, TrimCounts *c) {
+                                                               uint32_t *__restrict__ rec_len, TrimCounts *c,
+                                                               const uint32_t *__restrict__ clip_end = nullptr) {
     __shared__ uint4 s_q[TRIM_ROWS][TRIM_UNITS];
     const int rl = (int)threadIdx.x & (TRIM_ROW - 1), row = (int)threadIdx.x / TRIM_ROW;
     uint4 *sq = s_q[row];
@@ -65,8 +67,8 @@ __device__ inline void row_sync() {
         const uint32_t qb = lines[8 * r + 6], n = lines[8 * r + 7] - qb;
         const uint64_t unit0 = qb >> 4;          // the aligned unit that holds the line's first byte
         const uint32_t mis = qb & 15u;           // position p of the read is byte mis + p from there
-        uint32_t b = 0, e = n;
-        bool alive = n > 0;                      // (every step keeps e > b while the read lives)
+        uint32_t b = 0, e = clip_end ? clip_end[r] : n;   // K-CLIP (pf_clip.hip): the interval starts as [0, clip end), 0 = dropped
+        bool alive = e > 0;                      // (every step keeps e > b while the read lives)
         int64_t staged = -1;
         // row step `chunk` of the line into the row's LDS; position of byte x of it: chunk * 256 + x - mis
         auto stage = [&](int64_t chunk) {
@@ -163,10 +165,11 @@ __device__ inline void row_sync() {
 
 // ---- host side ----
 // the steps and the offset of one call: "" = accepted, else the refusal as K-TRIM words it (without the caller's name)
-static inline std::string trim_steps_refusal(const pf_trim_step *steps, uint32_t n_steps, uint32_t phred) {
+// (clip_open: a clip is open on the context, and no step beside it is a plan as well)
+static inline std::string trim_steps_refusal(const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, bool clip_open = false) {
     uint32_t bad_step = 0;
     const int c = pf_trim::steps_clause(reinterpret_cast<const pf_trim::Step *>(steps), n_steps, phred, &bad_step);
-    if (!c) return "";
+    if (!c || (c == pf_trim::REFUSE_NO_STEP && clip_open && n_steps == 0)) return "";
     if (c == pf_trim::REFUSE_PHRED) return std::string(pf_trim::refusal_text(c)) + ", not " + std::to_string(phred);
     if (c == pf_trim::REFUSE_NO_STEP || c == pf_trim::REFUSE_TOO_MANY) return pf_trim::refusal_text(c);
     return "step " + std::to_string(bad_step) + ": " + pf_trim::refusal_text(c);

@@ -4,6 +4,7 @@
 //
 //   index      fastq_index of pf_reads_dev.hpp, asked for the extents of all four lines of a record (K-TRIM's).
 //   intervals  k_trim_intervals of pf_trim_dev.hpp, the kernel of K-TRIM itself: (begin, len) per record, len 0 = dropped.
+//              With a clip open, K-CLIP (pf_clip.hip) runs first and the interval starts as [0, clip end).
 //   table      k_trimcount_keep, one thread a record: (begin, len) of file 1 (and of file 2), the hand-on predicate
 //              (pf_trimrun::handed_on: kept, and for a pair kept in both files), a keep flag of 4 bytes, the pair statistics.  One
 //              exclusive scan of the flags (pf_scan.hpp).  k_trimcount_scatter, one thread a record: (seq_begin + b, e - b) per file to
@@ -27,6 +28,7 @@
 #include <string>
 
 #include "../../include/ploidyfrost_hip.h"
+#include "pf_clip_dev.hpp"
 #include "pf_count_dev.hpp"
 #include "pf_ctx.hpp"
 #include "pf_reads_dev.hpp"
@@ -109,6 +111,7 @@ static int trim_table_core(pf_ctx *ctx, const std::string &who, int n_files, con
     auto refuse = [&](const std::string &m) { pf::CtxErr{ctx} = who + ": " + m; return (int)PF_ERR_ARG; };
     T = TrimTable{};
     T.n_files = n_files;
+    clip_forget(ctx);
 
     // ---- index ----
     FastqIndex ix[2];
@@ -139,7 +142,8 @@ static int trim_table_core(pf_ctx *ctx, const std::string &who, int n_files, con
     // ---- intervals, flags, places, table ----
     const size_t rec_bytes = up256((size_t)n * 4), flag_bytes = up256((size_t)(n + 1) * 4), off_bytes = up256((size_t)n * 8),
                  scr_bytes = up256(scan_scratch_bytes(n + 1));
-    char *ww = static_cast<char *>(ctx_ws(ctx, WS_TRIM_WORK, 6 * rec_bytes + 2 * flag_bytes + 2 * off_bytes + scr_bytes + 256));
+    const bool clip = clip_is_open(ctx);   // K-CLIP: two more arrays behind the counters
+    char *ww = static_cast<char *>(ctx_ws(ctx, WS_TRIM_WORK, 6 * rec_bytes + 2 * flag_bytes + 2 * off_bytes + scr_bytes + 256 + (clip ? 2 * rec_bytes : 0)));
     if (!ww) return PF_ERR_HIP;
     char *at = ww;
     auto take = [&](size_t bytes) { char *p = at; at += bytes; return p; };
@@ -154,10 +158,17 @@ static int trim_table_core(pf_ctx *ctx, const std::string &who, int n_files, con
     TrimCounts *dc = reinterpret_cast<TrimCounts *>(take(256));
     static_assert(2 * sizeof(TrimCounts) <= 256, "the counters of both files lie in the 256 bytes behind the work arrays");
     PF_HIP(hipMemsetAsync(dc, 0, 2 * sizeof(TrimCounts), ctx->stream));
+    uint32_t *d_clip[2] = {nullptr, nullptr};
+    if (clip) {
+        const uint32_t *lines[2] = {ix[0].lines, ix[1].lines};
+        for (int f = 0; f < 2; ++f) d_clip[f] = reinterpret_cast<uint32_t *>(take(rec_bytes));
+        const int rc = clip_launch(ctx, n_files, T.text, n_bytes, lines, n, plan->phred, d_clip);
+        if (rc) return rc;
+    }
     const TrimSteps ts = trim_steps_by_value(plan->steps, plan->n_steps, plan->phred);
     for (int f = 0; f < n_files; ++f)
         k_trim_intervals<<<ctx_grid(ctx, n * TRIM_ROW, TRIM_BLOCK, 8), TRIM_BLOCK, 0, ctx->stream>>>(T.text[f], n_bytes[f], ix[f].lines, n, ts, d_begin[f],
-                                                                                                     d_len[f], dc + f);
+                                                                                                     d_len[f], dc + f, d_clip[f]);
     k_trimcount_keep<<<ctx_grid(ctx, n, TRIM_BLOCK, 8), TRIM_BLOCK, 0, ctx->stream>>>(d_len[0], n_files == 2 ? d_len[1] : nullptr, n, d_keep, dc);
     PF_HIP(scan_exclusive_u32(d_keep, d_pos, n + 1, scratch, ctx->stream));
     TrimScatterArgs sa = {};
@@ -213,7 +224,7 @@ static int trim_table_args(pf_ctx *ctx, const std::string &who, int n_files, con
     auto refuse = [&](const std::string &m) { pf::CtxErr{ctx} = who + ": " + m; return (int)PF_ERR_ARG; };
     if (!bytes_used) return refuse("bytes_used is needed");
     if (!plan) return refuse("a plan is needed");
-    { const std::string why = trim_steps_refusal(plan->steps, plan->n_steps, plan->phred); if (!why.empty()) return refuse(why); }
+    { const std::string why = trim_steps_refusal(plan->steps, plan->n_steps, plan->phred, clip_is_open(ctx)); if (!why.empty()) return refuse(why); }
     for (int f = 0; f < n_files; ++f) {
         if (n_bytes[f] && !text[f]) return refuse("text is needed");
         if (n_bytes[f] > 0xFFFFFF00ull) return refuse("a chunk holds fewer than 2^32 bytes (line starts are 32 bits)");

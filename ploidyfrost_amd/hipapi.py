@@ -44,6 +44,8 @@ K_INFLATE = K_TRIMCOUNT + 1    # PF_K_INFLATE ("k_inflate"): everything one pf_i
 K_GUNZIP = K_INFLATE + 1       # PF_K_GUNZIP ("k_gunzip"): everything one pf_inflate_gzip launches; unit: inflated bytes
 K_FASTA = K_GUNZIP + 1         # PF_K_FASTA ("k_fasta"): everything the index of one pf_fasta_index / pf_*_fasta call launches; unit: bytes of the chunk
 K_DEFLATE = K_FASTA + 1        # PF_K_DEFLATE ("k_deflate"): everything one pf_deflate_bgzf launches; unit: bytes of text
+K_CLIP = K_DEFLATE + 1         # PF_K_CLIP ("k_clip"): the clipping kernels of one trim / trimmed-count call while a clip is open; unit: records
+CLIP_STATS = np.dtype([(f, "<u8", (2,)) for f in ("reads_clipped", "reads_dropped", "bases_clipped", "candidates_scored")])   # pf_clip_stats
 FASTA_TILE = 4096              # PF_FASTA_TILE: bytes of the chunk one block of K-FASTA's compaction kernel takes at a time
 GUNZIP_RESULT = np.dtype([("out_bytes", "<u8"), ("end_bit", "<u8"), ("final", "<u4"), ("n_window", "<u4"), ("crc_raw", "<u4"), ("clause", "<u4"),
                           ("clause_bit", "<u8")])   # pf_gunzip_result
@@ -276,6 +278,10 @@ def load_library() -> C.CDLL:
         "pf_count_fastq_pair_trimmed": (i, [vp, vp, u64, vp, u64, i, vp, C.POINTER(u64), vp, vp, C.POINTER(u64)]),
         "pf_maskcount_fastq_trimmed": (i, [vp, vp, u64, i, vp, u32, u32, C.POINTER(u64), vp, vp, C.POINTER(u64)]),
         "pf_maskcount_fastq_pair_trimmed": (i, [vp, vp, u64, vp, u64, i, vp, u32, u32, C.POINTER(u64), vp, vp, C.POINTER(u64)]),
+        "pf_clip_begin": (i, [vp, vp, vp, vp, u32, u32, u32]),
+        "pf_clip_stats_get": (i, [vp, vp]),
+        "pf_clip_end": (i, [vp]),
+        "pf_clip_last_ends": (i, [vp, i, vp, u64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError = header / library mismatch
@@ -305,7 +311,8 @@ DECLARED_SYMBOLS = ["pf_create", "pf_warmup", "pf_destroy", "pf_last_error", "pf
                     "pf_kmer_union", "pf_color_kmers", "pf_release_counts",
                     "pf_trim_table_fastq", "pf_trim_table_fastq_pair", "pf_count_fastq_trimmed", "pf_count_fastq_pair_trimmed",
                     "pf_maskcount_fastq_trimmed", "pf_maskcount_fastq_pair_trimmed", "pf_inflate_bgzf", "pf_inflate_gzip", "pf_device_alloc", "pf_copy",
-                    "pf_fasta_index", "pf_fasta_index_fetch", "pf_count_fasta", "pf_maskcount_fasta", "pf_color_fasta", "pf_deflate_bgzf"]
+                    "pf_fasta_index", "pf_fasta_index_fetch", "pf_count_fasta", "pf_maskcount_fasta", "pf_color_fasta", "pf_deflate_bgzf",
+                    "pf_clip_begin", "pf_clip_stats_get", "pf_clip_end", "pf_clip_last_ends"]
 
 
 class TrimPlan(C.Structure):   # pf_trim_plan
@@ -632,6 +639,39 @@ class Device:
             raise e
         return dict(out=out[: out_n.value], bytes_used=used.value, n_records=recs.value, begin=begin[: recs.value], len=ln[: recs.value],
                     stats={f: int(stats[0][f]) for f in TRIM_STATS.names})
+
+    def clip_begin(self, adapters, seed: int = 2, score: int = 10):
+        """K-CLIP (pf_clip_begin): opens a clip on the context -- until clip_end() trim_fastq, trim_fastq_pair, trim_table_fastq[_pair] and
+        the *_trimmed count calls clip adapter read-through first and take an empty list of steps.  adapters: a list of (sequence,
+        side) pairs (side 0: both files, 1, 2), or the dict of hostapi.clip_parse_adapters.  Refusals raise DeviceError by name."""
+        if isinstance(adapters, dict):
+            bases, off, side = adapters["bases"], adapters["off"], adapters["side"]
+        else:
+            seqs = [s.encode() if isinstance(s, str) else bytes(s) for s, _ in adapters]
+            bases = b"".join(seqs)
+            off = np.concatenate([[0], np.cumsum([len(s) for s in seqs])]) if seqs else np.zeros(1)
+            side = [sd for _, sd in adapters]
+        bases = np.frombuffer(bytes(bases), dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        side = np.ascontiguousarray(side, dtype=np.uint8)
+        self._check(self.L.pf_clip_begin(self.h, bases.ctypes.data if len(bases) else None, off.ctypes.data, side.ctypes.data if len(side) else None,
+                                         len(side), int(seed), int(score)))
+
+    def clip_stats(self) -> dict:
+        """pf_clip_stats_get: what the open clip has counted since clip_begin, each field [file 1 and single-ended calls, file 2]"""
+        st = np.zeros(1, dtype=CLIP_STATS)
+        self._check(self.L.pf_clip_stats_get(self.h, st.ctypes.data))
+        return {f: [int(v) for v in st[0][f]] for f in CLIP_STATS.names}
+
+    def clip_last_ends(self, n_records: int, file: int = 0) -> np.ndarray:
+        """pf_clip_last_ends: the clip ends (u32; n untouched, 0 dropped) of the first n_records records of file 0 or 1 of the last call"""
+        out = np.zeros(n_records, dtype=np.uint32)
+        self._check(self.L.pf_clip_last_ends(self.h, file, out.ctypes.data if n_records else None, n_records))
+        return out
+
+    def clip_end(self):
+        """pf_clip_end: closes the clip; the trim calls are what they were without one"""
+        self._check(self.L.pf_clip_end(self.h))
 
     def inflate_bgzf(self, comp, member_off, out=None, out_cap=None):
         """K-INFLATE (pf_inflate_bgzf): the BGZF members comp[member_off[m] : member_off[m + 1]] inflated one behind the other; returns

@@ -50,7 +50,9 @@ DECLARED_SYMBOLS = ["pfh_open", "pfh_close", "pfh_last_error", "pfh_set_output_d
                     "pfh_inflate_parse_member", "pfh_inflate_member", "pfh_inflate_bgzf_member", "pfh_inflate_crc32", "pfh_inflate_crc32_sliced",
                     "pfh_inflate_file_clause", "pfh_inflate_clause_text", "pfh_reads_gz", "pfh_reads_fasta", "pfh_fasta_index", "pfh_fasta_clause_text",
                     "pfh_gunzip_header", "pfh_gunzip_file_kind", "pfh_gunzip_candidate", "pfh_gunzip_call", "pfh_gunzip_file", "pfh_gunzip_clause_text",
-                    "pfh_deflate_member", "pfh_deflate_bound", "pfh_reads_gz_out"]
+                    "pfh_deflate_member", "pfh_deflate_bound", "pfh_reads_gz_out",
+                    "pfh_reads_adapters", "pfh_reads_adapters_report", "pfh_clip_parse_adapters", "pfh_clip_refusal_text", "pfh_clip_read",
+                    "pfh_trim_fastq_chunk_clip"]
 
 
 class RunOptions(C.Structure):   # pfh_run_options (include/ploidyfrost_host.h)
@@ -269,6 +271,22 @@ def load_library() -> C.CDLL:
     L.pfh_reads_gz.argtypes = [C.c_int]
     L.pfh_reads_gz_out.restype = None
     L.pfh_reads_gz_out.argtypes = [C.c_int]
+    L.pfh_reads_adapters.restype = None
+    L.pfh_reads_adapters.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32]
+    L.pfh_reads_adapters_report.restype = None
+    L.pfh_reads_adapters_report.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p]
+    L.pfh_clip_parse_adapters.restype = C.c_int
+    L.pfh_clip_parse_adapters.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                          C.POINTER(C.c_uint64)]
+    L.pfh_clip_refusal_text.restype = C.c_char_p
+    L.pfh_clip_refusal_text.argtypes = [C.c_int]
+    L.pfh_clip_read.restype = C.c_int
+    L.pfh_clip_read.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    L.pfh_trim_fastq_chunk_clip.restype = C.c_int
+    L.pfh_trim_fastq_chunk_clip.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                            C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p,
+                                            C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
     L.pfh_reads_fasta.restype = None
     L.pfh_reads_fasta.argtypes = [C.c_int]
     L.pfh_fasta_index.restype = C.c_int
@@ -610,6 +628,111 @@ def trim_fastq_chunk(text: bytes, steps, phred: int = 33, final: bool = True):
                 begin=begin[: recs.value].tolist(), len=ln[: recs.value].tolist(), stats={f: int(v) for f, v in zip(TRIM_STATS_FIELDS, stats)})
 
 
+CLIP_STATS_FIELDS = ("reads_clipped", "reads_dropped", "bases_clipped", "candidates_scored")   # pf_clip_stats: each [file 1, file 2]
+CLIP_REFUSALS = ("none", "not_fasta", "byte", "length", "too_many", "no_adapter", "seed", "score", "side")   # pf_clip::Refusal, in its order
+CLIP_MAX_ADAPTERS, CLIP_MAX_LEN = 64, 128
+
+
+def clip_parse_adapters(path_or_bytes) -> dict:
+    """The adapter file of `--adapters` by the parser of the rule header (pfh_clip_parse_adapters, csrc/pf_clip_rule.hpp; no device):
+    dict with bases (the usable adapters one behind the other, upper case), off (n + 1 offsets), side (0 both files, 1, 2), n and
+    skipped (the `Prefix` entries of palindrome mode, which is not built).  bytes are the file's text, anything else a path.  A file
+    that is refused raises ValueError with the refusal's text and the 1-based record; .refusal names it, .bad_record holds the record."""
+    L = load_library()
+    if isinstance(path_or_bytes, (bytes, bytearray)):
+        text, where = bytes(path_or_bytes), "adapters"
+    else:
+        with open(path_or_bytes, "rb") as f:
+            text = f.read()
+        where = "adapters %s" % os.fsdecode(path_or_bytes)
+    src = np.frombuffer(text, dtype=np.uint8)
+    bases = np.zeros(CLIP_MAX_ADAPTERS * CLIP_MAX_LEN, dtype=np.uint8)
+    off = np.zeros(CLIP_MAX_ADAPTERS + 1, dtype=np.uint32)
+    side = np.zeros(CLIP_MAX_ADAPTERS, dtype=np.uint8)
+    n, skipped, bad = C.c_uint32(), C.c_uint32(), C.c_uint64()
+    c = L.pfh_clip_parse_adapters(src.ctypes.data if len(src) else None, len(src), bases.ctypes.data, len(bases), off.ctypes.data, side.ctypes.data,
+                                  C.byref(n), C.byref(skipped), C.byref(bad))
+    if c:
+        e = ValueError("%s: %s%s" % (where, "record %d: " % bad.value if bad.value else "", L.pfh_clip_refusal_text(c).decode()))
+        e.refusal, e.bad_record = CLIP_REFUSALS[c], bad.value
+        raise e
+    return dict(bases=bases[: off[n.value]].tobytes(), off=off[: n.value + 1].copy(), side=side[: n.value].copy(), n=n.value, skipped=skipped.value)
+
+
+def clip_adapters(adapters) -> dict:
+    """adapters as the clip calls take them: the dict of clip_parse_adapters, a path or the bytes of an adapter file, or a list of
+    (sequence, side) pairs (nothing is checked there: the library refuses by name)."""
+    if isinstance(adapters, dict):
+        return adapters
+    if isinstance(adapters, (list, tuple)):
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s, _ in adapters]
+        off = np.zeros(len(seqs) + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64) if seqs else []
+        return dict(bases=b"".join(seqs), off=off, side=np.array([sd for _, sd in adapters], dtype=np.uint8), n=len(seqs), skipped=0)
+    return clip_parse_adapters(adapters)
+
+
+def clip_read(seq: bytes, qual: bytes, adapters, side: int = 1, seed: int = 2, score: int = 10, phred: int = 33, scored: bool = False):
+    """The rule of `--adapters` on one read of file `side` (1 or 2) (pfh_clip_read; no device): the clip end -- len(seq) for an untouched
+    read, 0 for a dropped one; scored=True: (clip end, the candidates whose seed held).  Values that are refused raise ValueError."""
+    L = load_library()
+    A = clip_adapters(adapters)
+    s, q = np.frombuffer(bytes(seq), dtype=np.uint8), np.frombuffer(bytes(qual), dtype=np.uint8)
+    if len(s) != len(q):
+        raise ValueError("clip_read: the quality line is as long as the sequence line")
+    bases = np.frombuffer(A["bases"], dtype=np.uint8)
+    end, sc = C.c_uint32(), C.c_uint64()
+    rc = L.pfh_clip_read(s.ctypes.data if len(s) else None, q.ctypes.data if len(q) else None, len(s), bases.ctypes.data if len(bases) else None,
+                         A["off"].ctypes.data, A["side"].ctypes.data if A["n"] else None, A["n"], int(side), int(seed), int(score), int(phred),
+                         C.byref(end), C.byref(sc))
+    if rc < 0:
+        raise ValueError(L.pfh_last_error(None).decode())
+    return (end.value, sc.value) if scored else end.value
+
+
+def trim_fastq_chunk_clip(text: bytes, steps, adapters, side: int = 1, seed: int = 2, score: int = 10, phred: int = 33, final: bool = True):
+    """What pf_trim_fastq gives for one chunk while a clip is open, by the host's plain restatement (pfh_trim_fastq_chunk_clip; no
+    device): the dict of trim_fastq_chunk and "clip" = the statistics of CLIP_STATS_FIELDS, each [file 1, file 2].  steps may be empty."""
+    L = load_library()
+    st = trim_parse_steps(steps) if len(steps) else np.zeros(0, dtype=TRIM_STEP)
+    A = clip_adapters(adapters)
+    bases = np.frombuffer(A["bases"], dtype=np.uint8)
+    src = np.frombuffer(bytes(text), dtype=np.uint8)
+    n = len(src)
+    out = np.zeros(n + 1, dtype=np.uint8)
+    cap = n // 4 + 1
+    begin, ln = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32)
+    stats = np.zeros(len(TRIM_STATS_FIELDS), dtype=np.uint64)
+    clip = np.zeros((len(CLIP_STATS_FIELDS), 2), dtype=np.uint64)
+    out_n, used, recs, bad = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    clause = L.pfh_trim_fastq_chunk_clip(src.ctypes.data if n else None, n, int(final), st.ctypes.data if len(st) else None, len(st), phred,
+                                         bases.ctypes.data if len(bases) else None, A["off"].ctypes.data, A["side"].ctypes.data if A["n"] else None, A["n"],
+                                         int(side), int(seed), int(score), out.ctypes.data, C.byref(out_n), C.byref(used), begin.ctypes.data, ln.ctypes.data,
+                                         cap, C.byref(recs), stats.ctypes.data, clip.ctypes.data, C.byref(bad))
+    if clause < 0:
+        raise ValueError(L.pfh_last_error(None).decode())
+    return dict(clause=MASK_CLAUSES[clause], bad_record=bad.value, out=out[: out_n.value].tobytes(), bytes_used=used.value, n_records=recs.value,
+                begin=begin[: recs.value].tolist(), len=ln[: recs.value].tolist(), stats={f: int(v) for f, v in zip(TRIM_STATS_FIELDS, stats)},
+                clip={f: [int(v) for v in row] for f, row in zip(CLIP_STATS_FIELDS, clip)})
+
+
+def _set_adapters(L, adapters, seed, score):
+    """`--adapters` of the next trim / run call (pfh_reads_adapters): a path, or None for no clipping"""
+    L.pfh_reads_adapters(None if adapters is None else os.fsencode(adapters), int(seed), int(score))
+
+
+def clip_report() -> dict:
+    """What the last trim / run call of this thread that took adapters= reported (pfh_reads_adapters_report): adapters, skipped and the
+    statistics of CLIP_STATS_FIELDS, each [file 1, file 2] -- the command's `clip:` line."""
+    L = load_library()
+    a, p = C.c_uint32(), C.c_uint32()
+    st = np.zeros((len(CLIP_STATS_FIELDS), 2), dtype=np.uint64)
+    L.pfh_reads_adapters_report(C.byref(a), C.byref(p), st.ctypes.data)
+    out = dict(adapters=a.value, skipped=p.value)
+    out.update({f: [int(v) for v in row] for f, row in zip(CLIP_STATS_FIELDS, st)})
+    return out
+
+
 TRIM_TABLE_CLAUSES = MASK_CLAUSES + ("pair_count",)   # pf_mask::Clause, then pf_trimrun::CLAUSE_PAIR_COUNT
 
 
@@ -657,19 +780,23 @@ def _gz_mode(gz) -> int:
     return int(bool(gz))
 
 
-def trim_fastq(inputs, out: str, steps, phred: int = 33, trimlog=None, chunk_bytes: int = 0, gz: bool = False, gz_out: bool = False) -> dict:
+def trim_fastq(inputs, out: str, steps, phred: int = 33, trimlog=None, chunk_bytes: int = 0, gz: bool = False, gz_out: bool = False,
+               adapters=None, adapter_seed: int = 2, adapter_score: int = 10) -> dict:
     """`ploidyfrost trim -i ... -o out STEP...` (pfh_trim_fastq): the reads of the FASTQ file(s) `inputs`, one after the other,
     quality-trimmed by `steps` (Trimmomatic's words) into `out`; trimlog: a file with one line per record.  Returns the statistics.  A
     refusal raises RuntimeError (format refusals with the input's path and the 1-based record number); nothing is left under any
-    output name.  gz_out (`--gz-out`): `out` is written as blocked gzip, deflated on the device (K-DEFLATE)."""
+    output name.  gz_out (`--gz-out`): `out` is written as blocked gzip, deflated on the device (K-DEFLATE).
+    adapters (`--adapters`): the path of an adapter file -- adapter read-through is clipped on the device before the steps (K-CLIP;
+    adapter_seed, adapter_score: `--adapter-seed`, `--adapter-score`); steps may then be empty; clip_report() gives the `clip:` line."""
     L = load_library()
     if isinstance(inputs, (str, bytes, os.PathLike)):
         inputs = [inputs]
-    st = trim_parse_steps(steps)
+    st = trim_parse_steps(steps) if len(steps) or adapters is None else np.zeros(0, dtype=TRIM_STEP)
     paths = (C.c_char_p * max(len(inputs), 1))(*[os.fsencode(p) for p in inputs])
     stats = np.zeros(len(TRIM_STATS_FIELDS), dtype=np.uint64)
     L.pfh_reads_gz(_gz_mode(gz))
     L.pfh_reads_gz_out(int(gz_out))
+    _set_adapters(L, adapters, adapter_seed, adapter_score)
     rc = L.pfh_trim_fastq(paths, len(inputs), os.fsencode(out), st.ctypes.data if len(st) else None, len(st), phred,
                           os.fsencode(trimlog) if trimlog else None, int(chunk_bytes), 0, stats.ctypes.data)
     if rc:
@@ -677,16 +804,19 @@ def trim_fastq(inputs, out: str, steps, phred: int = 33, trimlog=None, chunk_byt
     return {f: int(v) for f, v in zip(TRIM_STATS_FIELDS, stats)}
 
 
-def trim_fastq_pair(in1: str, in2: str, outs, steps, phred: int = 33, trimlog=None, chunk_bytes: int = 0, gz: bool = False, gz_out: bool = False):
+def trim_fastq_pair(in1: str, in2: str, outs, steps, phred: int = 33, trimlog=None, chunk_bytes: int = 0, gz: bool = False, gz_out: bool = False,
+                    adapters=None, adapter_seed: int = 2, adapter_score: int = 10):
     """`ploidyfrost trim -1 in1 -2 in2 -o1 .. -u1 .. -o2 .. -u2 .. STEP...` (pfh_trim_fastq_pair): outs = (o1, u1, o2, u2).  Returns the
-    statistics of file 1 and of file 2 (the pair fields are the same in both).  gz_out (`--gz-out`): the four outputs are blocked gzip."""
+    statistics of file 1 and of file 2 (the pair fields are the same in both).  gz_out (`--gz-out`): the four outputs are blocked gzip.
+    adapters, adapter_seed, adapter_score: as trim_fastq takes them (names ending in /1 and /2 choose the file)."""
     L = load_library()
-    st = trim_parse_steps(steps)
+    st = trim_parse_steps(steps) if len(steps) or adapters is None else np.zeros(0, dtype=TRIM_STEP)
     assert len(outs) == 4
     paths = (C.c_char_p * 4)(*[os.fsencode(p) for p in outs])
     stats = np.zeros((2, len(TRIM_STATS_FIELDS)), dtype=np.uint64)
     L.pfh_reads_gz(_gz_mode(gz))
     L.pfh_reads_gz_out(int(gz_out))
+    _set_adapters(L, adapters, adapter_seed, adapter_score)
     rc = L.pfh_trim_fastq_pair(os.fsencode(in1), os.fsencode(in2), paths, st.ctypes.data if len(st) else None, len(st), phred,
                                os.fsencode(trimlog) if trimlog else None, int(chunk_bytes), 0, stats.ctypes.data)
     if rc:
@@ -832,7 +962,8 @@ def build_graph(inputs, out_prefix: str, k: int = 25, clip_tips: bool = False, d
 def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 ** 9, cs: int = 10000, q: float = 0.998, mask_upper=None,
               keep_tips: bool = False, keep_isolated: bool = False, g=None, z: int = 8, M: float = 2.0, D: float = -1.0, G: float = -3.0,
               threads: int = 1, model=None, model_only: bool = False, db_out=None, gfa_out=None, chunk_bytes: int = 0,
-              initial_slots: int = 0, steps=None, phred: int = 33, pairs=None, gz: bool = False, fasta: bool = False) -> dict:
+              initial_slots: int = 0, steps=None, phred: int = 33, pairs=None, gz: bool = False, fasta: bool = False,
+              adapters=None, adapter_seed: int = 2, adapter_score: int = 10) -> dict:
     """`ploidyfrost run` (pfh_run_fastq): reads to ploidy estimate in one process -- the FASTQ file(s) `inputs` counted, the thresholds
     derived, the k-mers of the masked reads counted (K-MASKCOUNT), the graph built and the single-sample calling run made on one device
     context; PloidyFrost_output/<out_prefix>_*.txt in the working directory.  model: None, "cov" or "fre".  Returns the fields of the
@@ -842,13 +973,15 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
     only when both are kept.  The result then has "trim" as well: the statistics of every unit (one dict for all single-ended inputs;
     per pair a list of two, file 1 and file 2), as the command's `trim:` lines give them.
     fasta (`--fasta`): an input whose first byte is '>' (with gz: whose first inflated byte is) is read as FASTA in both passes (K-FASTA);
-    refused by name together with steps or pairs."""
+    refused by name together with steps or pairs.
+    adapters (`--adapters`, with adapter_seed and adapter_score): as trim_fastq takes them; they turn the trimming on as steps do, and
+    no step is needed beside them, also with pairs."""
     L = load_library()
     if pairs is not None:
         if inputs is not None:
             raise ValueError("run_reads: either inputs or pairs")
         inputs = [f for p in pairs for f in p]
-    st = trim_parse_steps(steps) if steps is not None else np.zeros(0, dtype=TRIM_STEP)
+    st = trim_parse_steps(steps) if steps is not None and (len(steps) or adapters is None) else np.zeros(0, dtype=TRIM_STEP)   # (adapters alone: no step)
     paths, n = _paths(inputs)
     o = RunOptions()
     L.pfh_run_defaults(C.byref(o))
@@ -867,7 +1000,7 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
     o.db_out = None if db_out is None else os.fsencode(db_out)
     o.gfa_out = None if gfa_out is None else os.fsencode(gfa_out)
     stats = np.zeros(len(RUN_STATS_FIELDS), dtype=np.uint64)
-    if steps is None and pairs is None:
+    if steps is None and pairs is None and adapters is None:
         L.pfh_reads_gz(_gz_mode(gz))
         L.pfh_reads_fasta(int(bool(fasta)))
         rc = L.pfh_run_fastq(paths, n, os.fsencode(out_prefix), C.byref(o), 0, stats.ctypes.data)
@@ -877,6 +1010,7 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
     per = np.zeros((max(n, 1), len(TRIM_STATS_FIELDS)), dtype=np.uint64)
     L.pfh_reads_gz(_gz_mode(gz))
     L.pfh_reads_fasta(int(bool(fasta)))
+    _set_adapters(L, adapters, adapter_seed, adapter_score)
     rc = L.pfh_run_fastq_trimmed(paths, n, int(pairs is not None), st.ctypes.data if len(st) else None, len(st), int(phred), os.fsencode(out_prefix),
                                  C.byref(o), 0, stats.ctypes.data, per.ctypes.data)
     if rc:
@@ -891,7 +1025,7 @@ def run_multi_reads(samples, out_prefix: str, k: int = 25, ci: int = 1, cx: int 
                     keep_tips: bool = False, keep_isolated: bool = False, g=None, z: int = 8, M: float = 2.0, D: float = -1.0, G: float = -3.0,
                     threads: int = 1, model=None, model_only: bool = False, filter_multi=None, each_color: bool = False, db_out=None, gfa_out=None,
                     chunk_bytes: int = 0, initial_slots: int = 0, steps=None, phred: int = 33, pairs=None, gz: bool = False,
-                    fasta: bool = False) -> dict:
+                    fasta: bool = False, adapters=None, adapter_seed: int = 2, adapter_score: int = 10) -> dict:
     """`ploidyfrost run-multi` (pfh_run_multi_fastq): reads of several samples to one estimate per sample in one process.  samples: a
     list of (name, file or list of files), a sample a colour in the order given.  Every sample is counted and its thresholds derived,
     the k-mers of its masked reads counted (K-MASKCOUNT), their union taken (K-UNION), the coloured graph built and coloured per
@@ -902,7 +1036,8 @@ def run_multi_reads(samples, out_prefix: str, k: int = 25, ci: int = 1, cx: int 
     steps: `run-multi STEP...` (pfh_run_multi_fastq_trimmed) -- the files are raw reads, trimmed on the way into both passes; pairs: the
     names of the samples whose files are pairs (file 1, file 2, file 1, ...).  The result then has "trim": per sample the statistics of
     its units, as run_reads gives them.
-    fasta (`--fasta`): as run_reads takes it; the files of a sample may mix FASTA and FASTQ."""
+    fasta (`--fasta`): as run_reads takes it; the files of a sample may mix FASTA and FASTQ.
+    adapters, adapter_seed, adapter_score: as run_reads takes them; they hold for every sample."""
     L = load_library()
     names, counts, flat, paired = [], [], [], []
     for name, files in samples:
@@ -912,7 +1047,7 @@ def run_multi_reads(samples, out_prefix: str, k: int = 25, ci: int = 1, cx: int 
         counts.append(len(files))
         flat.extend(files)
         paired.append(int(pairs is not None and name in pairs))
-    st = trim_parse_steps(steps) if steps is not None else np.zeros(0, dtype=TRIM_STEP)
+    st = trim_parse_steps(steps) if steps is not None and (len(steps) or adapters is None) else np.zeros(0, dtype=TRIM_STEP)   # (adapters alone: no step)
     c_names = (C.c_char_p * max(len(names), 1))(*names)
     n_of = np.ascontiguousarray(counts, dtype=np.uint32)
     paths, _ = _paths(flat)
@@ -938,12 +1073,13 @@ def run_multi_reads(samples, out_prefix: str, k: int = 25, ci: int = 1, cx: int 
     o.gfa_out = None if gfa_out is None else os.fsencode(gfa_out)
     stats = np.zeros(len(RUN_MULTI_STATS_FIELDS), dtype=np.uint64)
     per = np.zeros((max(len(names), 1), len(RUN_MULTI_COLOR_FIELDS)), dtype=np.uint64)
-    trimmed = steps is not None or pairs is not None
+    trimmed = steps is not None or pairs is not None or adapters is not None
     per_in = np.zeros((max(len(flat), 1), len(TRIM_STATS_FIELDS)), dtype=np.uint64)
     if trimmed:
         pair_of = np.ascontiguousarray(paired, dtype=np.int32)
         L.pfh_reads_gz(_gz_mode(gz))
         L.pfh_reads_fasta(int(bool(fasta)))
+        _set_adapters(L, adapters, adapter_seed, adapter_score)
         rc = L.pfh_run_multi_fastq_trimmed(c_names, n_of.ctypes.data if len(names) else None, pair_of.ctypes.data if len(names) else None, len(names), paths,
                                            st.ctypes.data if len(st) else None, len(st), int(phred), os.fsencode(out_prefix), C.byref(o),
                                            C.byref(multi) if multi is not None else None, int(each_color), 0, stats.ctypes.data, per.ctypes.data,
