@@ -76,7 +76,7 @@ enum pf_kernel {
     PF_K_GUNZIP, /* K-GUNZIP: everything one pf_inflate_gzip launches (find, count, chain, decode, window, resolve with the CRC), timed as one launch; unit: inflated bytes */
     PF_K_FASTA, /* K-FASTA: everything the index of one pf_fasta_index / pf_count_fasta / pf_maskcount_fasta / pf_color_fasta call launches (newlines, lines, words, scans, compact, table), timed as one launch; the core behind it is timed under its own kernel; unit: bytes of the chunk */
     PF_K_DEFLATE, /* K-DEFLATE: everything one pf_deflate_bgzf launches (deflate, scan of the members' sizes, pack), timed as one launch; unit: bytes of text */
-    PF_K_CLIP, /* K-CLIP: the kernels one pf_trim_fastq* / pf_trim_table_fastq* / pf_*_fastq*_trimmed call launches to clip adapters while a clip is open (one per file), timed as one launch inside the call's own; unit: records */
+    PF_K_CLIP, /* K-CLIP: the kernels one pf_trim_fastq* / pf_trim_table_fastq* / pf_*_fastq*_trimmed call launches to clip adapters while a clip is open (one per file), timed as one launch inside the call's own; unit: records */ PF_K_PALIN, /* K-PALIN: the kernel one pf_trim_fastq_pair / pf_trim_table_fastq_pair / pf_*_fastq_pair_trimmed call launches behind K-CLIP's while a clip with prefix pairs is open (palindrome mode), timed as one launch inside the call's own; unit: pairs */
     PF_K_COUNT_
 };
 int pf_enable_timing(pf_ctx *, int on);
@@ -472,6 +472,27 @@ int pf_clip_stats_get(pf_ctx *, pf_clip_stats *stats);
  * record (or was refused) clipped none: n_records == 0 is PF_OK, more is refused by name.  What `trim --trimlog` counts its last column from. */
 int pf_clip_last_ends(pf_ctx *, int file, uint32_t *clip_end, uint64_t n_records);
 int pf_clip_end(pf_ctx *);
+/* K-PALIN: palindrome mode beside simple mode (csrc/pf_clip.hip; the rule: csrc/pf_clip_rule.hpp, "PALINDROME MODE").  A clip opened
+ * with pf_clip_begin_pairs holds prefix pairs as well: pair q is P1 = prefix_bases[prefix_off[2q], prefix_off[2q + 1]) and P2 =
+ * [prefix_off[2q + 1], prefix_off[2q + 2]), both of one length 16 .. 128, 1 .. 8 pairs.  The simple adapters may be none
+ * (n_adapters == 0).  seed serves both modes; score is simple mode's T, pair_score palindrome mode's Tp (1 .. 1000), pair_min the
+ * fewest adapter bases A (1 .. 16); keep_both != 0 leaves file 2 of a clipped pair its first I* bases instead of dropping it.  While
+ * such a clip is open the paired calls named above clip every pair by both modes: a read's clip end is the smaller of its simple clip
+ * end and its pair end, pf_clip_last_ends hands out that final end, and reads_clipped / reads_dropped / bases_clipped of
+ * pf_clip_stats describe it.  A pair with a read of more than 1024 bases is clipped by simple mode alone.  A single-ended call clips
+ * with the simple adapters only (with none: nothing).  Refusals by name, as pf_clip_begin's.  pf_clip_pair_stats_get needs a clip
+ * opened with pairs. */
+typedef struct pf_clip_pair_stats {
+    uint64_t pairs_clipped;      /* pairs with I* > 0 */
+    uint64_t pairs_dropped;      /* pairs with I* == 0 */
+    uint64_t pairs_too_long;     /* pairs with a read of more than 1024 bases: no candidate */
+    uint64_t candidates_scored;  /* (prefix pair, I) examined whose seed held */
+    uint64_t bases_clipped[2];   /* simple clip end - final clip end, per file: what this mode took beyond simple mode */
+} pf_clip_pair_stats;
+int pf_clip_begin_pairs(pf_ctx *, const char *bases, const uint32_t *adapter_off, const uint8_t *side, uint32_t n_adapters /* may be 0 */,
+                        const char *prefix_bases, const uint32_t *prefix_off /* 2 * n_pairs + 1 */, uint32_t n_pairs,
+                        uint32_t seed, uint32_t score, uint32_t pair_score, uint32_t pair_min, int keep_both);
+int pf_clip_pair_stats_get(pf_ctx *, pf_clip_pair_stats *stats);
 /* K-INFLATE: blocked gzip (BGZF: what bgzip, bcl2fastq2 and BCL Convert write) inflated on the device, where pf_*_fastq read their text.
  * The rule -- the member header, RFC 1951, the refusals by name -- is csrc/pf_inflate_rule.hpp; the decoder one lane runs is
  * csrc/pf_inflate_core.hpp, shared with the host.  One wavefront per member; the CRC-32 of every member's text is checked against

@@ -249,8 +249,8 @@ int pfh_trim_fastq_chunk(const char *text, uint64_t n, int final, const pf_trim_
                          uint64_t *out_bytes, uint64_t *bytes_used, uint32_t *rec_begin, uint32_t *rec_len, uint64_t cap, uint64_t *n_records,
                          pf_trim_stats *stats, uint64_t *bad_record);
 /* ---- adapters clipped in front of the steps: `--adapters` (K-CLIP, pf_clip_begin .. pf_clip_end in ploidyfrost_hip.h) ----
- * The rule: csrc/pf_clip_rule.hpp (parity with Trimmomatic's ILLUMINACLIP unpinned; palindrome mode, overlaps below 16 and IUPAC
- * letters in adapters are not built).  pfh_reads_adapters(path, seed, score): the next pfh_trim_fastq or pfh_trim_fastq_pair of this
+ * The rule: csrc/pf_clip_rule.hpp (parity with Trimmomatic's ILLUMINACLIP unpinned; overlaps below 16 in simple mode and IUPAC
+ * letters in adapters are not built; palindrome mode: below).  pfh_reads_adapters(path, seed, score): the next pfh_trim_fastq or pfh_trim_fastq_pair of this
  * thread reads the adapter file (FASTA; names ending in /1 or /2 choose the file of a pair, names starting with Prefix are skipped and
  * counted), opens a clip on its context and clips every read before the steps; n_steps may then be 0; the call takes the switch back
  * (path NULL or "": no clipping).  The file and the values are refused by name before a device context exists, with the path and the
@@ -273,6 +273,30 @@ int pfh_trim_fastq_chunk_clip(const char *text, uint64_t n, int final, const pf_
                               const uint32_t *adapter_off, const uint8_t *side, uint32_t n_adapters, uint32_t file_side, uint32_t seed, uint32_t score, char *out,
                               uint64_t *out_bytes, uint64_t *bytes_used, uint32_t *rec_begin, uint32_t *rec_len, uint64_t cap, uint64_t *n_records,
                               pf_trim_stats *stats, pf_clip_stats *clip, uint64_t *bad_record);
+/* ---- palindrome mode: `--adapter-pairs` (K-PALIN, pf_clip_begin_pairs in ploidyfrost_hip.h) ----
+ * pfh_reads_adapter_pairs(pair_score, pair_min, keep_both), called behind pfh_reads_adapters: the next pfh_trim_fastq_pair,
+ * pfh_run_fastq_trimmed or pfh_run_multi_fastq_trimmed of this thread also reads the Prefix<X>/1, Prefix<X>/2 entries of the file as prefix
+ * pairs and clips every pair by both modes; a single-ended call or sample is refused by name (`--adapter-pairs needs -1 / -2`).
+ * pfh_reads_adapters_pair_report: the prefix pairs and what K-PALIN counted in that call.  The host's plain restatement, no device:
+ * pfh_clip_parse_adapter_pairs: pfh_clip_parse_adapters with the switch on -- the usable adapters (may be none) and the prefix pairs
+ * (prefix_bases: 8 * 2 * 128 bytes always suffice; prefix_off: room for 17).  pfh_clip_pair: the two reads of one pair under both
+ * modes: clip_end[f] = the final clip end of file f; clip / pairs: the statistics of this one pair.  pfh_trim_fastq_pair_chunk_clip:
+ * what pf_trim_fastq_pair gives for one chunk of each file while a clip with prefix pairs is open (out: o1, u1, o2, u2; clip_end[f]:
+ * the final clip ends, at most cap entries as rec_begin / rec_len). */
+void pfh_reads_adapter_pairs(uint32_t pair_score, uint32_t pair_min, int keep_both);
+void pfh_reads_adapters_pair_report(uint32_t *pairs, pf_clip_pair_stats *stats);
+int pfh_clip_parse_adapter_pairs(const char *text, uint64_t n, char *bases, uint64_t bases_cap, uint32_t *adapter_off, uint8_t *side, uint32_t *n_adapters,
+                                 char *prefix_bases, uint64_t prefix_cap, uint32_t *prefix_off, uint32_t *n_pairs, uint64_t *bad_record);
+int pfh_clip_pair(const char *seq1, const char *qual1, uint64_t n1, const char *seq2, const char *qual2, uint64_t n2, const char *bases,
+                  const uint32_t *adapter_off, const uint8_t *side, uint32_t n_adapters, const char *prefix_bases, const uint32_t *prefix_off, uint32_t n_pairs,
+                  uint32_t seed, uint32_t score, uint32_t pair_score, uint32_t pair_min, int keep_both, uint32_t phred, uint32_t clip_end[2],
+                  pf_clip_stats *clip, pf_clip_pair_stats *pairs);
+int pfh_trim_fastq_pair_chunk_clip(const char *text1, uint64_t n1, const char *text2, uint64_t n2, int final, const pf_trim_step *steps, uint32_t n_steps,
+                                   uint32_t phred, const char *bases, const uint32_t *adapter_off, const uint8_t *side, uint32_t n_adapters,
+                                   const char *prefix_bases, const uint32_t *prefix_off, uint32_t n_pairs, uint32_t seed, uint32_t score, uint32_t pair_score,
+                                   uint32_t pair_min, int keep_both, char *out[4], uint64_t out_bytes[4], uint64_t bytes_used[2], uint32_t *rec_begin[2],
+                                   uint32_t *rec_len[2], uint32_t *clip_end[2], uint64_t cap, uint64_t *n_records, pf_trim_stats stats[2], pf_clip_stats *clip,
+                                   pf_clip_pair_stats *pairs, uint64_t *bad_record);
 /* ---- raw reads to ploidy estimate in one process: step `1.trim` inside `run` / `run-multi` (K-TRIMCOUNT, pf_*_trimmed in ploidyfrost_hip.h) ----
  * The rule: csrc/pf_trimrun_rule.hpp.  pfh_run_fastq_trimmed: pfh_run_fastq on the raw reads -- both passes stream them and trim them on
  * the device on the way in, no trimmed file is written.  paired = 0: what `trim -i inputs... -o t.fq STEP...` followed by

@@ -332,6 +332,12 @@ void pfh_reads_adapters(const char *path, uint32_t seed, uint32_t score) {
     g_reads_adapters.seed = seed;
     g_reads_adapters.score = score;
 }
+void pfh_reads_adapter_pairs(uint32_t pair_score, uint32_t pair_min, int keep_both) {
+    g_reads_adapters.pairs = true;
+    g_reads_adapters.pair_score = pair_score;
+    g_reads_adapters.pair_min = pair_min;
+    g_reads_adapters.keep_both = keep_both != 0;
+}
 static pfh::ClipOptions take_reads_adapters() {
     const pfh::ClipOptions c = g_reads_adapters;
     g_reads_adapters = pfh::ClipOptions{};
@@ -342,6 +348,26 @@ void pfh_reads_adapters_report(uint32_t *adapters, uint32_t *skipped, pf_clip_st
     if (adapters) *adapters = g_clip_report.adapters;
     if (skipped) *skipped = g_clip_report.skipped;
     if (stats) *stats = g_clip_report.stats;
+}
+void pfh_reads_adapters_pair_report(uint32_t *pairs, pf_clip_pair_stats *stats) {
+    if (pairs) *pairs = g_clip_report.pairs;
+    if (stats) *stats = g_clip_report.pair_stats;
+}
+int pfh_clip_parse_adapter_pairs(const char *text, uint64_t n, char *bases, uint64_t bases_cap, uint32_t *adapter_off, uint8_t *side, uint32_t *n_adapters,
+                                 char *prefix_bases, uint64_t prefix_cap, uint32_t *prefix_off, uint32_t *n_pairs, uint64_t *bad_record) {
+    pf_clip::Adapters A;
+    uint64_t bad = 0;
+    const int c = pf_clip::parse_adapters(text ? text : "", text ? (size_t)n : 0, A, &bad, true);
+    if (n_adapters) *n_adapters = A.size();
+    if (n_pairs) *n_pairs = A.pairs();
+    if (bad_record) *bad_record = bad;
+    if (c) return c;
+    if (bases) memcpy(bases, A.bases.data(), std::min<uint64_t>(bases_cap, A.bases.size()));
+    if (adapter_off) memcpy(adapter_off, A.off.data(), A.off.size() * 4);
+    if (side && A.size()) memcpy(side, A.side.data(), A.size());
+    if (prefix_bases) memcpy(prefix_bases, A.prefix_bases.data(), std::min<uint64_t>(prefix_cap, A.prefix_bases.size()));
+    if (prefix_off) memcpy(prefix_off, A.prefix_off.data(), A.prefix_off.size() * 4);
+    return 0;
 }
 int pfh_clip_parse_adapters(const char *text, uint64_t n, char *bases, uint64_t bases_cap, uint32_t *adapter_off, uint8_t *side, uint32_t *n_adapters,
                             uint32_t *skipped, uint64_t *bad_record) {
@@ -375,6 +401,39 @@ int pfh_clip_read(const char *seq, const char *qual, uint64_t n, const char *bas
     const uint32_t e = pf_clip::clip_read(seq, qual, (uint32_t)n, bases, adapter_off, side, n_adapters, file_side, seed, score, phred, &sc);
     if (clip_end) *clip_end = e;
     if (scored) *scored = sc;
+    return 0;
+}
+static int clip_pair_set_refused(const char *who, const char *bases, const uint32_t *off, const uint8_t *side, uint32_t n_adapters, const char *prefix_bases,
+                                 const uint32_t *prefix_off, uint32_t n_pairs, uint32_t seed, uint32_t score, uint32_t pair_score, uint32_t pair_min, uint32_t phred) {
+    const int c = pf_clip::pair_set_clause(bases, off, side, n_adapters, prefix_bases, prefix_off, n_pairs, seed, score, pair_score, pair_min);
+    if (c) { g_open_err = std::string(who) + ": " + pf_clip::refusal_text(c); return 1; }
+    if (phred != 33 && phred != 64) { g_open_err = std::string(who) + ": " + pf_trim::refusal_text(pf_trim::REFUSE_PHRED) + ", not " + std::to_string(phred); return 1; }
+    return 0;
+}
+static pf_clip::PairSet pair_set(const char *prefix_bases, const uint32_t *prefix_off, uint32_t n_pairs, uint32_t pair_score, uint32_t pair_min, int keep_both) {
+    pf_clip::PairSet P;
+    P.prefix_bases = prefix_bases;
+    P.prefix_off = prefix_off;
+    P.n_pairs = n_pairs;
+    P.pair_score = pair_score;
+    P.pair_min = pair_min;
+    P.keep_both = keep_both != 0;
+    return P;
+}
+int pfh_clip_pair(const char *seq1, const char *qual1, uint64_t n1, const char *seq2, const char *qual2, uint64_t n2, const char *bases,
+                  const uint32_t *adapter_off, const uint8_t *side, uint32_t n_adapters, const char *prefix_bases, const uint32_t *prefix_off, uint32_t n_pairs,
+                  uint32_t seed, uint32_t score, uint32_t pair_score, uint32_t pair_min, int keep_both, uint32_t phred, uint32_t clip_end[2],
+                  pf_clip_stats *clip, pf_clip_pair_stats *pairs) {
+    if (clip_pair_set_refused("pfh_clip_pair", bases, adapter_off, side, n_adapters, prefix_bases, prefix_off, n_pairs, seed, score, pair_score, pair_min, phred)) return -1;
+    if (n1 > 0x7FFFFFFFull || n2 > 0x7FFFFFFFull) { g_open_err = "pfh_clip_pair: a read holds fewer than 2^31 bases"; return -1; }
+    uint32_t end[2] = {0, 0};
+    pf_clip::Stats cs = {};
+    pf_clip::PairStats ps = {};
+    pf_clip::clip_pair(seq1, qual1, (uint32_t)n1, seq2, qual2, (uint32_t)n2, bases, adapter_off, side, n_adapters,
+                       pair_set(prefix_bases, prefix_off, n_pairs, pair_score, pair_min, keep_both), seed, score, phred, end, &cs, &ps);
+    if (clip_end) { clip_end[0] = end[0]; clip_end[1] = end[1]; }
+    if (clip) memcpy(clip, &cs, sizeof cs);
+    if (pairs) memcpy(pairs, &ps, sizeof ps);
     return 0;
 }
 
@@ -465,6 +524,46 @@ int pfh_trim_fastq_chunk(const char *text, uint64_t n, int final, const pf_trim_
         if (rec_begin) rec_begin[i] = rb[i];
         if (rec_len) rec_len[i] = rl[i];
     }
+    return clause;
+}
+int pfh_trim_fastq_pair_chunk_clip(const char *text1, uint64_t n1, const char *text2, uint64_t n2, int final, const pf_trim_step *steps, uint32_t n_steps,
+                                   uint32_t phred, const char *bases, const uint32_t *adapter_off, const uint8_t *side, uint32_t n_adapters,
+                                   const char *prefix_bases, const uint32_t *prefix_off, uint32_t n_pairs, uint32_t seed, uint32_t score, uint32_t pair_score,
+                                   uint32_t pair_min, int keep_both, char *out[4], uint64_t out_bytes[4], uint64_t bytes_used[2], uint32_t *rec_begin[2],
+                                   uint32_t *rec_len[2], uint32_t *clip_end[2], uint64_t cap, uint64_t *n_records, pf_trim_stats stats[2], pf_clip_stats *clip,
+                                   pf_clip_pair_stats *pairs, uint64_t *bad_record) {
+    const char *who = "pfh_trim_fastq_pair_chunk_clip";
+    if (clip_pair_set_refused(who, bases, adapter_off, side, n_adapters, prefix_bases, prefix_off, n_pairs, seed, score, pair_score, pair_min, phred)) return -1;
+    if (n_steps && pfh::trim_options_clause(trim_options(steps, n_steps, phred, nullptr, 0), g_open_err)) return -1;   // (no step beside adapters is a plan)
+    std::string o[4];
+    std::vector<uint32_t> rb[2], rl[2], ce[2];
+    std::vector<uint32_t> *prb[2] = {&rb[0], &rb[1]}, *prl[2] = {&rl[0], &rl[1]}, *pce[2] = {&ce[0], &ce[1]};
+    uint64_t used[2] = {0, 0}, recs = 0, bad = 0;
+    pf_trim::Stats st[2] = {};
+    pf_clip::Stats cs = {};
+    pf_clip::PairStats ps = {};
+    const char *text[2] = {text1 ? text1 : "", text2 ? text2 : ""};
+    const uint64_t nn[2] = {text1 ? n1 : 0, text2 ? n2 : 0};
+    const int clause = pf_clip::trim_fastq_pair(text, nn, final != 0, reinterpret_cast<const pf_trim::Step *>(steps), n_steps, phred, bases, adapter_off, side, n_adapters,
+                                                pair_set(prefix_bases, prefix_off, n_pairs, pair_score, pair_min, keep_both), seed, score, o, used, recs, bad, prb, prl,
+                                                st, &cs, &ps, pce);
+    for (int d = 0; d < 4; ++d) {
+        if (out_bytes) out_bytes[d] = o[d].size();
+        if (out && out[d] && !o[d].empty()) memcpy(out[d], o[d].data(), o[d].size());
+    }
+    for (int f = 0; f < 2; ++f) {
+        if (bytes_used) bytes_used[f] = used[f];
+        if (stats) memcpy(&stats[f], &st[f], sizeof st[f]);
+        for (uint64_t i = 0; i < cap && i < rb[f].size(); ++i) {
+            if (rec_begin && rec_begin[f]) rec_begin[f][i] = rb[f][i];
+            if (rec_len && rec_len[f]) rec_len[f][i] = rl[f][i];
+            if (clip_end && clip_end[f]) clip_end[f][i] = ce[f][i];
+        }
+    }
+    if (n_records) *n_records = recs;
+    if (bad_record) *bad_record = bad;
+    if (clip) memcpy(clip, &cs, sizeof cs);
+    if (pairs) memcpy(pairs, &ps, sizeof ps);
     return clause;
 }
 int pfh_trim_fastq_chunk_clip(const char *text, uint64_t n, int final, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, const char *bases,
@@ -647,6 +746,13 @@ static void clip_report_sum(const std::vector<pfh::ClipReport> &units) {
     for (const pfh::ClipReport &u : units) {
         g_clip_report.adapters = u.adapters;
         g_clip_report.skipped = u.skipped;
+        g_clip_report.pairs_on = u.pairs_on;
+        g_clip_report.pairs = u.pairs;
+        g_clip_report.pair_stats.pairs_clipped += u.pair_stats.pairs_clipped;
+        g_clip_report.pair_stats.pairs_dropped += u.pair_stats.pairs_dropped;
+        g_clip_report.pair_stats.pairs_too_long += u.pair_stats.pairs_too_long;
+        g_clip_report.pair_stats.candidates_scored += u.pair_stats.candidates_scored;
+        for (int f = 0; f < 2; ++f) g_clip_report.pair_stats.bases_clipped[f] += u.pair_stats.bases_clipped[f];
         for (int f = 0; f < 2; ++f) {
             g_clip_report.stats.reads_clipped[f] += u.stats.reads_clipped[f];
             g_clip_report.stats.reads_dropped[f] += u.stats.reads_dropped[f];

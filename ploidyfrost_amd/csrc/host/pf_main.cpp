@@ -102,7 +102,9 @@ void PrintUsage() {
          << "Usage: PloidyFrost trim -1 <r1.fq> -2 <r2.fq> -o1 <p1.fq> -u1 <u1.fq> -o2 <p2.fq> -u2 <u2.fq> STEP... [the same options]" << endl
          << "                  (`trimmomatic SE|PE` on the device; STEP: LEADING:t TRAILING:t SLIDINGWINDOW:w:t MINLEN:l, applied in the order given)" << endl
          << "                  [--adapters <adapters.fa> [--adapter-seed 0..8] [--adapter-score 1..1000]] on trim, run STEP... and run-multi STEP...: adapter read-through is" << endl
-         << "                  clipped on the device before the steps (ILLUMINACLIP's simple mode; no STEP is needed beside --adapters, also with -1 / -2)" << endl << endl
+         << "                  clipped on the device before the steps (ILLUMINACLIP's simple mode; no STEP is needed beside --adapters, also with -1 / -2)" << endl
+         << "                  [--adapter-pairs [--adapter-pair-score 1..1000] [--adapter-pair-min 1..16] [--adapter-keep-both]] with -1 / -2: ILLUMINACLIP's palindrome mode" << endl
+         << "                  from the Prefix<X>/1 and Prefix<X>/2 entries of the adapter file; the reverse read of a clipped pair is dropped unless --adapter-keep-both" << endl << endl
          << "Usage: PloidyFrost build -k 25 [-i] [-d] -r <reads.fq> [-r <more.fq> ...] -o <sample> [-g G] [-t N] [--chunk-bytes N] [--initial-slots N] [-v]" << endl
          << "                  (`Bifrost build -r` on the device: <sample>.gfa, the compacted de Bruijn graph of the reads; -i clips tips, -d deletes" << endl
          << "                  isolated unitigs, both of fewer than k k-mers; single-sample graphs from FASTQ only)" << endl
@@ -809,18 +811,23 @@ int mask_main(int argc, char **argv) {
     return 0;
 }
 
-// `--adapters FILE [--adapter-seed S] [--adapter-score T]` of `trim`, `run` and `run-multi`: the one place they are parsed
+// `--adapters FILE [--adapter-seed S] [--adapter-score T] [--adapter-pairs [--adapter-pair-score T] [--adapter-pair-min A]
+// [--adapter-keep-both]]` of `trim`, `run` and `run-multi`: the one place they are parsed
 struct ClipCli {
-    string adapters, seed, score;
-    bool adapters_seen = false, seed_seen = false, score_seen = false;
+    string adapters, seed, score, pair_score, pair_min;
+    bool adapters_seen = false, seed_seen = false, score_seen = false, pairs_seen = false, pair_score_seen = false, pair_min_seen = false, keep_both_seen = false;
     // 1 = the option was taken (i moved past its value), 0 = not one of these, -1 = refused with `why`
     int take(int argc, char **argv, int &i, string &why) {
         const string a = argv[i];
-        if (a != "--adapters" && a != "--adapter-seed" && a != "--adapter-score") return 0;
+        if (a == "--adapter-pairs") { pairs_seen = true; return 1; }
+        if (a == "--adapter-keep-both") { keep_both_seen = true; return 1; }
+        if (a != "--adapters" && a != "--adapter-seed" && a != "--adapter-score" && a != "--adapter-pair-score" && a != "--adapter-pair-min") return 0;
         if (i + 1 >= argc) { why = a + " needs a value"; return -1; }
         const string v = argv[++i];
         if (a == "--adapters") { adapters = v; adapters_seen = true; }
         else if (a == "--adapter-seed") { seed = v; seed_seen = true; }
+        else if (a == "--adapter-pair-score") { pair_score = v; pair_score_seen = true; }
+        else if (a == "--adapter-pair-min") { pair_min = v; pair_min_seen = true; }
         else { score = v; score_seen = true; }
         return 1;
     }
@@ -835,12 +842,28 @@ struct ClipCli {
         if (!adapters_seen) {
             if (seed_seen) return "--adapter-seed needs --adapters: the seed is read by the adapter clipping alone";
             if (score_seen) return "--adapter-score needs --adapters: the score is read by the adapter clipping alone";
+            if (pairs_seen) return "--adapter-pairs needs --adapters: the prefix pairs are read from the adapter file";
+            if (pair_score_seen) return "--adapter-pair-score needs --adapters and --adapter-pairs";
+            if (pair_min_seen) return "--adapter-pair-min needs --adapters and --adapter-pairs";
+            if (keep_both_seen) return "--adapter-keep-both needs --adapters and --adapter-pairs";
             return "";
         }
         if (adapters.empty()) return "--adapters takes the path of a FASTA file";
         opt.adapters = adapters;
         if (seed_seen && !number(seed, 0, pf_clip::MAX_SEED, opt.seed)) return "--adapter-seed takes 0 to 8, not '" + seed + "'";
         if (score_seen && !number(score, pf_clip::MIN_SCORE, pf_clip::MAX_SCORE, opt.score)) return "--adapter-score takes 1 to 1000, not '" + score + "'";
+        if (!pairs_seen) {
+            if (pair_score_seen) return "--adapter-pair-score needs --adapter-pairs: the score is read by the palindrome mode alone";
+            if (pair_min_seen) return "--adapter-pair-min needs --adapter-pairs: the length is read by the palindrome mode alone";
+            if (keep_both_seen) return "--adapter-keep-both needs --adapter-pairs: the reverse read is dropped by the palindrome mode alone";
+            return "";
+        }
+        opt.pairs = true;
+        opt.keep_both = keep_both_seen;
+        if (pair_score_seen && !number(pair_score, pf_clip::MIN_SCORE, pf_clip::MAX_SCORE, opt.pair_score))
+            return "--adapter-pair-score takes 1 to 1000, not '" + pair_score + "'";
+        if (pair_min_seen && !number(pair_min, pf_clip::MIN_PAIR_MIN, pf_clip::MAX_PAIR_MIN, opt.pair_min))
+            return "--adapter-pair-min takes 1 to 16, not '" + pair_min + "'";
         return "";
     }
 };
@@ -851,7 +874,8 @@ int trim_main(int argc, char **argv) {
     const char *usage = "Usage:PloidyFrost trim -i reads.fq [-i more.fq ...] -o trimmed.fq STEP... [--phred 33|64] [--trimlog file] [--chunk-bytes N] [--gz] [--gz-plain] [--gz-out] [-v]\n"
                         "      PloidyFrost trim -1 r1.fq -2 r2.fq -o1 p1.fq -u1 u1.fq -o2 p2.fq -u2 u2.fq STEP... [the same options]\n"
                         "      STEP: LEADING:t TRAILING:t SLIDINGWINDOW:w:t MINLEN:l\n"
-                        "      [--adapters adapters.fa [--adapter-seed 0..8] [--adapter-score 1..1000]]: adapters are clipped first; no STEP is needed beside them";
+                        "      [--adapters adapters.fa [--adapter-seed 0..8] [--adapter-score 1..1000]]: adapters are clipped first; no STEP is needed beside them\n"
+                        "      [--adapter-pairs [--adapter-pair-score 1..1000] [--adapter-pair-min 1..16] [--adapter-keep-both]] with -1 / -2: palindrome mode from the file's Prefix pairs";
     vector<string> inputs, words;
     string out, in_pair[2], out_pair[4];
     pfh::TrimOptions opt;
@@ -910,6 +934,7 @@ int trim_main(int argc, char **argv) {
     const bool pair_out = !out_pair[0].empty() || !out_pair[1].empty() || !out_pair[2].empty() || !out_pair[3].empty();
     if (!inputs.empty() && pair_in) return refuse("-i does not go with -1 / -2 (the inputs are either single-ended or one pair)");
     if (pair_in && !out.empty()) return refuse("-o does not go with -1 / -2 (a pair is written to -o1 -u1 -o2 -u2)");
+    if (opt.clip.on() && opt.clip.pairs && !inputs.empty()) return refuse("--adapter-pairs needs -1 / -2");
     if (!pair_in && pair_out) return refuse(inputs.empty() ? "-1 <r1.fq> and -2 <r2.fq> are missing" : "-o1 -u1 -o2 -u2 do not go with -i (single-ended reads are written to -o)");
     pf_trim_stats st[2] = {};
     pfh::TrimTimes tm;

@@ -124,6 +124,7 @@ int colored_call_run(CCDBG &g, ColoredCallSetup &s, std::string &err) {
 std::string trim_inputs_refusal(const std::vector<std::string> &inputs, bool paired, const TrimInputs &trim) {
     if (paired && !trim.on()) return "the files of a pair are trimmed together: -1 / -2 need a step (two files without trimming go with -i)";
     if (!trim.on()) return "";
+    if (trim.clip.on() && trim.clip.pairs && !paired) return "--adapter-pairs needs -1 / -2";
     {
         TrimOptions o;
         o.steps = trim.steps;
@@ -157,20 +158,15 @@ void add_masked_stats(pf_maskcount_stats &a, const pf_maskcount_stats &b) {
 
 int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<ReadsInput> &inputs, bool paired, const TrimInputs &trim, uint64_t chunk_bytes,
                    bool masked, uint32_t low, uint32_t up, pf_trim_stats *unit_stats, pf_maskcount_stats *masked_stats, std::string &err,
-                   pf_clip_stats *unit_clip) {
+                   ClipCounts *unit_clip) {
     const pf_trim_plan plan = {trim.steps.data(), (uint32_t)trim.steps.size(), trim.phred};
     // what the clip has counted since the last unit ended, into unit u
-    pf_clip_stats clip_seen = {};
+    ClipCounts clip_seen;
     auto clip_unit = [&](size_t u, bool store) {
         if (!unit_clip) return 0;
-        pf_clip_stats now = {};
-        if (pf_clip_stats_get(ctx, &now) != PF_OK) { err = std::string(who) + ": " + pf_last_error(ctx); return 1; }
-        for (int f = 0; f < 2 && store; ++f) {
-            unit_clip[u].reads_clipped[f] = now.reads_clipped[f] - clip_seen.reads_clipped[f];
-            unit_clip[u].reads_dropped[f] = now.reads_dropped[f] - clip_seen.reads_dropped[f];
-            unit_clip[u].bases_clipped[f] = now.bases_clipped[f] - clip_seen.bases_clipped[f];
-            unit_clip[u].candidates_scored[f] = now.candidates_scored[f] - clip_seen.candidates_scored[f];
-        }
+        ClipCounts now;
+        if (clip_counts(ctx, trim.clip.pairs, now) != PF_OK) { err = std::string(who) + ": " + pf_last_error(ctx); return 1; }
+        if (store) unit_clip[u] = clip_counts_since(now, clip_seen);
         clip_seen = now;
         return 0;
     };
@@ -265,10 +261,10 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
         return 1;
     };
     auto dev_fail = [&]() { return fail(std::string("run: ") + pf_last_error(ctx)); };
-    std::vector<pf_clip_stats> unit_clip;
+    std::vector<ClipCounts> unit_clip;
     if (opt.trim.clip.on()) {   // the clip stays open over both passes; the first one is reported
         if (clip_open(ctx, adapters, opt.trim.clip) != PF_OK) return dev_fail();
-        unit_clip.assign(trim_unit_count(inputs.size(), opt.paired), pf_clip_stats{});
+        unit_clip.assign(trim_unit_count(inputs.size(), opt.paired), ClipCounts{});
     }
 
     // ---- count: every k-mer of the reads, both strands, the user's cut-offs ----
@@ -344,7 +340,7 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
         stats.distinct_kept = kept.n;
     }
     if (opt.trim.clip.on()) {
-        for (const pf_clip_stats &u : unit_clip) stats.clip.push_back(ClipReport{adapters.size(), adapters.skipped, u});
+        for (const ClipCounts &u : unit_clip) stats.clip.push_back(clip_report_of(adapters, opt.trim.clip, u));
         if (pf_clip_end(ctx) != PF_OK) return dev_fail();
     }
     if (kept.n >= pf_unitig::MAX_KMERS) return fail(std::string("run: ") + pf_unitig::TOO_MANY_TEXT + " (" + std::to_string(kept.n) + ")");

@@ -87,7 +87,7 @@ std::string trim_inputs_refusal(const std::vector<std::string> &inputs, bool pai
 // while the unit streamed.  0 = ok, else worded in err by `who`.
 int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<ReadsInput> &inputs, bool paired, const TrimInputs &trim, uint64_t chunk_bytes,
                    bool masked, uint32_t low, uint32_t up, pf_trim_stats *unit_stats, pf_maskcount_stats *masked_stats, std::string &err,
-                   pf_clip_stats *unit_clip = nullptr);
+                   ClipCounts *unit_clip = nullptr);
 // the `trim:` line of a unit on stderr, in `trim`'s own format: st = the unit's statistics (paired: of file 1 and of file 2)
 std::string trim_unit_line(const pf_trim_stats *st, bool paired);
 

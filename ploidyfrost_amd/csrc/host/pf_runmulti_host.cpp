@@ -151,10 +151,10 @@ int run_multi_fastq(const std::vector<MultiSample> &samples, const std::string &
     };
     auto dev_fail = [&]() { return fail(std::string("run-multi: ") + pf_last_error(ctx)); };
 
-    std::vector<std::vector<pf_clip_stats>> unit_clip(C);
+    std::vector<std::vector<ClipCounts>> unit_clip(C);
     if (opt.trim.clip.on()) {   // the clip stays open over both passes; the first one is reported
         if (clip_open(ctx, adapters, opt.trim.clip) != PF_OK) return dev_fail();
-        for (uint32_t c = 0; c < C; ++c) unit_clip[c].assign(trim_unit_count(samples[c].inputs.size(), samples[c].paired), pf_clip_stats{});
+        for (uint32_t c = 0; c < C; ++c) unit_clip[c].assign(trim_unit_count(samples[c].inputs.size(), samples[c].paired), ClipCounts{});
     }
     // ---- first pass, per sample: count, thresholds; the counters stay resident ----
     stats.colors = C;
@@ -248,7 +248,7 @@ int run_multi_fastq(const std::vector<MultiSample> &samples, const std::string &
     if (opt.trim.clip.on()) {
         stats.clip.resize(C);
         for (uint32_t c = 0; c < C; ++c)
-            for (const pf_clip_stats &u : unit_clip[c]) stats.clip[c].push_back(ClipReport{adapters.size(), adapters.skipped, u});
+            for (const ClipCounts &u : unit_clip[c]) stats.clip[c].push_back(clip_report_of(adapters, opt.trim.clip, u));
         if (pf_clip_end(ctx) != PF_OK) return dev_fail();
     }
     if (pf_release_counts(ctx) != PF_OK) return dev_fail();   // the last sample's table: the joined one takes its place in the end

@@ -54,7 +54,7 @@ int trim_clip_open(pf_ctx *ctx, const TrimOptions &opt, const pf_clip::Adapters 
     return 1;
 }
 int trim_clip_report(pf_ctx *ctx, const TrimOptions &opt, const pf_clip::Adapters &adapters, ClipReport *clip, std::string &err) {
-    if (!opt.clip.on() || !clip || clip_report(ctx, adapters, pf_clip_stats{}, *clip) == PF_OK) return 0;
+    if (!opt.clip.on() || !clip || clip_report(ctx, adapters, opt.clip, *clip) == PF_OK) return 0;
     err = std::string("trim: ") + pf_last_error(ctx);
     return 1;
 }
@@ -66,7 +66,8 @@ int trim_options_clause(const TrimOptions &opt, std::string &err) {
     int c = pf_trim::steps_clause(reinterpret_cast<const pf_trim::Step *>(opt.steps.data()), (uint32_t)opt.steps.size(), opt.phred, &bad);
     if (c == pf_trim::REFUSE_NO_STEP && opt.clip.on() && opt.steps.empty()) c = 0;   // --adapters alone is a plan
     if (!c && opt.clip.on()) {
-        const int cc = pf_clip::params_clause(opt.clip.seed, opt.clip.score);
+        int cc = pf_clip::params_clause(opt.clip.seed, opt.clip.score);
+        if (!cc && opt.clip.pairs) cc = pf_clip::pair_params_clause(opt.clip.pair_score, opt.clip.pair_min);
         if (cc) { err = std::string("trim: ") + pf_clip::refusal_text(cc); return cc; }
     }
     if (!c) return 0;
@@ -80,6 +81,7 @@ int trim_fastq(const std::vector<std::string> &inputs, const std::string &out_pa
                TrimTimes *times, std::string &err, ClipReport *clip) {
     stats = pf_trim_stats{};
     err.clear();
+    if (opt.clip.on() && opt.clip.pairs) { err = "trim: --adapter-pairs needs -1 / -2"; return 1; }
     const bool logs = !opt.trimlog.empty();
     std::vector<std::string> paths = {out_path};
     if (logs) paths.push_back(opt.trimlog);

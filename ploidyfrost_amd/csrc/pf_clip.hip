@@ -20,6 +20,21 @@
 // Budget: LDS 64 * 32 + 64 * 4 (adapters) + 16 rows * 3 planes * 16 words * 4 = 5376 bytes a block of 256 lanes; no array is indexed
 // by a run-time value in registers (the bitmaps slide in 64-bit pairs), so nothing goes to scratch.  The counters are kept per lane
 // and summed per wavefront when the kernel ends: four integer atomics a wavefront at most.  Writes are plain vector stores.
+//
+// K-PALIN: palindrome mode for the two reads of a pair (`--adapter-pairs`; the rule: "PALINDROME MODE" in pf_clip_rule.hpp), launched
+// behind K-CLIP by clip_launch when the open clip holds prefix pairs and the call has two files.
+//   strings    a row of 16 lanes per pair of reads.  S1 = P1.R1 and X2 = the reverse complement of S2 = P2.R2 (RC(R2) first, then
+//              RC(P2)) as three bit planes each (code low, code high, valid), bit i = position i, 40 words a plane: 36 hold 128 + 1024
+//              positions, four more let 128 bits be fetched from any of them.  A lane fills the words rl, rl + 16, rl + 32 of all six
+//              planes from the bytes in global memory (the reads are at most 1024 bases here; longer pairs are no candidates).
+//   candidates position i of S1 lies against position i + (n2 - p - I) of X2, so a candidate I is a plain shift of one bit string
+//              against the other: clip_bits128 / clip_range128 and K-CLIP's byte-count reject serve, in pieces of 128 bits that
+//              overlap by 15 so that every window of 16 lies whole in one.  The lanes take 16 consecutive I a round, upwards; the
+//              round in which some I passes is the last one of the prefix pair, and the next prefix pair only looks below it.
+//   score      only where the seed held: serial over pieces of 128, the quality bytes fetched from global memory at mismatches only.
+//   result     lane 0 combines I* with the simple clip ends K-CLIP left in clip_end[f][r] and writes both files' final ends.
+// Budget: LDS 16 rows * 6 planes * 40 words * 4 = 15360 bytes a block; no run-time-indexed register arrays.  With prefix pairs open
+// K-CLIP leaves reads_clipped / reads_dropped / bases_clipped to K-PALIN, which counts the final ends.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -33,6 +48,7 @@
 #include "pf_trim_dev.hpp"
 
 static_assert(sizeof(pf_clip_stats) == sizeof(pf_clip::Stats), "the rule header restates the ABI's record");
+static_assert(sizeof(pf_clip_pair_stats) == sizeof(pf_clip::PairStats), "the rule header restates the ABI's record");
 
 namespace pf {
 
@@ -54,6 +70,11 @@ struct ClipState {
     unsigned long long *d_counts = nullptr;  // pf_clip_stats as it lies
     const uint32_t *last[2] = {nullptr, nullptr};   // the clip ends of the last launch, in the caller's workspace until its next call
     uint64_t last_n = 0;
+    // K-PALIN: the prefix pairs of a clip opened with pf_clip_begin_pairs (n_pairs == 0: none)
+    uint32_t n_pairs = 0, pair_score = 0, pair_min = 0, keep_both = 0;
+    char *d_prefix = nullptr;                     // pair q: P1 at 256 q, P2 at 256 q + 128, upper case
+    uint32_t *d_plen = nullptr;                   // p of pair q
+    unsigned long long *d_pair_counts = nullptr;  // pf_clip_pair_stats as it lies
 };
 static inline ClipState *clip_state(pf_ctx *ctx) { return static_cast<ClipState *>(ctx->clip); }
 
@@ -67,6 +88,7 @@ struct ClipArgs {
     uint32_t n_adapters, file_side, seed, score, phred;
     uint32_t *clip_end;
     unsigned long long *counts;
+    uint32_t count_ends;   // 0: K-PALIN follows and counts the final ends (candidates_scored stays here)
 };
 
 // 128 bits of a plane from bit position `at` (0 <= at, at + 128 <= 32 * CLIP_PLANE_WORDS)
@@ -219,10 +241,207 @@ __global__ __launch_bounds__(TRIM_BLOCK) void k_clip(const ClipArgs a) {
     scored = wave_sum_u64(scored);
     if (lane_id() == 0) {
         const uint32_t f = a.file_side == 2 ? 1 : 0;   // pf_clip_stats: four pairs [file]
-        if (clipped) atomicAdd(&a.counts[0 + f], (unsigned long long)clipped);
-        if (dropped) atomicAdd(&a.counts[2 + f], (unsigned long long)dropped);
-        if (bases) atomicAdd(&a.counts[4 + f], (unsigned long long)bases);
+        if (clipped && a.count_ends) atomicAdd(&a.counts[0 + f], (unsigned long long)clipped);
+        if (dropped && a.count_ends) atomicAdd(&a.counts[2 + f], (unsigned long long)dropped);
+        if (bases && a.count_ends) atomicAdd(&a.counts[4 + f], (unsigned long long)bases);
         if (scored) atomicAdd(&a.counts[6 + f], (unsigned long long)scored);
+    }
+}
+
+// ---- K-PALIN ----
+constexpr int PALIN_WORDS = 40;                  // words of a plane: 36 hold 128 + 1024 positions, four more behind them
+constexpr int PALIN_PIECE = 128;                 // positions of a piece
+constexpr int PALIN_SEED_STEP = PALIN_PIECE - (int)pf_clip::WINDOW + 1;   // from piece to piece in the seed test: no window is split
+constexpr uint32_t PALIN_NONE = 0xFFFFFFFFu;
+static_assert(32 * (PALIN_WORDS - 4) >= (int)(pf_clip::MAX_LEN + pf_clip::MAX_PAIR_READ), "a plane holds a prefix and a read");
+
+struct PalinArgs {
+    const char *text[2];
+    const uint32_t *lines[2];
+    uint64_t n_rec;
+    const char *prefix;
+    const uint32_t *plen;
+    uint32_t n_pairs, seed, pair_score, pair_min, keep_both, phred, have_simple;
+    uint32_t *clip_end[2];
+    unsigned long long *counts;        // pf_clip_stats
+    unsigned long long *pair_counts;   // pf_clip_pair_stats
+};
+
+// L positions (1 .. 128) of S1 from position at1 against X2 from position at2: the positions that are no match (m) and the valid ones (v)
+__device__ inline void palin_piece(const uint32_t (*pl)[PALIN_WORDS], int at1, int at2, int L, uint64_t &m0, uint64_t &m1, uint64_t &v0, uint64_t &v1) {
+    uint64_t al0, al1, ah0, ah1, av0, av1, bl0, bl1, bh0, bh1, bv0, bv1, in0, in1;
+    clip_bits128(pl[0], at1, al0, al1);
+    clip_bits128(pl[1], at1, ah0, ah1);
+    clip_bits128(pl[2], at1, av0, av1);
+    clip_bits128(pl[3], at2, bl0, bl1);
+    clip_bits128(pl[4], at2, bh0, bh1);
+    clip_bits128(pl[5], at2, bv0, bv1);
+    clip_range128(0, L, in0, in1);
+    v0 = av0 & bv0 & in0;
+    v1 = av1 & bv1 & in1;
+    m0 = ((al0 ^ bl0) | (ah0 ^ bh0) | ~v0) & in0;
+    m1 = ((al1 ^ bl1) | (ah1 ^ bh1) | ~v1) & in1;
+}
+// (s0, s1): the mismatch bitmap of L >= 16 positions from bit 0: does some window of 16 hold at most `seed`?
+__device__ inline bool clip_some_window_holds(uint64_t s0, uint64_t s1, int L, uint32_t seed) {
+    uint32_t cnt = (uint32_t)__popc((uint32_t)s0 & 0xFFFFu);
+    for (int j = 0;; ++j) {
+        if (cnt <= seed) return true;
+        if (j + (int)pf_clip::WINDOW >= L) return false;
+        cnt += (uint32_t)((s0 >> 16) & 1ull) - (uint32_t)(s0 & 1ull);
+        s0 = (s0 >> 1) | (s1 << 63);
+        s1 >>= 1;
+    }
+}
+
+__global__ __launch_bounds__(TRIM_BLOCK) void k_palin(const PalinArgs a) {
+    __shared__ uint32_t s_pl[TRIM_ROWS][6][PALIN_WORDS];
+    const int rl = (int)threadIdx.x & (TRIM_ROW - 1), row = (int)threadIdx.x / TRIM_ROW;
+    uint32_t (*pl)[PALIN_WORDS] = s_pl[row];
+    uint64_t clipped0 = 0, clipped1 = 0, dropped0 = 0, dropped1 = 0, bases0 = 0, bases1 = 0;
+    uint64_t p_clipped = 0, p_dropped = 0, p_long = 0, p_scored = 0, p_bases0 = 0, p_bases1 = 0;
+    for (uint64_t r = (uint64_t)blockIdx.x * TRIM_ROWS + row; r < a.n_rec; r += (uint64_t)gridDim.x * TRIM_ROWS) {
+        const uint32_t sb1 = a.lines[0][8 * r + 2], n1 = a.lines[0][8 * r + 3] - sb1, qb1 = a.lines[0][8 * r + 6];
+        const uint32_t sb2 = a.lines[1][8 * r + 2], n2 = a.lines[1][8 * r + 3] - sb2, qb2 = a.lines[1][8 * r + 6];
+        const bool too_long = pf_clip::pair_too_long(n1, n2);
+        uint32_t limit = too_long ? 0u : pf_clip::pair_candidates(n1, n2, a.pair_min);   // candidates lie below it
+        bool found = false;
+        for (uint32_t q = 0; q < a.n_pairs && limit > 0; ++q) {
+            const uint32_t p = a.plen[q];
+            const char *P1 = a.prefix + 256u * q, *P2 = P1 + 128;
+            row_sync();   // the last strings have been read
+            for (int w = rl; w < PALIN_WORDS; w += TRIM_ROW) {
+                uint32_t lo = 0, hi = 0, ok = 0;
+                if (32u * (uint32_t)w < p + n1) {
+#pragma unroll 8
+                    for (uint32_t b = 0; b < 32; ++b) {
+                        const uint32_t i = 32u * (uint32_t)w + b;
+                        const uint8_t c = i < p ? (uint8_t)P1[i] : i - p < n1 ? (uint8_t)a.text[0][(uint64_t)sb1 + (i - p)] : (uint8_t)0;
+                        const uint32_t code = pf_mask::base_code(c);
+                        lo |= (code & 1u) << b;
+                        hi |= (code >> 1) << b;
+                        ok |= (uint32_t)pf_mask::is_base(c) << b;
+                    }
+                }
+                pl[0][w] = lo;
+                pl[1][w] = hi;
+                pl[2][w] = ok;
+                lo = hi = ok = 0;
+                if (32u * (uint32_t)w < p + n2) {
+#pragma unroll 8
+                    for (uint32_t b = 0; b < 32; ++b) {
+                        const uint32_t k = 32u * (uint32_t)w + b;   // position k of X2: RC(R2), then RC(P2)
+                        const uint8_t c = k < n2 ? (uint8_t)a.text[1][(uint64_t)sb2 + (n2 - 1 - k)] : k - n2 < p ? (uint8_t)P2[p - 1 - (k - n2)] : (uint8_t)0;
+                        const uint32_t code = pf_mask::base_code(c) ^ 3u;   // the complement
+                        lo |= (code & 1u) << b;
+                        hi |= (code >> 1) << b;
+                        ok |= (uint32_t)pf_mask::is_base(c) << b;
+                    }
+                }
+                pl[3][w] = lo;
+                pl[4][w] = hi;
+                pl[5][w] = ok;
+            }
+            row_sync();
+            for (uint32_t I0 = 0; I0 < limit; I0 += TRIM_ROW) {
+                const uint32_t I = I0 + (uint32_t)rl;
+                bool seed_ok = false, pass = false;
+                uint32_t lo = 0, hi = 0;
+                if (I < limit && pf_clip::pair_range(p, n1, n2, I, lo, hi)) {
+                    const int d = (int)n2 - (int)p - (int)I;   // position i of S1 lies against position i + d of X2; lo + d >= 0
+                    for (uint32_t i0 = lo; i0 + pf_clip::WINDOW <= hi && !seed_ok; i0 += PALIN_SEED_STEP) {
+                        const int L = (int)(hi - i0) < PALIN_PIECE ? (int)(hi - i0) : PALIN_PIECE;
+                        uint64_t m0, m1, v0, v1;
+                        palin_piece(pl, (int)i0, (int)i0 + d, L, m0, m1, v0, v1);
+                        seed_ok = (uint32_t)(__popcll(m0) + __popcll(m1)) <= a.seed;
+                        if (!seed_ok && clip_some_block_may_hold_a_seed(m0, m1, L, a.seed)) seed_ok = clip_some_window_holds(m0, m1, L, a.seed);
+                    }
+                    if (seed_ok) {
+                        const uint32_t T = 2 * p + I;
+                        int32_t run = 0, top = 0;
+                        for (uint32_t i0 = lo; i0 < hi; i0 += PALIN_PIECE) {
+                            const int L = (int)(hi - i0) < PALIN_PIECE ? (int)(hi - i0) : PALIN_PIECE;
+                            uint64_t m0, m1, v0, v1;
+                            palin_piece(pl, (int)i0, (int)i0 + d, L, m0, m1, v0, v1);
+                            for (int j = 0; j < L; ++j) {
+                                int32_t w = 0;
+                                if (v0 & 1ull) {
+                                    w = pf_clip::MATCH;
+                                    if (m0 & 1ull) {
+                                        const uint32_t i = i0 + (uint32_t)j, jj = T - 1 - i;   // (i < p and jj < p never meet)
+                                        const int q2 = jj >= p ? (int)(uint8_t)a.text[1][(uint64_t)qb2 + (jj - p)] - (int)a.phred : 0;
+                                        const int qq = i >= p ? pf_clip::pair_mismatch_quality((int)(uint8_t)a.text[0][(uint64_t)qb1 + (i - p)] - (int)a.phred, jj >= p, q2) : q2;
+                                        w = -pf_clip::PENALTY * (qq > 0 ? qq : 0);
+                                    }
+                                }
+                                run = run + w > 0 ? run + w : 0;
+                                top = run > top ? run : top;
+                                m0 = (m0 >> 1) | (m1 << 63);
+                                m1 >>= 1;
+                                v0 = (v0 >> 1) | (v1 << 63);
+                                v1 >>= 1;
+                            }
+                        }
+                        pass = pf_clip::score_passes(top, a.pair_score);
+                    }
+                }
+                const uint32_t least = row_min_u32(pass ? I : PALIN_NONE);
+                if (least != PALIN_NONE) {   // the smallest passing I of this prefix pair: the candidates beyond it were not examined
+                    p_scored += seed_ok && I <= least;
+                    limit = least;
+                    found = true;
+                    break;
+                }
+                p_scored += seed_ok;
+            }
+        }
+        if (rl == 0) {
+            const uint32_t n[2] = {n1, n2};
+            uint32_t took[2], e[2];
+            for (int f = 0; f < 2; ++f) {
+                const uint32_t simple = a.have_simple ? a.clip_end[f][r] : n[f];
+                e[f] = pf_clip::pair_end(found, limit, simple, f, a.keep_both != 0);
+                a.clip_end[f][r] = e[f];
+                took[f] = simple - e[f];
+            }
+            clipped0 += e[0] != n1 && e[0] != 0;
+            dropped0 += e[0] != n1 && e[0] == 0;
+            bases0 += n1 - e[0];
+            clipped1 += e[1] != n2 && e[1] != 0;
+            dropped1 += e[1] != n2 && e[1] == 0;
+            bases1 += n2 - e[1];
+            p_clipped += found && limit != 0;
+            p_dropped += found && limit == 0;
+            p_long += too_long;
+            p_bases0 += took[0];
+            p_bases1 += took[1];
+        }
+    }
+    clipped0 = wave_sum_u64(clipped0);
+    clipped1 = wave_sum_u64(clipped1);
+    dropped0 = wave_sum_u64(dropped0);
+    dropped1 = wave_sum_u64(dropped1);
+    bases0 = wave_sum_u64(bases0);
+    bases1 = wave_sum_u64(bases1);
+    p_clipped = wave_sum_u64(p_clipped);
+    p_dropped = wave_sum_u64(p_dropped);
+    p_long = wave_sum_u64(p_long);
+    p_scored = wave_sum_u64(p_scored);
+    p_bases0 = wave_sum_u64(p_bases0);
+    p_bases1 = wave_sum_u64(p_bases1);
+    if (lane_id() == 0) {
+        if (clipped0) atomicAdd(&a.counts[0], (unsigned long long)clipped0);
+        if (clipped1) atomicAdd(&a.counts[1], (unsigned long long)clipped1);
+        if (dropped0) atomicAdd(&a.counts[2], (unsigned long long)dropped0);
+        if (dropped1) atomicAdd(&a.counts[3], (unsigned long long)dropped1);
+        if (bases0) atomicAdd(&a.counts[4], (unsigned long long)bases0);
+        if (bases1) atomicAdd(&a.counts[5], (unsigned long long)bases1);
+        if (p_clipped) atomicAdd(&a.pair_counts[0], (unsigned long long)p_clipped);
+        if (p_dropped) atomicAdd(&a.pair_counts[1], (unsigned long long)p_dropped);
+        if (p_long) atomicAdd(&a.pair_counts[2], (unsigned long long)p_long);
+        if (p_scored) atomicAdd(&a.pair_counts[3], (unsigned long long)p_scored);
+        if (p_bases0) atomicAdd(&a.pair_counts[4], (unsigned long long)p_bases0);
+        if (p_bases1) atomicAdd(&a.pair_counts[5], (unsigned long long)p_bases1);
     }
 }
 
@@ -236,9 +455,11 @@ int clip_launch(pf_ctx *ctx, int n_files, const char *const *text, const uint64_
     S->last[0] = clip_end[0];
     S->last[1] = n_files == 2 ? clip_end[1] : nullptr;
     S->last_n = n_rec;
+    const bool palin = n_files == 2 && S->n_pairs != 0;               // K-PALIN follows and writes the final ends
+    const bool simple = S->n_adapters != 0 || !palin;                 // (a single-ended call with no simple adapter: every end is n)
     size_t at = (size_t)-1;
-    (void)ctx_begin_at(ctx, PF_K_CLIP, ctx->stream, &at);
-    for (int f = 0; f < n_files; ++f) {
+    if (simple) (void)ctx_begin_at(ctx, PF_K_CLIP, ctx->stream, &at);
+    for (int f = 0; f < n_files && simple; ++f) {
         ClipArgs a = {};
         a.text = text[f];
         a.n_bytes = n_bytes[f];
@@ -253,12 +474,38 @@ int clip_launch(pf_ctx *ctx, int n_files, const char *const *text, const uint64_
         a.phred = phred;
         a.clip_end = clip_end[f];
         a.counts = S->d_counts;
+        a.count_ends = palin ? 0u : 1u;
         k_clip<<<ctx_grid(ctx, n_rec * TRIM_ROW, TRIM_BLOCK, 8), TRIM_BLOCK, 0, ctx->stream>>>(a);
     }
-    ctx_end_at(ctx, at, ctx->stream);
+    if (simple) ctx_end_at(ctx, at, ctx->stream);
+    if (palin) {
+        PalinArgs a = {};
+        for (int f = 0; f < 2; ++f) {
+            a.text[f] = text[f];
+            a.lines[f] = lines[f];
+            a.clip_end[f] = clip_end[f];
+        }
+        a.n_rec = n_rec;
+        a.prefix = S->d_prefix;
+        a.plen = S->d_plen;
+        a.n_pairs = S->n_pairs;
+        a.seed = S->seed;
+        a.pair_score = S->pair_score;
+        a.pair_min = S->pair_min;
+        a.keep_both = S->keep_both;
+        a.phred = phred;
+        a.have_simple = simple ? 1u : 0u;
+        a.counts = S->d_counts;
+        a.pair_counts = S->d_pair_counts;
+        size_t pat = (size_t)-1;
+        (void)ctx_begin_at(ctx, PF_K_PALIN, ctx->stream, &pat);
+        k_palin<<<ctx_grid(ctx, n_rec * TRIM_ROW, TRIM_BLOCK, 8), TRIM_BLOCK, 0, ctx->stream>>>(a);
+        ctx_end_at(ctx, pat, ctx->stream);
+    }
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess) { pf::CtxErr{ctx} = std::string("K-CLIP launch: ") + hipGetErrorString(le); return PF_ERR_HIP; }
-    ctx_units(ctx, PF_K_CLIP, n_rec * (uint64_t)n_files);
+    if (simple) ctx_units(ctx, PF_K_CLIP, n_rec * (uint64_t)n_files);
+    if (palin) ctx_units(ctx, PF_K_PALIN, n_rec);
     return PF_OK;
 }
 
@@ -275,6 +522,9 @@ void clip_destroy(pf_ctx *ctx) {
     if (S->d_ad) (void)hipFree(S->d_ad);
     if (S->d_meta) (void)hipFree(S->d_meta);
     if (S->d_counts) (void)hipFree(S->d_counts);
+    if (S->d_prefix) (void)hipFree(S->d_prefix);
+    if (S->d_plen) (void)hipFree(S->d_plen);
+    if (S->d_pair_counts) (void)hipFree(S->d_pair_counts);
     delete S;
     ctx->clip = nullptr;
 }
@@ -283,13 +533,18 @@ void clip_destroy(pf_ctx *ctx) {
 
 using namespace pf;
 
-extern "C" int pf_clip_begin(pf_ctx *ctx, const char *bases, const uint32_t *adapter_off, const uint8_t *side, uint32_t n_adapters, uint32_t seed,
-                             uint32_t score) {
+// pf_clip_begin (prefix_off == nullptr, n_pairs == 0) and pf_clip_begin_pairs
+static int clip_begin(pf_ctx *ctx, const char *who, bool pairs, const char *bases, const uint32_t *adapter_off, const uint8_t *side, uint32_t n_adapters,
+                      const char *prefix_bases, const uint32_t *prefix_off, uint32_t n_pairs, uint32_t seed, uint32_t score, uint32_t pair_score,
+                      uint32_t pair_min, int keep_both) {
     if (!ctx) return PF_ERR_ARG;
-    auto refuse = [&](const std::string &m) { pf::CtxErr{ctx} = "pf_clip_begin: " + m; return (int)PF_ERR_ARG; };
+    auto refuse = [&](const std::string &m) { pf::CtxErr{ctx} = std::string(who) + ": " + m; return (int)PF_ERR_ARG; };
     if (ctx->clip) return refuse("a clip is open already");
     uint32_t bad = 0;
-    const int c = pf_clip::set_clause(bases, adapter_off, side, n_adapters, seed, score, &bad);
+    bool of_pair = false;   // the refusal names a prefix pair, not an adapter
+    const int c = pairs ? pf_clip::pair_set_clause(bases, adapter_off, side, n_adapters, prefix_bases, prefix_off, n_pairs, seed, score, pair_score, pair_min, &bad, &of_pair)
+                        : pf_clip::set_clause(bases, adapter_off, side, n_adapters, seed, score, &bad);
+    if (of_pair && (c == pf_clip::REFUSE_PAIR_LENGTHS || c == pf_clip::REFUSE_LENGTH || c == pf_clip::REFUSE_BYTE)) return refuse("prefix pair " + std::to_string(bad) + ": " + pf_clip::refusal_text(c));
     if (c == pf_clip::REFUSE_LENGTH || c == pf_clip::REFUSE_BYTE || c == pf_clip::REFUSE_SIDE)
         return refuse("adapter " + std::to_string(bad) + ": " + pf_clip::refusal_text(c));
     if (c) return refuse(pf_clip::refusal_text(c));
@@ -304,21 +559,66 @@ extern "C" int pf_clip_begin(pf_ctx *ctx, const char *bases, const uint32_t *ada
             ad[a].hi[j >> 5] |= (code >> 1) << (j & 31);
         }
     }
+    std::vector<char> prefix((size_t)n_pairs * 256, 'N');
+    std::vector<uint32_t> plen(n_pairs);
+    for (uint32_t q = 0; q < n_pairs; ++q) {
+        plen[q] = prefix_off[2 * q + 1] - prefix_off[2 * q];
+        for (uint32_t h = 0; h < 2; ++h)
+            for (uint32_t j = 0; j < plen[q]; ++j) prefix[256 * q + 128 * h + j] = (char)((uint8_t)prefix_bases[prefix_off[2 * q + h] + j] & 0xDFu);
+    }
     PF_HIP(hipSetDevice(ctx->device));
     ClipState *S = new ClipState;
     ctx->clip = S;
     S->n_adapters = n_adapters;
     S->seed = seed;
     S->score = score;
+    S->n_pairs = n_pairs;
+    S->pair_score = pair_score;
+    S->pair_min = pair_min;
+    S->keep_both = keep_both ? 1u : 0u;
     struct Undo { pf_ctx *c; bool armed; ~Undo() { if (armed) clip_destroy(c); } } undo{ctx, true};
-    PF_HIP(hipMalloc(reinterpret_cast<void **>(&S->d_ad), ad.size() * sizeof(ClipAdapter)));
-    PF_HIP(hipMalloc(reinterpret_cast<void **>(&S->d_meta), meta.size() * 4));
+    PF_HIP(hipMalloc(reinterpret_cast<void **>(&S->d_ad), (ad.size() + 1) * sizeof(ClipAdapter)));   // (+ 1: a clip of prefix pairs alone holds none)
+    PF_HIP(hipMalloc(reinterpret_cast<void **>(&S->d_meta), (meta.size() + 1) * 4));
     PF_HIP(hipMalloc(reinterpret_cast<void **>(&S->d_counts), sizeof(pf_clip_stats)));
-    PF_HIP(hipMemcpyAsync(S->d_ad, ad.data(), ad.size() * sizeof(ClipAdapter), hipMemcpyHostToDevice, ctx->stream));
-    PF_HIP(hipMemcpyAsync(S->d_meta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (n_adapters) {
+        PF_HIP(hipMemcpyAsync(S->d_ad, ad.data(), ad.size() * sizeof(ClipAdapter), hipMemcpyHostToDevice, ctx->stream));
+        PF_HIP(hipMemcpyAsync(S->d_meta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
     PF_HIP(hipMemsetAsync(S->d_counts, 0, sizeof(pf_clip_stats), ctx->stream));
+    if (n_pairs) {
+        PF_HIP(hipMalloc(reinterpret_cast<void **>(&S->d_prefix), prefix.size()));
+        PF_HIP(hipMalloc(reinterpret_cast<void **>(&S->d_plen), plen.size() * 4));
+        PF_HIP(hipMalloc(reinterpret_cast<void **>(&S->d_pair_counts), sizeof(pf_clip_pair_stats)));
+        PF_HIP(hipMemcpyAsync(S->d_prefix, prefix.data(), prefix.size(), hipMemcpyHostToDevice, ctx->stream));
+        PF_HIP(hipMemcpyAsync(S->d_plen, plen.data(), plen.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        PF_HIP(hipMemsetAsync(S->d_pair_counts, 0, sizeof(pf_clip_pair_stats), ctx->stream));
+    }
     PF_HIP(hipStreamSynchronize(ctx->stream));   // (the host vectors go away)
     undo.armed = false;
+    return PF_OK;
+}
+
+extern "C" int pf_clip_begin(pf_ctx *ctx, const char *bases, const uint32_t *adapter_off, const uint8_t *side, uint32_t n_adapters, uint32_t seed,
+                             uint32_t score) {
+    return clip_begin(ctx, "pf_clip_begin", false, bases, adapter_off, side, n_adapters, nullptr, nullptr, 0, seed, score, 0, 0, 0);
+}
+
+extern "C" int pf_clip_begin_pairs(pf_ctx *ctx, const char *bases, const uint32_t *adapter_off, const uint8_t *side, uint32_t n_adapters,
+                                   const char *prefix_bases, const uint32_t *prefix_off, uint32_t n_pairs, uint32_t seed, uint32_t score,
+                                   uint32_t pair_score, uint32_t pair_min, int keep_both) {
+    return clip_begin(ctx, "pf_clip_begin_pairs", true, bases, adapter_off, side, n_adapters, prefix_bases, prefix_off, n_pairs, seed, score, pair_score,
+                      pair_min, keep_both);
+}
+
+extern "C" int pf_clip_pair_stats_get(pf_ctx *ctx, pf_clip_pair_stats *stats) {
+    if (!ctx) return PF_ERR_ARG;
+    auto refuse = [&](const std::string &m) { pf::CtxErr{ctx} = "pf_clip_pair_stats_get: " + m; return (int)PF_ERR_ARG; };
+    if (!ctx->clip) return refuse("no clip is open");
+    if (!clip_state(ctx)->n_pairs) return refuse("the open clip holds no prefix pairs");
+    if (!stats) return refuse("stats is needed");
+    PF_HIP(hipSetDevice(ctx->device));
+    PF_HIP(hipMemcpyAsync(stats, clip_state(ctx)->d_pair_counts, sizeof(pf_clip_pair_stats), hipMemcpyDeviceToHost, ctx->stream));
+    PF_HIP(hipStreamSynchronize(ctx->stream));
     return PF_OK;
 }
 

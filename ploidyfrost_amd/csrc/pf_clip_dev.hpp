@@ -13,7 +13,9 @@ inline bool clip_is_open(const pf_ctx *ctx) { return ctx->clip != nullptr; }
 void clip_forget(pf_ctx *ctx);
 // clip_end[f][r] = the clip end of record r of file f (n: untouched, 0: dropped) for the n_rec whole records of each of n_files
 // chunks on the device (text 16-byte aligned, `lines` of fastq_index).  On the context's stream, no wait; the clip's counters are
-// added to on the device.  One timed launch of PF_K_CLIP; unit: records.  A clip is open.
+// added to on the device.  One timed launch of PF_K_CLIP; unit: records.  A clip is open.  Where it holds prefix pairs
+// (pf_clip_begin_pairs) and n_files == 2, K-PALIN follows in a timed launch of its own (PF_K_PALIN; unit: pairs) and clip_end[f][r]
+// is the final end -- the smaller of the simple end and the pair end; with no simple adapter K-CLIP is then not launched at all.
 int clip_launch(pf_ctx *ctx, int n_files, const char *const *text, const uint64_t *n_bytes, const uint32_t *const *lines, uint64_t n_rec, uint32_t phred,
                 uint32_t *const *clip_end);
 

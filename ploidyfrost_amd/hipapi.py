@@ -45,6 +45,9 @@ K_GUNZIP = K_INFLATE + 1       # PF_K_GUNZIP ("k_gunzip"): everything one pf_inf
 K_FASTA = K_GUNZIP + 1         # PF_K_FASTA ("k_fasta"): everything the index of one pf_fasta_index / pf_*_fasta call launches; unit: bytes of the chunk
 K_DEFLATE = K_FASTA + 1        # PF_K_DEFLATE ("k_deflate"): everything one pf_deflate_bgzf launches; unit: bytes of text
 K_CLIP = K_DEFLATE + 1         # PF_K_CLIP ("k_clip"): the clipping kernels of one trim / trimmed-count call while a clip is open; unit: records
+K_PALIN = K_CLIP + 1           # PF_K_PALIN ("k_palin"): palindrome mode's kernel of one paired trim / trimmed-count call while a clip with prefix pairs is open; unit: pairs
+CLIP_PAIR_STATS = np.dtype([("pairs_clipped", "<u8"), ("pairs_dropped", "<u8"), ("pairs_too_long", "<u8"), ("candidates_scored", "<u8"),
+                            ("bases_clipped", "<u8", (2,))])   # pf_clip_pair_stats
 CLIP_STATS = np.dtype([(f, "<u8", (2,)) for f in ("reads_clipped", "reads_dropped", "bases_clipped", "candidates_scored")])   # pf_clip_stats
 FASTA_TILE = 4096              # PF_FASTA_TILE: bytes of the chunk one block of K-FASTA's compaction kernel takes at a time
 GUNZIP_RESULT = np.dtype([("out_bytes", "<u8"), ("end_bit", "<u8"), ("final", "<u4"), ("n_window", "<u4"), ("crc_raw", "<u4"), ("clause", "<u4"),
@@ -279,6 +282,8 @@ def load_library() -> C.CDLL:
         "pf_maskcount_fastq_trimmed": (i, [vp, vp, u64, i, vp, u32, u32, C.POINTER(u64), vp, vp, C.POINTER(u64)]),
         "pf_maskcount_fastq_pair_trimmed": (i, [vp, vp, u64, vp, u64, i, vp, u32, u32, C.POINTER(u64), vp, vp, C.POINTER(u64)]),
         "pf_clip_begin": (i, [vp, vp, vp, vp, u32, u32, u32]),
+        "pf_clip_begin_pairs": (i, [vp, vp, vp, vp, u32, vp, vp, u32, u32, u32, u32, u32, i]),
+        "pf_clip_pair_stats_get": (i, [vp, vp]),
         "pf_clip_stats_get": (i, [vp, vp]),
         "pf_clip_end": (i, [vp]),
         "pf_clip_last_ends": (i, [vp, i, vp, u64]),
@@ -312,7 +317,8 @@ DECLARED_SYMBOLS = ["pf_create", "pf_warmup", "pf_destroy", "pf_last_error", "pf
                     "pf_trim_table_fastq", "pf_trim_table_fastq_pair", "pf_count_fastq_trimmed", "pf_count_fastq_pair_trimmed",
                     "pf_maskcount_fastq_trimmed", "pf_maskcount_fastq_pair_trimmed", "pf_inflate_bgzf", "pf_inflate_gzip", "pf_device_alloc", "pf_copy",
                     "pf_fasta_index", "pf_fasta_index_fetch", "pf_count_fasta", "pf_maskcount_fasta", "pf_color_fasta", "pf_deflate_bgzf",
-                    "pf_clip_begin", "pf_clip_stats_get", "pf_clip_end", "pf_clip_last_ends"]
+                    "pf_clip_begin", "pf_clip_stats_get", "pf_clip_end", "pf_clip_last_ends",
+                    "pf_clip_begin_pairs", "pf_clip_pair_stats_get"]
 
 
 class TrimPlan(C.Structure):   # pf_trim_plan
@@ -656,6 +662,38 @@ class Device:
         side = np.ascontiguousarray(side, dtype=np.uint8)
         self._check(self.L.pf_clip_begin(self.h, bases.ctypes.data if len(bases) else None, off.ctypes.data, side.ctypes.data if len(side) else None,
                                          len(side), int(seed), int(score)))
+
+    def clip_begin_pairs(self, adapters, prefix_pairs, seed: int = 2, score: int = 10, pair_score: int = 30, pair_min: int = 8, keep_both: bool = False):
+        """K-PALIN (pf_clip_begin_pairs): a clip with prefix pairs -- the paired calls also clip by palindrome mode.  adapters: as
+        clip_begin takes them, may be empty; prefix_pairs: a list of (P1, P2), or the dict of hostapi.clip_parse_adapters(pairs=True)
+        (then `adapters` may be that dict as well).  Refusals raise DeviceError by name."""
+        if isinstance(adapters, dict):
+            bases, off, side = adapters["bases"], adapters["off"], adapters["side"]
+        else:
+            seqs = [s.encode() if isinstance(s, str) else bytes(s) for s, _ in adapters]
+            bases = b"".join(seqs)
+            off = np.concatenate([[0], np.cumsum([len(s) for s in seqs])]) if seqs else np.zeros(1)
+            side = [sd for _, sd in adapters]
+        if isinstance(prefix_pairs, dict):
+            pbases, poff = prefix_pairs["prefix_bases"], prefix_pairs["prefix_off"]
+        else:
+            halves = [h.encode() if isinstance(h, str) else bytes(h) for pr in prefix_pairs for h in pr]
+            pbases = b"".join(halves)
+            poff = np.concatenate([[0], np.cumsum([len(h) for h in halves])]) if halves else np.zeros(1)
+        bases = np.frombuffer(bytes(bases), dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        side = np.ascontiguousarray(side, dtype=np.uint8)
+        pbases = np.frombuffer(bytes(pbases), dtype=np.uint8)
+        poff = np.ascontiguousarray(poff, dtype=np.uint32)
+        self._check(self.L.pf_clip_begin_pairs(self.h, bases.ctypes.data if len(bases) else None, off.ctypes.data, side.ctypes.data if len(side) else None,
+                                               len(side), pbases.ctypes.data if len(pbases) else None, poff.ctypes.data, (len(poff) - 1) // 2, int(seed),
+                                               int(score), int(pair_score), int(pair_min), int(bool(keep_both))))
+
+    def clip_pair_stats(self) -> dict:
+        """pf_clip_pair_stats_get: what K-PALIN has counted since clip_begin_pairs; bases_clipped is [file 1, file 2]"""
+        st = np.zeros(1, dtype=CLIP_PAIR_STATS)
+        self._check(self.L.pf_clip_pair_stats_get(self.h, st.ctypes.data))
+        return {f: ([int(v) for v in st[0][f]] if f == "bases_clipped" else int(st[0][f])) for f in CLIP_PAIR_STATS.names}
 
     def clip_stats(self) -> dict:
         """pf_clip_stats_get: what the open clip has counted since clip_begin, each field [file 1 and single-ended calls, file 2]"""

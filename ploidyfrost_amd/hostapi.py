@@ -52,7 +52,8 @@ DECLARED_SYMBOLS = ["pfh_open", "pfh_close", "pfh_last_error", "pfh_set_output_d
                     "pfh_gunzip_header", "pfh_gunzip_file_kind", "pfh_gunzip_candidate", "pfh_gunzip_call", "pfh_gunzip_file", "pfh_gunzip_clause_text",
                     "pfh_deflate_member", "pfh_deflate_bound", "pfh_reads_gz_out",
                     "pfh_reads_adapters", "pfh_reads_adapters_report", "pfh_clip_parse_adapters", "pfh_clip_refusal_text", "pfh_clip_read",
-                    "pfh_trim_fastq_chunk_clip"]
+                    "pfh_trim_fastq_chunk_clip", "pfh_reads_adapter_pairs", "pfh_reads_adapters_pair_report", "pfh_clip_parse_adapter_pairs",
+                    "pfh_clip_pair", "pfh_trim_fastq_pair_chunk_clip"]
 
 
 class RunOptions(C.Structure):   # pfh_run_options (include/ploidyfrost_host.h)
@@ -278,6 +279,22 @@ def load_library() -> C.CDLL:
     L.pfh_clip_parse_adapters.restype = C.c_int
     L.pfh_clip_parse_adapters.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                           C.POINTER(C.c_uint64)]
+    L.pfh_reads_adapter_pairs.restype = None
+    L.pfh_reads_adapter_pairs.argtypes = [C.c_uint32, C.c_uint32, C.c_int]
+    L.pfh_reads_adapters_pair_report.restype = None
+    L.pfh_reads_adapters_pair_report.argtypes = [C.POINTER(C.c_uint32), C.c_void_p]
+    L.pfh_clip_parse_adapter_pairs.restype = C.c_int
+    L.pfh_clip_parse_adapter_pairs.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p,
+                                               C.c_uint64, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    L.pfh_clip_pair.restype = C.c_int
+    L.pfh_clip_pair.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_void_p,
+                                C.c_void_p, C.c_void_p]
+    L.pfh_trim_fastq_pair_chunk_clip.restype = C.c_int
+    L.pfh_trim_fastq_pair_chunk_clip.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
     L.pfh_clip_refusal_text.restype = C.c_char_p
     L.pfh_clip_refusal_text.argtypes = [C.c_int]
     L.pfh_clip_read.restype = C.c_int
@@ -629,15 +646,26 @@ def trim_fastq_chunk(text: bytes, steps, phred: int = 33, final: bool = True):
 
 
 CLIP_STATS_FIELDS = ("reads_clipped", "reads_dropped", "bases_clipped", "candidates_scored")   # pf_clip_stats: each [file 1, file 2]
-CLIP_REFUSALS = ("none", "not_fasta", "byte", "length", "too_many", "no_adapter", "seed", "score", "side")   # pf_clip::Refusal, in its order
+CLIP_REFUSALS = ("none", "not_fasta", "byte", "length", "too_many", "no_adapter", "seed", "score", "side", "pair_partner", "pair_lengths",
+                 "too_many_pairs", "no_pair", "pair_score", "pair_min")   # pf_clip::Refusal, in its order
 CLIP_MAX_ADAPTERS, CLIP_MAX_LEN = 64, 128
+CLIP_MAX_PAIRS, CLIP_MAX_PAIR_READ = 8, 1024
+CLIP_PAIR_STATS_FIELDS = ("pairs_clipped", "pairs_dropped", "pairs_too_long", "candidates_scored", "bases_clipped")   # pf_clip_pair_stats; the last is [file 1, file 2]
 
 
-def clip_parse_adapters(path_or_bytes) -> dict:
+def _pair_stats_dict(raw) -> dict:
+    out = {f: int(v) for f, v in zip(CLIP_PAIR_STATS_FIELDS[:4], raw[:4])}
+    out["bases_clipped"] = [int(raw[4]), int(raw[5])]
+    return out
+
+
+def clip_parse_adapters(path_or_bytes, pairs: bool = False) -> dict:
     """The adapter file of `--adapters` by the parser of the rule header (pfh_clip_parse_adapters, csrc/pf_clip_rule.hpp; no device):
     dict with bases (the usable adapters one behind the other, upper case), off (n + 1 offsets), side (0 both files, 1, 2), n and
     skipped (the `Prefix` entries of palindrome mode, which is not built).  bytes are the file's text, anything else a path.  A file
-    that is refused raises ValueError with the refusal's text and the 1-based record; .refusal names it, .bad_record holds the record."""
+    that is refused raises ValueError with the refusal's text and the 1-based record; .refusal names it, .bad_record holds the record.
+    pairs=True (`--adapter-pairs`, pfh_clip_parse_adapter_pairs): the `Prefix<X>/1`, `Prefix<X>/2` entries are prefix pairs instead --
+    the dict also holds prefix_bases, prefix_off (2 * n_pairs + 1 offsets: P1, P2 of every pair) and n_pairs; n may then be 0."""
     L = load_library()
     if isinstance(path_or_bytes, (bytes, bytearray)):
         text, where = bytes(path_or_bytes), "adapters"
@@ -650,13 +678,23 @@ def clip_parse_adapters(path_or_bytes) -> dict:
     off = np.zeros(CLIP_MAX_ADAPTERS + 1, dtype=np.uint32)
     side = np.zeros(CLIP_MAX_ADAPTERS, dtype=np.uint8)
     n, skipped, bad = C.c_uint32(), C.c_uint32(), C.c_uint64()
-    c = L.pfh_clip_parse_adapters(src.ctypes.data if len(src) else None, len(src), bases.ctypes.data, len(bases), off.ctypes.data, side.ctypes.data,
-                                  C.byref(n), C.byref(skipped), C.byref(bad))
+    if pairs:
+        pbases = np.zeros(CLIP_MAX_PAIRS * 2 * CLIP_MAX_LEN, dtype=np.uint8)
+        poff = np.zeros(2 * CLIP_MAX_PAIRS + 1, dtype=np.uint32)
+        nq = C.c_uint32()
+        c = L.pfh_clip_parse_adapter_pairs(src.ctypes.data if len(src) else None, len(src), bases.ctypes.data, len(bases), off.ctypes.data, side.ctypes.data,
+                                           C.byref(n), pbases.ctypes.data, len(pbases), poff.ctypes.data, C.byref(nq), C.byref(bad))
+    else:
+        c = L.pfh_clip_parse_adapters(src.ctypes.data if len(src) else None, len(src), bases.ctypes.data, len(bases), off.ctypes.data, side.ctypes.data,
+                                      C.byref(n), C.byref(skipped), C.byref(bad))
     if c:
         e = ValueError("%s: %s%s" % (where, "record %d: " % bad.value if bad.value else "", L.pfh_clip_refusal_text(c).decode()))
         e.refusal, e.bad_record = CLIP_REFUSALS[c], bad.value
         raise e
-    return dict(bases=bases[: off[n.value]].tobytes(), off=off[: n.value + 1].copy(), side=side[: n.value].copy(), n=n.value, skipped=skipped.value)
+    out = dict(bases=bases[: off[n.value]].tobytes(), off=off[: n.value + 1].copy(), side=side[: n.value].copy(), n=n.value, skipped=skipped.value)
+    if pairs:
+        out.update(prefix_bases=pbases[: poff[2 * nq.value]].tobytes(), prefix_off=poff[: 2 * nq.value + 1].copy(), n_pairs=nq.value)
+    return out
 
 
 def clip_adapters(adapters) -> dict:
@@ -716,9 +754,108 @@ def trim_fastq_chunk_clip(text: bytes, steps, adapters, side: int = 1, seed: int
                 clip={f: [int(v) for v in row] for f, row in zip(CLIP_STATS_FIELDS, clip)})
 
 
-def _set_adapters(L, adapters, seed, score):
-    """`--adapters` of the next trim / run call (pfh_reads_adapters): a path, or None for no clipping"""
+def _prefix_pairs(adapters) -> dict:
+    """adapters with prefix pairs as the pair calls take them: the dict of clip_parse_adapters(pairs=True), a path or the bytes of an
+    adapter file, or (list of (sequence, side), list of (P1, P2)) (nothing is checked there: the library refuses by name)."""
+    if isinstance(adapters, dict):
+        return adapters
+    if isinstance(adapters, (list, tuple)):
+        simple, prefix = adapters
+        A = clip_adapters(list(simple))
+        halves = [h.encode() if isinstance(h, str) else bytes(h) for pr in prefix for h in pr]
+        poff = np.zeros(len(halves) + 1, dtype=np.uint32)
+        poff[1:] = np.cumsum([len(h) for h in halves], dtype=np.uint64) if halves else []
+        return dict(A, prefix_bases=b"".join(halves), prefix_off=poff, n_pairs=len(halves) // 2)
+    return clip_parse_adapters(adapters, pairs=True)
+
+
+def _pair_args(A):
+    bases, pbases = np.frombuffer(A["bases"], dtype=np.uint8), np.frombuffer(A["prefix_bases"], dtype=np.uint8)
+    keep = (bases, pbases, A["off"], A["side"], A["prefix_off"])   # (alive while the call runs)
+    return keep, (bases.ctypes.data if len(bases) else None, A["off"].ctypes.data, A["side"].ctypes.data if A["n"] else None, A["n"],
+                  pbases.ctypes.data if len(pbases) else None, A["prefix_off"].ctypes.data, A["n_pairs"])
+
+
+def clip_pair(seq1: bytes, qual1: bytes, seq2: bytes, qual2: bytes, adapters, seed: int = 2, score: int = 10, pair_score: int = 30, pair_min: int = 8,
+              keep_both: bool = False, phred: int = 33, stats: bool = False):
+    """The rule of `--adapters --adapter-pairs` on the two reads of one pair (pfh_clip_pair; no device): [clip end of file 1, of file 2]
+    -- simple mode and palindrome mode together.  adapters: see _prefix_pairs.  stats=True: (ends, clip statistics, pair statistics) of
+    this one pair.  Values that are refused raise ValueError."""
+    L = load_library()
+    A = _prefix_pairs(adapters)
+    arrs = [np.frombuffer(bytes(x), dtype=np.uint8) for x in (seq1, qual1, seq2, qual2)]
+    if len(arrs[0]) != len(arrs[1]) or len(arrs[2]) != len(arrs[3]):
+        raise ValueError("clip_pair: the quality line is as long as the sequence line")
+    ptr = [a.ctypes.data if len(a) else None for a in arrs]
+    keep, pa = _pair_args(A)
+    end = np.zeros(2, dtype=np.uint32)
+    clip = np.zeros((len(CLIP_STATS_FIELDS), 2), dtype=np.uint64)
+    ps = np.zeros(6, dtype=np.uint64)
+    rc = L.pfh_clip_pair(ptr[0], ptr[1], len(arrs[0]), ptr[2], ptr[3], len(arrs[2]), *pa, int(seed), int(score), int(pair_score), int(pair_min),
+                         int(bool(keep_both)), int(phred), end.ctypes.data, clip.ctypes.data, ps.ctypes.data)
+    if rc < 0:
+        raise ValueError(L.pfh_last_error(None).decode())
+    ends = [int(end[0]), int(end[1])]
+    return (ends, {f: [int(v) for v in row] for f, row in zip(CLIP_STATS_FIELDS, clip)}, _pair_stats_dict(ps)) if stats else ends
+
+
+TRIM_PAIR_CLIP_CLAUSES = MASK_CLAUSES + ("pair_count",)   # pf_mask::Clause, then pf_clip::PAIR_COUNTS_DIFFER
+
+
+def trim_fastq_pair_chunk_clip(text1: bytes, text2: bytes, steps, adapters, seed: int = 2, score: int = 10, pair_score: int = 30, pair_min: int = 8,
+                               keep_both: bool = False, phred: int = 33, final: bool = True) -> dict:
+    """What pf_trim_fastq_pair gives for one chunk of each file while a clip with prefix pairs is open, by the host's plain restatement
+    (pfh_trim_fastq_pair_chunk_clip; no device): dict with clause, bad_record (2 * record + file), out (o1, u1, o2, u2), bytes_used,
+    begin, len, clip_end and stats per file, n_records, clip (CLIP_STATS_FIELDS) and pairs (CLIP_PAIR_STATS_FIELDS).  steps may be empty."""
+    L = load_library()
+    st = trim_parse_steps(steps) if len(steps) else np.zeros(0, dtype=TRIM_STEP)
+    A = _prefix_pairs(adapters)
+    keep, pa = _pair_args(A)
+    src = [np.frombuffer(bytes(t), dtype=np.uint8) for t in (text1, text2)]
+    n = [len(x) for x in src]
+    outs = [np.zeros(n[d // 2] + 1, dtype=np.uint8) for d in range(4)]
+    cap = min(n) // 4 + 1
+    begin, ln, ce = ([np.zeros(cap, dtype=np.uint32) for _ in range(2)] for _ in range(3))
+    ptrs = lambda arrs: (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+    stats = np.zeros((2, len(TRIM_STATS_FIELDS)), dtype=np.uint64)
+    clip = np.zeros((len(CLIP_STATS_FIELDS), 2), dtype=np.uint64)
+    ps = np.zeros(6, dtype=np.uint64)
+    out_n, used = np.zeros(4, dtype=np.uint64), np.zeros(2, dtype=np.uint64)
+    recs, bad = C.c_uint64(), C.c_uint64()
+    clause = L.pfh_trim_fastq_pair_chunk_clip(src[0].ctypes.data if n[0] else None, n[0], src[1].ctypes.data if n[1] else None, n[1], int(final),
+                                              st.ctypes.data if len(st) else None, len(st), int(phred), *pa, int(seed), int(score), int(pair_score),
+                                              int(pair_min), int(bool(keep_both)), ptrs(outs), out_n.ctypes.data, used.ctypes.data, ptrs(begin), ptrs(ln),
+                                              ptrs(ce), cap, C.byref(recs), stats.ctypes.data, clip.ctypes.data, ps.ctypes.data, C.byref(bad))
+    if clause < 0:
+        raise ValueError(L.pfh_last_error(None).decode())
+    m = recs.value
+    return dict(clause=TRIM_PAIR_CLIP_CLAUSES[clause], bad_record=bad.value, out=[outs[d][: int(out_n[d])].tobytes() for d in range(4)],
+                bytes_used=[int(v) for v in used], n_records=m, begin=[b[:m].tolist() for b in begin], len=[x[:m].tolist() for x in ln],
+                clip_end=[x[:m].tolist() for x in ce], stats=[{f: int(v) for f, v in zip(TRIM_STATS_FIELDS, row)} for row in stats],
+                clip={f: [int(v) for v in row] for f, row in zip(CLIP_STATS_FIELDS, clip)}, pairs=_pair_stats_dict(ps))
+
+
+def _set_adapters(L, adapters, seed, score, pairs=False, pair_score=30, pair_min=8, keep_both=False):
+    """`--adapters` of the next trim / run call (pfh_reads_adapters): a path, or None for no clipping; pairs: `--adapter-pairs` and
+    its values (pfh_reads_adapter_pairs).  The pair options without adapters, or the values without pairs, are refused as the command
+    line refuses them."""
+    if adapters is None and (pairs or keep_both or pair_score != 30 or pair_min != 8):
+        raise ValueError("adapter_pairs, adapter_pair_score, adapter_pair_min and adapter_keep_both need adapters")
+    if not pairs and (keep_both or pair_score != 30 or pair_min != 8):
+        raise ValueError("adapter_pair_score, adapter_pair_min and adapter_keep_both need adapter_pairs")
     L.pfh_reads_adapters(None if adapters is None else os.fsencode(adapters), int(seed), int(score))
+    if pairs:
+        L.pfh_reads_adapter_pairs(int(pair_score), int(pair_min), int(bool(keep_both)))
+
+
+def clip_pair_report() -> dict:
+    """What the last trim / run call of this thread that took adapter_pairs= reported (pfh_reads_adapters_pair_report): pairs (the prefix
+    pairs of the file) and the statistics of CLIP_PAIR_STATS_FIELDS -- the tail of the command's `clip:` line."""
+    L = load_library()
+    q = C.c_uint32()
+    ps = np.zeros(6, dtype=np.uint64)
+    L.pfh_reads_adapters_pair_report(C.byref(q), ps.ctypes.data)
+    return dict(_pair_stats_dict(ps), pairs=q.value)
 
 
 def clip_report() -> dict:
@@ -805,10 +942,13 @@ def trim_fastq(inputs, out: str, steps, phred: int = 33, trimlog=None, chunk_byt
 
 
 def trim_fastq_pair(in1: str, in2: str, outs, steps, phred: int = 33, trimlog=None, chunk_bytes: int = 0, gz: bool = False, gz_out: bool = False,
-                    adapters=None, adapter_seed: int = 2, adapter_score: int = 10):
+                    adapters=None, adapter_seed: int = 2, adapter_score: int = 10, adapter_pairs: bool = False, adapter_pair_score: int = 30,
+                    adapter_pair_min: int = 8, adapter_keep_both: bool = False):
     """`ploidyfrost trim -1 in1 -2 in2 -o1 .. -u1 .. -o2 .. -u2 .. STEP...` (pfh_trim_fastq_pair): outs = (o1, u1, o2, u2).  Returns the
     statistics of file 1 and of file 2 (the pair fields are the same in both).  gz_out (`--gz-out`): the four outputs are blocked gzip.
-    adapters, adapter_seed, adapter_score: as trim_fastq takes them (names ending in /1 and /2 choose the file)."""
+    adapters, adapter_seed, adapter_score: as trim_fastq takes them (names ending in /1 and /2 choose the file).
+    adapter_pairs (`--adapter-pairs`, with adapter_pair_score, adapter_pair_min, adapter_keep_both): palindrome mode from the file's
+    prefix pairs beside simple mode (K-PALIN); clip_pair_report() gives the tail of the `clip:` line."""
     L = load_library()
     st = trim_parse_steps(steps) if len(steps) or adapters is None else np.zeros(0, dtype=TRIM_STEP)
     assert len(outs) == 4
@@ -816,7 +956,7 @@ def trim_fastq_pair(in1: str, in2: str, outs, steps, phred: int = 33, trimlog=No
     stats = np.zeros((2, len(TRIM_STATS_FIELDS)), dtype=np.uint64)
     L.pfh_reads_gz(_gz_mode(gz))
     L.pfh_reads_gz_out(int(gz_out))
-    _set_adapters(L, adapters, adapter_seed, adapter_score)
+    _set_adapters(L, adapters, adapter_seed, adapter_score, adapter_pairs, adapter_pair_score, adapter_pair_min, adapter_keep_both)
     rc = L.pfh_trim_fastq_pair(os.fsencode(in1), os.fsencode(in2), paths, st.ctypes.data if len(st) else None, len(st), phred,
                                os.fsencode(trimlog) if trimlog else None, int(chunk_bytes), 0, stats.ctypes.data)
     if rc:
@@ -963,7 +1103,8 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
               keep_tips: bool = False, keep_isolated: bool = False, g=None, z: int = 8, M: float = 2.0, D: float = -1.0, G: float = -3.0,
               threads: int = 1, model=None, model_only: bool = False, db_out=None, gfa_out=None, chunk_bytes: int = 0,
               initial_slots: int = 0, steps=None, phred: int = 33, pairs=None, gz: bool = False, fasta: bool = False,
-              adapters=None, adapter_seed: int = 2, adapter_score: int = 10) -> dict:
+              adapters=None, adapter_seed: int = 2, adapter_score: int = 10, adapter_pairs: bool = False, adapter_pair_score: int = 30,
+              adapter_pair_min: int = 8, adapter_keep_both: bool = False) -> dict:
     """`ploidyfrost run` (pfh_run_fastq): reads to ploidy estimate in one process -- the FASTQ file(s) `inputs` counted, the thresholds
     derived, the k-mers of the masked reads counted (K-MASKCOUNT), the graph built and the single-sample calling run made on one device
     context; PloidyFrost_output/<out_prefix>_*.txt in the working directory.  model: None, "cov" or "fre".  Returns the fields of the
@@ -975,7 +1116,10 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
     fasta (`--fasta`): an input whose first byte is '>' (with gz: whose first inflated byte is) is read as FASTA in both passes (K-FASTA);
     refused by name together with steps or pairs.
     adapters (`--adapters`, with adapter_seed and adapter_score): as trim_fastq takes them; they turn the trimming on as steps do, and
-    no step is needed beside them, also with pairs."""
+    no step is needed beside them, also with pairs.
+    adapter_pairs (`--adapter-pairs`, with adapter_pair_score, adapter_pair_min, adapter_keep_both): palindrome mode on pairs, as
+    trim_fastq_pair takes it; refused by name without pairs.  Only pairs of which both records are kept go on, so without
+    adapter_keep_both a clipped pair is not counted at all."""
     L = load_library()
     if pairs is not None:
         if inputs is not None:
@@ -1010,7 +1154,7 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
     per = np.zeros((max(n, 1), len(TRIM_STATS_FIELDS)), dtype=np.uint64)
     L.pfh_reads_gz(_gz_mode(gz))
     L.pfh_reads_fasta(int(bool(fasta)))
-    _set_adapters(L, adapters, adapter_seed, adapter_score)
+    _set_adapters(L, adapters, adapter_seed, adapter_score, adapter_pairs, adapter_pair_score, adapter_pair_min, adapter_keep_both)
     rc = L.pfh_run_fastq_trimmed(paths, n, int(pairs is not None), st.ctypes.data if len(st) else None, len(st), int(phred), os.fsencode(out_prefix),
                                  C.byref(o), 0, stats.ctypes.data, per.ctypes.data)
     if rc:
@@ -1025,7 +1169,8 @@ def run_multi_reads(samples, out_prefix: str, k: int = 25, ci: int = 1, cx: int 
                     keep_tips: bool = False, keep_isolated: bool = False, g=None, z: int = 8, M: float = 2.0, D: float = -1.0, G: float = -3.0,
                     threads: int = 1, model=None, model_only: bool = False, filter_multi=None, each_color: bool = False, db_out=None, gfa_out=None,
                     chunk_bytes: int = 0, initial_slots: int = 0, steps=None, phred: int = 33, pairs=None, gz: bool = False,
-                    fasta: bool = False, adapters=None, adapter_seed: int = 2, adapter_score: int = 10) -> dict:
+                    fasta: bool = False, adapters=None, adapter_seed: int = 2, adapter_score: int = 10, adapter_pairs: bool = False,
+                    adapter_pair_score: int = 30, adapter_pair_min: int = 8, adapter_keep_both: bool = False) -> dict:
     """`ploidyfrost run-multi` (pfh_run_multi_fastq): reads of several samples to one estimate per sample in one process.  samples: a
     list of (name, file or list of files), a sample a colour in the order given.  Every sample is counted and its thresholds derived,
     the k-mers of its masked reads counted (K-MASKCOUNT), their union taken (K-UNION), the coloured graph built and coloured per
@@ -1037,7 +1182,8 @@ def run_multi_reads(samples, out_prefix: str, k: int = 25, ci: int = 1, cx: int 
     names of the samples whose files are pairs (file 1, file 2, file 1, ...).  The result then has "trim": per sample the statistics of
     its units, as run_reads gives them.
     fasta (`--fasta`): as run_reads takes it; the files of a sample may mix FASTA and FASTQ.
-    adapters, adapter_seed, adapter_score: as run_reads takes them; they hold for every sample."""
+    adapters, adapter_seed, adapter_score: as run_reads takes them; they hold for every sample.
+    adapter_pairs, adapter_pair_score, adapter_pair_min, adapter_keep_both: as run_reads takes them; every sample is then a pair sample."""
     L = load_library()
     names, counts, flat, paired = [], [], [], []
     for name, files in samples:
@@ -1079,7 +1225,7 @@ def run_multi_reads(samples, out_prefix: str, k: int = 25, ci: int = 1, cx: int 
         pair_of = np.ascontiguousarray(paired, dtype=np.int32)
         L.pfh_reads_gz(_gz_mode(gz))
         L.pfh_reads_fasta(int(bool(fasta)))
-        _set_adapters(L, adapters, adapter_seed, adapter_score)
+        _set_adapters(L, adapters, adapter_seed, adapter_score, adapter_pairs, adapter_pair_score, adapter_pair_min, adapter_keep_both)
         rc = L.pfh_run_multi_fastq_trimmed(c_names, n_of.ctypes.data if len(names) else None, pair_of.ctypes.data if len(names) else None, len(names), paths,
                                            st.ctypes.data if len(st) else None, len(st), int(phred), os.fsencode(out_prefix), C.byref(o),
                                            C.byref(multi) if multi is not None else None, int(each_color), 0, stats.ctypes.data, per.ctypes.data,
