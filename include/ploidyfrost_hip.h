@@ -76,7 +76,7 @@ enum pf_kernel {
     PF_K_GUNZIP, /* K-GUNZIP: everything one pf_inflate_gzip launches (find, count, chain, decode, window, resolve with the CRC), timed as one launch; unit: inflated bytes */
     PF_K_FASTA, /* K-FASTA: everything the index of one pf_fasta_index / pf_count_fasta / pf_maskcount_fasta / pf_color_fasta call launches (newlines, lines, words, scans, compact, table), timed as one launch; the core behind it is timed under its own kernel; unit: bytes of the chunk */
     PF_K_DEFLATE, /* K-DEFLATE: everything one pf_deflate_bgzf launches (deflate, scan of the members' sizes, pack), timed as one launch; unit: bytes of text */
-    PF_K_CLIP, /* K-CLIP: the kernels one pf_trim_fastq* / pf_trim_table_fastq* / pf_*_fastq*_trimmed call launches to clip adapters while a clip is open (one per file), timed as one launch inside the call's own; unit: records */ PF_K_PALIN, /* K-PALIN: the kernel one pf_trim_fastq_pair / pf_trim_table_fastq_pair / pf_*_fastq_pair_trimmed call launches behind K-CLIP's while a clip with prefix pairs is open (palindrome mode), timed as one launch inside the call's own; unit: pairs */
+    PF_K_CLIP, /* K-CLIP: the kernels one pf_trim_fastq* / pf_trim_table_fastq* / pf_*_fastq*_trimmed call launches to clip adapters while a clip is open (one per file), timed as one launch inside the call's own; unit: records */ PF_K_PALIN, /* K-PALIN: the kernel one pf_trim_fastq_pair / pf_trim_table_fastq_pair / pf_*_fastq_pair_trimmed call launches behind K-CLIP's while a clip with prefix pairs is open (palindrome mode), timed as one launch inside the call's own; unit: pairs */ PF_K_QC, /* K-QC: the kernel one pf_qc_fastq call, or one pf_trim_fastq* / pf_trim_table_fastq* / pf_*_fastq*_trimmed call while a report is open, launches per file to add its records to the report's tables, timed as one launch per file inside the call's own; unit: records */
     PF_K_COUNT_
 };
 int pf_enable_timing(pf_ctx *, int on);
@@ -493,6 +493,24 @@ int pf_clip_begin_pairs(pf_ctx *, const char *bases, const uint32_t *adapter_off
                         const char *prefix_bases, const uint32_t *prefix_off /* 2 * n_pairs + 1 */, uint32_t n_pairs,
                         uint32_t seed, uint32_t score, uint32_t pair_score, uint32_t pair_min, int keep_both);
 int pf_clip_pair_stats_get(pf_ctx *, pf_clip_pair_stats *stats);
+/* K-QC: a read quality report accumulated on the device (csrc/pf_qc.hip; the rule, the words of a table and the text of the report:
+ * csrc/pf_qc_rule.hpp).  A report is state on the context, opened and closed as a clip is.  While one is open, pf_trim_fastq[_pair],
+ * pf_trim_table_fastq[_pair], pf_count_fastq[_pair]_trimmed and pf_maskcount_fastq[_pair]_trimmed add every whole record they take to
+ * the table (side, PF_QC_RAW) with the interval [0, n) and every record K-TRIM keeps to (side, PF_QC_KEPT) with its final interval,
+ * the clip included; with a clip open as well, every record with clip end < n adds one to clip[min(clip end, 1024)] of its side.
+ * Side 0: single-ended calls and file 1 of a pair; side 1: file 2.  Their outputs are what they are with no report open, and with
+ * none open they launch and allocate nothing new.  phred (33 or 64) is the offset the tables are taken with, whatever a call's own.
+ * pf_qc_fastq indexes one chunk by the chunk contract and the format clauses of pf_trim_fastq and adds its whole records to
+ * (side, PF_QC_RAW) alone.  pf_qc_get: words [host] receives PF_QC_TABLE_WORDS uint64_t, pf_qc_clip_get PF_QC_CLIP_WORDS (all 0 when
+ * no clip was open).  A table nothing was added to is all zero.  A second begin, and get / fastq / end without a begin: PF_ERR_ARG by name. */
+#define PF_QC_TABLE_WORDS 9515u
+#define PF_QC_CLIP_WORDS 1025u
+enum { PF_QC_RAW = 0, PF_QC_KEPT = 1 };
+int pf_qc_begin(pf_ctx *, uint32_t phred);
+int pf_qc_get(pf_ctx *, int side, int stage, uint64_t *words);
+int pf_qc_clip_get(pf_ctx *, int side, uint64_t *words);
+int pf_qc_fastq(pf_ctx *, int side, const char *text, uint64_t n_bytes, int final, uint64_t *bytes_used, uint64_t *n_records, uint64_t *bad_record);
+int pf_qc_end(pf_ctx *);
 /* K-INFLATE: blocked gzip (BGZF: what bgzip, bcl2fastq2 and BCL Convert write) inflated on the device, where pf_*_fastq read their text.
  * The rule -- the member header, RFC 1951, the refusals by name -- is csrc/pf_inflate_rule.hpp; the decoder one lane runs is
  * csrc/pf_inflate_core.hpp, shared with the host.  One wavefront per member; the CRC-32 of every member's text is checked against

@@ -297,6 +297,25 @@ int pfh_trim_fastq_pair_chunk_clip(const char *text1, uint64_t n1, const char *t
                                    uint32_t pair_min, int keep_both, char *out[4], uint64_t out_bytes[4], uint64_t bytes_used[2], uint32_t *rec_begin[2],
                                    uint32_t *rec_len[2], uint32_t *clip_end[2], uint64_t cap, uint64_t *n_records, pf_trim_stats stats[2], pf_clip_stats *clip,
                                    pf_clip_pair_stats *pairs, uint64_t *bad_record);
+/* ---- the read quality report: `ploidyfrost qc` and `--report` (K-QC, pf_qc_* in ploidyfrost_hip.h) ----
+ * The rule, the words of a table and the text of the report: csrc/pf_qc_rule.hpp.  pfh_reads_report(path): the next pfh_trim_fastq,
+ * pfh_trim_fastq_pair or pfh_run_fastq_trimmed of this thread writes the report of both stages to `path` beside its other outputs, every
+ * other output being what it is without; the call takes the switch back (null or "": none).  pfh_run_fastq refuses it by name (no
+ * trimming: `qc` reports on files as they are), pfh_run_multi_fastq* as not built.  pfh_qc_fastq: `qc` -- every file streamed on its
+ * own, inputs1 to side 1, inputs2 to side 2, stage raw alone, the report written under a temporary name and renamed at the end; takes
+ * the pfh_reads_gz switch.  The host's plain restatement, no device: pfh_qc_fastq_chunk adds one chunk of one file (file_side 1 or 2) to
+ * the tables raw, kept (trimmed != 0: the steps, and with clip_open the simple adapters as pfh_clip_read takes them) and clip, each of
+ * PF_QC_TABLE_WORDS / PF_QC_CLIP_WORDS words; it returns the clause of pfh_mask_index_fastq (0 = ok) or -1 for a refused argument.
+ * pfh_qc_report_text: tables [side][stage][PF_QC_TABLE_WORDS], clip [side][PF_QC_CLIP_WORDS] or null; *len = the bytes of the text, of
+ * which at most cap go to out.  pfh_qc_phred_hint: 33, 64 or 0 from the smallest quality byte and the number of reads that held one. */
+void pfh_reads_report(const char *path);
+int pfh_qc_fastq(const char *const *inputs1, uint32_t n1, const char *const *inputs2, uint32_t n2, const char *report_path, uint32_t phred, uint64_t chunk_bytes,
+                 int device);
+int pfh_qc_fastq_chunk(const char *text, uint64_t n, int final, uint32_t phred, uint32_t file_side, int trimmed, const pf_trim_step *steps, uint32_t n_steps,
+                       int clip_open, const char *bases, const uint32_t *adapter_off, const uint8_t *side, uint32_t n_adapters, uint32_t seed, uint32_t score,
+                       uint64_t *raw, uint64_t *kept, uint64_t *clip, uint64_t *bytes_used, uint64_t *n_records, uint64_t *bad_record);
+uint32_t pfh_qc_phred_hint(uint64_t min_byte, uint64_t reads);
+int pfh_qc_report_text(const uint64_t *tables, const uint64_t *clip, uint32_t phred, char *out, uint64_t cap, uint64_t *len);
 /* ---- raw reads to ploidy estimate in one process: step `1.trim` inside `run` / `run-multi` (K-TRIMCOUNT, pf_*_trimmed in ploidyfrost_hip.h) ----
  * The rule: csrc/pf_trimrun_rule.hpp.  pfh_run_fastq_trimmed: pfh_run_fastq on the raw reads -- both passes stream them and trim them on
  * the device on the way in, no trimmed file is written.  paired = 0: what `trim -i inputs... -o t.fq STEP...` followed by

@@ -437,6 +437,76 @@ int pfh_clip_pair(const char *seq1, const char *qual1, uint64_t n1, const char *
     return 0;
 }
 
+// ---- the read quality report (K-QC) --------------------------------------------------------------------
+// `--report`: the switch of the next trim / run call of this thread
+static thread_local std::string g_reads_report;
+void pfh_reads_report(const char *path) { g_reads_report = path ? path : ""; }
+static std::string take_reads_report() {
+    std::string r;
+    r.swap(g_reads_report);
+    return r;
+}
+int pfh_qc_fastq(const char *const *inputs1, uint32_t n1, const char *const *inputs2, uint32_t n2, const char *report_path, uint32_t phred, uint64_t chunk_bytes,
+                 int device) {
+    const int gz = take_reads_gz();
+    if ((n1 && !inputs1) || (n2 && !inputs2)) { g_open_err = "pfh_qc_fastq: inputs are needed"; return 1; }
+    try {
+        std::vector<std::string> in1, in2;
+        for (uint32_t i = 0; i < n1; ++i) in1.push_back(inputs1[i] ? inputs1[i] : "");
+        for (uint32_t i = 0; i < n2; ++i) in2.push_back(inputs2[i] ? inputs2[i] : "");
+        pfh::QcOptions opt;
+        opt.phred = phred;
+        opt.gz = gz;
+        opt.chunk_bytes = chunk_bytes;
+        pfh::QcReport rep;
+        return pfh::qc_fastq(in1, in2, report_path ? report_path : "", opt, device, rep, g_open_err);
+    } catch (const std::exception &e) {
+        g_open_err = std::string("ploidyfrost host layer: ") + e.what();
+        return 1;
+    }
+}
+int pfh_qc_fastq_chunk(const char *text, uint64_t n, int final, uint32_t phred, uint32_t file_side, int trimmed, const pf_trim_step *steps, uint32_t n_steps,
+                       int clip_open, const char *bases, const uint32_t *adapter_off, const uint8_t *side, uint32_t n_adapters, uint32_t seed, uint32_t score,
+                       uint64_t *raw, uint64_t *kept, uint64_t *clip, uint64_t *bytes_used, uint64_t *n_records, uint64_t *bad_record) {
+    auto refuse = [&](const std::string &m) { g_open_err = "pfh_qc_fastq_chunk: " + m; return -1; };
+    if (!raw || (trimmed && !kept) || (trimmed && clip_open && !clip)) return refuse("the tables are needed");
+    if (n && !text) return refuse("text is needed");
+    if (file_side != 1 && file_side != 2) return refuse("the side of a file is 1 or 2");
+    if (phred != 33 && phred != 64) return refuse(std::string(pf_trim::refusal_text(pf_trim::REFUSE_PHRED)) + ", not " + std::to_string(phred));
+    pf_qc::ClipSet cs;
+    if (trimmed) {
+        uint32_t bad = 0;
+        const int c = pf_trim::steps_clause(reinterpret_cast<const pf_trim::Step *>(steps), n_steps, phred, &bad);
+        if (c && !(c == pf_trim::REFUSE_NO_STEP && clip_open && n_steps == 0)) return refuse(pf_trim::refusal_text(c));
+        if (clip_open) {
+            const int cc = pf_clip::set_clause(bases, adapter_off, side, n_adapters, seed, score, &bad);
+            if (cc) return refuse(pf_clip::refusal_text(cc));
+            cs.open = true;
+            cs.bases = bases;
+            cs.off = adapter_off;
+            cs.side = side;
+            cs.n_adapters = n_adapters;
+            cs.seed = seed;
+            cs.score = score;
+        }
+    }
+    uint64_t used = 0, recs = 0, bad_rec = 0;
+    const int clause = pf_qc::qc_fastq_chunk(text ? text : "", n, final != 0, phred, file_side, trimmed != 0, reinterpret_cast<const pf_trim::Step *>(steps), n_steps, cs,
+                                             raw, kept, clip, used, recs, bad_rec);
+    if (bytes_used) *bytes_used = used;
+    if (n_records) *n_records = recs;
+    if (bad_record) *bad_record = bad_rec;
+    return clause;
+}
+uint32_t pfh_qc_phred_hint(uint64_t min_byte, uint64_t reads) { return pf_qc::phred_hint(min_byte, reads); }
+int pfh_qc_report_text(const uint64_t *tables, const uint64_t *clip, uint32_t phred, char *out, uint64_t cap, uint64_t *len) {
+    if (!tables || !len) { g_open_err = "pfh_qc_report_text: tables and len are needed"; return -1; }
+    const std::string t = pf_qc::report_text(tables, clip, phred);
+    *len = t.size();
+    if (out) memcpy(out, t.data(), std::min<uint64_t>(cap, t.size()));
+    return 0;
+}
+
 // ---- reads quality-trimmed (K-TRIM) ------------------------------------------------------------------
 static pfh::TrimOptions trim_options(const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, const char *trimlog, uint64_t chunk_bytes) {
     pfh::TrimOptions opt;
@@ -453,6 +523,7 @@ static pfh::TrimOptions trim_stream_options(const pf_trim_step *steps, uint32_t 
                                             const pfh::ClipOptions &clip) {
     pfh::TrimOptions opt = trim_options(steps, n_steps, phred, trimlog, chunk_bytes);
     opt.clip = clip;
+    opt.report = take_reads_report();
     return opt;
 }
 int pfh_trim_fastq(const char *const *inputs, uint32_t n_inputs, const char *out_path, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred,
@@ -784,6 +855,7 @@ static int run_fastq_c(const char *who, const char *const *inputs, uint32_t n_in
             opt.call.model.source = o->model_source;
         }
         trim_inputs_from(steps, n_steps, phred, clip, opt.trim);
+        opt.report = take_reads_report();
         opt.paired = paired != 0;
         pfh::RunStats st;
         const int rc = pfh::run_fastq(in, out_prefix, opt, device, st, nullptr, g_open_err);
@@ -812,6 +884,7 @@ static int run_multi_fastq_c(const char *who, const char *const *names, const ui
                              const pfh_run_options *o, const pf_filter_multi_opts *multi, int each_color, int device, pfh_run_multi_stats *stats,
                              uint64_t *per_color, pf_trim_stats *per_input) {
     const pfh::ClipOptions clip = take_reads_adapters();   // taken first: a refusal below does not leave the switch to the next call
+    if (!take_reads_report().empty()) { g_open_err = "run-multi: --report is not built into run-multi (`trim --report` or `run --report` per sample)"; return 1; }
     if (!out_prefix || !o || (n_samples && (!names || !n_inputs_of))) { g_open_err = std::string(who) + ": samples, output prefix and options are needed"; return 1; }
     try {
         std::vector<pfh::MultiSample> samples(n_samples);

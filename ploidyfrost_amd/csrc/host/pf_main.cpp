@@ -104,7 +104,11 @@ void PrintUsage() {
          << "                  [--adapters <adapters.fa> [--adapter-seed 0..8] [--adapter-score 1..1000]] on trim, run STEP... and run-multi STEP...: adapter read-through is" << endl
          << "                  clipped on the device before the steps (ILLUMINACLIP's simple mode; no STEP is needed beside --adapters, also with -1 / -2)" << endl
          << "                  [--adapter-pairs [--adapter-pair-score 1..1000] [--adapter-pair-min 1..16] [--adapter-keep-both]] with -1 / -2: ILLUMINACLIP's palindrome mode" << endl
-         << "                  from the Prefix<X>/1 and Prefix<X>/2 entries of the adapter file; the reverse read of a clipped pair is dropped unless --adapter-keep-both" << endl << endl
+         << "                  from the Prefix<X>/1 and Prefix<X>/2 entries of the adapter file; the reverse read of a clipped pair is dropped unless --adapter-keep-both" << endl
+         << "                  [--report <report.tsv>] on trim and on run STEP... / run --adapters: the read quality report of the reads as they come and as they are kept" << endl
+         << "Usage: PloidyFrost qc (-i <a.fq> [-i <b.fq> ...] | -1 <r1.fq> [-1 ...] -2 <r2.fq> [-2 ...]) -o <report.tsv> [--phred 33|64] [--gz | --gz-plain] [--chunk-bytes N] [-v]" << endl
+         << "                  (quality and base content by cycle, read lengths, quality and GC histograms and a hint about the quality offset, accumulated on" << endl
+         << "                  the device; one tab-separated text file)" << endl << endl
          << "Usage: PloidyFrost build -k 25 [-i] [-d] -r <reads.fq> [-r <more.fq> ...] -o <sample> [-g G] [-t N] [--chunk-bytes N] [--initial-slots N] [-v]" << endl
          << "                  (`Bifrost build -r` on the device: <sample>.gfa, the compacted de Bruijn graph of the reads; -i clips tips, -d deletes" << endl
          << "                  isolated unitigs, both of fewer than k k-mers; single-sample graphs from FASTQ only)" << endl
@@ -868,6 +872,51 @@ struct ClipCli {
     }
 };
 
+// `qc`: what FastQC is looked at for before the steps of `trim` are chosen -- quality and base content by cycle, read lengths, the
+// quality offset -- from the device, as one tab-separated report (../pf_qc_rule.hpp)
+int qc_main(int argc, char **argv) {
+    const char *usage = "Usage:PloidyFrost qc (-i a.fq [-i b.fq ...] | -1 r1.fq [-1 ...] -2 r2.fq [-2 ...]) -o report.tsv [--phred 33|64] [--gz | --gz-plain] [--chunk-bytes N] [-v]";
+    vector<string> inputs, in1, in2;
+    string out;
+    pfh::QcOptions opt;
+    bool verbose = false;
+    auto refuse = [&](const string &why) { cerr << "Error: qc: " << why << endl << usage << endl; return 1; };
+    for (int i = 2; i < argc; ++i) {
+        const string a = argv[i];
+        if (a == "-v") { verbose = true; continue; }
+        if (a == "--gz") { opt.gz = std::max(opt.gz, 1); continue; }
+        if (a == "--gz-plain") { opt.gz = 2; continue; }
+        if (a == "--fasta") return refuse("--fasta does not go with qc: FASTA has no qualities to report");
+        const bool known = a == "-i" || a == "-1" || a == "-2" || a == "-o" || a == "--phred" || a == "--chunk-bytes";
+        if (!known) return refuse("unknown option " + a);
+        if (i + 1 >= argc) return refuse(a + " needs a value");
+        const string v = argv[++i];
+        if (a == "-i") inputs.push_back(v);
+        else if (a == "-1") in1.push_back(v);
+        else if (a == "-2") in2.push_back(v);
+        else if (a == "-o") out = v;
+        else if (a == "--phred") {
+            if (v != "33" && v != "64") return refuse("--phred takes 33 or 64, not '" + v + "'");
+            opt.phred = (uint32_t)stoi(v);
+        } else {
+            char *end = nullptr;
+            errno = 0;
+            opt.chunk_bytes = strtoull(v.c_str(), &end, 10);
+            if (errno || !isdigit((unsigned char)v[0]) || *end || !opt.chunk_bytes) return refuse("--chunk-bytes takes a positive number, not '" + v + "'");
+        }
+    }
+    // refused by name, before anything is read or written
+    if (!inputs.empty() && (!in1.empty() || !in2.empty())) return refuse("-i does not go with -1 / -2 (the inputs are either single-ended or the two sides of pairs)");
+    if (inputs.empty() && in1.empty() && in2.empty()) return refuse("-i <reads.fq> is missing (or -1 <r1.fq> -2 <r2.fq>)");
+    if (out.empty()) return refuse("-o <report.tsv> is missing");
+    pfh::QcReport rep;
+    string err;
+    if (pfh::qc_fastq(inputs.empty() ? in1 : inputs, in2, out, opt, 0, rep, err)) { cerr << "Error: " << err << endl; return 1; }
+    for (const string &l : rep.lines()) cerr << l << endl;
+    if (verbose) cerr << "qc: report " << rep.text().size() << " bytes, phred " << rep.phred << " hint " << pf_qc::hint_of(rep.tables.data()) << endl;
+    return 0;
+}
+
 // `trim`: step 1 of the reference's workflow (`trimmomatic PE -phred33 r1 r2 trim1 u1 trim2 u2 LEADING:10 TRAILING:10 SLIDINGWINDOW:3:20
 // MINLEN:50`) on the device; the steps are Trimmomatic's words as positional arguments
 int trim_main(int argc, char **argv) {
@@ -875,7 +924,8 @@ int trim_main(int argc, char **argv) {
                         "      PloidyFrost trim -1 r1.fq -2 r2.fq -o1 p1.fq -u1 u1.fq -o2 p2.fq -u2 u2.fq STEP... [the same options]\n"
                         "      STEP: LEADING:t TRAILING:t SLIDINGWINDOW:w:t MINLEN:l\n"
                         "      [--adapters adapters.fa [--adapter-seed 0..8] [--adapter-score 1..1000]]: adapters are clipped first; no STEP is needed beside them\n"
-                        "      [--adapter-pairs [--adapter-pair-score 1..1000] [--adapter-pair-min 1..16] [--adapter-keep-both]] with -1 / -2: palindrome mode from the file's Prefix pairs";
+                        "      [--adapter-pairs [--adapter-pair-score 1..1000] [--adapter-pair-min 1..16] [--adapter-keep-both]] with -1 / -2: palindrome mode from the file's Prefix pairs\n"
+                        "      [--report report.tsv]: the read quality report of the reads as they come (raw) and as they are written (kept), as `qc` words it";
     vector<string> inputs, words;
     string out, in_pair[2], out_pair[4];
     pfh::TrimOptions opt;
@@ -897,7 +947,7 @@ int trim_main(int argc, char **argv) {
             if (taken < 0) return refuse(why);
             if (taken) continue;
         }
-        const bool known = a == "-i" || a == "-o" || a == "--phred" || a == "--trimlog" || a == "--chunk-bytes" ||
+        const bool known = a == "-i" || a == "-o" || a == "--phred" || a == "--trimlog" || a == "--chunk-bytes" || a == "--report" ||
                            std::find_if(pair_opts, pair_opts + 6, [&](const char *o) { return a == o; }) != pair_opts + 6;
         if (!known) return refuse("unknown option " + a);
         if (i + 1 >= argc) return refuse(a + " needs a value");
@@ -905,6 +955,7 @@ int trim_main(int argc, char **argv) {
         if (a == "-i") inputs.push_back(v);
         else if (a == "-o") out = v;
         else if (a == "--trimlog") opt.trimlog = v;
+        else if (a == "--report") { if (v.empty()) return refuse("--report needs a value"); opt.report = v; }
         else if (a == "--phred") {
             if (v != "33" && v != "64") return refuse("--phred takes 33 or 64, not '" + v + "'");
             opt.phred = (uint32_t)stoi(v);
@@ -939,24 +990,26 @@ int trim_main(int argc, char **argv) {
     pf_trim_stats st[2] = {};
     pfh::TrimTimes tm;
     pfh::ClipReport clip;
+    pfh::QcReport qc;
     string err;
     if (pair_in) {
         for (int j = 0; j < 2; ++j)
             if (in_pair[j].empty()) return refuse(string(pair_opts[j]) + " <r" + to_string(j + 1) + ".fq> is missing");
         for (int j = 0; j < 4; ++j)
             if (out_pair[j].empty()) return refuse(string(pair_opts[2 + j]) + " <out.fq> is missing");
-        if (pfh::trim_fastq_pair(in_pair[0], in_pair[1], out_pair, opt, 0, st, &tm, err, &clip)) { cerr << "Error: " << err << endl; return 1; }
+        if (pfh::trim_fastq_pair(in_pair[0], in_pair[1], out_pair, opt, 0, st, &tm, err, &clip, &qc)) { cerr << "Error: " << err << endl; return 1; }
         if (opt.clip.on()) cerr << pfh::clip_line(clip) << endl;
         cerr << "trim: pairs " << st[0].reads << " both " << st[0].both << " forward_only " << st[0].only1 << " reverse_only " << st[0].only2 << " dropped "
              << st[0].neither << " bases " << st[0].bases + st[1].bases << " bases_kept " << st[0].bases_kept + st[1].bases_kept << endl;
     } else {
         if (inputs.empty()) return refuse("-i <reads.fq> is missing (or -1 <r1.fq> -2 <r2.fq> for a pair)");
         if (out.empty()) return refuse("-o <trimmed.fq> is missing");
-        if (pfh::trim_fastq(inputs, out, opt, 0, st[0], &tm, err, &clip)) { cerr << "Error: " << err << endl; return 1; }
+        if (pfh::trim_fastq(inputs, out, opt, 0, st[0], &tm, err, &clip, &qc)) { cerr << "Error: " << err << endl; return 1; }
         if (opt.clip.on()) cerr << pfh::clip_line(clip) << endl;
         cerr << "trim: reads " << st[0].reads << " kept " << st[0].kept << " dropped " << st[0].dropped << " bases " << st[0].bases << " bases_kept "
              << st[0].bases_kept << endl;
     }
+    for (const string &l : qc.lines()) cerr << l << endl;
     if (verbose) cerr << "trim: stream " << tm.stream_s << "s (device " << tm.device_s << "s, read " << tm.read_s << "s, write " << tm.write_s << "s)" << endl;
     return 0;
 }
@@ -1029,7 +1082,8 @@ int run_main(int argc, char **argv) {
                         "                 [--db-out <KMCDatabase>] [--gfa-out <sample>] [--chunk-bytes N] [--initial-slots N] [--gz] [--gz-plain] [--fasta] [-v]\n"
                         "      PloidyFrost run [the same options] -i raw.fq [-i more.fq ...] -o sample STEP... [--phred 33|64]\n"
                         "      PloidyFrost run [the same options] -1 r1.fq -2 r2.fq [-1 r3.fq -2 r4.fq ...] -o sample STEP... [--phred 33|64]\n"
-                        "      STEP: LEADING:t TRAILING:t SLIDINGWINDOW:w:t MINLEN:l (the raw reads are trimmed on the way in, as `trim` trims them)";
+                        "      STEP: LEADING:t TRAILING:t SLIDINGWINDOW:w:t MINLEN:l (the raw reads are trimmed on the way in, as `trim` trims them)\n"
+                        "      [--report report.tsv] with STEP... or --adapters: the read quality report `trim --report` writes for the same inputs";
     auto refuse = [&](const string &why) { cerr << "Error: run: " << why << endl << usage << endl; return 1; };
     Options lopt;   // the long options of the calling run
     DensityCli dc;
@@ -1094,12 +1148,13 @@ int run_main(int argc, char **argv) {
         if (a == "--keep-tips") { opt.clip_tips = false; continue; }
         if (a == "--keep-isolated") { opt.del_isolated = false; continue; }
         const bool takes_value = a == "-i" || a == "-o" || a == "-q" || a == "-u" || a == "-g" || a == "-z" || a == "-M" || a == "-D" || a == "-G" || a == "-t" ||
-                                 a == "--db-out" || a == "--gfa-out" || a == "--chunk-bytes" || a == "--initial-slots";
+                                 a == "--db-out" || a == "--gfa-out" || a == "--chunk-bytes" || a == "--initial-slots" || a == "--report";
         if (!takes_value) return refuse("unknown option " + a);
         if (i + 1 >= argc) return refuse(a + " needs a value");
         const char *val = argv[++i];
         uint64_t v = 0;
-        if (a == "-i") inputs.push_back(val);
+        if (a == "--report") { if (!*val) return refuse("--report needs a value"); opt.report = val; }
+        else if (a == "-i") inputs.push_back(val);
         else if (a == "-o") out = val;
         else if (a == "--db-out") opt.db_out = val;
         else if (a == "--gfa-out") opt.gfa_out = val;
@@ -1156,6 +1211,7 @@ int run_main(int argc, char **argv) {
         if (u < st.clip.size()) cerr << pfh::clip_line(st.clip[u]) << endl;
         cerr << pfh::trim_unit_line(&st.trim[opt.paired ? 2 * u : 0], opt.paired) << endl;
     }
+    for (const string &l : st.qc.lines()) cerr << l << endl;
     cerr << "run: reads " << st.counted.reads << " bases " << st.counted.bases << " kmers " << st.counted.kmers << " bad " << st.counted.kmers_bad << " distinct "
          << st.counted.unique << " lower " << st.lower << " upper " << st.upper << " windows_bad " << st.masked.kmers_bad << " windows_kept " << st.masked.kmers_kept
          << " distinct_kept " << st.distinct_kept << " unitigs " << st.graph.unitigs << " removed " << st.graph.removed << " unitigs_out " << st.graph.unitigs_out
@@ -1342,6 +1398,7 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[1], "build")) return build_main(argc, argv);
     if (!strcmp(argv[1], "build-multi")) return build_multi_main(argc, argv);
     if (!strcmp(argv[1], "trim")) return trim_main(argc, argv);
+    if (!strcmp(argv[1], "qc")) return qc_main(argc, argv);
     if (!strcmp(argv[1], "histogram")) {   // the file `kmc_tools transform <db> histogram <file>` writes, from the database on the device
         string db, out;
         for (int i = 2; i < argc; ++i) {

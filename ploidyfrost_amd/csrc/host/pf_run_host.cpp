@@ -215,6 +215,8 @@ int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<ReadsInput> &
 
 // ---- run ----
 std::string run_options_refusal(const RunOptions &opt) {
+    if (opt.fasta && !opt.report.empty()) return "--fasta does not go with --report (FASTA has no qualities to report)";
+    if (!opt.report.empty() && !opt.trim.on()) return "--report needs a step or --adapters in run: ploidyfrost qc reports on files as they are";
     if (opt.fasta && opt.trim.clip.on()) return "--fasta does not go with --adapters (FASTA has no qualities to score an adapter by)";
     if (opt.fasta && (opt.trim.on() || opt.paired)) return "--fasta does not go with trim steps or -1 / -2 (FASTA has no qualities to trim)";
     { const int c = count_options_clause(count_options_of(opt), true); if (c) return pf_count::cut_text(c); }
@@ -241,6 +243,12 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
     std::vector<std::string> outputs;
     if (!opt.db_out.empty()) { outputs.push_back(opt.db_out + ".kmc_pre"); outputs.push_back(opt.db_out + ".kmc_suf"); }
     if (!gfa_path.empty()) outputs.push_back(gfa_path);
+    const std::string report_tmp = opt.report + tail;
+    if (!opt.report.empty()) {
+        for (const std::string &o : outputs)
+            if (same_file(o, opt.report)) { err = "run: two outputs have the same path (" + opt.report + ")"; return 1; }
+        outputs.push_back(opt.report);
+    }
     std::vector<ReadsInput> reads;   // what each input is: decided here, once, for both passes
     if (fastq_preflight("run", "read", inputs, outputs, ReadsOptions{opt.gz, opt.fasta}, reads, err)) return 1;
     pf_clip::Adapters adapters;   // --adapters: read and refused here, before a device context exists
@@ -253,11 +261,12 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
     }
     // (the context goes to the loader of the calling run in the end: destroyed here only on the way out before that)
     CtxGuard ctx_guard{ctx};
-    bool db_written = false, gfa_tmp_written = false;
+    bool db_written = false, gfa_tmp_written = false, report_tmp_written = false;
     auto fail = [&](const std::string &m) {   // nothing is left under any output name after a refusal
         err = m;
         if (db_written) { unlink((opt.db_out + ".kmc_pre").c_str()); unlink((opt.db_out + ".kmc_suf").c_str()); }
         if (gfa_tmp_written) unlink(gfa_tmp.c_str());
+        if (report_tmp_written) unlink(report_tmp.c_str());
         return 1;
     };
     auto dev_fail = [&]() { return fail(std::string("run: ") + pf_last_error(ctx)); };
@@ -266,6 +275,7 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
         if (clip_open(ctx, adapters, opt.trim.clip) != PF_OK) return dev_fail();
         unit_clip.assign(trim_unit_count(inputs.size(), opt.paired), ClipCounts{});
     }
+    if (!opt.report.empty() && qc_open(ctx, opt.trim.phred, "run", err)) return 1;   // open over the first pass alone
 
     // ---- count: every k-mer of the reads, both strands, the user's cut-offs ----
     std::vector<uint64_t> rows;
@@ -279,6 +289,15 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
                        }, db, stats.counted, ctm, err)
                      : count_stream(ctx, "run", reads, copt, db, stats.counted, ctm, err))
             return 1;
+        if (!opt.report.empty()) {   // closed before the second pass streams the same records again
+            if (qc_close(ctx, opt.trim.phred, opt.trim.clip.on(), "run", stats.qc, err)) return fail(err);
+            const std::string text = stats.qc.text();
+            const int fd = open(report_tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+            if (fd < 0) return fail("run: cannot write " + report_tmp + " (" + strerror(errno) + ")");
+            report_tmp_written = true;
+            if (!write_all(fd, text.data(), text.size())) { const int e = errno; close(fd); return fail("run: writing " + report_tmp + " (" + strerror(e) + ")"); }
+            if (close(fd) != 0) return fail("run: closing " + report_tmp + " (" + strerror(errno) + ")");
+        }
         struct Free { pf_ctx *c; Counted &d; ~Free() { pf_device_free(c, d.kmers); pf_device_free(c, d.counts); } } free_db{ctx, db};
         tm.count_s = ctm.stream_s;
         tm.finish_s = ctm.finish_s;
@@ -398,6 +417,8 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
     tm.call_s = since(t_call);
     if (!gfa_path.empty() && rename(gfa_tmp.c_str(), gfa_path.c_str()) != 0)
         return fail("run: renaming " + gfa_tmp + " to " + gfa_path + " (" + strerror(errno) + ")");
+    if (!opt.report.empty() && rename(report_tmp.c_str(), opt.report.c_str()) != 0)
+        return fail("run: renaming " + report_tmp + " to " + opt.report + " (" + strerror(errno) + ")");
     fflush(stdout);
     if (times) *times = tm;
     return 0;

@@ -22,6 +22,7 @@
 #include "pf_cdbg.hpp"
 #include "pf_count_host.hpp"
 #include "pf_clip_host.hpp"
+#include "pf_qc_host.hpp"
 #include "ploidyfrost_hip.h"
 
 namespace pfh {
@@ -112,6 +113,7 @@ struct RunOptions {
     TrimInputs trim;
     bool paired = false;
     int gz = 0;        // --gz (1), --gz-plain (2: any gzip, K-GUNZIP): inputs with the gzip magic are blocked gzip, inflated on the device in both passes (pf_gz_host.hpp)
+    std::string report;   // --report (with opt.trim alone): K-QC's report of both stages over the first pass, the one `trim --report` writes for the same inputs
     bool fasta = false;   // --fasta: a chunk whose first byte is '>' goes through pf_count_fasta / pf_maskcount_fasta in the two passes (K-FASTA); not with trim steps
 };
 struct RunStats {
@@ -123,6 +125,7 @@ struct RunStats {
     std::string model_last_line;       // with a model: what the calling run prints last
     std::vector<pf_trim_stats> trim;   // STEP...: the trimming of the first pass (paired: one entry per input file, else one entry)
     std::vector<ClipReport> clip;      // --adapters: the clipping of the first pass, one entry per unit
+    QcReport qc;                       // --report: the tables of the first pass
 };
 struct RunTimes {
     double count_s = 0, finish_s = 0, table_s = 0, db_out_s = 0, recount_s = 0, refinish_s = 0, graph_s = 0, gfa_out_s = 0, load_s = 0, call_s = 0;

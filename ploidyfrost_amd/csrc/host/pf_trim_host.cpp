@@ -53,6 +53,17 @@ int trim_clip_open(pf_ctx *ctx, const TrimOptions &opt, const pf_clip::Adapters 
     err = std::string("trim: ") + pf_last_error(ctx);
     return 1;
 }
+// --report: the report opened on the fresh context; closed, worded and written into its output file when the stream has ended
+int trim_qc_open(pf_ctx *ctx, const TrimOptions &opt, std::string &err) { return opt.report.empty() ? 0 : qc_open(ctx, opt.phred, "trim", err); }
+int trim_qc_write(pf_ctx *ctx, const TrimOptions &opt, const OutFiles::File &f, QcReport *qc, std::string &err) {
+    if (opt.report.empty()) return 0;
+    QcReport r;
+    if (qc_close(ctx, opt.phred, opt.clip.on(), "trim", r, err)) return 1;
+    const std::string text = r.text();
+    if (!write_all(f.fd, text.data(), text.size(), "trim", f.tmp, err)) return 1;
+    if (qc) *qc = std::move(r);
+    return 0;
+}
 int trim_clip_report(pf_ctx *ctx, const TrimOptions &opt, const pf_clip::Adapters &adapters, ClipReport *clip, std::string &err) {
     if (!opt.clip.on() || !clip || clip_report(ctx, adapters, opt.clip, *clip) == PF_OK) return 0;
     err = std::string("trim: ") + pf_last_error(ctx);
@@ -78,20 +89,21 @@ int trim_options_clause(const TrimOptions &opt, std::string &err) {
 }
 
 int trim_fastq(const std::vector<std::string> &inputs, const std::string &out_path, const TrimOptions &opt, int device, pf_trim_stats &stats,
-               TrimTimes *times, std::string &err, ClipReport *clip) {
+               TrimTimes *times, std::string &err, ClipReport *clip, QcReport *qc) {
     stats = pf_trim_stats{};
     err.clear();
     if (opt.clip.on() && opt.clip.pairs) { err = "trim: --adapter-pairs needs -1 / -2"; return 1; }
     const bool logs = !opt.trimlog.empty();
     std::vector<std::string> paths = {out_path};
     if (logs) paths.push_back(opt.trimlog);
+    if (!opt.report.empty()) paths.push_back(opt.report);   // (the last output)
     std::vector<ReadsInput> reads;
     pf_clip::Adapters adapters;
     if (trim_preflight(inputs, paths, opt, reads, adapters, err)) return 1;
     pf_ctx *ctx = nullptr;
     if (trim_create(device, &ctx, err)) return 1;
     CtxGuard ctx_guard{ctx};
-    if (trim_clip_open(ctx, opt, adapters, err)) return 1;
+    if (trim_clip_open(ctx, opt, adapters, err) || trim_qc_open(ctx, opt, err)) return 1;
     const auto t_stream = clk::now();
     OutFiles outs("trim");
     if (outs.open_all(paths, err)) return 1;
@@ -143,6 +155,7 @@ int trim_fastq(const std::vector<std::string> &inputs, const std::string &out_pa
     }
     if (err.empty()) err = log_err;
     if (err.empty()) trim_clip_report(ctx, opt, adapters, clip, err);
+    if (err.empty()) trim_qc_write(ctx, opt, outs.f.back(), qc, err);
     if (!err.empty() || outs.commit(err)) return 1;
     if (times) {
         times->stream_s = since(t_stream);
@@ -154,13 +167,14 @@ int trim_fastq(const std::vector<std::string> &inputs, const std::string &out_pa
 }
 
 int trim_fastq_pair(const std::string &in1, const std::string &in2, const std::string out_paths[4], const TrimOptions &opt, int device,
-                    pf_trim_stats stats[2], TrimTimes *times, std::string &err, ClipReport *clip) {
+                    pf_trim_stats stats[2], TrimTimes *times, std::string &err, ClipReport *clip, QcReport *qc) {
     stats[0] = stats[1] = pf_trim_stats{};
     err.clear();
     const bool logs = !opt.trimlog.empty();
     const std::vector<std::string> inputs = {in1, in2};
     std::vector<std::string> paths(out_paths, out_paths + 4);
     if (logs) paths.push_back(opt.trimlog);
+    if (!opt.report.empty()) paths.push_back(opt.report);   // (the last output)
     std::vector<ReadsInput> reads;
     pf_clip::Adapters adapters;
     if (trim_preflight(inputs, paths, opt, reads, adapters, err)) return 1;
@@ -168,7 +182,7 @@ int trim_fastq_pair(const std::string &in1, const std::string &in2, const std::s
     pf_ctx *ctx = nullptr;
     if (trim_create(device, &ctx, err)) return 1;
     CtxGuard ctx_guard{ctx};
-    if (trim_clip_open(ctx, opt, adapters, err)) return 1;
+    if (trim_clip_open(ctx, opt, adapters, err) || trim_qc_open(ctx, opt, err)) return 1;
     const auto t_stream = clk::now();
     OutFiles outs("trim");
     if (outs.open_all(paths, err)) return 1;
@@ -248,6 +262,7 @@ int trim_fastq_pair(const std::string &in1, const std::string &in2, const std::s
     }
     for (int d = 0; d < 4 && err.empty(); ++d) err = opt.gz_out ? gzo[d]->wr.err : wr[d].err;
     if (err.empty()) trim_clip_report(ctx, opt, adapters, clip, err);
+    if (err.empty()) trim_qc_write(ctx, opt, outs.f.back(), qc, err);
     if (!err.empty() || outs.commit(err)) return 1;
     if (times) {
         times->stream_s = since(t_stream);

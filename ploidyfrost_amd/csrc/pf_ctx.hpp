@@ -124,6 +124,7 @@ struct pf_ctx {
     void *gfa = nullptr;   // K-GFA (pf_gfa.hip): segment table of the last pf_gfa_ingest until pf_gfa_segments fetches it
     void *count = nullptr; // K-COUNT (pf_count.hip): the table of an open count, pf_count_begin .. pf_count_finish / pf_count_abort
     void *clip = nullptr;  // K-CLIP (pf_clip.hip): the adapters and counters of an open clip, pf_clip_begin .. pf_clip_end
+    void *qc = nullptr;    // K-QC (pf_qc.hip): the tables of an open report, pf_qc_begin .. pf_qc_end
     void *unitig = nullptr; // K-UNITIG (pf_unitig.hip): the text of a built graph, pf_unitig_build .. pf_unitig_release
     void *comm = nullptr;  // pf_gather.hip: this rank's RCCL communicator and its two small device buffers
     const void *cc_rec = nullptr;
@@ -228,6 +229,7 @@ void comm_destroy(pf_ctx *ctx);     // pf_gather.hip
 void count_destroy(pf_ctx *ctx);    // pf_count.hip
 void unitig_destroy(pf_ctx *ctx);   // pf_unitig.hip
 void clip_destroy(pf_ctx *ctx);     // pf_clip.hip
+void qc_destroy(pf_ctx *ctx);       // pf_qc.hip
 void call_invalidate(pf_ctx *ctx);  // graph or count table replaced
 int call_state_arrays(pf_ctx *ctx, uint8_t **flags, uint32_t **plus, uint32_t **minus);   // pf_call.hip: T1 state arrays for a device-side writer
 void call_state_resident(pf_ctx *ctx);

@@ -11,6 +11,7 @@
 //              A read of up to 256 - 15 bytes is staged once for all steps; a longer one loops, each step over the row steps that
 //              its [b, e) touches, forwards or backwards, and stops at the first hit.  Output: (begin, len) per record, len 0 = dropped.
 //              With a clip open (pf_clip_begin), K-CLIP (pf_clip.hip) runs first and the interval starts as [0, clip end).
+//              With a report open (pf_qc_begin), K-QC (pf_qc.hip) follows and adds both stages to its tables.
 //   sizes      k_trim_sizes, one thread a record: output bytes per destination (1 single-ended, 4 for a pair: o1 u1 o2 u2), the pair
 //              statistics.
 //   offsets    scan_exclusive_u32_u64 over the destinations laid end to end.
@@ -27,6 +28,7 @@
 #include "../../include/ploidyfrost_hip.h"
 #include "pf_clip_dev.hpp"
 #include "pf_ctx.hpp"
+#include "pf_qc_dev.hpp"
 #include "pf_reads_dev.hpp"
 #include "pf_scan.hpp"
 #include "pf_trim_dev.hpp"
@@ -84,21 +86,6 @@ struct TrimCopyArgs {
     uint64_t n_rec;
     int n_files;
 };
-// the 16 bytes of the text from byte s: one aligned unit, or two and a shift
-__device__ inline uint4 trim_load_shifted(const char *__restrict__ text, uint64_t n, uint64_t s) {
-    const uint4 lo = mask_load_unit(text, n, s >> 4);
-    const uint32_t sh = (uint32_t)(s & 15);
-    if (sh == 0) return lo;
-    const uint4 hi = mask_load_unit(text, n, (s >> 4) + 1);
-    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    const uint32_t d = sh >> 2, bits = (sh & 3) * 8;
-    uint32_t t[5], o[4];
-#pragma unroll
-    for (int i = 0; i < 5; ++i) t[i] = d == 0 ? w[i] : d == 1 ? w[i + 1] : d == 2 ? w[i + 2] : w[i + 3];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = (uint32_t)(((((uint64_t)t[i + 1]) << 32) | t[i]) >> bits);
-    return make_uint4(o[0], o[1], o[2], o[3]);
-}
 // one piece by a row: text[src, src + len) to out[dst ..), then '\n'
 __device__ inline void trim_row_copy(const char *__restrict__ text, uint64_t n_text, uint64_t src, uint32_t len, char *__restrict__ out, uint64_t dst,
                                      int rl) {
@@ -215,6 +202,11 @@ static int trim_core(pf_ctx *ctx, const char *who_c, int n_files, const char *co
     for (int f = 0; f < n_files; ++f)
         k_trim_intervals<<<ctx_grid(ctx, n * TRIM_ROW, TRIM_BLOCK, 8), TRIM_BLOCK, 0, ctx->stream>>>(dt[f], n_bytes[f], ix[f].lines, n, ts, d_begin[f],
                                                                                                      d_len[f], dc + f, d_clip[f]);
+    if (qc_is_open(ctx)) {   // K-QC: both stages from what is on the device now -- the index, the final intervals, the clip ends
+        const uint32_t *qc_lines[2] = {ix[0].lines, ix[1].lines};
+        const int rc = qc_launch(ctx, n_files, 0, dt, n_bytes, qc_lines, n, d_begin, d_len, clip ? d_clip : nullptr);
+        if (rc) return rc;
+    }
     k_trim_sizes<<<ctx_grid(ctx, n, TRIM_BLOCK, 8), TRIM_BLOCK, 0, ctx->stream>>>(ix[0].lines, d_len[0], n_files == 2 ? ix[1].lines : nullptr,
                                                                                   n_files == 2 ? d_len[1] : nullptr, n, d_size, dc);
     PF_HIP(scan_exclusive_u32_u64(d_size, d_offs, n_size, scratch, ctx->stream));

@@ -52,6 +52,22 @@ __device__ inline void row_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
+// the 16 bytes of the text from byte s: one aligned unit, or two and a shift (K-TRIM's copy, K-QC's reads)
+__device__ inline uint4 trim_load_shifted(const char *__restrict__ text, uint64_t n, uint64_t s) {
+    const uint4 lo = mask_load_unit(text, n, s >> 4);
+    const uint32_t sh = (uint32_t)(s & 15);
+    if (sh == 0) return lo;
+    const uint4 hi = mask_load_unit(text, n, (s >> 4) + 1);
+    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    const uint32_t d = sh >> 2, bits = (sh & 3) * 8;
+    uint32_t t[5], o[4];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) t[i] = d == 0 ? w[i] : d == 1 ? w[i + 1] : d == 2 ? w[i + 2] : w[i + 3];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = (uint32_t)(((((uint64_t)t[i + 1]) << 32) | t[i]) >> bits);
+    return make_uint4(o[0], o[1], o[2], o[3]);
+}
+
 // ---- intervals ----
 [[maybe_unused]] static __global__ __launch_bounds__(TRIM_BLOCK) void k_trim_intervals(const char *__restrict__ text, uint64_t n_bytes, const uint32_t *__restrict__ lines,
                                                                uint64_t n_rec, const TrimSteps ts, uint32_t *__restrict__ rec_begin,

@@ -5,6 +5,7 @@
 //   index      fastq_index of pf_reads_dev.hpp, asked for the extents of all four lines of a record (K-TRIM's).
 //   intervals  k_trim_intervals of pf_trim_dev.hpp, the kernel of K-TRIM itself: (begin, len) per record, len 0 = dropped.
 //              With a clip open, K-CLIP (pf_clip.hip) runs first and the interval starts as [0, clip end).
+//              With a report open, K-QC (pf_qc.hip) follows and adds both stages to its tables.
 //   table      k_trimcount_keep, one thread a record: (begin, len) of file 1 (and of file 2), the hand-on predicate
 //              (pf_trimrun::handed_on: kept, and for a pair kept in both files), a keep flag of 4 bytes, the pair statistics.  One
 //              exclusive scan of the flags (pf_scan.hpp).  k_trimcount_scatter, one thread a record: (seq_begin + b, e - b) per file to
@@ -31,6 +32,7 @@
 #include "pf_clip_dev.hpp"
 #include "pf_count_dev.hpp"
 #include "pf_ctx.hpp"
+#include "pf_qc_dev.hpp"
 #include "pf_reads_dev.hpp"
 #include "pf_scan.hpp"
 #include "pf_trim_dev.hpp"
@@ -169,6 +171,11 @@ static int trim_table_core(pf_ctx *ctx, const std::string &who, int n_files, con
     for (int f = 0; f < n_files; ++f)
         k_trim_intervals<<<ctx_grid(ctx, n * TRIM_ROW, TRIM_BLOCK, 8), TRIM_BLOCK, 0, ctx->stream>>>(T.text[f], n_bytes[f], ix[f].lines, n, ts, d_begin[f],
                                                                                                      d_len[f], dc + f, d_clip[f]);
+    if (qc_is_open(ctx)) {   // K-QC: both stages from what is on the device now -- the index, the final intervals, the clip ends
+        const uint32_t *qc_lines[2] = {ix[0].lines, ix[1].lines};
+        const int rc = qc_launch(ctx, n_files, 0, T.text, n_bytes, qc_lines, n, d_begin, d_len, clip ? d_clip : nullptr);
+        if (rc) return rc;
+    }
     k_trimcount_keep<<<ctx_grid(ctx, n, TRIM_BLOCK, 8), TRIM_BLOCK, 0, ctx->stream>>>(d_len[0], n_files == 2 ? d_len[1] : nullptr, n, d_keep, dc);
     PF_HIP(scan_exclusive_u32(d_keep, d_pos, n + 1, scratch, ctx->stream));
     TrimScatterArgs sa = {};

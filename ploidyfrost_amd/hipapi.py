@@ -46,6 +46,8 @@ K_FASTA = K_GUNZIP + 1         # PF_K_FASTA ("k_fasta"): everything the index of
 K_DEFLATE = K_FASTA + 1        # PF_K_DEFLATE ("k_deflate"): everything one pf_deflate_bgzf launches; unit: bytes of text
 K_CLIP = K_DEFLATE + 1         # PF_K_CLIP ("k_clip"): the clipping kernels of one trim / trimmed-count call while a clip is open; unit: records
 K_PALIN = K_CLIP + 1           # PF_K_PALIN ("k_palin"): palindrome mode's kernel of one paired trim / trimmed-count call while a clip with prefix pairs is open; unit: pairs
+K_QC = K_PALIN + 1             # PF_K_QC ("k_qc"): the report kernel of one qc_fastq call, or of one trim / trimmed-count call per file while a report is open; unit: records
+QC_TABLE_WORDS, QC_CLIP_WORDS = 9515, 1025   # PF_QC_TABLE_WORDS, PF_QC_CLIP_WORDS
 CLIP_PAIR_STATS = np.dtype([("pairs_clipped", "<u8"), ("pairs_dropped", "<u8"), ("pairs_too_long", "<u8"), ("candidates_scored", "<u8"),
                             ("bases_clipped", "<u8", (2,))])   # pf_clip_pair_stats
 CLIP_STATS = np.dtype([(f, "<u8", (2,)) for f in ("reads_clipped", "reads_dropped", "bases_clipped", "candidates_scored")])   # pf_clip_stats
@@ -287,6 +289,11 @@ def load_library() -> C.CDLL:
         "pf_clip_stats_get": (i, [vp, vp]),
         "pf_clip_end": (i, [vp]),
         "pf_clip_last_ends": (i, [vp, i, vp, u64]),
+        "pf_qc_begin": (i, [vp, u32]),
+        "pf_qc_get": (i, [vp, i, i, vp]),
+        "pf_qc_clip_get": (i, [vp, i, vp]),
+        "pf_qc_fastq": (i, [vp, i, vp, u64, i, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
+        "pf_qc_end": (i, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError = header / library mismatch
@@ -318,7 +325,8 @@ DECLARED_SYMBOLS = ["pf_create", "pf_warmup", "pf_destroy", "pf_last_error", "pf
                     "pf_maskcount_fastq_trimmed", "pf_maskcount_fastq_pair_trimmed", "pf_inflate_bgzf", "pf_inflate_gzip", "pf_device_alloc", "pf_copy",
                     "pf_fasta_index", "pf_fasta_index_fetch", "pf_count_fasta", "pf_maskcount_fasta", "pf_color_fasta", "pf_deflate_bgzf",
                     "pf_clip_begin", "pf_clip_stats_get", "pf_clip_end", "pf_clip_last_ends",
-                    "pf_clip_begin_pairs", "pf_clip_pair_stats_get"]
+                    "pf_clip_begin_pairs", "pf_clip_pair_stats_get",
+                    "pf_qc_begin", "pf_qc_get", "pf_qc_clip_get", "pf_qc_fastq", "pf_qc_end"]
 
 
 class TrimPlan(C.Structure):   # pf_trim_plan
@@ -710,6 +718,45 @@ class Device:
     def clip_end(self):
         """pf_clip_end: closes the clip; the trim calls are what they were without one"""
         self._check(self.L.pf_clip_end(self.h))
+
+    def qc_begin(self, phred: int = 33):
+        """K-QC (pf_qc_begin): opens a read quality report on the context -- until qc_end() trim_fastq, trim_fastq_pair,
+        trim_table_fastq[_pair] and the *_trimmed count calls add every record they take to the report's tables (stage raw, and the kept
+        ones with their final interval to stage kept), and qc_fastq adds a chunk to stage raw alone.  Refusals raise DeviceError by name."""
+        self._check(self.L.pf_qc_begin(self.h, int(phred)))
+
+    def qc_tables(self) -> np.ndarray:
+        """pf_qc_get for both sides and both stages: a u64 array [side][stage][QC_TABLE_WORDS] (the words: csrc/pf_qc_rule.hpp)"""
+        t = np.zeros((2, 2, QC_TABLE_WORDS), dtype=np.uint64)
+        for side in range(2):
+            for stage in range(2):
+                self._check(self.L.pf_qc_get(self.h, side, stage, t[side, stage].ctypes.data))
+        return t
+
+    def qc_clip_table(self) -> np.ndarray:
+        """pf_qc_clip_get for both sides: a u64 array [side][QC_CLIP_WORDS], the clip ends below the read length"""
+        t = np.zeros((2, QC_CLIP_WORDS), dtype=np.uint64)
+        for side in range(2):
+            self._check(self.L.pf_qc_clip_get(self.h, side, t[side].ctypes.data))
+        return t
+
+    def qc_fastq(self, text, side: int = 0, final: bool = True):
+        """K-QC on one chunk of a FASTQ file (pf_qc_fastq): its whole records into stage raw of `side` (0 or 1); returns (bytes_used,
+        n_records).  text: bytes, a uint8 numpy array or a device tensor.  A format error raises DeviceError with .bad_record."""
+        if isinstance(text, (bytes, bytearray)):
+            text = np.frombuffer(bytes(text), dtype=np.uint8)
+        n = int(text.shape[0])
+        used, recs, bad = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        st = self.L.pf_qc_fastq(self.h, int(side), _ptr(text) if n else None, n, int(final), C.byref(used), C.byref(recs), C.byref(bad))
+        if st != PF_OK:
+            e = DeviceError(st, self.L.pf_last_error(self.h).decode())
+            e.bad_record = bad.value
+            raise e
+        return used.value, recs.value
+
+    def qc_end(self):
+        """pf_qc_end: closes the report; the trim calls launch nothing more"""
+        self._check(self.L.pf_qc_end(self.h))
 
     def inflate_bgzf(self, comp, member_off, out=None, out_cap=None):
         """K-INFLATE (pf_inflate_bgzf): the BGZF members comp[member_off[m] : member_off[m + 1]] inflated one behind the other; returns

@@ -53,7 +53,8 @@ DECLARED_SYMBOLS = ["pfh_open", "pfh_close", "pfh_last_error", "pfh_set_output_d
                     "pfh_deflate_member", "pfh_deflate_bound", "pfh_reads_gz_out",
                     "pfh_reads_adapters", "pfh_reads_adapters_report", "pfh_clip_parse_adapters", "pfh_clip_refusal_text", "pfh_clip_read",
                     "pfh_trim_fastq_chunk_clip", "pfh_reads_adapter_pairs", "pfh_reads_adapters_pair_report", "pfh_clip_parse_adapter_pairs",
-                    "pfh_clip_pair", "pfh_trim_fastq_pair_chunk_clip"]
+                    "pfh_clip_pair", "pfh_trim_fastq_pair_chunk_clip",
+                    "pfh_reads_report", "pfh_qc_fastq", "pfh_qc_fastq_chunk", "pfh_qc_report_text", "pfh_qc_phred_hint"]
 
 
 class RunOptions(C.Structure):   # pfh_run_options (include/ploidyfrost_host.h)
@@ -279,6 +280,18 @@ def load_library() -> C.CDLL:
     L.pfh_clip_parse_adapters.restype = C.c_int
     L.pfh_clip_parse_adapters.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                           C.POINTER(C.c_uint64)]
+    L.pfh_reads_report.restype = None
+    L.pfh_reads_report.argtypes = [C.c_char_p]
+    L.pfh_qc_fastq.restype = C.c_int
+    L.pfh_qc_fastq.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p, C.c_uint32, C.c_uint64, C.c_int]
+    L.pfh_qc_fastq_chunk.restype = C.c_int
+    L.pfh_qc_fastq_chunk.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.pfh_qc_report_text.restype = C.c_int
+    L.pfh_qc_report_text.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.pfh_qc_phred_hint.restype = C.c_uint32
+    L.pfh_qc_phred_hint.argtypes = [C.c_uint64, C.c_uint64]
     L.pfh_reads_adapter_pairs.restype = None
     L.pfh_reads_adapter_pairs.argtypes = [C.c_uint32, C.c_uint32, C.c_int]
     L.pfh_reads_adapters_pair_report.restype = None
@@ -917,14 +930,87 @@ def _gz_mode(gz) -> int:
     return int(bool(gz))
 
 
+def _set_report(L, report):
+    """`--report` of the next trim / run call (pfh_reads_report): a path, or None for no report"""
+    L.pfh_reads_report(None if report is None else os.fsencode(report))
+
+
+QC_TABLE_WORDS, QC_CLIP_WORDS = 9515, 1025   # PF_QC_TABLE_WORDS, PF_QC_CLIP_WORDS (csrc/pf_qc_rule.hpp has the words)
+
+
+def qc_fastq(paths, report: str, paths2=None, phred: int = 33, gz: bool = False, chunk_bytes: int = 0) -> None:
+    """`ploidyfrost qc (-i ... | -1 ... -2 ...) -o report` (pfh_qc_fastq): the read quality report of the FASTQ file(s) `paths` (side 1)
+    and `paths2` (side 2, may be None) as they are, accumulated on the device (K-QC) and written to `report` as tab-separated text.  A
+    refusal raises RuntimeError by name; nothing is left under the report's name."""
+    L = load_library()
+    p1, n1 = _paths(paths)
+    p2, n2 = _paths([] if paths2 is None else paths2)
+    L.pfh_reads_gz(_gz_mode(gz))
+    rc = L.pfh_qc_fastq(p1, n1, p2, n2, os.fsencode(report), int(phred), int(chunk_bytes), 0)
+    if rc:
+        raise (ReadsRefused if gz else RuntimeError)(L.pfh_last_error(None).decode())
+
+
+def qc_fastq_chunk(text: bytes, tables=None, clip=None, side: int = 1, phred: int = 33, final: bool = True, steps=None, adapters=None, seed: int = 2,
+                   score: int = 10) -> dict:
+    """The rule of K-QC on one chunk of one file by the host's plain restatement (pfh_qc_fastq_chunk; no device): the whole records of
+    `text` added to tables[side - 1][0] (raw) and, with steps (Trimmomatic's words; may be [] beside adapters) the kept ones to
+    tables[side - 1][1]; with adapters (the dict of clip_parse_adapters) the clip ends below the read length to clip[side - 1].
+    tables: a u64 array [2][2][QC_TABLE_WORDS] to add to (None: a new one of zeros), clip: [2][QC_CLIP_WORDS] likewise.  Returns dict with
+    tables, clip, clause (a name of MASK_CLAUSES), bad_record, bytes_used, n_records."""
+    L = load_library()
+    if tables is None:
+        tables = np.zeros((2, 2, QC_TABLE_WORDS), dtype=np.uint64)
+    if clip is None:
+        clip = np.zeros((2, QC_CLIP_WORDS), dtype=np.uint64)
+    trimmed = steps is not None
+    st = trim_parse_steps(steps) if trimmed and len(steps) else np.zeros(0, dtype=TRIM_STEP)
+    t = np.frombuffer(bytes(text), dtype=np.uint8)
+    if adapters is not None:
+        bases = np.frombuffer(bytes(adapters["bases"]), dtype=np.uint8)
+        off = np.ascontiguousarray(adapters["off"], dtype=np.uint32)
+        sd = np.ascontiguousarray(adapters["side"], dtype=np.uint8)
+    else:
+        bases, off, sd = np.zeros(0, dtype=np.uint8), np.zeros(1, dtype=np.uint32), np.zeros(0, dtype=np.uint8)
+    used, recs, bad = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    clause = L.pfh_qc_fastq_chunk(t.ctypes.data if len(t) else None, len(t), int(final), int(phred), int(side), int(trimmed),
+                                  st.ctypes.data if len(st) else None, len(st), int(adapters is not None), bases.ctypes.data if len(bases) else None,
+                                  off.ctypes.data, sd.ctypes.data if len(sd) else None, len(sd), int(seed), int(score), tables[side - 1, 0].ctypes.data,
+                                  tables[side - 1, 1].ctypes.data, clip[side - 1].ctypes.data, C.byref(used), C.byref(recs), C.byref(bad))
+    if clause < 0:
+        raise ValueError(L.pfh_last_error(None).decode())
+    return dict(tables=tables, clip=clip, clause=MASK_CLAUSES[clause], bad_record=bad.value, bytes_used=used.value, n_records=recs.value)
+
+
+def qc_report_text(tables, clip=None, phred: int = 33) -> bytes:
+    """The report as `qc` and `--report` write it (pfh_qc_report_text): a function of the tables [2][2][QC_TABLE_WORDS] and, where a
+    clip was open, of clip [2][QC_CLIP_WORDS] alone."""
+    L = load_library()
+    tables = np.ascontiguousarray(tables, dtype=np.uint64).reshape(2, 2, QC_TABLE_WORDS)
+    cp = None if clip is None else np.ascontiguousarray(clip, dtype=np.uint64).reshape(2, QC_CLIP_WORDS)
+    n = C.c_uint64()
+    if L.pfh_qc_report_text(tables.ctypes.data, None if cp is None else cp.ctypes.data, int(phred), None, 0, C.byref(n)):
+        raise ValueError(L.pfh_last_error(None).decode())
+    buf = C.create_string_buffer(max(n.value, 1))
+    L.pfh_qc_report_text(tables.ctypes.data, None if cp is None else cp.ctypes.data, int(phred), buf, n.value, C.byref(n))
+    return buf.raw[: n.value]
+
+
+def qc_phred_hint(min_byte: int, reads: int) -> int:
+    """33, 64 or 0 (undecided) from the smallest quality byte of the raw stage and the number of reads that held one (pfh_qc_phred_hint)"""
+    return int(load_library().pfh_qc_phred_hint(int(min_byte), int(reads)))
+
+
 def trim_fastq(inputs, out: str, steps, phred: int = 33, trimlog=None, chunk_bytes: int = 0, gz: bool = False, gz_out: bool = False,
-               adapters=None, adapter_seed: int = 2, adapter_score: int = 10) -> dict:
+               adapters=None, adapter_seed: int = 2, adapter_score: int = 10, report=None) -> dict:
     """`ploidyfrost trim -i ... -o out STEP...` (pfh_trim_fastq): the reads of the FASTQ file(s) `inputs`, one after the other,
     quality-trimmed by `steps` (Trimmomatic's words) into `out`; trimlog: a file with one line per record.  Returns the statistics.  A
     refusal raises RuntimeError (format refusals with the input's path and the 1-based record number); nothing is left under any
     output name.  gz_out (`--gz-out`): `out` is written as blocked gzip, deflated on the device (K-DEFLATE).
     adapters (`--adapters`): the path of an adapter file -- adapter read-through is clipped on the device before the steps (K-CLIP;
-    adapter_seed, adapter_score: `--adapter-seed`, `--adapter-score`); steps may then be empty; clip_report() gives the `clip:` line."""
+    adapter_seed, adapter_score: `--adapter-seed`, `--adapter-score`); steps may then be empty; clip_report() gives the `clip:` line.
+    report (`--report`): a path for the read quality report of the reads as they come (raw) and as they are written (kept) (K-QC); every
+    other output is what it is without."""
     L = load_library()
     if isinstance(inputs, (str, bytes, os.PathLike)):
         inputs = [inputs]
@@ -934,6 +1020,7 @@ def trim_fastq(inputs, out: str, steps, phred: int = 33, trimlog=None, chunk_byt
     L.pfh_reads_gz(_gz_mode(gz))
     L.pfh_reads_gz_out(int(gz_out))
     _set_adapters(L, adapters, adapter_seed, adapter_score)
+    _set_report(L, report)
     rc = L.pfh_trim_fastq(paths, len(inputs), os.fsencode(out), st.ctypes.data if len(st) else None, len(st), phred,
                           os.fsencode(trimlog) if trimlog else None, int(chunk_bytes), 0, stats.ctypes.data)
     if rc:
@@ -943,12 +1030,13 @@ def trim_fastq(inputs, out: str, steps, phred: int = 33, trimlog=None, chunk_byt
 
 def trim_fastq_pair(in1: str, in2: str, outs, steps, phred: int = 33, trimlog=None, chunk_bytes: int = 0, gz: bool = False, gz_out: bool = False,
                     adapters=None, adapter_seed: int = 2, adapter_score: int = 10, adapter_pairs: bool = False, adapter_pair_score: int = 30,
-                    adapter_pair_min: int = 8, adapter_keep_both: bool = False):
+                    adapter_pair_min: int = 8, adapter_keep_both: bool = False, report=None):
     """`ploidyfrost trim -1 in1 -2 in2 -o1 .. -u1 .. -o2 .. -u2 .. STEP...` (pfh_trim_fastq_pair): outs = (o1, u1, o2, u2).  Returns the
     statistics of file 1 and of file 2 (the pair fields are the same in both).  gz_out (`--gz-out`): the four outputs are blocked gzip.
     adapters, adapter_seed, adapter_score: as trim_fastq takes them (names ending in /1 and /2 choose the file).
     adapter_pairs (`--adapter-pairs`, with adapter_pair_score, adapter_pair_min, adapter_keep_both): palindrome mode from the file's
-    prefix pairs beside simple mode (K-PALIN); clip_pair_report() gives the tail of the `clip:` line."""
+    prefix pairs beside simple mode (K-PALIN); clip_pair_report() gives the tail of the `clip:` line.
+    report (`--report`): as trim_fastq takes it; file 1 is side 1 of the report, file 2 side 2."""
     L = load_library()
     st = trim_parse_steps(steps) if len(steps) or adapters is None else np.zeros(0, dtype=TRIM_STEP)
     assert len(outs) == 4
@@ -957,6 +1045,7 @@ def trim_fastq_pair(in1: str, in2: str, outs, steps, phred: int = 33, trimlog=No
     L.pfh_reads_gz(_gz_mode(gz))
     L.pfh_reads_gz_out(int(gz_out))
     _set_adapters(L, adapters, adapter_seed, adapter_score, adapter_pairs, adapter_pair_score, adapter_pair_min, adapter_keep_both)
+    _set_report(L, report)
     rc = L.pfh_trim_fastq_pair(os.fsencode(in1), os.fsencode(in2), paths, st.ctypes.data if len(st) else None, len(st), phred,
                                os.fsencode(trimlog) if trimlog else None, int(chunk_bytes), 0, stats.ctypes.data)
     if rc:
@@ -1104,7 +1193,7 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
               threads: int = 1, model=None, model_only: bool = False, db_out=None, gfa_out=None, chunk_bytes: int = 0,
               initial_slots: int = 0, steps=None, phred: int = 33, pairs=None, gz: bool = False, fasta: bool = False,
               adapters=None, adapter_seed: int = 2, adapter_score: int = 10, adapter_pairs: bool = False, adapter_pair_score: int = 30,
-              adapter_pair_min: int = 8, adapter_keep_both: bool = False) -> dict:
+              adapter_pair_min: int = 8, adapter_keep_both: bool = False, report=None) -> dict:
     """`ploidyfrost run` (pfh_run_fastq): reads to ploidy estimate in one process -- the FASTQ file(s) `inputs` counted, the thresholds
     derived, the k-mers of the masked reads counted (K-MASKCOUNT), the graph built and the single-sample calling run made on one device
     context; PloidyFrost_output/<out_prefix>_*.txt in the working directory.  model: None, "cov" or "fre".  Returns the fields of the
@@ -1119,7 +1208,9 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
     no step is needed beside them, also with pairs.
     adapter_pairs (`--adapter-pairs`, with adapter_pair_score, adapter_pair_min, adapter_keep_both): palindrome mode on pairs, as
     trim_fastq_pair takes it; refused by name without pairs.  Only pairs of which both records are kept go on, so without
-    adapter_keep_both a clipped pair is not counted at all."""
+    adapter_keep_both a clipped pair is not counted at all.
+    report (`--report`): the report `trim_fastq(..., report=)` writes for the same inputs, taken over the first pass; refused by name
+    without steps or adapters."""
     L = load_library()
     if pairs is not None:
         if inputs is not None:
@@ -1147,6 +1238,7 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
     if steps is None and pairs is None and adapters is None:
         L.pfh_reads_gz(_gz_mode(gz))
         L.pfh_reads_fasta(int(bool(fasta)))
+        _set_report(L, report)
         rc = L.pfh_run_fastq(paths, n, os.fsencode(out_prefix), C.byref(o), 0, stats.ctypes.data)
         if rc:
             raise (ReadsRefused if gz else RuntimeError)(L.pfh_last_error(None).decode())
@@ -1155,6 +1247,7 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
     L.pfh_reads_gz(_gz_mode(gz))
     L.pfh_reads_fasta(int(bool(fasta)))
     _set_adapters(L, adapters, adapter_seed, adapter_score, adapter_pairs, adapter_pair_score, adapter_pair_min, adapter_keep_both)
+    _set_report(L, report)
     rc = L.pfh_run_fastq_trimmed(paths, n, int(pairs is not None), st.ctypes.data if len(st) else None, len(st), int(phred), os.fsencode(out_prefix),
                                  C.byref(o), 0, stats.ctypes.data, per.ctypes.data)
     if rc:
