@@ -76,7 +76,7 @@ enum pf_kernel {
     PF_K_GUNZIP, /* K-GUNZIP: everything one pf_inflate_gzip launches (find, count, chain, decode, window, resolve with the CRC), timed as one launch; unit: inflated bytes */
     PF_K_FASTA, /* K-FASTA: everything the index of one pf_fasta_index / pf_count_fasta / pf_maskcount_fasta / pf_color_fasta call launches (newlines, lines, words, scans, compact, table), timed as one launch; the core behind it is timed under its own kernel; unit: bytes of the chunk */
     PF_K_DEFLATE, /* K-DEFLATE: everything one pf_deflate_bgzf launches (deflate, scan of the members' sizes, pack), timed as one launch; unit: bytes of text */
-    PF_K_CLIP, /* K-CLIP: the kernels one pf_trim_fastq* / pf_trim_table_fastq* / pf_*_fastq*_trimmed call launches to clip adapters while a clip is open (one per file), timed as one launch inside the call's own; unit: records */ PF_K_PALIN, /* K-PALIN: the kernel one pf_trim_fastq_pair / pf_trim_table_fastq_pair / pf_*_fastq_pair_trimmed call launches behind K-CLIP's while a clip with prefix pairs is open (palindrome mode), timed as one launch inside the call's own; unit: pairs */ PF_K_QC, /* K-QC: the kernel one pf_qc_fastq call, or one pf_trim_fastq* / pf_trim_table_fastq* / pf_*_fastq*_trimmed call while a report is open, launches per file to add its records to the report's tables, timed as one launch per file inside the call's own; unit: records */
+    PF_K_CLIP, /* K-CLIP: the kernels one pf_trim_fastq* / pf_trim_table_fastq* / pf_*_fastq*_trimmed call launches to clip adapters while a clip is open (one per file), timed as one launch inside the call's own; unit: records */ PF_K_PALIN, /* K-PALIN: the kernel one pf_trim_fastq_pair / pf_trim_table_fastq_pair / pf_*_fastq_pair_trimmed call launches behind K-CLIP's while a clip with prefix pairs is open (palindrome mode), timed as one launch inside the call's own; unit: pairs */ PF_K_QC, /* K-QC: the kernel one pf_qc_fastq call, or one pf_trim_fastq* / pf_trim_table_fastq* / pf_*_fastq*_trimmed call while a report is open, launches per file to add its records to the report's tables, timed as one launch per file inside the call's own; unit: records */ PF_K_HETPAIR, /* K-HETPAIR: everything one pf_hetpairs launches (flag, scan, write, table), timed as one launch; unit: keys in range */
     PF_K_COUNT_
 };
 int pf_enable_timing(pf_ctx *, int on);
@@ -563,6 +563,29 @@ typedef struct pf_gunzip_stats {
  * comp, window, out, new_window: [host|dev] */
 int pf_inflate_gzip(pf_ctx *, const uint8_t *comp, uint64_t n_bytes, uint64_t start_bit, const uint8_t *window, uint32_t n_window,
                     uint32_t piece_bytes, char *out, uint64_t out_cap, uint8_t *new_window, pf_gunzip_result *res, pf_gunzip_stats *stats);
+
+/* K-HETPAIR: the heterozygous k-mer pairs of a Smudgeplot-style check of the ploidy estimate, from the distinct canonical k-mers and
+ * counters pf_count_finish / pf_kmc_decode leave on the device and the count table pf_upload_counts built from them (the rule is
+ * csrc/pf_hetpair_rule.hpp; PARITY UNPINNED, Smudgeplot is not part of the build).  S = the keys with lo <= counter <= hi; a pair is
+ * (x, y), x < y, both in S, one substitution apart as canonical k-mers, neither with another neighbour in S.  table: W * W uint64_t
+ * cells, W = hi - lo + 1 <= 4096, table[(a - lo) * W + (b - lo)] = pairs with the counters a <= b; [host|dev], may be NULL.  The four
+ * arrays (all given or all NULL) receive device arrays of *n_pairs entries in the order of x in `kmers`, released with pf_device_free
+ * (NULL when there is no pair).  kmers, counts: [host|dev], distinct keys.  Needs a resident single-sample count table of the same k,
+ * counted on both strands and uploaded from the same arrays (the caller's duty, as for K-MASK); each missing piece, lo < 1, lo > hi
+ * and W > 4096 are PF_ERR_ARG by name.  n = 0: empty results. */
+typedef struct pf_hetpair_stats {
+    uint64_t kmers;          /* keys given */
+    uint64_t in_range;       /* keys of S */
+    uint64_t one_partner;    /* keys of S with exactly one distinct neighbour in S */
+    uint64_t many_partners;  /* keys of S with two or more */
+    uint64_t pairs;
+} pf_hetpair_stats;
+int pf_hetpairs(pf_ctx *, const uint64_t *kmers, const uint32_t *counts, uint64_t n, uint32_t k, uint32_t lo, uint32_t hi,
+                uint64_t *table, uint64_t **pair_x_dev, uint64_t **pair_y_dev, uint32_t **cov_x_dev, uint32_t **cov_y_dev,
+                uint64_t *n_pairs, pf_hetpair_stats *stats);
+/* The table kernel of K-HETPAIR alone over compacted counters on the device (pairs with a counter outside [lo, hi] add nothing);
+ * table: [host|dev].  Timed as a launch of PF_K_HETPAIR; unit: pairs. */
+int pf_hetpair_table(pf_ctx *, const uint32_t *cov_x_dev, const uint32_t *cov_y_dev, uint64_t n_pairs, uint32_t lo, uint32_t hi, uint64_t *table);
 
 int pf_copy_to_host(pf_ctx *, void *dst, const void *src_dev, size_t bytes);
 /* Device memory of the caller's own (freed with pf_device_free), and a copy between any two places (host or device) on the launch

@@ -652,6 +652,39 @@ int pfh_gunzip_file(const uint8_t *bytes, uint64_t n, uint32_t piece_bytes, uint
                     uint64_t *out_len, uint64_t *member, uint64_t *byte, uint64_t stats[9]);
 const char *pfh_gunzip_clause_text(int clause);
 
+/* ---- heterozygous k-mer pairs: `ploidyfrost smudge` and `run --smudge` (K-HETPAIR, pf_hetpairs in ploidyfrost_hip.h) ----
+ * The rule, the summary and the text of the report: csrc/pf_hetpair_rule.hpp (PARITY UNPINNED: Smudgeplot is not part of the build).
+ * pfh_hetpairs_host: the host's plain restatement, no device -- distinct canonical keys and their counters in, table (W * W cells,
+ * W = hi - lo + 1, may be null), the pairs in the order of x (at most cap of *n_pairs are copied; the arrays may be null) and the
+ * statistics out; returns 0, the rule's refusal (lo < 1, lo > hi, W > 4096, k) or -1 for a missing argument.  pfh_smudge_report_text:
+ * table, statistics and n (0: none) to the report; *len = the bytes of the text, of which at most cap go to out.  pfh_smudge_of: the
+ * smudge (p, m) of a pair with the coverages a <= b at the haploid coverage n.  pfh_smudge: the sub-command -- db_prefix, or inputs
+ * counted with k, ci, cx, cs (db_prefix null; takes the pfh_reads_gz / pfh_reads_fasta switches); the bounds lo and hi or auto_cutoffs
+ * (lo = `cutoffL -d`, hi = `cutoffU -d [quantile]` of the counters); n_hap (0: no summary); pairs_path (null: none).  It writes
+ * <out>_smudge.tsv under a temporary name, renamed at the end; 0 = ok, else pfh_last_error(NULL) words the refusal and nothing is left
+ * under an output name. */
+typedef struct pfh_smudge_result {
+    pf_hetpair_stats stats;
+    uint32_t k, lo, hi, clamped;        /* the bounds that were used; clamped: hi was lowered to lo + 4095 */
+    uint32_t proposed_p, proposed_m;    /* with n_hap: the label with the most pairs (0, 0: no pair) */
+    uint64_t proposed_pairs, all_pairs;
+} pfh_smudge_result;
+/* `run --smudge [--smudge-n N] [--smudge-pairs FILE]`: after pfh_reads_smudge(1, n_hap, pairs_path) the next pfh_run_fastq or
+ * pfh_run_fastq_trimmed of this thread runs K-HETPAIR behind the table of its first pass (lo = L, hi = min(U, L + 4095)) and writes
+ * PloidyFrost_output/<out_prefix>_smudge.tsv, every other output being what it is without; n_hap < 0: no haploid coverage,
+ * pairs_path null: no pairs file.  The call takes the switch back; pfh_reads_smudge_result gives what it found.  pfh_run_multi_fastq*
+ * refuse the switch as not built. */
+void pfh_reads_smudge(int on, int64_t n_hap, const char *pairs_path);
+void pfh_reads_smudge_result(pfh_smudge_result *out);
+int pfh_hetpairs_host(const uint64_t *kmers, const uint32_t *counts, uint64_t n, uint32_t k, uint32_t lo, uint32_t hi, uint64_t *table, uint64_t *pair_x,
+                      uint64_t *pair_y, uint32_t *cov_x, uint32_t *cov_y, uint64_t cap, uint64_t *n_pairs, pf_hetpair_stats *stats);
+int pfh_smudge_report_text(const uint64_t *table, const pf_hetpair_stats *stats, uint32_t k, uint32_t lo, uint32_t hi, uint64_t n, char *out, uint64_t cap,
+                           uint64_t *len);
+int pfh_smudge_of(uint64_t a, uint64_t b, uint64_t n, uint32_t *p, uint32_t *m);
+int pfh_smudge(const char *db_prefix, const char *const *inputs, uint32_t n_inputs, uint32_t k, uint64_t ci, uint64_t cx, uint64_t cs, uint32_t lo, uint32_t hi,
+               int auto_cutoffs, double quantile, uint64_t n_hap, const char *pairs_path, const char *out, uint64_t chunk_bytes, uint64_t initial_slots,
+               int device, pfh_smudge_result *result);
+
 /* Kmer::hash(seed) of the reference's Bifrost build (wyhash over the 8-byte left-aligned k-mer) */
 uint64_t pfh_bifrost_kmer_hash(uint64_t left_aligned_kmer, uint64_t seed);
 

@@ -9,6 +9,7 @@
 #include "pf_cdbg.hpp"
 #include "pf_cutoffs.hpp"
 #include "pf_mask_host.hpp"
+#include "pf_hetpair_host.hpp"
 #include "pf_count_host.hpp"
 #include "pf_build_host.hpp"
 #include "pf_run_host.hpp"
@@ -837,9 +838,44 @@ static void trim_inputs_from(const pf_trim_step *steps, uint32_t n_steps, uint32
     t.phred = phred;
     t.clip = clip;
 }
+// `--smudge [--smudge-n N] [--smudge-pairs FILE]`: the switch of the next run call of this thread, and what that call found
+struct ReadsSmudge {
+    bool on = false, n_seen = false;
+    uint64_t n = 0;
+    std::string pairs;
+};
+static thread_local ReadsSmudge g_reads_smudge;
+static thread_local pfh_smudge_result g_smudge_result = {};
+void pfh_reads_smudge(int on, int64_t n_hap, const char *pairs_path) {
+    g_reads_smudge = ReadsSmudge();
+    g_reads_smudge.on = on != 0;
+    g_reads_smudge.n_seen = n_hap >= 0;
+    g_reads_smudge.n = n_hap >= 0 ? (uint64_t)n_hap : 0;
+    g_reads_smudge.pairs = pairs_path ? pairs_path : "";
+}
+void pfh_reads_smudge_result(pfh_smudge_result *out) { if (out) *out = g_smudge_result; }
+static ReadsSmudge take_reads_smudge() {
+    ReadsSmudge r;
+    std::swap(r, g_reads_smudge);
+    return r;
+}
+static void smudge_result_c(const pfh::SmudgeResult &r, pfh_smudge_result *out) {
+    if (!out) return;
+    out->stats = r.stats;
+    out->k = r.k;
+    out->lo = r.lo;
+    out->hi = r.hi;
+    out->clamped = r.clamped ? 1 : 0;
+    out->proposed_p = r.summary.best.p;
+    out->proposed_m = r.summary.best.m;
+    out->proposed_pairs = r.summary.best_pairs;
+    out->all_pairs = r.summary.all_pairs;
+}
 static int run_fastq_c(const char *who, const char *const *inputs, uint32_t n_inputs, int paired, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred,
                        const char *out_prefix, const pfh_run_options *o, int device, pfh_run_stats *stats, pf_trim_stats *per_unit) {
     const pfh::ClipOptions clip = take_reads_adapters();   // taken first: a refusal below does not leave the switch to the next call
+    const ReadsSmudge smudge = take_reads_smudge();
+    g_smudge_result = pfh_smudge_result{};
     if (!out_prefix || !o || (n_inputs && !inputs)) { g_open_err = std::string(who) + ": inputs, output prefix and options are needed"; return 1; }
     try {
         std::vector<std::string> in;
@@ -857,8 +893,13 @@ static int run_fastq_c(const char *who, const char *const *inputs, uint32_t n_in
         trim_inputs_from(steps, n_steps, phred, clip, opt.trim);
         opt.report = take_reads_report();
         opt.paired = paired != 0;
+        opt.smudge = smudge.on;
+        opt.smudge_n = smudge.n;
+        opt.smudge_n_seen = smudge.n_seen;
+        opt.smudge_pairs = smudge.pairs;
         pfh::RunStats st;
         const int rc = pfh::run_fastq(in, out_prefix, opt, device, st, nullptr, g_open_err);
+        if (!rc && opt.smudge) smudge_result_c(st.smudge, &g_smudge_result);
         if (stats)
             *stats = pfh_run_stats{st.counted.reads, st.counted.bases, st.counted.kmers, st.counted.kmers_bad, st.counted.unique, st.lower, st.upper,
                                    st.masked.kmers_bad, st.masked.kmers_kept, st.distinct_kept, st.graph.unitigs, st.graph.removed, st.graph.unitigs_out,
@@ -884,6 +925,7 @@ static int run_multi_fastq_c(const char *who, const char *const *names, const ui
                              const pfh_run_options *o, const pf_filter_multi_opts *multi, int each_color, int device, pfh_run_multi_stats *stats,
                              uint64_t *per_color, pf_trim_stats *per_input) {
     const pfh::ClipOptions clip = take_reads_adapters();   // taken first: a refusal below does not leave the switch to the next call
+    { const ReadsSmudge sm = take_reads_smudge(); if (sm.on || sm.n_seen || !sm.pairs.empty()) { g_open_err = "run-multi: --smudge is not built into run-multi (`smudge` or `run --smudge` per sample)"; return 1; } }
     if (!take_reads_report().empty()) { g_open_err = "run-multi: --report is not built into run-multi (`trim --report` or `run --report` per sample)"; return 1; }
     if (!out_prefix || !o || (n_samples && (!names || !n_inputs_of))) { g_open_err = std::string(who) + ": samples, output prefix and options are needed"; return 1; }
     try {
@@ -1962,6 +2004,79 @@ int pfh_gunzip_file(const uint8_t *bytes, uint64_t n, uint32_t piece_bytes, uint
     return c;
 }
 const char *pfh_gunzip_clause_text(int clause) { return pf_gunzip::clause_text(clause); }
+
+// ---- heterozygous k-mer pairs (K-HETPAIR, `smudge`) ----------------------------------------------------
+int pfh_hetpairs_host(const uint64_t *kmers, const uint32_t *counts, uint64_t n, uint32_t k, uint32_t lo, uint32_t hi, uint64_t *table, uint64_t *pair_x,
+                      uint64_t *pair_y, uint32_t *cov_x, uint32_t *cov_y, uint64_t cap, uint64_t *n_pairs, pf_hetpair_stats *stats) {
+    if (n_pairs) *n_pairs = 0;
+    const int clause = pf_hetpair::arg_clause((int64_t)k, lo, hi);
+    if (clause) { g_open_err = std::string("pfh_hetpairs_host: ") + pf_hetpair::arg_text(clause); return clause; }
+    if (n && (!kmers || !counts)) { g_open_err = "pfh_hetpairs_host: kmers and counts are needed"; return -1; }
+    pf_hetpair::Pairs pairs;
+    pf_hetpair::Stats st;
+    pf_hetpair::hetpairs_host(kmers, counts, n, (int)k, lo, hi, table, pairs, st);
+    if (stats) *stats = pf_hetpair_stats{st.kmers, st.in_range, st.one_partner, st.many_partners, st.pairs};
+    if (n_pairs) *n_pairs = pairs.x.size();
+    const size_t m = (size_t)std::min<uint64_t>(cap, pairs.x.size());
+    if (pair_x && m) memcpy(pair_x, pairs.x.data(), m * 8);
+    if (pair_y && m) memcpy(pair_y, pairs.y.data(), m * 8);
+    if (cov_x && m) memcpy(cov_x, pairs.cov_x.data(), m * 4);
+    if (cov_y && m) memcpy(cov_y, pairs.cov_y.data(), m * 4);
+    return 0;
+}
+int pfh_smudge_report_text(const uint64_t *table, const pf_hetpair_stats *stats, uint32_t k, uint32_t lo, uint32_t hi, uint64_t n, char *out, uint64_t cap,
+                           uint64_t *len) {
+    if (!table || !stats || !len) { g_open_err = "pfh_smudge_report_text: table, stats and len are needed"; return -1; }
+    const int clause = pf_hetpair::arg_clause((int64_t)k, lo, hi);
+    if (clause) { g_open_err = std::string("pfh_smudge_report_text: ") + pf_hetpair::arg_text(clause); return clause; }
+    const std::string t = pfh::smudge_report(table, *stats, k, lo, hi, n);
+    *len = t.size();
+    if (out) memcpy(out, t.data(), std::min<uint64_t>(cap, t.size()));
+    return 0;
+}
+int pfh_smudge_of(uint64_t a, uint64_t b, uint64_t n, uint32_t *p, uint32_t *m) {
+    if (!p || !m || a < 1 || b < a || n < 1) { g_open_err = "pfh_smudge_of: 1 <= a <= b and n >= 1"; return -1; }
+    const pf_hetpair::Smudge s = pf_hetpair::smudge_of(a, b, n);
+    *p = s.p;
+    *m = s.m;
+    return 0;
+}
+int pfh_smudge(const char *db_prefix, const char *const *inputs, uint32_t n_inputs, uint32_t k, uint64_t ci, uint64_t cx, uint64_t cs, uint32_t lo, uint32_t hi,
+               int auto_cutoffs, double quantile, uint64_t n_hap, const char *pairs_path, const char *out, uint64_t chunk_bytes, uint64_t initial_slots,
+               int device, pfh_smudge_result *result) {
+    const int gz = take_reads_gz();
+    const bool fasta = take_reads_fasta();
+    if (!out || (n_inputs && !inputs)) { g_open_err = "pfh_smudge: inputs and output are needed"; return 1; }
+    if ((db_prefix != nullptr) == (n_inputs != 0)) { g_open_err = "smudge: either a database or inputs to count are given"; return 1; }
+    try {
+        pfh::SmudgeOptions opt;
+        opt.lo = lo;
+        opt.hi = hi;
+        opt.auto_cutoffs = auto_cutoffs != 0;
+        opt.quantile = quantile;
+        opt.n = n_hap;
+        opt.pairs = pairs_path ? pairs_path : "";
+        pfh::SmudgeResult res;
+        int rc;
+        if (db_prefix) {
+            rc = pfh::smudge_db(db_prefix, opt, out, device, res, g_open_err);
+        } else {
+            std::vector<std::string> in;
+            for (uint32_t i = 0; i < n_inputs; ++i) in.push_back(inputs[i] ? inputs[i] : "");
+            pfh::CountOptions c = count_options(k, ci, cx, cs, 1);
+            c.chunk_bytes = chunk_bytes;
+            c.initial_slots = initial_slots;
+            c.gz = gz;
+            c.fasta = fasta;
+            rc = pfh::smudge_counted(c, in, opt, out, device, res, g_open_err);
+        }
+        smudge_result_c(res, result);
+        return rc;
+    } catch (const std::exception &e) {
+        g_open_err = std::string("ploidyfrost host layer: ") + e.what();
+        return 1;
+    }
+}
 
 uint64_t pfh_bifrost_kmer_hash(uint64_t left_aligned_kmer, uint64_t seed) { return pfh::bifrost_kmer_hash(left_aligned_kmer, seed); }
 

@@ -35,6 +35,7 @@
 #include "pf_count_host.hpp"
 #include "pf_build_host.hpp"
 #include "pf_mask_host.hpp"
+#include "pf_hetpair_host.hpp"
 #include "pf_run_host.hpp"
 #include "pf_runmulti_host.hpp"
 #include "pf_trim_host.hpp"
@@ -108,7 +109,12 @@ void PrintUsage() {
          << "                  [--report <report.tsv>] on trim and on run STEP... / run --adapters: the read quality report of the reads as they come and as they are kept" << endl
          << "Usage: PloidyFrost qc (-i <a.fq> [-i <b.fq> ...] | -1 <r1.fq> [-1 ...] -2 <r2.fq> [-2 ...]) -o <report.tsv> [--phred 33|64] [--gz | --gz-plain] [--chunk-bytes N] [-v]" << endl
          << "                  (quality and base content by cycle, read lengths, quality and GC histograms and a hint about the quality offset, accumulated on" << endl
-         << "                  the device; one tab-separated text file)" << endl << endl
+         << "                  the device; one tab-separated text file)" << endl
+         << "Usage: PloidyFrost smudge -d <KMCDatabase> (-l L -u U | --auto-cutoffs [-q Q]) -o <out> [-n N] [--pairs <file>] [-v]" << endl
+         << "Usage: PloidyFrost smudge -k 25 [-ci 1 -cs 10000 -cx N] -i <reads.fq> [-i <more.fq> ...] (-l L -u U | --auto-cutoffs [-q Q]) -o <out> [-n N] [--pairs <file>]" << endl
+         << "                  (a Smudgeplot-style check of the estimate: the pairs of k-mers one substitution apart with no other such neighbour, both" << endl
+         << "                  with a count in [L, U], and the table of their two coverages, on the device; <out>_smudge.tsv; -n N: the haploid coverage," << endl
+         << "                  for the summary by AB, AAB, AABB ...; run --smudge [--smudge-n N] [--smudge-pairs <file>] writes it beside the estimate)" << endl << endl
          << "Usage: PloidyFrost build -k 25 [-i] [-d] -r <reads.fq> [-r <more.fq> ...] -o <sample> [-g G] [-t N] [--chunk-bytes N] [--initial-slots N] [-v]" << endl
          << "                  (`Bifrost build -r` on the device: <sample>.gfa, the compacted de Bruijn graph of the reads; -i clips tips, -d deletes" << endl
          << "                  isolated unitigs, both of fewer than k k-mers; single-sample graphs from FASTQ only)" << endl
@@ -815,6 +821,111 @@ int mask_main(int argc, char **argv) {
     return 0;
 }
 
+// `smudge`: the Smudgeplot-style check of the ploidy estimate from the k-mer counts on the device (K-HETPAIR, ../pf_hetpair_rule.hpp)
+int smudge_main(int argc, char **argv) {
+    const char *usage = "Usage:PloidyFrost smudge -d kmc_database (-l L -u U | --auto-cutoffs [-q Q]) -o out [-n N] [--pairs FILE] [-v]\n"
+                        "      PloidyFrost smudge -k 25 [-ci 1 -cs 10000 -cx N] -i reads.fq [-i more.fq ...] (-l L -u U | --auto-cutoffs [-q Q]) -o out [-n N] [--pairs FILE]\n"
+                        "                         [--gz | --gz-plain] [--fasta] [--chunk-bytes N] [--initial-slots N] [-v]";
+    string db, out;
+    CountArgs c;   // -k: the inputs are counted instead of a database read
+    c.opt.ci = 1;  // the workflow's `kmc -ci1 -cs10000`
+    c.opt.cs = 10000;
+    vector<string> inputs;
+    pfh::SmudgeOptions opt;
+    bool l_seen = false, u_seen = false, q_seen = false, n_seen = false, verbose = false;
+    string reads_option;   // the first option that belongs to the count of the inputs
+    long long low = 0, up = 0, n_hap = 0;
+    auto refuse = [&](const string &why) { cerr << "Error: smudge: " << why << endl << usage << endl; return 1; };
+    auto number = [&](const string &o, const char *text, long long &v, long long top) {
+        char *end = nullptr;
+        errno = 0;
+        v = strtoll(text, &end, 10);
+        if (!errno && end != text && !*end && v >= 0 && v <= top) return true;
+        refuse(o + " takes a number from 0 to " + to_string(top) + ", not '" + text + "'");
+        return false;
+    };
+    auto positive = [&](const string &o, const char *text, uint64_t &v) {
+        long long x = 0;
+        if (!number(o, text, x, 0x7FFFFFFFFFFFFFFFll)) return false;
+        if (x < 1) { refuse(o + " takes a positive number"); return false; }
+        v = (uint64_t)x;
+        return true;
+    };
+    for (int i = 2; i < argc; ++i) {
+        const string a = argv[i];
+        {
+            string why;
+            const int taken = take_count_option(argc, argv, i, c, why);
+            if (taken < 0) return refuse(why);
+            if (taken) continue;
+        }
+        const bool has_value = i + 1 < argc;
+        const bool takes_value = a == "-d" || a == "-i" || a == "-o" || a == "-l" || a == "-u" || a == "-q" || a == "-n" || a == "--pairs" || a == "--chunk-bytes" ||
+                                 a == "--initial-slots";
+        if (a == "--auto-cutoffs") opt.auto_cutoffs = true;
+        else if (a == "-v") verbose = true;
+        else if (a == "--gz") { c.opt.gz = std::max(c.opt.gz, 1); if (reads_option.empty()) reads_option = a; }
+        else if (a == "--gz-plain") { c.opt.gz = 2; if (reads_option.empty()) reads_option = a; }
+        else if (a == "--fasta") { c.opt.fasta = true; if (reads_option.empty()) reads_option = a; }
+        else if (!takes_value) return refuse("unknown option " + a);
+        else if (!has_value) return refuse(a + " needs a value");
+        else if (a == "-d") db = argv[++i];
+        else if (a == "-i") { inputs.push_back(argv[++i]); if (reads_option.empty()) reads_option = a; }
+        else if (a == "-o") out = argv[++i];
+        else if (a == "--pairs") opt.pairs = argv[++i];
+        else if (a == "-l") { if (!number(a, argv[++i], low, 0xFFFFFFFFll)) return 1; l_seen = true; }
+        else if (a == "-u") { if (!number(a, argv[++i], up, 0xFFFFFFFFll)) return 1; u_seen = true; }
+        else if (a == "-n") { if (!number(a, argv[++i], n_hap, 0xFFFFFFFFll)) return 1; n_seen = true; }
+        else if (a == "-q") {
+            try { opt.quantile = stod(argv[++i]); } catch (const exception &) { return refuse(string("-q takes a quantile below 1, not '") + argv[i] + "'"); }
+            if (!(opt.quantile > 0) || opt.quantile >= 1) return refuse(string("-q takes a quantile below 1, not '") + argv[i] + "'");
+            q_seen = true;
+        }
+        else if (a == "--chunk-bytes") { if (!positive(a, argv[++i], c.opt.chunk_bytes)) return 1; if (reads_option.empty()) reads_option = a; }
+        else { if (!positive(a, argv[++i], c.opt.initial_slots)) return 1; if (reads_option.empty()) reads_option = a; }
+    }
+    // refused by name, before anything is read or written
+    if (!db.empty() && c.k_seen) return refuse("-d does not go with -k (the database is either read, or counted from the inputs)");
+    if (db.empty() && !c.k_seen) return refuse("-d <KMCDatabase> or -k <k> with -i <reads.fq> is missing");
+    if (!c.k_seen && !c.seen.empty()) return refuse(c.seen + " needs -k (it belongs to the count of the inputs)");
+    if (!c.k_seen && !reads_option.empty()) return refuse(reads_option + " needs -k (it belongs to the count of the inputs)");
+    if (c.k_seen && inputs.empty()) return refuse("-i <reads.fq> is missing");
+    if (out.empty()) return refuse("-o <out> is missing");
+    if ((l_seen || u_seen) && opt.auto_cutoffs) return refuse(string(l_seen ? "-l" : "-u") + " does not go with --auto-cutoffs (the bounds are derived: leave it out)");
+    if (!opt.auto_cutoffs && !(l_seen && u_seen)) return refuse("the bounds are missing: -l L and -u U, or --auto-cutoffs to derive them from the counts");
+    if (q_seen && !opt.auto_cutoffs) return refuse("-q needs --auto-cutoffs (it is the quantile of the derived upper bound)");
+    opt.lo = (uint32_t)low;
+    opt.hi = (uint32_t)up;
+    if (!opt.auto_cutoffs) {
+        if (low < 1) return refuse("-l " + to_string(low) + ": " + pf_hetpair::arg_text(pf_hetpair::ARG_LO_ZERO));
+        if (low > up) return refuse("-l " + to_string(low) + " is above -u " + to_string(up) + " (L > U)");
+        if (up - low + 1 > (long long)pf_hetpair::MAX_W) return refuse("-l " + to_string(low) + " -u " + to_string(up) + ": " + pf_hetpair::arg_text(pf_hetpair::ARG_TOO_WIDE));
+    }
+    if (n_seen && n_hap < 1) return refuse("-n takes a haploid coverage of at least 1");
+    opt.n = (uint64_t)n_hap;
+    if (c.k_seen) {
+        if (!c.opt.both_strands) return refuse("-b: smudge needs canonical counts");
+        const int clause = pfh::count_options_clause(c.opt, false);
+        if (clause) return refuse(pf_count::cut_text(clause));
+    }
+    pfh::SmudgeResult res;
+    string err;
+    const int rc = c.k_seen ? pfh::smudge_counted(c.opt, inputs, opt, out, 0, res, err) : pfh::smudge_db(db, opt, out, 0, res, err);
+    if (rc) {
+        cerr << "Error: " << err << endl;
+        return 1;
+    }
+    if (opt.auto_cutoffs) cout << "lower " << res.lo << " upper " << res.hi << endl;
+    if (res.clamped) cerr << "smudge: the upper bound was lowered to " << res.hi << " (lower + 4095: the table holds 4096 x 4096 cells)" << endl;
+    pf_hetpair::Stats st;
+    st.kmers = res.stats.kmers; st.in_range = res.stats.in_range; st.one_partner = res.stats.one_partner; st.many_partners = res.stats.many_partners;
+    st.pairs = res.stats.pairs;
+    cerr << pf_hetpair::stats_text(st) << endl;
+    if (opt.n) cerr << pf_hetpair::proposed_text(res.summary) << endl;
+    if (verbose) cerr << "smudge: load " << res.times.load_s << "s pairs " << res.times.pairs_s << "s write " << res.times.write_s << "s" << endl;
+    return 0;
+}
+
 // `--adapters FILE [--adapter-seed S] [--adapter-score T] [--adapter-pairs [--adapter-pair-score T] [--adapter-pair-min A]
 // [--adapter-keep-both]]` of `trim`, `run` and `run-multi`: the one place they are parsed
 struct ClipCli {
@@ -1083,7 +1194,8 @@ int run_main(int argc, char **argv) {
                         "      PloidyFrost run [the same options] -i raw.fq [-i more.fq ...] -o sample STEP... [--phred 33|64]\n"
                         "      PloidyFrost run [the same options] -1 r1.fq -2 r2.fq [-1 r3.fq -2 r4.fq ...] -o sample STEP... [--phred 33|64]\n"
                         "      STEP: LEADING:t TRAILING:t SLIDINGWINDOW:w:t MINLEN:l (the raw reads are trimmed on the way in, as `trim` trims them)\n"
-                        "      [--report report.tsv] with STEP... or --adapters: the read quality report `trim --report` writes for the same inputs";
+                        "      [--report report.tsv] with STEP... or --adapters: the read quality report `trim --report` writes for the same inputs\n"
+                        "      [--smudge [--smudge-n N] [--smudge-pairs FILE]]: the k-mer pair report `smudge` writes for the counted k-mers, as PloidyFrost_output/<sample>_smudge.tsv";
     auto refuse = [&](const string &why) { cerr << "Error: run: " << why << endl << usage << endl; return 1; };
     Options lopt;   // the long options of the calling run
     DensityCli dc;
@@ -1147,13 +1259,17 @@ int run_main(int argc, char **argv) {
         if (a == "--fasta") { opt.fasta = true; continue; }
         if (a == "--keep-tips") { opt.clip_tips = false; continue; }
         if (a == "--keep-isolated") { opt.del_isolated = false; continue; }
+        if (a == "--smudge") { opt.smudge = true; continue; }
         const bool takes_value = a == "-i" || a == "-o" || a == "-q" || a == "-u" || a == "-g" || a == "-z" || a == "-M" || a == "-D" || a == "-G" || a == "-t" ||
-                                 a == "--db-out" || a == "--gfa-out" || a == "--chunk-bytes" || a == "--initial-slots" || a == "--report";
+                                 a == "--db-out" || a == "--gfa-out" || a == "--chunk-bytes" || a == "--initial-slots" || a == "--report" || a == "--smudge-n" ||
+                                 a == "--smudge-pairs";
         if (!takes_value) return refuse("unknown option " + a);
         if (i + 1 >= argc) return refuse(a + " needs a value");
         const char *val = argv[++i];
         uint64_t v = 0;
         if (a == "--report") { if (!*val) return refuse("--report needs a value"); opt.report = val; }
+        else if (a == "--smudge-pairs") { if (!*val) return refuse("--smudge-pairs needs a value"); opt.smudge_pairs = val; }
+        else if (a == "--smudge-n") { if (!number(a, val, v, false)) return 1; opt.smudge_n = v; opt.smudge_n_seen = true; }
         else if (a == "-i") inputs.push_back(val);
         else if (a == "-o") out = val;
         else if (a == "--db-out") opt.db_out = val;
@@ -1216,6 +1332,14 @@ int run_main(int argc, char **argv) {
          << st.counted.unique << " lower " << st.lower << " upper " << st.upper << " windows_bad " << st.masked.kmers_bad << " windows_kept " << st.masked.kmers_kept
          << " distinct_kept " << st.distinct_kept << " unitigs " << st.graph.unitigs << " removed " << st.graph.removed << " unitigs_out " << st.graph.unitigs_out
          << " longest " << st.graph.longest << endl;
+    if (opt.smudge) {
+        pf_hetpair::Stats hs;
+        hs.kmers = st.smudge.stats.kmers; hs.in_range = st.smudge.stats.in_range; hs.one_partner = st.smudge.stats.one_partner;
+        hs.many_partners = st.smudge.stats.many_partners; hs.pairs = st.smudge.stats.pairs;
+        cerr << pf_hetpair::stats_text(hs) << endl;
+        if (opt.smudge_n) cerr << pf_hetpair::proposed_text(st.smudge.summary) << endl;
+        if (verbose) cerr << "smudge: pairs " << st.smudge.times.pairs_s << "s (inside run: " << tm.smudge_s << "s)" << endl;
+    }
     if (verbose)
         cerr << "run: count " << tm.count_s << "s finish " << tm.finish_s << "s table " << tm.table_s << "s db-out " << tm.db_out_s << "s recount " << tm.recount_s
              << "s refinish " << tm.refinish_s << "s graph " << tm.graph_s << "s gfa-out " << tm.gfa_out_s << "s load " << tm.load_s << "s call " << tm.call_s << "s" << endl;
@@ -1399,6 +1523,7 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[1], "build-multi")) return build_multi_main(argc, argv);
     if (!strcmp(argv[1], "trim")) return trim_main(argc, argv);
     if (!strcmp(argv[1], "qc")) return qc_main(argc, argv);
+    if (!strcmp(argv[1], "smudge")) return smudge_main(argc, argv);
     if (!strcmp(argv[1], "histogram")) {   // the file `kmc_tools transform <db> histogram <file>` writes, from the database on the device
         string db, out;
         for (int i = 2; i < argc; ++i) {

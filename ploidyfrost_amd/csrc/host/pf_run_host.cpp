@@ -217,6 +217,9 @@ int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<ReadsInput> &
 std::string run_options_refusal(const RunOptions &opt) {
     if (opt.fasta && !opt.report.empty()) return "--fasta does not go with --report (FASTA has no qualities to report)";
     if (!opt.report.empty() && !opt.trim.on()) return "--report needs a step or --adapters in run: ploidyfrost qc reports on files as they are";
+    if (!opt.smudge && opt.smudge_n_seen) return "--smudge-n needs --smudge (it is the haploid coverage of the k-mer pair report)";
+    if (!opt.smudge && !opt.smudge_pairs.empty()) return "--smudge-pairs needs --smudge (it is the pairs file of the k-mer pair report)";
+    if (opt.smudge && opt.smudge_n_seen && opt.smudge_n < 1) return "--smudge-n takes a haploid coverage of at least 1";
     if (opt.fasta && opt.trim.clip.on()) return "--fasta does not go with --adapters (FASTA has no qualities to score an adapter by)";
     if (opt.fasta && (opt.trim.on() || opt.paired)) return "--fasta does not go with trim steps or -1 / -2 (FASTA has no qualities to trim)";
     { const int c = count_options_clause(count_options_of(opt), true); if (c) return pf_count::cut_text(c); }
@@ -249,6 +252,18 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
             if (same_file(o, opt.report)) { err = "run: two outputs have the same path (" + opt.report + ")"; return 1; }
         outputs.push_back(opt.report);
     }
+    // --smudge: the report goes beside the calling run's files, the pairs file where it is asked for
+    const std::string smudge_path = opt.smudge ? "PloidyFrost_output/" + smudge_report_path(out_prefix) : "", smudge_tmp = smudge_path + tail;
+    const std::string pairs_tmp = opt.smudge_pairs + tail;
+    if (opt.smudge) {
+        for (const std::string &p : {smudge_path, opt.smudge_pairs}) {
+            if (p.empty()) continue;
+            for (const std::string &o : outputs)
+                if (o == p || same_file(o, p)) { err = "run: two outputs have the same path (" + p + ")"; return 1; }
+            outputs.push_back(p);
+        }
+    }
+    std::string smudge_text;
     std::vector<ReadsInput> reads;   // what each input is: decided here, once, for both passes
     if (fastq_preflight("run", "read", inputs, outputs, ReadsOptions{opt.gz, opt.fasta}, reads, err)) return 1;
     pf_clip::Adapters adapters;   // --adapters: read and refused here, before a device context exists
@@ -261,12 +276,14 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
     }
     // (the context goes to the loader of the calling run in the end: destroyed here only on the way out before that)
     CtxGuard ctx_guard{ctx};
-    bool db_written = false, gfa_tmp_written = false, report_tmp_written = false;
+    bool db_written = false, gfa_tmp_written = false, report_tmp_written = false, pairs_tmp_written = false, smudge_tmp_written = false;
     auto fail = [&](const std::string &m) {   // nothing is left under any output name after a refusal
         err = m;
         if (db_written) { unlink((opt.db_out + ".kmc_pre").c_str()); unlink((opt.db_out + ".kmc_suf").c_str()); }
         if (gfa_tmp_written) unlink(gfa_tmp.c_str());
         if (report_tmp_written) unlink(report_tmp.c_str());
+        if (pairs_tmp_written) unlink(pairs_tmp.c_str());
+        if (smudge_tmp_written) unlink(smudge_tmp.c_str());
         return 1;
     };
     auto dev_fail = [&]() { return fail(std::string("run: ") + pf_last_error(ctx)); };
@@ -315,9 +332,28 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
         if (pf_upload_counts(ctx, db.kmers, db.counts, db.n, opt.k, opt.ci, opt.cx, 1) != PF_OK)
             return fail(std::string("run: count table of the inputs: ") + pf_last_error(ctx));
         tm.table_s = since(t_table);
+        if (opt.smudge) {   // arrays and table are both alive here: the cross-check costs no pass over the reads
+            const auto t_smudge = clk::now();
+            const uint32_t s_lo = stats.lower, s_hi = (uint32_t)std::min<uint64_t>(stats.upper, (uint64_t)s_lo + pf_hetpair::MAX_W - 1);
+            if (s_lo > stats.upper) return fail("run: --smudge: the lower threshold " + std::to_string(s_lo) + " is above the upper threshold " + std::to_string(stats.upper));
+            if (s_hi != stats.upper)
+                fprintf(stderr, "run: smudge: the upper bound was lowered from %u to %u (lower + 4095: the table holds 4096 x 4096 cells)\n", stats.upper, s_hi);
+            int pairs_fd = -1;
+            if (!opt.smudge_pairs.empty()) {
+                pairs_fd = open(pairs_tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+                if (pairs_fd < 0) return fail("run: cannot write " + pairs_tmp + " (" + strerror(errno) + ")");
+                pairs_tmp_written = true;
+            }
+            std::string e;
+            const int rc = smudge_resident(ctx, "run", db.kmers, db.counts, db.n, opt.k, s_lo, s_hi, opt.smudge_n, pairs_fd, pairs_tmp, stats.smudge, smudge_text, e);
+            if (pairs_fd >= 0 && close(pairs_fd) != 0 && !rc) return fail("run: closing " + pairs_tmp + " (" + strerror(errno) + ")");
+            if (rc) return fail(e);
+            stats.smudge.clamped = s_hi != stats.upper;
+            tm.smudge_s = since(t_smudge);
+        }
         if (!opt.db_out.empty()) {
             const auto t_db = clk::now();
-            if (write_counted(ctx, "run", opt.db_out, db, copt, err)) return 1;
+            if (write_counted(ctx, "run", opt.db_out, db, copt, err)) return fail(err);
             db_written = true;
             tm.db_out_s = since(t_db);
         }
@@ -419,6 +455,16 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
         return fail("run: renaming " + gfa_tmp + " to " + gfa_path + " (" + strerror(errno) + ")");
     if (!opt.report.empty() && rename(report_tmp.c_str(), opt.report.c_str()) != 0)
         return fail("run: renaming " + report_tmp + " to " + opt.report + " (" + strerror(errno) + ")");
+    if (opt.smudge) {   // the directory is the calling run's: it exists by now
+        const int fd = open(smudge_tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (fd < 0) return fail("run: cannot write " + smudge_tmp + " (" + strerror(errno) + ")");
+        smudge_tmp_written = true;
+        if (!write_all(fd, smudge_text.data(), smudge_text.size())) { const int e = errno; close(fd); return fail("run: writing " + smudge_tmp + " (" + strerror(e) + ")"); }
+        if (close(fd) != 0) return fail("run: closing " + smudge_tmp + " (" + strerror(errno) + ")");
+        if (rename(smudge_tmp.c_str(), smudge_path.c_str()) != 0) return fail("run: renaming " + smudge_tmp + " to " + smudge_path + " (" + strerror(errno) + ")");
+        if (!opt.smudge_pairs.empty() && rename(pairs_tmp.c_str(), opt.smudge_pairs.c_str()) != 0)
+            return fail("run: renaming " + pairs_tmp + " to " + opt.smudge_pairs + " (" + strerror(errno) + ")");
+    }
     fflush(stdout);
     if (times) *times = tm;
     return 0;

@@ -23,6 +23,7 @@
 #include "pf_count_host.hpp"
 #include "pf_clip_host.hpp"
 #include "pf_qc_host.hpp"
+#include "pf_hetpair_host.hpp"
 #include "ploidyfrost_hip.h"
 
 namespace pfh {
@@ -115,6 +116,12 @@ struct RunOptions {
     int gz = 0;        // --gz (1), --gz-plain (2: any gzip, K-GUNZIP): inputs with the gzip magic are blocked gzip, inflated on the device in both passes (pf_gz_host.hpp)
     std::string report;   // --report (with opt.trim alone): K-QC's report of both stages over the first pass, the one `trim --report` writes for the same inputs
     bool fasta = false;   // --fasta: a chunk whose first byte is '>' goes through pf_count_fasta / pf_maskcount_fasta in the two passes (K-FASTA); not with trim steps
+    // --smudge [--smudge-n N] [--smudge-pairs FILE]: K-HETPAIR behind the table of the first pass (pf_hetpair_host.hpp), lo = L,
+    // hi = min(U, L + 4095); PloidyFrost_output/<o>_smudge.tsv beside the calling run's files
+    bool smudge = false;
+    uint64_t smudge_n = 0;
+    bool smudge_n_seen = false;
+    std::string smudge_pairs;
 };
 struct RunStats {
     pf_count_stats counted = {};       // the first pass, finished with ci / cx / cs
@@ -126,9 +133,11 @@ struct RunStats {
     std::vector<pf_trim_stats> trim;   // STEP...: the trimming of the first pass (paired: one entry per input file, else one entry)
     std::vector<ClipReport> clip;      // --adapters: the clipping of the first pass, one entry per unit
     QcReport qc;                       // --report: the tables of the first pass
+    SmudgeResult smudge;               // --smudge
 };
 struct RunTimes {
     double count_s = 0, finish_s = 0, table_s = 0, db_out_s = 0, recount_s = 0, refinish_s = 0, graph_s = 0, gfa_out_s = 0, load_s = 0, call_s = 0;
+    double smudge_s = 0;   // --smudge: K-HETPAIR and the report's text
 };
 
 // the refusal of the options that needs no file ("" = none): k outside 5 .. 31 (a database is implied), g, ci / cx / cs

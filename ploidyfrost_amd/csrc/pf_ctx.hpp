@@ -245,6 +245,7 @@ enum WsSlot {
     WS_MASK_TEXT, WS_MASK_OUT, WS_MASK_BITS, WS_MASK_TABLE, WS_MASK_INDEX,   // K-MASK (pf_mask.hip): staged text and output, the four bitmaps, the read table, the FASTQ index
     WS_TRIM_TEXT2, WS_TRIM_INDEX2, WS_TRIM_TABLE2, WS_TRIM_WORK, WS_TRIM_OUT,   // K-TRIM (pf_trim.hip): a pair's second file (text, index, table), intervals / sizes / offsets, the staged outputs
     WS_FASTA_WORK, WS_FASTA_LINES, WS_FASTA_TEXT, WS_FASTA_TABLE,   // K-FASTA (pf_fasta.hip): bitmaps, counts and sums per word; line and header starts; the compacted text; the read table
+    WS_HETPAIR,     // K-HETPAIR (pf_hetpair.hip): staged keys and counters, pair words, offsets, partners, the scan's scratch
     WS_BUB_LANES,   // K-BUBBLE's five launch workspaces (small, retry, scratch, work, idx2) of lanes 1 .. PF_CALL_LANES - 1 (bub_ws)
     WS_COUNT_ = WS_BUB_LANES + 5 * (PF_CALL_LANES - 1)
 };

@@ -48,6 +48,9 @@ K_CLIP = K_DEFLATE + 1         # PF_K_CLIP ("k_clip"): the clipping kernels of o
 K_PALIN = K_CLIP + 1           # PF_K_PALIN ("k_palin"): palindrome mode's kernel of one paired trim / trimmed-count call while a clip with prefix pairs is open; unit: pairs
 K_QC = K_PALIN + 1             # PF_K_QC ("k_qc"): the report kernel of one qc_fastq call, or of one trim / trimmed-count call per file while a report is open; unit: records
 QC_TABLE_WORDS, QC_CLIP_WORDS = 9515, 1025   # PF_QC_TABLE_WORDS, PF_QC_CLIP_WORDS
+K_HETPAIR = K_QC + 1           # PF_K_HETPAIR ("k_hetpair"): everything one pf_hetpairs launches (flag, scan, write, table); unit: keys in range
+HETPAIR_STATS = np.dtype([(f, "<u8") for f in ("kmers", "in_range", "one_partner", "many_partners", "pairs")])   # pf_hetpair_stats
+HETPAIR_MAX_W = 4096           # pf_hetpair::MAX_W: upper - lower + 1 of a table
 CLIP_PAIR_STATS = np.dtype([("pairs_clipped", "<u8"), ("pairs_dropped", "<u8"), ("pairs_too_long", "<u8"), ("candidates_scored", "<u8"),
                             ("bases_clipped", "<u8", (2,))])   # pf_clip_pair_stats
 CLIP_STATS = np.dtype([(f, "<u8", (2,)) for f in ("reads_clipped", "reads_dropped", "bases_clipped", "candidates_scored")])   # pf_clip_stats
@@ -294,6 +297,8 @@ def load_library() -> C.CDLL:
         "pf_qc_clip_get": (i, [vp, i, vp]),
         "pf_qc_fastq": (i, [vp, i, vp, u64, i, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
         "pf_qc_end": (i, [vp]),
+        "pf_hetpairs": (i, [vp, vp, vp, u64, u32, u32, u32, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), vp]),
+        "pf_hetpair_table": (i, [vp, vp, vp, u64, u32, u32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError = header / library mismatch
@@ -326,7 +331,8 @@ DECLARED_SYMBOLS = ["pf_create", "pf_warmup", "pf_destroy", "pf_last_error", "pf
                     "pf_fasta_index", "pf_fasta_index_fetch", "pf_count_fasta", "pf_maskcount_fasta", "pf_color_fasta", "pf_deflate_bgzf",
                     "pf_clip_begin", "pf_clip_stats_get", "pf_clip_end", "pf_clip_last_ends",
                     "pf_clip_begin_pairs", "pf_clip_pair_stats_get",
-                    "pf_qc_begin", "pf_qc_get", "pf_qc_clip_get", "pf_qc_fastq", "pf_qc_end"]
+                    "pf_qc_begin", "pf_qc_get", "pf_qc_clip_get", "pf_qc_fastq", "pf_qc_end",
+                    "pf_hetpairs", "pf_hetpair_table"]
 
 
 class TrimPlan(C.Structure):   # pf_trim_plan
@@ -580,6 +586,50 @@ class Device:
         buf = hist if len(hist) else np.zeros(1, dtype=np.uint64)
         self._check(self.L.pf_count_histogram(self.h, _ptr(counts) if n else None, n, lo, hi, n_bins, _ptr(buf)))
         return hist
+
+    def hetpairs(self, kmers, counts, k: int, lo: int, hi: int, want_pairs: bool = True, want_table: bool = True):
+        """K-HETPAIR (pf_hetpairs; the rule is csrc/pf_hetpair_rule.hpp): the pairs (x, y), x < y, of distinct canonical k-mers one
+        substitution apart, both with a counter in [lo, hi] and neither with another such neighbour, against the resident count table
+        (upload_counts of the same arrays, the same k, both strands).  kmers u64 / counts u32: numpy arrays or device tensors.  Returns
+        a dict: table (W x W uint64, W = hi - lo + 1, table[a - lo, b - lo] = pairs with the counters a <= b; None unless want_table),
+        pair_x, pair_y, cov_x, cov_y (in the order of x in kmers; None unless want_pairs), stats."""
+        if isinstance(kmers, np.ndarray):
+            kmers = np.ascontiguousarray(kmers, dtype=np.uint64)
+        if isinstance(counts, np.ndarray):
+            counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        n = int(kmers.shape[0])
+        W = int(hi) - int(lo) + 1
+        table = np.zeros((W, W), dtype=np.uint64) if want_table and 1 <= W <= HETPAIR_MAX_W else None
+        dummy = np.zeros(1, dtype=np.uint64)   # a refused call never writes it
+        px, py, cx, cy, n_pairs = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64()
+        stats = np.zeros(1, dtype=HETPAIR_STATS)
+        refs = [C.byref(p) if want_pairs else None for p in (px, py, cx, cy)]
+        try:
+            self._check(self.L.pf_hetpairs(self.h, _ptr(kmers) if n else None, _ptr(counts) if n else None, n, int(k), int(lo), int(hi),
+                                           _ptr(table) if table is not None else (_ptr(dummy) if want_table else None), *refs, C.byref(n_pairs),
+                                           stats.ctypes.data))
+            out = {"table": table, "pair_x": None, "pair_y": None, "cov_x": None, "cov_y": None,
+                   "stats": {f: int(stats[0][f]) for f in HETPAIR_STATS.names}}
+            if want_pairs:
+                m = n_pairs.value
+                for name, p, dt in (("pair_x", px, np.uint64), ("pair_y", py, np.uint64), ("cov_x", cx, np.uint32), ("cov_y", cy, np.uint32)):
+                    out[name] = np.zeros(m, dtype=dt)
+                    if m:
+                        self._check(self.L.pf_copy_to_host(self.h, _ptr(out[name]), p, m * out[name].itemsize))
+            return out
+        finally:
+            for p in (px, py, cx, cy):
+                if p.value:
+                    self.L.pf_device_free(self.h, p)
+
+    def hetpair_table(self, cov_x, cov_y, lo: int, hi: int):
+        """The table kernel of K-HETPAIR alone (pf_hetpair_table) over compacted counters in device tensors (int32 / uint32): the
+        W x W uint64 table; pairs with a counter outside [lo, hi] add nothing."""
+        n = int(cov_x.shape[0])
+        W = int(hi) - int(lo) + 1
+        table = np.zeros((max(W, 1), max(W, 1)), dtype=np.uint64)
+        self._check(self.L.pf_hetpair_table(self.h, _ptr(cov_x) if n else None, _ptr(cov_y) if n else None, n, int(lo), int(hi), _ptr(table)))
+        return table
 
     def kernel_time(self, kernel: int):
         """(ms, launches) of one kernel of the enum by number (K_DENSITY, K_HIST, K_MASK: not in KERNELS)"""

@@ -54,7 +54,8 @@ DECLARED_SYMBOLS = ["pfh_open", "pfh_close", "pfh_last_error", "pfh_set_output_d
                     "pfh_reads_adapters", "pfh_reads_adapters_report", "pfh_clip_parse_adapters", "pfh_clip_refusal_text", "pfh_clip_read",
                     "pfh_trim_fastq_chunk_clip", "pfh_reads_adapter_pairs", "pfh_reads_adapters_pair_report", "pfh_clip_parse_adapter_pairs",
                     "pfh_clip_pair", "pfh_trim_fastq_pair_chunk_clip",
-                    "pfh_reads_report", "pfh_qc_fastq", "pfh_qc_fastq_chunk", "pfh_qc_report_text", "pfh_qc_phred_hint"]
+                    "pfh_reads_report", "pfh_qc_fastq", "pfh_qc_fastq_chunk", "pfh_qc_report_text", "pfh_qc_phred_hint",
+                    "pfh_hetpairs_host", "pfh_smudge_report_text", "pfh_smudge_of", "pfh_smudge", "pfh_reads_smudge", "pfh_reads_smudge_result"]
 
 
 class RunOptions(C.Structure):   # pfh_run_options (include/ploidyfrost_host.h)
@@ -290,6 +291,20 @@ def load_library() -> C.CDLL:
                                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.pfh_qc_report_text.restype = C.c_int
     L.pfh_qc_report_text.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.pfh_hetpairs_host.restype = C.c_int
+    L.pfh_hetpairs_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
+    L.pfh_smudge_report_text.restype = C.c_int
+    L.pfh_smudge_report_text.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.pfh_smudge_of.restype = C.c_int
+    L.pfh_smudge_of.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.pfh_smudge.restype = C.c_int
+    L.pfh_smudge.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int,
+                             C.c_double, C.c_uint64, C.c_char_p, C.c_char_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
+    L.pfh_reads_smudge.restype = None
+    L.pfh_reads_smudge.argtypes = [C.c_int, C.c_int64, C.c_char_p]
+    L.pfh_reads_smudge_result.restype = None
+    L.pfh_reads_smudge_result.argtypes = [C.c_void_p]
     L.pfh_qc_phred_hint.restype = C.c_uint32
     L.pfh_qc_phred_hint.argtypes = [C.c_uint64, C.c_uint64]
     L.pfh_reads_adapter_pairs.restype = None
@@ -1001,6 +1016,105 @@ def qc_phred_hint(min_byte: int, reads: int) -> int:
     return int(load_library().pfh_qc_phred_hint(int(min_byte), int(reads)))
 
 
+HETPAIR_STATS_FIELDS = ("kmers", "in_range", "one_partner", "many_partners", "pairs")   # pf_hetpair_stats
+SMUDGE_RESULT = np.dtype([(f, "<u8") for f in HETPAIR_STATS_FIELDS] + [(f, "<u4") for f in ("k", "lower", "upper", "clamped", "proposed_p", "proposed_m")] +
+                         [("proposed_pairs", "<u8"), ("all_pairs", "<u8")])   # pfh_smudge_result
+assert SMUDGE_RESULT.itemsize == 80
+
+
+def hetpairs_host(kmers, counts, k: int, lo: int, hi: int) -> dict:
+    """The rule of K-HETPAIR by the host's plain restatement (pfh_hetpairs_host, csrc/pf_hetpair_rule.hpp; no device): distinct
+    canonical k-mers (u64) and their counters (u32) in; "table" (W x W uint64, W = hi - lo + 1), "pair_x", "pair_y", "cov_x", "cov_y" in
+    the order of x in kmers and "stats" out -- what hipapi.Device.hetpairs returns.  A refused argument raises ValueError by name."""
+    L = load_library()
+    kmers = np.ascontiguousarray(kmers, dtype=np.uint64)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    n = len(kmers)
+    assert len(counts) == n
+    W = int(hi) - int(lo) + 1
+    table = np.zeros((W, W), dtype=np.uint64) if 1 <= W <= 4096 else None
+    stats = np.zeros(len(HETPAIR_STATS_FIELDS), dtype=np.uint64)
+    m = C.c_uint64()
+    cap = n // 2 + 1   # a key is in one pair at most
+    px, py = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint64)
+    cx, cy = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32)
+    if L.pfh_hetpairs_host(kmers.ctypes.data if n else None, counts.ctypes.data if n else None, n, int(k), int(lo), int(hi),
+                           None if table is None else table.ctypes.data, px.ctypes.data, py.ctypes.data, cx.ctypes.data, cy.ctypes.data, cap, C.byref(m),
+                           stats.ctypes.data):
+        raise ValueError(L.pfh_last_error(None).decode())
+    assert m.value <= cap
+    return {"table": table, "pair_x": px[: m.value], "pair_y": py[: m.value], "cov_x": cx[: m.value], "cov_y": cy[: m.value],
+            "stats": {f: int(v) for f, v in zip(HETPAIR_STATS_FIELDS, stats)}}
+
+
+def smudge_report(table, stats, k: int, lo: int, hi: int, n: int = 0) -> bytes:
+    """The report as `smudge` and `run --smudge` write it (pfh_smudge_report_text): a function of the table (W x W), the statistics (a
+    dict of HETPAIR_STATS_FIELDS), k, the bounds and the haploid coverage n (0: none) alone."""
+    L = load_library()
+    W = int(hi) - int(lo) + 1
+    table = np.ascontiguousarray(table, dtype=np.uint64).reshape(max(W, 1), max(W, 1))
+    st = np.array([int(stats[f]) for f in HETPAIR_STATS_FIELDS], dtype=np.uint64)
+    ln = C.c_uint64()
+    if L.pfh_smudge_report_text(table.ctypes.data, st.ctypes.data, int(k), int(lo), int(hi), int(n), None, 0, C.byref(ln)):
+        raise ValueError(L.pfh_last_error(None).decode())
+    buf = C.create_string_buffer(max(ln.value, 1))
+    L.pfh_smudge_report_text(table.ctypes.data, st.ctypes.data, int(k), int(lo), int(hi), int(n), buf, ln.value, C.byref(ln))
+    return buf.raw[: ln.value]
+
+
+def smudge_of(a: int, b: int, n: int):
+    """(p, m, label) of a pair with the coverages a <= b at the haploid coverage n (pfh_smudge_of): p - m letters A, m letters B"""
+    L = load_library()
+    p, m = C.c_uint32(), C.c_uint32()
+    if L.pfh_smudge_of(int(a), int(b), int(n), C.byref(p), C.byref(m)):
+        raise ValueError(L.pfh_last_error(None).decode())
+    return p.value, m.value, "A" * (p.value - m.value) + "B" * m.value
+
+
+def _set_smudge(L, smudge, smudge_n, smudge_pairs):
+    """`--smudge [--smudge-n N] [--smudge-pairs FILE]` of the next run call (pfh_reads_smudge)"""
+    L.pfh_reads_smudge(int(bool(smudge)), -1 if smudge_n is None else int(smudge_n), None if smudge_pairs is None else os.fsencode(smudge_pairs))
+
+
+def _smudge_result(r) -> dict:
+    d = {f: int(r[0][f]) for f in SMUDGE_RESULT.names}
+    d["stats"] = {f: d.pop(f) for f in HETPAIR_STATS_FIELDS}
+    return d
+
+
+def smudge(out: str, db=None, inputs=None, lower=None, upper=None, auto: bool = False, q: float = 0.998, n=None, pairs=None, k: int = 25,
+           ci: int = 1, cx: int = 10 ** 9, cs: int = 10000, chunk_bytes: int = 0, initial_slots: int = 0, gz: bool = False, fasta: bool = False) -> dict:
+    """`ploidyfrost smudge` (pfh_smudge): the k-mer pair report <out>_smudge.tsv from a KMC database (db) or from reads counted first
+    (inputs, with k, ci, cx, cs) -- K-HETPAIR over the count table on the device.  lower and upper, or auto=True (what `cutoffL -d` and
+    `cutoffU -d q` print); n: the haploid coverage for the summary; pairs: a path for the pairs file.  Returns "stats", the bounds used
+    ("lower", "upper", "clamped") and with n the proposed ploidy.  A refusal raises RuntimeError by name; nothing is left under an
+    output name."""
+    L = load_library()
+    if (db is None) == (inputs is None):
+        raise ValueError("smudge: either db or inputs")
+    if auto == (lower is not None or upper is not None) or (not auto and (lower is None or upper is None)):
+        raise ValueError("smudge: either lower=L and upper=U or auto=True")
+    if n is not None and int(n) < 1:
+        raise ValueError("smudge: n is a haploid coverage of at least 1")
+    paths, n_in = _paths(inputs if inputs is not None else [])
+    res = np.zeros(1, dtype=SMUDGE_RESULT)
+    L.pfh_reads_gz(_gz_mode(gz))
+    L.pfh_reads_fasta(int(bool(fasta)))
+    rc = L.pfh_smudge(None if db is None else os.fsencode(db), paths, n_in, int(k), int(ci), int(cx), int(cs), 0 if lower is None else int(lower),
+                      0 if upper is None else int(upper), int(auto), float(q), 0 if n is None else int(n), None if pairs is None else os.fsencode(pairs),
+                      os.fsencode(out), int(chunk_bytes), int(initial_slots), 0, res.ctypes.data)
+    if rc:
+        raise (ReadsRefused if gz else RuntimeError)(L.pfh_last_error(None).decode())
+    return _smudge_result(res)
+
+
+def smudge_result() -> dict:
+    """What the last run_reads(..., smudge=True) of this thread found (pfh_reads_smudge_result)"""
+    res = np.zeros(1, dtype=SMUDGE_RESULT)
+    load_library().pfh_reads_smudge_result(res.ctypes.data)
+    return _smudge_result(res)
+
+
 def trim_fastq(inputs, out: str, steps, phred: int = 33, trimlog=None, chunk_bytes: int = 0, gz: bool = False, gz_out: bool = False,
                adapters=None, adapter_seed: int = 2, adapter_score: int = 10, report=None) -> dict:
     """`ploidyfrost trim -i ... -o out STEP...` (pfh_trim_fastq): the reads of the FASTQ file(s) `inputs`, one after the other,
@@ -1193,7 +1307,8 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
               threads: int = 1, model=None, model_only: bool = False, db_out=None, gfa_out=None, chunk_bytes: int = 0,
               initial_slots: int = 0, steps=None, phred: int = 33, pairs=None, gz: bool = False, fasta: bool = False,
               adapters=None, adapter_seed: int = 2, adapter_score: int = 10, adapter_pairs: bool = False, adapter_pair_score: int = 30,
-              adapter_pair_min: int = 8, adapter_keep_both: bool = False, report=None) -> dict:
+              adapter_pair_min: int = 8, adapter_keep_both: bool = False, report=None, smudge: bool = False, smudge_n=None,
+              smudge_pairs=None) -> dict:
     """`ploidyfrost run` (pfh_run_fastq): reads to ploidy estimate in one process -- the FASTQ file(s) `inputs` counted, the thresholds
     derived, the k-mers of the masked reads counted (K-MASKCOUNT), the graph built and the single-sample calling run made on one device
     context; PloidyFrost_output/<out_prefix>_*.txt in the working directory.  model: None, "cov" or "fre".  Returns the fields of the
@@ -1210,7 +1325,9 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
     trim_fastq_pair takes it; refused by name without pairs.  Only pairs of which both records are kept go on, so without
     adapter_keep_both a clipped pair is not counted at all.
     report (`--report`): the report `trim_fastq(..., report=)` writes for the same inputs, taken over the first pass; refused by name
-    without steps or adapters."""
+    without steps or adapters.
+    smudge (`--smudge`, with smudge_n and smudge_pairs): the k-mer pair report PloidyFrost_output/<out_prefix>_smudge.tsv from the table
+    of the first pass (K-HETPAIR), every other output being what it is without; the result then has "smudge" (smudge_result())."""
     L = load_library()
     if pairs is not None:
         if inputs is not None:
@@ -1239,15 +1356,20 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
         L.pfh_reads_gz(_gz_mode(gz))
         L.pfh_reads_fasta(int(bool(fasta)))
         _set_report(L, report)
+        _set_smudge(L, smudge, smudge_n, smudge_pairs)
         rc = L.pfh_run_fastq(paths, n, os.fsencode(out_prefix), C.byref(o), 0, stats.ctypes.data)
         if rc:
             raise (ReadsRefused if gz else RuntimeError)(L.pfh_last_error(None).decode())
-        return {f: int(v) for f, v in zip(RUN_STATS_FIELDS, stats)}
+        out = {f: int(v) for f, v in zip(RUN_STATS_FIELDS, stats)}
+        if smudge:
+            out["smudge"] = smudge_result()
+        return out
     per = np.zeros((max(n, 1), len(TRIM_STATS_FIELDS)), dtype=np.uint64)
     L.pfh_reads_gz(_gz_mode(gz))
     L.pfh_reads_fasta(int(bool(fasta)))
     _set_adapters(L, adapters, adapter_seed, adapter_score, adapter_pairs, adapter_pair_score, adapter_pair_min, adapter_keep_both)
     _set_report(L, report)
+    _set_smudge(L, smudge, smudge_n, smudge_pairs)
     rc = L.pfh_run_fastq_trimmed(paths, n, int(pairs is not None), st.ctypes.data if len(st) else None, len(st), int(phred), os.fsencode(out_prefix),
                                  C.byref(o), 0, stats.ctypes.data, per.ctypes.data)
     if rc:
@@ -1255,6 +1377,8 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
     out = {f: int(v) for f, v in zip(RUN_STATS_FIELDS, stats)}
     rows = [{f: int(v) for f, v in zip(TRIM_STATS_FIELDS, row)} for row in per]
     out["trim"] = [rows[0]] if pairs is None else [[rows[2 * u], rows[2 * u + 1]] for u in range(len(pairs))]
+    if smudge:
+        out["smudge"] = smudge_result()
     return out
 
 
