@@ -31,21 +31,17 @@
 #include <vector>
 
 #include "pf_cdbg.hpp"
+#include "pf_cli_subs.hpp"
 #include "pf_cutoffs.hpp"
-#include "pf_count_host.hpp"
-#include "pf_build_host.hpp"
-#include "pf_mask_host.hpp"
-#include "pf_hetpair_host.hpp"
 #include "pf_run_host.hpp"
 #include "pf_runmulti_host.hpp"
-#include "pf_trim_host.hpp"
-#include "../pf_trim_rule.hpp"
 #include "pf_filter.hpp"
 #include "pf_multi.hpp"
 #include "pf_gmm_model.hpp"
 #include "ploidyfrost_hip.h"
 
 using namespace std;
+using namespace pfcli;
 
 namespace {
 void PrintUsage() {
@@ -186,23 +182,6 @@ vector<uint64_t> database_rows(const string &db, uint64_t *min_count = nullptr) 
     return rows;
 }
 
-struct Options {
-    string graphfile, colorfile, outprefix = "output", db, coveragefile, hist;
-    size_t nb_threads = 1, complex_size = 8, ref_threads = 1, gpus = 1;
-    bool verbose = false, info = false, detach_teardown = false, gpus_seen = false;
-    int coverage_lower = 10, coverage_upper = 1000, k = 25;
-    vector<pair<int, int>> coverage_vec;
-    double match = 2, mismatch = -1, gap = -3, frequency = 0.998;
-    // --model ...: the estimate in the same run
-    string model_source, model_ploidy = "1:9";
-    bool model_only = false, model_option_seen = false, filter_seen = false, multi_seen = false, each_color = false;
-    bool auto_cutoffs = false, l_seen = false, u_seen = false, cfile_seen = false;   // --auto-cutoffs and what it does not go with
-    string filter_words;   // --filter "<options of `ploidyfrost filter`>"
-    string multi_words;    // --filter-multi "<options of `ploidyfrost filter-multi`>"
-    double model_q = 0, model_m = 5.0, model_n = 2.0, model_delta = 0.01;
-    int model_iter = 1000;
-};
-
 bool file_exists(const string &p) {
     struct stat sb;
     return stat(p.c_str(), &sb) == 0;
@@ -267,48 +246,6 @@ bool refuse_each_color_with_one(const pf_filter_multi_opts &m) {
     cerr << "Error: --model-each-color fits every colour: --filter-multi holds -c " << m.color << " (one colour: leave --model-each-color out)" << endl;
     return true;
 }
-
-// --density [--density-points N] [--density-adjust A]: the words as given, checked before anything is read or written
-struct DensityCli {
-    bool on = false, points_seen = false, adjust_seen = false;
-    string points_word, adjust_word;
-    unsigned points = 512;
-    double adjust = 1.0;
-    // takes argv[i] (and its value) when it is one of the three switches: 0 = not one of them, else the number of words taken
-    int take(int argc, char **argv, int i) {
-        if (strcmp(argv[i], "--density") == 0) { on = true; return 1; }
-        const bool p = strcmp(argv[i], "--density-points") == 0, a = strcmp(argv[i], "--density-adjust") == 0;
-        if ((p || a) && i + 1 < argc) {
-            (p ? points_seen : adjust_seen) = true;
-            (p ? points_word : adjust_word) = argv[i + 1];
-            return 2;
-        }
-        return 0;
-    }
-    // false: refused, one line on stderr
-    bool check(const char *points_name = "--density-points", const char *adjust_name = "--density-adjust") {
-        if ((points_seen || adjust_seen) && !on) { cerr << "Error: --density-points / --density-adjust need --density" << endl; return false; }
-        if (points_seen) {
-            char *end = nullptr;
-            const long v = strtol(points_word.c_str(), &end, 10);
-            if (end == points_word.c_str() || *end != 0 || v < PF_DENSITY_MIN_POINTS || v > PF_DENSITY_MAX_POINTS) {
-                cerr << "Error: " << points_name << " " << points_word << ": grid points from " << PF_DENSITY_MIN_POINTS << " to " << PF_DENSITY_MAX_POINTS << endl;
-                return false;
-            }
-            points = (unsigned)v;
-        }
-        if (adjust_seen) {
-            char *end = nullptr;
-            const double v = strtod(adjust_word.c_str(), &end);
-            if (end == adjust_word.c_str() || *end != 0 || !std::isfinite(v) || !(v > 0)) {
-                cerr << "Error: " << adjust_name << " " << adjust_word << ": the bandwidth factor is a finite positive number" << endl;
-                return false;
-            }
-            adjust = v;
-        }
-        return true;
-    }
-};
 
 // the density of the values `model` has on the device, written beside its result: 0 = ok, 2 = fewer than two values
 int density_of(pfh::GmmModel &model, const DensityCli &dc, const string &outprefix, string &err) {
@@ -534,981 +471,10 @@ int model_main(int argc, char **argv) {
 }
 }  // namespace
 
-// kmc's letters of `count` and `mask -k`, with a detached or an attached value (-k 25, -k25, -ci1, -cs10000), and -b
-struct CountArgs {
-    pfh::CountOptions opt;
-    string seen;   // the first of -ci -cx -cs -b that was given ("" = none)
-    bool k_seen = false;
-};
-// 0 = argv[i] is none of them, 1 = taken (i stands on its last word), -1 = refused with `why`
-int take_count_option(int argc, char **argv, int &i, CountArgs &c, string &why) {
-    const string a = argv[i];
-    if (a == "-b") { c.opt.both_strands = false; if (c.seen.empty()) c.seen = "-b"; return 1; }
-    string name;
-    for (const char *o : {"-ci", "-cx", "-cs", "-k"})
-        if (a.compare(0, strlen(o), o) == 0 && (a.size() == strlen(o) || isdigit((unsigned char)a[strlen(o)]))) { name = o; break; }
-    if (name.empty()) return 0;
-    string text = a.substr(name.size());
-    if (text.empty()) {
-        if (i + 1 >= argc) { why = name + " needs a value"; return -1; }
-        text = argv[++i];
-    }
-    char *end = nullptr;
-    errno = 0;
-    unsigned long long v = strtoull(text.c_str(), &end, 10);
-    if (!isdigit((unsigned char)text[0]) || *end) { why = name + " takes a number, not '" + text + "'"; return -1; }
-    if (errno == ERANGE) v = pf_count::COUNTER_MAX + 1;   // (refused with the cut-offs, by name)
-    if (name == "-k") { c.opt.k = (uint32_t)std::min<unsigned long long>(v, 0xFFFFFFFFull); c.k_seen = true; return 1; }
-    (name == "-ci" ? c.opt.ci : name == "-cx" ? c.opt.cx : c.opt.cs) = v;
-    if (c.seen.empty()) c.seen = name;
-    return 1;
-}
-
-// `count`: step `2.kmc_db` of the reference's workflow (`kmc -ci1 -cs10000 -k25 @FILES kmc_sample tmp`) on the device
-int count_main(int argc, char **argv) {
-    const char *usage = "Usage:PloidyFrost count -k 25 -ci 1 -cs 10000 [-cx N] [-b] -i reads.fq [-i more.fq ...] -o kmc_database [--hist file] [--chunk-bytes N] [--initial-slots N] [--gz] [--gz-plain] [--fasta] [-v]";
-    CountArgs c;
-    string out;
-    vector<string> inputs;
-    bool verbose = false;
-    auto refuse = [&](const string &why) { cerr << "Error: count: " << why << endl << usage << endl; return 1; };
-    auto number = [&](const string &opt, const char *text, uint64_t &v) {
-        char *end = nullptr;
-        errno = 0;
-        v = strtoull(text, &end, 10);
-        if (!errno && isdigit((unsigned char)text[0]) && !*end && v > 0) return true;
-        refuse(opt + " takes a positive number, not '" + text + "'");
-        return false;
-    };
-    for (int i = 2; i < argc; ++i) {
-        const string a = argv[i];
-        string why;
-        const int taken = take_count_option(argc, argv, i, c, why);
-        if (taken < 0) return refuse(why);
-        if (taken) continue;
-        const bool has_value = i + 1 < argc;
-        if (a == "-v") verbose = true;
-        else if (a == "--gz") c.opt.gz = std::max(c.opt.gz, 1);
-        else if (a == "--gz-plain") c.opt.gz = 2;
-        else if (a == "--fasta") c.opt.fasta = true;
-        else if (!has_value) return refuse(a == "-i" || a == "-o" || a == "--hist" || a == "--chunk-bytes" || a == "--initial-slots" ? a + " needs a value" : "unknown option " + a);
-        else if (a == "-i") inputs.push_back(argv[++i]);
-        else if (a == "-o") out = argv[++i];
-        else if (a == "--hist") c.opt.hist = argv[++i];
-        else if (a == "--chunk-bytes") { if (!number(a, argv[++i], c.opt.chunk_bytes)) return 1; }
-        else if (a == "--initial-slots") { if (!number(a, argv[++i], c.opt.initial_slots)) return 1; }
-        else return refuse("unknown option " + a);
-    }
-    // refused by name, before anything is read or written
-    if (inputs.empty()) return refuse("-i <reads.fq> is missing");
-    if (out.empty()) return refuse("-o <KMCDatabase> is missing");
-    { const int clause = pfh::count_options_clause(c.opt, true); if (clause) return refuse(pf_count::cut_text(clause)); }
-    pf_count_stats st = {};
-    pfh::CountTimes tm;
-    string err;
-    if (pfh::count_fastq(inputs, out, c.opt, 0, st, &tm, err)) {
-        cerr << "Error: " << err << endl;
-        return 1;
-    }
-    cerr << "count: reads " << st.reads << " bases " << st.bases << " kmers " << st.kmers << " bad " << st.kmers_bad << " unique " << st.unique << " below "
-         << st.below_min << " above " << st.above_max << " written " << st.written << endl;
-    if (verbose) cerr << "count: stream " << tm.stream_s << "s finish " << tm.finish_s << "s write " << tm.write_s << "s" << endl;
-    return 0;
-}
-
-// `build`: step `4.bifrost` of the reference's workflow (`Bifrost build -i -d -k 25 -r sample_filtered.fq -o sample`) on the device.  The
-// letters are Bifrost's: -i clips tips here, the reads come with -r.
-int build_main(int argc, char **argv) {
-    const char *usage = "Usage:PloidyFrost build -k 25 [-i] [-d] -r reads.fq [-r more.fq ...] -o sample [-g G] [-t N] [--chunk-bytes N] [--initial-slots N] [--fasta] [-v]";
-    pfh::BuildOptions opt;
-    string out;
-    vector<string> inputs;
-    bool verbose = false;
-    auto refuse = [&](const string &why) { cerr << "Error: build: " << why << endl << usage << endl; return 1; };
-    auto number = [&](const string &o, const char *text, uint64_t &v) {
-        char *end = nullptr;
-        errno = 0;
-        v = strtoull(text, &end, 10);
-        if (!errno && isdigit((unsigned char)text[0]) && !*end && v > 0) return true;
-        refuse(o + " takes a positive number, not '" + text + "'");
-        return false;
-    };
-    static const char *const not_built[] = {"-s", "-c", "-y", "-f", "-a", "-m", "-n", "-b", "-B", "-l", "-w", "-e"};
-    for (int i = 2; i < argc; ++i) {
-        const string a = argv[i];
-        for (const char *nb : not_built)
-            if (a == nb) return refuse(a + " is not built (a single-sample graph of the reads given with -r, written as GFA, is all there is)" +
-                                       (a == "-c" ? "; the coloured graph of several samples: `build-multi`" : ""));
-        if (a == "--gpus") return refuse("--gpus is not built: the graph is made on one GPU");
-        if (a == "-i") { opt.clip_tips = true; continue; }
-        if (a == "-d") { opt.del_isolated = true; continue; }
-        if (a == "-v") { verbose = true; continue; }
-        if (a == "--fasta") { opt.fasta = true; continue; }
-        const bool takes_value = a == "-k" || a == "-g" || a == "-t" || a == "-r" || a == "-o" || a == "--chunk-bytes" || a == "--initial-slots";
-        if (!takes_value) return refuse("unknown option " + a);
-        if (i + 1 >= argc) return refuse(a + " needs a value");
-        const char *val = argv[++i];
-        uint64_t v = 0;
-        if (a == "-r") inputs.push_back(val);
-        else if (a == "-o") out = val;
-        else if (!number(a, val, v)) return 1;
-        else if (a == "-k") opt.k = (uint32_t)std::min<uint64_t>(v, 0xFFFFFFFFull);
-        else if (a == "-g") opt.g = (int)std::min<uint64_t>(v, 0x7FFFFFFFull);
-        else if (a == "--chunk-bytes") opt.chunk_bytes = v;
-        else if (a == "--initial-slots") opt.initial_slots = v;
-        // (-t: accepted and ignored)
-    }
-    // refused by name, before anything is read or written
-    if (inputs.empty()) return refuse("-r <reads.fq> is missing");
-    if (out.empty()) return refuse("-o <sample> is missing");
-    { const string why = pfh::build_options_refusal(opt); if (!why.empty()) return refuse(why); }
-    pf_count_stats cst = {};
-    pf_unitig_stats st = {};
-    pfh::BuildTimes tm;
-    string err;
-    if (pfh::build_fastq(inputs, out, opt, 0, cst, st, &tm, err)) {
-        cerr << "Error: " << err << endl;
-        return 1;
-    }
-    cerr << "build: reads " << cst.reads << " bases " << cst.bases << " kmers " << cst.kmers << " bad " << cst.kmers_bad << " distinct " << st.distinct
-         << " unitigs " << st.unitigs << " removed " << st.removed << " unitigs_out " << st.unitigs_out << " longest " << st.longest << " bytes " << st.bytes
-         << (st.distinct == 0 ? " (no k-mer in the input: the header line alone is written)" : "") << endl;
-    if (verbose) {
-        cerr << "build: stream " << tm.stream_s << "s finish " << tm.finish_s << "s graph " << tm.graph_s << "s write " << tm.write_s << "s; device ms: index "
-             << st.stage_ms[0] << " adjacency " << st.stage_ms[1] << " simplify " << st.stage_ms[2] << " rank " << st.stage_ms[3] << " (" << st.rounds
-             << " rounds) cycles " << st.stage_ms[4] << " (" << st.cycles << " closed, " << st.cycle_rounds << " rounds) emit " << st.stage_ms[5] << endl;
-    }
-    return 0;
-}
-
-// `build-multi`: the last step of the reference's multi-sample workflow (`Bifrost build -i -d -k 25 -r s0.fq -r s1.fq ... -c -o sample`)
-// on the device: the graph of `build` from all files together, and the colour file with one colour per -r in the order given.
-int build_multi_main(int argc, char **argv) {
-    const char *usage = "Usage:PloidyFrost build-multi -k 25 [-i] [-d] -r s0.fq -r s1.fq [-r ...] -o sample [-g G] [-t N] [--chunk-bytes N] [--initial-slots N] [--fasta] [-v]";
-    pfh::BuildOptions opt;
-    string out;
-    vector<string> inputs;
-    bool verbose = false;
-    auto refuse = [&](const string &why) { cerr << "Error: build-multi: " << why << endl << usage << endl; return 1; };
-    auto number = [&](const string &o, const char *text, uint64_t &v) {
-        char *end = nullptr;
-        errno = 0;
-        v = strtoull(text, &end, 10);
-        if (!errno && isdigit((unsigned char)text[0]) && !*end && v > 0) return true;
-        refuse(o + " takes a positive number, not '" + text + "'");
-        return false;
-    };
-    static const char *const not_built[] = {"-s", "-y", "-f", "-a", "-m", "-n", "-b", "-B", "-l", "-w", "-e"};
-    for (int i = 2; i < argc; ++i) {
-        const string a = argv[i];
-        for (const char *nb : not_built)
-            if (a == nb) return refuse(a + " is not built (the coloured graph of the reads given with -r, one colour a file, is all there is)");
-        if (a == "--gpus") return refuse("--gpus is not built: the graph is made on one GPU");
-        if (a == "-i") { opt.clip_tips = true; continue; }
-        if (a == "-d") { opt.del_isolated = true; continue; }
-        if (a == "-v") { verbose = true; continue; }
-        if (a == "-c") continue;   // (Bifrost's letter for what this sub-command always does)
-        if (a == "--fasta") { opt.fasta = true; continue; }
-        const bool takes_value = a == "-k" || a == "-g" || a == "-t" || a == "-r" || a == "-o" || a == "--chunk-bytes" || a == "--initial-slots";
-        if (!takes_value) return refuse("unknown option " + a);
-        if (i + 1 >= argc) return refuse(a + " needs a value");
-        const char *val = argv[++i];
-        uint64_t v = 0;
-        if (a == "-r") inputs.push_back(val);
-        else if (a == "-o") out = val;
-        else if (!number(a, val, v)) return 1;
-        else if (a == "-k") opt.k = (uint32_t)std::min<uint64_t>(v, 0xFFFFFFFFull);
-        else if (a == "-g") opt.g = (int)std::min<uint64_t>(v, 0x7FFFFFFFull);
-        else if (a == "--chunk-bytes") opt.chunk_bytes = v;
-        else if (a == "--initial-slots") opt.initial_slots = v;
-        // (-t: accepted and ignored)
-    }
-    // refused by name, before anything is read or written
-    if (inputs.empty()) return refuse("-r <reads.fq> is missing");
-    if (out.empty()) return refuse("-o <sample> is missing");
-    { const string why = pfh::build_options_refusal(opt); if (!why.empty()) return refuse(why); }
-    { const string why = pfh::colored_inputs_refusal(inputs); if (!why.empty()) return refuse(why); }
-    pf_count_stats cst = {};
-    pf_unitig_stats st = {};
-    pf_color_stats col = {};
-    uint64_t color_bytes = 0;
-    pfh::ColoredTimes tm;
-    string err;
-    if (pfh::build_colored_fastq(inputs, out, opt, 0, 0, cst, st, col, color_bytes, &tm, err)) {
-        cerr << "Error: " << err << endl;
-        return 1;
-    }
-    cerr << "build-multi: colors " << col.colors << " reads " << cst.reads << " bases " << cst.bases << " kmers " << cst.kmers << " bad " << cst.kmers_bad
-         << " distinct " << st.distinct << " unitigs " << st.unitigs << " removed " << st.removed << " unitigs_out " << st.unitigs_out << " longest "
-         << st.longest << " bytes " << st.bytes << " windows_colored " << col.windows_colored << " windows_unplaced " << col.windows_unplaced << " runs "
-         << col.runs << " overflow " << col.overflow << " color_bytes " << color_bytes << endl;
-    if (verbose) {
-        cerr << "build-multi: stream " << tm.build.stream_s << "s finish " << tm.build.finish_s << "s graph " << tm.build.graph_s << "s color " << tm.color_s
-             << "s serialise " << tm.serialise_s << "s write " << tm.build.write_s << "s; device ms: index " << st.stage_ms[0] << " adjacency " << st.stage_ms[1]
-             << " simplify " << st.stage_ms[2] << " rank " << st.stage_ms[3] << " cycles " << st.stage_ms[4] << " emit " << st.stage_ms[5] << " table "
-             << col.table_ms << " mark " << col.mark_ms << " runs " << col.runs_ms << endl;
-    }
-    return 0;
-}
-
-// `mask`: step 2 of the reference's workflow (`kmc_tools filter -hm <db> <reads.fq> -ci<L> <out.fq>`) against the database on the device
-int mask_main(int argc, char **argv) {
-    // (the short form: `--gz-out`, blocked-gzip output, stands in the overall usage)
-    const char *usage = "Usage:PloidyFrost mask -d kmc_database -i reads.fq [-i more.fq ...] -o out.fq (-l L | --auto-cutoffs) [-u U] [--chunk-bytes N] [-v]";
-    string db, out, db_out;
-    CountArgs c;   // -k: the inputs are counted instead of a database read
-    vector<string> inputs;
-    bool l_seen = false, auto_cutoffs = false, verbose = false, gz_out = false;
-    long long low = 0, up = 0xFFFFFFFFll, chunk = 0;
-    auto refuse = [&](const string &why) { cerr << "Error: mask: " << why << endl << usage << endl; return 1; };
-    auto number = [&](const char *opt, const char *text, long long &v) {
-        char *end = nullptr;
-        errno = 0;
-        v = strtoll(text, &end, 10);
-        if (!errno && end != text && !*end && v >= 0 && v <= 0xFFFFFFFFll) return true;
-        refuse(string(opt) + " takes a number from 0 to 4294967295, not '" + text + "'");
-        return false;
-    };
-    for (int i = 2; i < argc; ++i) {
-        const string a = argv[i];
-        {
-            string why;
-            const int taken = take_count_option(argc, argv, i, c, why);
-            if (taken < 0) return refuse(why);
-            if (taken) continue;
-        }
-        const bool has_value = i + 1 < argc;
-        if (a == "--auto-cutoffs") auto_cutoffs = true;
-        else if (a == "--gz-out") gz_out = true;
-        else if (a == "--fasta") return refuse("--fasta is not built into mask: the masked output has the input's layout (count, build, build-multi, run and run-multi take FASTA)");
-        else if (a == "-v") verbose = true;
-        else if (!has_value) return refuse(a == "-d" || a == "-i" || a == "-o" || a == "-l" || a == "-u" || a == "--chunk-bytes" || a == "--db-out" ? a + " needs a value" : "unknown option " + a);
-        else if (a == "-d") db = argv[++i];
-        else if (a == "--db-out") db_out = argv[++i];
-        else if (a == "-i") inputs.push_back(argv[++i]);
-        else if (a == "-o") out = argv[++i];
-        else if (a == "-l") { if (!number("-l", argv[++i], low)) return 1; l_seen = true; }
-        else if (a == "-u") { if (!number("-u", argv[++i], up)) return 1; }
-        else if (a == "--chunk-bytes") { if (!number("--chunk-bytes", argv[++i], chunk)) return 1; if (!chunk) return refuse("--chunk-bytes takes a positive number"); }
-        else return refuse("unknown option " + a);
-    }
-    // refused by name, before anything is read or written
-    if (!db.empty() && c.k_seen) return refuse("-d does not go with -k (the database is either read, or counted from the inputs)");
-    if (!c.k_seen && !c.seen.empty()) return refuse(c.seen + " needs -k (it belongs to the count of the inputs)");
-    if (!c.k_seen && !db_out.empty()) return refuse("--db-out needs -k (it belongs to the count of the inputs)");
-    if (db.empty() && !c.k_seen) return refuse("-d <KMCDatabase> is missing");
-    if (inputs.empty()) return refuse("-i <reads.fq> is missing");
-    if (out.empty()) return refuse("-o <out.fq> is missing");
-    if (l_seen && auto_cutoffs) return refuse("-l does not go with --auto-cutoffs (the lower threshold is derived: leave it out)");
-    if (!l_seen && !auto_cutoffs) return refuse("the lower threshold is missing: -l L, or --auto-cutoffs to derive it from the database");
-    if (l_seen && low > up) return refuse("-l " + to_string(low) + " is above -u " + to_string(up) + " (L > U)");
-    if (c.k_seen) { const int clause = pfh::count_options_clause(c.opt, !db_out.empty()); if (clause) return refuse(pf_count::cut_text(clause)); }
-    pf_mask_stats st = {};
-    uint32_t lower = (uint32_t)low;
-    pfh::MaskTimes tm;
-    string err;
-    const int rc = c.k_seen ? pfh::mask_fastq_counted(c.opt, db_out, inputs, out, (uint32_t)low, (uint32_t)up, auto_cutoffs, (uint64_t)chunk, 0, st, lower, &tm, err, gz_out)
-                            : pfh::mask_fastq(db, inputs, out, (uint32_t)low, (uint32_t)up, auto_cutoffs, (uint64_t)chunk, 0, st, lower, &tm, err, gz_out);
-    if (rc) {
-        cerr << "Error: " << err << endl;
-        return 1;
-    }
-    if (auto_cutoffs) cout << lower << endl;   // exactly as `cutoffL -d` prints it
-    cerr << "mask: reads " << st.reads << " changed " << st.reads_changed << " bases " << st.bases << " masked " << st.bases_masked << " kmers " << st.kmers
-         << " bad " << st.kmers_bad << endl;
-    if (verbose)
-        cerr << "mask: load " << tm.load_s << "s stream " << tm.stream_s << "s (device " << tm.device_s << "s, read " << tm.read_s << "s, write " << tm.write_s << "s)" << endl;
-    return 0;
-}
-
-// `smudge`: the Smudgeplot-style check of the ploidy estimate from the k-mer counts on the device (K-HETPAIR, ../pf_hetpair_rule.hpp)
-int smudge_main(int argc, char **argv) {
-    const char *usage = "Usage:PloidyFrost smudge -d kmc_database (-l L -u U | --auto-cutoffs [-q Q]) -o out [-n N] [--pairs FILE] [-v]\n"
-                        "      PloidyFrost smudge -k 25 [-ci 1 -cs 10000 -cx N] -i reads.fq [-i more.fq ...] (-l L -u U | --auto-cutoffs [-q Q]) -o out [-n N] [--pairs FILE]\n"
-                        "                         [--gz | --gz-plain] [--fasta] [--chunk-bytes N] [--initial-slots N] [-v]";
-    string db, out;
-    CountArgs c;   // -k: the inputs are counted instead of a database read
-    c.opt.ci = 1;  // the workflow's `kmc -ci1 -cs10000`
-    c.opt.cs = 10000;
-    vector<string> inputs;
-    pfh::SmudgeOptions opt;
-    bool l_seen = false, u_seen = false, q_seen = false, n_seen = false, verbose = false;
-    string reads_option;   // the first option that belongs to the count of the inputs
-    long long low = 0, up = 0, n_hap = 0;
-    auto refuse = [&](const string &why) { cerr << "Error: smudge: " << why << endl << usage << endl; return 1; };
-    auto number = [&](const string &o, const char *text, long long &v, long long top) {
-        char *end = nullptr;
-        errno = 0;
-        v = strtoll(text, &end, 10);
-        if (!errno && end != text && !*end && v >= 0 && v <= top) return true;
-        refuse(o + " takes a number from 0 to " + to_string(top) + ", not '" + text + "'");
-        return false;
-    };
-    auto positive = [&](const string &o, const char *text, uint64_t &v) {
-        long long x = 0;
-        if (!number(o, text, x, 0x7FFFFFFFFFFFFFFFll)) return false;
-        if (x < 1) { refuse(o + " takes a positive number"); return false; }
-        v = (uint64_t)x;
-        return true;
-    };
-    for (int i = 2; i < argc; ++i) {
-        const string a = argv[i];
-        {
-            string why;
-            const int taken = take_count_option(argc, argv, i, c, why);
-            if (taken < 0) return refuse(why);
-            if (taken) continue;
-        }
-        const bool has_value = i + 1 < argc;
-        const bool takes_value = a == "-d" || a == "-i" || a == "-o" || a == "-l" || a == "-u" || a == "-q" || a == "-n" || a == "--pairs" || a == "--chunk-bytes" ||
-                                 a == "--initial-slots";
-        if (a == "--auto-cutoffs") opt.auto_cutoffs = true;
-        else if (a == "-v") verbose = true;
-        else if (a == "--gz") { c.opt.gz = std::max(c.opt.gz, 1); if (reads_option.empty()) reads_option = a; }
-        else if (a == "--gz-plain") { c.opt.gz = 2; if (reads_option.empty()) reads_option = a; }
-        else if (a == "--fasta") { c.opt.fasta = true; if (reads_option.empty()) reads_option = a; }
-        else if (!takes_value) return refuse("unknown option " + a);
-        else if (!has_value) return refuse(a + " needs a value");
-        else if (a == "-d") db = argv[++i];
-        else if (a == "-i") { inputs.push_back(argv[++i]); if (reads_option.empty()) reads_option = a; }
-        else if (a == "-o") out = argv[++i];
-        else if (a == "--pairs") opt.pairs = argv[++i];
-        else if (a == "-l") { if (!number(a, argv[++i], low, 0xFFFFFFFFll)) return 1; l_seen = true; }
-        else if (a == "-u") { if (!number(a, argv[++i], up, 0xFFFFFFFFll)) return 1; u_seen = true; }
-        else if (a == "-n") { if (!number(a, argv[++i], n_hap, 0xFFFFFFFFll)) return 1; n_seen = true; }
-        else if (a == "-q") {
-            try { opt.quantile = stod(argv[++i]); } catch (const exception &) { return refuse(string("-q takes a quantile below 1, not '") + argv[i] + "'"); }
-            if (!(opt.quantile > 0) || opt.quantile >= 1) return refuse(string("-q takes a quantile below 1, not '") + argv[i] + "'");
-            q_seen = true;
-        }
-        else if (a == "--chunk-bytes") { if (!positive(a, argv[++i], c.opt.chunk_bytes)) return 1; if (reads_option.empty()) reads_option = a; }
-        else { if (!positive(a, argv[++i], c.opt.initial_slots)) return 1; if (reads_option.empty()) reads_option = a; }
-    }
-    // refused by name, before anything is read or written
-    if (!db.empty() && c.k_seen) return refuse("-d does not go with -k (the database is either read, or counted from the inputs)");
-    if (db.empty() && !c.k_seen) return refuse("-d <KMCDatabase> or -k <k> with -i <reads.fq> is missing");
-    if (!c.k_seen && !c.seen.empty()) return refuse(c.seen + " needs -k (it belongs to the count of the inputs)");
-    if (!c.k_seen && !reads_option.empty()) return refuse(reads_option + " needs -k (it belongs to the count of the inputs)");
-    if (c.k_seen && inputs.empty()) return refuse("-i <reads.fq> is missing");
-    if (out.empty()) return refuse("-o <out> is missing");
-    if ((l_seen || u_seen) && opt.auto_cutoffs) return refuse(string(l_seen ? "-l" : "-u") + " does not go with --auto-cutoffs (the bounds are derived: leave it out)");
-    if (!opt.auto_cutoffs && !(l_seen && u_seen)) return refuse("the bounds are missing: -l L and -u U, or --auto-cutoffs to derive them from the counts");
-    if (q_seen && !opt.auto_cutoffs) return refuse("-q needs --auto-cutoffs (it is the quantile of the derived upper bound)");
-    opt.lo = (uint32_t)low;
-    opt.hi = (uint32_t)up;
-    if (!opt.auto_cutoffs) {
-        if (low < 1) return refuse("-l " + to_string(low) + ": " + pf_hetpair::arg_text(pf_hetpair::ARG_LO_ZERO));
-        if (low > up) return refuse("-l " + to_string(low) + " is above -u " + to_string(up) + " (L > U)");
-        if (up - low + 1 > (long long)pf_hetpair::MAX_W) return refuse("-l " + to_string(low) + " -u " + to_string(up) + ": " + pf_hetpair::arg_text(pf_hetpair::ARG_TOO_WIDE));
-    }
-    if (n_seen && n_hap < 1) return refuse("-n takes a haploid coverage of at least 1");
-    opt.n = (uint64_t)n_hap;
-    if (c.k_seen) {
-        if (!c.opt.both_strands) return refuse("-b: smudge needs canonical counts");
-        const int clause = pfh::count_options_clause(c.opt, false);
-        if (clause) return refuse(pf_count::cut_text(clause));
-    }
-    pfh::SmudgeResult res;
-    string err;
-    const int rc = c.k_seen ? pfh::smudge_counted(c.opt, inputs, opt, out, 0, res, err) : pfh::smudge_db(db, opt, out, 0, res, err);
-    if (rc) {
-        cerr << "Error: " << err << endl;
-        return 1;
-    }
-    if (opt.auto_cutoffs) cout << "lower " << res.lo << " upper " << res.hi << endl;
-    if (res.clamped) cerr << "smudge: the upper bound was lowered to " << res.hi << " (lower + 4095: the table holds 4096 x 4096 cells)" << endl;
-    pf_hetpair::Stats st;
-    st.kmers = res.stats.kmers; st.in_range = res.stats.in_range; st.one_partner = res.stats.one_partner; st.many_partners = res.stats.many_partners;
-    st.pairs = res.stats.pairs;
-    cerr << pf_hetpair::stats_text(st) << endl;
-    if (opt.n) cerr << pf_hetpair::proposed_text(res.summary) << endl;
-    if (verbose) cerr << "smudge: load " << res.times.load_s << "s pairs " << res.times.pairs_s << "s write " << res.times.write_s << "s" << endl;
-    return 0;
-}
-
-// `--adapters FILE [--adapter-seed S] [--adapter-score T] [--adapter-pairs [--adapter-pair-score T] [--adapter-pair-min A]
-// [--adapter-keep-both]]` of `trim`, `run` and `run-multi`: the one place they are parsed
-struct ClipCli {
-    string adapters, seed, score, pair_score, pair_min;
-    bool adapters_seen = false, seed_seen = false, score_seen = false, pairs_seen = false, pair_score_seen = false, pair_min_seen = false, keep_both_seen = false;
-    // 1 = the option was taken (i moved past its value), 0 = not one of these, -1 = refused with `why`
-    int take(int argc, char **argv, int &i, string &why) {
-        const string a = argv[i];
-        if (a == "--adapter-pairs") { pairs_seen = true; return 1; }
-        if (a == "--adapter-keep-both") { keep_both_seen = true; return 1; }
-        if (a != "--adapters" && a != "--adapter-seed" && a != "--adapter-score" && a != "--adapter-pair-score" && a != "--adapter-pair-min") return 0;
-        if (i + 1 >= argc) { why = a + " needs a value"; return -1; }
-        const string v = argv[++i];
-        if (a == "--adapters") { adapters = v; adapters_seen = true; }
-        else if (a == "--adapter-seed") { seed = v; seed_seen = true; }
-        else if (a == "--adapter-pair-score") { pair_score = v; pair_score_seen = true; }
-        else if (a == "--adapter-pair-min") { pair_min = v; pair_min_seen = true; }
-        else { score = v; score_seen = true; }
-        return 1;
-    }
-    static bool number(const string &v, uint32_t lo, uint32_t hi, uint32_t &out) {
-        if (v.empty() || v.size() > 6) return false;
-        for (char ch : v) if (ch < '0' || ch > '9') return false;
-        out = (uint32_t)stoul(v);
-        return out >= lo && out <= hi;
-    }
-    // after the last argument: "" = accepted
-    string finish(pfh::ClipOptions &opt) const {
-        if (!adapters_seen) {
-            if (seed_seen) return "--adapter-seed needs --adapters: the seed is read by the adapter clipping alone";
-            if (score_seen) return "--adapter-score needs --adapters: the score is read by the adapter clipping alone";
-            if (pairs_seen) return "--adapter-pairs needs --adapters: the prefix pairs are read from the adapter file";
-            if (pair_score_seen) return "--adapter-pair-score needs --adapters and --adapter-pairs";
-            if (pair_min_seen) return "--adapter-pair-min needs --adapters and --adapter-pairs";
-            if (keep_both_seen) return "--adapter-keep-both needs --adapters and --adapter-pairs";
-            return "";
-        }
-        if (adapters.empty()) return "--adapters takes the path of a FASTA file";
-        opt.adapters = adapters;
-        if (seed_seen && !number(seed, 0, pf_clip::MAX_SEED, opt.seed)) return "--adapter-seed takes 0 to 8, not '" + seed + "'";
-        if (score_seen && !number(score, pf_clip::MIN_SCORE, pf_clip::MAX_SCORE, opt.score)) return "--adapter-score takes 1 to 1000, not '" + score + "'";
-        if (!pairs_seen) {
-            if (pair_score_seen) return "--adapter-pair-score needs --adapter-pairs: the score is read by the palindrome mode alone";
-            if (pair_min_seen) return "--adapter-pair-min needs --adapter-pairs: the length is read by the palindrome mode alone";
-            if (keep_both_seen) return "--adapter-keep-both needs --adapter-pairs: the reverse read is dropped by the palindrome mode alone";
-            return "";
-        }
-        opt.pairs = true;
-        opt.keep_both = keep_both_seen;
-        if (pair_score_seen && !number(pair_score, pf_clip::MIN_SCORE, pf_clip::MAX_SCORE, opt.pair_score))
-            return "--adapter-pair-score takes 1 to 1000, not '" + pair_score + "'";
-        if (pair_min_seen && !number(pair_min, pf_clip::MIN_PAIR_MIN, pf_clip::MAX_PAIR_MIN, opt.pair_min))
-            return "--adapter-pair-min takes 1 to 16, not '" + pair_min + "'";
-        return "";
-    }
-};
-
-// `qc`: what FastQC is looked at for before the steps of `trim` are chosen -- quality and base content by cycle, read lengths, the
-// quality offset -- from the device, as one tab-separated report (../pf_qc_rule.hpp)
-int qc_main(int argc, char **argv) {
-    const char *usage = "Usage:PloidyFrost qc (-i a.fq [-i b.fq ...] | -1 r1.fq [-1 ...] -2 r2.fq [-2 ...]) -o report.tsv [--phred 33|64] [--gz | --gz-plain] [--chunk-bytes N] [-v]";
-    vector<string> inputs, in1, in2;
-    string out;
-    pfh::QcOptions opt;
-    bool verbose = false;
-    auto refuse = [&](const string &why) { cerr << "Error: qc: " << why << endl << usage << endl; return 1; };
-    for (int i = 2; i < argc; ++i) {
-        const string a = argv[i];
-        if (a == "-v") { verbose = true; continue; }
-        if (a == "--gz") { opt.gz = std::max(opt.gz, 1); continue; }
-        if (a == "--gz-plain") { opt.gz = 2; continue; }
-        if (a == "--fasta") return refuse("--fasta does not go with qc: FASTA has no qualities to report");
-        const bool known = a == "-i" || a == "-1" || a == "-2" || a == "-o" || a == "--phred" || a == "--chunk-bytes";
-        if (!known) return refuse("unknown option " + a);
-        if (i + 1 >= argc) return refuse(a + " needs a value");
-        const string v = argv[++i];
-        if (a == "-i") inputs.push_back(v);
-        else if (a == "-1") in1.push_back(v);
-        else if (a == "-2") in2.push_back(v);
-        else if (a == "-o") out = v;
-        else if (a == "--phred") {
-            if (v != "33" && v != "64") return refuse("--phred takes 33 or 64, not '" + v + "'");
-            opt.phred = (uint32_t)stoi(v);
-        } else {
-            char *end = nullptr;
-            errno = 0;
-            opt.chunk_bytes = strtoull(v.c_str(), &end, 10);
-            if (errno || !isdigit((unsigned char)v[0]) || *end || !opt.chunk_bytes) return refuse("--chunk-bytes takes a positive number, not '" + v + "'");
-        }
-    }
-    // refused by name, before anything is read or written
-    if (!inputs.empty() && (!in1.empty() || !in2.empty())) return refuse("-i does not go with -1 / -2 (the inputs are either single-ended or the two sides of pairs)");
-    if (inputs.empty() && in1.empty() && in2.empty()) return refuse("-i <reads.fq> is missing (or -1 <r1.fq> -2 <r2.fq>)");
-    if (out.empty()) return refuse("-o <report.tsv> is missing");
-    pfh::QcReport rep;
-    string err;
-    if (pfh::qc_fastq(inputs.empty() ? in1 : inputs, in2, out, opt, 0, rep, err)) { cerr << "Error: " << err << endl; return 1; }
-    for (const string &l : rep.lines()) cerr << l << endl;
-    if (verbose) cerr << "qc: report " << rep.text().size() << " bytes, phred " << rep.phred << " hint " << pf_qc::hint_of(rep.tables.data()) << endl;
-    return 0;
-}
-
-// `trim`: step 1 of the reference's workflow (`trimmomatic PE -phred33 r1 r2 trim1 u1 trim2 u2 LEADING:10 TRAILING:10 SLIDINGWINDOW:3:20
-// MINLEN:50`) on the device; the steps are Trimmomatic's words as positional arguments
-int trim_main(int argc, char **argv) {
-    const char *usage = "Usage:PloidyFrost trim -i reads.fq [-i more.fq ...] -o trimmed.fq STEP... [--phred 33|64] [--trimlog file] [--chunk-bytes N] [--gz] [--gz-plain] [--gz-out] [-v]\n"
-                        "      PloidyFrost trim -1 r1.fq -2 r2.fq -o1 p1.fq -u1 u1.fq -o2 p2.fq -u2 u2.fq STEP... [the same options]\n"
-                        "      STEP: LEADING:t TRAILING:t SLIDINGWINDOW:w:t MINLEN:l\n"
-                        "      [--adapters adapters.fa [--adapter-seed 0..8] [--adapter-score 1..1000]]: adapters are clipped first; no STEP is needed beside them\n"
-                        "      [--adapter-pairs [--adapter-pair-score 1..1000] [--adapter-pair-min 1..16] [--adapter-keep-both]] with -1 / -2: palindrome mode from the file's Prefix pairs\n"
-                        "      [--report report.tsv]: the read quality report of the reads as they come (raw) and as they are written (kept), as `qc` words it";
-    vector<string> inputs, words;
-    string out, in_pair[2], out_pair[4];
-    pfh::TrimOptions opt;
-    ClipCli clip_cli;
-    bool verbose = false;
-    auto refuse = [&](const string &why) { cerr << "Error: trim: " << why << endl << usage << endl; return 1; };
-    const char *pair_opts[6] = {"-1", "-2", "-o1", "-u1", "-o2", "-u2"};
-    for (int i = 2; i < argc; ++i) {
-        const string a = argv[i];
-        if (a.empty() || a[0] != '-') { words.push_back(a); continue; }
-        if (a == "-v") { verbose = true; continue; }
-        if (a == "--gz") { opt.gz = std::max(opt.gz, 1); continue; }
-        if (a == "--gz-plain") { opt.gz = 2; continue; }
-        if (a == "--gz-out") { opt.gz_out = true; continue; }
-        if (a == "--fasta") return refuse("--fasta does not go with trim: FASTA has no qualities to trim");
-        {
-            string why;
-            const int taken = clip_cli.take(argc, argv, i, why);
-            if (taken < 0) return refuse(why);
-            if (taken) continue;
-        }
-        const bool known = a == "-i" || a == "-o" || a == "--phred" || a == "--trimlog" || a == "--chunk-bytes" || a == "--report" ||
-                           std::find_if(pair_opts, pair_opts + 6, [&](const char *o) { return a == o; }) != pair_opts + 6;
-        if (!known) return refuse("unknown option " + a);
-        if (i + 1 >= argc) return refuse(a + " needs a value");
-        const string v = argv[++i];
-        if (a == "-i") inputs.push_back(v);
-        else if (a == "-o") out = v;
-        else if (a == "--trimlog") opt.trimlog = v;
-        else if (a == "--report") { if (v.empty()) return refuse("--report needs a value"); opt.report = v; }
-        else if (a == "--phred") {
-            if (v != "33" && v != "64") return refuse("--phred takes 33 or 64, not '" + v + "'");
-            opt.phred = (uint32_t)stoi(v);
-        } else if (a == "--chunk-bytes") {
-            char *end = nullptr;
-            errno = 0;
-            opt.chunk_bytes = strtoull(v.c_str(), &end, 10);
-            if (errno || !isdigit((unsigned char)v[0]) || *end || !opt.chunk_bytes) return refuse("--chunk-bytes takes a positive number, not '" + v + "'");
-        } else {
-            for (int j = 0; j < 6; ++j)
-                if (a == pair_opts[j]) (j < 2 ? in_pair[j] : out_pair[j - 2]) = v;
-        }
-    }
-    // refused by name, before anything is read or written
-    {
-        vector<const char *> w;
-        for (const string &x : words) w.push_back(x.c_str());
-        vector<pf_trim::Step> steps;
-        size_t bad = 0;
-        { const string why = clip_cli.finish(opt.clip); if (!why.empty()) return refuse(why); }
-        const int c = pf_trim::parse_steps(w.data(), w.size(), steps, &bad);
-        if (c == pf_trim::REFUSE_NO_STEP && !opt.clip.on()) return refuse(pf_trim::refusal_text(c));
-        if (c && c != pf_trim::REFUSE_NO_STEP) return refuse(words[bad] + ": " + pf_trim::refusal_text(c));
-        for (const pf_trim::Step &st : steps) opt.steps.push_back(pf_trim_step{st.kind, st.a, st.b});
-    }
-    const bool pair_in = !in_pair[0].empty() || !in_pair[1].empty();
-    const bool pair_out = !out_pair[0].empty() || !out_pair[1].empty() || !out_pair[2].empty() || !out_pair[3].empty();
-    if (!inputs.empty() && pair_in) return refuse("-i does not go with -1 / -2 (the inputs are either single-ended or one pair)");
-    if (pair_in && !out.empty()) return refuse("-o does not go with -1 / -2 (a pair is written to -o1 -u1 -o2 -u2)");
-    if (opt.clip.on() && opt.clip.pairs && !inputs.empty()) return refuse("--adapter-pairs needs -1 / -2");
-    if (!pair_in && pair_out) return refuse(inputs.empty() ? "-1 <r1.fq> and -2 <r2.fq> are missing" : "-o1 -u1 -o2 -u2 do not go with -i (single-ended reads are written to -o)");
-    pf_trim_stats st[2] = {};
-    pfh::TrimTimes tm;
-    pfh::ClipReport clip;
-    pfh::QcReport qc;
-    string err;
-    if (pair_in) {
-        for (int j = 0; j < 2; ++j)
-            if (in_pair[j].empty()) return refuse(string(pair_opts[j]) + " <r" + to_string(j + 1) + ".fq> is missing");
-        for (int j = 0; j < 4; ++j)
-            if (out_pair[j].empty()) return refuse(string(pair_opts[2 + j]) + " <out.fq> is missing");
-        if (pfh::trim_fastq_pair(in_pair[0], in_pair[1], out_pair, opt, 0, st, &tm, err, &clip, &qc)) { cerr << "Error: " << err << endl; return 1; }
-        if (opt.clip.on()) cerr << pfh::clip_line(clip) << endl;
-        cerr << "trim: pairs " << st[0].reads << " both " << st[0].both << " forward_only " << st[0].only1 << " reverse_only " << st[0].only2 << " dropped "
-             << st[0].neither << " bases " << st[0].bases + st[1].bases << " bases_kept " << st[0].bases_kept + st[1].bases_kept << endl;
-    } else {
-        if (inputs.empty()) return refuse("-i <reads.fq> is missing (or -1 <r1.fq> -2 <r2.fq> for a pair)");
-        if (out.empty()) return refuse("-o <trimmed.fq> is missing");
-        if (pfh::trim_fastq(inputs, out, opt, 0, st[0], &tm, err, &clip, &qc)) { cerr << "Error: " << err << endl; return 1; }
-        if (opt.clip.on()) cerr << pfh::clip_line(clip) << endl;
-        cerr << "trim: reads " << st[0].reads << " kept " << st[0].kept << " dropped " << st[0].dropped << " bases " << st[0].bases << " bases_kept "
-             << st[0].bases_kept << endl;
-    }
-    for (const string &l : qc.lines()) cerr << l << endl;
-    if (verbose) cerr << "trim: stream " << tm.stream_s << "s (device " << tm.device_s << "s, read " << tm.read_s << "s, write " << tm.write_s << "s)" << endl;
-    return 0;
-}
-
-// `run STEP...` / `run-multi STEP...`: the words and options of step 1 as `trim` takes them -- the same parser, refusals and texts
-struct TrimCli {
-    vector<string> words;   // the positional words: the steps
-    bool phred_seen = false, pair_seen = false;
-    uint32_t phred = 33;
-    string pending1;        // a -1 whose -2 has not come yet
-    ClipCli clip;           // --adapters and its two values
-    // 1 = the option was taken (i moved past its value), 0 = not one of these, -1 = refused with `why`
-    int take(int argc, char **argv, int &i, const char *sub, vector<string> &files, string &why) {
-        const string a = argv[i];
-        if (a.empty() || a[0] != '-') { words.push_back(a); return 1; }
-        for (const char *o : {"--trimlog", "-o1", "-u1", "-o2", "-u2"})
-            if (a == o) { why = a + " is not built into " + sub + ": `trim` writes the trimmed reads, the unpaired ones and the log"; return -1; }
-        { const int taken = clip.take(argc, argv, i, why); if (taken) return taken; }
-        if (a != "--phred" && a != "-1" && a != "-2") return 0;
-        if (i + 1 >= argc) { why = a + " needs a value"; return -1; }
-        const string v = argv[++i];
-        if (a == "--phred") {
-            if (v != "33" && v != "64") { why = "--phred takes 33 or 64, not '" + v + "'"; return -1; }
-            phred = (uint32_t)stoi(v);
-            phred_seen = true;
-        } else if (a == "-1") {
-            if (!pending1.empty()) { why = no_second(); return -1; }
-            pending1 = v;
-            pair_seen = true;
-        } else {
-            if (pending1.empty()) { why = "-2 " + v + " has no -1 in front of it (the files of a pair come as -1 <r1.fq> -2 <r2.fq>)"; return -1; }
-            files.push_back(pending1);
-            files.push_back(v);
-            pending1.clear();
-        }
-        return 1;
-    }
-    string no_second() const { return "-1 " + pending1 + " has no -2 behind it (the files of a pair come as -1 <r1.fq> -2 <r2.fq>)"; }
-    // after the last argument: "" = accepted, with the steps parsed
-    string finish(const char *sub, vector<pf_trim_step> &steps, pfh::ClipOptions &clip_opt) const {
-        if (!pending1.empty()) return no_second();
-        { const string why = clip.finish(clip_opt); if (!why.empty()) return why; }
-        if (words.empty() && clip_opt.on()) return "";   // --adapters turns trimming on as a step does
-        if (words.empty()) {
-            if (pair_seen) return string("-1 / -2 need a step: the files of a pair are trimmed together (two files without trimming go with -i: ") + sub + " -i r1.fq -i r2.fq)";
-            if (phred_seen) return "--phred needs a step: the quality offset is read by the trimming alone";
-            return "";
-        }
-        vector<const char *> w;
-        for (const string &x : words) w.push_back(x.c_str());
-        vector<pf_trim::Step> parsed;
-        size_t bad = 0;
-        const int c = pf_trim::parse_steps(w.data(), w.size(), parsed, &bad);
-        if (c) return words[bad] + ": " + pf_trim::refusal_text(c);
-        for (const pf_trim::Step &st : parsed) steps.push_back(pf_trim_step{st.kind, st.a, st.b});
-        return "";
-    }
-};
-
-bool take_long_options(int &argc, char **argv, int first, Options &opt, DensityCli &dc);
-bool model_setup(const Options &opt, DensityCli &dc, pfh::CDBG::ModelOptions &model, pf_filter_opts &filter, pf_filter_multi_opts &multi);
 int calling_main(Options &opt, DensityCli &dc);
 
-// `run`: steps 2 to 5 of the reference's workflow for one sample (`kmc`, `kmc_tools filter`, `Bifrost build`, `PloidyFrost`) in one
-// process and on one device context; the letters are those of `count` / `mask` (-k -ci -cs -cx -i -u), of `build` (-g) and of the
-// calling run (-z -M -D -G -t -q --model ...)
-int run_main(int argc, char **argv) {
-    const char *usage = "Usage:PloidyFrost run [-k 25] [-ci 1] [-cs 10000] [-cx N] -i trimmed.fq [-i more.fq ...] -o sample [-q Q] [-u U] [--keep-tips] [--keep-isolated] [-g G]\n"
-                        "                 [-z Z -M m -D d -G g -t T --ref-threads N] [--model cov|fre ... --model-only --filter \"OPTS\" --density ...]\n"
-                        "                 [--db-out <KMCDatabase>] [--gfa-out <sample>] [--chunk-bytes N] [--initial-slots N] [--gz] [--gz-plain] [--fasta] [-v]\n"
-                        "      PloidyFrost run [the same options] -i raw.fq [-i more.fq ...] -o sample STEP... [--phred 33|64]\n"
-                        "      PloidyFrost run [the same options] -1 r1.fq -2 r2.fq [-1 r3.fq -2 r4.fq ...] -o sample STEP... [--phred 33|64]\n"
-                        "      STEP: LEADING:t TRAILING:t SLIDINGWINDOW:w:t MINLEN:l (the raw reads are trimmed on the way in, as `trim` trims them)\n"
-                        "      [--report report.tsv] with STEP... or --adapters: the read quality report `trim --report` writes for the same inputs\n"
-                        "      [--smudge [--smudge-n N] [--smudge-pairs FILE]]: the k-mer pair report `smudge` writes for the counted k-mers, as PloidyFrost_output/<sample>_smudge.tsv";
-    auto refuse = [&](const string &why) { cerr << "Error: run: " << why << endl << usage << endl; return 1; };
-    Options lopt;   // the long options of the calling run
-    DensityCli dc;
-    if (!take_long_options(argc, argv, 2, lopt, dc)) return 1;
-    pfh::RunOptions opt;
-    CountArgs c;
-    c.opt.ci = opt.ci;
-    c.opt.cx = opt.cx;
-    c.opt.cs = opt.cs;
-    string out;
-    vector<string> inputs, pair_files;
-    TrimCli tc;
-    bool verbose = false;
-    auto number = [&](const string &o, const char *text, uint64_t &v, bool positive) {
-        char *end = nullptr;
-        errno = 0;
-        v = strtoull(text, &end, 10);
-        if (!errno && isdigit((unsigned char)text[0]) && !*end && (v > 0 || !positive)) return true;
-        refuse(o + " takes a " + (positive ? "positive " : "") + "number, not '" + text + "'");
-        return false;
-    };
-    auto real = [&](const string &o, const char *text, double &v) {
-        char *end = nullptr;
-        v = strtod(text, &end);
-        if (end != text && !*end && std::isfinite(v)) return true;
-        refuse(o + " takes a number, not '" + text + "'");
-        return false;
-    };
-    static const struct { const char *name, *why; } not_here[] = {
-        {"-f", "-f is not built into run: the coloured workflow goes in steps (`build-multi`, then the calling run with -f)"},
-        {"-C", "-C does not go with run: the thresholds come from the counted k-mers (one sample, no coverage file)"},
-        {"-d", "-d does not go with run: the database is counted from the reads (--db-out writes it; isolated unitigs are removed unless --keep-isolated)"},
-        {"-h", "-h does not go with run: the thresholds come from the counted k-mers, not from a histogram file"},
-        {"-l", "-l does not go with run: the lower threshold is derived from the counted k-mers (as --auto-cutoffs derives it)"},
-        {"-b", "-b does not go with run: the graph is built from both strands"},
-        {"--filtered-out", "--filtered-out is not built: the masked reads are never made (`mask` writes them)"},
-        {"--detach-teardown", "--detach-teardown is not built into run"},
-    };
-    if (lopt.gpus_seen) return refuse("--gpus is not built into run: one sample, one GPU");
-    if (lopt.each_color || lopt.multi_seen) return refuse("--filter-multi / --model-each-color belong to the coloured path: run has --filter");
-    if (lopt.detach_teardown) return refuse(not_here[7].why);
-    for (int i = 2; i < argc; ++i) {
-        const string a = argv[i];
-        for (const auto &nh : not_here)
-            if (a == nh.name) return refuse(nh.why);
-        {
-            string why;
-            const int taken = take_count_option(argc, argv, i, c, why);
-            if (taken < 0) return refuse(why);
-            if (taken) continue;
-        }
-        {
-            string why;
-            const int taken = tc.take(argc, argv, i, "run", pair_files, why);
-            if (taken < 0) return refuse(why);
-            if (taken) continue;
-        }
-        if (a == "-v") { verbose = true; continue; }
-        if (a == "--gz") { opt.gz = std::max(opt.gz, 1); continue; }
-        if (a == "--gz-plain") { opt.gz = 2; continue; }
-        if (a == "--fasta") { opt.fasta = true; continue; }
-        if (a == "--keep-tips") { opt.clip_tips = false; continue; }
-        if (a == "--keep-isolated") { opt.del_isolated = false; continue; }
-        if (a == "--smudge") { opt.smudge = true; continue; }
-        const bool takes_value = a == "-i" || a == "-o" || a == "-q" || a == "-u" || a == "-g" || a == "-z" || a == "-M" || a == "-D" || a == "-G" || a == "-t" ||
-                                 a == "--db-out" || a == "--gfa-out" || a == "--chunk-bytes" || a == "--initial-slots" || a == "--report" || a == "--smudge-n" ||
-                                 a == "--smudge-pairs";
-        if (!takes_value) return refuse("unknown option " + a);
-        if (i + 1 >= argc) return refuse(a + " needs a value");
-        const char *val = argv[++i];
-        uint64_t v = 0;
-        if (a == "--report") { if (!*val) return refuse("--report needs a value"); opt.report = val; }
-        else if (a == "--smudge-pairs") { if (!*val) return refuse("--smudge-pairs needs a value"); opt.smudge_pairs = val; }
-        else if (a == "--smudge-n") { if (!number(a, val, v, false)) return 1; opt.smudge_n = v; opt.smudge_n_seen = true; }
-        else if (a == "-i") inputs.push_back(val);
-        else if (a == "-o") out = val;
-        else if (a == "--db-out") opt.db_out = val;
-        else if (a == "--gfa-out") opt.gfa_out = val;
-        else if (a == "-q") { if (!real(a, val, opt.quantile)) return 1; }
-        else if (a == "-M") { if (!real(a, val, opt.match)) return 1; }
-        else if (a == "-D") { if (!real(a, val, opt.mismatch)) return 1; }
-        else if (a == "-G") { if (!real(a, val, opt.gap)) return 1; }
-        else if (a == "-u") { if (!number(a, val, v, false)) return 1; if (v > 0xFFFFFFFFull) return refuse("-u takes a number from 0 to 4294967295, not '" + string(val) + "'"); opt.mask_up = (uint32_t)v; }
-        else if (!number(a, val, v, true)) return 1;
-        else if (a == "-g") opt.g = (int)std::min<uint64_t>(v, 0x7FFFFFFFull);
-        else if (a == "-z") opt.complex_size = (size_t)v;
-        else if (a == "-t") opt.call.threads = (size_t)v;
-        else if (a == "--chunk-bytes") opt.chunk_bytes = v;
-        else if (a == "--initial-slots") opt.initial_slots = v;
-    }
-    // refused by name, before anything is read or written and before a device context exists
-    { const string why = tc.finish("run", opt.trim.steps, opt.trim.clip); if (!why.empty()) return refuse(why); }
-    opt.trim.phred = tc.phred;
-    if (tc.pair_seen && !inputs.empty()) return refuse("-i does not go with -1 / -2 (the inputs are either single-ended or pairs)");
-    if (tc.pair_seen) { inputs = pair_files; opt.paired = true; }
-    if (inputs.empty()) return refuse("-i <reads.fq> is missing");
-    if (out.empty()) return refuse("-o <sample> is missing");
-    opt.k = c.opt.k;
-    opt.ci = c.opt.ci;
-    opt.cx = c.opt.cx;
-    opt.cs = c.opt.cs;
-    { const string why = pfh::run_options_refusal(opt); if (!why.empty()) return refuse(why); }
-    if (opt.quantile < 0 || opt.quantile > 1) return refuse("-q: frequency cutoff value should be between 0 and 1");
-    if (opt.complex_size < 4) return refuse("-z: Maximum number of unitigs in superbubble is at least 4 !");
-    if (opt.mismatch > opt.match) return refuse("-D: Mismatch penalty should be smaller than match score !");
-    if (opt.gap > opt.match) return refuse("-G: Gap penalty should be smaller than match score !");
-    if (opt.call.threads > std::thread::hardware_concurrency()) return refuse("-t: Number of threads cannot be greater than " + to_string(std::thread::hardware_concurrency()));
-    pf_filter_opts filter = {};
-    pf_filter_multi_opts multi = {};
-    if (!model_setup(lopt, dc, opt.call.model, filter, multi)) return 1;
-    opt.call.ref_threads = lopt.ref_threads;
-    opt.call.verbose = verbose;
-    opt.call.filter = lopt.filter_seen ? &filter : nullptr;
-    opt.call.density_points = dc.on ? dc.points : 0;
-    opt.call.density_adjust = dc.adjust;
-    pfh::RunStats st;
-    pfh::RunTimes tm;
-    string err;
-    if (pfh::run_fastq(inputs, out, opt, 0, st, &tm, err)) {
-        cout.flush();
-        fflush(nullptr);
-        // (what the chain's last command says on stdout is said there; its own refusals carry their "Error:" already)
-        if (err.rfind("CompactedDBG::read()", 0) == 0) cout << err << endl;
-        else if (err.rfind("run: ", 0) == 0) cerr << "Error: " << err << endl;
-        else cerr << err << endl;
-        return EXIT_FAILURE;
-    }
-    for (size_t u = 0; u < pfh::trim_unit_count(inputs.size(), opt.paired) && opt.trim.on(); ++u) {   // one line per `trim` of the equivalent chain
-        if (u < st.clip.size()) cerr << pfh::clip_line(st.clip[u]) << endl;
-        cerr << pfh::trim_unit_line(&st.trim[opt.paired ? 2 * u : 0], opt.paired) << endl;
-    }
-    for (const string &l : st.qc.lines()) cerr << l << endl;
-    cerr << "run: reads " << st.counted.reads << " bases " << st.counted.bases << " kmers " << st.counted.kmers << " bad " << st.counted.kmers_bad << " distinct "
-         << st.counted.unique << " lower " << st.lower << " upper " << st.upper << " windows_bad " << st.masked.kmers_bad << " windows_kept " << st.masked.kmers_kept
-         << " distinct_kept " << st.distinct_kept << " unitigs " << st.graph.unitigs << " removed " << st.graph.removed << " unitigs_out " << st.graph.unitigs_out
-         << " longest " << st.graph.longest << endl;
-    if (opt.smudge) {
-        pf_hetpair::Stats hs;
-        hs.kmers = st.smudge.stats.kmers; hs.in_range = st.smudge.stats.in_range; hs.one_partner = st.smudge.stats.one_partner;
-        hs.many_partners = st.smudge.stats.many_partners; hs.pairs = st.smudge.stats.pairs;
-        cerr << pf_hetpair::stats_text(hs) << endl;
-        if (opt.smudge_n) cerr << pf_hetpair::proposed_text(st.smudge.summary) << endl;
-        if (verbose) cerr << "smudge: pairs " << st.smudge.times.pairs_s << "s (inside run: " << tm.smudge_s << "s)" << endl;
-    }
-    if (verbose)
-        cerr << "run: count " << tm.count_s << "s finish " << tm.finish_s << "s table " << tm.table_s << "s db-out " << tm.db_out_s << "s recount " << tm.recount_s
-             << "s refinish " << tm.refinish_s << "s graph " << tm.graph_s << "s gfa-out " << tm.gfa_out_s << "s load " << tm.load_s << "s call " << tm.call_s << "s" << endl;
-    return 0;
-}
-
-// `run-multi`: the multi-sample workflow (script/pipeline/run-multisample.sh) behind the trimmed reads in one process and on one device
-// context; `run`'s letters, with --sample NAME in front of every sample's -i and the coloured run's --filter-multi / --model-each-color
-int run_multi_main(int argc, char **argv) {
-    const char *usage = "Usage:PloidyFrost run-multi [-k 25] [-ci 1] [-cs 10000] [-cx N] --sample NAME -i a.fq [-i b.fq ...] --sample NAME2 -i c.fq [...] -o out\n"
-                        "                 [-q Q] [-u U] [--keep-tips] [--keep-isolated] [-g G] [-z Z -M m -D d -G g -t T --ref-threads N]\n"
-                        "                 [--model cov|fre --filter-multi \"OPTS\" [--model-each-color] [--density ...] [--model-only]]\n"
-                        "                 [--db-out <KMCDatabase>] [--gfa-out <graph>] [--chunk-bytes N] [--initial-slots N] [--gz] [--gz-plain] [--fasta] [-v]\n"
-                        "      PloidyFrost run-multi [the same options] --sample NAME (-i raw.fq ... | -1 r1.fq -2 r2.fq ...) --sample NAME2 ... -o out STEP... [--phred 33|64]\n"
-                        "      STEP: LEADING:t TRAILING:t SLIDINGWINDOW:w:t MINLEN:l (the raw reads are trimmed on the way in, as `trim` trims them)";
-    auto refuse = [&](const string &why) { cerr << "Error: run-multi: " << why << endl << usage << endl; return 1; };
-    Options lopt;   // the long options of the calling run
-    DensityCli dc;
-    if (!take_long_options(argc, argv, 2, lopt, dc)) return 1;
-    pfh::RunMultiOptions mopt;
-    pfh::RunOptions &opt = mopt.run;
-    CountArgs c;
-    c.opt.ci = opt.ci;
-    c.opt.cx = opt.cx;
-    c.opt.cs = opt.cs;
-    string out;
-    vector<pfh::MultiSample> samples;
-    TrimCli tc;
-    bool verbose = false;
-    size_t threads = 1;
-    auto number = [&](const string &o, const char *text, uint64_t &v, bool positive) {
-        char *end = nullptr;
-        errno = 0;
-        v = strtoull(text, &end, 10);
-        if (!errno && isdigit((unsigned char)text[0]) && !*end && (v > 0 || !positive)) return true;
-        refuse(o + " takes a " + (positive ? "positive " : "") + "number, not '" + text + "'");
-        return false;
-    };
-    auto real = [&](const string &o, const char *text, double &v) {
-        char *end = nullptr;
-        v = strtod(text, &end);
-        if (end != text && !*end && std::isfinite(v)) return true;
-        refuse(o + " takes a number, not '" + text + "'");
-        return false;
-    };
-    static const struct { const char *name, *why; } not_here[] = {
-        {"-f", "-f does not go with run-multi: the colour file is made from the samples (--gfa-out writes it)"},
-        {"-C", "-C does not go with run-multi: the thresholds come from every sample's counted k-mers (no coverage file)"},
-        {"-d", "-d does not go with run-multi: the databases are counted from the reads (--db-out writes them; isolated unitigs are removed unless --keep-isolated)"},
-        {"-h", "-h does not go with run-multi: the thresholds come from every sample's counted k-mers, not from histogram files"},
-        {"-l", "-l does not go with run-multi: the lower thresholds are derived from the counted k-mers (as --auto-cutoffs derives them)"},
-        {"-b", "-b does not go with run-multi: the graph is built from both strands"},
-        {"--filtered-out", "--filtered-out is not built: the masked reads are never made (`mask` writes them)"},
-        {"--detach-teardown", "--detach-teardown is not built into run-multi"},
-    };
-    if (lopt.gpus_seen) return refuse("--gpus is not built into run-multi: the coloured path runs on one GPU");
-    if (lopt.filter_seen) return refuse("--filter reads the single-sample result streams: run-multi has --filter-multi");
-    if (lopt.detach_teardown) return refuse(not_here[7].why);
-    for (int i = 2; i < argc; ++i) {
-        const string a = argv[i];
-        for (const auto &nh : not_here)
-            if (a == nh.name) return refuse(nh.why);
-        {
-            string why;
-            const int taken = take_count_option(argc, argv, i, c, why);
-            if (taken < 0) return refuse(why);
-            if (taken) continue;
-        }
-        {
-            if ((a == "-1" || a == "-2") && samples.empty()) return refuse(a + " stands before any --sample NAME: every input belongs to a sample");
-            if ((a == "-1" || a == "-2") && !samples.back().paired && !samples.back().inputs.empty())
-                return refuse("sample " + samples.back().name + ": -i does not go with -1 / -2 (the inputs of a sample are either single-ended or pairs)");
-            if (a == "--sample" && !tc.pending1.empty()) return refuse(tc.no_second());
-            static vector<string> no_files;
-            string why;
-            const int taken = tc.take(argc, argv, i, "run-multi", samples.empty() ? no_files : samples.back().inputs, why);
-            if (taken < 0) return refuse(why);
-            if (taken && (a == "-1" || a == "-2")) samples.back().paired = true;
-            if (taken) continue;
-        }
-        if (a == "-v") { verbose = true; continue; }
-        if (a == "--gz") { opt.gz = std::max(opt.gz, 1); continue; }
-        if (a == "--gz-plain") { opt.gz = 2; continue; }
-        if (a == "--fasta") { opt.fasta = true; continue; }
-        if (a == "--keep-tips") { opt.clip_tips = false; continue; }
-        if (a == "--keep-isolated") { opt.del_isolated = false; continue; }
-        const bool takes_value = a == "--sample" || a == "-i" || a == "-o" || a == "-q" || a == "-u" || a == "-g" || a == "-z" || a == "-M" || a == "-D" || a == "-G" ||
-                                 a == "-t" || a == "--db-out" || a == "--gfa-out" || a == "--chunk-bytes" || a == "--initial-slots";
-        if (!takes_value) return refuse("unknown option " + a);
-        if (i + 1 >= argc) return refuse(a + " needs a value");
-        const char *val = argv[++i];
-        uint64_t v = 0;
-        if (a == "--sample") { samples.emplace_back(); samples.back().name = val; }
-        else if (a == "-i") {
-            if (samples.empty()) return refuse(string("-i ") + val + " stands before any --sample NAME: every input belongs to a sample");
-            if (samples.back().paired) return refuse("sample " + samples.back().name + ": -i does not go with -1 / -2 (the inputs of a sample are either single-ended or pairs)");
-            samples.back().inputs.push_back(val);
-        }
-        else if (a == "-o") out = val;
-        else if (a == "--db-out") opt.db_out = val;
-        else if (a == "--gfa-out") opt.gfa_out = val;
-        else if (a == "-q") { if (!real(a, val, opt.quantile)) return 1; }
-        else if (a == "-M") { if (!real(a, val, opt.match)) return 1; }
-        else if (a == "-D") { if (!real(a, val, opt.mismatch)) return 1; }
-        else if (a == "-G") { if (!real(a, val, opt.gap)) return 1; }
-        else if (a == "-u") { if (!number(a, val, v, false)) return 1; if (v > 0xFFFFFFFFull) return refuse("-u takes a number from 0 to 4294967295, not '" + string(val) + "'"); opt.mask_up = (uint32_t)v; }
-        else if (!number(a, val, v, true)) return 1;
-        else if (a == "-g") opt.g = (int)std::min<uint64_t>(v, 0x7FFFFFFFull);
-        else if (a == "-z") opt.complex_size = (size_t)v;
-        else if (a == "-t") threads = (size_t)v;
-        else if (a == "--chunk-bytes") opt.chunk_bytes = v;
-        else if (a == "--initial-slots") opt.initial_slots = v;
-    }
-    // refused by name, before anything is read or written and before a device context exists
-    { const string why = tc.finish("run-multi", opt.trim.steps, opt.trim.clip); if (!why.empty()) return refuse(why); }
-    opt.trim.phred = tc.phred;
-    { const string why = pfh::run_multi_samples_refusal(samples); if (!why.empty()) return refuse(why); }
-    if (out.empty()) return refuse("-o <out> is missing");
-    opt.k = c.opt.k;
-    opt.ci = c.opt.ci;
-    opt.cx = c.opt.cx;
-    opt.cs = c.opt.cs;
-    { const string why = pfh::run_options_refusal(opt); if (!why.empty()) return refuse(why); }
-    if (opt.quantile < 0 || opt.quantile > 1) return refuse("-q: frequency cutoff value should be between 0 and 1");
-    if (opt.complex_size < 4) return refuse("-z: Maximum number of unitigs in superbubble is at least 4 !");
-    if (opt.mismatch > opt.match) return refuse("-D: Mismatch penalty should be smaller than match score !");
-    if (opt.gap > opt.match) return refuse("-G: Gap penalty should be smaller than match score !");
-    if (threads > std::thread::hardware_concurrency()) return refuse("-t: Number of threads cannot be greater than " + to_string(std::thread::hardware_concurrency()));
-    pf_filter_opts filter = {};
-    pf_filter_multi_opts multi = {};
-    lopt.colorfile = "run-multi";   // (the coloured run's rules for --model / --filter-multi: the colour file is made here)
-    if (!model_setup(lopt, dc, mopt.call.model, filter, multi)) return 1;
-    // (--ref-threads is taken and changes nothing, as in the coloured calling run: it writes the `-t 1` text format alone)
-    mopt.call.threads = threads;
-    mopt.call.verbose = verbose;
-    mopt.call.filter_multi = lopt.multi_seen ? &multi : nullptr;
-    mopt.call.each_color = lopt.each_color;
-    mopt.call.density_points = dc.on ? dc.points : 0;
-    mopt.call.density_adjust = dc.adjust;
-    pfh::RunMultiStats st;
-    pfh::RunMultiTimes tm;
-    string err;
-    if (pfh::run_multi_fastq(samples, out, mopt, 0, st, &tm, err)) {
-        cout.flush();
-        fflush(nullptr);
-        // (what the chain's last command says on stdout is said there; its own refusals carry their "Error:" already)
-        if (err.rfind("ColoredCDBG::read()", 0) == 0) cout << err << endl;
-        else if (err.rfind("run-multi: ", 0) == 0) cerr << "Error: " << err << endl;
-        else cerr << err << endl;
-        return EXIT_FAILURE;
-    }
-    for (size_t c = 0; c < st.trim.size(); ++c)   // one line per `trim` of the equivalent chain, in the order given
-        for (size_t u = 0; u < pfh::trim_unit_count(samples[c].inputs.size(), samples[c].paired); ++u) {
-            if (c < st.clip.size() && u < st.clip[c].size()) cerr << pfh::clip_line(st.clip[c][u]) << endl;
-            cerr << pfh::trim_unit_line(&st.trim[c][samples[c].paired ? 2 * u : 0], samples[c].paired) << endl;
-        }
-    cerr << "run-multi: colors " << st.colors << " reads " << st.reads << " bases " << st.bases << " kmers " << st.kmers << " bad " << st.bad << " distinct "
-         << st.distinct << " windows_bad " << st.windows_bad << " windows_kept " << st.windows_kept << " distinct_kept " << st.distinct_kept << " unitigs "
-         << st.graph.unitigs << " removed " << st.graph.removed << " unitigs_out " << st.graph.unitigs_out << " longest " << st.graph.longest << " kmers_colored "
-         << st.kmers_colored << " kmers_unplaced " << st.kmers_unplaced << " runs " << st.runs << " overflow " << st.overflow << " color_bytes " << st.color_bytes << endl;
-    for (size_t i = 0; i < st.color.size(); ++i)
-        cerr << "run-multi: color " << i << " lower " << st.color[i].lower << " upper " << st.color[i].upper << " distinct " << st.color[i].distinct << " kept "
-             << st.color[i].kept << endl;
-    if (verbose)
-        cerr << "run-multi: count " << tm.count_s << "s db-out " << tm.db_out_s << "s recount " << tm.recount_s << "s union " << tm.union_s << "s graph " << tm.graph_s
-             << "s color " << tm.color_s << "s serialise " << tm.serialise_s << "s gfa-out " << tm.gfa_out_s << "s load " << tm.load_s << "s call " << tm.call_s << "s" << endl;
-    return 0;
-}
-
+// (the reads sub-commands -- count, mask, smudge, qc, trim, build, build-multi, run, run-multi -- have their command lines in
+// pf_cli_reads.cpp, pf_cli_build.cpp and pf_cli_run.cpp; pf_cli_subs.hpp declares them)
 int main(int argc, char **argv) {
     if (argc < 2) { PrintUsage(); return 0; }
     if (!strcmp(argv[1], "run-multi")) return run_multi_main(argc, argv);
@@ -1519,8 +485,8 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[1], "filter-multi")) return pfh::filter_main(argc, argv, true);    // script/Filter-multi.R
     if (!strcmp(argv[1], "mask")) return mask_main(argc, argv);
     if (!strcmp(argv[1], "count")) return count_main(argc, argv);
-    if (!strcmp(argv[1], "build")) return build_main(argc, argv);
-    if (!strcmp(argv[1], "build-multi")) return build_multi_main(argc, argv);
+    if (!strcmp(argv[1], "build")) return build_main(argc, argv, false);
+    if (!strcmp(argv[1], "build-multi")) return build_main(argc, argv, true);
     if (!strcmp(argv[1], "trim")) return trim_main(argc, argv);
     if (!strcmp(argv[1], "qc")) return qc_main(argc, argv);
     if (!strcmp(argv[1], "smudge")) return smudge_main(argc, argv);

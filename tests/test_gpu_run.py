@@ -325,7 +325,7 @@ def test_run_against_the_chain(chain, tmp_path, name, tag, extra):
 
 def test_no_surviving_kmer_ends_with_the_calling_runs_message(tmp_path):
     """every k-mer occurs once or twice, L = 10: the masking leaves nothing and the graph is the header line alone.  `run` says on
-    stdout what the calling run says about such a graph (pf_main.cpp words it and leaves with EXIT_FAILURE), with that exit status,
+    stdout what the calling run says about such a graph (RunCli::failed in pf_cli_run.cpp words it and leaves with EXIT_FAILURE), with that exit status,
     and leaves nothing under an output name."""
     rng = np.random.default_rng(4)
     reads = [bytes(b"ACGT"[c] for c in rng.integers(0, 4, size=60)) for _ in range(40)]
