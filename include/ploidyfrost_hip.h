@@ -76,7 +76,7 @@ enum pf_kernel {
     PF_K_GUNZIP, /* K-GUNZIP: everything one pf_inflate_gzip launches (find, count, chain, decode, window, resolve with the CRC), timed as one launch; unit: inflated bytes */
     PF_K_FASTA, /* K-FASTA: everything the index of one pf_fasta_index / pf_count_fasta / pf_maskcount_fasta / pf_color_fasta call launches (newlines, lines, words, scans, compact, table), timed as one launch; the core behind it is timed under its own kernel; unit: bytes of the chunk */
     PF_K_DEFLATE, /* K-DEFLATE: everything one pf_deflate_bgzf launches (deflate, scan of the members' sizes, pack), timed as one launch; unit: bytes of text */
-    PF_K_CLIP, /* K-CLIP: the kernels one pf_trim_fastq* / pf_trim_table_fastq* / pf_*_fastq*_trimmed call launches to clip adapters while a clip is open (one per file), timed as one launch inside the call's own; unit: records */ PF_K_PALIN, /* K-PALIN: the kernel one pf_trim_fastq_pair / pf_trim_table_fastq_pair / pf_*_fastq_pair_trimmed call launches behind K-CLIP's while a clip with prefix pairs is open (palindrome mode), timed as one launch inside the call's own; unit: pairs */ PF_K_QC, /* K-QC: the kernel one pf_qc_fastq call, or one pf_trim_fastq* / pf_trim_table_fastq* / pf_*_fastq*_trimmed call while a report is open, launches per file to add its records to the report's tables, timed as one launch per file inside the call's own; unit: records */ PF_K_HETPAIR, /* K-HETPAIR: everything one pf_hetpairs launches (flag, scan, write, table), timed as one launch; unit: keys in range */
+    PF_K_CLIP, /* K-CLIP: the kernels one pf_trim_fastq* / pf_trim_table_fastq* / pf_*_fastq*_trimmed call launches to clip adapters while a clip is open (one per file), timed as one launch inside the call's own; unit: records */ PF_K_PALIN, /* K-PALIN: the kernel one pf_trim_fastq_pair / pf_trim_table_fastq_pair / pf_*_fastq_pair_trimmed call launches behind K-CLIP's while a clip with prefix pairs is open (palindrome mode), timed as one launch inside the call's own; unit: pairs */ PF_K_QC, /* K-QC: the kernel one pf_qc_fastq call, or one pf_trim_fastq* / pf_trim_table_fastq* / pf_*_fastq*_trimmed call while a report is open, launches per file to add its records to the report's tables, timed as one launch per file inside the call's own; unit: records */ PF_K_HETPAIR, /* K-HETPAIR: everything one pf_hetpairs launches (flag, scan, write, table), timed as one launch; unit: keys in range */ PF_K_DEDUP, /* K-DEDUP: the kernels one pf_trim_fastq* / pf_trim_table_fastq* / pf_*_fastq*_trimmed call launches while a dedup is open, or one pf_dedup_keys call (growth, insert, verdict), timed as one launch inside the call's own; unit: units that take part */
     PF_K_COUNT_
 };
 int pf_enable_timing(pf_ctx *, int on);
@@ -511,6 +511,26 @@ int pf_qc_get(pf_ctx *, int side, int stage, uint64_t *words);
 int pf_qc_clip_get(pf_ctx *, int side, uint64_t *words);
 int pf_qc_fastq(pf_ctx *, int side, const char *text, uint64_t n_bytes, int final, uint64_t *bytes_used, uint64_t *n_records, uint64_t *bad_record);
 int pf_qc_end(pf_ctx *);
+/* K-DEDUP: duplicate reads dropped on the device (csrc/pf_dedup.hip; the rule -- unit, key, decision, statistics: csrc/pf_dedup_rule.hpp).
+ * A dedup is state on the context, opened and closed as a clip and a report are: a hash table in HBM that lives across the chunks of a
+ * stream, and the number of units taken.  While one is open, pf_trim_fastq[_pair], pf_trim_table_fastq[_pair],
+ * pf_count_fastq[_pair]_trimmed and pf_maskcount_fastq[_pair]_trimmed give every unit K-TRIM keeps (a record; for a pair record r of
+ * both files, both kept) the 128-bit key of its raw sequence line(s) -- the first `bases` bases, 0 = the whole read -- and drop every
+ * unit whose key an earlier unit of the stream had: its interval becomes empty in every file, as if MINLEN had dropped it, and
+ * pf_trim_stats describes what is left.  They accept n_steps == 0 as with a clip open.  A refused call inserts nothing and does not
+ * advance the unit counter.  With none open they launch and allocate nothing new.  initial_slots: 0 = default, rounded up to a power
+ * of two, at least 64; the table grows by itself (2 * (entries + units of the call) <= slots before every call) and a table that
+ * does not fit the free device memory is refused by name with the units reached (PF_ERR_OVERFLOW).
+ * pf_dedup_stats_get: one pass over the table.  levels[c - 1] = keys with c copies, levels[9] = 10 or more.
+ * pf_dedup_keys: the table by itself, for tests and tools -- n keys (two words each, a zero word counts as 1) as units
+ * next_unit .. next_unit + n - 1 that all take part; keep[i] = 1 when key i had not been seen before (in the stream or in the call).
+ * A second begin, and stats / keys / end without a begin: PF_ERR_ARG by name.  A probe that went round the table (impossible at half
+ * load) is refused by name with PF_ERR_OVERFLOW by pf_dedup_stats_get and by pf_dedup_end, which frees the table all the same. */
+typedef struct pf_dedup_stats { uint64_t units, unique, duplicates, max_copies, levels[10], slots, growths; } pf_dedup_stats;
+int pf_dedup_begin(pf_ctx *, uint32_t bases /* 0 = whole read, else 16 .. 4096 */, uint64_t initial_slots /* 0 = default; rounded up to a power of two, at least 64 */);
+int pf_dedup_stats_get(pf_ctx *, pf_dedup_stats *);
+int pf_dedup_end(pf_ctx *);
+int pf_dedup_keys(pf_ctx *, const uint64_t *keys /* [host|dev], 2n words */, uint64_t n, uint8_t *keep /* [host|dev], n */);
 /* K-INFLATE: blocked gzip (BGZF: what bgzip, bcl2fastq2 and BCL Convert write) inflated on the device, where pf_*_fastq read their text.
  * The rule -- the member header, RFC 1951, the refusals by name -- is csrc/pf_inflate_rule.hpp; the decoder one lane runs is
  * csrc/pf_inflate_core.hpp, shared with the host.  One wavefront per member; the CRC-32 of every member's text is checked against

@@ -309,6 +309,28 @@ int pfh_trim_fastq_pair_chunk_clip(const char *text1, uint64_t n1, const char *t
  * pfh_qc_report_text: tables [side][stage][PF_QC_TABLE_WORDS], clip [side][PF_QC_CLIP_WORDS] or null; *len = the bytes of the text, of
  * which at most cap go to out.  pfh_qc_phred_hint: 33, 64 or 0 from the smallest quality byte and the number of reads that held one. */
 void pfh_reads_report(const char *path);
+/* Duplicate reads dropped (K-DEDUP, `--dedup`; the rule: csrc/pf_dedup_rule.hpp).  pfh_reads_dedup(on, bases, initial_slots): the next
+ * pfh_trim_fastq[_pair], pfh_run_fastq[_trimmed] or pfh_run_multi_fastq[_trimmed] call of this thread runs with a dedup, as `--dedup
+ * [--dedup-bases N] [--dedup-initial-slots N]` does -- one table per unit of the command (a `trim` command: all its inputs; `run`: all
+ * -i files together, each pair on its own; `run-multi`: the same per sample); no step is needed beside it, and in run / run-multi it
+ * turns trimming on as a step does.  pfh_reads_dedup_report: what that call found, summed over its units (max_copies and slots: the
+ * largest).  The host's plain restatement, no device: pfh_dedup_key: the key of one unit (seq2 NULL, n2 0: a single read); bases 0 =
+ * the whole read, else 16 .. 4096; -1 = refused (pfh_last_error(NULL)).  pfh_dedup_units: the keys (two words each) of the units of a
+ * whole stream in order, participates (may be NULL: all) -> keep[i] (1 = stays: the first of its key, or takes no part) and the
+ * statistics (slots and growths 0).  pfh_trim_fastq[_pair]_chunk_dedup: what pf_trim_fastq[_pair] gives for one chunk while a dedup is
+ * open and no clip, given the keys of the units that took part before (seen_keys, two words each, repeats allowed); rec_keys
+ * (may be NULL): two words per unit of the chunk, 0 0 for one that takes no part; at most cap entries per array.  n_steps may be 0. */
+void pfh_reads_dedup(int on, uint32_t bases, uint64_t initial_slots);
+void pfh_reads_dedup_report(pf_dedup_stats *stats);
+int pfh_dedup_key(const char *seq1, uint64_t n1, const char *seq2, uint64_t n2 /* NULL, 0: single */, uint32_t bases, uint64_t key[2]);
+int pfh_dedup_units(const uint64_t *keys, const uint8_t *participates, uint64_t n, uint8_t *keep, pf_dedup_stats *stats);
+int pfh_trim_fastq_chunk_dedup(const char *text, uint64_t n, int final, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, uint32_t bases,
+                               const uint64_t *seen_keys, uint64_t n_seen, char *out, uint64_t *out_bytes, uint64_t *bytes_used, uint32_t *rec_begin,
+                               uint32_t *rec_len, uint64_t *rec_keys, uint64_t cap, uint64_t *n_records, pf_trim_stats *stats, uint64_t *bad_record);
+int pfh_trim_fastq_pair_chunk_dedup(const char *text1, uint64_t n1, const char *text2, uint64_t n2, int final, const pf_trim_step *steps, uint32_t n_steps,
+                                    uint32_t phred, uint32_t bases, const uint64_t *seen_keys, uint64_t n_seen, char *out[4], uint64_t out_bytes[4],
+                                    uint64_t bytes_used[2], uint32_t *rec_begin[2], uint32_t *rec_len[2], uint64_t *rec_keys, uint64_t cap, uint64_t *n_records,
+                                    pf_trim_stats stats[2], uint64_t *bad_record);
 int pfh_qc_fastq(const char *const *inputs1, uint32_t n1, const char *const *inputs2, uint32_t n2, const char *report_path, uint32_t phred, uint64_t chunk_bytes,
                  int device);
 int pfh_qc_fastq_chunk(const char *text, uint64_t n, int final, uint32_t phred, uint32_t file_side, int trimmed, const pf_trim_step *steps, uint32_t n_steps,

@@ -190,6 +190,39 @@ struct ClipCli {
     }
 };
 
+// ---- `--dedup [--dedup-bases N] [--dedup-initial-slots N]` of trim, run and run-multi (K-DEDUP) ----
+struct DedupCli {
+    string bases, slots;
+    bool seen = false, bases_seen = false, slots_seen = false;
+    int take(int argc, char **argv, int &i, string &why) {
+        const string a = argv[i];
+        if (a == "--dedup") { seen = true; return 1; }
+        if (a != "--dedup-bases" && a != "--dedup-initial-slots") return 0;
+        const char *v = value_of(argc, argv, i, why);
+        if (!v) return -1;
+        if (a == "--dedup-bases") { bases = v; bases_seen = true; }
+        else { slots = v; slots_seen = true; }
+        return 1;
+    }
+    // after the last argument: "" = accepted
+    string finish(pfh::DedupOptions &opt) const {
+        if (!seen) {
+            if (bases_seen) return "--dedup-bases needs --dedup: the bases are read by the duplicate removal alone";
+            if (slots_seen) return "--dedup-initial-slots needs --dedup: the table is the duplicate removal's alone";
+            return "";
+        }
+        opt.on = true;
+        if (bases_seen && !ClipCli::number(bases, pf_dedup::MIN_BASES, pf_dedup::MAX_BASES, opt.bases)) return "--dedup-bases takes 16 to 4096, not '" + bases + "'";
+        if (slots_seen) {
+            if (slots.empty() || slots.size() > 12) return "--dedup-initial-slots takes a number of slots up to 2^36, not '" + slots + "'";
+            for (char ch : slots) if (ch < '0' || ch > '9') return "--dedup-initial-slots takes a number of slots up to 2^36, not '" + slots + "'";
+            opt.initial_slots = stoull(slots);
+            if (opt.initial_slots > (1ull << 36)) return "--dedup-initial-slots takes a number of slots up to 2^36, not '" + slots + "'";
+        }
+        return "";
+    }
+};
+
 // ---- `run STEP...` / `run-multi STEP...`: the words and options of step 1 as `trim` takes them -- the same refusals and texts ----
 struct TrimCli {
     vector<string> words;   // the positional words: the steps
@@ -197,12 +230,14 @@ struct TrimCli {
     PhredCli phred;
     string pending1;        // a -1 whose -2 has not come yet
     ClipCli clip;           // --adapters and what goes with it
+    DedupCli dedup;         // --dedup and what goes with it
     int take(int argc, char **argv, int &i, const char *sub, vector<string> &files, string &why) {
         const string a = argv[i];
         if (a.empty() || a[0] != '-') { words.push_back(a); return 1; }
         for (const char *o : {"--trimlog", "-o1", "-u1", "-o2", "-u2"})
             if (a == o) { why = a + " is not built into " + sub + ": `trim` writes the trimmed reads, the unpaired ones and the log"; return -1; }
         if (const int taken = clip.take(argc, argv, i, why)) return taken;
+        if (const int taken = dedup.take(argc, argv, i, why)) return taken;
         if (const int taken = phred.take(argc, argv, i, why)) return taken;
         if (a != "-1" && a != "-2") return 0;
         const char *v = value_of(argc, argv, i, why);
@@ -221,10 +256,11 @@ struct TrimCli {
     }
     string no_second() const { return "-1 " + pending1 + " has no -2 behind it (the files of a pair come as -1 <r1.fq> -2 <r2.fq>)"; }
     // after the last argument: "" = accepted, with the steps parsed
-    string finish(const char *sub, vector<pf_trim_step> &steps, pfh::ClipOptions &clip_opt) const {
+    string finish(const char *sub, vector<pf_trim_step> &steps, pfh::ClipOptions &clip_opt, pfh::DedupOptions &dedup_opt) const {
         if (!pending1.empty()) return no_second();
         { const string why = clip.finish(clip_opt); if (!why.empty()) return why; }
-        if (words.empty() && clip_opt.on()) return "";   // --adapters turns trimming on as a step does
+        { const string why = dedup.finish(dedup_opt); if (!why.empty()) return why; }
+        if (words.empty() && (clip_opt.on() || dedup_opt.on)) return "";   // --adapters and --dedup turn trimming on as a step does
         if (words.empty()) {
             if (pair_seen) return string("-1 / -2 need a step: the files of a pair are trimmed together (two files without trimming go with -i: ") + sub + " -i r1.fq -i r2.fq)";
             if (phred.seen) return "--phred needs a step: the quality offset is read by the trimming alone";

@@ -250,28 +250,35 @@ int trim_main(int argc, char **argv) {
     ReadsCli reads(ReadsCli::GZ | ReadsCli::CHUNK);
     PhredCli phred;
     ClipCli clip_cli;
+    DedupCli dedup_cli;
     const char *pair_opts[6] = {"-1", "-2", "-o1", "-u1", "-o2", "-u2"};
+    bool fasta_seen = false;
+    // --fasta is refused in front of everything that stands behind it, with --dedup by the pair of options, as run words it
+    auto fasta_refusal = [&]() { return refuse(dedup_cli.seen ? "--fasta does not go with --dedup" : "--fasta does not go with trim: FASTA has no qualities to trim"); };
+    auto bail = [&](const string &m) { return fasta_seen ? fasta_refusal() : refuse(m); };
     for (int i = 2; i < argc; ++i) {
         const string a = argv[i];
         string why;
         if (a.empty() || a[0] != '-') { words.push_back(a); continue; }
         if (a == "--gz-out") { opt.gz_out = true; continue; }
-        if (a == "--fasta") return refuse("--fasta does not go with trim: FASTA has no qualities to trim");
+        if (a == "--fasta") { fasta_seen = true; continue; }   // refused below, worded by what else was given
         int taken = reads.take(argc, argv, i, why);
         if (!taken) taken = clip_cli.take(argc, argv, i, why);
+        if (!taken) taken = dedup_cli.take(argc, argv, i, why);
         if (!taken) taken = phred.take(argc, argv, i, why);
-        if (taken < 0) return refuse(why);
+        if (taken < 0) return bail(why);
         if (taken) continue;
         const int pair = (int)(std::find_if(pair_opts, pair_opts + 6, [&](const char *o) { return a == o; }) - pair_opts);
-        if (pair == 6 && a != "-i" && a != "-o" && a != "--trimlog" && a != "--report") return refuse("unknown option " + a);
+        if (pair == 6 && a != "-i" && a != "-o" && a != "--trimlog" && a != "--report") return bail("unknown option " + a);
         const char *val = value_of(argc, argv, i, why);
-        if (!val) return refuse(why);
+        if (!val) return bail(why);
         if (a == "-i") inputs.push_back(val);
         else if (a == "-o") out = val;
         else if (a == "--trimlog") opt.trimlog = val;
-        else if (a == "--report") { if (!*val) return refuse("--report needs a value"); opt.report = val; }
+        else if (a == "--report") { if (!*val) return bail("--report needs a value"); opt.report = val; }
         else (pair < 2 ? in_pair[pair] : out_pair[pair - 2]) = val;
     }
+    if (fasta_seen) return fasta_refusal();
     opt.gz = reads.gz;
     opt.chunk_bytes = reads.chunk_bytes;
     opt.phred = phred.phred;
@@ -282,8 +289,9 @@ int trim_main(int argc, char **argv) {
         vector<pf_trim::Step> steps;
         size_t bad = 0;
         { const string why = clip_cli.finish(opt.clip); if (!why.empty()) return refuse(why); }
+        { const string why = dedup_cli.finish(opt.dedup); if (!why.empty()) return refuse(why); }
         const int c = pf_trim::parse_steps(w.data(), w.size(), steps, &bad);
-        if (c == pf_trim::REFUSE_NO_STEP && !opt.clip.on()) return refuse(pf_trim::refusal_text(c));
+        if (c == pf_trim::REFUSE_NO_STEP && !opt.clip.on() && !opt.dedup.on) return refuse(pf_trim::refusal_text(c));
         if (c && c != pf_trim::REFUSE_NO_STEP) return refuse(words[bad] + ": " + pf_trim::refusal_text(c));
         for (const pf_trim::Step &st : steps) opt.steps.push_back(pf_trim_step{st.kind, st.a, st.b});
     }
@@ -297,21 +305,24 @@ int trim_main(int argc, char **argv) {
     pfh::TrimTimes tm;
     pfh::ClipReport clip;
     pfh::QcReport qc;
+    pf_dedup_stats dedup = {};
     string err;
     if (pair_in) {
         for (int j = 0; j < 2; ++j)
             if (in_pair[j].empty()) return refuse(string(pair_opts[j]) + " <r" + to_string(j + 1) + ".fq> is missing");
         for (int j = 0; j < 4; ++j)
             if (out_pair[j].empty()) return refuse(string(pair_opts[2 + j]) + " <out.fq> is missing");
-        if (pfh::trim_fastq_pair(in_pair[0], in_pair[1], out_pair, opt, 0, st, &tm, err, &clip, &qc)) return failed(err);
+        if (pfh::trim_fastq_pair(in_pair[0], in_pair[1], out_pair, opt, 0, st, &tm, err, &clip, &qc, &dedup)) return failed(err);
         if (opt.clip.on()) cerr << pfh::clip_line(clip) << endl;
+        if (opt.dedup.on) cerr << pfh::dedup_line(dedup) << endl;
         cerr << "trim: pairs " << st[0].reads << " both " << st[0].both << " forward_only " << st[0].only1 << " reverse_only " << st[0].only2 << " dropped "
              << st[0].neither << " bases " << st[0].bases + st[1].bases << " bases_kept " << st[0].bases_kept + st[1].bases_kept << endl;
     } else {
         if (inputs.empty()) return refuse("-i <reads.fq> is missing (or -1 <r1.fq> -2 <r2.fq> for a pair)");
         if (out.empty()) return refuse("-o <trimmed.fq> is missing");
-        if (pfh::trim_fastq(inputs, out, opt, 0, st[0], &tm, err, &clip, &qc)) return failed(err);
+        if (pfh::trim_fastq(inputs, out, opt, 0, st[0], &tm, err, &clip, &qc, &dedup)) return failed(err);
         if (opt.clip.on()) cerr << pfh::clip_line(clip) << endl;
+        if (opt.dedup.on) cerr << pfh::dedup_line(dedup) << endl;
         cerr << "trim: reads " << st[0].reads << " kept " << st[0].kept << " dropped " << st[0].dropped << " bases " << st[0].bases << " bases_kept "
              << st[0].bases_kept << endl;
     }

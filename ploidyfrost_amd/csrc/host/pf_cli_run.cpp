@@ -67,7 +67,7 @@ struct RunCli {
     // behind the last word, in front of the sub-command's rules for its inputs: the trim words ("" = accepted)
     string finish_trim() {
         opt.trim.phred = tc.phred.phred;
-        return tc.finish(sub, opt.trim.steps, opt.trim.clip);
+        return tc.finish(sub, opt.trim.steps, opt.trim.clip, opt.trim.dedup);
     }
     // behind those rules: the fields of the count and of the reads, what the host layer refuses, the range checks of the calling run
     string finish() {
@@ -170,6 +170,7 @@ int run_main(int argc, char **argv) {
     if (pfh::run_fastq(inputs, cli.out, opt, 0, st, &tm, err)) return cli.failed(err, "CompactedDBG::read()");
     for (size_t u = 0; u < pfh::trim_unit_count(inputs.size(), opt.paired) && opt.trim.on(); ++u) {   // one line per `trim` of the equivalent chain
         if (u < st.clip.size()) cerr << pfh::clip_line(st.clip[u]) << endl;
+        if (u < st.dedup.size()) cerr << pfh::dedup_line(st.dedup[u]) << endl;
         cerr << pfh::trim_unit_line(&st.trim[opt.paired ? 2 * u : 0], opt.paired) << endl;
     }
     for (const string &l : st.qc.lines()) cerr << l << endl;
@@ -261,6 +262,7 @@ int run_multi_main(int argc, char **argv) {
     for (size_t c = 0; c < st.trim.size(); ++c)   // one line per `trim` of the equivalent chain, in the order given
         for (size_t u = 0; u < pfh::trim_unit_count(samples[c].inputs.size(), samples[c].paired); ++u) {
             if (c < st.clip.size() && u < st.clip[c].size()) cerr << pfh::clip_line(st.clip[c][u]) << endl;
+            if (c < st.dedup.size() && u < st.dedup[c].size()) cerr << pfh::dedup_line(st.dedup[c][u]) << endl;
             cerr << pfh::trim_unit_line(&st.trim[c][samples[c].paired ? 2 * u : 0], samples[c].paired) << endl;
         }
     cerr << "run-multi: colors " << st.colors << " reads " << st.reads << " bases " << st.bases << " kmers " << st.kmers << " bad " << st.bad << " distinct "

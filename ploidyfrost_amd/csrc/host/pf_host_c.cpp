@@ -508,6 +508,111 @@ int pfh_qc_report_text(const uint64_t *tables, const uint64_t *clip, uint32_t ph
     return 0;
 }
 
+// ---- duplicate reads dropped (K-DEDUP) ----------------------------------------------------------------
+// `--dedup`: the switch of the next trim / run call of this thread, and what that call reported (over all its units)
+static thread_local pfh::DedupOptions g_reads_dedup;
+static thread_local pf_dedup_stats g_dedup_report = {};
+void pfh_reads_dedup(int on, uint32_t bases, uint64_t initial_slots) {
+    g_reads_dedup = pfh::DedupOptions{};
+    g_reads_dedup.on = on != 0;
+    g_reads_dedup.bases = bases;
+    g_reads_dedup.initial_slots = initial_slots;
+}
+static pfh::DedupOptions take_reads_dedup() {
+    const pfh::DedupOptions d = g_reads_dedup;
+    g_reads_dedup = pfh::DedupOptions{};
+    g_dedup_report = pf_dedup_stats{};
+    return d;
+}
+static void dedup_report_add(const pf_dedup_stats &s) {
+    pf_dedup_stats &r = g_dedup_report;
+    r.units += s.units; r.unique += s.unique; r.duplicates += s.duplicates;
+    r.max_copies = std::max(r.max_copies, s.max_copies);
+    for (uint32_t l = 0; l < pf_dedup::LEVELS; ++l) r.levels[l] += s.levels[l];
+    r.slots = std::max(r.slots, s.slots);
+    r.growths += s.growths;
+}
+void pfh_reads_dedup_report(pf_dedup_stats *stats) { if (stats) *stats = g_dedup_report; }
+int pfh_dedup_key(const char *seq1, uint64_t n1, const char *seq2, uint64_t n2, uint32_t bases, uint64_t key[2]) {
+    auto refuse = [&](const std::string &m) { g_open_err = "pfh_dedup_key: " + m; return -1; };
+    if (!key) return refuse("key is needed");
+    if ((n1 && !seq1) || (n2 && !seq2)) return refuse("the reads are needed");
+    if (!pf_dedup::bases_ok(bases)) return refuse("bases is 0 (the whole read) or 16 .. 4096, not " + std::to_string(bases));
+    if (n1 > 0xFFFFFFFFull || n2 > 0xFFFFFFFFull) return refuse("a read holds fewer than 2^32 bases");
+    pf_dedup::key_of(seq1 ? seq1 : "", (uint32_t)n1, seq2 ? seq2 : "", (uint32_t)n2, seq2 != nullptr, bases, key);
+    return 0;
+}
+int pfh_dedup_units(const uint64_t *keys, const uint8_t *participates, uint64_t n, uint8_t *keep, pf_dedup_stats *stats) {
+    if (n && !keys) { g_open_err = "pfh_dedup_units: keys are needed"; return -1; }
+    pfh::DedupSeen seen;
+    pfh::dedup_units(seen, keys, participates, n, keep);
+    if (stats) *stats = pfh::dedup_stats_of(seen);
+    return 0;
+}
+// what pf_trim_fastq / pf_trim_fastq_pair give for one chunk while a dedup is open, given the keys of the units that took part before
+static int trim_chunk_dedup(const char *who, int n_files, const char *const *text_in, const uint64_t *n_in, int final, const pf_trim_step *steps, uint32_t n_steps,
+                            uint32_t phred, uint32_t bases, const uint64_t *seen_keys, uint64_t n_seen, char *const *out, uint64_t *out_bytes,
+                            uint64_t *bytes_used, uint32_t *const *rec_begin, uint32_t *const *rec_len, uint64_t *rec_keys, uint64_t cap, uint64_t *n_records,
+                            pf_trim_stats *stats, uint64_t *bad_record) {
+    auto refuse = [&](const std::string &m) { g_open_err = std::string(who) + ": " + m; return -1; };
+    if (!pf_dedup::bases_ok(bases)) return refuse("bases is 0 (the whole read) or 16 .. 4096, not " + std::to_string(bases));
+    if (n_seen && !seen_keys) return refuse("the keys seen before are needed");
+    {
+        pfh::TrimOptions o;
+        if (steps) o.steps.assign(steps, steps + n_steps);
+        o.phred = phred;
+        o.dedup.on = true;
+        o.dedup.bases = bases;
+        if (pfh::trim_options_clause(o, g_open_err)) return -1;
+    }
+    pfh::DedupSeen seen;
+    pfh::dedup_units(seen, seen_keys, nullptr, n_seen, nullptr);
+    const int n_dest = n_files == 2 ? 4 : 1;
+    std::string o[4];
+    std::vector<uint32_t> rb[2], rl[2];
+    std::vector<uint64_t> keys;
+    uint64_t used[2] = {0, 0}, recs = 0, bad = 0;
+    pf_trim::Stats st[2] = {};
+    const char *text[2] = {"", ""};
+    uint64_t nn[2] = {0, 0};
+    for (int f = 0; f < n_files; ++f)
+        if (text_in[f]) { text[f] = text_in[f]; nn[f] = n_in[f]; }
+    const int clause = pfh::dedup_trim_chunk(n_files, text, nn, final != 0, reinterpret_cast<const pf_trim::Step *>(steps), n_steps, phred, bases, seen, o, used, recs,
+                                             bad, rb, rl, st, &keys);
+    for (int d = 0; d < n_dest; ++d) {
+        if (out_bytes) out_bytes[d] = o[d].size();
+        if (out && out[d] && !o[d].empty()) memcpy(out[d], o[d].data(), o[d].size());
+    }
+    for (int f = 0; f < n_files; ++f) {
+        if (bytes_used) bytes_used[f] = used[f];
+        if (stats) memcpy(&stats[f], &st[f], sizeof st[f]);
+        for (uint64_t i = 0; i < cap && i < rb[f].size(); ++i) {
+            if (rec_begin && rec_begin[f]) rec_begin[f][i] = rb[f][i];
+            if (rec_len && rec_len[f]) rec_len[f][i] = rl[f][i];
+        }
+    }
+    if (rec_keys)
+        for (uint64_t i = 0; i < 2 * cap && i < keys.size(); ++i) rec_keys[i] = keys[i];
+    if (n_records) *n_records = recs;
+    if (bad_record) *bad_record = bad;
+    return clause;
+}
+int pfh_trim_fastq_chunk_dedup(const char *text, uint64_t n, int final, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, uint32_t bases,
+                               const uint64_t *seen_keys, uint64_t n_seen, char *out, uint64_t *out_bytes, uint64_t *bytes_used, uint32_t *rec_begin,
+                               uint32_t *rec_len, uint64_t *rec_keys, uint64_t cap, uint64_t *n_records, pf_trim_stats *stats, uint64_t *bad_record) {
+    return trim_chunk_dedup("pfh_trim_fastq_chunk_dedup", 1, &text, &n, final, steps, n_steps, phred, bases, seen_keys, n_seen, &out, out_bytes, bytes_used,
+                            &rec_begin, &rec_len, rec_keys, cap, n_records, stats, bad_record);
+}
+int pfh_trim_fastq_pair_chunk_dedup(const char *text1, uint64_t n1, const char *text2, uint64_t n2, int final, const pf_trim_step *steps, uint32_t n_steps,
+                                    uint32_t phred, uint32_t bases, const uint64_t *seen_keys, uint64_t n_seen, char *out[4], uint64_t out_bytes[4],
+                                    uint64_t bytes_used[2], uint32_t *rec_begin[2], uint32_t *rec_len[2], uint64_t *rec_keys, uint64_t cap, uint64_t *n_records,
+                                    pf_trim_stats stats[2], uint64_t *bad_record) {
+    const char *text[2] = {text1, text2};
+    const uint64_t n[2] = {n1, n2};
+    return trim_chunk_dedup("pfh_trim_fastq_pair_chunk_dedup", 2, text, n, final, steps, n_steps, phred, bases, seen_keys, n_seen, out, out_bytes, bytes_used,
+                            rec_begin, rec_len, rec_keys, cap, n_records, stats, bad_record);
+}
+
 // ---- reads quality-trimmed (K-TRIM) ------------------------------------------------------------------
 static pfh::TrimOptions trim_options(const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, const char *trimlog, uint64_t chunk_bytes) {
     pfh::TrimOptions opt;
@@ -525,6 +630,7 @@ static pfh::TrimOptions trim_stream_options(const pf_trim_step *steps, uint32_t 
     pfh::TrimOptions opt = trim_options(steps, n_steps, phred, trimlog, chunk_bytes);
     opt.clip = clip;
     opt.report = take_reads_report();
+    opt.dedup = take_reads_dedup();
     return opt;
 }
 int pfh_trim_fastq(const char *const *inputs, uint32_t n_inputs, const char *out_path, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred,
@@ -535,7 +641,8 @@ int pfh_trim_fastq(const char *const *inputs, uint32_t n_inputs, const char *out
         std::vector<std::string> in;
         for (uint32_t i = 0; i < n_inputs; ++i) in.push_back(inputs[i] ? inputs[i] : "");
         pf_trim_stats st = {};
-        const int rc = pfh::trim_fastq(in, out_path, trim_stream_options(steps, n_steps, phred, trimlog, chunk_bytes, clip), device, st, nullptr, g_open_err, &g_clip_report);
+        const pfh::TrimOptions topt = trim_stream_options(steps, n_steps, phred, trimlog, chunk_bytes, clip);
+        const int rc = pfh::trim_fastq(in, out_path, topt, device, st, nullptr, g_open_err, &g_clip_report, nullptr, &g_dedup_report);
         if (stats) *stats = st;
         return rc;
     } catch (const std::exception &e) {
@@ -553,7 +660,8 @@ int pfh_trim_fastq_pair(const char *in1, const char *in2, const char *const *out
     try {
         const std::string out[4] = {out_paths[0], out_paths[1], out_paths[2], out_paths[3]};
         pf_trim_stats st[2] = {};
-        const int rc = pfh::trim_fastq_pair(in1, in2, out, trim_stream_options(steps, n_steps, phred, trimlog, chunk_bytes, clip), device, st, nullptr, g_open_err, &g_clip_report);
+        const pfh::TrimOptions topt = trim_stream_options(steps, n_steps, phred, trimlog, chunk_bytes, clip);
+        const int rc = pfh::trim_fastq_pair(in1, in2, out, topt, device, st, nullptr, g_open_err, &g_clip_report, nullptr, &g_dedup_report);
         if (stats) { stats[0] = st[0]; stats[1] = st[1]; }
         return rc;
     } catch (const std::exception &e) {
@@ -833,10 +941,12 @@ static void clip_report_sum(const std::vector<pfh::ClipReport> &units) {
         }
     }
 }
-static void trim_inputs_from(const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, const pfh::ClipOptions &clip, pfh::TrimInputs &t) {
+static void trim_inputs_from(const pf_trim_step *steps, uint32_t n_steps, uint32_t phred, const pfh::ClipOptions &clip, const pfh::DedupOptions &dedup,
+                             pfh::TrimInputs &t) {
     t.steps.assign(steps, steps + (steps ? n_steps : 0));
     t.phred = phred;
     t.clip = clip;
+    t.dedup = dedup;
 }
 // `--smudge [--smudge-n N] [--smudge-pairs FILE]`: the switch of the next run call of this thread, and what that call found
 struct ReadsSmudge {
@@ -874,6 +984,7 @@ static void smudge_result_c(const pfh::SmudgeResult &r, pfh_smudge_result *out) 
 static int run_fastq_c(const char *who, const char *const *inputs, uint32_t n_inputs, int paired, const pf_trim_step *steps, uint32_t n_steps, uint32_t phred,
                        const char *out_prefix, const pfh_run_options *o, int device, pfh_run_stats *stats, pf_trim_stats *per_unit) {
     const pfh::ClipOptions clip = take_reads_adapters();   // taken first: a refusal below does not leave the switch to the next call
+    const pfh::DedupOptions dedup = take_reads_dedup();
     const ReadsSmudge smudge = take_reads_smudge();
     g_smudge_result = pfh_smudge_result{};
     if (!out_prefix || !o || (n_inputs && !inputs)) { g_open_err = std::string(who) + ": inputs, output prefix and options are needed"; return 1; }
@@ -890,7 +1001,7 @@ static int run_fastq_c(const char *who, const char *const *inputs, uint32_t n_in
             opt.call.model.only = o->model_only != 0;
             opt.call.model.source = o->model_source;
         }
-        trim_inputs_from(steps, n_steps, phred, clip, opt.trim);
+        trim_inputs_from(steps, n_steps, phred, clip, dedup, opt.trim);
         opt.report = take_reads_report();
         opt.paired = paired != 0;
         opt.smudge = smudge.on;
@@ -906,6 +1017,7 @@ static int run_fastq_c(const char *who, const char *const *inputs, uint32_t n_in
                                    st.graph.longest};
         if (per_unit) std::copy(st.trim.begin(), st.trim.end(), per_unit);
         clip_report_sum(st.clip);
+        for (const pf_dedup_stats &u : st.dedup) dedup_report_add(u);
         return rc;
     } catch (const std::exception &e) {
         g_open_err = std::string("ploidyfrost host layer: ") + e.what();
@@ -925,6 +1037,7 @@ static int run_multi_fastq_c(const char *who, const char *const *names, const ui
                              const pfh_run_options *o, const pf_filter_multi_opts *multi, int each_color, int device, pfh_run_multi_stats *stats,
                              uint64_t *per_color, pf_trim_stats *per_input) {
     const pfh::ClipOptions clip = take_reads_adapters();   // taken first: a refusal below does not leave the switch to the next call
+    const pfh::DedupOptions dedup = take_reads_dedup();
     { const ReadsSmudge sm = take_reads_smudge(); if (sm.on || sm.n_seen || !sm.pairs.empty()) { g_open_err = "run-multi: --smudge is not built into run-multi (`smudge` or `run --smudge` per sample)"; return 1; } }
     if (!take_reads_report().empty()) { g_open_err = "run-multi: --report is not built into run-multi (`trim --report` or `run --report` per sample)"; return 1; }
     if (!out_prefix || !o || (n_samples && (!names || !n_inputs_of))) { g_open_err = std::string(who) + ": samples, output prefix and options are needed"; return 1; }
@@ -941,7 +1054,7 @@ static int run_multi_fastq_c(const char *who, const char *const *names, const ui
         opt.gz = take_reads_gz();
         opt.fasta = take_reads_fasta();
         run_options_from(o, opt);
-        trim_inputs_from(steps, n_steps, phred, clip, opt.trim);
+        trim_inputs_from(steps, n_steps, phred, clip, dedup, opt.trim);
         mopt.call.threads = o->threads ? o->threads : 1;
         if (o->model_source >= 0) {
             if (!multi) { g_open_err = "run-multi: a model reads the coloured result streams behind the options of filter-multi: multi is needed"; return 1; }
@@ -965,6 +1078,8 @@ static int run_multi_fastq_c(const char *who, const char *const *names, const ui
                 per_color[4 * c + 3] = st.color[c].kept;
             }
         for (const auto &units : st.clip) clip_report_sum(units);
+        for (const auto &units : st.dedup)
+            for (const pf_dedup_stats &u : units) dedup_report_add(u);
         if (per_input) {   // one entry per input file; a single-ended sample's unit stands in its first entry
             uint64_t i = 0;
             for (uint32_t c = 0; c < n_samples; i += n_inputs_of[c], ++c)

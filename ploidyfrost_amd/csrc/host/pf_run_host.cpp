@@ -130,6 +130,7 @@ std::string trim_inputs_refusal(const std::vector<std::string> &inputs, bool pai
         o.steps = trim.steps;
         o.phred = trim.phred;
         o.clip = trim.clip;
+        o.dedup = trim.dedup;
         std::string e;
         if (trim_options_clause(o, e)) return e.substr(6);   // (worded "trim: ...": the caller puts its own name in front)
     }
@@ -158,7 +159,7 @@ void add_masked_stats(pf_maskcount_stats &a, const pf_maskcount_stats &b) {
 
 int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<ReadsInput> &inputs, bool paired, const TrimInputs &trim, uint64_t chunk_bytes,
                    bool masked, uint32_t low, uint32_t up, pf_trim_stats *unit_stats, pf_maskcount_stats *masked_stats, std::string &err,
-                   ClipCounts *unit_clip) {
+                   ClipCounts *unit_clip, pf_dedup_stats *unit_dedup) {
     const pf_trim_plan plan = {trim.steps.data(), (uint32_t)trim.steps.size(), trim.phred};
     // what the clip has counted since the last unit ended, into unit u
     ClipCounts clip_seen;
@@ -171,7 +172,19 @@ int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<ReadsInput> &
         return 0;
     };
     if (clip_unit(0, false)) return 1;
+    // --dedup: one table per unit, as one `trim --dedup` command of the equivalent chain has
+    auto dedup_begin = [&]() {
+        if (dedup_open(ctx, trim.dedup) == PF_OK) return 0;
+        err = std::string(who) + ": " + pf_last_error(ctx);
+        return 1;
+    };
+    auto dedup_end = [&](size_t u) {
+        if (dedup_close(ctx, trim.dedup, unit_dedup ? &unit_dedup[u] : nullptr) == PF_OK) return 0;
+        err = std::string(who) + ": " + pf_last_error(ctx);
+        return 1;
+    };
     if (!paired) {
+        if (dedup_begin()) return 1;
         StreamTimes stm;
         const int rc0 = stream_fastq(ctx, who, inputs, chunk_bytes, -1, "",
                             [&](const Chunk &c, Taken &t) {
@@ -187,9 +200,11 @@ int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<ReadsInput> &
                                 return (int)PF_OK;
                             },
                             stm, err);
-        return rc0 ? rc0 : clip_unit(0, true);
+        if (rc0) { if (trim.dedup.on) (void)pf_dedup_end(ctx); return rc0; }
+        return dedup_end(0) ? 1 : clip_unit(0, true);
     }
     for (size_t u = 0; u + 1 < inputs.size(); u += 2) {
+        if (dedup_begin()) return 1;
         PairStreamTimes ptm;
         if (stream_fastq_pair(ctx, who, inputs[u], inputs[u + 1], chunk_bytes,
                               [&](const PairChunk &c, PairTaken &t) {
@@ -206,9 +221,11 @@ int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<ReadsInput> &
                                   if (masked_stats) add_masked_stats(*masked_stats, ms);
                                   return (int)PF_OK;
                               },
-                              ptm, err))
+                              ptm, err)) {
+            if (trim.dedup.on) (void)pf_dedup_end(ctx);
             return 1;
-        if (clip_unit(u / 2, true)) return 1;
+        }
+        if (dedup_end(u / 2) || clip_unit(u / 2, true)) return 1;
     }
     return 0;
 }
@@ -220,6 +237,7 @@ std::string run_options_refusal(const RunOptions &opt) {
     if (!opt.smudge && opt.smudge_n_seen) return "--smudge-n needs --smudge (it is the haploid coverage of the k-mer pair report)";
     if (!opt.smudge && !opt.smudge_pairs.empty()) return "--smudge-pairs needs --smudge (it is the pairs file of the k-mer pair report)";
     if (opt.smudge && opt.smudge_n_seen && opt.smudge_n < 1) return "--smudge-n takes a haploid coverage of at least 1";
+    if (opt.fasta && opt.trim.dedup.on) return "--fasta does not go with --dedup";
     if (opt.fasta && opt.trim.clip.on()) return "--fasta does not go with --adapters (FASTA has no qualities to score an adapter by)";
     if (opt.fasta && (opt.trim.on() || opt.paired)) return "--fasta does not go with trim steps or -1 / -2 (FASTA has no qualities to trim)";
     { const int c = count_options_clause(count_options_of(opt), true); if (c) return pf_count::cut_text(c); }
@@ -293,6 +311,7 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
         unit_clip.assign(trim_unit_count(inputs.size(), opt.paired), ClipCounts{});
     }
     if (!opt.report.empty() && qc_open(ctx, opt.trim.phred, "run", err)) return 1;   // open over the first pass alone
+    if (opt.trim.dedup.on) stats.dedup.assign(trim_unit_count(inputs.size(), opt.paired), pf_dedup_stats{});   // (both passes decide alike; the first is reported)
 
     // ---- count: every k-mer of the reads, both strands, the user's cut-offs ----
     std::vector<uint64_t> rows;
@@ -302,7 +321,7 @@ int run_fastq(const std::vector<std::string> &inputs, const std::string &out_pre
         CountTimes ctm;
         if (trimming ? count_stream_with(ctx, "run", copt, [&](std::string &e) {
                            return stream_trimmed(ctx, "run", reads, opt.paired, opt.trim, opt.chunk_bytes, false, 0, 0, stats.trim.data(), nullptr, e,
-                                                 unit_clip.empty() ? nullptr : unit_clip.data());
+                                                 unit_clip.empty() ? nullptr : unit_clip.data(), stats.dedup.empty() ? nullptr : stats.dedup.data());
                        }, db, stats.counted, ctm, err)
                      : count_stream(ctx, "run", reads, copt, db, stats.counted, ctm, err))
             return 1;

@@ -22,6 +22,7 @@
 #include "pf_cdbg.hpp"
 #include "pf_count_host.hpp"
 #include "pf_clip_host.hpp"
+#include "pf_dedup_host.hpp"
 #include "pf_qc_host.hpp"
 #include "pf_hetpair_host.hpp"
 #include "ploidyfrost_hip.h"
@@ -74,7 +75,8 @@ struct TrimInputs {
     std::vector<pf_trim_step> steps;   // none: no trimming, the inputs are read as they are
     uint32_t phred = 33;
     ClipOptions clip;                  // --adapters: K-CLIP in front of the steps; turns trimming on as a step does
-    bool on() const { return !steps.empty() || clip.on(); }
+    DedupOptions dedup;                // --dedup: K-DEDUP behind the steps, a fresh table per unit in both passes; turns trimming on as a step does
+    bool on() const { return !steps.empty() || clip.on() || dedup.on; }
 };
 // A unit is what one `trim` command of the equivalent chain takes: all single-ended files together, or one pair.
 inline size_t trim_unit_count(size_t n_inputs, bool paired) { return paired ? n_inputs / 2 : 1; }
@@ -86,10 +88,11 @@ std::string trim_inputs_refusal(const std::vector<std::string> &inputs, bool pai
 // lock-step stream of pf_reads_stream.hpp; else they go through stream_fastq one after the other.  The inputs are what the preflight
 // made of them, the same for both passes.  unit_stats (may be null; paired: one entry per input file, else one entry) and masked_stats
 // (may be null) are added to.  unit_clip (may be null; a clip is open on the context): one entry per unit, what the clip counted
-// while the unit streamed.  0 = ok, else worded in err by `who`.
+// while the unit streamed.  With trim.dedup a fresh dedup is opened for every unit and closed behind it; unit_dedup (may be null): one
+// entry per unit, its statistics.  0 = ok, else worded in err by `who`.
 int stream_trimmed(pf_ctx *ctx, const char *who, const std::vector<ReadsInput> &inputs, bool paired, const TrimInputs &trim, uint64_t chunk_bytes,
                    bool masked, uint32_t low, uint32_t up, pf_trim_stats *unit_stats, pf_maskcount_stats *masked_stats, std::string &err,
-                   ClipCounts *unit_clip = nullptr);
+                   ClipCounts *unit_clip = nullptr, pf_dedup_stats *unit_dedup = nullptr);
 // the `trim:` line of a unit on stderr, in `trim`'s own format: st = the unit's statistics (paired: of file 1 and of file 2)
 std::string trim_unit_line(const pf_trim_stats *st, bool paired);
 
@@ -132,6 +135,7 @@ struct RunStats {
     std::string model_last_line;       // with a model: what the calling run prints last
     std::vector<pf_trim_stats> trim;   // STEP...: the trimming of the first pass (paired: one entry per input file, else one entry)
     std::vector<ClipReport> clip;      // --adapters: the clipping of the first pass, one entry per unit
+    std::vector<pf_dedup_stats> dedup; // --dedup: the duplicates of the first pass, one entry per unit
     QcReport qc;                       // --report: the tables of the first pass
     SmudgeResult smudge;               // --smudge
 };

@@ -156,6 +156,10 @@ int run_multi_fastq(const std::vector<MultiSample> &samples, const std::string &
         if (clip_open(ctx, adapters, opt.trim.clip) != PF_OK) return dev_fail();
         for (uint32_t c = 0; c < C; ++c) unit_clip[c].assign(trim_unit_count(samples[c].inputs.size(), samples[c].paired), ClipCounts{});
     }
+    if (opt.trim.dedup.on) {   // a fresh table per unit in both passes; the first one is reported
+        stats.dedup.resize(C);
+        for (uint32_t c = 0; c < C; ++c) stats.dedup[c].assign(trim_unit_count(samples[c].inputs.size(), samples[c].paired), pf_dedup_stats{});
+    }
     // ---- first pass, per sample: count, thresholds; the counters stay resident ----
     stats.colors = C;
     stats.color.assign(C, RunMultiColor{});
@@ -172,7 +176,8 @@ int run_multi_fastq(const std::vector<MultiSample> &samples, const std::string &
         std::string e;
         if (trimming ? count_stream_with(ctx, "run-multi", copt, [&](std::string &pe) {
                            return stream_trimmed(ctx, "run-multi", reads[c], samples[c].paired, opt.trim, opt.chunk_bytes, false, 0, 0, stats.trim[c].data(),
-                                                 nullptr, pe, unit_clip[c].empty() ? nullptr : unit_clip[c].data());
+                                                 nullptr, pe, unit_clip[c].empty() ? nullptr : unit_clip[c].data(),
+                                                 stats.dedup.empty() ? nullptr : stats.dedup[c].data());
                        }, db[c], counted, ctm, e)
                      : count_stream(ctx, "run-multi", reads[c], copt, db[c], counted, ctm, e))
             return fail(e);

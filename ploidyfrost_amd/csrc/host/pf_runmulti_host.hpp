@@ -50,6 +50,7 @@ struct RunMultiStats {
     std::vector<RunMultiColor> color;
     std::string model_last_line;
     std::vector<std::vector<ClipReport>> clip;      // --adapters: per sample the clipping of its first pass, one entry per unit
+    std::vector<std::vector<pf_dedup_stats>> dedup; // --dedup: per sample the duplicates of its first pass, one entry per unit
     std::vector<std::vector<pf_trim_stats>> trim;   // STEP...: per sample the trimming of its first pass (paired: per input file, else one entry)
 };
 struct RunMultiTimes {

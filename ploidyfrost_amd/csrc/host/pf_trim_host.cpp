@@ -64,6 +64,17 @@ int trim_qc_write(pf_ctx *ctx, const TrimOptions &opt, const OutFiles::File &f, 
     if (qc) *qc = std::move(r);
     return 0;
 }
+// --dedup: the table of the whole stream, opened on the fresh context; its statistics when the stream has ended
+int trim_dedup_open(pf_ctx *ctx, const TrimOptions &opt, std::string &err) {
+    if (dedup_open(ctx, opt.dedup) == PF_OK) return 0;
+    err = std::string("trim: ") + pf_last_error(ctx);
+    return 1;
+}
+int trim_dedup_report(pf_ctx *ctx, const TrimOptions &opt, pf_dedup_stats *dedup, std::string &err) {
+    if (dedup_close(ctx, opt.dedup, dedup) == PF_OK) return 0;
+    err = std::string("trim: ") + pf_last_error(ctx);
+    return 1;
+}
 int trim_clip_report(pf_ctx *ctx, const TrimOptions &opt, const pf_clip::Adapters &adapters, ClipReport *clip, std::string &err) {
     if (!opt.clip.on() || !clip || clip_report(ctx, adapters, opt.clip, *clip) == PF_OK) return 0;
     err = std::string("trim: ") + pf_last_error(ctx);
@@ -76,6 +87,11 @@ int trim_options_clause(const TrimOptions &opt, std::string &err) {
     uint32_t bad = 0;
     int c = pf_trim::steps_clause(reinterpret_cast<const pf_trim::Step *>(opt.steps.data()), (uint32_t)opt.steps.size(), opt.phred, &bad);
     if (c == pf_trim::REFUSE_NO_STEP && opt.clip.on() && opt.steps.empty()) c = 0;   // --adapters alone is a plan
+    if (c == pf_trim::REFUSE_NO_STEP && opt.dedup.on && opt.steps.empty()) c = 0;    // and so is --dedup
+    if (!c) {
+        const std::string why = dedup_options_refusal(opt.dedup);
+        if (!why.empty()) { err = "trim: " + why; return -1; }
+    }
     if (!c && opt.clip.on()) {
         int cc = pf_clip::params_clause(opt.clip.seed, opt.clip.score);
         if (!cc && opt.clip.pairs) cc = pf_clip::pair_params_clause(opt.clip.pair_score, opt.clip.pair_min);
@@ -89,7 +105,7 @@ int trim_options_clause(const TrimOptions &opt, std::string &err) {
 }
 
 int trim_fastq(const std::vector<std::string> &inputs, const std::string &out_path, const TrimOptions &opt, int device, pf_trim_stats &stats,
-               TrimTimes *times, std::string &err, ClipReport *clip, QcReport *qc) {
+               TrimTimes *times, std::string &err, ClipReport *clip, QcReport *qc, pf_dedup_stats *dedup) {
     stats = pf_trim_stats{};
     err.clear();
     if (opt.clip.on() && opt.clip.pairs) { err = "trim: --adapter-pairs needs -1 / -2"; return 1; }
@@ -103,7 +119,7 @@ int trim_fastq(const std::vector<std::string> &inputs, const std::string &out_pa
     pf_ctx *ctx = nullptr;
     if (trim_create(device, &ctx, err)) return 1;
     CtxGuard ctx_guard{ctx};
-    if (trim_clip_open(ctx, opt, adapters, err) || trim_qc_open(ctx, opt, err)) return 1;
+    if (trim_clip_open(ctx, opt, adapters, err) || trim_qc_open(ctx, opt, err) || trim_dedup_open(ctx, opt, err)) return 1;
     const auto t_stream = clk::now();
     OutFiles outs("trim");
     if (outs.open_all(paths, err)) return 1;
@@ -155,6 +171,7 @@ int trim_fastq(const std::vector<std::string> &inputs, const std::string &out_pa
     }
     if (err.empty()) err = log_err;
     if (err.empty()) trim_clip_report(ctx, opt, adapters, clip, err);
+    if (err.empty()) trim_dedup_report(ctx, opt, dedup, err);
     if (err.empty()) trim_qc_write(ctx, opt, outs.f.back(), qc, err);
     if (!err.empty() || outs.commit(err)) return 1;
     if (times) {
@@ -167,7 +184,7 @@ int trim_fastq(const std::vector<std::string> &inputs, const std::string &out_pa
 }
 
 int trim_fastq_pair(const std::string &in1, const std::string &in2, const std::string out_paths[4], const TrimOptions &opt, int device,
-                    pf_trim_stats stats[2], TrimTimes *times, std::string &err, ClipReport *clip, QcReport *qc) {
+                    pf_trim_stats stats[2], TrimTimes *times, std::string &err, ClipReport *clip, QcReport *qc, pf_dedup_stats *dedup) {
     stats[0] = stats[1] = pf_trim_stats{};
     err.clear();
     const bool logs = !opt.trimlog.empty();
@@ -182,7 +199,7 @@ int trim_fastq_pair(const std::string &in1, const std::string &in2, const std::s
     pf_ctx *ctx = nullptr;
     if (trim_create(device, &ctx, err)) return 1;
     CtxGuard ctx_guard{ctx};
-    if (trim_clip_open(ctx, opt, adapters, err) || trim_qc_open(ctx, opt, err)) return 1;
+    if (trim_clip_open(ctx, opt, adapters, err) || trim_qc_open(ctx, opt, err) || trim_dedup_open(ctx, opt, err)) return 1;
     const auto t_stream = clk::now();
     OutFiles outs("trim");
     if (outs.open_all(paths, err)) return 1;
@@ -262,6 +279,7 @@ int trim_fastq_pair(const std::string &in1, const std::string &in2, const std::s
     }
     for (int d = 0; d < 4 && err.empty(); ++d) err = opt.gz_out ? gzo[d]->wr.err : wr[d].err;
     if (err.empty()) trim_clip_report(ctx, opt, adapters, clip, err);
+    if (err.empty()) trim_dedup_report(ctx, opt, dedup, err);
     if (err.empty()) trim_qc_write(ctx, opt, outs.f.back(), qc, err);
     if (!err.empty() || outs.commit(err)) return 1;
     if (times) {

@@ -125,6 +125,7 @@ struct pf_ctx {
     void *count = nullptr; // K-COUNT (pf_count.hip): the table of an open count, pf_count_begin .. pf_count_finish / pf_count_abort
     void *clip = nullptr;  // K-CLIP (pf_clip.hip): the adapters and counters of an open clip, pf_clip_begin .. pf_clip_end
     void *qc = nullptr;    // K-QC (pf_qc.hip): the tables of an open report, pf_qc_begin .. pf_qc_end
+    void *dedup = nullptr; // K-DEDUP (pf_dedup.hip): the table and counters of an open dedup, pf_dedup_begin .. pf_dedup_end
     void *unitig = nullptr; // K-UNITIG (pf_unitig.hip): the text of a built graph, pf_unitig_build .. pf_unitig_release
     void *comm = nullptr;  // pf_gather.hip: this rank's RCCL communicator and its two small device buffers
     const void *cc_rec = nullptr;
@@ -230,6 +231,7 @@ void count_destroy(pf_ctx *ctx);    // pf_count.hip
 void unitig_destroy(pf_ctx *ctx);   // pf_unitig.hip
 void clip_destroy(pf_ctx *ctx);     // pf_clip.hip
 void qc_destroy(pf_ctx *ctx);       // pf_qc.hip
+void dedup_destroy(pf_ctx *ctx);    // pf_dedup.hip
 void call_invalidate(pf_ctx *ctx);  // graph or count table replaced
 int call_state_arrays(pf_ctx *ctx, uint8_t **flags, uint32_t **plus, uint32_t **minus);   // pf_call.hip: T1 state arrays for a device-side writer
 void call_state_resident(pf_ctx *ctx);
@@ -246,6 +248,7 @@ enum WsSlot {
     WS_TRIM_TEXT2, WS_TRIM_INDEX2, WS_TRIM_TABLE2, WS_TRIM_WORK, WS_TRIM_OUT,   // K-TRIM (pf_trim.hip): a pair's second file (text, index, table), intervals / sizes / offsets, the staged outputs
     WS_FASTA_WORK, WS_FASTA_LINES, WS_FASTA_TEXT, WS_FASTA_TABLE,   // K-FASTA (pf_fasta.hip): bitmaps, counts and sums per word; line and header starts; the compacted text; the read table
     WS_HETPAIR,     // K-HETPAIR (pf_hetpair.hip): staged keys and counters, pair words, offsets, partners, the scan's scratch
+    WS_DEDUP,       // K-DEDUP (pf_dedup.hip): the slot of every unit of a call; pf_dedup_keys' staged keys and flags
     WS_BUB_LANES,   // K-BUBBLE's five launch workspaces (small, retry, scratch, work, idx2) of lanes 1 .. PF_CALL_LANES - 1 (bub_ws)
     WS_COUNT_ = WS_BUB_LANES + 5 * (PF_CALL_LANES - 1)
 };

@@ -28,6 +28,7 @@
 #include "../../include/ploidyfrost_hip.h"
 #include "pf_clip_dev.hpp"
 #include "pf_ctx.hpp"
+#include "pf_dedup_dev.hpp"
 #include "pf_qc_dev.hpp"
 #include "pf_reads_dev.hpp"
 #include "pf_scan.hpp"
@@ -137,7 +138,7 @@ static int trim_core(pf_ctx *ctx, const char *who_c, int n_files, const char *co
     if (bad_record) *bad_record = 0;
     if (stats) for (int f = 0; f < n_files; ++f) stats[f] = pf_trim_stats{};
     clip_forget(ctx);
-    { const std::string why = trim_steps_refusal(steps, n_steps, phred, clip_is_open(ctx)); if (!why.empty()) return refuse(why); }
+    { const std::string why = trim_steps_refusal(steps, n_steps, phred, clip_is_open(ctx) || dedup_is_open(ctx)); if (!why.empty()) return refuse(why); }
     for (int f = 0; f < n_files; ++f) {
         if (n_bytes[f] && !text[f]) return refuse("text is needed");
         if (n_bytes[f] > 0xFFFFFF00ull) return refuse("a chunk holds fewer than 2^32 bytes (line starts are 32 bits)");
@@ -202,6 +203,11 @@ static int trim_core(pf_ctx *ctx, const char *who_c, int n_files, const char *co
     for (int f = 0; f < n_files; ++f)
         k_trim_intervals<<<ctx_grid(ctx, n * TRIM_ROW, TRIM_BLOCK, 8), TRIM_BLOCK, 0, ctx->stream>>>(dt[f], n_bytes[f], ix[f].lines, n, ts, d_begin[f],
                                                                                                      d_len[f], dc + f, d_clip[f]);
+    if (dedup_is_open(ctx)) {   // K-DEDUP: a later copy of a kept unit is dropped here, so stage `kept` of a report is what is written
+        const uint32_t *dd_lines[2] = {ix[0].lines, ix[1].lines};
+        const int rc = dedup_launch(ctx, n_files, dt, n_bytes, dd_lines, n, d_begin, d_len, dc);
+        if (rc) return rc;
+    }
     if (qc_is_open(ctx)) {   // K-QC: both stages from what is on the device now -- the index, the final intervals, the clip ends
         const uint32_t *qc_lines[2] = {ix[0].lines, ix[1].lines};
         const int rc = qc_launch(ctx, n_files, 0, dt, n_bytes, qc_lines, n, d_begin, d_len, clip ? d_clip : nullptr);
@@ -247,6 +253,7 @@ static int trim_core(pf_ctx *ctx, const char *who_c, int n_files, const char *co
     TrimCounts h[2] = {};
     PF_HIP(hipMemcpyAsync(h, dc, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
     PF_HIP(hipStreamSynchronize(ctx->stream));
+    dedup_settle(ctx);   // K-DEDUP's entries came back with the counters
     for (int d = 0; d < n_dest; ++d) {
         out_bytes[d] = base[d + 1] - base[d];
         if (!direct[d] && out_bytes[d]) PF_HIP(hipMemcpyAsync(out[d], ca.out[d], (size_t)out_bytes[d], hipMemcpyDefault, ctx->stream));

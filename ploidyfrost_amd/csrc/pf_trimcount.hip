@@ -32,6 +32,7 @@
 #include "pf_clip_dev.hpp"
 #include "pf_count_dev.hpp"
 #include "pf_ctx.hpp"
+#include "pf_dedup_dev.hpp"
 #include "pf_qc_dev.hpp"
 #include "pf_reads_dev.hpp"
 #include "pf_scan.hpp"
@@ -171,6 +172,11 @@ static int trim_table_core(pf_ctx *ctx, const std::string &who, int n_files, con
     for (int f = 0; f < n_files; ++f)
         k_trim_intervals<<<ctx_grid(ctx, n * TRIM_ROW, TRIM_BLOCK, 8), TRIM_BLOCK, 0, ctx->stream>>>(T.text[f], n_bytes[f], ix[f].lines, n, ts, d_begin[f],
                                                                                                      d_len[f], dc + f, d_clip[f]);
+    if (dedup_is_open(ctx)) {   // K-DEDUP: a later copy of a kept unit is dropped here, so stage `kept` of a report is what is handed on
+        const uint32_t *dd_lines[2] = {ix[0].lines, ix[1].lines};
+        const int rc = dedup_launch(ctx, n_files, T.text, n_bytes, dd_lines, n, d_begin, d_len, dc);
+        if (rc) return rc;
+    }
     if (qc_is_open(ctx)) {   // K-QC: both stages from what is on the device now -- the index, the final intervals, the clip ends
         const uint32_t *qc_lines[2] = {ix[0].lines, ix[1].lines};
         const int rc = qc_launch(ctx, n_files, 0, T.text, n_bytes, qc_lines, n, d_begin, d_len, clip ? d_clip : nullptr);
@@ -200,6 +206,7 @@ static int trim_table_core(pf_ctx *ctx, const std::string &who, int n_files, con
     PF_HIP(hipMemcpyAsync(&n_kept, d_pos + n, 4, hipMemcpyDeviceToHost, ctx->stream));
     PF_HIP(hipMemcpyAsync(h, dc, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
     PF_HIP(hipStreamSynchronize(ctx->stream));   // the one wait: the table's length
+    dedup_settle(ctx);   // K-DEDUP's entries came back with it
     for (int f = 0; f < n_files; ++f) {
         bytes_used[f] = T.used[f] = n < ix[f].n_rec ? (uint64_t)end32[f] : ix[f].used;
         T.off[f] = d_off[f];
@@ -231,7 +238,7 @@ static int trim_table_args(pf_ctx *ctx, const std::string &who, int n_files, con
     auto refuse = [&](const std::string &m) { pf::CtxErr{ctx} = who + ": " + m; return (int)PF_ERR_ARG; };
     if (!bytes_used) return refuse("bytes_used is needed");
     if (!plan) return refuse("a plan is needed");
-    { const std::string why = trim_steps_refusal(plan->steps, plan->n_steps, plan->phred, clip_is_open(ctx)); if (!why.empty()) return refuse(why); }
+    { const std::string why = trim_steps_refusal(plan->steps, plan->n_steps, plan->phred, clip_is_open(ctx) || dedup_is_open(ctx)); if (!why.empty()) return refuse(why); }
     for (int f = 0; f < n_files; ++f) {
         if (n_bytes[f] && !text[f]) return refuse("text is needed");
         if (n_bytes[f] > 0xFFFFFF00ull) return refuse("a chunk holds fewer than 2^32 bytes (line starts are 32 bits)");

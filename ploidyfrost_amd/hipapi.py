@@ -50,6 +50,8 @@ K_QC = K_PALIN + 1             # PF_K_QC ("k_qc"): the report kernel of one qc_f
 QC_TABLE_WORDS, QC_CLIP_WORDS = 9515, 1025   # PF_QC_TABLE_WORDS, PF_QC_CLIP_WORDS
 K_HETPAIR = K_QC + 1           # PF_K_HETPAIR ("k_hetpair"): everything one pf_hetpairs launches (flag, scan, write, table); unit: keys in range
 HETPAIR_STATS = np.dtype([(f, "<u8") for f in ("kmers", "in_range", "one_partner", "many_partners", "pairs")])   # pf_hetpair_stats
+K_DEDUP = K_HETPAIR + 1         # PF_K_DEDUP ("k_dedup"): the kernels of one trim / trimmed-count call while a dedup is open, or of one dedup_keys; unit: units that take part
+DEDUP_STATS = np.dtype([(f, "<u8") for f in ("units", "unique", "duplicates", "max_copies")] + [("levels", "<u8", (10,)), ("slots", "<u8"), ("growths", "<u8")])   # pf_dedup_stats
 HETPAIR_MAX_W = 4096           # pf_hetpair::MAX_W: upper - lower + 1 of a table
 CLIP_PAIR_STATS = np.dtype([("pairs_clipped", "<u8"), ("pairs_dropped", "<u8"), ("pairs_too_long", "<u8"), ("candidates_scored", "<u8"),
                             ("bases_clipped", "<u8", (2,))])   # pf_clip_pair_stats
@@ -299,6 +301,10 @@ def load_library() -> C.CDLL:
         "pf_qc_end": (i, [vp]),
         "pf_hetpairs": (i, [vp, vp, vp, u64, u32, u32, u32, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), vp]),
         "pf_hetpair_table": (i, [vp, vp, vp, u64, u32, u32, vp]),
+        "pf_dedup_begin": (i, [vp, u32, u64]),
+        "pf_dedup_stats_get": (i, [vp, vp]),
+        "pf_dedup_end": (i, [vp]),
+        "pf_dedup_keys": (i, [vp, vp, u64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError = header / library mismatch
@@ -332,7 +338,8 @@ DECLARED_SYMBOLS = ["pf_create", "pf_warmup", "pf_destroy", "pf_last_error", "pf
                     "pf_clip_begin", "pf_clip_stats_get", "pf_clip_end", "pf_clip_last_ends",
                     "pf_clip_begin_pairs", "pf_clip_pair_stats_get",
                     "pf_qc_begin", "pf_qc_get", "pf_qc_clip_get", "pf_qc_fastq", "pf_qc_end",
-                    "pf_hetpairs", "pf_hetpair_table"]
+                    "pf_hetpairs", "pf_hetpair_table",
+                    "pf_dedup_begin", "pf_dedup_stats_get", "pf_dedup_end", "pf_dedup_keys"]
 
 
 class TrimPlan(C.Structure):   # pf_trim_plan
@@ -807,6 +814,34 @@ class Device:
     def qc_end(self):
         """pf_qc_end: closes the report; the trim calls launch nothing more"""
         self._check(self.L.pf_qc_end(self.h))
+
+    def dedup_begin(self, bases: int = 0, initial_slots: int = 0):
+        """K-DEDUP (pf_dedup_begin): opens a dedup on the context -- until dedup_end() trim_fastq, trim_fastq_pair,
+        trim_table_fastq[_pair] and the *_trimmed count calls drop every kept unit whose key (the first `bases` bases of its raw
+        read(s), 0 = all; csrc/pf_dedup_rule.hpp) an earlier unit of the stream had, and take an empty list of steps.  initial_slots:
+        0 = default, rounded up to a power of two, at least 64.  Refusals raise DeviceError by name."""
+        self._check(self.L.pf_dedup_begin(self.h, int(bases), int(initial_slots)))
+
+    def dedup_stats(self) -> dict:
+        """pf_dedup_stats_get: units, unique, duplicates, max_copies, levels (a list of 10), slots, growths of the open dedup"""
+        st = np.zeros(1, dtype=DEDUP_STATS)
+        self._check(self.L.pf_dedup_stats_get(self.h, st.ctypes.data))
+        return {f: ([int(v) for v in st[0][f]] if f == "levels" else int(st[0][f])) for f in DEDUP_STATS.names}
+
+    def dedup_keys(self, keys, keep=None):
+        """pf_dedup_keys: the table by itself -- keys ([n, 2] u64: a numpy array or a device tensor) as the next n units, all taking
+        part; returns keep (u8 per key: 1 = not seen before), a numpy array, or the device tensor `keep` filled."""
+        if isinstance(keys, np.ndarray):
+            keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        n = int(keys.shape[0])
+        if keep is None:
+            keep = np.zeros(n, dtype=np.uint8)
+        self._check(self.L.pf_dedup_keys(self.h, _ptr(keys) if n else None, n, _ptr(keep) if n else None))
+        return keep
+
+    def dedup_end(self):
+        """pf_dedup_end: closes the dedup and frees its table; the trim calls are what they were without one"""
+        self._check(self.L.pf_dedup_end(self.h))
 
     def inflate_bgzf(self, comp, member_off, out=None, out_cap=None):
         """K-INFLATE (pf_inflate_bgzf): the BGZF members comp[member_off[m] : member_off[m + 1]] inflated one behind the other; returns

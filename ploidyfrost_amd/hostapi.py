@@ -55,7 +55,9 @@ DECLARED_SYMBOLS = ["pfh_open", "pfh_close", "pfh_last_error", "pfh_set_output_d
                     "pfh_trim_fastq_chunk_clip", "pfh_reads_adapter_pairs", "pfh_reads_adapters_pair_report", "pfh_clip_parse_adapter_pairs",
                     "pfh_clip_pair", "pfh_trim_fastq_pair_chunk_clip",
                     "pfh_reads_report", "pfh_qc_fastq", "pfh_qc_fastq_chunk", "pfh_qc_report_text", "pfh_qc_phred_hint",
-                    "pfh_hetpairs_host", "pfh_smudge_report_text", "pfh_smudge_of", "pfh_smudge", "pfh_reads_smudge", "pfh_reads_smudge_result"]
+                    "pfh_hetpairs_host", "pfh_smudge_report_text", "pfh_smudge_of", "pfh_smudge", "pfh_reads_smudge", "pfh_reads_smudge_result",
+                    "pfh_reads_dedup", "pfh_reads_dedup_report", "pfh_dedup_key", "pfh_dedup_units", "pfh_trim_fastq_chunk_dedup",
+                    "pfh_trim_fastq_pair_chunk_dedup"]
 
 
 class RunOptions(C.Structure):   # pfh_run_options (include/ploidyfrost_host.h)
@@ -281,6 +283,22 @@ def load_library() -> C.CDLL:
     L.pfh_clip_parse_adapters.restype = C.c_int
     L.pfh_clip_parse_adapters.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                           C.POINTER(C.c_uint64)]
+    L.pfh_reads_dedup.restype = None
+    L.pfh_reads_dedup.argtypes = [C.c_int, C.c_uint32, C.c_uint64]
+    L.pfh_reads_dedup_report.restype = None
+    L.pfh_reads_dedup_report.argtypes = [C.c_void_p]
+    L.pfh_dedup_key.restype = C.c_int
+    L.pfh_dedup_key.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_uint32, C.c_void_p]
+    L.pfh_dedup_units.restype = C.c_int
+    L.pfh_dedup_units.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    L.pfh_trim_fastq_chunk_dedup.restype = C.c_int
+    L.pfh_trim_fastq_chunk_dedup.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
+                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                             C.c_void_p, C.POINTER(C.c_uint64)]
+    L.pfh_trim_fastq_pair_chunk_dedup.restype = C.c_int
+    L.pfh_trim_fastq_pair_chunk_dedup.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                  C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                  C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_uint64)]
     L.pfh_reads_report.restype = None
     L.pfh_reads_report.argtypes = [C.c_char_p]
     L.pfh_qc_fastq.restype = C.c_int
@@ -1115,8 +1133,104 @@ def smudge_result() -> dict:
     return _smudge_result(res)
 
 
+DEDUP_STATS_FIELDS = ("units", "unique", "duplicates", "max_copies", "levels", "slots", "growths")   # pf_dedup_stats (levels: 10 words)
+DEDUP_STATS = hipapi.DEDUP_STATS
+
+
+def _dedup_dict(st) -> dict:
+    return {f: ([int(v) for v in st[0][f]] if f == "levels" else int(st[0][f])) for f in DEDUP_STATS_FIELDS}
+
+
+def _set_dedup(L, dedup, dedup_bases, dedup_initial_slots):
+    """`--dedup [--dedup-bases N] [--dedup-initial-slots N]` of the next trim / run call (pfh_reads_dedup); the values without the switch
+    are refused by name here, as the command line refuses them"""
+    if not dedup and dedup_bases:
+        raise RuntimeError("--dedup-bases needs --dedup: the bases are read by the duplicate removal alone")
+    if not dedup and dedup_initial_slots:
+        raise RuntimeError("--dedup-initial-slots needs --dedup: the table is the duplicate removal's alone")
+    L.pfh_reads_dedup(int(bool(dedup)), int(dedup_bases), int(dedup_initial_slots))
+
+
+def dedup_report() -> dict:
+    """What the last trim / run call of this thread that ran with dedup=True found (pfh_reads_dedup_report), summed over its units"""
+    st = np.zeros(1, dtype=DEDUP_STATS)
+    load_library().pfh_reads_dedup_report(st.ctypes.data)
+    return _dedup_dict(st)
+
+
+def dedup_key(seq1, seq2=None, bases: int = 0):
+    """The 128-bit key of one unit as K-DEDUP defines it (pfh_dedup_key, csrc/pf_dedup_rule.hpp; no device): (h1, h2) of the read seq1, or
+    of the pair (seq1, seq2); bases: 0 = the whole read, else the first 16 .. 4096 bases.  A refusal raises RuntimeError by name."""
+    L = load_library()
+    key = np.zeros(2, dtype=np.uint64)
+    s1 = bytes(seq1)
+    s2 = None if seq2 is None else bytes(seq2)
+    if L.pfh_dedup_key(s1, len(s1), s2, 0 if s2 is None else len(s2), int(bases), key.ctypes.data):
+        raise RuntimeError(L.pfh_last_error(None).decode())
+    return int(key[0]), int(key[1])
+
+
+def dedup_units(keys, participates=None):
+    """The decision of K-DEDUP over the keys ([n, 2] u64) of the units of a whole stream in order (pfh_dedup_units; no device):
+    (keep, stats) -- keep[i] = 1 for the first unit of its key and for a unit that takes no part (participates[i] == 0), 0 for a later
+    copy; stats: DEDUP_STATS_FIELDS (slots and growths 0)."""
+    L = load_library()
+    keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, 2)
+    n = len(keys)
+    part = None if participates is None else np.ascontiguousarray(participates, dtype=np.uint8)
+    keep = np.zeros(n, dtype=np.uint8)
+    st = np.zeros(1, dtype=DEDUP_STATS)
+    if L.pfh_dedup_units(keys.ctypes.data if n else None, None if part is None else part.ctypes.data, n, keep.ctypes.data if n else None, st.ctypes.data):
+        raise RuntimeError(L.pfh_last_error(None).decode())
+    return keep, _dedup_dict(st)
+
+
+def trim_fastq_chunk_dedup(text, steps, phred: int = 33, final: bool = True, bases: int = 0, seen_keys=None, text2=None):
+    """What Device.trim_fastq (text2 None) / Device.trim_fastq_pair give for one chunk while a dedup is open and no clip, restated on the
+    host (pfh_trim_fastq[_pair]_chunk_dedup; no device).  seen_keys: [m, 2] u64, the keys of the units that took part before.  Returns a
+    dict: clause, bad_record, n_records, keys ([n_records, 2]; 0 0 = takes no part), and per file (single-ended: the values
+    themselves; a pair: lists of two) out / outs (o1 u1 o2 u2), bytes_used, begin, len, stats."""
+    L = load_library()
+    st = trim_parse_steps(steps) if len(steps) else np.zeros(0, dtype=TRIM_STEP)
+    seen = np.zeros((0, 2), dtype=np.uint64) if seen_keys is None else np.ascontiguousarray(seen_keys, dtype=np.uint64).reshape(-1, 2)
+    texts = [bytes(text)] + ([] if text2 is None else [bytes(text2)])
+    nf = len(texts)
+    cap = max(len(t) for t in texts) // 4 + 1
+    outs = [np.zeros(len(texts[d // 2 if nf == 2 else 0]) + 1, dtype=np.uint8) for d in range(4 if nf == 2 else 1)]
+    begin = [np.zeros(cap, dtype=np.uint32) for _ in range(nf)]
+    ln = [np.zeros(cap, dtype=np.uint32) for _ in range(nf)]
+    keys = np.zeros((cap, 2), dtype=np.uint64)
+    stats = np.zeros((nf, len(TRIM_STATS_FIELDS)), dtype=np.uint64)
+    out_n = (C.c_uint64 * 4)()
+    used = (C.c_uint64 * 2)()
+    recs, bad = C.c_uint64(), C.c_uint64()
+    if nf == 1:
+        clause = L.pfh_trim_fastq_chunk_dedup(texts[0], len(texts[0]), int(final), st.ctypes.data if len(st) else None, len(st), int(phred), int(bases),
+                                              seen.ctypes.data if len(seen) else None, len(seen), outs[0].ctypes.data, out_n, used, begin[0].ctypes.data,
+                                              ln[0].ctypes.data, keys.ctypes.data, cap, C.byref(recs), stats.ctypes.data, C.byref(bad))
+    else:
+        p_out = (C.c_void_p * 4)(*[o.ctypes.data for o in outs])
+        p_b = (C.c_void_p * 2)(*[a.ctypes.data for a in begin])
+        p_l = (C.c_void_p * 2)(*[a.ctypes.data for a in ln])
+        clause = L.pfh_trim_fastq_pair_chunk_dedup(texts[0], len(texts[0]), texts[1], len(texts[1]), int(final), st.ctypes.data if len(st) else None, len(st),
+                                                   int(phred), int(bases), seen.ctypes.data if len(seen) else None, len(seen), p_out, out_n, used, p_b, p_l,
+                                                   keys.ctypes.data, cap, C.byref(recs), stats.ctypes.data, C.byref(bad))
+    if clause < 0:
+        raise RuntimeError(L.pfh_last_error(None).decode())
+    n = recs.value
+    res = dict(clause=clause, bad_record=bad.value, n_records=n, keys=keys[:n].copy())
+    sts = [{f: int(v) for f, v in zip(TRIM_STATS_FIELDS, row)} for row in stats]
+    if nf == 1:
+        res.update(out=outs[0][: out_n[0]].tobytes(), bytes_used=used[0], begin=begin[0][:n], len=ln[0][:n], stats=sts[0])
+    else:
+        res.update(outs=[outs[d][: out_n[d]].tobytes() for d in range(4)], bytes_used=[used[0], used[1]], begin=[b[:n] for b in begin],
+                   len=[a[:n] for a in ln], stats=sts)
+    return res
+
+
 def trim_fastq(inputs, out: str, steps, phred: int = 33, trimlog=None, chunk_bytes: int = 0, gz: bool = False, gz_out: bool = False,
-               adapters=None, adapter_seed: int = 2, adapter_score: int = 10, report=None) -> dict:
+               adapters=None, adapter_seed: int = 2, adapter_score: int = 10, report=None, dedup: bool = False, dedup_bases: int = 0,
+               dedup_initial_slots: int = 0) -> dict:
     """`ploidyfrost trim -i ... -o out STEP...` (pfh_trim_fastq): the reads of the FASTQ file(s) `inputs`, one after the other,
     quality-trimmed by `steps` (Trimmomatic's words) into `out`; trimlog: a file with one line per record.  Returns the statistics.  A
     refusal raises RuntimeError (format refusals with the input's path and the 1-based record number); nothing is left under any
@@ -1124,47 +1238,60 @@ def trim_fastq(inputs, out: str, steps, phred: int = 33, trimlog=None, chunk_byt
     adapters (`--adapters`): the path of an adapter file -- adapter read-through is clipped on the device before the steps (K-CLIP;
     adapter_seed, adapter_score: `--adapter-seed`, `--adapter-score`); steps may then be empty; clip_report() gives the `clip:` line.
     report (`--report`): a path for the read quality report of the reads as they come (raw) and as they are written (kept) (K-QC); every
-    other output is what it is without."""
+    other output is what it is without.
+    dedup (`--dedup`, with dedup_bases and dedup_initial_slots): every later copy of a kept read is dropped on the device (K-DEDUP; one
+    table over all inputs); steps may then be empty, and the returned dict gains "dedup" (DEDUP_STATS_FIELDS)."""
     L = load_library()
     if isinstance(inputs, (str, bytes, os.PathLike)):
         inputs = [inputs]
-    st = trim_parse_steps(steps) if len(steps) or adapters is None else np.zeros(0, dtype=TRIM_STEP)
+    st = trim_parse_steps(steps) if len(steps) or (adapters is None and not dedup) else np.zeros(0, dtype=TRIM_STEP)
     paths = (C.c_char_p * max(len(inputs), 1))(*[os.fsencode(p) for p in inputs])
     stats = np.zeros(len(TRIM_STATS_FIELDS), dtype=np.uint64)
     L.pfh_reads_gz(_gz_mode(gz))
     L.pfh_reads_gz_out(int(gz_out))
+    _set_dedup(L, dedup, dedup_bases, dedup_initial_slots)
     _set_adapters(L, adapters, adapter_seed, adapter_score)
     _set_report(L, report)
     rc = L.pfh_trim_fastq(paths, len(inputs), os.fsencode(out), st.ctypes.data if len(st) else None, len(st), phred,
                           os.fsencode(trimlog) if trimlog else None, int(chunk_bytes), 0, stats.ctypes.data)
     if rc:
         raise (ReadsRefused if gz else RuntimeError)(L.pfh_last_error(None).decode())
-    return {f: int(v) for f, v in zip(TRIM_STATS_FIELDS, stats)}
+    res = {f: int(v) for f, v in zip(TRIM_STATS_FIELDS, stats)}
+    if dedup:
+        res["dedup"] = dedup_report()
+    return res
 
 
 def trim_fastq_pair(in1: str, in2: str, outs, steps, phred: int = 33, trimlog=None, chunk_bytes: int = 0, gz: bool = False, gz_out: bool = False,
                     adapters=None, adapter_seed: int = 2, adapter_score: int = 10, adapter_pairs: bool = False, adapter_pair_score: int = 30,
-                    adapter_pair_min: int = 8, adapter_keep_both: bool = False, report=None):
+                    adapter_pair_min: int = 8, adapter_keep_both: bool = False, report=None, dedup: bool = False, dedup_bases: int = 0,
+                    dedup_initial_slots: int = 0):
     """`ploidyfrost trim -1 in1 -2 in2 -o1 .. -u1 .. -o2 .. -u2 .. STEP...` (pfh_trim_fastq_pair): outs = (o1, u1, o2, u2).  Returns the
     statistics of file 1 and of file 2 (the pair fields are the same in both).  gz_out (`--gz-out`): the four outputs are blocked gzip.
     adapters, adapter_seed, adapter_score: as trim_fastq takes them (names ending in /1 and /2 choose the file).
     adapter_pairs (`--adapter-pairs`, with adapter_pair_score, adapter_pair_min, adapter_keep_both): palindrome mode from the file's
     prefix pairs beside simple mode (K-PALIN); clip_pair_report() gives the tail of the `clip:` line.
-    report (`--report`): as trim_fastq takes it; file 1 is side 1 of the report, file 2 side 2."""
+    report (`--report`): as trim_fastq takes it; file 1 is side 1 of the report, file 2 side 2.
+    dedup, dedup_bases, dedup_initial_slots: as trim_fastq takes them; the unit is the pair, and both dicts gain "dedup"."""
     L = load_library()
-    st = trim_parse_steps(steps) if len(steps) or adapters is None else np.zeros(0, dtype=TRIM_STEP)
+    st = trim_parse_steps(steps) if len(steps) or (adapters is None and not dedup) else np.zeros(0, dtype=TRIM_STEP)
     assert len(outs) == 4
     paths = (C.c_char_p * 4)(*[os.fsencode(p) for p in outs])
     stats = np.zeros((2, len(TRIM_STATS_FIELDS)), dtype=np.uint64)
     L.pfh_reads_gz(_gz_mode(gz))
     L.pfh_reads_gz_out(int(gz_out))
+    _set_dedup(L, dedup, dedup_bases, dedup_initial_slots)
     _set_adapters(L, adapters, adapter_seed, adapter_score, adapter_pairs, adapter_pair_score, adapter_pair_min, adapter_keep_both)
     _set_report(L, report)
     rc = L.pfh_trim_fastq_pair(os.fsencode(in1), os.fsencode(in2), paths, st.ctypes.data if len(st) else None, len(st), phred,
                                os.fsencode(trimlog) if trimlog else None, int(chunk_bytes), 0, stats.ctypes.data)
     if rc:
         raise (ReadsRefused if gz else RuntimeError)(L.pfh_last_error(None).decode())
-    return [{f: int(v) for f, v in zip(TRIM_STATS_FIELDS, row)} for row in stats]
+    res = [{f: int(v) for f, v in zip(TRIM_STATS_FIELDS, row)} for row in stats]
+    if dedup:
+        for r in res:
+            r["dedup"] = dedup_report()
+    return res
 
 
 COUNT_STATS_FIELDS = ("reads", "bases", "kmers", "kmers_bad", "unique", "below_min", "above_max", "written")   # pf_count_stats
@@ -1308,7 +1435,7 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
               initial_slots: int = 0, steps=None, phred: int = 33, pairs=None, gz: bool = False, fasta: bool = False,
               adapters=None, adapter_seed: int = 2, adapter_score: int = 10, adapter_pairs: bool = False, adapter_pair_score: int = 30,
               adapter_pair_min: int = 8, adapter_keep_both: bool = False, report=None, smudge: bool = False, smudge_n=None,
-              smudge_pairs=None) -> dict:
+              smudge_pairs=None, dedup: bool = False, dedup_bases: int = 0, dedup_initial_slots: int = 0) -> dict:
     """`ploidyfrost run` (pfh_run_fastq): reads to ploidy estimate in one process -- the FASTQ file(s) `inputs` counted, the thresholds
     derived, the k-mers of the masked reads counted (K-MASKCOUNT), the graph built and the single-sample calling run made on one device
     context; PloidyFrost_output/<out_prefix>_*.txt in the working directory.  model: None, "cov" or "fre".  Returns the fields of the
@@ -1327,13 +1454,15 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
     report (`--report`): the report `trim_fastq(..., report=)` writes for the same inputs, taken over the first pass; refused by name
     without steps or adapters.
     smudge (`--smudge`, with smudge_n and smudge_pairs): the k-mer pair report PloidyFrost_output/<out_prefix>_smudge.tsv from the table
-    of the first pass (K-HETPAIR), every other output being what it is without; the result then has "smudge" (smudge_result())."""
+    of the first pass (K-HETPAIR), every other output being what it is without; the result then has "smudge" (smudge_result()).
+    dedup (`--dedup`, with dedup_bases and dedup_initial_slots): as trim_fastq takes them -- one table per unit in both passes (all
+    inputs together, each pair on its own); it turns the trimming on as steps do, and the result gains "dedup" (summed over the units)."""
     L = load_library()
     if pairs is not None:
         if inputs is not None:
             raise ValueError("run_reads: either inputs or pairs")
         inputs = [f for p in pairs for f in p]
-    st = trim_parse_steps(steps) if steps is not None and (len(steps) or adapters is None) else np.zeros(0, dtype=TRIM_STEP)   # (adapters alone: no step)
+    st = trim_parse_steps(steps) if steps is not None and (len(steps) or (adapters is None and not dedup)) else np.zeros(0, dtype=TRIM_STEP)   # (adapters or dedup alone: no step)
     paths, n = _paths(inputs)
     o = RunOptions()
     L.pfh_run_defaults(C.byref(o))
@@ -1352,7 +1481,9 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
     o.db_out = None if db_out is None else os.fsencode(db_out)
     o.gfa_out = None if gfa_out is None else os.fsencode(gfa_out)
     stats = np.zeros(len(RUN_STATS_FIELDS), dtype=np.uint64)
-    if steps is None and pairs is None and adapters is None:
+    if not dedup:
+        _set_dedup(L, False, dedup_bases, dedup_initial_slots)   # (the values without the switch are refused)
+    if steps is None and pairs is None and adapters is None and not dedup:
         L.pfh_reads_gz(_gz_mode(gz))
         L.pfh_reads_fasta(int(bool(fasta)))
         _set_report(L, report)
@@ -1370,6 +1501,7 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
     _set_adapters(L, adapters, adapter_seed, adapter_score, adapter_pairs, adapter_pair_score, adapter_pair_min, adapter_keep_both)
     _set_report(L, report)
     _set_smudge(L, smudge, smudge_n, smudge_pairs)
+    _set_dedup(L, dedup, dedup_bases, dedup_initial_slots)
     rc = L.pfh_run_fastq_trimmed(paths, n, int(pairs is not None), st.ctypes.data if len(st) else None, len(st), int(phred), os.fsencode(out_prefix),
                                  C.byref(o), 0, stats.ctypes.data, per.ctypes.data)
     if rc:
@@ -1379,6 +1511,8 @@ def run_reads(inputs, out_prefix: str, k: int = 25, ci: int = 1, cx: int = 10 **
     out["trim"] = [rows[0]] if pairs is None else [[rows[2 * u], rows[2 * u + 1]] for u in range(len(pairs))]
     if smudge:
         out["smudge"] = smudge_result()
+    if dedup:
+        out["dedup"] = dedup_report()
     return out
 
 
@@ -1387,7 +1521,8 @@ def run_multi_reads(samples, out_prefix: str, k: int = 25, ci: int = 1, cx: int 
                     threads: int = 1, model=None, model_only: bool = False, filter_multi=None, each_color: bool = False, db_out=None, gfa_out=None,
                     chunk_bytes: int = 0, initial_slots: int = 0, steps=None, phred: int = 33, pairs=None, gz: bool = False,
                     fasta: bool = False, adapters=None, adapter_seed: int = 2, adapter_score: int = 10, adapter_pairs: bool = False,
-                    adapter_pair_score: int = 30, adapter_pair_min: int = 8, adapter_keep_both: bool = False) -> dict:
+                    adapter_pair_score: int = 30, adapter_pair_min: int = 8, adapter_keep_both: bool = False, dedup: bool = False,
+                    dedup_bases: int = 0, dedup_initial_slots: int = 0) -> dict:
     """`ploidyfrost run-multi` (pfh_run_multi_fastq): reads of several samples to one estimate per sample in one process.  samples: a
     list of (name, file or list of files), a sample a colour in the order given.  Every sample is counted and its thresholds derived,
     the k-mers of its masked reads counted (K-MASKCOUNT), their union taken (K-UNION), the coloured graph built and coloured per
@@ -1400,7 +1535,8 @@ def run_multi_reads(samples, out_prefix: str, k: int = 25, ci: int = 1, cx: int 
     its units, as run_reads gives them.
     fasta (`--fasta`): as run_reads takes it; the files of a sample may mix FASTA and FASTQ.
     adapters, adapter_seed, adapter_score: as run_reads takes them; they hold for every sample.
-    adapter_pairs, adapter_pair_score, adapter_pair_min, adapter_keep_both: as run_reads takes them; every sample is then a pair sample."""
+    adapter_pairs, adapter_pair_score, adapter_pair_min, adapter_keep_both: as run_reads takes them; every sample is then a pair sample.
+    dedup, dedup_bases, dedup_initial_slots: as run_reads takes them, per sample; the result gains "dedup" (summed over all units)."""
     L = load_library()
     names, counts, flat, paired = [], [], [], []
     for name, files in samples:
@@ -1410,7 +1546,7 @@ def run_multi_reads(samples, out_prefix: str, k: int = 25, ci: int = 1, cx: int 
         counts.append(len(files))
         flat.extend(files)
         paired.append(int(pairs is not None and name in pairs))
-    st = trim_parse_steps(steps) if steps is not None and (len(steps) or adapters is None) else np.zeros(0, dtype=TRIM_STEP)   # (adapters alone: no step)
+    st = trim_parse_steps(steps) if steps is not None and (len(steps) or (adapters is None and not dedup)) else np.zeros(0, dtype=TRIM_STEP)   # (adapters or dedup alone: no step)
     c_names = (C.c_char_p * max(len(names), 1))(*names)
     n_of = np.ascontiguousarray(counts, dtype=np.uint32)
     paths, _ = _paths(flat)
@@ -1436,7 +1572,8 @@ def run_multi_reads(samples, out_prefix: str, k: int = 25, ci: int = 1, cx: int 
     o.gfa_out = None if gfa_out is None else os.fsencode(gfa_out)
     stats = np.zeros(len(RUN_MULTI_STATS_FIELDS), dtype=np.uint64)
     per = np.zeros((max(len(names), 1), len(RUN_MULTI_COLOR_FIELDS)), dtype=np.uint64)
-    trimmed = steps is not None or pairs is not None or adapters is not None
+    trimmed = steps is not None or pairs is not None or adapters is not None or bool(dedup)
+    _set_dedup(L, dedup, dedup_bases, dedup_initial_slots)
     per_in = np.zeros((max(len(flat), 1), len(TRIM_STATS_FIELDS)), dtype=np.uint64)
     if trimmed:
         pair_of = np.ascontiguousarray(paired, dtype=np.int32)
@@ -1462,6 +1599,8 @@ def run_multi_reads(samples, out_prefix: str, k: int = 25, ci: int = 1, cx: int 
         for c in range(len(names)):
             out["trim"].append([[rows[at + 2 * u], rows[at + 2 * u + 1]] for u in range(counts[c] // 2)] if paired[c] else [rows[at]])
             at += counts[c]
+    if dedup:
+        out["dedup"] = dedup_report()
     return out
 
 
